@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the regrid apply path (BASELINE.json metric: regridded cells/s).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
-One "step" = one pass of the hot path over the whole batch of the workload.
+One "step" = one pass of the hot path over the whole batch of the workload.  A plain run does what the headline
+needs and nothing else: set up, W warm-up steps, K timed steps, the outputs of the last step written to DIR
+(--dump-outputs; the inputs are seeded, so two builds compare output for output), the line.  Everything else
+described below -- `roofline`, the spot checks against the CPU oracle, `cpu_baseline`, the secondary workloads,
+the user-visible paths, `baseline_configs` and the `with_gather` loop at N > 1 -- runs with --full only.
 Default workload = config 2 of BASELINE.json (the configuration the metric is
 quoted on): r1440x721 -> r360x180 bilinear, 3600 time steps, f64, X and Y
 resident in HBM.  Other workloads (--workload, see WORKLOADS): cfg3 / cfg3c / cfg3sb (masked ocean
@@ -26,7 +30,7 @@ gather is the library's own RCCL communicator (--comm native, default: no torch 
 torch.distributed (--comm torch).  `n_gpus` is the number of ranks that really joined.
 
 Rank 0 prints TWO stdout lines.  The LAST one is the compact JSON line (< 4 kB, every string < 100 characters):
-the driver's contract plus `roofline` (HBM bound; algorithmic bytes of SURVEY 8d over the live HIP-event kernel time;
+the driver's contract plus, with --full, `roofline` (HBM bound; algorithmic bytes of SURVEY 8d over the live HIP-event kernel time;
 `roofline.layouts` = config 2 in the native and the batch-fastest layout, `roofline.configs` = the secondary
 workloads' fractions and traffic ratios), `cpu_baseline` (the CPU oracle -- a port of the reference's step sequence --
 timed on this host's cores over a bounded sample of the same workload) and `baseline_configs` (one rank's share of
@@ -108,13 +112,22 @@ def parse_args():
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU, no kernel: a stand-in step exercises launcher, rendezvous, barriers, "
                          "max over ranks and the JSON line (CPU tests of the N>1 path)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline and copy-rate figures, the bit-equality spot checks "
+                         "against the CPU oracle, the CPU baseline, the secondary workloads, the user-visible paths, "
+                         "BASELINE configs 4 / 5 and at N > 1 the compute + gather loop. Without it a run sets up, "
+                         "warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's Y) as DIR/y.npy: "
+                         "Y as (rows, last axis), a fixed seeded sample of rows (indices in DIR/y_rows.npy) when larger "
+                         "than 48 MB")
     ap.add_argument("--others", default="default",
-                    help="secondary workloads timed after the headline at N=1 (comma list, 'default' or 'none')")
+                    help="--full: secondary workloads timed after the headline at N=1 (comma list, 'default' or 'none')")
     ap.add_argument("--others-steps", type=int, default=20)
     ap.add_argument("--others-budget", type=float, default=240.0,
                     help="seconds after which remaining secondary workloads are skipped")
     ap.add_argument("--configs", default="default",
-                    help="BASELINE configs run after the headline on the same ranks, each rank its share of the "
+                    help="--full: BASELINE configs run after the headline on the same ranks, each rank its share of the "
                          "fixed total batch (comma list, 'default' = cfg4,cfg5, 'none')")
     ap.add_argument("--config-steps", type=int, default=10)
     ap.add_argument("--config-warmup", type=int, default=2)
@@ -122,13 +135,13 @@ def parse_args():
                     help="steps of the compute + gather loop of a BASELINE config (config 4 moves 110 GB per rank and step)")
     ap.add_argument("--config-batch", type=int, default=0, help="override the rows per GPU of --configs (tests)")
     ap.add_argument("--user-path", default="default", choices=["default", "none"],
-                    help="N = 1: also time the user-visible paths host to host (tools/user_path_bench.py): smm_apply_host on "
+                    help="--full, N = 1: also time the user-visible paths host to host (tools/user_path_bench.py): smm_apply_host on "
                          "config-2 rows (block `host_to_host`) and Regridder.regrid on the reference's own fields with the CPU "
                          "oracle beside them (block `reference_sized`)")
     ap.add_argument("--host-rows", type=int, default=512, help="batch rows of the host_to_host block")
     ap.add_argument("--host-level-steps", type=int, default=40,
                     help="time steps of the config-3 field held in host memory (75 levels each; 40 = 35 GB; packing needs >= 32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"),
                     help="PMC-derived HBM bytes per launch (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
@@ -1017,6 +1030,42 @@ def gather_phase(args, runner, prob, y, flags, comm, world, n_ranks, steps, warm
     return res
 
 
+DUMP_BUDGET_BYTES = 48 << 20    # --dump-outputs writes at most this much
+DUMP_SEED = 20260723
+
+
+def dump_outputs(dirname, y):
+    """--dump-outputs: what the last timed step left in Y (a DeviceArray, or the dry run's ndarray) as DIR/y.npy in its
+    own dtype (f64, or f32 for the opt-in store), viewed as (rows, last axis).  Larger than DUMP_BUDGET_BYTES: a fixed seeded
+    sample of rows (and of columns when one row alone exceeds it), the same for the same arguments; the indices go to
+    DIR/y_rows.npy (and DIR/y_cols.npy) so that two runs compare cell for cell."""
+    os.makedirs(dirname, exist_ok=True)
+    n_cols = int(y.shape[-1])
+    n_rows = int(np.prod(y.shape[:-1], dtype=np.int64))
+    itemsize = np.dtype(y.dtype).itemsize
+    rng = np.random.default_rng(DUMP_SEED)
+    # a sampled row costs its values and its f64 index; a sampled column likewise
+    k = int(max(1, min(n_rows, DUMP_BUDGET_BYTES // (n_cols * itemsize + 8))))
+    rows = np.arange(n_rows) if k == n_rows else np.sort(rng.choice(n_rows, size=k, replace=False))
+    cols = None
+    if n_cols * itemsize > DUMP_BUDGET_BYTES:
+        cols = np.sort(rng.choice(n_cols, size=DUMP_BUDGET_BYTES // (itemsize + 8), replace=False))
+    y2 = y.reshape(n_rows, n_cols)
+    sample = np.empty((k, n_cols if cols is None else cols.size), dtype=y.dtype)
+    row = np.empty((1, n_cols), dtype=y.dtype)
+    for i, r in enumerate(rows):
+        if isinstance(y2, np.ndarray):
+            row[0] = y2[r]
+        else:
+            y2.rows(r, r + 1).to_host(out=row)
+        sample[i] = row[0] if cols is None else row[0, cols]
+    np.save(os.path.join(dirname, "y.npy"), sample)
+    if k < n_rows:
+        np.save(os.path.join(dirname, "y_rows.npy"), rows.astype(np.float64))
+    if cols is not None:
+        np.save(os.path.join(dirname, "y_cols.npy"), cols.astype(np.float64))
+
+
 def compact(obj, digits=6):
     """Nested blocks of the final line: floats to `digits` significant digits (the line stays small)."""
     if isinstance(obj, float):
@@ -1311,11 +1360,13 @@ def main():
 
     # the measured job: every rank regrids its shard, Y shards stay resident on their GPUs
     elapsed, kernel_ms = runner.timed(prob, y, flags, args.steps, args.warmup)
-    k_mine, k_ranks = runner.kernel_ms_over_ranks(kernel_ms)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y)
+    if args.full:
+        k_mine, k_ranks = runner.kernel_ms_over_ranks(kernel_ms)
 
     out, details = None, {}
     if rank == 0:
-        k_avg = k_mine * 1e-3
         cfg = {"workload": prob.desc, "kernel": args.kernel, "gather": args.gather if use_dist else "n/a",
                "comm": args.comm if use_dist else "n/a", "device": dev_name,
                "launched_by": "bench.py" if os.environ.get("LOCAL_WORLD_SIZE") and "TORCHELASTIC_RUN_ID" not in os.environ
@@ -1343,6 +1394,8 @@ def main():
             "data": "synthetic",
             "config": cfg,
         }
+    if rank == 0 and args.full:
+        k_avg = k_mine * 1e-3
         if args.dry_run:
             out["roofline"] = {"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
                                "traffic": None, "kernel_ms": k_avg * 1e3, "dry_run": True}
@@ -1371,7 +1424,7 @@ def main():
 
     # Everything that involves RCCL runs under a watchdog: the compute measurement above stands whatever
     # happens below; a phase that does not finish in time costs its own figures and a non-zero exit status.
-    gather_wanted = use_dist and args.gather == "root"
+    gather_wanted = use_dist and args.gather == "root" and args.full
     done = threading.Event()
 
     def give_up():
@@ -1436,7 +1489,7 @@ def main():
             if rank == 0:
                 out["with_gather"] = {"error": short(repr(exc), 200)}
 
-    if rank == 0 and world == 1 and not args.dry_run:
+    if args.full and rank == 0 and world == 1 and not args.dry_run:
         if not args.no_cpu_baseline:                 # CPU baseline: rank 0 at N = 1 only
             cpu = prob.cpu_baseline(args.cpu_seconds)
             details["cpu_baseline_legs"] = cpu.get("legs")
@@ -1445,7 +1498,7 @@ def main():
         y.free()
     if hasattr(prob, "free"):
         prob.free()
-    if rank == 0 and world == 1 and not args.dry_run and args.user_path != "none" and args.workload == "cfg2" \
+    if args.full and rank == 0 and world == 1 and not args.dry_run and args.user_path != "none" and args.workload == "cfg2" \
             and args.batch is None:
         # the path a user of the drop-in sees: host buffers in, host buffers out (PCIe-inclusive; never `value`)
         from tools.user_path_bench import host_to_host, reference_sized
@@ -1458,7 +1511,7 @@ def main():
             except Exception as exc:       # must not lose the headline
                 details[key] = {"error": short(repr(exc), 90)}
             details.setdefault("user_path_seconds", {})[key] = round(time.perf_counter() - t0, 1)
-    if rank == 0 and world == 1 and not args.dry_run:
+    if args.full and rank == 0 and world == 1 and not args.dry_run:
         names = OTHERS_DEFAULT if args.others == "default" else [n for n in args.others.split(",") if n and n != "none"]
         if names and args.workload == "cfg2" and args.batch is None:
             unknown = [n for n in names if n not in WORKLOADS]
@@ -1467,8 +1520,8 @@ def main():
             details["others"] = run_others(args, names, local_rank, flags, t_start)
 
     # BASELINE configs 4 and 5 on the same ranks (each rank its share of the fixed total batch)
-    names = [] if args.configs == "none" else (BASELINE_CONFIGS if args.configs == "default" else
-                                               [n for n in args.configs.split(",") if n])
+    names = [] if args.configs == "none" or not args.full else (BASELINE_CONFIGS if args.configs == "default" else
+                                                                [n for n in args.configs.split(",") if n])
     if names and args.workload == "cfg2" and args.batch is None:
         unknown = [n for n in names if n not in WORKLOADS or WORKLOADS[n][0] == "con3d"]
         if unknown:

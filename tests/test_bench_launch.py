@@ -39,7 +39,7 @@ def test_gpus_n_starts_n_ranks(n):
 
 def test_gather_phase_on_two_gloo_ranks():
     out = run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1", "--comm", "torch",
-               "--gather-tiles", "5"])
+               "--gather-tiles", "5", "--full"])
     assert out.returncode == 0, out.stderr[-2000:]
     line = json_line(out)
     g = line["with_gather"]
@@ -54,7 +54,7 @@ def test_n_rank_line_carries_baseline_configs_4_and_5():
     the communicator saw and the gathered bytes.  The last line is the compact one; the bulky details come
     first on a line that does not start with '{'."""
     out = run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1", "--comm", "torch",
-               "--config-steps", "3"])
+               "--config-steps", "3", "--full"])
     assert out.returncode == 0, out.stderr[-2000:]
     line = json_line(out)
     assert len(json.dumps(line)) < 4096 and out.stdout.rstrip().splitlines()[-1].startswith("{")
@@ -86,7 +86,7 @@ def test_eight_rank_dry_run_prints_the_hbm_need_and_skips_what_does_not_fit():
     n5 = bench.hbm_need(a, "cfg5", 12741, 8, True)
     assert round(n5["x"] / 1e9, 1) == 105.8 and round(n5["y"] / 1e9, 1) == 26.4 and n5["total"] < 288e9
     out = run([sys.executable, BENCH, "--gpus", "8", "--dry-run", "--steps", "2", "--warmup", "1", "--comm", "torch",
-               "--config-steps", "2"], timeout=300)
+               "--config-steps", "2", "--full"], timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json_line(out)
     assert line["n_gpus"] == 8 and len(json.dumps(line)) < 4096
@@ -94,7 +94,7 @@ def test_eight_rank_dry_run_prints_the_hbm_need_and_skips_what_does_not_fit():
     assert line["baseline_configs"]["cfg5"]["hbm_needed_gb"] == round(n5["total"] / 1e9, 1)
     # a GPU with 180 GB free: config 4 (206 GB on rank 0, 171 GB elsewhere) is skipped by ALL ranks, config 5 runs
     out = run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1", "--comm", "torch",
-               "--config-steps", "2"], env={"SMM_BENCH_TEST_FREE_GB": "180"}, timeout=300)
+               "--config-steps", "2", "--full"], env={"SMM_BENCH_TEST_FREE_GB": "180"}, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json_line(out)
     c4 = line["baseline_configs"]["cfg4"]
@@ -136,7 +136,7 @@ def test_a_hanging_gather_ends_non_zero_with_the_line_still_printed():
     """The gather watchdog: a rank that never reaches the collective costs the gather figures and the exit
     status (a hung RCCL must not look like a clean run), never the compute value."""
     out = run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1", "--comm", "torch",
-               "--gather-timeout", "4"], env={"SMM_BENCH_TEST_HANG_GATHER": "1"}, timeout=120)
+               "--gather-timeout", "4", "--full"], env={"SMM_BENCH_TEST_HANG_GATHER": "1"}, timeout=120)
     assert out.returncode != 0
     line = json_line(out)
     assert line["value"] > 0 and "error" in line["with_gather"]
@@ -203,6 +203,68 @@ def test_secondary_entries_keep_their_units():
     assert r["traffic_ratio"] == 1.827 and r["batch_fastest_traffic_ratio"] == 1.002 and "traffic_ratio" not in r["layouts"]["native"]
     assert r["configs"]["cfg3c"] == {"error": "boom"}
     assert len(line["config"]["workload"]) <= 100 and "plan" not in line["config"]
+
+
+def test_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full the line is the headline (no roofline, spot check, CPU baseline, other workloads or configs), --steps
+    is the number of timed steps, and --dump-outputs writes the last step's Y -- the same bits from run to run."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = run([sys.executable, BENCH, "--gpus", "1", "--dry-run", "--steps", "4", "--warmup", "2",
+                   "--dump-outputs", str(d)])
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json_line(out)
+        assert line["steps"] == 4 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        for k in ("metric", "unit", "higher_is_better", "dtype"):
+            assert k in line
+        for k in ("roofline", "spot_check", "cpu_baseline", "baseline_configs", "with_gather", "host_to_host"):
+            assert k not in line, k
+        assert sorted(os.listdir(d)) == ["y.npy"]
+        dumps.append(np.load(d / "y.npy"))
+    assert dumps[0].shape == (64, 96) and dumps[0].dtype == "float64"
+    assert dumps[0].tobytes() == dumps[1].tobytes()
+
+
+def test_dump_outputs_samples_what_exceeds_the_budget(tmp_path, monkeypatch):
+    """A Y larger than the dump budget is written as a fixed seeded sample of rows (columns too when one row alone is too
+    large), with the indices beside it, and the files stay within the budget."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096)
+    y = np.arange(300 * 40, dtype=np.float64).reshape(3, 100, 40)
+    bench.dump_outputs(str(tmp_path / "a"), y)
+    bench.dump_outputs(str(tmp_path / "b"), y)
+    s, rows = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "a" / "y_rows.npy")
+    assert s.shape == (12, 40) and rows.dtype == np.float64 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(s, y.reshape(300, 40)[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "y_rows.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a")) <= 4096
+    wide = np.arange(2 * 2000, dtype=np.float32).reshape(2, 2000)
+    bench.dump_outputs(str(tmp_path / "w"), wide)
+    s, cols = np.load(tmp_path / "w" / "y.npy"), np.load(tmp_path / "w" / "y_cols.npy")
+    rows = np.load(tmp_path / "w" / "y_rows.npy").astype(np.int64)
+    assert s.dtype == np.float32 and s.shape == (1, 341) and np.array_equal(s, wide[rows][:, cols.astype(np.int64)])
+
+
+@pytest.mark.gpu
+def test_plain_gpu_run_dumps_the_same_outputs_twice(hip, tmp_path):
+    """The plain run on the device (config 2 with a short batch): the line is the headline only and two runs write the same
+    bits for the last step's Y."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16",
+                   "--dump-outputs", str(d)], timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json_line(out)
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and "roofline" not in line and "spot_check" not in line
+        dumps.append(np.load(d / "y.npy"))
+    assert dumps[0].shape == (16, 64800) and dumps[0].dtype == np.float64 and np.isfinite(dumps[0]).all()
+    assert dumps[0].tobytes() == dumps[1].tobytes()
 
 
 def test_world_size_must_match_gpus():

@@ -95,7 +95,7 @@ def test_bench_two_ranks_with_gather_through_the_stand_in(hip, fake_rccl):
     set-up, the compute + tiled-gather loop (`gather_phase`) and the JSON line -- a `with_gather` block without
     `error`, bytes as the schedule predicts."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--gather", "root", "--steps", "2",
-                          "--warmup", "1", "--batch", "96", "--gather-tiles", "5", "--no-cpu-baseline"], cwd=ROOT,
+                          "--warmup", "1", "--batch", "96", "--gather-tiles", "5", "--no-cpu-baseline", "--full"], cwd=ROOT,
                          env=_env(fake_rccl, SMM_BENCH_SHARE_GPUS="1"), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -117,7 +117,7 @@ def test_bench_two_ranks_run_the_baseline_configs_with_their_gathers(hip, fake_r
     rendezvous and the compute + tiled-gather loop of `baseline_config_block`, all through the stand-in library."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--gather", "root", "--steps", "2",
                           "--warmup", "1", "--config-batch", "8", "--config-steps", "2", "--config-warmup", "1",
-                          "--config-gather-steps", "1", "--gather-tiles", "3"], cwd=ROOT,
+                          "--config-gather-steps", "1", "--gather-tiles", "3", "--full"], cwd=ROOT,
                          env=_env(fake_rccl, SMM_BENCH_SHARE_GPUS="1"), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

@@ -13,7 +13,7 @@ out=$root/gpurun_out/profiles_new
 mkdir -p $out
 export TMPDIR=/tmp
 for wl in $wls; do
-  python3 bench.py --workload $wl --steps 20 --warmup 3 --others none --configs none --user-path none > $out/${tag}_bench_$wl.json
+  python3 bench.py --full --workload $wl --steps 20 --warmup 3 --others none --configs none --user-path none > $out/${tag}_bench_$wl.json
   d=/tmp/prof_$wl
   rm -rf $d
   (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $d/kt -- python3 $root/bench.py --workload $wl \
@@ -33,7 +33,7 @@ for wl in $wls; do
   echo "done $wl"
 done
 if [ -n "$SMM_DRIVER_CMD" ]; then
-  # the driver's own command (headline + the secondary workloads of the same line) under the kernel trace
+  # the driver's own command (the headline only; the secondary workloads run with --full) under the kernel trace
   rm -rf /tmp/prof_driver
   (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_driver/kt -- python3 $root/bench.py \
       --gpus 1 --steps 20 --warmup 5 > $out/${tag}_driver_cmd_bench_under_rocprof.json)

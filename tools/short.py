@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Compact one-line summary of a bench.py JSON line read from stdin (optionally prefixed by argv[1:])."""
+"""Compact one-line summary of a `bench.py --full` JSON line read from stdin (optionally prefixed by argv[1:])."""
 import json
 import sys
 
