@@ -65,9 +65,18 @@ enum {
   SMM_APPLY_SB_PACKED = 1u << 2, /* smm_apply_sb: X holds only the used source cells (smm_operator_used_sources order) */
   SMM_APPLY_HOST_NO_PACK = 1u << 3, /* smm_apply_host: always ship whole rows (no packing of the used source cells) */
   SMM_APPLY_SB_Y_SB = 1u << 4,   /* smm_apply_sb: the result is kept batch-fastest too, Y (n_dst, ldy >= n_batch) */
+  SMM_APPLY_SKIPNA = 1u << 6,    /* renormalise over the valid source values of each batch row (see below) */
   SMM_APPLY_KERNEL_SELL = 1u << 8, /* force the row-per-lane SELL-64 kernel                  */
   SMM_APPLY_KERNEL_TILE = 1u << 9  /* force the LDS-staged source-tile kernel (if planned)   */
 };
+/* SMM_APPLY_SKIPNA, for destination row d and batch row b, links k of the canonical CSR in ascending source order:
+ * a link is invalid when x[b, col_k] is not finite and w_k != 0.  In f64, from +0.0, multiply and add kept apart:
+ *   num = sum over valid links of w * x     den = sum over valid links of w     tot = sum over all links of w
+ * inv = the row has an invalid link;  r = inv ? den / tot : 1.0;  v = inv ? num * (tot / den) : num.
+ * The row is dead when it is masked (SMM_APPLY_MASKED, dst_imask[d] == 0), when inv && !(r > 0.0), or when
+ * remap_area_min > 0 && (the operator has dst_frac || inv) && frac_d * r < remap_area_min (frac_d = dst_frac[d],
+ * 1.0 without dst_frac); y = (dead || v > 1e19) ? NaN : v.  A row without an invalid link is bit-identical to the
+ * plain apply.  Finite values, huge ones included, are valid.  With SMM_APPLY_NO_FILL: SMM_ERR_INVALID. */
 typedef struct smm_operator* smm_operator_t; /* one (S x D) weights matrix resident in HBM      */
 typedef struct smm_group* smm_group_t;       /* ordered set of operators (one per masked level) */
 

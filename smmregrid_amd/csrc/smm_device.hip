@@ -40,18 +40,30 @@
 #pragma clang fp contract(off)
 
 namespace smm_launch {
-#define SMM_EXTERN_PAIR(XT, YT)                                                                         \
-  extern template int launch_sell<XT, YT>(const ApplyArgs&, int64_t, bool, unsigned, hipStream_t);      \
-  extern template int launch_tile<XT, YT>(const ApplyArgs&, int64_t, int, int64_t, int64_t, int, bool, \
-                                          unsigned, hipStream_t);                                       \
-  extern template int launch_sb<XT, YT>(const SbArgs&, bool, unsigned, hipStream_t);                   \
-  extern template int launch_sb_group<XT, YT>(const SbGroupArgs&, bool, unsigned, hipStream_t);
-SMM_EXTERN_PAIR(double, double)
-SMM_EXTERN_PAIR(double, float)
-SMM_EXTERN_PAIR(float, double)
-SMM_EXTERN_PAIR(float, float)
+#define SMM_EXTERN_PAIR(XT, YT, NA)                                                                         \
+  extern template int launch_sell<XT, YT, NA>(const ApplyArgs&, int64_t, bool, unsigned, hipStream_t);      \
+  extern template int launch_tile<XT, YT, NA>(const ApplyArgs&, int64_t, int, int64_t, int64_t, int, bool, \
+                                              unsigned, hipStream_t);                                       \
+  extern template int launch_sb<XT, YT, NA>(const SbArgs&, bool, unsigned, hipStream_t);                   \
+  extern template int launch_sb_group<XT, YT, NA>(const SbGroupArgs&, bool, unsigned, hipStream_t);
+SMM_EXTERN_PAIR(double, double, false)
+SMM_EXTERN_PAIR(double, float, false)
+SMM_EXTERN_PAIR(float, double, false)
+SMM_EXTERN_PAIR(float, float, false)
+SMM_EXTERN_PAIR(double, double, true)
+SMM_EXTERN_PAIR(double, float, true)
+SMM_EXTERN_PAIR(float, double, true)
+SMM_EXTERN_PAIR(float, float, true)
 #undef SMM_EXTERN_PAIR
 }  // namespace smm_launch
+
+// FN<XT, YT, SKIPNA>(...) for the run-time dtypes (SMM_F64 / SMM_F32) and SMM_APPLY_SKIPNA
+#define SMM_DISPATCH_NA(FN, NA, XD, YD, ...)                                                   \
+  ((XD) == SMM_F64 ? ((YD) == SMM_F64 ? FN<double, double, NA>(__VA_ARGS__) : FN<double, float, NA>(__VA_ARGS__)) \
+                   : ((YD) == SMM_F64 ? FN<float, double, NA>(__VA_ARGS__) : FN<float, float, NA>(__VA_ARGS__)))
+#define SMM_DISPATCH_ALL(FN, FLAGS, XD, YD, ...)                      \
+  (((FLAGS) & SMM_APPLY_SKIPNA) ? SMM_DISPATCH_NA(FN, true, XD, YD, __VA_ARGS__) \
+                                : SMM_DISPATCH_NA(FN, false, XD, YD, __VA_ARGS__))
 
 namespace {
 
@@ -410,11 +422,16 @@ int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t*
 
   const size_t xsz = x_dtype == SMM_F64 ? 8 : 4;
   bool use_tile = false;
+  // SMM_APPLY_SKIPNA: tile forms without a skipna variant (split rows, rows streamed from L2) run kernel A instead
+  const bool tile_skipna_ok = !(flags & SMM_APPLY_SKIPNA) ||
+                              smm_launch::tile_has_skipna(tile_which, tile_which >= 2 ? tile_which - 1 : 0, max_row_nnz);
   if (flags & SMM_APPLY_KERNEL_TILE) {
     if (!tile_ok) return fail(SMM_ERR_UNSUPPORTED, "operator has no LDS tile plan");
+    if (!tile_skipna_ok)
+      return fail(SMM_ERR_UNSUPPORTED, "SMM_APPLY_SKIPNA: the planned tile form (split or streamed rows) has no skipna variant");
     use_tile = true;
   } else if (!(flags & SMM_APPLY_KERNEL_SELL)) {
-    use_tile = tile_ok && tile_preferred;
+    use_tile = tile_ok && tile_preferred && tile_skipna_ok;
   }
   // The staging loads are 16 B wide but only need element alignment (unaligned 16-B global loads
   // are legal on gfx950; rows of odd length still run ~10 % faster than the SELL kernel).
@@ -423,10 +440,7 @@ int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t*
     use_tile = false;
   }
 
-#define SMM_DISPATCH(FN, ...)                                                        \
-  (x_dtype == SMM_F64                                                                \
-       ? (y_dtype == SMM_F64 ? FN<double, double>(__VA_ARGS__) : FN<double, float>(__VA_ARGS__)) \
-       : (y_dtype == SMM_F64 ? FN<float, double>(__VA_ARGS__) : FN<float, float>(__VA_ARGS__)))
+#define SMM_DISPATCH(FN, ...) SMM_DISPATCH_ALL(FN, flags, x_dtype, y_dtype, __VA_ARGS__)
   if (use_tile) {
     const int64_t rows = shape_rows(tile_which);          // destination rows per block of the tile plan
     a.n_dblocks = (n_dst + rows - 1) / rows;
@@ -593,7 +607,8 @@ int guarded(F&& body) noexcept {
 
 // apply flags the ABI defines; anything else (ABI v4 callers encoded kernel variants in bits 16..23) is refused
 constexpr unsigned kApplyFlagMask = SMM_APPLY_MASKED | SMM_APPLY_NO_FILL | SMM_APPLY_SB_PACKED | SMM_APPLY_HOST_NO_PACK |
-                                    SMM_APPLY_SB_Y_SB | SMM_APPLY_KERNEL_SELL | SMM_APPLY_KERNEL_TILE;
+                                    SMM_APPLY_SB_Y_SB | SMM_APPLY_SKIPNA | SMM_APPLY_KERNEL_SELL |
+                                    SMM_APPLY_KERNEL_TILE;
 inline int check_flags(unsigned flags) {
   if (flags & ~kApplyFlagMask)
     return fail(SMM_ERR_INVALID, "unknown apply flag bits 0x" + [](unsigned v) {
@@ -601,6 +616,8 @@ inline int check_flags(unsigned flags) {
              snprintf(buf, sizeof(buf), "%x", v);
              return std::string(buf);
            }(flags & ~kApplyFlagMask) + " (launch-shape knobs are smm_debug_set_tuning entries, not flags)");
+  if ((flags & SMM_APPLY_SKIPNA) && (flags & SMM_APPLY_NO_FILL))
+    return fail(SMM_ERR_INVALID, "SMM_APPLY_SKIPNA tests every source value: it cannot take SMM_APPLY_NO_FILL");
   return SMM_OK;
 }
 
@@ -1127,9 +1144,7 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int6
     a.x = (const char*)x + b0 * (int64_t)xsz;
     a.y = (char*)y + ((flags & SMM_APPLY_SB_Y_SB) ? b0 : b0 * ldy) * (int64_t)ysz;
     a.n_batch = std::min(part, n_batch - b0);
-    rc = x_dtype == SMM_F64
-             ? (y_dtype == SMM_F64 ? launch_sb<double, double>(a, fill, flags, s) : launch_sb<double, float>(a, fill, flags, s))
-             : (y_dtype == SMM_F64 ? launch_sb<float, double>(a, fill, flags, s) : launch_sb<float, float>(a, fill, flags, s));
+    rc = SMM_DISPATCH_ALL(launch_sb, flags, x_dtype, y_dtype, a, fill, flags, s);
     if (rc) return rc;
   }
   return SMM_OK;
@@ -1261,7 +1276,8 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int x_dtyp
     int rc = SMM_OK;
     if (pack)
       rc = smm_apply_sb_impl(op, pipe.dx[b], x_dtype, rows, pipe.dy[b], y_dtype, D, rows, remap_area_min,
-                         (flags & (SMM_APPLY_MASKED | SMM_APPLY_NO_FILL)) | SMM_APPLY_SB_PACKED, pipe.stream[b]);
+                         (flags & (SMM_APPLY_MASKED | SMM_APPLY_NO_FILL | SMM_APPLY_SKIPNA)) | SMM_APPLY_SB_PACKED,
+                         pipe.stream[b]);
     else
       rc = run_apply(op->d_desc, nullptr, nullptr, S, op->csr.n_dst, pw, pl.valid, pl.preferred, (pl.reuse ? 1 : 0),
                      pl.max_chunks, op->csr.max_row_nnz, pipe.dx[b], x_dtype,
@@ -1587,11 +1603,7 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, in
         const bool m = (flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w]);   // regrid.py:405
         a.lev[i] = SbLevelPtrs{op->d_csr_rowptr, op->d_csr_col, op->d_csr_val, m ? op->d_imask : nullptr, op->d_frac};
       }
-      const int rc = x_dtype == SMM_F64
-                         ? (y_dtype == SMM_F64 ? launch_sb_group<double, double>(a, fill, flags, caller)
-                                               : launch_sb_group<double, float>(a, fill, flags, caller))
-                         : (y_dtype == SMM_F64 ? launch_sb_group<float, double>(a, fill, flags, caller)
-                                               : launch_sb_group<float, float>(a, fill, flags, caller));
+      const int rc = SMM_DISPATCH_ALL(launch_sb_group, flags, x_dtype, y_dtype, a, fill, flags, caller);
       if (rc) return rc;
     }
     return SMM_OK;
@@ -1859,7 +1871,7 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
       for (int64_t ll = 0; ll < ck.nl && !rc; ++ll) {
         const int w = level_index[ck.l0 + ll];
         smm_operator* op = g->ops[(size_t)w];
-        unsigned fl = (flags & SMM_APPLY_NO_FILL) | SMM_APPLY_SB_PACKED;
+        unsigned fl = (flags & (SMM_APPLY_NO_FILL | SMM_APPLY_SKIPNA)) | SMM_APPLY_SB_PACKED;
         if ((flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w])) fl |= SMM_APPLY_MASKED;
         // Y of the chunk: entry (b, ll, d) at (b * nl + ll) * D + d when transpose, at (ll * bc + b) * D + d else
         rc = smm_apply_sb(op, (char*)pipe.dx[b] + off, x_dtype, bc,

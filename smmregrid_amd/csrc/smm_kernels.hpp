@@ -151,6 +151,79 @@ __device__ __forceinline__ double epilogue(double v, bool dead) {
   return (dead || v > 1e19) ? __builtin_nan("") : v;
 }
 
+// Running sum of one destination row for one batch row.  Plain: num = sum w * fill(x), the value handed in
+// is already filled (load_fixed).  SKIPNA (SMM_APPLY_SKIPNA): the value is raw; a link is invalid when x is
+// not finite and w != 0 -- it adds nothing and marks the row -- and valid links add w * fill(x) to num and w
+// to den (a zero-weight link over a non-finite x adds w * (XT)1e20 = +-0, exactly as the plain sum does).
+// Padded slots (weight +0.0) are never invalid and add +-0 to sums that are never -0.0: bitwise no-ops.
+template <typename XT, bool SKIPNA>
+struct RowSum {
+  double num = 0.0, den = 0.0;
+  bool inv = false;
+  __device__ __forceinline__ void add(double w, double x) {
+    if constexpr (SKIPNA) {
+      const bool fin = __builtin_isfinite(x);
+      const bool bad = !fin && w != 0.0;
+      const double p = w * (fin ? x : (double)(XT)1e20);
+      const double ns = num + p, ds = den + w;
+      num = bad ? num : ns;
+      den = bad ? den : ds;
+      inv = inv || bad;
+    } else {
+      const double p = w * x;
+      num = num + p;
+    }
+  }
+  __device__ __forceinline__ void add_if(bool on, double w, double x) {   // slot k of a walk that may pass the row's end
+    if constexpr (SKIPNA) {
+      const bool fin = __builtin_isfinite(x);
+      const bool bad = on && !fin && w != 0.0;
+      const double p = w * (fin ? x : (double)(XT)1e20);
+      const double ns = num + p, ds = den + w;
+      num = (on && !bad) ? ns : num;
+      den = (on && !bad) ? ds : den;
+      inv = inv || bad;
+    } else {
+      const double p = w * x;
+      const double sum = num + p;
+      num = on ? sum : num;
+    }
+  }
+  __device__ __forceinline__ void clear() {
+    num = 0.0;
+    den = 0.0;
+    inv = false;
+  }
+  __device__ __forceinline__ void keep_if(bool on) {   // a row without links never looks at the tile: +0.0
+    num = on ? num : 0.0;
+    if constexpr (SKIPNA) inv = on && inv;
+  }
+};
+
+// The gathered value a RowSum takes: filled for the plain sum, raw under SKIPNA.
+template <bool SKIPNA, typename T>
+__device__ __forceinline__ double load_link(const T* __restrict__ p, bool fill) {
+  if constexpr (SKIPNA)
+    return (double)*p;
+  else
+    return load_fixed(p, fill);
+}
+
+// SKIPNA epilogue.  dead_m: the static mask alone (SMM_APPLY_MASKED); frac_d: dst_frac[d], 1.0 without dst_frac;
+// tot: sum of all the row's weights in ascending source order.  A row without an invalid link takes exactly the
+// plain epilogue (r = 1: the area test is the plain frac_d < area_min when the operator has dst_frac).
+__device__ __forceinline__ double skipna_epilogue(double num, double den, bool inv, double tot, bool dead_m,
+                                                  bool has_frac, double frac_d, double area_min) {
+  const double r = inv ? den / tot : 1.0;
+  const double v = inv ? num * (tot / den) : num;
+  bool dead = dead_m || (inv && !(r > 0.0));
+  if (area_min > 0.0 && (has_frac || inv)) {
+    const double fr = frac_d * r;
+    dead = dead || fr < area_min;
+  }
+  return epilogue(v, dead);
+}
+
 // Row pointers of batch row j of level l.
 __device__ __forceinline__ int64_t row_off(int64_t j, int64_t l, int64_t n_inner, int64_t s_o,
                                            int64_t s_l, int64_t s_i) {
@@ -183,7 +256,7 @@ struct RowWalker {
 // col/val stream is read once per BT outputs and BT independent gathers are in
 // flight per link.  Gathers hit X directly: neighbouring lanes read
 // neighbouring source cells, L1/L2 absorb the line reuse.
-template <typename XT, typename YT, int BT>
+template <typename XT, typename YT, int BT, bool SKIPNA = false>
 __global__ __launch_bounds__(kThreads) void smm_apply_sell_kernel(ApplyArgs a, bool fill) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -216,9 +289,8 @@ __global__ __launch_bounds__(kThreads) void smm_apply_sell_kernel(ApplyArgs a, b
   const int32_t* __restrict__ cp = L.col + off + lane;
   const double* __restrict__ vp = L.val + off + lane;
 
-  double acc[BT];
-#pragma unroll
-  for (int t = 0; t < BT; ++t) acc[t] = 0.0;
+  RowSum<XT, SKIPNA> acc[BT];
+  double tot = 0.0;   // SKIPNA: the row's weight sum, shared by the BT batch rows
 
   // Padded slots carry a valid column (the row's last one) and weight +0.0: the running sum is
   // never -0.0 and the gathered value is finite after the fill, so acc + 0*x == acc bit for bit --
@@ -229,26 +301,34 @@ __global__ __launch_bounds__(kThreads) void smm_apply_sell_kernel(ApplyArgs a, b
     const double w = vp[(int64_t)k * 64];
     double xv[BT];
 #pragma unroll
-    for (int t = 0; t < BT; ++t) xv[t] = load_fixed(xr[t] + c, fill);
+    for (int t = 0; t < BT; ++t) xv[t] = load_link<SKIPNA>(xr[t] + c, fill);
 #pragma unroll
-    for (int t = 0; t < BT; ++t) {
-      const double p = w * xv[t];
-      acc[t] = acc[t] + p;
-    }
+    for (int t = 0; t < BT; ++t) acc[t].add(w, xv[t]);
+    if (SKIPNA) tot = tot + w;
   }
   if (len == 0) {  // a row without links never looks at X (its padded slots read column 0)
 #pragma unroll
-    for (int t = 0; t < BT; ++t) acc[t] = 0.0;
+    for (int t = 0; t < BT; ++t) acc[t].clear();
   }
 
   if (d < a.n_dst) {
     const bool use_mask = a.masked && (a.lev_masked ? a.lev_masked[di] != 0 : true);
     bool dead = false;
     if (use_mask && L.imask) dead = (L.imask[d] == 0);
-    if (a.area_min > 0.0 && L.frac) dead = dead || (L.frac[d] < a.area_min);
+    if constexpr (SKIPNA) {
+      const double frac_d = L.frac ? L.frac[d] : 1.0;
 #pragma unroll
-    for (int t = 0; t < BT; ++t) {
-      if (j0 + t < a.n_j) yr[t][d] = (YT)epilogue(acc[t], dead);
+      for (int t = 0; t < BT; ++t) {
+        if (j0 + t < a.n_j)
+          yr[t][d] = (YT)skipna_epilogue(acc[t].num, acc[t].den, acc[t].inv, tot, dead, L.frac != nullptr, frac_d,
+                                         a.area_min);
+      }
+    } else {
+      if (a.area_min > 0.0 && L.frac) dead = dead || (L.frac[d] < a.area_min);
+#pragma unroll
+      for (int t = 0; t < BT; ++t) {
+        if (j0 + t < a.n_j) yr[t][d] = (YT)epilogue(acc[t].num, dead);
+      }
     }
   }
 }
@@ -300,7 +380,12 @@ constexpr int tile_waves(int maxk) { return (maxk > 0 && maxk <= 16) ? kWavesPer
 // never better than two slots (config-4 geometry 4.83 ms with three slots and the wait counted so that
 // neither the younger row nor the latest Y store is waited for, against 4.86; 5.56 with four): that
 // kernel is bound by its bytes, not by a workgroup's round trips, and deeper rings cost workgroups per CU.
-template <typename XT, typename YT, int MAXK, int NP, int NT, int R = 1, bool SPLIT = false, bool DMA = false>
+//
+// SKIPNA (SMM_APPLY_SKIPNA): the staged pieces keep their non-finite values (no fill at the stage) and every gathered
+// value is tested per link (RowSum); the row's weight sum comes from the link registers once per block.  Built for the
+// forms that keep the links in registers without SPLIT (tile_has_skipna): the others run kernel A instead.
+template <typename XT, typename YT, int MAXK, int NP, int NT, int R = 1, bool SPLIT = false, bool DMA = false,
+          bool SKIPNA = false>
 __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kernel(ApplyArgs a, bool fill) {
   constexpr int WPB = tile_waves(MAXK);
   constexpr int T = WPB * 64;
@@ -309,7 +394,8 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
   // LDS (a 48-link row would test 48 gathered values per batch row, its ~15 pieces hold 30); short
   // rows gather few values from comparatively many staged ones (config 4: 4 links, 8 staged f32 per
   // lane and step) and test what they gather.
-  constexpr bool kFixAtStage = !DMA && (MAXK == 0 || MAXK > 16);   // LDS-DMA bypasses the registers: test at the gather
+  constexpr bool kFixAtStage = !DMA && !SKIPNA && (MAXK == 0 || MAXK > 16);   // LDS-DMA bypasses the registers: test at the gather
+  static_assert(!SKIPNA || (!SPLIT && MAXK > 0), "SKIPNA: links in registers, one lane per row");
   static_assert(!SPLIT || (WPB == 1 && R == 1 && MAXK > 0), "split rows: single-wave, single-row steps");
   static_assert(R == 1 || (MAXK > 0 && MAXK <= 16), "multi-row steps exist for the 4-wave shape only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -405,11 +491,26 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
   wmax = __builtin_amdgcn_readfirstlane(wmax);
 
   bool dead = false;
+  bool dead_m = false;    // SKIPNA: the static mask alone; the area test moves into skipna_epilogue
+  double frac_d = 1.0;
   if (row_live) {
     const bool use_mask = a.masked && (a.lev_masked ? a.lev_masked[di] != 0 : true);
     if (use_mask && L.imask) dead = (L.imask[d] == 0);
+    dead_m = dead;
+    if (SKIPNA && L.frac) frac_d = L.frac[d];
     if (a.area_min > 0.0 && L.frac) dead = dead || (L.frac[d] < a.area_min);
   }
+  double tot = 0.0;   // SKIPNA: the row's weight sum in ascending source order (padded slots hold +0.0)
+  if constexpr (SKIPNA) {
+#pragma unroll
+    for (int k = 0; k < KREG; ++k) tot = tot + w[k];
+  }
+  auto finish = [&](const RowSum<XT, SKIPNA>& s) -> double {
+    if constexpr (SKIPNA)
+      return skipna_epilogue(s.num, s.den, s.inv, tot, dead_m, L.frac != nullptr, frac_d, a.area_min);
+    else
+      return epilogue(s.num, dead);
+  };
 
   const int64_t c0 = L.blk_chunk_off[db];
   const int nch = (int)(L.blk_chunk_off[db + 1] - c0);
@@ -485,7 +586,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
       RowWalker ywd(j_begin, l, a.n_inner, a.ys_o, a.ys_l, a.ys_i);
       for (int64_t j = j_begin; j < j_end; ++j, xwd.next(), ywd.next()) {
         const XT* __restrict__ xrow = (const XT*)a.x + xwd.off;
-        double acc = 0.0;
+        RowSum<XT, SKIPNA> acc;
         // eight slots at a time: their column / weight loads, then the eight gathers, are in flight
         // together (a load per link in front of its gather would serialise the round trips)
         for (int k0 = 0; k0 < dmax; k0 += 8) {
@@ -498,17 +599,13 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
             wv[q] = gvp[(int64_t)kc * 64];
           }
 #pragma unroll
-          for (int q = 0; q < 8; ++q) xv[q] = load_fixed(xrow + gc[q], fill);
+          for (int q = 0; q < 8; ++q) xv[q] = load_link<SKIPNA>(xrow + gc[q], fill);
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const double p = wv[q] * xv[q];
-            const double sum = acc + p;
-            acc = (k0 + q < dlen) ? sum : acc;
-          }
+          for (int q = 0; q < 8; ++q) acc.add_if(k0 + q < dlen, wv[q], xv[q]);
         }
         if (dlive) {
           YT* __restrict__ yrow = (YT*)a.y + ywd.off;
-          yrow[ddy] = (YT)epilogue(acc, ddead);
+          yrow[ddy] = (YT)(SKIPNA ? finish(acc) : epilogue(acc.num, ddead));   // SKIPNA: never SPLIT, ddead == dead
         }
       }
     }
@@ -598,9 +695,9 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
         if (jb + r < j_end) {
           if (slice_live) {
             const char* lds_b = smem + (size_t)(group * R + r) * tile_bytes;
-            double acc = 0.0;
+            RowSum<XT, SKIPNA> acc;
 #ifdef SMM_EXP_SKIP_COMPUTE   // timing-only ablation (tools/exp/build_exp.sh): stage and store, no link loop
-            acc = w[0] + (double)(lds_b - smem);
+            acc.num = w[0] + (double)(lds_b - smem);
 #else
 #pragma unroll
             for (int k0 = 0; k0 < KREG; k0 += 4) {
@@ -610,21 +707,18 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
                 for (int kk = 0; kk < 4; ++kk) {
                   const int k = k0 + kk;
                   const uint32_t li = (k & 1) ? (lc2[(k < KREG ? k : 0) / 2] >> 16) : (lc2[(k < KREG ? k : 0) / 2] & 0xFFFFu);
-                  xv[kk] = load_fixed((const XT*)(lds_b + li), fill);
+                  xv[kk] = load_link<SKIPNA>((const XT*)(lds_b + li), fill);
                 }
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
                   const int k = k0 + kk;
-                  if (k < KREG) {
-                    const double p = w[k] * xv[kk];
-                    acc = acc + p;
-                  }
+                  if (k < KREG) acc.add(w[k], xv[kk]);
                 }
               }
             }
 #endif
-            acc = len > 0 ? acc : 0.0;
-            pend_out[r] = (YT)epilogue(acc, dead);
+            acc.keep_if(len > 0);
+            pend_out[r] = (YT)finish(acc);
             pend_off[r] = yw.off;
           }
           n_pend = r + 1;
@@ -736,7 +830,8 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
       }
 #endif
       if (slice_live) {
-        double acc = 0.0;
+        double acc = 0.0;          // SPLIT and streamed links (plain only)
+        RowSum<XT, SKIPNA> rs;     // links in registers
         if constexpr (SPLIT) {
           // lane groups take their turn: group g continues the sums group g-1 handed over
           const int rows_blk = 64 >> a.sub_shift;
@@ -769,7 +864,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
           }
 #ifdef SMM_EXP_SKIP_COMPUTE
         } else if (true) {   // timing-only ablation: one LDS read instead of the link loop
-          acc = (double)lds_x[lane];
+          rs.num = acc = (double)lds_x[lane];
 #endif
         } else if (MAXK > 0) {
 #pragma unroll
@@ -781,15 +876,12 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
                 const int k = k0 + kk;
                 const uint32_t li = (k & 1) ? (lc2[(k < KREG ? k : 0) / 2] >> 16)
                                             : (lc2[(k < KREG ? k : 0) / 2] & 0xFFFFu);
-                xv[kk] = load_fixed((const XT*)((const char*)lds_x + li), fill && !kFixAtStage);  // unconditional: offset 0 for unused slots
+                xv[kk] = load_link<SKIPNA>((const XT*)((const char*)lds_x + li), fill && !kFixAtStage);  // unconditional: offset 0 for unused slots
               }
 #pragma unroll
               for (int kk = 0; kk < 4; ++kk) {
                 const int k = k0 + kk;
-                if (k < KREG) {
-                  const double p = w[k] * xv[kk];
-                  acc = acc + p;
-                }
+                if (k < KREG) rs.add(w[k], xv[kk]);
               }
             }
           }
@@ -814,8 +906,9 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
             }
           }
         }
-        if (MAXK > 0 && !SPLIT) acc = len > 0 ? acc : 0.0;   // a row without links never looks at the tile
-        pend_out = (YT)epilogue(acc, dead);
+        if (MAXK > 0 && !SPLIT) rs.keep_if(len > 0);   // a row without links never looks at the tile
+        else rs.num = acc;
+        pend_out = (YT)finish(rs);
         pend_off = yw.off;
         if (!kDeferStore && row_live) flush_pending();
       }
@@ -924,10 +1017,10 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const XT* lds_r = (const XT*)(smem + r * tile_bytes);
-          double acc = 0.0;
+          RowSum<XT, SKIPNA> acc;
 #ifdef SMM_EXP_SKIP_COMPUTE
           if (true) {   // timing-only ablation: one LDS read instead of the link loop
-            acc = (double)lds_r[lane];
+            acc.num = (double)lds_r[lane];
           } else
 #endif
           if (MAXK > 0) {
@@ -940,15 +1033,12 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
                   const int k = k0 + kk;
                   const uint32_t li = (k & 1) ? (lc2[(k < KREG ? k : 0) / 2] >> 16)
                                               : (lc2[(k < KREG ? k : 0) / 2] & 0xFFFFu);
-                  xv[kk] = load_fixed((const XT*)((const char*)lds_r + li), fill && !kFixAtStage);  // unconditional: offset 0 for unused slots
+                  xv[kk] = load_link<SKIPNA>((const XT*)((const char*)lds_r + li), fill && !kFixAtStage);  // unconditional: offset 0 for unused slots
                 }
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
                   const int k = k0 + kk;
-                  if (k < KREG) {
-                    const double p = w[k] * xv[kk];
-                    acc = acc + p;
-                  }
+                  if (k < KREG) acc.add(w[k], xv[kk]);
                 }
               }
             }
@@ -958,14 +1048,12 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
               const int kc = min(k, nslots - 1);
               const bool on = k < len;
               const int32_t li = cp[(int64_t)kc * 64];
-              const double xv = load_fixed(lds_r + (on ? li : 0), fill && !kFixAtStage);
-              const double p = vp[(int64_t)kc * 64] * xv;
-              const double sum = acc + p;
-              acc = on ? sum : acc;
+              const double xv = load_link<SKIPNA>(lds_r + (on ? li : 0), fill && !kFixAtStage);
+              acc.add_if(on, vp[(int64_t)kc * 64], xv);
             }
           }
-          if (MAXK > 0) acc = len > 0 ? acc : 0.0;   // a row without links never looks at the tile
-          pend_out = (YT)epilogue(acc, dead);
+          if (MAXK > 0) acc.keep_if(len > 0);   // a row without links never looks at the tile
+          pend_out = (YT)finish(acc);
           pend_off = yw.off;
           if (!kDeferStore && row_live && jb + r < j_end) flush_pending();
           if (jb + r + 1 < j_end) yw.next();
@@ -1021,7 +1109,10 @@ struct SbTile {   // what does not depend on the level
   int masked, xcd_remap, b_fastest;
 };
 
-template <typename XT, typename YT, int TD, int U, bool FILL, bool YSB, typename M>
+// SKIPNA (SMM_APPLY_SKIPNA): the links are tested per batch entry (RowSum) and the row's weight sum runs wave-uniform
+// beside them; the ballot covers the static mask only, and the area test of each batch entry takes dst_frac of the
+// row from lane r of a per-tile load (a register read with a wave-uniform index: no vector load at a row end).
+template <typename XT, typename YT, int TD, int U, bool FILL, bool YSB, bool SKIPNA, typename M>
 __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32_t bid) {
   constexpr int VEC = 2;                    // batch entries per lane
   constexpr int BT = 64 * VEC;              // batch entries per tile
@@ -1077,28 +1168,41 @@ __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32
   int d_local = 0;
   int64_t row_end = m.rowptr[d0 + 1];
   int64_t row_end_next = m.rowptr[d0 + (rows > 1 ? 2 : 1)];   // scalar prefetch, one row ahead
-  double acc[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) acc[v] = 0.0;
+  RowSum<XT, SKIPNA> acc[VEC];
+  double tot = 0.0;   // SKIPNA: weight sum of the current row (wave-uniform)
 
   // regrid.py:553-565 per destination row, gathered once per tile (lane r looks at row r) into a
   // wave-uniform bit mask: a vector load inside flush_row would make every row end wait for all
   // outstanding X loads
   bool dead_lane = false;
+  double frac_lane = 1.0;   // SKIPNA: dst_frac of row d0 + lane
   if (lane < rows) {
     if (a.masked && m.imask) dead_lane = m.imask[d0 + lane] == 0;
-    if (a.area_min > 0.0 && m.frac) dead_lane = dead_lane || (m.frac[d0 + lane] < a.area_min);
+    if (SKIPNA && m.frac) frac_lane = m.frac[d0 + lane];
+    if (!SKIPNA && a.area_min > 0.0 && m.frac) dead_lane = dead_lane || (m.frac[d0 + lane] < a.area_min);
   }
   const unsigned long long dead_mask = __ballot(dead_lane);
 
   auto flush_row = [&]() {
     const bool dead = (dead_mask >> d_local) & 1ull;   // wave-uniform
+    double frac_d = 1.0;
+    if constexpr (SKIPNA) {
+      const uint64_t fb = __builtin_bit_cast(uint64_t, frac_lane);
+      const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)fb, d_local);
+      const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(fb >> 32), d_local);
+      frac_d = __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+    }
     YT out[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
-      out[v] = (YT)epilogue(acc[v], dead);
-      acc[v] = 0.0;
+      if constexpr (SKIPNA)
+        out[v] = (YT)skipna_epilogue(acc[v].num, acc[v].den, acc[v].inv, tot, dead, m.frac != nullptr, frac_d,
+                                     a.area_min);
+      else
+        out[v] = (YT)epilogue(acc[v].num, dead);
+      acc[v].clear();
     }
+    tot = 0.0;
     typedef YT yvec __attribute__((ext_vector_type(VEC)));
     yvec o;
 #pragma unroll
@@ -1131,10 +1235,10 @@ __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
           XT e = (v == 0 && shift1) ? xv[buf][u][1] : xv[buf][u][v];
-          if (FILL) e = __builtin_isfinite(e) ? e : (XT)1e20;   // regrid.py:545-547, dtype's own 1e20
-          const double prod = w[buf][u] * (double)e;
-          acc[v] = acc[v] + prod;
+          if (FILL && !SKIPNA) e = __builtin_isfinite(e) ? e : (XT)1e20;   // regrid.py:545-547, dtype's own 1e20
+          acc[v].add(w[buf][u], (double)e);
         }
+        if (SKIPNA) tot = tot + w[buf][u];
       }
     }
   };
@@ -1157,10 +1261,10 @@ __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32
       for (int v = 0; v < VEC; ++v) {
         const int64_t b = b0 + (int64_t)lane * VEC + v;
         XT e = ((const XT*)a.x)[c * a.ldx + (b < a.n_batch ? b : a.n_batch - 1)];
-        if (FILL) e = __builtin_isfinite(e) ? e : (XT)1e20;
-        const double prod = wv * (double)e;
-        acc[v] = acc[v] + prod;
+        if (FILL && !SKIPNA) e = __builtin_isfinite(e) ? e : (XT)1e20;
+        acc[v].add(wv, (double)e);
       }
+      if (SKIPNA) tot = tot + wv;
     }
   }
   while (d_local < rows) flush_row();
@@ -1212,18 +1316,18 @@ __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32
   }
 }
 
-template <typename XT, typename YT, int TD, int U, bool FILL, bool YSB = false>
+template <typename XT, typename YT, int TD, int U, bool FILL, bool YSB = false, bool SKIPNA = false>
 __global__ __launch_bounds__(64) void smm_apply_sb_kernel(SbArgs a) {
   const SbMatrix<const int64_t*, const int32_t*, const double*, const uint8_t*> m{a.rowptr, a.col, a.val, a.imask, a.frac};
   const SbTile t{a.x, a.y, a.ldx, a.ldy, a.n_batch, a.n_dst, a.n_dtiles, a.n_btiles, (uint32_t)a.n_blocks,
                  a.area_min, a.masked, a.xcd_remap, a.b_fastest};
-  sb_tile_body<XT, YT, TD, U, FILL, YSB>(m, t, blockIdx.x);
+  sb_tile_body<XT, YT, TD, U, FILL, YSB, SKIPNA>(m, t, blockIdx.x);
 }
 
 // The same tiles for every data level of a group in one launch: workgroup -> (level, tile of that level's grid).
 // Levels are independent, so the dispatcher backfills the thin deep levels' tails with the next level's tiles -- no
 // ramp-up and tail per level as with one launch each.
-template <typename XT, typename YT, int TD, int U, bool FILL, bool YSB = false>
+template <typename XT, typename YT, int TD, int U, bool FILL, bool YSB = false, bool SKIPNA = false>
 __global__ __launch_bounds__(64) void smm_group_apply_sb_kernel(SbGroupArgs a) {
   typedef const __attribute__((address_space(4))) int64_t* k_i64;
   typedef const __attribute__((address_space(4))) int32_t* k_i32;
@@ -1237,7 +1341,7 @@ __global__ __launch_bounds__(64) void smm_group_apply_sb_kernel(SbGroupArgs a) {
   const SbMatrix<k_i64, k_i32, k_f64, k_u8> m{(k_i64)L.rowptr, (k_i32)L.col, (k_f64)L.val, (k_u8)L.imask, (k_f64)L.frac};
   const SbTile t{(const XT*)a.x + (int64_t)lvl * a.xs_lev, (YT*)a.y + (int64_t)lvl * a.ys_lev, a.ldx, a.ldy, a.n_batch,
                  a.n_dst, a.n_dtiles, a.n_btiles, per, a.area_min, L.imask != nullptr, a.xcd_remap, a.b_fastest};
-  sb_tile_body<XT, YT, TD, U, FILL, YSB>(m, t, bid);
+  sb_tile_body<XT, YT, TD, U, FILL, YSB, SKIPNA>(m, t, bid);
 }
 
 // counter-based synthetic field: splitmix64 -> two uniforms -> Box-Muller

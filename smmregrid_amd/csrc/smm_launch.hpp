@@ -1,6 +1,7 @@
-// Kernel launch templates, one explicit instantiation per (X dtype, Y dtype) pair
-// (smm_launch_inst.hip is compiled four times, in parallel): the tile kernel alone has several
-// hundred instantiations, which one translation unit would compile for minutes.
+// Kernel launch templates, one explicit instantiation per (X dtype, Y dtype, SKIPNA) triple
+// (smm_launch_inst.hip is compiled eight times, in parallel): the tile kernel alone has several
+// hundred instantiations, which one translation unit would compile for minutes.  SKIPNA = true
+// builds the SMM_APPLY_SKIPNA variants (smm_kernels.hpp, RowSum) in objects of their own.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,7 +51,7 @@ inline int xcd_run_length() {
   return want < 0 ? 0 : (want > 0 ? want : 32);
 }
 
-template <typename XT, typename YT>
+template <typename XT, typename YT, bool SKIPNA>
 int launch_sell(const ApplyArgs& a, int64_t n_lev, bool fill, unsigned flags, hipStream_t s) {
   ApplyArgs args = a;
   auto go = [&](auto bt_tag) -> int {
@@ -59,7 +60,7 @@ int launch_sell(const ApplyArgs& a, int64_t n_lev, bool fill, unsigned flags, hi
     const int64_t total = args.n_dblocks * args.n_jtiles * n_lev;
     if (total <= 0) return SMM_OK;
     if (total > 0x7fffffffLL) return smm::fail_msg(SMM_ERR_INVALID, "launch grid exceeds 2^31-1 blocks");
-    hipLaunchKernelGGL((smm_apply_sell_kernel<XT, YT, BT>), dim3((unsigned)total), dim3(kThreads), 0,
+    hipLaunchKernelGGL((smm_apply_sell_kernel<XT, YT, BT, SKIPNA>), dim3((unsigned)total), dim3(kThreads), 0,
                        s, args, fill);
     SMM_LAUNCH_HIP(hipGetLastError());
     return SMM_OK;
@@ -143,7 +144,22 @@ inline TileLaunchCfg tile_launch_cfg(const ApplyArgs& a, int64_t n_lev, int tile
   return c;
 }
 
-template <typename XT, typename YT>
+// Part-of-a-slice blocks (sub_shift > 0) let the idle lanes take over parts of the rows (SPLIT kernels) when a
+// lane group's share fits the link registers (SMM_TUNE_TILE_SPLIT_ROWS = 1: off, for A/B runs).
+inline bool tile_split(int sub_shift, int64_t max_row_nnz) {
+  return sub_shift > 0 && smm::tuning(SMM_TUNE_TILE_SPLIT_ROWS) != 1 && max_row_nnz <= ((int64_t)48 << sub_shift);
+}
+
+// Whether the tile form launch_tile would pick has an SMM_APPLY_SKIPNA variant: the forms that keep the links in
+// registers, one lane per row (4-wave blocks, single-wave blocks of 17 - 48 links, register or LDS-DMA staging).
+// SPLIT rows and rows streamed from L2 (more than 48 links) have none: SKIPNA runs kernel A for them.
+inline bool tile_has_skipna(int tile_which, int sub_shift, int64_t max_row_nnz) {
+  if (!tile_which) return max_row_nnz <= 16;
+  if (tile_split(sub_shift, max_row_nnz)) return false;
+  return smm::tuning(SMM_TUNE_TILE_LINKS) != 1 && max_row_nnz <= 48;
+}
+
+template <typename XT, typename YT, bool SKIPNA>
 int launch_tile(const ApplyArgs& a, int64_t n_lev, int tile_which, int64_t max_chunks,
                 int64_t max_row_nnz, int tile_flags, bool fill, unsigned flags, hipStream_t s) {
   ApplyArgs args = a;
@@ -169,17 +185,17 @@ int launch_tile(const ApplyArgs& a, int64_t n_lev, int tile_which, int64_t max_c
       const dim3 grid((unsigned)total), block(tile_waves(MAXK) * 64);
       if constexpr (MAXK <= 16 && NPV <= 4) {
         if (rows == 4) {
-          hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NPV, NTV, 4, false, true>), grid, block, lds, s, args, fill);
+          hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NPV, NTV, 4, false, true, SKIPNA>), grid, block, lds, s, args, fill);
           SMM_LAUNCH_HIP(hipGetLastError());
           return SMM_OK;
         }
         if (rows == 2) {
-          hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NPV, NTV, 2, false, true>), grid, block, lds, s, args, fill);
+          hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NPV, NTV, 2, false, true, SKIPNA>), grid, block, lds, s, args, fill);
           SMM_LAUNCH_HIP(hipGetLastError());
           return SMM_OK;
         }
       }
-      hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NPV, NTV, 1, false, true>), grid, block, lds, s, args, fill);
+      hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NPV, NTV, 1, false, true, SKIPNA>), grid, block, lds, s, args, fill);
       SMM_LAUNCH_HIP(hipGetLastError());
       return SMM_OK;
     } else {
@@ -191,20 +207,21 @@ int launch_tile(const ApplyArgs& a, int64_t n_lev, int tile_which, int64_t max_c
     constexpr int NP = decltype(np_tag)::value;
     constexpr int NT = decltype(nt_tag)::value;
     constexpr int R = decltype(r_tag)::value;
-    hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NP, NT, R>), dim3((unsigned)total),
+    hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NP, NT, R, false, false, SKIPNA>), dim3((unsigned)total),
                        dim3(tile_waves(MAXK) * 64), lds, s, args, fill);
     SMM_LAUNCH_HIP(hipGetLastError());
     return SMM_OK;
   };
-  // Part-of-a-slice blocks: the idle lanes take over parts of the rows (SPLIT kernels) when a lane
-  // group's share fits the link registers (SMM_TUNE_TILE_SPLIT_ROWS = 1: off, for A/B runs).
+  // Part-of-a-slice blocks: the idle lanes take over parts of the rows (SPLIT kernels, tile_split).
   const int n_grp = 1 << args.sub_shift;
-  const bool split = args.sub_shift > 0 && smm::tuning(SMM_TUNE_TILE_SPLIT_ROWS) != 1 && max_row_nnz <= (int64_t)n_grp * 48;
+  const bool split = tile_split(args.sub_shift, max_row_nnz);
   const int64_t per_grp = (max_row_nnz + n_grp - 1) / n_grp;
+  if (SKIPNA && !tile_has_skipna(tile_which, args.sub_shift, max_row_nnz))
+    return smm::fail_msg(SMM_ERR_UNSUPPORTED, "SMM_APPLY_SKIPNA: the planned tile form (split or streamed rows) has no skipna variant");
   auto go2 = [&](auto k_tag, auto np_tag, auto nt_tag) -> int {
     constexpr int MAXK = decltype(k_tag)::value;
     if (dma) return go_dma(k_tag, np_tag, nt_tag);
-    if constexpr (MAXK == 32 || MAXK == 48) {
+    if constexpr (!SKIPNA && (MAXK == 32 || MAXK == 48)) {
       if (split) {
         hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, decltype(np_tag)::value, decltype(nt_tag)::value, 1, true>),
                            dim3((unsigned)total), dim3(64), lds, s, args, fill);
@@ -216,7 +233,10 @@ int launch_tile(const ApplyArgs& a, int64_t n_lev, int tile_which, int64_t max_c
       if (rows == 4) return go3(k_tag, std::integral_constant<int, 1>(), nt_tag, std::integral_constant<int, 4>());
       if (rows == 2) return go3(k_tag, std::integral_constant<int, 2>(), nt_tag, std::integral_constant<int, 2>());
     }
-    return go3(k_tag, np_tag, nt_tag, std::integral_constant<int, 1>());
+    if constexpr (SKIPNA && MAXK == 0)
+      return smm::fail_msg(SMM_ERR_INTERNAL, "SMM_APPLY_SKIPNA reached the streamed-link tile form");   // refused above
+    else
+      return go3(k_tag, np_tag, nt_tag, std::integral_constant<int, 1>());
   };
   auto with_k = [&](auto fn) -> int {  // plan shape 0 <-> 4 waves (rows of <= 16 links), shape 1.. <-> 1 wave
     if (!tile_which) {
@@ -254,7 +274,7 @@ int launch_tile(const ApplyArgs& a, int64_t n_lev, int tile_which, int64_t max_c
 
 // Batch-fastest layout (kernel C).  TD destination rows per tile: 16 doubles = one 128-B line of Y
 // per batch row; f32 output takes 32 rows for the same line.
-template <typename XT, typename YT>
+template <typename XT, typename YT, bool SKIPNA>
 int launch_sb(const SbArgs& a, bool fill, unsigned flags, hipStream_t s) {
   SbArgs args = a;
   constexpr int TD = sizeof(YT) == 8 ? 16 : 32;
@@ -276,13 +296,13 @@ int launch_sb(const SbArgs& a, bool fill, unsigned flags, hipStream_t s) {
     constexpr int UU = decltype(u_tag)::value;
     constexpr bool FF = decltype(fill_tag)::value;
     if (ysb)
-      hipLaunchKernelGGL((smm_apply_sb_kernel<XT, YT, TD, UU, FF, true>), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
+      hipLaunchKernelGGL((smm_apply_sb_kernel<XT, YT, TD, UU, FF, true, SKIPNA>), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
     else
-      hipLaunchKernelGGL((smm_apply_sb_kernel<XT, YT, TD, UU, FF>), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
+      hipLaunchKernelGGL((smm_apply_sb_kernel<XT, YT, TD, UU, FF, false, SKIPNA>), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
   };
-  auto with_fill = [&](auto u_tag) {
-    if (fill) go(u_tag, std::true_type());
-    else go(u_tag, std::false_type());
+  auto with_fill = [&](auto u_tag) {   // SKIPNA tests the raw values itself (SMM_APPLY_NO_FILL is refused with it)
+    if (fill || SKIPNA) go(u_tag, std::true_type());
+    else if constexpr (!SKIPNA) go(u_tag, std::false_type());
   };
   if (smm::tuning(SMM_TUNE_SB_LOADS) == 4) with_fill(std::integral_constant<int, 4>());   // tuning: 4 loads per batch instead of 8
   else with_fill(std::integral_constant<int, 8>());
@@ -292,7 +312,7 @@ int launch_sb(const SbArgs& a, bool fill, unsigned flags, hipStream_t s) {
 
 // The batch-fastest kernel over the data levels of a group in ONE launch (smm_group_apply_sb): grid = levels x
 // (destination tiles x batch tiles); the caller has filled a.lev[0 .. n_lev) and the per-level strides.
-template <typename XT, typename YT>
+template <typename XT, typename YT, bool SKIPNA>
 int launch_sb_group(const SbGroupArgs& a, bool fill, unsigned flags, hipStream_t s) {
   SbGroupArgs args = a;
   constexpr int TD = sizeof(YT) == 8 ? 16 : 32;
@@ -311,13 +331,13 @@ int launch_sb_group(const SbGroupArgs& a, bool fill, unsigned flags, hipStream_t
     constexpr int UU = decltype(u_tag)::value;
     constexpr bool FF = decltype(fill_tag)::value;
     if (ysb)
-      hipLaunchKernelGGL((smm_group_apply_sb_kernel<XT, YT, TD, UU, FF, true>), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
+      hipLaunchKernelGGL((smm_group_apply_sb_kernel<XT, YT, TD, UU, FF, true, SKIPNA>), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
     else
-      hipLaunchKernelGGL((smm_group_apply_sb_kernel<XT, YT, TD, UU, FF>), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
+      hipLaunchKernelGGL((smm_group_apply_sb_kernel<XT, YT, TD, UU, FF, false, SKIPNA>), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
   };
-  auto with_fill = [&](auto u_tag) {
-    if (fill) go(u_tag, std::true_type());
-    else go(u_tag, std::false_type());
+  auto with_fill = [&](auto u_tag) {   // SKIPNA tests the raw values itself (SMM_APPLY_NO_FILL is refused with it)
+    if (fill || SKIPNA) go(u_tag, std::true_type());
+    else if constexpr (!SKIPNA) go(u_tag, std::false_type());
   };
   if (smm::tuning(SMM_TUNE_SB_LOADS) == 4) with_fill(std::integral_constant<int, 4>());
   else with_fill(std::integral_constant<int, 8>());

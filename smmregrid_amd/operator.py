@@ -168,16 +168,18 @@ class SparseOperator:
         return out
 
     def apply(self, x, y=None, masked=False, remap_area_min=0.0, out_dtype=np.float64,
-              flags=0, stream=None, keep_batch_fastest=False):
+              flags=0, stream=None, keep_batch_fastest=False, skipna=False):
         """Y = epilogue(fill(X) . W) for a device-resident X of shape (B, S), or (B, ldx) with a
         padded row pitch ldx >= S (rows that start on 128-B lines are staged without straddling).
         A field tagged batch-fastest (`x.layout == "sb"`, shape (S, B)) goes through the batch-fastest
-        kernel (`apply_sb`); with keep_batch_fastest the result stays batch-fastest too, (D, B)."""
+        kernel (`apply_sb`); with keep_batch_fastest the result stays batch-fastest too, (D, B).
+        skipna: non-finite source values drop out of each batch row's sums and the row is renormalised over
+        the valid weight (SMM_APPLY_SKIPNA; rows without one are bit-identical to the plain apply)."""
         if not isinstance(x, DeviceArray):
             raise TypeError("SparseOperator.apply takes a DeviceArray (use Regridder for host data)")
         if x.layout == "sb":
             return self.apply_sb(x, y=y, masked=masked, remap_area_min=remap_area_min, out_dtype=out_dtype,
-                                 flags=flags, stream=stream, keep_batch_fastest=keep_batch_fastest)
+                                 flags=flags, skipna=skipna, stream=stream, keep_batch_fastest=keep_batch_fastest)
         if keep_batch_fastest:
             raise ValueError("keep_batch_fastest needs a batch-fastest field (DeviceArray(..., layout='sb'))")
         if x.ndim != 2 or x.shape[1] < self.n_src:
@@ -187,7 +189,7 @@ class SparseOperator:
             y = DeviceArray((n_batch, self.n_dst), out_dtype)
         elif y.shape != (n_batch, self.n_dst):
             raise ValueError(f"Y must be ({n_batch}, {self.n_dst}), got {y.shape}")
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
         _lib.call("smm_apply", self.handle, ctypes.c_void_p(x.ptr), dtype_code(x.dtype),
                   x.shape[1], ctypes.c_void_p(y.ptr), dtype_code(y.dtype), self.n_dst, n_batch,
                   float(remap_area_min), fl, _stream_handle(stream))
@@ -206,7 +208,7 @@ class SparseOperator:
         return self
 
     def apply_sb(self, x, y=None, masked=False, remap_area_min=0.0, packed=False, out_dtype=np.float64,
-                 flags=0, stream=None, keep_batch_fastest=False, n_batch=None):
+                 flags=0, stream=None, keep_batch_fastest=False, n_batch=None, skipna=False):
         """The same product for a device-resident field kept batch-fastest: x of shape (S, B) -- or
         (n_used_src, B) with packed=True, rows in `used_sources()` order -- holds the B batch values
         of each source cell contiguously.  Y is (B, D) as `apply` returns it, bit-identical to
@@ -230,7 +232,8 @@ class SparseOperator:
             y = DeviceArray(y_shape, out_dtype, layout="sb" if keep_batch_fastest else "bs")
         elif y.shape != y_shape:
             raise ValueError(f"Y must be {y_shape}, got {y.shape}")
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SB_PACKED if packed else 0)
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        fl |= _lib.APPLY_SB_PACKED if packed else 0
         if keep_batch_fastest:
             fl |= _lib.APPLY_SB_Y_SB
         _lib.call("smm_apply_sb", self.handle, ctypes.c_void_p(x.ptr), dtype_code(x.dtype), max(ldx, 1),
@@ -239,7 +242,7 @@ class SparseOperator:
         return y
 
     def apply_host(self, x, out=None, masked=False, remap_area_min=0.0, out_dtype=np.float64,
-                   flags=0, chunk_rows=0):
+                   flags=0, chunk_rows=0, skipna=False):
         """Same product for a host (numpy) array of shape (B, S): the rows stream through the
         library's double-buffered H2D / kernel / D2H pipeline (smm_apply_host).  Arrays from
         `pinned_empty` are DMA'd without staging copies.  Returns a (B, D) numpy array."""
@@ -255,7 +258,7 @@ class SparseOperator:
             out = result_cache.empty((n_batch, self.n_dst), out_dtype)      # page-locked and recycled when large
         if out.shape != (n_batch, self.n_dst) or not out.flags.c_contiguous:
             raise ValueError(f"out must be a C-contiguous ({n_batch}, {self.n_dst}) array")
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
         _lib.call("smm_apply_host", self.handle, _cptr(x), dtype_code(x.dtype),
                   x.strides[0] // x.itemsize if n_batch > 1 else max(self.n_src, 1),
                   _cptr(out), dtype_code(out.dtype), self.n_dst, n_batch, float(remap_area_min), fl,
@@ -327,7 +330,7 @@ class OperatorGroup:
                             (int(n_outer), int(n_lev), int(n_inner)), flags)
 
     def apply(self, x, level_index, masked_levels=None, y=None, masked=False, remap_area_min=0.0,
-              transpose=True, out_dtype=np.float64, flags=0, stream=None):
+              transpose=True, out_dtype=np.float64, flags=0, stream=None, skipna=False):
         """x: DeviceArray (n_outer, n_lev, n_inner, S) -- or (..., ldx) with a padded row pitch ldx >= S.  Returns
         (n_outer, n_inner, n_lev, D) when transpose (regrid.py:420-427) else
         (n_lev, n_outer, n_inner, D) (the concat order, regrid.py:410)."""
@@ -349,7 +352,7 @@ class OperatorGroup:
         elif y.shape != shape:
             raise ValueError(f"Y must be {shape}, got {y.shape}")
         xs = (n_lev * n_inner * S, n_inner * S, S)
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
         _lib.call("smm_group_apply", self.handle, ctypes.c_void_p(x.ptr), dtype_code(x.dtype),
                   xs[0], xs[1], xs[2], ctypes.c_void_p(y.ptr), dtype_code(y.dtype),
                   ys[0], ys[1], ys[2], n_outer, n_lev, n_inner, _cptr(lev), _cptr(ml),
@@ -357,7 +360,8 @@ class OperatorGroup:
         return y
 
     def apply_sb(self, x, level_index, masked_levels=None, y=None, masked=False, remap_area_min=0.0,
-                 transpose=True, out_dtype=np.float64, flags=0, stream=None, keep_batch_fastest=False, n_batch=None):
+                 transpose=True, out_dtype=np.float64, flags=0, stream=None, keep_batch_fastest=False, n_batch=None,
+                 skipna=False):
         """Masked levels for a field kept batch-fastest per level: x is a DeviceArray (n_lev, S, B) --
         per data level the B batch values of each source cell contiguous.  Returns (B, n_lev, D) when
         transpose (regrid.py:420-427) else (n_lev, B, D); bit-identical to `apply` on the transposed field.
@@ -381,14 +385,15 @@ class OperatorGroup:
             y = DeviceArray(shape, out_dtype, layout="sb" if keep_batch_fastest else "bs")
         elif y.shape != shape:
             raise ValueError(f"Y must be {shape}, got {y.shape}")
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SB_Y_SB if keep_batch_fastest else 0)
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        fl |= _lib.APPLY_SB_Y_SB if keep_batch_fastest else 0
         _lib.call("smm_group_apply_sb", self.handle, ctypes.c_void_p(x.ptr), dtype_code(x.dtype), S * max(ldx, 1),
                   max(ldx, 1), ctypes.c_void_p(y.ptr), dtype_code(y.dtype), ys_lev, ys_b, B, n_lev, _cptr(lev),
                   _cptr(ml), float(remap_area_min), fl, _stream_handle(stream))
         return y
 
     def apply_host(self, x, level_index, masked_levels=None, masked=False, remap_area_min=0.0,
-                   transpose=True, out_dtype=np.float64, flags=0, chunk_outer=0):
+                   transpose=True, out_dtype=np.float64, flags=0, chunk_outer=0, skipna=False):
         """Host (numpy) variant: x of shape (n_outer, n_lev, n_inner, S); chunks of the outer
         axis stream through the group's H2D / kernel / D2H pipeline (smm_group_apply_host)."""
         x = np.asarray(x)
@@ -401,7 +406,7 @@ class OperatorGroup:
         lev, ml = self._level_args(level_index, masked_levels, n_lev)
         shape = (n_outer, n_inner, n_lev, self.n_dst) if transpose else (n_lev, n_outer, n_inner, self.n_dst)
         out = result_cache.empty(shape, out_dtype)
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
         _lib.call("smm_group_apply_host", self.handle, _cptr(x), dtype_code(x.dtype), _cptr(out),
                   dtype_code(out.dtype), n_outer, n_lev, n_inner, int(bool(transpose)), _cptr(lev),
                   _cptr(ml), float(remap_area_min), fl, int(chunk_outer))

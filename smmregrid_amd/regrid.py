@@ -55,7 +55,7 @@ class Regridder(object):
                  method='con', remap_area_min=DEFAULT_AREA_MIN, transpose=True, mask_dim=None,
                  vertical_dim=None, horizontal_dims=None, cdo_extra=None, cdo_options=None,
                  check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=np.float64,
-                 lazy=False, prune_zero_weights=False, keep_batch_fastest=False):
+                 lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -78,6 +78,10 @@ class Regridder(object):
         # keep_batch_fastest the result stays in that layout too -- (lat, lon, time) on the target grid,
         # HBM-resident -- so a second Regridder consumes it without a transpose.
         self.keep_batch_fastest = bool(keep_batch_fastest)
+        # skipna: each time step's non-finite source values drop out of every sum they touch and the rest is
+        # renormalised -- the weights regenerated with that step's validity as source mask (SMM_APPLY_SKIPNA);
+        # remap_area_min then thresholds the valid fraction of each target cell
+        self.skipna = bool(skipna)
         # the reference always yields float64 (result_type(x, f64)); float32 is an opt-in narrowing store
         self.out_dtype = np.dtype(out_dtype)
         if self.out_dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -353,7 +357,7 @@ class Regridder(object):
         masked = bool(np.asarray(masked).any()) if np.ndim(masked) else bool(masked)
 
         src = source_data.data
-        area_min, out_dtype = self.remap_area_min, self.out_dtype
+        area_min, out_dtype, skipna = self.remap_area_min, self.out_dtype, self.skipna
         sb_in = isinstance(src, DeviceArray) and src.layout == "sb"
         if sb_in:
             n_h = len(source_data.dims) - len(kept_dims)
@@ -376,7 +380,7 @@ class Regridder(object):
             host = np.ascontiguousarray(host)
             if host.shape[1] != op.n_src:
                 raise ValueError(f"source grid has {host.shape[1]} cells, weights expect {op.n_src}")
-            return op.apply_host(host, masked=masked, remap_area_min=area_min, out_dtype=out_dtype)
+            return op.apply_host(host, masked=masked, remap_area_min=area_min, out_dtype=out_dtype, skipna=skipna)
 
         def compute():
             if sb_in:
@@ -384,13 +388,13 @@ class Regridder(object):
                 if x.shape[0] != op.n_src:
                     raise ValueError(f"source grid has {x.shape[0]} cells, weights expect {op.n_src}")
                 y = op.apply(x, masked=masked, remap_area_min=area_min, out_dtype=out_dtype,
-                             keep_batch_fastest=sb_out)
+                             keep_batch_fastest=sb_out, skipna=skipna)
                 return y.reshape(*out_shape)
             if isinstance(src, DeviceArray):
                 x = src.reshape(n_batch, -1)
                 if x.shape[1] != op.n_src:
                     raise ValueError(f"source grid has {x.shape[1]} cells, weights expect {op.n_src}")
-                y = op.apply(x, masked=masked, remap_area_min=area_min, out_dtype=out_dtype)
+                y = op.apply(x, masked=masked, remap_area_min=area_min, out_dtype=out_dtype, skipna=skipna)
                 return y.reshape(*(kept_shape + tgt_shape))
             host = src.compute() if isinstance(src, LazyArray) else np.asarray(src)
             return apply_rows(host.reshape(n_batch, -1)).reshape(kept_shape + tgt_shape)
@@ -458,6 +462,7 @@ class Regridder(object):
         src = source_data.data
         S, D = group.n_src, group.n_dst
         area_min, out_dtype, transpose = self.remap_area_min, self.out_dtype, self.transpose
+        skipna = self.skipna
         sb_in = isinstance(src, DeviceArray) and src.layout == "sb"
         if sb_in:
             # batch-fastest per level: (mask_dim, horizontal..., everything else...)
@@ -479,12 +484,12 @@ class Regridder(object):
                 if x.shape[1] != S:
                     raise ValueError(f"source grid has {x.shape[1]} cells, weights expect {S}")
                 y = group.apply_sb(x, level_index, masked_levels, masked=any_masked, remap_area_min=area_min,
-                                   transpose=transpose, out_dtype=out_dtype, keep_batch_fastest=sb_out)
+                                   transpose=transpose, out_dtype=out_dtype, keep_batch_fastest=sb_out, skipna=skipna)
                 return y.reshape(*out_shape)
             if isinstance(src, DeviceArray):
                 x = src.reshape(n_outer, n_lev, n_inner, -1)
                 y = group.apply(x, level_index, masked_levels, masked=any_masked, remap_area_min=area_min,
-                                transpose=transpose, out_dtype=out_dtype)
+                                transpose=transpose, out_dtype=out_dtype, skipna=skipna)
                 return y.reshape(*out_shape)
             host = src.compute() if isinstance(src, LazyArray) else np.asarray(src)   # a dask field is computed here
             if host.dtype not in (np.float32, np.float64):
@@ -494,7 +499,7 @@ class Regridder(object):
                 raise ValueError(f"source grid has {host.shape[3]} cells, weights expect {S}")
             # host field: chunks of the outer axis stream through the group's pipeline
             out = group.apply_host(host, level_index, masked_levels, masked=any_masked, remap_area_min=area_min,
-                                   transpose=transpose, out_dtype=out_dtype)
+                                   transpose=transpose, out_dtype=out_dtype, skipna=skipna)
             return out.reshape(out_shape)
 
         out_data = LazyArray(out_shape, out_dtype, compute) if self.lazy else compute()
