@@ -54,8 +54,24 @@ enum {
 /* element types of the dense field buffers */
 enum {
   SMM_F32 = 0,
-  SMM_F64 = 1
+  SMM_F64 = 1,
+  SMM_I16 = 2,  /* CF-packed fields, X only, through the _cf entries below (every other entry: SMM_ERR_UNSUPPORTED) */
+  SMM_U16 = 3
 };
+
+/* CF "packed data" (scale_factor / add_offset / _FillValue / missing_value): how a raw int16 / uint16 element q
+ * becomes a field value, with T = float (decode_dtype SMM_F32) or double (SMM_F64):
+ *     v = (T)q;  v = v * (T)scale;  v = v + (T)offset;        two rounded operations, never an FMA
+ *     if (q == fill[0] || q == fill[1])  v = NaN;              the first n_fill entries, compared on the raw integer
+ * v then takes the place of an element of a T-typed field (1e20 fill of non-finite values, SMM_APPLY_SKIPNA
+ * validity, ...): the results are bit-identical to decoding on the host in type T and calling the plain entry with
+ * the same flags.  An absent scale / offset is 1 / 0.  Fill values must be representable in the raw type. */
+typedef struct smm_cf_decode_t {
+  double scale, offset;
+  int32_t fill[2];
+  int n_fill;        /* 0, 1 or 2 */
+  int decode_dtype;  /* SMM_F32 or SMM_F64 */
+} smm_cf_decode_t;
 
 /* smm_apply flags.  Bits outside this set are refused with SMM_ERR_INVALID by every entry that takes `flags`
  * (ABI <= 4 encoded kernel variants in bits 16..23: those are smm_debug_set_tuning knobs now). */
@@ -205,7 +221,9 @@ int smm_operator_plan_info(smm_operator_t op, int* kernel_kind, int64_t* lds_byt
  * The answer assumes a field whose base, row pitch and strides are multiples of 16 B (what the LDS-DMA
  * staging needs): smm_apply checks the real field and falls back from kernel 2 to kernel 1 (with that
  * kernel's rows_per_step / lds_bytes) when it is not.  n_blocks is the whole batch; beyond 2^31 - 1
- * workgroups smm_apply launches it in parts.  Any out pointer may be NULL. */
+ * workgroups smm_apply launches it in parts.  Any out pointer may be NULL.
+ * x_dtype SMM_I16 / SMM_U16 answers for smm_apply_cf: packed fields always run kernel 0 (the LDS tile kernel is
+ * not built for 2-byte elements), whatever the operator's plan; with SMM_APPLY_KERNEL_TILE: SMM_ERR_UNSUPPORTED. */
 int smm_operator_launch_info(smm_operator_t op, int x_dtype, int64_t n_batch, unsigned flags,
                              int* kernel, int* j_per_block, int* rows_per_step, int* rows_per_block,
                              int64_t* n_blocks, int64_t* lds_bytes, int* big_operator);
@@ -281,6 +299,32 @@ int smm_apply_host(smm_operator_t op,
                    const void* x_host, int x_dtype, int64_t ldx,
                    void* y_host, int y_dtype, int64_t ldy,
                    int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows);
+
+/*
+ * The three entries above for CF-packed fields: x_dtype SMM_I16 / SMM_U16, x holds the raw 2-byte integers (2-byte
+ * aligned, ldx in elements) and is decoded inside the kernels by *cf (smm_cf_decode_t above) -- a quarter of the
+ * bytes of an f64 field in HBM, over PCIe and through the host pack.  y_dtype must be SMM_F64 (SMM_F32 results are
+ * not built: SMM_ERR_UNSUPPORTED).  cf == NULL with a float x_dtype is the plain entry; cf == NULL with an integer
+ * x_dtype, cf != NULL with a float one, a fill value outside the raw type, or SMM_APPLY_NO_FILL with n_fill > 0 (the
+ * decode makes NaN) are SMM_ERR_INVALID.  MASKED, SKIPNA, HOST_NO_PACK, SB_PACKED, SB_Y_SB and KERNEL_SELL work as
+ * for float fields; smm_apply_cf runs the SELL kernel whatever the operator's plan (smm_operator_launch_info says
+ * so) and SMM_APPLY_KERNEL_TILE is SMM_ERR_UNSUPPORTED.  Level groups take no packed input.
+ */
+int smm_apply_cf(smm_operator_t op,
+                 const void* x, int x_dtype, int64_t ldx,
+                 void* y, int y_dtype, int64_t ldy,
+                 int64_t n_batch, double remap_area_min, unsigned flags, void* stream,
+                 const smm_cf_decode_t* cf);
+int smm_apply_sb_cf(smm_operator_t op,
+                    const void* x, int x_dtype, int64_t ldx,
+                    void* y, int y_dtype, int64_t ldy,
+                    int64_t n_batch, double remap_area_min, unsigned flags, void* stream,
+                    const smm_cf_decode_t* cf);
+int smm_apply_host_cf(smm_operator_t op,
+                      const void* x_host, int x_dtype, int64_t ldx,
+                      void* y_host, int y_dtype, int64_t ldy,
+                      int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows,
+                      const smm_cf_decode_t* cf);
 
 /*
  * Masked-level apply (regrid.py:387-418 in one launch).  The kept dims of the
@@ -368,6 +412,8 @@ enum {
   SMM_HOST_STAT_WAIT_MS,
   SMM_HOST_STAT_TOTAL_MS,
   SMM_HOST_STAT_THREADS,   /* staging threads in force at the last call (count) */
+  SMM_HOST_STAT_H2D_BYTES, /* bytes queued host -> device (X as shipped: packed or whole rows, 2 B per cell of a packed field) */
+  SMM_HOST_STAT_D2H_BYTES, /* bytes queued device -> host (Y) */
   SMM_HOST_STAT_COUNT
 };
 int smm_debug_host_stats(double* out, int n, int reset);

@@ -20,6 +20,8 @@ SMM_ERR_INTERNAL = 6
 
 SMM_F32 = 0
 SMM_F64 = 1
+SMM_I16 = 2     # CF-packed fields: the _cf entries only
+SMM_U16 = 3
 
 APPLY_MASKED = 1 << 0
 APPLY_NO_FILL = 1 << 1
@@ -58,6 +60,16 @@ _int = ctypes.c_int
 _dbl = ctypes.c_double
 _uint = ctypes.c_uint
 _size = ctypes.c_size_t
+
+
+
+class CfDecodeStruct(ctypes.Structure):
+    """smm_cf_decode_t"""
+    _fields_ = [("scale", _dbl), ("offset", _dbl), ("fill", ctypes.c_int32 * 2), ("n_fill", _int),
+                ("decode_dtype", _int)]
+
+
+_cfp = ctypes.POINTER(CfDecodeStruct)
 
 # name -> argtypes; every entry point returns int status except the two noted
 SIGNATURES = {
@@ -112,6 +124,9 @@ SIGNATURES = {
     "smm_operator_used_sources": [_p, _p],
     "smm_apply_sb": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _p],
     "smm_apply_host": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _i64],
+    "smm_apply_cf": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _p, _cfp],
+    "smm_apply_sb_cf": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _p, _cfp],
+    "smm_apply_host_cf": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _i64, _cfp],
     "smm_group_apply": [_p, _p, _int, _i64, _i64, _i64, _p, _int, _i64, _i64, _i64,
                         _i64, _i64, _i64, _p, _p, _dbl, _uint, _p],
     "smm_group_prepare_sb": [_p],
@@ -196,7 +211,7 @@ def device_count():
 
 
 HOST_STATS = ("calls", "chunks", "stage_in_ms", "h2d_ms", "kernel_ms", "d2h_ms", "copy_out_ms", "wait_ms", "total_ms",
-              "threads")
+              "threads", "h2d_bytes", "d2h_bytes")
 
 
 def host_stats(reset=False):

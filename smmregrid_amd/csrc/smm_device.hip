@@ -55,6 +55,19 @@ SMM_EXTERN_PAIR(double, float, true)
 SMM_EXTERN_PAIR(float, double, true)
 SMM_EXTERN_PAIR(float, float, true)
 #undef SMM_EXTERN_PAIR
+// CF-packed 16-bit X (PackedX<raw, decode type>): kernels A and C, f64 results
+#define SMM_EXTERN_PACKED(Q, T, NA)                                                                             \
+  extern template int launch_sell<PackedX<Q, T>, double, NA>(const ApplyArgs&, int64_t, bool, unsigned, hipStream_t); \
+  extern template int launch_sb<PackedX<Q, T>, double, NA>(const SbArgs&, bool, unsigned, hipStream_t);
+SMM_EXTERN_PACKED(int16_t, float, false)
+SMM_EXTERN_PACKED(int16_t, double, false)
+SMM_EXTERN_PACKED(uint16_t, float, false)
+SMM_EXTERN_PACKED(uint16_t, double, false)
+SMM_EXTERN_PACKED(int16_t, float, true)
+SMM_EXTERN_PACKED(int16_t, double, true)
+SMM_EXTERN_PACKED(uint16_t, float, true)
+SMM_EXTERN_PACKED(uint16_t, double, true)
+#undef SMM_EXTERN_PACKED
 }  // namespace smm_launch
 
 // FN<XT, YT, SKIPNA>(...) for the run-time dtypes (SMM_F64 / SMM_F32) and SMM_APPLY_SKIPNA
@@ -65,6 +78,16 @@ SMM_EXTERN_PAIR(float, float, true)
   (((FLAGS) & SMM_APPLY_SKIPNA) ? SMM_DISPATCH_NA(FN, true, XD, YD, __VA_ARGS__) \
                                 : SMM_DISPATCH_NA(FN, false, XD, YD, __VA_ARGS__))
 
+// FN<PackedX<raw, decode type>, double, SKIPNA>(...) for packed X (SMM_I16 / SMM_U16) decoded to DD (SMM_F32 / SMM_F64)
+#define SMM_DISPATCH_CF_NA(FN, NA, XD, DD, ...)                                                       \
+  ((XD) == SMM_I16 ? ((DD) == SMM_F64 ? FN<PackedX<int16_t, double>, double, NA>(__VA_ARGS__)         \
+                                      : FN<PackedX<int16_t, float>, double, NA>(__VA_ARGS__))         \
+                   : ((DD) == SMM_F64 ? FN<PackedX<uint16_t, double>, double, NA>(__VA_ARGS__)        \
+                                      : FN<PackedX<uint16_t, float>, double, NA>(__VA_ARGS__)))
+#define SMM_DISPATCH_CF(FN, FLAGS, XD, DD, ...)                                        \
+  (((FLAGS) & SMM_APPLY_SKIPNA) ? SMM_DISPATCH_CF_NA(FN, true, XD, DD, __VA_ARGS__)    \
+                                : SMM_DISPATCH_CF_NA(FN, false, XD, DD, __VA_ARGS__))
+
 namespace {
 
 thread_local std::string g_last_error;
@@ -72,6 +95,26 @@ thread_local std::string g_last_error;
 int fail(int code, const std::string& msg) {
   g_last_error = msg;
   return code;
+}
+
+inline bool is_float_dtype(int d) { return d == SMM_F32 || d == SMM_F64; }
+inline bool is_packed_dtype(int d) { return d == SMM_I16 || d == SMM_U16; }
+inline size_t dtype_size(int d) { return d == SMM_F64 ? 8 : (d == SMM_F32 ? 4 : 2); }
+
+// A validated smm_cf_decode_t as the kernels take it (null = a float field, the plain entries)
+struct CfCall {
+  CfParams p;
+  int decode_dtype;
+};
+// X dtype check shared by the apply paths: float always, packed only through the _cf entries
+inline int check_x_dtype(int x_dtype, int y_dtype, const CfCall* cf) {
+  if (!(is_float_dtype(x_dtype) || (cf && is_packed_dtype(x_dtype))) || !is_float_dtype(y_dtype))
+    return fail(SMM_ERR_UNSUPPORTED, is_packed_dtype(x_dtype)
+                                         ? "SMM_I16 / SMM_U16 fields go through the _cf entries (smm_apply_cf, ...)"
+                                         : "field dtype must be SMM_F32 or SMM_F64");
+  if (cf && is_packed_dtype(x_dtype) && y_dtype != SMM_F64)
+    return fail(SMM_ERR_UNSUPPORTED, "packed fields produce SMM_F64 results (y_dtype SMM_F32 is not built)");
+  return SMM_OK;
 }
 
 }  // namespace
@@ -390,12 +433,14 @@ int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t*
               int64_t max_row_nnz, const void* x, int x_dtype, int64_t xs_o, int64_t xs_l,
               int64_t xs_i, void* y, int y_dtype, int64_t ys_o, int64_t ys_l, int64_t ys_i,
               int64_t n_outer, int64_t n_lev, int64_t n_inner, double area_min, unsigned flags,
-              hipStream_t s, LaunchInfo* info_only = nullptr) {
+              hipStream_t s, LaunchInfo* info_only = nullptr, const CfCall* cf = nullptr) {
   if (n_outer < 0 || n_lev < 0 || n_inner < 0) return fail(SMM_ERR_INVALID, "negative batch size");
   if (n_outer == 0 || n_lev == 0 || n_inner == 0 || n_dst == 0) return SMM_OK;
   if (!info_only && (!x || !y)) return fail(SMM_ERR_INVALID, "null field pointer");
-  if ((x_dtype != SMM_F32 && x_dtype != SMM_F64) || (y_dtype != SMM_F32 && y_dtype != SMM_F64))
-    return fail(SMM_ERR_UNSUPPORTED, "field dtype must be SMM_F32 or SMM_F64");
+  const bool packed = is_packed_dtype(x_dtype);
+  static const CfCall kInfoCf{{1.0, 0.0, 0x7fffffff, 0x7fffffff}, SMM_F32};   // launch info: the geometry does not depend on it
+  if (packed && info_only && !cf) cf = &kInfoCf;
+  if (int drc = check_x_dtype(x_dtype, y_dtype, cf)) return drc;
   if (!(area_min >= 0.0 && area_min <= 1.0))
     return fail(SMM_ERR_INVALID, "remap_area_min must be within [0, 1]");  // regrid.py:124-125
 
@@ -419,13 +464,19 @@ int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t*
   a.area_min = area_min;
   a.masked = (flags & SMM_APPLY_MASKED) ? 1 : 0;
   const bool fill = !(flags & SMM_APPLY_NO_FILL);
+  if (packed) a.cf = cf->p;
 
-  const size_t xsz = x_dtype == SMM_F64 ? 8 : 4;
+  const size_t xsz = dtype_size(x_dtype);
   bool use_tile = false;
   // SMM_APPLY_SKIPNA: tile forms without a skipna variant (split rows, rows streamed from L2) run kernel A instead
   const bool tile_skipna_ok = !(flags & SMM_APPLY_SKIPNA) ||
                               smm_launch::tile_has_skipna(tile_which, tile_which >= 2 ? tile_which - 1 : 0, max_row_nnz);
-  if (flags & SMM_APPLY_KERNEL_TILE) {
+  if (packed) {
+    // the LDS tile kernel stages 16-B pieces of 4- or 8-byte elements: packed X runs kernel A whatever the plan
+    if (flags & SMM_APPLY_KERNEL_TILE)
+      return fail(SMM_ERR_UNSUPPORTED, "the LDS tile kernel is not built for packed fields (SMM_I16 / SMM_U16)");
+    if (!info_only && ((uintptr_t)x % 2) != 0) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
+  } else if (flags & SMM_APPLY_KERNEL_TILE) {
     if (!tile_ok) return fail(SMM_ERR_UNSUPPORTED, "operator has no LDS tile plan");
     if (!tile_skipna_ok)
       return fail(SMM_ERR_UNSUPPORTED, "SMM_APPLY_SKIPNA: the planned tile form (split or streamed rows) has no skipna variant");
@@ -487,6 +538,7 @@ int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t*
     p.y = (char*)y + (o0 * ys_o + i0 * ys_i) * (int64_t)ysz;
     p.n_j = n_o * n_i;
     p.n_inner = n_i;
+    if (packed) return SMM_DISPATCH_CF(launch_sell, flags, x_dtype, cf->decode_dtype, p, n_lev, fill, flags, s);
     if (use_tile)
       return SMM_DISPATCH(launch_tile, p, n_lev, tile_which, tile_max_chunks, max_row_nnz, tile_flags, fill, flags, s);
     return SMM_DISPATCH(launch_sell, p, n_lev, fill, flags, s);
@@ -1058,7 +1110,8 @@ static int smm_operator_plan_info_impl(smm_operator_t op, int* kernel_kind, int6
 }
 
 static int smm_apply_impl(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype,
-              int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream) {
+              int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream,
+              const CfCall* cf = nullptr) {
   if (int frc = check_flags(flags)) return frc;
   if (!op) return fail(SMM_ERR_INVALID, "null operator");
   if (n_batch > 0 && (ldx < op->csr.n_src || ldy < op->csr.n_dst))
@@ -1073,7 +1126,7 @@ static int smm_apply_impl(smm_operator_t op, const void* x, int x_dtype, int64_t
   const smm_operator::TilePlan& pl = op->plan[pw];
   return run_apply(op->d_desc, nullptr, nullptr, op->csr.n_src, op->csr.n_dst, pw, pl.valid,
                    pl.preferred, (pl.reuse ? 1 : 0), pl.max_chunks, op->csr.max_row_nnz, x, x_dtype, ldx, 0, 0, y, y_dtype, ldy,
-                   0, 0, n_batch, 1, 1, remap_area_min, flags, (hipStream_t)stream);
+                   0, 0, n_batch, 1, 1, remap_area_min, flags, (hipStream_t)stream, nullptr, cf);
 }
 
 static int smm_operator_prepare_sb_impl(smm_operator_t op) {
@@ -1095,14 +1148,15 @@ static int smm_operator_used_sources_impl(smm_operator_t op, int32_t* used) {
 }
 
 static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype,
-                 int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream) {
+                 int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream,
+                 const CfCall* cf = nullptr) {
   if (int frc = check_flags(flags)) return frc;
   if (!op) return fail(SMM_ERR_INVALID, "null operator");
   if (n_batch < 0) return fail(SMM_ERR_INVALID, "negative batch size");
   if (n_batch == 0 || op->csr.n_dst == 0) return SMM_OK;
   if (!x || !y) return fail(SMM_ERR_INVALID, "null field pointer");
-  if ((x_dtype != SMM_F32 && x_dtype != SMM_F64) || (y_dtype != SMM_F32 && y_dtype != SMM_F64))
-    return fail(SMM_ERR_UNSUPPORTED, "field dtype must be SMM_F32 or SMM_F64");
+  if (int drc = check_x_dtype(x_dtype, y_dtype, cf)) return drc;
+  const bool packed = is_packed_dtype(x_dtype);
   if (ldx < n_batch || ldy < ((flags & SMM_APPLY_SB_Y_SB) ? n_batch : op->csr.n_dst))
     return fail(SMM_ERR_INVALID, "ldx smaller than the batch or ldy smaller than a row of Y");
   if (!(remap_area_min >= 0.0 && remap_area_min <= 1.0))
@@ -1111,7 +1165,7 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int6
     return fail(SMM_ERR_INVALID, "masked apply requested but the operator has no dst_imask");
   if (remap_area_min > 0.0 && !op->d_frac)
     return fail(SMM_ERR_INVALID, "remap_area_min > 0 requested but the operator has no dst_frac");
-  const size_t xsz = x_dtype == SMM_F64 ? 8 : 4, ysz = y_dtype == SMM_F64 ? 8 : 4;
+  const size_t xsz = dtype_size(x_dtype), ysz = dtype_size(y_dtype);
   if ((uintptr_t)x % xsz || (uintptr_t)y % ysz) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
   DeviceGuard guard(op->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
@@ -1131,6 +1185,7 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int6
   a.n_dst = op->csr.n_dst;
   a.area_min = remap_area_min;
   a.masked = (flags & SMM_APPLY_MASKED) ? 1 : 0;
+  if (packed) a.cf = cf->p;
   const bool fill = !(flags & SMM_APPLY_NO_FILL);
   hipStream_t s = (hipStream_t)stream;
   // grid = destination tiles x batch tiles of 128 entries: beyond the limit the batch is cut into runs of
@@ -1144,7 +1199,8 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int6
     a.x = (const char*)x + b0 * (int64_t)xsz;
     a.y = (char*)y + ((flags & SMM_APPLY_SB_Y_SB) ? b0 : b0 * ldy) * (int64_t)ysz;
     a.n_batch = std::min(part, n_batch - b0);
-    rc = SMM_DISPATCH_ALL(launch_sb, flags, x_dtype, y_dtype, a, fill, flags, s);
+    rc = packed ? SMM_DISPATCH_CF(launch_sb, flags, x_dtype, cf->decode_dtype, a, fill, flags, s)
+                : SMM_DISPATCH_ALL(launch_sb, flags, x_dtype, y_dtype, a, fill, flags, s);
     if (rc) return rc;
   }
   return SMM_OK;
@@ -1154,20 +1210,20 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int6
 
 static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int x_dtype, int64_t ldx, void* y_host,
                    int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags,
-                   int64_t chunk_rows) {
+                   int64_t chunk_rows, const CfCall* cf = nullptr) {
   if (int frc = check_flags(flags)) return frc;
   if (!op) return fail(SMM_ERR_INVALID, "null operator");
   if (n_batch < 0) return fail(SMM_ERR_INVALID, "negative batch size");
   if (n_batch == 0 || op->csr.n_dst == 0) return SMM_OK;
   if (!x_host || !y_host) return fail(SMM_ERR_INVALID, "null field pointer");
-  if ((x_dtype != SMM_F32 && x_dtype != SMM_F64) || (y_dtype != SMM_F32 && y_dtype != SMM_F64))
-    return fail(SMM_ERR_UNSUPPORTED, "field dtype must be SMM_F32 or SMM_F64");
+  if (int drc = check_x_dtype(x_dtype, y_dtype, cf)) return drc;
+  if ((uintptr_t)x_host % dtype_size(x_dtype)) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
   const int64_t S = op->csr.n_src, D = op->csr.n_dst;
   if (ldx < S || ldy < D) return fail(SMM_ERR_INVALID, "ldx/ldy smaller than the grid size");
   DeviceGuard guard(op->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
 
-  const size_t xsz = x_dtype == SMM_F64 ? 8 : 4, ysz = y_dtype == SMM_F64 ? 8 : 4;
+  const size_t xsz = dtype_size(x_dtype), ysz = dtype_size(y_dtype);   // packed X is staged, packed and shipped raw: 2 B per cell
   const size_t xrow = (size_t)ldx * xsz, yrow = (size_t)ldy * ysz;   // host row pitches
   // device rows start on 128-B lines: the tile plan stages whole lines of a row, and a row that
   // starts mid-line makes every staged run of chunks straddle one line more (config 3's 1442x1021
@@ -1251,6 +1307,7 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int x_dtyp
       }
       SMM_HIP(hipEventRecord(pipe.ev[b][0], pipe.stream[b]));
       SMM_HIP(hipMemcpyAsync(pipe.dx[b], pipe.hx[b], (size_t)U * rows * xsz, hipMemcpyHostToDevice, pipe.stream[b]));
+      st.v[SMM_HOST_STAT_H2D_BYTES] += (double)((size_t)U * rows * xsz);
     } else if (!x_direct) {
       {
         StageTimer t(st.v[SMM_HOST_STAT_STAGE_IN_MS]);
@@ -1270,6 +1327,7 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int x_dtyp
       SMM_HIP(hipMemcpy2DAsync(pipe.dx[b], xrow_d, xsrc, xrow, (size_t)S * xsz, (size_t)rows,
                                hipMemcpyHostToDevice, pipe.stream[b]));
     }
+    if (!pack) st.v[SMM_HOST_STAT_H2D_BYTES] += (double)((size_t)S * rows * xsz);
     SMM_HIP(hipEventRecord(pipe.ev[b][1], pipe.stream[b]));
     const int pw = op->native_plan();
     const smm_operator::TilePlan& pl = op->plan[pw];
@@ -1277,13 +1335,14 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int x_dtyp
     if (pack)
       rc = smm_apply_sb_impl(op, pipe.dx[b], x_dtype, rows, pipe.dy[b], y_dtype, D, rows, remap_area_min,
                          (flags & (SMM_APPLY_MASKED | SMM_APPLY_NO_FILL | SMM_APPLY_SKIPNA)) | SMM_APPLY_SB_PACKED,
-                         pipe.stream[b]);
+                         pipe.stream[b], cf);
     else
       rc = run_apply(op->d_desc, nullptr, nullptr, S, op->csr.n_dst, pw, pl.valid, pl.preferred, (pl.reuse ? 1 : 0),
                      pl.max_chunks, op->csr.max_row_nnz, pipe.dx[b], x_dtype,
                      ldx_d, 0, 0, pipe.dy[b], y_dtype, D, 0, 0, rows, 1, 1, remap_area_min, flags,
-                     pipe.stream[b]);
+                     pipe.stream[b], nullptr, cf);
     if (rc) return rc;
+    st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)rows * D * ysz);
     SMM_HIP(hipEventRecord(pipe.ev[b][2], pipe.stream[b]));
     if (!y_direct) {
       SMM_HIP(hipMemcpyAsync(pipe.hy[b], pipe.dy[b], (size_t)rows * D * ysz, hipMemcpyDeviceToHost,
@@ -1866,6 +1925,7 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
       }
       SMM_HIP(hipEventRecord(pipe.ev[b][0], pipe.stream[b]));
       SMM_HIP(hipMemcpyAsync(pipe.dx[b], pipe.hx[b], off, hipMemcpyHostToDevice, pipe.stream[b]));
+      st.v[SMM_HOST_STAT_H2D_BYTES] += (double)off;
       SMM_HIP(hipEventRecord(pipe.ev[b][1], pipe.stream[b]));
       off = 0;
       for (int64_t ll = 0; ll < ck.nl && !rc; ++ll) {
@@ -1897,6 +1957,7 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
       SMM_HIP(hipEventRecord(pipe.ev[b][0], pipe.stream[b]));
       SMM_HIP(hipMemcpy2DAsync(pipe.dx[b], xrow_d, h2d_src, (size_t)S * xsz, (size_t)S * xsz, (size_t)rows,
                                hipMemcpyHostToDevice, pipe.stream[b]));
+      st.v[SMM_HOST_STAT_H2D_BYTES] += (double)((size_t)S * xsz * (size_t)rows);
       SMM_HIP(hipEventRecord(pipe.ev[b][1], pipe.stream[b]));
       rc = smm_group_apply(g, pipe.dx[b], x_dtype, rows_per_outer * ldx_d, n_inner * ldx_d, ldx_d,
                            pipe.dy[b], y_dtype, ys_o, ys_l, ys_i, no, n_lev, n_inner, level_index,
@@ -1904,6 +1965,7 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
     }
     if (rc) return rc;
     SMM_HIP(hipEventRecord(pipe.ev[b][2], pipe.stream[b]));
+    st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)no * n_inner * ck.nl * D * ysz);
     if (!y_direct) {
       SMM_HIP(hipMemcpyAsync(pipe.hy[b], pipe.dy[b], (size_t)no * n_inner * ck.nl * D * ysz, hipMemcpyDeviceToHost,
                              pipe.stream[b]));
@@ -1956,6 +2018,67 @@ int smm_apply_sb(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, voi
 
 int smm_apply_host(smm_operator_t op, const void* x_host, int x_dtype, int64_t ldx, void* y_host, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows) {
   return guarded([&] { return smm_apply_host_impl(op, x_host, x_dtype, ldx, y_host, y_dtype, ldy, n_batch, remap_area_min, flags, chunk_rows); });
+}
+
+}  // extern "C"
+
+namespace {
+// smm_cf_decode_t -> CfCall.  Returns SMM_OK with *use = null when the call is a plain float one (cf == NULL).
+int make_cf(const smm_cf_decode_t* cf, int x_dtype, unsigned flags, CfCall* out, const CfCall** use) {
+  *use = nullptr;
+  if (!is_packed_dtype(x_dtype)) {
+    if (cf && is_float_dtype(x_dtype))
+      return fail(SMM_ERR_INVALID, "a decode rule was given with a float field: pass cf = NULL, or the raw 16-bit field");
+    return SMM_OK;   // float: the plain entry; anything else: refused by the dtype check
+  }
+  if (!cf) return fail(SMM_ERR_INVALID, "SMM_I16 / SMM_U16 fields need a decode rule (cf is NULL)");
+  if (cf->decode_dtype != SMM_F32 && cf->decode_dtype != SMM_F64)
+    return fail(SMM_ERR_INVALID, "cf->decode_dtype must be SMM_F32 or SMM_F64");
+  if (cf->n_fill < 0 || cf->n_fill > 2) return fail(SMM_ERR_INVALID, "cf->n_fill must be 0, 1 or 2");
+  const int32_t lo = x_dtype == SMM_I16 ? -32768 : 0, hi = x_dtype == SMM_I16 ? 32767 : 65535;
+  for (int i = 0; i < cf->n_fill; ++i)
+    if (cf->fill[i] < lo || cf->fill[i] > hi)
+      return fail(SMM_ERR_INVALID, "cf->fill[" + std::to_string(i) + "] is not representable in the raw type");
+  if (cf->n_fill > 0 && (flags & SMM_APPLY_NO_FILL))
+    return fail(SMM_ERR_INVALID, "SMM_APPLY_NO_FILL with fill values: the decode makes NaN");
+  const int32_t none = 0x7fffffff;   // no 16-bit element compares equal
+  out->p.scale = cf->scale;
+  out->p.offset = cf->offset;
+  out->p.fill0 = cf->n_fill > 0 ? cf->fill[0] : none;
+  out->p.fill1 = cf->n_fill > 1 ? cf->fill[1] : out->p.fill0;
+  out->decode_dtype = cf->decode_dtype;
+  *use = out;
+  return SMM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int smm_apply_cf(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf) {
+  return guarded([&] {
+    CfCall c;
+    const CfCall* use;
+    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
+    return smm_apply_impl(op, x, x_dtype, ldx, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream, use);
+  });
+}
+
+int smm_apply_sb_cf(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf) {
+  return guarded([&] {
+    CfCall c;
+    const CfCall* use;
+    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
+    return smm_apply_sb_impl(op, x, x_dtype, ldx, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream, use);
+  });
+}
+
+int smm_apply_host_cf(smm_operator_t op, const void* x_host, int x_dtype, int64_t ldx, void* y_host, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows, const smm_cf_decode_t* cf) {
+  return guarded([&] {
+    CfCall c;
+    const CfCall* use;
+    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
+    return smm_apply_host_impl(op, x_host, x_dtype, ldx, y_host, y_dtype, ldy, n_batch, remap_area_min, flags, chunk_rows, use);
+  });
 }
 
 int smm_group_create(const smm_operator_t* ops, int n_ops, smm_group_t* out) {

@@ -395,7 +395,7 @@ int host_copy_2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_
 
 namespace {
 
-// 16 batch entries of one used cell are 128 B (f64) / 64 B (f32) of the packed block: whole cache lines of a buffer
+// 16 batch entries of one used cell are 128 B (f64) / 64 B (f32) of the packed block (32 entries of a 2-byte field: 64 B): whole cache lines of a buffer
 // nothing reads before the DMA engine does.  Written with non-temporal stores they do not pull the line in first
 // (a plain store reads it for ownership: a third more host-memory traffic on a path that host memory bounds).
 inline void store_run(double* dst, const double* const* row, int32_t c) {
@@ -405,10 +405,18 @@ inline void store_run(float* dst, const float* const* row, int32_t c) {
   for (int k = 0; k < 16; k += 4) _mm_stream_ps(dst + k, _mm_set_ps(row[k + 3][c], row[k + 2][c], row[k + 1][c], row[k][c]));
 }
 
+// 2-byte elements (CF-packed fields, copied as raw bits): 32 batch entries make the 64-B line
+inline void store_run(uint16_t* dst, const uint16_t* const* row, int32_t c) {
+  for (int k = 0; k < 32; k += 8)
+    _mm_stream_si128((__m128i*)(dst + k),
+                     _mm_set_epi16((short)row[k + 7][c], (short)row[k + 6][c], (short)row[k + 5][c], (short)row[k + 4][c],
+                                   (short)row[k + 3][c], (short)row[k + 2][c], (short)row[k + 1][c], (short)row[k][c]));
+}
+
 template <typename T>
 void pack_rows_t(T* __restrict__ out, const T* __restrict__ x, int64_t n_inner, int64_t stride_o, int64_t stride_i,
                  const int32_t* __restrict__ used, int64_t u0, int64_t u1, int64_t rows, bool streaming) {
-  constexpr int64_t RB = 16;
+  constexpr int64_t RB = sizeof(T) == 2 ? 32 : 16;   // one store_run: at least a whole 64-B line
   for (int64_t r0 = 0; r0 < rows; r0 += RB) {
     const int64_t rn = std::min(RB, rows - r0);
     const T* row[RB];
@@ -442,7 +450,9 @@ struct PackJob {
 void pack_task(void* c, int64_t i) {
   const PackJob& j = *(const PackJob*)c;
   const int64_t u0 = std::min(j.U, i * j.per), u1 = std::min(j.U, u0 + j.per);
-  if (j.xsz == 8)
+  if (j.xsz == 2)
+    pack_rows_t((uint16_t*)j.out, (const uint16_t*)j.x, j.n_inner, j.stride_o, j.stride_i, j.used, u0, u1, j.rows, j.streaming);
+  else if (j.xsz == 8)
     pack_rows_t((double*)j.out, (const double*)j.x, j.n_inner, j.stride_o, j.stride_i, j.used, u0, u1, j.rows, j.streaming);
   else
     pack_rows_t((float*)j.out, (const float*)j.x, j.n_inner, j.stride_o, j.stride_i, j.used, u0, u1, j.rows, j.streaming);

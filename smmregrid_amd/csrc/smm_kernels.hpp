@@ -39,6 +39,21 @@ struct LevelDesc {
   const uint8_t* blk_direct;     // [n_blocks] 1 = block not staged, links gathered from X directly
 };
 
+// CF-packed source fields (smm_apply_cf and friends): how a raw 16-bit element becomes a field value.  scale and
+// offset are rounded to the decode type before use; a raw element equal to fill0 or fill1 decodes to NaN (an unused
+// slot holds a value no 16-bit element can take).  Unused by the float kernels.
+struct CfParams {
+  double scale, offset;
+  int32_t fill0, fill1;
+};
+
+// X element type tag of a packed field: Q (int16_t / uint16_t) in memory, decoded to T (float / double); see XTraits.
+// External linkage like the argument structs: it names launch-template instantiations across translation units.
+template <typename Q, typename T>
+struct PackedX {
+  Q q;
+};
+
 struct ApplyArgs {
   const LevelDesc* descs;     // device array
   const int32_t* lev_map;     // device [n_lev] -> desc index, null = identity 0
@@ -59,6 +74,7 @@ struct ApplyArgs {
   int64_t n_blocks;  // grid size (for the remap)
   int tile_bytes;    // tile kernel with R > 1: LDS bytes of one batch row's tile
   int sub_shift;     // single-wave tile kernel: a block owns 64 >> sub_shift rows of its slice
+  CfParams cf;       // packed X only
 };
 
 // arguments of the batch-fastest kernel (kernel C below)
@@ -76,6 +92,7 @@ struct SbArgs {
   int masked;
   int xcd_remap;
   int b_fastest;           // > 0: width (destination tiles) of the strips the tiles are ordered in
+  CfParams cf;             // packed X only
 };
 
 // Arguments of the batch-fastest kernel over a whole level group in ONE launch (smm_group_apply_sb).  The levels'
@@ -123,6 +140,32 @@ constexpr int kChunkElems = SMM_CHUNK_ELEMS;
 static_assert(SMM_CHUNK_ELEMS >= 4 && (SMM_CHUNK_ELEMS & (SMM_CHUNK_ELEMS - 1)) == 0, "a chunk holds at least one 16-B piece of f32");
 constexpr int64_t kTileMaxChunks = 8192 / SMM_CHUNK_ELEMS;  // 64 KiB of f64 per staged batch row
 
+// X element types.  A float type is its own storage and value type.  PackedX<Q, T> is a CF-packed field: Q
+// (int16_t / uint16_t) in memory, decoded in registers to T (float / double) by the one rule of the ABI --
+//   v = (T)q;  v = v * (T)scale;  v = v + (T)offset;  q == fill0 || q == fill1 -> NaN
+// two rounded operations (this header is compiled with contraction off), the fills compared on the raw integer --
+// after which v is treated exactly as an element of a T-typed field: the results are bit-identical to a host decode.
+template <typename XT>
+struct XTraits {
+  typedef XT raw;   // what X holds
+  typedef XT val;   // what enters the arithmetic (the type whose own cast of 1e20 is the fill)
+  static constexpr bool packed = false;
+  static __device__ __forceinline__ val decode(raw q, const CfParams&) { return q; }
+};
+template <typename Q, typename T>
+struct XTraits<PackedX<Q, T>> {
+  typedef Q raw;
+  typedef T val;
+  static constexpr bool packed = true;
+  static __device__ __forceinline__ T decode(Q q, const CfParams& cf) {
+    T v = (T)q;
+    v = v * (T)cf.scale;
+    v = v + (T)cf.offset;
+    const int32_t qi = (int32_t)q;
+    return (qi == cf.fill0 || qi == cf.fill1) ? (T)__builtin_nan("") : v;
+  }
+};
+
 template <typename T>
 __device__ __forceinline__ double load_fixed(const T* __restrict__ p, bool fill) {
   const T v = *p;
@@ -158,13 +201,14 @@ __device__ __forceinline__ double epilogue(double v, bool dead) {
 // Padded slots (weight +0.0) are never invalid and add +-0 to sums that are never -0.0: bitwise no-ops.
 template <typename XT, bool SKIPNA>
 struct RowSum {
+  typedef typename XTraits<XT>::val VT;
   double num = 0.0, den = 0.0;
   bool inv = false;
   __device__ __forceinline__ void add(double w, double x) {
     if constexpr (SKIPNA) {
       const bool fin = __builtin_isfinite(x);
       const bool bad = !fin && w != 0.0;
-      const double p = w * (fin ? x : (double)(XT)1e20);
+      const double p = w * (fin ? x : (double)(VT)1e20);
       const double ns = num + p, ds = den + w;
       num = bad ? num : ns;
       den = bad ? den : ds;
@@ -178,7 +222,7 @@ struct RowSum {
     if constexpr (SKIPNA) {
       const bool fin = __builtin_isfinite(x);
       const bool bad = on && !fin && w != 0.0;
-      const double p = w * (fin ? x : (double)(XT)1e20);
+      const double p = w * (fin ? x : (double)(VT)1e20);
       const double ns = num + p, ds = den + w;
       num = (on && !bad) ? ns : num;
       den = (on && !bad) ? ds : den;
@@ -207,6 +251,22 @@ __device__ __forceinline__ double load_link(const T* __restrict__ p, bool fill) 
     return (double)*p;
   else
     return load_fixed(p, fill);
+}
+
+// The same for any X element type: a packed element is decoded first, then filled or kept raw like a float one.
+template <typename XT, bool SKIPNA>
+__device__ __forceinline__ double load_link_x(const typename XTraits<XT>::raw* __restrict__ p, bool fill,
+                                              const CfParams& cf) {
+  if constexpr (XTraits<XT>::packed) {
+    typedef typename XTraits<XT>::val T;
+    const T v = XTraits<XT>::decode(*p, cf);
+    if constexpr (SKIPNA)
+      return (double)v;
+    else
+      return (double)((fill && !__builtin_isfinite(v)) ? (T)1e20 : v);
+  } else {
+    return load_link<SKIPNA>(p, fill);
+  }
 }
 
 // SKIPNA epilogue.  dead_m: the static mask alone (SMM_APPLY_MASKED); frac_d: dst_frac[d], 1.0 without dst_frac;
@@ -273,13 +333,14 @@ __global__ __launch_bounds__(kThreads) void smm_apply_sell_kernel(ApplyArgs a, b
   if (slice * 64 >= a.n_dst) return;
 
   const int64_t j0 = jt * BT;
-  const XT* __restrict__ xr[BT];
+  typedef typename XTraits<XT>::raw XR;
+  const XR* __restrict__ xr[BT];
   YT* __restrict__ yr[BT];
 #pragma unroll
   for (int t = 0; t < BT; ++t) {
     int64_t j = j0 + t;
     if (j > a.n_j - 1) j = a.n_j - 1;
-    xr[t] = (const XT*)a.x + row_off(j, l, a.n_inner, a.xs_o, a.xs_l, a.xs_i);
+    xr[t] = (const XR*)a.x + row_off(j, l, a.n_inner, a.xs_o, a.xs_l, a.xs_i);
     yr[t] = (YT*)a.y + row_off(j, l, a.n_inner, a.ys_o, a.ys_l, a.ys_i);
   }
 
@@ -301,7 +362,7 @@ __global__ __launch_bounds__(kThreads) void smm_apply_sell_kernel(ApplyArgs a, b
     const double w = vp[(int64_t)k * 64];
     double xv[BT];
 #pragma unroll
-    for (int t = 0; t < BT; ++t) xv[t] = load_link<SKIPNA>(xr[t] + c, fill);
+    for (int t = 0; t < BT; ++t) xv[t] = load_link_x<XT, SKIPNA>(xr[t] + c, fill, a.cf);
 #pragma unroll
     for (int t = 0; t < BT; ++t) acc[t].add(w, xv[t]);
     if (SKIPNA) tot = tot + w;
@@ -1107,6 +1168,7 @@ struct SbTile {   // what does not depend on the level
   uint32_t n_blocks;   // blocks of this operator's grid (for the XCD remap)
   double area_min;
   int masked, xcd_remap, b_fastest;
+  CfParams cf;         // packed X only (value-initialised otherwise)
 };
 
 // SKIPNA (SMM_APPLY_SKIPNA): the links are tested per batch entry (RowSum) and the row's weight sum runs wave-uniform
@@ -1120,8 +1182,10 @@ __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32
   constexpr int LROW = BT + PAD;
   static_assert(TD % 2 == 0 && 128 % TD == 0 && TD <= 64, "store phase: TD / 2 lanes per batch row");
   __shared__ __attribute__((aligned(16))) YT tile[TD * LROW];
-  typedef XT xvec __attribute__((ext_vector_type(VEC)));
-  typedef xvec xvec_u __attribute__((aligned(sizeof(XT))));   // element-aligned (any ldx / base)
+  typedef typename XTraits<XT>::raw XR;     // element in memory (a packed field: the raw 16-bit integer, 4 B per lane)
+  typedef typename XTraits<XT>::val XV;     // element in the arithmetic
+  typedef XR xvec __attribute__((ext_vector_type(VEC)));
+  typedef xvec xvec_u __attribute__((aligned(sizeof(XR))));   // element-aligned (any ldx / base)
 
   const int lane = threadIdx.x;
   // grids stay below 2^31 blocks: 32-bit index arithmetic
@@ -1162,7 +1226,7 @@ __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32
   // its second element (lanes further out have no valid entry at all)
   const bool shift1 = !tiny_batch && bl == a.n_batch - 1;
   if (bl > b_last) bl = b_last;
-  const XT* __restrict__ xl = (const XT*)a.x + bl;
+  const XR* __restrict__ xl = (const XR*)a.x + bl;
 
   const int64_t p0 = m.rowptr[d0], p1 = m.rowptr[d0 + rows];
   int d_local = 0;
@@ -1234,8 +1298,9 @@ __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32
         while (row_end <= p) flush_row();     // rows ending before this link (empty rows included)
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
-          XT e = (v == 0 && shift1) ? xv[buf][u][1] : xv[buf][u][v];
-          if (FILL && !SKIPNA) e = __builtin_isfinite(e) ? e : (XT)1e20;   // regrid.py:545-547, dtype's own 1e20
+          const XR q = (v == 0 && shift1) ? xv[buf][u][1] : xv[buf][u][v];
+          XV e = XTraits<XT>::decode(q, a.cf);
+          if (FILL && !SKIPNA) e = __builtin_isfinite(e) ? e : (XV)1e20;   // regrid.py:545-547, dtype's own 1e20
           acc[v].add(w[buf][u], (double)e);
         }
         if (SKIPNA) tot = tot + w[buf][u];
@@ -1260,8 +1325,8 @@ __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         const int64_t b = b0 + (int64_t)lane * VEC + v;
-        XT e = ((const XT*)a.x)[c * a.ldx + (b < a.n_batch ? b : a.n_batch - 1)];
-        if (FILL && !SKIPNA) e = __builtin_isfinite(e) ? e : (XT)1e20;
+        XV e = XTraits<XT>::decode(((const XR*)a.x)[c * a.ldx + (b < a.n_batch ? b : a.n_batch - 1)], a.cf);
+        if (FILL && !SKIPNA) e = __builtin_isfinite(e) ? e : (XV)1e20;
         acc[v].add(wv, (double)e);
       }
       if (SKIPNA) tot = tot + wv;
@@ -1320,7 +1385,7 @@ template <typename XT, typename YT, int TD, int U, bool FILL, bool YSB = false, 
 __global__ __launch_bounds__(64) void smm_apply_sb_kernel(SbArgs a) {
   const SbMatrix<const int64_t*, const int32_t*, const double*, const uint8_t*> m{a.rowptr, a.col, a.val, a.imask, a.frac};
   const SbTile t{a.x, a.y, a.ldx, a.ldy, a.n_batch, a.n_dst, a.n_dtiles, a.n_btiles, (uint32_t)a.n_blocks,
-                 a.area_min, a.masked, a.xcd_remap, a.b_fastest};
+                 a.area_min, a.masked, a.xcd_remap, a.b_fastest, a.cf};
   sb_tile_body<XT, YT, TD, U, FILL, YSB, SKIPNA>(m, t, blockIdx.x);
 }
 

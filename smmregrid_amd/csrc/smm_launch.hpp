@@ -1,5 +1,5 @@
 // Kernel launch templates, one explicit instantiation per (X dtype, Y dtype, SKIPNA) triple
-// (smm_launch_inst.hip is compiled eight times, in parallel): the tile kernel alone has several
+// (smm_launch_inst.hip is compiled eight times, in parallel, and four more for CF-packed X): the tile kernel alone has several
 // hundred instantiations, which one translation unit would compile for minutes.  SKIPNA = true
 // builds the SMM_APPLY_SKIPNA variants (smm_kernels.hpp, RowSum) in objects of their own.
 #pragma once

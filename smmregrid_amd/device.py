@@ -15,6 +15,101 @@ def dtype_code(dtype):
         raise TypeError(f"field dtype {dtype} not supported on device (float32/float64 only)")
 
 
+_PACKED_CODE = {np.dtype(np.int16): _lib.SMM_I16, np.dtype(np.uint16): _lib.SMM_U16}
+
+
+def is_packed_dtype(dtype):
+    """int16 / uint16: what a CF-packed field holds (regridded raw with a `CFDecode`)."""
+    return np.dtype(dtype) in _PACKED_CODE
+
+
+def field_dtype_code(dtype, cf=None):
+    """dtype_code for a field that may be CF-packed: int16 / uint16 are taken with a decode rule only."""
+    if cf is not None and is_packed_dtype(dtype):
+        return _PACKED_CODE[np.dtype(dtype)]
+    if cf is not None:
+        raise TypeError(f"a CFDecode rule goes with a raw int16 / uint16 field, not {np.dtype(dtype)}")
+    return dtype_code(dtype)
+
+
+class CFDecode:
+    """How a CF-packed 16-bit field becomes values (`scale_factor`, `add_offset`, `_FillValue` / `missing_value`):
+
+        v = dtype(q);  v = v * dtype(scale_factor);  v = v + dtype(add_offset);  q in fill_values -> NaN
+
+    two rounded operations in `dtype` (float32, what `io.open_dataset` decodes 2-byte integers to, or float64), the
+    fill values compared on the raw integers.  Passed as `cf=` to `SparseOperator.apply` / `apply_sb` / `apply_host`
+    the raw int16 / uint16 field is decoded inside the kernels; the result is bit-identical to regridding
+    `cf.decode(q)`.  `scale_factor` / `add_offset` None = absent (the step is skipped)."""
+
+    def __init__(self, scale_factor=1.0, add_offset=0.0, fill_values=(), dtype=np.float32):
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("CFDecode dtype must be float32 or float64")
+        self.scale_factor = None if scale_factor is None else float(scale_factor)
+        self.add_offset = None if add_offset is None else float(add_offset)
+        fills = []
+        for f in np.atleast_1d(np.asarray(fill_values)).ravel().tolist() if np.size(fill_values) else []:
+            if float(f) != int(f):
+                raise ValueError(f"fill value {f!r} is not an integer")
+            if int(f) not in fills:
+                fills.append(int(f))
+        if len(fills) > 2:
+            raise ValueError("at most two distinct fill values (_FillValue and missing_value)")
+        self.fill_values = tuple(fills)
+
+    @classmethod
+    def from_attrs(cls, attrs, dtype=None, raw_dtype=None):
+        """The rule of a variable's CF attributes.  dtype None = what `io.open_dataset` picks for a 2-byte integer
+        variable: float32 with a scale_factor / add_offset, float64 with fill values alone.  Fill values no element
+        of raw_dtype (or, without it, no 16-bit integer) can equal -- a NaN, 9.96921e36 -- are dropped: they never
+        match on the host either."""
+        scale, offset = attrs.get("scale_factor"), attrs.get("add_offset")
+        if dtype is None:
+            dtype = np.float32 if (scale is not None or offset is not None) else np.float64
+        lo, hi = (-32768, 65535) if raw_dtype is None else (np.iinfo(raw_dtype).min, np.iinfo(raw_dtype).max)
+        fills = []
+        for k in ("_FillValue", "missing_value"):
+            if k in attrs:
+                for f in np.atleast_1d(np.asarray(attrs[k])).ravel().tolist():
+                    if isinstance(f, (int, float)) and f == f and float(f) == int(f) and lo <= int(f) <= hi:
+                        fills.append(int(f))
+        return cls(None if scale is None else np.asarray(scale).ravel()[0],
+                   None if offset is None else np.asarray(offset).ravel()[0], fills, dtype)
+
+    def decode(self, values):
+        """The numpy statement of the rule (what the kernels reproduce bit for bit)."""
+        values = np.asarray(values)
+        if not is_packed_dtype(values.dtype):
+            raise TypeError(f"CFDecode.decode takes int16 / uint16, got {values.dtype}")
+        out = values.astype(self.dtype)
+        if self.scale_factor is not None:
+            out = out * np.asarray(self.scale_factor, dtype=self.dtype)
+        if self.add_offset is not None:
+            out = out + np.asarray(self.add_offset, dtype=self.dtype)
+        for f in self.fill_values:
+            if np.iinfo(values.dtype).min <= f <= np.iinfo(values.dtype).max:
+                out[values == f] = np.nan
+        return out
+
+    def _struct(self, raw_dtype):
+        """smm_cf_decode_t for a field of raw_dtype (fills the raw type cannot hold never match: dropped)."""
+        info = np.iinfo(raw_dtype)
+        fills = [f for f in self.fill_values if info.min <= f <= info.max]
+        st = _lib.CfDecodeStruct()
+        st.scale = 1.0 if self.scale_factor is None else self.scale_factor
+        st.offset = 0.0 if self.add_offset is None else self.add_offset
+        for i, f in enumerate(fills):
+            st.fill[i] = f
+        st.n_fill = len(fills)
+        st.decode_dtype = dtype_code(self.dtype)
+        return st
+
+    def __repr__(self):
+        return (f"CFDecode(scale_factor={self.scale_factor}, add_offset={self.add_offset}, "
+                f"fill_values={self.fill_values}, dtype={self.dtype.name})")
+
+
 def device_count():
     return _lib.device_count()
 

@@ -73,7 +73,9 @@ def write_netcdf3(ds, path):
     return path
 
 
-def open_weights(path):
+def open_weights(path, decode=True):
+    """decode=False keeps CF-packed variables as stored -- the raw integers with their scale_factor / add_offset /
+    _FillValue / missing_value attributes -- which is what `Regridder(..., packed=True)` regrids without a host decode."""
     if str(path).endswith(".npz"):
         z = np.load(path, allow_pickle=False)
         meta = json.loads(str(z["__meta__"]))
@@ -101,9 +103,10 @@ def open_weights(path):
                 values = np.array(var[...])
                 if values.dtype.kind in "iuf" and not values.dtype.isnative:
                     values = values.astype(values.dtype.newbyteorder("="))
-                values = _cf_decode(values, attrs)
-                for a in ("_FillValue", "missing_value", "scale_factor", "add_offset"):
-                    attrs.pop(a, None)
+                if decode:
+                    values = _cf_decode(values, attrs)
+                    for a in ("_FillValue", "missing_value", "scale_factor", "add_offset"):
+                        attrs.pop(a, None)
                 arr = DataArray(values, dims=var.dimensions, name=k, attrs=attrs)
                 if var.dimensions == (k,):
                     ds.coords[k] = arr
@@ -113,15 +116,15 @@ def open_weights(path):
     if HAVE_XARRAY:
         import xarray
         from .xrlite import from_xarray
-        return from_xarray(xarray.open_dataset(path))
+        return from_xarray(xarray.open_dataset(path) if decode else xarray.open_dataset(path, mask_and_scale=False))
     try:
         import h5py
     except ImportError:
-        return _open_netcdf4_lite(path)      # built-in pure-Python HDF5 reader (hdf5lite.py)
-    return _open_netcdf4_h5py(h5py, path)
+        return _open_netcdf4_lite(path, decode=decode)      # built-in pure-Python HDF5 reader (hdf5lite.py)
+    return _open_netcdf4_h5py(h5py, path, decode=decode)
 
 
-open_dataset = open_weights                 # fields and grids come through the same readers
+open_dataset = open_weights                 # fields and grids come through the same readers (decode= included)
 
 
 _NC4_INTERNAL = {"DIMENSION_LIST", "REFERENCE_LIST", "CLASS", "NAME", "_Netcdf4Dimid", "_Netcdf4Coordinates",

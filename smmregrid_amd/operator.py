@@ -11,7 +11,8 @@ import time
 import numpy as np
 
 from . import _lib
-from .device import DeviceArray, dtype_code, result_cache, _stream_handle, current_device
+from .device import (DeviceArray, dtype_code, field_dtype_code, is_packed_dtype, result_cache, _stream_handle,
+                     current_device)
 
 
 def _cptr(a):
@@ -154,9 +155,10 @@ class SparseOperator:
                 "rows_per_block": kind.value >> 8}
 
     def launch_info(self, n_batch, dtype=np.float64, flags=0):
-        """Launch geometry `apply` would use for `n_batch` rows (nothing is launched)."""
-        return _launch_info("smm_operator_launch_info", self.handle, dtype_code(np.dtype(dtype)),
-                            (int(n_batch),), flags)
+        """Launch geometry `apply` would use for `n_batch` rows (nothing is launched).  dtype int16 / uint16: a
+        CF-packed field given with `cf=` (always the SELL kernel)."""
+        code = field_dtype_code(dtype, cf=True) if is_packed_dtype(dtype) else dtype_code(np.dtype(dtype))
+        return _launch_info("smm_operator_launch_info", self.handle, code, (int(n_batch),), flags)
 
     def mask_apply(self, src_imask):
         """weights.py:47-52 on the device: (src_imask . W) < 0.5 ? 0 : 1."""
@@ -168,18 +170,21 @@ class SparseOperator:
         return out
 
     def apply(self, x, y=None, masked=False, remap_area_min=0.0, out_dtype=np.float64,
-              flags=0, stream=None, keep_batch_fastest=False, skipna=False):
+              flags=0, stream=None, keep_batch_fastest=False, skipna=False, cf=None):
         """Y = epilogue(fill(X) . W) for a device-resident X of shape (B, S), or (B, ldx) with a
         padded row pitch ldx >= S (rows that start on 128-B lines are staged without straddling).
         A field tagged batch-fastest (`x.layout == "sb"`, shape (S, B)) goes through the batch-fastest
         kernel (`apply_sb`); with keep_batch_fastest the result stays batch-fastest too, (D, B).
         skipna: non-finite source values drop out of each batch row's sums and the row is renormalised over
-        the valid weight (SMM_APPLY_SKIPNA; rows without one are bit-identical to the plain apply)."""
+        the valid weight (SMM_APPLY_SKIPNA; rows without one are bit-identical to the plain apply).
+        cf: a `CFDecode` -- x holds the raw int16 / uint16 of a CF-packed field, decoded inside the kernel
+        (bit-identical to applying `cf.decode` on the host first; float64 results only)."""
         if not isinstance(x, DeviceArray):
             raise TypeError("SparseOperator.apply takes a DeviceArray (use Regridder for host data)")
         if x.layout == "sb":
             return self.apply_sb(x, y=y, masked=masked, remap_area_min=remap_area_min, out_dtype=out_dtype,
-                                 flags=flags, skipna=skipna, stream=stream, keep_batch_fastest=keep_batch_fastest)
+                                 flags=flags, skipna=skipna, stream=stream, keep_batch_fastest=keep_batch_fastest,
+                                 cf=cf)
         if keep_batch_fastest:
             raise ValueError("keep_batch_fastest needs a batch-fastest field (DeviceArray(..., layout='sb'))")
         if x.ndim != 2 or x.shape[1] < self.n_src:
@@ -190,6 +195,13 @@ class SparseOperator:
         elif y.shape != (n_batch, self.n_dst):
             raise ValueError(f"Y must be ({n_batch}, {self.n_dst}), got {y.shape}")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        if cf is not None:
+            code = field_dtype_code(x.dtype, cf)
+            st = cf._struct(x.dtype)
+            _lib.call("smm_apply_cf", self.handle, ctypes.c_void_p(x.ptr), code,
+                      x.shape[1], ctypes.c_void_p(y.ptr), dtype_code(y.dtype), self.n_dst, n_batch,
+                      float(remap_area_min), fl, _stream_handle(stream), ctypes.byref(st))
+            return y
         _lib.call("smm_apply", self.handle, ctypes.c_void_p(x.ptr), dtype_code(x.dtype),
                   x.shape[1], ctypes.c_void_p(y.ptr), dtype_code(y.dtype), self.n_dst, n_batch,
                   float(remap_area_min), fl, _stream_handle(stream))
@@ -208,7 +220,7 @@ class SparseOperator:
         return self
 
     def apply_sb(self, x, y=None, masked=False, remap_area_min=0.0, packed=False, out_dtype=np.float64,
-                 flags=0, stream=None, keep_batch_fastest=False, n_batch=None, skipna=False):
+                 flags=0, stream=None, keep_batch_fastest=False, n_batch=None, skipna=False, cf=None):
         """The same product for a device-resident field kept batch-fastest: x of shape (S, B) -- or
         (n_used_src, B) with packed=True, rows in `used_sources()` order -- holds the B batch values
         of each source cell contiguously.  Y is (B, D) as `apply` returns it, bit-identical to
@@ -217,7 +229,8 @@ class SparseOperator:
         stays batch-fastest as well -- Y (D, B), tagged layout "sb" -- which is what a following regrid
         on the target grid consumes without any transpose (SMM_APPLY_SB_Y_SB).  n_batch: batch entries
         when the last axis of x is a padded pitch (cells that start on 128-B lines -- a pitch of a multiple
-        of 16 doubles -- are what the cell-staging kernel likes: every 16-entry run is then one line)."""
+        of 16 doubles -- are what the cell-staging kernel likes: every 16-entry run is then one line).
+        cf: a `CFDecode` for a raw int16 / uint16 field (see `apply`)."""
         if not isinstance(x, DeviceArray):
             raise TypeError("SparseOperator.apply_sb takes a DeviceArray")
         rows = self.n_used_src if packed else self.n_src
@@ -236,18 +249,29 @@ class SparseOperator:
         fl |= _lib.APPLY_SB_PACKED if packed else 0
         if keep_batch_fastest:
             fl |= _lib.APPLY_SB_Y_SB
+        if cf is not None:
+            code = field_dtype_code(x.dtype, cf)
+            st = cf._struct(x.dtype)
+            _lib.call("smm_apply_sb_cf", self.handle, ctypes.c_void_p(x.ptr), code, max(ldx, 1),
+                      ctypes.c_void_p(y.ptr), dtype_code(y.dtype), max(y_shape[1], 1), n_batch, float(remap_area_min),
+                      fl, _stream_handle(stream), ctypes.byref(st))
+            return y
         _lib.call("smm_apply_sb", self.handle, ctypes.c_void_p(x.ptr), dtype_code(x.dtype), max(ldx, 1),
                   ctypes.c_void_p(y.ptr), dtype_code(y.dtype), max(y_shape[1], 1), n_batch, float(remap_area_min), fl,
                   _stream_handle(stream))
         return y
 
     def apply_host(self, x, out=None, masked=False, remap_area_min=0.0, out_dtype=np.float64,
-                   flags=0, chunk_rows=0, skipna=False):
+                   flags=0, chunk_rows=0, skipna=False, cf=None):
         """Same product for a host (numpy) array of shape (B, S): the rows stream through the
         library's double-buffered H2D / kernel / D2H pipeline (smm_apply_host).  Arrays from
-        `pinned_empty` are DMA'd without staging copies.  Returns a (B, D) numpy array."""
+        `pinned_empty` are DMA'd without staging copies.  Returns a (B, D) numpy array.
+        cf: a `CFDecode` -- x is the raw int16 / uint16 of a CF-packed field: it is staged, packed and shipped as
+        2-byte elements and decoded inside the kernels (smm_apply_host_cf)."""
         x = np.asarray(x)
-        if x.dtype not in (np.float32, np.float64):
+        if cf is not None and not is_packed_dtype(x.dtype):
+            raise TypeError(f"a CFDecode rule goes with a raw int16 / uint16 field, not {x.dtype}")
+        if cf is None and x.dtype not in (np.float32, np.float64):
             x = x.astype(np.float64)          # result_type(x, f64), regrid.py:550
         if x.ndim != 2 or x.shape[1] != self.n_src:
             raise ValueError(f"X must be (B, {self.n_src}), got {x.shape}")
@@ -259,8 +283,14 @@ class SparseOperator:
         if out.shape != (n_batch, self.n_dst) or not out.flags.c_contiguous:
             raise ValueError(f"out must be a C-contiguous ({n_batch}, {self.n_dst}) array")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
-        _lib.call("smm_apply_host", self.handle, _cptr(x), dtype_code(x.dtype),
-                  x.strides[0] // x.itemsize if n_batch > 1 else max(self.n_src, 1),
+        ldx = x.strides[0] // x.itemsize if n_batch > 1 else max(self.n_src, 1)
+        if cf is not None:
+            st = cf._struct(x.dtype)
+            _lib.call("smm_apply_host_cf", self.handle, _cptr(x), field_dtype_code(x.dtype, cf), ldx,
+                      _cptr(out), dtype_code(out.dtype), self.n_dst, n_batch, float(remap_area_min), fl,
+                      int(chunk_rows), ctypes.byref(st))
+            return out
+        _lib.call("smm_apply_host", self.handle, _cptr(x), dtype_code(x.dtype), ldx,
                   _cptr(out), dtype_code(out.dtype), self.n_dst, n_batch, float(remap_area_min), fl,
                   int(chunk_rows))
         return out

@@ -18,7 +18,7 @@ import os
 
 import numpy as np
 
-from .device import DeviceArray
+from .device import CFDecode, DeviceArray, is_packed_dtype, to_device
 from .gridtype import GridType, tolist
 from .lazy import LazyArray, is_dask, map_batch_blocks
 from .operator import OperatorGroup
@@ -26,6 +26,7 @@ from .weights import (_level_slice, check_mask, compute_weights_matrix, compute_
                       mask_weights)
 from .xrlite import DataArray, Dataset, from_xarray, is_xarray, to_xarray
 
+_CF_PACKING_ATTRS = ("scale_factor", "add_offset", "_FillValue", "missing_value")
 DEFAULT_AREA_MIN = 0.5  # default minimum area for conservative remapping (regrid.py:49)
 
 
@@ -55,7 +56,7 @@ class Regridder(object):
                  method='con', remap_area_min=DEFAULT_AREA_MIN, transpose=True, mask_dim=None,
                  vertical_dim=None, horizontal_dims=None, cdo_extra=None, cdo_options=None,
                  check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=np.float64,
-                 lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False):
+                 lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -82,6 +83,10 @@ class Regridder(object):
         # renormalised -- the weights regenerated with that step's validity as source mask (SMM_APPLY_SKIPNA);
         # remap_area_min then thresholds the valid fraction of each target cell
         self.skipna = bool(skipna)
+        # packed: an int16 / uint16 variable that carries scale_factor / add_offset / _FillValue / missing_value (a
+        # file opened undecoded: io.open_dataset(path, decode=False)) is regridded raw -- shipped and gathered as
+        # 2-byte elements, decoded inside the kernels (CFDecode) -- with the bits of a host decode
+        self.packed = bool(packed)
         # the reference always yields float64 (result_type(x, f64)); float32 is an opt-in narrowing store
         self.out_dtype = np.dtype(out_dtype)
         if self.out_dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -270,9 +275,42 @@ class Regridder(object):
             # without horizontal or mask dimension is cleaned away, :133-143 -- time_bnds(time, bnds) is one): nothing
             # to regrid, and the empty result is dropped from a Dataset (regrid.py:308-312, :262-264)
             return DataArray(data=None)
+        cf = self._packed_rule(source_data) if self.packed else None
+        if cf is not None and (datagridtype.mask_dim or self.out_dtype != np.dtype(np.float64)):
+            # level groups and float32 results take no packed input: decoded on the host, regridded as before
+            self.loggy.info("packed variable %s is decoded on the host (%s)", source_data.name,
+                            "masked levels" if datagridtype.mask_dim else "out_dtype float32")
+            source_data = self._decode_on_host(source_data, cf)
+            cf = None
         if datagridtype.mask_dim:
-            return self.regrid3d(source_data, datagridtype)
-        return self.regrid2d(source_data, datagridtype)
+            out = self.regrid3d(source_data, datagridtype)
+        else:
+            out = self.regrid2d(source_data, datagridtype, cf=cf)
+        if cf is not None:
+            for k in _CF_PACKING_ATTRS:
+                out.attrs.pop(k, None)
+        return out
+
+    def _packed_rule(self, source_data):
+        """The CFDecode of a 2-byte integer variable that carries CF packing attributes, else None."""
+        dtype = getattr(source_data.data, "dtype", None)
+        if dtype is None or not is_packed_dtype(dtype) or not any(k in source_data.attrs for k in _CF_PACKING_ATTRS):
+            return None
+        try:
+            return CFDecode.from_attrs(source_data.attrs, raw_dtype=dtype)
+        except ValueError as err:      # more than two distinct fill values: the field is regridded as it was before
+            self.loggy.warning("packed variable %s is not regridded raw: %s", source_data.name, err)
+            return None
+
+    @staticmethod
+    def _decode_on_host(source_data, cf):
+        src = source_data.data
+        if isinstance(src, DeviceArray):
+            data = to_device(cf.decode(src.to_host()), layout=src.layout)
+        else:
+            data = cf.decode(src.compute() if hasattr(src, "compute") else np.asarray(src))
+        attrs = {k: v for k, v in source_data.attrs.items() if k not in _CF_PACKING_ATTRS}
+        return DataArray(data, dims=source_data.dims, coords=source_data.coords, attrs=attrs, name=source_data.name)
 
     def _get_gridtype(self, datagridtype):
         """regrid.py:324-337."""
@@ -282,7 +320,7 @@ class Regridder(object):
             self.grids[0].other_dims = datagridtype.other_dims
         return next((grid for grid in self.grids if grid == datagridtype), None)
 
-    def regrid2d(self, source_data, datagridtype):
+    def regrid2d(self, source_data, datagridtype, cf=None):
         """regrid.py:429-456."""
         gridtype = self._get_gridtype(datagridtype)
         if gridtype is None:
@@ -290,7 +328,7 @@ class Regridder(object):
         return self.apply_weights(source_data, gridtype.weights,
                                   weights_matrix=gridtype.weights_matrix,
                                   masked=gridtype.masked,
-                                  horizontal_dims=gridtype.horizontal_dims)
+                                  horizontal_dims=gridtype.horizontal_dims, cf=cf)
 
     # ------------------------------------------------------------------ apply (2-D)
     def _target_layout(self, weights):
@@ -329,8 +367,8 @@ class Regridder(object):
         return out
 
     def apply_weights(self, source_data, weights, weights_matrix=None, masked=True,
-                      horizontal_dims=None):
-        """regrid.py:458-628 for one 2-D operator."""
+                      horizontal_dims=None, cf=None):
+        """regrid.py:458-628 for one 2-D operator.  cf: the CFDecode of a raw int16 / uint16 field (packed=True)."""
         source_data = from_xarray(source_data)
         weights = from_xarray(weights)
         name = source_data.name or ''
@@ -375,12 +413,13 @@ class Regridder(object):
             """(rows, S) host block -> (rows, D): chunks stream through the library's H2D / kernel /
             D2H pipeline."""
             host = np.asarray(host)
-            if host.dtype not in (np.float32, np.float64):
+            if cf is None and host.dtype not in (np.float32, np.float64):
                 host = host.astype(np.float64)  # result_type(x, f64), regrid.py:550
             host = np.ascontiguousarray(host)
             if host.shape[1] != op.n_src:
                 raise ValueError(f"source grid has {host.shape[1]} cells, weights expect {op.n_src}")
-            return op.apply_host(host, masked=masked, remap_area_min=area_min, out_dtype=out_dtype, skipna=skipna)
+            return op.apply_host(host, masked=masked, remap_area_min=area_min, out_dtype=out_dtype, skipna=skipna,
+                                 cf=cf)
 
         def compute():
             if sb_in:
@@ -388,13 +427,13 @@ class Regridder(object):
                 if x.shape[0] != op.n_src:
                     raise ValueError(f"source grid has {x.shape[0]} cells, weights expect {op.n_src}")
                 y = op.apply(x, masked=masked, remap_area_min=area_min, out_dtype=out_dtype,
-                             keep_batch_fastest=sb_out, skipna=skipna)
+                             keep_batch_fastest=sb_out, skipna=skipna, cf=cf)
                 return y.reshape(*out_shape)
             if isinstance(src, DeviceArray):
                 x = src.reshape(n_batch, -1)
                 if x.shape[1] != op.n_src:
                     raise ValueError(f"source grid has {x.shape[1]} cells, weights expect {op.n_src}")
-                y = op.apply(x, masked=masked, remap_area_min=area_min, out_dtype=out_dtype, skipna=skipna)
+                y = op.apply(x, masked=masked, remap_area_min=area_min, out_dtype=out_dtype, skipna=skipna, cf=cf)
                 return y.reshape(*(kept_shape + tgt_shape))
             host = src.compute() if isinstance(src, LazyArray) else np.asarray(src)
             return apply_rows(host.reshape(n_batch, -1)).reshape(kept_shape + tgt_shape)
