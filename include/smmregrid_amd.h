@@ -242,6 +242,8 @@ int smm_group_prepare(smm_group_t g, int64_t n_lev, const int32_t* level_index,
 int smm_group_launch_info(smm_group_t g, int x_dtype, int64_t n_outer, int64_t n_lev, int64_t n_inner,
                           unsigned flags, int* kernel, int* j_per_block, int* rows_per_step,
                           int* rows_per_block, int64_t* n_blocks, int64_t* lds_bytes, int* big_operator);
+/* (smm_group_launch_info: x_dtype SMM_I16 / SMM_U16 answers for smm_group_apply_cf -- kernel 0, as for single operators;
+ * with SMM_APPLY_KERNEL_TILE: SMM_ERR_UNSUPPORTED) */
 /* bit 0: every member has an LDS tile plan of the group's block shape, bit 1: the tile kernel is the default */
 int smm_group_plan_info(smm_group_t g, int* kernel_kind, int* slices_per_block);
 
@@ -308,7 +310,8 @@ int smm_apply_host(smm_operator_t op,
  * x_dtype, cf != NULL with a float one, a fill value outside the raw type, or SMM_APPLY_NO_FILL with n_fill > 0 (the
  * decode makes NaN) are SMM_ERR_INVALID.  MASKED, SKIPNA, HOST_NO_PACK, SB_PACKED, SB_Y_SB and KERNEL_SELL work as
  * for float fields; smm_apply_cf runs the SELL kernel whatever the operator's plan (smm_operator_launch_info says
- * so) and SMM_APPLY_KERNEL_TILE is SMM_ERR_UNSUPPORTED.  Level groups take no packed input.
+ * so) and SMM_APPLY_KERNEL_TILE is SMM_ERR_UNSUPPORTED.  Level groups take packed input through the three
+ * smm_group_apply*_cf entries further down.
  */
 int smm_apply_cf(smm_operator_t op,
                  const void* x, int x_dtype, int64_t ldx,
@@ -383,6 +386,49 @@ int smm_group_apply_host(smm_group_t g,
                          int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose,
                          const int32_t* level_index, const uint8_t* masked_levels,
                          double remap_area_min, unsigned flags, int64_t chunk_outer);
+
+/*
+ * The three group entries above for CF-packed fields (SMM_I16 / SMM_U16 X, raw 2-byte elements, decoded inside the
+ * kernels), with the contract of smm_apply_cf / smm_apply_sb_cf / smm_apply_host_cf: y_dtype must be SMM_F64
+ * (else SMM_ERR_UNSUPPORTED); cf == NULL with a float x_dtype is the plain entry; cf == NULL with an integer x_dtype,
+ * cf != NULL with a float one, a fill value outside the raw type, or SMM_APPLY_NO_FILL with n_fill > 0 are
+ * SMM_ERR_INVALID.  One decode rule per call: a variable has one set of packing attributes, it applies to every level.
+ * The plain group entries refuse the integer codes with SMM_ERR_UNSUPPORTED.  The whole call is validated before
+ * the first launch.  level_index / masked_levels, MASKED, SKIPNA, SB_Y_SB, HOST_NO_PACK and KERNEL_SELL work as for
+ * float fields, with the bits of decoding on the host and calling the plain entry.
+ *   smm_group_apply_cf      native layout, strides in elements of the raw type.  Runs the SELL kernel whatever the
+ *                           group's tile plan (smm_group_launch_info says so for SMM_I16 / SMM_U16);
+ *                           SMM_APPLY_KERNEL_TILE is SMM_ERR_UNSUPPORTED.
+ *   smm_group_apply_sb_cf   per-level (S, ldx) slabs of raw elements, xs_lev in raw elements; all data levels in one
+ *                           launch of the grouped batch-fastest kernel as for float fields (the decode rule travels
+ *                           in the kernel arguments beside the 88 levels' pointers).  SMM_APPLY_SB_PACKED is refused.
+ *   smm_group_apply_host_cf host X (n_outer, n_lev, n_inner, S) of raw elements: staged, packed level-major or per
+ *                           outer block and shipped as 2-byte elements (SMM_HOST_STAT_H2D_BYTES counts 2 B per cell).
+ *                           The slabs of a packed chunk lie back to back without padding: the kernel's loads need
+ *                           element alignment only.
+ */
+int smm_group_apply_cf(smm_group_t g,
+                       const void* x, int x_dtype,
+                       int64_t xs_outer, int64_t xs_lev, int64_t xs_inner,
+                       void* y, int y_dtype,
+                       int64_t ys_outer, int64_t ys_lev, int64_t ys_inner,
+                       int64_t n_outer, int64_t n_lev, int64_t n_inner,
+                       const int32_t* level_index, const uint8_t* masked_levels,
+                       double remap_area_min, unsigned flags, void* stream,
+                       const smm_cf_decode_t* cf);
+int smm_group_apply_sb_cf(smm_group_t g,
+                          const void* x, int x_dtype, int64_t xs_lev, int64_t ldx,
+                          void* y, int y_dtype, int64_t ys_lev, int64_t ys_batch,
+                          int64_t n_batch, int64_t n_lev,
+                          const int32_t* level_index, const uint8_t* masked_levels,
+                          double remap_area_min, unsigned flags, void* stream,
+                          const smm_cf_decode_t* cf);
+int smm_group_apply_host_cf(smm_group_t g,
+                            const void* x_host, int x_dtype, void* y_host, int y_dtype,
+                            int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose,
+                            const int32_t* level_index, const uint8_t* masked_levels,
+                            double remap_area_min, unsigned flags, int64_t chunk_outer,
+                            const smm_cf_decode_t* cf);
 
 /* Test hook of the two host pipelines' error path: chunk number `chunk` (0-based) of every following
  * smm_apply_host / smm_group_apply_host call fails with SMM_ERR_HIP before its copies are queued;

@@ -55,10 +55,11 @@ SMM_EXTERN_PAIR(double, float, true)
 SMM_EXTERN_PAIR(float, double, true)
 SMM_EXTERN_PAIR(float, float, true)
 #undef SMM_EXTERN_PAIR
-// CF-packed 16-bit X (PackedX<raw, decode type>): kernels A and C, f64 results
+// CF-packed 16-bit X (PackedX<raw, decode type>): kernels A and C and the grouped kernel C, f64 results
 #define SMM_EXTERN_PACKED(Q, T, NA)                                                                             \
   extern template int launch_sell<PackedX<Q, T>, double, NA>(const ApplyArgs&, int64_t, bool, unsigned, hipStream_t); \
-  extern template int launch_sb<PackedX<Q, T>, double, NA>(const SbArgs&, bool, unsigned, hipStream_t);
+  extern template int launch_sb<PackedX<Q, T>, double, NA>(const SbArgs&, bool, unsigned, hipStream_t);          \
+  extern template int launch_sb_group<PackedX<Q, T>, double, NA>(const SbGroupArgs&, bool, unsigned, hipStream_t);
 SMM_EXTERN_PACKED(int16_t, float, false)
 SMM_EXTERN_PACKED(int16_t, double, false)
 SMM_EXTERN_PACKED(uint16_t, float, false)
@@ -1544,7 +1545,7 @@ static int smm_group_apply_impl(smm_group_t g, const void* x, int x_dtype, int64
                     int64_t xs_inner, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev,
                     int64_t ys_inner, int64_t n_outer, int64_t n_lev, int64_t n_inner,
                     const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min,
-                    unsigned flags, void* stream) {
+                    unsigned flags, void* stream, const CfCall* cf = nullptr) {
   if (int frc = check_flags(flags)) return frc;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
   DeviceGuard guard(g->device);
@@ -1557,7 +1558,7 @@ static int smm_group_apply_impl(smm_group_t g, const void* x, int x_dtype, int64
   return run_apply(g->d_descs, d_map, d_masked, op0->csr.n_src, op0->csr.n_dst, g->tile_which,
                    g->tile_valid, g->tile_preferred, (g->tile_reuse ? 1 : 0), g->tile_max_chunks, g->max_row_nnz, x, x_dtype, xs_outer, xs_lev, xs_inner, y,
                    y_dtype, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner, remap_area_min,
-                   flags, (hipStream_t)stream);
+                   flags, (hipStream_t)stream, nullptr, cf);
 }
 
 extern "C++" {
@@ -1603,15 +1604,15 @@ static int smm_group_prepare_sb_impl(smm_group_t g) {
 static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, int64_t xs_lev, int64_t ldx, void* y,
                        int y_dtype, int64_t ys_lev, int64_t ys_batch, int64_t n_batch, int64_t n_lev,
                        const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min,
-                       unsigned flags, void* stream) {
+                       unsigned flags, void* stream, const CfCall* cf = nullptr) {
   if (int frc = check_flags(flags)) return frc;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
   if (n_batch < 0 || n_lev < 0) return fail(SMM_ERR_INVALID, "negative batch size / level count");
   if (n_lev > 0 && !level_index) return fail(SMM_ERR_INVALID, "null level_index");
   if (flags & SMM_APPLY_SB_PACKED)
     return fail(SMM_ERR_UNSUPPORTED, "packed fields are per operator: a group takes whole (S, B) slabs");
-  if ((x_dtype != SMM_F32 && x_dtype != SMM_F64) || (y_dtype != SMM_F32 && y_dtype != SMM_F64))
-    return fail(SMM_ERR_UNSUPPORTED, "field dtype must be SMM_F32 or SMM_F64");
+  if (int drc = check_x_dtype(x_dtype, y_dtype, cf)) return drc;
+  const bool packed = is_packed_dtype(x_dtype);   // CF-packed: raw 2-byte slabs, one decode rule for every level
   const int n_ops = (int)g->ops.size();
   for (int64_t l = 0; l < n_lev; ++l)
     if (level_index[l] < 0 || level_index[l] >= n_ops)
@@ -1619,7 +1620,7 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, in
                                        " outside the group");
   if (n_lev == 0 || n_batch == 0 || g->ops[0]->csr.n_dst == 0) return SMM_OK;
   if (!x || !y) return fail(SMM_ERR_INVALID, "null field pointer");
-  const size_t xsz = x_dtype == SMM_F64 ? 8 : 4, ysz = y_dtype == SMM_F64 ? 8 : 4;
+  const size_t xsz = dtype_size(x_dtype), ysz = dtype_size(y_dtype);
   // the whole call is validated before the first launch (as smm_group_apply does): a later level's
   // missing dst_imask / dst_frac or a bad stride must not surface after earlier levels wrote part of Y
   if (ldx < n_batch) return fail(SMM_ERR_INVALID, "ldx smaller than the batch");
@@ -1662,7 +1663,9 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, in
         const bool m = (flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w]);   // regrid.py:405
         a.lev[i] = SbLevelPtrs{op->d_csr_rowptr, op->d_csr_col, op->d_csr_val, m ? op->d_imask : nullptr, op->d_frac};
       }
-      const int rc = SMM_DISPATCH_ALL(launch_sb_group, flags, x_dtype, y_dtype, a, fill, flags, caller);
+      if (packed) a.cf = cf->p;
+      const int rc = packed ? SMM_DISPATCH_CF(launch_sb_group, flags, x_dtype, cf->decode_dtype, a, fill, flags, caller)
+                            : SMM_DISPATCH_ALL(launch_sb_group, flags, x_dtype, y_dtype, a, fill, flags, caller);
       if (rc) return rc;
     }
     return SMM_OK;
@@ -1674,8 +1677,9 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, in
     const int w = level_index[l];
     unsigned fl = flags & ~(unsigned)SMM_APPLY_MASKED;
     if ((flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w])) fl |= SMM_APPLY_MASKED;   // regrid.py:405
-    status = smm_apply_sb(g->ops[(size_t)w], (const char*)x + (size_t)l * xs_lev * xsz, x_dtype, ldx,
-                          (char*)y + (size_t)l * ys_lev * ysz, y_dtype, ys_batch, n_batch, remap_area_min, fl, caller);
+    status = smm_apply_sb_impl(g->ops[(size_t)w], (const char*)x + (size_t)l * xs_lev * xsz, x_dtype, ldx,
+                               (char*)y + (size_t)l * ys_lev * ysz, y_dtype, ys_batch, n_batch, remap_area_min, fl,
+                               caller, cf);
   }
   return status;
 }
@@ -1731,19 +1735,26 @@ static int smm_group_launch_info_impl(smm_group_t g, int x_dtype, int64_t n_oute
 static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dtype, void* y_host, int y_dtype,
                          int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose,
                          const int32_t* level_index, const uint8_t* masked_levels,
-                         double remap_area_min, unsigned flags, int64_t chunk_outer) {
+                         double remap_area_min, unsigned flags, int64_t chunk_outer, const CfCall* cf = nullptr) {
   if (int frc = check_flags(flags)) return frc;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
   if (n_outer < 0 || n_lev < 0 || n_inner < 0) return fail(SMM_ERR_INVALID, "negative batch size");
-  if ((x_dtype != SMM_F32 && x_dtype != SMM_F64) || (y_dtype != SMM_F32 && y_dtype != SMM_F64))
-    return fail(SMM_ERR_UNSUPPORTED, "field dtype must be SMM_F32 or SMM_F64");
+  if (int drc = check_x_dtype(x_dtype, y_dtype, cf)) return drc;
+  const bool packed = is_packed_dtype(x_dtype);
+  if (packed && (flags & SMM_APPLY_KERNEL_TILE))
+    return fail(SMM_ERR_UNSUPPORTED, "the LDS tile kernel is not built for packed fields (SMM_I16 / SMM_U16)");
   const int64_t S = g->ops[0]->csr.n_src, D = g->ops[0]->csr.n_dst;
   if (n_outer == 0 || n_lev == 0 || n_inner == 0 || D == 0) return SMM_OK;
   if (!x_host || !y_host) return fail(SMM_ERR_INVALID, "null field pointer");
+  if (packed && (uintptr_t)x_host % 2) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
   DeviceGuard guard(g->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the group's device");
 
-  const size_t xsz = x_dtype == SMM_F64 ? 8 : 4, ysz = y_dtype == SMM_F64 ? 8 : 4;
+  // a packed field is staged, packed and shipped raw, 2 B per cell: every size below follows xsz.  The slabs of a packed
+  // chunk lie back to back (level l's at the running sum of U_l * batch * xsz): kernel C's 4-B-per-lane loads of 2-byte
+  // elements only assume element alignment (xvec_u, smm_kernels.hpp), and a slab can start on an odd element only when
+  // the batch count is odd -- when every other row of every slab starts on one anyway -- so no padding is added
+  const size_t xsz = dtype_size(x_dtype), ysz = dtype_size(y_dtype);
   const size_t xrow_d = (((size_t)S * xsz + 127) / 128) * 128;   // device rows start on 128-B lines (see smm_apply_host)
   const int64_t ldx_d = (int64_t)(xrow_d / xsz);
   const int64_t rows_per_outer = n_lev * n_inner;
@@ -1934,9 +1945,9 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
         unsigned fl = (flags & (SMM_APPLY_NO_FILL | SMM_APPLY_SKIPNA)) | SMM_APPLY_SB_PACKED;
         if ((flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w])) fl |= SMM_APPLY_MASKED;
         // Y of the chunk: entry (b, ll, d) at (b * nl + ll) * D + d when transpose, at (ll * bc + b) * D + d else
-        rc = smm_apply_sb(op, (char*)pipe.dx[b] + off, x_dtype, bc,
-                          (char*)pipe.dy[b] + (size_t)ll * (transpose ? D : bc * D) * ysz, y_dtype,
-                          transpose ? ck.nl * D : D, bc, remap_area_min, fl, pipe.stream[b]);
+        rc = smm_apply_sb_impl(op, (char*)pipe.dx[b] + off, x_dtype, bc,
+                               (char*)pipe.dy[b] + (size_t)ll * (transpose ? D : bc * D) * ysz, y_dtype,
+                               transpose ? ck.nl * D : D, bc, remap_area_min, fl, pipe.stream[b], cf);
         off += (size_t)op->csr.n_used_src * bc * xsz;
       }
     } else {
@@ -1959,9 +1970,9 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
                                hipMemcpyHostToDevice, pipe.stream[b]));
       st.v[SMM_HOST_STAT_H2D_BYTES] += (double)((size_t)S * xsz * (size_t)rows);
       SMM_HIP(hipEventRecord(pipe.ev[b][1], pipe.stream[b]));
-      rc = smm_group_apply(g, pipe.dx[b], x_dtype, rows_per_outer * ldx_d, n_inner * ldx_d, ldx_d,
-                           pipe.dy[b], y_dtype, ys_o, ys_l, ys_i, no, n_lev, n_inner, level_index,
-                           masked_levels, remap_area_min, flags, pipe.stream[b]);
+      rc = smm_group_apply_impl(g, pipe.dx[b], x_dtype, rows_per_outer * ldx_d, n_inner * ldx_d, ldx_d,
+                                pipe.dy[b], y_dtype, ys_o, ys_l, ys_i, no, n_lev, n_inner, level_index,
+                                masked_levels, remap_area_min, flags, pipe.stream[b], cf);
     }
     if (rc) return rc;
     SMM_HIP(hipEventRecord(pipe.ev[b][2], pipe.stream[b]));
@@ -2103,6 +2114,34 @@ int smm_group_apply_sb(smm_group_t g, const void* x, int x_dtype, int64_t xs_lev
 
 int smm_group_apply_host(smm_group_t g, const void* x_host, int x_dtype, void* y_host, int y_dtype, int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, int64_t chunk_outer) {
   return guarded([&] { return smm_group_apply_host_impl(g, x_host, x_dtype, y_host, y_dtype, n_outer, n_lev, n_inner, transpose, level_index, masked_levels, remap_area_min, flags, chunk_outer); });
+}
+
+// The three group entries for CF-packed fields (see smm_apply_cf): one decode rule for every level
+int smm_group_apply_cf(smm_group_t g, const void* x, int x_dtype, int64_t xs_outer, int64_t xs_lev, int64_t xs_inner, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev, int64_t ys_inner, int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf) {
+  return guarded([&] {
+    CfCall c;
+    const CfCall* use;
+    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
+    return smm_group_apply_impl(g, x, x_dtype, xs_outer, xs_lev, xs_inner, y, y_dtype, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner, level_index, masked_levels, remap_area_min, flags, stream, use);
+  });
+}
+
+int smm_group_apply_sb_cf(smm_group_t g, const void* x, int x_dtype, int64_t xs_lev, int64_t ldx, void* y, int y_dtype, int64_t ys_lev, int64_t ys_batch, int64_t n_batch, int64_t n_lev, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf) {
+  return guarded([&] {
+    CfCall c;
+    const CfCall* use;
+    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
+    return smm_group_apply_sb_impl(g, x, x_dtype, xs_lev, ldx, y, y_dtype, ys_lev, ys_batch, n_batch, n_lev, level_index, masked_levels, remap_area_min, flags, stream, use);
+  });
+}
+
+int smm_group_apply_host_cf(smm_group_t g, const void* x_host, int x_dtype, void* y_host, int y_dtype, int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, int64_t chunk_outer, const smm_cf_decode_t* cf) {
+  return guarded([&] {
+    CfCall c;
+    const CfCall* use;
+    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
+    return smm_group_apply_host_impl(g, x_host, x_dtype, y_host, y_dtype, n_outer, n_lev, n_inner, transpose, level_index, masked_levels, remap_area_min, flags, chunk_outer, use);
+  });
 }
 
 int smm_operator_launch_info(smm_operator_t op, int x_dtype, int64_t n_batch, unsigned flags, int* kernel, int* j_per_block, int* rows_per_step, int* rows_per_block, int64_t* n_blocks, int64_t* lds_bytes, int* big_operator) {

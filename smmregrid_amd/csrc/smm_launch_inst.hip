@@ -9,11 +9,14 @@
 
 namespace smm_launch {
 #ifdef SMM_PACKED
-// CF-packed 16-bit X decoded to SMM_XT in registers (PackedX, smm_kernels.hpp): kernel A and kernel C, f64 results
+// CF-packed 16-bit X decoded to SMM_XT in registers (PackedX, smm_kernels.hpp): kernel A, kernel C and the grouped
+// kernel C of level groups, f64 results
 #define SMM_INST_PACKED(Q)                                                                                          \
   template int launch_sell<PackedX<Q, SMM_XT>, double, SMM_SKIPNA != 0>(const ApplyArgs&, int64_t, bool, unsigned,  \
                                                                         hipStream_t);                               \
-  template int launch_sb<PackedX<Q, SMM_XT>, double, SMM_SKIPNA != 0>(const SbArgs&, bool, unsigned, hipStream_t);
+  template int launch_sb<PackedX<Q, SMM_XT>, double, SMM_SKIPNA != 0>(const SbArgs&, bool, unsigned, hipStream_t); \
+  template int launch_sb_group<PackedX<Q, SMM_XT>, double, SMM_SKIPNA != 0>(const SbGroupArgs&, bool, unsigned,     \
+                                                                            hipStream_t);
 SMM_INST_PACKED(int16_t)
 SMM_INST_PACKED(uint16_t)
 #undef SMM_INST_PACKED

@@ -356,14 +356,19 @@ class OperatorGroup:
         return self
 
     def launch_info(self, n_outer, n_lev, n_inner=1, dtype=np.float64, flags=0):
-        return _launch_info("smm_group_launch_info", self.handle, dtype_code(np.dtype(dtype)),
+        """Launch geometry `apply` would use (nothing is launched).  dtype int16 / uint16: a CF-packed field given
+        with `cf=` (always the SELL kernel)."""
+        code = field_dtype_code(dtype, cf=True) if is_packed_dtype(dtype) else dtype_code(np.dtype(dtype))
+        return _launch_info("smm_group_launch_info", self.handle, code,
                             (int(n_outer), int(n_lev), int(n_inner)), flags)
 
     def apply(self, x, level_index, masked_levels=None, y=None, masked=False, remap_area_min=0.0,
-              transpose=True, out_dtype=np.float64, flags=0, stream=None, skipna=False):
+              transpose=True, out_dtype=np.float64, flags=0, stream=None, skipna=False, cf=None):
         """x: DeviceArray (n_outer, n_lev, n_inner, S) -- or (..., ldx) with a padded row pitch ldx >= S.  Returns
         (n_outer, n_inner, n_lev, D) when transpose (regrid.py:420-427) else
-        (n_lev, n_outer, n_inner, D) (the concat order, regrid.py:410)."""
+        (n_lev, n_outer, n_inner, D) (the concat order, regrid.py:410).
+        cf: a `CFDecode` -- x holds the raw int16 / uint16 of a CF-packed field, decoded inside the kernel with one
+        rule for every level (smm_group_apply_cf; bit-identical to applying `cf.decode` first; float64 results only)."""
         if not isinstance(x, DeviceArray) or x.ndim != 4 or x.shape[3] < self.n_src:
             raise ValueError(f"X must be a DeviceArray (n_outer, n_lev, n_inner, >= {self.n_src})")
         # the last axis may be a padded row pitch (>= S): rows that start on 128-B lines (a multiple
@@ -383,6 +388,14 @@ class OperatorGroup:
             raise ValueError(f"Y must be {shape}, got {y.shape}")
         xs = (n_lev * n_inner * S, n_inner * S, S)
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        if cf is not None:
+            code = field_dtype_code(x.dtype, cf)
+            st = cf._struct(x.dtype)
+            _lib.call("smm_group_apply_cf", self.handle, ctypes.c_void_p(x.ptr), code,
+                      xs[0], xs[1], xs[2], ctypes.c_void_p(y.ptr), dtype_code(y.dtype),
+                      ys[0], ys[1], ys[2], n_outer, n_lev, n_inner, _cptr(lev), _cptr(ml),
+                      float(remap_area_min), fl, _stream_handle(stream), ctypes.byref(st))
+            return y
         _lib.call("smm_group_apply", self.handle, ctypes.c_void_p(x.ptr), dtype_code(x.dtype),
                   xs[0], xs[1], xs[2], ctypes.c_void_p(y.ptr), dtype_code(y.dtype),
                   ys[0], ys[1], ys[2], n_outer, n_lev, n_inner, _cptr(lev), _cptr(ml),
@@ -391,13 +404,14 @@ class OperatorGroup:
 
     def apply_sb(self, x, level_index, masked_levels=None, y=None, masked=False, remap_area_min=0.0,
                  transpose=True, out_dtype=np.float64, flags=0, stream=None, keep_batch_fastest=False, n_batch=None,
-                 skipna=False):
+                 skipna=False, cf=None):
         """Masked levels for a field kept batch-fastest per level: x is a DeviceArray (n_lev, S, B) --
         per data level the B batch values of each source cell contiguous.  Returns (B, n_lev, D) when
         transpose (regrid.py:420-427) else (n_lev, B, D); bit-identical to `apply` on the transposed field.
         keep_batch_fastest: the result stays batch-fastest per level, (n_lev, D, B) tagged "sb".
         All data levels run in one grouped launch (several for more than 88 levels), ordered on `stream`.
-        n_batch: batch entries when the last axis of x is a padded pitch (see SparseOperator.apply_sb)."""
+        n_batch: batch entries when the last axis of x is a padded pitch (see SparseOperator.apply_sb).
+        cf: a `CFDecode` for a raw int16 / uint16 field (see `apply`; smm_group_apply_sb_cf)."""
         if not isinstance(x, DeviceArray) or x.ndim != 3 or x.shape[1] != self.n_src:
             raise ValueError(f"X must be a DeviceArray (n_lev, {self.n_src}, B)")
         n_lev, S, ldx = x.shape
@@ -417,17 +431,28 @@ class OperatorGroup:
             raise ValueError(f"Y must be {shape}, got {y.shape}")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
         fl |= _lib.APPLY_SB_Y_SB if keep_batch_fastest else 0
+        if cf is not None:
+            code = field_dtype_code(x.dtype, cf)
+            st = cf._struct(x.dtype)
+            _lib.call("smm_group_apply_sb_cf", self.handle, ctypes.c_void_p(x.ptr), code,
+                      S * max(ldx, 1), max(ldx, 1), ctypes.c_void_p(y.ptr), dtype_code(y.dtype), ys_lev, ys_b, B, n_lev,
+                      _cptr(lev), _cptr(ml), float(remap_area_min), fl, _stream_handle(stream), ctypes.byref(st))
+            return y
         _lib.call("smm_group_apply_sb", self.handle, ctypes.c_void_p(x.ptr), dtype_code(x.dtype), S * max(ldx, 1),
                   max(ldx, 1), ctypes.c_void_p(y.ptr), dtype_code(y.dtype), ys_lev, ys_b, B, n_lev, _cptr(lev),
                   _cptr(ml), float(remap_area_min), fl, _stream_handle(stream))
         return y
 
     def apply_host(self, x, level_index, masked_levels=None, masked=False, remap_area_min=0.0,
-                   transpose=True, out_dtype=np.float64, flags=0, chunk_outer=0, skipna=False):
+                   transpose=True, out_dtype=np.float64, flags=0, chunk_outer=0, skipna=False, cf=None):
         """Host (numpy) variant: x of shape (n_outer, n_lev, n_inner, S); chunks of the outer
-        axis stream through the group's H2D / kernel / D2H pipeline (smm_group_apply_host)."""
+        axis stream through the group's H2D / kernel / D2H pipeline (smm_group_apply_host).
+        cf: a `CFDecode` -- x is the raw int16 / uint16 of a CF-packed field: it is staged, packed and shipped as
+        2-byte elements and decoded inside the kernels (smm_group_apply_host_cf)."""
         x = np.asarray(x)
-        if x.dtype not in (np.float32, np.float64):
+        if cf is not None and not is_packed_dtype(x.dtype):
+            raise TypeError(f"a CFDecode rule goes with a raw int16 / uint16 field, not {x.dtype}")
+        if cf is None and x.dtype not in (np.float32, np.float64):
             x = x.astype(np.float64)
         x = np.ascontiguousarray(x)
         if x.ndim != 4 or x.shape[3] != self.n_src:
@@ -437,6 +462,12 @@ class OperatorGroup:
         shape = (n_outer, n_inner, n_lev, self.n_dst) if transpose else (n_lev, n_outer, n_inner, self.n_dst)
         out = result_cache.empty(shape, out_dtype)
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        if cf is not None:
+            st = cf._struct(x.dtype)
+            _lib.call("smm_group_apply_host_cf", self.handle, _cptr(x), field_dtype_code(x.dtype, cf), _cptr(out),
+                      dtype_code(out.dtype), n_outer, n_lev, n_inner, int(bool(transpose)), _cptr(lev),
+                      _cptr(ml), float(remap_area_min), fl, int(chunk_outer), ctypes.byref(st))
+            return out
         _lib.call("smm_group_apply_host", self.handle, _cptr(x), dtype_code(x.dtype), _cptr(out),
                   dtype_code(out.dtype), n_outer, n_lev, n_inner, int(bool(transpose)), _cptr(lev),
                   _cptr(ml), float(remap_area_min), fl, int(chunk_outer))

@@ -56,7 +56,8 @@ class Regridder(object):
                  method='con', remap_area_min=DEFAULT_AREA_MIN, transpose=True, mask_dim=None,
                  vertical_dim=None, horizontal_dims=None, cdo_extra=None, cdo_options=None,
                  check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=np.float64,
-                 lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False):
+                 lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False,
+                 packed_levels=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -87,6 +88,12 @@ class Regridder(object):
         # file opened undecoded: io.open_dataset(path, decode=False)) is regridded raw -- shipped and gathered as
         # 2-byte elements, decoded inside the kernels (CFDecode) -- with the bits of a host decode
         self.packed = bool(packed)
+        # packed_levels (with packed=True): packed variables on masked-level (3-D) weights are regridded raw too,
+        # through the level-group entries (smm_group_apply*_cf).  Off by default: such a variable is decoded on
+        # the host first, as before
+        self.packed_levels = bool(packed_levels)
+        if self.packed_levels and not self.packed:
+            raise ValueError('packed_levels=True needs packed=True')
         # the reference always yields float64 (result_type(x, f64)); float32 is an opt-in narrowing store
         self.out_dtype = np.dtype(out_dtype)
         if self.out_dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -276,14 +283,16 @@ class Regridder(object):
             # to regrid, and the empty result is dropped from a Dataset (regrid.py:308-312, :262-264)
             return DataArray(data=None)
         cf = self._packed_rule(source_data) if self.packed else None
-        if cf is not None and (datagridtype.mask_dim or self.out_dtype != np.dtype(np.float64)):
-            # level groups and float32 results take no packed input: decoded on the host, regridded as before
+        if cf is not None and ((datagridtype.mask_dim and not self.packed_levels)
+                               or self.out_dtype != np.dtype(np.float64)):
+            # float32 results take no packed input, level groups only with packed_levels=True: decoded on the host,
+            # regridded as before
             self.loggy.info("packed variable %s is decoded on the host (%s)", source_data.name,
                             "masked levels" if datagridtype.mask_dim else "out_dtype float32")
             source_data = self._decode_on_host(source_data, cf)
             cf = None
         if datagridtype.mask_dim:
-            out = self.regrid3d(source_data, datagridtype)
+            out = self.regrid3d(source_data, datagridtype, cf=cf)
         else:
             out = self.regrid2d(source_data, datagridtype, cf=cf)
         if cf is not None:
@@ -451,9 +460,10 @@ class Regridder(object):
                             tgt_shape, tgt_dims)
 
     # ------------------------------------------------------------------ apply (masked levels)
-    def regrid3d(self, source_data, datagridtype):
+    def regrid3d(self, source_data, datagridtype, cf=None):
         """regrid.py:339-427 as one grouped launch: per data level the nearest
-        weights level (tolerance 1e-3) selects operator, mask and frac."""
+        weights level (tolerance 1e-3) selects operator, mask and frac.  cf: the CFDecode of a raw int16 / uint16
+        field (packed=True, packed_levels=True)."""
         source_data = from_xarray(source_data)
         gridtype = self._get_gridtype(datagridtype)
         if gridtype is None:
@@ -523,22 +533,23 @@ class Regridder(object):
                 if x.shape[1] != S:
                     raise ValueError(f"source grid has {x.shape[1]} cells, weights expect {S}")
                 y = group.apply_sb(x, level_index, masked_levels, masked=any_masked, remap_area_min=area_min,
-                                   transpose=transpose, out_dtype=out_dtype, keep_batch_fastest=sb_out, skipna=skipna)
+                                   transpose=transpose, out_dtype=out_dtype, keep_batch_fastest=sb_out, skipna=skipna,
+                                   cf=cf)
                 return y.reshape(*out_shape)
             if isinstance(src, DeviceArray):
                 x = src.reshape(n_outer, n_lev, n_inner, -1)
                 y = group.apply(x, level_index, masked_levels, masked=any_masked, remap_area_min=area_min,
-                                transpose=transpose, out_dtype=out_dtype, skipna=skipna)
+                                transpose=transpose, out_dtype=out_dtype, skipna=skipna, cf=cf)
                 return y.reshape(*out_shape)
             host = src.compute() if isinstance(src, LazyArray) else np.asarray(src)   # a dask field is computed here
-            if host.dtype not in (np.float32, np.float64):
+            if cf is None and host.dtype not in (np.float32, np.float64):
                 host = host.astype(np.float64)
             host = np.ascontiguousarray(host).reshape(n_outer, n_lev, n_inner, -1)
             if host.shape[3] != S:
                 raise ValueError(f"source grid has {host.shape[3]} cells, weights expect {S}")
             # host field: chunks of the outer axis stream through the group's pipeline
             out = group.apply_host(host, level_index, masked_levels, masked=any_masked, remap_area_min=area_min,
-                                   transpose=transpose, out_dtype=out_dtype, skipna=skipna)
+                                   transpose=transpose, out_dtype=out_dtype, skipna=skipna, cf=cf)
             return out.reshape(out_shape)
 
         out_data = LazyArray(out_shape, out_dtype, compute) if self.lazy else compute()
