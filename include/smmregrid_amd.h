@@ -55,7 +55,7 @@ enum {
 enum {
   SMM_F32 = 0,
   SMM_F64 = 1,
-  SMM_I16 = 2,  /* CF-packed fields, X only, through the _cf entries below (every other entry: SMM_ERR_UNSUPPORTED) */
+  SMM_I16 = 2,  /* CF-packed fields: X through the _cf entries below, Y through the _pk entries (every other entry: SMM_ERR_UNSUPPORTED) */
   SMM_U16 = 3
 };
 
@@ -72,6 +72,21 @@ typedef struct smm_cf_decode_t {
   int n_fill;        /* 0, 1 or 2 */
   int decode_dtype;  /* SMM_F32 or SMM_F64 */
 } smm_cf_decode_t;
+
+/* CF-packed RESULTS (the _pk entries): how a float64 result v becomes a raw element q of y_dtype SMM_I16 / SMM_U16,
+ * always in float64 arithmetic:
+ *     t = (v - offset) / scale;                                 two rounded operations, IEEE division (no reciprocal)
+ *     r = rint(t);                                              ties to even
+ *     q = (!isfinite(v) || r < MIN || r > MAX) ? fill : (raw type)r
+ * NaN results (masked cells, fills, remap_area_min) and values that round outside the raw range become `fill`: there
+ * is no wrap-around and no saturation.  A valid value that rounds onto `fill` is stored as is.  The stored bits are
+ * those of the same rule applied on the host to the float64 result of the plain / _cf entry.  An absent scale /
+ * offset is 1 / 0; scale must be finite and non-zero, offset finite, fill representable in the raw type, reserved 0. */
+typedef struct smm_cf_encode_t {
+  double scale, offset;
+  int32_t fill;
+  int32_t reserved;  /* 0 */
+} smm_cf_encode_t;
 
 /* smm_apply flags.  Bits outside this set are refused with SMM_ERR_INVALID by every entry that takes `flags`
  * (ABI <= 4 encoded kernel variants in bits 16..23: those are smm_debug_set_tuning knobs now). */
@@ -330,6 +345,35 @@ int smm_apply_host_cf(smm_operator_t op,
                       const smm_cf_decode_t* cf);
 
 /*
+ * The three _cf entries with a CF-packed RESULT: enc != NULL stores Y as raw 2-byte integers, encoded inside the
+ * kernels' stores by *enc (smm_cf_encode_t above); y_dtype must then be SMM_I16 / SMM_U16, y 2-byte aligned and ldy in
+ * 2-byte elements -- a quarter of the f64 result in HBM and over PCIe (smm_apply_host_pk stages, copies and counts
+ * SMM_HOST_STAT_D2H_BYTES in 2-byte cells).  enc == NULL is the _cf entry unchanged.  X is float (cf == NULL) or packed
+ * with Y's own raw type (a packed X of the other raw type: SMM_ERR_UNSUPPORTED).  SMM_ERR_INVALID, before any device
+ * is touched: enc != NULL with a float y_dtype, an integer y_dtype without enc, a fill the raw type cannot hold, a
+ * zero or non-finite scale, a non-finite offset, reserved != 0.  Packed results run the SELL kernel (smm_apply_pk, the
+ * whole-row chunks of smm_apply_host_pk) or the batch-fastest kernel, for float X too: the LDS tile kernel is not
+ * built for them and SMM_APPLY_KERNEL_TILE with enc is SMM_ERR_UNSUPPORTED.  MASKED, SKIPNA, SB_PACKED, SB_Y_SB,
+ * HOST_NO_PACK, KERNEL_SELL and the split of grids beyond 2^31 - 1 blocks behave as for float Y; a batch-fastest
+ * packed result (SB_Y_SB) is what a following smm_apply_sb_cf consumes.  Level groups have no _pk entries.
+ */
+int smm_apply_pk(smm_operator_t op,
+                 const void* x, int x_dtype, int64_t ldx,
+                 void* y, int y_dtype, int64_t ldy,
+                 int64_t n_batch, double remap_area_min, unsigned flags, void* stream,
+                 const smm_cf_decode_t* cf, const smm_cf_encode_t* enc);
+int smm_apply_sb_pk(smm_operator_t op,
+                    const void* x, int x_dtype, int64_t ldx,
+                    void* y, int y_dtype, int64_t ldy,
+                    int64_t n_batch, double remap_area_min, unsigned flags, void* stream,
+                    const smm_cf_decode_t* cf, const smm_cf_encode_t* enc);
+int smm_apply_host_pk(smm_operator_t op,
+                      const void* x_host, int x_dtype, int64_t ldx,
+                      void* y_host, int y_dtype, int64_t ldy,
+                      int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows,
+                      const smm_cf_decode_t* cf, const smm_cf_encode_t* enc);
+
+/*
  * Masked-level apply (regrid.py:387-418 in one launch).  The kept dims of the
  * field are viewed as (n_outer, n_lev, n_inner) around the mask dimension;
  * data level l uses group member level_index[l] (host int32[n_lev], result of
@@ -489,6 +533,7 @@ enum {
   SMM_TUNE_SB_LDS_PAD,          /* batch-fastest kernels: extra LDS bytes per wave, capping the waves per CU    */
   SMM_TUNE_HOST_PACK_STORES,    /* host pipelines: 1 = the pack writes its staging block with plain (not non-temporal) stores */
   SMM_TUNE_HOST_CHUNK_KB,       /* smm_group_apply_host: > 0 forces level-major packed chunks with this staging budget in KiB (default: 256 MiB, only when a block of the outer axis with all levels does not fit) */
+  SMM_TUNE_SB_PACKED_Y_ROWS,    /* batch-fastest kernel, packed Y (_pk entries): destination rows per tile, 16 or 64 */
   SMM_TUNE_COUNT
 };
 int smm_debug_set_tuning(int knob, int value, int* previous);

@@ -20,7 +20,7 @@ SMM_ERR_INTERNAL = 6
 
 SMM_F32 = 0
 SMM_F64 = 1
-SMM_I16 = 2     # CF-packed fields: the _cf entries only
+SMM_I16 = 2     # CF-packed fields: X through the _cf entries, Y through the _pk entries
 SMM_U16 = 3
 
 APPLY_MASKED = 1 << 0
@@ -36,7 +36,7 @@ APPLY_KERNEL_TILE = 1 << 9
 # smm_debug_set_tuning knobs (tests, tools, benchmarks; the results do not depend on them)
 TUNE_KNOBS = ("sell_batch_rows", "tile_walk", "tile_staging", "tile_rows_per_step", "tile_x_loads",
               "tile_split_rows", "tile_links", "xcd_run", "sb_strip", "sb_loads", "sb_level_launches", "sb_lds_pad",
-              "host_pack_stores", "host_chunk_kb")
+              "host_pack_stores", "host_chunk_kb", "sb_packed_y_rows")
 TUNE = {name: i for i, name in enumerate(TUNE_KNOBS)}
 STAGING_REGISTERS, STAGING_DMA = 1, 2
 
@@ -70,6 +70,14 @@ class CfDecodeStruct(ctypes.Structure):
 
 
 _cfp = ctypes.POINTER(CfDecodeStruct)
+
+
+class CfEncodeStruct(ctypes.Structure):
+    """smm_cf_encode_t"""
+    _fields_ = [("scale", _dbl), ("offset", _dbl), ("fill", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+_cep = ctypes.POINTER(CfEncodeStruct)
 
 # name -> argtypes; every entry point returns int status except the two noted
 SIGNATURES = {
@@ -127,6 +135,9 @@ SIGNATURES = {
     "smm_apply_cf": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _p, _cfp],
     "smm_apply_sb_cf": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _p, _cfp],
     "smm_apply_host_cf": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _i64, _cfp],
+    "smm_apply_pk": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _p, _cfp, _cep],
+    "smm_apply_sb_pk": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _p, _cfp, _cep],
+    "smm_apply_host_pk": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _i64, _cfp, _cep],
     "smm_group_apply": [_p, _p, _int, _i64, _i64, _i64, _p, _int, _i64, _i64, _i64,
                         _i64, _i64, _i64, _p, _p, _dbl, _uint, _p],
     "smm_group_prepare_sb": [_p],

@@ -69,6 +69,23 @@ SMM_EXTERN_PACKED(int16_t, double, true)
 SMM_EXTERN_PACKED(uint16_t, float, true)
 SMM_EXTERN_PACKED(uint16_t, double, true)
 #undef SMM_EXTERN_PACKED
+// CF-packed 16-bit Y (PackedY<raw>): kernels A and C of single operators, float X or packed X of the same raw type
+#define SMM_EXTERN_PACKED_Y(XT, Q, NA)                                                                          \
+  extern template int launch_sell<XT, PackedY<Q>, NA>(const ApplyArgs&, int64_t, bool, unsigned, hipStream_t); \
+  extern template int launch_sb<XT, PackedY<Q>, NA>(const SbArgs&, bool, unsigned, hipStream_t);
+#define SMM_EXTERN_PACKED_Y_Q(Q, NA)              \
+  SMM_EXTERN_PACKED_Y(float, Q, NA)               \
+  SMM_EXTERN_PACKED_Y(double, Q, NA)              \
+  SMM_EXTERN_PACKED_Y(PackedX<Q SMM_COMMA float>, Q, NA)  \
+  SMM_EXTERN_PACKED_Y(PackedX<Q SMM_COMMA double>, Q, NA)
+#define SMM_COMMA ,
+SMM_EXTERN_PACKED_Y_Q(int16_t, false)
+SMM_EXTERN_PACKED_Y_Q(uint16_t, false)
+SMM_EXTERN_PACKED_Y_Q(int16_t, true)
+SMM_EXTERN_PACKED_Y_Q(uint16_t, true)
+#undef SMM_COMMA
+#undef SMM_EXTERN_PACKED_Y_Q
+#undef SMM_EXTERN_PACKED_Y
 }  // namespace smm_launch
 
 // FN<XT, YT, SKIPNA>(...) for the run-time dtypes (SMM_F64 / SMM_F32) and SMM_APPLY_SKIPNA
@@ -89,6 +106,20 @@ SMM_EXTERN_PACKED(uint16_t, double, true)
   (((FLAGS) & SMM_APPLY_SKIPNA) ? SMM_DISPATCH_CF_NA(FN, true, XD, DD, __VA_ARGS__)    \
                                 : SMM_DISPATCH_CF_NA(FN, false, XD, DD, __VA_ARGS__))
 
+// FN<X, PackedY<raw>, SKIPNA>(...) for packed Y (YD: SMM_I16 / SMM_U16); X float (XD) or packed with Y's raw type,
+// decoded to DD
+#define SMM_DISPATCH_PK_Q(FN, NA, Q, XD, DD, ...)                                                      \
+  ((XD) == SMM_F64   ? FN<double, PackedY<Q>, NA>(__VA_ARGS__)                                         \
+   : (XD) == SMM_F32 ? FN<float, PackedY<Q>, NA>(__VA_ARGS__)                                          \
+   : (DD) == SMM_F64 ? FN<PackedX<Q, double>, PackedY<Q>, NA>(__VA_ARGS__)                             \
+                     : FN<PackedX<Q, float>, PackedY<Q>, NA>(__VA_ARGS__))
+#define SMM_DISPATCH_PK_NA(FN, NA, YD, XD, DD, ...)                                  \
+  ((YD) == SMM_I16 ? SMM_DISPATCH_PK_Q(FN, NA, int16_t, XD, DD, __VA_ARGS__)         \
+                   : SMM_DISPATCH_PK_Q(FN, NA, uint16_t, XD, DD, __VA_ARGS__))
+#define SMM_DISPATCH_PK(FN, FLAGS, YD, XD, DD, ...)                                        \
+  (((FLAGS) & SMM_APPLY_SKIPNA) ? SMM_DISPATCH_PK_NA(FN, true, YD, XD, DD, __VA_ARGS__)    \
+                                : SMM_DISPATCH_PK_NA(FN, false, YD, XD, DD, __VA_ARGS__))
+
 namespace {
 
 thread_local std::string g_last_error;
@@ -108,7 +139,17 @@ struct CfCall {
   int decode_dtype;
 };
 // X dtype check shared by the apply paths: float always, packed only through the _cf entries
-inline int check_x_dtype(int x_dtype, int y_dtype, const CfCall* cf) {
+// (enc: a validated smm_cf_encode_t of the _pk entries -- y_dtype is then SMM_I16 / SMM_U16, checked by make_enc)
+inline int check_x_dtype(int x_dtype, int y_dtype, const CfCall* cf, const CfOutParams* enc = nullptr) {
+  if (enc) {
+    if (!is_packed_dtype(y_dtype)) return fail(SMM_ERR_INVALID, "an encode rule needs y_dtype SMM_I16 or SMM_U16");
+    if (is_float_dtype(x_dtype)) return SMM_OK;
+    if (!(cf && is_packed_dtype(x_dtype)))
+      return fail(SMM_ERR_UNSUPPORTED, "field dtype must be SMM_F32, SMM_F64 or, with a decode rule, SMM_I16 / SMM_U16");
+    if (x_dtype != y_dtype)
+      return fail(SMM_ERR_UNSUPPORTED, "a packed field produces packed results of its own raw type only");
+    return SMM_OK;
+  }
   if (!(is_float_dtype(x_dtype) || (cf && is_packed_dtype(x_dtype))) || !is_float_dtype(y_dtype))
     return fail(SMM_ERR_UNSUPPORTED, is_packed_dtype(x_dtype)
                                          ? "SMM_I16 / SMM_U16 fields go through the _cf entries (smm_apply_cf, ...)"
@@ -434,14 +475,15 @@ int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t*
               int64_t max_row_nnz, const void* x, int x_dtype, int64_t xs_o, int64_t xs_l,
               int64_t xs_i, void* y, int y_dtype, int64_t ys_o, int64_t ys_l, int64_t ys_i,
               int64_t n_outer, int64_t n_lev, int64_t n_inner, double area_min, unsigned flags,
-              hipStream_t s, LaunchInfo* info_only = nullptr, const CfCall* cf = nullptr) {
+              hipStream_t s, LaunchInfo* info_only = nullptr, const CfCall* cf = nullptr,
+              const CfOutParams* enc = nullptr) {
   if (n_outer < 0 || n_lev < 0 || n_inner < 0) return fail(SMM_ERR_INVALID, "negative batch size");
   if (n_outer == 0 || n_lev == 0 || n_inner == 0 || n_dst == 0) return SMM_OK;
   if (!info_only && (!x || !y)) return fail(SMM_ERR_INVALID, "null field pointer");
   const bool packed = is_packed_dtype(x_dtype);
   static const CfCall kInfoCf{{1.0, 0.0, 0x7fffffff, 0x7fffffff}, SMM_F32};   // launch info: the geometry does not depend on it
   if (packed && info_only && !cf) cf = &kInfoCf;
-  if (int drc = check_x_dtype(x_dtype, y_dtype, cf)) return drc;
+  if (int drc = check_x_dtype(x_dtype, y_dtype, cf, enc)) return drc;
   if (!(area_min >= 0.0 && area_min <= 1.0))
     return fail(SMM_ERR_INVALID, "remap_area_min must be within [0, 1]");  // regrid.py:124-125
 
@@ -466,17 +508,20 @@ int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t*
   a.masked = (flags & SMM_APPLY_MASKED) ? 1 : 0;
   const bool fill = !(flags & SMM_APPLY_NO_FILL);
   if (packed) a.cf = cf->p;
+  if (enc) a.cfo = *enc;
 
   const size_t xsz = dtype_size(x_dtype);
   bool use_tile = false;
   // SMM_APPLY_SKIPNA: tile forms without a skipna variant (split rows, rows streamed from L2) run kernel A instead
   const bool tile_skipna_ok = !(flags & SMM_APPLY_SKIPNA) ||
                               smm_launch::tile_has_skipna(tile_which, tile_which >= 2 ? tile_which - 1 : 0, max_row_nnz);
-  if (packed) {
-    // the LDS tile kernel stages 16-B pieces of 4- or 8-byte elements: packed X runs kernel A whatever the plan
+  if (packed || enc) {
+    // the LDS tile kernel stages 16-B pieces of 4- or 8-byte elements: packed X runs kernel A whatever the plan, and
+    // so do packed results (the tile kernel is not built for them either)
     if (flags & SMM_APPLY_KERNEL_TILE)
-      return fail(SMM_ERR_UNSUPPORTED, "the LDS tile kernel is not built for packed fields (SMM_I16 / SMM_U16)");
-    if (!info_only && ((uintptr_t)x % 2) != 0) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
+      return fail(SMM_ERR_UNSUPPORTED, "the LDS tile kernel is not built for packed fields or results (SMM_I16 / SMM_U16)");
+    if (!info_only && ((uintptr_t)x % xsz) != 0) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
+    if (!info_only && enc && ((uintptr_t)y % 2) != 0) return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
   } else if (flags & SMM_APPLY_KERNEL_TILE) {
     if (!tile_ok) return fail(SMM_ERR_UNSUPPORTED, "operator has no LDS tile plan");
     if (!tile_skipna_ok)
@@ -532,13 +577,15 @@ int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t*
     const int bt = smm_launch::sell_batch_rows(t.n_j);
     return t.n_dblocks * ((t.n_j + bt - 1) / bt) * n_lev;
   };
-  const size_t ysz = y_dtype == SMM_F64 ? 8 : 4;
+  const size_t ysz = dtype_size(y_dtype);
   auto launch_part = [&](int64_t o0, int64_t n_o, int64_t i0, int64_t n_i) -> int {
     ApplyArgs p = a;
     p.x = (const char*)x + (o0 * xs_o + i0 * xs_i) * (int64_t)xsz;
     p.y = (char*)y + (o0 * ys_o + i0 * ys_i) * (int64_t)ysz;
     p.n_j = n_o * n_i;
     p.n_inner = n_i;
+    if (enc)
+      return SMM_DISPATCH_PK(launch_sell, flags, y_dtype, x_dtype, (cf ? cf->decode_dtype : SMM_F64), p, n_lev, fill, flags, s);
     if (packed) return SMM_DISPATCH_CF(launch_sell, flags, x_dtype, cf->decode_dtype, p, n_lev, fill, flags, s);
     if (use_tile)
       return SMM_DISPATCH(launch_tile, p, n_lev, tile_which, tile_max_chunks, max_row_nnz, tile_flags, fill, flags, s);
@@ -1112,7 +1159,7 @@ static int smm_operator_plan_info_impl(smm_operator_t op, int* kernel_kind, int6
 
 static int smm_apply_impl(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype,
               int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream,
-              const CfCall* cf = nullptr) {
+              const CfCall* cf = nullptr, const CfOutParams* enc = nullptr) {
   if (int frc = check_flags(flags)) return frc;
   if (!op) return fail(SMM_ERR_INVALID, "null operator");
   if (n_batch > 0 && (ldx < op->csr.n_src || ldy < op->csr.n_dst))
@@ -1127,7 +1174,7 @@ static int smm_apply_impl(smm_operator_t op, const void* x, int x_dtype, int64_t
   const smm_operator::TilePlan& pl = op->plan[pw];
   return run_apply(op->d_desc, nullptr, nullptr, op->csr.n_src, op->csr.n_dst, pw, pl.valid,
                    pl.preferred, (pl.reuse ? 1 : 0), pl.max_chunks, op->csr.max_row_nnz, x, x_dtype, ldx, 0, 0, y, y_dtype, ldy,
-                   0, 0, n_batch, 1, 1, remap_area_min, flags, (hipStream_t)stream, nullptr, cf);
+                   0, 0, n_batch, 1, 1, remap_area_min, flags, (hipStream_t)stream, nullptr, cf, enc);
 }
 
 static int smm_operator_prepare_sb_impl(smm_operator_t op) {
@@ -1150,13 +1197,13 @@ static int smm_operator_used_sources_impl(smm_operator_t op, int32_t* used) {
 
 static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype,
                  int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream,
-                 const CfCall* cf = nullptr) {
+                 const CfCall* cf = nullptr, const CfOutParams* enc = nullptr) {
   if (int frc = check_flags(flags)) return frc;
   if (!op) return fail(SMM_ERR_INVALID, "null operator");
   if (n_batch < 0) return fail(SMM_ERR_INVALID, "negative batch size");
   if (n_batch == 0 || op->csr.n_dst == 0) return SMM_OK;
   if (!x || !y) return fail(SMM_ERR_INVALID, "null field pointer");
-  if (int drc = check_x_dtype(x_dtype, y_dtype, cf)) return drc;
+  if (int drc = check_x_dtype(x_dtype, y_dtype, cf, enc)) return drc;
   const bool packed = is_packed_dtype(x_dtype);
   if (ldx < n_batch || ldy < ((flags & SMM_APPLY_SB_Y_SB) ? n_batch : op->csr.n_dst))
     return fail(SMM_ERR_INVALID, "ldx smaller than the batch or ldy smaller than a row of Y");
@@ -1187,11 +1234,13 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int6
   a.area_min = remap_area_min;
   a.masked = (flags & SMM_APPLY_MASKED) ? 1 : 0;
   if (packed) a.cf = cf->p;
+  if (enc) a.cfo = *enc;
   const bool fill = !(flags & SMM_APPLY_NO_FILL);
   hipStream_t s = (hipStream_t)stream;
   // grid = destination tiles x batch tiles of 128 entries: beyond the limit the batch is cut into runs of
   // whole batch tiles, launched one after the other
-  const int64_t n_dtiles = (a.n_dst + (ysz == 8 ? 16 : 32) - 1) / (ysz == 8 ? 16 : 32);
+  const int64_t td = smm_launch::sb_tile_rows(ysz);
+  const int64_t n_dtiles = (a.n_dst + td - 1) / td;
   const int64_t limit = grid_limit();
   if (n_dtiles > limit)
     return fail(SMM_ERR_INVALID, "one batch tile alone needs a launch grid beyond " + std::to_string(limit) + " workgroups");
@@ -1200,8 +1249,9 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int6
     a.x = (const char*)x + b0 * (int64_t)xsz;
     a.y = (char*)y + ((flags & SMM_APPLY_SB_Y_SB) ? b0 : b0 * ldy) * (int64_t)ysz;
     a.n_batch = std::min(part, n_batch - b0);
-    rc = packed ? SMM_DISPATCH_CF(launch_sb, flags, x_dtype, cf->decode_dtype, a, fill, flags, s)
-                : SMM_DISPATCH_ALL(launch_sb, flags, x_dtype, y_dtype, a, fill, flags, s);
+    rc = enc      ? SMM_DISPATCH_PK(launch_sb, flags, y_dtype, x_dtype, (cf ? cf->decode_dtype : SMM_F64), a, fill, flags, s)
+         : packed ? SMM_DISPATCH_CF(launch_sb, flags, x_dtype, cf->decode_dtype, a, fill, flags, s)
+                  : SMM_DISPATCH_ALL(launch_sb, flags, x_dtype, y_dtype, a, fill, flags, s);
     if (rc) return rc;
   }
   return SMM_OK;
@@ -1211,20 +1261,22 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int6
 
 static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int x_dtype, int64_t ldx, void* y_host,
                    int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags,
-                   int64_t chunk_rows, const CfCall* cf = nullptr) {
+                   int64_t chunk_rows, const CfCall* cf = nullptr, const CfOutParams* enc = nullptr) {
   if (int frc = check_flags(flags)) return frc;
   if (!op) return fail(SMM_ERR_INVALID, "null operator");
   if (n_batch < 0) return fail(SMM_ERR_INVALID, "negative batch size");
   if (n_batch == 0 || op->csr.n_dst == 0) return SMM_OK;
   if (!x_host || !y_host) return fail(SMM_ERR_INVALID, "null field pointer");
-  if (int drc = check_x_dtype(x_dtype, y_dtype, cf)) return drc;
+  if (int drc = check_x_dtype(x_dtype, y_dtype, cf, enc)) return drc;
   if ((uintptr_t)x_host % dtype_size(x_dtype)) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
+  if (enc && (uintptr_t)y_host % 2) return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
   const int64_t S = op->csr.n_src, D = op->csr.n_dst;
   if (ldx < S || ldy < D) return fail(SMM_ERR_INVALID, "ldx/ldy smaller than the grid size");
   DeviceGuard guard(op->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
 
-  const size_t xsz = dtype_size(x_dtype), ysz = dtype_size(y_dtype);   // packed X is staged, packed and shipped raw: 2 B per cell
+  // packed X is staged, packed and shipped raw: 2 B per cell; a packed Y (enc) comes back, is staged and copied out raw too
+  const size_t xsz = dtype_size(x_dtype), ysz = dtype_size(y_dtype);
   const size_t xrow = (size_t)ldx * xsz, yrow = (size_t)ldy * ysz;   // host row pitches
   // device rows start on 128-B lines: the tile plan stages whole lines of a row, and a row that
   // starts mid-line makes every staged run of chunks straddle one line more (config 3's 1442x1021
@@ -1336,12 +1388,12 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int x_dtyp
     if (pack)
       rc = smm_apply_sb_impl(op, pipe.dx[b], x_dtype, rows, pipe.dy[b], y_dtype, D, rows, remap_area_min,
                          (flags & (SMM_APPLY_MASKED | SMM_APPLY_NO_FILL | SMM_APPLY_SKIPNA)) | SMM_APPLY_SB_PACKED,
-                         pipe.stream[b], cf);
+                         pipe.stream[b], cf, enc);
     else
       rc = run_apply(op->d_desc, nullptr, nullptr, S, op->csr.n_dst, pw, pl.valid, pl.preferred, (pl.reuse ? 1 : 0),
                      pl.max_chunks, op->csr.max_row_nnz, pipe.dx[b], x_dtype,
                      ldx_d, 0, 0, pipe.dy[b], y_dtype, D, 0, 0, rows, 1, 1, remap_area_min, flags,
-                     pipe.stream[b], nullptr, cf);
+                     pipe.stream[b], nullptr, cf, enc);
     if (rc) return rc;
     st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)rows * D * ysz);
     SMM_HIP(hipEventRecord(pipe.ev[b][2], pipe.stream[b]));
@@ -2089,6 +2141,74 @@ int smm_apply_host_cf(smm_operator_t op, const void* x_host, int x_dtype, int64_
     const CfCall* use;
     if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
     return smm_apply_host_impl(op, x_host, x_dtype, ldx, y_host, y_dtype, ldy, n_batch, remap_area_min, flags, chunk_rows, use);
+  });
+}
+
+}  // extern "C"
+
+namespace {
+// smm_cf_encode_t -> CfOutParams, with every refusal of the _pk entries that needs no device.  Returns SMM_OK with
+// *use = null when the call is the _cf entry unchanged (enc == NULL).
+int make_enc(const smm_cf_encode_t* enc, int y_dtype, unsigned flags, CfOutParams* out, const CfOutParams** use) {
+  *use = nullptr;
+  if (!enc) {
+    if (is_packed_dtype(y_dtype))
+      return fail(SMM_ERR_INVALID, "SMM_I16 / SMM_U16 results need an encode rule (enc is NULL)");
+    return SMM_OK;
+  }
+  if (!is_packed_dtype(y_dtype))
+    return fail(SMM_ERR_INVALID, "an encode rule was given with a float y_dtype: pass enc = NULL, or y_dtype SMM_I16 / SMM_U16");
+  if (enc->reserved != 0) return fail(SMM_ERR_INVALID, "enc->reserved must be 0");
+  if (!std::isfinite(enc->scale) || enc->scale == 0.0) return fail(SMM_ERR_INVALID, "enc->scale must be finite and non-zero");
+  if (!std::isfinite(enc->offset)) return fail(SMM_ERR_INVALID, "enc->offset must be finite");
+  const int32_t lo = y_dtype == SMM_I16 ? -32768 : 0, hi = y_dtype == SMM_I16 ? 32767 : 65535;
+  if (enc->fill < lo || enc->fill > hi) return fail(SMM_ERR_INVALID, "enc->fill is not representable in the raw type");
+  if (flags & SMM_APPLY_KERNEL_TILE)
+    return fail(SMM_ERR_UNSUPPORTED, "the LDS tile kernel is not built for packed results (SMM_I16 / SMM_U16)");
+  out->scale = enc->scale;
+  out->offset = enc->offset;
+  out->fill = enc->fill;
+  out->reserved = 0;
+  *use = out;
+  return SMM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int smm_apply_pk(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
+  return guarded([&] {
+    CfOutParams e;
+    const CfOutParams* use_e;
+    if (int rc = make_enc(enc, y_dtype, flags, &e, &use_e)) return rc;
+    CfCall c;
+    const CfCall* use;
+    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
+    return smm_apply_impl(op, x, x_dtype, ldx, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream, use, use_e);
+  });
+}
+
+int smm_apply_sb_pk(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
+  return guarded([&] {
+    CfOutParams e;
+    const CfOutParams* use_e;
+    if (int rc = make_enc(enc, y_dtype, flags, &e, &use_e)) return rc;
+    CfCall c;
+    const CfCall* use;
+    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
+    return smm_apply_sb_impl(op, x, x_dtype, ldx, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream, use, use_e);
+  });
+}
+
+int smm_apply_host_pk(smm_operator_t op, const void* x_host, int x_dtype, int64_t ldx, void* y_host, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
+  return guarded([&] {
+    CfOutParams e;
+    const CfOutParams* use_e;
+    if (int rc = make_enc(enc, y_dtype, flags, &e, &use_e)) return rc;
+    CfCall c;
+    const CfCall* use;
+    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
+    return smm_apply_host_impl(op, x_host, x_dtype, ldx, y_host, y_dtype, ldy, n_batch, remap_area_min, flags, chunk_rows, use, use_e);
   });
 }
 

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -54,6 +55,21 @@ struct PackedX {
   Q q;
 };
 
+// CF-packed results (smm_apply_pk and friends): how a float64 result becomes a raw 16-bit element; see YTraits.
+// Unused by the float-Y kernels.
+struct CfOutParams {
+  double scale, offset;
+  int32_t fill;
+  int32_t reserved;
+};
+
+// Y element type tag of a packed result: Q (int16_t / uint16_t) in memory, encoded from the float64 result.
+// External linkage like PackedX.
+template <typename Q>
+struct PackedY {
+  Q q;
+};
+
 struct ApplyArgs {
   const LevelDesc* descs;     // device array
   const int32_t* lev_map;     // device [n_lev] -> desc index, null = identity 0
@@ -75,6 +91,7 @@ struct ApplyArgs {
   int tile_bytes;    // tile kernel with R > 1: LDS bytes of one batch row's tile
   int sub_shift;     // single-wave tile kernel: a block owns 64 >> sub_shift rows of its slice
   CfParams cf;       // packed X only
+  CfOutParams cfo;   // packed Y only (appended: the offsets above stay)
 };
 
 // arguments of the batch-fastest kernel (kernel C below)
@@ -93,6 +110,7 @@ struct SbArgs {
   int xcd_remap;
   int b_fastest;           // > 0: width (destination tiles) of the strips the tiles are ordered in
   CfParams cf;             // packed X only
+  CfOutParams cfo;         // packed Y only (appended: the offsets above stay)
 };
 
 // Arguments of the batch-fastest kernel over a whole level group in ONE launch (smm_group_apply_sb).  The levels'
@@ -165,6 +183,34 @@ struct XTraits<PackedX<Q, T>> {
     v = v + (T)cf.offset;
     const int32_t qi = (int32_t)q;
     return (qi == cf.fill0 || qi == cf.fill1) ? (T)__builtin_nan("") : v;
+  }
+};
+
+// Y element types.  A float type is its own storage type and takes the plain narrowing cast.  PackedY<Q> is a
+// CF-packed result: the float64 value v of the epilogue is stored as the raw Q (int16_t / uint16_t) of the ABI's rule --
+//   t = (v - offset) / scale;  r = rint(t);  !isfinite(v) || r < min(Q) || r > max(Q) -> fill, else (Q)r
+// two rounded f64 operations (contraction off, IEEE division: no reciprocal), ties to even, the range tested on the
+// rounded double so that the convert is exact: bit-identical to the numpy statement (CFEncode.encode).  No wrap-around,
+// no saturation: what does not fit becomes the fill value.
+template <typename YT>
+struct YTraits {
+  typedef YT raw;   // what Y holds
+  static constexpr bool packed = false;
+  static __device__ __forceinline__ YT encode(double v, const CfOutParams&) { return (YT)v; }
+};
+template <typename Q>
+struct YTraits<PackedY<Q>> {
+  typedef Q raw;
+  static constexpr bool packed = true;
+  static __device__ __forceinline__ Q encode(double v, const CfOutParams& e) {
+    double t = v - e.offset;
+    t = t / e.scale;
+    const double r = __builtin_rint(t);
+    constexpr double lo = std::is_signed<Q>::value ? -32768.0 : 0.0;
+    constexpr double hi = std::is_signed<Q>::value ? 32767.0 : 65535.0;
+    const bool bad = !__builtin_isfinite(v) || r < lo || r > hi;   // a NaN r cannot occur with a finite v
+    const int32_t q = (int32_t)(bad ? 0.0 : r);
+    return (Q)(bad ? e.fill : q);
   }
 };
 
@@ -336,14 +382,15 @@ __global__ __launch_bounds__(kThreads) void smm_apply_sell_kernel(ApplyArgs a, b
 
   const int64_t j0 = jt * BT;
   typedef typename XTraits<XT>::raw XR;
+  typedef typename YTraits<YT>::raw YR;
   const XR* __restrict__ xr[BT];
-  YT* __restrict__ yr[BT];
+  YR* __restrict__ yr[BT];
 #pragma unroll
   for (int t = 0; t < BT; ++t) {
     int64_t j = j0 + t;
     if (j > a.n_j - 1) j = a.n_j - 1;
     xr[t] = (const XR*)a.x + row_off(j, l, a.n_inner, a.xs_o, a.xs_l, a.xs_i);
-    yr[t] = (YT*)a.y + row_off(j, l, a.n_inner, a.ys_o, a.ys_l, a.ys_i);
+    yr[t] = (YR*)a.y + row_off(j, l, a.n_inner, a.ys_o, a.ys_l, a.ys_i);
   }
 
   const int64_t off = L.slice_off[slice];
@@ -383,14 +430,14 @@ __global__ __launch_bounds__(kThreads) void smm_apply_sell_kernel(ApplyArgs a, b
 #pragma unroll
       for (int t = 0; t < BT; ++t) {
         if (j0 + t < a.n_j)
-          yr[t][d] = (YT)skipna_epilogue(acc[t].num, acc[t].den, acc[t].inv, tot, dead, L.frac != nullptr, frac_d,
-                                         a.area_min);
+          yr[t][d] = YTraits<YT>::encode(skipna_epilogue(acc[t].num, acc[t].den, acc[t].inv, tot, dead,
+                                                         L.frac != nullptr, frac_d, a.area_min), a.cfo);
       }
     } else {
       if (a.area_min > 0.0 && L.frac) dead = dead || (L.frac[d] < a.area_min);
 #pragma unroll
       for (int t = 0; t < BT; ++t) {
-        if (j0 + t < a.n_j) yr[t][d] = (YT)epilogue(acc[t].num, dead);
+        if (j0 + t < a.n_j) yr[t][d] = YTraits<YT>::encode(epilogue(acc[t].num, dead), a.cfo);
       }
     }
   }
@@ -1171,6 +1218,7 @@ struct SbTile {   // what does not depend on the level
   double area_min;
   int masked, xcd_remap, b_fastest;
   CfParams cf;         // packed X only (value-initialised otherwise)
+  CfOutParams cfo;     // packed Y only (value-initialised otherwise)
 };
 
 // SKIPNA (SMM_APPLY_SKIPNA): the links are tested per batch entry (RowSum) and the row's weight sum runs wave-uniform
@@ -1180,10 +1228,11 @@ template <typename XT, typename YT, int TD, int U, bool FILL, bool YSB, bool SKI
 __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32_t bid) {
   constexpr int VEC = 2;                    // batch entries per lane
   constexpr int BT = 64 * VEC;              // batch entries per tile
-  constexpr int PAD = 16 / (int)sizeof(YT); // LDS row padding: one 16-B slot (conflict-free transposed reads)
+  typedef typename YTraits<YT>::raw YR;     // element of Y in memory (a packed result: the raw 16-bit integer)
+  constexpr int PAD = 16 / (int)sizeof(YR); // LDS row padding: one 16-B slot (conflict-free transposed reads)
   constexpr int LROW = BT + PAD;
   static_assert(TD % 2 == 0 && 128 % TD == 0 && TD <= 64, "store phase: TD / 2 lanes per batch row");
-  __shared__ __attribute__((aligned(16))) YT tile[TD * LROW];
+  __shared__ __attribute__((aligned(16))) YR tile[TD * LROW];
   typedef typename XTraits<XT>::raw XR;     // element in memory (a packed field: the raw 16-bit integer, 4 B per lane)
   typedef typename XTraits<XT>::val XV;     // element in the arithmetic
   typedef XR xvec __attribute__((ext_vector_type(VEC)));
@@ -1258,18 +1307,18 @@ __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32
       const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(fb >> 32), d_local);
       frac_d = __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
     }
-    YT out[VEC];
+    YR out[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
       if constexpr (SKIPNA)
-        out[v] = (YT)skipna_epilogue(acc[v].num, acc[v].den, acc[v].inv, tot, dead, m.frac != nullptr, frac_d,
-                                     a.area_min);
+        out[v] = YTraits<YT>::encode(skipna_epilogue(acc[v].num, acc[v].den, acc[v].inv, tot, dead, m.frac != nullptr,
+                                                     frac_d, a.area_min), a.cfo);
       else
-        out[v] = (YT)epilogue(acc[v].num, dead);
+        out[v] = YTraits<YT>::encode(epilogue(acc[v].num, dead), a.cfo);
       acc[v].clear();
     }
     tot = 0.0;
-    typedef YT yvec __attribute__((ext_vector_type(VEC)));
+    typedef YR yvec __attribute__((ext_vector_type(VEC)));
     yvec o;
 #pragma unroll
     for (int v = 0; v < VEC; ++v) o[v] = out[v];
@@ -1339,14 +1388,14 @@ __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32
 
   if constexpr (YSB) {
     // batch-fastest result: row r's 128 batch entries are one contiguous run of Y row d0 + r
-    typedef YT yvec __attribute__((ext_vector_type(VEC)));
-    typedef yvec yvec_u __attribute__((aligned(sizeof(YT))));
+    typedef YR yvec __attribute__((ext_vector_type(VEC)));
+    typedef yvec yvec_u __attribute__((aligned(sizeof(YR))));
     const int64_t b = b0 + (int64_t)lane * VEC;
-    YT* __restrict__ yb = (YT*)a.y + d0 * a.ldy + b;
+    YR* __restrict__ yb = (YR*)a.y + d0 * a.ldy + b;
 #pragma unroll 4
     for (int r = 0; r < rows; ++r) {
       const yvec o = *(const yvec*)(&tile[r * LROW + lane * VEC]);
-      YT* dst = yb + (int64_t)r * a.ldy;
+      YR* dst = yb + (int64_t)r * a.ldy;
       if (b + VEC <= a.n_batch)
         __builtin_nontemporal_store(o, (yvec_u*)dst);
       else if (b < a.n_batch)
@@ -1360,18 +1409,18 @@ __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32
   constexpr int BPI = 64 / LPB;          // batch rows per store instruction
   const int dp = lane % LPB, bsub = lane / LPB;
   const int64_t dd = d0 + 2 * dp;
-  YT* __restrict__ yb = (YT*)a.y + dd;
+  YR* __restrict__ yb = (YR*)a.y + dd;
 #pragma unroll 4
   for (int i = 0; i < BT / BPI; ++i) {
     const int bloc = i * BPI + bsub;
     const int64_t b = b0 + bloc;
-    const YT v0 = tile[(2 * dp) * LROW + bloc];
-    const YT v1 = tile[(2 * dp + 1) * LROW + bloc];
+    const YR v0 = tile[(2 * dp) * LROW + bloc];
+    const YR v1 = tile[(2 * dp + 1) * LROW + bloc];
     if (b < a.n_batch) {
-      YT* dst = yb + b * a.ldy;
+      YR* dst = yb + b * a.ldy;
       if (dd + 1 < a.n_dst) {
-        typedef YT y2 __attribute__((ext_vector_type(2)));
-        typedef y2 y2_u __attribute__((aligned(sizeof(YT))));
+        typedef YR y2 __attribute__((ext_vector_type(2)));
+        typedef y2 y2_u __attribute__((aligned(sizeof(YR))));
         y2 o;
         o[0] = v0;
         o[1] = v1;
@@ -1387,7 +1436,7 @@ template <typename XT, typename YT, int TD, int U, bool FILL, bool YSB = false, 
 __global__ __launch_bounds__(64) void smm_apply_sb_kernel(SbArgs a) {
   const SbMatrix<const int64_t*, const int32_t*, const double*, const uint8_t*> m{a.rowptr, a.col, a.val, a.imask, a.frac};
   const SbTile t{a.x, a.y, a.ldx, a.ldy, a.n_batch, a.n_dst, a.n_dtiles, a.n_btiles, (uint32_t)a.n_blocks,
-                 a.area_min, a.masked, a.xcd_remap, a.b_fastest, a.cf};
+                 a.area_min, a.masked, a.xcd_remap, a.b_fastest, a.cf, a.cfo};
   sb_tile_body<XT, YT, TD, U, FILL, YSB, SKIPNA>(m, t, blockIdx.x);
 }
 
@@ -1407,8 +1456,9 @@ __global__ __launch_bounds__(64) void smm_group_apply_sb_kernel(SbGroupArgs a) {
   // the operator's arrays are immutable while a kernel runs: constant address space keeps their loads scalar
   const SbMatrix<k_i64, k_i32, k_f64, k_u8> m{(k_i64)L.rowptr, (k_i32)L.col, (k_f64)L.val, (k_u8)L.imask, (k_f64)L.frac};
   typedef typename XTraits<XT>::raw XR;   // a packed field's slabs are counted in raw 2-byte elements
-  const SbTile t{(const XR*)a.x + (int64_t)lvl * a.xs_lev, (YT*)a.y + (int64_t)lvl * a.ys_lev, a.ldx, a.ldy, a.n_batch,
-                 a.n_dst, a.n_dtiles, a.n_btiles, per, a.area_min, L.imask != nullptr, a.xcd_remap, a.b_fastest, a.cf};
+  const SbTile t{(const XR*)a.x + (int64_t)lvl * a.xs_lev, (typename YTraits<YT>::raw*)a.y + (int64_t)lvl * a.ys_lev, a.ldx, a.ldy, a.n_batch,
+                 a.n_dst, a.n_dtiles, a.n_btiles, per, a.area_min, L.imask != nullptr, a.xcd_remap, a.b_fastest, a.cf,
+                 CfOutParams{}};
   sb_tile_body<XT, YT, TD, U, FILL, YSB, SKIPNA>(m, t, bid);
 }
 

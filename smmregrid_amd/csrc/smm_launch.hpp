@@ -1,5 +1,5 @@
 // Kernel launch templates, one explicit instantiation per (X dtype, Y dtype, SKIPNA) triple
-// (smm_launch_inst.hip is compiled eight times, in parallel, and four more for CF-packed X): the tile kernel alone has several
+// (smm_launch_inst.hip is compiled eight times, in parallel, four more for CF-packed X and eight for CF-packed Y): the tile kernel alone has several
 // hundred instantiations, which one translation unit would compile for minutes.  SKIPNA = true
 // builds the SMM_APPLY_SKIPNA variants (smm_kernels.hpp, RowSum) in objects of their own.
 #pragma once
@@ -49,6 +49,16 @@ inline size_t sb_lds_pad() { return (size_t)std::max(smm::tuning(SMM_TUNE_SB_LDS
 inline int xcd_run_length() {
   const int want = smm::tuning(SMM_TUNE_XCD_RUN);
   return want < 0 ? 0 : (want > 0 ? want : 32);
+}
+
+// Destination rows per tile (TD) of the batch-fastest kernel for a Y element of ysz bytes: one 128-B line of Y per
+// batch row for f64 (16 rows) and f32 (32).  A packed 2-byte Y takes 64 rows -- the same 128-B runs, a 17-KB LDS tile
+// like f64's -- or 16 (32-B runs, a 4-KB tile) under SMM_TUNE_SB_PACKED_Y_ROWS = 16: both are built, DESIGN.md section 4
+// has the measurement.
+inline int sb_tile_rows(size_t ysz) {
+  if (ysz == 8) return 16;
+  if (ysz == 4) return 32;
+  return smm::tuning(SMM_TUNE_SB_PACKED_Y_ROWS) == 16 ? 16 : 64;
 }
 
 template <typename XT, typename YT, bool SKIPNA>
@@ -273,11 +283,23 @@ int launch_tile(const ApplyArgs& a, int64_t n_lev, int tile_which, int64_t max_c
 }
 
 // Batch-fastest layout (kernel C).  TD destination rows per tile: 16 doubles = one 128-B line of Y
-// per batch row; f32 output takes 32 rows for the same line.
+// per batch row; f32 output takes 32 rows for the same line; a packed 2-byte Y: sb_tile_rows.
+template <typename XT, typename YT, bool SKIPNA, int TD>
+int launch_sb_td(const SbArgs& a, bool fill, unsigned flags, hipStream_t s);
+
 template <typename XT, typename YT, bool SKIPNA>
 int launch_sb(const SbArgs& a, bool fill, unsigned flags, hipStream_t s) {
+  constexpr size_t YSZ = sizeof(typename YTraits<YT>::raw);
+  if constexpr (YSZ == 8) return launch_sb_td<XT, YT, SKIPNA, 16>(a, fill, flags, s);
+  else if constexpr (YSZ == 4) return launch_sb_td<XT, YT, SKIPNA, 32>(a, fill, flags, s);
+  else
+    return sb_tile_rows(YSZ) == 16 ? launch_sb_td<XT, YT, SKIPNA, 16>(a, fill, flags, s)
+                                   : launch_sb_td<XT, YT, SKIPNA, 64>(a, fill, flags, s);
+}
+
+template <typename XT, typename YT, bool SKIPNA, int TD>
+int launch_sb_td(const SbArgs& a, bool fill, unsigned flags, hipStream_t s) {
   SbArgs args = a;
-  constexpr int TD = sizeof(YT) == 8 ? 16 : 32;
   constexpr int BT = 128;
   args.n_dtiles = (a.n_dst + TD - 1) / TD;
   args.n_btiles = (a.n_batch + BT - 1) / BT;
@@ -315,6 +337,7 @@ int launch_sb(const SbArgs& a, bool fill, unsigned flags, hipStream_t s) {
 template <typename XT, typename YT, bool SKIPNA>
 int launch_sb_group(const SbGroupArgs& a, bool fill, unsigned flags, hipStream_t s) {
   SbGroupArgs args = a;
+  static_assert(!YTraits<YT>::packed, "level groups have no packed-Y launchers");
   constexpr int TD = sizeof(YT) == 8 ? 16 : 32;
   constexpr int BT = 128;
   args.n_dtiles = (a.n_dst + TD - 1) / TD;

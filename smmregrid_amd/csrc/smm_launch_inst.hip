@@ -1,6 +1,7 @@
 // One (X dtype, Y dtype, SKIPNA) triple of the kernel launch templates; built with -DSMM_XT=... -DSMM_YT=...
 // and -DSMM_SKIPNA=1 for the SMM_APPLY_SKIPNA variants.  With -DSMM_PACKED=1: the int16 / uint16 packed-X launchers
-// that decode to SMM_XT instead
+// that decode to SMM_XT instead.  With -DSMM_PACKED_Y=1: the launchers that store CF-packed int16 / uint16 results
+// (PackedY), for float X of type SMM_XT or, with -DSMM_PACKED=1 too, packed X of the same raw type decoded to SMM_XT
 #include "smm_launch.hpp"
 
 #ifndef SMM_SKIPNA
@@ -8,7 +9,23 @@
 #endif
 
 namespace smm_launch {
+#ifdef SMM_PACKED_Y
+// CF-packed 16-bit results encoded in the stores (PackedY, smm_kernels.hpp): kernel A and kernel C of single
+// operators.  No tile kernel, no level groups; packed X only with Y's own raw type.
 #ifdef SMM_PACKED
+#define SMM_PKY_X(Q) PackedX<Q, SMM_XT>
+#else
+#define SMM_PKY_X(Q) SMM_XT
+#endif
+#define SMM_INST_PACKED_Y(Q)                                                                                        \
+  template int launch_sell<SMM_PKY_X(Q), PackedY<Q>, SMM_SKIPNA != 0>(const ApplyArgs&, int64_t, bool, unsigned,    \
+                                                                      hipStream_t);                                 \
+  template int launch_sb<SMM_PKY_X(Q), PackedY<Q>, SMM_SKIPNA != 0>(const SbArgs&, bool, unsigned, hipStream_t);
+SMM_INST_PACKED_Y(int16_t)
+SMM_INST_PACKED_Y(uint16_t)
+#undef SMM_INST_PACKED_Y
+#undef SMM_PKY_X
+#elif defined(SMM_PACKED)
 // CF-packed 16-bit X decoded to SMM_XT in registers (PackedX, smm_kernels.hpp): kernel A, kernel C and the grouped
 // kernel C of level groups, f64 results
 #define SMM_INST_PACKED(Q)                                                                                          \

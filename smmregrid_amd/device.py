@@ -110,6 +110,89 @@ class CFDecode:
                 f"fill_values={self.fill_values}, dtype={self.dtype.name})")
 
 
+class CFEncode:
+    """How a float64 regrid result becomes a CF-packed 16-bit variable (`scale_factor`, `add_offset`, `_FillValue`):
+
+        t = (float64(y) - float64(add_offset)) / float64(scale_factor)      two rounded float64 operations
+        r = rint(t)                                                         ties to even
+        q = fill_value  where  y is not finite  or  r < iinfo.min  or  r > iinfo.max,  else raw_dtype(r)
+
+    Always float64 arithmetic: the regrid result is float64.  NaN results go to `fill_value`, and so does every value
+    that rounds outside the raw range: there is NO wrap-around and NO saturation.  A valid value that happens to
+    round onto `fill_value` is stored as is (as xarray does): it reads back as missing.  Passed as `cf_out=` to
+    `SparseOperator.apply` / `apply_sb` / `apply_host` the rule runs inside the kernels' stores and the result has
+    `raw_dtype`; the bits are those of `encode` applied to the float64 result.  `scale_factor` / `add_offset` None =
+    absent (1 / 0).  `fill_value` is mandatory: NaN results need somewhere to go."""
+
+    def __init__(self, scale_factor, add_offset, fill_value, raw_dtype):
+        self.raw_dtype = np.dtype(raw_dtype)
+        if not is_packed_dtype(self.raw_dtype):
+            raise TypeError("CFEncode raw_dtype must be int16 or uint16")
+        self.scale_factor = None if scale_factor is None else float(np.asarray(scale_factor).ravel()[0])
+        self.add_offset = None if add_offset is None else float(np.asarray(add_offset).ravel()[0])
+        if self.scale_factor is not None and (not np.isfinite(self.scale_factor) or self.scale_factor == 0.0):
+            raise ValueError(f"scale_factor must be finite and non-zero, got {self.scale_factor}")
+        if self.add_offset is not None and not np.isfinite(self.add_offset):
+            raise ValueError(f"add_offset must be finite, got {self.add_offset}")
+        if fill_value is None:
+            raise ValueError("CFEncode needs a fill_value: NaN results need somewhere to go")
+        f = np.asarray(fill_value).ravel()[0].item()
+        info = np.iinfo(self.raw_dtype)
+        if f != f or float(f) != int(f) or not info.min <= int(f) <= info.max:
+            raise ValueError(f"fill value {f!r} is not representable in {self.raw_dtype.name}")
+        self.fill_value = int(f)
+
+    @classmethod
+    def from_attrs(cls, attrs, raw_dtype):
+        """The rule of a variable's CF attributes: `_FillValue`, else `missing_value` (ValueError without one)."""
+        fill = attrs.get("_FillValue", attrs.get("missing_value"))
+        if fill is None:
+            raise ValueError("no _FillValue / missing_value attribute: NaN results would have nowhere to go")
+        return cls(attrs.get("scale_factor"), attrs.get("add_offset"), fill, raw_dtype)
+
+    def attrs(self):
+        """The attributes to put on an encoded result (it then reads back through `CFDecode.from_attrs`)."""
+        out = {}
+        if self.scale_factor is not None:
+            out["scale_factor"] = np.float64(self.scale_factor)
+        if self.add_offset is not None:
+            out["add_offset"] = np.float64(self.add_offset)
+        out["_FillValue"] = self.raw_dtype.type(self.fill_value)
+        return out
+
+    def encode(self, values):
+        """The numpy statement of the rule (what the kernels reproduce bit for bit)."""
+        y = np.asarray(values, dtype=np.float64)
+        info = np.iinfo(self.raw_dtype)
+        with np.errstate(invalid="ignore", over="ignore"):
+            t = (y - np.float64(0.0 if self.add_offset is None else self.add_offset)) \
+                / np.float64(1.0 if self.scale_factor is None else self.scale_factor)
+            r = np.rint(t)
+            bad = ~np.isfinite(y) | (r < info.min) | (r > info.max)
+            return np.where(bad, self.fill_value, r).astype(self.raw_dtype)
+
+    def _struct(self):
+        """smm_cf_encode_t"""
+        return _lib.CfEncodeStruct(1.0 if self.scale_factor is None else self.scale_factor,
+                                   0.0 if self.add_offset is None else self.add_offset, self.fill_value, 0)
+
+    def __repr__(self):
+        return (f"CFEncode(scale_factor={self.scale_factor}, add_offset={self.add_offset}, "
+                f"fill_value={self.fill_value}, raw_dtype={self.raw_dtype.name})")
+
+
+def result_dtype(out_dtype, cf_out):
+    """(numpy dtype, ABI code) of an apply result: `out_dtype`, or the raw dtype of a `CFEncode` given as cf_out
+    (which excludes out_dtype=float32)."""
+    if cf_out is None:
+        return np.dtype(out_dtype), dtype_code(out_dtype)
+    if not isinstance(cf_out, CFEncode):
+        raise TypeError("cf_out must be a CFEncode")
+    if np.dtype(out_dtype) != np.dtype(np.float64):
+        raise ValueError("cf_out encodes the float64 result: out_dtype must stay float64")
+    return cf_out.raw_dtype, _PACKED_CODE[cf_out.raw_dtype]
+
+
 def device_count():
     return _lib.device_count()
 

@@ -11,8 +11,8 @@ import time
 import numpy as np
 
 from . import _lib
-from .device import (DeviceArray, dtype_code, field_dtype_code, is_packed_dtype, result_cache, _stream_handle,
-                     current_device)
+from .device import (DeviceArray, dtype_code, field_dtype_code, is_packed_dtype, result_cache, result_dtype,
+                     _stream_handle, current_device)
 
 
 def _cptr(a):
@@ -170,7 +170,7 @@ class SparseOperator:
         return out
 
     def apply(self, x, y=None, masked=False, remap_area_min=0.0, out_dtype=np.float64,
-              flags=0, stream=None, keep_batch_fastest=False, skipna=False, cf=None):
+              flags=0, stream=None, keep_batch_fastest=False, skipna=False, cf=None, cf_out=None):
         """Y = epilogue(fill(X) . W) for a device-resident X of shape (B, S), or (B, ldx) with a
         padded row pitch ldx >= S (rows that start on 128-B lines are staged without straddling).
         A field tagged batch-fastest (`x.layout == "sb"`, shape (S, B)) goes through the batch-fastest
@@ -178,23 +178,36 @@ class SparseOperator:
         skipna: non-finite source values drop out of each batch row's sums and the row is renormalised over
         the valid weight (SMM_APPLY_SKIPNA; rows without one are bit-identical to the plain apply).
         cf: a `CFDecode` -- x holds the raw int16 / uint16 of a CF-packed field, decoded inside the kernel
-        (bit-identical to applying `cf.decode` on the host first; float64 results only)."""
+        (bit-identical to applying `cf.decode` on the host first; float64 results only).
+        cf_out: a `CFEncode` -- the result is stored as raw int16 / uint16, encoded inside the kernel's stores
+        (bit-identical to `cf_out.encode` of the float64 result; out of range -> fill value, never wrapped)."""
         if not isinstance(x, DeviceArray):
             raise TypeError("SparseOperator.apply takes a DeviceArray (use Regridder for host data)")
         if x.layout == "sb":
             return self.apply_sb(x, y=y, masked=masked, remap_area_min=remap_area_min, out_dtype=out_dtype,
                                  flags=flags, skipna=skipna, stream=stream, keep_batch_fastest=keep_batch_fastest,
-                                 cf=cf)
+                                 cf=cf, cf_out=cf_out)
         if keep_batch_fastest:
             raise ValueError("keep_batch_fastest needs a batch-fastest field (DeviceArray(..., layout='sb'))")
         if x.ndim != 2 or x.shape[1] < self.n_src:
             raise ValueError(f"X must be (B, >= {self.n_src}), got {x.shape}")
         n_batch = x.shape[0]
+        y_dtype, y_code = result_dtype(out_dtype, cf_out)
         if y is None:
-            y = DeviceArray((n_batch, self.n_dst), out_dtype)
+            y = DeviceArray((n_batch, self.n_dst), y_dtype)
         elif y.shape != (n_batch, self.n_dst):
             raise ValueError(f"Y must be ({n_batch}, {self.n_dst}), got {y.shape}")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        if cf_out is not None:
+            if y.dtype != y_dtype:
+                raise TypeError(f"Y must be {y_dtype} for this cf_out, got {y.dtype}")
+            st = None if cf is None else cf._struct(x.dtype)
+            enc = cf_out._struct()
+            _lib.call("smm_apply_pk", self.handle, ctypes.c_void_p(x.ptr), field_dtype_code(x.dtype, cf),
+                      x.shape[1], ctypes.c_void_p(y.ptr), y_code, self.n_dst, n_batch,
+                      float(remap_area_min), fl, _stream_handle(stream), None if st is None else ctypes.byref(st),
+                      ctypes.byref(enc))
+            return y
         if cf is not None:
             code = field_dtype_code(x.dtype, cf)
             st = cf._struct(x.dtype)
@@ -220,7 +233,7 @@ class SparseOperator:
         return self
 
     def apply_sb(self, x, y=None, masked=False, remap_area_min=0.0, packed=False, out_dtype=np.float64,
-                 flags=0, stream=None, keep_batch_fastest=False, n_batch=None, skipna=False, cf=None):
+                 flags=0, stream=None, keep_batch_fastest=False, n_batch=None, skipna=False, cf=None, cf_out=None):
         """The same product for a device-resident field kept batch-fastest: x of shape (S, B) -- or
         (n_used_src, B) with packed=True, rows in `used_sources()` order -- holds the B batch values
         of each source cell contiguously.  Y is (B, D) as `apply` returns it, bit-identical to
@@ -230,7 +243,8 @@ class SparseOperator:
         on the target grid consumes without any transpose (SMM_APPLY_SB_Y_SB).  n_batch: batch entries
         when the last axis of x is a padded pitch (cells that start on 128-B lines -- a pitch of a multiple
         of 16 doubles -- are what the cell-staging kernel likes: every 16-entry run is then one line).
-        cf: a `CFDecode` for a raw int16 / uint16 field (see `apply`)."""
+        cf: a `CFDecode` for a raw int16 / uint16 field (see `apply`).  cf_out: a `CFEncode` -- the result is raw
+        int16 / uint16 (see `apply`); kept batch-fastest it is what a following `apply_sb(..., cf=)` consumes."""
         if not isinstance(x, DeviceArray):
             raise TypeError("SparseOperator.apply_sb takes a DeviceArray")
         rows = self.n_used_src if packed else self.n_src
@@ -241,14 +255,24 @@ class SparseOperator:
         if not 0 <= n_batch <= ldx:
             raise ValueError(f"n_batch must be within the pitch {ldx}")
         y_shape = (self.n_dst, n_batch) if keep_batch_fastest else (n_batch, self.n_dst)
+        y_dtype, y_code = result_dtype(out_dtype, cf_out)
         if y is None:
-            y = DeviceArray(y_shape, out_dtype, layout="sb" if keep_batch_fastest else "bs")
+            y = DeviceArray(y_shape, y_dtype, layout="sb" if keep_batch_fastest else "bs")
         elif y.shape != y_shape:
             raise ValueError(f"Y must be {y_shape}, got {y.shape}")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
         fl |= _lib.APPLY_SB_PACKED if packed else 0
         if keep_batch_fastest:
             fl |= _lib.APPLY_SB_Y_SB
+        if cf_out is not None:
+            if y.dtype != y_dtype:
+                raise TypeError(f"Y must be {y_dtype} for this cf_out, got {y.dtype}")
+            st = None if cf is None else cf._struct(x.dtype)
+            enc = cf_out._struct()
+            _lib.call("smm_apply_sb_pk", self.handle, ctypes.c_void_p(x.ptr), field_dtype_code(x.dtype, cf), max(ldx, 1),
+                      ctypes.c_void_p(y.ptr), y_code, max(y_shape[1], 1), n_batch, float(remap_area_min),
+                      fl, _stream_handle(stream), None if st is None else ctypes.byref(st), ctypes.byref(enc))
+            return y
         if cf is not None:
             code = field_dtype_code(x.dtype, cf)
             st = cf._struct(x.dtype)
@@ -262,12 +286,14 @@ class SparseOperator:
         return y
 
     def apply_host(self, x, out=None, masked=False, remap_area_min=0.0, out_dtype=np.float64,
-                   flags=0, chunk_rows=0, skipna=False, cf=None):
+                   flags=0, chunk_rows=0, skipna=False, cf=None, cf_out=None):
         """Same product for a host (numpy) array of shape (B, S): the rows stream through the
         library's double-buffered H2D / kernel / D2H pipeline (smm_apply_host).  Arrays from
         `pinned_empty` are DMA'd without staging copies.  Returns a (B, D) numpy array.
         cf: a `CFDecode` -- x is the raw int16 / uint16 of a CF-packed field: it is staged, packed and shipped as
-        2-byte elements and decoded inside the kernels (smm_apply_host_cf)."""
+        2-byte elements and decoded inside the kernels (smm_apply_host_cf).
+        cf_out: a `CFEncode` -- the result is encoded inside the kernels and comes back, is staged and copied out as
+        raw int16 / uint16: a quarter of the float64 result's bytes over PCIe (smm_apply_host_pk)."""
         x = np.asarray(x)
         if cf is not None and not is_packed_dtype(x.dtype):
             raise TypeError(f"a CFDecode rule goes with a raw int16 / uint16 field, not {x.dtype}")
@@ -278,12 +304,22 @@ class SparseOperator:
         if x.strides[1] != x.itemsize or x.strides[0] % x.itemsize or x.strides[0] < self.n_src * x.itemsize:
             x = np.ascontiguousarray(x)
         n_batch = x.shape[0]
+        y_dtype, y_code = result_dtype(out_dtype, cf_out)
         if out is None:
-            out = result_cache.empty((n_batch, self.n_dst), out_dtype)      # page-locked and recycled when large
+            out = result_cache.empty((n_batch, self.n_dst), y_dtype)      # page-locked and recycled when large
         if out.shape != (n_batch, self.n_dst) or not out.flags.c_contiguous:
             raise ValueError(f"out must be a C-contiguous ({n_batch}, {self.n_dst}) array")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
         ldx = x.strides[0] // x.itemsize if n_batch > 1 else max(self.n_src, 1)
+        if cf_out is not None:
+            if out.dtype != y_dtype:
+                raise TypeError(f"out must be {y_dtype} for this cf_out, got {out.dtype}")
+            st = None if cf is None else cf._struct(x.dtype)
+            enc = cf_out._struct()
+            _lib.call("smm_apply_host_pk", self.handle, _cptr(x), field_dtype_code(x.dtype, cf), ldx,
+                      _cptr(out), y_code, self.n_dst, n_batch, float(remap_area_min), fl,
+                      int(chunk_rows), None if st is None else ctypes.byref(st), ctypes.byref(enc))
+            return out
         if cf is not None:
             st = cf._struct(x.dtype)
             _lib.call("smm_apply_host_cf", self.handle, _cptr(x), field_dtype_code(x.dtype, cf), ldx,

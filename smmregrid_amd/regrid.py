@@ -18,7 +18,7 @@ import os
 
 import numpy as np
 
-from .device import CFDecode, DeviceArray, is_packed_dtype, to_device
+from .device import CFDecode, CFEncode, DeviceArray, is_packed_dtype, to_device
 from .gridtype import GridType, tolist
 from .lazy import LazyArray, is_dask, map_batch_blocks
 from .operator import OperatorGroup
@@ -57,7 +57,7 @@ class Regridder(object):
                  vertical_dim=None, horizontal_dims=None, cdo_extra=None, cdo_options=None,
                  check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=np.float64,
                  lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False,
-                 packed_levels=False):
+                 packed_levels=False, packed_out=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -94,10 +94,18 @@ class Regridder(object):
         self.packed_levels = bool(packed_levels)
         if self.packed_levels and not self.packed:
             raise ValueError('packed_levels=True needs packed=True')
+        # packed_out (with packed=True): a variable regridded raw comes back in its own raw dtype, encoded by the rule
+        # of its own attributes (CFEncode) inside the kernels' stores, and keeps its packing attributes: it can be
+        # written straight to a file.  Values that round outside the raw range become the fill value (no wrap-around)
+        self.packed_out = bool(packed_out)
+        if self.packed_out and not self.packed:
+            raise ValueError('packed_out=True needs packed=True')
         # the reference always yields float64 (result_type(x, f64)); float32 is an opt-in narrowing store
         self.out_dtype = np.dtype(out_dtype)
         if self.out_dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise ValueError('out_dtype must be float32 or float64')
+        if self.packed_out and self.out_dtype != np.dtype(np.float64):
+            raise ValueError('packed_out=True encodes the float64 result: out_dtype must stay float64')
         mask_dim = tolist(mask_dim)
         horizontal_dims = tolist(horizontal_dims)
         self.extra_dims = {'mask': mask_dim, 'horizontal': horizontal_dims}
@@ -283,6 +291,8 @@ class Regridder(object):
             # to regrid, and the empty result is dropped from a Dataset (regrid.py:308-312, :262-264)
             return DataArray(data=None)
         cf = self._packed_rule(source_data) if self.packed else None
+        enc = self._packed_out_rule(source_data) if (self.packed_out and cf is not None) else None
+        packing = {k: source_data.attrs[k] for k in _CF_PACKING_ATTRS if k in source_data.attrs}
         if cf is not None and ((datagridtype.mask_dim and not self.packed_levels)
                                or self.out_dtype != np.dtype(np.float64)):
             # float32 results take no packed input, level groups only with packed_levels=True: decoded on the host,
@@ -293,12 +303,39 @@ class Regridder(object):
             cf = None
         if datagridtype.mask_dim:
             out = self.regrid3d(source_data, datagridtype, cf=cf)
+            if enc is not None and out.data is not None:
+                enc = self._encode_on_host(out, enc)      # None when the result stays float64 (device-resident)
         else:
-            out = self.regrid2d(source_data, datagridtype, cf=cf)
-        if cf is not None:
+            out = self.regrid2d(source_data, datagridtype, cf=cf, cf_out=enc)
+        if enc is not None:
+            out.attrs.update(packing)      # the result is raw again: it keeps the rule it was encoded with
+        elif cf is not None:
             for k in _CF_PACKING_ATTRS:
                 out.attrs.pop(k, None)
         return out
+
+    def _packed_out_rule(self, source_data):
+        """The CFEncode of a packed variable's own attributes, or None (one WARNING) when they name no fill value."""
+        try:
+            return CFEncode.from_attrs(source_data.attrs, source_data.data.dtype)
+        except ValueError as err:
+            self.loggy.warning("packed variable %s comes back as float64, not packed: %s", source_data.name, err)
+            return None
+
+    def _encode_on_host(self, out, enc):
+        """packed_out on masked-level (3-D) weights: the level-group entries have no packed-result form, so a host
+        result is encoded here with the same rule (the same bits); a device-resident one stays float64."""
+        data = out.data
+        if isinstance(data, DeviceArray):
+            self.loggy.warning("packed_out: the device-resident result of %s on masked-level weights stays float64",
+                               out.name)
+            return None
+        self.loggy.info("packed_out: %s on masked-level weights is encoded on the host", out.name)
+        if isinstance(data, LazyArray):
+            out.data = LazyArray(data.shape, enc.raw_dtype, lambda: enc.encode(data.compute()))
+        else:
+            out.data = enc.encode(np.asarray(data))
+        return enc
 
     def _packed_rule(self, source_data):
         """The CFDecode of a 2-byte integer variable that carries CF packing attributes, else None."""
@@ -329,7 +366,7 @@ class Regridder(object):
             self.grids[0].other_dims = datagridtype.other_dims
         return next((grid for grid in self.grids if grid == datagridtype), None)
 
-    def regrid2d(self, source_data, datagridtype, cf=None):
+    def regrid2d(self, source_data, datagridtype, cf=None, cf_out=None):
         """regrid.py:429-456."""
         gridtype = self._get_gridtype(datagridtype)
         if gridtype is None:
@@ -337,7 +374,7 @@ class Regridder(object):
         return self.apply_weights(source_data, gridtype.weights,
                                   weights_matrix=gridtype.weights_matrix,
                                   masked=gridtype.masked,
-                                  horizontal_dims=gridtype.horizontal_dims, cf=cf)
+                                  horizontal_dims=gridtype.horizontal_dims, cf=cf, cf_out=cf_out)
 
     # ------------------------------------------------------------------ apply (2-D)
     def _target_layout(self, weights):
@@ -376,8 +413,9 @@ class Regridder(object):
         return out
 
     def apply_weights(self, source_data, weights, weights_matrix=None, masked=True,
-                      horizontal_dims=None, cf=None):
-        """regrid.py:458-628 for one 2-D operator.  cf: the CFDecode of a raw int16 / uint16 field (packed=True)."""
+                      horizontal_dims=None, cf=None, cf_out=None):
+        """regrid.py:458-628 for one 2-D operator.  cf: the CFDecode of a raw int16 / uint16 field (packed=True);
+        cf_out: the CFEncode its result is stored with (packed_out=True)."""
         source_data = from_xarray(source_data)
         weights = from_xarray(weights)
         name = source_data.name or ''
@@ -405,6 +443,7 @@ class Regridder(object):
 
         src = source_data.data
         area_min, out_dtype, skipna = self.remap_area_min, self.out_dtype, self.skipna
+        res_dtype = out_dtype if cf_out is None else cf_out.raw_dtype
         sb_in = isinstance(src, DeviceArray) and src.layout == "sb"
         if sb_in:
             n_h = len(source_data.dims) - len(kept_dims)
@@ -428,7 +467,7 @@ class Regridder(object):
             if host.shape[1] != op.n_src:
                 raise ValueError(f"source grid has {host.shape[1]} cells, weights expect {op.n_src}")
             return op.apply_host(host, masked=masked, remap_area_min=area_min, out_dtype=out_dtype, skipna=skipna,
-                                 cf=cf)
+                                 cf=cf, cf_out=cf_out)
 
         def compute():
             if sb_in:
@@ -436,13 +475,14 @@ class Regridder(object):
                 if x.shape[0] != op.n_src:
                     raise ValueError(f"source grid has {x.shape[0]} cells, weights expect {op.n_src}")
                 y = op.apply(x, masked=masked, remap_area_min=area_min, out_dtype=out_dtype,
-                             keep_batch_fastest=sb_out, skipna=skipna, cf=cf)
+                             keep_batch_fastest=sb_out, skipna=skipna, cf=cf, cf_out=cf_out)
                 return y.reshape(*out_shape)
             if isinstance(src, DeviceArray):
                 x = src.reshape(n_batch, -1)
                 if x.shape[1] != op.n_src:
                     raise ValueError(f"source grid has {x.shape[1]} cells, weights expect {op.n_src}")
-                y = op.apply(x, masked=masked, remap_area_min=area_min, out_dtype=out_dtype, skipna=skipna, cf=cf)
+                y = op.apply(x, masked=masked, remap_area_min=area_min, out_dtype=out_dtype, skipna=skipna, cf=cf,
+                             cf_out=cf_out)
                 return y.reshape(*(kept_shape + tgt_shape))
             host = src.compute() if isinstance(src, LazyArray) else np.asarray(src)
             return apply_rows(host.reshape(n_batch, -1)).reshape(kept_shape + tgt_shape)
@@ -450,9 +490,9 @@ class Regridder(object):
         if self.lazy and is_dask(src):
             # dask in, dask out: one task per block of the kept dimensions (regrid.py:538-541)
             out_data = map_batch_blocks(src, len(source_data.dims) - len(kept_dims), tgt_shape, apply_rows,
-                                        dtype=out_dtype)
+                                        dtype=res_dtype)
         elif self.lazy:
-            out_data = LazyArray(out_shape, out_dtype, compute)
+            out_data = LazyArray(out_shape, res_dtype, compute)
         else:
             out_data = compute()
 
