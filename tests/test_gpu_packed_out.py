@@ -7,7 +7,8 @@ are multiples of 1/8 and the encoded t = (y - offset) / scale is a half-integer 
 (config 2's bilinear weights are 1 and 0: every second result is a tie) and on one batch row whose sources decode to
 exactly 0 (t = n + 0.5 on every geometry).  The values are plateaus over the whole raw range, placed so that one to
 three per cent of the results round beyond its upper end; fill values on a rectangle and scattered cells, the static mask
-and remap_area_min make NaN."""
+and remap_area_min make NaN.
+Non-dyadic rules and values that tell a wrong division or rounding apart: tests/test_gpu_packed_out_exact.py."""
 import ctypes
 
 import numpy as np
