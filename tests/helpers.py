@@ -115,3 +115,46 @@ def kernel_forms(*tile_knobs, sell_knobs=({"sell_batch_rows": 8}, {"sell_batch_r
     from smmregrid_amd import _lib
     t, s = _lib.APPLY_KERNEL_TILE, _lib.APPLY_KERNEL_SELL
     return [(0, {}), (t, {})] + [(t, dict(k)) for k in tile_knobs] + [(s, {})] + [(s, dict(k)) for k in sell_knobs]
+
+
+def skipna_ref(csr, x, masked=False, imask=None, frac=None, area_min=0.0, out_dtype=np.float64):
+    """The rule restated: a loop over link slots, vectorised over (batch, destination)."""
+    rowptr, col, val = csr
+    D, B = rowptr.size - 1, x.shape[0]
+    xd = np.asarray(x).astype(np.float64)
+    fill = np.float64(x.dtype.type(1e20))
+    lens = np.diff(rowptr)
+    num, den = np.zeros((B, D)), np.zeros((B, D))
+    inv = np.zeros((B, D), dtype=bool)
+    tot = np.zeros(D)
+    for k in range(int(lens.max()) if D else 0):
+        rows = np.nonzero(lens > k)[0]
+        p = rowptr[rows] + k
+        w, xv = val[p], xd[:, col[p]]
+        fin = np.isfinite(xv)
+        bad = ~fin & (w != 0.0)
+        prod = w * np.where(fin, xv, fill)
+        num[:, rows] = np.where(bad, num[:, rows], num[:, rows] + prod)
+        den[:, rows] = np.where(bad, den[:, rows], den[:, rows] + w)
+        inv[:, rows] |= bad
+        tot[rows] = tot[rows] + w
+    with np.errstate(all="ignore"):
+        r = np.where(inv, den / tot, 1.0)
+        v = np.where(inv, num * (tot / den), num)
+        dead = inv & ~(r > 0.0)
+        if masked and imask is not None:
+            dead |= (np.asarray(imask) == 0)[None, :]
+        if area_min > 0.0:
+            fd = np.ones(D) if frac is None else np.asarray(frac, dtype=np.float64)
+            dead |= (inv | (frac is not None)) & (fd * r < area_min)
+        y = np.where(dead | (v > 1e19), np.nan, v)
+    return y.astype(out_dtype)
+
+
+def bits_equal(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype
+    na, nb = np.isnan(a), np.isnan(b)
+    assert np.array_equal(na, nb), f"NaN sets differ at {np.argwhere(na != nb)[:5].tolist()}"
+    assert np.array_equal(a[~na].view(f"u{a.itemsize}"), b[~nb].view(f"u{b.itemsize}")), \
+        f"values differ at {np.argwhere((a != b) & ~na)[:5].tolist()}"
