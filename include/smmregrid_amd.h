@@ -355,7 +355,8 @@ int smm_apply_host_cf(smm_operator_t op,
  * whole-row chunks of smm_apply_host_pk) or the batch-fastest kernel, for float X too: the LDS tile kernel is not
  * built for them and SMM_APPLY_KERNEL_TILE with enc is SMM_ERR_UNSUPPORTED.  MASKED, SKIPNA, SB_PACKED, SB_Y_SB,
  * HOST_NO_PACK, KERNEL_SELL and the split of grids beyond 2^31 - 1 blocks behave as for float Y; a batch-fastest
- * packed result (SB_Y_SB) is what a following smm_apply_sb_cf consumes.  Level groups have no _pk entries.
+ * packed result (SB_Y_SB) is what a following smm_apply_sb_cf consumes.  Level groups: smm_group_apply_pk and friends,
+ * below the group _cf entries.
  */
 int smm_apply_pk(smm_operator_t op,
                  const void* x, int x_dtype, int64_t ldx,
@@ -473,6 +474,50 @@ int smm_group_apply_host_cf(smm_group_t g,
                             const int32_t* level_index, const uint8_t* masked_levels,
                             double remap_area_min, unsigned flags, int64_t chunk_outer,
                             const smm_cf_decode_t* cf);
+
+/*
+ * The three group _cf entries with a CF-packed RESULT, with the contract of smm_apply_pk / smm_apply_sb_pk /
+ * smm_apply_host_pk: enc != NULL stores Y as raw 2-byte integers, encoded inside the kernels' stores by *enc; y_dtype
+ * must then be SMM_I16 / SMM_U16, y 2-byte aligned, and every Y stride (ys_outer / ys_lev / ys_inner, ys_lev / ys_batch)
+ * counts 2-byte elements.  enc == NULL is the _cf entry unchanged.  X is float (cf == NULL) or packed with Y's own raw
+ * type (a packed X of the other raw type: SMM_ERR_UNSUPPORTED).  SMM_ERR_INVALID, before any device is touched: enc !=
+ * NULL with a float y_dtype, an integer y_dtype without enc, a fill the raw type cannot hold, a zero or non-finite
+ * scale, a non-finite offset, reserved != 0.  SMM_APPLY_KERNEL_TILE with enc is SMM_ERR_UNSUPPORTED (the LDS tile kernel
+ * is not built for packed results); SMM_APPLY_SB_PACKED stays refused for groups.  One encode rule per call, for every
+ * level: a variable has one set of packing attributes.  The whole call is validated before the first launch.
+ * level_index / masked_levels, MASKED, SKIPNA, SB_Y_SB, HOST_NO_PACK, KERNEL_SELL and the split of oversized grids
+ * behave as for float Y, with the bits of encoding the float64 result of the _cf entry on the host.
+ *   smm_group_apply_pk      runs the SELL kernel whatever the group's tile plan.
+ *   smm_group_apply_sb_pk   all data levels in one launch of the grouped batch-fastest kernel (the encode rule travels
+ *                           in the kernel arguments behind the decode rule); tiles of 64 destination rows, or 16 under the
+ *                           tuning knob SMM_TUNE_SB_PACKED_Y_ROWS (as in smm_apply_sb_pk).  A batch-fastest packed result (SB_Y_SB,
+ *                           Y (L, D, ys_batch) raw) is what a following smm_apply_sb_cf / smm_group_apply_sb_cf consumes.
+ *   smm_group_apply_host_pk Y host (n_outer, n_inner, n_lev, D) or (n_lev, n_outer, n_inner, D) of raw elements: chunks
+ *                           are sized, staged, copied back and copied out as 2-byte cells in every form of the pipeline
+ *                           (SMM_HOST_STAT_D2H_BYTES counts 2 B per cell) -- a quarter of the float64 result over PCIe.
+ */
+int smm_group_apply_pk(smm_group_t g,
+                       const void* x, int x_dtype,
+                       int64_t xs_outer, int64_t xs_lev, int64_t xs_inner,
+                       void* y, int y_dtype,
+                       int64_t ys_outer, int64_t ys_lev, int64_t ys_inner,
+                       int64_t n_outer, int64_t n_lev, int64_t n_inner,
+                       const int32_t* level_index, const uint8_t* masked_levels,
+                       double remap_area_min, unsigned flags, void* stream,
+                       const smm_cf_decode_t* cf, const smm_cf_encode_t* enc);
+int smm_group_apply_sb_pk(smm_group_t g,
+                          const void* x, int x_dtype, int64_t xs_lev, int64_t ldx,
+                          void* y, int y_dtype, int64_t ys_lev, int64_t ys_batch,
+                          int64_t n_batch, int64_t n_lev,
+                          const int32_t* level_index, const uint8_t* masked_levels,
+                          double remap_area_min, unsigned flags, void* stream,
+                          const smm_cf_decode_t* cf, const smm_cf_encode_t* enc);
+int smm_group_apply_host_pk(smm_group_t g,
+                            const void* x_host, int x_dtype, void* y_host, int y_dtype,
+                            int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose,
+                            const int32_t* level_index, const uint8_t* masked_levels,
+                            double remap_area_min, unsigned flags, int64_t chunk_outer,
+                            const smm_cf_decode_t* cf, const smm_cf_encode_t* enc);
 
 /* Test hook of the two host pipelines' error path: chunk number `chunk` (0-based) of every following
  * smm_apply_host / smm_group_apply_host call fails with SMM_ERR_HIP before its copies are queued;

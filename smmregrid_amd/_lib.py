@@ -148,6 +148,12 @@ SIGNATURES = {
     "smm_group_apply_sb_cf": [_p, _p, _int, _i64, _i64, _p, _int, _i64, _i64, _i64, _i64, _p, _p, _dbl, _uint, _p,
                               _cfp],
     "smm_group_apply_host_cf": [_p, _p, _int, _p, _int, _i64, _i64, _i64, _int, _p, _p, _dbl, _uint, _i64, _cfp],
+    "smm_group_apply_pk": [_p, _p, _int, _i64, _i64, _i64, _p, _int, _i64, _i64, _i64,
+                           _i64, _i64, _i64, _p, _p, _dbl, _uint, _p, _cfp, _cep],
+    "smm_group_apply_sb_pk": [_p, _p, _int, _i64, _i64, _p, _int, _i64, _i64, _i64, _i64, _p, _p, _dbl, _uint, _p,
+                              _cfp, _cep],
+    "smm_group_apply_host_pk": [_p, _p, _int, _p, _int, _i64, _i64, _i64, _int, _p, _p, _dbl, _uint, _i64, _cfp,
+                                _cep],
     "smm_debug_fail_at_chunk": [_i64],
     "smm_debug_host_stats": [ctypes.POINTER(_dbl), _int, _int],
     "smm_debug_staging_faults": [_int, _i64],

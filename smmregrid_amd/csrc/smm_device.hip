@@ -69,10 +69,11 @@ SMM_EXTERN_PACKED(int16_t, double, true)
 SMM_EXTERN_PACKED(uint16_t, float, true)
 SMM_EXTERN_PACKED(uint16_t, double, true)
 #undef SMM_EXTERN_PACKED
-// CF-packed 16-bit Y (PackedY<raw>): kernels A and C of single operators, float X or packed X of the same raw type
+// CF-packed 16-bit Y (PackedY<raw>): kernels A and C and the grouped kernel C, float X or packed X of the same raw type
 #define SMM_EXTERN_PACKED_Y(XT, Q, NA)                                                                          \
   extern template int launch_sell<XT, PackedY<Q>, NA>(const ApplyArgs&, int64_t, bool, unsigned, hipStream_t); \
-  extern template int launch_sb<XT, PackedY<Q>, NA>(const SbArgs&, bool, unsigned, hipStream_t);
+  extern template int launch_sb<XT, PackedY<Q>, NA>(const SbArgs&, bool, unsigned, hipStream_t);               \
+  extern template int launch_sb_group<XT, PackedY<Q>, NA>(const SbGroupArgs&, bool, unsigned, hipStream_t);
 #define SMM_EXTERN_PACKED_Y_Q(Q, NA)              \
   SMM_EXTERN_PACKED_Y(float, Q, NA)               \
   SMM_EXTERN_PACKED_Y(double, Q, NA)              \
@@ -1597,7 +1598,7 @@ static int smm_group_apply_impl(smm_group_t g, const void* x, int x_dtype, int64
                     int64_t xs_inner, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev,
                     int64_t ys_inner, int64_t n_outer, int64_t n_lev, int64_t n_inner,
                     const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min,
-                    unsigned flags, void* stream, const CfCall* cf = nullptr) {
+                    unsigned flags, void* stream, const CfCall* cf = nullptr, const CfOutParams* enc = nullptr) {
   if (int frc = check_flags(flags)) return frc;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
   DeviceGuard guard(g->device);
@@ -1610,7 +1611,7 @@ static int smm_group_apply_impl(smm_group_t g, const void* x, int x_dtype, int64
   return run_apply(g->d_descs, d_map, d_masked, op0->csr.n_src, op0->csr.n_dst, g->tile_which,
                    g->tile_valid, g->tile_preferred, (g->tile_reuse ? 1 : 0), g->tile_max_chunks, g->max_row_nnz, x, x_dtype, xs_outer, xs_lev, xs_inner, y,
                    y_dtype, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner, remap_area_min,
-                   flags, (hipStream_t)stream, nullptr, cf);
+                   flags, (hipStream_t)stream, nullptr, cf, enc);
 }
 
 extern "C++" {
@@ -1656,14 +1657,14 @@ static int smm_group_prepare_sb_impl(smm_group_t g) {
 static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, int64_t xs_lev, int64_t ldx, void* y,
                        int y_dtype, int64_t ys_lev, int64_t ys_batch, int64_t n_batch, int64_t n_lev,
                        const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min,
-                       unsigned flags, void* stream, const CfCall* cf = nullptr) {
+                       unsigned flags, void* stream, const CfCall* cf = nullptr, const CfOutParams* enc = nullptr) {
   if (int frc = check_flags(flags)) return frc;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
   if (n_batch < 0 || n_lev < 0) return fail(SMM_ERR_INVALID, "negative batch size / level count");
   if (n_lev > 0 && !level_index) return fail(SMM_ERR_INVALID, "null level_index");
   if (flags & SMM_APPLY_SB_PACKED)
     return fail(SMM_ERR_UNSUPPORTED, "packed fields are per operator: a group takes whole (S, B) slabs");
-  if (int drc = check_x_dtype(x_dtype, y_dtype, cf)) return drc;
+  if (int drc = check_x_dtype(x_dtype, y_dtype, cf, enc)) return drc;
   const bool packed = is_packed_dtype(x_dtype);   // CF-packed: raw 2-byte slabs, one decode rule for every level
   const int n_ops = (int)g->ops.size();
   for (int64_t l = 0; l < n_lev; ++l)
@@ -1688,7 +1689,8 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, in
   DeviceGuard guard(g->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the group's device");
   const int64_t n_dst = g->ops[0]->csr.n_dst;
-  const int64_t per_level = ((n_dst + (ysz == 8 ? 16 : 32) - 1) / (ysz == 8 ? 16 : 32)) * ((n_batch + 127) / 128);
+  const int64_t td = smm_launch::sb_tile_rows(ysz);   // the tile height launch_sb_group takes (a packed Y: 64 or 16)
+  const int64_t per_level = ((n_dst + td - 1) / td) * ((n_batch + 127) / 128);
   if (!per_level_launches && per_level <= grid_limit()) {
     // grouped launches of as many levels as the kernel arguments (and the launch grid) hold
     for (smm_operator* op : g->ops) {          // the canonical CSR copies the kernel reads (uploaded once)
@@ -1716,8 +1718,11 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, in
         a.lev[i] = SbLevelPtrs{op->d_csr_rowptr, op->d_csr_col, op->d_csr_val, m ? op->d_imask : nullptr, op->d_frac};
       }
       if (packed) a.cf = cf->p;
-      const int rc = packed ? SMM_DISPATCH_CF(launch_sb_group, flags, x_dtype, cf->decode_dtype, a, fill, flags, caller)
-                            : SMM_DISPATCH_ALL(launch_sb_group, flags, x_dtype, y_dtype, a, fill, flags, caller);
+      if (enc) a.cfo = *enc;   // one encode rule for every level
+      const int rc =
+          enc      ? SMM_DISPATCH_PK(launch_sb_group, flags, y_dtype, x_dtype, (cf ? cf->decode_dtype : SMM_F64), a, fill, flags, caller)
+          : packed ? SMM_DISPATCH_CF(launch_sb_group, flags, x_dtype, cf->decode_dtype, a, fill, flags, caller)
+                   : SMM_DISPATCH_ALL(launch_sb_group, flags, x_dtype, y_dtype, a, fill, flags, caller);
       if (rc) return rc;
     }
     return SMM_OK;
@@ -1731,7 +1736,7 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, in
     if ((flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w])) fl |= SMM_APPLY_MASKED;   // regrid.py:405
     status = smm_apply_sb_impl(g->ops[(size_t)w], (const char*)x + (size_t)l * xs_lev * xsz, x_dtype, ldx,
                                (char*)y + (size_t)l * ys_lev * ysz, y_dtype, ys_batch, n_batch, remap_area_min, fl,
-                               caller, cf);
+                               caller, cf, enc);
   }
   return status;
 }
@@ -1787,25 +1792,29 @@ static int smm_group_launch_info_impl(smm_group_t g, int x_dtype, int64_t n_oute
 static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dtype, void* y_host, int y_dtype,
                          int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose,
                          const int32_t* level_index, const uint8_t* masked_levels,
-                         double remap_area_min, unsigned flags, int64_t chunk_outer, const CfCall* cf = nullptr) {
+                         double remap_area_min, unsigned flags, int64_t chunk_outer, const CfCall* cf = nullptr,
+                         const CfOutParams* enc = nullptr) {
   if (int frc = check_flags(flags)) return frc;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
   if (n_outer < 0 || n_lev < 0 || n_inner < 0) return fail(SMM_ERR_INVALID, "negative batch size");
-  if (int drc = check_x_dtype(x_dtype, y_dtype, cf)) return drc;
+  if (int drc = check_x_dtype(x_dtype, y_dtype, cf, enc)) return drc;
   const bool packed = is_packed_dtype(x_dtype);
-  if (packed && (flags & SMM_APPLY_KERNEL_TILE))
-    return fail(SMM_ERR_UNSUPPORTED, "the LDS tile kernel is not built for packed fields (SMM_I16 / SMM_U16)");
+  if ((packed || enc) && (flags & SMM_APPLY_KERNEL_TILE))
+    return fail(SMM_ERR_UNSUPPORTED, "the LDS tile kernel is not built for packed fields or results (SMM_I16 / SMM_U16)");
   const int64_t S = g->ops[0]->csr.n_src, D = g->ops[0]->csr.n_dst;
   if (n_outer == 0 || n_lev == 0 || n_inner == 0 || D == 0) return SMM_OK;
   if (!x_host || !y_host) return fail(SMM_ERR_INVALID, "null field pointer");
   if (packed && (uintptr_t)x_host % 2) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
+  if (enc && (uintptr_t)y_host % 2) return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
   DeviceGuard guard(g->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the group's device");
 
   // a packed field is staged, packed and shipped raw, 2 B per cell: every size below follows xsz.  The slabs of a packed
   // chunk lie back to back (level l's at the running sum of U_l * batch * xsz): kernel C's 4-B-per-lane loads of 2-byte
   // elements only assume element alignment (xvec_u, smm_kernels.hpp), and a slab can start on an odd element only when
-  // the batch count is odd -- when every other row of every slab starts on one anyway -- so no padding is added
+  // the batch count is odd -- when every other row of every slab starts on one anyway -- so no padding is added.  A packed
+  // result (enc) comes back, is staged and copied out raw too: every Y size below follows ysz = 2, in the outer-block clamp,
+  // the level-major chunks, the pinned staging and both host layouts of a chunk's level range
   const size_t xsz = dtype_size(x_dtype), ysz = dtype_size(y_dtype);
   const size_t xrow_d = (((size_t)S * xsz + 127) / 128) * 128;   // device rows start on 128-B lines (see smm_apply_host)
   const int64_t ldx_d = (int64_t)(xrow_d / xsz);
@@ -1999,7 +2008,7 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
         // Y of the chunk: entry (b, ll, d) at (b * nl + ll) * D + d when transpose, at (ll * bc + b) * D + d else
         rc = smm_apply_sb_impl(op, (char*)pipe.dx[b] + off, x_dtype, bc,
                                (char*)pipe.dy[b] + (size_t)ll * (transpose ? D : bc * D) * ysz, y_dtype,
-                               transpose ? ck.nl * D : D, bc, remap_area_min, fl, pipe.stream[b], cf);
+                               transpose ? ck.nl * D : D, bc, remap_area_min, fl, pipe.stream[b], cf, enc);
         off += (size_t)op->csr.n_used_src * bc * xsz;
       }
     } else {
@@ -2024,7 +2033,7 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
       SMM_HIP(hipEventRecord(pipe.ev[b][1], pipe.stream[b]));
       rc = smm_group_apply_impl(g, pipe.dx[b], x_dtype, rows_per_outer * ldx_d, n_inner * ldx_d, ldx_d,
                                 pipe.dy[b], y_dtype, ys_o, ys_l, ys_i, no, n_lev, n_inner, level_index,
-                                masked_levels, remap_area_min, flags, pipe.stream[b], cf);
+                                masked_levels, remap_area_min, flags, pipe.stream[b], cf, enc);
     }
     if (rc) return rc;
     SMM_HIP(hipEventRecord(pipe.ev[b][2], pipe.stream[b]));
@@ -2261,6 +2270,41 @@ int smm_group_apply_host_cf(smm_group_t g, const void* x_host, int x_dtype, void
     const CfCall* use;
     if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
     return smm_group_apply_host_impl(g, x_host, x_dtype, y_host, y_dtype, n_outer, n_lev, n_inner, transpose, level_index, masked_levels, remap_area_min, flags, chunk_outer, use);
+  });
+}
+
+// the three _cf group entries with a CF-packed result: the rule is validated (make_enc) before the group is looked at
+int smm_group_apply_pk(smm_group_t g, const void* x, int x_dtype, int64_t xs_outer, int64_t xs_lev, int64_t xs_inner, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev, int64_t ys_inner, int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
+  return guarded([&] {
+    CfOutParams e;
+    const CfOutParams* use_e = nullptr;
+    if (int rc = make_enc(enc, y_dtype, flags, &e, &use_e)) return rc;
+    CfCall c;
+    const CfCall* use = nullptr;
+    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
+    return smm_group_apply_impl(g, x, x_dtype, xs_outer, xs_lev, xs_inner, y, y_dtype, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner, level_index, masked_levels, remap_area_min, flags, stream, use, use_e);
+  });
+}
+int smm_group_apply_sb_pk(smm_group_t g, const void* x, int x_dtype, int64_t xs_lev, int64_t ldx, void* y, int y_dtype, int64_t ys_lev, int64_t ys_batch, int64_t n_batch, int64_t n_lev, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
+  return guarded([&] {
+    CfOutParams e;
+    const CfOutParams* use_e = nullptr;
+    if (int rc = make_enc(enc, y_dtype, flags, &e, &use_e)) return rc;
+    CfCall c;
+    const CfCall* use = nullptr;
+    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
+    return smm_group_apply_sb_impl(g, x, x_dtype, xs_lev, ldx, y, y_dtype, ys_lev, ys_batch, n_batch, n_lev, level_index, masked_levels, remap_area_min, flags, stream, use, use_e);
+  });
+}
+int smm_group_apply_host_pk(smm_group_t g, const void* x_host, int x_dtype, void* y_host, int y_dtype, int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, int64_t chunk_outer, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
+  return guarded([&] {
+    CfOutParams e;
+    const CfOutParams* use_e = nullptr;
+    if (int rc = make_enc(enc, y_dtype, flags, &e, &use_e)) return rc;
+    CfCall c;
+    const CfCall* use = nullptr;
+    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
+    return smm_group_apply_host_impl(g, x_host, x_dtype, y_host, y_dtype, n_outer, n_lev, n_inner, transpose, level_index, masked_levels, remap_area_min, flags, chunk_outer, use, use_e);
   });
 }
 

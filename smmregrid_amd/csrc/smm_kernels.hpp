@@ -118,8 +118,9 @@ struct SbArgs {
 // pointers with a wave-uniform index -- scalar loads from the kernarg segment -- and reads the CSR through
 // constant-address-space views of them, so the column / weight / row-pointer streams stay scalar loads exactly as
 // in the single-operator kernel (a pointer table in device memory turned them into vector loads: 162 instead of
-// 88 VGPRs).  kSbGroupLevels * 40 B + the rest (112 B + the 24-B decode rule of a packed field = 3656 B) stays below
-// the 4-KiB kernarg limit, for float and packed groups alike; longer groups take several launches.
+// 88 VGPRs).  kSbGroupLevels * 40 B + the rest (112 B + the 24-B decode rule of a packed field + the 24-B encode rule
+// of a packed result = 3680 B) stays below the 4-KiB kernarg limit, for float and packed groups alike; longer groups
+// take several launches.
 constexpr int kSbGroupLevels = 88;
 struct SbLevelPtrs {
   const int64_t* rowptr;
@@ -140,6 +141,7 @@ struct SbGroupArgs {
   int n_lev;
   SbLevelPtrs lev[kSbGroupLevels];
   CfParams cf;               // packed X only: one decode rule for every level (last: the float kernels' offsets stay)
+  CfOutParams cfo;           // packed Y only: one encode rule for every level (appended: the offsets above stay)
 };
 static_assert(sizeof(SbGroupArgs) <= 4096, "kernel arguments are limited to 4 KiB");
 
@@ -1458,7 +1460,7 @@ __global__ __launch_bounds__(64) void smm_group_apply_sb_kernel(SbGroupArgs a) {
   typedef typename XTraits<XT>::raw XR;   // a packed field's slabs are counted in raw 2-byte elements
   const SbTile t{(const XR*)a.x + (int64_t)lvl * a.xs_lev, (typename YTraits<YT>::raw*)a.y + (int64_t)lvl * a.ys_lev, a.ldx, a.ldy, a.n_batch,
                  a.n_dst, a.n_dtiles, a.n_btiles, per, a.area_min, L.imask != nullptr, a.xcd_remap, a.b_fastest, a.cf,
-                 CfOutParams{}};
+                 a.cfo};
   sb_tile_body<XT, YT, TD, U, FILL, YSB, SKIPNA>(m, t, bid);
 }
 

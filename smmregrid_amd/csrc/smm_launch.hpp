@@ -334,11 +334,23 @@ int launch_sb_td(const SbArgs& a, bool fill, unsigned flags, hipStream_t s) {
 
 // The batch-fastest kernel over the data levels of a group in ONE launch (smm_group_apply_sb): grid = levels x
 // (destination tiles x batch tiles); the caller has filled a.lev[0 .. n_lev) and the per-level strides.
+template <typename XT, typename YT, bool SKIPNA, int TD>
+int launch_sb_group_td(const SbGroupArgs& a, bool fill, unsigned flags, hipStream_t s);
+
+// TD as launch_sb chooses it: 16 / 32 rows for an 8- / 4-byte Y, sb_tile_rows for a packed 2-byte one
 template <typename XT, typename YT, bool SKIPNA>
 int launch_sb_group(const SbGroupArgs& a, bool fill, unsigned flags, hipStream_t s) {
+  constexpr size_t YSZ = sizeof(typename YTraits<YT>::raw);
+  if constexpr (YSZ == 8) return launch_sb_group_td<XT, YT, SKIPNA, 16>(a, fill, flags, s);
+  else if constexpr (YSZ == 4) return launch_sb_group_td<XT, YT, SKIPNA, 32>(a, fill, flags, s);
+  else
+    return sb_tile_rows(YSZ) == 16 ? launch_sb_group_td<XT, YT, SKIPNA, 16>(a, fill, flags, s)
+                                   : launch_sb_group_td<XT, YT, SKIPNA, 64>(a, fill, flags, s);
+}
+
+template <typename XT, typename YT, bool SKIPNA, int TD>
+int launch_sb_group_td(const SbGroupArgs& a, bool fill, unsigned flags, hipStream_t s) {
   SbGroupArgs args = a;
-  static_assert(!YTraits<YT>::packed, "level groups have no packed-Y launchers");
-  constexpr int TD = sizeof(YT) == 8 ? 16 : 32;
   constexpr int BT = 128;
   args.n_dtiles = (a.n_dst + TD - 1) / TD;
   args.n_btiles = (a.n_batch + BT - 1) / BT;

@@ -10,8 +10,8 @@
 
 namespace smm_launch {
 #ifdef SMM_PACKED_Y
-// CF-packed 16-bit results encoded in the stores (PackedY, smm_kernels.hpp): kernel A and kernel C of single
-// operators.  No tile kernel, no level groups; packed X only with Y's own raw type.
+// CF-packed 16-bit results encoded in the stores (PackedY, smm_kernels.hpp): kernel A, kernel C of single operators
+// and the grouped kernel C of level groups.  No tile kernel; packed X only with Y's own raw type.
 #ifdef SMM_PACKED
 #define SMM_PKY_X(Q) PackedX<Q, SMM_XT>
 #else
@@ -20,7 +20,9 @@ namespace smm_launch {
 #define SMM_INST_PACKED_Y(Q)                                                                                        \
   template int launch_sell<SMM_PKY_X(Q), PackedY<Q>, SMM_SKIPNA != 0>(const ApplyArgs&, int64_t, bool, unsigned,    \
                                                                       hipStream_t);                                 \
-  template int launch_sb<SMM_PKY_X(Q), PackedY<Q>, SMM_SKIPNA != 0>(const SbArgs&, bool, unsigned, hipStream_t);
+  template int launch_sb<SMM_PKY_X(Q), PackedY<Q>, SMM_SKIPNA != 0>(const SbArgs&, bool, unsigned, hipStream_t);    \
+  template int launch_sb_group<SMM_PKY_X(Q), PackedY<Q>, SMM_SKIPNA != 0>(const SbGroupArgs&, bool, unsigned,       \
+                                                                          hipStream_t);
 SMM_INST_PACKED_Y(int16_t)
 SMM_INST_PACKED_Y(uint16_t)
 #undef SMM_INST_PACKED_Y

@@ -399,12 +399,14 @@ class OperatorGroup:
                             (int(n_outer), int(n_lev), int(n_inner)), flags)
 
     def apply(self, x, level_index, masked_levels=None, y=None, masked=False, remap_area_min=0.0,
-              transpose=True, out_dtype=np.float64, flags=0, stream=None, skipna=False, cf=None):
+              transpose=True, out_dtype=np.float64, flags=0, stream=None, skipna=False, cf=None, cf_out=None):
         """x: DeviceArray (n_outer, n_lev, n_inner, S) -- or (..., ldx) with a padded row pitch ldx >= S.  Returns
         (n_outer, n_inner, n_lev, D) when transpose (regrid.py:420-427) else
         (n_lev, n_outer, n_inner, D) (the concat order, regrid.py:410).
         cf: a `CFDecode` -- x holds the raw int16 / uint16 of a CF-packed field, decoded inside the kernel with one
-        rule for every level (smm_group_apply_cf; bit-identical to applying `cf.decode` first; float64 results only)."""
+        rule for every level (smm_group_apply_cf; bit-identical to applying `cf.decode` first; float64 results only).
+        cf_out: a `CFEncode` -- the result is stored as raw int16 / uint16, encoded inside the kernel's stores with one
+        rule for every level (smm_group_apply_pk; bit-identical to `cf_out.encode` of the float64 result)."""
         if not isinstance(x, DeviceArray) or x.ndim != 4 or x.shape[3] < self.n_src:
             raise ValueError(f"X must be a DeviceArray (n_outer, n_lev, n_inner, >= {self.n_src})")
         # the last axis may be a padded row pitch (>= S): rows that start on 128-B lines (a multiple
@@ -418,12 +420,24 @@ class OperatorGroup:
         else:
             shape = (n_lev, n_outer, n_inner, D)
             ys = (n_inner * D, n_outer * n_inner * D, D)
+        y_dtype, y_code = result_dtype(out_dtype, cf_out)
         if y is None:
-            y = DeviceArray(shape, out_dtype)
+            y = DeviceArray(shape, y_dtype)
         elif y.shape != shape:
             raise ValueError(f"Y must be {shape}, got {y.shape}")
         xs = (n_lev * n_inner * S, n_inner * S, S)
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        if cf_out is not None:
+            if y.dtype != y_dtype:
+                raise TypeError(f"Y must be {y_dtype} for this cf_out, got {y.dtype}")
+            st = None if cf is None else cf._struct(x.dtype)
+            enc = cf_out._struct()
+            _lib.call("smm_group_apply_pk", self.handle, ctypes.c_void_p(x.ptr), field_dtype_code(x.dtype, cf),
+                      xs[0], xs[1], xs[2], ctypes.c_void_p(y.ptr), y_code,
+                      ys[0], ys[1], ys[2], n_outer, n_lev, n_inner, _cptr(lev), _cptr(ml),
+                      float(remap_area_min), fl, _stream_handle(stream), None if st is None else ctypes.byref(st),
+                      ctypes.byref(enc))
+            return y
         if cf is not None:
             code = field_dtype_code(x.dtype, cf)
             st = cf._struct(x.dtype)
@@ -440,14 +454,16 @@ class OperatorGroup:
 
     def apply_sb(self, x, level_index, masked_levels=None, y=None, masked=False, remap_area_min=0.0,
                  transpose=True, out_dtype=np.float64, flags=0, stream=None, keep_batch_fastest=False, n_batch=None,
-                 skipna=False, cf=None):
+                 skipna=False, cf=None, cf_out=None):
         """Masked levels for a field kept batch-fastest per level: x is a DeviceArray (n_lev, S, B) --
         per data level the B batch values of each source cell contiguous.  Returns (B, n_lev, D) when
         transpose (regrid.py:420-427) else (n_lev, B, D); bit-identical to `apply` on the transposed field.
         keep_batch_fastest: the result stays batch-fastest per level, (n_lev, D, B) tagged "sb".
         All data levels run in one grouped launch (several for more than 88 levels), ordered on `stream`.
         n_batch: batch entries when the last axis of x is a padded pitch (see SparseOperator.apply_sb).
-        cf: a `CFDecode` for a raw int16 / uint16 field (see `apply`; smm_group_apply_sb_cf)."""
+        cf: a `CFDecode` for a raw int16 / uint16 field (see `apply`; smm_group_apply_sb_cf).
+        cf_out: a `CFEncode` -- the result is raw int16 / uint16 (see `apply`; smm_group_apply_sb_pk); kept
+        batch-fastest it is what a following `apply_sb(..., cf=)` consumes."""
         if not isinstance(x, DeviceArray) or x.ndim != 3 or x.shape[1] != self.n_src:
             raise ValueError(f"X must be a DeviceArray (n_lev, {self.n_src}, B)")
         n_lev, S, ldx = x.shape
@@ -461,12 +477,23 @@ class OperatorGroup:
         else:
             shape = (B, n_lev, D) if transpose else (n_lev, B, D)
             ys_lev, ys_b = (D, n_lev * D) if transpose else (B * D, D)
+        y_dtype, y_code = result_dtype(out_dtype, cf_out)
         if y is None:
-            y = DeviceArray(shape, out_dtype, layout="sb" if keep_batch_fastest else "bs")
+            y = DeviceArray(shape, y_dtype, layout="sb" if keep_batch_fastest else "bs")
         elif y.shape != shape:
             raise ValueError(f"Y must be {shape}, got {y.shape}")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
         fl |= _lib.APPLY_SB_Y_SB if keep_batch_fastest else 0
+        if cf_out is not None:
+            if y.dtype != y_dtype:
+                raise TypeError(f"Y must be {y_dtype} for this cf_out, got {y.dtype}")
+            st = None if cf is None else cf._struct(x.dtype)
+            enc = cf_out._struct()
+            _lib.call("smm_group_apply_sb_pk", self.handle, ctypes.c_void_p(x.ptr), field_dtype_code(x.dtype, cf),
+                      S * max(ldx, 1), max(ldx, 1), ctypes.c_void_p(y.ptr), y_code, ys_lev, ys_b, B, n_lev,
+                      _cptr(lev), _cptr(ml), float(remap_area_min), fl, _stream_handle(stream),
+                      None if st is None else ctypes.byref(st), ctypes.byref(enc))
+            return y
         if cf is not None:
             code = field_dtype_code(x.dtype, cf)
             st = cf._struct(x.dtype)
@@ -480,11 +507,13 @@ class OperatorGroup:
         return y
 
     def apply_host(self, x, level_index, masked_levels=None, masked=False, remap_area_min=0.0,
-                   transpose=True, out_dtype=np.float64, flags=0, chunk_outer=0, skipna=False, cf=None):
+                   transpose=True, out_dtype=np.float64, flags=0, chunk_outer=0, skipna=False, cf=None, cf_out=None):
         """Host (numpy) variant: x of shape (n_outer, n_lev, n_inner, S); chunks of the outer
         axis stream through the group's H2D / kernel / D2H pipeline (smm_group_apply_host).
         cf: a `CFDecode` -- x is the raw int16 / uint16 of a CF-packed field: it is staged, packed and shipped as
-        2-byte elements and decoded inside the kernels (smm_group_apply_host_cf)."""
+        2-byte elements and decoded inside the kernels (smm_group_apply_host_cf).
+        cf_out: a `CFEncode` -- the result is encoded inside the kernels and comes back, is staged and copied out as
+        raw int16 / uint16: a quarter of the float64 result's bytes over PCIe (smm_group_apply_host_pk)."""
         x = np.asarray(x)
         if cf is not None and not is_packed_dtype(x.dtype):
             raise TypeError(f"a CFDecode rule goes with a raw int16 / uint16 field, not {x.dtype}")
@@ -496,8 +525,17 @@ class OperatorGroup:
         n_outer, n_lev, n_inner, _ = x.shape
         lev, ml = self._level_args(level_index, masked_levels, n_lev)
         shape = (n_outer, n_inner, n_lev, self.n_dst) if transpose else (n_lev, n_outer, n_inner, self.n_dst)
-        out = result_cache.empty(shape, out_dtype)
+        y_dtype, y_code = result_dtype(out_dtype, cf_out)
+        out = result_cache.empty(shape, y_dtype)
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        if cf_out is not None:
+            st = None if cf is None else cf._struct(x.dtype)
+            enc = cf_out._struct()
+            _lib.call("smm_group_apply_host_pk", self.handle, _cptr(x), field_dtype_code(x.dtype, cf), _cptr(out),
+                      y_code, n_outer, n_lev, n_inner, int(bool(transpose)), _cptr(lev),
+                      _cptr(ml), float(remap_area_min), fl, int(chunk_outer),
+                      None if st is None else ctypes.byref(st), ctypes.byref(enc))
+            return out
         if cf is not None:
             st = cf._struct(x.dtype)
             _lib.call("smm_group_apply_host_cf", self.handle, _cptr(x), field_dtype_code(x.dtype, cf), _cptr(out),

@@ -57,7 +57,7 @@ class Regridder(object):
                  vertical_dim=None, horizontal_dims=None, cdo_extra=None, cdo_options=None,
                  check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=np.float64,
                  lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False,
-                 packed_levels=False, packed_out=False):
+                 packed_levels=False, packed_out=False, packed_out_levels=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -100,6 +100,13 @@ class Regridder(object):
         self.packed_out = bool(packed_out)
         if self.packed_out and not self.packed:
             raise ValueError('packed_out=True needs packed=True')
+        # packed_out_levels (with packed_out=True): on masked-level (3-D) weights the result is encoded inside the
+        # level-group kernels too (smm_group_apply*_pk) -- a host result comes back over PCIe as 2-byte cells, a
+        # device-resident one stays raw in HBM.  Off by default: a host result is then encoded on the host and a
+        # device-resident one stays float64, as before
+        self.packed_out_levels = bool(packed_out_levels)
+        if self.packed_out_levels and not self.packed_out:
+            raise ValueError('packed_out_levels=True needs packed_out=True')
         # the reference always yields float64 (result_type(x, f64)); float32 is an opt-in narrowing store
         self.out_dtype = np.dtype(out_dtype)
         if self.out_dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -301,7 +308,11 @@ class Regridder(object):
                             "masked levels" if datagridtype.mask_dim else "out_dtype float32")
             source_data = self._decode_on_host(source_data, cf)
             cf = None
-        if datagridtype.mask_dim:
+        if datagridtype.mask_dim and self.packed_out_levels:
+            out = self.regrid3d(source_data, datagridtype, cf=cf, cf_out=enc)   # encoded inside the group kernels
+            if out.data is None:
+                enc = None
+        elif datagridtype.mask_dim:
             out = self.regrid3d(source_data, datagridtype, cf=cf)
             if enc is not None and out.data is not None:
                 enc = self._encode_on_host(out, enc)      # None when the result stays float64 (device-resident)
@@ -323,8 +334,8 @@ class Regridder(object):
             return None
 
     def _encode_on_host(self, out, enc):
-        """packed_out on masked-level (3-D) weights: the level-group entries have no packed-result form, so a host
-        result is encoded here with the same rule (the same bits); a device-resident one stays float64."""
+        """packed_out on masked-level (3-D) weights without packed_out_levels: a host result is encoded here with the
+        same rule (the same bits as the level-group _pk entries give); a device-resident one stays float64."""
         data = out.data
         if isinstance(data, DeviceArray):
             self.loggy.warning("packed_out: the device-resident result of %s on masked-level weights stays float64",
@@ -500,10 +511,11 @@ class Regridder(object):
                             tgt_shape, tgt_dims)
 
     # ------------------------------------------------------------------ apply (masked levels)
-    def regrid3d(self, source_data, datagridtype, cf=None):
+    def regrid3d(self, source_data, datagridtype, cf=None, cf_out=None):
         """regrid.py:339-427 as one grouped launch: per data level the nearest
         weights level (tolerance 1e-3) selects operator, mask and frac.  cf: the CFDecode of a raw int16 / uint16
-        field (packed=True, packed_levels=True)."""
+        field (packed=True, packed_levels=True); cf_out: the CFEncode its result is stored with (packed_out=True,
+        packed_out_levels=True)."""
         source_data = from_xarray(source_data)
         gridtype = self._get_gridtype(datagridtype)
         if gridtype is None:
@@ -574,12 +586,12 @@ class Regridder(object):
                     raise ValueError(f"source grid has {x.shape[1]} cells, weights expect {S}")
                 y = group.apply_sb(x, level_index, masked_levels, masked=any_masked, remap_area_min=area_min,
                                    transpose=transpose, out_dtype=out_dtype, keep_batch_fastest=sb_out, skipna=skipna,
-                                   cf=cf)
+                                   cf=cf, cf_out=cf_out)
                 return y.reshape(*out_shape)
             if isinstance(src, DeviceArray):
                 x = src.reshape(n_outer, n_lev, n_inner, -1)
                 y = group.apply(x, level_index, masked_levels, masked=any_masked, remap_area_min=area_min,
-                                transpose=transpose, out_dtype=out_dtype, skipna=skipna, cf=cf)
+                                transpose=transpose, out_dtype=out_dtype, skipna=skipna, cf=cf, cf_out=cf_out)
                 return y.reshape(*out_shape)
             host = src.compute() if isinstance(src, LazyArray) else np.asarray(src)   # a dask field is computed here
             if cf is None and host.dtype not in (np.float32, np.float64):
@@ -589,10 +601,11 @@ class Regridder(object):
                 raise ValueError(f"source grid has {host.shape[3]} cells, weights expect {S}")
             # host field: chunks of the outer axis stream through the group's pipeline
             out = group.apply_host(host, level_index, masked_levels, masked=any_masked, remap_area_min=area_min,
-                                   transpose=transpose, out_dtype=out_dtype, skipna=skipna, cf=cf)
+                                   transpose=transpose, out_dtype=out_dtype, skipna=skipna, cf=cf, cf_out=cf_out)
             return out.reshape(out_shape)
 
-        out_data = LazyArray(out_shape, out_dtype, compute) if self.lazy else compute()
+        res_dtype = out_dtype if cf_out is None else cf_out.raw_dtype
+        out_data = LazyArray(out_shape, res_dtype, compute) if self.lazy else compute()
 
         kept_for_coords = kept_dims
         w2d = weights
