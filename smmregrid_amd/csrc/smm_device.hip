@@ -35,91 +35,9 @@
 
 #include "../../include/smmregrid_amd.h"
 #include "smm_internal.h"
-#include "smm_launch.hpp"
+#include "smm_built.hpp"
 
 #pragma clang fp contract(off)
-
-namespace smm_launch {
-#define SMM_EXTERN_PAIR(XT, YT, NA)                                                                         \
-  extern template int launch_sell<XT, YT, NA>(const ApplyArgs&, int64_t, bool, unsigned, hipStream_t);      \
-  extern template int launch_tile<XT, YT, NA>(const ApplyArgs&, int64_t, int, int64_t, int64_t, int, bool, \
-                                              unsigned, hipStream_t);                                       \
-  extern template int launch_sb<XT, YT, NA>(const SbArgs&, bool, unsigned, hipStream_t);                   \
-  extern template int launch_sb_group<XT, YT, NA>(const SbGroupArgs&, bool, unsigned, hipStream_t);
-SMM_EXTERN_PAIR(double, double, false)
-SMM_EXTERN_PAIR(double, float, false)
-SMM_EXTERN_PAIR(float, double, false)
-SMM_EXTERN_PAIR(float, float, false)
-SMM_EXTERN_PAIR(double, double, true)
-SMM_EXTERN_PAIR(double, float, true)
-SMM_EXTERN_PAIR(float, double, true)
-SMM_EXTERN_PAIR(float, float, true)
-#undef SMM_EXTERN_PAIR
-// CF-packed 16-bit X (PackedX<raw, decode type>): kernels A and C and the grouped kernel C, f64 results
-#define SMM_EXTERN_PACKED(Q, T, NA)                                                                             \
-  extern template int launch_sell<PackedX<Q, T>, double, NA>(const ApplyArgs&, int64_t, bool, unsigned, hipStream_t); \
-  extern template int launch_sb<PackedX<Q, T>, double, NA>(const SbArgs&, bool, unsigned, hipStream_t);          \
-  extern template int launch_sb_group<PackedX<Q, T>, double, NA>(const SbGroupArgs&, bool, unsigned, hipStream_t);
-SMM_EXTERN_PACKED(int16_t, float, false)
-SMM_EXTERN_PACKED(int16_t, double, false)
-SMM_EXTERN_PACKED(uint16_t, float, false)
-SMM_EXTERN_PACKED(uint16_t, double, false)
-SMM_EXTERN_PACKED(int16_t, float, true)
-SMM_EXTERN_PACKED(int16_t, double, true)
-SMM_EXTERN_PACKED(uint16_t, float, true)
-SMM_EXTERN_PACKED(uint16_t, double, true)
-#undef SMM_EXTERN_PACKED
-// CF-packed 16-bit Y (PackedY<raw>): kernels A and C and the grouped kernel C, float X or packed X of the same raw type
-#define SMM_EXTERN_PACKED_Y(XT, Q, NA)                                                                          \
-  extern template int launch_sell<XT, PackedY<Q>, NA>(const ApplyArgs&, int64_t, bool, unsigned, hipStream_t); \
-  extern template int launch_sb<XT, PackedY<Q>, NA>(const SbArgs&, bool, unsigned, hipStream_t);               \
-  extern template int launch_sb_group<XT, PackedY<Q>, NA>(const SbGroupArgs&, bool, unsigned, hipStream_t);
-#define SMM_EXTERN_PACKED_Y_Q(Q, NA)              \
-  SMM_EXTERN_PACKED_Y(float, Q, NA)               \
-  SMM_EXTERN_PACKED_Y(double, Q, NA)              \
-  SMM_EXTERN_PACKED_Y(PackedX<Q SMM_COMMA float>, Q, NA)  \
-  SMM_EXTERN_PACKED_Y(PackedX<Q SMM_COMMA double>, Q, NA)
-#define SMM_COMMA ,
-SMM_EXTERN_PACKED_Y_Q(int16_t, false)
-SMM_EXTERN_PACKED_Y_Q(uint16_t, false)
-SMM_EXTERN_PACKED_Y_Q(int16_t, true)
-SMM_EXTERN_PACKED_Y_Q(uint16_t, true)
-#undef SMM_COMMA
-#undef SMM_EXTERN_PACKED_Y_Q
-#undef SMM_EXTERN_PACKED_Y
-}  // namespace smm_launch
-
-// FN<XT, YT, SKIPNA>(...) for the run-time dtypes (SMM_F64 / SMM_F32) and SMM_APPLY_SKIPNA
-#define SMM_DISPATCH_NA(FN, NA, XD, YD, ...)                                                   \
-  ((XD) == SMM_F64 ? ((YD) == SMM_F64 ? FN<double, double, NA>(__VA_ARGS__) : FN<double, float, NA>(__VA_ARGS__)) \
-                   : ((YD) == SMM_F64 ? FN<float, double, NA>(__VA_ARGS__) : FN<float, float, NA>(__VA_ARGS__)))
-#define SMM_DISPATCH_ALL(FN, FLAGS, XD, YD, ...)                      \
-  (((FLAGS) & SMM_APPLY_SKIPNA) ? SMM_DISPATCH_NA(FN, true, XD, YD, __VA_ARGS__) \
-                                : SMM_DISPATCH_NA(FN, false, XD, YD, __VA_ARGS__))
-
-// FN<PackedX<raw, decode type>, double, SKIPNA>(...) for packed X (SMM_I16 / SMM_U16) decoded to DD (SMM_F32 / SMM_F64)
-#define SMM_DISPATCH_CF_NA(FN, NA, XD, DD, ...)                                                       \
-  ((XD) == SMM_I16 ? ((DD) == SMM_F64 ? FN<PackedX<int16_t, double>, double, NA>(__VA_ARGS__)         \
-                                      : FN<PackedX<int16_t, float>, double, NA>(__VA_ARGS__))         \
-                   : ((DD) == SMM_F64 ? FN<PackedX<uint16_t, double>, double, NA>(__VA_ARGS__)        \
-                                      : FN<PackedX<uint16_t, float>, double, NA>(__VA_ARGS__)))
-#define SMM_DISPATCH_CF(FN, FLAGS, XD, DD, ...)                                        \
-  (((FLAGS) & SMM_APPLY_SKIPNA) ? SMM_DISPATCH_CF_NA(FN, true, XD, DD, __VA_ARGS__)    \
-                                : SMM_DISPATCH_CF_NA(FN, false, XD, DD, __VA_ARGS__))
-
-// FN<X, PackedY<raw>, SKIPNA>(...) for packed Y (YD: SMM_I16 / SMM_U16); X float (XD) or packed with Y's raw type,
-// decoded to DD
-#define SMM_DISPATCH_PK_Q(FN, NA, Q, XD, DD, ...)                                                      \
-  ((XD) == SMM_F64   ? FN<double, PackedY<Q>, NA>(__VA_ARGS__)                                         \
-   : (XD) == SMM_F32 ? FN<float, PackedY<Q>, NA>(__VA_ARGS__)                                          \
-   : (DD) == SMM_F64 ? FN<PackedX<Q, double>, PackedY<Q>, NA>(__VA_ARGS__)                             \
-                     : FN<PackedX<Q, float>, PackedY<Q>, NA>(__VA_ARGS__))
-#define SMM_DISPATCH_PK_NA(FN, NA, YD, XD, DD, ...)                                  \
-  ((YD) == SMM_I16 ? SMM_DISPATCH_PK_Q(FN, NA, int16_t, XD, DD, __VA_ARGS__)         \
-                   : SMM_DISPATCH_PK_Q(FN, NA, uint16_t, XD, DD, __VA_ARGS__))
-#define SMM_DISPATCH_PK(FN, FLAGS, YD, XD, DD, ...)                                        \
-  (((FLAGS) & SMM_APPLY_SKIPNA) ? SMM_DISPATCH_PK_NA(FN, true, YD, XD, DD, __VA_ARGS__)    \
-                                : SMM_DISPATCH_PK_NA(FN, false, YD, XD, DD, __VA_ARGS__))
 
 namespace {
 
@@ -130,35 +48,74 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
-inline bool is_float_dtype(int d) { return d == SMM_F32 || d == SMM_F64; }
-inline bool is_packed_dtype(int d) { return d == SMM_I16 || d == SMM_U16; }
+constexpr bool is_float_dtype(int d) { return d == SMM_F32 || d == SMM_F64; }
+constexpr bool is_packed_dtype(int d) { return d == SMM_I16 || d == SMM_U16; }
 inline size_t dtype_size(int d) { return d == SMM_F64 ? 8 : (d == SMM_F32 ? 4 : 2); }
 
-// A validated smm_cf_decode_t as the kernels take it (null = a float field, the plain entries)
-struct CfCall {
-  CfParams p;
-  int decode_dtype;
+// The field types and rules of one apply call: filled once at the ABI boundary (apply_entry), then passed down by
+// const reference.  has_cf / has_enc: a validated smm_cf_decode_t (make_cf) / smm_cf_encode_t (make_enc) is in cf / enc.
+struct CallDesc {
+  int x_dtype, y_dtype;
+  unsigned flags;
+  double area_min;               // remap_area_min
+  bool has_cf = false, has_enc = false;
+  CfParams cf{};
+  int decode_dtype = SMM_F64;    // of a packed X
+  CfOutParams enc{};
+  bool packed_x() const { return is_packed_dtype(x_dtype); }
+  bool skipna() const { return (flags & SMM_APPLY_SKIPNA) != 0; }
+  CallDesc with_flags(unsigned f) const {
+    CallDesc c = *this;
+    c.flags = f;
+    return c;
+  }
+  // fn(smm_launch::Built<XT, YT, SKIPNA, TILE>()) for the call's types
+  template <typename F>
+  int dispatch(F&& fn) const {
+    return smm_launch::visit_built(x_dtype, y_dtype, decode_dtype, skipna(), fn);
+  }
 };
-// X dtype check shared by the apply paths: float always, packed only through the _cf entries
-// (enc: a validated smm_cf_encode_t of the _pk entries -- y_dtype is then SMM_I16 / SMM_U16, checked by make_enc)
-inline int check_x_dtype(int x_dtype, int y_dtype, const CfCall* cf, const CfOutParams* enc = nullptr) {
+
+// X dtype check shared by the apply paths: float always, packed only with a decode rule (the _cf / _pk entries); with an
+// encode rule (the _pk entries) y_dtype is SMM_I16 / SMM_U16, checked by make_enc.  This is the place that words the
+// refusals; what it lets through is exactly the built list of smm_built.hpp (static_assert below).
+struct Refusal {
+  int code;
+  const char* msg;
+};
+constexpr Refusal x_dtype_refusal(int x_dtype, int y_dtype, bool cf, bool enc) {
   if (enc) {
-    if (!is_packed_dtype(y_dtype)) return fail(SMM_ERR_INVALID, "an encode rule needs y_dtype SMM_I16 or SMM_U16");
-    if (is_float_dtype(x_dtype)) return SMM_OK;
+    if (!is_packed_dtype(y_dtype)) return {SMM_ERR_INVALID, "an encode rule needs y_dtype SMM_I16 or SMM_U16"};
+    if (is_float_dtype(x_dtype)) return {SMM_OK, nullptr};
     if (!(cf && is_packed_dtype(x_dtype)))
-      return fail(SMM_ERR_UNSUPPORTED, "field dtype must be SMM_F32, SMM_F64 or, with a decode rule, SMM_I16 / SMM_U16");
+      return {SMM_ERR_UNSUPPORTED, "field dtype must be SMM_F32, SMM_F64 or, with a decode rule, SMM_I16 / SMM_U16"};
     if (x_dtype != y_dtype)
-      return fail(SMM_ERR_UNSUPPORTED, "a packed field produces packed results of its own raw type only");
-    return SMM_OK;
+      return {SMM_ERR_UNSUPPORTED, "a packed field produces packed results of its own raw type only"};
+    return {SMM_OK, nullptr};
   }
   if (!(is_float_dtype(x_dtype) || (cf && is_packed_dtype(x_dtype))) || !is_float_dtype(y_dtype))
-    return fail(SMM_ERR_UNSUPPORTED, is_packed_dtype(x_dtype)
-                                         ? "SMM_I16 / SMM_U16 fields go through the _cf entries (smm_apply_cf, ...)"
-                                         : "field dtype must be SMM_F32 or SMM_F64");
+    return {SMM_ERR_UNSUPPORTED, is_packed_dtype(x_dtype)
+                                     ? "SMM_I16 / SMM_U16 fields go through the _cf entries (smm_apply_cf, ...)"
+                                     : "field dtype must be SMM_F32 or SMM_F64"};
   if (cf && is_packed_dtype(x_dtype) && y_dtype != SMM_F64)
-    return fail(SMM_ERR_UNSUPPORTED, "packed fields produce SMM_F64 results (y_dtype SMM_F32 is not built)");
-  return SMM_OK;
+    return {SMM_ERR_UNSUPPORTED, "packed fields produce SMM_F64 results (y_dtype SMM_F32 is not built)"};
+  return {SMM_OK, nullptr};
 }
+inline int check_x_dtype(const CallDesc& c) {
+  const Refusal r = x_dtype_refusal(c.x_dtype, c.y_dtype, c.has_cf, c.has_enc);
+  return r.code ? fail(r.code, r.msg) : SMM_OK;
+}
+// A call that carries the rules its dtypes need (a packed X its decode rule, a packed Y its encode rule) is accepted
+// exactly when its combination is built.
+constexpr bool refusals_match_built() {
+  for (int x = SMM_F32; x <= SMM_U16; ++x)
+    for (int y = SMM_F32; y <= SMM_U16; ++y)
+      for (int dd = SMM_F32; dd <= SMM_F64; ++dd)
+        if ((x_dtype_refusal(x, y, is_packed_dtype(x), is_packed_dtype(y)).code == SMM_OK) != smm_launch::is_built(x, y, dd))
+          return false;
+  return true;
+}
+static_assert(refusals_match_built(), "check_x_dtype and SMM_BUILT (smm_built.hpp) disagree");
 
 }  // namespace
 
@@ -230,6 +187,7 @@ struct HostPipe {
     grow_host(hy, cap_hy, need_hy);
     return e;
   }
+  hipError_t mark(int b, int k) { return hipEventRecord(ev[b][k], stream[b]); }   // stage boundary k of buffer b
   // After a failed chunk: wait for whatever is still queued on both streams (an async D2H into the
   // caller's Y of the previous chunk), so that nothing writes into caller memory after the return.
   void quiesce() {
@@ -421,8 +379,8 @@ int ensure_plan(smm_operator* op, int which) {
   return SMM_OK;
 }
 
-// launch_sell / launch_tile live in smm_launch.hpp; their four dtype instantiations are compiled in
-// smm_launch_inst.hip (one object per pair) and only declared here
+// the launch templates live in smm_launch.hpp; their instantiations (SMM_BUILT, smm_built.hpp) are compiled in
+// smm_launch_inst.hip and only declared here
 using smm_launch::launch_sell;
 using smm_launch::launch_tile;
 using smm_launch::launch_sb;
@@ -469,27 +427,44 @@ struct LaunchInfo {
   int64_t n_jtiles = 0, n_blocks = 0, lds_bytes = 0;
 };
 
-// Common launch path for a single operator (descs = op->d_desc) or a group.
-int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t* d_lev_masked,
-              int64_t n_src, int64_t n_dst, int tile_which, bool tile_ok, bool tile_preferred,
-              int tile_flags, int64_t tile_max_chunks,
-              int64_t max_row_nnz, const void* x, int x_dtype, int64_t xs_o, int64_t xs_l,
-              int64_t xs_i, void* y, int y_dtype, int64_t ys_o, int64_t ys_l, int64_t ys_i,
-              int64_t n_outer, int64_t n_lev, int64_t n_inner, double area_min, unsigned flags,
-              hipStream_t s, LaunchInfo* info_only = nullptr, const CfCall* cf = nullptr,
-              const CfOutParams* enc = nullptr) {
+// What run_apply launches: the level descriptors and the tile plan of one operator or of a group
+struct ApplyTarget {
+  const LevelDesc* d_descs;
+  int64_t n_src, n_dst;
+  int tile_which;
+  bool tile_ok, tile_preferred;
+  int tile_flags;   // bit 0: some staged lines are shared by several blocks
+  int64_t tile_max_chunks, max_row_nnz;
+};
+ApplyTarget target_of(const smm_operator* op) {
+  const int pw = op->native_plan();
+  const smm_operator::TilePlan& pl = op->plan[pw];
+  return {op->d_desc, op->csr.n_src, op->csr.n_dst, pw, pl.valid, pl.preferred, pl.reuse ? 1 : 0, pl.max_chunks,
+          op->csr.max_row_nnz};
+}
+ApplyTarget target_of(const smm_group* g) {
+  return {g->d_descs, g->ops[0]->csr.n_src, g->ops[0]->csr.n_dst, g->tile_which, g->tile_valid, g->tile_preferred,
+          g->tile_reuse ? 1 : 0, g->tile_max_chunks, g->max_row_nnz};
+}
+
+// Common launch path for a single operator or a group.  info_only: nothing is launched, *info_only gets the geometry.
+int run_apply(const ApplyTarget& t, const int32_t* d_lev_map, const uint8_t* d_lev_masked, const void* x, int64_t xs_o,
+              int64_t xs_l, int64_t xs_i, void* y, int64_t ys_o, int64_t ys_l, int64_t ys_i, int64_t n_outer,
+              int64_t n_lev, int64_t n_inner, const CallDesc& call, hipStream_t s, LaunchInfo* info_only = nullptr) {
+  const int64_t n_src = t.n_src, n_dst = t.n_dst, tile_max_chunks = t.tile_max_chunks, max_row_nnz = t.max_row_nnz;
+  const int tile_which = t.tile_which;
+  const unsigned flags = call.flags;
+  const double area_min = call.area_min;
   if (n_outer < 0 || n_lev < 0 || n_inner < 0) return fail(SMM_ERR_INVALID, "negative batch size");
   if (n_outer == 0 || n_lev == 0 || n_inner == 0 || n_dst == 0) return SMM_OK;
   if (!info_only && (!x || !y)) return fail(SMM_ERR_INVALID, "null field pointer");
-  const bool packed = is_packed_dtype(x_dtype);
-  static const CfCall kInfoCf{{1.0, 0.0, 0x7fffffff, 0x7fffffff}, SMM_F32};   // launch info: the geometry does not depend on it
-  if (packed && info_only && !cf) cf = &kInfoCf;
-  if (int drc = check_x_dtype(x_dtype, y_dtype, cf, enc)) return drc;
+  const bool packed = call.packed_x(), enc = call.has_enc;
+  if (int drc = check_x_dtype(call)) return drc;
   if (!(area_min >= 0.0 && area_min <= 1.0))
     return fail(SMM_ERR_INVALID, "remap_area_min must be within [0, 1]");  // regrid.py:124-125
 
   ApplyArgs a{};
-  a.descs = d_descs;
+  a.descs = t.d_descs;
   a.lev_map = d_lev_map;
   a.lev_masked = d_lev_masked;
   a.x = x;
@@ -508,10 +483,10 @@ int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t*
   a.area_min = area_min;
   a.masked = (flags & SMM_APPLY_MASKED) ? 1 : 0;
   const bool fill = !(flags & SMM_APPLY_NO_FILL);
-  if (packed) a.cf = cf->p;
-  if (enc) a.cfo = *enc;
+  if (packed) a.cf = call.cf;
+  if (enc) a.cfo = call.enc;
 
-  const size_t xsz = dtype_size(x_dtype);
+  const size_t xsz = dtype_size(call.x_dtype);
   bool use_tile = false;
   // SMM_APPLY_SKIPNA: tile forms without a skipna variant (split rows, rows streamed from L2) run kernel A instead
   const bool tile_skipna_ok = !(flags & SMM_APPLY_SKIPNA) ||
@@ -524,12 +499,12 @@ int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t*
     if (!info_only && ((uintptr_t)x % xsz) != 0) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
     if (!info_only && enc && ((uintptr_t)y % 2) != 0) return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
   } else if (flags & SMM_APPLY_KERNEL_TILE) {
-    if (!tile_ok) return fail(SMM_ERR_UNSUPPORTED, "operator has no LDS tile plan");
+    if (!t.tile_ok) return fail(SMM_ERR_UNSUPPORTED, "operator has no LDS tile plan");
     if (!tile_skipna_ok)
       return fail(SMM_ERR_UNSUPPORTED, "SMM_APPLY_SKIPNA: the planned tile form (split or streamed rows) has no skipna variant");
     use_tile = true;
   } else if (!(flags & SMM_APPLY_KERNEL_SELL)) {
-    use_tile = tile_ok && tile_preferred && tile_skipna_ok;
+    use_tile = t.tile_ok && t.tile_preferred && tile_skipna_ok;
   }
   // The staging loads are 16 B wide but only need element alignment (unaligned 16-B global loads
   // are legal on gfx950; rows of odd length still run ~10 % faster than the SELL kernel).
@@ -538,7 +513,6 @@ int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t*
     use_tile = false;
   }
 
-#define SMM_DISPATCH(FN, ...) SMM_DISPATCH_ALL(FN, flags, x_dtype, y_dtype, __VA_ARGS__)
   if (use_tile) {
     const int64_t rows = shape_rows(tile_which);          // destination rows per block of the tile plan
     a.n_dblocks = (n_dst + rows - 1) / rows;
@@ -578,26 +552,27 @@ int run_apply(const LevelDesc* d_descs, const int32_t* d_lev_map, const uint8_t*
     const int bt = smm_launch::sell_batch_rows(t.n_j);
     return t.n_dblocks * ((t.n_j + bt - 1) / bt) * n_lev;
   };
-  const size_t ysz = dtype_size(y_dtype);
+  const size_t ysz = dtype_size(call.y_dtype);
   auto launch_part = [&](int64_t o0, int64_t n_o, int64_t i0, int64_t n_i) -> int {
     ApplyArgs p = a;
     p.x = (const char*)x + (o0 * xs_o + i0 * xs_i) * (int64_t)xsz;
     p.y = (char*)y + (o0 * ys_o + i0 * ys_i) * (int64_t)ysz;
     p.n_j = n_o * n_i;
     p.n_inner = n_i;
-    if (enc)
-      return SMM_DISPATCH_PK(launch_sell, flags, y_dtype, x_dtype, (cf ? cf->decode_dtype : SMM_F64), p, n_lev, fill, flags, s);
-    if (packed) return SMM_DISPATCH_CF(launch_sell, flags, x_dtype, cf->decode_dtype, p, n_lev, fill, flags, s);
-    if (use_tile)
-      return SMM_DISPATCH(launch_tile, p, n_lev, tile_which, tile_max_chunks, max_row_nnz, tile_flags, fill, flags, s);
-    return SMM_DISPATCH(launch_sell, p, n_lev, fill, flags, s);
+    return call.dispatch([&](auto b) -> int {
+      using B = decltype(b);
+      if constexpr (B::tile)   // float pairs: the only ones use_tile can be set for
+        if (use_tile)
+          return launch_tile<typename B::XT, typename B::YT, B::skipna>(p, n_lev, tile_which, tile_max_chunks, max_row_nnz,
+                                                                        t.tile_flags, fill, flags, s);
+      return launch_sell<typename B::XT, typename B::YT, B::skipna>(p, n_lev, fill, flags, s);
+    });
   };
   const int rc = smm::split_batch(0, n_outer, 0, n_inner, grid_limit(), blocks_for, launch_part);
   if (rc == -1)
     return fail(SMM_ERR_INVALID, "one batch row alone needs a launch grid beyond " + std::to_string(grid_limit()) +
                                      " workgroups (destination blocks x levels)");
   return rc;
-#undef SMM_DISPATCH
 }
 
 }  // namespace
@@ -672,6 +647,39 @@ bool is_pinned(const void* p) {
     return false;
   }
   return attr.type == hipMemoryTypeHost;
+}
+
+// The loop both host pipelines share; chunk c runs in buffer c & 1.  launch(c, b) stages chunk c, enqueues its H2D, its
+// kernels and its D2H on pipe.stream[b] and marks the four stage boundaries between them (pipe.mark: the first lies
+// between the host staging and the H2D, so the marks cannot sit out here); deliver(c, b) copies the chunk's results out
+// of the pinned buffer once its stream has drained.  Buffer b is free again once chunk c-2 has been delivered.  Any
+// failure first waits for the copies still in flight into the caller's buffers (chunk c-1's D2H) before it is returned.
+template <typename Launch, typename Deliver>
+int run_host_pipeline(HostPipe& pipe, int64_t n_chunks, CallStats& st, Launch&& launch, Deliver&& deliver) {
+  auto drain = [&](int64_t c) -> int {
+    const int b = (int)(c & 1);
+    {
+      StageTimer t(st.v[SMM_HOST_STAT_WAIT_MS]);
+      SMM_HIP(hipStreamSynchronize(pipe.stream[b]));
+    }
+    st.chunk_done(pipe, b);
+    return deliver(c, b);
+  };
+  const int64_t fail_at = test_fail_chunk();
+  auto loop = [&]() -> int {
+    for (int64_t c = 0; c < n_chunks; ++c) {
+      if (c >= 2)
+        if (int rc = drain(c - 2)) return rc;
+      if (c == fail_at) return fail(SMM_ERR_HIP, "injected failure (smm_debug_fail_at_chunk)");
+      if (int rc = launch(c, (int)(c & 1))) return rc;
+    }
+    for (int64_t c = std::max<int64_t>(0, n_chunks - 2); c < n_chunks; ++c)
+      if (int rc = drain(c)) return rc;
+    return SMM_OK;
+  };
+  const int rc = loop();
+  if (rc) pipe.quiesce();   // keeps the thread's error message of the first failure
+  return rc;
 }
 
 }  // namespace
@@ -1158,9 +1166,10 @@ static int smm_operator_plan_info_impl(smm_operator_t op, int* kernel_kind, int6
   return SMM_OK;
 }
 
-static int smm_apply_impl(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype,
-              int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream,
-              const CfCall* cf = nullptr, const CfOutParams* enc = nullptr) {
+static int smm_apply_impl(smm_operator_t op, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t n_batch,
+                          void* stream, const CallDesc& call) {
+  const unsigned flags = call.flags;
+  const double remap_area_min = call.area_min;
   if (int frc = check_flags(flags)) return frc;
   if (!op) return fail(SMM_ERR_INVALID, "null operator");
   if (n_batch > 0 && (ldx < op->csr.n_src || ldy < op->csr.n_dst))
@@ -1171,11 +1180,7 @@ static int smm_apply_impl(smm_operator_t op, const void* x, int x_dtype, int64_t
     return fail(SMM_ERR_INVALID, "remap_area_min > 0 requested but the operator has no dst_frac");
   DeviceGuard guard(op->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
-  const int pw = op->native_plan();
-  const smm_operator::TilePlan& pl = op->plan[pw];
-  return run_apply(op->d_desc, nullptr, nullptr, op->csr.n_src, op->csr.n_dst, pw, pl.valid,
-                   pl.preferred, (pl.reuse ? 1 : 0), pl.max_chunks, op->csr.max_row_nnz, x, x_dtype, ldx, 0, 0, y, y_dtype, ldy,
-                   0, 0, n_batch, 1, 1, remap_area_min, flags, (hipStream_t)stream, nullptr, cf, enc);
+  return run_apply(target_of(op), nullptr, nullptr, x, ldx, 0, 0, y, ldy, 0, 0, n_batch, 1, 1, call, (hipStream_t)stream);
 }
 
 static int smm_operator_prepare_sb_impl(smm_operator_t op) {
@@ -1196,16 +1201,16 @@ static int smm_operator_used_sources_impl(smm_operator_t op, int32_t* used) {
   return SMM_OK;
 }
 
-static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype,
-                 int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream,
-                 const CfCall* cf = nullptr, const CfOutParams* enc = nullptr) {
+static int smm_apply_sb_impl(smm_operator_t op, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t n_batch,
+                             void* stream, const CallDesc& call) {
+  const unsigned flags = call.flags;
+  const double remap_area_min = call.area_min;
   if (int frc = check_flags(flags)) return frc;
   if (!op) return fail(SMM_ERR_INVALID, "null operator");
   if (n_batch < 0) return fail(SMM_ERR_INVALID, "negative batch size");
   if (n_batch == 0 || op->csr.n_dst == 0) return SMM_OK;
   if (!x || !y) return fail(SMM_ERR_INVALID, "null field pointer");
-  if (int drc = check_x_dtype(x_dtype, y_dtype, cf, enc)) return drc;
-  const bool packed = is_packed_dtype(x_dtype);
+  if (int drc = check_x_dtype(call)) return drc;
   if (ldx < n_batch || ldy < ((flags & SMM_APPLY_SB_Y_SB) ? n_batch : op->csr.n_dst))
     return fail(SMM_ERR_INVALID, "ldx smaller than the batch or ldy smaller than a row of Y");
   if (!(remap_area_min >= 0.0 && remap_area_min <= 1.0))
@@ -1214,7 +1219,7 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int6
     return fail(SMM_ERR_INVALID, "masked apply requested but the operator has no dst_imask");
   if (remap_area_min > 0.0 && !op->d_frac)
     return fail(SMM_ERR_INVALID, "remap_area_min > 0 requested but the operator has no dst_frac");
-  const size_t xsz = dtype_size(x_dtype), ysz = dtype_size(y_dtype);
+  const size_t xsz = dtype_size(call.x_dtype), ysz = dtype_size(call.y_dtype);
   if ((uintptr_t)x % xsz || (uintptr_t)y % ysz) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
   DeviceGuard guard(op->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
@@ -1234,8 +1239,8 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int6
   a.n_dst = op->csr.n_dst;
   a.area_min = remap_area_min;
   a.masked = (flags & SMM_APPLY_MASKED) ? 1 : 0;
-  if (packed) a.cf = cf->p;
-  if (enc) a.cfo = *enc;
+  if (call.packed_x()) a.cf = call.cf;
+  if (call.has_enc) a.cfo = call.enc;
   const bool fill = !(flags & SMM_APPLY_NO_FILL);
   hipStream_t s = (hipStream_t)stream;
   // grid = destination tiles x batch tiles of 128 entries: beyond the limit the batch is cut into runs of
@@ -1250,9 +1255,10 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int6
     a.x = (const char*)x + b0 * (int64_t)xsz;
     a.y = (char*)y + ((flags & SMM_APPLY_SB_Y_SB) ? b0 : b0 * ldy) * (int64_t)ysz;
     a.n_batch = std::min(part, n_batch - b0);
-    rc = enc      ? SMM_DISPATCH_PK(launch_sb, flags, y_dtype, x_dtype, (cf ? cf->decode_dtype : SMM_F64), a, fill, flags, s)
-         : packed ? SMM_DISPATCH_CF(launch_sb, flags, x_dtype, cf->decode_dtype, a, fill, flags, s)
-                  : SMM_DISPATCH_ALL(launch_sb, flags, x_dtype, y_dtype, a, fill, flags, s);
+    rc = call.dispatch([&](auto b) {
+      using B = decltype(b);
+      return launch_sb<typename B::XT, typename B::YT, B::skipna>(a, fill, flags, s);
+    });
     if (rc) return rc;
   }
   return SMM_OK;
@@ -1260,15 +1266,17 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int x_dtype, int6
 
 // ---- host-buffer path: chunked, double-buffered H2D -> kernel -> D2H pipeline
 
-static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int x_dtype, int64_t ldx, void* y_host,
-                   int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags,
-                   int64_t chunk_rows, const CfCall* cf = nullptr, const CfOutParams* enc = nullptr) {
+static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int64_t ldx, void* y_host, int64_t ldy,
+                               int64_t n_batch, int64_t chunk_rows, const CallDesc& call) {
+  const int x_dtype = call.x_dtype, y_dtype = call.y_dtype;
+  const unsigned flags = call.flags;
+  const bool enc = call.has_enc;
   if (int frc = check_flags(flags)) return frc;
   if (!op) return fail(SMM_ERR_INVALID, "null operator");
   if (n_batch < 0) return fail(SMM_ERR_INVALID, "negative batch size");
   if (n_batch == 0 || op->csr.n_dst == 0) return SMM_OK;
   if (!x_host || !y_host) return fail(SMM_ERR_INVALID, "null field pointer");
-  if (int drc = check_x_dtype(x_dtype, y_dtype, cf, enc)) return drc;
+  if (int drc = check_x_dtype(call)) return drc;
   if ((uintptr_t)x_host % dtype_size(x_dtype)) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
   if (enc && (uintptr_t)y_host % 2) return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
   const int64_t S = op->csr.n_src, D = op->csr.n_dst;
@@ -1318,40 +1326,17 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int x_dtyp
 
   const int64_t n_chunks = (n_batch + chunk_rows - 1) / chunk_rows;
   CallStats st;
-  auto drain = [&](int64_t c) -> int {  // results of chunk c: wait, then pinned -> user rows
-    const int b = (int)(c & 1);
-    {
-      StageTimer t(st.v[SMM_HOST_STAT_WAIT_MS]);
-      SMM_HIP(hipStreamSynchronize(pipe.stream[b]));
-    }
-    st.chunk_done(pipe, b);
-    if (!y_direct) {
-      StageTimer t(st.v[SMM_HOST_STAT_COPY_OUT_MS]);
-      const int64_t r0 = c * chunk_rows, rows = std::min(chunk_rows, n_batch - r0);
-      if ((int64_t)ldy == D) {
-        int rc = host_copy((char*)y_host + (size_t)r0 * yrow, pipe.hy[b], (size_t)rows * D * ysz);
-        if (rc) return rc;
-      } else {
-        for (int64_t r = 0; r < rows; ++r)
-          memcpy((char*)y_host + (size_t)(r0 + r) * yrow, (char*)pipe.hy[b] + (size_t)r * D * ysz,
-                 (size_t)D * ysz);
-      }
-    }
+  auto deliver = [&](int64_t c, int b) -> int {  // results of chunk c: pinned -> user rows
+    if (y_direct) return SMM_OK;
+    StageTimer t(st.v[SMM_HOST_STAT_COPY_OUT_MS]);
+    const int64_t r0 = c * chunk_rows, rows = std::min(chunk_rows, n_batch - r0);
+    if ((int64_t)ldy == D) return host_copy((char*)y_host + (size_t)r0 * yrow, pipe.hy[b], (size_t)rows * D * ysz);
+    for (int64_t r = 0; r < rows; ++r)
+      memcpy((char*)y_host + (size_t)(r0 + r) * yrow, (char*)pipe.hy[b] + (size_t)r * D * ysz, (size_t)D * ysz);
     return SMM_OK;
   };
-
-  // The chunk loop runs inside a lambda so that any failure can first wait for the copies still
-  // in flight into the caller's buffers (chunk c-1's D2H) before the error is returned.
-  const int64_t fail_at = test_fail_chunk();
-  auto pipeline = [&]() -> int {
-  for (int64_t c = 0; c < n_chunks; ++c) {
-    const int b = (int)(c & 1);
+  auto launch = [&](int64_t c, int b) -> int {
     const int64_t r0 = c * chunk_rows, rows = std::min(chunk_rows, n_batch - r0);
-    if (c >= 2) {
-      int rc = drain(c - 2);  // buffer b is free again once chunk c-2 has been delivered
-      if (rc) return rc;
-    }
-    if (c == fail_at) return fail(SMM_ERR_HIP, "injected failure (smm_debug_fail_at_chunk)");
     const char* xsrc = (const char*)x_host + (size_t)r0 * xrow;
     if (pack) {
       {
@@ -1359,7 +1344,7 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int x_dtyp
         int rc = host_pack(pipe.hx[b], xsrc, xsz, ldx, op->h_used, rows);
         if (rc) return rc;
       }
-      SMM_HIP(hipEventRecord(pipe.ev[b][0], pipe.stream[b]));
+      SMM_HIP(pipe.mark(b, 0));
       SMM_HIP(hipMemcpyAsync(pipe.dx[b], pipe.hx[b], (size_t)U * rows * xsz, hipMemcpyHostToDevice, pipe.stream[b]));
       st.v[SMM_HOST_STAT_H2D_BYTES] += (double)((size_t)U * rows * xsz);
     } else if (!x_direct) {
@@ -1373,31 +1358,27 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int x_dtyp
             memcpy((char*)pipe.hx[b] + (size_t)r * S * xsz, xsrc + (size_t)r * xrow, (size_t)S * xsz);
         }
       }
-      SMM_HIP(hipEventRecord(pipe.ev[b][0], pipe.stream[b]));
+      SMM_HIP(pipe.mark(b, 0));
       SMM_HIP(hipMemcpy2DAsync(pipe.dx[b], xrow_d, pipe.hx[b], (size_t)S * xsz, (size_t)S * xsz,
                                (size_t)rows, hipMemcpyHostToDevice, pipe.stream[b]));
     } else {
-      SMM_HIP(hipEventRecord(pipe.ev[b][0], pipe.stream[b]));
+      SMM_HIP(pipe.mark(b, 0));
       SMM_HIP(hipMemcpy2DAsync(pipe.dx[b], xrow_d, xsrc, xrow, (size_t)S * xsz, (size_t)rows,
                                hipMemcpyHostToDevice, pipe.stream[b]));
     }
     if (!pack) st.v[SMM_HOST_STAT_H2D_BYTES] += (double)((size_t)S * rows * xsz);
-    SMM_HIP(hipEventRecord(pipe.ev[b][1], pipe.stream[b]));
-    const int pw = op->native_plan();
-    const smm_operator::TilePlan& pl = op->plan[pw];
+    SMM_HIP(pipe.mark(b, 1));
     int rc = SMM_OK;
     if (pack)
-      rc = smm_apply_sb_impl(op, pipe.dx[b], x_dtype, rows, pipe.dy[b], y_dtype, D, rows, remap_area_min,
-                         (flags & (SMM_APPLY_MASKED | SMM_APPLY_NO_FILL | SMM_APPLY_SKIPNA)) | SMM_APPLY_SB_PACKED,
-                         pipe.stream[b], cf, enc);
+      rc = smm_apply_sb_impl(op, pipe.dx[b], rows, pipe.dy[b], D, rows, pipe.stream[b],
+                             call.with_flags((flags & (SMM_APPLY_MASKED | SMM_APPLY_NO_FILL | SMM_APPLY_SKIPNA)) |
+                                             SMM_APPLY_SB_PACKED));
     else
-      rc = run_apply(op->d_desc, nullptr, nullptr, S, op->csr.n_dst, pw, pl.valid, pl.preferred, (pl.reuse ? 1 : 0),
-                     pl.max_chunks, op->csr.max_row_nnz, pipe.dx[b], x_dtype,
-                     ldx_d, 0, 0, pipe.dy[b], y_dtype, D, 0, 0, rows, 1, 1, remap_area_min, flags,
-                     pipe.stream[b], nullptr, cf, enc);
+      rc = run_apply(target_of(op), nullptr, nullptr, pipe.dx[b], ldx_d, 0, 0, pipe.dy[b], D, 0, 0, rows, 1, 1, call,
+                     pipe.stream[b]);
     if (rc) return rc;
     st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)rows * D * ysz);
-    SMM_HIP(hipEventRecord(pipe.ev[b][2], pipe.stream[b]));
+    SMM_HIP(pipe.mark(b, 2));
     if (!y_direct) {
       SMM_HIP(hipMemcpyAsync(pipe.hy[b], pipe.dy[b], (size_t)rows * D * ysz, hipMemcpyDeviceToHost,
                              pipe.stream[b]));
@@ -1405,17 +1386,10 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int x_dtyp
       SMM_HIP(hipMemcpy2DAsync((char*)y_host + (size_t)r0 * yrow, yrow, pipe.dy[b], (size_t)D * ysz,
                                (size_t)D * ysz, (size_t)rows, hipMemcpyDeviceToHost, pipe.stream[b]));
     }
-    SMM_HIP(hipEventRecord(pipe.ev[b][3], pipe.stream[b]));
-  }
-  for (int64_t c = std::max<int64_t>(0, n_chunks - 2); c < n_chunks; ++c) {
-    int rc = drain(c);
-    if (rc) return rc;
-  }
-  return SMM_OK;
+    SMM_HIP(pipe.mark(b, 3));
+    return SMM_OK;
   };
-  const int prc = pipeline();
-  if (prc) pipe.quiesce();   // keeps the thread's error message of the first failure
-  return prc;
+  return run_host_pipeline(pipe, n_chunks, st, launch, deliver);
 }
 
 static int smm_operator_mask_apply_impl(smm_operator_t op, const int32_t* src_imask, int32_t* dst_imask) {
@@ -1446,9 +1420,10 @@ static int smm_operator_mask_apply_impl(smm_operator_t op, const int32_t* src_im
     cleanup();
     return fail(SMM_ERR_HIP, "hipMemcpy failed in smm_operator_mask_apply");
   }
-  rc = run_apply(op->d_desc, nullptr, nullptr, S, op->csr.n_dst, 0, false, false, false, 0, op->csr.max_row_nnz, dx, SMM_F64,
-                 std::max<int64_t>(S, 1), 0, 0, dy, SMM_F64, D, 0, 0, 1, 1, 1, 0.0,
-                 SMM_APPLY_NO_FILL, nullptr);
+  ApplyTarget sell_only = target_of(op);   // one row: kernel A whatever the plan
+  sell_only.tile_ok = false;
+  rc = run_apply(sell_only, nullptr, nullptr, dx, std::max<int64_t>(S, 1), 0, 0, dy, D, 0, 0, 1, 1, 1,
+                 CallDesc{SMM_F64, SMM_F64, SMM_APPLY_NO_FILL, 0.0}, nullptr);
   if (rc == SMM_OK) {
     const int threads = 256;
     hipLaunchKernelGGL(smm_mask_threshold_kernel, dim3((unsigned)((D + threads - 1) / threads)),
@@ -1594,24 +1569,20 @@ static int smm_group_prepare_impl(smm_group_t g, int64_t n_lev, const int32_t* l
   return group_level_cfg(g, n_lev, level_index, masked_levels, 0.0, 0u, &d_map, &d_masked);
 }
 
-static int smm_group_apply_impl(smm_group_t g, const void* x, int x_dtype, int64_t xs_outer, int64_t xs_lev,
-                    int64_t xs_inner, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev,
-                    int64_t ys_inner, int64_t n_outer, int64_t n_lev, int64_t n_inner,
-                    const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min,
-                    unsigned flags, void* stream, const CfCall* cf = nullptr, const CfOutParams* enc = nullptr) {
-  if (int frc = check_flags(flags)) return frc;
+static int smm_group_apply_impl(smm_group_t g, const void* x, int64_t xs_outer, int64_t xs_lev, int64_t xs_inner, void* y,
+                                int64_t ys_outer, int64_t ys_lev, int64_t ys_inner, int64_t n_outer, int64_t n_lev,
+                                int64_t n_inner, const int32_t* level_index, const uint8_t* masked_levels, void* stream,
+                                const CallDesc& call) {
+  if (int frc = check_flags(call.flags)) return frc;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
   DeviceGuard guard(g->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the group's device");
   const int32_t* d_map;
   const uint8_t* d_masked;
-  int rc = group_level_cfg(g, n_lev, level_index, masked_levels, remap_area_min, flags, &d_map, &d_masked);
+  int rc = group_level_cfg(g, n_lev, level_index, masked_levels, call.area_min, call.flags, &d_map, &d_masked);
   if (rc || n_lev == 0) return rc;
-  const smm_operator* op0 = g->ops[0];
-  return run_apply(g->d_descs, d_map, d_masked, op0->csr.n_src, op0->csr.n_dst, g->tile_which,
-                   g->tile_valid, g->tile_preferred, (g->tile_reuse ? 1 : 0), g->tile_max_chunks, g->max_row_nnz, x, x_dtype, xs_outer, xs_lev, xs_inner, y,
-                   y_dtype, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner, remap_area_min,
-                   flags, (hipStream_t)stream, nullptr, cf, enc);
+  return run_apply(target_of(g), d_map, d_masked, x, xs_outer, xs_lev, xs_inner, y, ys_outer, ys_lev, ys_inner, n_outer,
+                   n_lev, n_inner, call, (hipStream_t)stream);
 }
 
 extern "C++" {
@@ -1654,18 +1625,18 @@ static int smm_group_prepare_sb_impl(smm_group_t g) {
 // BASELINE config 3 kept batch-fastest, same box: 9.51 ms against 10.24 ms for one launch per level dealt over a
 // pool of 8 streams (round 4's form, removed: profiles/r05_cfg3sb_grouped_vs_stream_pool.txt) and 14.4 ms for one
 // launch per level on one stream (still there: SMM_TUNE_SB_LEVEL_LAUNCHES, and for levels beyond the grid limit).
-static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, int64_t xs_lev, int64_t ldx, void* y,
-                       int y_dtype, int64_t ys_lev, int64_t ys_batch, int64_t n_batch, int64_t n_lev,
-                       const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min,
-                       unsigned flags, void* stream, const CfCall* cf = nullptr, const CfOutParams* enc = nullptr) {
+static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int64_t xs_lev, int64_t ldx, void* y, int64_t ys_lev,
+                                   int64_t ys_batch, int64_t n_batch, int64_t n_lev, const int32_t* level_index,
+                                   const uint8_t* masked_levels, void* stream, const CallDesc& call) {
+  const unsigned flags = call.flags;
+  const double remap_area_min = call.area_min;
   if (int frc = check_flags(flags)) return frc;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
   if (n_batch < 0 || n_lev < 0) return fail(SMM_ERR_INVALID, "negative batch size / level count");
   if (n_lev > 0 && !level_index) return fail(SMM_ERR_INVALID, "null level_index");
   if (flags & SMM_APPLY_SB_PACKED)
     return fail(SMM_ERR_UNSUPPORTED, "packed fields are per operator: a group takes whole (S, B) slabs");
-  if (int drc = check_x_dtype(x_dtype, y_dtype, cf, enc)) return drc;
-  const bool packed = is_packed_dtype(x_dtype);   // CF-packed: raw 2-byte slabs, one decode rule for every level
+  if (int drc = check_x_dtype(call)) return drc;
   const int n_ops = (int)g->ops.size();
   for (int64_t l = 0; l < n_lev; ++l)
     if (level_index[l] < 0 || level_index[l] >= n_ops)
@@ -1673,7 +1644,7 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, in
                                        " outside the group");
   if (n_lev == 0 || n_batch == 0 || g->ops[0]->csr.n_dst == 0) return SMM_OK;
   if (!x || !y) return fail(SMM_ERR_INVALID, "null field pointer");
-  const size_t xsz = dtype_size(x_dtype), ysz = dtype_size(y_dtype);
+  const size_t xsz = dtype_size(call.x_dtype), ysz = dtype_size(call.y_dtype);
   // the whole call is validated before the first launch (as smm_group_apply does): a later level's
   // missing dst_imask / dst_frac or a bad stride must not surface after earlier levels wrote part of Y
   if (ldx < n_batch) return fail(SMM_ERR_INVALID, "ldx smaller than the batch");
@@ -1717,12 +1688,12 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, in
         const bool m = (flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w]);   // regrid.py:405
         a.lev[i] = SbLevelPtrs{op->d_csr_rowptr, op->d_csr_col, op->d_csr_val, m ? op->d_imask : nullptr, op->d_frac};
       }
-      if (packed) a.cf = cf->p;
-      if (enc) a.cfo = *enc;   // one encode rule for every level
-      const int rc =
-          enc      ? SMM_DISPATCH_PK(launch_sb_group, flags, y_dtype, x_dtype, (cf ? cf->decode_dtype : SMM_F64), a, fill, flags, caller)
-          : packed ? SMM_DISPATCH_CF(launch_sb_group, flags, x_dtype, cf->decode_dtype, a, fill, flags, caller)
-                   : SMM_DISPATCH_ALL(launch_sb_group, flags, x_dtype, y_dtype, a, fill, flags, caller);
+      if (call.packed_x()) a.cf = call.cf;      // CF-packed: raw 2-byte slabs, one decode rule for every level
+      if (call.has_enc) a.cfo = call.enc;       // one encode rule for every level
+      const int rc = call.dispatch([&](auto b) {
+        using B = decltype(b);
+        return launch_sb_group<typename B::XT, typename B::YT, B::skipna>(a, fill, flags, caller);
+      });
       if (rc) return rc;
     }
     return SMM_OK;
@@ -1734,14 +1705,20 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int x_dtype, in
     const int w = level_index[l];
     unsigned fl = flags & ~(unsigned)SMM_APPLY_MASKED;
     if ((flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w])) fl |= SMM_APPLY_MASKED;   // regrid.py:405
-    status = smm_apply_sb_impl(g->ops[(size_t)w], (const char*)x + (size_t)l * xs_lev * xsz, x_dtype, ldx,
-                               (char*)y + (size_t)l * ys_lev * ysz, y_dtype, ys_batch, n_batch, remap_area_min, fl,
-                               caller, cf, enc);
+    status = smm_apply_sb_impl(g->ops[(size_t)w], (const char*)x + (size_t)l * xs_lev * xsz, ldx,
+                               (char*)y + (size_t)l * ys_lev * ysz, ys_batch, n_batch, caller, call.with_flags(fl));
   }
   return status;
 }
 
 extern "C++" {
+// The call the *_launch_info entries describe: an f64 result; a packed x_dtype answers for the _cf entries (the
+// geometry does not depend on the rule)
+static CallDesc info_call(int x_dtype, unsigned flags) {
+  CallDesc c{x_dtype, SMM_F64, flags, 0.0};
+  c.has_cf = c.packed_x();
+  return c;
+}
 static void fill_launch_info(const LaunchInfo& li, int* kernel, int* j_per_block, int* rows_per_step,
                              int* rows_per_block, int64_t* n_blocks, int64_t* lds_bytes, int* big_operator) {
   if (kernel) *kernel = li.tile ? (li.dma ? 2 : 1) : 0;
@@ -1759,12 +1736,9 @@ static int smm_operator_launch_info_impl(smm_operator_t op, int x_dtype, int64_t
                              int64_t* lds_bytes, int* big_operator) {
   if (int frc = check_flags(flags)) return frc;
   if (!op) return fail(SMM_ERR_INVALID, "null operator");
-  const int pw = op->native_plan();
-  const smm_operator::TilePlan& pl = op->plan[pw];
   LaunchInfo li;
-  int rc = run_apply(op->d_desc, nullptr, nullptr, op->csr.n_src, op->csr.n_dst, pw, pl.valid, pl.preferred,
-                     (pl.reuse ? 1 : 0), pl.max_chunks, op->csr.max_row_nnz, nullptr, x_dtype, op->csr.n_src, 0, 0,
-                     nullptr, SMM_F64, op->csr.n_dst, 0, 0, n_batch, 1, 1, 0.0, flags, nullptr, &li);
+  int rc = run_apply(target_of(op), nullptr, nullptr, nullptr, op->csr.n_src, 0, 0, nullptr, op->csr.n_dst, 0, 0, n_batch,
+                     1, 1, info_call(x_dtype, flags), nullptr, &li);
   if (rc) return rc;
   fill_launch_info(li, kernel, j_per_block, rows_per_step, rows_per_block, n_blocks, lds_bytes, big_operator);
   return SMM_OK;
@@ -1775,11 +1749,9 @@ static int smm_group_launch_info_impl(smm_group_t g, int x_dtype, int64_t n_oute
                           int* rows_per_block, int64_t* n_blocks, int64_t* lds_bytes, int* big_operator) {
   if (int frc = check_flags(flags)) return frc;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
-  const smm_operator* op0 = g->ops[0];
   LaunchInfo li;
-  int rc = run_apply(g->d_descs, nullptr, nullptr, op0->csr.n_src, op0->csr.n_dst, g->tile_which, g->tile_valid,
-                     g->tile_preferred, (g->tile_reuse ? 1 : 0), g->tile_max_chunks, g->max_row_nnz, nullptr,
-                     x_dtype, 0, 0, 0, nullptr, SMM_F64, 0, 0, 0, n_outer, n_lev, n_inner, 0.0, flags, nullptr, &li);
+  int rc = run_apply(target_of(g), nullptr, nullptr, nullptr, 0, 0, 0, nullptr, 0, 0, 0, n_outer, n_lev, n_inner,
+                     info_call(x_dtype, flags), nullptr, &li);
   if (rc) return rc;
   fill_launch_info(li, kernel, j_per_block, rows_per_step, rows_per_block, n_blocks, lds_bytes, big_operator);
   return SMM_OK;
@@ -1789,16 +1761,18 @@ static int smm_group_launch_info_impl(smm_group_t g, int x_dtype, int64_t n_oute
 // Y host (n_outer, n_inner, n_lev, D) when transpose != 0 (regrid.py:420-427), else
 // (n_lev, n_outer, n_inner, D) (concat order, regrid.py:410).  Chunks of the outer axis
 // stream through the group's double-buffered H2D / kernel / D2H pipeline.
-static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dtype, void* y_host, int y_dtype,
-                         int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose,
-                         const int32_t* level_index, const uint8_t* masked_levels,
-                         double remap_area_min, unsigned flags, int64_t chunk_outer, const CfCall* cf = nullptr,
-                         const CfOutParams* enc = nullptr) {
+static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, void* y_host, int64_t n_outer, int64_t n_lev,
+                                     int64_t n_inner, int transpose, const int32_t* level_index,
+                                     const uint8_t* masked_levels, int64_t chunk_outer, const CallDesc& call) {
+  const int x_dtype = call.x_dtype, y_dtype = call.y_dtype;
+  const unsigned flags = call.flags;
+  const double remap_area_min = call.area_min;
+  const bool enc = call.has_enc;
   if (int frc = check_flags(flags)) return frc;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
   if (n_outer < 0 || n_lev < 0 || n_inner < 0) return fail(SMM_ERR_INVALID, "negative batch size");
-  if (int drc = check_x_dtype(x_dtype, y_dtype, cf, enc)) return drc;
-  const bool packed = is_packed_dtype(x_dtype);
+  if (int drc = check_x_dtype(call)) return drc;
+  const bool packed = call.packed_x();
   if ((packed || enc) && (flags & SMM_APPLY_KERNEL_TILE))
     return fail(SMM_ERR_UNSUPPORTED, "the LDS tile kernel is not built for packed fields or results (SMM_I16 / SMM_U16)");
   const int64_t S = g->ops[0]->csr.n_src, D = g->ops[0]->csr.n_dst;
@@ -1954,32 +1928,14 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
     }
     return SMM_OK;
   };
-  auto drain = [&](int64_t c) -> int {
-    const int b = (int)(c & 1);
-    {
-      StageTimer t(st.v[SMM_HOST_STAT_WAIT_MS]);
-      SMM_HIP(hipStreamSynchronize(pipe.stream[b]));
-    }
-    st.chunk_done(pipe, b);
-    if (!y_direct) {
-      StageTimer t(st.v[SMM_HOST_STAT_COPY_OUT_MS]);
-      int rc = y_to_host(chunks[(size_t)c], (const char*)pipe.hy[b], false, nullptr);
-      if (rc) return rc;
-    }
-    return SMM_OK;
+  auto deliver = [&](int64_t c, int b) -> int {
+    if (y_direct) return SMM_OK;
+    StageTimer t(st.v[SMM_HOST_STAT_COPY_OUT_MS]);
+    return y_to_host(chunks[(size_t)c], (const char*)pipe.hy[b], false, nullptr);
   };
-
-  const int64_t fail_at = test_fail_chunk();
-  auto pipeline = [&]() -> int {   // see smm_apply_host: errors drain both streams before returning
-  for (int64_t c = 0; c < n_chunks; ++c) {
-    const int b = (int)(c & 1);
+  auto launch = [&](int64_t c, int b) -> int {
     const GChunk& ck = chunks[(size_t)c];
     const int64_t o0 = ck.o0, no = ck.no;
-    if (c >= 2) {
-      int rc = drain(c - 2);
-      if (rc) return rc;
-    }
-    if (c == fail_at) return fail(SMM_ERR_HIP, "injected failure (smm_debug_fail_at_chunk)");
     const char* xsrc = (const char*)x_host + (size_t)o0 * rows_per_outer * S * xsz;
     int rc = SMM_OK;
     if (pack) {
@@ -1995,10 +1951,10 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
           off += (size_t)op->csr.n_used_src * bc * xsz;
         }
       }
-      SMM_HIP(hipEventRecord(pipe.ev[b][0], pipe.stream[b]));
+      SMM_HIP(pipe.mark(b, 0));
       SMM_HIP(hipMemcpyAsync(pipe.dx[b], pipe.hx[b], off, hipMemcpyHostToDevice, pipe.stream[b]));
       st.v[SMM_HOST_STAT_H2D_BYTES] += (double)off;
-      SMM_HIP(hipEventRecord(pipe.ev[b][1], pipe.stream[b]));
+      SMM_HIP(pipe.mark(b, 1));
       off = 0;
       for (int64_t ll = 0; ll < ck.nl && !rc; ++ll) {
         const int w = level_index[ck.l0 + ll];
@@ -2006,9 +1962,9 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
         unsigned fl = (flags & (SMM_APPLY_NO_FILL | SMM_APPLY_SKIPNA)) | SMM_APPLY_SB_PACKED;
         if ((flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w])) fl |= SMM_APPLY_MASKED;
         // Y of the chunk: entry (b, ll, d) at (b * nl + ll) * D + d when transpose, at (ll * bc + b) * D + d else
-        rc = smm_apply_sb_impl(op, (char*)pipe.dx[b] + off, x_dtype, bc,
-                               (char*)pipe.dy[b] + (size_t)ll * (transpose ? D : bc * D) * ysz, y_dtype,
-                               transpose ? ck.nl * D : D, bc, remap_area_min, fl, pipe.stream[b], cf, enc);
+        rc = smm_apply_sb_impl(op, (char*)pipe.dx[b] + off, bc,
+                               (char*)pipe.dy[b] + (size_t)ll * (transpose ? D : bc * D) * ysz,
+                               transpose ? ck.nl * D : D, bc, pipe.stream[b], call.with_flags(fl));
         off += (size_t)op->csr.n_used_src * bc * xsz;
       }
     } else {
@@ -2026,17 +1982,16 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
         if (hrc) return hrc;
         h2d_src = pipe.hx[b];
       }
-      SMM_HIP(hipEventRecord(pipe.ev[b][0], pipe.stream[b]));
+      SMM_HIP(pipe.mark(b, 0));
       SMM_HIP(hipMemcpy2DAsync(pipe.dx[b], xrow_d, h2d_src, (size_t)S * xsz, (size_t)S * xsz, (size_t)rows,
                                hipMemcpyHostToDevice, pipe.stream[b]));
       st.v[SMM_HOST_STAT_H2D_BYTES] += (double)((size_t)S * xsz * (size_t)rows);
-      SMM_HIP(hipEventRecord(pipe.ev[b][1], pipe.stream[b]));
-      rc = smm_group_apply_impl(g, pipe.dx[b], x_dtype, rows_per_outer * ldx_d, n_inner * ldx_d, ldx_d,
-                                pipe.dy[b], y_dtype, ys_o, ys_l, ys_i, no, n_lev, n_inner, level_index,
-                                masked_levels, remap_area_min, flags, pipe.stream[b], cf, enc);
+      SMM_HIP(pipe.mark(b, 1));
+      rc = smm_group_apply_impl(g, pipe.dx[b], rows_per_outer * ldx_d, n_inner * ldx_d, ldx_d, pipe.dy[b], ys_o, ys_l,
+                                ys_i, no, n_lev, n_inner, level_index, masked_levels, pipe.stream[b], call);
     }
     if (rc) return rc;
-    SMM_HIP(hipEventRecord(pipe.ev[b][2], pipe.stream[b]));
+    SMM_HIP(pipe.mark(b, 2));
     st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)no * n_inner * ck.nl * D * ysz);
     if (!y_direct) {
       SMM_HIP(hipMemcpyAsync(pipe.hy[b], pipe.dy[b], (size_t)no * n_inner * ck.nl * D * ysz, hipMemcpyDeviceToHost,
@@ -2045,17 +2000,10 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, int x_dt
       int yrc = y_to_host(ck, (const char*)pipe.dy[b], true, pipe.stream[b]);
       if (yrc) return yrc;
     }
-    SMM_HIP(hipEventRecord(pipe.ev[b][3], pipe.stream[b]));
-  }
-  for (int64_t c = std::max<int64_t>(0, n_chunks - 2); c < n_chunks; ++c) {
-    int rc = drain(c);
-    if (rc) return rc;
-  }
-  return SMM_OK;
+    SMM_HIP(pipe.mark(b, 3));
+    return SMM_OK;
   };
-  const int prc = pipeline();
-  if (prc) pipe.quiesce();
-  return prc;
+  return run_host_pipeline(pipe, n_chunks, st, launch, deliver);
 }
 
 }  // extern "C"
@@ -2080,26 +2028,13 @@ int smm_operator_used_sources(smm_operator_t op, int32_t* used) {
   return guarded([&] { return smm_operator_used_sources_impl(op, used); });
 }
 
-int smm_apply(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream) {
-  return guarded([&] { return smm_apply_impl(op, x, x_dtype, ldx, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream); });
-}
-
-int smm_apply_sb(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream) {
-  return guarded([&] { return smm_apply_sb_impl(op, x, x_dtype, ldx, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream); });
-}
-
-int smm_apply_host(smm_operator_t op, const void* x_host, int x_dtype, int64_t ldx, void* y_host, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows) {
-  return guarded([&] { return smm_apply_host_impl(op, x_host, x_dtype, ldx, y_host, y_dtype, ldy, n_batch, remap_area_min, flags, chunk_rows); });
-}
-
 }  // extern "C"
 
 namespace {
-// smm_cf_decode_t -> CfCall.  Returns SMM_OK with *use = null when the call is a plain float one (cf == NULL).
-int make_cf(const smm_cf_decode_t* cf, int x_dtype, unsigned flags, CfCall* out, const CfCall** use) {
-  *use = nullptr;
-  if (!is_packed_dtype(x_dtype)) {
-    if (cf && is_float_dtype(x_dtype))
+// smm_cf_decode_t -> the call's decode rule.  A plain float call (cf == NULL) is left as it is.
+int make_cf(const smm_cf_decode_t* cf, CallDesc& c) {
+  if (!c.packed_x()) {
+    if (cf && is_float_dtype(c.x_dtype))
       return fail(SMM_ERR_INVALID, "a decode rule was given with a float field: pass cf = NULL, or the raw 16-bit field");
     return SMM_OK;   // float: the plain entry; anything else: refused by the dtype check
   }
@@ -2107,117 +2042,127 @@ int make_cf(const smm_cf_decode_t* cf, int x_dtype, unsigned flags, CfCall* out,
   if (cf->decode_dtype != SMM_F32 && cf->decode_dtype != SMM_F64)
     return fail(SMM_ERR_INVALID, "cf->decode_dtype must be SMM_F32 or SMM_F64");
   if (cf->n_fill < 0 || cf->n_fill > 2) return fail(SMM_ERR_INVALID, "cf->n_fill must be 0, 1 or 2");
-  const int32_t lo = x_dtype == SMM_I16 ? -32768 : 0, hi = x_dtype == SMM_I16 ? 32767 : 65535;
+  const int32_t lo = c.x_dtype == SMM_I16 ? -32768 : 0, hi = c.x_dtype == SMM_I16 ? 32767 : 65535;
   for (int i = 0; i < cf->n_fill; ++i)
     if (cf->fill[i] < lo || cf->fill[i] > hi)
       return fail(SMM_ERR_INVALID, "cf->fill[" + std::to_string(i) + "] is not representable in the raw type");
-  if (cf->n_fill > 0 && (flags & SMM_APPLY_NO_FILL))
+  if (cf->n_fill > 0 && (c.flags & SMM_APPLY_NO_FILL))
     return fail(SMM_ERR_INVALID, "SMM_APPLY_NO_FILL with fill values: the decode makes NaN");
   const int32_t none = 0x7fffffff;   // no 16-bit element compares equal
-  out->p.scale = cf->scale;
-  out->p.offset = cf->offset;
-  out->p.fill0 = cf->n_fill > 0 ? cf->fill[0] : none;
-  out->p.fill1 = cf->n_fill > 1 ? cf->fill[1] : out->p.fill0;
-  out->decode_dtype = cf->decode_dtype;
-  *use = out;
+  c.cf.scale = cf->scale;
+  c.cf.offset = cf->offset;
+  c.cf.fill0 = cf->n_fill > 0 ? cf->fill[0] : none;
+  c.cf.fill1 = cf->n_fill > 1 ? cf->fill[1] : c.cf.fill0;
+  c.decode_dtype = cf->decode_dtype;
+  c.has_cf = true;
   return SMM_OK;
 }
-}  // namespace
 
-extern "C" {
-
-int smm_apply_cf(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf) {
-  return guarded([&] {
-    CfCall c;
-    const CfCall* use;
-    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
-    return smm_apply_impl(op, x, x_dtype, ldx, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream, use);
-  });
-}
-
-int smm_apply_sb_cf(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf) {
-  return guarded([&] {
-    CfCall c;
-    const CfCall* use;
-    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
-    return smm_apply_sb_impl(op, x, x_dtype, ldx, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream, use);
-  });
-}
-
-int smm_apply_host_cf(smm_operator_t op, const void* x_host, int x_dtype, int64_t ldx, void* y_host, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows, const smm_cf_decode_t* cf) {
-  return guarded([&] {
-    CfCall c;
-    const CfCall* use;
-    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
-    return smm_apply_host_impl(op, x_host, x_dtype, ldx, y_host, y_dtype, ldy, n_batch, remap_area_min, flags, chunk_rows, use);
-  });
-}
-
-}  // extern "C"
-
-namespace {
-// smm_cf_encode_t -> CfOutParams, with every refusal of the _pk entries that needs no device.  Returns SMM_OK with
-// *use = null when the call is the _cf entry unchanged (enc == NULL).
-int make_enc(const smm_cf_encode_t* enc, int y_dtype, unsigned flags, CfOutParams* out, const CfOutParams** use) {
-  *use = nullptr;
+// smm_cf_encode_t -> the call's encode rule, with every refusal of the _pk entries that needs no device.  enc == NULL
+// with a float y_dtype: the _cf entry unchanged.
+int make_enc(const smm_cf_encode_t* enc, CallDesc& c) {
   if (!enc) {
-    if (is_packed_dtype(y_dtype))
+    if (is_packed_dtype(c.y_dtype))
       return fail(SMM_ERR_INVALID, "SMM_I16 / SMM_U16 results need an encode rule (enc is NULL)");
     return SMM_OK;
   }
-  if (!is_packed_dtype(y_dtype))
+  if (!is_packed_dtype(c.y_dtype))
     return fail(SMM_ERR_INVALID, "an encode rule was given with a float y_dtype: pass enc = NULL, or y_dtype SMM_I16 / SMM_U16");
   if (enc->reserved != 0) return fail(SMM_ERR_INVALID, "enc->reserved must be 0");
   if (!std::isfinite(enc->scale) || enc->scale == 0.0) return fail(SMM_ERR_INVALID, "enc->scale must be finite and non-zero");
   if (!std::isfinite(enc->offset)) return fail(SMM_ERR_INVALID, "enc->offset must be finite");
-  const int32_t lo = y_dtype == SMM_I16 ? -32768 : 0, hi = y_dtype == SMM_I16 ? 32767 : 65535;
+  const int32_t lo = c.y_dtype == SMM_I16 ? -32768 : 0, hi = c.y_dtype == SMM_I16 ? 32767 : 65535;
   if (enc->fill < lo || enc->fill > hi) return fail(SMM_ERR_INVALID, "enc->fill is not representable in the raw type");
-  if (flags & SMM_APPLY_KERNEL_TILE)
+  if (c.flags & SMM_APPLY_KERNEL_TILE)
     return fail(SMM_ERR_UNSUPPORTED, "the LDS tile kernel is not built for packed results (SMM_I16 / SMM_U16)");
-  out->scale = enc->scale;
-  out->offset = enc->offset;
-  out->fill = enc->fill;
-  out->reserved = 0;
-  *use = out;
+  c.enc = CfOutParams{enc->scale, enc->offset, enc->fill, 0};
+  c.has_enc = true;
   return SMM_OK;
+}
+
+// The preamble of every apply entry: the plain ones take no rule (16-bit dtypes are then refused by the dtype check),
+// the _cf ones a decode rule, the _pk ones both -- the encode rule is validated first, before the handle is looked at.
+enum class Entry { plain, cf, pk };
+template <typename F>
+int apply_entry(Entry kind, int x_dtype, int y_dtype, double remap_area_min, unsigned flags, const smm_cf_decode_t* cf,
+                const smm_cf_encode_t* enc, F&& body) {
+  return guarded([&] {
+    CallDesc c{x_dtype, y_dtype, flags, remap_area_min};
+    if (kind == Entry::pk)
+      if (int rc = make_enc(enc, c)) return rc;
+    if (kind != Entry::plain)
+      if (int rc = make_cf(cf, c)) return rc;
+    return body(c);
+  });
 }
 }  // namespace
 
 extern "C" {
 
-int smm_apply_pk(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
-  return guarded([&] {
-    CfOutParams e;
-    const CfOutParams* use_e;
-    if (int rc = make_enc(enc, y_dtype, flags, &e, &use_e)) return rc;
-    CfCall c;
-    const CfCall* use;
-    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
-    return smm_apply_impl(op, x, x_dtype, ldx, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream, use, use_e);
+int smm_apply(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy,
+              int64_t n_batch, double remap_area_min, unsigned flags, void* stream) {
+  return apply_entry(Entry::plain, x_dtype, y_dtype, remap_area_min, flags, nullptr, nullptr, [&](const CallDesc& c) {
+    return smm_apply_impl(op, x, ldx, y, ldy, n_batch, stream, c);
   });
 }
 
-int smm_apply_sb_pk(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
-  return guarded([&] {
-    CfOutParams e;
-    const CfOutParams* use_e;
-    if (int rc = make_enc(enc, y_dtype, flags, &e, &use_e)) return rc;
-    CfCall c;
-    const CfCall* use;
-    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
-    return smm_apply_sb_impl(op, x, x_dtype, ldx, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream, use, use_e);
+int smm_apply_cf(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy,
+                 int64_t n_batch, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf) {
+  return apply_entry(Entry::cf, x_dtype, y_dtype, remap_area_min, flags, cf, nullptr, [&](const CallDesc& c) {
+    return smm_apply_impl(op, x, ldx, y, ldy, n_batch, stream, c);
   });
 }
 
-int smm_apply_host_pk(smm_operator_t op, const void* x_host, int x_dtype, int64_t ldx, void* y_host, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
-  return guarded([&] {
-    CfOutParams e;
-    const CfOutParams* use_e;
-    if (int rc = make_enc(enc, y_dtype, flags, &e, &use_e)) return rc;
-    CfCall c;
-    const CfCall* use;
-    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
-    return smm_apply_host_impl(op, x_host, x_dtype, ldx, y_host, y_dtype, ldy, n_batch, remap_area_min, flags, chunk_rows, use, use_e);
+int smm_apply_pk(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy,
+                 int64_t n_batch, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf,
+                 const smm_cf_encode_t* enc) {
+  return apply_entry(Entry::pk, x_dtype, y_dtype, remap_area_min, flags, cf, enc, [&](const CallDesc& c) {
+    return smm_apply_impl(op, x, ldx, y, ldy, n_batch, stream, c);
+  });
+}
+
+int smm_apply_sb(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy,
+                 int64_t n_batch, double remap_area_min, unsigned flags, void* stream) {
+  return apply_entry(Entry::plain, x_dtype, y_dtype, remap_area_min, flags, nullptr, nullptr, [&](const CallDesc& c) {
+    return smm_apply_sb_impl(op, x, ldx, y, ldy, n_batch, stream, c);
+  });
+}
+
+int smm_apply_sb_cf(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy,
+                    int64_t n_batch, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf) {
+  return apply_entry(Entry::cf, x_dtype, y_dtype, remap_area_min, flags, cf, nullptr, [&](const CallDesc& c) {
+    return smm_apply_sb_impl(op, x, ldx, y, ldy, n_batch, stream, c);
+  });
+}
+
+int smm_apply_sb_pk(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int y_dtype, int64_t ldy,
+                    int64_t n_batch, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf,
+                    const smm_cf_encode_t* enc) {
+  return apply_entry(Entry::pk, x_dtype, y_dtype, remap_area_min, flags, cf, enc, [&](const CallDesc& c) {
+    return smm_apply_sb_impl(op, x, ldx, y, ldy, n_batch, stream, c);
+  });
+}
+
+int smm_apply_host(smm_operator_t op, const void* x_host, int x_dtype, int64_t ldx, void* y_host, int y_dtype,
+                   int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows) {
+  return apply_entry(Entry::plain, x_dtype, y_dtype, remap_area_min, flags, nullptr, nullptr, [&](const CallDesc& c) {
+    return smm_apply_host_impl(op, x_host, ldx, y_host, ldy, n_batch, chunk_rows, c);
+  });
+}
+
+int smm_apply_host_cf(smm_operator_t op, const void* x_host, int x_dtype, int64_t ldx, void* y_host, int y_dtype,
+                      int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows,
+                      const smm_cf_decode_t* cf) {
+  return apply_entry(Entry::cf, x_dtype, y_dtype, remap_area_min, flags, cf, nullptr, [&](const CallDesc& c) {
+    return smm_apply_host_impl(op, x_host, ldx, y_host, ldy, n_batch, chunk_rows, c);
+  });
+}
+
+int smm_apply_host_pk(smm_operator_t op, const void* x_host, int x_dtype, int64_t ldx, void* y_host, int y_dtype,
+                      int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows,
+                      const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
+  return apply_entry(Entry::pk, x_dtype, y_dtype, remap_area_min, flags, cf, enc, [&](const CallDesc& c) {
+    return smm_apply_host_impl(op, x_host, ldx, y_host, ldy, n_batch, chunk_rows, c);
   });
 }
 
@@ -2229,91 +2174,116 @@ int smm_group_prepare(smm_group_t g, int64_t n_lev, const int32_t* level_index, 
   return guarded([&] { return smm_group_prepare_impl(g, n_lev, level_index, masked_levels); });
 }
 
-int smm_group_apply(smm_group_t g, const void* x, int x_dtype, int64_t xs_outer, int64_t xs_lev, int64_t xs_inner, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev, int64_t ys_inner, int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream) {
-  return guarded([&] { return smm_group_apply_impl(g, x, x_dtype, xs_outer, xs_lev, xs_inner, y, y_dtype, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner, level_index, masked_levels, remap_area_min, flags, stream); });
-}
-
 int smm_group_prepare_sb(smm_group_t g) {
   return guarded([&] { return smm_group_prepare_sb_impl(g); });
 }
 
-int smm_group_apply_sb(smm_group_t g, const void* x, int x_dtype, int64_t xs_lev, int64_t ldx, void* y, int y_dtype, int64_t ys_lev, int64_t ys_batch, int64_t n_batch, int64_t n_lev, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream) {
-  return guarded([&] { return smm_group_apply_sb_impl(g, x, x_dtype, xs_lev, ldx, y, y_dtype, ys_lev, ys_batch, n_batch, n_lev, level_index, masked_levels, remap_area_min, flags, stream); });
-}
-
-int smm_group_apply_host(smm_group_t g, const void* x_host, int x_dtype, void* y_host, int y_dtype, int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, int64_t chunk_outer) {
-  return guarded([&] { return smm_group_apply_host_impl(g, x_host, x_dtype, y_host, y_dtype, n_outer, n_lev, n_inner, transpose, level_index, masked_levels, remap_area_min, flags, chunk_outer); });
-}
-
-// The three group entries for CF-packed fields (see smm_apply_cf): one decode rule for every level
-int smm_group_apply_cf(smm_group_t g, const void* x, int x_dtype, int64_t xs_outer, int64_t xs_lev, int64_t xs_inner, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev, int64_t ys_inner, int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf) {
-  return guarded([&] {
-    CfCall c;
-    const CfCall* use;
-    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
-    return smm_group_apply_impl(g, x, x_dtype, xs_outer, xs_lev, xs_inner, y, y_dtype, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner, level_index, masked_levels, remap_area_min, flags, stream, use);
+// the group entries: one decode rule / encode rule for every level
+int smm_group_apply(smm_group_t g, const void* x, int x_dtype, int64_t xs_outer, int64_t xs_lev, int64_t xs_inner,
+                    void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev, int64_t ys_inner, int64_t n_outer,
+                    int64_t n_lev, int64_t n_inner, const int32_t* level_index, const uint8_t* masked_levels,
+                    double remap_area_min, unsigned flags, void* stream) {
+  return apply_entry(Entry::plain, x_dtype, y_dtype, remap_area_min, flags, nullptr, nullptr, [&](const CallDesc& c) {
+    return smm_group_apply_impl(g, x, xs_outer, xs_lev, xs_inner, y, ys_outer, ys_lev, ys_inner, n_outer, n_lev,
+                                n_inner, level_index, masked_levels, stream, c);
   });
 }
 
-int smm_group_apply_sb_cf(smm_group_t g, const void* x, int x_dtype, int64_t xs_lev, int64_t ldx, void* y, int y_dtype, int64_t ys_lev, int64_t ys_batch, int64_t n_batch, int64_t n_lev, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf) {
-  return guarded([&] {
-    CfCall c;
-    const CfCall* use;
-    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
-    return smm_group_apply_sb_impl(g, x, x_dtype, xs_lev, ldx, y, y_dtype, ys_lev, ys_batch, n_batch, n_lev, level_index, masked_levels, remap_area_min, flags, stream, use);
+int smm_group_apply_cf(smm_group_t g, const void* x, int x_dtype, int64_t xs_outer, int64_t xs_lev, int64_t xs_inner,
+                       void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev, int64_t ys_inner, int64_t n_outer,
+                       int64_t n_lev, int64_t n_inner, const int32_t* level_index, const uint8_t* masked_levels,
+                       double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf) {
+  return apply_entry(Entry::cf, x_dtype, y_dtype, remap_area_min, flags, cf, nullptr, [&](const CallDesc& c) {
+    return smm_group_apply_impl(g, x, xs_outer, xs_lev, xs_inner, y, ys_outer, ys_lev, ys_inner, n_outer, n_lev,
+                                n_inner, level_index, masked_levels, stream, c);
   });
 }
 
-int smm_group_apply_host_cf(smm_group_t g, const void* x_host, int x_dtype, void* y_host, int y_dtype, int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, int64_t chunk_outer, const smm_cf_decode_t* cf) {
-  return guarded([&] {
-    CfCall c;
-    const CfCall* use;
-    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
-    return smm_group_apply_host_impl(g, x_host, x_dtype, y_host, y_dtype, n_outer, n_lev, n_inner, transpose, level_index, masked_levels, remap_area_min, flags, chunk_outer, use);
+int smm_group_apply_pk(smm_group_t g, const void* x, int x_dtype, int64_t xs_outer, int64_t xs_lev, int64_t xs_inner,
+                       void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev, int64_t ys_inner, int64_t n_outer,
+                       int64_t n_lev, int64_t n_inner, const int32_t* level_index, const uint8_t* masked_levels,
+                       double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf,
+                       const smm_cf_encode_t* enc) {
+  return apply_entry(Entry::pk, x_dtype, y_dtype, remap_area_min, flags, cf, enc, [&](const CallDesc& c) {
+    return smm_group_apply_impl(g, x, xs_outer, xs_lev, xs_inner, y, ys_outer, ys_lev, ys_inner, n_outer, n_lev,
+                                n_inner, level_index, masked_levels, stream, c);
   });
 }
 
-// the three _cf group entries with a CF-packed result: the rule is validated (make_enc) before the group is looked at
-int smm_group_apply_pk(smm_group_t g, const void* x, int x_dtype, int64_t xs_outer, int64_t xs_lev, int64_t xs_inner, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev, int64_t ys_inner, int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
-  return guarded([&] {
-    CfOutParams e;
-    const CfOutParams* use_e = nullptr;
-    if (int rc = make_enc(enc, y_dtype, flags, &e, &use_e)) return rc;
-    CfCall c;
-    const CfCall* use = nullptr;
-    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
-    return smm_group_apply_impl(g, x, x_dtype, xs_outer, xs_lev, xs_inner, y, y_dtype, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner, level_index, masked_levels, remap_area_min, flags, stream, use, use_e);
-  });
-}
-int smm_group_apply_sb_pk(smm_group_t g, const void* x, int x_dtype, int64_t xs_lev, int64_t ldx, void* y, int y_dtype, int64_t ys_lev, int64_t ys_batch, int64_t n_batch, int64_t n_lev, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
-  return guarded([&] {
-    CfOutParams e;
-    const CfOutParams* use_e = nullptr;
-    if (int rc = make_enc(enc, y_dtype, flags, &e, &use_e)) return rc;
-    CfCall c;
-    const CfCall* use = nullptr;
-    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
-    return smm_group_apply_sb_impl(g, x, x_dtype, xs_lev, ldx, y, y_dtype, ys_lev, ys_batch, n_batch, n_lev, level_index, masked_levels, remap_area_min, flags, stream, use, use_e);
-  });
-}
-int smm_group_apply_host_pk(smm_group_t g, const void* x_host, int x_dtype, void* y_host, int y_dtype, int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose, const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min, unsigned flags, int64_t chunk_outer, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
-  return guarded([&] {
-    CfOutParams e;
-    const CfOutParams* use_e = nullptr;
-    if (int rc = make_enc(enc, y_dtype, flags, &e, &use_e)) return rc;
-    CfCall c;
-    const CfCall* use = nullptr;
-    if (int rc = make_cf(cf, x_dtype, flags, &c, &use)) return rc;
-    return smm_group_apply_host_impl(g, x_host, x_dtype, y_host, y_dtype, n_outer, n_lev, n_inner, transpose, level_index, masked_levels, remap_area_min, flags, chunk_outer, use, use_e);
+int smm_group_apply_sb(smm_group_t g, const void* x, int x_dtype, int64_t xs_lev, int64_t ldx, void* y, int y_dtype,
+                       int64_t ys_lev, int64_t ys_batch, int64_t n_batch, int64_t n_lev, const int32_t* level_index,
+                       const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream) {
+  return apply_entry(Entry::plain, x_dtype, y_dtype, remap_area_min, flags, nullptr, nullptr, [&](const CallDesc& c) {
+    return smm_group_apply_sb_impl(g, x, xs_lev, ldx, y, ys_lev, ys_batch, n_batch, n_lev, level_index,
+                                   masked_levels, stream, c);
   });
 }
 
-int smm_operator_launch_info(smm_operator_t op, int x_dtype, int64_t n_batch, unsigned flags, int* kernel, int* j_per_block, int* rows_per_step, int* rows_per_block, int64_t* n_blocks, int64_t* lds_bytes, int* big_operator) {
-  return guarded([&] { return smm_operator_launch_info_impl(op, x_dtype, n_batch, flags, kernel, j_per_block, rows_per_step, rows_per_block, n_blocks, lds_bytes, big_operator); });
+int smm_group_apply_sb_cf(smm_group_t g, const void* x, int x_dtype, int64_t xs_lev, int64_t ldx, void* y,
+                          int y_dtype, int64_t ys_lev, int64_t ys_batch, int64_t n_batch, int64_t n_lev,
+                          const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min,
+                          unsigned flags, void* stream, const smm_cf_decode_t* cf) {
+  return apply_entry(Entry::cf, x_dtype, y_dtype, remap_area_min, flags, cf, nullptr, [&](const CallDesc& c) {
+    return smm_group_apply_sb_impl(g, x, xs_lev, ldx, y, ys_lev, ys_batch, n_batch, n_lev, level_index,
+                                   masked_levels, stream, c);
+  });
 }
 
-int smm_group_launch_info(smm_group_t g, int x_dtype, int64_t n_outer, int64_t n_lev, int64_t n_inner, unsigned flags, int* kernel, int* j_per_block, int* rows_per_step, int* rows_per_block, int64_t* n_blocks, int64_t* lds_bytes, int* big_operator) {
-  return guarded([&] { return smm_group_launch_info_impl(g, x_dtype, n_outer, n_lev, n_inner, flags, kernel, j_per_block, rows_per_step, rows_per_block, n_blocks, lds_bytes, big_operator); });
+int smm_group_apply_sb_pk(smm_group_t g, const void* x, int x_dtype, int64_t xs_lev, int64_t ldx, void* y,
+                          int y_dtype, int64_t ys_lev, int64_t ys_batch, int64_t n_batch, int64_t n_lev,
+                          const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min,
+                          unsigned flags, void* stream, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
+  return apply_entry(Entry::pk, x_dtype, y_dtype, remap_area_min, flags, cf, enc, [&](const CallDesc& c) {
+    return smm_group_apply_sb_impl(g, x, xs_lev, ldx, y, ys_lev, ys_batch, n_batch, n_lev, level_index,
+                                   masked_levels, stream, c);
+  });
+}
+
+int smm_group_apply_host(smm_group_t g, const void* x_host, int x_dtype, void* y_host, int y_dtype, int64_t n_outer,
+                         int64_t n_lev, int64_t n_inner, int transpose, const int32_t* level_index,
+                         const uint8_t* masked_levels, double remap_area_min, unsigned flags, int64_t chunk_outer) {
+  return apply_entry(Entry::plain, x_dtype, y_dtype, remap_area_min, flags, nullptr, nullptr, [&](const CallDesc& c) {
+    return smm_group_apply_host_impl(g, x_host, y_host, n_outer, n_lev, n_inner, transpose, level_index,
+                                     masked_levels, chunk_outer, c);
+  });
+}
+
+int smm_group_apply_host_cf(smm_group_t g, const void* x_host, int x_dtype, void* y_host, int y_dtype,
+                            int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose,
+                            const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min,
+                            unsigned flags, int64_t chunk_outer, const smm_cf_decode_t* cf) {
+  return apply_entry(Entry::cf, x_dtype, y_dtype, remap_area_min, flags, cf, nullptr, [&](const CallDesc& c) {
+    return smm_group_apply_host_impl(g, x_host, y_host, n_outer, n_lev, n_inner, transpose, level_index,
+                                     masked_levels, chunk_outer, c);
+  });
+}
+
+int smm_group_apply_host_pk(smm_group_t g, const void* x_host, int x_dtype, void* y_host, int y_dtype,
+                            int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose,
+                            const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min,
+                            unsigned flags, int64_t chunk_outer, const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
+  return apply_entry(Entry::pk, x_dtype, y_dtype, remap_area_min, flags, cf, enc, [&](const CallDesc& c) {
+    return smm_group_apply_host_impl(g, x_host, y_host, n_outer, n_lev, n_inner, transpose, level_index,
+                                     masked_levels, chunk_outer, c);
+  });
+}
+
+int smm_operator_launch_info(smm_operator_t op, int x_dtype, int64_t n_batch, unsigned flags, int* kernel,
+                             int* j_per_block, int* rows_per_step, int* rows_per_block, int64_t* n_blocks,
+                             int64_t* lds_bytes, int* big_operator) {
+  return guarded([&] {
+    return smm_operator_launch_info_impl(op, x_dtype, n_batch, flags, kernel, j_per_block, rows_per_step, rows_per_block,
+                                         n_blocks, lds_bytes, big_operator);
+  });
+}
+
+int smm_group_launch_info(smm_group_t g, int x_dtype, int64_t n_outer, int64_t n_lev, int64_t n_inner, unsigned flags,
+                          int* kernel, int* j_per_block, int* rows_per_step, int* rows_per_block, int64_t* n_blocks,
+                          int64_t* lds_bytes, int* big_operator) {
+  return guarded([&] {
+    return smm_group_launch_info_impl(g, x_dtype, n_outer, n_lev, n_inner, flags, kernel, j_per_block, rows_per_step,
+                                      rows_per_block, n_blocks, lds_bytes, big_operator);
+  });
 }
 
 int smm_operator_plan_info(smm_operator_t op, int* kernel_kind, int64_t* lds_bytes, int64_t* staged_src_elems) {

@@ -1,7 +1,7 @@
-// Kernel launch templates, one explicit instantiation per (X dtype, Y dtype, SKIPNA) triple
-// (smm_launch_inst.hip is compiled eight times, in parallel, four more for CF-packed X and eight for CF-packed Y): the tile kernel alone has several
-// hundred instantiations, which one translation unit would compile for minutes.  SKIPNA = true
-// builds the SMM_APPLY_SKIPNA variants (smm_kernels.hpp, RowSum) in objects of their own.
+// Kernel launch templates, one explicit instantiation per built (X type, Y type, SKIPNA) triple -- the list is SMM_BUILT
+// in smm_built.hpp.  smm_launch_inst.hip is compiled once per variant of the Makefile's INST list, twenty objects side by
+// side: the tile kernel alone has several hundred instantiations, which one translation unit would compile for minutes.
+// SKIPNA = true builds the SMM_APPLY_SKIPNA variants (smm_kernels.hpp, RowSum) in objects of their own.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,7 +1,8 @@
-// One (X dtype, Y dtype, SKIPNA) triple of the kernel launch templates; built with -DSMM_XT=... -DSMM_YT=...
-// and -DSMM_SKIPNA=1 for the SMM_APPLY_SKIPNA variants.  With -DSMM_PACKED=1: the int16 / uint16 packed-X launchers
-// that decode to SMM_XT instead.  With -DSMM_PACKED_Y=1: the launchers that store CF-packed int16 / uint16 results
-// (PackedY), for float X of type SMM_XT or, with -DSMM_PACKED=1 too, packed X of the same raw type decoded to SMM_XT
+// One variant of the kernel launch templates (the Makefile's INST list; all of them together: SMM_BUILT, smm_built.hpp).
+// -DSMM_XT=... -DSMM_YT=...: one float (X, Y) pair, all four launchers.  With -DSMM_PACKED=1: the int16 / uint16 packed-X
+// launchers that decode to SMM_XT instead.  With -DSMM_PACKED_Y=1: the launchers that store CF-packed int16 / uint16
+// results (PackedY), for float X of type SMM_XT or, with -DSMM_PACKED=1 too, packed X of the same raw type decoded to
+// SMM_XT.  -DSMM_SKIPNA=1: the SMM_APPLY_SKIPNA variants of the same.
 #include "smm_launch.hpp"
 
 #ifndef SMM_SKIPNA

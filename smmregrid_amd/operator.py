@@ -19,6 +19,29 @@ def _cptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _ptr(a):
+    return _cptr(a) if isinstance(a, np.ndarray) else ctypes.c_void_p(a.ptr)
+
+
+def _apply_call(entry, handle, x, mid, y, rest, y_res, cf, cf_out, y_name="Y"):
+    """One apply through `entry`: the plain entry, `entry`_cf with a CFDecode (cf), `entry`_pk with a CFEncode (cf_out).
+    The arguments are handle, X, its dtype code, *mid, Y, its dtype code, *rest, then the rule structs the entry takes.
+    y_res: result_dtype(out_dtype, cf_out) -- what the result array of a cf_out call must be.  Returns y."""
+    rules = []
+    if cf_out is not None:
+        if y.dtype != y_res[0]:
+            raise TypeError(f"{y_name} must be {y_res[0]} for this cf_out, got {y.dtype}")
+        entry, y_code = entry + "_pk", y_res[1]
+        rules = [None if cf is None else ctypes.byref(cf._struct(x.dtype)), ctypes.byref(cf_out._struct())]
+    else:
+        y_code = dtype_code(y.dtype)
+    x_code = field_dtype_code(x.dtype, cf)
+    if cf is not None and cf_out is None:
+        entry, rules = entry + "_cf", [ctypes.byref(cf._struct(x.dtype))]
+    _lib.call(entry, handle, _ptr(x), x_code, *mid, _ptr(y), y_code, *rest, *rules)
+    return y
+
+
 def _launch_info(fn, handle, dt, sizes, flags):
     ints = [ctypes.c_int(0) for _ in range(5)]
     nb, lds = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -192,33 +215,14 @@ class SparseOperator:
         if x.ndim != 2 or x.shape[1] < self.n_src:
             raise ValueError(f"X must be (B, >= {self.n_src}), got {x.shape}")
         n_batch = x.shape[0]
-        y_dtype, y_code = result_dtype(out_dtype, cf_out)
+        y_res = result_dtype(out_dtype, cf_out)
         if y is None:
-            y = DeviceArray((n_batch, self.n_dst), y_dtype)
+            y = DeviceArray((n_batch, self.n_dst), y_res[0])
         elif y.shape != (n_batch, self.n_dst):
             raise ValueError(f"Y must be ({n_batch}, {self.n_dst}), got {y.shape}")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
-        if cf_out is not None:
-            if y.dtype != y_dtype:
-                raise TypeError(f"Y must be {y_dtype} for this cf_out, got {y.dtype}")
-            st = None if cf is None else cf._struct(x.dtype)
-            enc = cf_out._struct()
-            _lib.call("smm_apply_pk", self.handle, ctypes.c_void_p(x.ptr), field_dtype_code(x.dtype, cf),
-                      x.shape[1], ctypes.c_void_p(y.ptr), y_code, self.n_dst, n_batch,
-                      float(remap_area_min), fl, _stream_handle(stream), None if st is None else ctypes.byref(st),
-                      ctypes.byref(enc))
-            return y
-        if cf is not None:
-            code = field_dtype_code(x.dtype, cf)
-            st = cf._struct(x.dtype)
-            _lib.call("smm_apply_cf", self.handle, ctypes.c_void_p(x.ptr), code,
-                      x.shape[1], ctypes.c_void_p(y.ptr), dtype_code(y.dtype), self.n_dst, n_batch,
-                      float(remap_area_min), fl, _stream_handle(stream), ctypes.byref(st))
-            return y
-        _lib.call("smm_apply", self.handle, ctypes.c_void_p(x.ptr), dtype_code(x.dtype),
-                  x.shape[1], ctypes.c_void_p(y.ptr), dtype_code(y.dtype), self.n_dst, n_batch,
-                  float(remap_area_min), fl, _stream_handle(stream))
-        return y
+        return _apply_call("smm_apply", self.handle, x, (x.shape[1],), y,
+                           (self.n_dst, n_batch, float(remap_area_min), fl, _stream_handle(stream)), y_res, cf, cf_out)
 
     def used_sources(self):
         """Ascending 0-based indices of the source cells that carry a link (length n_used_src):
@@ -255,35 +259,18 @@ class SparseOperator:
         if not 0 <= n_batch <= ldx:
             raise ValueError(f"n_batch must be within the pitch {ldx}")
         y_shape = (self.n_dst, n_batch) if keep_batch_fastest else (n_batch, self.n_dst)
-        y_dtype, y_code = result_dtype(out_dtype, cf_out)
+        y_res = result_dtype(out_dtype, cf_out)
         if y is None:
-            y = DeviceArray(y_shape, y_dtype, layout="sb" if keep_batch_fastest else "bs")
+            y = DeviceArray(y_shape, y_res[0], layout="sb" if keep_batch_fastest else "bs")
         elif y.shape != y_shape:
             raise ValueError(f"Y must be {y_shape}, got {y.shape}")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
         fl |= _lib.APPLY_SB_PACKED if packed else 0
         if keep_batch_fastest:
             fl |= _lib.APPLY_SB_Y_SB
-        if cf_out is not None:
-            if y.dtype != y_dtype:
-                raise TypeError(f"Y must be {y_dtype} for this cf_out, got {y.dtype}")
-            st = None if cf is None else cf._struct(x.dtype)
-            enc = cf_out._struct()
-            _lib.call("smm_apply_sb_pk", self.handle, ctypes.c_void_p(x.ptr), field_dtype_code(x.dtype, cf), max(ldx, 1),
-                      ctypes.c_void_p(y.ptr), y_code, max(y_shape[1], 1), n_batch, float(remap_area_min),
-                      fl, _stream_handle(stream), None if st is None else ctypes.byref(st), ctypes.byref(enc))
-            return y
-        if cf is not None:
-            code = field_dtype_code(x.dtype, cf)
-            st = cf._struct(x.dtype)
-            _lib.call("smm_apply_sb_cf", self.handle, ctypes.c_void_p(x.ptr), code, max(ldx, 1),
-                      ctypes.c_void_p(y.ptr), dtype_code(y.dtype), max(y_shape[1], 1), n_batch, float(remap_area_min),
-                      fl, _stream_handle(stream), ctypes.byref(st))
-            return y
-        _lib.call("smm_apply_sb", self.handle, ctypes.c_void_p(x.ptr), dtype_code(x.dtype), max(ldx, 1),
-                  ctypes.c_void_p(y.ptr), dtype_code(y.dtype), max(y_shape[1], 1), n_batch, float(remap_area_min), fl,
-                  _stream_handle(stream))
-        return y
+        return _apply_call("smm_apply_sb", self.handle, x, (max(ldx, 1),), y,
+                           (max(y_shape[1], 1), n_batch, float(remap_area_min), fl, _stream_handle(stream)), y_res, cf,
+                           cf_out)
 
     def apply_host(self, x, out=None, masked=False, remap_area_min=0.0, out_dtype=np.float64,
                    flags=0, chunk_rows=0, skipna=False, cf=None, cf_out=None):
@@ -304,32 +291,15 @@ class SparseOperator:
         if x.strides[1] != x.itemsize or x.strides[0] % x.itemsize or x.strides[0] < self.n_src * x.itemsize:
             x = np.ascontiguousarray(x)
         n_batch = x.shape[0]
-        y_dtype, y_code = result_dtype(out_dtype, cf_out)
+        y_res = result_dtype(out_dtype, cf_out)
         if out is None:
-            out = result_cache.empty((n_batch, self.n_dst), y_dtype)      # page-locked and recycled when large
+            out = result_cache.empty((n_batch, self.n_dst), y_res[0])      # page-locked and recycled when large
         if out.shape != (n_batch, self.n_dst) or not out.flags.c_contiguous:
             raise ValueError(f"out must be a C-contiguous ({n_batch}, {self.n_dst}) array")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
         ldx = x.strides[0] // x.itemsize if n_batch > 1 else max(self.n_src, 1)
-        if cf_out is not None:
-            if out.dtype != y_dtype:
-                raise TypeError(f"out must be {y_dtype} for this cf_out, got {out.dtype}")
-            st = None if cf is None else cf._struct(x.dtype)
-            enc = cf_out._struct()
-            _lib.call("smm_apply_host_pk", self.handle, _cptr(x), field_dtype_code(x.dtype, cf), ldx,
-                      _cptr(out), y_code, self.n_dst, n_batch, float(remap_area_min), fl,
-                      int(chunk_rows), None if st is None else ctypes.byref(st), ctypes.byref(enc))
-            return out
-        if cf is not None:
-            st = cf._struct(x.dtype)
-            _lib.call("smm_apply_host_cf", self.handle, _cptr(x), field_dtype_code(x.dtype, cf), ldx,
-                      _cptr(out), dtype_code(out.dtype), self.n_dst, n_batch, float(remap_area_min), fl,
-                      int(chunk_rows), ctypes.byref(st))
-            return out
-        _lib.call("smm_apply_host", self.handle, _cptr(x), dtype_code(x.dtype), ldx,
-                  _cptr(out), dtype_code(out.dtype), self.n_dst, n_batch, float(remap_area_min), fl,
-                  int(chunk_rows))
-        return out
+        return _apply_call("smm_apply_host", self.handle, x, (ldx,), out,
+                           (self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows)), y_res, cf, cf_out, "out")
 
     def close(self):
         if getattr(self, "handle", None):
@@ -420,37 +390,16 @@ class OperatorGroup:
         else:
             shape = (n_lev, n_outer, n_inner, D)
             ys = (n_inner * D, n_outer * n_inner * D, D)
-        y_dtype, y_code = result_dtype(out_dtype, cf_out)
+        y_res = result_dtype(out_dtype, cf_out)
         if y is None:
-            y = DeviceArray(shape, y_dtype)
+            y = DeviceArray(shape, y_res[0])
         elif y.shape != shape:
             raise ValueError(f"Y must be {shape}, got {y.shape}")
         xs = (n_lev * n_inner * S, n_inner * S, S)
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
-        if cf_out is not None:
-            if y.dtype != y_dtype:
-                raise TypeError(f"Y must be {y_dtype} for this cf_out, got {y.dtype}")
-            st = None if cf is None else cf._struct(x.dtype)
-            enc = cf_out._struct()
-            _lib.call("smm_group_apply_pk", self.handle, ctypes.c_void_p(x.ptr), field_dtype_code(x.dtype, cf),
-                      xs[0], xs[1], xs[2], ctypes.c_void_p(y.ptr), y_code,
-                      ys[0], ys[1], ys[2], n_outer, n_lev, n_inner, _cptr(lev), _cptr(ml),
-                      float(remap_area_min), fl, _stream_handle(stream), None if st is None else ctypes.byref(st),
-                      ctypes.byref(enc))
-            return y
-        if cf is not None:
-            code = field_dtype_code(x.dtype, cf)
-            st = cf._struct(x.dtype)
-            _lib.call("smm_group_apply_cf", self.handle, ctypes.c_void_p(x.ptr), code,
-                      xs[0], xs[1], xs[2], ctypes.c_void_p(y.ptr), dtype_code(y.dtype),
-                      ys[0], ys[1], ys[2], n_outer, n_lev, n_inner, _cptr(lev), _cptr(ml),
-                      float(remap_area_min), fl, _stream_handle(stream), ctypes.byref(st))
-            return y
-        _lib.call("smm_group_apply", self.handle, ctypes.c_void_p(x.ptr), dtype_code(x.dtype),
-                  xs[0], xs[1], xs[2], ctypes.c_void_p(y.ptr), dtype_code(y.dtype),
-                  ys[0], ys[1], ys[2], n_outer, n_lev, n_inner, _cptr(lev), _cptr(ml),
-                  float(remap_area_min), fl, _stream_handle(stream))
-        return y
+        return _apply_call("smm_group_apply", self.handle, x, xs, y,
+                           (*ys, n_outer, n_lev, n_inner, _cptr(lev), _cptr(ml), float(remap_area_min), fl,
+                            _stream_handle(stream)), y_res, cf, cf_out)
 
     def apply_sb(self, x, level_index, masked_levels=None, y=None, masked=False, remap_area_min=0.0,
                  transpose=True, out_dtype=np.float64, flags=0, stream=None, keep_batch_fastest=False, n_batch=None,
@@ -477,34 +426,16 @@ class OperatorGroup:
         else:
             shape = (B, n_lev, D) if transpose else (n_lev, B, D)
             ys_lev, ys_b = (D, n_lev * D) if transpose else (B * D, D)
-        y_dtype, y_code = result_dtype(out_dtype, cf_out)
+        y_res = result_dtype(out_dtype, cf_out)
         if y is None:
-            y = DeviceArray(shape, y_dtype, layout="sb" if keep_batch_fastest else "bs")
+            y = DeviceArray(shape, y_res[0], layout="sb" if keep_batch_fastest else "bs")
         elif y.shape != shape:
             raise ValueError(f"Y must be {shape}, got {y.shape}")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
         fl |= _lib.APPLY_SB_Y_SB if keep_batch_fastest else 0
-        if cf_out is not None:
-            if y.dtype != y_dtype:
-                raise TypeError(f"Y must be {y_dtype} for this cf_out, got {y.dtype}")
-            st = None if cf is None else cf._struct(x.dtype)
-            enc = cf_out._struct()
-            _lib.call("smm_group_apply_sb_pk", self.handle, ctypes.c_void_p(x.ptr), field_dtype_code(x.dtype, cf),
-                      S * max(ldx, 1), max(ldx, 1), ctypes.c_void_p(y.ptr), y_code, ys_lev, ys_b, B, n_lev,
-                      _cptr(lev), _cptr(ml), float(remap_area_min), fl, _stream_handle(stream),
-                      None if st is None else ctypes.byref(st), ctypes.byref(enc))
-            return y
-        if cf is not None:
-            code = field_dtype_code(x.dtype, cf)
-            st = cf._struct(x.dtype)
-            _lib.call("smm_group_apply_sb_cf", self.handle, ctypes.c_void_p(x.ptr), code,
-                      S * max(ldx, 1), max(ldx, 1), ctypes.c_void_p(y.ptr), dtype_code(y.dtype), ys_lev, ys_b, B, n_lev,
-                      _cptr(lev), _cptr(ml), float(remap_area_min), fl, _stream_handle(stream), ctypes.byref(st))
-            return y
-        _lib.call("smm_group_apply_sb", self.handle, ctypes.c_void_p(x.ptr), dtype_code(x.dtype), S * max(ldx, 1),
-                  max(ldx, 1), ctypes.c_void_p(y.ptr), dtype_code(y.dtype), ys_lev, ys_b, B, n_lev, _cptr(lev),
-                  _cptr(ml), float(remap_area_min), fl, _stream_handle(stream))
-        return y
+        return _apply_call("smm_group_apply_sb", self.handle, x, (S * max(ldx, 1), max(ldx, 1)), y,
+                           (ys_lev, ys_b, B, n_lev, _cptr(lev), _cptr(ml), float(remap_area_min), fl,
+                            _stream_handle(stream)), y_res, cf, cf_out)
 
     def apply_host(self, x, level_index, masked_levels=None, masked=False, remap_area_min=0.0,
                    transpose=True, out_dtype=np.float64, flags=0, chunk_outer=0, skipna=False, cf=None, cf_out=None):
@@ -525,27 +456,12 @@ class OperatorGroup:
         n_outer, n_lev, n_inner, _ = x.shape
         lev, ml = self._level_args(level_index, masked_levels, n_lev)
         shape = (n_outer, n_inner, n_lev, self.n_dst) if transpose else (n_lev, n_outer, n_inner, self.n_dst)
-        y_dtype, y_code = result_dtype(out_dtype, cf_out)
-        out = result_cache.empty(shape, y_dtype)
+        y_res = result_dtype(out_dtype, cf_out)
+        out = result_cache.empty(shape, y_res[0])
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
-        if cf_out is not None:
-            st = None if cf is None else cf._struct(x.dtype)
-            enc = cf_out._struct()
-            _lib.call("smm_group_apply_host_pk", self.handle, _cptr(x), field_dtype_code(x.dtype, cf), _cptr(out),
-                      y_code, n_outer, n_lev, n_inner, int(bool(transpose)), _cptr(lev),
-                      _cptr(ml), float(remap_area_min), fl, int(chunk_outer),
-                      None if st is None else ctypes.byref(st), ctypes.byref(enc))
-            return out
-        if cf is not None:
-            st = cf._struct(x.dtype)
-            _lib.call("smm_group_apply_host_cf", self.handle, _cptr(x), field_dtype_code(x.dtype, cf), _cptr(out),
-                      dtype_code(out.dtype), n_outer, n_lev, n_inner, int(bool(transpose)), _cptr(lev),
-                      _cptr(ml), float(remap_area_min), fl, int(chunk_outer), ctypes.byref(st))
-            return out
-        _lib.call("smm_group_apply_host", self.handle, _cptr(x), dtype_code(x.dtype), _cptr(out),
-                  dtype_code(out.dtype), n_outer, n_lev, n_inner, int(bool(transpose)), _cptr(lev),
-                  _cptr(ml), float(remap_area_min), fl, int(chunk_outer))
-        return out
+        return _apply_call("smm_group_apply_host", self.handle, x, (), out,
+                           (n_outer, n_lev, n_inner, int(bool(transpose)), _cptr(lev), _cptr(ml), float(remap_area_min),
+                            fl, int(chunk_outer)), y_res, cf, cf_out, "out")
 
     def close(self):
         if getattr(self, "handle", None):
