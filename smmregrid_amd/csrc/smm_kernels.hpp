@@ -361,6 +361,38 @@ struct RowWalker {
   }
 };
 
+// Largest value of v over the wave's lanes, wave-uniform (a scalar).
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
+  return __builtin_amdgcn_readfirstlane(v);
+}
+
+// Hardware block b runs on XCD b % 8.  Runs of `run` consecutive logical blocks (neighbours in space, sharing halo
+// lines) go to one XCD, and the runs are dealt round-robin so that every XCD sees the same mix of light and heavy
+// levels.  Blocks past the last full round keep their id (bijective for any grid size).  run <= 0: dispatcher order.
+// I: the kernel's index type.  n_blocks by reference: it is read only when the remap is on.
+template <typename I, typename N>
+__device__ __forceinline__ I xcd_remap_block(I bid, int run, const N& n_blocks) {
+  if (run > 0) {
+    const I C = (I)run, round = 8 * C;
+    if (bid < (n_blocks / round) * round) {
+      const I xcd = bid & 7, slot = bid >> 3;
+      bid = (slot / C) * round + xcd * C + (slot % C);
+    }
+  }
+  return bid;
+}
+
+// One result to cell d of the Y row at yrow, non-temporal or plain.
+template <bool NT, typename YT>
+__device__ __forceinline__ void store_y(YT* __restrict__ yrow, int64_t d, YT v) {
+  if constexpr (NT)
+    __builtin_nontemporal_store(v, yrow + d);
+  else
+    yrow[d] = v;
+}
+
 // ------------------------------------------------------------------ kernel A
 // SELL-64, one destination row per lane, BT batch rows register-blocked so the
 // col/val stream is read once per BT outputs and BT independent gathers are in
@@ -469,6 +501,41 @@ typedef u32x4 u32x4_u __attribute__((aligned(4)));  // 16-B piece that may start
 // drift apart and overlap each other's HBM waits.
 constexpr int tile_waves(int maxk) { return (maxk > 0 && maxk <= 16) ? kWavesPerBlock : 1; }
 
+// The stages the walks of kernel B share.  The link registers (lc2) are passed by reference to force-inlined
+// templates and indexed by unrolled loop counters only: a pointer to them, or an index computed at run time, would
+// send the arrays to scratch.  The link loop itself ("gather four staged values, then add four") stays written out
+// in each walk, and the dead-row test in the prologue: lifted into helpers that take the running RowSum or the
+// argument structs by reference they compiled to different code -- commuted adds, up to 36 instructions and 8 SGPR
+// spills more per kernel, one scalar instruction more in kernel A -- while every helper below compiles to the
+// parent's instructions in the DMA walk and to the same or fewer in the register-staged walks.
+
+// LDS byte offset of link k of a row whose links live in registers: two 16-bit offsets per register (tiles are
+// <= 64 KiB).  A slot past the row's registers (k >= KREG) reads link 0; its value is never added.
+template <int KREG>
+__device__ __forceinline__ uint32_t lds_offset(const uint32_t (&lc2)[KREG / 2], int k) {
+  return (k & 1) ? (lc2[(k < KREG ? k : 0) / 2] >> 16) : (lc2[(k < KREG ? k : 0) / 2] & 0xFFFFu);
+}
+
+// The row-end piece was loaded shift_amt elements early (its 16-B load clamped into the row): move the valid tail
+// to the front, zeros behind it.
+template <typename XT>
+__device__ __forceinline__ u32x4 realign_piece(u32x4 piece, int shift_amt) {
+  constexpr int N = 16 / (int)sizeof(XT);
+  XT tmp[N];
+  __builtin_memcpy(tmp, &piece, 16);
+  XT out[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    XT val = (XT)0;
+#pragma unroll
+    for (int q = 0; q < N; ++q)
+      if (q == e + shift_amt) val = tmp[q];
+    out[e] = val;
+  }
+  __builtin_memcpy(&piece, out, 16);
+  return piece;
+}
+
 //
 // R > 1 (small tiles only): R batch rows are staged, consumed and stored per barrier pair, each in
 // its own LDS region.  A workgroup whose tile needs one or two pieces per thread is bound by the
@@ -507,6 +574,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
   // rows gather few values from comparatively many staged ones (config 4: 4 links, 8 staged f32 per
   // lane and step) and test what they gather.
   constexpr bool kFixAtStage = !DMA && !SKIPNA && (MAXK == 0 || MAXK > 16);   // LDS-DMA bypasses the registers: test at the gather
+  constexpr bool kNtY = (NT & 2) != 0;   // non-temporal Y stores
   static_assert(!SKIPNA || (!SPLIT && MAXK > 0), "SKIPNA: links in registers, one lane per row");
   static_assert(!SPLIT || (WPB == 1 && R == 1 && MAXK > 0), "split rows: single-wave, single-row steps");
   static_assert(R == 1 || (MAXK > 0 && MAXK <= 16), "multi-row steps exist for the 4-wave shape only");
@@ -514,18 +582,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
-  int64_t bid = blockIdx.x;
-  if (a.xcd_remap > 0) {
-    // Hardware block b runs on XCD b % 8.  Runs of C consecutive logical blocks (neighbours in
-    // space, sharing halo lines) go to one XCD, and the runs are dealt round-robin so that every
-    // XCD sees the same mix of light and heavy levels.  Blocks past the last full round keep
-    // their id (bijective for any grid size).
-    const int64_t C = a.xcd_remap, round = 8 * C;
-    if (bid < (a.n_blocks / round) * round) {
-      const int64_t xcd = bid & 7, slot = bid >> 3;
-      bid = (slot / C) * round + xcd * C + (slot % C);
-    }
-  }
+  int64_t bid = xcd_remap_block<int64_t>(blockIdx.x, a.xcd_remap, a.n_blocks);
   const int64_t db = bid % a.n_dblocks;
   bid /= a.n_dblocks;
   const int64_t jt = bid % a.n_jtiles;
@@ -561,10 +618,8 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
     nslots = (int)((L.slice_off[slice + 1] - soff) >> 6);
     len = (in_blk && d < a.n_dst) ? L.rowlen[d] : 0;
     if (SPLIT) {
-      int longest = len;   // longest row of the block -> links per lane group (wave-uniform)
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) longest = max(longest, __shfl_xor(longest, off));
-      const int per_grp = (__builtin_amdgcn_readfirstlane(longest) + n_grp - 1) >> a.sub_shift;
+      // longest row of the block -> links per lane group (wave-uniform)
+      const int per_grp = (wave_max(len) + n_grp - 1) >> a.sub_shift;
       first = grp * per_grp;
       len = min(max(len - first, 0), per_grp);
     }
@@ -596,11 +651,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
       w[k + 1] = 0.0;
     }
   }
-  // wave-uniform trip count: longest row of this wave
-  int wmax = len;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) wmax = max(wmax, __shfl_xor(wmax, off));
-  wmax = __builtin_amdgcn_readfirstlane(wmax);
+  int wmax = wave_max(len);   // wave-uniform trip count: longest row of this wave
 
   bool dead = false;
   bool dead_m = false;    // SKIPNA: the static mask alone; the area test moves into skipna_epilogue
@@ -681,10 +732,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
       bool ddead = dead;
       if (SPLIT) {
         dlen = dlive ? L.rowlen[dd] : 0;
-        dmax = dlen;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) dmax = max(dmax, __shfl_xor(dmax, off));
-        dmax = __builtin_amdgcn_readfirstlane(dmax);
+        dmax = wave_max(dlen);
         ddead = false;
         if (dlive) {
           const bool use_mask = a.masked && (a.lev_masked ? a.lev_masked[di] != 0 : true);
@@ -730,11 +778,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
       const YT out = (YT)epilogue(0.0, dead);
       RowWalker yw0(j_begin, l, a.n_inner, a.ys_o, a.ys_l, a.ys_i);
       for (int64_t j = j_begin; j < j_end; ++j) {
-        YT* __restrict__ yrow = (YT*)a.y + yw0.off;
-        if (NT & 2)
-          __builtin_nontemporal_store(out, yrow + dy);
-        else
-          yrow[dy] = out;
+        store_y<kNtY>((YT*)a.y + yw0.off, dy, out);
         yw0.next();
       }
     }
@@ -768,13 +812,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
     auto flush_pending = [&]() {
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        if (r < n_pend) {
-          YT* __restrict__ yrow = (YT*)a.y + pend_off[r];
-          if (NT & 2)
-            __builtin_nontemporal_store(pend_out[r], yrow + dy);
-          else
-            yrow[dy] = pend_out[r];
-        }
+        if (r < n_pend) store_y<kNtY>((YT*)a.y + pend_off[r], dy, pend_out[r]);
       }
     };
     int64_t j_issue = j_begin;
@@ -791,7 +829,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
     issue_group(0);
     int group = 0;
     for (int64_t jb = j_begin; jb < j_end; jb += R) {
-      asm volatile("" : "+s"(np_w), "+s"(wmax));
+      asm volatile("" : "+s"(np_w), "+s"(wmax));   // see the register-staged walk
       if (MAXK > 16) {
 #pragma unroll
         for (int q = 0; q < KREG / 2; ++q) asm volatile("" : "+v"(lc2[q]));
@@ -813,13 +851,13 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
 #else
 #pragma unroll
             for (int k0 = 0; k0 < KREG; k0 += 4) {
-              if (k0 < wmax) {
+              if (k0 < wmax) {  // wave-uniform guard: whole groups of slots are skipped, indices stay static
                 double xv[4];
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
                   const int k = k0 + kk;
-                  const uint32_t li = (k & 1) ? (lc2[(k < KREG ? k : 0) / 2] >> 16) : (lc2[(k < KREG ? k : 0) / 2] & 0xFFFFu);
-                  xv[kk] = load_link<SKIPNA>((const XT*)(lds_b + li), fill);
+                  const uint32_t li = lds_offset<KREG>(lc2, k);
+                  xv[kk] = load_link<SKIPNA>((const XT*)(lds_b + li), fill);  // unconditional: offset 0 for unused slots
                 }
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
@@ -841,9 +879,15 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
     }
     if (row_live) flush_pending();
   } else if constexpr (R == 1) {
+    // Register-staged walk, one batch row per barrier pair: stage (load_row -> store_tile), barrier, prefetch of
+    // the next row, link loop (links in registers, SPLIT or streamed), store, barrier.
     const XT* lds_x = (const XT*)smem;
     u32x4 v[NP];
     auto load_row = [&](int64_t xoff) {
+#ifdef SMM_EXP_SKIP_STAGE   // timing-only ablation (tools/exp/build_exp.sh): no HBM -> register loads, the tile holds zeros
+#pragma unroll
+      for (int k = 0; k < NP; ++k) v[k] = u32x4{0, 0, 0, 0};
+#else
       const XT* __restrict__ xrow = (const XT*)a.x + xoff;
 #pragma unroll
       for (int k = 0; k < NP; ++k) {
@@ -851,6 +895,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
         const u32x4_u* src = (const u32x4_u*)(xrow + poff[k]);
         v[k] = (NT & 1) ? __builtin_nontemporal_load(src) : *src;
       }
+#endif
     };
     // the row-end piece (clamped load, see above) exists in at most one block per row: keep its
     // element shuffle out of the common path with a wave-uniform branch
@@ -879,20 +924,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
       for (int k = 0; k < NP; ++k) {
         if (k < np_w) {
           u32x4 piece = v[k];
-          if ((shifted >> k) & 1u) {  // last piece of the row: move the valid tail to the front
-            XT tmp[kElemsPerPiece];
-            __builtin_memcpy(tmp, &piece, 16);
-            XT out[kElemsPerPiece];
-#pragma unroll
-            for (int e = 0; e < kElemsPerPiece; ++e) {
-              XT val = (XT)0;
-#pragma unroll
-              for (int q = 0; q < kElemsPerPiece; ++q)
-                if (q == e + shift_amt) val = tmp[q];
-              out[e] = val;
-            }
-            __builtin_memcpy(&piece, out, 16);
-          }
+          if ((shifted >> k) & 1u) piece = realign_piece<XT>(piece, shift_amt);
           *(u32x4*)(smem + (size_t)(tid + k * T) * 16) = (kFixAtStage && fill) ? fix_piece<XT>(piece) : piece;
         }
       }
@@ -900,25 +932,13 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
 
     RowWalker xw(j_begin, l, a.n_inner, a.xs_o, a.xs_l, a.xs_i);   // row being prefetched
     RowWalker yw(j_begin, l, a.n_inner, a.ys_o, a.ys_l, a.ys_i);   // row being written
-#ifndef SMM_EXP_SKIP_STAGE
     load_row(xw.off);
-#else
-#pragma unroll
-    for (int k = 0; k < NP; ++k) v[k] = u32x4{0, 0, 0, 0};
-#endif
     // Single-wave workgroups issue the Y store of row j after the LDS writes of row j+1: the wait
     // for the prefetched pieces (in-order memory counter) then never includes the latest store's
     // acknowledgement (cfg3 -6 %).  Four-wave workgroups store at once (deferring cost cfg4s 13 %).
     constexpr bool kDeferStore = (WPB == 1);
     YT pend_out = (YT)0;
     int64_t pend_off = 0;
-    auto flush_pending = [&]() {
-      YT* __restrict__ yrow = (YT*)a.y + pend_off;
-      if (NT & 2)
-        __builtin_nontemporal_store(pend_out, yrow + dy);
-      else
-        yrow[dy] = pend_out;
-    };
     for (int64_t j = j_begin; j < j_end; ++j) {
       // The counts are loop invariant, and hipcc would keep one 64-bit predicate per piece / link
       // group (k < np_w, k0 < wmax) live across the walk -- dozens of SGPR pairs, spilled to VGPR
@@ -933,52 +953,46 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
         for (int q = 0; q < KREG / 2; ++q) asm volatile("" : "+v"(lc2[q]));
       }
       store_tile();
-      if (kDeferStore && row_live && j > j_begin) flush_pending();
+      if (kDeferStore && row_live && j > j_begin) store_y<kNtY>((YT*)a.y + pend_off, dy, pend_out);
       __syncthreads();
-#ifndef SMM_EXP_SKIP_STAGE
       if (j + 1 < j_end) {
         xw.next();
         load_row(xw.off);
       }
-#endif
       if (slice_live) {
         double acc = 0.0;          // SPLIT and streamed links (plain only)
         RowSum<XT, SKIPNA> rs;     // links in registers
+#ifdef SMM_EXP_SKIP_COMPUTE   // timing-only ablation: one LDS read instead of the link loop
+        rs.num = acc = (double)lds_x[lane];
+#else
         if constexpr (SPLIT) {
           // lane groups take their turn: group g continues the sums group g-1 handed over
           const int rows_blk = 64 >> a.sub_shift;
           for (int g = 0; g < n_grp; ++g) {
-            double t = acc;
+            RowSum<XT, false> t;
+            t.num = acc;
 #pragma unroll
             for (int k0 = 0; k0 < KREG; k0 += 4) {
-              if (k0 < wmax) {
+              if (k0 < wmax) {  // wave-uniform guard: whole groups of slots are skipped, indices stay static
                 double xv[4];
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
                   const int k = k0 + kk;
-                  const uint32_t li = (k & 1) ? (lc2[(k < KREG ? k : 0) / 2] >> 16)
-                                              : (lc2[(k < KREG ? k : 0) / 2] & 0xFFFFu);
-                  xv[kk] = load_fixed((const XT*)((const char*)lds_x + li), fill && !kFixAtStage);
+                  const uint32_t li = lds_offset<KREG>(lc2, k);
+                  xv[kk] = load_link<false>((const XT*)((const char*)lds_x + li), fill && !kFixAtStage);  // unconditional: offset 0 for unused slots
                 }
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
                   const int k = k0 + kk;
-                  if (k < KREG) {
-                    const double p = w[k] * xv[kk];
-                    t = t + p;
-                  }
+                  if (k < KREG) t.add(w[k], xv[kk]);
                 }
               }
             }
-            acc = (grp == g && len > 0) ? t : acc;
+            acc = (grp == g && len > 0) ? t.num : acc;
             const double handed = __shfl(acc, (lane - rows_blk) & 63);
             acc = (grp == g + 1) ? handed : acc;
           }
-#ifdef SMM_EXP_SKIP_COMPUTE
-        } else if (true) {   // timing-only ablation: one LDS read instead of the link loop
-          rs.num = acc = (double)lds_x[lane];
-#endif
-        } else if (MAXK > 0) {
+        } else if constexpr (MAXK > 0) {
 #pragma unroll
           for (int k0 = 0; k0 < KREG; k0 += 4) {
             if (k0 < wmax) {  // wave-uniform guard: whole groups of slots are skipped, indices stay static
@@ -986,8 +1000,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
 #pragma unroll
               for (int kk = 0; kk < 4; ++kk) {
                 const int k = k0 + kk;
-                const uint32_t li = (k & 1) ? (lc2[(k < KREG ? k : 0) / 2] >> 16)
-                                            : (lc2[(k < KREG ? k : 0) / 2] & 0xFFFFu);
+                const uint32_t li = lds_offset<KREG>(lc2, k);
                 xv[kk] = load_link<SKIPNA>((const XT*)((const char*)lds_x + li), fill && !kFixAtStage);  // unconditional: offset 0 for unused slots
               }
 #pragma unroll
@@ -1018,19 +1031,26 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
             }
           }
         }
+#endif
         if (MAXK > 0 && !SPLIT) rs.keep_if(len > 0);   // a row without links never looks at the tile
         else rs.num = acc;
         pend_out = (YT)finish(rs);
         pend_off = yw.off;
-        if (!kDeferStore && row_live) flush_pending();
+        if (!kDeferStore && row_live) store_y<kNtY>((YT*)a.y + pend_off, dy, pend_out);
       }
       yw.next();
       __syncthreads();
     }
-    if (kDeferStore && row_live) flush_pending();
+    if (kDeferStore && row_live) store_y<kNtY>((YT*)a.y + pend_off, dy, pend_out);
   } else {
+    // Register-staged walk of the small 4-wave tiles, R batch rows per barrier pair: row r of a step is staged
+    // from v[r] into the LDS region at r * tile_bytes.  Links in registers, stores at once (see the R == 1 walk).
     u32x4 v[R][NP];
     auto load_row = [&](int r, int64_t xoff) {
+#ifdef SMM_EXP_SKIP_STAGE   // timing-only ablation: see the R == 1 walk
+#pragma unroll
+      for (int k = 0; k < NP; ++k) v[r][k] = u32x4{0, 0, 0, 0};
+#else
       const XT* __restrict__ xrow = (const XT*)a.x + xoff;
 #pragma unroll
       for (int k = 0; k < NP; ++k) {
@@ -1038,11 +1058,10 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
         const u32x4_u* src = (const u32x4_u*)(xrow + poff[k]);
         v[r][k] = (NT & 1) ? __builtin_nontemporal_load(src) : *src;
       }
+#endif
     };
-    // the row-end piece (clamped load, see above) exists in at most one block per row: keep its
-    // element shuffle out of the common path with a wave-uniform branch
-    const bool any_shifted = __builtin_amdgcn_readfirstlane((int)__any(shifted != 0)) != 0;
-    const int tile_bytes = R > 1 ? a.tile_bytes : 0;  // LDS region of batch row r of a step: r * tile_bytes
+    const bool any_shifted = __builtin_amdgcn_readfirstlane((int)__any(shifted != 0)) != 0;   // see the R == 1 walk
+    const int tile_bytes = a.tile_bytes;  // LDS region of batch row r of a step: r * tile_bytes
     auto store_tile = [&](int r) {   // unconditional natural-slot writes, fill on the way in (see R == 1)
       char* region = smem + r * tile_bytes;
       if (!any_shifted) {
@@ -1065,20 +1084,7 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
       for (int k = 0; k < NP; ++k) {
         if (k < np_w) {
           u32x4 piece = v[r][k];
-          if ((shifted >> k) & 1u) {  // last piece of the row: move the valid tail to the front
-            XT tmp[kElemsPerPiece];
-            __builtin_memcpy(tmp, &piece, 16);
-            XT out[kElemsPerPiece];
-#pragma unroll
-            for (int e = 0; e < kElemsPerPiece; ++e) {
-              XT val = (XT)0;
-#pragma unroll
-              for (int q = 0; q < kElemsPerPiece; ++q)
-                if (q == e + shift_amt) val = tmp[q];
-              out[e] = val;
-            }
-            __builtin_memcpy(&piece, out, 16);
-          }
+          if ((shifted >> k) & 1u) piece = realign_piece<XT>(piece, shift_amt);
           *(u32x4*)(region + (size_t)(tid + k * T) * 16) = (kFixAtStage && fill) ? fix_piece<XT>(piece) : piece;
         }
       }
@@ -1095,85 +1101,46 @@ __global__ __launch_bounds__(tile_waves(MAXK) * 64, 2) void smm_apply_tile2_kern
         if (jb + r + 1 < j_end) xw.next();
       }
     };
-#ifndef SMM_EXP_SKIP_STAGE
     load_step(j_begin);
-#else
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-      for (int k = 0; k < NP; ++k) v[r][k] = u32x4{0, 0, 0, 0};
-#endif
-    // Single-wave workgroups issue the Y store of row j after the LDS writes of row j+1: the wait
-    // for the prefetched pieces (in-order memory counter) then never includes the latest store's
-    // acknowledgement (cfg3 -6 %).  Four-wave workgroups store at once (deferring cost cfg4s 13 %).
-    constexpr bool kDeferStore = (WPB == 1 && R == 1);
-    YT pend_out = (YT)0;
-    int64_t pend_off = 0;
-    auto flush_pending = [&]() {
-      YT* __restrict__ yrow = (YT*)a.y + pend_off;
-      if (NT & 2)
-        __builtin_nontemporal_store(pend_out, yrow + dy);
-      else
-        yrow[dy] = pend_out;
-    };
     for (int64_t jb = j_begin; jb < j_end; jb += R) {
       asm volatile("" : "+s"(np_w), "+s"(wmax));   // see the R == 1 walk
 #pragma unroll
       for (int r = 0; r < R; ++r) store_tile(r);
-      if (kDeferStore && row_live && jb > j_begin) flush_pending();
       __syncthreads();
-#ifndef SMM_EXP_SKIP_STAGE
       if (jb + R < j_end) load_step(jb + R);
-#endif
       if (slice_live) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const XT* lds_r = (const XT*)(smem + r * tile_bytes);
           RowSum<XT, SKIPNA> acc;
-#ifdef SMM_EXP_SKIP_COMPUTE
-          if (true) {   // timing-only ablation: one LDS read instead of the link loop
-            acc.num = (double)lds_r[lane];
-          } else
-#endif
-          if (MAXK > 0) {
+#ifdef SMM_EXP_SKIP_COMPUTE   // timing-only ablation: one LDS read instead of the link loop
+          acc.num = (double)lds_r[lane];
+#else
 #pragma unroll
-            for (int k0 = 0; k0 < KREG; k0 += 4) {
-              if (k0 < wmax) {  // wave-uniform guard: whole groups of slots are skipped, indices stay static
-                double xv[4];
+          for (int k0 = 0; k0 < KREG; k0 += 4) {
+            if (k0 < wmax) {  // wave-uniform guard: whole groups of slots are skipped, indices stay static
+              double xv[4];
 #pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                  const int k = k0 + kk;
-                  const uint32_t li = (k & 1) ? (lc2[(k < KREG ? k : 0) / 2] >> 16)
-                                              : (lc2[(k < KREG ? k : 0) / 2] & 0xFFFFu);
-                  xv[kk] = load_link<SKIPNA>((const XT*)((const char*)lds_r + li), fill && !kFixAtStage);  // unconditional: offset 0 for unused slots
-                }
+              for (int kk = 0; kk < 4; ++kk) {
+                const int k = k0 + kk;
+                const uint32_t li = lds_offset<KREG>(lc2, k);
+                xv[kk] = load_link<SKIPNA>((const XT*)((const char*)lds_r + li), fill && !kFixAtStage);  // unconditional: offset 0 for unused slots
+              }
 #pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                  const int k = k0 + kk;
-                  if (k < KREG) acc.add(w[k], xv[kk]);
-                }
+              for (int kk = 0; kk < 4; ++kk) {
+                const int k = k0 + kk;
+                if (k < KREG) acc.add(w[k], xv[kk]);
               }
             }
-          } else {
-#pragma unroll 4
-            for (int k = 0; k < wmax; ++k) {
-              const int kc = min(k, nslots - 1);
-              const bool on = k < len;
-              const int32_t li = cp[(int64_t)kc * 64];
-              const double xv = load_link<SKIPNA>(lds_r + (on ? li : 0), fill && !kFixAtStage);
-              acc.add_if(on, vp[(int64_t)kc * 64], xv);
-            }
           }
-          if (MAXK > 0) acc.keep_if(len > 0);   // a row without links never looks at the tile
-          pend_out = (YT)finish(acc);
-          pend_off = yw.off;
-          if (!kDeferStore && row_live && jb + r < j_end) flush_pending();
+#endif
+          acc.keep_if(len > 0);   // a row without links never looks at the tile
+          if (row_live && jb + r < j_end) store_y<kNtY>((YT*)a.y + yw.off, dy, (YT)finish(acc));
           if (jb + r + 1 < j_end) yw.next();
         }
       }
       __syncthreads();
     }
-    if (kDeferStore && row_live) flush_pending();
   }
 }
 
@@ -1241,14 +1208,8 @@ __device__ __forceinline__ void sb_tile_body(const M& m, const SbTile& a, uint32
   typedef xvec xvec_u __attribute__((aligned(sizeof(XR))));   // element-aligned (any ldx / base)
 
   const int lane = threadIdx.x;
-  // grids stay below 2^31 blocks: 32-bit index arithmetic
-  if (a.xcd_remap > 0) {   // runs of consecutive tiles (neighbours in space) share one XCD's L2
-    const uint32_t C = (uint32_t)a.xcd_remap, round = 8 * C;
-    if (bid < (a.n_blocks / round) * round) {
-      const uint32_t xcd = bid & 7, slot = bid >> 3;
-      bid = (slot / C) * round + xcd * C + (slot % C);
-    }
-  }
+  // grids stay below 2^31 blocks: 32-bit index arithmetic; runs of consecutive tiles (neighbours in space) share one XCD's L2
+  bid = xcd_remap_block<uint32_t>(bid, a.xcd_remap, a.n_blocks);
   int64_t dt, bt;
   if (a.b_fastest > 0) {
     // strips of `b_fastest` destination tiles: inside a strip the destination tile runs fastest, then the

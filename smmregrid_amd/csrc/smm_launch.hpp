@@ -187,40 +187,29 @@ int launch_tile(const ApplyArgs& a, int64_t n_lev, int tile_which, int64_t max_c
   const size_t lds = cfg.lds;
 
   const bool dma = cfg.dma;   // LDS-DMA staging into a ring of two tile slots (tile_launch_cfg)
-  auto go_dma = [&](auto k_tag, auto np_tag, auto nt_tag) -> int {
-    constexpr int MAXK = decltype(k_tag)::value;
-    if constexpr (MAXK > 0) {
-      constexpr int NPV = decltype(np_tag)::value;
-      constexpr int NTV = decltype(nt_tag)::value;
-      const dim3 grid((unsigned)total), block(tile_waves(MAXK) * 64);
-      if constexpr (MAXK <= 16 && NPV <= 4) {
-        if (rows == 4) {
-          hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NPV, NTV, 4, false, true, SKIPNA>), grid, block, lds, s, args, fill);
-          SMM_LAUNCH_HIP(hipGetLastError());
-          return SMM_OK;
-        }
-        if (rows == 2) {
-          hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NPV, NTV, 2, false, true, SKIPNA>), grid, block, lds, s, args, fill);
-          SMM_LAUNCH_HIP(hipGetLastError());
-          return SMM_OK;
-        }
-      }
-      hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NPV, NTV, 1, false, true, SKIPNA>), grid, block, lds, s, args, fill);
-      SMM_LAUNCH_HIP(hipGetLastError());
-      return SMM_OK;
-    } else {
-      return smm::fail_msg(SMM_ERR_UNSUPPORTED, "LDS-DMA staging needs the links in registers");
-    }
-  };
-  auto go3 = [&](auto k_tag, auto np_tag, auto nt_tag, auto r_tag) -> int {
+  // one tile form: links in registers (MAXK, 0 = streamed), pieces per thread, NT bits, rows per step, SPLIT, DMA
+  auto go3 = [&](auto k_tag, auto np_tag, auto nt_tag, auto r_tag, auto split_tag, auto dma_tag) -> int {
     constexpr int MAXK = decltype(k_tag)::value;
     constexpr int NP = decltype(np_tag)::value;
     constexpr int NT = decltype(nt_tag)::value;
     constexpr int R = decltype(r_tag)::value;
-    hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NP, NT, R, false, false, SKIPNA>), dim3((unsigned)total),
-                       dim3(tile_waves(MAXK) * 64), lds, s, args, fill);
+    hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, NP, NT, R, decltype(split_tag)::value, decltype(dma_tag)::value, SKIPNA>),
+                       dim3((unsigned)total), dim3(tile_waves(MAXK) * 64), lds, s, args, fill);
     SMM_LAUNCH_HIP(hipGetLastError());
     return SMM_OK;
+  };
+  auto go_dma = [&](auto k_tag, auto np_tag, auto nt_tag) -> int {
+    constexpr int MAXK = decltype(k_tag)::value;
+    if constexpr (MAXK > 0) {
+      auto go_r = [&](auto r_tag) -> int { return go3(k_tag, np_tag, nt_tag, r_tag, std::false_type(), std::true_type()); };
+      if constexpr (MAXK <= 16 && decltype(np_tag)::value <= 4) {
+        if (rows == 4) return go_r(std::integral_constant<int, 4>());
+        if (rows == 2) return go_r(std::integral_constant<int, 2>());
+      }
+      return go_r(std::integral_constant<int, 1>());
+    } else {
+      return smm::fail_msg(SMM_ERR_UNSUPPORTED, "LDS-DMA staging needs the links in registers");
+    }
   };
   // Part-of-a-slice blocks: the idle lanes take over parts of the rows (SPLIT kernels, tile_split).
   const int n_grp = 1 << args.sub_shift;
@@ -232,21 +221,17 @@ int launch_tile(const ApplyArgs& a, int64_t n_lev, int tile_which, int64_t max_c
     constexpr int MAXK = decltype(k_tag)::value;
     if (dma) return go_dma(k_tag, np_tag, nt_tag);
     if constexpr (!SKIPNA && (MAXK == 32 || MAXK == 48)) {
-      if (split) {
-        hipLaunchKernelGGL((smm_apply_tile2_kernel<XT, YT, MAXK, decltype(np_tag)::value, decltype(nt_tag)::value, 1, true>),
-                           dim3((unsigned)total), dim3(64), lds, s, args, fill);
-        SMM_LAUNCH_HIP(hipGetLastError());
-        return SMM_OK;
-      }
+      if (split) return go3(k_tag, np_tag, nt_tag, std::integral_constant<int, 1>(), std::true_type(), std::false_type());
     }
+    auto go_r = [&](auto np, auto r_tag) -> int { return go3(k_tag, np, nt_tag, r_tag, std::false_type(), std::false_type()); };
     if constexpr (MAXK > 0 && MAXK <= 16) {
-      if (rows == 4) return go3(k_tag, std::integral_constant<int, 1>(), nt_tag, std::integral_constant<int, 4>());
-      if (rows == 2) return go3(k_tag, std::integral_constant<int, 2>(), nt_tag, std::integral_constant<int, 2>());
+      if (rows == 4) return go_r(std::integral_constant<int, 1>(), std::integral_constant<int, 4>());
+      if (rows == 2) return go_r(std::integral_constant<int, 2>(), std::integral_constant<int, 2>());
     }
     if constexpr (SKIPNA && MAXK == 0)
       return smm::fail_msg(SMM_ERR_INTERNAL, "SMM_APPLY_SKIPNA reached the streamed-link tile form");   // refused above
     else
-      return go3(k_tag, np_tag, nt_tag, std::integral_constant<int, 1>());
+      return go_r(np_tag, std::integral_constant<int, 1>());
   };
   auto with_k = [&](auto fn) -> int {  // plan shape 0 <-> 4 waves (rows of <= 16 links), shape 1.. <-> 1 wave
     if (!tile_which) {
@@ -284,29 +269,37 @@ int launch_tile(const ApplyArgs& a, int64_t n_lev, int tile_which, int64_t max_c
 
 // Batch-fastest layout (kernel C).  TD destination rows per tile: 16 doubles = one 128-B line of Y
 // per batch row; f32 output takes 32 rows for the same line; a packed 2-byte Y: sb_tile_rows.
-template <typename XT, typename YT, bool SKIPNA, int TD>
-int launch_sb_td(const SbArgs& a, bool fill, unsigned flags, hipStream_t s);
-
-template <typename XT, typename YT, bool SKIPNA>
-int launch_sb(const SbArgs& a, bool fill, unsigned flags, hipStream_t s) {
+template <typename YT, typename F>
+int with_sb_tile_rows(F fn) {
   constexpr size_t YSZ = sizeof(typename YTraits<YT>::raw);
-  if constexpr (YSZ == 8) return launch_sb_td<XT, YT, SKIPNA, 16>(a, fill, flags, s);
-  else if constexpr (YSZ == 4) return launch_sb_td<XT, YT, SKIPNA, 32>(a, fill, flags, s);
+  if constexpr (YSZ == 8) return fn(std::integral_constant<int, 16>());
+  else if constexpr (YSZ == 4) return fn(std::integral_constant<int, 32>());
   else
-    return sb_tile_rows(YSZ) == 16 ? launch_sb_td<XT, YT, SKIPNA, 16>(a, fill, flags, s)
-                                   : launch_sb_td<XT, YT, SKIPNA, 64>(a, fill, flags, s);
+    return sb_tile_rows(YSZ) == 16 ? fn(std::integral_constant<int, 16>()) : fn(std::integral_constant<int, 64>());
 }
 
-template <typename XT, typename YT, bool SKIPNA, int TD>
-int launch_sb_td(const SbArgs& a, bool fill, unsigned flags, hipStream_t s) {
-  SbArgs args = a;
+// The two kernels behind launch_sb_any: the kernel template, and where its argument struct keeps the grid size.
+struct SbSingle {
+  template <typename XT, typename YT, int TD, int U, bool FILL, bool YSB, bool SKIPNA>
+  static constexpr auto kernel() { return &smm_apply_sb_kernel<XT, YT, TD, U, FILL, YSB, SKIPNA>; }
+  static int64_t set_grid(SbArgs& a, int64_t tiles) { return a.n_blocks = tiles; }
+};
+// grid = levels x (destination tiles x batch tiles); the caller has filled a.lev[0 .. n_lev) and the per-level strides
+struct SbGroup {
+  template <typename XT, typename YT, int TD, int U, bool FILL, bool YSB, bool SKIPNA>
+  static constexpr auto kernel() { return &smm_group_apply_sb_kernel<XT, YT, TD, U, FILL, YSB, SKIPNA>; }
+  static int64_t set_grid(SbGroupArgs& a, int64_t tiles) { return (a.blocks_per_level = tiles) * a.n_lev; }
+};
+
+template <typename K, typename XT, typename YT, bool SKIPNA, int TD, typename Args>
+int launch_sb_any(const Args& a, bool fill, unsigned flags, hipStream_t s) {
+  Args args = a;
   constexpr int BT = 128;
   args.n_dtiles = (a.n_dst + TD - 1) / TD;
   args.n_btiles = (a.n_batch + BT - 1) / BT;
-  const int64_t total = args.n_dtiles * args.n_btiles;
+  const int64_t total = K::set_grid(args, args.n_dtiles * args.n_btiles);
   if (total <= 0) return SMM_OK;
   if (total > 0x7fffffffLL) return smm::fail_msg(SMM_ERR_INVALID, "launch grid exceeds 2^31-1 blocks");
-  args.n_blocks = total;
   args.xcd_remap = xcd_run_length();
   // Tile order: strips of 2 destination tiles, inside a strip destination tile fastest, then batch tile
   // (config 2: 1.76 -> 1.65 ms against destination-tile-fastest order over the whole grid; strips of 1, 4,
@@ -318,9 +311,9 @@ int launch_sb_td(const SbArgs& a, bool fill, unsigned flags, hipStream_t s) {
     constexpr int UU = decltype(u_tag)::value;
     constexpr bool FF = decltype(fill_tag)::value;
     if (ysb)
-      hipLaunchKernelGGL((smm_apply_sb_kernel<XT, YT, TD, UU, FF, true, SKIPNA>), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
+      hipLaunchKernelGGL((K::template kernel<XT, YT, TD, UU, FF, true, SKIPNA>()), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
     else
-      hipLaunchKernelGGL((smm_apply_sb_kernel<XT, YT, TD, UU, FF, false, SKIPNA>), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
+      hipLaunchKernelGGL((K::template kernel<XT, YT, TD, UU, FF, false, SKIPNA>()), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
   };
   auto with_fill = [&](auto u_tag) {   // SKIPNA tests the raw values itself (SMM_APPLY_NO_FILL is refused with it)
     if (fill || SKIPNA) go(u_tag, std::true_type());
@@ -332,52 +325,15 @@ int launch_sb_td(const SbArgs& a, bool fill, unsigned flags, hipStream_t s) {
   return SMM_OK;
 }
 
-// The batch-fastest kernel over the data levels of a group in ONE launch (smm_group_apply_sb): grid = levels x
-// (destination tiles x batch tiles); the caller has filled a.lev[0 .. n_lev) and the per-level strides.
-template <typename XT, typename YT, bool SKIPNA, int TD>
-int launch_sb_group_td(const SbGroupArgs& a, bool fill, unsigned flags, hipStream_t s);
-
-// TD as launch_sb chooses it: 16 / 32 rows for an 8- / 4-byte Y, sb_tile_rows for a packed 2-byte one
 template <typename XT, typename YT, bool SKIPNA>
-int launch_sb_group(const SbGroupArgs& a, bool fill, unsigned flags, hipStream_t s) {
-  constexpr size_t YSZ = sizeof(typename YTraits<YT>::raw);
-  if constexpr (YSZ == 8) return launch_sb_group_td<XT, YT, SKIPNA, 16>(a, fill, flags, s);
-  else if constexpr (YSZ == 4) return launch_sb_group_td<XT, YT, SKIPNA, 32>(a, fill, flags, s);
-  else
-    return sb_tile_rows(YSZ) == 16 ? launch_sb_group_td<XT, YT, SKIPNA, 16>(a, fill, flags, s)
-                                   : launch_sb_group_td<XT, YT, SKIPNA, 64>(a, fill, flags, s);
+int launch_sb(const SbArgs& a, bool fill, unsigned flags, hipStream_t s) {
+  return with_sb_tile_rows<YT>([&](auto td) { return launch_sb_any<SbSingle, XT, YT, SKIPNA, decltype(td)::value>(a, fill, flags, s); });
 }
 
-template <typename XT, typename YT, bool SKIPNA, int TD>
-int launch_sb_group_td(const SbGroupArgs& a, bool fill, unsigned flags, hipStream_t s) {
-  SbGroupArgs args = a;
-  constexpr int BT = 128;
-  args.n_dtiles = (a.n_dst + TD - 1) / TD;
-  args.n_btiles = (a.n_batch + BT - 1) / BT;
-  args.blocks_per_level = args.n_dtiles * args.n_btiles;
-  const int64_t total = args.blocks_per_level * a.n_lev;
-  if (total <= 0) return SMM_OK;
-  if (total > 0x7fffffffLL) return smm::fail_msg(SMM_ERR_INVALID, "launch grid exceeds 2^31-1 blocks");
-  args.xcd_remap = xcd_run_length();
-  const int strip = smm::tuning(SMM_TUNE_SB_STRIP);
-  args.b_fastest = strip < 0 ? 0 : (strip > 0 ? strip : 2);
-  const bool ysb = (flags & SMM_APPLY_SB_Y_SB) != 0;
-  auto go = [&](auto u_tag, auto fill_tag) {
-    constexpr int UU = decltype(u_tag)::value;
-    constexpr bool FF = decltype(fill_tag)::value;
-    if (ysb)
-      hipLaunchKernelGGL((smm_group_apply_sb_kernel<XT, YT, TD, UU, FF, true, SKIPNA>), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
-    else
-      hipLaunchKernelGGL((smm_group_apply_sb_kernel<XT, YT, TD, UU, FF, false, SKIPNA>), dim3((unsigned)total), dim3(64), sb_lds_pad(), s, args);
-  };
-  auto with_fill = [&](auto u_tag) {   // SKIPNA tests the raw values itself (SMM_APPLY_NO_FILL is refused with it)
-    if (fill || SKIPNA) go(u_tag, std::true_type());
-    else if constexpr (!SKIPNA) go(u_tag, std::false_type());
-  };
-  if (smm::tuning(SMM_TUNE_SB_LOADS) == 4) with_fill(std::integral_constant<int, 4>());
-  else with_fill(std::integral_constant<int, 8>());
-  SMM_LAUNCH_HIP(hipGetLastError());
-  return SMM_OK;
+// The batch-fastest kernel over the data levels of a group in ONE launch (smm_group_apply_sb).
+template <typename XT, typename YT, bool SKIPNA>
+int launch_sb_group(const SbGroupArgs& a, bool fill, unsigned flags, hipStream_t s) {
+  return with_sb_tile_rows<YT>([&](auto td) { return launch_sb_any<SbGroup, XT, YT, SKIPNA, decltype(td)::value>(a, fill, flags, s); });
 }
 
 }  // namespace smm_launch
