@@ -490,6 +490,83 @@ HostChunk host_chunk_units(int64_t n_units, size_t x_unit, size_t y_unit, size_t
   return c;
 }
 
+GroupChunkPlan plan_group_chunks(int64_t n_outer, int64_t n_lev, int64_t n_inner, int64_t S, int64_t D, size_t xsz,
+                                 size_t ysz, const int64_t* used_per_level, bool packing_allowed,
+                                 int64_t requested_outer, size_t free_bytes, int64_t budget_kb) {
+  // a packed field is shipped raw, 2 B per cell, and so is a packed result: every X size below follows xsz, every Y size ysz
+  GroupChunkPlan plan;
+  plan.x_row = (((size_t)S * xsz + 127) / 128) * 128;   // device rows start on 128-B lines (see smm_apply_host)
+  const int64_t rows_per_outer = n_lev * n_inner;
+  const size_t x_outer_d = (size_t)rows_per_outer * plan.x_row;   // device bytes per outer index
+  const size_t y_outer = (size_t)rows_per_outer * D * ysz;        // Y bytes per outer index
+  auto used = [&](int64_t l, int64_t no) { return (size_t)used_per_level[l] * no * n_inner * xsz; };   // packed bytes
+  // Packing variant (see smm_apply_host): when the selected levels use at most four fifths of their source
+  // cells in total -- masked ocean levels thin out with depth -- each level's used cells of a chunk are
+  // packed batch-fastest, one (U_l, batch) block per data level, and every level runs through the
+  // batch-fastest kernel on its block.
+  int64_t used_total = 0, max_used = 0;
+  for (int64_t l = 0; l < n_lev; ++l) {
+    used_total += used_per_level[l];
+    max_used = std::max(max_used, used_per_level[l]);
+  }
+  // Chunks of the pipeline.  Whole rows: blocks of the outer axis with every level.  Packed: a chunk needs >= 32 batch
+  // entries per level to feed the batch-fastest kernel and the pack loops; when that many entries of ALL selected levels
+  // fit the staging budget a chunk is again a block of the outer axis (host_chunk_units); when they do not (config 3: 39 M
+  // used cells per time step, 10 GB for 32 steps) the chunks become LEVEL-MAJOR: a few consecutive data levels x as many
+  // outer indices as one level's used cells allow (round 6; before, such a field went whole rows over PCIe: config 3 ships
+  // 106 GB that way and 37 GB packed).  One time step per chunk with all levels (round 3) ran 4x slower than whole rows.
+  const int64_t min_outer = (32 + n_inner - 1) / n_inner;
+  const bool may_pack = packing_allowed && used_total > 0 && used_total * 5 <= n_lev * S * 4;
+  // X and Y bytes per outer index size the chunk (host_chunk_units, as in smm_apply_host)
+  const HostChunk hc = host_chunk_units(n_outer, x_outer_d, y_outer, may_pack ? (size_t)used_total * n_inner * xsz : 0,
+                                        min_outer, 1, requested_outer, free_bytes);
+  std::vector<GroupChunk>& chunks = plan.chunks;
+  auto whole_levels = [&]() {   // blocks of the outer axis, every level
+    for (int64_t o0 = 0; o0 < n_outer; o0 += hc.units)
+      chunks.push_back({o0, std::min<int64_t>(hc.units, n_outer - o0), 0, n_lev, 0});
+  };
+  plan.pack = hc.pack && budget_kb <= 0;   // tests: budget_kb > 0 forces level-major chunks of that staging budget
+  if (plan.pack || !may_pack || requested_outer > 0) whole_levels();
+  // level-major chunks pay from 8 batch entries on (12 monthly means of 75 levels: 10.6 GB whole rows, 3.7 GB packed; the
+  // batch-fastest kernel fills few of its lanes then, but PCIe, not the kernel, is what such a call waits for)
+  const int64_t min_outer_lm = std::max<int64_t>(1, (8 + n_inner - 1) / n_inner);
+  if (!plan.pack && may_pack && requested_outer <= 0 && n_outer >= min_outer_lm) {
+    // level-major: the staging budget per chunk (SMM_TUNE_HOST_CHUNK_KB lowers it so that tests reach every branch)
+    const size_t target = budget_kb > 0 ? (size_t)budget_kb << 10 : (size_t)256 << 20, cap = 4 * target;
+    const size_t per_outer = (size_t)std::max<int64_t>(max_used, 1) * n_inner * xsz;   // the widest level, one outer index
+    int64_t bo = (int64_t)(cap / per_outer);
+    if (free_bytes > 0) bo = std::min<int64_t>(bo, (int64_t)(free_bytes / 8 / (per_outer + (size_t)n_inner * D * ysz)));
+    bo = std::min(bo, n_outer);
+    if (bo >= std::min(min_outer, n_outer)) {
+      plan.pack = true;
+      chunks.clear();
+      for (int64_t o0 = 0; o0 < n_outer; o0 += bo) {
+        const int64_t no = std::min(bo, n_outer - o0);
+        for (int64_t l0 = 0; l0 < n_lev;) {
+          // levels are added while their X bytes fit the target, at least one; the chunk's Y is not bounded here
+          int64_t nl = 0;
+          size_t bytes = 0;
+          do {
+            bytes += used(l0 + nl, no);
+            ++nl;
+          } while (l0 + nl < n_lev && bytes + used(l0 + nl, no) <= target);
+          chunks.push_back({o0, no, l0, nl, bytes});
+          l0 += nl;
+        }
+      }
+    }
+  }
+  if (chunks.empty()) whole_levels();   // packing not possible after all: whole rows
+  for (GroupChunk& c : chunks) {
+    if (plan.pack && c.x_bytes == 0)
+      for (int64_t l = c.l0; l < c.l0 + c.nl; ++l) c.x_bytes += used(l, c.no);
+    plan.max_x = std::max(plan.max_x, plan.pack ? c.x_bytes : (size_t)c.no * x_outer_d);
+    plan.max_y = std::max(plan.max_y, (size_t)c.no * n_inner * c.nl * D * ysz);
+    plan.max_rows = std::max(plan.max_rows, (size_t)c.no * rows_per_outer);
+  }
+  return plan;
+}
+
 void build_sell(const HostCsr& csr, HostSell& out) {
   BuilderScope scope;
   const int nt = host_threads(csr.nnz + csr.n_dst, (int64_t)1 << 17);

@@ -105,6 +105,11 @@ inline int check_x_dtype(const CallDesc& c) {
   const Refusal r = x_dtype_refusal(c.x_dtype, c.y_dtype, c.has_cf, c.has_enc);
   return r.code ? fail(r.code, r.msg) : SMM_OK;
 }
+inline int check_area_min(double area_min) {
+  if (!(area_min >= 0.0 && area_min <= 1.0))
+    return fail(SMM_ERR_INVALID, "remap_area_min must be within [0, 1]");  // regrid.py:124-125
+  return SMM_OK;
+}
 // A call that carries the rules its dtypes need (a packed X its decode rule, a packed Y its encode rule) is accepted
 // exactly when its combination is built.
 constexpr bool refusals_match_built() {
@@ -460,8 +465,7 @@ int run_apply(const ApplyTarget& t, const int32_t* d_lev_map, const uint8_t* d_l
   if (!info_only && (!x || !y)) return fail(SMM_ERR_INVALID, "null field pointer");
   const bool packed = call.packed_x(), enc = call.has_enc;
   if (int drc = check_x_dtype(call)) return drc;
-  if (!(area_min >= 0.0 && area_min <= 1.0))
-    return fail(SMM_ERR_INVALID, "remap_area_min must be within [0, 1]");  // regrid.py:124-125
+  if (int arc = check_area_min(area_min)) return arc;
 
   ApplyArgs a{};
   a.descs = t.d_descs;
@@ -728,6 +732,39 @@ inline int check_flags(unsigned flags) {
   if ((flags & SMM_APPLY_SKIPNA) && (flags & SMM_APPLY_NO_FILL))
     return fail(SMM_ERR_INVALID, "SMM_APPLY_SKIPNA tests every source value: it cannot take SMM_APPLY_NO_FILL");
   return SMM_OK;
+}
+
+// ---- what an apply refuses about its epilogue and its levels, written once for every entry (check_area_min is with
+// check_x_dtype).  what: "the operator" or "a level"
+inline int check_epilogue(const smm_operator* op, bool masked, double area_min, const char* what) {
+  if (masked && !op->d_imask)
+    return fail(SMM_ERR_INVALID, std::string("masked apply requested but ") + what + " has no dst_imask");
+  if (area_min > 0.0 && !op->d_frac)
+    return fail(SMM_ERR_INVALID, std::string("remap_area_min > 0 requested but ") + what + " has no dst_frac");
+  return SMM_OK;
+}
+// member w of a group takes the masked epilogue: the call asks for it and the member is not exempt (regrid.py:405)
+inline bool level_masked(unsigned flags, const uint8_t* masked_levels, int w) {
+  return (flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w]);
+}
+// Every selected level of a group call, before anything is uploaded or launched: a later level's missing dst_imask /
+// dst_frac must not surface after earlier levels have written part of Y.  flags 0 and area_min 0 ask about level_index only.
+inline int check_levels(const smm_group* g, int64_t n_lev, const int32_t* level_index, const uint8_t* masked_levels,
+                        double area_min, unsigned flags) {
+  if (n_lev > 0 && !level_index) return fail(SMM_ERR_INVALID, "null level_index");
+  for (int64_t l = 0; l < n_lev; ++l) {
+    const int w = level_index[l];
+    if (w < 0 || w >= (int)g->ops.size())
+      return fail(SMM_ERR_INVALID, "level_index[" + std::to_string(l) + "]=" + std::to_string(w) + " outside the group");
+    if (int rc = check_epilogue(g->ops[(size_t)w], level_masked(flags, masked_levels, w), area_min, "a level")) return rc;
+  }
+  return SMM_OK;
+}
+inline size_t free_device_bytes() {   // 0 when it cannot be told (the error is cleared)
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) return free_b;
+  (void)hipGetLastError();
+  return 0;
 }
 
 }  // namespace
@@ -1168,16 +1205,11 @@ static int smm_operator_plan_info_impl(smm_operator_t op, int* kernel_kind, int6
 
 static int smm_apply_impl(smm_operator_t op, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t n_batch,
                           void* stream, const CallDesc& call) {
-  const unsigned flags = call.flags;
-  const double remap_area_min = call.area_min;
-  if (int frc = check_flags(flags)) return frc;
+  if (int frc = check_flags(call.flags)) return frc;
   if (!op) return fail(SMM_ERR_INVALID, "null operator");
   if (n_batch > 0 && (ldx < op->csr.n_src || ldy < op->csr.n_dst))
     return fail(SMM_ERR_INVALID, "ldx/ldy smaller than the grid size");
-  if ((flags & SMM_APPLY_MASKED) && !op->d_imask)
-    return fail(SMM_ERR_INVALID, "masked apply requested but the operator has no dst_imask");
-  if (remap_area_min > 0.0 && !op->d_frac)
-    return fail(SMM_ERR_INVALID, "remap_area_min > 0 requested but the operator has no dst_frac");
+  if (int erc = check_epilogue(op, call.flags & SMM_APPLY_MASKED, call.area_min, "the operator")) return erc;
   DeviceGuard guard(op->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
   return run_apply(target_of(op), nullptr, nullptr, x, ldx, 0, 0, y, ldy, 0, 0, n_batch, 1, 1, call, (hipStream_t)stream);
@@ -1213,12 +1245,8 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int64_t ldx, void
   if (int drc = check_x_dtype(call)) return drc;
   if (ldx < n_batch || ldy < ((flags & SMM_APPLY_SB_Y_SB) ? n_batch : op->csr.n_dst))
     return fail(SMM_ERR_INVALID, "ldx smaller than the batch or ldy smaller than a row of Y");
-  if (!(remap_area_min >= 0.0 && remap_area_min <= 1.0))
-    return fail(SMM_ERR_INVALID, "remap_area_min must be within [0, 1]");  // regrid.py:124-125
-  if ((flags & SMM_APPLY_MASKED) && !op->d_imask)
-    return fail(SMM_ERR_INVALID, "masked apply requested but the operator has no dst_imask");
-  if (remap_area_min > 0.0 && !op->d_frac)
-    return fail(SMM_ERR_INVALID, "remap_area_min > 0 requested but the operator has no dst_frac");
+  if (int arc = check_area_min(remap_area_min)) return arc;
+  if (int erc = check_epilogue(op, flags & SMM_APPLY_MASKED, remap_area_min, "the operator")) return erc;
   const size_t xsz = dtype_size(call.x_dtype), ysz = dtype_size(call.y_dtype);
   if ((uintptr_t)x % xsz || (uintptr_t)y % ysz) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
   DeviceGuard guard(op->device);
@@ -1300,13 +1328,8 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int64_t ld
                         U > 0 && U * 5 <= S * 4;
   // Chunk size from the X AND Y bytes of a row (an operator with few used cells and a large target
   // is bound by its Y staging), clamped to a quarter of the free device memory: smm_internal.h
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-    (void)hipGetLastError();
-    free_b = 0;
-  }
   const smm::HostChunk hc = smm::host_chunk_units(n_batch, xrow_d, (size_t)D * ysz, may_pack ? (size_t)U * xsz : 0,
-                                                  8, 128, chunk_rows, free_b);   // packing pays from 8 rows on (24 rows: 4.2 -> 1.9 ms)
+                                                  8, 128, chunk_rows, free_device_bytes());   // packing pays from 8 rows on (24 rows: 4.2 -> 1.9 ms)
   const bool pack = hc.pack;
   chunk_rows = hc.units;
   if (pack) {
@@ -1509,21 +1532,9 @@ static int group_level_cfg(smm_group_t g, int64_t n_lev, const int32_t* level_in
   *d_masked = nullptr;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
   if (n_lev < 0) return fail(SMM_ERR_INVALID, "negative level count");
-  if (n_lev > 0 && !level_index) return fail(SMM_ERR_INVALID, "null level_index");
-  const int n_ops = (int)g->ops.size();
-  for (int64_t l = 0; l < n_lev; ++l) {
-    const int32_t w = level_index[l];
-    if (w < 0 || w >= n_ops)
-      return fail(SMM_ERR_INVALID, "level_index[" + std::to_string(l) + "]=" + std::to_string(w) +
-                                       " outside the group");
-    const smm_operator* op = g->ops[(size_t)w];
-    const bool m = (flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w]);
-    if (m && !op->d_imask)
-      return fail(SMM_ERR_INVALID, "masked apply requested but a level has no dst_imask");
-    if (remap_area_min > 0.0 && !op->d_frac)
-      return fail(SMM_ERR_INVALID, "remap_area_min > 0 requested but a level has no dst_frac");
-  }
+  if (int vrc = check_levels(g, n_lev, level_index, masked_levels, remap_area_min, flags)) return vrc;
   if (n_lev == 0) return SMM_OK;
+  const int n_ops = (int)g->ops.size();
 
   // key: level count, then the map, then (if given) one masked flag per member -- unambiguous
   std::string key((const char*)&n_lev, sizeof(n_lev));
@@ -1585,27 +1596,6 @@ static int smm_group_apply_impl(smm_group_t g, const void* x, int64_t xs_outer, 
                    n_lev, n_inner, call, (hipStream_t)stream);
 }
 
-extern "C++" {
-// What smm_apply_sb would reject for one of the selected levels, checked for all of them up front.
-static int check_sb_levels(smm_group_t g, int64_t n_lev, const int32_t* level_index, const uint8_t* masked_levels,
-                           double remap_area_min, unsigned flags) {
-  if (!(remap_area_min >= 0.0 && remap_area_min <= 1.0))
-    return fail(SMM_ERR_INVALID, "remap_area_min must be within [0, 1]");  // regrid.py:124-125
-  const int n_ops = (int)g->ops.size();
-  for (int64_t l = 0; l < n_lev; ++l) {
-    const int32_t w = level_index[l];
-    if (w < 0 || w >= n_ops)
-      return fail(SMM_ERR_INVALID, "level_index[" + std::to_string(l) + "]=" + std::to_string(w) + " outside the group");
-    const smm_operator* op = g->ops[(size_t)w];
-    const bool m = (flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w]);
-    if (m && !op->d_imask) return fail(SMM_ERR_INVALID, "masked apply requested but a level has no dst_imask");
-    if (remap_area_min > 0.0 && !op->d_frac)
-      return fail(SMM_ERR_INVALID, "remap_area_min > 0 requested but a level has no dst_frac");
-  }
-  return SMM_OK;
-}
-}  // extern "C++"
-
 static int smm_group_prepare_sb_impl(smm_group_t g) {
   if (!g) return fail(SMM_ERR_INVALID, "null group");
   DeviceGuard guard(g->device);
@@ -1633,15 +1623,10 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int64_t xs_lev,
   if (int frc = check_flags(flags)) return frc;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
   if (n_batch < 0 || n_lev < 0) return fail(SMM_ERR_INVALID, "negative batch size / level count");
-  if (n_lev > 0 && !level_index) return fail(SMM_ERR_INVALID, "null level_index");
   if (flags & SMM_APPLY_SB_PACKED)
     return fail(SMM_ERR_UNSUPPORTED, "packed fields are per operator: a group takes whole (S, B) slabs");
   if (int drc = check_x_dtype(call)) return drc;
-  const int n_ops = (int)g->ops.size();
-  for (int64_t l = 0; l < n_lev; ++l)
-    if (level_index[l] < 0 || level_index[l] >= n_ops)
-      return fail(SMM_ERR_INVALID, "level_index[" + std::to_string(l) + "]=" + std::to_string(level_index[l]) +
-                                       " outside the group");
+  if (int irc = check_levels(g, n_lev, level_index, nullptr, 0.0, 0u)) return irc;   // an empty call answers for these only
   if (n_lev == 0 || n_batch == 0 || g->ops[0]->csr.n_dst == 0) return SMM_OK;
   if (!x || !y) return fail(SMM_ERR_INVALID, "null field pointer");
   const size_t xsz = dtype_size(call.x_dtype), ysz = dtype_size(call.y_dtype);
@@ -1651,10 +1636,8 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int64_t xs_lev,
   if (ys_batch < ((flags & SMM_APPLY_SB_Y_SB) ? n_batch : g->ops[0]->csr.n_dst))
     return fail(SMM_ERR_INVALID, "ys_batch smaller than a row of Y");
   if ((uintptr_t)x % xsz || (uintptr_t)y % ysz) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
-  {
-    int vrc = check_sb_levels(g, n_lev, level_index, masked_levels, remap_area_min, flags);
-    if (vrc) return vrc;
-  }
+  if (int arc = check_area_min(remap_area_min)) return arc;
+  if (int vrc = check_levels(g, n_lev, level_index, masked_levels, remap_area_min, flags)) return vrc;
   const bool per_level_launches = smm::tuning(SMM_TUNE_SB_LEVEL_LAUNCHES) == 1;
   hipStream_t caller = (hipStream_t)stream;
   DeviceGuard guard(g->device);
@@ -1685,8 +1668,8 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int64_t xs_lev,
       for (int i = 0; i < a.n_lev; ++i) {
         const int w = level_index[l0 + i];
         const smm_operator* op = g->ops[(size_t)w];
-        const bool m = (flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w]);   // regrid.py:405
-        a.lev[i] = SbLevelPtrs{op->d_csr_rowptr, op->d_csr_col, op->d_csr_val, m ? op->d_imask : nullptr, op->d_frac};
+        a.lev[i] = SbLevelPtrs{op->d_csr_rowptr, op->d_csr_col, op->d_csr_val,
+                               level_masked(flags, masked_levels, w) ? op->d_imask : nullptr, op->d_frac};
       }
       if (call.packed_x()) a.cf = call.cf;      // CF-packed: raw 2-byte slabs, one decode rule for every level
       if (call.has_enc) a.cfo = call.enc;       // one encode rule for every level
@@ -1704,7 +1687,7 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int64_t xs_lev,
   for (int64_t l = 0; l < n_lev && status == SMM_OK; ++l) {
     const int w = level_index[l];
     unsigned fl = flags & ~(unsigned)SMM_APPLY_MASKED;
-    if ((flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w])) fl |= SMM_APPLY_MASKED;   // regrid.py:405
+    if (level_masked(flags, masked_levels, w)) fl |= SMM_APPLY_MASKED;
     status = smm_apply_sb_impl(g->ops[(size_t)w], (const char*)x + (size_t)l * xs_lev * xsz, ldx,
                                (char*)y + (size_t)l * ys_lev * ysz, ys_batch, n_batch, caller, call.with_flags(fl));
   }
@@ -1766,7 +1749,6 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, void* y_
                                      const uint8_t* masked_levels, int64_t chunk_outer, const CallDesc& call) {
   const int x_dtype = call.x_dtype, y_dtype = call.y_dtype;
   const unsigned flags = call.flags;
-  const double remap_area_min = call.area_min;
   const bool enc = call.has_enc;
   if (int frc = check_flags(flags)) return frc;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
@@ -1783,114 +1765,37 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, void* y_
   DeviceGuard guard(g->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the group's device");
 
-  // a packed field is staged, packed and shipped raw, 2 B per cell: every size below follows xsz.  The slabs of a packed
-  // chunk lie back to back (level l's at the running sum of U_l * batch * xsz): kernel C's 4-B-per-lane loads of 2-byte
-  // elements only assume element alignment (xvec_u, smm_kernels.hpp), and a slab can start on an odd element only when
-  // the batch count is odd -- when every other row of every slab starts on one anyway -- so no padding is added.  A packed
-  // result (enc) comes back, is staged and copied out raw too: every Y size below follows ysz = 2, in the outer-block clamp,
-  // the level-major chunks, the pinned staging and both host layouts of a chunk's level range
+  // every selected level is checked before anything is staged or launched (as smm_group_apply does): a level that
+  // lacks dst_imask / dst_frac must not surface after earlier levels have written part of Y
+  if (int arc = check_area_min(call.area_min)) return arc;
+  if (int vrc = check_levels(g, n_lev, level_index, masked_levels, call.area_min, flags)) return vrc;
+
+  // The chunks of the pipeline (smm::plan_group_chunks): whole rows, or each level's used cells packed batch-fastest.
+  // The slabs of a packed chunk lie back to back (level l's at the running sum of U_l * batch * xsz): kernel C's
+  // 4-B-per-lane loads of 2-byte elements only assume element alignment (xvec_u, smm_kernels.hpp), and a slab can start
+  // on an odd element only when the batch count is odd -- when every other row of every slab starts on one anyway -- so
+  // no padding is added.  The pinned staging and both host layouts of a chunk's level range follow xsz / ysz too.
   const size_t xsz = dtype_size(x_dtype), ysz = dtype_size(y_dtype);
-  const size_t xrow_d = (((size_t)S * xsz + 127) / 128) * 128;   // device rows start on 128-B lines (see smm_apply_host)
-  const int64_t ldx_d = (int64_t)(xrow_d / xsz);
   const int64_t rows_per_outer = n_lev * n_inner;
-  const size_t x_outer_d = (size_t)rows_per_outer * xrow_d;   // device bytes per outer index
-  const size_t y_outer = (size_t)rows_per_outer * D * ysz;    // Y bytes per outer index
-  // Packing variant (see smm_apply_host): when the selected levels use at most four fifths of their source
-  // cells in total -- masked ocean levels thin out with depth -- each level's used cells of a chunk are
-  // packed batch-fastest, one (U_l, batch) block per data level, and every level runs through the
-  // batch-fastest kernel on its block.
-  if (n_lev > 0 && !level_index) return fail(SMM_ERR_INVALID, "null level_index");
-  int64_t used_total = 0;
-  for (int64_t l = 0; l < n_lev; ++l) {
-    if (level_index[l] < 0 || level_index[l] >= (int32_t)g->ops.size())
-      return fail(SMM_ERR_INVALID, "level_index[" + std::to_string(l) + "] outside the group");
-    used_total += g->ops[(size_t)level_index[l]]->csr.n_used_src;
-  }
-  // Chunks of the pipeline.  Whole rows: blocks of the outer axis with every level.  Packed: a chunk needs >= 32 batch
-  // entries per level to feed the batch-fastest kernel and the pack loops; when that many entries of ALL selected levels
-  // fit the staging budget a chunk is again a block of the outer axis (host_chunk_units); when they do not (config 3: 39 M
-  // used cells per time step, 10 GB for 32 steps) the chunks become LEVEL-MAJOR: a few consecutive data levels x as many
-  // outer indices as one level's used cells allow (round 6; before, such a field went whole rows over PCIe: config 3 ships
-  // 106 GB that way and 37 GB packed).  One time step per chunk with all levels (round 3) ran 4x slower than whole rows.
-  const int64_t min_outer = (32 + n_inner - 1) / n_inner;
-  const bool may_pack = !(flags & (SMM_APPLY_HOST_NO_PACK | SMM_APPLY_KERNEL_SELL | SMM_APPLY_KERNEL_TILE)) &&
-                        used_total > 0 && used_total * 5 <= n_lev * S * 4;
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-    (void)hipGetLastError();
-    free_b = 0;
-  }
-  // X and Y bytes per outer index size the chunk (smm_internal.h host_chunk_units, as in smm_apply_host)
-  const smm::HostChunk hc = smm::host_chunk_units(n_outer, x_outer_d, y_outer,
-                                                  may_pack ? (size_t)used_total * n_inner * xsz : 0, min_outer, 1,
-                                                  chunk_outer, free_b);
-  struct GChunk {
-    int64_t o0, no, l0, nl;
-    size_t x_bytes;   // packed X bytes of the chunk (pack mode)
-  };
-  std::vector<GChunk> chunks;
-  const int64_t budget_kb = smm::tuning(SMM_TUNE_HOST_CHUNK_KB);   // tests: > 0 forces level-major chunks of that staging budget
-  bool pack = hc.pack && budget_kb <= 0;
-  if (pack || !may_pack || chunk_outer > 0) {
-    for (int64_t o0 = 0; o0 < n_outer; o0 += hc.units)
-      chunks.push_back({o0, std::min<int64_t>(hc.units, n_outer - o0), 0, n_lev, 0});
-  }
-  // level-major chunks pay from 8 batch entries on (12 monthly means of 75 levels: 10.6 GB whole rows, 3.7 GB packed; the
-  // batch-fastest kernel fills few of its lanes then, but PCIe, not the kernel, is what such a call waits for)
-  const int64_t min_outer_lm = std::max<int64_t>(1, (8 + n_inner - 1) / n_inner);
-  if (!pack && may_pack && chunk_outer <= 0 && n_outer >= min_outer_lm) {
-    // level-major: the staging budget per chunk (SMM_TUNE_HOST_CHUNK_KB lowers it so that tests reach every branch)
-    const size_t target = budget_kb > 0 ? (size_t)budget_kb << 10 : (size_t)256 << 20, cap = 4 * target;
-    int64_t max_used = 0;
-    for (int64_t l = 0; l < n_lev; ++l) max_used = std::max(max_used, g->ops[(size_t)level_index[l]]->csr.n_used_src);
-    const size_t per_outer = (size_t)std::max<int64_t>(max_used, 1) * n_inner * xsz;   // the widest level, one outer index
-    int64_t bo = (int64_t)(cap / per_outer);
-    if (free_b > 0) bo = std::min<int64_t>(bo, (int64_t)(free_b / 8 / (per_outer + (size_t)n_inner * D * ysz)));
-    bo = std::min(bo, n_outer);
-    if (bo >= std::min(min_outer, n_outer)) {
-      pack = true;
-      chunks.clear();
-      for (int64_t o0 = 0; o0 < n_outer; o0 += bo) {
-        const int64_t no = std::min(bo, n_outer - o0);
-        for (int64_t l0 = 0; l0 < n_lev;) {
-          int64_t nl = 0;
-          size_t bytes = 0;
-          do {
-            bytes += (size_t)g->ops[(size_t)level_index[l0 + nl]]->csr.n_used_src * no * n_inner * xsz;
-            ++nl;
-          } while (l0 + nl < n_lev &&
-                   bytes + (size_t)g->ops[(size_t)level_index[l0 + nl]]->csr.n_used_src * no * n_inner * xsz <= target);
-          chunks.push_back({o0, no, l0, nl, bytes});
-          l0 += nl;
-        }
-      }
-    }
-  }
-  if (chunks.empty())   // packing not possible after all: whole rows
-    for (int64_t o0 = 0; o0 < n_outer; o0 += hc.units)
-      chunks.push_back({o0, std::min<int64_t>(hc.units, n_outer - o0), 0, n_lev, 0});
-  size_t max_x = 0, max_y = 0, max_rows = 0;
-  for (GChunk& c : chunks) {
-    if (pack && c.x_bytes == 0)
-      for (int64_t l = c.l0; l < c.l0 + c.nl; ++l)
-        c.x_bytes += (size_t)g->ops[(size_t)level_index[l]]->csr.n_used_src * c.no * n_inner * xsz;
-    max_x = std::max(max_x, pack ? c.x_bytes : (size_t)c.no * x_outer_d);
-    max_y = std::max(max_y, (size_t)c.no * n_inner * c.nl * D * ysz);
-    max_rows = std::max(max_rows, (size_t)c.no * rows_per_outer);
-  }
-  if (pack) {
-    // every selected level is checked before the first launch (as smm_group_apply does): a level that
-    // lacks dst_imask / dst_frac must not surface after earlier levels have written part of Y
-    int vrc = check_sb_levels(g, n_lev, level_index, masked_levels, remap_area_min, flags);
-    if (vrc) return vrc;
-    int prc = smm_group_prepare_sb(g);
-    if (prc) return prc;
-  }
+  std::vector<int64_t> used_per_level((size_t)n_lev);
+  for (int64_t l = 0; l < n_lev; ++l) used_per_level[(size_t)l] = g->ops[(size_t)level_index[l]]->csr.n_used_src;
+  const smm::GroupChunkPlan plan = smm::plan_group_chunks(
+      n_outer, n_lev, n_inner, S, D, xsz, ysz, used_per_level.data(),
+      !(flags & (SMM_APPLY_HOST_NO_PACK | SMM_APPLY_KERNEL_SELL | SMM_APPLY_KERNEL_TILE)), chunk_outer,
+      free_device_bytes(), smm::tuning(SMM_TUNE_HOST_CHUNK_KB));
+  using GChunk = smm::GroupChunk;
+  const std::vector<GChunk>& chunks = plan.chunks;
+  const bool pack = plan.pack;
+  const size_t xrow_d = plan.x_row;
+  const int64_t ldx_d = (int64_t)(xrow_d / xsz);
+  if (pack)
+    if (int prc = smm_group_prepare_sb(g)) return prc;
   const bool x_direct = is_pinned(x_host) && !pack, y_direct = is_pinned(y_host);
 
   std::lock_guard<std::mutex> pipe_lock(g->pipe_mu);
   HostPipe& pipe = g->pipe;
-  SMM_HIP(pipe.ensure(max_x, max_y, x_direct ? 0 : (pack ? max_x : max_rows * S * xsz), y_direct ? 0 : max_y));
+  SMM_HIP(pipe.ensure(plan.max_x, plan.max_y, x_direct ? 0 : (pack ? plan.max_x : plan.max_rows * S * xsz),
+                      y_direct ? 0 : plan.max_y));
 
   const int64_t n_chunks = (int64_t)chunks.size();
   CallStats st;
@@ -1960,7 +1865,7 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, void* y_
         const int w = level_index[ck.l0 + ll];
         smm_operator* op = g->ops[(size_t)w];
         unsigned fl = (flags & (SMM_APPLY_NO_FILL | SMM_APPLY_SKIPNA)) | SMM_APPLY_SB_PACKED;
-        if ((flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w])) fl |= SMM_APPLY_MASKED;
+        if (level_masked(flags, masked_levels, w)) fl |= SMM_APPLY_MASKED;
         // Y of the chunk: entry (b, ll, d) at (b * nl + ll) * D + d when transpose, at (ll * bc + b) * D + d else
         rc = smm_apply_sb_impl(op, (char*)pipe.dx[b] + off, bc,
                                (char*)pipe.dy[b] + (size_t)ll * (transpose ? D : bc * D) * ysz,

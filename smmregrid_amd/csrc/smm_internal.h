@@ -168,4 +168,22 @@ HostChunk host_chunk_units(int64_t n_units, size_t x_unit, size_t y_unit, size_t
                            int64_t min_pack_units, int64_t pack_align, int64_t requested,
                            size_t free_bytes);
 
+// Chunk plan of smm_group_apply_host: which outer indices x data levels each chunk of the pipeline holds.
+struct GroupChunk {
+  int64_t o0, no, l0, nl;   // outer indices [o0, o0 + no) of data levels [l0, l0 + nl)
+  size_t x_bytes;           // packed X bytes of the chunk (pack mode; 0 for whole rows)
+};
+struct GroupChunkPlan {
+  bool pack = false;                 // chunks ship each level's used cells batch-fastest, else whole rows
+  size_t x_row = 0;                  // device bytes of a whole row of X: rows start on 128-B lines
+  std::vector<GroupChunk> chunks;    // tile [0, n_outer) x [0, n_lev) exactly once, in pipeline order
+  size_t max_x = 0, max_y = 0, max_rows = 0;   // largest device X / Y bytes and whole batch rows of one chunk
+};
+// X (n_outer, n_lev, n_inner, S) of xsz-byte cells, Y (.., D) of ysz-byte cells; used_per_level[l] = n_used_src of data
+// level l.  packing_allowed: no flag of the call rules packing out.  requested_outer, free_bytes: as host_chunk_units.
+// budget_kb > 0 (SMM_TUNE_HOST_CHUNK_KB) forces level-major chunks of that staging budget.  Rules: with the body.
+GroupChunkPlan plan_group_chunks(int64_t n_outer, int64_t n_lev, int64_t n_inner, int64_t S, int64_t D, size_t xsz,
+                                 size_t ysz, const int64_t* used_per_level, bool packing_allowed,
+                                 int64_t requested_outer, size_t free_bytes, int64_t budget_kb);
+
 }  // namespace smm

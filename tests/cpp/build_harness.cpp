@@ -165,6 +165,144 @@ int main(int argc, char** argv) {
     if (c.pack || c.units < 1) ++cbad;
     printf("CHUNKBAD %lld\n", cbad);
   }
+  // chunk plan of smm_group_apply_host (smm::plan_group_chunks): outer blocks with every level, or level-major
+  {
+    long long gbad = 0;
+    struct Args {
+      int64_t n_outer, n_lev, n_inner, S, D;
+      size_t xsz, ysz;
+      std::vector<int64_t> used;
+      bool allowed;
+      int64_t requested;
+      size_t free_bytes;
+      int64_t budget_kb;
+    };
+    // what holds for every plan: the chunks tile (outer x level) exactly once, none is empty, x_bytes is the packed
+    // size of the chunk's levels, the maxima are the maxima of the list
+    auto plan_of = [&](const Args& a) {
+      const smm::GroupChunkPlan p = smm::plan_group_chunks(a.n_outer, a.n_lev, a.n_inner, a.S, a.D, a.xsz, a.ysz, a.used.data(),
+                                                           a.allowed, a.requested, a.free_bytes, a.budget_kb);
+      std::vector<int> seen((size_t)(a.n_outer * a.n_lev), 0);
+      size_t max_x = 0, max_y = 0, max_rows = 0;
+      if (p.x_row != (a.S * a.xsz + 127) / 128 * 128) ++gbad;
+      for (const smm::GroupChunk& c : p.chunks) {
+        if (c.no < 1 || c.nl < 1 || c.o0 < 0 || c.l0 < 0 || c.o0 + c.no > a.n_outer || c.l0 + c.nl > a.n_lev) {
+          ++gbad;
+          continue;
+        }
+        size_t xb = 0;
+        for (int64_t l = c.l0; l < c.l0 + c.nl; ++l) {
+          xb += (size_t)a.used[(size_t)l] * c.no * a.n_inner * a.xsz;
+          for (int64_t o = c.o0; o < c.o0 + c.no; ++o) ++seen[(size_t)(o * a.n_lev + l)];
+        }
+        if (c.x_bytes != (p.pack ? xb : 0)) ++gbad;
+        max_x = std::max(max_x, p.pack ? xb : (size_t)c.no * a.n_lev * a.n_inner * p.x_row);
+        max_y = std::max(max_y, (size_t)c.no * a.n_inner * c.nl * a.D * a.ysz);
+        max_rows = std::max(max_rows, (size_t)(c.no * a.n_lev * a.n_inner));
+      }
+      for (int v : seen) gbad += v != 1;
+      if (p.max_x != max_x || p.max_y != max_y || p.max_rows != max_rows) ++gbad;
+      return p;
+    };
+    struct C { int64_t o0, no, l0, nl; size_t x_bytes; };
+    auto expect = [&](const Args& a, bool pack, const std::vector<C>& want) {
+      const smm::GroupChunkPlan p = plan_of(a);
+      bool ok = p.pack == pack && p.chunks.size() == want.size();
+      for (size_t i = 0; ok && i < want.size(); ++i) {
+        const smm::GroupChunk& c = p.chunks[i];
+        ok = c.o0 == want[i].o0 && c.no == want[i].no && c.l0 == want[i].l0 && c.nl == want[i].nl && c.x_bytes == want[i].x_bytes;
+      }
+      if (!ok) ++gbad;
+    };
+    const size_t MiB = (size_t)1 << 20, GiB = (size_t)1 << 30;
+    // Outer-block packing.  S = 10^6 f64 (rows of 8 000 000 B, a multiple of 128), D = 1000, U = 350 000 of 3 * 10^6 cells
+    // (<= 4/5).  host_chunk_units: packed unit 350 000 * 8 + 3 * 1000 * 8 = 2 824 000 B; 256 MiB / that = 95 units, cut
+    // to the cap max(32, 32 MiB / unit = 11, ceil(100 / 8) = 13) = 32: blocks of 32, 32, 32 and a short 4, all levels each,
+    // x_bytes = 350 000 * no * 8
+    const Args big{100, 3, 1, 1000000, 1000, 8, 8, {200000, 100000, 50000}, true, 0, 0, 0};
+    expect(big, true, {{0, 32, 0, 3, 89600000}, {32, 32, 0, 3, 89600000}, {64, 32, 0, 3, 89600000}, {96, 4, 0, 3, 11200000}});
+    // packing ruled out by the flags: whole rows, unit 3 * 8 000 000 + 24 000 B, 256 MiB / that = 11 (< the 13 of
+    // eight chunks per call): nine blocks of 11 and a last of 1
+    std::vector<C> rows11;
+    for (int64_t o = 0; o < 100; o += 11) rows11.push_back({o, std::min<int64_t>(11, 100 - o), 0, 3, 0});
+    Args a = big;
+    a.allowed = false;
+    expect(a, false, rows11);
+    // more than four fifths of the cells used (2.5 M * 5 > 3 M * 4): whole rows, the same blocks
+    a = big;
+    a.used = {900000, 800000, 800000};
+    expect(a, false, rows11);
+    // a requested chunk_outer is kept and level-major never entered, whatever the budget: 7 (< 32 entries) does not
+    // pack; 40 packs, but not when the tuning knob asks for level-major chunks
+    a = big;
+    a.requested = 7;
+    a.budget_kb = 64;
+    std::vector<C> rows7;
+    for (int64_t o = 0; o < 100; o += 7) rows7.push_back({o, std::min<int64_t>(7, 100 - o), 0, 3, 0});
+    expect(a, false, rows7);
+    a.requested = 40;
+    expect(a, false, {{0, 40, 0, 3, 0}, {40, 40, 0, 3, 0}, {80, 20, 0, 3, 0}});
+    a.budget_kb = 0;
+    expect(a, true, {{0, 40, 0, 3, 112000000}, {40, 40, 0, 3, 112000000}, {80, 20, 0, 3, 56000000}});
+    // Level-major, budget 64 KiB: target 65 536 B, cap 262 144 B.  40 outer indices, f64: a level of 100 used cells is
+    // 100 * 40 * 8 = 32 000 B, one of 10 is 3 200 B; bo = 262 144 / 800 = 327 -> 40.  32 000 + 32 000 = 64 000 fits,
+    // + 32 000 does not: {2}; then 32 000 + 3 200 + 3 200 = 38 400: {3}
+    const Args thin{40, 5, 1, 1000, 50, 8, 8, {100, 100, 100, 10, 10}, true, 0, 0, 64};
+    expect(thin, true, {{0, 40, 0, 2, 64000}, {0, 40, 2, 3, 38400}});
+    // the same for a packed field and result (2-byte cells) under 16 KiB: levels of 8 000 and 800 B, 16 000 <= 16 384
+    a = thin;
+    a.xsz = a.ysz = 2;
+    a.budget_kb = 16;
+    expect(a, true, {{0, 40, 0, 2, 16000}, {0, 40, 2, 3, 9600}});
+    // a level beyond the target on its own (500 * 40 * 8 = 160 000 B > 65 536) is still taken, alone
+    const Args wide{40, 3, 1, 1000, 50, 8, 8, {100, 500, 100}, true, 0, 0, 64};
+    expect(wide, true, {{0, 40, 0, 1, 32000}, {0, 40, 1, 1, 160000}, {0, 40, 2, 1, 32000}});
+    // bo cut by the cap: the widest level is 4 000 B per outer index, 262 144 / 4 000 = 65: blocks of 65 and 35.
+    // 65: 260 000 | 52 000 | 52 000 (two would be 104 000); 35: 140 000 | 28 000 + 28 000 = 56 000
+    const Args capped{100, 3, 1, 1000, 50, 8, 8, {500, 100, 100}, true, 0, 0, 64};
+    expect(capped, true, {{0, 65, 0, 1, 260000}, {0, 65, 1, 1, 52000}, {0, 65, 2, 1, 52000}, {65, 35, 0, 1, 140000}, {65, 35, 1, 2, 56000}});
+    // bo cut by the free memory: free / 8 / (4 000 + 50 * 8) = 40 with 1 408 000 B free: blocks of 40, 40, 20.
+    // 40: 160 000 | 32 000 + 32 000; 20: 80 000 | 16 000 + 16 000
+    a = capped;
+    a.free_bytes = 8 * 4400 * 40;
+    expect(a, true, {{0, 40, 0, 1, 160000}, {0, 40, 1, 2, 64000}, {40, 40, 0, 1, 160000}, {40, 40, 1, 2, 64000},
+                     {80, 20, 0, 1, 80000}, {80, 20, 1, 2, 32000}});
+    // ... and to 31 (< the 32 entries a packed chunk needs): whole rows after all, in host_chunk_units' block (all 100)
+    a.free_bytes = 8 * 4400 * 31;
+    expect(a, false, {{0, 100, 0, 3, 0}});
+    // 10 outer indices (>= 8, < 32) are still packed level-major: the default 256-MiB target takes all three levels,
+    // 16 KiB (cap 65 536, bo = 16 -> 10) takes 40 000 | 8 000 + 8 000; 7 outer indices are not packed
+    a = capped;
+    a.n_outer = 10;
+    a.budget_kb = 0;
+    expect(a, true, {{0, 10, 0, 3, 56000}});
+    a.budget_kb = 16;
+    expect(a, true, {{0, 10, 0, 1, 40000}, {0, 10, 1, 2, 16000}});
+    a.n_outer = 7;
+    expect(a, false, {{0, 7, 0, 3, 0}});
+    // n_inner = 2: a packed chunk needs 16 outer indices.  The widest level is 8 000 B per outer index, cap / that = 32
+    // -> 20: 160 000 | 32 000 + 32 000.  Free memory for 16 (per outer index 8 000 + 2 * 50 * 8): blocks of 16
+    // (128 000 | 25 600 + 25 600) and 4 (32 000 + 6 400 + 6 400 = 44 800, all three levels); for 15: whole rows
+    a = capped;
+    a.n_outer = 20;
+    a.n_inner = 2;
+    expect(a, true, {{0, 20, 0, 1, 160000}, {0, 20, 1, 2, 64000}});
+    a.free_bytes = 8 * 8800 * 16;
+    expect(a, true, {{0, 16, 0, 1, 128000}, {0, 16, 1, 2, 51200}, {16, 4, 0, 3, 44800}});
+    a.free_bytes = 8 * 8800 * 15;
+    expect(a, false, {{0, 20, 0, 3, 0}});
+    // config 3's sizes (120 steps x 75 levels of 1442 x 1021 -> 64 800 cells) with levels thinning from 10^6 used
+    // cells by 12 800 a level (39.5 M in all): 32 steps of all levels exceed 1 GiB, so level-major, and no chunk's
+    // packed X goes beyond the cap of four targets
+    {
+      Args c3{120, 75, 1, 1442 * 1021, 64800, 8, 8, {}, true, 0, 200 * GiB, 0};
+      for (int64_t l = 0; l < 75; ++l) c3.used.push_back(1000000 - 12800 * l);
+      const smm::GroupChunkPlan p = plan_of(c3);
+      if (!p.pack || p.chunks.size() <= 1) ++gbad;
+      for (const smm::GroupChunk& c : p.chunks) gbad += c.x_bytes > 4 * 256 * MiB;
+    }
+    printf("GCHUNKBAD %lld\n", gbad);
+  }
   // exact-zero links dropped: what is left is the same matrix without its zeros
   {
     long long pbad = 0;

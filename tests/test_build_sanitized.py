@@ -100,6 +100,7 @@ def test_builder_under_sanitizers(harness, rng, case, threads):
     # a throwing worker task surfaces on the caller (no std::terminate), unstartable threads only cost parallelism
     assert fault[1] == "0" and (int(fault[2]) > 0 or threads == 1)
     assert "CHUNKBAD 0" in lines            # host pipelines size their chunks from X AND Y bytes (U << D)
+    assert "GCHUNKBAD 0" in lines           # chunk plan of smm_group_apply_host: outer blocks or level-major, by hand
     prune = [ln.split() for ln in lines if ln.startswith("PRUNEBAD")][0]
     assert prune[1] == "0" and int(prune[2]) == int((val == 0.0).sum())     # exact-zero links dropped, rest intact
     check_pool_line(lines)
@@ -127,6 +128,7 @@ def test_staging_pool_under_thread_sanitizer(rng, tmp_path):
                          env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1 exitcode=66"))
     assert out.returncode == 0, out.stderr[-3000:]
     assert "ThreadSanitizer" not in out.stderr
+    assert "GCHUNKBAD 0" in out.stdout.splitlines()
     check_pool_line(out.stdout.splitlines())
 
 
