@@ -36,8 +36,12 @@
 #include "../../include/smmregrid_amd.h"
 #include "smm_internal.h"
 #include "smm_built.hpp"
+#include "smm_devmem.hpp"
 
 #pragma clang fp contract(off)
+
+using smm::DeviceBuf;   // every HBM / page-locked block the library owns (smm_devmem.hpp)
+using smm::PinnedBuf;
 
 namespace {
 
@@ -153,11 +157,8 @@ namespace {
 // two pinned X/Y staging buffers, grown on demand.
 struct HostPipe {
   hipStream_t stream[2] = {nullptr, nullptr};
-  void* dx[2] = {nullptr, nullptr};
-  void* dy[2] = {nullptr, nullptr};
-  void* hx[2] = {nullptr, nullptr};
-  void* hy[2] = {nullptr, nullptr};
-  size_t cap_dx = 0, cap_dy = 0, cap_hx = 0, cap_hy = 0;
+  DeviceBuf<char> dx[2], dy[2];
+  PinnedBuf hx[2], hy[2];
   // per buffer: before the H2D, after it, after the kernel(s), after the D2H -- the stage times of a chunk
   // (smm_debug_host_stats) are read from them once the chunk has been drained
   hipEvent_t ev[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
@@ -168,28 +169,15 @@ struct HostPipe {
     for (int i = 0; i < 2; ++i)
       for (int k = 0; k < 4 && e == hipSuccess; ++k)
         if (!ev[i][k]) e = hipEventCreate(&ev[i][k]);
-    auto grow_dev = [&](void* (&buf)[2], size_t& cap, size_t need) {
-      if (need <= cap || e != hipSuccess) return;
-      for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        (void)hipFree(buf[i]);
-        buf[i] = nullptr;
-        e = hipMalloc(&buf[i], need);
-      }
-      cap = e == hipSuccess ? need : 0;
+    // a pair's capacity is that of its smaller buffer: zero after a failed allocation (alloc frees first)
+    auto grow = [&](auto(&buf)[2], size_t need) {
+      if (need <= std::min(buf[0].bytes(), buf[1].bytes())) return;
+      for (int i = 0; i < 2 && e == hipSuccess; ++i) e = buf[i].alloc(need);
     };
-    auto grow_host = [&](void* (&buf)[2], size_t& cap, size_t need) {
-      if (need <= cap || e != hipSuccess) return;
-      for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        if (buf[i]) (void)hipHostFree(buf[i]);
-        buf[i] = nullptr;
-        e = hipHostMalloc(&buf[i], need, hipHostMallocDefault);
-      }
-      cap = e == hipSuccess ? need : 0;
-    };
-    grow_dev(dx, cap_dx, need_dx);
-    grow_dev(dy, cap_dy, need_dy);
-    grow_host(hx, cap_hx, need_hx);
-    grow_host(hy, cap_hy, need_hy);
+    grow(dx, need_dx);
+    grow(dy, need_dy);
+    grow(hx, need_hx);
+    grow(hy, need_hy);
     return e;
   }
   hipError_t mark(int b, int k) { return hipEventRecord(ev[b][k], stream[b]); }   // stage boundary k of buffer b
@@ -205,10 +193,6 @@ struct HostPipe {
       if (stream[i]) (void)hipStreamDestroy(stream[i]);
       for (int k = 0; k < 4; ++k)
         if (ev[i][k]) (void)hipEventDestroy(ev[i][k]);
-      (void)hipFree(dx[i]);
-      (void)hipFree(dy[i]);
-      if (hx[i]) (void)hipHostFree(hx[i]);
-      if (hy[i]) (void)hipHostFree(hy[i]);
     }
   }
 };
@@ -225,12 +209,12 @@ struct smm_operator {
   smm::HostCsr csr;          // canonical: row = destination cell
   int64_t pruned_links = 0;  // exact-zero links dropped at create time (SMM_CREATE_PRUNE_ZEROS)
   int64_t n_slices = 0, n_slots = 0;
-  int64_t* d_slice_off = nullptr;
-  int32_t* d_col = nullptr;
-  double* d_val = nullptr;
-  int32_t* d_rowlen = nullptr;
-  uint8_t* d_imask = nullptr;
-  double* d_frac = nullptr;
+  DeviceBuf<int64_t> d_slice_off;
+  DeviceBuf<int32_t> d_col;
+  DeviceBuf<double> d_val;
+  DeviceBuf<int32_t> d_rowlen;
+  DeviceBuf<uint8_t> d_imask;
+  DeviceBuf<double> d_frac;
   // LDS tile plans by block shape: [0] = 4 slices (256 rows) per block, [1] = 1 slice (heavy rows),
   // [2..4] = 32 / 16 / 8 rows of a slice (rows so long -- high-resolution source, coarse target --
   // that a whole slice's footprint exceeds the LDS budget).  The operator's own shape is built at
@@ -240,10 +224,10 @@ struct smm_operator {
     int64_t max_chunks = 0, total_chunks = 0, total_lines = 0;
     bool preferred = false;  // staged lines are used well enough to beat direct gathers
     bool reuse = false;      // some staged lines are shared by several blocks (keep them cacheable)
-    int64_t* d_blk_chunk_off = nullptr;
-    int32_t* d_chunk_src = nullptr;
-    int32_t* d_lcol = nullptr;
-    uint8_t* d_blk_direct = nullptr;
+    DeviceBuf<int64_t> d_blk_chunk_off;
+    DeviceBuf<int32_t> d_chunk_src;
+    DeviceBuf<int32_t> d_lcol;
+    DeviceBuf<uint8_t> d_blk_direct;
   } plan[kNumShapes];
   smm::HostSell sell_shape;  // slice_off / rowlen only (col/val dropped after upload)
   std::mutex plan_mu;
@@ -252,26 +236,26 @@ struct smm_operator {
   // plain canonical CSR on the device for the batch-fastest kernel, uploaded on first use
   bool sb_ready = false;
   std::vector<int32_t> h_used;        // ascending used source cells (host pack of the pipeline)
-  int64_t* d_csr_rowptr = nullptr;
-  int32_t* d_csr_col = nullptr;       // source cell
-  int32_t* d_csr_colp = nullptr;      // rank of the source cell among the used cells (packed X)
-  double* d_csr_val = nullptr;
+  DeviceBuf<int64_t> d_csr_rowptr;
+  DeviceBuf<int32_t> d_csr_col;       // source cell
+  DeviceBuf<int32_t> d_csr_colp;      // rank of the source cell among the used cells (packed X)
+  DeviceBuf<double> d_csr_val;
   std::atomic<int> group_refs{0};  // groups borrowing this operator (their descriptors hold its device pointers)
   int native = 0;            // shape of the operator's own plan (choose_native_plan)
   int native_plan() const { return native; }
-  LevelDesc* d_desc = nullptr;  // one-element device copy (native plan)
+  DeviceBuf<LevelDesc> d_desc;  // one-element device copy (native plan)
   LevelDesc desc(int which) const {
     LevelDesc L;
-    L.slice_off = d_slice_off;
-    L.col = d_col;
-    L.val = d_val;
-    L.rowlen = d_rowlen;
-    L.imask = d_imask;
-    L.frac = d_frac;
-    L.blk_chunk_off = plan[which].d_blk_chunk_off;
-    L.chunk_src = plan[which].d_chunk_src;
-    L.lcol = plan[which].d_lcol;
-    L.blk_direct = plan[which].d_blk_direct;
+    L.slice_off = d_slice_off.get();
+    L.col = d_col.get();
+    L.val = d_val.get();
+    L.rowlen = d_rowlen.get();
+    L.imask = d_imask.get();
+    L.frac = d_frac.get();
+    L.blk_chunk_off = plan[which].d_blk_chunk_off.get();
+    L.chunk_src = plan[which].d_chunk_src.get();
+    L.lcol = plan[which].d_lcol.get();
+    L.blk_direct = plan[which].d_blk_direct.get();
     return L;
   }
 };
@@ -279,7 +263,7 @@ struct smm_operator {
 struct smm_group {
   int device = -1;
   std::vector<smm_operator_t> ops;
-  LevelDesc* d_descs = nullptr;
+  DeviceBuf<LevelDesc> d_descs;
   int tile_which = 0;  // plan shape shared by all members
   bool tile_valid = false;
   bool tile_preferred = false;
@@ -290,7 +274,7 @@ struct smm_group {
   // smm_group_destroy: a kernel enqueued by another thread may still read it, so nothing is ever
   // evicted (an entry is n_lev * 4 + n_ops bytes; callers cycle through a few level subsets).
   std::mutex mu;
-  std::map<std::string, void*> cfg_cache;
+  std::map<std::string, DeviceBuf<char>> cfg_cache;
   std::mutex pipe_mu;  // smm_group_apply_host calls on one group take turns
   HostPipe pipe;
 };
@@ -298,11 +282,8 @@ struct smm_group {
 namespace {
 
 template <typename T>
-int upload(T** dptr, const std::vector<T>& h) {
-  *dptr = nullptr;
-  const size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
-  SMM_HIP(hipMalloc((void**)dptr, bytes));
-  if (!h.empty()) SMM_HIP(hipMemcpy(*dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+int upload(DeviceBuf<T>& buf, const std::vector<T>& h) {   // buf is empty after a failure
+  SMM_HIP(buf.upload(h));
   return SMM_OK;
 }
 
@@ -327,34 +308,12 @@ struct DeviceGuard {
 
 int refresh_desc(smm_operator* op) {
   const LevelDesc L = op->desc(op->native_plan());
-  if (!op->d_desc) SMM_HIP(hipMalloc((void**)&op->d_desc, sizeof(LevelDesc)));
-  SMM_HIP(hipMemcpy(op->d_desc, &L, sizeof(LevelDesc), hipMemcpyHostToDevice));
+  if (!op->d_desc.get()) SMM_HIP(op->d_desc.alloc(1));
+  SMM_HIP(hipMemcpy(op->d_desc.get(), &L, sizeof(LevelDesc), hipMemcpyHostToDevice));
   return SMM_OK;
 }
 
-void release(smm_operator* op) {
-  if (!op) return;
-  (void)hipFree(op->d_slice_off);
-  (void)hipFree(op->d_col);
-  (void)hipFree(op->d_val);
-  (void)hipFree(op->d_rowlen);
-  (void)hipFree(op->d_imask);
-  (void)hipFree(op->d_frac);
-  for (auto& pl : op->plan) {
-    (void)hipFree(pl.d_blk_chunk_off);
-    (void)hipFree(pl.d_chunk_src);
-    (void)hipFree(pl.d_lcol);
-    (void)hipFree(pl.d_blk_direct);
-  }
-  (void)hipFree(op->d_desc);
-  (void)hipFree(op->d_csr_rowptr);
-  (void)hipFree(op->d_csr_col);
-  (void)hipFree(op->d_csr_colp);
-  (void)hipFree(op->d_csr_val);
-  delete op;
-}
-
-// Build and upload tile plan `which` of the operator if it does not exist yet.
+// Build and upload tile plan `which` of the operator if it does not exist yet (a failed upload: built, not valid, empty).
 int ensure_plan(smm_operator* op, int which) {
   std::lock_guard<std::mutex> lock(op->plan_mu);
   smm_operator::TilePlan& pl = op->plan[which];
@@ -367,20 +326,22 @@ int ensure_plan(smm_operator* op, int which) {
   smm::tighten_tile_plan(op->csr, hp, budget);
   pl.built = true;
   if (!hp.valid) return SMM_OK;
+  smm_operator::TilePlan up;   // filled here, moved into the handle once every upload has succeeded
   int rc = SMM_OK;
-  if ((rc = upload(&pl.d_blk_chunk_off, hp.blk_chunk_off)) || (rc = upload(&pl.d_chunk_src, hp.chunk_src)) ||
-      (rc = upload(&pl.d_lcol, hp.lcol)) || (rc = upload(&pl.d_blk_direct, hp.blk_direct)))
+  if ((rc = upload(up.d_blk_chunk_off, hp.blk_chunk_off)) || (rc = upload(up.d_chunk_src, hp.chunk_src)) ||
+      (rc = upload(up.d_lcol, hp.lcol)) || (rc = upload(up.d_blk_direct, hp.blk_direct)))
     return rc;
-  pl.valid = true;
-  pl.max_chunks = hp.max_block_chunks;
-  pl.total_chunks = hp.total_chunks;
-  pl.total_lines = hp.total_lines;
-  pl.reuse = hp.total_chunks * 50 > hp.distinct_chunks * 51;  // > 2 % of lines staged twice
+  up.built = up.valid = true;
+  up.max_chunks = hp.max_block_chunks;
+  up.total_chunks = hp.total_chunks;
+  up.total_lines = hp.total_lines;
+  up.reuse = hp.total_chunks * 50 > hp.distinct_chunks * 51;  // > 2 % of lines staged twice
   // at least a tenth of every staged 128-B line is consumed: the lines are the ones a gather would
   // fetch anyway, and staging fetches them coalesced (r3600x1800 -> r360x180 bilinear uses 20 %:
   // tile 0.48 ms, SELL 0.64 ms; HEALPix-nested source, nearest neighbour, 14 %: 1.87 vs 2.10 ms;
   // r3600x1800 nearest neighbour, 10 %: equal)
-  pl.preferred = hp.total_distinct * 10 >= hp.total_lines * 16;
+  up.preferred = hp.total_distinct * 10 >= hp.total_lines * 16;
+  pl = std::move(up);
   return SMM_OK;
 }
 
@@ -406,18 +367,17 @@ int ensure_sb(smm_operator* op) {
   op->h_used.reserve((size_t)c.n_used_src);
   for (int64_t s = 0; s < c.n_src; ++s)
     if (rank[(size_t)s] >= 0) op->h_used.push_back((int32_t)s);
+  DeviceBuf<int64_t> rowptr;
+  DeviceBuf<int32_t> col, colp_d;
+  DeviceBuf<double> val;
   int rc = SMM_OK;
-  if ((rc = upload(&op->d_csr_rowptr, c.rowptr)) || (rc = upload(&op->d_csr_col, c.col)) ||
-      (rc = upload(&op->d_csr_colp, colp)) || (rc = upload(&op->d_csr_val, c.val))) {
-    (void)hipFree(op->d_csr_rowptr);
-    (void)hipFree(op->d_csr_col);
-    (void)hipFree(op->d_csr_colp);
-    (void)hipFree(op->d_csr_val);
-    op->d_csr_rowptr = nullptr;
-    op->d_csr_col = op->d_csr_colp = nullptr;
-    op->d_csr_val = nullptr;
-    return rc;
-  }
+  if ((rc = upload(rowptr, c.rowptr)) || (rc = upload(col, c.col)) || (rc = upload(colp_d, colp)) ||
+      (rc = upload(val, c.val)))
+    return rc;   // the handle holds none of the four
+  op->d_csr_rowptr = std::move(rowptr);
+  op->d_csr_col = std::move(col);
+  op->d_csr_colp = std::move(colp_d);
+  op->d_csr_val = std::move(val);
   op->sb_ready = true;
   return SMM_OK;
 }
@@ -444,11 +404,11 @@ struct ApplyTarget {
 ApplyTarget target_of(const smm_operator* op) {
   const int pw = op->native_plan();
   const smm_operator::TilePlan& pl = op->plan[pw];
-  return {op->d_desc, op->csr.n_src, op->csr.n_dst, pw, pl.valid, pl.preferred, pl.reuse ? 1 : 0, pl.max_chunks,
+  return {op->d_desc.get(), op->csr.n_src, op->csr.n_dst, pw, pl.valid, pl.preferred, pl.reuse ? 1 : 0, pl.max_chunks,
           op->csr.max_row_nnz};
 }
 ApplyTarget target_of(const smm_group* g) {
-  return {g->d_descs, g->ops[0]->csr.n_src, g->ops[0]->csr.n_dst, g->tile_which, g->tile_valid, g->tile_preferred,
+  return {g->d_descs.get(), g->ops[0]->csr.n_src, g->ops[0]->csr.n_dst, g->tile_which, g->tile_valid, g->tile_preferred,
           g->tile_reuse ? 1 : 0, g->tile_max_chunks, g->max_row_nnz};
 }
 
@@ -737,9 +697,9 @@ inline int check_flags(unsigned flags) {
 // ---- what an apply refuses about its epilogue and its levels, written once for every entry (check_area_min is with
 // check_x_dtype).  what: "the operator" or "a level"
 inline int check_epilogue(const smm_operator* op, bool masked, double area_min, const char* what) {
-  if (masked && !op->d_imask)
+  if (masked && !op->d_imask.get())
     return fail(SMM_ERR_INVALID, std::string("masked apply requested but ") + what + " has no dst_imask");
-  if (area_min > 0.0 && !op->d_frac)
+  if (area_min > 0.0 && !op->d_frac.get())
     return fail(SMM_ERR_INVALID, std::string("remap_area_min > 0 requested but ") + what + " has no dst_frac");
   return SMM_OK;
 }
@@ -1007,33 +967,26 @@ static int create_operator(int device, smm_operator_t* out, F fill_csr, unsigned
   if (device < 0 || device >= ndev)
     return fail(SMM_ERR_NO_DEVICE, "device ordinal " + std::to_string(device) + " out of range");
 
-  smm_operator* op = new (std::nothrow) smm_operator();
-  if (!op) return fail(SMM_ERR_ALLOC, "out of host memory");
+  std::unique_ptr<smm_operator> owner(new (std::nothrow) smm_operator());   // freed on every early return and throw
+  if (!owner) return fail(SMM_ERR_ALLOC, "out of host memory");
+  smm_operator* op = owner.get();
   op->device = device;
   try {
     std::string err;
-    if (!fill_csr(op->csr, err)) {
-      delete op;
-      return fail(SMM_ERR_INVALID, err);
-    }
+    if (!fill_csr(op->csr, err)) return fail(SMM_ERR_INVALID, err);
     if (options & SMM_CREATE_PRUNE_ZEROS) op->pruned_links = smm::prune_zero_links(op->csr);
     const smm::HostCsr& kc = op->csr;
     smm::HostSell sell;
     smm::build_sell(kc, sell);
 
     DeviceGuard guard(device);
-    if (!guard.ok) {
-      delete op;
-      return fail(SMM_ERR_HIP, "cannot select device " + std::to_string(device));
-    }
+    if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select device " + std::to_string(device));
     op->n_slices = sell.n_slices;
     op->n_slots = sell.n_slots;
     int rc = SMM_OK;
-    if ((rc = upload(&op->d_slice_off, sell.slice_off)) || (rc = upload(&op->d_col, sell.col)) ||
-        (rc = upload(&op->d_val, sell.val)) || (rc = upload(&op->d_rowlen, sell.rowlen))) {
-      release(op);
+    if ((rc = upload(op->d_slice_off, sell.slice_off)) || (rc = upload(op->d_col, sell.col)) ||
+        (rc = upload(op->d_val, sell.val)) || (rc = upload(op->d_rowlen, sell.rowlen)))
       return rc;
-    }
     op->sell_shape.n_slices = sell.n_slices;
     op->sell_shape.n_slots = sell.n_slots;
     op->sell_shape.slice_off = std::move(sell.slice_off);
@@ -1041,10 +994,7 @@ static int create_operator(int device, smm_operator_t* out, F fill_csr, unsigned
     // own block shape: 256 rows for rows of <= 16 links; else one slice, or the largest part of a
     // slice whose footprint fits the LDS budget and is used well enough (plan valid and preferred)
     op->native = kc.max_row_nnz > 16 ? 1 : 0;
-    if ((rc = ensure_plan(op, op->native))) {
-      release(op);
-      return rc;
-    }
+    if ((rc = ensure_plan(op, op->native))) return rc;
     if (op->native == 1) {
       // rows beyond 48 links: start at the shape whose lane groups can keep the whole row in
       // registers (split rows) -- streaming the links from L2 is ~2x slower; else from one slice
@@ -1053,41 +1003,25 @@ static int create_operator(int device, smm_operator_t* out, F fill_csr, unsigned
       bool found = false;
       for (int pass = 0; pass < 2 && !found; ++pass) {
         for (int w = pass == 0 ? w_first : 1; w < (pass == 0 ? kNumShapes : w_first) && !found; ++w) {
-          if ((rc = ensure_plan(op, w))) {
-            release(op);
-            return rc;
-          }
+          if ((rc = ensure_plan(op, w))) return rc;
           if (op->plan[w].valid && op->plan[w].preferred) {
             op->native = w;
             found = true;
           }
         }
       }
-      for (int w = 1; w < kNumShapes; ++w) {   // plans tried on the way are rebuilt on demand
-        if (w == op->native) continue;
-        smm_operator::TilePlan& pl = op->plan[w];
-        (void)hipFree(pl.d_blk_chunk_off);
-        (void)hipFree(pl.d_chunk_src);
-        (void)hipFree(pl.d_lcol);
-        (void)hipFree(pl.d_blk_direct);
-        pl = smm_operator::TilePlan();
-      }
+      for (int w = 1; w < kNumShapes; ++w)   // plans tried on the way are rebuilt on demand
+        if (w != op->native) op->plan[w] = smm_operator::TilePlan();
     }
-    if ((rc = refresh_desc(op))) {
-      release(op);
-      return rc;
-    }
+    if ((rc = refresh_desc(op))) return rc;
   } catch (const std::bad_alloc&) {
-    release(op);
     return fail(SMM_ERR_ALLOC, "out of host memory while building the operator");
   } catch (const std::exception& e) {   // nothing may cross the extern "C" boundary
-    release(op);
     return fail(SMM_ERR_INTERNAL, std::string("operator build failed: ") + e.what());
   } catch (...) {
-    release(op);
     return fail(SMM_ERR_INTERNAL, "operator build failed");
   }
-  *out = op;
+  *out = owner.release();
   return SMM_OK;
 }
 }  // extern "C++"
@@ -1120,7 +1054,7 @@ int smm_operator_destroy(smm_operator_t op) {
   if (op->group_refs.load() > 0)
     return fail(SMM_ERR_INVALID, "operator still belongs to a group: destroy the group first");
   DeviceGuard guard(op->device);
-  release(op);
+  delete op;   // also when the device could not be selected
   return SMM_OK;
 }
 
@@ -1152,44 +1086,27 @@ static int smm_operator_set_epilogue_impl(smm_operator_t op, const int32_t* dst_
   DeviceGuard guard(op->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
   const size_t n = (size_t)op->csr.n_dst;
-  // upload the new vectors first: on failure the operator keeps its old state untouched
-  uint8_t* new_imask = nullptr;
-  double* new_frac = nullptr;
-  auto drop_new = [&]() {
-    (void)hipFree(new_imask);
-    (void)hipFree(new_frac);
-  };
+  // upload the new vectors first: on failure the operator keeps its old state untouched.  The two locals hold the new
+  // vectors, after the swap the old ones, and free whichever pair the operator does not keep (imask, then frac)
+  DeviceBuf<double> frac;
+  DeviceBuf<uint8_t> imask;
   if (dst_imask) {
     std::vector<uint8_t> m(n);
     for (size_t i = 0; i < n; ++i) m[i] = dst_imask[i] != 0;  // .astype(bool), regrid.py:557
-    int rc = upload(&new_imask, m);
-    if (rc) {
-      drop_new();
-      return rc;
-    }
+    if (int rc = upload(imask, m)) return rc;
   }
   if (dst_frac) {
     std::vector<double> f(dst_frac, dst_frac + n);
-    int rc = upload(&new_frac, f);
-    if (rc) {
-      drop_new();
-      return rc;
-    }
+    if (int rc = upload(frac, f)) return rc;
   }
-  uint8_t* old_imask = op->d_imask;
-  double* old_frac = op->d_frac;
-  op->d_imask = new_imask;
-  op->d_frac = new_frac;
+  std::swap(op->d_imask, imask);
+  std::swap(op->d_frac, frac);
   int rc = refresh_desc(op);
   if (rc) {  // the device descriptor still names the old vectors: keep them
-    op->d_imask = old_imask;
-    op->d_frac = old_frac;
-    drop_new();
-    return rc;
+    std::swap(op->d_imask, imask);
+    std::swap(op->d_frac, frac);
   }
-  (void)hipFree(old_imask);
-  (void)hipFree(old_frac);
-  return SMM_OK;
+  return rc;
 }
 
 static int smm_operator_plan_info_impl(smm_operator_t op, int* kernel_kind, int64_t* lds_bytes,
@@ -1254,11 +1171,11 @@ static int smm_apply_sb_impl(smm_operator_t op, const void* x, int64_t ldx, void
   int rc = ensure_sb(op);   // first call uploads the CSR (smm_operator_prepare_sb does it ahead of time)
   if (rc) return rc;
   SbArgs a{};
-  a.rowptr = op->d_csr_rowptr;
-  a.col = (flags & SMM_APPLY_SB_PACKED) ? op->d_csr_colp : op->d_csr_col;
-  a.val = op->d_csr_val;
-  a.imask = op->d_imask;
-  a.frac = op->d_frac;
+  a.rowptr = op->d_csr_rowptr.get();
+  a.col = (flags & SMM_APPLY_SB_PACKED) ? op->d_csr_colp.get() : op->d_csr_col.get();
+  a.val = op->d_csr_val.get();
+  a.imask = op->d_imask.get();
+  a.frac = op->d_frac.get();
   a.x = x;
   a.y = y;
   a.ldx = ldx;
@@ -1353,9 +1270,9 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int64_t ld
     if (y_direct) return SMM_OK;
     StageTimer t(st.v[SMM_HOST_STAT_COPY_OUT_MS]);
     const int64_t r0 = c * chunk_rows, rows = std::min(chunk_rows, n_batch - r0);
-    if ((int64_t)ldy == D) return host_copy((char*)y_host + (size_t)r0 * yrow, pipe.hy[b], (size_t)rows * D * ysz);
+    if (ldy == D) return host_copy((char*)y_host + (size_t)r0 * yrow, pipe.hy[b].get(), (size_t)rows * D * ysz);
     for (int64_t r = 0; r < rows; ++r)
-      memcpy((char*)y_host + (size_t)(r0 + r) * yrow, (char*)pipe.hy[b] + (size_t)r * D * ysz, (size_t)D * ysz);
+      memcpy((char*)y_host + (size_t)(r0 + r) * yrow, (char*)pipe.hy[b].get() + (size_t)r * D * ysz, (size_t)D * ysz);
     return SMM_OK;
   };
   auto launch = [&](int64_t c, int b) -> int {
@@ -1364,49 +1281,50 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int64_t ld
     if (pack) {
       {
         StageTimer t(st.v[SMM_HOST_STAT_STAGE_IN_MS]);
-        int rc = host_pack(pipe.hx[b], xsrc, xsz, ldx, op->h_used, rows);
+        int rc = host_pack(pipe.hx[b].get(), xsrc, xsz, ldx, op->h_used, rows);
         if (rc) return rc;
       }
       SMM_HIP(pipe.mark(b, 0));
-      SMM_HIP(hipMemcpyAsync(pipe.dx[b], pipe.hx[b], (size_t)U * rows * xsz, hipMemcpyHostToDevice, pipe.stream[b]));
+      SMM_HIP(hipMemcpyAsync(pipe.dx[b].get(), pipe.hx[b].get(), (size_t)U * rows * xsz, hipMemcpyHostToDevice,
+                             pipe.stream[b]));
       st.v[SMM_HOST_STAT_H2D_BYTES] += (double)((size_t)U * rows * xsz);
     } else if (!x_direct) {
       {
         StageTimer t(st.v[SMM_HOST_STAT_STAGE_IN_MS]);
         if (ldx == S) {
-          int rc = host_copy(pipe.hx[b], xsrc, (size_t)rows * S * xsz);
+          int rc = host_copy(pipe.hx[b].get(), xsrc, (size_t)rows * S * xsz);
           if (rc) return rc;
         } else {
           for (int64_t r = 0; r < rows; ++r)
-            memcpy((char*)pipe.hx[b] + (size_t)r * S * xsz, xsrc + (size_t)r * xrow, (size_t)S * xsz);
+            memcpy((char*)pipe.hx[b].get() + (size_t)r * S * xsz, xsrc + (size_t)r * xrow, (size_t)S * xsz);
         }
       }
       SMM_HIP(pipe.mark(b, 0));
-      SMM_HIP(hipMemcpy2DAsync(pipe.dx[b], xrow_d, pipe.hx[b], (size_t)S * xsz, (size_t)S * xsz,
+      SMM_HIP(hipMemcpy2DAsync(pipe.dx[b].get(), xrow_d, pipe.hx[b].get(), (size_t)S * xsz, (size_t)S * xsz,
                                (size_t)rows, hipMemcpyHostToDevice, pipe.stream[b]));
     } else {
       SMM_HIP(pipe.mark(b, 0));
-      SMM_HIP(hipMemcpy2DAsync(pipe.dx[b], xrow_d, xsrc, xrow, (size_t)S * xsz, (size_t)rows,
+      SMM_HIP(hipMemcpy2DAsync(pipe.dx[b].get(), xrow_d, xsrc, xrow, (size_t)S * xsz, (size_t)rows,
                                hipMemcpyHostToDevice, pipe.stream[b]));
     }
     if (!pack) st.v[SMM_HOST_STAT_H2D_BYTES] += (double)((size_t)S * rows * xsz);
     SMM_HIP(pipe.mark(b, 1));
     int rc = SMM_OK;
     if (pack)
-      rc = smm_apply_sb_impl(op, pipe.dx[b], rows, pipe.dy[b], D, rows, pipe.stream[b],
+      rc = smm_apply_sb_impl(op, pipe.dx[b].get(), rows, pipe.dy[b].get(), D, rows, pipe.stream[b],
                              call.with_flags((flags & (SMM_APPLY_MASKED | SMM_APPLY_NO_FILL | SMM_APPLY_SKIPNA)) |
                                              SMM_APPLY_SB_PACKED));
     else
-      rc = run_apply(target_of(op), nullptr, nullptr, pipe.dx[b], ldx_d, 0, 0, pipe.dy[b], D, 0, 0, rows, 1, 1, call,
-                     pipe.stream[b]);
+      rc = run_apply(target_of(op), nullptr, nullptr, pipe.dx[b].get(), ldx_d, 0, 0, pipe.dy[b].get(), D, 0, 0, rows, 1, 1,
+                     call, pipe.stream[b]);
     if (rc) return rc;
     st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)rows * D * ysz);
     SMM_HIP(pipe.mark(b, 2));
     if (!y_direct) {
-      SMM_HIP(hipMemcpyAsync(pipe.hy[b], pipe.dy[b], (size_t)rows * D * ysz, hipMemcpyDeviceToHost,
+      SMM_HIP(hipMemcpyAsync(pipe.hy[b].get(), pipe.dy[b].get(), (size_t)rows * D * ysz, hipMemcpyDeviceToHost,
                              pipe.stream[b]));
     } else {
-      SMM_HIP(hipMemcpy2DAsync((char*)y_host + (size_t)r0 * yrow, yrow, pipe.dy[b], (size_t)D * ysz,
+      SMM_HIP(hipMemcpy2DAsync((char*)y_host + (size_t)r0 * yrow, yrow, pipe.dy[b].get(), (size_t)D * ysz,
                                (size_t)D * ysz, (size_t)rows, hipMemcpyDeviceToHost, pipe.stream[b]));
     }
     SMM_HIP(pipe.mark(b, 3));
@@ -1424,39 +1342,25 @@ static int smm_operator_mask_apply_impl(smm_operator_t op, const int32_t* src_im
   // int32 mask promoted to f64 for the product (weights.py:50)
   std::vector<double> xs((size_t)std::max<int64_t>(S, 1));
   for (int64_t i = 0; i < S; ++i) xs[(size_t)i] = (double)src_imask[i];
-  double *dx = nullptr, *dy = nullptr;
-  int32_t* dm = nullptr;
-  int rc = SMM_OK;
-  auto cleanup = [&]() {
-    (void)hipFree(dx);
-    (void)hipFree(dy);
-    (void)hipFree(dm);
-  };
-  if (hipMalloc((void**)&dx, xs.size() * 8) != hipSuccess ||
-      hipMalloc((void**)&dy, (size_t)D * 8) != hipSuccess ||
-      hipMalloc((void**)&dm, (size_t)D * 4) != hipSuccess) {
-    cleanup();
-    (void)hipGetLastError();
-    return fail(SMM_ERR_HIP, "hipMalloc failed in smm_operator_mask_apply");
-  }
-  if (hipMemcpy(dx, xs.data(), xs.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-    cleanup();
+  DeviceBuf<int32_t> dm;   // freed on every return, in the order dx, dy, dm
+  DeviceBuf<double> dy, dx;
+  if (dx.alloc(xs.size()) != hipSuccess || dy.alloc((size_t)D) != hipSuccess || dm.alloc((size_t)D) != hipSuccess)
+    return fail(SMM_ERR_HIP, "device allocation failed in smm_operator_mask_apply");
+  if (hipMemcpy(dx.get(), xs.data(), xs.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
     return fail(SMM_ERR_HIP, "hipMemcpy failed in smm_operator_mask_apply");
-  }
   ApplyTarget sell_only = target_of(op);   // one row: kernel A whatever the plan
   sell_only.tile_ok = false;
-  rc = run_apply(sell_only, nullptr, nullptr, dx, std::max<int64_t>(S, 1), 0, 0, dy, D, 0, 0, 1, 1, 1,
-                 CallDesc{SMM_F64, SMM_F64, SMM_APPLY_NO_FILL, 0.0}, nullptr);
+  int rc = run_apply(sell_only, nullptr, nullptr, dx.get(), std::max<int64_t>(S, 1), 0, 0, dy.get(), D, 0, 0, 1, 1, 1,
+                     CallDesc{SMM_F64, SMM_F64, SMM_APPLY_NO_FILL, 0.0}, nullptr);
   if (rc == SMM_OK) {
     const int threads = 256;
     hipLaunchKernelGGL(smm_mask_threshold_kernel, dim3((unsigned)((D + threads - 1) / threads)),
-                       dim3(threads), 0, nullptr, dy, dm, D);
+                       dim3(threads), 0, nullptr, dy.get(), dm.get(), D);
     if (hipGetLastError() != hipSuccess ||
-        hipMemcpy(dst_imask, dm, (size_t)D * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+        hipMemcpy(dst_imask, dm.get(), (size_t)D * 4, hipMemcpyDeviceToHost) != hipSuccess) {
       rc = fail(SMM_ERR_HIP, "mask threshold kernel / copy failed");
     }
   }
-  cleanup();
   return rc;
 }
 
@@ -1498,7 +1402,7 @@ static int smm_group_create_impl(const smm_operator_t* ops, int n_ops, smm_group
     g->max_row_nnz = std::max(g->max_row_nnz, ops[i]->csr.max_row_nnz);
   }
   g->tile_preferred = 2 * nnz_pref >= nnz_all;
-  int rc = upload(&g->d_descs, descs);
+  int rc = upload(g->d_descs, descs);
   if (rc) return rc;
   for (int i = 0; i < n_ops; ++i) ops[i]->group_refs.fetch_add(1);
   *out = owner.release();
@@ -1515,8 +1419,6 @@ int smm_group_plan_info(smm_group_t g, int* kernel_kind, int* slices_per_block) 
 int smm_group_destroy(smm_group_t g) {
   if (!g) return SMM_OK;
   DeviceGuard guard(g->device);
-  for (auto& kv : g->cfg_cache) (void)hipFree(kv.second);
-  (void)hipFree(g->d_descs);
   for (smm_operator_t op : g->ops) op->group_refs.fetch_sub(1);
   delete g;
   return SMM_OK;
@@ -1541,31 +1443,27 @@ static int group_level_cfg(smm_group_t g, int64_t n_lev, const int32_t* level_in
   key.append((const char*)level_index, (size_t)n_lev * sizeof(int32_t));
   key.push_back(masked_levels ? 1 : 0);
   if (masked_levels) key.append((const char*)masked_levels, (size_t)n_ops);
-  void* d_cfg = nullptr;
+  const char* d_cfg = nullptr;
   const size_t map_bytes = ((size_t)n_lev * 4 + 15) & ~(size_t)15;
   {
     std::lock_guard<std::mutex> lock(g->mu);
     auto it = g->cfg_cache.find(key);
     if (it != g->cfg_cache.end()) {
-      d_cfg = it->second;
+      d_cfg = it->second.get();
     } else {
       // first sight of this configuration (smm_group_prepare does this ahead of time): one small
       // allocation + blocking copy, no device-wide synchronisation, nothing is ever evicted
       std::vector<char> buf(map_bytes + (size_t)n_ops, 0);
       memcpy(buf.data(), level_index, (size_t)n_lev * 4);
       if (masked_levels) memcpy(buf.data() + map_bytes, masked_levels, (size_t)n_ops);
-      SMM_HIP(hipMalloc(&d_cfg, buf.size()));
-      hipError_t e = hipMemcpy(d_cfg, buf.data(), buf.size(), hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        (void)hipFree(d_cfg);
-        (void)hipGetLastError();
-        return fail(SMM_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-      }
-      g->cfg_cache.emplace(std::move(key), d_cfg);
+      DeviceBuf<char> cfg;   // filled before it enters the map
+      SMM_HIP(cfg.upload(buf));
+      d_cfg = cfg.get();
+      g->cfg_cache.emplace(std::move(key), std::move(cfg));
     }
   }
   *d_map = (const int32_t*)d_cfg;
-  *d_masked = masked_levels ? (const uint8_t*)d_cfg + map_bytes : nullptr;
+  *d_masked = masked_levels ? (const uint8_t*)(d_cfg + map_bytes) : nullptr;
   return SMM_OK;
 }
 }  // extern "C++"
@@ -1668,8 +1566,8 @@ static int smm_group_apply_sb_impl(smm_group_t g, const void* x, int64_t xs_lev,
       for (int i = 0; i < a.n_lev; ++i) {
         const int w = level_index[l0 + i];
         const smm_operator* op = g->ops[(size_t)w];
-        a.lev[i] = SbLevelPtrs{op->d_csr_rowptr, op->d_csr_col, op->d_csr_val,
-                               level_masked(flags, masked_levels, w) ? op->d_imask : nullptr, op->d_frac};
+        a.lev[i] = SbLevelPtrs{op->d_csr_rowptr.get(), op->d_csr_col.get(), op->d_csr_val.get(),
+                               level_masked(flags, masked_levels, w) ? op->d_imask.get() : nullptr, op->d_frac.get()};
       }
       if (call.packed_x()) a.cf = call.cf;      // CF-packed: raw 2-byte slabs, one decode rule for every level
       if (call.has_enc) a.cfo = call.enc;       // one encode rule for every level
@@ -1836,7 +1734,7 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, void* y_
   auto deliver = [&](int64_t c, int b) -> int {
     if (y_direct) return SMM_OK;
     StageTimer t(st.v[SMM_HOST_STAT_COPY_OUT_MS]);
-    return y_to_host(chunks[(size_t)c], (const char*)pipe.hy[b], false, nullptr);
+    return y_to_host(chunks[(size_t)c], (const char*)pipe.hy[b].get(), false, nullptr);
   };
   auto launch = [&](int64_t c, int b) -> int {
     const GChunk& ck = chunks[(size_t)c];
@@ -1850,14 +1748,14 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, void* y_
         StageTimer t(st.v[SMM_HOST_STAT_STAGE_IN_MS]);
         for (int64_t l = ck.l0; l < ck.l0 + ck.nl; ++l) {
           smm_operator* op = g->ops[(size_t)level_index[l]];
-          int hrc = host_pack((char*)pipe.hx[b] + off, xsrc + (size_t)l * n_inner * S * xsz, xsz, n_inner,
+          int hrc = host_pack((char*)pipe.hx[b].get() + off, xsrc + (size_t)l * n_inner * S * xsz, xsz, n_inner,
                               rows_per_outer * S, S, op->h_used, bc);
           if (hrc) return hrc;
           off += (size_t)op->csr.n_used_src * bc * xsz;
         }
       }
       SMM_HIP(pipe.mark(b, 0));
-      SMM_HIP(hipMemcpyAsync(pipe.dx[b], pipe.hx[b], off, hipMemcpyHostToDevice, pipe.stream[b]));
+      SMM_HIP(hipMemcpyAsync(pipe.dx[b].get(), pipe.hx[b].get(), off, hipMemcpyHostToDevice, pipe.stream[b]));
       st.v[SMM_HOST_STAT_H2D_BYTES] += (double)off;
       SMM_HIP(pipe.mark(b, 1));
       off = 0;
@@ -1867,8 +1765,8 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, void* y_
         unsigned fl = (flags & (SMM_APPLY_NO_FILL | SMM_APPLY_SKIPNA)) | SMM_APPLY_SB_PACKED;
         if (level_masked(flags, masked_levels, w)) fl |= SMM_APPLY_MASKED;
         // Y of the chunk: entry (b, ll, d) at (b * nl + ll) * D + d when transpose, at (ll * bc + b) * D + d else
-        rc = smm_apply_sb_impl(op, (char*)pipe.dx[b] + off, bc,
-                               (char*)pipe.dy[b] + (size_t)ll * (transpose ? D : bc * D) * ysz,
+        rc = smm_apply_sb_impl(op, (char*)pipe.dx[b].get() + off, bc,
+                               (char*)pipe.dy[b].get() + (size_t)ll * (transpose ? D : bc * D) * ysz,
                                transpose ? ck.nl * D : D, bc, pipe.stream[b], call.with_flags(fl));
         off += (size_t)op->csr.n_used_src * bc * xsz;
       }
@@ -1883,26 +1781,26 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, void* y_
       const void* h2d_src = xsrc;
       if (!x_direct) {
         StageTimer t(st.v[SMM_HOST_STAT_STAGE_IN_MS]);
-        int hrc = host_copy(pipe.hx[b], xsrc, (size_t)rows * S * xsz);
+        int hrc = host_copy(pipe.hx[b].get(), xsrc, (size_t)rows * S * xsz);
         if (hrc) return hrc;
-        h2d_src = pipe.hx[b];
+        h2d_src = pipe.hx[b].get();
       }
       SMM_HIP(pipe.mark(b, 0));
-      SMM_HIP(hipMemcpy2DAsync(pipe.dx[b], xrow_d, h2d_src, (size_t)S * xsz, (size_t)S * xsz, (size_t)rows,
+      SMM_HIP(hipMemcpy2DAsync(pipe.dx[b].get(), xrow_d, h2d_src, (size_t)S * xsz, (size_t)S * xsz, (size_t)rows,
                                hipMemcpyHostToDevice, pipe.stream[b]));
       st.v[SMM_HOST_STAT_H2D_BYTES] += (double)((size_t)S * xsz * (size_t)rows);
       SMM_HIP(pipe.mark(b, 1));
-      rc = smm_group_apply_impl(g, pipe.dx[b], rows_per_outer * ldx_d, n_inner * ldx_d, ldx_d, pipe.dy[b], ys_o, ys_l,
-                                ys_i, no, n_lev, n_inner, level_index, masked_levels, pipe.stream[b], call);
+      rc = smm_group_apply_impl(g, pipe.dx[b].get(), rows_per_outer * ldx_d, n_inner * ldx_d, ldx_d, pipe.dy[b].get(),
+                                ys_o, ys_l, ys_i, no, n_lev, n_inner, level_index, masked_levels, pipe.stream[b], call);
     }
     if (rc) return rc;
     SMM_HIP(pipe.mark(b, 2));
     st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)no * n_inner * ck.nl * D * ysz);
     if (!y_direct) {
-      SMM_HIP(hipMemcpyAsync(pipe.hy[b], pipe.dy[b], (size_t)no * n_inner * ck.nl * D * ysz, hipMemcpyDeviceToHost,
-                             pipe.stream[b]));
+      SMM_HIP(hipMemcpyAsync(pipe.hy[b].get(), pipe.dy[b].get(), (size_t)no * n_inner * ck.nl * D * ysz,
+                             hipMemcpyDeviceToHost, pipe.stream[b]));
     } else {
-      int yrc = y_to_host(ck, (const char*)pipe.dy[b], true, pipe.stream[b]);
+      int yrc = y_to_host(ck, (const char*)pipe.dy[b].get(), true, pipe.stream[b]);
       if (yrc) return yrc;
     }
     SMM_HIP(pipe.mark(b, 3));
