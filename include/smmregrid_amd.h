@@ -58,6 +58,27 @@ enum {
   SMM_I16 = 2,  /* CF-packed fields: X through the _cf entries below, Y through the _pk entries (every other entry: SMM_ERR_UNSUPPORTED) */
   SMM_U16 = 3
 };
+/* half-precision element types, the codes that follow SMM_U16 (rule below) */
+enum {
+  SMM_F16 = SMM_U16 + 1,  /* 4: IEEE binary16, X and Y of the plain entries */
+  SMM_BF16 = SMM_U16 + 2  /* 5: bfloat16, the same */
+};
+
+/* Half-precision fields and results (SMM_F16 / SMM_BF16), valid as x_dtype and y_dtype of the plain entries --
+ * smm_apply, smm_apply_sb, smm_apply_host, smm_group_apply, smm_group_apply_sb, smm_group_apply_host -- and as
+ * x_dtype of the two *_launch_info entries.  Elements are 2 bytes, pointers 2-byte aligned, strides in elements.
+ *   Half X: an element is widened exactly to float32 in registers and from there treated exactly as an element of a
+ *     float32 field (fill float32(1e20), promotion f32 -> f64, plain or SMM_APPLY_SKIPNA epilogue): the result bits are
+ *     those of the float32 entry on the widened field.  NaN, +-inf and subnormals are not special-cased and nothing is
+ *     flushed to zero.
+ *   Half Y: the float64 value v the epilogue produces (after the > 1e19 -> NaN test, the mask and dst_frac) is stored
+ *     with ONE correctly rounded conversion, ties to even, never through float32.  Overflow becomes +-inf, subnormal
+ *     results are kept, NaN is stored as the canonical quiet NaN (0x7E00 / 0x7FC0).
+ *   Built pairs (x -> y), each plain and with SMM_APPLY_SKIPNA, kernel 0 and the batch-fastest kernels (the LDS tile
+ *     kernel is not built for them: SMM_APPLY_KERNEL_TILE is SMM_ERR_UNSUPPORTED):
+ *       F16 -> F64, F16 -> F16, BF16 -> F64, BF16 -> BF16, F32 -> F16, F64 -> F16, F32 -> BF16, F64 -> BF16
+ *     any other pair with a half type is SMM_ERR_UNSUPPORTED; a half type in a call that carries a decode or an encode
+ *     rule (the _cf / _pk entries) is SMM_ERR_INVALID. */
 
 /* CF "packed data" (scale_factor / add_offset / _FillValue / missing_value): how a raw int16 / uint16 element q
  * becomes a field value, with T = float (decode_dtype SMM_F32) or double (SMM_F64):
@@ -258,7 +279,7 @@ int smm_group_launch_info(smm_group_t g, int x_dtype, int64_t n_outer, int64_t n
                           unsigned flags, int* kernel, int* j_per_block, int* rows_per_step,
                           int* rows_per_block, int64_t* n_blocks, int64_t* lds_bytes, int* big_operator);
 /* (smm_group_launch_info: x_dtype SMM_I16 / SMM_U16 answers for smm_group_apply_cf -- kernel 0, as for single operators;
- * with SMM_APPLY_KERNEL_TILE: SMM_ERR_UNSUPPORTED) */
+ * with SMM_APPLY_KERNEL_TILE: SMM_ERR_UNSUPPORTED.  SMM_F16 / SMM_BF16 fields: the same, for either entry.) */
 /* bit 0: every member has an LDS tile plan of the group's block shape, bit 1: the tile kernel is the default */
 int smm_group_plan_info(smm_group_t g, int* kernel_kind, int* slices_per_block);
 

@@ -22,6 +22,8 @@ SMM_F32 = 0
 SMM_F64 = 1
 SMM_I16 = 2     # CF-packed fields: X through the _cf entries, Y through the _pk entries
 SMM_U16 = 3
+SMM_F16 = 4     # half-precision fields and results: X and Y of the plain entries
+SMM_BF16 = 5
 
 APPLY_MASKED = 1 << 0
 APPLY_NO_FILL = 1 << 1

@@ -13,6 +13,10 @@ using XU16F = PackedX<uint16_t, float>;
 using XU16D = PackedX<uint16_t, double>;
 using YI16 = PackedY<int16_t>;
 using YU16 = PackedY<uint16_t>;
+using XF16 = HalfX<HalfKind::f16>;
+using XBF16 = HalfX<HalfKind::bf16>;
+using YF16 = HalfY<HalfKind::f16>;
+using YBF16 = HalfY<HalfKind::bf16>;
 constexpr int kAnyDecode = -1;   // float X: the decode dtype plays no part
 
 // M(x_dtype, decode_dtype, XT, y_dtype, YT, TILE): TILE = 1 where launch_tile is built too (float pairs only)
@@ -32,7 +36,15 @@ constexpr int kAnyDecode = -1;   // float X: the decode dtype plays no part
   M(SMM_F32, kAnyDecode, float, SMM_U16, YU16, 0)    \
   M(SMM_F64, kAnyDecode, double, SMM_U16, YU16, 0)   \
   M(SMM_U16, SMM_F32, XU16F, SMM_U16, YU16, 0)       \
-  M(SMM_U16, SMM_F64, XU16D, SMM_U16, YU16, 0)
+  M(SMM_U16, SMM_F64, XU16D, SMM_U16, YU16, 0)       \
+  M(SMM_F16, kAnyDecode, XF16, SMM_F64, double, 0)   \
+  M(SMM_F16, kAnyDecode, XF16, SMM_F16, YF16, 0)     \
+  M(SMM_BF16, kAnyDecode, XBF16, SMM_F64, double, 0) \
+  M(SMM_BF16, kAnyDecode, XBF16, SMM_BF16, YBF16, 0) \
+  M(SMM_F32, kAnyDecode, float, SMM_F16, YF16, 0)    \
+  M(SMM_F64, kAnyDecode, double, SMM_F16, YF16, 0)   \
+  M(SMM_F32, kAnyDecode, float, SMM_BF16, YBF16, 0)  \
+  M(SMM_F64, kAnyDecode, double, SMM_BF16, YBF16, 0)
 
 #define SMM_EXTERN_TILE_0(XT, YT, NA)
 #define SMM_EXTERN_TILE_1(XT, YT, NA)                                                                       \

@@ -54,6 +54,7 @@ int fail(int code, const std::string& msg) {
 
 constexpr bool is_float_dtype(int d) { return d == SMM_F32 || d == SMM_F64; }
 constexpr bool is_packed_dtype(int d) { return d == SMM_I16 || d == SMM_U16; }
+constexpr bool is_half_dtype(int d) { return d == SMM_F16 || d == SMM_BF16; }
 inline size_t dtype_size(int d) { return d == SMM_F64 ? 8 : (d == SMM_F32 ? 4 : 2); }
 
 // The field types and rules of one apply call: filled once at the ABI boundary (apply_entry), then passed down by
@@ -67,6 +68,7 @@ struct CallDesc {
   int decode_dtype = SMM_F64;    // of a packed X
   CfOutParams enc{};
   bool packed_x() const { return is_packed_dtype(x_dtype); }
+  bool half() const { return is_half_dtype(x_dtype) || is_half_dtype(y_dtype); }   // SMM_F16 / SMM_BF16 X or Y
   bool skipna() const { return (flags & SMM_APPLY_SKIPNA) != 0; }
   CallDesc with_flags(unsigned f) const {
     CallDesc c = *this;
@@ -88,6 +90,12 @@ struct Refusal {
   const char* msg;
 };
 constexpr Refusal x_dtype_refusal(int x_dtype, int y_dtype, bool cf, bool enc) {
+  if (is_half_dtype(x_dtype) || is_half_dtype(y_dtype)) {
+    if (cf || enc) return {SMM_ERR_INVALID, "SMM_F16 / SMM_BF16 take no decode or encode rule: use the plain entries"};
+    if (is_half_dtype(x_dtype) ? (y_dtype == SMM_F64 || y_dtype == x_dtype) : is_float_dtype(x_dtype)) return {SMM_OK, nullptr};
+    return {SMM_ERR_UNSUPPORTED, "this SMM_F16 / SMM_BF16 pairing is not built: a half field gives SMM_F64 or its own type, "
+                                 "a half result takes an SMM_F32 / SMM_F64 field or a field of its own type"};
+  }
   if (enc) {
     if (!is_packed_dtype(y_dtype)) return {SMM_ERR_INVALID, "an encode rule needs y_dtype SMM_I16 or SMM_U16"};
     if (is_float_dtype(x_dtype)) return {SMM_OK, nullptr};
@@ -117,8 +125,8 @@ inline int check_area_min(double area_min) {
 // A call that carries the rules its dtypes need (a packed X its decode rule, a packed Y its encode rule) is accepted
 // exactly when its combination is built.
 constexpr bool refusals_match_built() {
-  for (int x = SMM_F32; x <= SMM_U16; ++x)
-    for (int y = SMM_F32; y <= SMM_U16; ++y)
+  for (int x = SMM_F32; x <= SMM_BF16; ++x)
+    for (int y = SMM_F32; y <= SMM_BF16; ++y)
       for (int dd = SMM_F32; dd <= SMM_F64; ++dd)
         if ((x_dtype_refusal(x, y, is_packed_dtype(x), is_packed_dtype(y)).code == SMM_OK) != smm_launch::is_built(x, y, dd))
           return false;
@@ -423,7 +431,7 @@ int run_apply(const ApplyTarget& t, const int32_t* d_lev_map, const uint8_t* d_l
   if (n_outer < 0 || n_lev < 0 || n_inner < 0) return fail(SMM_ERR_INVALID, "negative batch size");
   if (n_outer == 0 || n_lev == 0 || n_inner == 0 || n_dst == 0) return SMM_OK;
   if (!info_only && (!x || !y)) return fail(SMM_ERR_INVALID, "null field pointer");
-  const bool packed = call.packed_x(), enc = call.has_enc;
+  const bool packed = call.packed_x(), enc = call.has_enc, half = call.half();
   if (int drc = check_x_dtype(call)) return drc;
   if (int arc = check_area_min(area_min)) return arc;
 
@@ -455,13 +463,15 @@ int run_apply(const ApplyTarget& t, const int32_t* d_lev_map, const uint8_t* d_l
   // SMM_APPLY_SKIPNA: tile forms without a skipna variant (split rows, rows streamed from L2) run kernel A instead
   const bool tile_skipna_ok = !(flags & SMM_APPLY_SKIPNA) ||
                               smm_launch::tile_has_skipna(tile_which, tile_which >= 2 ? tile_which - 1 : 0, max_row_nnz);
-  if (packed || enc) {
+  if (packed || enc || half) {
     // the LDS tile kernel stages 16-B pieces of 4- or 8-byte elements: packed X runs kernel A whatever the plan, and
-    // so do packed results (the tile kernel is not built for them either)
+    // so do packed results and half-precision fields and results (the tile kernel is not built for them either)
     if (flags & SMM_APPLY_KERNEL_TILE)
-      return fail(SMM_ERR_UNSUPPORTED, "the LDS tile kernel is not built for packed fields or results (SMM_I16 / SMM_U16)");
+      return fail(SMM_ERR_UNSUPPORTED, half ? "the LDS tile kernel is not built for half-precision fields or results (SMM_F16 / SMM_BF16)"
+                                            : "the LDS tile kernel is not built for packed fields or results (SMM_I16 / SMM_U16)");
     if (!info_only && ((uintptr_t)x % xsz) != 0) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
-    if (!info_only && enc && ((uintptr_t)y % 2) != 0) return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
+    if (!info_only && (enc || is_half_dtype(call.y_dtype)) && ((uintptr_t)y % 2) != 0)
+      return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
   } else if (flags & SMM_APPLY_KERNEL_TILE) {
     if (!t.tile_ok) return fail(SMM_ERR_UNSUPPORTED, "operator has no LDS tile plan");
     if (!tile_skipna_ok)
@@ -1223,13 +1233,14 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int64_t ld
   if (!x_host || !y_host) return fail(SMM_ERR_INVALID, "null field pointer");
   if (int drc = check_x_dtype(call)) return drc;
   if ((uintptr_t)x_host % dtype_size(x_dtype)) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
-  if (enc && (uintptr_t)y_host % 2) return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
+  if ((enc || is_half_dtype(y_dtype)) && (uintptr_t)y_host % 2) return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
   const int64_t S = op->csr.n_src, D = op->csr.n_dst;
   if (ldx < S || ldy < D) return fail(SMM_ERR_INVALID, "ldx/ldy smaller than the grid size");
   DeviceGuard guard(op->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
 
-  // packed X is staged, packed and shipped raw: 2 B per cell; a packed Y (enc) comes back, is staged and copied out raw too
+  // packed X is staged, packed and shipped raw: 2 B per cell; a packed Y (enc) comes back, is staged and copied out raw too;
+  // half-precision X and Y travel as their 2-byte elements the same way
   const size_t xsz = dtype_size(x_dtype), ysz = dtype_size(y_dtype);
   const size_t xrow = (size_t)ldx * xsz, yrow = (size_t)ldy * ysz;   // host row pitches
   // device rows start on 128-B lines: the tile plan stages whole lines of a row, and a row that
@@ -1653,13 +1664,15 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, void* y_
   if (n_outer < 0 || n_lev < 0 || n_inner < 0) return fail(SMM_ERR_INVALID, "negative batch size");
   if (int drc = check_x_dtype(call)) return drc;
   const bool packed = call.packed_x();
+  if (call.half() && (flags & SMM_APPLY_KERNEL_TILE))
+    return fail(SMM_ERR_UNSUPPORTED, "the LDS tile kernel is not built for half-precision fields or results (SMM_F16 / SMM_BF16)");
   if ((packed || enc) && (flags & SMM_APPLY_KERNEL_TILE))
     return fail(SMM_ERR_UNSUPPORTED, "the LDS tile kernel is not built for packed fields or results (SMM_I16 / SMM_U16)");
   const int64_t S = g->ops[0]->csr.n_src, D = g->ops[0]->csr.n_dst;
   if (n_outer == 0 || n_lev == 0 || n_inner == 0 || D == 0) return SMM_OK;
   if (!x_host || !y_host) return fail(SMM_ERR_INVALID, "null field pointer");
-  if (packed && (uintptr_t)x_host % 2) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
-  if (enc && (uintptr_t)y_host % 2) return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
+  if ((packed || is_half_dtype(x_dtype)) && (uintptr_t)x_host % 2) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
+  if ((enc || is_half_dtype(y_dtype)) && (uintptr_t)y_host % 2) return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
   DeviceGuard guard(g->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the group's device");
 
@@ -1839,6 +1852,8 @@ int make_cf(const smm_cf_decode_t* cf, CallDesc& c) {
   if (!c.packed_x()) {
     if (cf && is_float_dtype(c.x_dtype))
       return fail(SMM_ERR_INVALID, "a decode rule was given with a float field: pass cf = NULL, or the raw 16-bit field");
+    if (cf && is_half_dtype(c.x_dtype))
+      return fail(SMM_ERR_INVALID, "a decode rule was given with an SMM_F16 / SMM_BF16 field: half-precision fields take the plain entries");
     return SMM_OK;   // float: the plain entry; anything else: refused by the dtype check
   }
   if (!cf) return fail(SMM_ERR_INVALID, "SMM_I16 / SMM_U16 fields need a decode rule (cf is NULL)");

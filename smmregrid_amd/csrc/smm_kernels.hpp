@@ -70,6 +70,18 @@ struct PackedY {
   Q q;
 };
 
+// Half-precision element type tags (SMM_F16 / SMM_BF16): 2 bytes in memory, X widened to float, Y narrowed from the
+// float64 result; see XTraits / YTraits.  External linkage like PackedX / PackedY.
+enum class HalfKind { f16, bf16 };
+template <HalfKind K>
+struct HalfX {
+  uint16_t bits;
+};
+template <HalfKind K>
+struct HalfY {
+  uint16_t bits;
+};
+
 struct ApplyArgs {
   const LevelDesc* descs;     // device array
   const int32_t* lev_map;     // device [n_lev] -> desc index, null = identity 0
@@ -188,6 +200,51 @@ struct XTraits<PackedX<Q, T>> {
   }
 };
 
+// HalfX<K> is a half-precision field: the 16 bits of a binary16 / bfloat16 element in memory, widened EXACTLY to float
+// in registers (binary16: the hardware convert, which keeps subnormals -- f16 denormals are never flushed on gfx950 --
+// and every NaN a NaN; bfloat16: the bits are the upper half of the float), after which the value is treated exactly as
+// an element of a float field -- `packed` selects that decode-then-fill path, the rule is unused.
+template <HalfKind K>
+struct XTraits<HalfX<K>> {
+  typedef uint16_t raw;
+  typedef float val;
+  static constexpr bool packed = true;
+  static __device__ __forceinline__ float decode(uint16_t q, const CfParams&) {
+    if constexpr (K == HalfKind::f16)
+      return (float)__builtin_bit_cast(_Float16, q);
+    else
+      return __builtin_bit_cast(float, (uint32_t)q << 16);
+  }
+};
+
+// The float64 value v as the bits of a half type with EB exponent and MB stored significand bits (binary16: 5 / 10,
+// bfloat16: 8 / 7): ONE correctly rounded conversion, ties to even, in integer arithmetic on v's bits -- no float32 in
+// between (1 + 2^-11 + 2^-40 would round to 1 + 2^-11 in float32 and from that tie down to 1.0; the correct binary16 is
+// 1 + 2^-10).  Overflow gives +-inf, subnormal results are kept, every NaN becomes the canonical quiet NaN.
+template <int EB, int MB>
+__host__ __device__ __forceinline__ uint16_t f64_to_half_bits(double v) {
+  const uint64_t u = __builtin_bit_cast(uint64_t, v);
+  const uint32_t sign = (uint32_t)(u >> 48) & 0x8000u;
+  const uint64_t a = u & 0x7fffffffffffffffull;
+  constexpr uint32_t kInf = ((1u << EB) - 1u) << MB;
+  if (a > 0x7ff0000000000000ull) return (uint16_t)(kInf | (1u << (MB - 1)));   // NaN: 0x7E00 / 0x7FC0
+  constexpr int kBias = (1 << (EB - 1)) - 1;
+  const int he = (int)(a >> 52) - 1023 + kBias;          // biased exponent in the half type (before rounding)
+  if (he >= (1 << EB) - 1) return (uint16_t)(sign | kInf);   // +-inf and everything beyond the largest binade
+  // significand with its leading one; a float64 subnormal or zero (exponent field 0) is far below half of the smallest
+  // half subnormal and shifts out entirely
+  const uint64_t m = (a & 0x000fffffffffffffull) | 0x0010000000000000ull;
+  int shift = 52 - MB + (he <= 0 ? 1 - he : 0);          // he <= 0: a subnormal result loses 1 - he bits more
+  if (shift > 63) shift = 63;                            // m < 2^53: nothing but a sticky remainder is left
+  const uint64_t q = m >> shift;
+  const uint64_t rem = m & ((1ull << shift) - 1ull), half = 1ull << (shift - 1);
+  const uint32_t up = (rem > half || (rem == half && (q & 1ull))) ? 1u : 0u;
+  // normal: q carries the leading one, (he - 1) << MB + q = he << MB + fraction; subnormal: q is the fraction.  A
+  // carry out of the fraction moves into the exponent: the next binade, the first normal, or +-inf
+  const uint32_t bits = ((uint32_t)(he > 0 ? he - 1 : 0) << MB) + (uint32_t)q + up;
+  return (uint16_t)(sign | bits);
+}
+
 // Y element types.  A float type is its own storage type and takes the plain narrowing cast.  PackedY<Q> is a
 // CF-packed result: the float64 value v of the epilogue is stored as the raw Q (int16_t / uint16_t) of the ABI's rule --
 //   t = (v - offset) / scale;  r = rint(t);  !isfinite(v) || r < min(Q) || r > max(Q) -> fill, else (Q)r
@@ -213,6 +270,19 @@ struct YTraits<PackedY<Q>> {
     const bool bad = !__builtin_isfinite(v) || r < lo || r > hi;   // a NaN r cannot occur with a finite v
     const int32_t q = (int32_t)(bad ? 0.0 : r);
     return (Q)(bad ? e.fill : q);
+  }
+};
+
+// HalfY<K> is a half-precision result: the epilogue's float64 value stored by f64_to_half_bits.
+template <HalfKind K>
+struct YTraits<HalfY<K>> {
+  typedef uint16_t raw;
+  static constexpr bool packed = false;
+  static __device__ __forceinline__ uint16_t encode(double v, const CfOutParams&) {
+    if constexpr (K == HalfKind::f16)
+      return f64_to_half_bits<5, 10>(v);
+    else
+      return f64_to_half_bits<8, 7>(v);
   }
 };
 

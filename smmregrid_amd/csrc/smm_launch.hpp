@@ -1,5 +1,5 @@
 // Kernel launch templates, one explicit instantiation per built (X type, Y type, SKIPNA) triple -- the list is SMM_BUILT
-// in smm_built.hpp.  smm_launch_inst.hip is compiled once per variant of the Makefile's INST list, twenty objects side by
+// in smm_built.hpp.  smm_launch_inst.hip is compiled once per variant of the Makefile's INST list, twenty-eight objects side by
 // side: the tile kernel alone has several hundred instantiations, which one translation unit would compile for minutes.
 // SKIPNA = true builds the SMM_APPLY_SKIPNA variants (smm_kernels.hpp, RowSum) in objects of their own.
 #pragma once
@@ -52,7 +52,7 @@ inline int xcd_run_length() {
 }
 
 // Destination rows per tile (TD) of the batch-fastest kernel for a Y element of ysz bytes: one 128-B line of Y per
-// batch row for f64 (16 rows) and f32 (32).  A packed 2-byte Y takes 64 rows -- the same 128-B runs, a 17-KB LDS tile
+// batch row for f64 (16 rows) and f32 (32).  A 2-byte Y (packed or half precision) takes 64 rows -- the same 128-B runs, a 17-KB LDS tile
 // like f64's -- or 16 (32-B runs, a 4-KB tile) under SMM_TUNE_SB_PACKED_Y_ROWS = 16: both are built, DESIGN.md section 4
 // has the measurement.
 inline int sb_tile_rows(size_t ysz) {

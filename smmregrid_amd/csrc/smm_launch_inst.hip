@@ -2,7 +2,9 @@
 // -DSMM_XT=... -DSMM_YT=...: one float (X, Y) pair, all four launchers.  With -DSMM_PACKED=1: the int16 / uint16 packed-X
 // launchers that decode to SMM_XT instead.  With -DSMM_PACKED_Y=1: the launchers that store CF-packed int16 / uint16
 // results (PackedY), for float X of type SMM_XT or, with -DSMM_PACKED=1 too, packed X of the same raw type decoded to
-// SMM_XT.  -DSMM_SKIPNA=1: the SMM_APPLY_SKIPNA variants of the same.
+// SMM_XT.  With -DSMM_HALF=f16 / bf16: the half-precision rows of that kind (HalfX / HalfY) -- -DSMM_HALF_X=1: a half field
+// to f64 and to its own type; else: f32 and f64 fields to a half result.  -DSMM_SKIPNA=1: the SMM_APPLY_SKIPNA variants of
+// the same.
 #include "smm_launch.hpp"
 
 #ifndef SMM_SKIPNA
@@ -10,7 +12,21 @@
 #endif
 
 namespace smm_launch {
-#ifdef SMM_PACKED_Y
+#ifdef SMM_HALF
+// Half-precision fields and results (smm_kernels.hpp): kernel A, kernel C and the grouped kernel C.  No tile kernel.
+#define SMM_INST_HALF(XT, YT)                                                                            \
+  template int launch_sell<XT, YT, SMM_SKIPNA != 0>(const ApplyArgs&, int64_t, bool, unsigned, hipStream_t); \
+  template int launch_sb<XT, YT, SMM_SKIPNA != 0>(const SbArgs&, bool, unsigned, hipStream_t);           \
+  template int launch_sb_group<XT, YT, SMM_SKIPNA != 0>(const SbGroupArgs&, bool, unsigned, hipStream_t);
+#ifdef SMM_HALF_X
+SMM_INST_HALF(HalfX<HalfKind::SMM_HALF>, double)
+SMM_INST_HALF(HalfX<HalfKind::SMM_HALF>, HalfY<HalfKind::SMM_HALF>)
+#else
+SMM_INST_HALF(float, HalfY<HalfKind::SMM_HALF>)
+SMM_INST_HALF(double, HalfY<HalfKind::SMM_HALF>)
+#endif
+#undef SMM_INST_HALF
+#elif defined(SMM_PACKED_Y)
 // CF-packed 16-bit results encoded in the stores (PackedY, smm_kernels.hpp): kernel A, kernel C of single operators
 // and the grouped kernel C of level groups.  No tile kernel; packed X only with Y's own raw type.
 #ifdef SMM_PACKED

@@ -5,14 +5,88 @@ import numpy as np
 
 from . import _lib
 
-_DTYPE_CODE = {np.dtype(np.float32): _lib.SMM_F32, np.dtype(np.float64): _lib.SMM_F64}
+# numpy has no bfloat16: a 2-byte dtype of the project's own (one `<u2` field holding the bits) names it, so that
+# `np.empty(shape, bfloat16)`, `bits.view(bfloat16)` and `DeviceArray(shape, bfloat16)` work; `to_bfloat16` /
+# `from_bfloat16` convert
+bfloat16 = np.dtype([("bfloat16", "<u2")])
+
+_DTYPE_CODE = {np.dtype(np.float32): _lib.SMM_F32, np.dtype(np.float64): _lib.SMM_F64,
+               np.dtype(np.float16): _lib.SMM_F16, bfloat16: _lib.SMM_BF16}
+_HALF = (np.dtype(np.float16), bfloat16)
+# (field dtype, result dtype) pairs the kernels are built for when either is a half type (SMM_BUILT)
+HALF_PAIRS = tuple((h, y) for h in _HALF for y in (np.dtype(np.float64), h)) + \
+    tuple((x, h) for h in _HALF for x in (np.dtype(np.float32), np.dtype(np.float64)))
 
 
 def dtype_code(dtype):
     try:
         return _DTYPE_CODE[np.dtype(dtype)]
     except KeyError:
-        raise TypeError(f"field dtype {dtype} not supported on device (float32/float64 only)")
+        raise TypeError(f"field dtype {dtype} not supported on device (float32/float64, float16/bfloat16 only)")
+
+
+def is_half_dtype(dtype):
+    """float16 / `bfloat16`: regridded as 2-byte elements (widened to float32 in the kernels' registers)."""
+    return dtype is not None and np.dtype(dtype) in _HALF
+
+
+def _dtype_name(dtype):
+    return "bfloat16" if np.dtype(dtype) == bfloat16 else np.dtype(dtype).name
+
+
+def check_half_pair(x_dtype, y_dtype):
+    """TypeError for a (field, result) dtype pair with a half type that the kernels are not built for."""
+    x_dtype, y_dtype = np.dtype(x_dtype), np.dtype(y_dtype)
+    if (x_dtype in _HALF or y_dtype in _HALF) and (x_dtype, y_dtype) not in HALF_PAIRS:
+        built = ", ".join(f"{_dtype_name(a)} -> {_dtype_name(b)}" for a, b in HALF_PAIRS)
+        raise TypeError(f"{_dtype_name(x_dtype)} -> {_dtype_name(y_dtype)} is not built; the half-precision pairs "
+                        f"(field -> result) are: {built}")
+
+
+def _round_bits(u, drop):
+    """u >> drop rounded to nearest, ties to even (integer arrays)."""
+    q = u >> drop
+    rem = u & ((1 << drop) - 1)
+    half = 1 << (drop - 1)
+    return q + ((rem > half) | ((rem == half) & ((q & 1) == 1))).astype(u.dtype)
+
+
+def to_bfloat16(a):
+    """float32 / float64 (float16 is widened exactly) -> `bfloat16`, round to nearest even, correctly rounded from the
+    input's OWN precision (a float64 never passes through float32).  Overflow gives +-inf, NaN the quiet NaN 0x7FC0
+    with the sign kept."""
+    a = np.asarray(a)
+    if a.dtype == np.float16:
+        a = a.astype(np.float32)
+    if a.dtype == np.float32:
+        u = np.ascontiguousarray(a).view(np.uint32).astype(np.uint64)
+        mag, sign = u & 0x7FFFFFFF, (u >> 16) & 0x8000
+        bits = _round_bits(mag, 16)          # the carry moves into the exponent: next binade or inf
+        bits = np.where(mag > 0x7F800000, 0x7FC0, bits)
+    elif a.dtype == np.float64:
+        u = np.ascontiguousarray(a).view(np.uint64)
+        mag, sign = u & 0x7FFFFFFFFFFFFFFF, (u >> 48) & 0x8000
+        he = (mag >> 52).astype(np.int64) - 1023 + 127        # biased bfloat16 exponent before rounding
+        m = (mag & 0x000FFFFFFFFFFFFF) | 0x0010000000000000
+        drop = np.minimum(45 + np.where(he <= 0, 1 - he, 0), 63).astype(np.uint64)
+        q = m >> drop
+        rem, half = m & ((np.uint64(1) << drop) - np.uint64(1)), np.uint64(1) << (drop - np.uint64(1))
+        up = (rem > half) | ((rem == half) & ((q & np.uint64(1)) == 1))
+        bits = (np.maximum(he - 1, 0).astype(np.uint64) << np.uint64(7)) + q + up.astype(np.uint64)
+        bits = np.where(he >= 255, 0x7F80, bits)
+        bits = np.where(mag > 0x7FF0000000000000, 0x7FC0, bits)
+    else:
+        raise TypeError(f"to_bfloat16 takes float32 or float64, got {a.dtype}")
+    return (bits | sign).astype(np.uint16).view(bfloat16).reshape(a.shape)
+
+
+def from_bfloat16(a):
+    """`bfloat16` (or its raw uint16 bits) -> float32, exact."""
+    a = np.asarray(a)
+    if a.dtype != bfloat16 and a.dtype != np.uint16:
+        raise TypeError(f"from_bfloat16 takes bfloat16 (or uint16 bits), got {a.dtype}")
+    bits = np.ascontiguousarray(a).view(np.uint16)
+    return (bits.astype(np.uint32) << 16).view(np.float32).reshape(a.shape)
 
 
 _PACKED_CODE = {np.dtype(np.int16): _lib.SMM_I16, np.dtype(np.uint16): _lib.SMM_U16}
@@ -326,6 +400,30 @@ class DeviceArray:
         cupy, numba): the buffer stays owned by this DeviceArray."""
         return {"shape": self.shape, "typestr": self.dtype.str, "data": (int(self.ptr), False),
                 "version": 2, "strides": None}
+
+    @classmethod
+    def from_interface(cls, obj, layout="bs"):
+        """Zero-copy view of any C-contiguous object that speaks ``__cuda_array_interface__`` (a torch or cupy
+        tensor on this device, another DeviceArray) holding float16 / float32 / float64.  The view keeps a reference
+        to `obj`, which keeps owning the memory.  A torch bfloat16 tensor does not export the protocol: wrap it
+        with ``DeviceArray(t.shape, bfloat16, ptr=t.data_ptr(), base=t)``."""
+        iface = getattr(obj, "__cuda_array_interface__", None)
+        if not isinstance(iface, dict):
+            raise TypeError(f"{type(obj).__name__} does not export __cuda_array_interface__")
+        dtype = np.dtype(iface["typestr"])
+        if dtype not in (np.dtype(np.float16), np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError(f"from_interface takes float16 / float32 / float64, got {iface['typestr']}")
+        shape = tuple(int(n) for n in iface["shape"])
+        strides = iface.get("strides")
+        if strides is not None:
+            want, step = [], dtype.itemsize
+            for n in reversed(shape):
+                want.append(step)
+                step *= max(n, 1)
+            if any(n > 1 and int(st) != w for n, st, w in zip(shape, strides, reversed(want))):
+                raise ValueError("from_interface needs a C-contiguous array")
+        ptr = iface["data"][0]
+        return cls(shape, dtype, ptr=int(ptr or 0), base=obj, layout=layout)
 
     def reshape(self, *shape):
         if len(shape) == 1 and isinstance(shape[0], (tuple, list)):

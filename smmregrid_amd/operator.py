@@ -11,8 +11,8 @@ import time
 import numpy as np
 
 from . import _lib
-from .device import (DeviceArray, dtype_code, field_dtype_code, is_packed_dtype, result_cache, result_dtype,
-                     _stream_handle, current_device)
+from .device import (DeviceArray, bfloat16, check_half_pair, dtype_code, field_dtype_code, is_half_dtype,
+                     is_packed_dtype, result_cache, result_dtype, _stream_handle, current_device)
 
 
 def _cptr(a):
@@ -28,6 +28,10 @@ def _apply_call(entry, handle, x, mid, y, rest, y_res, cf, cf_out, y_name="Y"):
     The arguments are handle, X, its dtype code, *mid, Y, its dtype code, *rest, then the rule structs the entry takes.
     y_res: result_dtype(out_dtype, cf_out) -- what the result array of a cf_out call must be.  Returns y."""
     rules = []
+    if is_half_dtype(x.dtype) or is_half_dtype(y.dtype):
+        if cf is not None or cf_out is not None:
+            raise TypeError("float16 / bfloat16 fields and results take no CFDecode / CFEncode rule")
+        check_half_pair(x.dtype, y.dtype)      # an unbuilt pairing names the built ones
     if cf_out is not None:
         if y.dtype != y_res[0]:
             raise TypeError(f"{y_name} must be {y_res[0]} for this cf_out, got {y.dtype}")
@@ -40,6 +44,19 @@ def _apply_call(entry, handle, x, mid, y, rest, y_res, cf, cf_out, y_name="Y"):
         entry, rules = entry + "_cf", [ctypes.byref(cf._struct(x.dtype))]
     _lib.call(entry, handle, _ptr(x), x_code, *mid, _ptr(y), y_code, *rest, *rules)
     return y
+
+
+def _host_field(x, cf, half):
+    """A host field as the host entries ship it: float32 / float64 and raw CF-packed integers as they are, `bfloat16`
+    as it is, float16 as it is with half=True; anything else -- float16 by default -- is promoted to float64
+    (result_type(x, f64), regrid.py:550)."""
+    x = np.asarray(x)
+    if cf is not None and not is_packed_dtype(x.dtype):
+        raise TypeError(f"a CFDecode rule goes with a raw int16 / uint16 field, not {x.dtype}")
+    if cf is None and x.dtype not in (np.float32, np.float64) and x.dtype != bfloat16 \
+            and not (half and x.dtype == np.float16):
+        x = x.astype(np.float64)
+    return x
 
 
 def _launch_info(fn, handle, dt, sizes, flags):
@@ -198,6 +215,9 @@ class SparseOperator:
         padded row pitch ldx >= S (rows that start on 128-B lines are staged without straddling).
         A field tagged batch-fastest (`x.layout == "sb"`, shape (S, B)) goes through the batch-fastest
         kernel (`apply_sb`); with keep_batch_fastest the result stays batch-fastest too, (D, B).
+        x float16 / `bfloat16` (2-byte elements widened exactly to float32 in the kernel, then treated as a float32
+        field) and out_dtype float16 / `bfloat16` (the float64 result stored with one correctly rounded conversion) are
+        built for the pairs of `device.HALF_PAIRS`; any other pairing with a half type is a TypeError.
         skipna: non-finite source values drop out of each batch row's sums and the row is renormalised over
         the valid weight (SMM_APPLY_SKIPNA; rows without one are bit-identical to the plain apply).
         cf: a `CFDecode` -- x holds the raw int16 / uint16 of a CF-packed field, decoded inside the kernel
@@ -273,19 +293,18 @@ class SparseOperator:
                            cf_out)
 
     def apply_host(self, x, out=None, masked=False, remap_area_min=0.0, out_dtype=np.float64,
-                   flags=0, chunk_rows=0, skipna=False, cf=None, cf_out=None):
+                   flags=0, chunk_rows=0, skipna=False, cf=None, cf_out=None, half=False):
         """Same product for a host (numpy) array of shape (B, S): the rows stream through the
         library's double-buffered H2D / kernel / D2H pipeline (smm_apply_host).  Arrays from
         `pinned_empty` are DMA'd without staging copies.  Returns a (B, D) numpy array.
         cf: a `CFDecode` -- x is the raw int16 / uint16 of a CF-packed field: it is staged, packed and shipped as
         2-byte elements and decoded inside the kernels (smm_apply_host_cf).
         cf_out: a `CFEncode` -- the result is encoded inside the kernels and comes back, is staged and copied out as
-        raw int16 / uint16: a quarter of the float64 result's bytes over PCIe (smm_apply_host_pk)."""
-        x = np.asarray(x)
-        if cf is not None and not is_packed_dtype(x.dtype):
-            raise TypeError(f"a CFDecode rule goes with a raw int16 / uint16 field, not {x.dtype}")
-        if cf is None and x.dtype not in (np.float32, np.float64):
-            x = x.astype(np.float64)          # result_type(x, f64), regrid.py:550
+        raw int16 / uint16: a quarter of the float64 result's bytes over PCIe (smm_apply_host_pk).
+        half: a float16 field is shipped as 2-byte cells and widened to float32 inside the kernels (by default it is
+        promoted to float64 on the host, as before); a `bfloat16` field always is.  out_dtype float16 / `bfloat16`: the
+        result comes back as 2-byte cells."""
+        x = _host_field(x, cf, half)
         if x.ndim != 2 or x.shape[1] != self.n_src:
             raise ValueError(f"X must be (B, {self.n_src}), got {x.shape}")
         if x.strides[1] != x.itemsize or x.strides[0] % x.itemsize or x.strides[0] < self.n_src * x.itemsize:
@@ -438,19 +457,16 @@ class OperatorGroup:
                             _stream_handle(stream)), y_res, cf, cf_out)
 
     def apply_host(self, x, level_index, masked_levels=None, masked=False, remap_area_min=0.0,
-                   transpose=True, out_dtype=np.float64, flags=0, chunk_outer=0, skipna=False, cf=None, cf_out=None):
+                   transpose=True, out_dtype=np.float64, flags=0, chunk_outer=0, skipna=False, cf=None, cf_out=None,
+                   half=False):
         """Host (numpy) variant: x of shape (n_outer, n_lev, n_inner, S); chunks of the outer
         axis stream through the group's H2D / kernel / D2H pipeline (smm_group_apply_host).
         cf: a `CFDecode` -- x is the raw int16 / uint16 of a CF-packed field: it is staged, packed and shipped as
         2-byte elements and decoded inside the kernels (smm_group_apply_host_cf).
         cf_out: a `CFEncode` -- the result is encoded inside the kernels and comes back, is staged and copied out as
-        raw int16 / uint16: a quarter of the float64 result's bytes over PCIe (smm_group_apply_host_pk)."""
-        x = np.asarray(x)
-        if cf is not None and not is_packed_dtype(x.dtype):
-            raise TypeError(f"a CFDecode rule goes with a raw int16 / uint16 field, not {x.dtype}")
-        if cf is None and x.dtype not in (np.float32, np.float64):
-            x = x.astype(np.float64)
-        x = np.ascontiguousarray(x)
+        raw int16 / uint16: a quarter of the float64 result's bytes over PCIe (smm_group_apply_host_pk).
+        half: a float16 field is shipped as 2-byte cells (see SparseOperator.apply_host); `bfloat16` always is."""
+        x = np.ascontiguousarray(_host_field(x, cf, half))
         if x.ndim != 4 or x.shape[3] != self.n_src:
             raise ValueError(f"X must be (n_outer, n_lev, n_inner, {self.n_src}), got {x.shape}")
         n_outer, n_lev, n_inner, _ = x.shape

@@ -18,7 +18,7 @@ import os
 
 import numpy as np
 
-from .device import CFDecode, CFEncode, DeviceArray, is_packed_dtype, to_device
+from .device import CFDecode, CFEncode, DeviceArray, bfloat16, is_half_dtype, is_packed_dtype, to_device
 from .gridtype import GridType, tolist
 from .lazy import LazyArray, is_dask, map_batch_blocks
 from .operator import OperatorGroup
@@ -55,9 +55,9 @@ class Regridder(object):
     def __init__(self, source_grid=None, target_grid=None, weights=None,
                  method='con', remap_area_min=DEFAULT_AREA_MIN, transpose=True, mask_dim=None,
                  vertical_dim=None, horizontal_dims=None, cdo_extra=None, cdo_options=None,
-                 check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=np.float64,
+                 check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=None,
                  lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False,
-                 packed_levels=False, packed_out=False, packed_out_levels=False):
+                 packed_levels=False, packed_out=False, packed_out_levels=False, half=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -107,9 +107,16 @@ class Regridder(object):
         self.packed_out_levels = bool(packed_out_levels)
         if self.packed_out_levels and not self.packed_out:
             raise ValueError('packed_out_levels=True needs packed_out=True')
-        # the reference always yields float64 (result_type(x, f64)); float32 is an opt-in narrowing store
-        self.out_dtype = np.dtype(out_dtype)
-        if self.out_dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        # half: host float16 / bfloat16 fields are shipped as their 2-byte cells and widened to float32 inside the
+        # kernels (the bits of regridding field.astype(float32)), and without an explicit out_dtype the result has the
+        # field's own half type.  Off by default: a host float16 field is promoted to float64 first, as before.
+        # Device-resident half fields take the half path either way (they were an error before)
+        self.half = bool(half)
+        # the reference always yields float64 (result_type(x, f64)); float32 is an opt-in narrowing store, float16 /
+        # bfloat16 a correctly rounded one (no float32 in between)
+        self.out_dtype_given = out_dtype is not None
+        self.out_dtype = np.dtype(np.float64 if out_dtype is None else out_dtype)
+        if self.out_dtype not in (np.dtype(np.float32), np.dtype(np.float64)) and not is_half_dtype(self.out_dtype):
             raise ValueError('out_dtype must be float32 or float64')
         if self.packed_out and self.out_dtype != np.dtype(np.float64):
             raise ValueError('packed_out=True encodes the float64 result: out_dtype must stay float64')
@@ -300,6 +307,10 @@ class Regridder(object):
         cf = self._packed_rule(source_data) if self.packed else None
         enc = self._packed_out_rule(source_data) if (self.packed_out and cf is not None) else None
         packing = {k: source_data.attrs[k] for k in _CF_PACKING_ATTRS if k in source_data.attrs}
+        out_dtype = self._result_dtype(source_data)
+        if cf is not None and is_half_dtype(out_dtype):
+            raise ValueError(f"packed=True regrids {source_data.name} raw: its result is float64 or packed, "
+                             "a half-precision out_dtype does not go with it")
         if cf is not None and ((datagridtype.mask_dim and not self.packed_levels)
                                or self.out_dtype != np.dtype(np.float64)):
             # float32 results take no packed input, level groups only with packed_levels=True: decoded on the host,
@@ -309,21 +320,33 @@ class Regridder(object):
             source_data = self._decode_on_host(source_data, cf)
             cf = None
         if datagridtype.mask_dim and self.packed_out_levels:
-            out = self.regrid3d(source_data, datagridtype, cf=cf, cf_out=enc)   # encoded inside the group kernels
+            out = self.regrid3d(source_data, datagridtype, cf=cf, cf_out=enc, out_dtype=out_dtype)   # encoded inside the group kernels
             if out.data is None:
                 enc = None
         elif datagridtype.mask_dim:
-            out = self.regrid3d(source_data, datagridtype, cf=cf)
+            out = self.regrid3d(source_data, datagridtype, cf=cf, out_dtype=out_dtype)
             if enc is not None and out.data is not None:
                 enc = self._encode_on_host(out, enc)      # None when the result stays float64 (device-resident)
         else:
-            out = self.regrid2d(source_data, datagridtype, cf=cf, cf_out=enc)
+            out = self.regrid2d(source_data, datagridtype, cf=cf, cf_out=enc, out_dtype=out_dtype)
         if enc is not None:
             out.attrs.update(packing)      # the result is raw again: it keeps the rule it was encoded with
         elif cf is not None:
             for k in _CF_PACKING_ATTRS:
                 out.attrs.pop(k, None)
         return out
+
+    def _result_dtype(self, source_data):
+        """out_dtype of one variable: the Regridder's, or with half=True and no explicit out_dtype the own type of a
+        float16 / bfloat16 field."""
+        dtype = getattr(source_data.data, "dtype", None)
+        if self.half and not self.out_dtype_given and is_half_dtype(dtype):
+            return np.dtype(dtype)
+        return self.out_dtype
+
+    def _ships_half(self, dtype):
+        """Whether a host field of `dtype` is handed to the host entries as it is (half=True; bfloat16 has no other way)."""
+        return is_half_dtype(dtype) and (self.half or np.dtype(dtype) == bfloat16)
 
     def _packed_out_rule(self, source_data):
         """The CFEncode of a packed variable's own attributes, or None (one WARNING) when they name no fill value."""
@@ -377,7 +400,7 @@ class Regridder(object):
             self.grids[0].other_dims = datagridtype.other_dims
         return next((grid for grid in self.grids if grid == datagridtype), None)
 
-    def regrid2d(self, source_data, datagridtype, cf=None, cf_out=None):
+    def regrid2d(self, source_data, datagridtype, cf=None, cf_out=None, out_dtype=None):
         """regrid.py:429-456."""
         gridtype = self._get_gridtype(datagridtype)
         if gridtype is None:
@@ -385,7 +408,7 @@ class Regridder(object):
         return self.apply_weights(source_data, gridtype.weights,
                                   weights_matrix=gridtype.weights_matrix,
                                   masked=gridtype.masked,
-                                  horizontal_dims=gridtype.horizontal_dims, cf=cf, cf_out=cf_out)
+                                  horizontal_dims=gridtype.horizontal_dims, cf=cf, cf_out=cf_out, out_dtype=out_dtype)
 
     # ------------------------------------------------------------------ apply (2-D)
     def _target_layout(self, weights):
@@ -424,10 +447,13 @@ class Regridder(object):
         return out
 
     def apply_weights(self, source_data, weights, weights_matrix=None, masked=True,
-                      horizontal_dims=None, cf=None, cf_out=None):
+                      horizontal_dims=None, cf=None, cf_out=None, out_dtype=None):
         """regrid.py:458-628 for one 2-D operator.  cf: the CFDecode of a raw int16 / uint16 field (packed=True);
-        cf_out: the CFEncode its result is stored with (packed_out=True)."""
+        cf_out: the CFEncode its result is stored with (packed_out=True); out_dtype: this variable's result dtype
+        (None: the Regridder's, or the field's own half type under half=True)."""
         source_data = from_xarray(source_data)
+        if out_dtype is None:
+            out_dtype = self._result_dtype(source_data)
         weights = from_xarray(weights)
         name = source_data.name or ''
         if any(s in name for s in ("bnds", "bounds", "vertices")):
@@ -453,8 +479,10 @@ class Regridder(object):
         masked = bool(np.asarray(masked).any()) if np.ndim(masked) else bool(masked)
 
         src = source_data.data
-        area_min, out_dtype, skipna = self.remap_area_min, self.out_dtype, self.skipna
+        area_min, skipna = self.remap_area_min, self.skipna
         res_dtype = out_dtype if cf_out is None else cf_out.raw_dtype
+        src_dtype = getattr(src, "dtype", None)
+        ship_half = self._ships_half(src_dtype)
         sb_in = isinstance(src, DeviceArray) and src.layout == "sb"
         if sb_in:
             n_h = len(source_data.dims) - len(kept_dims)
@@ -472,13 +500,16 @@ class Regridder(object):
             """(rows, S) host block -> (rows, D): chunks stream through the library's H2D / kernel /
             D2H pipeline."""
             host = np.asarray(host)
-            if cf is None and host.dtype not in (np.float32, np.float64):
+            if ship_half and host.dtype != src_dtype:
+                # a lazy field promised half-precision chunks (the result dtype was fixed from that): no silent promotion
+                raise ValueError(f"half=True: a chunk of dtype {host.dtype} in a field of dtype {src_dtype}")
+            if cf is None and host.dtype not in (np.float32, np.float64) and not ship_half:
                 host = host.astype(np.float64)  # result_type(x, f64), regrid.py:550
             host = np.ascontiguousarray(host)
             if host.shape[1] != op.n_src:
                 raise ValueError(f"source grid has {host.shape[1]} cells, weights expect {op.n_src}")
             return op.apply_host(host, masked=masked, remap_area_min=area_min, out_dtype=out_dtype, skipna=skipna,
-                                 cf=cf, cf_out=cf_out)
+                                 cf=cf, cf_out=cf_out, half=ship_half)
 
         def compute():
             if sb_in:
@@ -511,7 +542,7 @@ class Regridder(object):
                             tgt_shape, tgt_dims)
 
     # ------------------------------------------------------------------ apply (masked levels)
-    def regrid3d(self, source_data, datagridtype, cf=None, cf_out=None):
+    def regrid3d(self, source_data, datagridtype, cf=None, cf_out=None, out_dtype=None):
         """regrid.py:339-427 as one grouped launch: per data level the nearest
         weights level (tolerance 1e-3) selects operator, mask and frac.  cf: the CFDecode of a raw int16 / uint16
         field (packed=True, packed_levels=True); cf_out: the CFEncode its result is stored with (packed_out=True,
@@ -562,8 +593,11 @@ class Regridder(object):
 
         src = source_data.data
         S, D = group.n_src, group.n_dst
-        area_min, out_dtype, transpose = self.remap_area_min, self.out_dtype, self.transpose
+        area_min, transpose = self.remap_area_min, self.transpose
+        if out_dtype is None:
+            out_dtype = self._result_dtype(source_data)
         skipna = self.skipna
+        ship_half = self._ships_half(getattr(src, "dtype", None))
         sb_in = isinstance(src, DeviceArray) and src.layout == "sb"
         if sb_in:
             # batch-fastest per level: (mask_dim, horizontal..., everything else...)
@@ -594,14 +628,17 @@ class Regridder(object):
                                 transpose=transpose, out_dtype=out_dtype, skipna=skipna, cf=cf, cf_out=cf_out)
                 return y.reshape(*out_shape)
             host = src.compute() if isinstance(src, LazyArray) else np.asarray(src)   # a dask field is computed here
-            if cf is None and host.dtype not in (np.float32, np.float64):
+            if ship_half and host.dtype != src.dtype:
+                raise ValueError(f"half=True: a chunk of dtype {host.dtype} in a field of dtype {src.dtype}")
+            if cf is None and host.dtype not in (np.float32, np.float64) and not ship_half:
                 host = host.astype(np.float64)
             host = np.ascontiguousarray(host).reshape(n_outer, n_lev, n_inner, -1)
             if host.shape[3] != S:
                 raise ValueError(f"source grid has {host.shape[3]} cells, weights expect {S}")
             # host field: chunks of the outer axis stream through the group's pipeline
             out = group.apply_host(host, level_index, masked_levels, masked=any_masked, remap_area_min=area_min,
-                                   transpose=transpose, out_dtype=out_dtype, skipna=skipna, cf=cf, cf_out=cf_out)
+                                   transpose=transpose, out_dtype=out_dtype, skipna=skipna, cf=cf, cf_out=cf_out,
+                                   half=ship_half)
             return out.reshape(out_shape)
 
         res_dtype = out_dtype if cf_out is None else cf_out.raw_dtype
