@@ -518,8 +518,8 @@ GroupChunkPlan plan_group_chunks(int64_t n_outer, int64_t n_lev, int64_t n_inner
   const int64_t min_outer = (32 + n_inner - 1) / n_inner;
   const bool may_pack = packing_allowed && used_total > 0 && used_total * 5 <= n_lev * S * 4;
   // X and Y bytes per outer index size the chunk (host_chunk_units, as in smm_apply_host)
-  const HostChunk hc = host_chunk_units(n_outer, x_outer_d, y_outer, may_pack ? (size_t)used_total * n_inner * xsz : 0,
-                                        min_outer, 1, requested_outer, free_bytes);
+  HostChunk hc = host_chunk_units(n_outer, x_outer_d, y_outer, may_pack ? (size_t)used_total * n_inner * xsz : 0,
+                                  min_outer, 1, requested_outer, free_bytes);
   std::vector<GroupChunk>& chunks = plan.chunks;
   auto whole_levels = [&]() {   // blocks of the outer axis, every level
     for (int64_t o0 = 0; o0 < n_outer; o0 += hc.units)
@@ -534,29 +534,49 @@ GroupChunkPlan plan_group_chunks(int64_t n_outer, int64_t n_lev, int64_t n_inner
     // level-major: the staging budget per chunk (SMM_TUNE_HOST_CHUNK_KB lowers it so that tests reach every branch)
     const size_t target = budget_kb > 0 ? (size_t)budget_kb << 10 : (size_t)256 << 20, cap = 4 * target;
     const size_t per_outer = (size_t)std::max<int64_t>(max_used, 1) * n_inner * xsz;   // the widest level, one outer index
+    const size_t y_level = (size_t)n_inner * D * ysz;   // one level's Y, one outer index
     int64_t bo = (int64_t)(cap / per_outer);
-    if (free_bytes > 0) bo = std::min<int64_t>(bo, (int64_t)(free_bytes / 8 / (per_outer + (size_t)n_inner * D * ysz)));
+    // a chunk of the widest level alone: its two X and two Y buffers within a quarter of the free memory
+    if (free_bytes > 0) bo = std::min<int64_t>(bo, (int64_t)(free_bytes / 8 / (per_outer + y_level)));
     bo = std::min(bo, n_outer);
     if (bo >= std::min(min_outer, n_outer)) {
       plan.pack = true;
       chunks.clear();
+      // the largest X and Y so far: the pipeline allocates each buffer for the largest chunk of its kind, which need not
+      // be one and the same chunk.  A chunk of one level stays within those of the widest level (the clamp on bo above).
+      size_t big_x = (size_t)bo * per_outer, big_y = (size_t)bo * y_level;
       for (int64_t o0 = 0; o0 < n_outer; o0 += bo) {
         const int64_t no = std::min(bo, n_outer - o0);
+        // Levels are added while the chunk's X AND Y bytes fit the target (what host_chunk_units sizes too), at least one.
+        // Thin and empty levels add next to no X but a full slab of Y each (no * n_inner * D * ysz): bounded by X alone,
+        // a run of them put tens of GB of Y into one chunk when D is not small against S.  Beyond 2 GiB of device
+        // buffers (what host_chunk_units tolerates unasked) a level joins only while 2 x X and 2 x Y stay within a
+        // quarter of the free memory.
+        auto fits = [&](size_t x, int64_t nl) {
+          const size_t y = (size_t)no * y_level * (size_t)nl;
+          if (x + y > target) return false;
+          const size_t all = 2 * (std::max(x, big_x) + std::max(y, big_y));
+          return !(free_bytes > 0 && all > ((size_t)2 << 30) && all > free_bytes / 4);
+        };
         for (int64_t l0 = 0; l0 < n_lev;) {
-          // levels are added while their X bytes fit the target, at least one; the chunk's Y is not bounded here
           int64_t nl = 0;
           size_t bytes = 0;
           do {
             bytes += used(l0 + nl, no);
             ++nl;
-          } while (l0 + nl < n_lev && bytes + used(l0 + nl, no) <= target);
+          } while (l0 + nl < n_lev && fits(bytes + used(l0 + nl, no), nl + 1));
           chunks.push_back({o0, no, l0, nl, bytes});
+          big_x = std::max(big_x, bytes);
+          big_y = std::max(big_y, (size_t)no * y_level * (size_t)nl);
           l0 += nl;
         }
       }
     }
   }
-  if (chunks.empty()) whole_levels();   // packing not possible after all: whole rows
+  if (chunks.empty()) {   // packing not possible after all: whole rows, in blocks sized (and clamped) for whole rows
+    if (hc.pack) hc = host_chunk_units(n_outer, x_outer_d, y_outer, 0, min_outer, 1, requested_outer, free_bytes);
+    whole_levels();
+  }
   for (GroupChunk& c : chunks) {
     if (plan.pack && c.x_bytes == 0)
       for (int64_t l = c.l0; l < c.l0 + c.nl; ++l) c.x_bytes += used(l, c.no);

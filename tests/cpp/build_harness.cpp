@@ -177,19 +177,34 @@ int main(int argc, char** argv) {
       size_t free_bytes;
       int64_t budget_kb;
     };
-    // what holds for every plan: the chunks tile (outer x level) exactly once, none is empty, x_bytes is the packed
-    // size of the chunk's levels, the maxima are the maxima of the list
+    // What holds for every plan.  The chunks tile (outer x level) exactly once in pipeline order (outer blocks ascending,
+    // the level ranges of a block ascending), none is empty, x_bytes is the packed size of the chunk's levels, the maxima
+    // are the maxima of the list.  pack is false exactly when the chunks are whole rows: every level, blocks of one
+    // size, no packed bytes.  A level-major plan (packed, and not host_chunk_units' packed outer blocks) has blocks of
+    // bo >= min(32 batch entries, n_outer) outer indices; a chunk of several levels keeps X + Y within the staging
+    // target (256 MiB, or budget_kb) and takes every level that fits; a chunk of one level keeps X within four targets.
+    // With free_bytes known, the four device buffers (2 x max_x, 2 x max_y) stay within a quarter of it once they
+    // exceed the 2 GiB that host_chunk_units' clamp tolerates -- in blocks of the outer axis unless one index is left.
+    long long n_level_major = 0, n_multi = 0, n_y_ended = 0, n_whole = 0, n_mem_bound = 0;
     auto plan_of = [&](const Args& a) {
+      const size_t GiB = (size_t)1 << 30;
       const smm::GroupChunkPlan p = smm::plan_group_chunks(a.n_outer, a.n_lev, a.n_inner, a.S, a.D, a.xsz, a.ysz, a.used.data(),
                                                            a.allowed, a.requested, a.free_bytes, a.budget_kb);
       std::vector<int> seen((size_t)(a.n_outer * a.n_lev), 0);
       size_t max_x = 0, max_y = 0, max_rows = 0;
       if (p.x_row != (a.S * a.xsz + 127) / 128 * 128) ++gbad;
+      if (p.chunks.empty()) ++gbad;
+      int64_t next_o = 0, next_l = 0, block_no = 0;
       for (const smm::GroupChunk& c : p.chunks) {
         if (c.no < 1 || c.nl < 1 || c.o0 < 0 || c.l0 < 0 || c.o0 + c.no > a.n_outer || c.l0 + c.nl > a.n_lev) {
           ++gbad;
           continue;
         }
+        // pipeline order: the next level range of the same block, or the first one of the next block
+        if (c.l0 != next_l || c.o0 != next_o || (c.l0 > 0 && c.no != block_no)) ++gbad;
+        block_no = c.no;
+        next_l = c.l0 + c.nl;
+        if (next_l == a.n_lev) next_l = 0, next_o = c.o0 + c.no;
         size_t xb = 0;
         for (int64_t l = c.l0; l < c.l0 + c.nl; ++l) {
           xb += (size_t)a.used[(size_t)l] * c.no * a.n_inner * a.xsz;
@@ -200,8 +215,50 @@ int main(int argc, char** argv) {
         max_y = std::max(max_y, (size_t)c.no * a.n_inner * c.nl * a.D * a.ysz);
         max_rows = std::max(max_rows, (size_t)(c.no * a.n_lev * a.n_inner));
       }
+      if (next_l != 0 || next_o != a.n_outer) ++gbad;
       for (int v : seen) gbad += v != 1;
       if (p.max_x != max_x || p.max_y != max_y || p.max_rows != max_rows) ++gbad;
+      if (p.chunks.empty()) return p;
+      // packing: only when the call allows it and at most four fifths of the selected cells are used
+      int64_t used_total = 0;
+      for (int64_t u : a.used) used_total += u;
+      const bool may_pack = a.allowed && used_total > 0 && used_total * 5 <= a.n_lev * a.S * 4;
+      if (p.pack && !may_pack) ++gbad;
+      if (p.pack && a.requested > 0 && a.budget_kb > 0) ++gbad;
+      const int64_t min_outer = (32 + a.n_inner - 1) / a.n_inner, bo = p.chunks[0].no;
+      const smm::HostChunk hc = smm::host_chunk_units(a.n_outer, (size_t)a.n_lev * a.n_inner * p.x_row,
+                                                      (size_t)a.n_lev * a.n_inner * a.D * a.ysz,
+                                                      may_pack ? (size_t)used_total * a.n_inner * a.xsz : 0, min_outer, 1,
+                                                      a.requested, a.free_bytes);
+      const bool level_major = p.pack && !(hc.pack && a.budget_kb <= 0);
+      const size_t all = 2 * (max_x + max_y);
+      if (!level_major) {   // blocks of the outer axis, every level: whole rows or packed
+        for (const smm::GroupChunk& c : p.chunks)
+          if (c.l0 != 0 || c.nl != a.n_lev || (c.no != bo && c.o0 + c.no != a.n_outer) || c.no > bo) ++gbad;
+        if (a.requested > 0 && bo != std::min(a.requested, a.n_outer)) ++gbad;
+        if (a.requested <= 0 && a.free_bytes > 0 && all > 2 * GiB && max_x + max_y > a.free_bytes / 4 && bo > 1) ++gbad;
+        n_whole += !p.pack;
+        return p;
+      }
+      ++n_level_major;
+      const size_t target = a.budget_kb > 0 ? (size_t)a.budget_kb << 10 : 256 * ((size_t)1 << 20);
+      if (a.requested > 0 || bo < std::min(min_outer, a.n_outer)) ++gbad;
+      if (a.free_bytes > 0 && all > 2 * GiB && all > a.free_bytes / 4) ++gbad;
+      n_mem_bound += a.free_bytes > 0 && all > 2 * GiB;
+      for (const smm::GroupChunk& c : p.chunks) {
+        if ((c.no != bo && c.o0 + c.no != a.n_outer) || c.no > bo) ++gbad;
+        const size_t y_level = (size_t)c.no * a.n_inner * a.D * a.ysz;
+        if (c.nl == 1 && c.x_bytes > 4 * target) ++gbad;
+        if (c.nl > 1 && c.x_bytes + (size_t)c.nl * y_level > target) ++gbad;
+        n_multi += c.nl > 1;
+        if (c.l0 + c.nl < a.n_lev) {   // the next level was refused: it did not fit
+          const size_t x1 = c.x_bytes + (size_t)a.used[(size_t)(c.l0 + c.nl)] * c.no * a.n_inner * a.xsz;
+          const size_t y1 = (size_t)(c.nl + 1) * y_level, all1 = 2 * (std::max(x1, max_x) + std::max(y1, max_y));
+          const bool no_memory = a.free_bytes > 0 && all1 > 2 * GiB && all1 > a.free_bytes / 4;
+          if (x1 + y1 <= target && !no_memory) ++gbad;
+          n_y_ended += x1 <= target && x1 + y1 > target;   // the Y bound, not the X bound, ended the chunk
+        }
+      }
       return p;
     };
     struct C { int64_t o0, no, l0, nl; size_t x_bytes; };
@@ -245,62 +302,157 @@ int main(int argc, char** argv) {
     a.budget_kb = 0;
     expect(a, true, {{0, 40, 0, 3, 112000000}, {40, 40, 0, 3, 112000000}, {80, 20, 0, 3, 56000000}});
     // Level-major, budget 64 KiB: target 65 536 B, cap 262 144 B.  40 outer indices, f64: a level of 100 used cells is
-    // 100 * 40 * 8 = 32 000 B, one of 10 is 3 200 B; bo = 262 144 / 800 = 327 -> 40.  32 000 + 32 000 = 64 000 fits,
-    // + 32 000 does not: {2}; then 32 000 + 3 200 + 3 200 = 38 400: {3}
+    // 100 * 40 * 8 = 32 000 B of X, one of 10 is 3 200 B, and every level brings 40 * 50 * 8 = 16 000 B of Y;
+    // bo = 262 144 / 800 = 327 -> 40.  Two wide levels are 64 000 + 32 000 = 96 000 B: {1}, {1}; the third with a thin
+    // one 35 200 + 32 000 = 67 200: {1}; the two thin ones 6 400 + 32 000 = 38 400: {2}.  (X alone took 64 000 | 38 400:
+    // {2}, {3} before Y counted.)
     const Args thin{40, 5, 1, 1000, 50, 8, 8, {100, 100, 100, 10, 10}, true, 0, 0, 64};
-    expect(thin, true, {{0, 40, 0, 2, 64000}, {0, 40, 2, 3, 38400}});
-    // the same for a packed field and result (2-byte cells) under 16 KiB: levels of 8 000 and 800 B, 16 000 <= 16 384
+    expect(thin, true, {{0, 40, 0, 1, 32000}, {0, 40, 1, 1, 32000}, {0, 40, 2, 1, 32000}, {0, 40, 3, 2, 6400}});
+    // with D = 1 the Y of a level is 320 B and X decides, the plan from before Y counted: 64 000 + 640 = 64 640 fits, a
+    // third wide level (96 000) does not: {2}; then 38 400 + 960 = 39 360: {3}
+    a = thin;
+    a.D = 1;
+    expect(a, true, {{0, 40, 0, 2, 64000}, {0, 40, 2, 3, 38400}});
+    // the same for a packed field and result (2-byte cells) under 16 KiB: levels of 8 000 and 800 B of X, 4 000 B of Y
+    // each: 16 000 + 8 000 > 16 384: {1}, {1}; 8 800 + 8 000 = 16 800: {1}; 1 600 + 8 000 = 9 600: {2}
     a = thin;
     a.xsz = a.ysz = 2;
     a.budget_kb = 16;
-    expect(a, true, {{0, 40, 0, 2, 16000}, {0, 40, 2, 3, 9600}});
+    expect(a, true, {{0, 40, 0, 1, 8000}, {0, 40, 1, 1, 8000}, {0, 40, 2, 1, 8000}, {0, 40, 3, 2, 1600}});
     // a level beyond the target on its own (500 * 40 * 8 = 160 000 B > 65 536) is still taken, alone
     const Args wide{40, 3, 1, 1000, 50, 8, 8, {100, 500, 100}, true, 0, 0, 64};
     expect(wide, true, {{0, 40, 0, 1, 32000}, {0, 40, 1, 1, 160000}, {0, 40, 2, 1, 32000}});
     // bo cut by the cap: the widest level is 4 000 B per outer index, 262 144 / 4 000 = 65: blocks of 65 and 35.
-    // 65: 260 000 | 52 000 | 52 000 (two would be 104 000); 35: 140 000 | 28 000 + 28 000 = 56 000
+    // 65: 260 000 | 52 000 | 52 000 (two would be 104 000 of X); 35: 140 000 | 28 000 | 28 000 (two are 56 000 of X and
+    // 2 * 35 * 400 = 28 000 of Y: 84 000; one chunk of 56 000 before Y counted)
     const Args capped{100, 3, 1, 1000, 50, 8, 8, {500, 100, 100}, true, 0, 0, 64};
-    expect(capped, true, {{0, 65, 0, 1, 260000}, {0, 65, 1, 1, 52000}, {0, 65, 2, 1, 52000}, {65, 35, 0, 1, 140000}, {65, 35, 1, 2, 56000}});
+    expect(capped, true, {{0, 65, 0, 1, 260000}, {0, 65, 1, 1, 52000}, {0, 65, 2, 1, 52000}, {65, 35, 0, 1, 140000},
+                          {65, 35, 1, 1, 28000}, {65, 35, 2, 1, 28000}});
     // bo cut by the free memory: free / 8 / (4 000 + 50 * 8) = 40 with 1 408 000 B free: blocks of 40, 40, 20.
-    // 40: 160 000 | 32 000 + 32 000; 20: 80 000 | 16 000 + 16 000
+    // 40: 160 000 | 32 000 | 32 000 (two: 64 000 + 32 000 of Y = 96 000; one chunk before); 20: 80 000 | 16 000 + 16 000
+    // with 16 000 of Y = 48 000
     a = capped;
     a.free_bytes = 8 * 4400 * 40;
-    expect(a, true, {{0, 40, 0, 1, 160000}, {0, 40, 1, 2, 64000}, {40, 40, 0, 1, 160000}, {40, 40, 1, 2, 64000},
-                     {80, 20, 0, 1, 80000}, {80, 20, 1, 2, 32000}});
+    expect(a, true, {{0, 40, 0, 1, 160000}, {0, 40, 1, 1, 32000}, {0, 40, 2, 1, 32000}, {40, 40, 0, 1, 160000},
+                     {40, 40, 1, 1, 32000}, {40, 40, 2, 1, 32000}, {80, 20, 0, 1, 80000}, {80, 20, 1, 2, 32000}});
     // ... and to 31 (< the 32 entries a packed chunk needs): whole rows after all, in host_chunk_units' block (all 100)
     a.free_bytes = 8 * 4400 * 31;
     expect(a, false, {{0, 100, 0, 3, 0}});
-    // 10 outer indices (>= 8, < 32) are still packed level-major: the default 256-MiB target takes all three levels,
-    // 16 KiB (cap 65 536, bo = 16 -> 10) takes 40 000 | 8 000 + 8 000; 7 outer indices are not packed
+    // 10 outer indices (>= 8, < 32) are still packed level-major: the default 256-MiB target takes all three levels
+    // (56 000 of X, 12 000 of Y), 16 KiB (cap 65 536, bo = 16 -> 10) takes 40 000 | 8 000 | 8 000 (two: 16 000 + 8 000
+    // of Y = 24 000 > 16 384; one chunk before Y counted); 7 outer indices are not packed
     a = capped;
     a.n_outer = 10;
     a.budget_kb = 0;
     expect(a, true, {{0, 10, 0, 3, 56000}});
     a.budget_kb = 16;
-    expect(a, true, {{0, 10, 0, 1, 40000}, {0, 10, 1, 2, 16000}});
+    expect(a, true, {{0, 10, 0, 1, 40000}, {0, 10, 1, 1, 8000}, {0, 10, 2, 1, 8000}});
     a.n_outer = 7;
     expect(a, false, {{0, 7, 0, 3, 0}});
     // n_inner = 2: a packed chunk needs 16 outer indices.  The widest level is 8 000 B per outer index, cap / that = 32
-    // -> 20: 160 000 | 32 000 + 32 000.  Free memory for 16 (per outer index 8 000 + 2 * 50 * 8): blocks of 16
-    // (128 000 | 25 600 + 25 600) and 4 (32 000 + 6 400 + 6 400 = 44 800, all three levels); for 15: whole rows
+    // -> 20: 160 000 | 32 000 | 32 000 (two: 64 000 + 2 * 20 * 800 = 32 000 of Y; one chunk before Y counted).  Free
+    // memory for 16 (per outer index 8 000 + 2 * 50 * 8): blocks of 16 (128 000 | 25 600 | 25 600: two are 51 200 +
+    // 25 600 of Y = 76 800) and 4 (32 000 + 6 400 + 6 400 = 44 800 and 3 * 4 * 800 = 9 600 of Y, all three levels); for
+    // 15: whole rows
     a = capped;
     a.n_outer = 20;
     a.n_inner = 2;
-    expect(a, true, {{0, 20, 0, 1, 160000}, {0, 20, 1, 2, 64000}});
+    expect(a, true, {{0, 20, 0, 1, 160000}, {0, 20, 1, 1, 32000}, {0, 20, 2, 1, 32000}});
     a.free_bytes = 8 * 8800 * 16;
-    expect(a, true, {{0, 16, 0, 1, 128000}, {0, 16, 1, 2, 51200}, {16, 4, 0, 3, 44800}});
+    expect(a, true, {{0, 16, 0, 1, 128000}, {0, 16, 1, 1, 25600}, {0, 16, 2, 1, 25600}, {16, 4, 0, 3, 44800}});
     a.free_bytes = 8 * 8800 * 15;
     expect(a, false, {{0, 20, 0, 3, 0}});
     // config 3's sizes (120 steps x 75 levels of 1442 x 1021 -> 64 800 cells) with levels thinning from 10^6 used
     // cells by 12 800 a level (39.5 M in all): 32 steps of all levels exceed 1 GiB, so level-major, and no chunk's
-    // packed X goes beyond the cap of four targets
+    // packed X goes beyond the cap of four targets.  bo = min(1 GiB / 8 MB = 134, 200 GiB / 8 / (8 000 000 + 518 400)
+    // = 3151, 120) = 120: level l is x_l = 960 000 000 - 12 288 000 l bytes of X and 120 * 64 800 * 8 = 62 208 000 of
+    // Y, the target 268 435 456.  Levels 0 - 56 exceed the target alone (x_56 = 271 872 000), 57 - 66 by X in pairs
+    // (x_66 + x_67 = 285 696 000): one chunk each.  Before Y counted the rest paired by X: {67, 68} 261 120 000,
+    // {69, 70} 211 968 000, {71, 72, 73} 225 792 000, {74}: 71 chunks.  With two levels' Y (124 416 000) a pair needs
+    // X <= 144 019 456: x_71 + x_72 = 162 816 000 does not, x_72 + x_73 = 138 240 000 does, and a third level
+    // (188 928 000 + 186 624 000) does not: 67 - 71 alone, {72, 73}, {74}: 74 chunks.
     {
       Args c3{120, 75, 1, 1442 * 1021, 64800, 8, 8, {}, true, 0, 200 * GiB, 0};
       for (int64_t l = 0; l < 75; ++l) c3.used.push_back(1000000 - 12800 * l);
       const smm::GroupChunkPlan p = plan_of(c3);
       if (!p.pack || p.chunks.size() <= 1) ++gbad;
       for (const smm::GroupChunk& c : p.chunks) gbad += c.x_bytes > 4 * 256 * MiB;
+      std::vector<C> want;
+      for (int64_t l = 0; l < 72; ++l) want.push_back({0, 120, l, 1, (size_t)(960000000 - 12288000 * l)});
+      want.push_back({0, 120, 72, 2, 138240000});
+      want.push_back({0, 120, 74, 1, 50688000});
+      if (want.size() != 74) ++gbad;
+      expect(c3, true, want);
     }
+    // ADVICE.md's case: D >= S, one wide level and 24 thin or empty ones, the free memory of a 288-GB card.  S = 100 000,
+    // D = 200 000, f64, 64 outer indices; level 0 uses 60 000 cells, level l >= 1 uses (l - 1) % 3 = 0, 1, 2, 0, ... cells
+    // (60 024 of 2 500 000: packed).  32 outer indices of all levels are 32 * (480 192 + 25 * 1 600 000) B = 1.3 GB > 1 GiB:
+    // level-major.  bo = min(1 GiB / 480 000 = 2236, 256 GiB / 8 / (480 000 + 1 600 000) = 16 519, 64) = 64.  A level
+    // is 64 * 200 000 * 8 = 102 400 000 B of Y and U * 512 B of X (level 0: 30 720 000): two levels' Y (204 800 000) fit
+    // the 268 435 456 with any of these X, three (307 200 000) never do.  So {0, 1} 30 720 000 + 0, then pairs
+    // {2, 3} (1 + 2) * 512 = 1536, {4, 5} 512, {6, 7} 1024, ... repeating, and {24} (U = 2) alone: 13 chunks of at most
+    // 235 520 000 B.  Bounded by X alone, all 25 levels made ONE chunk with 2 560 000 000 B of Y, four times over in
+    // device and pinned memory.
+    {
+      Args adv{64, 25, 1, 100000, 200000, 8, 8, {60000}, true, 0, 256 * GiB, 0};
+      for (int64_t l = 1; l < 25; ++l) adv.used.push_back((l - 1) % 3);
+      expect(adv, true, {{0, 64, 0, 2, 30720000}, {0, 64, 2, 2, 1536}, {0, 64, 4, 2, 512}, {0, 64, 6, 2, 1024},
+                         {0, 64, 8, 2, 1536}, {0, 64, 10, 2, 512}, {0, 64, 12, 2, 1024}, {0, 64, 14, 2, 1536},
+                         {0, 64, 16, 2, 512}, {0, 64, 18, 2, 1024}, {0, 64, 20, 2, 1536}, {0, 64, 22, 2, 512},
+                         {0, 64, 24, 1, 1024}});
+      const smm::GroupChunkPlan p = plan_of(adv);
+      if (p.max_y > 2 * (size_t)102400000 || p.max_x != 30720000) ++gbad;
+    }
+    // Seeded sweep: every plan of 3000 drawn calls keeps the invariants of plan_of.  Sizes from a handful of cells to
+    // config 3's, D / S from 1 / 64 to 64, 2-, 4- and 8-byte cells, four shapes of used counts (dense; thinning with depth
+    // as config 3; one wide level and runs of levels with 0, 1 or 2 used cells; thinning into an all-empty tail), packing
+    // allowed or not, a requested chunk size, unknown / little / a card's free memory, the default and small budgets.
+    const long long hand_bad = gbad;
+    {
+      uint64_t state = 0x9e3779b97f4a7c15ull;
+      auto next = [&]() {   // splitmix64
+        uint64_t z = (state += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        return z ^ (z >> 31);
+      };
+      auto below = [&](uint64_t n) { return (int64_t)(next() % n); };
+      const int64_t sizes[] = {16, 288, 5000, 64800, 259200, 1472282, 2000000};
+      const int64_t ratio_num[] = {1, 1, 1, 1, 2, 8, 64}, ratio_den[] = {64, 8, 2, 1, 1, 1, 1};
+      const size_t cell[] = {2, 4, 8};
+      const int64_t requested[] = {0, 0, 0, 1, 7};
+      for (int it = 0; it < 3000; ++it) {
+        Args a;
+        a.n_outer = it % 5 == 0 ? 1 + below(400) : 1 + below(40) * below(11);   // short batches as often as long ones
+        a.n_lev = 1 + below(90);
+        a.n_inner = 1 + below(3);
+        a.S = sizes[below(7)] + below(3);
+        const int64_t r = below(7);
+        a.D = std::max<int64_t>(1, a.S * ratio_num[r] / ratio_den[r]);
+        a.xsz = cell[below(3)];
+        a.ysz = cell[below(3)];
+        const int64_t pattern = below(4), wide = 1 + below(a.S * 4 / 5);
+        for (int64_t l = 0; l < a.n_lev; ++l) {
+          int64_t u;
+          if (pattern == 0) u = a.S - below(a.S / 4 + 1);                                   // dense: rarely packed
+          else if (pattern == 1) u = std::max<int64_t>(0, wide - wide * l / a.n_lev);       // thinning with depth
+          else if (pattern == 2) u = l % 23 == 0 ? wide : below(3);                         // wide, then runs of 0, 1, 2
+          else u = l < a.n_lev / 3 ? std::max<int64_t>(1, wide - wide * 3 * l / a.n_lev) : 0;   // an all-empty tail
+          a.used.push_back(u);
+        }
+        a.allowed = below(8) != 0;
+        a.requested = requested[below(5)];
+        const int64_t f = below(4);
+        a.free_bytes = f == 0 ? 0 : f == 1 ? (size_t)(1 + below(4096)) << 20 : f == 2 ? 6 * GiB : 256 * GiB;
+        const int64_t b = below(3);
+        a.budget_kb = b == 0 ? 0 : b == 1 ? 1 + below(512) : 4096 << below(7);
+        plan_of(a);
+      }
+      // the sweep reached what it is for: level-major plans with chunks of several levels, chunks that the Y bound
+      // ended, plans that the free memory bounds, whole rows
+      if (n_level_major < 300 || n_multi < 1000 || n_y_ended < 300 || n_mem_bound < 10 || n_whole < 300) ++gbad;
+    }
+    printf("GSWEEPBAD %lld %lld %lld %lld %lld %lld\n", gbad - hand_bad, n_level_major, n_multi, n_y_ended, n_mem_bound, n_whole);
     printf("GCHUNKBAD %lld\n", gbad);
   }
   // exact-zero links dropped: what is left is the same matrix without its zeros

@@ -101,6 +101,10 @@ def test_builder_under_sanitizers(harness, rng, case, threads):
     assert fault[1] == "0" and (int(fault[2]) > 0 or threads == 1)
     assert "CHUNKBAD 0" in lines            # host pipelines size their chunks from X AND Y bytes (U << D)
     assert "GCHUNKBAD 0" in lines           # chunk plan of smm_group_apply_host: outer blocks or level-major, by hand
+    # ... and over a seeded sweep of calls: GSWEEPBAD <bad plans> <level-major plans> <chunks of several levels> <chunks
+    # ended by the Y bound> <plans bound by the free memory> <whole-row plans>
+    sweep = [ln.split() for ln in lines if ln.startswith("GSWEEPBAD")][0]
+    assert sweep[1] == "0" and all(int(v) > 0 for v in sweep[2:]), sweep
     prune = [ln.split() for ln in lines if ln.startswith("PRUNEBAD")][0]
     assert prune[1] == "0" and int(prune[2]) == int((val == 0.0).sum())     # exact-zero links dropped, rest intact
     check_pool_line(lines)
