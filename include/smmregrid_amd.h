@@ -109,6 +109,26 @@ typedef struct smm_cf_encode_t {
   int32_t reserved;  /* 0 */
 } smm_cf_encode_t;
 
+/* GRIB simple packing (smm_apply_grib / smm_apply_host_grib): the data section of a message goes to the kernel as it
+ * is on disk and is unpacked there.  One rule per batch row -- a row is one GRIB field, with its own R, E, D and bit
+ * width.  Element i of row b is the unsigned big-endian integer q of `nbits` bits at bit position
+ * 8 * byte_off + i * nbits of x (any byte alignment, any width 0..32), and becomes a field value in float64:
+ *     t = (double)q * bscale;                                   exact (bscale is a power of two)
+ *     t = ref + t;                                              one rounding
+ *     t = t / ddiv;                                             IEEE division; skipped, with the same bits, when ddiv == 1.0
+ *     v = (float)t;                                             round to nearest even, subnormals kept
+ * v then takes the place of an element of a float32 field (fill float32(1e20) for a non-finite v, promotion f32 -> f64,
+ * the plain epilogue): the results are bit-identical to smm_apply with SMM_F32 X on the field decoded on the host by
+ * (ref + q * 2^E) / 10.0^D in float64 and stored as float32.  nbits == 0 is a constant field (q = 0, no bits read). */
+typedef struct smm_grib_row_t {   /* one batch row = one GRIB field, 40 B */
+  uint64_t byte_off;  /* of the row's first packed value, from x */
+  double ref;         /* R widened to double (IBM float of edition 1, IEEE f32 of edition 2) */
+  double bscale;      /* 2^E, exactly a power of two in the normal range */
+  double ddiv;        /* 10.0^D as the host computes it; finite, > 0 */
+  int32_t nbits;      /* 0..32; 0 = constant field, no bits read */
+  int32_t reserved;   /* 0 */
+} smm_grib_row_t;
+
 /* smm_apply flags.  Bits outside this set are refused with SMM_ERR_INVALID by every entry that takes `flags`
  * (ABI <= 4 encoded kernel variants in bits 16..23: those are smm_debug_set_tuning knobs now). */
 enum {
@@ -394,6 +414,41 @@ int smm_apply_host_pk(smm_operator_t op,
                       void* y_host, int y_dtype, int64_t ldy,
                       int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows,
                       const smm_cf_decode_t* cf, const smm_cf_encode_t* enc);
+
+/*
+ * smm_apply / smm_apply_host for GRIB simple-packed fields shipped RAW (smm_grib_row_t above): x holds the packed bit
+ * streams of n_batch fields -- typically the file's bytes as they are -- and rows[b] says where batch row b starts in
+ * it and how it decodes; rows need not lie in buffer order, may have different widths and may overlap.  2 B per cell
+ * at 16 bits (1.5 B at 12) cross PCIe and HBM instead of 4, and no host decode runs.  The kernel is the row-per-lane
+ * SELL-64 kernel with the bit extraction and the decode in its gather (two instantiations, without and with the f64
+ * division: the one without runs when every row of the call has ddiv == 1.0; their bits are identical).
+ *   smm_apply_grib       x device bytes, 4-byte aligned, the allocation covering x_bytes rounded up to 4 (the kernel
+ *                        reads whole 32-bit words, never past that).  rows is a HOST array (pageable or page-locked): it is copied on `stream`
+ *                        into a device table the operator owns (grown on demand) and may be reused on return.  Calls on
+ *                        one operator share that table: they take turns, and are ordered against each other only on
+ *                        one stream -- concurrent calls on different streams need one operator handle each.
+ *   smm_apply_host_grib  x_host host bytes (no alignment needed), Y host (n_batch, ldy).  Chunks of consecutive rows flow
+ *                        through the pipeline of smm_apply_host: each row's ceil(n_src * nbits / 8) data bytes are copied
+ *                        into the pinned staging back to back at 4-byte-aligned starts (pinned x_host too: the rows of a
+ *                        chunk need not be adjacent in a file), the chunk's table rides in front of them.  A chunk is
+ *                        sized by bytes, not rows (rows may differ in width): staged X plus rows * n_dst * 8 of Y against
+ *                        ~256 MiB and an eighth of the free device memory (a chunk's X and Y exist twice on the
+ *                        device: a quarter in all); chunk_rows > 0 fixes the rows per chunk.
+ *                        SMM_HOST_STAT_H2D_BYTES counts the staged bytes with their <= 3 B pads and the tables.
+ * y_dtype must be SMM_F64 (else SMM_ERR_UNSUPPORTED).  SMM_APPLY_MASKED and SMM_APPLY_NO_FILL work as for float fields,
+ * SMM_APPLY_KERNEL_SELL is accepted (it is the kernel that runs); SMM_APPLY_SKIPNA, SMM_APPLY_KERNEL_TILE and the
+ * batch-fastest / host-pack flags are SMM_ERR_UNSUPPORTED.  SMM_ERR_INVALID, before any device is touched: flag bits
+ * outside the set, null pointers, a negative n_batch, ldy < n_dst, a misaligned x (device entry) or y, nbits outside
+ * 0..32, reserved != 0, a bscale that is not a normal power of two, a ddiv that is not finite or <= 0, a non-finite ref,
+ * a row whose [byte_off, byte_off + ceil(n_src * nbits / 8)) leaves [0, x_bytes).  The rules are checked before the
+ * operator handle is looked at (a NULL handle is SMM_ERR_INVALID, as everywhere).
+ */
+int smm_apply_grib(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows /* host */,
+                   void* y, int y_dtype, int64_t ldy, int64_t n_batch,
+                   double remap_area_min, unsigned flags, void* stream);
+int smm_apply_host_grib(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                        void* y_host, int y_dtype, int64_t ldy, int64_t n_batch,
+                        double remap_area_min, unsigned flags, int64_t chunk_rows);
 
 /*
  * Masked-level apply (regrid.py:387-418 in one launch).  The kept dims of the

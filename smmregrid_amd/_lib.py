@@ -81,6 +81,15 @@ class CfEncodeStruct(ctypes.Structure):
 
 _cep = ctypes.POINTER(CfEncodeStruct)
 
+
+class GribRowStruct(ctypes.Structure):
+    """smm_grib_row_t: where one GRIB field starts in the packed bytes and how it decodes"""
+    _fields_ = [("byte_off", ctypes.c_uint64), ("ref", _dbl), ("bscale", _dbl), ("ddiv", _dbl),
+                ("nbits", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+_grp = ctypes.POINTER(GribRowStruct)
+
 # name -> argtypes; every entry point returns int status except the two noted
 SIGNATURES = {
     "smm_device_count": [ctypes.POINTER(_int)],
@@ -140,6 +149,8 @@ SIGNATURES = {
     "smm_apply_pk": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _p, _cfp, _cep],
     "smm_apply_sb_pk": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _p, _cfp, _cep],
     "smm_apply_host_pk": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _i64, _cfp, _cep],
+    "smm_apply_grib": [_p, _p, _i64, _grp, _p, _int, _i64, _i64, _dbl, _uint, _p],
+    "smm_apply_host_grib": [_p, _p, _i64, _grp, _p, _int, _i64, _i64, _dbl, _uint, _i64],
     "smm_group_apply": [_p, _p, _int, _i64, _i64, _i64, _p, _int, _i64, _i64, _i64,
                         _i64, _i64, _i64, _p, _p, _dbl, _uint, _p],
     "smm_group_prepare_sb": [_p],

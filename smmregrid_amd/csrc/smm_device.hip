@@ -37,6 +37,8 @@
 #include "smm_internal.h"
 #include "smm_built.hpp"
 #include "smm_devmem.hpp"
+#include "smm_grib.hpp"
+#include "smm_grib_codec.hpp"
 
 #pragma clang fp contract(off)
 
@@ -248,6 +250,9 @@ struct smm_operator {
   DeviceBuf<int32_t> d_csr_col;       // source cell
   DeviceBuf<int32_t> d_csr_colp;      // rank of the source cell among the used cells (packed X)
   DeviceBuf<double> d_csr_val;
+  // row table of smm_apply_grib on the device, grown on demand; calls on one operator take turns filling it
+  std::mutex grib_mu;
+  DeviceBuf<smm_grib_row_t> d_grib_rows;
   std::atomic<int> group_refs{0};  // groups borrowing this operator (their descriptors hold its device pointers)
   int native = 0;            // shape of the operator's own plan (choose_native_plan)
   int native_plan() const { return native; }
@@ -1344,6 +1349,167 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int64_t ld
   return run_host_pipeline(pipe, n_chunks, st, launch, deliver);
 }
 
+// ---- GRIB simple-packed fields shipped raw: smm_apply_grib / smm_apply_host_grib (kernel: smm_grib.hip)
+
+// Everything the two entries refuse before the operator is looked at and before any device is touched.
+static int check_grib_call(const void* x, bool x_device, int64_t x_bytes, const smm_grib_row_t* rows, const void* y,
+                           int y_dtype, int64_t n_batch, double area_min, unsigned flags) {
+  if (int frc = check_flags(flags)) return frc;
+  if (flags & ~(unsigned)(SMM_APPLY_MASKED | SMM_APPLY_NO_FILL | SMM_APPLY_KERNEL_SELL))
+    return fail(SMM_ERR_UNSUPPORTED, "GRIB fields run the SELL kernel on whole rows: SMM_APPLY_SKIPNA, SMM_APPLY_KERNEL_TILE "
+                                     "and the batch-fastest / host-pack flags are not built for them");
+  if (y_dtype != SMM_F64) return fail(SMM_ERR_UNSUPPORTED, "GRIB fields produce SMM_F64 results");
+  if (n_batch < 0) return fail(SMM_ERR_INVALID, "negative batch size");
+  if (x_bytes < 0) return fail(SMM_ERR_INVALID, "negative x_bytes");
+  if ((!x && x_bytes > 0) || !y || (!rows && n_batch > 0)) return fail(SMM_ERR_INVALID, "null field, result or row-table pointer");
+  if (x_device && (uintptr_t)x % 4) return fail(SMM_ERR_INVALID, "field pointer is not 4-byte aligned");
+  if ((uintptr_t)y % 8) return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
+  if (int arc = check_area_min(area_min)) return arc;
+  std::string err;
+  if (!smm::check_grib_rules(rows, n_batch, err)) return fail(SMM_ERR_INVALID, err);
+  return SMM_OK;
+}
+// ... and what needs the operator's sizes.
+static int check_grib_operator(smm_operator_t op, int64_t x_bytes, const smm_grib_row_t* rows, int64_t ldy, int64_t n_batch,
+                               double area_min, unsigned flags) {
+  if (!op) return fail(SMM_ERR_INVALID, "null operator");
+  if (n_batch > 0 && ldy < op->csr.n_dst) return fail(SMM_ERR_INVALID, "ldy smaller than the grid size");
+  std::string err;
+  if (!smm::check_grib_ranges(rows, n_batch, op->csr.n_src, x_bytes, err)) return fail(SMM_ERR_INVALID, err);
+  return check_epilogue(op, flags & SMM_APPLY_MASKED, area_min, "the operator");
+}
+static bool grib_needs_division(const smm_grib_row_t* rows, int64_t n_batch) {
+  for (int64_t b = 0; b < n_batch; ++b)
+    if (rows[b].ddiv != 1.0) return true;
+  return false;
+}
+
+// n_batch rows whose table is on the device already (d_rows) over the x_bytes bytes at x: one launch, or parts of the
+// batch when the grid would pass the limit (smm::split_batch, as run_apply)
+static int launch_grib_rows(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* d_rows, bool div, void* y,
+                            int64_t ldy, int64_t n_batch, double area_min, unsigned flags, hipStream_t s) {
+  GribArgs a{};
+  a.descs = op->d_desc.get();
+  // no data bytes at all (every row has 0 bits): the loads, clamped to word 0, read the table instead
+  a.x = x_bytes > 0 ? (const uint32_t*)x : (const uint32_t*)d_rows;
+  a.last_word = x_bytes > 0 ? smm_grib::align4((uint64_t)x_bytes) / 4 - 1 : 0;
+  a.ldy = ldy;
+  a.n_dst = op->csr.n_dst;
+  a.n_dblocks = ((a.n_dst + 63) / 64 + kWavesPerBlock - 1) / kWavesPerBlock;
+  a.area_min = area_min;
+  a.masked = (flags & SMM_APPLY_MASKED) ? 1 : 0;
+  const bool fill = !(flags & SMM_APPLY_NO_FILL);
+  auto blocks_for = [&](int64_t n_o, int64_t) -> int64_t {
+    const int bt = smm_launch::sell_batch_rows(n_o);
+    return a.n_dblocks * ((n_o + bt - 1) / bt);
+  };
+  auto launch_part = [&](int64_t o0, int64_t n_o, int64_t, int64_t) -> int {
+    GribArgs p = a;
+    p.rows = d_rows + o0;
+    p.y = (double*)y + o0 * ldy;
+    p.n_j = n_o;
+    return smm_launch::launch_grib(p, div, fill, s);
+  };
+  const int rc = smm::split_batch(0, n_batch, 0, 1, grid_limit(), blocks_for, launch_part);
+  if (rc == -1)
+    return fail(SMM_ERR_INVALID, "one batch row alone needs a launch grid beyond " + std::to_string(grid_limit()) +
+                                     " workgroups (destination blocks)");
+  return rc;
+}
+
+static int smm_apply_grib_impl(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows, void* y,
+                               int64_t ldy, int64_t n_batch, double area_min, unsigned flags, void* stream) {
+  if (n_batch == 0 || op->csr.n_dst == 0) return SMM_OK;
+  DeviceGuard guard(op->device);
+  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lock(op->grib_mu);
+  if (op->d_grib_rows.bytes() < (size_t)n_batch * sizeof(smm_grib_row_t)) {
+    // freeing the old table waits for the device: no kernel still reads it
+    const size_t have = op->d_grib_rows.bytes() / sizeof(smm_grib_row_t);
+    SMM_HIP(op->d_grib_rows.alloc(std::max<size_t>((size_t)n_batch, 2 * have)));
+  }
+  // `rows` may be reused on return: from pageable memory the runtime has taken the bytes when hipMemcpyAsync returns,
+  // from page-locked memory it has not -- such a table goes through a pageable copy first.  The copy itself is ordered
+  // on the stream behind the kernel of an earlier call that still reads the device table.
+  std::vector<smm_grib_row_t> pageable;
+  if (is_pinned(rows)) {
+    pageable.assign(rows, rows + n_batch);
+    rows = pageable.data();
+  }
+  SMM_HIP(hipMemcpyAsync(op->d_grib_rows.get(), rows, (size_t)n_batch * sizeof(smm_grib_row_t), hipMemcpyHostToDevice, s));
+  return launch_grib_rows(op, x, x_bytes, op->d_grib_rows.get(), grib_needs_division(rows, n_batch), y, ldy, n_batch, area_min,
+                          flags, s);
+}
+
+static int smm_apply_host_grib_impl(smm_operator_t op, const void* x_host, const smm_grib_row_t* rows, void* y_host,
+                                    int64_t ldy, int64_t n_batch, double area_min, unsigned flags, int64_t chunk_rows) {
+  const int64_t S = op->csr.n_src, D = op->csr.n_dst;
+  if (n_batch == 0 || D == 0) return SMM_OK;
+  DeviceGuard guard(op->device);
+  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
+  // chunks of consecutive rows, sized by their bytes (rows differ in width): smm_internal.h
+  const smm::GribChunkPlan plan = smm::plan_grib_chunks(rows, n_batch, S, D, chunk_rows, free_device_bytes());
+  const bool div = grib_needs_division(rows, n_batch);
+  const bool y_direct = is_pinned(y_host);
+  const size_t yrow = (size_t)ldy * 8;
+
+  std::lock_guard<std::mutex> pipe_lock(op->pipe_mu);
+  HostPipe& pipe = op->pipe;
+  const size_t y_chunk = (size_t)plan.max_rows * D * 8;
+  SMM_HIP(pipe.ensure(plan.max_x, y_chunk, plan.max_x, y_direct ? 0 : y_chunk));
+
+  CallStats st;
+  auto deliver = [&](int64_t c, int b) -> int {   // results of chunk c: pinned -> user rows
+    if (y_direct) return SMM_OK;
+    StageTimer t(st.v[SMM_HOST_STAT_COPY_OUT_MS]);
+    const smm::GribChunk& ch = plan.chunks[(size_t)c];
+    if (ldy == D) return host_copy((char*)y_host + (size_t)ch.r0 * yrow, pipe.hy[b].get(), (size_t)ch.nr * D * 8);
+    for (int64_t r = 0; r < ch.nr; ++r)
+      memcpy((char*)y_host + (size_t)(ch.r0 + r) * yrow, (char*)pipe.hy[b].get() + (size_t)r * D * 8, (size_t)D * 8);
+    return SMM_OK;
+  };
+  // Staging of a chunk: its table first, then each row's data bytes at the next 4-byte-aligned offset; the table's
+  // byte_off are those offsets, from the start of the buffer.  A pinned x_host is staged all the same: the rows of a
+  // chunk need not be adjacent in it.
+  auto launch = [&](int64_t c, int b) -> int {
+    const smm::GribChunk& ch = plan.chunks[(size_t)c];
+    char* hx = (char*)pipe.hx[b].get();
+    {
+      StageTimer t(st.v[SMM_HOST_STAT_STAGE_IN_MS]);
+      smm_grib_row_t* table = (smm_grib_row_t*)hx;
+      uint64_t cursor = (uint64_t)ch.nr * sizeof(smm_grib_row_t);
+      for (int64_t r = 0; r < ch.nr; ++r) {
+        table[r] = rows[ch.r0 + r];
+        table[r].byte_off = cursor;
+        cursor += smm_grib::align4(smm_grib::row_bytes((uint64_t)S, table[r].nbits));
+      }
+      for (int64_t r = 0; r < ch.nr; ++r)   // each row's copy is spread over the staging pool (host_copy)
+        if (int rc = host_copy(hx + table[r].byte_off, (const char*)x_host + rows[ch.r0 + r].byte_off,
+                               (size_t)smm_grib::row_bytes((uint64_t)S, table[r].nbits)))
+          return rc;
+    }
+    SMM_HIP(pipe.mark(b, 0));
+    SMM_HIP(hipMemcpyAsync(pipe.dx[b].get(), hx, ch.x_bytes, hipMemcpyHostToDevice, pipe.stream[b]));
+    st.v[SMM_HOST_STAT_H2D_BYTES] += (double)ch.x_bytes;
+    SMM_HIP(pipe.mark(b, 1));
+    if (int rc = launch_grib_rows(op, pipe.dx[b].get(), (int64_t)ch.x_bytes, (const smm_grib_row_t*)pipe.dx[b].get(), div,
+                                  pipe.dy[b].get(), D, ch.nr, area_min, flags, pipe.stream[b]))
+      return rc;
+    st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)ch.nr * D * 8);
+    SMM_HIP(pipe.mark(b, 2));
+    if (!y_direct) {
+      SMM_HIP(hipMemcpyAsync(pipe.hy[b].get(), pipe.dy[b].get(), (size_t)ch.nr * D * 8, hipMemcpyDeviceToHost, pipe.stream[b]));
+    } else {
+      SMM_HIP(hipMemcpy2DAsync((char*)y_host + (size_t)ch.r0 * yrow, yrow, pipe.dy[b].get(), (size_t)D * 8, (size_t)D * 8,
+                               (size_t)ch.nr, hipMemcpyDeviceToHost, pipe.stream[b]));
+    }
+    SMM_HIP(pipe.mark(b, 3));
+    return SMM_OK;
+  };
+  return run_host_pipeline(pipe, (int64_t)plan.chunks.size(), st, launch, deliver);
+}
+
 static int smm_operator_mask_apply_impl(smm_operator_t op, const int32_t* src_imask, int32_t* dst_imask) {
   if (!op || !src_imask || !dst_imask) return fail(SMM_ERR_INVALID, "null argument");
   DeviceGuard guard(op->device);
@@ -1981,6 +2147,25 @@ int smm_apply_host_pk(smm_operator_t op, const void* x_host, int x_dtype, int64_
                       const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
   return apply_entry(Entry::pk, x_dtype, y_dtype, remap_area_min, flags, cf, enc, [&](const CallDesc& c) {
     return smm_apply_host_impl(op, x_host, ldx, y_host, ldy, n_batch, chunk_rows, c);
+  });
+}
+
+int smm_apply_grib(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows, void* y, int y_dtype,
+                   int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream) {
+  return guarded([&] {
+    if (int rc = check_grib_call(x, true, x_bytes, rows, y, y_dtype, n_batch, remap_area_min, flags)) return rc;
+    if (int rc = check_grib_operator(op, x_bytes, rows, ldy, n_batch, remap_area_min, flags)) return rc;
+    return smm_apply_grib_impl(op, x, x_bytes, rows, y, ldy, n_batch, remap_area_min, flags, stream);
+  });
+}
+
+int smm_apply_host_grib(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows, void* y_host,
+                        int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags,
+                        int64_t chunk_rows) {
+  return guarded([&] {
+    if (int rc = check_grib_call(x_host, false, x_bytes, rows, y_host, y_dtype, n_batch, remap_area_min, flags)) return rc;
+    if (int rc = check_grib_operator(op, x_bytes, rows, ldy, n_batch, remap_area_min, flags)) return rc;
+    return smm_apply_host_grib_impl(op, x_host, rows, y_host, ldy, n_batch, remap_area_min, flags, chunk_rows);
   });
 }
 

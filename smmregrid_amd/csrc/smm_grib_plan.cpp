@@ -1,0 +1,73 @@
+// Host side of the GRIB entries that needs no device: the refusals of a row table and the chunk plan of
+// smm_apply_host_grib (declared in smm_internal.h).  Plain C++: tests/cpp/grib_harness.cpp links this file.
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "../../include/smmregrid_amd.h"
+#include "smm_grib_codec.hpp"
+#include "smm_internal.h"
+
+namespace smm {
+
+bool check_grib_rules(const smm_grib_row_t* rows, int64_t n_batch, std::string& err) {
+  for (int64_t b = 0; b < n_batch; ++b) {
+    const smm_grib_row_t& r = rows[b];
+    const std::string at = "rows[" + std::to_string(b) + "]";
+    if (r.nbits < 0 || r.nbits > 32) return err = at + ".nbits must be within 0..32", false;
+    if (r.reserved != 0) return err = at + ".reserved must be 0", false;
+    int e = 0;
+    if (!std::isnormal(r.bscale) || r.bscale <= 0.0 || std::frexp(r.bscale, &e) != 0.5)
+      return err = at + ".bscale must be a power of two in the normal range (2^E)", false;
+    if (!std::isfinite(r.ddiv) || !(r.ddiv > 0.0)) return err = at + ".ddiv must be finite and > 0 (10^D)", false;
+    if (!std::isfinite(r.ref)) return err = at + ".ref must be finite", false;
+  }
+  return true;
+}
+
+bool check_grib_ranges(const smm_grib_row_t* rows, int64_t n_batch, int64_t n_src, int64_t x_bytes, std::string& err) {
+  for (int64_t b = 0; b < n_batch; ++b) {
+    const uint64_t need = smm_grib::row_bytes((uint64_t)n_src, rows[b].nbits);   // n_src < 2^31, nbits <= 32: no overflow
+    if (rows[b].byte_off > (uint64_t)x_bytes || need > (uint64_t)x_bytes - rows[b].byte_off)
+      return err = "rows[" + std::to_string(b) + "]: bytes [" + std::to_string(rows[b].byte_off) + ", " +
+                   std::to_string(rows[b].byte_off) + " + " + std::to_string(need) + ") leave the buffer of " +
+                   std::to_string(x_bytes) + " bytes", false;
+  }
+  return true;
+}
+
+GribChunkPlan plan_grib_chunks(const smm_grib_row_t* rows, int64_t n_batch, int64_t n_src, int64_t D,
+                               int64_t requested_rows, size_t free_bytes) {
+  constexpr size_t kTarget = (size_t)256 << 20, kMinChunk = (size_t)32 << 20;
+  constexpr int64_t kMinChunks = 8;
+  GribChunkPlan plan;
+  auto row_cost_x = [&](int64_t b) {
+    return sizeof(smm_grib_row_t) + (size_t)smm_grib::align4(smm_grib::row_bytes((uint64_t)n_src, rows[b].nbits));
+  };
+  const size_t y_row = (size_t)std::max<int64_t>(D, 0) * 8;
+  if (requested_rows <= 0) {
+    size_t total = 0;
+    for (int64_t b = 0; b < n_batch; ++b) total += row_cost_x(b) + y_row;
+    plan.target = std::min(kTarget, std::max(kMinChunk, total / (size_t)kMinChunks));
+    if (free_bytes > 0) plan.target = std::min(plan.target, std::max<size_t>(free_bytes / 8, 1));
+  }
+  for (int64_t b = 0; b < n_batch;) {
+    GribChunk c{b, 0, 0};
+    size_t bytes = 0;
+    while (b < n_batch) {
+      const size_t x = row_cost_x(b);
+      if (requested_rows > 0 ? c.nr >= requested_rows : (c.nr > 0 && bytes + x + y_row > plan.target)) break;
+      bytes += x + y_row;
+      c.x_bytes += x;
+      ++c.nr;
+      ++b;
+    }
+    plan.max_x = std::max(plan.max_x, c.x_bytes);
+    plan.max_rows = std::max(plan.max_rows, c.nr);
+    plan.chunks.push_back(c);
+  }
+  return plan;
+}
+
+}  // namespace smm

@@ -6,6 +6,8 @@
 #include <string>
 #include <vector>
 
+struct smm_grib_row_t;   // include/smmregrid_amd.h
+
 namespace smm {
 
 // Canonical CSR: row = destination cell, columns ascending, duplicates summed.
@@ -185,5 +187,29 @@ struct GroupChunkPlan {
 GroupChunkPlan plan_group_chunks(int64_t n_outer, int64_t n_lev, int64_t n_inner, int64_t S, int64_t D, size_t xsz,
                                  size_t ysz, const int64_t* used_per_level, bool packing_allowed,
                                  int64_t requested_outer, size_t free_bytes, int64_t budget_kb);
+
+// ---- GRIB simple-packed fields shipped raw (smm_apply_grib / smm_apply_host_grib; smm_grib_plan.cpp, plain C++).
+// What the two entries refuse about their row table before any device is touched: false + err.  check_grib_rules looks
+// at the rules alone (nbits, reserved, bscale a normal power of two, ddiv finite and > 0, ref finite); check_grib_ranges
+// at where each row's ceil(n_src * nbits / 8) bytes lie in [0, x_bytes).
+bool check_grib_rules(const smm_grib_row_t* rows, int64_t n_batch, std::string& err);
+bool check_grib_ranges(const smm_grib_row_t* rows, int64_t n_batch, int64_t n_src, int64_t x_bytes, std::string& err);
+// Chunk plan of smm_apply_host_grib: consecutive rows [r0, r0 + nr) per chunk.  Rows differ in width, so a chunk is sized
+// by bytes, not by rows: its staging -- the table (one smm_grib_row_t per row) and each row's data bytes rounded up to 4
+// -- plus nr * D * 8 of Y stay within the target (~256 MiB; an eighth of the call so that chunks overlap, but no less
+// than 32 MiB; an eighth of free_bytes when that is known: the four device buffers of a chunk take a quarter of it at
+// most).  A row that alone exceeds the target still gets a chunk of its own.  requested_rows > 0: that many rows per chunk.
+struct GribChunk {
+  int64_t r0, nr;
+  size_t x_bytes;   // staged bytes of the chunk: table + padded rows
+};
+struct GribChunkPlan {
+  std::vector<GribChunk> chunks;   // cover [0, n_batch) exactly once, in order
+  size_t target = 0;               // the byte bound in force (0 with requested_rows)
+  size_t max_x = 0;                // largest staged X of one chunk
+  int64_t max_rows = 0;            // most rows of one chunk
+};
+GribChunkPlan plan_grib_chunks(const smm_grib_row_t* rows, int64_t n_batch, int64_t n_src, int64_t D,
+                               int64_t requested_rows, size_t free_bytes);
 
 }  // namespace smm

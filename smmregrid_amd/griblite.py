@@ -35,6 +35,55 @@ class GribUnsupported(NotImplementedError):
     pass
 
 
+# smm_grib_row_t, field for field: one record per GRIB field of a variable kept raw (open_grib(path, decode=False))
+GRIB_ROW_DTYPE = np.dtype({"names": ["byte_off", "ref", "bscale", "ddiv", "nbits", "reserved"],
+                           "formats": ["<u8", "<f8", "<f8", "<f8", "<i4", "<i4"],
+                           "offsets": [0, 8, 16, 24, 32, 36], "itemsize": 40})
+
+
+class GribField:
+    """The fields of one GRIB variable kept as the file has them: `buf`, the file's bytes (one uint8 array shared by
+    every variable of the file), and `rows`, a GRIB_ROW_DTYPE record per field in (time, level) order that says where
+    the field's simple-packed values start in `buf` and how they decode -- value = (ref + q * bscale) / ddiv in float64,
+    stored as float32.  It stands where the decoded float32 array stands (`shape`, `dtype`, `np.asarray`), and
+    `Regridder(packed=True)` hands buf and rows to the GPU as they are (smm_apply_host_grib): the bits are unpacked in
+    the kernel, with the results of regridding `decode()`."""
+
+    dtype = np.dtype(np.float32)
+
+    def __init__(self, buf, rows, shape, n_points):
+        """n_points: grid points of one field -- the product of the trailing (horizontal) axes of `shape`."""
+        self.buf = buf
+        self.rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
+        self.shape = tuple(int(n) for n in shape)
+        self.n_points = int(n_points)
+        if self.rows.size * self.n_points != int(np.prod(self.shape)):
+            raise ValueError(f"{self.rows.size} GRIB fields of {self.n_points} points for a variable of shape {self.shape}")
+
+    @property
+    def ndim(self):
+        return len(self.shape)
+
+    @property
+    def size(self):
+        return int(np.prod(self.shape))
+
+    def decode(self):
+        """The float32 array `open_grib(path)` gives for this variable, bit for bit."""
+        out = np.empty((self.rows.size, self.n_points), dtype=np.float32)
+        for i, r in enumerate(self.rows):
+            out[i] = _decode_rule(self.buf, (int(r["byte_off"]), float(r["ref"]), float(r["bscale"]), float(r["ddiv"]),
+                                             int(r["nbits"])), self.n_points)
+        return out.reshape(self.shape)
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.decode()
+        return a if dtype is None else a.astype(dtype, copy=False)
+
+    def __repr__(self):
+        return f"<GribField {self.shape} float32, {self.rows.size} packed fields, widths {sorted(set(self.rows['nbits'].tolist()))}>"
+
+
 # ECMWF table 128 entries that turn up in climate work -> (cfgrib variable name, long name, units)
 _TABLE_128 = {
     31: ("siconc", "Sea ice area fraction", "(0 - 1)"), 34: ("sst", "Sea surface temperature", "K"),
@@ -103,8 +152,20 @@ def _unpack_bits(raw, nbits, count):
     return bits.astype(np.uint64) @ (np.uint64(1) << np.arange(nbits - 1, -1, -1, dtype=np.uint64))
 
 
+def _decode_rule(buf, rule, count):
+    """The float64 values of one message without a bitmap from its rule (file offset of the packed values, R, 2^E,
+    10^D, bit width): the statement the message classes evaluate, on the message's own bytes only."""
+    off, ref, scale, ddiv, nbits = rule
+    raw = bytes(memoryview(buf)[off:off + (count * nbits + 7) // 8])
+    return (ref + _unpack_bits(raw, nbits, count) * scale) / ddiv
+
+
 class _Field:
-    """Grid and coordinates shared by the fields of both editions."""
+    """Grid and coordinates shared by the fields of both editions.  `values` is None for a message read with
+    keep_raw (no bitmap: only its `raw_rule` was recorded); `field_values` decodes it on demand."""
+
+    def field_values(self, buf):
+        return self.values if self.values is not None else _decode_rule(buf, self.raw_rule, self.npoints)
 
     def _set_grid(self, rep, ni, nj, la1, lo1, la2, lo2, n_gauss, scan, pl, tol):
         if scan & 0x20:
@@ -155,7 +216,7 @@ class _Message(_Field):
     """One decoded GRIB-1 message: metadata + values in the file's scanning order (NaN where the bitmap says so)."""
     edition = 1
 
-    def __init__(self, buf, start):
+    def __init__(self, buf, start, keep_raw=False):
         if buf[start:start + 4] != b"GRIB":
             raise ValueError("not a GRIB message")
         if buf[start + 7] != 1:
@@ -207,6 +268,11 @@ class _Message(_Field):
         avail = ((len(bds) - 11) * 8 - (flag & 0x0F)) // nbits if nbits else count
         if avail < count:
             raise ValueError(f"GRIB data section holds {avail} values, the grid needs {count}")
+        # where the packed values lie in the file and how they decode (open_grib(decode=False)); None with a bitmap
+        self.raw_rule = None if bitmap is not None else (pos + 11, ref, scale, 10.0 ** self.decimal_scale, nbits)
+        if keep_raw and bitmap is None:
+            self.values = None               # nothing is unpacked: the rule is all a raw-kept variable needs
+            return
         x = _unpack_bits(bds[11:], nbits, count)
         packed = (ref + x * scale) / 10.0 ** self.decimal_scale
         if bitmap is None:
@@ -233,7 +299,8 @@ class _Field2(_Field):
     """One field of a GRIB-2 message (a message may repeat sections 2 - 7 / 3 - 7 / 4 - 7 for further fields)."""
     edition = 2
 
-    def __init__(self, discipline, sec1, sec3, sec4, sec5, sec6, sec7, prev_bitmap):
+    def __init__(self, discipline, sec1, sec3, sec4, sec5, sec6, sec7, prev_bitmap, data_pos=None, keep_raw=False):
+        """data_pos: file offset of section 7 (its packed values follow 5 octets later)."""
         self.centre = _uint(sec1[5:7])
         self.time = np.datetime64(f"{_uint(sec1[12:14]):04d}-{max(sec1[14], 1):02d}-{max(sec1[15], 1):02d}"
                                   f"T{sec1[16]:02d}:{sec1[17]:02d}:{sec1[18]:02d}")
@@ -293,6 +360,11 @@ class _Field2(_Field):
             raise ValueError(f"GRIB-2 data section codes {n_coded} values, grid and bitmap need {count}")
         if nbits and (len(sec7) - 5) * 8 < count * nbits:
             raise ValueError("GRIB-2 data section is shorter than its values")
+        self.raw_rule = None if (self.bitmap is not None or data_pos is None) else \
+            (data_pos + 5, ref, scale, 10.0 ** decimal, nbits)
+        if keep_raw and self.raw_rule is not None:
+            self.values = None
+            return
         packed = (ref + _unpack_bits(bytes(sec7[5:]), nbits, count) * scale) / 10.0 ** decimal
         if self.bitmap is None:
             self.values = packed
@@ -301,7 +373,7 @@ class _Field2(_Field):
             self.values[self.bitmap] = packed
 
 
-def _fields_of_message2(buf, start):
+def _fields_of_message2(buf, start, keep_raw=False):
     """The fields of the GRIB-2 message at `start`, and the message's length."""
     discipline, total = buf[start + 6], _uint(buf[start + 8:start + 16])
     if buf[start + total - 4:start + total] != b"7777":
@@ -320,7 +392,7 @@ def _fields_of_message2(buf, start):
             for need in (1, 3, 4, 5):
                 if need not in sec:
                     raise ValueError(f"GRIB-2 message without section {need}")
-            f = _Field2(discipline, sec[1], sec[3], sec[4], sec[5], sec.get(6), sec[7], bitmap)
+            f = _Field2(discipline, sec[1], sec[3], sec[4], sec[5], sec.get(6), sec[7], bitmap, data_pos=pos, keep_raw=keep_raw)
             bitmap = f.bitmap
             fields.append(f)
         pos += length
@@ -329,7 +401,12 @@ def _fields_of_message2(buf, start):
 
 def read_messages(path):
     with open(path, "rb") as f:
-        buf = f.read()
+        return _messages_of(f.read(), path)
+
+
+def _messages_of(buf, path, keep_raw=False):
+    """The messages of a file's bytes.  keep_raw: those without a bitmap are not unpacked (`values` is None, `raw_rule`
+    says how to)."""
     out, pos = [], 0
     while True:
         pos = buf.find(b"GRIB", pos)
@@ -337,13 +414,13 @@ def read_messages(path):
             break
         edition = buf[pos + 7] if pos + 8 <= len(buf) else 0
         if edition == 2:
-            fields, length = _fields_of_message2(buf, pos)
+            fields, length = _fields_of_message2(buf, pos, keep_raw)
             out.extend(fields)
             pos += length
             continue
         if edition != 1:
             raise GribUnsupported(f"GRIB edition {edition}")
-        m = _Message(buf, pos)
+        m = _Message(buf, pos, keep_raw)
         out.append(m)
         pos += m.length
     if not out:
@@ -351,9 +428,15 @@ def read_messages(path):
     return out
 
 
-def open_grib(path):
-    """Dataset of the fields of a GRIB file, one variable per parameter.  All messages must share one grid."""
-    msgs = read_messages(path)
+def open_grib(path, decode=True):
+    """Dataset of the fields of a GRIB file, one variable per parameter.  All messages must share one grid.
+    decode=False keeps every variable whose (time, level) slots are all filled by messages without a bitmap as a
+    `GribField` -- the file's bytes and one decode rule per field, which `Regridder(packed=True)` ships to the GPU as
+    they are; `np.asarray` of it is the decoded float32 array.  Any other variable is decoded as with decode=True."""
+    with open(path, "rb") as f:
+        file_bytes = f.read()
+    msgs = _messages_of(file_bytes, path, keep_raw=not decode)
+    shared = np.frombuffer(file_bytes, dtype=np.uint8) if not decode else None
     if len({m.grid_key for m in msgs}) != 1:
         raise GribUnsupported("GRIB file with fields on several grids")
     g = msgs[0]
@@ -394,23 +477,40 @@ def open_grib(path):
             name = f"{name}_{level_type}"
         times = sorted({m.time + np.timedelta64(int(round(m.step_hours * 3600)), "s") for m in group})
         levels = sorted({m.level for m in group})
-        arr = np.full((len(times), len(levels)) + hshape, np.nan, dtype=np.float32)
-        for m in group:
-            t = times.index(m.time + np.timedelta64(int(round(m.step_hours * 3600)), "s"))
-            arr[t, levels.index(m.level)] = m.values.reshape(hshape)
+        slots = [(times.index(m.time + np.timedelta64(int(round(m.step_hours * 3600)), "s")), levels.index(m.level))
+                 for m in group]
+        rows = np.zeros((len(times), len(levels)), dtype=GRIB_ROW_DTYPE)
+        filled = np.zeros((len(times), len(levels)), dtype=bool)
+        for m, slot in zip(group, slots):
+            if m.raw_rule is not None:
+                rows[slot] = m.raw_rule + (0,)
+                filled[slot] = True
+        # raw: every (time, level) slot filled by a message without a bitmap (a missing slot is NaN, which only a
+        # decoded array holds).  Such a variable is never unpacked here; any other is decoded as with decode=True
+        raw_ok = not decode and all(m.raw_rule is not None for m in group) and bool(filled.all())
+        arr = None
+        if not raw_ok:
+            arr = np.full((len(times), len(levels)) + hshape, np.nan, dtype=np.float32)
+            for m, slot in zip(group, slots):
+                arr[slot] = m.field_values(file_bytes).reshape(hshape)
         dims, vcoords = [], dict(coords)
         level_dim = (_LEVEL_DIMS_G2 if isinstance(param, tuple) else _LEVEL_DIMS).get(level_type, "level")
         if len(times) > 1:
             dims.append("time")
             vcoords["time"] = DataArray(np.array(times, dtype="datetime64[s]").astype(np.float64), dims=("time",),
                                         attrs={"units": "seconds since 1970-01-01", "standard_name": "time"})
-        else:
+        elif arr is not None:
             arr = arr[0:1]
         if len(levels) > 1:
             dims.append(level_dim)
             vcoords[level_dim] = DataArray(np.array(levels, dtype=np.float64), dims=(level_dim,))
-        arr = arr.reshape(tuple(n for n, keep in ((len(times), len(times) > 1), (len(levels), len(levels) > 1)) if keep)
-                          + hshape)
+        shape = tuple(n for n, keep in ((len(times), len(times) > 1), (len(levels), len(levels) > 1)) if keep) + hshape
+        if raw_ok:
+            if len(times) == 1:
+                rows = rows[0:1]
+            arr = GribField(shared, rows, shape, int(np.prod(hshape)))
+        else:
+            arr = arr.reshape(shape)
         ds[name] = DataArray(arr, dims=tuple(dims) + hdims, coords=vcoords, name=name,
                              attrs={"long_name": long_name, "units": units, "GRIB_paramId": param_id,
                                     "GRIB_gridType": grid_type, "GRIB_shortName": name})

@@ -320,6 +320,58 @@ class SparseOperator:
         return _apply_call("smm_apply_host", self.handle, x, (ldx,), out,
                            (self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows)), y_res, cf, cf_out, "out")
 
+    def _grib_rows(self, rows):
+        from .griblite import GRIB_ROW_DTYPE
+        rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
+        return rows, ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct))
+
+    def apply_grib(self, x, rows, x_bytes=None, y=None, masked=False, remap_area_min=0.0, flags=0, stream=None):
+        """Y = epilogue(fill(decode(X)) . W) for GRIB simple-packed fields resident in HBM as they are on disk
+        (smm_apply_grib).  x: a `DeviceArray` of uint8 -- or a raw device pointer with x_bytes -- holding the packed
+        bit streams (4-byte aligned; the array -- or the allocation behind a raw pointer -- must cover x_bytes rounded
+        up to 4, the kernel reads whole 32-bit words: a shorter DeviceArray is a ValueError); rows: one `GRIB_ROW_DTYPE`
+        record per batch row (where its values start in x, its reference value, 2^E, 10^D, its bit width).  The bits
+        are unpacked in the kernel's gather; the float64 result is bit-identical to `apply` on the float32 field a
+        host decode gives.  Returns a (B, D) DeviceArray."""
+        rows, rows_p = self._grib_rows(rows)
+        if isinstance(x, DeviceArray):
+            if x.dtype != np.uint8:
+                raise TypeError(f"apply_grib takes the packed bytes as uint8, got {x.dtype}")
+            x_ptr, n_bytes = ctypes.c_void_p(x.ptr), x.nbytes if x_bytes is None else int(x_bytes)
+            if (n_bytes + 3) // 4 * 4 > x.nbytes:      # the kernel reads whole 32-bit words
+                raise ValueError(f"x must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {x.nbytes}")
+        else:
+            if x_bytes is None:
+                raise TypeError("a raw device pointer needs x_bytes")
+            x_ptr, n_bytes = ctypes.c_void_p(int(x)), int(x_bytes)
+        n_batch = rows.size
+        if y is None:
+            y = DeviceArray((n_batch, self.n_dst), np.float64)
+        elif y.shape != (n_batch, self.n_dst) or y.dtype != np.float64:
+            raise ValueError(f"Y must be a float64 ({n_batch}, {self.n_dst}) DeviceArray")
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        _lib.call("smm_apply_grib", self.handle, x_ptr, n_bytes, rows_p, _ptr(y), _lib.SMM_F64, self.n_dst, n_batch,
+                  float(remap_area_min), fl, _stream_handle(stream))
+        return y
+
+    def apply_host_grib(self, buf, rows, out=None, masked=False, remap_area_min=0.0, flags=0, chunk_rows=0):
+        """The host twin (smm_apply_host_grib): buf is a host uint8 array -- typically a whole GRIB file -- and rows as
+        for `apply_grib`.  Each row's packed bytes are staged and cross PCIe as they are (2 B per cell at 16 bits), no
+        host decode runs.  Returns a float64 (B, D) numpy array, the bits of `apply_host` on the decoded float32 field."""
+        rows, rows_p = self._grib_rows(rows)
+        buf = np.ascontiguousarray(buf)
+        if buf.dtype != np.uint8 or buf.ndim != 1:
+            raise TypeError("apply_host_grib takes the packed bytes as a 1-d uint8 array")
+        n_batch = rows.size
+        if out is None:
+            out = result_cache.empty((n_batch, self.n_dst), np.float64)
+        if out.shape != (n_batch, self.n_dst) or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous float64 ({n_batch}, {self.n_dst}) array")
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        _lib.call("smm_apply_host_grib", self.handle, _cptr(buf), buf.size, rows_p, _cptr(out), _lib.SMM_F64,
+                  self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows))
+        return out
+
     def close(self):
         if getattr(self, "handle", None):
             _lib.call("smm_operator_destroy", self.handle)

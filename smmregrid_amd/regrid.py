@@ -19,6 +19,7 @@ import os
 import numpy as np
 
 from .device import CFDecode, CFEncode, DeviceArray, bfloat16, is_half_dtype, is_packed_dtype, to_device
+from .griblite import GribField
 from .gridtype import GridType, tolist
 from .lazy import LazyArray, is_dask, map_batch_blocks
 from .operator import OperatorGroup
@@ -304,6 +305,8 @@ class Regridder(object):
             # without horizontal or mask dimension is cleaned away, :133-143 -- time_bnds(time, bnds) is one): nothing
             # to regrid, and the empty result is dropped from a Dataset (regrid.py:308-312, :262-264)
             return DataArray(data=None)
+        if isinstance(source_data.data, GribField):
+            source_data = self._grib_or_decoded(source_data, datagridtype)
         cf = self._packed_rule(source_data) if self.packed else None
         enc = self._packed_out_rule(source_data) if (self.packed_out and cf is not None) else None
         packing = {k: source_data.attrs[k] for k in _CF_PACKING_ATTRS if k in source_data.attrs}
@@ -347,6 +350,24 @@ class Regridder(object):
     def _ships_half(self, dtype):
         """Whether a host field of `dtype` is handed to the host entries as it is (half=True; bfloat16 has no other way)."""
         return is_half_dtype(dtype) and (self.half or np.dtype(dtype) == bfloat16)
+
+    def _grib_or_decoded(self, source_data, datagridtype):
+        """A GRIB variable kept raw (`GribField`): with packed=True on 2-D weights and a float64 result it stays as it
+        is and apply_weights ships its bit streams (smm_apply_host_grib); everything else decodes it on the host --
+        what np.asarray would do anyway -- and goes on as before."""
+        why = None
+        if self.packed:
+            if datagridtype.mask_dim:
+                why = "masked levels"
+            elif self.skipna:
+                why = "skipna"
+            elif self._result_dtype(source_data) != np.dtype(np.float64):
+                why = f"out_dtype {self._result_dtype(source_data)}"
+            if why is None:
+                return source_data
+            self.loggy.info("packed variable %s is decoded on the host (%s)", source_data.name, why)
+        return DataArray(source_data.data.decode(), dims=source_data.dims, coords=source_data.coords,
+                         attrs=source_data.attrs, name=source_data.name)
 
     def _packed_out_rule(self, source_data):
         """The CFEncode of a packed variable's own attributes, or None (one WARNING) when they name no fill value."""
@@ -480,6 +501,8 @@ class Regridder(object):
 
         src = source_data.data
         area_min, skipna = self.remap_area_min, self.skipna
+        if isinstance(src, GribField) and (not self.packed or skipna or np.dtype(out_dtype) != np.dtype(np.float64)):
+            src = src.decode()      # a direct call: only packed=True, plain sums and float64 results take the raw road
         res_dtype = out_dtype if cf_out is None else cf_out.raw_dtype
         src_dtype = getattr(src, "dtype", None)
         ship_half = self._ships_half(src_dtype)
@@ -512,6 +535,14 @@ class Regridder(object):
                                  cf=cf, cf_out=cf_out, half=ship_half)
 
         def compute():
+            if isinstance(src, GribField):
+                # GRIB simple packing regridded raw (packed=True): the file's bytes and one rule per field go to the GPU
+                if src.n_points != op.n_src:
+                    raise ValueError(f"source grid has {src.n_points} cells, weights expect {op.n_src}")
+                if src.rows.size != n_batch:
+                    raise ValueError(f"{src.rows.size} GRIB fields for {n_batch} batch rows of shape {tuple(kept_shape)}")
+                y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min)
+                return y.reshape(kept_shape + tgt_shape)
             if sb_in:
                 x = src.reshape(-1, n_batch)                  # (S, B): the batch values of a cell contiguous
                 if x.shape[0] != op.n_src:
