@@ -129,6 +129,16 @@ typedef struct smm_grib_row_t {   /* one batch row = one GRIB field, 40 B */
   int32_t reserved;   /* 0 */
 } smm_grib_row_t;
 
+/* A GRIB field with a bitmap (smm_apply_grib_bm / smm_apply_host_grib_bm): one record per batch row, parallel to the
+ * row table.  The packed stream of such a row holds the present cells only: the value of grid cell c is packed value
+ * number rank(c), the count of set bitmap bits before c; a cell whose bit is 0 is a float32 NaN. */
+#define SMM_GRIB_NO_BITMAP UINT64_MAX
+typedef struct smm_grib_bitmap_t {   /* 16 B */
+  uint64_t bitmap_off;   /* byte offset in x of the row's bitmap: bit i (MSB first) of the stream says whether grid
+                            cell i has a value; SMM_GRIB_NO_BITMAP (UINT64_MAX): the row has none, every cell present */
+  uint64_t n_values;     /* values in the row's packed stream = set bits among the first n_src; n_src without a bitmap */
+} smm_grib_bitmap_t;
+
 /* smm_apply flags.  Bits outside this set are refused with SMM_ERR_INVALID by every entry that takes `flags`
  * (ABI <= 4 encoded kernel variants in bits 16..23: those are smm_debug_set_tuning knobs now). */
 enum {
@@ -449,6 +459,42 @@ int smm_apply_grib(smm_operator_t op, const void* x, int64_t x_bytes, const smm_
 int smm_apply_host_grib(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
                         void* y_host, int y_dtype, int64_t ldy, int64_t n_batch,
                         double remap_area_min, unsigned flags, int64_t chunk_rows);
+
+/*
+ * The two entries above for fields with a bitmap (ocean and land-surface variables, regional and masked grids):
+ * `bitmaps` is a HOST array of n_batch records parallel to `rows` (smm_grib_bitmap_t above), or NULL -- then the call
+ * is the entry above in every respect.  Rows with and without a bitmap may be mixed, and several rows may name one
+ * bitmap_off (GRIB-2's "same bitmap as the previous field").  A cell whose bitmap bit is 0 becomes a float32 NaN, a
+ * cell whose bit is 1 the decode of packed value number rank(c); after that nothing differs (the fill to float32(1e20)
+ * unless SMM_APPLY_NO_FILL, promotion to f64, the plain epilogue): the results are bit-identical to smm_apply with
+ * SMM_F32 X on the field a host decode gives, NaN where the bitmap is 0.
+ * How: ahead of the gather, on the same stream, two small kernels turn each bitmapped row's bitmap into a device
+ * table of one 8-byte entry per 32 cells -- the 32 bitmap bits and the count of set bits before them (a popcount
+ * per (row, segment of 32768 cells), then a scan inside every segment) -- 0.25 B per cell; the gather loads one entry
+ * per link, takes a popcount and a bit test and reads the stream at the rank instead of the cell.  Bits at or beyond
+ * n_src in the bitmap's last byte influence nothing.
+ *   smm_apply_grib_bm       as smm_apply_grib.  The tables live in a buffer the operator owns (grown on demand, only
+ *                           bitmapped rows take space), as the row table does: the same rule holds -- calls on one
+ *                           operator take turns and are ordered against each other only on ONE stream; concurrent
+ *                           calls on different streams need one operator handle each.
+ *   smm_apply_host_grib_bm  as smm_apply_host_grib.  With bitmaps a chunk stages its row table, then its bitmap records
+ *                           (16 B per row), then per row its ceil(n_values * nbits / 8) data bytes and, for a bitmapped
+ *                           row, its ceil(n_src / 8) bitmap bytes (a row that shares another row's bitmap stages its
+ *                           own copy), every piece at the next 4-byte-aligned offset, all in one H2D copy: per row
+ *                           40 + 16 + align4(data) + (bitmapped ? align4(ceil(n_src / 8)) : 0) bytes in
+ *                           SMM_HOST_STAT_H2D_BYTES.  The rank tables are device-only, one buffer per pipeline slot,
+ *                           and count against the chunk's byte budget with the staged bytes.
+ * SMM_ERR_INVALID in addition to the refusals above, before any launch: n_values > n_src; a bitmap whose
+ * ceil(n_src / 8) bytes leave [0, x_bytes); a row whose ceil(n_values * nbits / 8) data bytes leave it (for a bitmapped
+ * row this takes the place of the n_src-based check).  n_values is trusted for sizes only: every kernel load stays
+ * clamped to the buffer's last word, so a lying n_values yields wrong numbers and never a read outside the allocation.
+ */
+int smm_apply_grib_bm(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows /* host */,
+                      const smm_grib_bitmap_t* bitmaps /* host, or NULL */, void* y, int y_dtype, int64_t ldy,
+                      int64_t n_batch, double remap_area_min, unsigned flags, void* stream);
+int smm_apply_host_grib_bm(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                           const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t ldy,
+                           int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows);
 
 /*
  * Masked-level apply (regrid.py:387-418 in one launch).  The kept dims of the

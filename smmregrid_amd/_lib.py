@@ -90,6 +90,14 @@ class GribRowStruct(ctypes.Structure):
 
 _grp = ctypes.POINTER(GribRowStruct)
 
+
+class GribBitmapStruct(ctypes.Structure):
+    """smm_grib_bitmap_t: where the bitmap of one GRIB field lies in the packed bytes and how many values it leaves"""
+    _fields_ = [("bitmap_off", ctypes.c_uint64), ("n_values", ctypes.c_uint64)]
+
+
+_gbp = ctypes.POINTER(GribBitmapStruct)
+
 # name -> argtypes; every entry point returns int status except the two noted
 SIGNATURES = {
     "smm_device_count": [ctypes.POINTER(_int)],
@@ -151,6 +159,8 @@ SIGNATURES = {
     "smm_apply_host_pk": [_p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _i64, _cfp, _cep],
     "smm_apply_grib": [_p, _p, _i64, _grp, _p, _int, _i64, _i64, _dbl, _uint, _p],
     "smm_apply_host_grib": [_p, _p, _i64, _grp, _p, _int, _i64, _i64, _dbl, _uint, _i64],
+    "smm_apply_grib_bm": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _dbl, _uint, _p],
+    "smm_apply_host_grib_bm": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _dbl, _uint, _i64],
     "smm_group_apply": [_p, _p, _int, _i64, _i64, _i64, _p, _int, _i64, _i64, _i64,
                         _i64, _i64, _i64, _p, _p, _dbl, _uint, _p],
     "smm_group_prepare_sb": [_p],

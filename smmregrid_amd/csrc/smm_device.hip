@@ -253,6 +253,10 @@ struct smm_operator {
   // row table of smm_apply_grib on the device, grown on demand; calls on one operator take turns filling it
   std::mutex grib_mu;
   DeviceBuf<smm_grib_row_t> d_grib_rows;
+  // smm_apply_grib_bm, under the same mutex: the rows' bitmap records and the rank tables of the bitmapped ones (with
+  // their segment totals behind them); smm_apply_host_grib_bm, under pipe_mu: the rank buffer of each pipeline slot
+  DeviceBuf<GribRowBitmap> d_grib_bm;
+  DeviceBuf<char> d_grib_rank, d_pipe_rank[2];
   std::atomic<int> group_refs{0};  // groups borrowing this operator (their descriptors hold its device pointers)
   int native = 0;            // shape of the operator's own plan (choose_native_plan)
   int native_plan() const { return native; }
@@ -1369,13 +1373,16 @@ static int check_grib_call(const void* x, bool x_device, int64_t x_bytes, const 
   if (!smm::check_grib_rules(rows, n_batch, err)) return fail(SMM_ERR_INVALID, err);
   return SMM_OK;
 }
-// ... and what needs the operator's sizes.
-static int check_grib_operator(smm_operator_t op, int64_t x_bytes, const smm_grib_row_t* rows, int64_t ldy, int64_t n_batch,
-                               double area_min, unsigned flags) {
+// ... and what needs the operator's sizes.  With bitmaps (the _bm entries) check_grib_bitmaps stands where
+// check_grib_ranges stands.
+static int check_grib_operator(smm_operator_t op, int64_t x_bytes, const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps,
+                               int64_t ldy, int64_t n_batch, double area_min, unsigned flags) {
   if (!op) return fail(SMM_ERR_INVALID, "null operator");
   if (n_batch > 0 && ldy < op->csr.n_dst) return fail(SMM_ERR_INVALID, "ldy smaller than the grid size");
   std::string err;
-  if (!smm::check_grib_ranges(rows, n_batch, op->csr.n_src, x_bytes, err)) return fail(SMM_ERR_INVALID, err);
+  if (!(bitmaps ? smm::check_grib_bitmaps(rows, bitmaps, n_batch, op->csr.n_src, x_bytes, err)
+                : smm::check_grib_ranges(rows, n_batch, op->csr.n_src, x_bytes, err)))
+    return fail(SMM_ERR_INVALID, err);
   return check_epilogue(op, flags & SMM_APPLY_MASKED, area_min, "the operator");
 }
 static bool grib_needs_division(const smm_grib_row_t* rows, int64_t n_batch) {
@@ -1386,8 +1393,11 @@ static bool grib_needs_division(const smm_grib_row_t* rows, int64_t n_batch) {
 
 // n_batch rows whose table is on the device already (d_rows) over the x_bytes bytes at x: one launch, or parts of the
 // batch when the grid would pass the limit (smm::split_batch, as run_apply)
+// d_bm with n_tables > 0 (smm_apply_grib_bm): the rows' device bitmap records; d_rank holds n_tables rank tables of
+// ceil(n_src / 32) entries and behind them n_tables x segments totals.  The tables are built first, on the same stream.
 static int launch_grib_rows(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* d_rows, bool div, void* y,
-                            int64_t ldy, int64_t n_batch, double area_min, unsigned flags, hipStream_t s) {
+                            int64_t ldy, int64_t n_batch, double area_min, unsigned flags, hipStream_t s,
+                            const GribRowBitmap* d_bm = nullptr, char* d_rank = nullptr, size_t n_tables = 0) {
   GribArgs a{};
   a.descs = op->d_desc.get();
   // no data bytes at all (every row has 0 bits): the loads, clamped to word 0, read the table instead
@@ -1403,12 +1413,31 @@ static int launch_grib_rows(smm_operator_t op, const void* x, int64_t x_bytes, c
     const int bt = smm_launch::sell_batch_rows(n_o);
     return a.n_dblocks * ((n_o + bt - 1) / bt);
   };
+  const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)op->csr.n_src);
+  const bool with_tables = d_bm && n_tables > 0 && n_blocks > 0;
+  if (with_tables) {
+    GribBuildArgs b{};
+    b.x = a.x;
+    b.bm = d_bm;
+    b.table = (smm_grib::GribRankEntry*)d_rank;
+    b.totals = (uint32_t*)(d_rank + n_tables * (size_t)n_blocks * sizeof(smm_grib::GribRankEntry));
+    b.last_word = a.last_word;
+    b.n_j = n_batch;
+    b.n_src = (uint32_t)op->csr.n_src;
+    b.n_blocks = (uint32_t)n_blocks;
+    b.n_segs = (uint32_t)smm_grib::bitmap_segments((uint64_t)op->csr.n_src);
+    if (int rc = smm_launch::launch_grib_build(b, s)) return rc;
+  }
   auto launch_part = [&](int64_t o0, int64_t n_o, int64_t, int64_t) -> int {
-    GribArgs p = a;
+    GribBitmapArgs p{};
+    static_cast<GribArgs&>(p) = a;
     p.rows = d_rows + o0;
     p.y = (double*)y + o0 * ldy;
     p.n_j = n_o;
-    return smm_launch::launch_grib(p, div, fill, s);
+    if (!with_tables) return smm_launch::launch_grib(p, div, fill, s);
+    p.bm = d_bm + o0;
+    p.table = (const smm_grib::GribRankEntry*)d_rank;
+    return smm_launch::launch_grib_bitmap(p, div, fill, s);
   };
   const int rc = smm::split_batch(0, n_batch, 0, 1, grid_limit(), blocks_for, launch_part);
   if (rc == -1)
@@ -1417,8 +1446,10 @@ static int launch_grib_rows(smm_operator_t op, const void* x, int64_t x_bytes, c
   return rc;
 }
 
-static int smm_apply_grib_impl(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows, void* y,
-                               int64_t ldy, int64_t n_batch, double area_min, unsigned flags, void* stream) {
+// bitmaps: null, or the records of smm_apply_grib_bm
+static int smm_apply_grib_impl(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
+                               const smm_grib_bitmap_t* bitmaps, void* y, int64_t ldy, int64_t n_batch, double area_min,
+                               unsigned flags, void* stream) {
   if (n_batch == 0 || op->csr.n_dst == 0) return SMM_OK;
   DeviceGuard guard(op->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
@@ -1438,18 +1469,44 @@ static int smm_apply_grib_impl(smm_operator_t op, const void* x, int64_t x_bytes
     rows = pageable.data();
   }
   SMM_HIP(hipMemcpyAsync(op->d_grib_rows.get(), rows, (size_t)n_batch * sizeof(smm_grib_row_t), hipMemcpyHostToDevice, s));
+  // the bitmap records go up beside it, each bitmapped row with the place of its rank table; a pageable vector in any
+  // case.  Only bitmapped rows take table space; a call without one runs the plain gather.
+  std::vector<GribRowBitmap> bm;
+  size_t n_tables = 0;
+  if (bitmaps) {
+    const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)op->csr.n_src);
+    bm.resize((size_t)n_batch);
+    for (int64_t b = 0; b < n_batch; ++b) {
+      const bool has = bitmaps[b].bitmap_off != SMM_GRIB_NO_BITMAP;
+      bm[(size_t)b] = GribRowBitmap{bitmaps[b].bitmap_off, has ? n_tables * n_blocks : 0};
+      n_tables += has;
+    }
+  }
+  if (n_tables > 0) {
+    if (op->d_grib_bm.bytes() < bm.size() * sizeof(GribRowBitmap)) {
+      const size_t have = op->d_grib_bm.bytes() / sizeof(GribRowBitmap);
+      SMM_HIP(op->d_grib_bm.alloc(std::max<size_t>(bm.size(), 2 * have)));
+    }
+    const size_t need = n_tables * (size_t)smm_grib::bitmap_blocks((uint64_t)op->csr.n_src) * sizeof(smm_grib::GribRankEntry) +
+                        n_tables * (size_t)smm_grib::bitmap_segments((uint64_t)op->csr.n_src) * sizeof(uint32_t);
+    if (op->d_grib_rank.bytes() < need) SMM_HIP(op->d_grib_rank.alloc(std::max(need, 2 * op->d_grib_rank.bytes())));
+    SMM_HIP(hipMemcpyAsync(op->d_grib_bm.get(), bm.data(), bm.size() * sizeof(GribRowBitmap), hipMemcpyHostToDevice, s));
+  }
   return launch_grib_rows(op, x, x_bytes, op->d_grib_rows.get(), grib_needs_division(rows, n_batch), y, ldy, n_batch, area_min,
-                          flags, s);
+                          flags, s, n_tables ? op->d_grib_bm.get() : nullptr, op->d_grib_rank.get(), n_tables);
 }
 
-static int smm_apply_host_grib_impl(smm_operator_t op, const void* x_host, const smm_grib_row_t* rows, void* y_host,
-                                    int64_t ldy, int64_t n_batch, double area_min, unsigned flags, int64_t chunk_rows) {
+static int smm_apply_host_grib_impl(smm_operator_t op, const void* x_host, const smm_grib_row_t* rows,
+                                    const smm_grib_bitmap_t* bitmaps, void* y_host, int64_t ldy, int64_t n_batch,
+                                    double area_min, unsigned flags, int64_t chunk_rows) {
   const int64_t S = op->csr.n_src, D = op->csr.n_dst;
   if (n_batch == 0 || D == 0) return SMM_OK;
   DeviceGuard guard(op->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
   // chunks of consecutive rows, sized by their bytes (rows differ in width): smm_internal.h
-  const smm::GribChunkPlan plan = smm::plan_grib_chunks(rows, n_batch, S, D, chunk_rows, free_device_bytes());
+  const smm::GribChunkPlan plan =
+      bitmaps ? smm::plan_grib_chunks_bm(rows, bitmaps, n_batch, S, D, chunk_rows, free_device_bytes())
+              : smm::plan_grib_chunks(rows, n_batch, S, D, chunk_rows, free_device_bytes());
   const bool div = grib_needs_division(rows, n_batch);
   const bool y_direct = is_pinned(y_host);
   const size_t yrow = (size_t)ldy * 8;
@@ -1458,6 +1515,8 @@ static int smm_apply_host_grib_impl(smm_operator_t op, const void* x_host, const
   HostPipe& pipe = op->pipe;
   const size_t y_chunk = (size_t)plan.max_rows * D * 8;
   SMM_HIP(pipe.ensure(plan.max_x, y_chunk, plan.max_x, y_direct ? 0 : y_chunk));
+  if (plan.max_rank > std::min(op->d_pipe_rank[0].bytes(), op->d_pipe_rank[1].bytes()))   // device-only, one per slot
+    for (int i = 0; i < 2; ++i) SMM_HIP(op->d_pipe_rank[i].alloc(plan.max_rank));
 
   CallStats st;
   auto deliver = [&](int64_t c, int b) -> int {   // results of chunk c: pinned -> user rows
@@ -1471,30 +1530,49 @@ static int smm_apply_host_grib_impl(smm_operator_t op, const void* x_host, const
   };
   // Staging of a chunk: its table first, then each row's data bytes at the next 4-byte-aligned offset; the table's
   // byte_off are those offsets, from the start of the buffer.  A pinned x_host is staged all the same: the rows of a
-  // chunk need not be adjacent in it.
+  // chunk need not be adjacent in it.  With bitmaps the chunk's bitmap records follow the table (their bitmap_off
+  // are staged offsets as well, their second word the place of the row's rank table in the slot's rank buffer), and a
+  // bitmapped row's data bytes -- ceil(n_values * nbits / 8) of them -- are followed by its own copy of its bitmap.
   auto launch = [&](int64_t c, int b) -> int {
     const smm::GribChunk& ch = plan.chunks[(size_t)c];
     char* hx = (char*)pipe.hx[b].get();
+    size_t n_tables = 0;
     {
       StageTimer t(st.v[SMM_HOST_STAT_STAGE_IN_MS]);
       smm_grib_row_t* table = (smm_grib_row_t*)hx;
-      uint64_t cursor = (uint64_t)ch.nr * sizeof(smm_grib_row_t);
+      GribRowBitmap* bm = (GribRowBitmap*)(hx + (size_t)ch.nr * sizeof(smm_grib_row_t));
+      uint64_t cursor = (uint64_t)ch.nr * (sizeof(smm_grib_row_t) + (bitmaps ? sizeof(GribRowBitmap) : 0));
+      const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)S), bm_bytes = smm_grib::bitmap_bytes((uint64_t)S);
+      auto data_bytes = [&](int64_t r) {
+        const bool has = bitmaps && bitmaps[ch.r0 + r].bitmap_off != SMM_GRIB_NO_BITMAP;
+        return smm_grib::row_bytes(has ? bitmaps[ch.r0 + r].n_values : (uint64_t)S, rows[ch.r0 + r].nbits);
+      };
       for (int64_t r = 0; r < ch.nr; ++r) {
         table[r] = rows[ch.r0 + r];
         table[r].byte_off = cursor;
-        cursor += smm_grib::align4(smm_grib::row_bytes((uint64_t)S, table[r].nbits));
+        cursor += smm_grib::align4(data_bytes(r));
+        if (!bitmaps) continue;
+        const bool has = bitmaps[ch.r0 + r].bitmap_off != SMM_GRIB_NO_BITMAP;
+        bm[r] = GribRowBitmap{has ? cursor : SMM_GRIB_NO_BITMAP, has ? n_tables * n_blocks : 0};
+        if (has) cursor += smm_grib::align4(bm_bytes), ++n_tables;
       }
-      for (int64_t r = 0; r < ch.nr; ++r)   // each row's copy is spread over the staging pool (host_copy)
-        if (int rc = host_copy(hx + table[r].byte_off, (const char*)x_host + rows[ch.r0 + r].byte_off,
-                               (size_t)smm_grib::row_bytes((uint64_t)S, table[r].nbits)))
+      for (int64_t r = 0; r < ch.nr; ++r) {   // each row's copy is spread over the staging pool (host_copy)
+        if (int rc = host_copy(hx + table[r].byte_off, (const char*)x_host + rows[ch.r0 + r].byte_off, (size_t)data_bytes(r)))
           return rc;
+        if (bitmaps && bm[r].bitmap_off != SMM_GRIB_NO_BITMAP)
+          if (int rc = host_copy(hx + bm[r].bitmap_off, (const char*)x_host + bitmaps[ch.r0 + r].bitmap_off, (size_t)bm_bytes))
+            return rc;
+      }
     }
     SMM_HIP(pipe.mark(b, 0));
     SMM_HIP(hipMemcpyAsync(pipe.dx[b].get(), hx, ch.x_bytes, hipMemcpyHostToDevice, pipe.stream[b]));
     st.v[SMM_HOST_STAT_H2D_BYTES] += (double)ch.x_bytes;
     SMM_HIP(pipe.mark(b, 1));
     if (int rc = launch_grib_rows(op, pipe.dx[b].get(), (int64_t)ch.x_bytes, (const smm_grib_row_t*)pipe.dx[b].get(), div,
-                                  pipe.dy[b].get(), D, ch.nr, area_min, flags, pipe.stream[b]))
+                                  pipe.dy[b].get(), D, ch.nr, area_min, flags, pipe.stream[b],
+                                  n_tables ? (const GribRowBitmap*)(pipe.dx[b].get() + (size_t)ch.nr * sizeof(smm_grib_row_t))
+                                           : nullptr,
+                                  op->d_pipe_rank[b].get(), n_tables))
       return rc;
     st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)ch.nr * D * 8);
     SMM_HIP(pipe.mark(b, 2));
@@ -2152,20 +2230,34 @@ int smm_apply_host_pk(smm_operator_t op, const void* x_host, int x_dtype, int64_
 
 int smm_apply_grib(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows, void* y, int y_dtype,
                    int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream) {
+  return smm_apply_grib_bm(op, x, x_bytes, rows, nullptr, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream);
+}
+
+// bitmaps == NULL: the entry above
+int smm_apply_grib_bm(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
+                      const smm_grib_bitmap_t* bitmaps, void* y, int y_dtype, int64_t ldy, int64_t n_batch,
+                      double remap_area_min, unsigned flags, void* stream) {
   return guarded([&] {
     if (int rc = check_grib_call(x, true, x_bytes, rows, y, y_dtype, n_batch, remap_area_min, flags)) return rc;
-    if (int rc = check_grib_operator(op, x_bytes, rows, ldy, n_batch, remap_area_min, flags)) return rc;
-    return smm_apply_grib_impl(op, x, x_bytes, rows, y, ldy, n_batch, remap_area_min, flags, stream);
+    if (int rc = check_grib_operator(op, x_bytes, rows, bitmaps, ldy, n_batch, remap_area_min, flags)) return rc;
+    return smm_apply_grib_impl(op, x, x_bytes, rows, bitmaps, y, ldy, n_batch, remap_area_min, flags, stream);
   });
 }
 
 int smm_apply_host_grib(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows, void* y_host,
                         int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags,
                         int64_t chunk_rows) {
+  return smm_apply_host_grib_bm(op, x_host, x_bytes, rows, nullptr, y_host, y_dtype, ldy, n_batch, remap_area_min, flags,
+                                chunk_rows);
+}
+
+int smm_apply_host_grib_bm(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                           const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t ldy, int64_t n_batch,
+                           double remap_area_min, unsigned flags, int64_t chunk_rows) {
   return guarded([&] {
     if (int rc = check_grib_call(x_host, false, x_bytes, rows, y_host, y_dtype, n_batch, remap_area_min, flags)) return rc;
-    if (int rc = check_grib_operator(op, x_bytes, rows, ldy, n_batch, remap_area_min, flags)) return rc;
-    return smm_apply_host_grib_impl(op, x_host, rows, y_host, ldy, n_batch, remap_area_min, flags, chunk_rows);
+    if (int rc = check_grib_operator(op, x_bytes, rows, bitmaps, ldy, n_batch, remap_area_min, flags)) return rc;
+    return smm_apply_host_grib_impl(op, x_host, rows, bitmaps, y_host, ldy, n_batch, remap_area_min, flags, chunk_rows);
   });
 }
 

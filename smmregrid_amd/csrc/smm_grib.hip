@@ -1,5 +1,6 @@
 // smm_apply_grib's kernel and launcher (gfx950): kernel A with the gather replaced -- per link two unconditional
-// 32-bit loads from the packed bit stream, a byte swap, a 64-bit shift and the row's decode rule.
+// 32-bit loads from the packed bit stream, a byte swap, a 64-bit shift and the row's decode rule.  For
+// smm_apply_grib_bm: the two kernels that build the rank tables of bitmapped rows, and the gather that reads them.
 #include "smm_grib.hpp"
 
 #include <algorithm>
@@ -16,8 +17,12 @@ namespace {
 // BT batch rows per thread as in smm_apply_sell_kernel.  What a batch row needs -- its first word, the bit offset of
 // its first value inside it, its width and rule -- is read once per block through a block-uniform index of the
 // const __restrict__ row table: scalar loads, scalar registers.  DIV: grib_decode.
-template <int BT, bool DIV>
-__global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(GribArgs a, bool fill) {
+// BM (smm_apply_grib_bm): a row with a bitmap loads, per link, the 8-byte rank-table entry of the cell's 32-cell block
+// and reads the stream at the cell's rank; its table pointer -- null for a row without a bitmap, which takes
+// rank = c, present = true -- is scalar like the rest of the rule, so the branch on it is block-uniform.
+template <int BT, bool DIV, bool BM>
+__global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(std::conditional_t<BM, GribBitmapArgs, GribArgs> a,
+                                                                   bool fill) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int64_t bid = blockIdx.x;
@@ -36,11 +41,17 @@ __global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(GribArgs a, bo
   uint32_t bit0[BT], lastw[BT];
   int nbits[BT];
   double ref[BT], bscale[BT], ddiv[BT];
+  const smm_grib::GribRankEntry* __restrict__ tab[BM ? BT : 1];
 #pragma unroll
   for (int t = 0; t < BT; ++t) {
     int64_t j = j0 + t;
     if (j > a.n_j - 1) j = a.n_j - 1;
     const smm_grib_row_t r = rows[j];
+    if constexpr (BM) {
+      const GribRowBitmap* __restrict__ bm = a.bm;
+      const GribRowBitmap m = bm[j];
+      tab[t] = m.bitmap_off == SMM_GRIB_NO_BITMAP ? nullptr : a.table + m.table_off;
+    }
     // a 0-bit row may start at the very end of the buffer: its words are clamped like every other load
     const uint64_t w = std::min<uint64_t>(r.byte_off >> 2, a.last_word);
     xw[t] = a.x + w;
@@ -68,9 +79,19 @@ __global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(GribArgs a, bo
     double xv[BT];
 #pragma unroll
     for (int t = 0; t < BT; ++t) {
-      const uint64_t p = (uint64_t)bit0[t] + (uint64_t)c * (uint32_t)nbits[t];
+      uint32_t i = c;   // the value's index in the row's stream
+      bool present = true;
+      if constexpr (BM) {
+        if (tab[t]) {
+          const smm_grib::GribRankEntry e = tab[t][c >> 5];
+          i = smm_grib::bitmap_index(e, c);
+          present = smm_grib::bitmap_present(e, c);
+        }
+      }
+      const uint64_t p = (uint64_t)bit0[t] + (uint64_t)i * (uint32_t)nbits[t];
       const uint32_t q = smm_grib::grib_extract(xw[t], p, nbits[t], lastw[t]);
-      const float v = smm_grib::grib_decode<DIV>(q, ref[t], bscale[t], ddiv[t]);
+      float v = smm_grib::grib_decode<DIV>(q, ref[t], bscale[t], ddiv[t]);
+      if constexpr (BM) v = present ? v : __builtin_nanf("");   // a missing cell: its loads went out, a select drops them
       xv[t] = (double)((fill && !__builtin_isfinite(v)) ? (float)1e20 : v);
     }
 #pragma unroll
@@ -92,20 +113,116 @@ __global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(GribArgs a, bo
   }
 }
 
+// ---- the rank tables of smm_apply_grib_bm.  One workgroup per (row, segment of kGribSegBlocks 32-cell blocks); a
+// thread holds kBuildPerThread consecutive blocks.  Rows without a bitmap leave at once (block-uniform).
+constexpr int kBuildThreads = 256, kBuildWaves = kBuildThreads / 64;
+constexpr int kBuildPerThread = smm_grib::kGribSegBlocks / kBuildThreads;
+static_assert(kBuildPerThread * kBuildThreads == smm_grib::kGribSegBlocks, "a segment is whole blocks per thread");
+
+struct BuildRow {
+  const uint32_t* __restrict__ words;
+  uint32_t bit0, lastw;
+};
+__device__ __forceinline__ BuildRow build_row(const GribBuildArgs& a, uint64_t bitmap_off) {
+  const uint64_t w = std::min<uint64_t>(bitmap_off >> 2, a.last_word);   // as the gather clamps a row's first word
+  return BuildRow{a.x + w, 8u * (uint32_t)(bitmap_off & 3), (uint32_t)std::min<uint64_t>(a.last_word - w, 0xfffffffeull)};
+}
+// sum over the wave, in every lane
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// 1: totals[table number * n_segs + seg] = set bits of the segment
+__global__ __launch_bounds__(kBuildThreads) void smm_grib_bitmap_totals_kernel(GribBuildArgs a) {
+  __shared__ uint32_t wsum[kBuildWaves];
+  const int64_t j = blockIdx.x / a.n_segs;
+  const uint32_t seg = blockIdx.x % a.n_segs;
+  const GribRowBitmap* __restrict__ bm = a.bm;
+  const uint64_t off = bm[j].bitmap_off;
+  if (off == SMM_GRIB_NO_BITMAP) return;
+  const BuildRow r = build_row(a, off);
+  const uint32_t k0 = seg * (uint32_t)smm_grib::kGribSegBlocks + threadIdx.x * kBuildPerThread;
+  uint32_t n = 0;
+#pragma unroll
+  for (int i = 0; i < kBuildPerThread; ++i)
+    if (k0 + i < a.n_blocks) n += smm_grib::popcount32(smm_grib::bitmap_block(r.words, r.bit0, k0 + i, a.n_src, r.lastw));
+  n = wave_sum(n);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+#pragma unroll
+    for (int w = 0; w < kBuildWaves; ++w) t += wsum[w];
+    a.totals[bm[j].table_off / a.n_blocks * a.n_segs + seg] = t;   // every table has n_blocks entries: its number
+  }
+}
+
+// 2: the entries of one segment.  The totals of the segments before it are summed by the whole workgroup; inside the
+// segment a thread's blocks are scanned in registers, the threads of a wave by an inclusive shuffle scan, the waves
+// through LDS.
+__global__ __launch_bounds__(kBuildThreads) void smm_grib_bitmap_scan_kernel(GribBuildArgs a) {
+  __shared__ uint32_t wsum[kBuildWaves], wbefore[kBuildWaves];
+  const int64_t j = blockIdx.x / a.n_segs;
+  const uint32_t seg = blockIdx.x % a.n_segs;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const GribRowBitmap* __restrict__ bm = a.bm;
+  const GribRowBitmap m = bm[j];
+  if (m.bitmap_off == SMM_GRIB_NO_BITMAP) return;
+  const BuildRow r = build_row(a, m.bitmap_off);
+
+  uint32_t before = 0;
+  const uint32_t* __restrict__ tot = a.totals + m.table_off / a.n_blocks * a.n_segs;
+  for (uint32_t s = threadIdx.x; s < seg; s += kBuildThreads) before += tot[s];
+  before = wave_sum(before);
+  if (lane == 0) wbefore[wave] = before;
+
+  const uint32_t k0 = seg * (uint32_t)smm_grib::kGribSegBlocks + threadIdx.x * kBuildPerThread;
+  uint32_t bits[kBuildPerThread], mine = 0;
+#pragma unroll
+  for (int i = 0; i < kBuildPerThread; ++i) {
+    bits[i] = k0 + i < a.n_blocks ? smm_grib::bitmap_block(r.words, r.bit0, k0 + i, a.n_src, r.lastw) : 0u;
+    mine += smm_grib::popcount32(bits[i]);
+  }
+  uint32_t incl = mine;   // inclusive scan over the lanes of the wave
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  uint32_t rank = incl - mine;
+#pragma unroll
+  for (int w = 0; w < kBuildWaves; ++w) {
+    rank += wbefore[w];
+    if (w < wave) rank += wsum[w];
+  }
+  smm_grib::GribRankEntry* __restrict__ out = a.table + m.table_off;
+#pragma unroll
+  for (int i = 0; i < kBuildPerThread; ++i) {
+    if (k0 + i < a.n_blocks) out[k0 + i] = smm_grib::GribRankEntry{bits[i], rank};
+    rank += smm_grib::popcount32(bits[i]);
+  }
+}
+
 }  // namespace
 
 namespace smm_launch {
 
-int launch_grib(const GribArgs& a, bool div, bool fill, hipStream_t s) {
-  GribArgs args = a;
+namespace {
+template <bool BM, class Args>
+int launch_grib_any(const Args& a, bool div, bool fill, hipStream_t s) {
+  Args args = a;
   auto go = [&](auto bt_tag, auto div_tag) -> int {
     constexpr int BT = decltype(bt_tag)::value;
     args.n_jtiles = (a.n_j + BT - 1) / BT;
     const int64_t total = args.n_dblocks * args.n_jtiles;
     if (total <= 0) return SMM_OK;
     if (total > 0x7fffffffLL) return smm::fail_msg(SMM_ERR_INVALID, "launch grid exceeds 2^31-1 blocks");
-    hipLaunchKernelGGL((smm_apply_grib_kernel<BT, decltype(div_tag)::value>), dim3((unsigned)total), dim3(kThreads), 0, s,
-                       args, fill);
+    hipLaunchKernelGGL((smm_apply_grib_kernel<BT, decltype(div_tag)::value, BM>), dim3((unsigned)total), dim3(kThreads), 0,
+                       s, args, fill);
     SMM_LAUNCH_HIP(hipGetLastError());
     return SMM_OK;
   };
@@ -118,6 +235,23 @@ int launch_grib(const GribArgs& a, bool div, bool fill, hipStream_t s) {
     }
   };
   return div ? with_bt(std::true_type()) : with_bt(std::false_type());
+}
+}  // namespace
+
+int launch_grib(const GribArgs& a, bool div, bool fill, hipStream_t s) { return launch_grib_any<false>(a, div, fill, s); }
+int launch_grib_bitmap(const GribBitmapArgs& a, bool div, bool fill, hipStream_t s) {
+  return launch_grib_any<true>(a, div, fill, s);
+}
+
+int launch_grib_build(const GribBuildArgs& a, hipStream_t s) {
+  const int64_t total = a.n_j * (int64_t)a.n_segs;
+  if (total <= 0) return SMM_OK;
+  if (total > 0x7fffffffLL) return smm::fail_msg(SMM_ERR_INVALID, "bitmap table build exceeds 2^31-1 blocks");
+  hipLaunchKernelGGL(smm_grib_bitmap_totals_kernel, dim3((unsigned)total), dim3(kBuildThreads), 0, s, a);
+  SMM_LAUNCH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(smm_grib_bitmap_scan_kernel, dim3((unsigned)total), dim3(kBuildThreads), 0, s, a);
+  SMM_LAUNCH_HIP(hipGetLastError());
+  return SMM_OK;
 }
 
 }  // namespace smm_launch

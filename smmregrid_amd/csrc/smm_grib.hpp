@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/smmregrid_amd.h"
+#include "smm_grib_codec.hpp"
 #include "smm_kernels.hpp"
 
 struct GribArgs {
@@ -21,7 +22,34 @@ struct GribArgs {
   int masked;
 };
 
+// smm_apply_grib_bm.  The device copy of a row's smm_grib_bitmap_t: n_values, which only the host's size checks
+// read, gives its place to the row's rank table.
+struct GribRowBitmap {
+  uint64_t bitmap_off;   // byte offset of the bitmap in x; SMM_GRIB_NO_BITMAP: the row has none
+  uint64_t table_off;    // first entry of the row's table in GribBitmapArgs::table (bitmapped rows only)
+};
+static_assert(sizeof(GribRowBitmap) == sizeof(smm_grib_bitmap_t), "one record per row, 16 B");
+struct GribBitmapArgs : GribArgs {
+  const GribRowBitmap* bm;                 // device [n_j], parallel to rows
+  const smm_grib::GribRankEntry* table;    // device: the rank tables of the call's bitmapped rows
+};
+// the table build: n_j rows of n_src cells over the words of x.  Every table has n_blocks entries, so table_off / n_blocks
+// numbers the tables: totals[(that number) * n_segs + s] = set bits of segment s
+struct GribBuildArgs {
+  const uint32_t* x;
+  const GribRowBitmap* bm;
+  smm_grib::GribRankEntry* table;
+  uint32_t* totals;
+  uint64_t last_word;
+  int64_t n_j;
+  uint32_t n_src, n_blocks, n_segs;
+};
+
 namespace smm_launch {
 // div: some row of the call has ddiv != 1.0 (the instantiation with the f64 division); fill: the 1e20 fill is on
 int launch_grib(const GribArgs& a, bool div, bool fill, hipStream_t s);
+// the gather that consults the rank tables (rows without a bitmap take rank = c on a block-uniform branch) ...
+int launch_grib_bitmap(const GribBitmapArgs& a, bool div, bool fill, hipStream_t s);
+// ... and the two kernels that fill them, in stream order ahead of it: segment totals, then the scan
+int launch_grib_build(const GribBuildArgs& a, hipStream_t s);
 }

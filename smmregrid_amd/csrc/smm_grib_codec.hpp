@@ -1,6 +1,7 @@
 // GRIB simple packing: the bit extraction and the decode of smm_apply_grib (rule: smm_grib_row_t in
 // include/smmregrid_amd.h), as two small functions that the kernel (smm_grib.hip) and plain host code share -- this
 // header needs no HIP: tests/cpp/grib_harness.cpp compiles it with g++ and checks the very code the kernel runs.
+// Below them the bitmap arithmetic of smm_apply_grib_bm (tests/cpp/grib_bitmap_harness.cpp).
 #pragma once
 
 #include <cstdint>
@@ -48,6 +49,38 @@ SMM_GRIB_HD float grib_decode(uint32_t q, double ref, double bscale, double ddiv
   t = ref + t;
   if (DIV) t = t / ddiv;
   return (float)t;
+}
+
+// ---- bitmaps (smm_apply_grib_bm): the packed stream of a bitmapped row holds the present cells only, and cell c's
+// value is packed value number rank(c) = set bitmap bits before c.  The rank table has one entry per 32 cells.
+struct alignas(8) GribRankEntry {
+  uint32_t bits;          // bitmap bits [32k, 32k + 32) in stream order: cell 32k is the top bit
+  uint32_t rank_before;   // set bits among cells [0, 32k); n_src < 2^31
+};
+// 32-cell blocks of one segment of the table build: a (row, segment) workgroup counts, then scans, this many blocks
+// (smm_grib.hip: 256 threads x 4 blocks) -- 32768 cells
+constexpr int kGribSegBlocks = 1024;
+inline uint64_t bitmap_bytes(uint64_t n_src) { return (n_src + 7) / 8; }
+inline uint64_t bitmap_blocks(uint64_t n_src) { return (n_src + 31) / 32; }
+inline uint64_t bitmap_segments(uint64_t n_src) { return (bitmap_blocks(n_src) + kGribSegBlocks - 1) / kGribSegBlocks; }
+
+// Block k (32 * k < n_src) of the bitmap whose first bit is bit bit0 of `words`: grib_extract's clamped two-word
+// window with nbits = 32 -- the bitmap may start at any byte.  Bits of cells >= n_src (the last byte's pad, whatever
+// follows the bitmap, the clamped second word) are cleared: they reach neither a rank nor a total.
+SMM_GRIB_HD uint32_t bitmap_block(const uint32_t* __restrict__ words, uint32_t bit0, uint32_t k, uint32_t n_src,
+                                  uint32_t last_word) {
+  const uint32_t b = grib_extract(words, (uint64_t)bit0 + 32ull * k, 32, last_word);
+  const uint32_t left = n_src - 32u * k;   // cells from 32k on: >= 1
+  return left >= 32u ? b : b & ~(0xffffffffu >> left);
+}
+SMM_GRIB_HD uint32_t popcount32(uint32_t v) { return (uint32_t)__builtin_popcount(v); }
+// is cell c present, by its block's entry
+SMM_GRIB_HD bool bitmap_present(GribRankEntry e, uint32_t c) { return ((e.bits >> (31u - (c & 31u))) & 1u) != 0u; }
+// Index of cell c's value in the packed stream: the block's rank plus the set bits above c's bit.  c % 32 == 0 has
+// none above it: the shift is taken in two steps (by 1, then by 31 - c % 32 <= 31), never by 32.  A missing cell gets
+// the index of the next present one: its loads are issued all the same, the caller replaces the value by NaN.
+SMM_GRIB_HD uint32_t bitmap_index(GribRankEntry e, uint32_t c) {
+  return e.rank_before + popcount32((e.bits >> 1) >> (31u - (c & 31u)));
 }
 
 }  // namespace smm_grib

@@ -7,6 +7,7 @@
 #include <vector>
 
 struct smm_grib_row_t;   // include/smmregrid_amd.h
+struct smm_grib_bitmap_t;
 
 namespace smm {
 
@@ -201,15 +202,32 @@ bool check_grib_ranges(const smm_grib_row_t* rows, int64_t n_batch, int64_t n_sr
 // most).  A row that alone exceeds the target still gets a chunk of its own.  requested_rows > 0: that many rows per chunk.
 struct GribChunk {
   int64_t r0, nr;
-  size_t x_bytes;   // staged bytes of the chunk: table + padded rows
+  size_t x_bytes;          // staged bytes of the chunk: table + padded rows
+  size_t rank_bytes = 0;   // plan_grib_chunks_bm: the chunk's device-only rank tables and segment totals
 };
 struct GribChunkPlan {
   std::vector<GribChunk> chunks;   // cover [0, n_batch) exactly once, in order
   size_t target = 0;               // the byte bound in force (0 with requested_rows)
   size_t max_x = 0;                // largest staged X of one chunk
   int64_t max_rows = 0;            // most rows of one chunk
+  size_t max_rank = 0;             // largest rank_bytes of one chunk
 };
 GribChunkPlan plan_grib_chunks(const smm_grib_row_t* rows, int64_t n_batch, int64_t n_src, int64_t D,
                                int64_t requested_rows, size_t free_bytes);
+
+// ---- the same with bitmaps (smm_apply_grib_bm / smm_apply_host_grib_bm; bitmaps is never null here).
+// check_grib_bitmaps stands where check_grib_ranges stands: n_values <= n_src in every row; a bitmapped row's
+// ceil(n_src / 8) bitmap bytes and its ceil(n_values * nbits / 8) data bytes inside [0, x_bytes); a row without a bitmap
+// as check_grib_ranges has it.
+bool check_grib_bitmaps(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_batch, int64_t n_src,
+                        int64_t x_bytes, std::string& err);
+// Bytes a row stages through smm_apply_host_grib_bm: its table record (40), its bitmap record (16), its data bytes and,
+// with a bitmap, its bitmap bytes, each rounded up to 4 -- and what it takes of the device-only rank buffer: one 8-byte
+// entry per 32 cells when it has a bitmap, and its 4-byte segment totals.
+size_t grib_bm_row_staged(const smm_grib_row_t& row, const smm_grib_bitmap_t& bm, int64_t n_src);
+size_t grib_bm_row_rank(const smm_grib_bitmap_t& bm, int64_t n_src);
+// plan_grib_chunks with those costs: staged bytes, rank bytes and Y of a chunk against the same target.
+GribChunkPlan plan_grib_chunks_bm(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_batch,
+                                  int64_t n_src, int64_t D, int64_t requested_rows, size_t free_bytes);
 
 }  // namespace smm

@@ -41,20 +41,33 @@ GRIB_ROW_DTYPE = np.dtype({"names": ["byte_off", "ref", "bscale", "ddiv", "nbits
                            "offsets": [0, 8, 16, 24, 32, 36], "itemsize": 40})
 
 
+# smm_grib_bitmap_t, field for field: one record per GRIB field of a raw-kept variable some of whose messages carry a
+# bitmap -- where the bitmap's bytes start in the file (GRIB_NO_BITMAP: the message has none) and how many values the
+# message's packed stream holds (the set bits; the grid's points without a bitmap)
+GRIB_BITMAP_DTYPE = np.dtype({"names": ["bitmap_off", "n_values"], "formats": ["<u8", "<u8"], "offsets": [0, 8],
+                              "itemsize": 16})
+GRIB_NO_BITMAP = 2 ** 64 - 1
+
+
 class GribField:
     """The fields of one GRIB variable kept as the file has them: `buf`, the file's bytes (one uint8 array shared by
     every variable of the file), and `rows`, a GRIB_ROW_DTYPE record per field in (time, level) order that says where
     the field's simple-packed values start in `buf` and how they decode -- value = (ref + q * bscale) / ddiv in float64,
     stored as float32.  It stands where the decoded float32 array stands (`shape`, `dtype`, `np.asarray`), and
     `Regridder(packed=True)` hands buf and rows to the GPU as they are (smm_apply_host_grib): the bits are unpacked in
-    the kernel, with the results of regridding `decode()`."""
+    the kernel, with the results of regridding `decode()`.  `bitmaps` is None, or a GRIB_BITMAP_DTYPE record per field
+    (open_grib(path, decode=False, bitmaps=True) on a variable with bitmapped messages): the stream of a bitmapped
+    field holds its present points only, the others are NaN (smm_apply_host_grib_bm)."""
 
     dtype = np.dtype(np.float32)
 
-    def __init__(self, buf, rows, shape, n_points):
+    def __init__(self, buf, rows, shape, n_points, bitmaps=None):
         """n_points: grid points of one field -- the product of the trailing (horizontal) axes of `shape`."""
         self.buf = buf
         self.rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
+        self.bitmaps = None if bitmaps is None else np.ascontiguousarray(bitmaps, dtype=GRIB_BITMAP_DTYPE).ravel()
+        if self.bitmaps is not None and self.bitmaps.size != self.rows.size:
+            raise ValueError(f"{self.bitmaps.size} bitmap records for {self.rows.size} GRIB fields")
         self.shape = tuple(int(n) for n in shape)
         self.n_points = int(n_points)
         if self.rows.size * self.n_points != int(np.prod(self.shape)):
@@ -72,8 +85,11 @@ class GribField:
         """The float32 array `open_grib(path)` gives for this variable, bit for bit."""
         out = np.empty((self.rows.size, self.n_points), dtype=np.float32)
         for i, r in enumerate(self.rows):
-            out[i] = _decode_rule(self.buf, (int(r["byte_off"]), float(r["ref"]), float(r["bscale"]), float(r["ddiv"]),
-                                             int(r["nbits"])), self.n_points)
+            rule = (int(r["byte_off"]), float(r["ref"]), float(r["bscale"]), float(r["ddiv"]), int(r["nbits"]))
+            bm = None
+            if self.bitmaps is not None and int(self.bitmaps[i]["bitmap_off"]) != GRIB_NO_BITMAP:
+                bm = (int(self.bitmaps[i]["bitmap_off"]), int(self.bitmaps[i]["n_values"]))
+            out[i] = _decode_rule(self.buf, rule, self.n_points, bm)
         return out.reshape(self.shape)
 
     def __array__(self, dtype=None, copy=None):
@@ -81,7 +97,9 @@ class GribField:
         return a if dtype is None else a.astype(dtype, copy=False)
 
     def __repr__(self):
-        return f"<GribField {self.shape} float32, {self.rows.size} packed fields, widths {sorted(set(self.rows['nbits'].tolist()))}>"
+        n_bm = 0 if self.bitmaps is None else int((self.bitmaps["bitmap_off"] != GRIB_NO_BITMAP).sum())
+        return (f"<GribField {self.shape} float32, {self.rows.size} packed fields, widths "
+                f"{sorted(set(self.rows['nbits'].tolist()))}" + (f", {n_bm} with a bitmap>" if n_bm else ">"))
 
 
 # ECMWF table 128 entries that turn up in climate work -> (cfgrib variable name, long name, units)
@@ -152,20 +170,45 @@ def _unpack_bits(raw, nbits, count):
     return bits.astype(np.uint64) @ (np.uint64(1) << np.arange(nbits - 1, -1, -1, dtype=np.uint64))
 
 
-def _decode_rule(buf, rule, count):
-    """The float64 values of one message without a bitmap from its rule (file offset of the packed values, R, 2^E,
-    10^D, bit width): the statement the message classes evaluate, on the message's own bytes only."""
+def _decode_rule(buf, rule, count, bitmap=None):
+    """The float64 values of one message from its rule (file offset of the packed values, R, 2^E, 10^D, bit width):
+    the statement the message classes evaluate, on the message's own bytes only.  bitmap: None, or (file offset of the
+    bitmap's bytes, values in the stream) -- the values go to the points whose bit is set, the others are NaN."""
     off, ref, scale, ddiv, nbits = rule
-    raw = bytes(memoryview(buf)[off:off + (count * nbits + 7) // 8])
-    return (ref + _unpack_bits(raw, nbits, count) * scale) / ddiv
+    n = count if bitmap is None else bitmap[1]
+    raw = bytes(memoryview(buf)[off:off + (n * nbits + 7) // 8])
+    packed = (ref + _unpack_bits(raw, nbits, n) * scale) / ddiv
+    if bitmap is None:
+        return packed
+    present = np.unpackbits(np.frombuffer(bytes(memoryview(buf)[bitmap[0]:bitmap[0] + (count + 7) // 8]),
+                                          dtype=np.uint8))[:count].astype(bool)
+    values = np.full(count, np.nan)
+    values[present] = packed
+    return values
+
+
+_POPCOUNT8 = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint8)
+
+
+def _count_bits(raw, n):
+    """Set bits among the first n of the byte string `raw` (MSB first), without unpacking them."""
+    if len(raw) * 8 < n:
+        raise ValueError(f"GRIB bitmap of {len(raw)} bytes for {n} grid points")
+    b = np.frombuffer(bytes(raw[:(n + 7) // 8]), dtype=np.uint8)
+    total = int(_POPCOUNT8[b].sum(dtype=np.int64))
+    if n % 8:
+        total -= int(_POPCOUNT8[int(b[-1]) & (0xFF >> (n % 8))])
+    return total
 
 
 class _Field:
     """Grid and coordinates shared by the fields of both editions.  `values` is None for a message read with
-    keep_raw (no bitmap: only its `raw_rule` was recorded); `field_values` decodes it on demand."""
+    keep_raw (only its `raw_rule` was recorded, and with keep_bitmaps the `raw_bitmap` of a message that has one: file
+    offset of the bitmap's bytes and values in the stream); `field_values` decodes it on demand."""
+    raw_bitmap = None
 
     def field_values(self, buf):
-        return self.values if self.values is not None else _decode_rule(buf, self.raw_rule, self.npoints)
+        return self.values if self.values is not None else _decode_rule(buf, self.raw_rule, self.npoints, self.raw_bitmap)
 
     def _set_grid(self, rep, ni, nj, la1, lo1, la2, lo2, n_gauss, scan, pl, tol):
         if scan & 0x20:
@@ -216,7 +259,7 @@ class _Message(_Field):
     """One decoded GRIB-1 message: metadata + values in the file's scanning order (NaN where the bitmap says so)."""
     edition = 1
 
-    def __init__(self, buf, start, keep_raw=False):
+    def __init__(self, buf, start, keep_raw=False, keep_bitmaps=False):
         if buf[start:start + 4] != b"GRIB":
             raise ValueError("not a GRIB message")
         if buf[start + 7] != 1:
@@ -252,6 +295,10 @@ class _Message(_Field):
             pos += len(bms)
             if _uint(bms[4:6]) != 0:
                 raise GribUnsupported("predefined GRIB-1 bitmaps")
+            if keep_raw and keep_bitmaps:
+                # kept raw with its bitmap: where the bitmap lies and how many bits it sets, nothing unpacked
+                self._keep_bitmapped(buf, pos, (pos - len(bms) + 6, _count_bits(bms[6:], self.npoints)))
+                return
             bitmap = np.unpackbits(np.frombuffer(bms[6:], dtype=np.uint8))[:self.npoints].astype(bool)
         bds = buf[pos:pos + _uint(buf[pos:pos + 3])]
         flag = bds[3]
@@ -281,6 +328,24 @@ class _Message(_Field):
             self.values = np.full(self.npoints, np.nan)
             self.values[bitmap] = packed
 
+    def _keep_bitmapped(self, buf, pos, raw_bitmap):
+        """The binary data section at `pos` of a message whose bitmap is `raw_bitmap`: the rule, no value unpacked."""
+        bds = buf[pos:pos + _uint(buf[pos:pos + 3])]
+        flag = bds[3]
+        if flag & 0x80:
+            raise GribUnsupported("spherical harmonic coefficients")
+        if flag & 0x40:
+            raise GribUnsupported("second-order (complex) packing")
+        if flag & 0x10:
+            raise GribUnsupported("GRIB-1 binary data section with additional flags (matrix of values)")
+        nbits, count = bds[10], raw_bitmap[1]
+        avail = ((len(bds) - 11) * 8 - (flag & 0x0F)) // nbits if nbits else count
+        if avail < count:
+            raise ValueError(f"GRIB data section holds {avail} values, the grid needs {count}")
+        self.raw_rule = (pos + 11, _ibm_float(bds[6:10]), 2.0 ** _sint(bds[4:6]), 10.0 ** self.decimal_scale, nbits)
+        self.raw_bitmap = raw_bitmap
+        self.values = None
+
     def _grid(self, gds):
         nv, pvpl, rep = gds[3], gds[4], gds[5]
         if rep not in (0, 4):
@@ -299,8 +364,11 @@ class _Field2(_Field):
     """One field of a GRIB-2 message (a message may repeat sections 2 - 7 / 3 - 7 / 4 - 7 for further fields)."""
     edition = 2
 
-    def __init__(self, discipline, sec1, sec3, sec4, sec5, sec6, sec7, prev_bitmap, data_pos=None, keep_raw=False):
-        """data_pos: file offset of section 7 (its packed values follow 5 octets later)."""
+    def __init__(self, discipline, sec1, sec3, sec4, sec5, sec6, sec7, prev_bitmap, data_pos=None, keep_raw=False,
+                 bitmap_pos=None, prev_raw_bitmap=None):
+        """data_pos: file offset of section 7 (its packed values follow 5 octets later).  bitmap_pos: file offset of
+        section 6 when bitmapped fields are kept raw too (its bits follow 6 octets later); prev_raw_bitmap: the
+        `raw_bitmap` of the field before, for a field that reuses its bitmap."""
         self.centre = _uint(sec1[5:7])
         self.time = np.datetime64(f"{_uint(sec1[12:14]):04d}-{max(sec1[14], 1):02d}-{max(sec1[15], 1):02d}"
                                   f"T{sec1[16]:02d}:{sec1[17]:02d}:{sec1[18]:02d}")
@@ -345,6 +413,19 @@ class _Field2(_Field):
         ref = float(np.frombuffer(bytes(sec5[11:15]), dtype=">f4")[0])
         scale, decimal, nbits = 2.0 ** _sint(sec5[15:17]), _sint(sec5[17:19]), sec5[19]
         indicator = sec6[5] if sec6 is not None else 255
+        if keep_raw and bitmap_pos is not None and data_pos is not None and indicator in (0, 254):
+            # kept raw with its bitmap: where the bitmap lies and how many bits it sets, nothing unpacked
+            if indicator == 254 and prev_raw_bitmap is None:
+                raise ValueError("GRIB-2 field refers to a previous bitmap that does not exist")
+            self.raw_bitmap = (bitmap_pos + 6, _count_bits(sec6[6:], self.npoints)) if indicator == 0 else prev_raw_bitmap
+            self.bitmap = None
+            if n_coded != self.raw_bitmap[1]:
+                raise ValueError(f"GRIB-2 data section codes {n_coded} values, grid and bitmap need {self.raw_bitmap[1]}")
+            if nbits and (len(sec7) - 5) * 8 < n_coded * nbits:
+                raise ValueError("GRIB-2 data section is shorter than its values")
+            self.raw_rule = (data_pos + 5, ref, scale, 10.0 ** decimal, nbits)
+            self.values = None
+            return
         if indicator == 0:
             self.bitmap = np.unpackbits(np.frombuffer(bytes(sec6[6:]), dtype=np.uint8))[:self.npoints].astype(bool)
         elif indicator == 254:
@@ -373,14 +454,14 @@ class _Field2(_Field):
             self.values[self.bitmap] = packed
 
 
-def _fields_of_message2(buf, start, keep_raw=False):
+def _fields_of_message2(buf, start, keep_raw=False, keep_bitmaps=False):
     """The fields of the GRIB-2 message at `start`, and the message's length."""
     discipline, total = buf[start + 6], _uint(buf[start + 8:start + 16])
     if buf[start + total - 4:start + total] != b"7777":
         raise ValueError("GRIB message does not end in 7777 (truncated file?)")
     pos, end = start + 16, start + total - 4
-    sec = {}
-    fields, bitmap = [], None
+    sec, sec6_pos = {}, None
+    fields, bitmap, raw_bitmap = [], None, None
     while pos < end:
         length, number = _uint(buf[pos:pos + 4]), buf[pos + 4]
         if length < 5 or pos + length > end:
@@ -388,12 +469,15 @@ def _fields_of_message2(buf, start, keep_raw=False):
         sec[number] = buf[pos:pos + length]
         if number == 3:                       # a new grid: sections 4 - 7 follow again
             sec.pop(6, None)
+        if number == 6 and sec[6][5] == 0:    # a bitmap of its own: a later "same as before" (254) means this one
+            sec6_pos = pos
         if number == 7:
             for need in (1, 3, 4, 5):
                 if need not in sec:
                     raise ValueError(f"GRIB-2 message without section {need}")
-            f = _Field2(discipline, sec[1], sec[3], sec[4], sec[5], sec.get(6), sec[7], bitmap, data_pos=pos, keep_raw=keep_raw)
-            bitmap = f.bitmap
+            f = _Field2(discipline, sec[1], sec[3], sec[4], sec[5], sec.get(6), sec[7], bitmap, data_pos=pos, keep_raw=keep_raw,
+                        bitmap_pos=sec6_pos if keep_bitmaps else None, prev_raw_bitmap=raw_bitmap)
+            bitmap, raw_bitmap = f.bitmap, f.raw_bitmap
             fields.append(f)
         pos += length
     return fields, total
@@ -404,9 +488,9 @@ def read_messages(path):
         return _messages_of(f.read(), path)
 
 
-def _messages_of(buf, path, keep_raw=False):
+def _messages_of(buf, path, keep_raw=False, keep_bitmaps=False):
     """The messages of a file's bytes.  keep_raw: those without a bitmap are not unpacked (`values` is None, `raw_rule`
-    says how to)."""
+    says how to); with keep_bitmaps neither are those with one (`raw_bitmap` says where it lies)."""
     out, pos = [], 0
     while True:
         pos = buf.find(b"GRIB", pos)
@@ -414,13 +498,13 @@ def _messages_of(buf, path, keep_raw=False):
             break
         edition = buf[pos + 7] if pos + 8 <= len(buf) else 0
         if edition == 2:
-            fields, length = _fields_of_message2(buf, pos, keep_raw)
+            fields, length = _fields_of_message2(buf, pos, keep_raw, keep_bitmaps)
             out.extend(fields)
             pos += length
             continue
         if edition != 1:
             raise GribUnsupported(f"GRIB edition {edition}")
-        m = _Message(buf, pos, keep_raw)
+        m = _Message(buf, pos, keep_raw, keep_bitmaps)
         out.append(m)
         pos += m.length
     if not out:
@@ -428,14 +512,17 @@ def _messages_of(buf, path, keep_raw=False):
     return out
 
 
-def open_grib(path, decode=True):
+def open_grib(path, decode=True, bitmaps=False):
     """Dataset of the fields of a GRIB file, one variable per parameter.  All messages must share one grid.
     decode=False keeps every variable whose (time, level) slots are all filled by messages without a bitmap as a
     `GribField` -- the file's bytes and one decode rule per field, which `Regridder(packed=True)` ships to the GPU as
-    they are; `np.asarray` of it is the decoded float32 array.  Any other variable is decoded as with decode=True."""
+    they are; `np.asarray` of it is the decoded float32 array.  Any other variable is decoded as with decode=True.
+    bitmaps=True (with decode=False) keeps messages with a bitmap section raw as well (edition 1 section 3; edition 2
+    section 6 with its own bitmap or the previous field's): the reader records where the bitmap lies and how many bits
+    it sets, `GribField.bitmaps` holds one record per field, and a variable may mix messages with and without one."""
     with open(path, "rb") as f:
         file_bytes = f.read()
-    msgs = _messages_of(file_bytes, path, keep_raw=not decode)
+    msgs = _messages_of(file_bytes, path, keep_raw=not decode, keep_bitmaps=bool(bitmaps) and not decode)
     shared = np.frombuffer(file_bytes, dtype=np.uint8) if not decode else None
     if len({m.grid_key for m in msgs}) != 1:
         raise GribUnsupported("GRIB file with fields on several grids")
@@ -481,10 +568,14 @@ def open_grib(path, decode=True):
                  for m in group]
         rows = np.zeros((len(times), len(levels)), dtype=GRIB_ROW_DTYPE)
         filled = np.zeros((len(times), len(levels)), dtype=bool)
+        bms = np.zeros((len(times), len(levels)), dtype=GRIB_BITMAP_DTYPE)
+        bms["bitmap_off"], bms["n_values"] = GRIB_NO_BITMAP, g.npoints
         for m, slot in zip(group, slots):
             if m.raw_rule is not None:
                 rows[slot] = m.raw_rule + (0,)
                 filled[slot] = True
+                if m.raw_bitmap is not None:
+                    bms[slot] = m.raw_bitmap
         # raw: every (time, level) slot filled by a message without a bitmap (a missing slot is NaN, which only a
         # decoded array holds).  Such a variable is never unpacked here; any other is decoded as with decode=True
         raw_ok = not decode and all(m.raw_rule is not None for m in group) and bool(filled.all())
@@ -507,8 +598,9 @@ def open_grib(path, decode=True):
         shape = tuple(n for n, keep in ((len(times), len(times) > 1), (len(levels), len(levels) > 1)) if keep) + hshape
         if raw_ok:
             if len(times) == 1:
-                rows = rows[0:1]
-            arr = GribField(shared, rows, shape, int(np.prod(hshape)))
+                rows, bms = rows[0:1], bms[0:1]
+            arr = GribField(shared, rows, shape, int(np.prod(hshape)),
+                            bitmaps=bms if any(m.raw_bitmap is not None for m in group) else None)
         else:
             arr = arr.reshape(shape)
         ds[name] = DataArray(arr, dims=tuple(dims) + hdims, coords=vcoords, name=name,

@@ -73,10 +73,11 @@ def write_netcdf3(ds, path):
     return path
 
 
-def open_weights(path, decode=True):
+def open_weights(path, decode=True, bitmaps=False):
     """decode=False keeps CF-packed variables as stored -- the raw integers with their scale_factor / add_offset /
     _FillValue / missing_value attributes -- which is what `Regridder(..., packed=True)` regrids without a host decode.
-    For a GRIB file it keeps the simple-packed bit streams (`griblite.GribField`), regridded raw the same way."""
+    For a GRIB file it keeps the simple-packed bit streams (`griblite.GribField`), regridded raw the same way;
+    bitmaps=True keeps the variables whose messages carry a bitmap raw as well (`griblite.open_grib`)."""
     if str(path).endswith(".npz"):
         z = np.load(path, allow_pickle=False)
         meta = json.loads(str(z["__meta__"]))
@@ -92,7 +93,7 @@ def open_weights(path, decode=True):
         magic = f.read(4)
     if magic == b"GRIB":
         from .griblite import open_grib      # GRIB edition 1 (the reference reads these through cfgrib)
-        return open_grib(path, decode=decode)    # decode=False: variables stay GribFields (raw bits + rules)
+        return open_grib(path, decode=decode, bitmaps=bitmaps)    # decode=False: variables stay GribFields (raw bits + rules)
     if magic[:3] == b"CDF":
         from scipy.io import netcdf_file
         with netcdf_file(path, "r", mmap=False) as nc:

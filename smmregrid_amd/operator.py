@@ -325,14 +325,25 @@ class SparseOperator:
         rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
         return rows, ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct))
 
-    def apply_grib(self, x, rows, x_bytes=None, y=None, masked=False, remap_area_min=0.0, flags=0, stream=None):
+    def _grib_bitmaps(self, bitmaps, n_batch):
+        from .griblite import GRIB_BITMAP_DTYPE
+        bitmaps = np.ascontiguousarray(bitmaps, dtype=GRIB_BITMAP_DTYPE).ravel()
+        if bitmaps.size != n_batch:
+            raise ValueError(f"{bitmaps.size} bitmap records for {n_batch} rows")
+        return bitmaps, ctypes.cast(bitmaps.ctypes.data, ctypes.POINTER(_lib.GribBitmapStruct))
+
+    def apply_grib(self, x, rows, x_bytes=None, y=None, masked=False, remap_area_min=0.0, flags=0, stream=None,
+                   bitmaps=None):
         """Y = epilogue(fill(decode(X)) . W) for GRIB simple-packed fields resident in HBM as they are on disk
         (smm_apply_grib).  x: a `DeviceArray` of uint8 -- or a raw device pointer with x_bytes -- holding the packed
         bit streams (4-byte aligned; the array -- or the allocation behind a raw pointer -- must cover x_bytes rounded
         up to 4, the kernel reads whole 32-bit words: a shorter DeviceArray is a ValueError); rows: one `GRIB_ROW_DTYPE`
         record per batch row (where its values start in x, its reference value, 2^E, 10^D, its bit width).  The bits
         are unpacked in the kernel's gather; the float64 result is bit-identical to `apply` on the float32 field a
-        host decode gives.  Returns a (B, D) DeviceArray."""
+        host decode gives.  Returns a (B, D) DeviceArray.
+        bitmaps: one `GRIB_BITMAP_DTYPE` record per row (smm_apply_grib_bm) -- where the row's bitmap lies in x, or
+        `GRIB_NO_BITMAP`, and how many values its stream holds.  A cell whose bit is 0 is NaN, as the host decode has
+        it; the cell's rank in the stream is looked up in a table built on the device ahead of the gather."""
         rows, rows_p = self._grib_rows(rows)
         if isinstance(x, DeviceArray):
             if x.dtype != np.uint8:
@@ -350,14 +361,20 @@ class SparseOperator:
         elif y.shape != (n_batch, self.n_dst) or y.dtype != np.float64:
             raise ValueError(f"Y must be a float64 ({n_batch}, {self.n_dst}) DeviceArray")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        if bitmaps is not None:
+            bitmaps, bm_p = self._grib_bitmaps(bitmaps, n_batch)
+            _lib.call("smm_apply_grib_bm", self.handle, x_ptr, n_bytes, rows_p, bm_p, _ptr(y), _lib.SMM_F64, self.n_dst,
+                      n_batch, float(remap_area_min), fl, _stream_handle(stream))
+            return y
         _lib.call("smm_apply_grib", self.handle, x_ptr, n_bytes, rows_p, _ptr(y), _lib.SMM_F64, self.n_dst, n_batch,
                   float(remap_area_min), fl, _stream_handle(stream))
         return y
 
-    def apply_host_grib(self, buf, rows, out=None, masked=False, remap_area_min=0.0, flags=0, chunk_rows=0):
+    def apply_host_grib(self, buf, rows, out=None, masked=False, remap_area_min=0.0, flags=0, chunk_rows=0, bitmaps=None):
         """The host twin (smm_apply_host_grib): buf is a host uint8 array -- typically a whole GRIB file -- and rows as
         for `apply_grib`.  Each row's packed bytes are staged and cross PCIe as they are (2 B per cell at 16 bits), no
-        host decode runs.  Returns a float64 (B, D) numpy array, the bits of `apply_host` on the decoded float32 field."""
+        host decode runs.  Returns a float64 (B, D) numpy array, the bits of `apply_host` on the decoded float32 field.
+        bitmaps as for `apply_grib` (smm_apply_host_grib_bm): a bitmapped row's bitmap bytes are staged behind its data."""
         rows, rows_p = self._grib_rows(rows)
         buf = np.ascontiguousarray(buf)
         if buf.dtype != np.uint8 or buf.ndim != 1:
@@ -368,6 +385,11 @@ class SparseOperator:
         if out.shape != (n_batch, self.n_dst) or out.dtype != np.float64 or not out.flags.c_contiguous:
             raise ValueError(f"out must be a C-contiguous float64 ({n_batch}, {self.n_dst}) array")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        if bitmaps is not None:
+            bitmaps, bm_p = self._grib_bitmaps(bitmaps, n_batch)
+            _lib.call("smm_apply_host_grib_bm", self.handle, _cptr(buf), buf.size, rows_p, bm_p, _cptr(out), _lib.SMM_F64,
+                      self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows))
+            return out
         _lib.call("smm_apply_host_grib", self.handle, _cptr(buf), buf.size, rows_p, _cptr(out), _lib.SMM_F64,
                   self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows))
         return out

@@ -353,7 +353,7 @@ class Regridder(object):
 
     def _grib_or_decoded(self, source_data, datagridtype):
         """A GRIB variable kept raw (`GribField`): with packed=True on 2-D weights and a float64 result it stays as it
-        is and apply_weights ships its bit streams (smm_apply_host_grib); everything else decodes it on the host --
+        is and apply_weights ships its bit streams (smm_apply_host_grib, with bitmaps smm_apply_host_grib_bm); everything else decodes it on the host --
         what np.asarray would do anyway -- and goes on as before."""
         why = None
         if self.packed:
@@ -541,7 +541,8 @@ class Regridder(object):
                     raise ValueError(f"source grid has {src.n_points} cells, weights expect {op.n_src}")
                 if src.rows.size != n_batch:
                     raise ValueError(f"{src.rows.size} GRIB fields for {n_batch} batch rows of shape {tuple(kept_shape)}")
-                y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min)
+                # (with their bitmaps, if any: smm_apply_host_grib_bm ranks them on the device)
+                y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps)
                 return y.reshape(kept_shape + tgt_shape)
             if sb_in:
                 x = src.reshape(-1, n_batch)                  # (S, B): the batch values of a cell contiguous
