@@ -598,6 +598,51 @@ int smm_group_apply_host_cf(smm_group_t g,
                             const smm_cf_decode_t* cf);
 
 /*
+ * smm_group_apply / smm_group_apply_host for GRIB simple-packed fields shipped RAW, with or without bitmaps: the masked
+ * levels of ocean variables, whose bitmapped streams hold the present cells only.  rows (and bitmaps, or NULL: no row has
+ * one, as in smm_apply_grib_bm) are HOST arrays of n_outer * n_lev * n_inner records; batch row (o, l, i) is record
+ * (o * n_lev + l) * n_inner + i, data level l uses group member level_index[l].  Every row keeps the semantics of
+ * smm_apply_grib_bm -- any width 0..32 and byte alignment, rows in any buffer order and overlapping, rows with and
+ * without a bitmap mixed, several rows naming one bitmap_off, a cell whose bitmap bit is 0 a float32 NaN -- and the
+ * results are bit-identical to smm_group_apply / smm_group_apply_host with SMM_F32 X on the field a host decode gives.
+ * One kernel launch covers all levels (the grouped form of the GRIB gather: grid = destination blocks x batch tiles x
+ * levels, the BT batch rows of a thread are rows (o, i) of one level); ahead of it, on the same stream, one build of the
+ * rank tables runs over all rows of the call or chunk.  A grid beyond the launch limit is cut over the outer and inner
+ * range and, for a single row, over the levels.
+ *   smm_group_apply_grib       x device bytes as in smm_apply_grib; Y rows at o*ys_outer + l*ys_lev + i*ys_inner
+ *                              (elements, 64-bit) as in smm_group_apply.  The device row table, the bitmap records and the
+ *                              rank tables live in buffers the GROUP owns (grown on demand, under a mutex of their own),
+ *                              as an operator holds them for smm_apply_grib_bm: calls on one group take turns and are
+ *                              ordered against each other only on ONE stream; concurrent calls on different streams
+ *                              need one group handle each.
+ *   smm_group_apply_host_grib  x_host host bytes; Y host (n_outer, n_inner, n_lev, D) when transpose != 0, else
+ *                              (n_lev, n_outer, n_inner, D), pinned or pageable, as smm_group_apply_host.  A chunk is a
+ *                              block of consecutive outer indices with all n_lev * n_inner of their rows (consecutive
+ *                              records), staged as smm_apply_host_grib_bm stages a chunk and sized by bytes the same
+ *                              way -- staged bytes, rank tables and rows * n_dst * 8 of Y against ~256 MiB and an eighth
+ *                              of the free device memory -- but never less than one outer index; chunk_outer > 0 fixes
+ *                              the outer indices per chunk.  SMM_HOST_STAT_H2D_BYTES counts per row
+ *                              40 + (bitmaps ? 16 : 0) + align4(data) + (bitmapped ? align4(ceil(n_src / 8)) : 0).
+ * Refusals, before any device is touched, in the order and with the codes of smm_apply_grib_bm: flag bits outside the
+ * set; SMM_APPLY_SKIPNA, SMM_APPLY_KERNEL_TILE and the batch-fastest / host-pack flags, and y_dtype != SMM_F64:
+ * SMM_ERR_UNSUPPORTED; null pointers, negative counts, a misaligned x (device entry) or y, a bad rule: SMM_ERR_INVALID.
+ * Then, SMM_ERR_INVALID all: a NULL group, a level_index entry outside the group, a row or bitmap that leaves
+ * [0, x_bytes) for the group's n_src, a used member without the dst_imask / dst_frac the call asks for.
+ */
+int smm_group_apply_grib(smm_group_t g, const void* x, int64_t x_bytes,
+                         const smm_grib_row_t* rows /* host */, const smm_grib_bitmap_t* bitmaps /* host, or NULL */,
+                         void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev, int64_t ys_inner,
+                         int64_t n_outer, int64_t n_lev, int64_t n_inner,
+                         const int32_t* level_index, const uint8_t* masked_levels,
+                         double remap_area_min, unsigned flags, void* stream);
+int smm_group_apply_host_grib(smm_group_t g, const void* x_host, int64_t x_bytes,
+                              const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps,
+                              void* y_host, int y_dtype,
+                              int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose,
+                              const int32_t* level_index, const uint8_t* masked_levels,
+                              double remap_area_min, unsigned flags, int64_t chunk_outer);
+
+/*
  * The three group _cf entries with a CF-packed RESULT, with the contract of smm_apply_pk / smm_apply_sb_pk /
  * smm_apply_host_pk: enc != NULL stores Y as raw 2-byte integers, encoded inside the kernels' stores by *enc; y_dtype
  * must then be SMM_I16 / SMM_U16, y 2-byte aligned, and every Y stride (ys_outer / ys_lev / ys_inner, ys_lev / ys_batch)

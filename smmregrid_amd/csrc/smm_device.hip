@@ -294,6 +294,12 @@ struct smm_group {
   std::map<std::string, DeviceBuf<char>> cfg_cache;
   std::mutex pipe_mu;  // smm_group_apply_host calls on one group take turns
   HostPipe pipe;
+  // smm_group_apply_grib / smm_group_apply_host_grib: the row table, the bitmap records and the rank tables, as
+  // smm_operator holds them -- grown on demand, the first three under grib_mu, the slots' rank buffers under pipe_mu
+  std::mutex grib_mu;
+  DeviceBuf<smm_grib_row_t> d_grib_rows;
+  DeviceBuf<GribRowBitmap> d_grib_bm;
+  DeviceBuf<char> d_grib_rank, d_pipe_rank[2];
 };
 
 namespace {
@@ -1395,6 +1401,24 @@ static bool grib_needs_division(const smm_grib_row_t* rows, int64_t n_batch) {
 // batch when the grid would pass the limit (smm::split_batch, as run_apply)
 // d_bm with n_tables > 0 (smm_apply_grib_bm): the rows' device bitmap records; d_rank holds n_tables rank tables of
 // ceil(n_src / 32) entries and behind them n_tables x segments totals.  The tables are built first, on the same stream.
+// The rank tables of n_rows rows' bitmaps over the words of x (launch_grib_build): d_rank holds n_tables tables of
+// ceil(n_src / 32) entries and behind them n_tables x segments totals.
+static int launch_grib_tables(const uint32_t* x, uint64_t last_word, const GribRowBitmap* d_bm, char* d_rank, size_t n_tables,
+                              int64_t n_rows, int64_t n_src, hipStream_t s) {
+  const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)n_src);
+  GribBuildArgs b{};
+  b.x = x;
+  b.bm = d_bm;
+  b.table = (smm_grib::GribRankEntry*)d_rank;
+  b.totals = (uint32_t*)(d_rank + n_tables * (size_t)n_blocks * sizeof(smm_grib::GribRankEntry));
+  b.last_word = last_word;
+  b.n_j = n_rows;
+  b.n_src = (uint32_t)n_src;
+  b.n_blocks = (uint32_t)n_blocks;
+  b.n_segs = (uint32_t)smm_grib::bitmap_segments((uint64_t)n_src);
+  return smm_launch::launch_grib_build(b, s);
+}
+
 static int launch_grib_rows(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* d_rows, bool div, void* y,
                             int64_t ldy, int64_t n_batch, double area_min, unsigned flags, hipStream_t s,
                             const GribRowBitmap* d_bm = nullptr, char* d_rank = nullptr, size_t n_tables = 0) {
@@ -1415,19 +1439,8 @@ static int launch_grib_rows(smm_operator_t op, const void* x, int64_t x_bytes, c
   };
   const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)op->csr.n_src);
   const bool with_tables = d_bm && n_tables > 0 && n_blocks > 0;
-  if (with_tables) {
-    GribBuildArgs b{};
-    b.x = a.x;
-    b.bm = d_bm;
-    b.table = (smm_grib::GribRankEntry*)d_rank;
-    b.totals = (uint32_t*)(d_rank + n_tables * (size_t)n_blocks * sizeof(smm_grib::GribRankEntry));
-    b.last_word = a.last_word;
-    b.n_j = n_batch;
-    b.n_src = (uint32_t)op->csr.n_src;
-    b.n_blocks = (uint32_t)n_blocks;
-    b.n_segs = (uint32_t)smm_grib::bitmap_segments((uint64_t)op->csr.n_src);
-    if (int rc = smm_launch::launch_grib_build(b, s)) return rc;
-  }
+  if (with_tables)
+    if (int rc = launch_grib_tables(a.x, a.last_word, d_bm, d_rank, n_tables, n_batch, op->csr.n_src, s)) return rc;
   auto launch_part = [&](int64_t o0, int64_t n_o, int64_t, int64_t) -> int {
     GribBitmapArgs p{};
     static_cast<GribArgs&>(p) = a;
@@ -1446,19 +1459,17 @@ static int launch_grib_rows(smm_operator_t op, const void* x, int64_t x_bytes, c
   return rc;
 }
 
-// bitmaps: null, or the records of smm_apply_grib_bm
-static int smm_apply_grib_impl(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
-                               const smm_grib_bitmap_t* bitmaps, void* y, int64_t ldy, int64_t n_batch, double area_min,
-                               unsigned flags, void* stream) {
-  if (n_batch == 0 || op->csr.n_dst == 0) return SMM_OK;
-  DeviceGuard guard(op->device);
-  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
-  hipStream_t s = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lock(op->grib_mu);
-  if (op->d_grib_rows.bytes() < (size_t)n_batch * sizeof(smm_grib_row_t)) {
+// The host tables of a device-entry call into the buffers their owner -- an operator or a group, under its grib_mu --
+// keeps for them: h->d_grib_rows, and when some row has a bitmap h->d_grib_bm, with h->d_grib_rank sized for the
+// *n_tables rank tables.
+extern "C++" {
+template <typename Handle>
+static int upload_grib_tables(Handle* h, const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_batch,
+                              int64_t n_src, hipStream_t s, size_t* n_tables_out) {
+  if (h->d_grib_rows.bytes() < (size_t)n_batch * sizeof(smm_grib_row_t)) {
     // freeing the old table waits for the device: no kernel still reads it
-    const size_t have = op->d_grib_rows.bytes() / sizeof(smm_grib_row_t);
-    SMM_HIP(op->d_grib_rows.alloc(std::max<size_t>((size_t)n_batch, 2 * have)));
+    const size_t have = h->d_grib_rows.bytes() / sizeof(smm_grib_row_t);
+    SMM_HIP(h->d_grib_rows.alloc(std::max<size_t>((size_t)n_batch, 2 * have)));
   }
   // `rows` may be reused on return: from pageable memory the runtime has taken the bytes when hipMemcpyAsync returns,
   // from page-locked memory it has not -- such a table goes through a pageable copy first.  The copy itself is ordered
@@ -1468,13 +1479,13 @@ static int smm_apply_grib_impl(smm_operator_t op, const void* x, int64_t x_bytes
     pageable.assign(rows, rows + n_batch);
     rows = pageable.data();
   }
-  SMM_HIP(hipMemcpyAsync(op->d_grib_rows.get(), rows, (size_t)n_batch * sizeof(smm_grib_row_t), hipMemcpyHostToDevice, s));
+  SMM_HIP(hipMemcpyAsync(h->d_grib_rows.get(), rows, (size_t)n_batch * sizeof(smm_grib_row_t), hipMemcpyHostToDevice, s));
   // the bitmap records go up beside it, each bitmapped row with the place of its rank table; a pageable vector in any
   // case.  Only bitmapped rows take table space; a call without one runs the plain gather.
   std::vector<GribRowBitmap> bm;
   size_t n_tables = 0;
   if (bitmaps) {
-    const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)op->csr.n_src);
+    const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)n_src);
     bm.resize((size_t)n_batch);
     for (int64_t b = 0; b < n_batch; ++b) {
       const bool has = bitmaps[b].bitmap_off != SMM_GRIB_NO_BITMAP;
@@ -1483,17 +1494,70 @@ static int smm_apply_grib_impl(smm_operator_t op, const void* x, int64_t x_bytes
     }
   }
   if (n_tables > 0) {
-    if (op->d_grib_bm.bytes() < bm.size() * sizeof(GribRowBitmap)) {
-      const size_t have = op->d_grib_bm.bytes() / sizeof(GribRowBitmap);
-      SMM_HIP(op->d_grib_bm.alloc(std::max<size_t>(bm.size(), 2 * have)));
+    if (h->d_grib_bm.bytes() < bm.size() * sizeof(GribRowBitmap)) {
+      const size_t have = h->d_grib_bm.bytes() / sizeof(GribRowBitmap);
+      SMM_HIP(h->d_grib_bm.alloc(std::max<size_t>(bm.size(), 2 * have)));
     }
-    const size_t need = n_tables * (size_t)smm_grib::bitmap_blocks((uint64_t)op->csr.n_src) * sizeof(smm_grib::GribRankEntry) +
-                        n_tables * (size_t)smm_grib::bitmap_segments((uint64_t)op->csr.n_src) * sizeof(uint32_t);
-    if (op->d_grib_rank.bytes() < need) SMM_HIP(op->d_grib_rank.alloc(std::max(need, 2 * op->d_grib_rank.bytes())));
-    SMM_HIP(hipMemcpyAsync(op->d_grib_bm.get(), bm.data(), bm.size() * sizeof(GribRowBitmap), hipMemcpyHostToDevice, s));
+    const size_t need = n_tables * (size_t)smm_grib::bitmap_blocks((uint64_t)n_src) * sizeof(smm_grib::GribRankEntry) +
+                        n_tables * (size_t)smm_grib::bitmap_segments((uint64_t)n_src) * sizeof(uint32_t);
+    if (h->d_grib_rank.bytes() < need) SMM_HIP(h->d_grib_rank.alloc(std::max(need, 2 * h->d_grib_rank.bytes())));
+    SMM_HIP(hipMemcpyAsync(h->d_grib_bm.get(), bm.data(), bm.size() * sizeof(GribRowBitmap), hipMemcpyHostToDevice, s));
   }
+  *n_tables_out = n_tables;
+  return SMM_OK;
+}
+}  // extern "C++"
+
+// bitmaps: null, or the records of smm_apply_grib_bm
+static int smm_apply_grib_impl(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
+                               const smm_grib_bitmap_t* bitmaps, void* y, int64_t ldy, int64_t n_batch, double area_min,
+                               unsigned flags, void* stream) {
+  if (n_batch == 0 || op->csr.n_dst == 0) return SMM_OK;
+  DeviceGuard guard(op->device);
+  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lock(op->grib_mu);
+  size_t n_tables = 0;
+  if (int rc = upload_grib_tables(op, rows, bitmaps, n_batch, op->csr.n_src, s, &n_tables)) return rc;
   return launch_grib_rows(op, x, x_bytes, op->d_grib_rows.get(), grib_needs_division(rows, n_batch), y, ldy, n_batch, area_min,
                           flags, s, n_tables ? op->d_grib_bm.get() : nullptr, op->d_grib_rank.get(), n_tables);
+}
+
+// Staging of a chunk (rows [ch.r0, ch.r0 + ch.nr) of the call) into the pinned buffer hx: its table first, then each
+// row's data bytes at the next 4-byte-aligned offset; the table's byte_off are those offsets, from the start of the
+// buffer.  A pinned x_host is staged all the same: the rows of a chunk need not be adjacent in it.  With bitmaps the
+// chunk's bitmap records follow the table (their bitmap_off are staged offsets as well, their second word the place of
+// the row's rank table in the slot's rank buffer), and a bitmapped row's data bytes -- ceil(n_values * nbits / 8) of
+// them -- are followed by its own copy of its bitmap.  *n_tables: the bitmapped rows of the chunk.
+static int stage_grib_chunk(char* hx, const smm::GribChunk& ch, const void* x_host, const smm_grib_row_t* rows,
+                            const smm_grib_bitmap_t* bitmaps, int64_t S, size_t* n_tables_out) {
+  size_t n_tables = 0;
+  smm_grib_row_t* table = (smm_grib_row_t*)hx;
+  GribRowBitmap* bm = (GribRowBitmap*)(hx + (size_t)ch.nr * sizeof(smm_grib_row_t));
+  uint64_t cursor = (uint64_t)ch.nr * (sizeof(smm_grib_row_t) + (bitmaps ? sizeof(GribRowBitmap) : 0));
+  const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)S), bm_bytes = smm_grib::bitmap_bytes((uint64_t)S);
+  auto data_bytes = [&](int64_t r) {
+    const bool has = bitmaps && bitmaps[ch.r0 + r].bitmap_off != SMM_GRIB_NO_BITMAP;
+    return smm_grib::row_bytes(has ? bitmaps[ch.r0 + r].n_values : (uint64_t)S, rows[ch.r0 + r].nbits);
+  };
+  for (int64_t r = 0; r < ch.nr; ++r) {
+    table[r] = rows[ch.r0 + r];
+    table[r].byte_off = cursor;
+    cursor += smm_grib::align4(data_bytes(r));
+    if (!bitmaps) continue;
+    const bool has = bitmaps[ch.r0 + r].bitmap_off != SMM_GRIB_NO_BITMAP;
+    bm[r] = GribRowBitmap{has ? cursor : SMM_GRIB_NO_BITMAP, has ? n_tables * n_blocks : 0};
+    if (has) cursor += smm_grib::align4(bm_bytes), ++n_tables;
+  }
+  for (int64_t r = 0; r < ch.nr; ++r) {   // each row's copy is spread over the staging pool (host_copy)
+    if (int rc = host_copy(hx + table[r].byte_off, (const char*)x_host + rows[ch.r0 + r].byte_off, (size_t)data_bytes(r)))
+      return rc;
+    if (bitmaps && bm[r].bitmap_off != SMM_GRIB_NO_BITMAP)
+      if (int rc = host_copy(hx + bm[r].bitmap_off, (const char*)x_host + bitmaps[ch.r0 + r].bitmap_off, (size_t)bm_bytes))
+        return rc;
+  }
+  *n_tables_out = n_tables;
+  return SMM_OK;
 }
 
 static int smm_apply_host_grib_impl(smm_operator_t op, const void* x_host, const smm_grib_row_t* rows,
@@ -1528,41 +1592,13 @@ static int smm_apply_host_grib_impl(smm_operator_t op, const void* x_host, const
       memcpy((char*)y_host + (size_t)(ch.r0 + r) * yrow, (char*)pipe.hy[b].get() + (size_t)r * D * 8, (size_t)D * 8);
     return SMM_OK;
   };
-  // Staging of a chunk: its table first, then each row's data bytes at the next 4-byte-aligned offset; the table's
-  // byte_off are those offsets, from the start of the buffer.  A pinned x_host is staged all the same: the rows of a
-  // chunk need not be adjacent in it.  With bitmaps the chunk's bitmap records follow the table (their bitmap_off
-  // are staged offsets as well, their second word the place of the row's rank table in the slot's rank buffer), and a
-  // bitmapped row's data bytes -- ceil(n_values * nbits / 8) of them -- are followed by its own copy of its bitmap.
   auto launch = [&](int64_t c, int b) -> int {
     const smm::GribChunk& ch = plan.chunks[(size_t)c];
     char* hx = (char*)pipe.hx[b].get();
     size_t n_tables = 0;
     {
       StageTimer t(st.v[SMM_HOST_STAT_STAGE_IN_MS]);
-      smm_grib_row_t* table = (smm_grib_row_t*)hx;
-      GribRowBitmap* bm = (GribRowBitmap*)(hx + (size_t)ch.nr * sizeof(smm_grib_row_t));
-      uint64_t cursor = (uint64_t)ch.nr * (sizeof(smm_grib_row_t) + (bitmaps ? sizeof(GribRowBitmap) : 0));
-      const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)S), bm_bytes = smm_grib::bitmap_bytes((uint64_t)S);
-      auto data_bytes = [&](int64_t r) {
-        const bool has = bitmaps && bitmaps[ch.r0 + r].bitmap_off != SMM_GRIB_NO_BITMAP;
-        return smm_grib::row_bytes(has ? bitmaps[ch.r0 + r].n_values : (uint64_t)S, rows[ch.r0 + r].nbits);
-      };
-      for (int64_t r = 0; r < ch.nr; ++r) {
-        table[r] = rows[ch.r0 + r];
-        table[r].byte_off = cursor;
-        cursor += smm_grib::align4(data_bytes(r));
-        if (!bitmaps) continue;
-        const bool has = bitmaps[ch.r0 + r].bitmap_off != SMM_GRIB_NO_BITMAP;
-        bm[r] = GribRowBitmap{has ? cursor : SMM_GRIB_NO_BITMAP, has ? n_tables * n_blocks : 0};
-        if (has) cursor += smm_grib::align4(bm_bytes), ++n_tables;
-      }
-      for (int64_t r = 0; r < ch.nr; ++r) {   // each row's copy is spread over the staging pool (host_copy)
-        if (int rc = host_copy(hx + table[r].byte_off, (const char*)x_host + rows[ch.r0 + r].byte_off, (size_t)data_bytes(r)))
-          return rc;
-        if (bitmaps && bm[r].bitmap_off != SMM_GRIB_NO_BITMAP)
-          if (int rc = host_copy(hx + bm[r].bitmap_off, (const char*)x_host + bitmaps[ch.r0 + r].bitmap_off, (size_t)bm_bytes))
-            return rc;
-      }
+      if (int rc = stage_grib_chunk(hx, ch, x_host, rows, bitmaps, S, &n_tables)) return rc;
     }
     SMM_HIP(pipe.mark(b, 0));
     SMM_HIP(hipMemcpyAsync(pipe.dx[b].get(), hx, ch.x_bytes, hipMemcpyHostToDevice, pipe.stream[b]));
@@ -2066,6 +2102,200 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, void* y_
   return run_host_pipeline(pipe, n_chunks, st, launch, deliver);
 }
 
+// ---- GRIB simple-packed fields on a level group: smm_group_apply_grib / smm_group_apply_host_grib
+
+// What the two entries refuse once check_grib_call has passed, still before any device is touched: the group, its
+// level_index, where the rows lie in the buffer (the members share n_src) and each used member's epilogue.
+static int check_grib_group(smm_group_t g, int64_t x_bytes, const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps,
+                            int64_t n_rows, int64_t n_lev, const int32_t* level_index, const uint8_t* masked_levels,
+                            double area_min, unsigned flags) {
+  if (!g) return fail(SMM_ERR_INVALID, "null group");
+  if (int rc = check_levels(g, n_lev, level_index, masked_levels, 0.0, 0u)) return rc;   // level_index alone
+  const int64_t S = g->ops[0]->csr.n_src;
+  std::string err;
+  if (!(bitmaps ? smm::check_grib_bitmaps(rows, bitmaps, n_rows, S, x_bytes, err)
+                : smm::check_grib_ranges(rows, n_rows, S, x_bytes, err)))
+    return fail(SMM_ERR_INVALID, err);
+  return check_levels(g, n_lev, level_index, masked_levels, area_min, flags);
+}
+// rows of the call, or -1 when a count is negative (check_grib_call refuses it in its place)
+static int64_t grib_group_rows(int64_t n_outer, int64_t n_lev, int64_t n_inner) {
+  return (n_outer < 0 || n_lev < 0 || n_inner < 0) ? -1 : n_outer * n_lev * n_inner;
+}
+
+// The rows of (n_outer, n_lev, n_inner) -- record (o * n_lev + l) * n_inner + i of d_rows / d_bm -- over the x_bytes
+// bytes at x, all levels in one launch; the rank tables of all rows are built first, on the same stream.  A grid
+// beyond the limit is cut over the outer and the inner range (smm::split_batch, as run_apply); a single batch row whose
+// levels still do not fit is cut over the levels.
+static int launch_grib_group_rows(smm_group_t g, const int32_t* d_map, const uint8_t* d_masked, const void* x, int64_t x_bytes,
+                                  const smm_grib_row_t* d_rows, bool div, void* y, int64_t ys_o, int64_t ys_l, int64_t ys_i,
+                                  int64_t n_outer, int64_t n_lev, int64_t n_inner, double area_min, unsigned flags,
+                                  hipStream_t s, const GribRowBitmap* d_bm, char* d_rank, size_t n_tables) {
+  const int64_t S = g->ops[0]->csr.n_src;
+  GribGroupArgs a{};
+  a.descs = g->d_descs.get();
+  a.lev_masked = d_masked;
+  a.x = x_bytes > 0 ? (const uint32_t*)x : (const uint32_t*)d_rows;   // as launch_grib_rows
+  a.last_word = x_bytes > 0 ? smm_grib::align4((uint64_t)x_bytes) / 4 - 1 : 0;
+  a.n_dst = g->ops[0]->csr.n_dst;
+  a.n_dblocks = ((a.n_dst + 63) / 64 + kWavesPerBlock - 1) / kWavesPerBlock;
+  a.area_min = area_min;
+  a.masked = (flags & SMM_APPLY_MASKED) ? 1 : 0;
+  a.rec_o = n_lev * n_inner;
+  a.rec_l = n_inner;
+  a.ys_o = ys_o;
+  a.ys_l = ys_l;
+  a.ys_i = ys_i;
+  const bool fill = !(flags & SMM_APPLY_NO_FILL);
+  const bool with_tables = d_bm && n_tables > 0 && smm_grib::bitmap_blocks((uint64_t)S) > 0;
+  if (with_tables)
+    if (int rc = launch_grib_tables(a.x, a.last_word, d_bm, d_rank, n_tables, n_outer * n_lev * n_inner, S, s)) return rc;
+  const int64_t limit = grid_limit();
+  // the kernel's row indices inside a level are 32-bit: a part of 2^31 rows or more per level counts as too large
+  auto blocks_for = [&](int64_t n_o, int64_t n_i, int64_t n_l) -> int64_t {
+    const int64_t n_j = n_o * n_i;
+    if (n_j > 0x7fffffffLL) return limit + 1;
+    const int bt = smm_launch::sell_batch_rows(n_j);
+    return a.n_dblocks * ((n_j + bt - 1) / bt) * n_l;
+  };
+  auto launch_part = [&](int64_t o0, int64_t n_o, int64_t i0, int64_t n_i, int64_t l0, int64_t n_l) -> int {
+    GribGroupArgs p = a;
+    const int64_t first = (o0 * n_lev + l0) * n_inner + i0;
+    p.rows = d_rows + first;
+    p.lev_map = d_map + l0;
+    p.y = (double*)y + (o0 * ys_o + l0 * ys_l + i0 * ys_i);
+    p.n_j = n_o * n_i;
+    p.n_inner = n_i;
+    if (with_tables) {
+      p.bm = d_bm + first;
+      p.table = (const smm_grib::GribRankEntry*)d_rank;
+    }
+    return smm_launch::launch_grib_group(p, n_l, with_tables, div, fill, s);
+  };
+  // a part of several rows is cut further while it does not fit; a single row goes to the level split whatever it needs
+  const int rc = smm::split_batch(
+      0, n_outer, 0, n_inner, limit,
+      [&](int64_t n_o, int64_t n_i) -> int64_t { return n_o * n_i == 1 ? 0 : blocks_for(n_o, n_i, n_lev); },
+      [&](int64_t o0, int64_t n_o, int64_t i0, int64_t n_i) -> int {
+        return smm::split_batch(
+            0, n_lev, 0, 1, limit, [&](int64_t n_l, int64_t) { return blocks_for(n_o, n_i, n_l); },
+            [&](int64_t l0, int64_t n_l, int64_t, int64_t) { return launch_part(o0, n_o, i0, n_i, l0, n_l); });
+      });
+  if (rc == -1)
+    return fail(SMM_ERR_INVALID, "one batch row of one level alone needs a launch grid beyond " + std::to_string(limit) +
+                                     " workgroups (destination blocks)");
+  return rc;
+}
+
+static int smm_group_apply_grib_impl(smm_group_t g, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
+                                     const smm_grib_bitmap_t* bitmaps, void* y, int64_t ys_o, int64_t ys_l, int64_t ys_i,
+                                     int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index,
+                                     const uint8_t* masked_levels, double area_min, unsigned flags, void* stream) {
+  const int64_t n_rows = n_outer * n_lev * n_inner;
+  if (n_rows == 0 || g->ops[0]->csr.n_dst == 0) return SMM_OK;
+  DeviceGuard guard(g->device);
+  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the group's device");
+  const int32_t* d_map;
+  const uint8_t* d_masked;
+  if (int rc = group_level_cfg(g, n_lev, level_index, masked_levels, area_min, flags, &d_map, &d_masked)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lock(g->grib_mu);
+  size_t n_tables = 0;
+  if (int rc = upload_grib_tables(g, rows, bitmaps, n_rows, g->ops[0]->csr.n_src, s, &n_tables)) return rc;
+  return launch_grib_group_rows(g, d_map, d_masked, x, x_bytes, g->d_grib_rows.get(), grib_needs_division(rows, n_rows), y,
+                                ys_o, ys_l, ys_i, n_outer, n_lev, n_inner, area_min, flags, s,
+                                n_tables ? g->d_grib_bm.get() : nullptr, g->d_grib_rank.get(), n_tables);
+}
+
+// Host buffers: chunks of whole outer indices (smm::plan_grib_chunks_units) -- their n_lev * n_inner rows each are
+// consecutive records, staged as smm_apply_host_grib stages a chunk -- through the group's pipeline; Y is delivered as the
+// whole-row mode of smm_group_apply_host delivers it, (n_outer, n_inner, n_lev, D) when transpose, else
+// (n_lev, n_outer, n_inner, D).
+static int smm_group_apply_host_grib_impl(smm_group_t g, const void* x_host, const smm_grib_row_t* rows,
+                                          const smm_grib_bitmap_t* bitmaps, void* y_host, int64_t n_outer, int64_t n_lev,
+                                          int64_t n_inner, int transpose, const int32_t* level_index,
+                                          const uint8_t* masked_levels, double area_min, unsigned flags, int64_t chunk_outer) {
+  const int64_t S = g->ops[0]->csr.n_src, D = g->ops[0]->csr.n_dst;
+  const int64_t unit = n_lev * n_inner, n_rows = n_outer * unit;
+  if (n_rows == 0 || D == 0) return SMM_OK;
+  DeviceGuard guard(g->device);
+  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the group's device");
+  const int32_t* d_map;
+  const uint8_t* d_masked;
+  if (int rc = group_level_cfg(g, n_lev, level_index, masked_levels, area_min, flags, &d_map, &d_masked)) return rc;
+  const smm::GribChunkPlan plan =
+      smm::plan_grib_chunks_units(rows, bitmaps, n_outer, unit, S, D, chunk_outer, free_device_bytes());
+  const bool div = grib_needs_division(rows, n_rows);
+  const bool y_direct = is_pinned(y_host);
+
+  std::lock_guard<std::mutex> pipe_lock(g->pipe_mu);
+  HostPipe& pipe = g->pipe;
+  const size_t y_chunk = (size_t)plan.max_rows * D * 8;
+  SMM_HIP(pipe.ensure(plan.max_x, y_chunk, plan.max_x, y_direct ? 0 : y_chunk));
+  if (plan.max_rank > std::min(g->d_pipe_rank[0].bytes(), g->d_pipe_rank[1].bytes()))   // device-only, one per slot
+    for (int i = 0; i < 2; ++i) SMM_HIP(g->d_pipe_rank[i].alloc(plan.max_rank));
+
+  CallStats st;
+  // Y of a chunk of `no` outer indices from o0: on the device (no, n_inner, n_lev, D) when transpose -- one block of
+  // the host array -- else (n_lev, no, n_inner, D): one run per level
+  auto y_to_host = [&](int64_t o0, int64_t no, const char* src, bool async, hipStream_t stream) -> int {
+    const size_t blk = (size_t)no * n_inner * D * 8;
+    const int64_t runs = transpose ? 1 : n_lev;
+    for (int64_t r = 0; r < runs; ++r) {
+      const size_t bytes = transpose ? blk * (size_t)n_lev : blk;
+      char* dst = (char*)y_host + (transpose ? (size_t)o0 * unit : (size_t)r * n_outer * n_inner + (size_t)o0 * n_inner) * D * 8;
+      if (async) {
+        SMM_HIP(hipMemcpyAsync(dst, src + (size_t)r * blk, bytes, hipMemcpyDeviceToHost, stream));
+      } else if (int rc = host_copy(dst, src + (size_t)r * blk, bytes)) {
+        return rc;
+      }
+    }
+    return SMM_OK;
+  };
+  auto deliver = [&](int64_t c, int b) -> int {
+    if (y_direct) return SMM_OK;
+    StageTimer t(st.v[SMM_HOST_STAT_COPY_OUT_MS]);
+    const smm::GribChunk& ch = plan.chunks[(size_t)c];
+    return y_to_host(ch.r0 / unit, ch.nr / unit, (const char*)pipe.hy[b].get(), false, nullptr);
+  };
+  auto launch = [&](int64_t c, int b) -> int {
+    const smm::GribChunk& ch = plan.chunks[(size_t)c];
+    const int64_t o0 = ch.r0 / unit, no = ch.nr / unit;
+    char* hx = (char*)pipe.hx[b].get();
+    size_t n_tables = 0;
+    {
+      StageTimer t(st.v[SMM_HOST_STAT_STAGE_IN_MS]);
+      if (int rc = stage_grib_chunk(hx, ch, x_host, rows, bitmaps, S, &n_tables)) return rc;
+    }
+    SMM_HIP(pipe.mark(b, 0));
+    SMM_HIP(hipMemcpyAsync(pipe.dx[b].get(), hx, ch.x_bytes, hipMemcpyHostToDevice, pipe.stream[b]));
+    st.v[SMM_HOST_STAT_H2D_BYTES] += (double)ch.x_bytes;
+    SMM_HIP(pipe.mark(b, 1));
+    int64_t ys_o, ys_l, ys_i;   // the chunk's Y on the device, as smm_group_apply_host lays out a whole-row chunk
+    if (transpose) {
+      ys_o = n_inner * n_lev * D, ys_l = D, ys_i = n_lev * D;
+    } else {
+      ys_o = n_inner * D, ys_l = no * n_inner * D, ys_i = D;
+    }
+    if (int rc = launch_grib_group_rows(
+            g, d_map, d_masked, pipe.dx[b].get(), (int64_t)ch.x_bytes, (const smm_grib_row_t*)pipe.dx[b].get(), div,
+            pipe.dy[b].get(), ys_o, ys_l, ys_i, no, n_lev, n_inner, area_min, flags, pipe.stream[b],
+            n_tables ? (const GribRowBitmap*)(pipe.dx[b].get() + (size_t)ch.nr * sizeof(smm_grib_row_t)) : nullptr,
+            g->d_pipe_rank[b].get(), n_tables))
+      return rc;
+    st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)ch.nr * D * 8);
+    SMM_HIP(pipe.mark(b, 2));
+    if (!y_direct) {
+      SMM_HIP(hipMemcpyAsync(pipe.hy[b].get(), pipe.dy[b].get(), (size_t)ch.nr * D * 8, hipMemcpyDeviceToHost, pipe.stream[b]));
+    } else if (int rc = y_to_host(o0, no, (const char*)pipe.dy[b].get(), true, pipe.stream[b])) {
+      return rc;
+    }
+    SMM_HIP(pipe.mark(b, 3));
+    return SMM_OK;
+  };
+  return run_host_pipeline(pipe, (int64_t)plan.chunks.size(), st, launch, deliver);
+}
+
 }  // extern "C"
 
 // ---- the guarded entry points: whatever an implementation above throws (std::bad_alloc from a plan vector, a
@@ -2258,6 +2488,34 @@ int smm_apply_host_grib_bm(smm_operator_t op, const void* x_host, int64_t x_byte
     if (int rc = check_grib_call(x_host, false, x_bytes, rows, y_host, y_dtype, n_batch, remap_area_min, flags)) return rc;
     if (int rc = check_grib_operator(op, x_bytes, rows, bitmaps, ldy, n_batch, remap_area_min, flags)) return rc;
     return smm_apply_host_grib_impl(op, x_host, rows, bitmaps, y_host, ldy, n_batch, remap_area_min, flags, chunk_rows);
+  });
+}
+
+int smm_group_apply_grib(smm_group_t g, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
+                         const smm_grib_bitmap_t* bitmaps, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev,
+                         int64_t ys_inner, int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index,
+                         const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream) {
+  return guarded([&] {
+    const int64_t n_rows = grib_group_rows(n_outer, n_lev, n_inner);
+    if (int rc = check_grib_call(x, true, x_bytes, rows, y, y_dtype, n_rows, remap_area_min, flags)) return rc;
+    if (int rc = check_grib_group(g, x_bytes, rows, bitmaps, n_rows, n_lev, level_index, masked_levels, remap_area_min, flags))
+      return rc;
+    return smm_group_apply_grib_impl(g, x, x_bytes, rows, bitmaps, y, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner,
+                                     level_index, masked_levels, remap_area_min, flags, stream);
+  });
+}
+
+int smm_group_apply_host_grib(smm_group_t g, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                              const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t n_outer,
+                              int64_t n_lev, int64_t n_inner, int transpose, const int32_t* level_index,
+                              const uint8_t* masked_levels, double remap_area_min, unsigned flags, int64_t chunk_outer) {
+  return guarded([&] {
+    const int64_t n_rows = grib_group_rows(n_outer, n_lev, n_inner);
+    if (int rc = check_grib_call(x_host, false, x_bytes, rows, y_host, y_dtype, n_rows, remap_area_min, flags)) return rc;
+    if (int rc = check_grib_group(g, x_bytes, rows, bitmaps, n_rows, n_lev, level_index, masked_levels, remap_area_min, flags))
+      return rc;
+    return smm_group_apply_host_grib_impl(g, x_host, rows, bitmaps, y_host, n_outer, n_lev, n_inner, transpose, level_index,
+                                          masked_levels, remap_area_min, flags, chunk_outer);
   });
 }
 

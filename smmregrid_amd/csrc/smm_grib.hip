@@ -20,24 +20,53 @@ namespace {
 // BM (smm_apply_grib_bm): a row with a bitmap loads, per link, the 8-byte rank-table entry of the cell's 32-cell block
 // and reads the stream at the cell's rank; its table pointer -- null for a row without a bitmap, which takes
 // rank = c, present = true -- is scalar like the rest of the rule, so the branch on it is block-uniform.
-template <int BT, bool DIV, bool BM>
-__global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(std::conditional_t<BM, GribBitmapArgs, GribArgs> a,
-                                                                   bool fill) {
+// GRP (smm_group_apply_grib): the block id splits into (destination block, batch tile, level) as in
+// smm_apply_sell_kernel; the level's descriptor comes from descs[lev_map[l]], its mask switch from lev_masked, and the
+// BT batch rows are rows (o, i) of that one level: row j of the level is record o * rec_o + l * rec_l + i of the row
+// table and the bitmap records -- a block-uniform index like j itself, so the rule stays in scalar registers -- and its
+// results go to y + o * ys_o + l * ys_l + i * ys_i.
+template <bool GRP, bool BM>
+using GribKernelArgs = std::conditional_t<GRP, GribGroupArgs, std::conditional_t<BM, GribBitmapArgs, GribArgs>>;
+
+template <int BT, bool DIV, bool BM, bool GRP = false>
+__global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(GribKernelArgs<GRP, BM> a, bool fill) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int64_t bid = blockIdx.x;
-  const int64_t db = bid % a.n_dblocks;
-  const int64_t jt = bid / a.n_dblocks;
-  const LevelDesc L = a.descs[0];
+  int64_t db = bid % a.n_dblocks;
+  int64_t jt = bid / a.n_dblocks;
+  int64_t l = 0;
+  int di = 0;
+  if constexpr (GRP) {
+    // the grid has fewer than 2^31 blocks, so its three factors fit 32 bits: plain 32-bit scalar divisions
+    const uint32_t nd = (uint32_t)a.n_dblocks, nt = (uint32_t)a.n_jtiles;
+    const uint32_t q = blockIdx.x / nd, lev = q / nt;
+    db = blockIdx.x - q * nd;
+    jt = q - lev * nt;
+    l = lev;
+    di = a.lev_map[l];
+  }
+  const LevelDesc L = a.descs[di];
 
   const int64_t slice = db * kWavesPerBlock + wave;
   const int64_t d = slice * 64 + lane;
   if (slice * 64 >= a.n_dst) return;
 
   const int64_t j0 = jt * BT;
+  // GRP: (o, i) of the block's first batch row -- one division per block; a launch holds fewer than 2^31 rows per
+  // level (launch_grib_group), so 32 bits do.  The rows are walked from it twice, for the rules here and for the Y
+  // rows in the epilogue: BT result pointers would sit in scalar registers through the whole link loop.
+  uint32_t go0 = 0, gi0 = 0;
+  bool use_mask = a.masked != 0;
+  if constexpr (GRP) {
+    go0 = (uint32_t)j0 / (uint32_t)a.n_inner;
+    gi0 = (uint32_t)j0 - go0 * (uint32_t)a.n_inner;
+    use_mask = use_mask && (a.lev_masked ? a.lev_masked[di] != 0 : true);
+  }
+  uint32_t go = go0, gi = gi0;
   const smm_grib_row_t* __restrict__ rows = a.rows;
   const uint32_t* __restrict__ xw[BT];
-  double* __restrict__ yr[BT];
+  double* __restrict__ yr[GRP ? 1 : BT];
   uint32_t bit0[BT], lastw[BT];
   int nbits[BT];
   double ref[BT], bscale[BT], ddiv[BT];
@@ -46,10 +75,15 @@ __global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(std::condition
   for (int t = 0; t < BT; ++t) {
     int64_t j = j0 + t;
     if (j > a.n_j - 1) j = a.n_j - 1;
-    const smm_grib_row_t r = rows[j];
+    int64_t rec = j;
+    if constexpr (GRP) {
+      rec = (int64_t)go * a.rec_o + l * a.rec_l + gi;
+      if (j0 + t < a.n_j - 1 && ++gi == (uint32_t)a.n_inner) gi = 0, ++go;   // the next row; past the last: repeated
+    }
+    const smm_grib_row_t r = rows[rec];
     if constexpr (BM) {
       const GribRowBitmap* __restrict__ bm = a.bm;
-      const GribRowBitmap m = bm[j];
+      const GribRowBitmap m = bm[rec];
       tab[t] = m.bitmap_off == SMM_GRIB_NO_BITMAP ? nullptr : a.table + m.table_off;
     }
     // a 0-bit row may start at the very end of the buffer: its words are clamped like every other load
@@ -61,7 +95,7 @@ __global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(std::condition
     ref[t] = r.ref;
     bscale[t] = r.bscale;
     ddiv[t] = r.ddiv;
-    yr[t] = a.y + j * a.ldy;
+    if constexpr (!GRP) yr[t] = a.y + j * a.ldy;
   }
 
   const int64_t off = L.slice_off[slice];
@@ -104,11 +138,23 @@ __global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(std::condition
 
   if (d < a.n_dst) {
     bool dead = false;
-    if (a.masked && L.imask) dead = (L.imask[d] == 0);
+    if (use_mask && L.imask) dead = (L.imask[d] == 0);
     if (a.area_min > 0.0 && L.frac) dead = dead || (L.frac[d] < a.area_min);
+    if constexpr (GRP) {
+      go = go0, gi = gi0;
 #pragma unroll
-    for (int t = 0; t < BT; ++t) {
-      if (j0 + t < a.n_j) yr[t][d] = epilogue(acc[t].num, dead);
+      for (int t = 0; t < BT; ++t) {
+        if (j0 + t < a.n_j) {
+          double* __restrict__ yrow = a.y + ((int64_t)go * a.ys_o + l * a.ys_l + (int64_t)gi * a.ys_i);
+          yrow[d] = epilogue(acc[t].num, dead);
+          if (++gi == (uint32_t)a.n_inner) gi = 0, ++go;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < BT; ++t) {
+        if (j0 + t < a.n_j) yr[t][d] = epilogue(acc[t].num, dead);
+      }
     }
   }
 }
@@ -212,17 +258,18 @@ __global__ __launch_bounds__(kBuildThreads) void smm_grib_bitmap_scan_kernel(Gri
 namespace smm_launch {
 
 namespace {
-template <bool BM, class Args>
-int launch_grib_any(const Args& a, bool div, bool fill, hipStream_t s) {
+// n_lev: the levels of a grouped launch (GribGroupArgs), 1 for the operator entries
+template <bool BM, bool GRP, class Args>
+int launch_grib_any(const Args& a, int64_t n_lev, bool div, bool fill, hipStream_t s) {
   Args args = a;
   auto go = [&](auto bt_tag, auto div_tag) -> int {
     constexpr int BT = decltype(bt_tag)::value;
     args.n_jtiles = (a.n_j + BT - 1) / BT;
-    const int64_t total = args.n_dblocks * args.n_jtiles;
+    const int64_t total = args.n_dblocks * args.n_jtiles * n_lev;
     if (total <= 0) return SMM_OK;
     if (total > 0x7fffffffLL) return smm::fail_msg(SMM_ERR_INVALID, "launch grid exceeds 2^31-1 blocks");
-    hipLaunchKernelGGL((smm_apply_grib_kernel<BT, decltype(div_tag)::value, BM>), dim3((unsigned)total), dim3(kThreads), 0,
-                       s, args, fill);
+    hipLaunchKernelGGL((smm_apply_grib_kernel<BT, decltype(div_tag)::value, BM, GRP>), dim3((unsigned)total),
+                       dim3(kThreads), 0, s, args, fill);
     SMM_LAUNCH_HIP(hipGetLastError());
     return SMM_OK;
   };
@@ -238,9 +285,14 @@ int launch_grib_any(const Args& a, bool div, bool fill, hipStream_t s) {
 }
 }  // namespace
 
-int launch_grib(const GribArgs& a, bool div, bool fill, hipStream_t s) { return launch_grib_any<false>(a, div, fill, s); }
+int launch_grib(const GribArgs& a, bool div, bool fill, hipStream_t s) {
+  return launch_grib_any<false, false>(a, 1, div, fill, s);
+}
 int launch_grib_bitmap(const GribBitmapArgs& a, bool div, bool fill, hipStream_t s) {
-  return launch_grib_any<true>(a, div, fill, s);
+  return launch_grib_any<true, false>(a, 1, div, fill, s);
+}
+int launch_grib_group(const GribGroupArgs& a, int64_t n_lev, bool bitmaps, bool div, bool fill, hipStream_t s) {
+  return bitmaps ? launch_grib_any<true, true>(a, n_lev, div, fill, s) : launch_grib_any<false, true>(a, n_lev, div, fill, s);
 }
 
 int launch_grib_build(const GribBuildArgs& a, hipStream_t s) {

@@ -33,6 +33,18 @@ struct GribBitmapArgs : GribArgs {
   const GribRowBitmap* bm;                 // device [n_j], parallel to rows
   const smm_grib::GribRankEntry* table;    // device: the rank tables of the call's bitmapped rows
 };
+// smm_group_apply_grib: one launch over the data levels of a group.  descs holds the group's members, lev_map[l] names
+// the member of the launch's level l and lev_masked[member] its mask switch (null: every member masks) -- the group's
+// cfg_cache upload.  n_j = n_o * n_inner batch rows PER LEVEL; row (o, l, i) of the launch is record
+// o * rec_o + l * rec_l + i of rows / bm (the launch's first record at rows[0]: a part of a call advances the pointers)
+// and writes y + o * ys_o + l * ys_l + i * ys_i, all in 64-bit arithmetic.  ldy is unused; bm / table are null when no
+// row of the call has a bitmap (the BM = false instantiations).
+struct GribGroupArgs : GribBitmapArgs {
+  const int32_t* lev_map;
+  const uint8_t* lev_masked;
+  int64_t n_inner, rec_o, rec_l;
+  int64_t ys_o, ys_l, ys_i;
+};
 // the table build: n_j rows of n_src cells over the words of x.  Every table has n_blocks entries, so table_off / n_blocks
 // numbers the tables: totals[(that number) * n_segs + s] = set bits of segment s
 struct GribBuildArgs {
@@ -50,6 +62,8 @@ namespace smm_launch {
 int launch_grib(const GribArgs& a, bool div, bool fill, hipStream_t s);
 // the gather that consults the rank tables (rows without a bitmap take rank = c on a block-uniform branch) ...
 int launch_grib_bitmap(const GribBitmapArgs& a, bool div, bool fill, hipStream_t s);
-// ... and the two kernels that fill them, in stream order ahead of it: segment totals, then the scan
+// the grouped gather over n_lev levels (grid = destination blocks x batch tiles x levels); bitmaps: a.bm / a.table are set
+int launch_grib_group(const GribGroupArgs& a, int64_t n_lev, bool bitmaps, bool div, bool fill, hipStream_t s);
+// ... and the two kernels that fill the rank tables, in stream order ahead of it: segment totals, then the scan
 int launch_grib_build(const GribBuildArgs& a, hipStream_t s);
 }

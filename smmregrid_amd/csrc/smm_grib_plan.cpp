@@ -1,6 +1,7 @@
 // Host side of the GRIB entries that needs no device: the refusals of a row table and the chunk plan of
-// smm_apply_host_grib, and the same with bitmaps for the _bm entries (declared in smm_internal.h).  Plain C++:
-// tests/cpp/grib_harness.cpp and tests/cpp/grib_bitmap_harness.cpp link this file.
+// smm_apply_host_grib, the same with bitmaps for the _bm entries, and the unit plan of smm_group_apply_host_grib
+// (declared in smm_internal.h).  Plain C++: tests/cpp/grib_harness.cpp, grib_bitmap_harness.cpp and
+// grib_levels_harness.cpp link this file.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -130,6 +131,58 @@ GribChunkPlan plan_grib_chunks_bm(const smm_grib_row_t* rows, const smm_grib_bit
       c.rank_bytes += r;
       ++c.nr;
       ++b;
+    }
+    plan.max_x = std::max(plan.max_x, c.x_bytes);
+    plan.max_rank = std::max(plan.max_rank, c.rank_bytes);
+    plan.max_rows = std::max(plan.max_rows, c.nr);
+    plan.chunks.push_back(c);
+  }
+  return plan;
+}
+
+GribChunkPlan plan_grib_chunks_units(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_outer,
+                                     int64_t unit, int64_t n_src, int64_t D, int64_t requested_units, size_t free_bytes) {
+  constexpr size_t kTarget = (size_t)256 << 20, kMinChunk = (size_t)32 << 20;   // plan_grib_chunks' bounds
+  constexpr int64_t kMinChunks = 8;
+  GribChunkPlan plan;
+  if (n_outer <= 0 || unit <= 0) return plan;
+  const size_t y_row = (size_t)std::max<int64_t>(D, 0) * 8;
+  // staged and rank bytes of outer index o: its `unit` consecutive records
+  auto unit_cost = [&](int64_t o, size_t& x, size_t& r) {
+    x = r = 0;
+    for (int64_t b = o * unit; b < (o + 1) * unit; ++b) {
+      if (bitmaps) {
+        x += grib_bm_row_staged(rows[b], bitmaps[b], n_src);
+        r += grib_bm_row_rank(bitmaps[b], n_src);
+      } else {
+        x += sizeof(smm_grib_row_t) + (size_t)smm_grib::align4(smm_grib::row_bytes((uint64_t)n_src, rows[b].nbits));
+      }
+    }
+  };
+  if (requested_units <= 0) {
+    size_t total = 0, x = 0, r = 0;
+    for (int64_t o = 0; o < n_outer; ++o) {
+      unit_cost(o, x, r);
+      total += x + r + (size_t)unit * y_row;
+    }
+    plan.target = std::min(kTarget, std::max(kMinChunk, total / (size_t)kMinChunks));
+    if (free_bytes > 0) plan.target = std::min(plan.target, std::max<size_t>(free_bytes / 8, 1));
+  }
+  for (int64_t o = 0; o < n_outer;) {
+    GribChunk c{o * unit, 0, 0};
+    size_t bytes = 0;
+    int64_t units = 0;
+    while (o < n_outer) {
+      size_t x = 0, r = 0;
+      unit_cost(o, x, r);
+      const size_t all = x + r + (size_t)unit * y_row;
+      if (requested_units > 0 ? units >= requested_units : (units > 0 && bytes + all > plan.target)) break;
+      bytes += all;
+      c.x_bytes += x;
+      c.rank_bytes += r;
+      c.nr += unit;
+      ++units;
+      ++o;
     }
     plan.max_x = std::max(plan.max_x, c.x_bytes);
     plan.max_rank = std::max(plan.max_rank, c.rank_bytes);

@@ -230,4 +230,13 @@ size_t grib_bm_row_rank(const smm_grib_bitmap_t& bm, int64_t n_src);
 GribChunkPlan plan_grib_chunks_bm(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_batch,
                                   int64_t n_src, int64_t D, int64_t requested_rows, size_t free_bytes);
 
+// ---- smm_group_apply_host_grib: chunks of whole outer indices.  The n_outer * unit records (unit = n_lev * n_inner rows
+// per outer index, consecutive in the table) are chunked in units: r0 and nr of every chunk are multiples of `unit`.
+// bitmaps may be null (no row has one: 40 B of table and align4(ceil(n_src * nbits / 8)) data bytes per row); else the
+// costs of plan_grib_chunks_bm.  Y costs rows * D * 8; the byte bound and the free-memory clamp are plan_grib_chunks_bm's.
+// A chunk holds at least one unit even when that unit alone exceeds the bound; requested_units > 0 fixes the units per
+// chunk (the last may be short).  n_outer <= 0 or unit <= 0: no chunks.
+GribChunkPlan plan_grib_chunks_units(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_outer,
+                                     int64_t unit, int64_t n_src, int64_t D, int64_t requested_units, size_t free_bytes);
+
 }  // namespace smm

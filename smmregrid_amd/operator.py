@@ -553,6 +553,86 @@ class OperatorGroup:
                            (n_outer, n_lev, n_inner, int(bool(transpose)), _cptr(lev), _cptr(ml), float(remap_area_min),
                             fl, int(chunk_outer)), y_res, cf, cf_out, "out")
 
+    def _grib_args(self, rows, bitmaps, level_index, masked_levels, n_inner):
+        """rows / bitmaps flat -- then n_lev is len(level_index) and n_inner the keyword -- or shaped
+        (n_outer, n_lev, n_inner).  Returns (n_outer, n_lev, n_inner), the two record arrays with their pointers and
+        the level arguments."""
+        from .griblite import GRIB_ROW_DTYPE
+        shaped = np.asarray(rows, dtype=GRIB_ROW_DTYPE)
+        if shaped.ndim == 3:
+            dims = shaped.shape
+        elif shaped.ndim == 1:
+            n_lev, n_inner = np.asarray(level_index).size, int(n_inner)
+            if n_lev <= 0 or n_inner <= 0 or shaped.size % (n_lev * n_inner):
+                raise ValueError(f"{shaped.size} rows are no whole number of (n_lev = {n_lev}) x (n_inner = {n_inner}) blocks")
+            dims = (shaped.size // (n_lev * n_inner), n_lev, n_inner)
+        else:
+            raise ValueError(f"rows must be flat or (n_outer, n_lev, n_inner), got {shaped.shape}")
+        lev, ml = self._level_args(level_index, masked_levels, dims[1])
+        rows, rows_p = self.operators[0]._grib_rows(shaped)
+        bm, bm_p = None, None
+        if bitmaps is not None:
+            if np.ndim(bitmaps) not in (1, 3) or (np.ndim(bitmaps) == 3 and np.shape(bitmaps) != dims):
+                raise ValueError(f"bitmaps must be flat or {dims}, got {np.shape(bitmaps)}")
+            bm, bm_p = self.operators[0]._grib_bitmaps(bitmaps, rows.size)
+        return dims, (rows, rows_p), (bm, bm_p), (lev, ml)
+
+    def apply_grib(self, x, rows, level_index, masked_levels=None, bitmaps=None, y=None, x_bytes=None, masked=False,
+                   remap_area_min=0.0, transpose=True, flags=0, stream=None, n_inner=1):
+        """`apply` for GRIB simple-packed fields resident in HBM as they are on disk (smm_group_apply_grib): x and the
+        `GRIB_ROW_DTYPE` / `GRIB_BITMAP_DTYPE` records as for `SparseOperator.apply_grib`, one record per batch row
+        (o, l, i) in C order -- rows shaped (n_outer, n_lev, n_inner), or flat with n_lev = len(level_index) and
+        `n_inner`.  All levels run in one launch of the grouped GRIB gather.  Returns the float64 DeviceArray `apply`
+        returns, (n_outer, n_inner, n_lev, D) when transpose else (n_lev, n_outer, n_inner, D), bit-identical to
+        `apply` on the float32 field a host decode gives (NaN where a bitmap bit is 0)."""
+        (n_outer, n_lev, n_in), (rows, rows_p), (bm, bm_p), (lev, ml) = self._grib_args(rows, bitmaps, level_index,
+                                                                                         masked_levels, n_inner)
+        if isinstance(x, DeviceArray):
+            if x.dtype != np.uint8:
+                raise TypeError(f"apply_grib takes the packed bytes as uint8, got {x.dtype}")
+            x_ptr, n_bytes = ctypes.c_void_p(x.ptr), x.nbytes if x_bytes is None else int(x_bytes)
+            if (n_bytes + 3) // 4 * 4 > x.nbytes:      # the kernel reads whole 32-bit words
+                raise ValueError(f"x must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {x.nbytes}")
+        else:
+            if x_bytes is None:
+                raise TypeError("a raw device pointer needs x_bytes")
+            x_ptr, n_bytes = ctypes.c_void_p(int(x)), int(x_bytes)
+        D = self.n_dst
+        if transpose:
+            shape, ys = (n_outer, n_in, n_lev, D), (n_in * n_lev * D, D, n_lev * D)     # (outer, lev, inner) strides
+        else:
+            shape, ys = (n_lev, n_outer, n_in, D), (n_in * D, n_outer * n_in * D, D)
+        if y is None:
+            y = DeviceArray(shape, np.float64)
+        elif y.shape != shape or y.dtype != np.float64:
+            raise ValueError(f"Y must be a float64 {shape} DeviceArray")
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        _lib.call("smm_group_apply_grib", self.handle, x_ptr, n_bytes, rows_p, bm_p, _ptr(y), _lib.SMM_F64, *ys, n_outer,
+                  n_lev, n_in, _cptr(lev), _cptr(ml), float(remap_area_min), fl, _stream_handle(stream))
+        return y
+
+    def apply_host_grib(self, buf, rows, level_index, masked_levels=None, bitmaps=None, out=None, masked=False,
+                        remap_area_min=0.0, transpose=True, flags=0, chunk_outer=0, n_inner=1):
+        """The host twin (smm_group_apply_host_grib): buf is a host uint8 array -- typically a whole GRIB file -- rows
+        and bitmaps as for `apply_grib`.  Blocks of the outer axis stream through the group's pipeline; each row's
+        packed bytes (a bitmapped row's: its present cells only, and its bitmap) cross PCIe as they are and no host
+        decode runs.  Returns the float64 array `apply_host` returns on the decoded float32 field, bit for bit."""
+        (n_outer, n_lev, n_in), (rows, rows_p), (bm, bm_p), (lev, ml) = self._grib_args(rows, bitmaps, level_index,
+                                                                                         masked_levels, n_inner)
+        buf = np.ascontiguousarray(buf)
+        if buf.dtype != np.uint8 or buf.ndim != 1:
+            raise TypeError("apply_host_grib takes the packed bytes as a 1-d uint8 array")
+        shape = (n_outer, n_in, n_lev, self.n_dst) if transpose else (n_lev, n_outer, n_in, self.n_dst)
+        if out is None:
+            out = result_cache.empty(shape, np.float64)
+        if out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous float64 {shape} array")
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        _lib.call("smm_group_apply_host_grib", self.handle, _cptr(buf), buf.size, rows_p, bm_p, _cptr(out), _lib.SMM_F64,
+                  n_outer, n_lev, n_in, int(bool(transpose)), _cptr(lev), _cptr(ml), float(remap_area_min), fl,
+                  int(chunk_outer))
+        return out
+
     def close(self):
         if getattr(self, "handle", None):
             _lib.call("smm_group_destroy", self.handle)

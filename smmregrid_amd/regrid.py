@@ -90,8 +90,8 @@ class Regridder(object):
         # 2-byte elements, decoded inside the kernels (CFDecode) -- with the bits of a host decode
         self.packed = bool(packed)
         # packed_levels (with packed=True): packed variables on masked-level (3-D) weights are regridded raw too,
-        # through the level-group entries (smm_group_apply*_cf).  Off by default: such a variable is decoded on
-        # the host first, as before
+        # through the level-group entries (smm_group_apply*_cf; a raw GRIB variable: smm_group_apply_host_grib).  Off by
+        # default: such a variable is decoded on the host first, as before
         self.packed_levels = bool(packed_levels)
         if self.packed_levels and not self.packed:
             raise ValueError('packed_levels=True needs packed=True')
@@ -353,21 +353,34 @@ class Regridder(object):
 
     def _grib_or_decoded(self, source_data, datagridtype):
         """A GRIB variable kept raw (`GribField`): with packed=True on 2-D weights and a float64 result it stays as it
-        is and apply_weights ships its bit streams (smm_apply_host_grib, with bitmaps smm_apply_host_grib_bm); everything else decodes it on the host --
-        what np.asarray would do anyway -- and goes on as before."""
+        is and apply_weights ships its bit streams (smm_apply_host_grib, with bitmaps smm_apply_host_grib_bm); so it
+        does on masked-level weights with packed_levels=True (regrid3d: smm_group_apply_host_grib) when its dims are
+        (outer..., level, inner..., horizontal...).  Everything else decodes it on the host -- what np.asarray would do
+        anyway -- and goes on as before."""
         why = None
         if self.packed:
-            if datagridtype.mask_dim:
+            if datagridtype.mask_dim and not self.packed_levels:
                 why = "masked levels"
             elif self.skipna:
                 why = "skipna"
             elif self._result_dtype(source_data) != np.dtype(np.float64):
                 why = f"out_dtype {self._result_dtype(source_data)}"
+            elif datagridtype.mask_dim and not self._grib_rows_by_level(source_data.dims, datagridtype):
+                why = "masked levels: its fields are not ordered (outer..., level, inner...)"
             if why is None:
                 return source_data
             self.loggy.info("packed variable %s is decoded on the host (%s)", source_data.name, why)
         return DataArray(source_data.data.decode(), dims=source_data.dims, coords=source_data.coords,
                          attrs=source_data.attrs, name=source_data.name)
+
+    @staticmethod
+    def _grib_rows_by_level(dims, datagridtype):
+        """Whether the fields of a GribField with these dims -- one per index of its leading dims, in C order -- are the
+        (outer..., level, inner...) batch rows of the group entry: the mask dimension among the leading dims, the
+        horizontal ones trailing."""
+        horizontal = [d for d in dims if d in (datagridtype.horizontal_dims or [])]
+        lead = list(dims[:len(dims) - len(horizontal)])
+        return bool(horizontal) and datagridtype.mask_dim in lead and not any(d in horizontal for d in lead)
 
     def _packed_out_rule(self, source_data):
         """The CFEncode of a packed variable's own attributes, or None (one WARNING) when they name no fill value."""
@@ -629,6 +642,10 @@ class Regridder(object):
         if out_dtype is None:
             out_dtype = self._result_dtype(source_data)
         skipna = self.skipna
+        if isinstance(src, GribField) and not (self.packed and self.packed_levels and not skipna
+                                               and np.dtype(out_dtype) == np.dtype(np.float64)
+                                               and self._grib_rows_by_level(source_data.dims, gridtype)):
+            src = src.decode()      # a direct call: only the raw road of _grib_or_decoded ships the bit streams
         ship_half = self._ships_half(getattr(src, "dtype", None))
         sb_in = isinstance(src, DeviceArray) and src.layout == "sb"
         if sb_in:
@@ -646,6 +663,18 @@ class Regridder(object):
             out_shape = [n_lev] + tgt_shape + rest_shape
 
         def compute():
+            if isinstance(src, GribField):
+                # GRIB simple packing regridded raw (packed=True, packed_levels=True): the file's bytes, one rule per
+                # field and the fields' bitmaps go to the GPU, all levels of a block of the outer axis in one launch
+                if src.n_points != S:
+                    raise ValueError(f"source grid has {src.n_points} cells, weights expect {S}")
+                if src.rows.size != n_outer * n_lev * n_inner:
+                    raise ValueError(f"{src.rows.size} GRIB fields for batch rows of shape {(n_outer, n_lev, n_inner)}")
+                dims3 = (n_outer, n_lev, n_inner)
+                out = group.apply_host_grib(src.buf, src.rows.reshape(dims3), level_index, masked_levels,
+                                            bitmaps=None if src.bitmaps is None else src.bitmaps.reshape(dims3),
+                                            masked=any_masked, remap_area_min=area_min, transpose=transpose)
+                return out.reshape(out_shape)
             if sb_in:
                 x = src.reshape(n_lev, -1, n_outer * n_inner)
                 if x.shape[1] != S:
