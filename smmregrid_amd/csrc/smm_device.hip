@@ -36,23 +36,13 @@
 #include "../../include/smmregrid_amd.h"
 #include "smm_internal.h"
 #include "smm_built.hpp"
-#include "smm_devmem.hpp"
-#include "smm_grib.hpp"
-#include "smm_grib_codec.hpp"
+#include "smm_device.hpp"
 
 #pragma clang fp contract(off)
-
-using smm::DeviceBuf;   // every HBM / page-locked block the library owns (smm_devmem.hpp)
-using smm::PinnedBuf;
 
 namespace {
 
 thread_local std::string g_last_error;
-
-int fail(int code, const std::string& msg) {
-  g_last_error = msg;
-  return code;
-}
 
 constexpr bool is_float_dtype(int d) { return d == SMM_F32 || d == SMM_F64; }
 constexpr bool is_packed_dtype(int d) { return d == SMM_I16 || d == SMM_U16; }
@@ -119,11 +109,6 @@ inline int check_x_dtype(const CallDesc& c) {
   const Refusal r = x_dtype_refusal(c.x_dtype, c.y_dtype, c.has_cf, c.has_enc);
   return r.code ? fail(r.code, r.msg) : SMM_OK;
 }
-inline int check_area_min(double area_min) {
-  if (!(area_min >= 0.0 && area_min <= 1.0))
-    return fail(SMM_ERR_INVALID, "remap_area_min must be within [0, 1]");  // regrid.py:124-125
-  return SMM_OK;
-}
 // A call that carries the rules its dtypes need (a packed X its decode rule, a packed Y its encode rule) is accepted
 // exactly when its combination is built.
 constexpr bool refusals_match_built() {
@@ -141,166 +126,32 @@ static_assert(refusals_match_built(), "check_x_dtype and SMM_BUILT (smm_built.hp
 namespace {
 // smm_debug_set_tuning: process-wide knobs of tests / tools / benchmarks, 0 = the library's own choice
 std::atomic<int> g_tuning[SMM_TUNE_COUNT];
-}  // namespace
-
-namespace smm {
-int fail_msg(int code, const std::string& msg) { return fail(code, msg); }  // for smm_comm.cpp
-int tuning(int knob) { return (knob >= 0 && knob < SMM_TUNE_COUNT) ? g_tuning[knob].load(std::memory_order_relaxed) : 0; }
-}
-
-namespace {
-
-#define SMM_HIP(call)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (call);                                                             \
-    if (e_ != hipSuccess) {                                                             \
-      (void)hipGetLastError();                                                          \
-      return fail(e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice                 \
-                      ? SMM_ERR_NO_DEVICE                                               \
-                      : SMM_ERR_HIP,                                                    \
-                  std::string(#call) + ": " + hipGetErrorString(e_));                   \
-    }                                                                                   \
-  } while (0)
-
-// Staging resources of the host-buffer pipeline, cached per operator (allocation costs
-// milliseconds, a small regrid microseconds): two streams, two device X/Y chunk buffers,
-// two pinned X/Y staging buffers, grown on demand.
-struct HostPipe {
-  hipStream_t stream[2] = {nullptr, nullptr};
-  DeviceBuf<char> dx[2], dy[2];
-  PinnedBuf hx[2], hy[2];
-  // per buffer: before the H2D, after it, after the kernel(s), after the D2H -- the stage times of a chunk
-  // (smm_debug_host_stats) are read from them once the chunk has been drained
-  hipEvent_t ev[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
-  hipError_t ensure(size_t need_dx, size_t need_dy, size_t need_hx, size_t need_hy) {
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 2 && e == hipSuccess; ++i)
-      if (!stream[i]) e = hipStreamCreateWithFlags(&stream[i], hipStreamNonBlocking);
-    for (int i = 0; i < 2; ++i)
-      for (int k = 0; k < 4 && e == hipSuccess; ++k)
-        if (!ev[i][k]) e = hipEventCreate(&ev[i][k]);
-    // a pair's capacity is that of its smaller buffer: zero after a failed allocation (alloc frees first)
-    auto grow = [&](auto(&buf)[2], size_t need) {
-      if (need <= std::min(buf[0].bytes(), buf[1].bytes())) return;
-      for (int i = 0; i < 2 && e == hipSuccess; ++i) e = buf[i].alloc(need);
-    };
-    grow(dx, need_dx);
-    grow(dy, need_dy);
-    grow(hx, need_hx);
-    grow(hy, need_hy);
-    return e;
-  }
-  hipError_t mark(int b, int k) { return hipEventRecord(ev[b][k], stream[b]); }   // stage boundary k of buffer b
-  // After a failed chunk: wait for whatever is still queued on both streams (an async D2H into the
-  // caller's Y of the previous chunk), so that nothing writes into caller memory after the return.
-  void quiesce() {
-    for (int i = 0; i < 2; ++i)
-      if (stream[i]) (void)hipStreamSynchronize(stream[i]);
-    (void)hipGetLastError();
-  }
-  ~HostPipe() {
-    for (int i = 0; i < 2; ++i) {
-      if (stream[i]) (void)hipStreamDestroy(stream[i]);
-      for (int k = 0; k < 4; ++k)
-        if (ev[i][k]) (void)hipEventDestroy(ev[i][k]);
-    }
-  }
-};
-
-}  // namespace
-
-// ------------------------------------------------------------------ handles
-
-constexpr int kNumShapes = 5;
-constexpr int shape_rows(int which) { return which == 0 ? 256 : (64 >> (which - 1)); }
-
-struct smm_operator {
-  int device = -1;
-  smm::HostCsr csr;          // canonical: row = destination cell
-  int64_t pruned_links = 0;  // exact-zero links dropped at create time (SMM_CREATE_PRUNE_ZEROS)
-  int64_t n_slices = 0, n_slots = 0;
-  DeviceBuf<int64_t> d_slice_off;
-  DeviceBuf<int32_t> d_col;
-  DeviceBuf<double> d_val;
-  DeviceBuf<int32_t> d_rowlen;
-  DeviceBuf<uint8_t> d_imask;
-  DeviceBuf<double> d_frac;
-  // LDS tile plans by block shape: [0] = 4 slices (256 rows) per block, [1] = 1 slice (heavy rows),
-  // [2..4] = 32 / 16 / 8 rows of a slice (rows so long -- high-resolution source, coarse target --
-  // that a whole slice's footprint exceeds the LDS budget).  The operator's own shape is built at
-  // create time, the others on demand when it joins a group of another shape.
-  struct TilePlan {
-    bool built = false, valid = false;
-    int64_t max_chunks = 0, total_chunks = 0, total_lines = 0;
-    bool preferred = false;  // staged lines are used well enough to beat direct gathers
-    bool reuse = false;      // some staged lines are shared by several blocks (keep them cacheable)
-    DeviceBuf<int64_t> d_blk_chunk_off;
-    DeviceBuf<int32_t> d_chunk_src;
-    DeviceBuf<int32_t> d_lcol;
-    DeviceBuf<uint8_t> d_blk_direct;
-  } plan[kNumShapes];
-  smm::HostSell sell_shape;  // slice_off / rowlen only (col/val dropped after upload)
-  std::mutex plan_mu;
-  std::mutex pipe_mu;        // smm_apply_host calls on one operator take turns
-  HostPipe pipe;
-  // plain canonical CSR on the device for the batch-fastest kernel, uploaded on first use
-  bool sb_ready = false;
-  std::vector<int32_t> h_used;        // ascending used source cells (host pack of the pipeline)
-  DeviceBuf<int64_t> d_csr_rowptr;
-  DeviceBuf<int32_t> d_csr_col;       // source cell
-  DeviceBuf<int32_t> d_csr_colp;      // rank of the source cell among the used cells (packed X)
-  DeviceBuf<double> d_csr_val;
-  // row table of smm_apply_grib on the device, grown on demand; calls on one operator take turns filling it
-  std::mutex grib_mu;
-  DeviceBuf<smm_grib_row_t> d_grib_rows;
-  // smm_apply_grib_bm, under the same mutex: the rows' bitmap records and the rank tables of the bitmapped ones (with
-  // their segment totals behind them); smm_apply_host_grib_bm, under pipe_mu: the rank buffer of each pipeline slot
-  DeviceBuf<GribRowBitmap> d_grib_bm;
-  DeviceBuf<char> d_grib_rank, d_pipe_rank[2];
-  std::atomic<int> group_refs{0};  // groups borrowing this operator (their descriptors hold its device pointers)
-  int native = 0;            // shape of the operator's own plan (choose_native_plan)
-  int native_plan() const { return native; }
-  DeviceBuf<LevelDesc> d_desc;  // one-element device copy (native plan)
-  LevelDesc desc(int which) const {
-    LevelDesc L;
-    L.slice_off = d_slice_off.get();
-    L.col = d_col.get();
-    L.val = d_val.get();
-    L.rowlen = d_rowlen.get();
-    L.imask = d_imask.get();
-    L.frac = d_frac.get();
-    L.blk_chunk_off = plan[which].d_blk_chunk_off.get();
-    L.chunk_src = plan[which].d_chunk_src.get();
-    L.lcol = plan[which].d_lcol.get();
-    L.blk_direct = plan[which].d_blk_direct.get();
-    return L;
-  }
-};
-
-struct smm_group {
-  int device = -1;
-  std::vector<smm_operator_t> ops;
-  DeviceBuf<LevelDesc> d_descs;
-  int tile_which = 0;  // plan shape shared by all members
-  bool tile_valid = false;
-  bool tile_preferred = false;
-  bool tile_reuse = false;
-  int64_t tile_max_chunks = 0;
-  int64_t max_row_nnz = 0;
-  // uploaded (level_index, masked_levels) configurations, keyed by content.  An entry lives until
-  // smm_group_destroy: a kernel enqueued by another thread may still read it, so nothing is ever
-  // evicted (an entry is n_lev * 4 + n_ops bytes; callers cycle through a few level subsets).
+// largest 1-D launch grid (workgroups); smm_debug_set_grid_limit lowers it so that tests reach the split path
+std::atomic<int64_t> g_grid_limit{0x7fffffffLL};
+// test hook for the pipelines' error path (smm_debug_fail_at_chunk): chunk c of the next host-pipeline
+// calls fails; -1 (the default) = off.  Set explicitly by the tests, never read from the environment.
+std::atomic<int64_t> g_fail_at_chunk{-1};
+// What the host pipelines spent where, summed since the last reset (smm_debug_host_stats).
+struct HostStats {
   std::mutex mu;
-  std::map<std::string, DeviceBuf<char>> cfg_cache;
-  std::mutex pipe_mu;  // smm_group_apply_host calls on one group take turns
-  HostPipe pipe;
-  // smm_group_apply_grib / smm_group_apply_host_grib: the row table, the bitmap records and the rank tables, as
-  // smm_operator holds them -- grown on demand, the first three under grib_mu, the slots' rank buffers under pipe_mu
-  std::mutex grib_mu;
-  DeviceBuf<smm_grib_row_t> d_grib_rows;
-  DeviceBuf<GribRowBitmap> d_grib_bm;
-  DeviceBuf<char> d_grib_rank, d_pipe_rank[2];
-};
+  double v[SMM_HOST_STAT_COUNT] = {};
+} g_host_stats;
+}  // namespace
+
+namespace smm {   // declared in smm_launch.hpp (smm_comm.cpp declares fail_msg itself) and smm_device.hpp
+int fail_msg(int code, const std::string& msg) {
+  g_last_error = msg;
+  return code;
+}
+int tuning(int knob) { return (knob >= 0 && knob < SMM_TUNE_COUNT) ? g_tuning[knob].load(std::memory_order_relaxed) : 0; }
+int64_t grid_limit() { return g_grid_limit.load(); }
+int64_t test_fail_chunk() { return g_fail_at_chunk.load(std::memory_order_relaxed); }
+void add_host_stats(const double* v) {
+  std::lock_guard<std::mutex> lock(g_host_stats.mu);
+  for (int i = 0; i < SMM_HOST_STAT_COUNT; ++i) g_host_stats.v[i] += v[i];
+  g_host_stats.v[SMM_HOST_STAT_THREADS] = (double)smm::staging_threads();
+}
+}  // namespace smm
 
 namespace {
 
@@ -309,25 +160,6 @@ int upload(DeviceBuf<T>& buf, const std::vector<T>& h) {   // buf is empty after
   SMM_HIP(buf.upload(h));
   return SMM_OK;
 }
-
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) {
-      (void)hipGetLastError();
-      return;
-    }
-    if (prev == dev) {
-      ok = true;
-      return;
-    }
-    ok = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    if (ok && prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 int refresh_desc(smm_operator* op) {
   const LevelDesc L = op->desc(op->native_plan());
@@ -404,10 +236,6 @@ int ensure_sb(smm_operator* op) {
   op->sb_ready = true;
   return SMM_OK;
 }
-
-// largest 1-D launch grid (workgroups); smm_debug_set_grid_limit lowers it so that tests reach the split path
-std::atomic<int64_t> g_grid_limit{0x7fffffffLL};
-inline int64_t grid_limit() { return g_grid_limit.load(); }
 
 struct LaunchInfo {
   bool tile = false, big_operator = false, dma = false;
@@ -568,19 +396,6 @@ int run_apply(const ApplyTarget& t, const int32_t* d_lev_map, const uint8_t* d_l
 
 namespace {
 
-// test hook for the pipelines' error path (smm_debug_fail_at_chunk): chunk c of the next host-pipeline
-// calls fails; -1 (the default) = off.  Set explicitly by the tests, never read from the environment.
-std::atomic<int64_t> g_fail_at_chunk{-1};
-int64_t test_fail_chunk() { return g_fail_at_chunk.load(std::memory_order_relaxed); }
-
-// Staging stages of the two host pipelines (smm_hostpool.cpp: one persistent worker pool, nothing throws):
-// their int results become statuses here.
-int stage_status(int rc, const char* what) {
-  if (rc == 0) return SMM_OK;
-  return fail(rc == 1 ? SMM_ERR_ALLOC : SMM_ERR_INTERNAL,
-              std::string(what) + (rc == 1 ? ": out of host memory in a staging task" : ": a staging task failed"));
-}
-int host_copy(void* dst, const void* src, size_t bytes) { return stage_status(smm::host_copy(dst, src, bytes), "host copy"); }
 int host_pack(void* out, const void* x, size_t xsz, int64_t n_inner, int64_t stride_o, int64_t stride_i,
               const std::vector<int32_t>& used, int64_t rows) {
   return stage_status(smm::host_pack(out, x, xsz, n_inner, stride_o, stride_i, used.data(), (int64_t)used.size(), rows,
@@ -589,167 +404,6 @@ int host_pack(void* out, const void* x, size_t xsz, int64_t n_inner, int64_t str
 }
 int host_pack(void* out, const void* x, size_t xsz, int64_t ldx, const std::vector<int32_t>& used, int64_t rows) {
   return host_pack(out, x, xsz, std::max<int64_t>(rows, 1), 0, ldx, used, rows);
-}
-
-// What the two host pipelines spent where, summed since the last reset (smm_debug_host_stats).
-struct HostStats {
-  std::mutex mu;
-  double v[SMM_HOST_STAT_COUNT] = {};
-} g_host_stats;
-
-inline double wall_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// one call's share: host-side stages by the wall clock of the calling thread, device-side stages from the
-// chunk's four events once its stream has been synchronised
-struct CallStats {
-  double v[SMM_HOST_STAT_COUNT] = {};
-  double t_call = wall_ms();
-  void chunk_done(HostPipe& pipe, int b) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, pipe.ev[b][0], pipe.ev[b][1]) == hipSuccess) v[SMM_HOST_STAT_H2D_MS] += ms;
-    if (hipEventElapsedTime(&ms, pipe.ev[b][1], pipe.ev[b][2]) == hipSuccess) v[SMM_HOST_STAT_KERNEL_MS] += ms;
-    if (hipEventElapsedTime(&ms, pipe.ev[b][2], pipe.ev[b][3]) == hipSuccess) v[SMM_HOST_STAT_D2H_MS] += ms;
-    (void)hipGetLastError();
-    v[SMM_HOST_STAT_CHUNKS] += 1;
-  }
-  ~CallStats() {
-    v[SMM_HOST_STAT_CALLS] = 1;
-    v[SMM_HOST_STAT_TOTAL_MS] = wall_ms() - t_call;
-    std::lock_guard<std::mutex> lock(g_host_stats.mu);
-    for (int i = 0; i < SMM_HOST_STAT_COUNT; ++i) g_host_stats.v[i] += v[i];
-    g_host_stats.v[SMM_HOST_STAT_THREADS] = (double)smm::staging_threads();
-  }
-};
-struct StageTimer {   // adds the scope's wall time to one entry
-  double& acc;
-  double t0 = wall_ms();
-  explicit StageTimer(double& a) : acc(a) {}
-  ~StageTimer() { acc += wall_ms() - t0; }
-};
-
-bool is_pinned(const void* p) {
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return attr.type == hipMemoryTypeHost;
-}
-
-// The loop both host pipelines share; chunk c runs in buffer c & 1.  launch(c, b) stages chunk c, enqueues its H2D, its
-// kernels and its D2H on pipe.stream[b] and marks the four stage boundaries between them (pipe.mark: the first lies
-// between the host staging and the H2D, so the marks cannot sit out here); deliver(c, b) copies the chunk's results out
-// of the pinned buffer once its stream has drained.  Buffer b is free again once chunk c-2 has been delivered.  Any
-// failure first waits for the copies still in flight into the caller's buffers (chunk c-1's D2H) before it is returned.
-template <typename Launch, typename Deliver>
-int run_host_pipeline(HostPipe& pipe, int64_t n_chunks, CallStats& st, Launch&& launch, Deliver&& deliver) {
-  auto drain = [&](int64_t c) -> int {
-    const int b = (int)(c & 1);
-    {
-      StageTimer t(st.v[SMM_HOST_STAT_WAIT_MS]);
-      SMM_HIP(hipStreamSynchronize(pipe.stream[b]));
-    }
-    st.chunk_done(pipe, b);
-    return deliver(c, b);
-  };
-  const int64_t fail_at = test_fail_chunk();
-  auto loop = [&]() -> int {
-    for (int64_t c = 0; c < n_chunks; ++c) {
-      if (c >= 2)
-        if (int rc = drain(c - 2)) return rc;
-      if (c == fail_at) return fail(SMM_ERR_HIP, "injected failure (smm_debug_fail_at_chunk)");
-      if (int rc = launch(c, (int)(c & 1))) return rc;
-    }
-    for (int64_t c = std::max<int64_t>(0, n_chunks - 2); c < n_chunks; ++c)
-      if (int rc = drain(c)) return rc;
-    return SMM_OK;
-  };
-  const int rc = loop();
-  if (rc) pipe.quiesce();   // keeps the thread's error message of the first failure
-  return rc;
-}
-
-}  // namespace
-
-namespace {
-
-// Every extern "C" entry that can reach an allocation runs its body through this: the header promises an int
-// status, never an exception.  (fail() assigns a std::string and may itself run out of memory: then the status
-// alone has to do.)
-template <typename F>
-int guarded(F&& body) noexcept {
-  try {
-    return body();
-  } catch (const std::bad_alloc&) {
-    try {
-      return fail(SMM_ERR_ALLOC, "out of host memory");
-    } catch (...) {
-      return SMM_ERR_ALLOC;
-    }
-  } catch (const std::exception& e) {
-    try {
-      return fail(SMM_ERR_INTERNAL, std::string("unexpected failure: ") + e.what());
-    } catch (...) {
-      return SMM_ERR_INTERNAL;
-    }
-  } catch (...) {
-    try {
-      return fail(SMM_ERR_INTERNAL, "unexpected failure (unknown exception)");
-    } catch (...) {
-      return SMM_ERR_INTERNAL;
-    }
-  }
-}
-
-// apply flags the ABI defines; anything else (ABI v4 callers encoded kernel variants in bits 16..23) is refused
-constexpr unsigned kApplyFlagMask = SMM_APPLY_MASKED | SMM_APPLY_NO_FILL | SMM_APPLY_SB_PACKED | SMM_APPLY_HOST_NO_PACK |
-                                    SMM_APPLY_SB_Y_SB | SMM_APPLY_SKIPNA | SMM_APPLY_KERNEL_SELL |
-                                    SMM_APPLY_KERNEL_TILE;
-inline int check_flags(unsigned flags) {
-  if (flags & ~kApplyFlagMask)
-    return fail(SMM_ERR_INVALID, "unknown apply flag bits 0x" + [](unsigned v) {
-             char buf[16];
-             snprintf(buf, sizeof(buf), "%x", v);
-             return std::string(buf);
-           }(flags & ~kApplyFlagMask) + " (launch-shape knobs are smm_debug_set_tuning entries, not flags)");
-  if ((flags & SMM_APPLY_SKIPNA) && (flags & SMM_APPLY_NO_FILL))
-    return fail(SMM_ERR_INVALID, "SMM_APPLY_SKIPNA tests every source value: it cannot take SMM_APPLY_NO_FILL");
-  return SMM_OK;
-}
-
-// ---- what an apply refuses about its epilogue and its levels, written once for every entry (check_area_min is with
-// check_x_dtype).  what: "the operator" or "a level"
-inline int check_epilogue(const smm_operator* op, bool masked, double area_min, const char* what) {
-  if (masked && !op->d_imask.get())
-    return fail(SMM_ERR_INVALID, std::string("masked apply requested but ") + what + " has no dst_imask");
-  if (area_min > 0.0 && !op->d_frac.get())
-    return fail(SMM_ERR_INVALID, std::string("remap_area_min > 0 requested but ") + what + " has no dst_frac");
-  return SMM_OK;
-}
-// member w of a group takes the masked epilogue: the call asks for it and the member is not exempt (regrid.py:405)
-inline bool level_masked(unsigned flags, const uint8_t* masked_levels, int w) {
-  return (flags & SMM_APPLY_MASKED) && (!masked_levels || masked_levels[w]);
-}
-// Every selected level of a group call, before anything is uploaded or launched: a later level's missing dst_imask /
-// dst_frac must not surface after earlier levels have written part of Y.  flags 0 and area_min 0 ask about level_index only.
-inline int check_levels(const smm_group* g, int64_t n_lev, const int32_t* level_index, const uint8_t* masked_levels,
-                        double area_min, unsigned flags) {
-  if (n_lev > 0 && !level_index) return fail(SMM_ERR_INVALID, "null level_index");
-  for (int64_t l = 0; l < n_lev; ++l) {
-    const int w = level_index[l];
-    if (w < 0 || w >= (int)g->ops.size())
-      return fail(SMM_ERR_INVALID, "level_index[" + std::to_string(l) + "]=" + std::to_string(w) + " outside the group");
-    if (int rc = check_epilogue(g->ops[(size_t)w], level_masked(flags, masked_levels, w), area_min, "a level")) return rc;
-  }
-  return SMM_OK;
-}
-inline size_t free_device_bytes() {   // 0 when it cannot be told (the error is cleared)
-  size_t free_b = 0, total_b = 0;
-  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) return free_b;
-  (void)hipGetLastError();
-  return 0;
 }
 
 }  // namespace
@@ -1359,271 +1013,6 @@ static int smm_apply_host_impl(smm_operator_t op, const void* x_host, int64_t ld
   return run_host_pipeline(pipe, n_chunks, st, launch, deliver);
 }
 
-// ---- GRIB simple-packed fields shipped raw: smm_apply_grib / smm_apply_host_grib (kernel: smm_grib.hip)
-
-// Everything the two entries refuse before the operator is looked at and before any device is touched.
-static int check_grib_call(const void* x, bool x_device, int64_t x_bytes, const smm_grib_row_t* rows, const void* y,
-                           int y_dtype, int64_t n_batch, double area_min, unsigned flags) {
-  if (int frc = check_flags(flags)) return frc;
-  if (flags & ~(unsigned)(SMM_APPLY_MASKED | SMM_APPLY_NO_FILL | SMM_APPLY_KERNEL_SELL))
-    return fail(SMM_ERR_UNSUPPORTED, "GRIB fields run the SELL kernel on whole rows: SMM_APPLY_SKIPNA, SMM_APPLY_KERNEL_TILE "
-                                     "and the batch-fastest / host-pack flags are not built for them");
-  if (y_dtype != SMM_F64) return fail(SMM_ERR_UNSUPPORTED, "GRIB fields produce SMM_F64 results");
-  if (n_batch < 0) return fail(SMM_ERR_INVALID, "negative batch size");
-  if (x_bytes < 0) return fail(SMM_ERR_INVALID, "negative x_bytes");
-  if ((!x && x_bytes > 0) || !y || (!rows && n_batch > 0)) return fail(SMM_ERR_INVALID, "null field, result or row-table pointer");
-  if (x_device && (uintptr_t)x % 4) return fail(SMM_ERR_INVALID, "field pointer is not 4-byte aligned");
-  if ((uintptr_t)y % 8) return fail(SMM_ERR_INVALID, "result pointer is not element aligned");
-  if (int arc = check_area_min(area_min)) return arc;
-  std::string err;
-  if (!smm::check_grib_rules(rows, n_batch, err)) return fail(SMM_ERR_INVALID, err);
-  return SMM_OK;
-}
-// ... and what needs the operator's sizes.  With bitmaps (the _bm entries) check_grib_bitmaps stands where
-// check_grib_ranges stands.
-static int check_grib_operator(smm_operator_t op, int64_t x_bytes, const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps,
-                               int64_t ldy, int64_t n_batch, double area_min, unsigned flags) {
-  if (!op) return fail(SMM_ERR_INVALID, "null operator");
-  if (n_batch > 0 && ldy < op->csr.n_dst) return fail(SMM_ERR_INVALID, "ldy smaller than the grid size");
-  std::string err;
-  if (!(bitmaps ? smm::check_grib_bitmaps(rows, bitmaps, n_batch, op->csr.n_src, x_bytes, err)
-                : smm::check_grib_ranges(rows, n_batch, op->csr.n_src, x_bytes, err)))
-    return fail(SMM_ERR_INVALID, err);
-  return check_epilogue(op, flags & SMM_APPLY_MASKED, area_min, "the operator");
-}
-static bool grib_needs_division(const smm_grib_row_t* rows, int64_t n_batch) {
-  for (int64_t b = 0; b < n_batch; ++b)
-    if (rows[b].ddiv != 1.0) return true;
-  return false;
-}
-
-// n_batch rows whose table is on the device already (d_rows) over the x_bytes bytes at x: one launch, or parts of the
-// batch when the grid would pass the limit (smm::split_batch, as run_apply)
-// d_bm with n_tables > 0 (smm_apply_grib_bm): the rows' device bitmap records; d_rank holds n_tables rank tables of
-// ceil(n_src / 32) entries and behind them n_tables x segments totals.  The tables are built first, on the same stream.
-// The rank tables of n_rows rows' bitmaps over the words of x (launch_grib_build): d_rank holds n_tables tables of
-// ceil(n_src / 32) entries and behind them n_tables x segments totals.
-static int launch_grib_tables(const uint32_t* x, uint64_t last_word, const GribRowBitmap* d_bm, char* d_rank, size_t n_tables,
-                              int64_t n_rows, int64_t n_src, hipStream_t s) {
-  const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)n_src);
-  GribBuildArgs b{};
-  b.x = x;
-  b.bm = d_bm;
-  b.table = (smm_grib::GribRankEntry*)d_rank;
-  b.totals = (uint32_t*)(d_rank + n_tables * (size_t)n_blocks * sizeof(smm_grib::GribRankEntry));
-  b.last_word = last_word;
-  b.n_j = n_rows;
-  b.n_src = (uint32_t)n_src;
-  b.n_blocks = (uint32_t)n_blocks;
-  b.n_segs = (uint32_t)smm_grib::bitmap_segments((uint64_t)n_src);
-  return smm_launch::launch_grib_build(b, s);
-}
-
-static int launch_grib_rows(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* d_rows, bool div, void* y,
-                            int64_t ldy, int64_t n_batch, double area_min, unsigned flags, hipStream_t s,
-                            const GribRowBitmap* d_bm = nullptr, char* d_rank = nullptr, size_t n_tables = 0) {
-  GribArgs a{};
-  a.descs = op->d_desc.get();
-  // no data bytes at all (every row has 0 bits): the loads, clamped to word 0, read the table instead
-  a.x = x_bytes > 0 ? (const uint32_t*)x : (const uint32_t*)d_rows;
-  a.last_word = x_bytes > 0 ? smm_grib::align4((uint64_t)x_bytes) / 4 - 1 : 0;
-  a.ldy = ldy;
-  a.n_dst = op->csr.n_dst;
-  a.n_dblocks = ((a.n_dst + 63) / 64 + kWavesPerBlock - 1) / kWavesPerBlock;
-  a.area_min = area_min;
-  a.masked = (flags & SMM_APPLY_MASKED) ? 1 : 0;
-  const bool fill = !(flags & SMM_APPLY_NO_FILL);
-  auto blocks_for = [&](int64_t n_o, int64_t) -> int64_t {
-    const int bt = smm_launch::sell_batch_rows(n_o);
-    return a.n_dblocks * ((n_o + bt - 1) / bt);
-  };
-  const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)op->csr.n_src);
-  const bool with_tables = d_bm && n_tables > 0 && n_blocks > 0;
-  if (with_tables)
-    if (int rc = launch_grib_tables(a.x, a.last_word, d_bm, d_rank, n_tables, n_batch, op->csr.n_src, s)) return rc;
-  auto launch_part = [&](int64_t o0, int64_t n_o, int64_t, int64_t) -> int {
-    GribBitmapArgs p{};
-    static_cast<GribArgs&>(p) = a;
-    p.rows = d_rows + o0;
-    p.y = (double*)y + o0 * ldy;
-    p.n_j = n_o;
-    if (!with_tables) return smm_launch::launch_grib(p, div, fill, s);
-    p.bm = d_bm + o0;
-    p.table = (const smm_grib::GribRankEntry*)d_rank;
-    return smm_launch::launch_grib_bitmap(p, div, fill, s);
-  };
-  const int rc = smm::split_batch(0, n_batch, 0, 1, grid_limit(), blocks_for, launch_part);
-  if (rc == -1)
-    return fail(SMM_ERR_INVALID, "one batch row alone needs a launch grid beyond " + std::to_string(grid_limit()) +
-                                     " workgroups (destination blocks)");
-  return rc;
-}
-
-// The host tables of a device-entry call into the buffers their owner -- an operator or a group, under its grib_mu --
-// keeps for them: h->d_grib_rows, and when some row has a bitmap h->d_grib_bm, with h->d_grib_rank sized for the
-// *n_tables rank tables.
-extern "C++" {
-template <typename Handle>
-static int upload_grib_tables(Handle* h, const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_batch,
-                              int64_t n_src, hipStream_t s, size_t* n_tables_out) {
-  if (h->d_grib_rows.bytes() < (size_t)n_batch * sizeof(smm_grib_row_t)) {
-    // freeing the old table waits for the device: no kernel still reads it
-    const size_t have = h->d_grib_rows.bytes() / sizeof(smm_grib_row_t);
-    SMM_HIP(h->d_grib_rows.alloc(std::max<size_t>((size_t)n_batch, 2 * have)));
-  }
-  // `rows` may be reused on return: from pageable memory the runtime has taken the bytes when hipMemcpyAsync returns,
-  // from page-locked memory it has not -- such a table goes through a pageable copy first.  The copy itself is ordered
-  // on the stream behind the kernel of an earlier call that still reads the device table.
-  std::vector<smm_grib_row_t> pageable;
-  if (is_pinned(rows)) {
-    pageable.assign(rows, rows + n_batch);
-    rows = pageable.data();
-  }
-  SMM_HIP(hipMemcpyAsync(h->d_grib_rows.get(), rows, (size_t)n_batch * sizeof(smm_grib_row_t), hipMemcpyHostToDevice, s));
-  // the bitmap records go up beside it, each bitmapped row with the place of its rank table; a pageable vector in any
-  // case.  Only bitmapped rows take table space; a call without one runs the plain gather.
-  std::vector<GribRowBitmap> bm;
-  size_t n_tables = 0;
-  if (bitmaps) {
-    const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)n_src);
-    bm.resize((size_t)n_batch);
-    for (int64_t b = 0; b < n_batch; ++b) {
-      const bool has = bitmaps[b].bitmap_off != SMM_GRIB_NO_BITMAP;
-      bm[(size_t)b] = GribRowBitmap{bitmaps[b].bitmap_off, has ? n_tables * n_blocks : 0};
-      n_tables += has;
-    }
-  }
-  if (n_tables > 0) {
-    if (h->d_grib_bm.bytes() < bm.size() * sizeof(GribRowBitmap)) {
-      const size_t have = h->d_grib_bm.bytes() / sizeof(GribRowBitmap);
-      SMM_HIP(h->d_grib_bm.alloc(std::max<size_t>(bm.size(), 2 * have)));
-    }
-    const size_t need = n_tables * (size_t)smm_grib::bitmap_blocks((uint64_t)n_src) * sizeof(smm_grib::GribRankEntry) +
-                        n_tables * (size_t)smm_grib::bitmap_segments((uint64_t)n_src) * sizeof(uint32_t);
-    if (h->d_grib_rank.bytes() < need) SMM_HIP(h->d_grib_rank.alloc(std::max(need, 2 * h->d_grib_rank.bytes())));
-    SMM_HIP(hipMemcpyAsync(h->d_grib_bm.get(), bm.data(), bm.size() * sizeof(GribRowBitmap), hipMemcpyHostToDevice, s));
-  }
-  *n_tables_out = n_tables;
-  return SMM_OK;
-}
-}  // extern "C++"
-
-// bitmaps: null, or the records of smm_apply_grib_bm
-static int smm_apply_grib_impl(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
-                               const smm_grib_bitmap_t* bitmaps, void* y, int64_t ldy, int64_t n_batch, double area_min,
-                               unsigned flags, void* stream) {
-  if (n_batch == 0 || op->csr.n_dst == 0) return SMM_OK;
-  DeviceGuard guard(op->device);
-  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
-  hipStream_t s = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lock(op->grib_mu);
-  size_t n_tables = 0;
-  if (int rc = upload_grib_tables(op, rows, bitmaps, n_batch, op->csr.n_src, s, &n_tables)) return rc;
-  return launch_grib_rows(op, x, x_bytes, op->d_grib_rows.get(), grib_needs_division(rows, n_batch), y, ldy, n_batch, area_min,
-                          flags, s, n_tables ? op->d_grib_bm.get() : nullptr, op->d_grib_rank.get(), n_tables);
-}
-
-// Staging of a chunk (rows [ch.r0, ch.r0 + ch.nr) of the call) into the pinned buffer hx: its table first, then each
-// row's data bytes at the next 4-byte-aligned offset; the table's byte_off are those offsets, from the start of the
-// buffer.  A pinned x_host is staged all the same: the rows of a chunk need not be adjacent in it.  With bitmaps the
-// chunk's bitmap records follow the table (their bitmap_off are staged offsets as well, their second word the place of
-// the row's rank table in the slot's rank buffer), and a bitmapped row's data bytes -- ceil(n_values * nbits / 8) of
-// them -- are followed by its own copy of its bitmap.  *n_tables: the bitmapped rows of the chunk.
-static int stage_grib_chunk(char* hx, const smm::GribChunk& ch, const void* x_host, const smm_grib_row_t* rows,
-                            const smm_grib_bitmap_t* bitmaps, int64_t S, size_t* n_tables_out) {
-  size_t n_tables = 0;
-  smm_grib_row_t* table = (smm_grib_row_t*)hx;
-  GribRowBitmap* bm = (GribRowBitmap*)(hx + (size_t)ch.nr * sizeof(smm_grib_row_t));
-  uint64_t cursor = (uint64_t)ch.nr * (sizeof(smm_grib_row_t) + (bitmaps ? sizeof(GribRowBitmap) : 0));
-  const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)S), bm_bytes = smm_grib::bitmap_bytes((uint64_t)S);
-  auto data_bytes = [&](int64_t r) {
-    const bool has = bitmaps && bitmaps[ch.r0 + r].bitmap_off != SMM_GRIB_NO_BITMAP;
-    return smm_grib::row_bytes(has ? bitmaps[ch.r0 + r].n_values : (uint64_t)S, rows[ch.r0 + r].nbits);
-  };
-  for (int64_t r = 0; r < ch.nr; ++r) {
-    table[r] = rows[ch.r0 + r];
-    table[r].byte_off = cursor;
-    cursor += smm_grib::align4(data_bytes(r));
-    if (!bitmaps) continue;
-    const bool has = bitmaps[ch.r0 + r].bitmap_off != SMM_GRIB_NO_BITMAP;
-    bm[r] = GribRowBitmap{has ? cursor : SMM_GRIB_NO_BITMAP, has ? n_tables * n_blocks : 0};
-    if (has) cursor += smm_grib::align4(bm_bytes), ++n_tables;
-  }
-  for (int64_t r = 0; r < ch.nr; ++r) {   // each row's copy is spread over the staging pool (host_copy)
-    if (int rc = host_copy(hx + table[r].byte_off, (const char*)x_host + rows[ch.r0 + r].byte_off, (size_t)data_bytes(r)))
-      return rc;
-    if (bitmaps && bm[r].bitmap_off != SMM_GRIB_NO_BITMAP)
-      if (int rc = host_copy(hx + bm[r].bitmap_off, (const char*)x_host + bitmaps[ch.r0 + r].bitmap_off, (size_t)bm_bytes))
-        return rc;
-  }
-  *n_tables_out = n_tables;
-  return SMM_OK;
-}
-
-static int smm_apply_host_grib_impl(smm_operator_t op, const void* x_host, const smm_grib_row_t* rows,
-                                    const smm_grib_bitmap_t* bitmaps, void* y_host, int64_t ldy, int64_t n_batch,
-                                    double area_min, unsigned flags, int64_t chunk_rows) {
-  const int64_t S = op->csr.n_src, D = op->csr.n_dst;
-  if (n_batch == 0 || D == 0) return SMM_OK;
-  DeviceGuard guard(op->device);
-  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
-  // chunks of consecutive rows, sized by their bytes (rows differ in width): smm_internal.h
-  const smm::GribChunkPlan plan =
-      bitmaps ? smm::plan_grib_chunks_bm(rows, bitmaps, n_batch, S, D, chunk_rows, free_device_bytes())
-              : smm::plan_grib_chunks(rows, n_batch, S, D, chunk_rows, free_device_bytes());
-  const bool div = grib_needs_division(rows, n_batch);
-  const bool y_direct = is_pinned(y_host);
-  const size_t yrow = (size_t)ldy * 8;
-
-  std::lock_guard<std::mutex> pipe_lock(op->pipe_mu);
-  HostPipe& pipe = op->pipe;
-  const size_t y_chunk = (size_t)plan.max_rows * D * 8;
-  SMM_HIP(pipe.ensure(plan.max_x, y_chunk, plan.max_x, y_direct ? 0 : y_chunk));
-  if (plan.max_rank > std::min(op->d_pipe_rank[0].bytes(), op->d_pipe_rank[1].bytes()))   // device-only, one per slot
-    for (int i = 0; i < 2; ++i) SMM_HIP(op->d_pipe_rank[i].alloc(plan.max_rank));
-
-  CallStats st;
-  auto deliver = [&](int64_t c, int b) -> int {   // results of chunk c: pinned -> user rows
-    if (y_direct) return SMM_OK;
-    StageTimer t(st.v[SMM_HOST_STAT_COPY_OUT_MS]);
-    const smm::GribChunk& ch = plan.chunks[(size_t)c];
-    if (ldy == D) return host_copy((char*)y_host + (size_t)ch.r0 * yrow, pipe.hy[b].get(), (size_t)ch.nr * D * 8);
-    for (int64_t r = 0; r < ch.nr; ++r)
-      memcpy((char*)y_host + (size_t)(ch.r0 + r) * yrow, (char*)pipe.hy[b].get() + (size_t)r * D * 8, (size_t)D * 8);
-    return SMM_OK;
-  };
-  auto launch = [&](int64_t c, int b) -> int {
-    const smm::GribChunk& ch = plan.chunks[(size_t)c];
-    char* hx = (char*)pipe.hx[b].get();
-    size_t n_tables = 0;
-    {
-      StageTimer t(st.v[SMM_HOST_STAT_STAGE_IN_MS]);
-      if (int rc = stage_grib_chunk(hx, ch, x_host, rows, bitmaps, S, &n_tables)) return rc;
-    }
-    SMM_HIP(pipe.mark(b, 0));
-    SMM_HIP(hipMemcpyAsync(pipe.dx[b].get(), hx, ch.x_bytes, hipMemcpyHostToDevice, pipe.stream[b]));
-    st.v[SMM_HOST_STAT_H2D_BYTES] += (double)ch.x_bytes;
-    SMM_HIP(pipe.mark(b, 1));
-    if (int rc = launch_grib_rows(op, pipe.dx[b].get(), (int64_t)ch.x_bytes, (const smm_grib_row_t*)pipe.dx[b].get(), div,
-                                  pipe.dy[b].get(), D, ch.nr, area_min, flags, pipe.stream[b],
-                                  n_tables ? (const GribRowBitmap*)(pipe.dx[b].get() + (size_t)ch.nr * sizeof(smm_grib_row_t))
-                                           : nullptr,
-                                  op->d_pipe_rank[b].get(), n_tables))
-      return rc;
-    st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)ch.nr * D * 8);
-    SMM_HIP(pipe.mark(b, 2));
-    if (!y_direct) {
-      SMM_HIP(hipMemcpyAsync(pipe.hy[b].get(), pipe.dy[b].get(), (size_t)ch.nr * D * 8, hipMemcpyDeviceToHost, pipe.stream[b]));
-    } else {
-      SMM_HIP(hipMemcpy2DAsync((char*)y_host + (size_t)ch.r0 * yrow, yrow, pipe.dy[b].get(), (size_t)D * 8, (size_t)D * 8,
-                               (size_t)ch.nr, hipMemcpyDeviceToHost, pipe.stream[b]));
-    }
-    SMM_HIP(pipe.mark(b, 3));
-    return SMM_OK;
-  };
-  return run_host_pipeline(pipe, (int64_t)plan.chunks.size(), st, launch, deliver);
-}
-
 static int smm_operator_mask_apply_impl(smm_operator_t op, const int32_t* src_imask, int32_t* dst_imask) {
   if (!op || !src_imask || !dst_imask) return fail(SMM_ERR_INVALID, "null argument");
   DeviceGuard guard(op->device);
@@ -1716,11 +1105,9 @@ int smm_group_destroy(smm_group_t g) {
 }
 
 extern "C++" {
-// Validates (level_index, masked_levels) against the group and returns the device copy of that
-// configuration, uploading it on first sight.  Entries live until smm_group_destroy.
-static int group_level_cfg(smm_group_t g, int64_t n_lev, const int32_t* level_index,
-                           const uint8_t* masked_levels, double remap_area_min, unsigned flags,
-                           const int32_t** d_map, const uint8_t** d_masked) {
+int smm::group_level_cfg(smm_group_t g, int64_t n_lev, const int32_t* level_index,
+                         const uint8_t* masked_levels, double remap_area_min, unsigned flags,
+                         const int32_t** d_map, const uint8_t** d_masked) {   // smm_device.hpp
   *d_map = nullptr;
   *d_masked = nullptr;
   if (!g) return fail(SMM_ERR_INVALID, "null group");
@@ -2102,200 +1489,6 @@ static int smm_group_apply_host_impl(smm_group_t g, const void* x_host, void* y_
   return run_host_pipeline(pipe, n_chunks, st, launch, deliver);
 }
 
-// ---- GRIB simple-packed fields on a level group: smm_group_apply_grib / smm_group_apply_host_grib
-
-// What the two entries refuse once check_grib_call has passed, still before any device is touched: the group, its
-// level_index, where the rows lie in the buffer (the members share n_src) and each used member's epilogue.
-static int check_grib_group(smm_group_t g, int64_t x_bytes, const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps,
-                            int64_t n_rows, int64_t n_lev, const int32_t* level_index, const uint8_t* masked_levels,
-                            double area_min, unsigned flags) {
-  if (!g) return fail(SMM_ERR_INVALID, "null group");
-  if (int rc = check_levels(g, n_lev, level_index, masked_levels, 0.0, 0u)) return rc;   // level_index alone
-  const int64_t S = g->ops[0]->csr.n_src;
-  std::string err;
-  if (!(bitmaps ? smm::check_grib_bitmaps(rows, bitmaps, n_rows, S, x_bytes, err)
-                : smm::check_grib_ranges(rows, n_rows, S, x_bytes, err)))
-    return fail(SMM_ERR_INVALID, err);
-  return check_levels(g, n_lev, level_index, masked_levels, area_min, flags);
-}
-// rows of the call, or -1 when a count is negative (check_grib_call refuses it in its place)
-static int64_t grib_group_rows(int64_t n_outer, int64_t n_lev, int64_t n_inner) {
-  return (n_outer < 0 || n_lev < 0 || n_inner < 0) ? -1 : n_outer * n_lev * n_inner;
-}
-
-// The rows of (n_outer, n_lev, n_inner) -- record (o * n_lev + l) * n_inner + i of d_rows / d_bm -- over the x_bytes
-// bytes at x, all levels in one launch; the rank tables of all rows are built first, on the same stream.  A grid
-// beyond the limit is cut over the outer and the inner range (smm::split_batch, as run_apply); a single batch row whose
-// levels still do not fit is cut over the levels.
-static int launch_grib_group_rows(smm_group_t g, const int32_t* d_map, const uint8_t* d_masked, const void* x, int64_t x_bytes,
-                                  const smm_grib_row_t* d_rows, bool div, void* y, int64_t ys_o, int64_t ys_l, int64_t ys_i,
-                                  int64_t n_outer, int64_t n_lev, int64_t n_inner, double area_min, unsigned flags,
-                                  hipStream_t s, const GribRowBitmap* d_bm, char* d_rank, size_t n_tables) {
-  const int64_t S = g->ops[0]->csr.n_src;
-  GribGroupArgs a{};
-  a.descs = g->d_descs.get();
-  a.lev_masked = d_masked;
-  a.x = x_bytes > 0 ? (const uint32_t*)x : (const uint32_t*)d_rows;   // as launch_grib_rows
-  a.last_word = x_bytes > 0 ? smm_grib::align4((uint64_t)x_bytes) / 4 - 1 : 0;
-  a.n_dst = g->ops[0]->csr.n_dst;
-  a.n_dblocks = ((a.n_dst + 63) / 64 + kWavesPerBlock - 1) / kWavesPerBlock;
-  a.area_min = area_min;
-  a.masked = (flags & SMM_APPLY_MASKED) ? 1 : 0;
-  a.rec_o = n_lev * n_inner;
-  a.rec_l = n_inner;
-  a.ys_o = ys_o;
-  a.ys_l = ys_l;
-  a.ys_i = ys_i;
-  const bool fill = !(flags & SMM_APPLY_NO_FILL);
-  const bool with_tables = d_bm && n_tables > 0 && smm_grib::bitmap_blocks((uint64_t)S) > 0;
-  if (with_tables)
-    if (int rc = launch_grib_tables(a.x, a.last_word, d_bm, d_rank, n_tables, n_outer * n_lev * n_inner, S, s)) return rc;
-  const int64_t limit = grid_limit();
-  // the kernel's row indices inside a level are 32-bit: a part of 2^31 rows or more per level counts as too large
-  auto blocks_for = [&](int64_t n_o, int64_t n_i, int64_t n_l) -> int64_t {
-    const int64_t n_j = n_o * n_i;
-    if (n_j > 0x7fffffffLL) return limit + 1;
-    const int bt = smm_launch::sell_batch_rows(n_j);
-    return a.n_dblocks * ((n_j + bt - 1) / bt) * n_l;
-  };
-  auto launch_part = [&](int64_t o0, int64_t n_o, int64_t i0, int64_t n_i, int64_t l0, int64_t n_l) -> int {
-    GribGroupArgs p = a;
-    const int64_t first = (o0 * n_lev + l0) * n_inner + i0;
-    p.rows = d_rows + first;
-    p.lev_map = d_map + l0;
-    p.y = (double*)y + (o0 * ys_o + l0 * ys_l + i0 * ys_i);
-    p.n_j = n_o * n_i;
-    p.n_inner = n_i;
-    if (with_tables) {
-      p.bm = d_bm + first;
-      p.table = (const smm_grib::GribRankEntry*)d_rank;
-    }
-    return smm_launch::launch_grib_group(p, n_l, with_tables, div, fill, s);
-  };
-  // a part of several rows is cut further while it does not fit; a single row goes to the level split whatever it needs
-  const int rc = smm::split_batch(
-      0, n_outer, 0, n_inner, limit,
-      [&](int64_t n_o, int64_t n_i) -> int64_t { return n_o * n_i == 1 ? 0 : blocks_for(n_o, n_i, n_lev); },
-      [&](int64_t o0, int64_t n_o, int64_t i0, int64_t n_i) -> int {
-        return smm::split_batch(
-            0, n_lev, 0, 1, limit, [&](int64_t n_l, int64_t) { return blocks_for(n_o, n_i, n_l); },
-            [&](int64_t l0, int64_t n_l, int64_t, int64_t) { return launch_part(o0, n_o, i0, n_i, l0, n_l); });
-      });
-  if (rc == -1)
-    return fail(SMM_ERR_INVALID, "one batch row of one level alone needs a launch grid beyond " + std::to_string(limit) +
-                                     " workgroups (destination blocks)");
-  return rc;
-}
-
-static int smm_group_apply_grib_impl(smm_group_t g, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
-                                     const smm_grib_bitmap_t* bitmaps, void* y, int64_t ys_o, int64_t ys_l, int64_t ys_i,
-                                     int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index,
-                                     const uint8_t* masked_levels, double area_min, unsigned flags, void* stream) {
-  const int64_t n_rows = n_outer * n_lev * n_inner;
-  if (n_rows == 0 || g->ops[0]->csr.n_dst == 0) return SMM_OK;
-  DeviceGuard guard(g->device);
-  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the group's device");
-  const int32_t* d_map;
-  const uint8_t* d_masked;
-  if (int rc = group_level_cfg(g, n_lev, level_index, masked_levels, area_min, flags, &d_map, &d_masked)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lock(g->grib_mu);
-  size_t n_tables = 0;
-  if (int rc = upload_grib_tables(g, rows, bitmaps, n_rows, g->ops[0]->csr.n_src, s, &n_tables)) return rc;
-  return launch_grib_group_rows(g, d_map, d_masked, x, x_bytes, g->d_grib_rows.get(), grib_needs_division(rows, n_rows), y,
-                                ys_o, ys_l, ys_i, n_outer, n_lev, n_inner, area_min, flags, s,
-                                n_tables ? g->d_grib_bm.get() : nullptr, g->d_grib_rank.get(), n_tables);
-}
-
-// Host buffers: chunks of whole outer indices (smm::plan_grib_chunks_units) -- their n_lev * n_inner rows each are
-// consecutive records, staged as smm_apply_host_grib stages a chunk -- through the group's pipeline; Y is delivered as the
-// whole-row mode of smm_group_apply_host delivers it, (n_outer, n_inner, n_lev, D) when transpose, else
-// (n_lev, n_outer, n_inner, D).
-static int smm_group_apply_host_grib_impl(smm_group_t g, const void* x_host, const smm_grib_row_t* rows,
-                                          const smm_grib_bitmap_t* bitmaps, void* y_host, int64_t n_outer, int64_t n_lev,
-                                          int64_t n_inner, int transpose, const int32_t* level_index,
-                                          const uint8_t* masked_levels, double area_min, unsigned flags, int64_t chunk_outer) {
-  const int64_t S = g->ops[0]->csr.n_src, D = g->ops[0]->csr.n_dst;
-  const int64_t unit = n_lev * n_inner, n_rows = n_outer * unit;
-  if (n_rows == 0 || D == 0) return SMM_OK;
-  DeviceGuard guard(g->device);
-  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the group's device");
-  const int32_t* d_map;
-  const uint8_t* d_masked;
-  if (int rc = group_level_cfg(g, n_lev, level_index, masked_levels, area_min, flags, &d_map, &d_masked)) return rc;
-  const smm::GribChunkPlan plan =
-      smm::plan_grib_chunks_units(rows, bitmaps, n_outer, unit, S, D, chunk_outer, free_device_bytes());
-  const bool div = grib_needs_division(rows, n_rows);
-  const bool y_direct = is_pinned(y_host);
-
-  std::lock_guard<std::mutex> pipe_lock(g->pipe_mu);
-  HostPipe& pipe = g->pipe;
-  const size_t y_chunk = (size_t)plan.max_rows * D * 8;
-  SMM_HIP(pipe.ensure(plan.max_x, y_chunk, plan.max_x, y_direct ? 0 : y_chunk));
-  if (plan.max_rank > std::min(g->d_pipe_rank[0].bytes(), g->d_pipe_rank[1].bytes()))   // device-only, one per slot
-    for (int i = 0; i < 2; ++i) SMM_HIP(g->d_pipe_rank[i].alloc(plan.max_rank));
-
-  CallStats st;
-  // Y of a chunk of `no` outer indices from o0: on the device (no, n_inner, n_lev, D) when transpose -- one block of
-  // the host array -- else (n_lev, no, n_inner, D): one run per level
-  auto y_to_host = [&](int64_t o0, int64_t no, const char* src, bool async, hipStream_t stream) -> int {
-    const size_t blk = (size_t)no * n_inner * D * 8;
-    const int64_t runs = transpose ? 1 : n_lev;
-    for (int64_t r = 0; r < runs; ++r) {
-      const size_t bytes = transpose ? blk * (size_t)n_lev : blk;
-      char* dst = (char*)y_host + (transpose ? (size_t)o0 * unit : (size_t)r * n_outer * n_inner + (size_t)o0 * n_inner) * D * 8;
-      if (async) {
-        SMM_HIP(hipMemcpyAsync(dst, src + (size_t)r * blk, bytes, hipMemcpyDeviceToHost, stream));
-      } else if (int rc = host_copy(dst, src + (size_t)r * blk, bytes)) {
-        return rc;
-      }
-    }
-    return SMM_OK;
-  };
-  auto deliver = [&](int64_t c, int b) -> int {
-    if (y_direct) return SMM_OK;
-    StageTimer t(st.v[SMM_HOST_STAT_COPY_OUT_MS]);
-    const smm::GribChunk& ch = plan.chunks[(size_t)c];
-    return y_to_host(ch.r0 / unit, ch.nr / unit, (const char*)pipe.hy[b].get(), false, nullptr);
-  };
-  auto launch = [&](int64_t c, int b) -> int {
-    const smm::GribChunk& ch = plan.chunks[(size_t)c];
-    const int64_t o0 = ch.r0 / unit, no = ch.nr / unit;
-    char* hx = (char*)pipe.hx[b].get();
-    size_t n_tables = 0;
-    {
-      StageTimer t(st.v[SMM_HOST_STAT_STAGE_IN_MS]);
-      if (int rc = stage_grib_chunk(hx, ch, x_host, rows, bitmaps, S, &n_tables)) return rc;
-    }
-    SMM_HIP(pipe.mark(b, 0));
-    SMM_HIP(hipMemcpyAsync(pipe.dx[b].get(), hx, ch.x_bytes, hipMemcpyHostToDevice, pipe.stream[b]));
-    st.v[SMM_HOST_STAT_H2D_BYTES] += (double)ch.x_bytes;
-    SMM_HIP(pipe.mark(b, 1));
-    int64_t ys_o, ys_l, ys_i;   // the chunk's Y on the device, as smm_group_apply_host lays out a whole-row chunk
-    if (transpose) {
-      ys_o = n_inner * n_lev * D, ys_l = D, ys_i = n_lev * D;
-    } else {
-      ys_o = n_inner * D, ys_l = no * n_inner * D, ys_i = D;
-    }
-    if (int rc = launch_grib_group_rows(
-            g, d_map, d_masked, pipe.dx[b].get(), (int64_t)ch.x_bytes, (const smm_grib_row_t*)pipe.dx[b].get(), div,
-            pipe.dy[b].get(), ys_o, ys_l, ys_i, no, n_lev, n_inner, area_min, flags, pipe.stream[b],
-            n_tables ? (const GribRowBitmap*)(pipe.dx[b].get() + (size_t)ch.nr * sizeof(smm_grib_row_t)) : nullptr,
-            g->d_pipe_rank[b].get(), n_tables))
-      return rc;
-    st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)ch.nr * D * 8);
-    SMM_HIP(pipe.mark(b, 2));
-    if (!y_direct) {
-      SMM_HIP(hipMemcpyAsync(pipe.hy[b].get(), pipe.dy[b].get(), (size_t)ch.nr * D * 8, hipMemcpyDeviceToHost, pipe.stream[b]));
-    } else if (int rc = y_to_host(o0, no, (const char*)pipe.dy[b].get(), true, pipe.stream[b])) {
-      return rc;
-    }
-    SMM_HIP(pipe.mark(b, 3));
-    return SMM_OK;
-  };
-  return run_host_pipeline(pipe, (int64_t)plan.chunks.size(), st, launch, deliver);
-}
-
 }  // extern "C"
 
 // ---- the guarded entry points: whatever an implementation above throws (std::bad_alloc from a plan vector, a
@@ -2455,67 +1648,6 @@ int smm_apply_host_pk(smm_operator_t op, const void* x_host, int x_dtype, int64_
                       const smm_cf_decode_t* cf, const smm_cf_encode_t* enc) {
   return apply_entry(Entry::pk, x_dtype, y_dtype, remap_area_min, flags, cf, enc, [&](const CallDesc& c) {
     return smm_apply_host_impl(op, x_host, ldx, y_host, ldy, n_batch, chunk_rows, c);
-  });
-}
-
-int smm_apply_grib(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows, void* y, int y_dtype,
-                   int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* stream) {
-  return smm_apply_grib_bm(op, x, x_bytes, rows, nullptr, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream);
-}
-
-// bitmaps == NULL: the entry above
-int smm_apply_grib_bm(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
-                      const smm_grib_bitmap_t* bitmaps, void* y, int y_dtype, int64_t ldy, int64_t n_batch,
-                      double remap_area_min, unsigned flags, void* stream) {
-  return guarded([&] {
-    if (int rc = check_grib_call(x, true, x_bytes, rows, y, y_dtype, n_batch, remap_area_min, flags)) return rc;
-    if (int rc = check_grib_operator(op, x_bytes, rows, bitmaps, ldy, n_batch, remap_area_min, flags)) return rc;
-    return smm_apply_grib_impl(op, x, x_bytes, rows, bitmaps, y, ldy, n_batch, remap_area_min, flags, stream);
-  });
-}
-
-int smm_apply_host_grib(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows, void* y_host,
-                        int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags,
-                        int64_t chunk_rows) {
-  return smm_apply_host_grib_bm(op, x_host, x_bytes, rows, nullptr, y_host, y_dtype, ldy, n_batch, remap_area_min, flags,
-                                chunk_rows);
-}
-
-int smm_apply_host_grib_bm(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
-                           const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t ldy, int64_t n_batch,
-                           double remap_area_min, unsigned flags, int64_t chunk_rows) {
-  return guarded([&] {
-    if (int rc = check_grib_call(x_host, false, x_bytes, rows, y_host, y_dtype, n_batch, remap_area_min, flags)) return rc;
-    if (int rc = check_grib_operator(op, x_bytes, rows, bitmaps, ldy, n_batch, remap_area_min, flags)) return rc;
-    return smm_apply_host_grib_impl(op, x_host, rows, bitmaps, y_host, ldy, n_batch, remap_area_min, flags, chunk_rows);
-  });
-}
-
-int smm_group_apply_grib(smm_group_t g, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
-                         const smm_grib_bitmap_t* bitmaps, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev,
-                         int64_t ys_inner, int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index,
-                         const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream) {
-  return guarded([&] {
-    const int64_t n_rows = grib_group_rows(n_outer, n_lev, n_inner);
-    if (int rc = check_grib_call(x, true, x_bytes, rows, y, y_dtype, n_rows, remap_area_min, flags)) return rc;
-    if (int rc = check_grib_group(g, x_bytes, rows, bitmaps, n_rows, n_lev, level_index, masked_levels, remap_area_min, flags))
-      return rc;
-    return smm_group_apply_grib_impl(g, x, x_bytes, rows, bitmaps, y, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner,
-                                     level_index, masked_levels, remap_area_min, flags, stream);
-  });
-}
-
-int smm_group_apply_host_grib(smm_group_t g, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
-                              const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t n_outer,
-                              int64_t n_lev, int64_t n_inner, int transpose, const int32_t* level_index,
-                              const uint8_t* masked_levels, double remap_area_min, unsigned flags, int64_t chunk_outer) {
-  return guarded([&] {
-    const int64_t n_rows = grib_group_rows(n_outer, n_lev, n_inner);
-    if (int rc = check_grib_call(x_host, false, x_bytes, rows, y_host, y_dtype, n_rows, remap_area_min, flags)) return rc;
-    if (int rc = check_grib_group(g, x_bytes, rows, bitmaps, n_rows, n_lev, level_index, masked_levels, remap_area_min, flags))
-      return rc;
-    return smm_group_apply_host_grib_impl(g, x_host, rows, bitmaps, y_host, n_outer, n_lev, n_inner, transpose, level_index,
-                                          masked_levels, remap_area_min, flags, chunk_outer);
   });
 }
 

@@ -22,13 +22,7 @@ struct GribArgs {
   int masked;
 };
 
-// smm_apply_grib_bm.  The device copy of a row's smm_grib_bitmap_t: n_values, which only the host's size checks
-// read, gives its place to the row's rank table.
-struct GribRowBitmap {
-  uint64_t bitmap_off;   // byte offset of the bitmap in x; SMM_GRIB_NO_BITMAP: the row has none
-  uint64_t table_off;    // first entry of the row's table in GribBitmapArgs::table (bitmapped rows only)
-};
-static_assert(sizeof(GribRowBitmap) == sizeof(smm_grib_bitmap_t), "one record per row, 16 B");
+// smm_apply_grib_bm (GribRowBitmap: smm_grib_codec.hpp)
 struct GribBitmapArgs : GribArgs {
   const GribRowBitmap* bm;                 // device [n_j], parallel to rows
   const smm_grib::GribRankEntry* table;    // device: the rank tables of the call's bitmapped rows

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "../../include/smmregrid_amd.h"
+
 #if defined(__HIPCC__)
 #define SMM_GRIB_HD __host__ __device__ __forceinline__
 #else
@@ -84,3 +86,11 @@ SMM_GRIB_HD uint32_t bitmap_index(GribRankEntry e, uint32_t c) {
 }
 
 }  // namespace smm_grib
+
+// smm_apply_grib_bm.  The device copy of a row's smm_grib_bitmap_t: n_values, which only the host's size checks
+// read, gives its place to the row's rank table.
+struct GribRowBitmap {
+  uint64_t bitmap_off;   // byte offset of the bitmap in x; SMM_GRIB_NO_BITMAP: the row has none
+  uint64_t table_off;    // first entry of the row's table in GribBitmapArgs::table (bitmapped rows only)
+};
+static_assert(sizeof(GribRowBitmap) == sizeof(smm_grib_bitmap_t), "one record per row, 16 B");

@@ -1,7 +1,6 @@
-// Host side of the GRIB entries that needs no device: the refusals of a row table and the chunk plan of
-// smm_apply_host_grib, the same with bitmaps for the _bm entries, and the unit plan of smm_group_apply_host_grib
-// (declared in smm_internal.h).  Plain C++: tests/cpp/grib_harness.cpp, grib_bitmap_harness.cpp and
-// grib_levels_harness.cpp link this file.
+// Host side of the GRIB entries that needs no device: the refusals of a row table and of its bitmap records, the chunk
+// plan of the host entries and the layout of a staged chunk (declared in smm_internal.h).  Plain C++:
+// tests/cpp/grib_harness.cpp, grib_bitmap_harness.cpp and grib_levels_harness.cpp link this file.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -28,121 +27,43 @@ bool check_grib_rules(const smm_grib_row_t* rows, int64_t n_batch, std::string& 
   return true;
 }
 
-bool check_grib_ranges(const smm_grib_row_t* rows, int64_t n_batch, int64_t n_src, int64_t x_bytes, std::string& err) {
-  for (int64_t b = 0; b < n_batch; ++b) {
-    const uint64_t need = smm_grib::row_bytes((uint64_t)n_src, rows[b].nbits);   // n_src < 2^31, nbits <= 32: no overflow
-    if (rows[b].byte_off > (uint64_t)x_bytes || need > (uint64_t)x_bytes - rows[b].byte_off)
-      return err = "rows[" + std::to_string(b) + "]: bytes [" + std::to_string(rows[b].byte_off) + ", " +
-                   std::to_string(rows[b].byte_off) + " + " + std::to_string(need) + ") leave the buffer of " +
-                   std::to_string(x_bytes) + " bytes", false;
-  }
-  return true;
-}
-
-GribChunkPlan plan_grib_chunks(const smm_grib_row_t* rows, int64_t n_batch, int64_t n_src, int64_t D,
-                               int64_t requested_rows, size_t free_bytes) {
-  constexpr size_t kTarget = (size_t)256 << 20, kMinChunk = (size_t)32 << 20;
-  constexpr int64_t kMinChunks = 8;
-  GribChunkPlan plan;
-  auto row_cost_x = [&](int64_t b) {
-    return sizeof(smm_grib_row_t) + (size_t)smm_grib::align4(smm_grib::row_bytes((uint64_t)n_src, rows[b].nbits));
-  };
-  const size_t y_row = (size_t)std::max<int64_t>(D, 0) * 8;
-  if (requested_rows <= 0) {
-    size_t total = 0;
-    for (int64_t b = 0; b < n_batch; ++b) total += row_cost_x(b) + y_row;
-    plan.target = std::min(kTarget, std::max(kMinChunk, total / (size_t)kMinChunks));
-    if (free_bytes > 0) plan.target = std::min(plan.target, std::max<size_t>(free_bytes / 8, 1));
-  }
-  for (int64_t b = 0; b < n_batch;) {
-    GribChunk c{b, 0, 0};
-    size_t bytes = 0;
-    while (b < n_batch) {
-      const size_t x = row_cost_x(b);
-      if (requested_rows > 0 ? c.nr >= requested_rows : (c.nr > 0 && bytes + x + y_row > plan.target)) break;
-      bytes += x + y_row;
-      c.x_bytes += x;
-      ++c.nr;
-      ++b;
-    }
-    plan.max_x = std::max(plan.max_x, c.x_bytes);
-    plan.max_rows = std::max(plan.max_rows, c.nr);
-    plan.chunks.push_back(c);
-  }
-  return plan;
-}
-
-bool check_grib_bitmaps(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_batch, int64_t n_src,
-                        int64_t x_bytes, std::string& err) {
+bool check_grib_ranges(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_batch, int64_t n_src,
+                       int64_t x_bytes, std::string& err) {
   auto outside = [&](uint64_t off, uint64_t need) { return off > (uint64_t)x_bytes || need > (uint64_t)x_bytes - off; };
   for (int64_t b = 0; b < n_batch; ++b) {
-    const smm_grib_bitmap_t& m = bitmaps[b];
     const std::string at = "rows[" + std::to_string(b) + "]";
-    if (m.n_values > (uint64_t)n_src)
-      return err = at + ": n_values " + std::to_string(m.n_values) + " exceeds the grid's " + std::to_string(n_src) + " cells",
-             false;
-    const bool has = m.bitmap_off != SMM_GRIB_NO_BITMAP;
-    if (has && outside(m.bitmap_off, smm_grib::bitmap_bytes((uint64_t)n_src)))
-      return err = at + ": bitmap bytes [" + std::to_string(m.bitmap_off) + ", " + std::to_string(m.bitmap_off) + " + " +
-                   std::to_string(smm_grib::bitmap_bytes((uint64_t)n_src)) + ") leave the buffer of " +
-                   std::to_string(x_bytes) + " bytes", false;
-    const uint64_t need = smm_grib::row_bytes(has ? m.n_values : (uint64_t)n_src, rows[b].nbits);
-    if (outside(rows[b].byte_off, need))
+    if (bitmaps && bitmaps[b].n_values > (uint64_t)n_src)
+      return err = at + ": n_values " + std::to_string(bitmaps[b].n_values) + " exceeds the grid's " + std::to_string(n_src) +
+                   " cells", false;
+    const GribRowCost c = grib_row_cost(rows[b], bitmaps ? &bitmaps[b] : nullptr, n_src);   // n_src < 2^31, nbits <= 32: no overflow
+    if (c.has_bitmap && outside(bitmaps[b].bitmap_off, c.bitmap_bytes))
+      return err = at + ": bitmap bytes [" + std::to_string(bitmaps[b].bitmap_off) + ", " + std::to_string(bitmaps[b].bitmap_off) +
+                   " + " + std::to_string(c.bitmap_bytes) + ") leave the buffer of " + std::to_string(x_bytes) + " bytes", false;
+    if (outside(rows[b].byte_off, c.data_bytes))
       return err = at + ": bytes [" + std::to_string(rows[b].byte_off) + ", " + std::to_string(rows[b].byte_off) + " + " +
-                   std::to_string(need) + ") leave the buffer of " + std::to_string(x_bytes) + " bytes", false;
+                   std::to_string(c.data_bytes) + ") leave the buffer of " + std::to_string(x_bytes) + " bytes", false;
   }
   return true;
 }
 
-size_t grib_bm_row_staged(const smm_grib_row_t& row, const smm_grib_bitmap_t& bm, int64_t n_src) {
-  const bool has = bm.bitmap_off != SMM_GRIB_NO_BITMAP;
-  return sizeof(smm_grib_row_t) + sizeof(smm_grib_bitmap_t) +
-         (size_t)smm_grib::align4(smm_grib::row_bytes(has ? bm.n_values : (uint64_t)n_src, row.nbits)) +
-         (has ? (size_t)smm_grib::align4(smm_grib::bitmap_bytes((uint64_t)n_src)) : 0);
-}
-
-size_t grib_bm_row_rank(const smm_grib_bitmap_t& bm, int64_t n_src) {
-  if (bm.bitmap_off == SMM_GRIB_NO_BITMAP) return 0;
-  return (size_t)smm_grib::bitmap_blocks((uint64_t)n_src) * sizeof(smm_grib::GribRankEntry) +
-         (size_t)smm_grib::bitmap_segments((uint64_t)n_src) * sizeof(uint32_t);
-}
-
-GribChunkPlan plan_grib_chunks_bm(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_batch,
-                                  int64_t n_src, int64_t D, int64_t requested_rows, size_t free_bytes) {
-  constexpr size_t kTarget = (size_t)256 << 20, kMinChunk = (size_t)32 << 20;   // plan_grib_chunks' bounds
-  constexpr int64_t kMinChunks = 8;
-  GribChunkPlan plan;
-  const size_t y_row = (size_t)std::max<int64_t>(D, 0) * 8;
-  if (requested_rows <= 0) {
-    size_t total = 0;
-    for (int64_t b = 0; b < n_batch; ++b)
-      total += grib_bm_row_staged(rows[b], bitmaps[b], n_src) + grib_bm_row_rank(bitmaps[b], n_src) + y_row;
-    plan.target = std::min(kTarget, std::max(kMinChunk, total / (size_t)kMinChunks));
-    if (free_bytes > 0) plan.target = std::min(plan.target, std::max<size_t>(free_bytes / 8, 1));
+GribRowCost grib_row_cost(const smm_grib_row_t& row, const smm_grib_bitmap_t* bm, int64_t n_src) {
+  GribRowCost c;
+  c.has_bitmap = bm && bm->bitmap_off != SMM_GRIB_NO_BITMAP;
+  c.records = sizeof(smm_grib_row_t) + (bm ? sizeof(GribRowBitmap) : 0);
+  c.data_bytes = (size_t)smm_grib::row_bytes(c.has_bitmap ? bm->n_values : (uint64_t)n_src, row.nbits);
+  c.staged_data = (size_t)smm_grib::align4(c.data_bytes);
+  if (c.has_bitmap) {
+    c.bitmap_bytes = (size_t)smm_grib::bitmap_bytes((uint64_t)n_src);
+    c.staged_bitmap = (size_t)smm_grib::align4(c.bitmap_bytes);
+    c.rank = (size_t)smm_grib::bitmap_blocks((uint64_t)n_src) * sizeof(smm_grib::GribRankEntry) +
+             (size_t)smm_grib::bitmap_segments((uint64_t)n_src) * sizeof(uint32_t);
   }
-  for (int64_t b = 0; b < n_batch;) {
-    GribChunk c{b, 0, 0};
-    size_t bytes = 0;
-    while (b < n_batch) {
-      const size_t x = grib_bm_row_staged(rows[b], bitmaps[b], n_src), r = grib_bm_row_rank(bitmaps[b], n_src);
-      if (requested_rows > 0 ? c.nr >= requested_rows : (c.nr > 0 && bytes + x + r + y_row > plan.target)) break;
-      bytes += x + r + y_row;
-      c.x_bytes += x;
-      c.rank_bytes += r;
-      ++c.nr;
-      ++b;
-    }
-    plan.max_x = std::max(plan.max_x, c.x_bytes);
-    plan.max_rank = std::max(plan.max_rank, c.rank_bytes);
-    plan.max_rows = std::max(plan.max_rows, c.nr);
-    plan.chunks.push_back(c);
-  }
-  return plan;
+  return c;
 }
 
-GribChunkPlan plan_grib_chunks_units(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_outer,
-                                     int64_t unit, int64_t n_src, int64_t D, int64_t requested_units, size_t free_bytes) {
-  constexpr size_t kTarget = (size_t)256 << 20, kMinChunk = (size_t)32 << 20;   // plan_grib_chunks' bounds
+GribChunkPlan plan_grib_chunks(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_outer, int64_t unit,
+                               int64_t n_src, int64_t D, int64_t requested_units, size_t free_bytes) {
+  constexpr size_t kTarget = (size_t)256 << 20, kMinChunk = (size_t)32 << 20;
   constexpr int64_t kMinChunks = 8;
   GribChunkPlan plan;
   if (n_outer <= 0 || unit <= 0) return plan;
@@ -151,12 +72,9 @@ GribChunkPlan plan_grib_chunks_units(const smm_grib_row_t* rows, const smm_grib_
   auto unit_cost = [&](int64_t o, size_t& x, size_t& r) {
     x = r = 0;
     for (int64_t b = o * unit; b < (o + 1) * unit; ++b) {
-      if (bitmaps) {
-        x += grib_bm_row_staged(rows[b], bitmaps[b], n_src);
-        r += grib_bm_row_rank(bitmaps[b], n_src);
-      } else {
-        x += sizeof(smm_grib_row_t) + (size_t)smm_grib::align4(smm_grib::row_bytes((uint64_t)n_src, rows[b].nbits));
-      }
+      const GribRowCost c = grib_row_cost(rows[b], bitmaps ? &bitmaps[b] : nullptr, n_src);
+      x += c.staged();
+      r += c.rank;
     }
   };
   if (requested_units <= 0) {
@@ -192,4 +110,26 @@ GribChunkPlan plan_grib_chunks_units(const smm_grib_row_t* rows, const smm_grib_
   return plan;
 }
 
+GribChunkLayout layout_grib_chunk(char* hx, const GribChunk& ch, const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps,
+                                  int64_t n_src) {
+  smm_grib_row_t* table = (smm_grib_row_t*)hx;
+  GribRowBitmap* bm = (GribRowBitmap*)(hx + (size_t)ch.nr * sizeof(smm_grib_row_t));
+  const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)n_src);
+  GribChunkLayout out;
+  for (int64_t r = 0; r < ch.nr; ++r)   // the records come first ...
+    out.end += grib_row_cost(rows[ch.r0 + r], bitmaps ? &bitmaps[ch.r0 + r] : nullptr, n_src).records;
+  for (int64_t r = 0; r < ch.nr; ++r) {   // ... then each row's data and, behind it, its bitmap
+    const GribRowCost c = grib_row_cost(rows[ch.r0 + r], bitmaps ? &bitmaps[ch.r0 + r] : nullptr, n_src);
+    table[r] = rows[ch.r0 + r];
+    table[r].byte_off = out.end;
+    out.end += c.staged_data;
+    if (!bitmaps) continue;
+    bm[r] = GribRowBitmap{c.has_bitmap ? (uint64_t)out.end : SMM_GRIB_NO_BITMAP, c.has_bitmap ? out.n_tables * n_blocks : 0};
+    out.end += c.staged_bitmap;
+    out.n_tables += c.has_bitmap;
+  }
+  return out;
+}
+
 }  // namespace smm
+

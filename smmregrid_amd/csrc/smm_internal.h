@@ -189,54 +189,59 @@ GroupChunkPlan plan_group_chunks(int64_t n_outer, int64_t n_lev, int64_t n_inner
                                  size_t ysz, const int64_t* used_per_level, bool packing_allowed,
                                  int64_t requested_outer, size_t free_bytes, int64_t budget_kb);
 
-// ---- GRIB simple-packed fields shipped raw (smm_apply_grib / smm_apply_host_grib; smm_grib_plan.cpp, plain C++).
-// What the two entries refuse about their row table before any device is touched: false + err.  check_grib_rules looks
-// at the rules alone (nbits, reserved, bscale a normal power of two, ddiv finite and > 0, ref finite); check_grib_ranges
-// at where each row's ceil(n_src * nbits / 8) bytes lie in [0, x_bytes).
+// ---- GRIB simple-packed fields shipped raw (the smm_*apply*_grib* entries; smm_grib_plan.cpp, plain C++).  `bitmaps` is
+// null in a call without bitmap records (smm_apply_grib, smm_apply_host_grib) and has one record per row otherwise.
+// What the entries refuse about their row table before any device is touched: false + err.  check_grib_rules looks at the
+// rules alone (nbits, reserved, bscale a normal power of two, ddiv finite and > 0, ref finite); check_grib_ranges at where
+// each row's bytes lie in [0, x_bytes): ceil(n_src * nbits / 8) data bytes, or with a bitmap ceil(n_values * nbits / 8) of
+// them and the ceil(n_src / 8) bytes of the bitmap -- and at n_values <= n_src in every record.
 bool check_grib_rules(const smm_grib_row_t* rows, int64_t n_batch, std::string& err);
-bool check_grib_ranges(const smm_grib_row_t* rows, int64_t n_batch, int64_t n_src, int64_t x_bytes, std::string& err);
-// Chunk plan of smm_apply_host_grib: consecutive rows [r0, r0 + nr) per chunk.  Rows differ in width, so a chunk is sized
-// by bytes, not by rows: its staging -- the table (one smm_grib_row_t per row) and each row's data bytes rounded up to 4
-// -- plus nr * D * 8 of Y stay within the target (~256 MiB; an eighth of the call so that chunks overlap, but no less
-// than 32 MiB; an eighth of free_bytes when that is known: the four device buffers of a chunk take a quarter of it at
-// most).  A row that alone exceeds the target still gets a chunk of its own.  requested_rows > 0: that many rows per chunk.
+bool check_grib_ranges(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_batch, int64_t n_src,
+                       int64_t x_bytes, std::string& err);
+// What a row costs a host entry.  Staged through the pinned buffer: its table record (40 B), its bitmap record (16 B, when
+// the call has records), its data bytes and, with a bitmap, its bitmap bytes, each rounded up to 4.  Device-only: its
+// share of the rank buffer -- with a bitmap one 8-byte entry per 32 cells and its 4-byte segment totals.  bm: the row's
+// record, or null.  The planner sums these and the layout of a chunk advances by them: there is no second arithmetic.
+struct GribRowCost {
+  bool has_bitmap = false;
+  size_t records = 0;
+  size_t data_bytes = 0, bitmap_bytes = 0;       // as they lie in the caller's buffer
+  size_t staged_data = 0, staged_bitmap = 0;     // the same rounded up to 4
+  size_t rank = 0;
+  size_t staged() const { return records + staged_data + staged_bitmap; }
+};
+GribRowCost grib_row_cost(const smm_grib_row_t& row, const smm_grib_bitmap_t* bm, int64_t n_src);
+// Chunk plan of the host entries: consecutive rows [r0, r0 + nr) per chunk, in whole units -- a unit is one row for
+// smm_apply_host_grib(_bm) (n_outer = n_batch, unit = 1) and the n_lev * n_inner consecutive records of an outer index
+// for smm_group_apply_host_grib: r0 and nr of every chunk are multiples of `unit`.  Rows differ in width, so a chunk is
+// sized by bytes, not by rows: its staged bytes, its rank bytes and nr * D * 8 of Y stay within the target (~256 MiB; an
+// eighth of the call so that chunks overlap, but no less than 32 MiB; an eighth of free_bytes when that is known: the
+// four device buffers of a chunk take a quarter of it at most).  A unit that alone exceeds the target still gets a chunk
+// of its own.  requested_units > 0: that many units per chunk (the last may be short).  n_outer <= 0 or unit <= 0: no chunks.
 struct GribChunk {
   int64_t r0, nr;
-  size_t x_bytes;          // staged bytes of the chunk: table + padded rows
-  size_t rank_bytes = 0;   // plan_grib_chunks_bm: the chunk's device-only rank tables and segment totals
+  size_t x_bytes;          // staged bytes of the chunk: the sum of its rows' GribRowCost::staged()
+  size_t rank_bytes = 0;   // the chunk's device-only rank tables and segment totals
 };
 struct GribChunkPlan {
-  std::vector<GribChunk> chunks;   // cover [0, n_batch) exactly once, in order
-  size_t target = 0;               // the byte bound in force (0 with requested_rows)
+  std::vector<GribChunk> chunks;   // cover [0, n_outer * unit) exactly once, in order
+  size_t target = 0;               // the byte bound in force (0 with requested_units)
   size_t max_x = 0;                // largest staged X of one chunk
   int64_t max_rows = 0;            // most rows of one chunk
   size_t max_rank = 0;             // largest rank_bytes of one chunk
 };
-GribChunkPlan plan_grib_chunks(const smm_grib_row_t* rows, int64_t n_batch, int64_t n_src, int64_t D,
-                               int64_t requested_rows, size_t free_bytes);
-
-// ---- the same with bitmaps (smm_apply_grib_bm / smm_apply_host_grib_bm; bitmaps is never null here).
-// check_grib_bitmaps stands where check_grib_ranges stands: n_values <= n_src in every row; a bitmapped row's
-// ceil(n_src / 8) bitmap bytes and its ceil(n_values * nbits / 8) data bytes inside [0, x_bytes); a row without a bitmap
-// as check_grib_ranges has it.
-bool check_grib_bitmaps(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_batch, int64_t n_src,
-                        int64_t x_bytes, std::string& err);
-// Bytes a row stages through smm_apply_host_grib_bm: its table record (40), its bitmap record (16), its data bytes and,
-// with a bitmap, its bitmap bytes, each rounded up to 4 -- and what it takes of the device-only rank buffer: one 8-byte
-// entry per 32 cells when it has a bitmap, and its 4-byte segment totals.
-size_t grib_bm_row_staged(const smm_grib_row_t& row, const smm_grib_bitmap_t& bm, int64_t n_src);
-size_t grib_bm_row_rank(const smm_grib_bitmap_t& bm, int64_t n_src);
-// plan_grib_chunks with those costs: staged bytes, rank bytes and Y of a chunk against the same target.
-GribChunkPlan plan_grib_chunks_bm(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_batch,
-                                  int64_t n_src, int64_t D, int64_t requested_rows, size_t free_bytes);
-
-// ---- smm_group_apply_host_grib: chunks of whole outer indices.  The n_outer * unit records (unit = n_lev * n_inner rows
-// per outer index, consecutive in the table) are chunked in units: r0 and nr of every chunk are multiples of `unit`.
-// bitmaps may be null (no row has one: 40 B of table and align4(ceil(n_src * nbits / 8)) data bytes per row); else the
-// costs of plan_grib_chunks_bm.  Y costs rows * D * 8; the byte bound and the free-memory clamp are plan_grib_chunks_bm's.
-// A chunk holds at least one unit even when that unit alone exceeds the bound; requested_units > 0 fixes the units per
-// chunk (the last may be short).  n_outer <= 0 or unit <= 0: no chunks.
-GribChunkPlan plan_grib_chunks_units(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_outer,
-                                     int64_t unit, int64_t n_src, int64_t D, int64_t requested_units, size_t free_bytes);
+GribChunkPlan plan_grib_chunks(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_outer, int64_t unit,
+                               int64_t n_src, int64_t D, int64_t requested_units, size_t free_bytes);
+// Where a chunk's pieces lie in its staging buffer hx (ch.x_bytes bytes, 8-byte aligned), written into hx: the table first
+// -- the rows' records with byte_off the staged offset of the row's data -- then, with bitmaps, their records
+// (GribRowBitmap, smm_grib_codec.hpp: bitmap_off a staged offset too, table_off the place of the row's rank table among
+// the chunk's: its number among the bitmapped rows x ceil(n_src / 32)), then row by row the room for the data and, behind
+// it, for the row's own copy of its bitmap.  Only the records are written; the caller copies the bytes.
+struct GribChunkLayout {
+  size_t end = 0;        // first byte behind the last piece: ch.x_bytes
+  size_t n_tables = 0;   // bitmapped rows of the chunk
+};
+GribChunkLayout layout_grib_chunk(char* hx, const GribChunk& ch, const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps,
+                                  int64_t n_src);
 
 }  // namespace smm

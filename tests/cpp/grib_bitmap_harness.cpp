@@ -1,7 +1,7 @@
 // Stand-alone check of the bitmap code of smm_apply_grib_bm that needs no device, built with
 // -fsanitize=address,undefined by tests/test_grib_bitmap_harness.py: bitmap_block / bitmap_present / bitmap_index of
 // smm_grib_codec.hpp -- the very functions the table build and the gather run -- against a bit-by-bit loop, and
-// check_grib_bitmaps / plan_grib_chunks_bm of smm_grib_plan.cpp.  Prints "<NAME>BAD <count> ..." lines; 0 is a pass.
+// check_grib_ranges / plan_grib_chunks of smm_grib_plan.cpp with bitmap records.  Prints "<NAME>BAD <count> ..." lines; 0 is a pass.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -103,31 +103,31 @@ int checks_bad() {
   // bitmap: 20 values of 12 bits = 30 B at 27; row 2: no value at all, data "at" the end, bitmap shared with row 0
   std::vector<smm_grib_row_t> r = {row(0, 16), row(27, 12), row(57, 16)};
   std::vector<smm_grib_bitmap_t> m = {bm(24, 12), bm(NO, 20), bm(24, 0)};
-  bad += !smm::check_grib_bitmaps(r.data(), m.data(), 3, 20, 57, err);
-  bad += smm::check_grib_bitmaps(r.data(), m.data(), 3, 20, 56, err);                 // row 1 ends at 57
+  bad += !smm::check_grib_ranges(r.data(), m.data(), 3, 20, 57, err);
+  bad += smm::check_grib_ranges(r.data(), m.data(), 3, 20, 56, err);                 // row 1 ends at 57
   m[0].n_values = 21;                                                                    // more values than cells
-  bad += smm::check_grib_bitmaps(r.data(), m.data(), 3, 20, 57, err) || err.find("n_values") == std::string::npos ||
+  bad += smm::check_grib_ranges(r.data(), m.data(), 3, 20, 57, err) || err.find("n_values") == std::string::npos ||
          err.find("rows[0]") == std::string::npos;
   m[0].n_values = 12;
   m[1].n_values = 21;                                                                    // ... in a row without a bitmap too
-  bad += smm::check_grib_bitmaps(r.data(), m.data(), 3, 20, 57, err) || err.find("rows[1]") == std::string::npos;
+  bad += smm::check_grib_ranges(r.data(), m.data(), 3, 20, 57, err) || err.find("rows[1]") == std::string::npos;
   m[1].n_values = 20;
   m[2].bitmap_off = 55;                                                                  // 55 + 3 = 58 > 57
-  bad += smm::check_grib_bitmaps(r.data(), m.data(), 3, 20, 57, err) || err.find("bitmap") == std::string::npos ||
+  bad += smm::check_grib_ranges(r.data(), m.data(), 3, 20, 57, err) || err.find("bitmap") == std::string::npos ||
          err.find("leave the buffer") == std::string::npos;
   m[2].bitmap_off = 54;                                                                  // ends exactly at x_bytes
-  bad += !smm::check_grib_bitmaps(r.data(), m.data(), 3, 20, 57, err);
+  bad += !smm::check_grib_ranges(r.data(), m.data(), 3, 20, 57, err);
   m[2].bitmap_off = ~0ull - 1;                                                           // no wrap-around
-  bad += smm::check_grib_bitmaps(r.data(), m.data(), 3, 20, 57, err);
+  bad += smm::check_grib_ranges(r.data(), m.data(), 3, 20, 57, err);
   m[2].bitmap_off = 24;
   m[0].n_values = 13;                                                                    // 26 B of data: still inside
-  bad += !smm::check_grib_bitmaps(r.data(), m.data(), 3, 20, 57, err);
+  bad += !smm::check_grib_ranges(r.data(), m.data(), 3, 20, 57, err);
   r[0].byte_off = 32;                                                                    // 32 + 26 = 58: the n_values-based range
-  bad += smm::check_grib_bitmaps(r.data(), m.data(), 3, 20, 57, err) || err.find("rows[0]") == std::string::npos ||
+  bad += smm::check_grib_ranges(r.data(), m.data(), 3, 20, 57, err) || err.find("rows[0]") == std::string::npos ||
          err.find("leave the buffer") == std::string::npos;
   m[0].n_values = 12;                                                                    // 32 + 24 = 56: inside again, where
-  bad += !smm::check_grib_bitmaps(r.data(), m.data(), 3, 20, 57, err);                // 20 values (40 B) would not be
-  bad += smm::check_grib_ranges(r.data(), 1, 20, 57, err);
+  bad += !smm::check_grib_ranges(r.data(), m.data(), 3, 20, 57, err);                // 20 values (40 B) would not be
+  bad += smm::check_grib_ranges(r.data(), nullptr, 1, 20, 57, err);
   return bad;
 }
 
@@ -165,34 +165,34 @@ int plan_bad(int* multi_row_plans, int* single_over_target, int* rank_counted) {
   const int64_t S = 6599680, D = 786432;
   std::vector<smm_grib_row_t> rows(128, row(0, 16));
   std::vector<smm_grib_bitmap_t> bms(128, bm(0, (uint64_t)(0.7 * S)));
-  smm::GribChunkPlan p = smm::plan_grib_chunks_bm(rows.data(), bms.data(), 128, S, D, 0, (size_t)200 << 30);
+  smm::GribChunkPlan p = smm::plan_grib_chunks(rows.data(), bms.data(), 128, 1, S, D, 0, (size_t)200 << 30);
   bad += plan_ok(p, rows, bms, S, D, 0) || p.target > 256 * MiB || p.target < 32 * MiB || p.chunks.size() < 8;
   *multi_row_plans += p.max_rows > 1;
   // the table bytes count: the same rows without bitmaps (and so with all their values) make another plan
   std::vector<smm_grib_bitmap_t> none(128, bm(NO, (uint64_t)S));
-  smm::GribChunkPlan q = smm::plan_grib_chunks_bm(rows.data(), none.data(), 128, S, D, 0, (size_t)200 << 30);
+  smm::GribChunkPlan q = smm::plan_grib_chunks(rows.data(), none.data(), 128, 1, S, D, 0, (size_t)200 << 30);
   bad += plan_ok(q, rows, none, S, D, 0) || q.max_rank != 0;
   *rank_counted += p.max_rank > 0 && p.chunks[0].rank_bytes == (size_t)p.chunks[0].nr * (206240 * 8 + 202 * 4);
-  // without bitmaps the plan is plan_grib_chunks' with 16 B more per row
-  smm::GribChunkPlan o = smm::plan_grib_chunks(rows.data(), 128, S, D, 0, (size_t)200 << 30);
+  // without bitmaps the plan is that of the call without records, with 16 B more per row
+  smm::GribChunkPlan o = smm::plan_grib_chunks(rows.data(), nullptr, 128, 1, S, D, 0, (size_t)200 << 30);
   bad += o.chunks.size() != q.chunks.size() || q.chunks[0].x_bytes != o.chunks[0].x_bytes + 16 * (size_t)o.chunks[0].nr;
   // mixed: every other row bitmapped, widths mixed, 0-bit rows
   for (size_t b = 0; b < rows.size(); ++b) {
     rows[b].nbits = (b % 4 == 0) ? 0 : (b % 4 == 1 ? 12 : (b % 4 == 2 ? 24 : 7));
     if (b % 2) bms[b] = bm(NO, (uint64_t)S);
   }
-  p = smm::plan_grib_chunks_bm(rows.data(), bms.data(), 128, S, 1000, 0, 0);
+  p = smm::plan_grib_chunks(rows.data(), bms.data(), 128, 1, S, 1000, 0, 0);
   bad += plan_ok(p, rows, bms, S, 1000, 0);
   // a fat row gets a chunk of one; free memory bounds the target
   std::vector<smm_grib_row_t> fat(3, row(0, 32));
   std::vector<smm_grib_bitmap_t> fatbm(3, bm(0, 90000000));
-  p = smm::plan_grib_chunks_bm(fat.data(), fatbm.data(), 3, 100000000, 5, 0, 64 * MiB);
+  p = smm::plan_grib_chunks(fat.data(), fatbm.data(), 3, 1, 100000000, 5, 0, 64 * MiB);
   bad += plan_ok(p, fat, fatbm, 100000000, 5, 0) || p.chunks.size() != 3 || p.target != 8 * MiB;
   *single_over_target += p.chunks[0].x_bytes > p.target;
   // chunk_rows overrides
-  p = smm::plan_grib_chunks_bm(rows.data(), bms.data(), 128, S, D, 5, 0);
+  p = smm::plan_grib_chunks(rows.data(), bms.data(), 128, 1, S, D, 5, 0);
   bad += plan_ok(p, rows, bms, S, D, 5) || p.chunks.size() != 26 || p.chunks.back().nr != 3 || p.target != 0;
-  p = smm::plan_grib_chunks_bm(rows.data(), bms.data(), 0, S, D, 0, 0);
+  p = smm::plan_grib_chunks(rows.data(), bms.data(), 0, 1, S, D, 0, 0);
   bad += !p.chunks.empty();
   // a seeded sweep
   std::mt19937_64 rng(11);
@@ -206,7 +206,7 @@ int plan_bad(int* multi_row_plans, int* single_over_target, int* rank_counted) {
     }
     const int64_t req = (it % 3 == 0) ? 1 + (int64_t)(rng() % 9) : 0;
     const size_t free_b = (it % 5 == 0) ? (size_t)(rng() % (8ull << 30)) : 0;
-    p = smm::plan_grib_chunks_bm(rr.data(), bb.data(), n, s, d, req, free_b);
+    p = smm::plan_grib_chunks(rr.data(), bb.data(), n, 1, s, d, req, free_b);
     bad += plan_ok(p, rr, bb, s, d, req);
     *multi_row_plans += p.max_rows > 1;
   }

@@ -99,14 +99,14 @@ int checks_bad() {
   std::vector<smm_grib_row_t> r = {row(0, 16), row(3, 12), row(40, 0)};
   bad += !smm::check_grib_rules(r.data(), 3, err);
   // 10 values: 20 B at 16 bits from 0, 15 B at 12 bits from 3, nothing at 0 bits from 40 = x_bytes
-  bad += !smm::check_grib_ranges(r.data(), 3, 10, 40, err);
-  bad += smm::check_grib_ranges(r.data(), 3, 10, 39, err);            // the 0-bit row starts past the end
+  bad += !smm::check_grib_ranges(r.data(), nullptr, 3, 10, 40, err);
+  bad += smm::check_grib_ranges(r.data(), nullptr, 3, 10, 39, err);            // the 0-bit row starts past the end
   r[1].byte_off = 26;                                                  // 26 + 15 = 41 > 40
-  bad += smm::check_grib_ranges(r.data(), 3, 10, 40, err) || err.find("rows[1]") == std::string::npos;
+  bad += smm::check_grib_ranges(r.data(), nullptr, 3, 10, 40, err) || err.find("rows[1]") == std::string::npos;
   r[1].byte_off = 25;                                                  // ends exactly at x_bytes
-  bad += !smm::check_grib_ranges(r.data(), 3, 10, 40, err);
+  bad += !smm::check_grib_ranges(r.data(), nullptr, 3, 10, 40, err);
   r[1].byte_off = ~0ull - 3;                                           // no wrap-around
-  bad += smm::check_grib_ranges(r.data(), 3, 10, 40, err);
+  bad += smm::check_grib_ranges(r.data(), nullptr, 3, 10, 40, err);
   r[1] = row(0, 33);
   bad += smm::check_grib_rules(r.data(), 3, err) || err.find("nbits") == std::string::npos;
   r[1] = row(0, 8);
@@ -153,28 +153,28 @@ int plan_bad(int* multi_row_chunks, int* single_over_target) {
   const size_t MiB = (size_t)1 << 20;
   // config-4 geometry: 6.6 M source cells at 16 bits, 786432 target cells, 128 rows: 13 MB + 6 MB per row
   std::vector<smm_grib_row_t> rows(128, row(0, 16));
-  smm::GribChunkPlan p = smm::plan_grib_chunks(rows.data(), 128, 6599680, 786432, 0, (size_t)200 << 30);
+  smm::GribChunkPlan p = smm::plan_grib_chunks(rows.data(), nullptr, 128, 1, 6599680, 786432, 0, (size_t)200 << 30);
   bad += plan_ok(p, rows, 6599680, 786432, 0);
   bad += p.target > 256 * MiB || p.target < 32 * MiB || p.chunks.size() < 8;
   *multi_row_chunks += p.max_rows > 1;
   // mixed widths with 0-bit rows: a chunk is sized by bytes, so the thin rows gather in long chunks
   for (size_t b = 0; b < rows.size(); ++b) rows[b].nbits = (b % 4 == 0) ? 0 : (b % 4 == 1 ? 12 : (b % 4 == 2 ? 24 : 7));
-  p = smm::plan_grib_chunks(rows.data(), 128, 6599680, 1000, 0, 0);
+  p = smm::plan_grib_chunks(rows.data(), nullptr, 128, 1, 6599680, 1000, 0, 0);
   bad += plan_ok(p, rows, 6599680, 1000, 0);
   std::vector<smm_grib_row_t> thin(1000, row(0, 0));
-  p = smm::plan_grib_chunks(thin.data(), 1000, 6599680, 10, 0, 0);
+  p = smm::plan_grib_chunks(thin.data(), nullptr, 1000, 1, 6599680, 10, 0, 0);
   bad += plan_ok(p, thin, 6599680, 10, 0) || p.chunks.size() != 1 || p.chunks[0].x_bytes != 40000;
   // a single row larger than the target still gets a chunk of one; free memory bounds the target
   std::vector<smm_grib_row_t> fat(3, row(0, 32));
-  p = smm::plan_grib_chunks(fat.data(), 3, 100000000, 5, 0, 64 * MiB);      // 400 MB per row, target 8 MiB
+  p = smm::plan_grib_chunks(fat.data(), nullptr, 3, 1, 100000000, 5, 0, 64 * MiB);      // 400 MB per row, target 8 MiB
   bad += plan_ok(p, fat, 100000000, 5, 0) || p.chunks.size() != 3 || p.target != 8 * MiB;
   *single_over_target += p.chunks[0].x_bytes > p.target;
   // chunk_rows overrides the plan
-  p = smm::plan_grib_chunks(rows.data(), 128, 6599680, 786432, 5, 0);
+  p = smm::plan_grib_chunks(rows.data(), nullptr, 128, 1, 6599680, 786432, 5, 0);
   bad += plan_ok(p, rows, 6599680, 786432, 5) || p.chunks.size() != 26 || p.chunks.back().nr != 3;
-  p = smm::plan_grib_chunks(rows.data(), 7, 100, 50, 1000, 0);
+  p = smm::plan_grib_chunks(rows.data(), nullptr, 7, 1, 100, 50, 1000, 0);
   bad += plan_ok(p, std::vector<smm_grib_row_t>(rows.begin(), rows.begin() + 7), 100, 50, 1000) || p.chunks.size() != 1;
-  p = smm::plan_grib_chunks(rows.data(), 0, 100, 50, 0, 0);
+  p = smm::plan_grib_chunks(rows.data(), nullptr, 0, 1, 100, 50, 0, 0);
   bad += !p.chunks.empty();
   // a seeded sweep
   std::mt19937_64 rng(7);
@@ -184,7 +184,7 @@ int plan_bad(int* multi_row_chunks, int* single_over_target) {
     for (auto& q : rr) q = row(0, (int)(rng() % 33));
     const int64_t req = (it % 3 == 0) ? 1 + (int64_t)(rng() % 9) : 0;
     const size_t free_b = (it % 5 == 0) ? (size_t)(rng() % (8ull << 30)) : 0;
-    p = smm::plan_grib_chunks(rr.data(), n, S, D, req, free_b);
+    p = smm::plan_grib_chunks(rr.data(), nullptr, n, 1, S, D, req, free_b);
     bad += plan_ok(p, rr, S, D, req);
     *multi_row_chunks += p.max_rows > 1;
   }

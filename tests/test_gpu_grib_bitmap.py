@@ -494,3 +494,49 @@ def test_the_old_entry_keeps_its_bits_between_bm_calls(hip):
     stream.synchronize()
     for i, (y, want) in enumerate(ys):
         same_bits(y.to_host(), want, f"interleaved call {i}")
+
+
+# ---------------------------------------------------------------------------------------------- 9: the batch split
+
+def test_a_small_grid_limit_cuts_the_batch(hip):
+    """4050 destination cells are 16 destination blocks, 9 rows at 4 rows per thread 3 batch tiles: 48 workgroups.  A limit
+    of 20 cuts the 9 rows into parts of 2, 1, 2 and 4 rows, 16 leaves one batch tile per launch, and 15 is below the 16
+    destination blocks of a single row.  The host entry cuts each chunk's launch alike: chunk_rows=4 gives chunks that
+    fit as they are, chunk_rows=0 one chunk of all 9 rows.  Once with bitmaps (the BM gather and its rank tables, whose
+    records move with the parts), once without (the plain gather)."""
+    name = "bil_r180x90_r90x45"
+    rng = np.random.default_rng(90)
+    op = operator(name)[0]
+    S = op.n_src
+    assert (op.n_dst + 255) // 256 == 16
+    specs = random_bitmaps(rng, grib_cases.row_specs(rng, S, 9, (16, 12, 7, 25, 0, 32, 17), D=(0, 1)), S)
+    for b in (1, 4, 6):
+        specs[b]["bitmap"] = None
+    buf, rows, bitmaps, field = build_bm(specs, rng, tail_residue=3)
+    pbuf, prows, pfield = grib_cases.build(grib_cases.row_specs(rng, S, 9, (16, 12, 7, 24), D=(0, 2)), rng)
+    assert sorted(np.flatnonzero(bitmaps["bitmap_off"] == GRIB_NO_BITMAP).tolist()) == [1, 4, 6]
+    kw = dict(masked=True, remap_area_min=0.5)
+    cases = []
+    for b, r, bm, f in ((buf, rows, bitmaps, field), (pbuf, prows, None, pfield)):
+        x = device_bytes(b)
+        want = op.apply_grib(x, r, x_bytes=b.size, bitmaps=bm, **kw).to_host()   # the unlimited run of the same call
+        same_bits(want, expected_bm(name, f, True, 0.5), "no limit")
+        cases.append((b, x, r, bm, want))
+    try:
+        for limit in (20, 16):
+            _lib.call("smm_debug_set_grid_limit", limit)
+            for b, x, r, bm, want in cases:
+                what = f"grid limit {limit}, bitmaps={bm is not None}"
+                same_bits(op.apply_grib(x, r, x_bytes=b.size, bitmaps=bm, **kw).to_host(), want, what)
+                for chunk_rows in (4, 0):
+                    same_bits(op.apply_host_grib(b, r, chunk_rows=chunk_rows, bitmaps=bm, **kw), want,
+                              f"{what}, host chunk_rows={chunk_rows}")
+        _lib.call("smm_debug_set_grid_limit", 15)
+        for b, x, r, bm, want in cases:
+            with pytest.raises(_lib.SmmError, match="launch grid beyond 15 workgroups") as err:
+                op.apply_grib(x, r, x_bytes=b.size, bitmaps=bm, **kw)
+            assert err.value.code == _lib.SMM_ERR_INVALID
+    finally:
+        _lib.call("smm_debug_set_grid_limit", 0)
+    for b, x, r, bm, want in cases:
+        same_bits(op.apply_grib(x, r, x_bytes=b.size, bitmaps=bm, **kw).to_host(), want, "limit restored")
