@@ -446,8 +446,8 @@ int smm_apply_host_pk(smm_operator_t op,
  *                        device: a quarter in all); chunk_rows > 0 fixes the rows per chunk.
  *                        SMM_HOST_STAT_H2D_BYTES counts the staged bytes with their <= 3 B pads and the tables.
  * y_dtype must be SMM_F64 (else SMM_ERR_UNSUPPORTED).  SMM_APPLY_MASKED and SMM_APPLY_NO_FILL work as for float fields,
- * SMM_APPLY_KERNEL_SELL is accepted (it is the kernel that runs); SMM_APPLY_SKIPNA, SMM_APPLY_KERNEL_TILE and the
- * batch-fastest / host-pack flags are SMM_ERR_UNSUPPORTED.  SMM_ERR_INVALID, before any device is touched: flag bits
+ * SMM_APPLY_KERNEL_SELL is accepted (it is the kernel that runs); SMM_APPLY_SKIPNA (its form of these entries is the _na
+ * pair below), SMM_APPLY_KERNEL_TILE and the batch-fastest / host-pack flags are SMM_ERR_UNSUPPORTED.  SMM_ERR_INVALID, before any device is touched: flag bits
  * outside the set, null pointers, a negative n_batch, ldy < n_dst, a misaligned x (device entry) or y, nbits outside
  * 0..32, reserved != 0, a bscale that is not a normal power of two, a ddiv that is not finite or <= 0, a non-finite ref,
  * a row whose [byte_off, byte_off + ceil(n_src * nbits / 8)) leaves [0, x_bytes).  The rules are checked before the
@@ -493,6 +493,25 @@ int smm_apply_grib_bm(smm_operator_t op, const void* x, int64_t x_bytes, const s
                       const smm_grib_bitmap_t* bitmaps /* host, or NULL */, void* y, int y_dtype, int64_t ldy,
                       int64_t n_batch, double remap_area_min, unsigned flags, void* stream);
 int smm_apply_host_grib_bm(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                           const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t ldy,
+                           int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows);
+
+/*
+ * The SMM_APPLY_SKIPNA form of the two _bm entries above, with their argument lists (`bitmaps` may be NULL): the bit is
+ * implied and may be passed.  The gather hands every value to the sum raw -- no 1e20 fill; a cell whose bitmap bit is 0
+ * is the float32 NaN, a value whose rule overflows float32 is the infinity the decode gives -- and the kernel applies
+ * the SMM_APPLY_SKIPNA rule above (num / den / tot per destination row, the area test on frac_d * r).  The result: the
+ * bits of smm_apply with SMM_APPLY_SKIPNA | SMM_APPLY_KERNEL_SELL on the float32 field a host decode gives, NaN where
+ * the bitmap is 0.  Staging, chunks, rank tables and the splits of oversized grids are those of the twins.
+ * Refusals, in this order: flag bits outside the set, and SMM_APPLY_NO_FILL (the SKIPNA rule above): SMM_ERR_INVALID;
+ * SMM_APPLY_KERNEL_TILE and the batch-fastest / host-pack flags, then y_dtype != SMM_F64: SMM_ERR_UNSUPPORTED; after
+ * that everything the twins refuse, as they refuse it (remap_area_min > 0 without dst_frac and SMM_APPLY_MASKED without
+ * dst_imask are SMM_ERR_INVALID, as for smm_apply with SMM_APPLY_SKIPNA).
+ */
+int smm_apply_grib_na(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows /* host */,
+                      const smm_grib_bitmap_t* bitmaps /* host, or NULL */, void* y, int y_dtype, int64_t ldy,
+                      int64_t n_batch, double remap_area_min, unsigned flags, void* stream);
+int smm_apply_host_grib_na(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
                            const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t ldy,
                            int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows);
 
@@ -641,6 +660,26 @@ int smm_group_apply_host_grib(smm_group_t g, const void* x_host, int64_t x_bytes
                               int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose,
                               const int32_t* level_index, const uint8_t* masked_levels,
                               double remap_area_min, unsigned flags, int64_t chunk_outer);
+
+/*
+ * The SMM_APPLY_SKIPNA form of the two group entries above, with their argument lists (`bitmaps` may be NULL), as
+ * smm_apply_grib_na is the form of smm_apply_grib_bm: the bit is implied and may be passed, every level renormalises
+ * over its valid source values with its own member, mask switch and dst_frac, and the result has the bits of
+ * smm_group_apply / smm_group_apply_host with SMM_APPLY_SKIPNA | SMM_APPLY_KERNEL_SELL on the float32 field a host
+ * decode gives, NaN where the bitmap is 0.  Refusals in the order of smm_apply_grib_na, then those of the twins.
+ */
+int smm_group_apply_grib_na(smm_group_t g, const void* x, int64_t x_bytes,
+                            const smm_grib_row_t* rows /* host */, const smm_grib_bitmap_t* bitmaps /* host, or NULL */,
+                            void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev, int64_t ys_inner,
+                            int64_t n_outer, int64_t n_lev, int64_t n_inner,
+                            const int32_t* level_index, const uint8_t* masked_levels,
+                            double remap_area_min, unsigned flags, void* stream);
+int smm_group_apply_host_grib_na(smm_group_t g, const void* x_host, int64_t x_bytes,
+                                 const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps,
+                                 void* y_host, int y_dtype,
+                                 int64_t n_outer, int64_t n_lev, int64_t n_inner, int transpose,
+                                 const int32_t* level_index, const uint8_t* masked_levels,
+                                 double remap_area_min, unsigned flags, int64_t chunk_outer);
 
 /*
  * The three group _cf entries with a CF-packed RESULT, with the contract of smm_apply_pk / smm_apply_sb_pk /

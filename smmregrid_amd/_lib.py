@@ -161,6 +161,8 @@ SIGNATURES = {
     "smm_apply_host_grib": [_p, _p, _i64, _grp, _p, _int, _i64, _i64, _dbl, _uint, _i64],
     "smm_apply_grib_bm": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _dbl, _uint, _p],
     "smm_apply_host_grib_bm": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _dbl, _uint, _i64],
+    "smm_apply_grib_na": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _dbl, _uint, _p],
+    "smm_apply_host_grib_na": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _dbl, _uint, _i64],
     "smm_group_apply": [_p, _p, _int, _i64, _i64, _i64, _p, _int, _i64, _i64, _i64,
                         _i64, _i64, _i64, _p, _p, _dbl, _uint, _p],
     "smm_group_prepare_sb": [_p],
@@ -175,6 +177,10 @@ SIGNATURES = {
                              _p],
     "smm_group_apply_host_grib": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _i64, _int, _p, _p, _dbl, _uint,
                                   _i64],
+    "smm_group_apply_grib_na": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _dbl,
+                                _uint, _p],
+    "smm_group_apply_host_grib_na": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _i64, _int, _p, _p, _dbl, _uint,
+                                     _i64],
     "smm_group_apply_pk": [_p, _p, _int, _i64, _i64, _i64, _p, _int, _i64, _i64, _i64,
                            _i64, _i64, _i64, _p, _p, _dbl, _uint, _p, _cfp, _cep],
     "smm_group_apply_sb_pk": [_p, _p, _int, _i64, _i64, _p, _int, _i64, _i64, _i64, _i64, _p, _p, _dbl, _uint, _p,

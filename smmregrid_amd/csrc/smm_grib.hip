@@ -25,10 +25,14 @@ namespace {
 // BT batch rows are rows (o, i) of that one level: row j of the level is record o * rec_o + l * rec_l + i of the row
 // table and the bitmap records -- a block-uniform index like j itself, so the rule stays in scalar registers -- and its
 // results go to y + o * ys_o + l * ys_l + i * ys_i.
+// NA (the _na entries): the SMM_APPLY_SKIPNA rule of include/smmregrid_amd.h as smm_apply_sell_kernel<float, double, BT,
+// true> applies it to the decoded field -- the value goes to a RowSum<float, true> raw (no 1e20 fill; a missing cell is
+// the NaN of the select), tot takes every slot's weight in slot order, and the store is skipna_epilogue with the static
+// mask alone.
 template <bool GRP, bool BM>
 using GribKernelArgs = std::conditional_t<GRP, GribGroupArgs, std::conditional_t<BM, GribBitmapArgs, GribArgs>>;
 
-template <int BT, bool DIV, bool BM, bool GRP = false>
+template <int BT, bool DIV, bool BM, bool GRP = false, bool NA = false>
 __global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(GribKernelArgs<GRP, BM> a, bool fill) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -104,7 +108,8 @@ __global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(GribKernelArgs
   const int32_t* __restrict__ cp = L.col + off + lane;
   const double* __restrict__ vp = L.val + off + lane;
 
-  RowSum<float, false> acc[BT];
+  RowSum<float, NA> acc[BT];
+  [[maybe_unused]] double tot = 0.0;   // NA: the row's weight sum, shared by the BT batch rows
   // padded slots: a valid column and weight +0.0, bitwise no-ops on a finite value (smm_apply_sell_kernel)
 #pragma unroll 2
   for (int k = 0; k < nslots; ++k) {
@@ -126,10 +131,14 @@ __global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(GribKernelArgs
       const uint32_t q = smm_grib::grib_extract(xw[t], p, nbits[t], lastw[t]);
       float v = smm_grib::grib_decode<DIV>(q, ref[t], bscale[t], ddiv[t]);
       if constexpr (BM) v = present ? v : __builtin_nanf("");   // a missing cell: its loads went out, a select drops them
-      xv[t] = (double)((fill && !__builtin_isfinite(v)) ? (float)1e20 : v);
+      if constexpr (NA)
+        xv[t] = (double)v;
+      else
+        xv[t] = (double)((fill && !__builtin_isfinite(v)) ? (float)1e20 : v);
     }
 #pragma unroll
     for (int t = 0; t < BT; ++t) acc[t].add(w, xv[t]);
+    if constexpr (NA) tot = tot + w;
   }
   if (len == 0) {
 #pragma unroll
@@ -139,21 +148,32 @@ __global__ __launch_bounds__(kThreads) void smm_apply_grib_kernel(GribKernelArgs
   if (d < a.n_dst) {
     bool dead = false;
     if (use_mask && L.imask) dead = (L.imask[d] == 0);
-    if (a.area_min > 0.0 && L.frac) dead = dead || (L.frac[d] < a.area_min);
+    [[maybe_unused]] double frac_d = 1.0;
+    if constexpr (NA) {
+      if (L.frac) frac_d = L.frac[d];   // the area test is skipna_epilogue's
+    } else {
+      if (a.area_min > 0.0 && L.frac) dead = dead || (L.frac[d] < a.area_min);
+    }
+    auto finish = [&](const RowSum<float, NA>& s) -> double {
+      if constexpr (NA)
+        return skipna_epilogue(s.num, s.den, s.inv, tot, dead, L.frac != nullptr, frac_d, a.area_min);
+      else
+        return epilogue(s.num, dead);
+    };
     if constexpr (GRP) {
       go = go0, gi = gi0;
 #pragma unroll
       for (int t = 0; t < BT; ++t) {
         if (j0 + t < a.n_j) {
           double* __restrict__ yrow = a.y + ((int64_t)go * a.ys_o + l * a.ys_l + (int64_t)gi * a.ys_i);
-          yrow[d] = epilogue(acc[t].num, dead);
+          yrow[d] = finish(acc[t]);
           if (++gi == (uint32_t)a.n_inner) gi = 0, ++go;
         }
       }
     } else {
 #pragma unroll
       for (int t = 0; t < BT; ++t) {
-        if (j0 + t < a.n_j) yr[t][d] = epilogue(acc[t].num, dead);
+        if (j0 + t < a.n_j) yr[t][d] = finish(acc[t]);
       }
     }
   }
@@ -260,39 +280,43 @@ namespace smm_launch {
 namespace {
 // n_lev: the levels of a grouped launch (GribGroupArgs), 1 for the operator entries
 template <bool BM, bool GRP, class Args>
-int launch_grib_any(const Args& a, int64_t n_lev, bool div, bool fill, hipStream_t s) {
+int launch_grib_any(const Args& a, int64_t n_lev, bool div, bool na, bool fill, hipStream_t s) {
   Args args = a;
-  auto go = [&](auto bt_tag, auto div_tag) -> int {
+  auto go = [&](auto bt_tag, auto div_tag, auto na_tag) -> int {
     constexpr int BT = decltype(bt_tag)::value;
     args.n_jtiles = (a.n_j + BT - 1) / BT;
     const int64_t total = args.n_dblocks * args.n_jtiles * n_lev;
     if (total <= 0) return SMM_OK;
     if (total > 0x7fffffffLL) return smm::fail_msg(SMM_ERR_INVALID, "launch grid exceeds 2^31-1 blocks");
-    hipLaunchKernelGGL((smm_apply_grib_kernel<BT, decltype(div_tag)::value, BM, GRP>), dim3((unsigned)total),
-                       dim3(kThreads), 0, s, args, fill);
+    hipLaunchKernelGGL((smm_apply_grib_kernel<BT, decltype(div_tag)::value, BM, GRP, decltype(na_tag)::value>),
+                       dim3((unsigned)total), dim3(kThreads), 0, s, args, fill);
     SMM_LAUNCH_HIP(hipGetLastError());
     return SMM_OK;
   };
-  auto with_bt = [&](auto div_tag) -> int {
+  auto with_bt = [&](auto div_tag, auto na_tag) -> int {
     switch (sell_batch_rows(a.n_j)) {   // as launch_sell: 4 rows per thread, SMM_TUNE_SELL_BATCH_ROWS asks for 8 or 2
-      case 8: return go(std::integral_constant<int, 8>(), div_tag);
-      case 4: return go(std::integral_constant<int, 4>(), div_tag);
-      case 2: return go(std::integral_constant<int, 2>(), div_tag);
-      default: return go(std::integral_constant<int, 1>(), div_tag);
+      case 8: return go(std::integral_constant<int, 8>(), div_tag, na_tag);
+      case 4: return go(std::integral_constant<int, 4>(), div_tag, na_tag);
+      case 2: return go(std::integral_constant<int, 2>(), div_tag, na_tag);
+      default: return go(std::integral_constant<int, 1>(), div_tag, na_tag);
     }
   };
-  return div ? with_bt(std::true_type()) : with_bt(std::false_type());
+  auto with_div = [&](auto na_tag) -> int {
+    return div ? with_bt(std::true_type(), na_tag) : with_bt(std::false_type(), na_tag);
+  };
+  return na ? with_div(std::true_type()) : with_div(std::false_type());
 }
 }  // namespace
 
-int launch_grib(const GribArgs& a, bool div, bool fill, hipStream_t s) {
-  return launch_grib_any<false, false>(a, 1, div, fill, s);
+int launch_grib(const GribArgs& a, bool div, bool na, bool fill, hipStream_t s) {
+  return launch_grib_any<false, false>(a, 1, div, na, fill, s);
 }
-int launch_grib_bitmap(const GribBitmapArgs& a, bool div, bool fill, hipStream_t s) {
-  return launch_grib_any<true, false>(a, 1, div, fill, s);
+int launch_grib_bitmap(const GribBitmapArgs& a, bool div, bool na, bool fill, hipStream_t s) {
+  return launch_grib_any<true, false>(a, 1, div, na, fill, s);
 }
-int launch_grib_group(const GribGroupArgs& a, int64_t n_lev, bool bitmaps, bool div, bool fill, hipStream_t s) {
-  return bitmaps ? launch_grib_any<true, true>(a, n_lev, div, fill, s) : launch_grib_any<false, true>(a, n_lev, div, fill, s);
+int launch_grib_group(const GribGroupArgs& a, int64_t n_lev, bool bitmaps, bool div, bool na, bool fill, hipStream_t s) {
+  return bitmaps ? launch_grib_any<true, true>(a, n_lev, div, na, fill, s)
+                 : launch_grib_any<false, true>(a, n_lev, div, na, fill, s);
 }
 
 int launch_grib_build(const GribBuildArgs& a, hipStream_t s) {

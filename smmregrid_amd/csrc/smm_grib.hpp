@@ -52,12 +52,13 @@ struct GribBuildArgs {
 };
 
 namespace smm_launch {
-// div: some row of the call has ddiv != 1.0 (the instantiation with the f64 division); fill: the 1e20 fill is on
-int launch_grib(const GribArgs& a, bool div, bool fill, hipStream_t s);
+// div: some row of the call has ddiv != 1.0 (the instantiation with the f64 division); na: the SMM_APPLY_SKIPNA rule
+// (the NA instantiations, which take the values raw whatever fill says); fill: the 1e20 fill is on
+int launch_grib(const GribArgs& a, bool div, bool na, bool fill, hipStream_t s);
 // the gather that consults the rank tables (rows without a bitmap take rank = c on a block-uniform branch) ...
-int launch_grib_bitmap(const GribBitmapArgs& a, bool div, bool fill, hipStream_t s);
+int launch_grib_bitmap(const GribBitmapArgs& a, bool div, bool na, bool fill, hipStream_t s);
 // the grouped gather over n_lev levels (grid = destination blocks x batch tiles x levels); bitmaps: a.bm / a.table are set
-int launch_grib_group(const GribGroupArgs& a, int64_t n_lev, bool bitmaps, bool div, bool fill, hipStream_t s);
+int launch_grib_group(const GribGroupArgs& a, int64_t n_lev, bool bitmaps, bool div, bool na, bool fill, hipStream_t s);
 // ... and the two kernels that fill the rank tables, in stream order ahead of it: segment totals, then the scan
 int launch_grib_build(const GribBuildArgs& a, hipStream_t s);
 }

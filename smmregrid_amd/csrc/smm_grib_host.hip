@@ -1,18 +1,23 @@
 // GRIB simple-packed fields shipped raw: the host side of smm_apply_grib(_bm), smm_apply_host_grib(_bm),
-// smm_group_apply_grib and smm_group_apply_host_grib.  The kernels and their launchers are in smm_grib.hip; what needs no
+// smm_group_apply_grib and smm_group_apply_host_grib, and of their four SMM_APPLY_SKIPNA twins (_na).  The kernels and their launchers are in smm_grib.hip; what needs no
 // device -- the refusals of a row table, the chunk plan and the layout of a staged chunk -- in smm_grib_plan.cpp.  An
 // operator and a group differ in how a launch grid is cut into parts and in where Y goes; everything else is written once.
 #include "smm_device.hpp"
 
 namespace {
 
-// Everything the entries refuse before the handle is looked at and before any device is touched.
+// Everything the entries refuse before the handle is looked at and before any device is touched.  na: a _na entry -- on
+// return *flags_io carries SMM_APPLY_SKIPNA, which those entries imply (so SMM_APPLY_NO_FILL is check_flags' refusal) and
+// the others refuse.
 int check_grib_call(const void* x, bool x_device, int64_t x_bytes, const smm_grib_row_t* rows, const void* y, int y_dtype,
-                    int64_t n_batch, double area_min, unsigned flags) {
+                    int64_t n_batch, double area_min, unsigned* flags_io, bool na) {
+  if (na) *flags_io |= SMM_APPLY_SKIPNA;
+  const unsigned flags = *flags_io;
   if (int frc = check_flags(flags)) return frc;
-  if (flags & ~(unsigned)(SMM_APPLY_MASKED | SMM_APPLY_NO_FILL | SMM_APPLY_KERNEL_SELL))
-    return fail(SMM_ERR_UNSUPPORTED, "GRIB fields run the SELL kernel on whole rows: SMM_APPLY_SKIPNA, SMM_APPLY_KERNEL_TILE "
-                                     "and the batch-fastest / host-pack flags are not built for them");
+  if (flags & ~(unsigned)(SMM_APPLY_MASKED | SMM_APPLY_NO_FILL | SMM_APPLY_KERNEL_SELL | (na ? SMM_APPLY_SKIPNA : 0u)))
+    return fail(SMM_ERR_UNSUPPORTED, std::string("GRIB fields run the SELL kernel on whole rows: ") +
+                                         (na ? "" : "SMM_APPLY_SKIPNA, ") + "SMM_APPLY_KERNEL_TILE "
+                                         "and the batch-fastest / host-pack flags are not built for them");
   if (y_dtype != SMM_F64) return fail(SMM_ERR_UNSUPPORTED, "GRIB fields produce SMM_F64 results");
   if (n_batch < 0) return fail(SMM_ERR_INVALID, "negative batch size");
   if (x_bytes < 0) return fail(SMM_ERR_INVALID, "negative x_bytes");
@@ -102,7 +107,7 @@ int launch_grib_rows(smm_operator_t op, const GribIn& in, void* y, int64_t ldy, 
   if (int rc = grib_launch_base(a, &with_tables, in, op->d_desc.get(), op->csr.n_src, op->csr.n_dst, n_batch, area_min, flags, s))
     return rc;
   a.ldy = ldy;
-  const bool fill = !(flags & SMM_APPLY_NO_FILL);
+  const bool fill = !(flags & SMM_APPLY_NO_FILL), na = (flags & SMM_APPLY_SKIPNA) != 0;
   auto blocks_for = [&](int64_t n_o, int64_t) -> int64_t {
     const int bt = smm_launch::sell_batch_rows(n_o);
     return a.n_dblocks * ((n_o + bt - 1) / bt);
@@ -113,10 +118,10 @@ int launch_grib_rows(smm_operator_t op, const GribIn& in, void* y, int64_t ldy, 
     p.rows = in.rows + o0;
     p.y = (double*)y + o0 * ldy;
     p.n_j = n_o;
-    if (!with_tables) return smm_launch::launch_grib(p, in.div, fill, s);
+    if (!with_tables) return smm_launch::launch_grib(p, in.div, na, fill, s);
     p.bm = in.bm + o0;
     p.table = (const smm_grib::GribRankEntry*)in.rank;
-    return smm_launch::launch_grib_bitmap(p, in.div, fill, s);
+    return smm_launch::launch_grib_bitmap(p, in.div, na, fill, s);
   };
   const int rc = smm::split_batch(0, n_batch, 0, 1, grid_limit(), blocks_for, launch_part);
   if (rc == -1)
@@ -142,7 +147,7 @@ int launch_grib_group_rows(smm_group_t g, const int32_t* d_map, const uint8_t* d
   a.ys_o = ys_o;
   a.ys_l = ys_l;
   a.ys_i = ys_i;
-  const bool fill = !(flags & SMM_APPLY_NO_FILL);
+  const bool fill = !(flags & SMM_APPLY_NO_FILL), na = (flags & SMM_APPLY_SKIPNA) != 0;
   const int64_t limit = grid_limit();
   // the kernel's row indices inside a level are 32-bit: a part of 2^31 rows or more per level counts as too large
   auto blocks_for = [&](int64_t n_o, int64_t n_i, int64_t n_l) -> int64_t {
@@ -163,7 +168,7 @@ int launch_grib_group_rows(smm_group_t g, const int32_t* d_map, const uint8_t* d
       p.bm = in.bm + first;
       p.table = (const smm_grib::GribRankEntry*)in.rank;
     }
-    return smm_launch::launch_grib_group(p, n_l, with_tables, in.div, fill, s);
+    return smm_launch::launch_grib_group(p, n_l, with_tables, in.div, na, fill, s);
   };
   // a part of several rows is cut further while it does not fit; a single row goes to the level split whatever it needs
   const int rc = smm::split_batch(
@@ -409,6 +414,56 @@ int smm_group_apply_host_grib_impl(smm_group_t g, const void* x_host, const smm_
                            is_pinned(y_host), launch_chunk, y_to_host);
 }
 
+// ---- the four entries behind the extern "C" names.  na: the _na twin -- check_grib_call puts SMM_APPLY_SKIPNA into
+// flags, and from there the flag travels with them down to the launch
+int grib_entry(bool na, smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
+               const smm_grib_bitmap_t* bitmaps, void* y, int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min,
+               unsigned flags, void* stream) {
+  return guarded([&] {
+    if (int rc = check_grib_call(x, true, x_bytes, rows, y, y_dtype, n_batch, remap_area_min, &flags, na)) return rc;
+    if (int rc = check_grib_operator(op, x_bytes, rows, bitmaps, ldy, n_batch, remap_area_min, flags)) return rc;
+    return smm_apply_grib_impl(op, x, x_bytes, rows, bitmaps, y, ldy, n_batch, remap_area_min, flags, stream);
+  });
+}
+
+int grib_host_entry(bool na, smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                    const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t ldy, int64_t n_batch,
+                    double remap_area_min, unsigned flags, int64_t chunk_rows) {
+  return guarded([&] {
+    if (int rc = check_grib_call(x_host, false, x_bytes, rows, y_host, y_dtype, n_batch, remap_area_min, &flags, na)) return rc;
+    if (int rc = check_grib_operator(op, x_bytes, rows, bitmaps, ldy, n_batch, remap_area_min, flags)) return rc;
+    return smm_apply_host_grib_impl(op, x_host, rows, bitmaps, y_host, ldy, n_batch, remap_area_min, flags, chunk_rows);
+  });
+}
+
+int grib_group_entry(bool na, smm_group_t g, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
+                     const smm_grib_bitmap_t* bitmaps, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev, int64_t ys_inner,
+                     int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index, const uint8_t* masked_levels,
+                     double remap_area_min, unsigned flags, void* stream) {
+  return guarded([&] {
+    const int64_t n_rows = grib_group_rows(n_outer, n_lev, n_inner);
+    if (int rc = check_grib_call(x, true, x_bytes, rows, y, y_dtype, n_rows, remap_area_min, &flags, na)) return rc;
+    if (int rc = check_grib_group(g, x_bytes, rows, bitmaps, n_rows, n_lev, level_index, masked_levels, remap_area_min, flags))
+      return rc;
+    return smm_group_apply_grib_impl(g, x, x_bytes, rows, bitmaps, y, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner,
+                                     level_index, masked_levels, remap_area_min, flags, stream);
+  });
+}
+
+int grib_group_host_entry(bool na, smm_group_t g, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                          const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t n_outer, int64_t n_lev,
+                          int64_t n_inner, int transpose, const int32_t* level_index, const uint8_t* masked_levels,
+                          double remap_area_min, unsigned flags, int64_t chunk_outer) {
+  return guarded([&] {
+    const int64_t n_rows = grib_group_rows(n_outer, n_lev, n_inner);
+    if (int rc = check_grib_call(x_host, false, x_bytes, rows, y_host, y_dtype, n_rows, remap_area_min, &flags, na)) return rc;
+    if (int rc = check_grib_group(g, x_bytes, rows, bitmaps, n_rows, n_lev, level_index, masked_levels, remap_area_min, flags))
+      return rc;
+    return smm_group_apply_host_grib_impl(g, x_host, rows, bitmaps, y_host, n_outer, n_lev, n_inner, transpose, level_index,
+                                          masked_levels, remap_area_min, flags, chunk_outer);
+  });
+}
+
 }  // namespace
 
 // ---- the guarded entry points (include/smmregrid_amd.h): nothing crosses the extern "C" boundary but a status
@@ -423,11 +478,13 @@ int smm_apply_grib(smm_operator_t op, const void* x, int64_t x_bytes, const smm_
 int smm_apply_grib_bm(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
                       const smm_grib_bitmap_t* bitmaps, void* y, int y_dtype, int64_t ldy, int64_t n_batch,
                       double remap_area_min, unsigned flags, void* stream) {
-  return guarded([&] {
-    if (int rc = check_grib_call(x, true, x_bytes, rows, y, y_dtype, n_batch, remap_area_min, flags)) return rc;
-    if (int rc = check_grib_operator(op, x_bytes, rows, bitmaps, ldy, n_batch, remap_area_min, flags)) return rc;
-    return smm_apply_grib_impl(op, x, x_bytes, rows, bitmaps, y, ldy, n_batch, remap_area_min, flags, stream);
-  });
+  return grib_entry(false, op, x, x_bytes, rows, bitmaps, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream);
+}
+
+int smm_apply_grib_na(smm_operator_t op, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
+                      const smm_grib_bitmap_t* bitmaps, void* y, int y_dtype, int64_t ldy, int64_t n_batch,
+                      double remap_area_min, unsigned flags, void* stream) {
+  return grib_entry(true, op, x, x_bytes, rows, bitmaps, y, y_dtype, ldy, n_batch, remap_area_min, flags, stream);
 }
 
 int smm_apply_host_grib(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows, void* y_host,
@@ -440,39 +497,47 @@ int smm_apply_host_grib(smm_operator_t op, const void* x_host, int64_t x_bytes, 
 int smm_apply_host_grib_bm(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
                            const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t ldy, int64_t n_batch,
                            double remap_area_min, unsigned flags, int64_t chunk_rows) {
-  return guarded([&] {
-    if (int rc = check_grib_call(x_host, false, x_bytes, rows, y_host, y_dtype, n_batch, remap_area_min, flags)) return rc;
-    if (int rc = check_grib_operator(op, x_bytes, rows, bitmaps, ldy, n_batch, remap_area_min, flags)) return rc;
-    return smm_apply_host_grib_impl(op, x_host, rows, bitmaps, y_host, ldy, n_batch, remap_area_min, flags, chunk_rows);
-  });
+  return grib_host_entry(false, op, x_host, x_bytes, rows, bitmaps, y_host, y_dtype, ldy, n_batch, remap_area_min, flags,
+                         chunk_rows);
+}
+
+int smm_apply_host_grib_na(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                           const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t ldy, int64_t n_batch,
+                           double remap_area_min, unsigned flags, int64_t chunk_rows) {
+  return grib_host_entry(true, op, x_host, x_bytes, rows, bitmaps, y_host, y_dtype, ldy, n_batch, remap_area_min, flags,
+                         chunk_rows);
 }
 
 int smm_group_apply_grib(smm_group_t g, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
                          const smm_grib_bitmap_t* bitmaps, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev,
                          int64_t ys_inner, int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index,
                          const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream) {
-  return guarded([&] {
-    const int64_t n_rows = grib_group_rows(n_outer, n_lev, n_inner);
-    if (int rc = check_grib_call(x, true, x_bytes, rows, y, y_dtype, n_rows, remap_area_min, flags)) return rc;
-    if (int rc = check_grib_group(g, x_bytes, rows, bitmaps, n_rows, n_lev, level_index, masked_levels, remap_area_min, flags))
-      return rc;
-    return smm_group_apply_grib_impl(g, x, x_bytes, rows, bitmaps, y, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner,
-                                     level_index, masked_levels, remap_area_min, flags, stream);
-  });
+  return grib_group_entry(false, g, x, x_bytes, rows, bitmaps, y, y_dtype, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner,
+                          level_index, masked_levels, remap_area_min, flags, stream);
+}
+
+int smm_group_apply_grib_na(smm_group_t g, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
+                            const smm_grib_bitmap_t* bitmaps, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev,
+                            int64_t ys_inner, int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index,
+                            const uint8_t* masked_levels, double remap_area_min, unsigned flags, void* stream) {
+  return grib_group_entry(true, g, x, x_bytes, rows, bitmaps, y, y_dtype, ys_outer, ys_lev, ys_inner, n_outer, n_lev, n_inner,
+                          level_index, masked_levels, remap_area_min, flags, stream);
 }
 
 int smm_group_apply_host_grib(smm_group_t g, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
                               const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t n_outer,
                               int64_t n_lev, int64_t n_inner, int transpose, const int32_t* level_index,
                               const uint8_t* masked_levels, double remap_area_min, unsigned flags, int64_t chunk_outer) {
-  return guarded([&] {
-    const int64_t n_rows = grib_group_rows(n_outer, n_lev, n_inner);
-    if (int rc = check_grib_call(x_host, false, x_bytes, rows, y_host, y_dtype, n_rows, remap_area_min, flags)) return rc;
-    if (int rc = check_grib_group(g, x_bytes, rows, bitmaps, n_rows, n_lev, level_index, masked_levels, remap_area_min, flags))
-      return rc;
-    return smm_group_apply_host_grib_impl(g, x_host, rows, bitmaps, y_host, n_outer, n_lev, n_inner, transpose, level_index,
-                                          masked_levels, remap_area_min, flags, chunk_outer);
-  });
+  return grib_group_host_entry(false, g, x_host, x_bytes, rows, bitmaps, y_host, y_dtype, n_outer, n_lev, n_inner, transpose,
+                               level_index, masked_levels, remap_area_min, flags, chunk_outer);
+}
+
+int smm_group_apply_host_grib_na(smm_group_t g, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                                 const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t n_outer,
+                                 int64_t n_lev, int64_t n_inner, int transpose, const int32_t* level_index,
+                                 const uint8_t* masked_levels, double remap_area_min, unsigned flags, int64_t chunk_outer) {
+  return grib_group_host_entry(true, g, x_host, x_bytes, rows, bitmaps, y_host, y_dtype, n_outer, n_lev, n_inner, transpose,
+                               level_index, masked_levels, remap_area_min, flags, chunk_outer);
 }
 
 }  // extern "C"

@@ -333,7 +333,7 @@ class SparseOperator:
         return bitmaps, ctypes.cast(bitmaps.ctypes.data, ctypes.POINTER(_lib.GribBitmapStruct))
 
     def apply_grib(self, x, rows, x_bytes=None, y=None, masked=False, remap_area_min=0.0, flags=0, stream=None,
-                   bitmaps=None):
+                   bitmaps=None, skipna=False):
         """Y = epilogue(fill(decode(X)) . W) for GRIB simple-packed fields resident in HBM as they are on disk
         (smm_apply_grib).  x: a `DeviceArray` of uint8 -- or a raw device pointer with x_bytes -- holding the packed
         bit streams (4-byte aligned; the array -- or the allocation behind a raw pointer -- must cover x_bytes rounded
@@ -343,7 +343,9 @@ class SparseOperator:
         host decode gives.  Returns a (B, D) DeviceArray.
         bitmaps: one `GRIB_BITMAP_DTYPE` record per row (smm_apply_grib_bm) -- where the row's bitmap lies in x, or
         `GRIB_NO_BITMAP`, and how many values its stream holds.  A cell whose bit is 0 is NaN, as the host decode has
-        it; the cell's rank in the stream is looked up in a table built on the device ahead of the gather."""
+        it; the cell's rank in the stream is looked up in a table built on the device ahead of the gather.
+        skipna: renormalise over the valid source values of each row (smm_apply_grib_na) -- the bits of
+        `apply(..., skipna=True, flags=APPLY_KERNEL_SELL)` on the decoded float32 field, NaN where the bitmap is 0."""
         rows, rows_p = self._grib_rows(rows)
         if isinstance(x, DeviceArray):
             if x.dtype != np.uint8:
@@ -361,6 +363,11 @@ class SparseOperator:
         elif y.shape != (n_batch, self.n_dst) or y.dtype != np.float64:
             raise ValueError(f"Y must be a float64 ({n_batch}, {self.n_dst}) DeviceArray")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        if skipna:
+            bitmaps, bm_p = (None, None) if bitmaps is None else self._grib_bitmaps(bitmaps, n_batch)
+            _lib.call("smm_apply_grib_na", self.handle, x_ptr, n_bytes, rows_p, bm_p, _ptr(y), _lib.SMM_F64, self.n_dst,
+                      n_batch, float(remap_area_min), fl, _stream_handle(stream))
+            return y
         if bitmaps is not None:
             bitmaps, bm_p = self._grib_bitmaps(bitmaps, n_batch)
             _lib.call("smm_apply_grib_bm", self.handle, x_ptr, n_bytes, rows_p, bm_p, _ptr(y), _lib.SMM_F64, self.n_dst,
@@ -370,11 +377,13 @@ class SparseOperator:
                   float(remap_area_min), fl, _stream_handle(stream))
         return y
 
-    def apply_host_grib(self, buf, rows, out=None, masked=False, remap_area_min=0.0, flags=0, chunk_rows=0, bitmaps=None):
+    def apply_host_grib(self, buf, rows, out=None, masked=False, remap_area_min=0.0, flags=0, chunk_rows=0, bitmaps=None,
+                        skipna=False):
         """The host twin (smm_apply_host_grib): buf is a host uint8 array -- typically a whole GRIB file -- and rows as
         for `apply_grib`.  Each row's packed bytes are staged and cross PCIe as they are (2 B per cell at 16 bits), no
         host decode runs.  Returns a float64 (B, D) numpy array, the bits of `apply_host` on the decoded float32 field.
-        bitmaps as for `apply_grib` (smm_apply_host_grib_bm): a bitmapped row's bitmap bytes are staged behind its data."""
+        bitmaps as for `apply_grib` (smm_apply_host_grib_bm): a bitmapped row's bitmap bytes are staged behind its data.
+        skipna as for `apply_grib` (smm_apply_host_grib_na): the bits of `apply_host(..., skipna=True)`'s SELL kernel."""
         rows, rows_p = self._grib_rows(rows)
         buf = np.ascontiguousarray(buf)
         if buf.dtype != np.uint8 or buf.ndim != 1:
@@ -385,6 +394,11 @@ class SparseOperator:
         if out.shape != (n_batch, self.n_dst) or out.dtype != np.float64 or not out.flags.c_contiguous:
             raise ValueError(f"out must be a C-contiguous float64 ({n_batch}, {self.n_dst}) array")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        if skipna:
+            bitmaps, bm_p = (None, None) if bitmaps is None else self._grib_bitmaps(bitmaps, n_batch)
+            _lib.call("smm_apply_host_grib_na", self.handle, _cptr(buf), buf.size, rows_p, bm_p, _cptr(out), _lib.SMM_F64,
+                      self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows))
+            return out
         if bitmaps is not None:
             bitmaps, bm_p = self._grib_bitmaps(bitmaps, n_batch)
             _lib.call("smm_apply_host_grib_bm", self.handle, _cptr(buf), buf.size, rows_p, bm_p, _cptr(out), _lib.SMM_F64,
@@ -578,13 +592,15 @@ class OperatorGroup:
         return dims, (rows, rows_p), (bm, bm_p), (lev, ml)
 
     def apply_grib(self, x, rows, level_index, masked_levels=None, bitmaps=None, y=None, x_bytes=None, masked=False,
-                   remap_area_min=0.0, transpose=True, flags=0, stream=None, n_inner=1):
+                   remap_area_min=0.0, transpose=True, flags=0, stream=None, n_inner=1, skipna=False):
         """`apply` for GRIB simple-packed fields resident in HBM as they are on disk (smm_group_apply_grib): x and the
         `GRIB_ROW_DTYPE` / `GRIB_BITMAP_DTYPE` records as for `SparseOperator.apply_grib`, one record per batch row
         (o, l, i) in C order -- rows shaped (n_outer, n_lev, n_inner), or flat with n_lev = len(level_index) and
         `n_inner`.  All levels run in one launch of the grouped GRIB gather.  Returns the float64 DeviceArray `apply`
         returns, (n_outer, n_inner, n_lev, D) when transpose else (n_lev, n_outer, n_inner, D), bit-identical to
-        `apply` on the float32 field a host decode gives (NaN where a bitmap bit is 0)."""
+        `apply` on the float32 field a host decode gives (NaN where a bitmap bit is 0).
+        skipna: every level renormalises over its valid source values (smm_group_apply_grib_na) -- the bits of
+        `apply(..., skipna=True, flags=APPLY_KERNEL_SELL)` on that field."""
         (n_outer, n_lev, n_in), (rows, rows_p), (bm, bm_p), (lev, ml) = self._grib_args(rows, bitmaps, level_index,
                                                                                          masked_levels, n_inner)
         if isinstance(x, DeviceArray):
@@ -607,16 +623,17 @@ class OperatorGroup:
         elif y.shape != shape or y.dtype != np.float64:
             raise ValueError(f"Y must be a float64 {shape} DeviceArray")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
-        _lib.call("smm_group_apply_grib", self.handle, x_ptr, n_bytes, rows_p, bm_p, _ptr(y), _lib.SMM_F64, *ys, n_outer,
+        _lib.call("smm_group_apply_grib_na" if skipna else "smm_group_apply_grib", self.handle, x_ptr, n_bytes, rows_p, bm_p, _ptr(y), _lib.SMM_F64, *ys, n_outer,
                   n_lev, n_in, _cptr(lev), _cptr(ml), float(remap_area_min), fl, _stream_handle(stream))
         return y
 
     def apply_host_grib(self, buf, rows, level_index, masked_levels=None, bitmaps=None, out=None, masked=False,
-                        remap_area_min=0.0, transpose=True, flags=0, chunk_outer=0, n_inner=1):
+                        remap_area_min=0.0, transpose=True, flags=0, chunk_outer=0, n_inner=1, skipna=False):
         """The host twin (smm_group_apply_host_grib): buf is a host uint8 array -- typically a whole GRIB file -- rows
         and bitmaps as for `apply_grib`.  Blocks of the outer axis stream through the group's pipeline; each row's
         packed bytes (a bitmapped row's: its present cells only, and its bitmap) cross PCIe as they are and no host
-        decode runs.  Returns the float64 array `apply_host` returns on the decoded float32 field, bit for bit."""
+        decode runs.  Returns the float64 array `apply_host` returns on the decoded float32 field, bit for bit.
+        skipna as for `apply_grib` (smm_group_apply_host_grib_na)."""
         (n_outer, n_lev, n_in), (rows, rows_p), (bm, bm_p), (lev, ml) = self._grib_args(rows, bitmaps, level_index,
                                                                                          masked_levels, n_inner)
         buf = np.ascontiguousarray(buf)
@@ -628,7 +645,7 @@ class OperatorGroup:
         if out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
             raise ValueError(f"out must be a C-contiguous float64 {shape} array")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
-        _lib.call("smm_group_apply_host_grib", self.handle, _cptr(buf), buf.size, rows_p, bm_p, _cptr(out), _lib.SMM_F64,
+        _lib.call("smm_group_apply_host_grib_na" if skipna else "smm_group_apply_host_grib", self.handle, _cptr(buf), buf.size, rows_p, bm_p, _cptr(out), _lib.SMM_F64,
                   n_outer, n_lev, n_in, int(bool(transpose)), _cptr(lev), _cptr(ml), float(remap_area_min), fl,
                   int(chunk_outer))
         return out

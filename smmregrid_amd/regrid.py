@@ -58,7 +58,7 @@ class Regridder(object):
                  vertical_dim=None, horizontal_dims=None, cdo_extra=None, cdo_options=None,
                  check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=None,
                  lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False,
-                 packed_levels=False, packed_out=False, packed_out_levels=False, half=False):
+                 packed_levels=False, packed_out=False, packed_out_levels=False, half=False, packed_skipna=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -95,6 +95,13 @@ class Regridder(object):
         self.packed_levels = bool(packed_levels)
         if self.packed_levels and not self.packed:
             raise ValueError('packed_levels=True needs packed=True')
+        # packed_skipna (with packed=True and skipna=True): a raw GRIB variable stays raw under skipna too -- the gather
+        # renormalises over the cells its bitmap leaves and the values its rule keeps finite (smm_apply_host_grib_na;
+        # with packed_levels=True on masked-level weights smm_group_apply_host_grib_na).  Off by default: such a variable
+        # is decoded on the host first, as before
+        self.packed_skipna = bool(packed_skipna)
+        if self.packed_skipna and not (self.packed and self.skipna):
+            raise ValueError('packed_skipna=True needs packed=True and skipna=True')
         # packed_out (with packed=True): a variable regridded raw comes back in its own raw dtype, encoded by the rule
         # of its own attributes (CFEncode) inside the kernels' stores, and keeps its packing attributes: it can be
         # written straight to a file.  Values that round outside the raw range become the fill value (no wrap-around)
@@ -356,22 +363,31 @@ class Regridder(object):
         is and apply_weights ships its bit streams (smm_apply_host_grib, with bitmaps smm_apply_host_grib_bm); so it
         does on masked-level weights with packed_levels=True (regrid3d: smm_group_apply_host_grib) when its dims are
         (outer..., level, inner..., horizontal...).  Everything else decodes it on the host -- what np.asarray would do
-        anyway -- and goes on as before."""
-        why = None
+        anyway -- and goes on as before.  Under skipna it stays raw with packed_skipna=True (the _na entries)."""
+        why = self._grib_decode_reason(source_data.dims, datagridtype, self._result_dtype(source_data),
+                                       bool(datagridtype.mask_dim))
+        if why is None:
+            return source_data
         if self.packed:
-            if datagridtype.mask_dim and not self.packed_levels:
-                why = "masked levels"
-            elif self.skipna:
-                why = "skipna"
-            elif self._result_dtype(source_data) != np.dtype(np.float64):
-                why = f"out_dtype {self._result_dtype(source_data)}"
-            elif datagridtype.mask_dim and not self._grib_rows_by_level(source_data.dims, datagridtype):
-                why = "masked levels: its fields are not ordered (outer..., level, inner...)"
-            if why is None:
-                return source_data
             self.loggy.info("packed variable %s is decoded on the host (%s)", source_data.name, why)
         return DataArray(source_data.data.decode(), dims=source_data.dims, coords=source_data.coords,
                          attrs=source_data.attrs, name=source_data.name)
+
+    def _grib_decode_reason(self, dims, gridtype, out_dtype, levels):
+        """Why a `GribField` with these dims is decoded on the host, or None: it takes the raw road.  levels: it meets
+        masked-level (3-D) weights.  The one condition behind `_grib_or_decoded` and the guards of `apply_weights` and
+        `regrid3d`, which direct calls reach without it."""
+        if not self.packed:
+            return "packed=False"
+        if levels and not self.packed_levels:
+            return "masked levels"
+        if self.skipna and not self.packed_skipna:
+            return "skipna"
+        if np.dtype(out_dtype) != np.dtype(np.float64):
+            return f"out_dtype {np.dtype(out_dtype)}"
+        if levels and not self._grib_rows_by_level(dims, gridtype):
+            return "masked levels: its fields are not ordered (outer..., level, inner...)"
+        return None
 
     @staticmethod
     def _grib_rows_by_level(dims, datagridtype):
@@ -514,8 +530,8 @@ class Regridder(object):
 
         src = source_data.data
         area_min, skipna = self.remap_area_min, self.skipna
-        if isinstance(src, GribField) and (not self.packed or skipna or np.dtype(out_dtype) != np.dtype(np.float64)):
-            src = src.decode()      # a direct call: only packed=True, plain sums and float64 results take the raw road
+        if isinstance(src, GribField) and self._grib_decode_reason(source_data.dims, None, out_dtype, False):
+            src = src.decode()      # a direct call: only the raw road of _grib_or_decoded ships the bit streams
         res_dtype = out_dtype if cf_out is None else cf_out.raw_dtype
         src_dtype = getattr(src, "dtype", None)
         ship_half = self._ships_half(src_dtype)
@@ -555,7 +571,8 @@ class Regridder(object):
                 if src.rows.size != n_batch:
                     raise ValueError(f"{src.rows.size} GRIB fields for {n_batch} batch rows of shape {tuple(kept_shape)}")
                 # (with their bitmaps, if any: smm_apply_host_grib_bm ranks them on the device)
-                y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps)
+                y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps,
+                                       skipna=skipna)
                 return y.reshape(kept_shape + tgt_shape)
             if sb_in:
                 x = src.reshape(-1, n_batch)                  # (S, B): the batch values of a cell contiguous
@@ -642,9 +659,7 @@ class Regridder(object):
         if out_dtype is None:
             out_dtype = self._result_dtype(source_data)
         skipna = self.skipna
-        if isinstance(src, GribField) and not (self.packed and self.packed_levels and not skipna
-                                               and np.dtype(out_dtype) == np.dtype(np.float64)
-                                               and self._grib_rows_by_level(source_data.dims, gridtype)):
+        if isinstance(src, GribField) and self._grib_decode_reason(source_data.dims, gridtype, out_dtype, True):
             src = src.decode()      # a direct call: only the raw road of _grib_or_decoded ships the bit streams
         ship_half = self._ships_half(getattr(src, "dtype", None))
         sb_in = isinstance(src, DeviceArray) and src.layout == "sb"
@@ -673,7 +688,7 @@ class Regridder(object):
                 dims3 = (n_outer, n_lev, n_inner)
                 out = group.apply_host_grib(src.buf, src.rows.reshape(dims3), level_index, masked_levels,
                                             bitmaps=None if src.bitmaps is None else src.bitmaps.reshape(dims3),
-                                            masked=any_masked, remap_area_min=area_min, transpose=transpose)
+                                            masked=any_masked, remap_area_min=area_min, transpose=transpose, skipna=skipna)
                 return out.reshape(out_shape)
             if sb_in:
                 x = src.reshape(n_lev, -1, n_outer * n_inner)
