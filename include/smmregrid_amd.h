@@ -139,6 +139,23 @@ typedef struct smm_grib_bitmap_t {   /* 16 B */
   uint64_t n_values;     /* values in the row's packed stream = set bits among the first n_src; n_src without a bitmap */
 } smm_grib_bitmap_t;
 
+/* How one float64 result row goes back into GRIB simple packing (smm_grib_pack / smm_apply_host_grib_pk): the width
+ * asked for and 10^D.  The row's reference value and binary scale follow from its own minimum and maximum:
+ *     t = v * ddiv;                                             one rounding
+ *     present iff v is finite and |t| <= FLT_MAX;               NaN, +-inf and overflow are missing cells
+ *     R = the largest float32 <= min t;  ref = (double)R + 0.0; edition 2's IEEE reference value (-0 stored as +0)
+ *     range = max t - ref;                                      one rounding
+ *     E = the smallest integer with range * 2^-E <= 2^nbits - 1, at least -1022;  bscale = 2^E
+ *     q = rint(ldexp(t - ref, -E));                             ties to even; 0 <= q <= 2^nbits - 1
+ * A row whose range is 0 or that has no present cell is stored with width 0 (ref = 0 for the empty row).  These are not
+ * the bits ecCodes would choose (it picks E by heuristics of its own); it is a valid simple packing that the decode above
+ * inverts.  The text of the rule is smmregrid_amd/csrc/smm_grib_codec.hpp; smmregrid_amd.GribEncode states it in numpy. */
+typedef struct smm_grib_encode_t {   /* 16 B */
+  double ddiv;        /* 10.0^D as the host computes it; finite, > 0 */
+  int32_t nbits;      /* 1..32 */
+  int32_t reserved;   /* 0 */
+} smm_grib_encode_t;
+
 /* smm_apply flags.  Bits outside this set are refused with SMM_ERR_INVALID by every entry that takes `flags`
  * (ABI <= 4 encoded kernel variants in bits 16..23: those are smm_debug_set_tuning knobs now). */
 enum {
@@ -513,6 +530,47 @@ int smm_apply_grib_na(smm_operator_t op, const void* x, int64_t x_bytes, const s
                       int64_t n_batch, double remap_area_min, unsigned flags, void* stream);
 int smm_apply_host_grib_na(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
                            const smm_grib_bitmap_t* bitmaps, void* y_host, int y_dtype, int64_t ldy,
+                           int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows);
+
+/*
+ * Results in GRIB simple packing (smm_grib_encode_t above): 16 or 12 bits per cell, a reference value and a binary scale
+ * per row and a bitmap where cells are missing cross PCIe instead of 8 B per cell, in a form the _bm entries above take
+ * back as they are.  The packing cannot sit in the apply kernels' stores (a row's rule depends on the row's own minimum
+ * and maximum): four steps run on the float64 Y before it leaves the device -- a range pass that also writes the bitmap
+ * (one workgroup per row and segment of 32768 cells), a rule pass (one wave per row), the rank tables of the bitmaps
+ * just written (the build of smm_apply_grib_bm), and a pack pass with one thread per 32-bit word of a row's stream.
+ * The layout is known before any launch: row b owns a slot of align4(ceil(n_dst / 8)) bitmap bytes followed by
+ * align4(ceil(n_dst * nbits_b / 8)) stream bytes, slots back to back in row order.  The bitmap is MSB first with zero
+ * pad bits; the stream holds the present cells in cell order, big-endian, and every byte of it that the values do not
+ * reach is zero: every byte of every slot is written.  rows_out[b] = {byte offset of the stream, ref, bscale, ddiv,
+ * stored width (nbits, or 0 for a constant or empty row), 0}; bitmaps_out[b] = {byte offset of the bitmap, n_values},
+ * the offset SMM_GRIB_NO_BITMAP when n_values == n_dst.
+ *   smm_grib_out_layout     host only: byte_off[b] (may be NULL) = where row b's slot starts, *total_bytes = all slots.
+ *   smm_grib_pack           packs any float64 device result (n_batch, ldy) on `device` into `out` (device, 4-byte
+ *                           aligned, out_bytes >= the layout's total).  enc, rows_out and bitmaps_out are HOST arrays of
+ *                           n_batch records; the stream is synchronised before the call returns (the records come
+ *                           back to the host arrays).  Scratch is allocated and freed inside the call.
+ *   smm_apply_host_grib_pk  smm_apply_host_grib_bm (bitmaps may be NULL; SMM_APPLY_SKIPNA in flags: smm_apply_host_grib_na)
+ *                           with the result packed: each chunk's float64 Y stays on the device and is packed on the
+ *                           chunk's stream into a buffer that holds the chunk's row and bitmap records followed by its
+ *                           slots.  A pageable out_host receives one D2H copy per chunk through the pinned slot
+ *                           buffer; a page-locked out_host receives the slots directly, the records (56 B per row) in
+ *                           a copy of their own.  SMM_HOST_STAT_D2H_BYTES counts the slots and the records;
+ *                           SMM_HOST_STAT_H2D_BYTES also counts 48 B per row of pack tables staged behind the chunk's X.
+ *                           The chunk plan budgets the packed buffer and the scratch beside the device-only Y.
+ * SMM_ERR_INVALID, before any device is touched: nbits outside 1..32, a ddiv that is not finite or <= 0, reserved != 0,
+ * out_bytes below the layout, a misaligned out (device entry) or y, ldy < n_dst, n_dst >= 2^31, null pointers, a negative
+ * count; for the host entry everything smm_apply_host_grib_bm / _na refuses, as they refuse it (SMM_APPLY_KERNEL_TILE
+ * included).
+ */
+int smm_grib_out_layout(int64_t n_dst, const smm_grib_encode_t* enc, int64_t n_batch, uint64_t* byte_off,
+                        uint64_t* total_bytes);
+int smm_grib_pack(int device, const void* y, int64_t ldy, int64_t n_dst, int64_t n_batch,
+                  const smm_grib_encode_t* enc /* host */, void* out, int64_t out_bytes,
+                  smm_grib_row_t* rows_out /* host */, smm_grib_bitmap_t* bitmaps_out /* host */, void* stream);
+int smm_apply_host_grib_pk(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                           const smm_grib_bitmap_t* bitmaps /* or NULL */, const smm_grib_encode_t* enc,
+                           void* out_host, int64_t out_bytes, smm_grib_row_t* rows_out, smm_grib_bitmap_t* bitmaps_out,
                            int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows);
 
 /*

@@ -98,6 +98,15 @@ class GribBitmapStruct(ctypes.Structure):
 
 _gbp = ctypes.POINTER(GribBitmapStruct)
 
+
+class GribEncodeStruct(ctypes.Structure):
+    """smm_grib_encode_t: the width and 10^D one result row is packed with"""
+    _fields_ = [("ddiv", _dbl), ("nbits", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+_gep = ctypes.POINTER(GribEncodeStruct)
+_u64p = ctypes.POINTER(ctypes.c_uint64)
+
 # name -> argtypes; every entry point returns int status except the two noted
 SIGNATURES = {
     "smm_device_count": [ctypes.POINTER(_int)],
@@ -163,6 +172,9 @@ SIGNATURES = {
     "smm_apply_host_grib_bm": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _dbl, _uint, _i64],
     "smm_apply_grib_na": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _dbl, _uint, _p],
     "smm_apply_host_grib_na": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _dbl, _uint, _i64],
+    "smm_grib_out_layout": [_i64, _gep, _i64, _u64p, _u64p],
+    "smm_grib_pack": [_int, _p, _i64, _i64, _i64, _gep, _p, _i64, _grp, _gbp, _p],
+    "smm_apply_host_grib_pk": [_p, _p, _i64, _grp, _gbp, _gep, _p, _i64, _grp, _gbp, _i64, _dbl, _uint, _i64],
     "smm_group_apply": [_p, _p, _int, _i64, _i64, _i64, _p, _int, _i64, _i64, _i64,
                         _i64, _i64, _i64, _p, _p, _dbl, _uint, _p],
     "smm_group_prepare_sb": [_p],

@@ -123,6 +123,8 @@ struct GribState {
   DeviceBuf<smm_grib_row_t> d_rows;
   DeviceBuf<GribRowBitmap> d_bm;
   DeviceBuf<char> d_rank, d_pipe_rank[2];
+  // smm_apply_host_grib_pk, per pipeline slot: the chunk's packed result (records, then slots) and the pack's scratch
+  DeviceBuf<char> d_pipe_pk[2], d_pipe_scratch[2];
 };
 
 struct smm_operator {

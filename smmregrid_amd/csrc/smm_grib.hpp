@@ -51,7 +51,36 @@ struct GribBuildArgs {
   uint32_t n_src, n_blocks, n_segs;
 };
 
+// smm_grib_pack / smm_apply_host_grib_pk: float64 results into GRIB simple packing (the rule: smm_grib_codec.hpp).
+// What a row of the call brings to the device
+struct GribPackRow {     // 32 B
+  double ddiv;
+  uint64_t slot_off;     // of the row's slot -- bitmap part, then stream part -- from `out`; a multiple of 4
+  uint64_t pub_off;      // the same place as the records report it: the slot's offset in the caller's buffer
+  int32_t nbits;         // the requested width, 1..32
+  int32_t pad;
+};
+struct GribPackArgs {
+  const double* y;                // device: row j at y + j * ldy
+  int64_t ldy, n_j;
+  uint32_t n_dst, n_blocks, n_segs;   // cells, 32-cell blocks and kGribSegBlocks-block segments of a row
+  uint32_t max_words;             // stream words of the widest row: the pack grid covers that many per row
+  const GribPackRow* rows;        // device [n_j]
+  uint32_t* out;                  // device: the slots, as 32-bit words
+  double* part_min;               // device scratch [n_j * n_segs] each: the segments' tmin / tmax / present cells
+  double* part_max;
+  uint32_t* part_cnt;
+  smm_grib::GribPackRule* rules;  // device [n_j]: what the rule pass leaves for the pack
+  smm_grib_row_t* rec_rows;       // device [n_j]: the records of the result as the caller gets them
+  smm_grib_bitmap_t* rec_bm;      // device [n_j]
+  const smm_grib::GribRankEntry* table;   // device: row j's rank table at table + j * n_blocks (launch_grib_build)
+};
+
 namespace smm_launch {
+// the four steps of a pack in stream order: range + bitmap, rule, the rank tables of the bitmaps just written
+// (launch_grib_build over `build`: x = a.out, one table per row), pack.  limit: the largest launch grid (rows are
+// launched in parts beyond it)
+int launch_grib_pack(const GribPackArgs& a, const GribBuildArgs& build, int64_t limit, hipStream_t s);
 // div: some row of the call has ddiv != 1.0 (the instantiation with the f64 division); na: the SMM_APPLY_SKIPNA rule
 // (the NA instantiations, which take the values raw whatever fill says); fill: the 1e20 fill is on
 int launch_grib(const GribArgs& a, bool div, bool na, bool fill, hipStream_t s);

@@ -17,8 +17,8 @@
 namespace smm_grib {
 
 // bytes a row of n values of nbits bits occupies; a byte count rounded up to whole 4-byte words
-inline uint64_t row_bytes(uint64_t n, int nbits) { return (n * (uint64_t)nbits + 7) / 8; }
-inline uint64_t align4(uint64_t bytes) { return (bytes + 3) & ~(uint64_t)3; }
+SMM_GRIB_HD uint64_t row_bytes(uint64_t n, int nbits) { return (n * (uint64_t)nbits + 7) / 8; }
+SMM_GRIB_HD uint64_t align4(uint64_t bytes) { return (bytes + 3) & ~(uint64_t)3; }
 
 // The unsigned big-endian integer of nbits (0..32) bits at bit position p of the byte stream that `words` holds, read
 // as 32-bit words: word p / 32 and the one after it, both clamped to last_word (the last word of the buffer: nothing
@@ -62,7 +62,7 @@ struct alignas(8) GribRankEntry {
 // 32-cell blocks of one segment of the table build: a (row, segment) workgroup counts, then scans, this many blocks
 // (smm_grib.hip: 256 threads x 4 blocks) -- 32768 cells
 constexpr int kGribSegBlocks = 1024;
-inline uint64_t bitmap_bytes(uint64_t n_src) { return (n_src + 7) / 8; }
+SMM_GRIB_HD uint64_t bitmap_bytes(uint64_t n_src) { return (n_src + 7) / 8; }
 inline uint64_t bitmap_blocks(uint64_t n_src) { return (n_src + 31) / 32; }
 inline uint64_t bitmap_segments(uint64_t n_src) { return (bitmap_blocks(n_src) + kGribSegBlocks - 1) / kGribSegBlocks; }
 
@@ -83,6 +83,142 @@ SMM_GRIB_HD bool bitmap_present(GribRankEntry e, uint32_t c) { return ((e.bits >
 // the index of the next present one: its loads are issued all the same, the caller replaces the value by NaN.
 SMM_GRIB_HD uint32_t bitmap_index(GribRankEntry e, uint32_t c) {
   return e.rank_before + popcount32((e.bits >> 1) >> (31u - (c & 31u)));
+}
+
+// ---- the encode (smm_grib_pack / smm_apply_host_grib_pk; numpy: smmregrid_amd.GribEncode.encode).  THE RULE, for one
+// batch row with a requested width nbits in 1..32 and ddiv = 10^D > 0, on float64 result values v:
+//   t = v * ddiv                                  one rounding
+//   present  iff  v is finite and |t| <= FLT_MAX; every other cell (NaN, +-inf, overflow) is missing
+//   tmin, tmax = min, max of t over the present cells; n_values = their count
+//   R = the largest float32 <= tmin: round to nearest, one float32 down if that lies above tmin
+//   ref = (double)R + 0.0                         (a reference of -0 is stored as +0: min(-0, +0) has no order)
+//   range = tmax - ref                            one rounding
+//   range == 0 or n_values == 0: stored width 0, E = 0, no data bits; n_values == 0: ref = 0
+//   else E = the smallest integer with range * 2^-E <= 2^nbits - 1 -- frexp(range) = (m, e): e - nbits when
+//        m * 2^nbits <= 2^nbits - 1, else e - nbits + 1 -- raised to -1022 if below; bscale = 2^E; stored width nbits
+//   q = rint(ldexp(t - ref, -E))                  the subtraction rounds once, the scaling is exact, ties to even
+// 0 <= q <= 2^nbits - 1 follows: t <= tmax and rounding is monotonic, so t - ref <= range.  No multiply-add pair of it
+// may be contracted (the pragma of grib_decode, -ffp-contract=off elsewhere).
+constexpr double kGribFltMax = 3.4028234663852886e38;
+
+// t of a cell and whether the cell is present
+SMM_GRIB_HD bool grib_encode_t(double v, double ddiv, double* t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  *t = v * ddiv;
+  return __builtin_isfinite(v) && __builtin_fabs(*t) <= kGribFltMax;
+}
+
+struct GribPackRule {   // what the rule pass leaves per row on the device; 24 B
+  double ref;
+  int32_t E;
+  int32_t width;       // the stored width: the requested one, or 0
+  uint32_t n_values;   // present cells; n_dst < 2^31
+  uint32_t pad;
+};
+
+// the rule of a row from its tmin / tmax / n_values
+SMM_GRIB_HD GribPackRule grib_encode_rule(double tmin, double tmax, uint32_t n_values, int nbits) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  GribPackRule r{0.0, 0, 0, n_values, 0u};
+  if (n_values == 0) return r;
+  float R = (float)tmin;
+  if ((double)R > tmin) {   // one float32 down, on the bits: 0 -> the negative subnormal next to it
+    uint32_t u;
+    __builtin_memcpy(&u, &R, 4);
+    if ((u & 0x7fffffffu) == 0u)
+      u = 0x80000001u;
+    else if (u >> 31)
+      u += 1u;
+    else
+      u -= 1u;
+    __builtin_memcpy(&R, &u, 4);
+  }
+  r.ref = (double)R + 0.0;
+  const double range = tmax - r.ref;
+  if (range == 0.0) return r;
+  int e = 0;
+  const double m = __builtin_frexp(range, &e);
+  const double top = __builtin_ldexp(1.0, nbits);   // 2^nbits
+  int E = __builtin_ldexp(m, nbits) <= top - 1.0 ? e - nbits : e - nbits + 1;
+  if (E < -1022) E = -1022;
+  r.E = E;
+  r.width = nbits;
+  return r;
+}
+
+// q of a present cell's t
+SMM_GRIB_HD uint32_t grib_encode_q(double t, double ref, int E) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double d = t - ref;
+  return (uint32_t)__builtin_rint(__builtin_ldexp(d, -E));
+}
+
+// The output layout: row b owns a slot of align4(ceil(n_dst / 8)) bitmap bytes and align4(ceil(n_dst * nbits_b / 8))
+// stream bytes, slots back to back in row order
+SMM_GRIB_HD uint64_t pack_bitmap_bytes(uint64_t n_dst) { return align4(bitmap_bytes(n_dst)); }
+SMM_GRIB_HD uint64_t pack_slot_bytes(uint64_t n_dst, int nbits) { return pack_bitmap_bytes(n_dst) + align4(row_bytes(n_dst, nbits)); }
+
+// What value number i (at bit i * width of the row's stream) contributes to the stream's 32-bit word w, as the
+// big-endian number the word holds: q shifted to its place, the bits that belong to the neighbouring words dropped.
+// The value must overlap the word: 32 * w - width < i * width < 32 * w + 32.
+SMM_GRIB_HD uint32_t grib_word_part(uint32_t q, uint64_t i, int width, uint64_t w) {
+  const int shift = (int)((int64_t)(32 * w + 32) - (int64_t)(i * (uint64_t)width) - width);   // -31 .. 31
+  return shift >= 0 ? (uint32_t)((uint64_t)q << shift) : q >> (-shift);
+}
+// the values [first, end) that overlap word w of a stream of n_values values of `width` (>= 1) bits; end <= first: none
+SMM_GRIB_HD void grib_word_values(uint64_t w, int width, uint64_t n_values, uint64_t* first, uint64_t* end) {
+  *first = (32 * w) / (uint64_t)width;
+  const uint64_t e = (32 * w + 32 + (uint64_t)width - 1) / (uint64_t)width;
+  *end = e < n_values ? e : n_values;
+}
+// Word w of a row's stream as the big-endian number it holds: what one thread of the pack kernel computes.  y: the row's
+// n_dst result values; rule: the row's; tab: the row's rank table of n_blocks entries, read only when cells are missing.
+// The values that overlap the word are found, their q recomputed from y, and put in place.  With every cell present
+// value i is cell i; else the block of the first value is the last one whose rank_before <= i (binary search), the value
+// is that block's (i - rank_before)-th set bit from the top, and the set bits are walked forward from there.  A word
+// the stream does not reach, and every word of a width-0 row, is 0.
+SMM_GRIB_HD uint32_t grib_pack_word(const double* __restrict__ y, double ddiv, const GribPackRule& rule, uint32_t n_dst,
+                                    const GribRankEntry* __restrict__ tab, uint32_t n_blocks, uint32_t w) {
+  uint32_t word = 0;
+  if (rule.width <= 0) return word;
+  uint64_t i = 0, end = 0;
+  grib_word_values(w, rule.width, rule.n_values, &i, &end);
+  if (i >= end) return word;
+  if (rule.n_values == n_dst) {
+    for (; i < end; ++i) {
+      double t;
+      (void)grib_encode_t(y[i], ddiv, &t);
+      word |= grib_word_part(grib_encode_q(t, rule.ref, rule.E), i, rule.width, w);
+    }
+    return word;
+  }
+  uint32_t lo = 0, hi = n_blocks - 1;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo + 1) / 2;
+    if (tab[mid].rank_before <= (uint32_t)i)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  uint32_t k = lo, bits = tab[lo].bits;
+  for (uint32_t skip = (uint32_t)i - tab[lo].rank_before; skip > 0 && bits != 0u; --skip)
+    bits &= ~(0x80000000u >> __builtin_clz(bits));
+  for (; i < end; ++i) {
+    while (bits == 0u && k + 1 < n_blocks) bits = tab[++k].bits;   // i < n_values: a set bit lies ahead
+    if (bits == 0u) break;                                          // (a table that disagrees with n_values: stop)
+    const uint32_t pos = (uint32_t)__builtin_clz(bits);
+    bits &= ~(0x80000000u >> pos);
+    double t;
+    (void)grib_encode_t(y[32u * k + pos], ddiv, &t);
+    word |= grib_word_part(grib_encode_q(t, rule.ref, rule.E), i, rule.width, w);
+  }
+  return word;
 }
 
 }  // namespace smm_grib

@@ -1,5 +1,7 @@
 // GRIB simple-packed fields shipped raw: the host side of smm_apply_grib(_bm), smm_apply_host_grib(_bm),
-// smm_group_apply_grib and smm_group_apply_host_grib, and of their four SMM_APPLY_SKIPNA twins (_na).  The kernels and their launchers are in smm_grib.hip; what needs no
+// smm_group_apply_grib and smm_group_apply_host_grib, and of their four SMM_APPLY_SKIPNA twins (_na); and the way back,
+// float64 results into GRIB simple packing: smm_grib_out_layout, smm_grib_pack and smm_apply_host_grib_pk (kernels:
+// smm_grib_pack.hip).  The kernels and their launchers are in smm_grib.hip; what needs no
 // device -- the refusals of a row table, the chunk plan and the layout of a staged chunk -- in smm_grib_plan.cpp.  An
 // operator and a group differ in how a launch grid is cut into parts and in where Y goes; everything else is written once.
 #include "smm_device.hpp"
@@ -288,22 +290,117 @@ int stage_grib_chunk(char* hx, const smm::GribChunk& ch, const void* x_host, con
   return SMM_OK;
 }
 
+// ---- results packed back into GRIB (smm_grib_pack, smm_apply_host_grib_pk)
+
+// Where the packed result of a host call goes: offs[b] = row b's slot in out_host (n_batch + 1 entries, the last the total)
+struct GribOut {
+  const smm_grib_encode_t* enc;
+  const uint64_t* offs;
+  char* out_host;
+  smm_grib_row_t* rows_out;
+  smm_grib_bitmap_t* bitmaps_out;
+};
+
+// The pack tables of nr rows into t (nr GribPackRow, then nr GribRowBitmap for the rank-table build: every row has a
+// bitmap there, table r).  The rows' slots lie back to back from slot_base of the device buffer; offs[r] is where the
+// caller sees row r's slot.  Returns the stream words of the widest row.
+uint32_t fill_pack_tables(char* t, const smm_grib_encode_t* enc, int64_t nr, int64_t D, size_t slot_base, const uint64_t* offs) {
+  GribPackRow* rows = (GribPackRow*)t;
+  GribRowBitmap* bm = (GribRowBitmap*)(t + (size_t)nr * sizeof(GribPackRow));
+  const uint64_t n_blocks = smm_grib::bitmap_blocks((uint64_t)D);
+  uint32_t max_words = 0;
+  for (int64_t r = 0; r < nr; ++r) {
+    const uint64_t slot = slot_base + (offs[r] - offs[0]);
+    rows[r] = GribPackRow{enc[r].ddiv, slot, offs[r], enc[r].nbits, 0};
+    bm[r] = GribRowBitmap{slot, (uint64_t)r * n_blocks};
+    max_words = std::max(max_words, (uint32_t)(smm_grib::align4(smm_grib::row_bytes((uint64_t)D, enc[r].nbits)) / 4));
+  }
+  return max_words;
+}
+static_assert(sizeof(GribPackRow) + sizeof(GribRowBitmap) == smm::kGribPackTableBytes, "the pack tables of a row");
+static_assert(sizeof(smm_grib_row_t) + sizeof(smm_grib_bitmap_t) == smm::kGribOutRecordBytes, "the records of a row");
+
+// The four pack steps on stream s: nr rows of D cells of the device result y into d_out (out_bytes of it hold the slots,
+// a multiple of 4), the records into d_recs (nr smm_grib_row_t, then nr smm_grib_bitmap_t); d_tables: fill_pack_tables
+// on the device; scratch: smm::grib_pack_scratch(D, nr) bytes.
+int launch_pack(int64_t D, int64_t nr, const double* y, int64_t ldy, const char* d_tables, char* d_out, size_t out_bytes,
+                char* d_recs, char* scratch, uint32_t max_words, hipStream_t s) {
+  const smm::GribPackScratch sc = smm::grib_pack_scratch(D, nr);
+  GribPackArgs a{};
+  a.y = y;
+  a.ldy = ldy;
+  a.n_j = nr;
+  a.n_dst = (uint32_t)D;
+  a.n_blocks = (uint32_t)smm_grib::bitmap_blocks((uint64_t)D);
+  a.n_segs = (uint32_t)smm_grib::bitmap_segments((uint64_t)D);
+  a.max_words = max_words;
+  a.rows = (const GribPackRow*)d_tables;
+  a.out = (uint32_t*)d_out;
+  a.part_min = (double*)(scratch + sc.part_min);
+  a.part_max = (double*)(scratch + sc.part_max);
+  a.part_cnt = (uint32_t*)(scratch + sc.part_cnt);
+  a.rules = (smm_grib::GribPackRule*)(scratch + sc.rules);
+  a.rec_rows = (smm_grib_row_t*)d_recs;
+  a.rec_bm = (smm_grib_bitmap_t*)(d_recs + (size_t)nr * sizeof(smm_grib_row_t));
+  a.table = (const smm_grib::GribRankEntry*)(scratch + sc.table);
+  GribBuildArgs b{};
+  b.x = (const uint32_t*)d_out;
+  b.bm = (const GribRowBitmap*)(d_tables + (size_t)nr * sizeof(GribPackRow));
+  b.table = (smm_grib::GribRankEntry*)(scratch + sc.table);
+  b.totals = (uint32_t*)(scratch + sc.totals);
+  b.last_word = out_bytes / 4 - 1;
+  b.n_j = nr;
+  b.n_src = a.n_dst;
+  b.n_blocks = a.n_blocks;
+  b.n_segs = a.n_segs;
+  return smm_launch::launch_grib_pack(a, b, grid_limit(), s);
+}
+
 // A chunk plan of host rows through a handle's pipeline (the caller holds its pipe_mu; gs: the handle's, for the slots'
 // rank buffers).  Per chunk: stage, H2D, launch_chunk(in, ch, dy, stream) -- the chunk's launch from its slot's device
 // buffers, Y into dy -- then Y to the host: y_to_host(ch, src, async, stream) copies the chunk's results from src to
 // their place in the caller's Y, from the slot's device buffer on the stream when Y is page-locked (y_direct), else from
 // the slot's pinned buffer once the chunk has drained.  div: grib_needs_division of the whole call.
+// pk (smm_apply_host_grib_pk), or null: the chunk's Y stays in the slot's device buffer and is packed there, on the
+// chunk's stream, into the slot's packed buffer -- the chunk's row and bitmap records, then its slots.  The pack tables
+// of the chunk ride behind its staged X (8-byte aligned).  y_direct then says that pk->out_host is page-locked: the slots
+// go there straight from the device and only the records pass through the pinned buffer; else both come back in one copy
+// and the slots are copied out once the chunk has drained.  y_to_host is not called.
 template <typename Launch, typename YToHost>
 int run_grib_pipeline(HostPipe& pipe, GribState& gs, const smm::GribChunkPlan& plan, const void* x_host,
                       const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t S, int64_t D, bool div, bool y_direct,
-                      Launch&& launch_chunk, YToHost&& y_to_host) {
+                      Launch&& launch_chunk, YToHost&& y_to_host, const GribOut* pk = nullptr) {
   const size_t y_chunk = (size_t)plan.max_rows * D * 8;
-  SMM_HIP(pipe.ensure(plan.max_x, y_chunk, plan.max_x, y_direct ? 0 : y_chunk));
+  auto align8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
+  auto rec_bytes = [](const smm::GribChunk& ch) { return (size_t)ch.nr * smm::kGribOutRecordBytes; };
+  auto slot_bytes = [&](const smm::GribChunk& ch) { return (size_t)(pk->offs[ch.r0 + ch.nr] - pk->offs[ch.r0]); };
+  if (!pk) {
+    SMM_HIP(pipe.ensure(plan.max_x, y_chunk, plan.max_x, y_direct ? 0 : y_chunk));
+  } else {
+    size_t max_pk = 0;
+    for (const smm::GribChunk& ch : plan.chunks) max_pk = std::max(max_pk, rec_bytes(ch) + slot_bytes(ch));
+    const size_t x_all = align8(plan.max_x) + (size_t)plan.max_rows * smm::kGribPackTableBytes;
+    SMM_HIP(pipe.ensure(x_all, y_chunk, x_all, y_direct ? (size_t)plan.max_rows * smm::kGribOutRecordBytes : max_pk));
+    const size_t scratch = smm::grib_pack_scratch(D, plan.max_rows).bytes;
+    if (max_pk > std::min(gs.d_pipe_pk[0].bytes(), gs.d_pipe_pk[1].bytes()))
+      for (int i = 0; i < 2; ++i) SMM_HIP(gs.d_pipe_pk[i].alloc(max_pk));
+    if (scratch > std::min(gs.d_pipe_scratch[0].bytes(), gs.d_pipe_scratch[1].bytes()))
+      for (int i = 0; i < 2; ++i) SMM_HIP(gs.d_pipe_scratch[i].alloc(scratch));
+  }
   if (plan.max_rank > std::min(gs.d_pipe_rank[0].bytes(), gs.d_pipe_rank[1].bytes()))   // device-only, one per slot
     for (int i = 0; i < 2; ++i) SMM_HIP(gs.d_pipe_rank[i].alloc(plan.max_rank));
 
   CallStats st;
   auto deliver = [&](int64_t c, int b) -> int {   // results of chunk c: pinned -> the caller's Y
+    if (pk) {
+      const smm::GribChunk& ch = plan.chunks[(size_t)c];
+      StageTimer t(st.v[SMM_HOST_STAT_COPY_OUT_MS]);
+      const char* h = (const char*)pipe.hy[b].get();
+      memcpy(pk->rows_out + ch.r0, h, (size_t)ch.nr * sizeof(smm_grib_row_t));
+      memcpy(pk->bitmaps_out + ch.r0, h + (size_t)ch.nr * sizeof(smm_grib_row_t), (size_t)ch.nr * sizeof(smm_grib_bitmap_t));
+      if (y_direct) return SMM_OK;
+      return host_copy(pk->out_host + pk->offs[ch.r0], h + rec_bytes(ch), slot_bytes(ch));
+    }
     if (y_direct) return SMM_OK;
     StageTimer t(st.v[SMM_HOST_STAT_COPY_OUT_MS]);
     return y_to_host(plan.chunks[(size_t)c], (const char*)pipe.hy[b].get(), false, nullptr);
@@ -317,14 +414,38 @@ int run_grib_pipeline(HostPipe& pipe, GribState& gs, const smm::GribChunkPlan& p
       StageTimer t(st.v[SMM_HOST_STAT_STAGE_IN_MS]);
       if (int rc = stage_grib_chunk(hx, ch, x_host, rows, bitmaps, S, &n_tables)) return rc;
     }
+    size_t h2d = ch.x_bytes;
+    uint32_t max_words = 0;
+    if (pk) {   // the chunk's pack tables behind its X
+      h2d = align8(ch.x_bytes);
+      max_words = fill_pack_tables(hx + h2d, pk->enc + ch.r0, ch.nr, D, rec_bytes(ch), pk->offs + ch.r0);
+      h2d += (size_t)ch.nr * smm::kGribPackTableBytes;
+    }
     SMM_HIP(pipe.mark(b, 0));
-    SMM_HIP(hipMemcpyAsync(dx, hx, ch.x_bytes, hipMemcpyHostToDevice, pipe.stream[b]));
-    st.v[SMM_HOST_STAT_H2D_BYTES] += (double)ch.x_bytes;
+    SMM_HIP(hipMemcpyAsync(dx, hx, h2d, hipMemcpyHostToDevice, pipe.stream[b]));
+    st.v[SMM_HOST_STAT_H2D_BYTES] += (double)h2d;
     SMM_HIP(pipe.mark(b, 1));
     const GribIn in{dx, (int64_t)ch.x_bytes, (const smm_grib_row_t*)dx,
                     bitmaps ? (const GribRowBitmap*)(dx + (size_t)ch.nr * sizeof(smm_grib_row_t)) : nullptr,
                     gs.d_pipe_rank[b].get(), n_tables, div};
     if (int rc = launch_chunk(in, ch, pipe.dy[b].get(), pipe.stream[b])) return rc;
+    if (pk) {
+      char* dpk = gs.d_pipe_pk[b].get();
+      const size_t recs = rec_bytes(ch), slots = slot_bytes(ch);
+      if (int rc = launch_pack(D, ch.nr, (const double*)pipe.dy[b].get(), D, dx + align8(ch.x_bytes), dpk, recs + slots, dpk,
+                               gs.d_pipe_scratch[b].get(), max_words, pipe.stream[b]))
+        return rc;
+      st.v[SMM_HOST_STAT_D2H_BYTES] += (double)(recs + slots);
+      SMM_HIP(pipe.mark(b, 2));
+      if (y_direct) {
+        SMM_HIP(hipMemcpyAsync(pk->out_host + pk->offs[ch.r0], dpk + recs, slots, hipMemcpyDeviceToHost, pipe.stream[b]));
+        SMM_HIP(hipMemcpyAsync(pipe.hy[b].get(), dpk, recs, hipMemcpyDeviceToHost, pipe.stream[b]));
+      } else {
+        SMM_HIP(hipMemcpyAsync(pipe.hy[b].get(), dpk, recs + slots, hipMemcpyDeviceToHost, pipe.stream[b]));
+      }
+      SMM_HIP(pipe.mark(b, 3));
+      return SMM_OK;
+    }
     st.v[SMM_HOST_STAT_D2H_BYTES] += (double)((size_t)ch.nr * D * 8);
     SMM_HIP(pipe.mark(b, 2));
     if (!y_direct) {
@@ -341,12 +462,20 @@ int run_grib_pipeline(HostPipe& pipe, GribState& gs, const smm::GribChunkPlan& p
 // Host buffers, an operator: chunks of consecutive rows, sized by their bytes (rows differ in width: smm::plan_grib_chunks
 // with units of one row); Y is (n_batch, ldy).
 int smm_apply_host_grib_impl(smm_operator_t op, const void* x_host, const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps,
-                             void* y_host, int64_t ldy, int64_t n_batch, double area_min, unsigned flags, int64_t chunk_rows) {
+                             void* y_host, int64_t ldy, int64_t n_batch, double area_min, unsigned flags, int64_t chunk_rows,
+                             const GribOut* pk = nullptr) {
   const int64_t S = op->csr.n_src, D = op->csr.n_dst;
   if (n_batch == 0 || D == 0) return SMM_OK;
   DeviceGuard guard(op->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
-  const smm::GribChunkPlan plan = smm::plan_grib_chunks(rows, bitmaps, n_batch, 1, S, D, chunk_rows, free_device_bytes());
+  std::vector<size_t> out_row;   // pk: what a row's packed result takes on the device beside its Y
+  if (pk) {
+    const size_t scratch = smm::grib_pack_scratch(D, 1).bytes;
+    for (int64_t b = 0; b < n_batch; ++b)
+      out_row.push_back((size_t)(pk->offs[b + 1] - pk->offs[b]) + smm::kGribOutRecordBytes + smm::kGribPackTableBytes + scratch);
+  }
+  const smm::GribChunkPlan plan = smm::plan_grib_chunks(rows, bitmaps, n_batch, 1, S, D, chunk_rows, free_device_bytes(),
+                                                        pk ? out_row.data() : nullptr);
   const size_t yrow = (size_t)ldy * 8;
   auto launch_chunk = [&](const GribIn& in, const smm::GribChunk& ch, void* dy, hipStream_t s) -> int {
     return launch_grib_rows(op, in, dy, D, ch.nr, area_min, flags, s);
@@ -363,7 +492,36 @@ int smm_apply_host_grib_impl(smm_operator_t op, const void* x_host, const smm_gr
   };
   std::lock_guard<std::mutex> pipe_lock(op->pipe_mu);
   return run_grib_pipeline(op->pipe, op->grib, plan, x_host, rows, bitmaps, S, D, grib_needs_division(rows, n_batch),
-                           is_pinned(y_host), launch_chunk, y_to_host);
+                           is_pinned(pk ? (const void*)pk->out_host : y_host), launch_chunk, y_to_host, pk);
+}
+
+// smm_grib_pack: any float64 device result.  The tables go up from pageable vectors (taken when hipMemcpyAsync returns),
+// the records come back into one, and the stream is synchronised before the scratch is freed.
+int smm_grib_pack_impl(int device, const void* y, int64_t ldy, int64_t D, int64_t n_batch, const smm_grib_encode_t* enc,
+                       void* out, const uint64_t* offs, smm_grib_row_t* rows_out, smm_grib_bitmap_t* bitmaps_out, void* stream) {
+  if (n_batch == 0 || D == 0) return SMM_OK;
+  DeviceGuard guard(device);
+  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the device");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)n_batch, tables = n * smm::kGribPackTableBytes, recs = n * smm::kGribOutRecordBytes;
+  const smm::GribPackScratch sc = smm::grib_pack_scratch(D, n_batch);
+  std::vector<uint64_t> t8(tables / 8);   // 8-byte aligned
+  const uint32_t max_words = fill_pack_tables((char*)t8.data(), enc, n_batch, D, 0, offs);
+  DeviceBuf<char> d;   // tables, records, scratch
+  SMM_HIP(d.alloc(tables + recs + sc.bytes));
+  SMM_HIP(hipMemcpyAsync(d.get(), t8.data(), tables, hipMemcpyHostToDevice, s));
+  if (int rc = launch_pack(D, n_batch, (const double*)y, ldy, d.get(), (char*)out, (size_t)offs[n_batch], d.get() + tables,
+                           d.get() + tables + recs, max_words, s)) {
+    (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+    return rc;
+  }
+  std::vector<uint64_t> r8(recs / 8);
+  SMM_HIP(hipMemcpyAsync(r8.data(), d.get() + tables, recs, hipMemcpyDeviceToHost, s));
+  SMM_HIP(hipStreamSynchronize(s));
+  memcpy(rows_out, r8.data(), n * sizeof(smm_grib_row_t));
+  memcpy(bitmaps_out, (const char*)r8.data() + n * sizeof(smm_grib_row_t), n * sizeof(smm_grib_bitmap_t));
+  return SMM_OK;
 }
 
 // Host buffers, a group: chunks of whole outer indices (units of n_lev * n_inner consecutive records); Y is delivered as
@@ -436,6 +594,25 @@ int grib_host_entry(bool na, smm_operator_t op, const void* x_host, int64_t x_by
   });
 }
 
+// What the two packing entries refuse about the result side, before any device is touched; fills offs (n_batch + 1)
+int check_grib_out(const smm_grib_encode_t* enc, const void* out, bool out_device, int64_t out_bytes,
+                   const smm_grib_row_t* rows_out, const smm_grib_bitmap_t* bitmaps_out, int64_t n_dst, int64_t n_batch,
+                   std::vector<uint64_t>& offs) {
+  if (n_batch < 0) return fail(SMM_ERR_INVALID, "negative batch size");
+  if (out_bytes < 0) return fail(SMM_ERR_INVALID, "negative out_bytes");
+  if (n_batch > 0 && (!enc || !rows_out || !bitmaps_out)) return fail(SMM_ERR_INVALID, "null encode, row or bitmap record pointer");
+  std::string err;
+  if (!smm::check_grib_encode(enc, n_batch, n_dst, err)) return fail(SMM_ERR_INVALID, err);
+  offs.assign((size_t)n_batch + 1, 0);
+  offs[(size_t)n_batch] = smm::grib_out_layout(n_dst, enc, n_batch, offs.data());
+  if ((uint64_t)out_bytes < offs[(size_t)n_batch])
+    return fail(SMM_ERR_INVALID, "out_bytes " + std::to_string(out_bytes) + " is below the layout's " +
+                                     std::to_string(offs[(size_t)n_batch]) + " bytes");
+  if (!out && offs[(size_t)n_batch] > 0) return fail(SMM_ERR_INVALID, "null result pointer");
+  if (out_device && (uintptr_t)out % 4) return fail(SMM_ERR_INVALID, "result pointer is not 4-byte aligned");
+  return SMM_OK;
+}
+
 int grib_group_entry(bool na, smm_group_t g, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,
                      const smm_grib_bitmap_t* bitmaps, void* y, int y_dtype, int64_t ys_outer, int64_t ys_lev, int64_t ys_inner,
                      int64_t n_outer, int64_t n_lev, int64_t n_inner, const int32_t* level_index, const uint8_t* masked_levels,
@@ -506,6 +683,48 @@ int smm_apply_host_grib_na(smm_operator_t op, const void* x_host, int64_t x_byte
                            double remap_area_min, unsigned flags, int64_t chunk_rows) {
   return grib_host_entry(true, op, x_host, x_bytes, rows, bitmaps, y_host, y_dtype, ldy, n_batch, remap_area_min, flags,
                          chunk_rows);
+}
+
+int smm_grib_out_layout(int64_t n_dst, const smm_grib_encode_t* enc, int64_t n_batch, uint64_t* byte_off,
+                        uint64_t* total_bytes) {
+  return guarded([&] {
+    if (n_batch < 0) return fail(SMM_ERR_INVALID, "negative batch size");
+    if (!total_bytes || (n_batch > 0 && !enc)) return fail(SMM_ERR_INVALID, "null encode or total pointer");
+    std::string err;
+    if (!smm::check_grib_encode(enc, n_batch, n_dst, err)) return fail(SMM_ERR_INVALID, err);
+    *total_bytes = smm::grib_out_layout(n_dst, enc, n_batch, byte_off);
+    return (int)SMM_OK;
+  });
+}
+
+int smm_grib_pack(int device, const void* y, int64_t ldy, int64_t n_dst, int64_t n_batch, const smm_grib_encode_t* enc,
+                  void* out, int64_t out_bytes, smm_grib_row_t* rows_out, smm_grib_bitmap_t* bitmaps_out, void* stream) {
+  return guarded([&] {
+    std::vector<uint64_t> offs;
+    if (int rc = check_grib_out(enc, out, true, out_bytes, rows_out, bitmaps_out, n_dst, n_batch, offs)) return rc;
+    if (!y && n_batch > 0 && n_dst > 0) return fail(SMM_ERR_INVALID, "null field pointer");
+    if ((uintptr_t)y % 8) return fail(SMM_ERR_INVALID, "field pointer is not element aligned");
+    if (n_batch > 0 && ldy < n_dst) return fail(SMM_ERR_INVALID, "ldy smaller than the grid size");
+    return smm_grib_pack_impl(device, y, ldy, n_dst, n_batch, enc, out, offs.data(), rows_out, bitmaps_out, stream);
+  });
+}
+
+int smm_apply_host_grib_pk(smm_operator_t op, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                           const smm_grib_bitmap_t* bitmaps, const smm_grib_encode_t* enc, void* out_host, int64_t out_bytes,
+                           smm_grib_row_t* rows_out, smm_grib_bitmap_t* bitmaps_out, int64_t n_batch, double remap_area_min,
+                           unsigned flags, int64_t chunk_rows) {
+  return guarded([&] {
+    static const double no_y = 0.0;   // the float64 Y of this entry never leaves the device: nothing of the caller's to check
+    const bool na = (flags & SMM_APPLY_SKIPNA) != 0;
+    if (int rc = check_grib_call(x_host, false, x_bytes, rows, &no_y, SMM_F64, n_batch, remap_area_min, &flags, na)) return rc;
+    if (!op) return fail(SMM_ERR_INVALID, "null operator");
+    std::vector<uint64_t> offs;
+    if (int rc = check_grib_out(enc, out_host, false, out_bytes, rows_out, bitmaps_out, op->csr.n_dst, n_batch, offs)) return rc;
+    if (int rc = check_grib_operator(op, x_bytes, rows, bitmaps, op->csr.n_dst, n_batch, remap_area_min, flags)) return rc;
+    const GribOut pk{enc, offs.data(), (char*)out_host, rows_out, bitmaps_out};
+    return smm_apply_host_grib_impl(op, x_host, rows, bitmaps, nullptr, op->csr.n_dst, n_batch, remap_area_min, flags,
+                                    chunk_rows, &pk);
+  });
 }
 
 int smm_group_apply_grib(smm_group_t g, const void* x, int64_t x_bytes, const smm_grib_row_t* rows,

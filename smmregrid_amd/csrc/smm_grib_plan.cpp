@@ -62,26 +62,29 @@ GribRowCost grib_row_cost(const smm_grib_row_t& row, const smm_grib_bitmap_t* bm
 }
 
 GribChunkPlan plan_grib_chunks(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_outer, int64_t unit,
-                               int64_t n_src, int64_t D, int64_t requested_units, size_t free_bytes) {
+                               int64_t n_src, int64_t D, int64_t requested_units, size_t free_bytes,
+                               const size_t* out_row_bytes) {
   constexpr size_t kTarget = (size_t)256 << 20, kMinChunk = (size_t)32 << 20;
   constexpr int64_t kMinChunks = 8;
   GribChunkPlan plan;
   if (n_outer <= 0 || unit <= 0) return plan;
   const size_t y_row = (size_t)std::max<int64_t>(D, 0) * 8;
   // staged and rank bytes of outer index o: its `unit` consecutive records
-  auto unit_cost = [&](int64_t o, size_t& x, size_t& r) {
-    x = r = 0;
+  // ... and, for a packed result, what its rows add on the device (out_row_bytes)
+  auto unit_cost = [&](int64_t o, size_t& x, size_t& r, size_t& e) {
+    x = r = e = 0;
     for (int64_t b = o * unit; b < (o + 1) * unit; ++b) {
       const GribRowCost c = grib_row_cost(rows[b], bitmaps ? &bitmaps[b] : nullptr, n_src);
       x += c.staged();
       r += c.rank;
+      if (out_row_bytes) e += out_row_bytes[b];
     }
   };
   if (requested_units <= 0) {
-    size_t total = 0, x = 0, r = 0;
+    size_t total = 0, x = 0, r = 0, e = 0;
     for (int64_t o = 0; o < n_outer; ++o) {
-      unit_cost(o, x, r);
-      total += x + r + (size_t)unit * y_row;
+      unit_cost(o, x, r, e);
+      total += x + r + e + (size_t)unit * y_row;
     }
     plan.target = std::min(kTarget, std::max(kMinChunk, total / (size_t)kMinChunks));
     if (free_bytes > 0) plan.target = std::min(plan.target, std::max<size_t>(free_bytes / 8, 1));
@@ -91,9 +94,9 @@ GribChunkPlan plan_grib_chunks(const smm_grib_row_t* rows, const smm_grib_bitmap
     size_t bytes = 0;
     int64_t units = 0;
     while (o < n_outer) {
-      size_t x = 0, r = 0;
-      unit_cost(o, x, r);
-      const size_t all = x + r + (size_t)unit * y_row;
+      size_t x = 0, r = 0, e = 0;
+      unit_cost(o, x, r, e);
+      const size_t all = x + r + e + (size_t)unit * y_row;
       if (requested_units > 0 ? units >= requested_units : (units > 0 && bytes + all > plan.target)) break;
       bytes += all;
       c.x_bytes += x;
@@ -129,6 +132,42 @@ GribChunkLayout layout_grib_chunk(char* hx, const GribChunk& ch, const smm_grib_
     out.n_tables += c.has_bitmap;
   }
   return out;
+}
+
+bool check_grib_encode(const smm_grib_encode_t* enc, int64_t n_batch, int64_t n_dst, std::string& err) {
+  if (n_dst < 0 || n_dst >= ((int64_t)1 << 31)) return err = "n_dst must be within [0, 2^31)", false;
+  for (int64_t b = 0; b < n_batch; ++b) {
+    const std::string at = "enc[" + std::to_string(b) + "]";
+    if (enc[b].nbits < 1 || enc[b].nbits > 32) return err = at + ".nbits must be within 1..32", false;
+    if (!std::isfinite(enc[b].ddiv) || !(enc[b].ddiv > 0.0)) return err = at + ".ddiv must be finite and > 0 (10^D)", false;
+    if (enc[b].reserved != 0) return err = at + ".reserved must be 0", false;
+  }
+  return true;
+}
+
+uint64_t grib_out_layout(int64_t n_dst, const smm_grib_encode_t* enc, int64_t n_batch, uint64_t* byte_off) {
+  uint64_t at = 0;
+  for (int64_t b = 0; b < n_batch; ++b) {
+    if (byte_off) byte_off[b] = at;
+    at += smm_grib::pack_slot_bytes((uint64_t)n_dst, enc[b].nbits);
+  }
+  return at;
+}
+
+GribPackScratch grib_pack_scratch(int64_t n_dst, int64_t n_rows) {
+  const size_t n = (size_t)std::max<int64_t>(n_rows, 0);
+  const size_t segs = n * (size_t)smm_grib::bitmap_segments((uint64_t)n_dst);
+  const size_t blocks = n * (size_t)smm_grib::bitmap_blocks((uint64_t)n_dst);
+  auto align8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
+  GribPackScratch s;
+  s.part_min = 0;
+  s.part_max = s.part_min + segs * 8;
+  s.part_cnt = s.part_max + segs * 8;
+  s.rules = align8(s.part_cnt + segs * 4);
+  s.table = s.rules + n * sizeof(smm_grib::GribPackRule);
+  s.totals = s.table + blocks * sizeof(smm_grib::GribRankEntry);
+  s.bytes = align8(s.totals + segs * 4);
+  return s;
 }
 
 }  // namespace smm

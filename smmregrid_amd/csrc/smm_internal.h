@@ -8,6 +8,7 @@
 
 struct smm_grib_row_t;   // include/smmregrid_amd.h
 struct smm_grib_bitmap_t;
+struct smm_grib_encode_t;
 
 namespace smm {
 
@@ -230,8 +231,27 @@ struct GribChunkPlan {
   int64_t max_rows = 0;            // most rows of one chunk
   size_t max_rank = 0;             // largest rank_bytes of one chunk
 };
+// out_row_bytes: null, or per row what its packed result adds on the device beside its Y (smm_apply_host_grib_pk: the
+// row's records, slot and scratch -- grib_pack_row_bytes): counted into the chunk's bytes with the rest.
 GribChunkPlan plan_grib_chunks(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_outer, int64_t unit,
-                               int64_t n_src, int64_t D, int64_t requested_units, size_t free_bytes);
+                               int64_t n_src, int64_t D, int64_t requested_units, size_t free_bytes,
+                               const size_t* out_row_bytes = nullptr);
+
+// ---- results packed back into GRIB (smm_grib_pack, smm_apply_host_grib_pk; smm_grib_plan.cpp).  What the entries refuse
+// about the encode records (nbits 1..32, ddiv finite and > 0, reserved 0) and the sizes (n_dst in [0, 2^31)): false + err
+bool check_grib_encode(const smm_grib_encode_t* enc, int64_t n_batch, int64_t n_dst, std::string& err);
+// the layout: byte_off[b] (byte_off may be null) = start of row b's slot; returns the bytes of all slots
+uint64_t grib_out_layout(int64_t n_dst, const smm_grib_encode_t* enc, int64_t n_batch, uint64_t* byte_off);
+// Device scratch of a pack of n_rows rows of n_dst cells, one block cut into pieces at these byte offsets (each a
+// multiple of 8): the segments' partial tmin / tmax / counts, the rows' rules, the rank tables and their segment totals
+struct GribPackScratch {
+  size_t part_min = 0, part_max = 0, part_cnt = 0, rules = 0, table = 0, totals = 0, bytes = 0;
+};
+GribPackScratch grib_pack_scratch(int64_t n_dst, int64_t n_rows);
+// the records of a packed row as they travel in front of a chunk's slots: smm_grib_row_t + smm_grib_bitmap_t
+constexpr size_t kGribOutRecordBytes = 40 + 16;
+// the pack tables of a row staged behind a chunk's X: GribPackRow + GribRowBitmap (smm_grib.hpp, smm_grib_codec.hpp)
+constexpr size_t kGribPackTableBytes = 32 + 16;
 // Where a chunk's pieces lie in its staging buffer hx (ch.x_bytes bytes, 8-byte aligned), written into hx: the table first
 // -- the rows' records with byte_off the staged offset of the row's data -- then, with bitmaps, their records
 // (GribRowBitmap, smm_grib_codec.hpp: bitmap_off a staged offset too, table_off the place of the row's rank table among

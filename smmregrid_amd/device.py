@@ -532,6 +532,34 @@ def to_device_pitched(host, dtype=None, stream=None):
     return out
 
 
+def grib_pack(y, enc, n_points=None, out=None, stream=None):
+    """Pack a float64 `DeviceArray` (..., ld) into GRIB simple packing on the device (smm_grib_pack): every leading
+    index is one field of n_points cells (default: the whole last axis; a smaller n_points leaves the row's tail
+    unread).  enc: a `GribEncode`.  Returns (DeviceArray of uint8 in the layout of `enc.layout`, GRIB_ROW_DTYPE
+    records, GRIB_BITMAP_DTYPE records) -- what `SparseOperator.apply_grib(x, rows, bitmaps=bitmaps)` takes as it is,
+    and bytewise what `enc.encode` gives for the same values.  out: a uint8 DeviceArray to pack into (at least the
+    layout's bytes).  The stream is synchronised on return."""
+    from .griblite import GRIB_BITMAP_DTYPE, GRIB_ROW_DTYPE
+    if not isinstance(y, DeviceArray) or y.dtype != np.float64 or y.ndim < 1:
+        raise TypeError("grib_pack takes a float64 DeviceArray")
+    ld = y.shape[-1]
+    n_points = ld if n_points is None else int(n_points)
+    n_fields = y.size // ld if ld else 0
+    _, total = enc.layout(n_points, n_fields)
+    if out is None:
+        out = DeviceArray((max(total, 4),), np.uint8)
+    elif not isinstance(out, DeviceArray) or out.dtype != np.uint8 or out.nbytes < total:
+        raise ValueError(f"out must be a uint8 DeviceArray of at least {total} bytes")
+    rec = enc.records(n_fields)
+    rows = np.zeros(n_fields, dtype=GRIB_ROW_DTYPE)
+    bitmaps = np.zeros(n_fields, dtype=GRIB_BITMAP_DTYPE)
+    _lib.call("smm_grib_pack", current_device(), ctypes.c_void_p(y.ptr), ld, n_points, n_fields,
+              ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribEncodeStruct)), ctypes.c_void_p(out.ptr), out.nbytes,
+              ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)),
+              ctypes.cast(bitmaps.ctypes.data, ctypes.POINTER(_lib.GribBitmapStruct)), _stream_handle(stream))
+    return out, rows, bitmaps
+
+
 def empty(shape, dtype=np.float64):
     if not isinstance(shape, tuple):
         shape = tuple(np.atleast_1d(shape).tolist())

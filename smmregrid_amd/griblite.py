@@ -48,6 +48,10 @@ GRIB_BITMAP_DTYPE = np.dtype({"names": ["bitmap_off", "n_values"], "formats": ["
                               "itemsize": 16})
 GRIB_NO_BITMAP = 2 ** 64 - 1
 
+# smm_grib_encode_t, field for field: how one result row is packed (GribEncode)
+GRIB_ENCODE_DTYPE = np.dtype({"names": ["ddiv", "nbits", "reserved"], "formats": ["<f8", "<i4", "<i4"],
+                              "offsets": [0, 8, 12], "itemsize": 16})
+
 
 class GribField:
     """The fields of one GRIB variable kept as the file has them: `buf`, the file's bytes (one uint8 array shared by
@@ -100,6 +104,130 @@ class GribField:
         n_bm = 0 if self.bitmaps is None else int((self.bitmaps["bitmap_off"] != GRIB_NO_BITMAP).sum())
         return (f"<GribField {self.shape} float32, {self.rows.size} packed fields, widths "
                 f"{sorted(set(self.rows['nbits'].tolist()))}" + (f", {n_bm} with a bitmap>" if n_bm else ">"))
+
+
+_FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def _align4(n):
+    return (int(n) + 3) // 4 * 4
+
+
+class GribEncode:
+    """How regrid results go back into GRIB simple packing: a bit width and a decimal scale factor D per field (scalars,
+    or one entry per field).  The reference value and the binary scale of a field follow from the field's own minimum
+    and maximum by the rule of smm_grib_codec.hpp, which `encode` states in numpy -- the oracle of smm_grib_pack:
+        t = v * 10^D; present iff v finite and |t| <= FLT_MAX; R = the largest float32 <= min t; ref = R + 0.0;
+        range = max t - ref; E = the smallest integer with range * 2^-E <= 2^nbits - 1 (at least -1022);
+        q = rint(ldexp(t - ref, -E)); a constant or empty field has width 0 and no data bits.
+    The result decodes with `GribField.decode` (value = (ref + q * 2^E) / 10^D)."""
+
+    def __init__(self, nbits, decimal_scale=0):
+        nb, ds = np.asarray(nbits), np.asarray(decimal_scale)
+        if nb.ndim > 1 or ds.ndim > 1:
+            raise ValueError("nbits and decimal_scale are scalars or one entry per field")
+        if not (np.issubdtype(nb.dtype, np.integer) and np.issubdtype(ds.dtype, np.integer)):
+            raise ValueError("nbits and decimal_scale are integers")
+        if nb.ndim == 1 and ds.ndim == 1 and nb.size != ds.size:
+            raise ValueError(f"{nb.size} widths for {ds.size} decimal scale factors")
+        self.n_fields = None if nb.ndim == 0 and ds.ndim == 0 else int(max(nb.size if nb.ndim else 0, ds.size if ds.ndim else 0))
+        n = 1 if self.n_fields is None else self.n_fields
+        self.nbits = np.broadcast_to(nb.astype(np.int32), (n,)).copy()
+        self.decimal_scale = np.broadcast_to(ds.astype(np.int64), (n,)).copy()
+        if ((self.nbits < 1) | (self.nbits > 32)).any():
+            raise ValueError("GRIB output widths are 1..32 bits")
+        self.ddiv = np.array([10.0 ** int(d) if abs(int(d)) < 309 else np.inf for d in self.decimal_scale], dtype=np.float64)
+        if not (np.isfinite(self.ddiv) & (self.ddiv > 0)).all():
+            raise ValueError("10^D must be finite and positive")
+
+    @classmethod
+    def from_field(cls, field):
+        """Each source row's own width and D.  A width of 0 (a constant field) becomes the variable's largest width,
+        or 16 if all are 0."""
+        nbits = field.rows["nbits"].astype(np.int32)
+        top = int(nbits.max()) if nbits.size and nbits.max() > 0 else 16
+        nbits = np.where(nbits == 0, top, nbits).astype(np.int32)
+        ddiv = field.rows["ddiv"].astype(np.float64)
+        if not (np.isfinite(ddiv) & (ddiv > 0)).all():
+            raise ValueError("a source row's ddiv is not finite and positive")
+        dec = np.rint(np.log10(ddiv)).astype(np.int64)
+        for d, want in zip(dec, ddiv):
+            if 10.0 ** int(d) != want:
+                raise ValueError(f"ddiv {want!r} is not 10.0 ** D for an integer D")
+        return cls(nbits, dec)
+
+    def _per_field(self, n_fields):
+        n_fields = int(n_fields)
+        if self.n_fields is not None and self.n_fields != n_fields:
+            raise ValueError(f"a GribEncode of {self.n_fields} fields for {n_fields} fields")
+        return np.broadcast_to(self.nbits, (n_fields,)), np.broadcast_to(self.ddiv, (n_fields,))
+
+    def records(self, n_fields):
+        """The smm_grib_encode_t records of n_fields fields."""
+        nbits, ddiv = self._per_field(n_fields)
+        rec = np.zeros(int(n_fields), dtype=GRIB_ENCODE_DTYPE)
+        rec["ddiv"], rec["nbits"] = ddiv, nbits
+        return rec
+
+    def layout(self, n_points, n_fields):
+        """(byte offset of every field's slot, total bytes): a slot is align4(ceil(n_points / 8)) bitmap bytes and
+        align4(ceil(n_points * nbits / 8)) stream bytes, slots back to back in field order."""
+        n_points = int(n_points)
+        if n_points < 0 or n_points >= 2 ** 31:
+            raise ValueError("n_points must be within [0, 2^31)")
+        nbits, _ = self._per_field(n_fields)
+        sizes = np.array([_align4((n_points + 7) // 8) + _align4((n_points * int(w) + 7) // 8) for w in nbits], dtype=np.uint64)
+        offs = np.zeros(int(n_fields), dtype=np.uint64)
+        if offs.size:
+            offs[1:] = np.cumsum(sizes)[:-1]
+        return offs, int(sizes.sum())
+
+    def encode(self, values):
+        """values: float64, (..., n_points) -- every leading index is one field.  Returns a `GribField` of that shape
+        over a fresh buffer in the layout of `layout`, `bitmaps` set."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if v.ndim < 1:
+            raise ValueError("encode takes at least one axis of points")
+        shape, n = v.shape, int(v.shape[-1])
+        v = v.reshape(-1, n)
+        nf = v.shape[0]
+        nbits, ddiv = self._per_field(nf)
+        offs, total = self.layout(n, nf)
+        buf = np.zeros(total, dtype=np.uint8)
+        rows = np.zeros(nf, dtype=GRIB_ROW_DTYPE)
+        bitmaps = np.zeros(nf, dtype=GRIB_BITMAP_DTYPE)
+        bm_bytes = _align4((n + 7) // 8)
+        for b in range(nf):
+            w, dd, off = int(nbits[b]), float(ddiv[b]), int(offs[b])
+            with np.errstate(over="ignore", invalid="ignore"):
+                t = v[b] * dd
+                present = np.isfinite(v[b]) & (np.abs(t) <= _FLT_MAX)
+            nv = int(present.sum())
+            buf[off:off + (n + 7) // 8] = np.packbits(present)
+            ref, E, width = 0.0, 0, 0
+            if nv:
+                tp = t[present]
+                tmin, tmax = float(tp.min()), float(tp.max())
+                R = np.float32(tmin)
+                if float(R) > tmin:
+                    R = np.nextafter(R, np.float32(-np.inf))
+                ref = float(R) + 0.0
+                rng = tmax - ref
+                if rng != 0.0:
+                    m, e = np.frexp(rng)
+                    E = int(e) - w if float(np.ldexp(m, w)) <= float(2 ** w - 1) else int(e) - w + 1
+                    E = max(E, -1022)
+                    width = w
+                    q = np.rint(np.ldexp(tp - ref, -E)).astype(np.uint64)
+                    bits = ((q[:, None] >> np.arange(w - 1, -1, -1, dtype=np.uint64)) & np.uint64(1)).astype(np.uint8)
+                    packed = np.packbits(bits.ravel())
+                    buf[off + bm_bytes:off + bm_bytes + packed.size] = packed
+            rows[b] = (off + bm_bytes, ref, float(np.ldexp(1.0, E)), dd, width, 0)
+            bitmaps[b] = (GRIB_NO_BITMAP if nv == n else off, nv)
+        return GribField(buf, rows, shape, n, bitmaps=bitmaps)
+
+    def __repr__(self):
+        return f"<GribEncode widths {sorted(set(self.nbits.tolist()))}, D {sorted(set(self.decimal_scale.tolist()))}>"
 
 
 # ECMWF table 128 entries that turn up in climate work -> (cfgrib variable name, long name, units)

@@ -377,17 +377,48 @@ class SparseOperator:
                   float(remap_area_min), fl, _stream_handle(stream))
         return y
 
+    def _apply_host_grib_out(self, buf, rows, rows_p, out, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna,
+                             grib_out):
+        """`apply_host_grib(grib_out=)`: smm_apply_host_grib_pk."""
+        from .griblite import GRIB_BITMAP_DTYPE, GRIB_ROW_DTYPE, GribField
+        n_batch = rows.size
+        _, total = grib_out.layout(self.n_dst, n_batch)
+        if out is None:
+            out = result_cache.empty((max(total, 1),), np.uint8)
+        if out.dtype != np.uint8 or out.ndim != 1 or out.size < total or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous 1-d uint8 array of at least {total} bytes")
+        bm_p = None
+        if bitmaps is not None:
+            bitmaps, bm_p = self._grib_bitmaps(bitmaps, n_batch)
+        rec = grib_out.records(n_batch)
+        rows_out = np.zeros(n_batch, dtype=GRIB_ROW_DTYPE)
+        bitmaps_out = np.zeros(n_batch, dtype=GRIB_BITMAP_DTYPE)
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        _lib.call("smm_apply_host_grib_pk", self.handle, _cptr(buf), buf.size, rows_p, bm_p,
+                  ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribEncodeStruct)), _cptr(out), out.size,
+                  ctypes.cast(rows_out.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)),
+                  ctypes.cast(bitmaps_out.ctypes.data, ctypes.POINTER(_lib.GribBitmapStruct)), n_batch,
+                  float(remap_area_min), fl, int(chunk_rows))
+        return GribField(out, rows_out, (n_batch, self.n_dst), self.n_dst, bitmaps=bitmaps_out)
+
     def apply_host_grib(self, buf, rows, out=None, masked=False, remap_area_min=0.0, flags=0, chunk_rows=0, bitmaps=None,
-                        skipna=False):
+                        skipna=False, grib_out=None):
         """The host twin (smm_apply_host_grib): buf is a host uint8 array -- typically a whole GRIB file -- and rows as
         for `apply_grib`.  Each row's packed bytes are staged and cross PCIe as they are (2 B per cell at 16 bits), no
         host decode runs.  Returns a float64 (B, D) numpy array, the bits of `apply_host` on the decoded float32 field.
         bitmaps as for `apply_grib` (smm_apply_host_grib_bm): a bitmapped row's bitmap bytes are staged behind its data.
-        skipna as for `apply_grib` (smm_apply_host_grib_na): the bits of `apply_host(..., skipna=True)`'s SELL kernel."""
+        skipna as for `apply_grib` (smm_apply_host_grib_na): the bits of `apply_host(..., skipna=True)`'s SELL kernel.
+        grib_out: a `GribEncode` -- the result comes back GRIB simple-packed (smm_apply_host_grib_pk): a `GribField` of
+        shape (B, D) with `bitmaps` set, over `out` (a 1-d uint8 array of at least `grib_out.layout(D, B)` bytes) or a
+        fresh buffer; its bytes and records are those of `grib_out.encode` on the float64 result of the same call
+        without grib_out.  The float64 result never leaves the device."""
         rows, rows_p = self._grib_rows(rows)
         buf = np.ascontiguousarray(buf)
         if buf.dtype != np.uint8 or buf.ndim != 1:
             raise TypeError("apply_host_grib takes the packed bytes as a 1-d uint8 array")
+        if grib_out is not None:
+            return self._apply_host_grib_out(buf, rows, rows_p, out, masked, remap_area_min, flags, chunk_rows, bitmaps,
+                                             skipna, grib_out)
         n_batch = rows.size
         if out is None:
             out = result_cache.empty((n_batch, self.n_dst), np.float64)

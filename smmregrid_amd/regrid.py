@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from .device import CFDecode, CFEncode, DeviceArray, bfloat16, is_half_dtype, is_packed_dtype, to_device
-from .griblite import GribField
+from .griblite import GribEncode, GribField
 from .gridtype import GridType, tolist
 from .lazy import LazyArray, is_dask, map_batch_blocks
 from .operator import OperatorGroup
@@ -58,7 +58,7 @@ class Regridder(object):
                  vertical_dim=None, horizontal_dims=None, cdo_extra=None, cdo_options=None,
                  check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=None,
                  lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False,
-                 packed_levels=False, packed_out=False, packed_out_levels=False, half=False, packed_skipna=False):
+                 packed_levels=False, packed_out=False, packed_out_levels=False, half=False, packed_skipna=False, grib_out=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -102,6 +102,15 @@ class Regridder(object):
         self.packed_skipna = bool(packed_skipna)
         if self.packed_skipna and not (self.packed and self.skipna):
             raise ValueError('packed_skipna=True needs packed=True and skipna=True')
+        # grib_out (with packed=True): a raw GRIB variable on 2-D weights comes back GRIB simple-packed -- a `GribField`
+        # encoded on the device with each source field's own width and decimal scale (GribEncode.from_field;
+        # smm_apply_host_grib_pk), 2 B per cell at 16 bits over PCIe -- which a second Regridder(packed=True) ships raw
+        # again and np.asarray decodes to float32.  Every other variable comes back as without it, with one INFO line
+        self.grib_out = bool(grib_out)
+        if self.grib_out and not self.packed:
+            raise ValueError('grib_out=True needs packed=True')
+        if self.grib_out and self.lazy:
+            raise ValueError('grib_out=True packs an eager result: it does not go with lazy=True')
         # packed_out (with packed=True): a variable regridded raw comes back in its own raw dtype, encoded by the rule
         # of its own attributes (CFEncode) inside the kernels' stores, and keeps its packing attributes: it can be
         # written straight to a file.  Values that round outside the raw range become the fill value (no wrap-around)
@@ -128,6 +137,8 @@ class Regridder(object):
             raise ValueError('out_dtype must be float32 or float64')
         if self.packed_out and self.out_dtype != np.dtype(np.float64):
             raise ValueError('packed_out=True encodes the float64 result: out_dtype must stay float64')
+        if self.grib_out and self.out_dtype != np.dtype(np.float64):
+            raise ValueError('grib_out=True packs the float64 result: out_dtype must stay float64')
         mask_dim = tolist(mask_dim)
         horizontal_dims = tolist(horizontal_dims)
         self.extra_dims = {'mask': mask_dim, 'horizontal': horizontal_dims}
@@ -312,8 +323,13 @@ class Regridder(object):
             # without horizontal or mask dimension is cleaned away, :133-143 -- time_bnds(time, bnds) is one): nothing
             # to regrid, and the empty result is dropped from a Dataset (regrid.py:308-312, :262-264)
             return DataArray(data=None)
-        if isinstance(source_data.data, GribField):
+        was_grib = isinstance(source_data.data, GribField)
+        if was_grib:
             source_data = self._grib_or_decoded(source_data, datagridtype)
+        if self.grib_out and not (isinstance(source_data.data, GribField) and not datagridtype.mask_dim):
+            why = ("masked levels" if isinstance(source_data.data, GribField)
+                   else "decoded on the host" if was_grib else "not a raw GRIB variable")
+            self.loggy.info("grib_out: %s comes back as without it (%s)", source_data.name, why)
         cf = self._packed_rule(source_data) if self.packed else None
         enc = self._packed_out_rule(source_data) if (self.packed_out and cf is not None) else None
         packing = {k: source_data.attrs[k] for k in _CF_PACKING_ATTRS if k in source_data.attrs}
@@ -571,6 +587,10 @@ class Regridder(object):
                 if src.rows.size != n_batch:
                     raise ValueError(f"{src.rows.size} GRIB fields for {n_batch} batch rows of shape {tuple(kept_shape)}")
                 # (with their bitmaps, if any: smm_apply_host_grib_bm ranks them on the device)
+                if self.grib_out:     # the result packed on the device, each field by its source's width and D
+                    y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps,
+                                           skipna=skipna, grib_out=GribEncode.from_field(src))
+                    return GribField(y.buf, y.rows, kept_shape + tgt_shape, op.n_dst, bitmaps=y.bitmaps)
                 y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps,
                                        skipna=skipna)
                 return y.reshape(kept_shape + tgt_shape)
