@@ -558,10 +558,21 @@ int smm_apply_host_grib_na(smm_operator_t op, const void* x_host, int64_t x_byte
  *                           a copy of their own.  SMM_HOST_STAT_D2H_BYTES counts the slots and the records;
  *                           SMM_HOST_STAT_H2D_BYTES also counts 48 B per row of pack tables staged behind the chunk's X.
  *                           The chunk plan budgets the packed buffer and the scratch beside the device-only Y.
+ *   smm_group_apply_host_grib_pk  smm_group_apply_host_grib (below; SMM_APPLY_SKIPNA in flags:
+ *                           smm_group_apply_host_grib_na) with the result packed the same way.  enc, rows_out and
+ *                           bitmaps_out are HOST arrays of n_outer * n_lev * n_inner records in record order (o, l, i);
+ *                           row b owns slot b of smm_grib_out_layout(D, enc, n_rows).  There is no `transpose`: no Y
+ *                           array is delivered.  A chunk is a block of whole outer indices; the grouped gather writes
+ *                           its Y on the device in record order, (rows of the chunk, D), and the four pack steps run
+ *                           behind it on the chunk's stream over all of the chunk's rows.  Pack tables, result copies,
+ *                           the two SMM_HOST_STAT byte counts and the chunk plan's budget are those of
+ *                           smm_apply_host_grib_pk, with never less than one outer index per chunk.
  * SMM_ERR_INVALID, before any device is touched: nbits outside 1..32, a ddiv that is not finite or <= 0, reserved != 0,
  * out_bytes below the layout, a misaligned out (device entry) or y, ldy < n_dst, n_dst >= 2^31, null pointers, a negative
  * count; for the host entry everything smm_apply_host_grib_bm / _na refuses, as they refuse it (SMM_APPLY_KERNEL_TILE
- * included).
+ * included).  The group entry refuses the result side first -- null enc, rows_out or bitmaps_out and a bad encode rule
+ * whatever the handle, out_bytes below the layout and a null out_host once the group gives n_dst -- then everything
+ * smm_group_apply_host_grib / _na refuses, in their order and with their codes.
  */
 int smm_grib_out_layout(int64_t n_dst, const smm_grib_encode_t* enc, int64_t n_batch, uint64_t* byte_off,
                         uint64_t* total_bytes);
@@ -572,6 +583,12 @@ int smm_apply_host_grib_pk(smm_operator_t op, const void* x_host, int64_t x_byte
                            const smm_grib_bitmap_t* bitmaps /* or NULL */, const smm_grib_encode_t* enc,
                            void* out_host, int64_t out_bytes, smm_grib_row_t* rows_out, smm_grib_bitmap_t* bitmaps_out,
                            int64_t n_batch, double remap_area_min, unsigned flags, int64_t chunk_rows);
+int smm_group_apply_host_grib_pk(smm_group_t g, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                                 const smm_grib_bitmap_t* bitmaps /* or NULL */, const smm_grib_encode_t* enc,
+                                 void* out_host, int64_t out_bytes, smm_grib_row_t* rows_out,
+                                 smm_grib_bitmap_t* bitmaps_out, int64_t n_outer, int64_t n_lev, int64_t n_inner,
+                                 const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min,
+                                 unsigned flags, int64_t chunk_outer);
 
 /*
  * Masked-level apply (regrid.py:387-418 in one launch).  The kept dims of the

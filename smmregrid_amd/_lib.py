@@ -193,6 +193,8 @@ SIGNATURES = {
                                 _uint, _p],
     "smm_group_apply_host_grib_na": [_p, _p, _i64, _grp, _gbp, _p, _int, _i64, _i64, _i64, _int, _p, _p, _dbl, _uint,
                                      _i64],
+    "smm_group_apply_host_grib_pk": [_p, _p, _i64, _grp, _gbp, _gep, _p, _i64, _grp, _gbp, _i64, _i64, _i64, _p, _p, _dbl,
+                                     _uint, _i64],
     "smm_group_apply_pk": [_p, _p, _int, _i64, _i64, _i64, _p, _int, _i64, _i64, _i64,
                            _i64, _i64, _i64, _p, _p, _dbl, _uint, _p, _cfp, _cep],
     "smm_group_apply_sb_pk": [_p, _p, _int, _i64, _i64, _p, _int, _i64, _i64, _i64, _i64, _p, _p, _dbl, _uint, _p,

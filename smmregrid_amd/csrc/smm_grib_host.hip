@@ -1,9 +1,10 @@
 // GRIB simple-packed fields shipped raw: the host side of smm_apply_grib(_bm), smm_apply_host_grib(_bm),
 // smm_group_apply_grib and smm_group_apply_host_grib, and of their four SMM_APPLY_SKIPNA twins (_na); and the way back,
-// float64 results into GRIB simple packing: smm_grib_out_layout, smm_grib_pack and smm_apply_host_grib_pk (kernels:
-// smm_grib_pack.hip).  The kernels and their launchers are in smm_grib.hip; what needs no
-// device -- the refusals of a row table, the chunk plan and the layout of a staged chunk -- in smm_grib_plan.cpp.  An
-// operator and a group differ in how a launch grid is cut into parts and in where Y goes; everything else is written once.
+// float64 results into GRIB simple packing: smm_grib_out_layout, smm_grib_pack, smm_apply_host_grib_pk and
+// smm_group_apply_host_grib_pk (kernels: smm_grib_pack.hip).  The kernels and their launchers are in smm_grib.hip; what
+// needs no device -- the refusals of a row table, the chunk plan and the layout of a staged chunk -- in
+// smm_grib_plan.cpp.  An operator and a group differ in how a launch grid is cut into parts and in where Y goes;
+// everything else is written once.
 #include "smm_device.hpp"
 
 namespace {
@@ -317,6 +318,16 @@ uint32_t fill_pack_tables(char* t, const smm_grib_encode_t* enc, int64_t nr, int
   }
   return max_words;
 }
+// What each of n_rows rows' packed result takes on the device beside its Y (smm::plan_grib_chunks' out_row_bytes): its
+// slot, its records, its pack tables and one row's scratch.  Empty without pk.
+std::vector<size_t> grib_out_row_bytes(const GribOut* pk, int64_t n_rows, int64_t D) {
+  std::vector<size_t> out_row;
+  if (!pk) return out_row;
+  const size_t scratch = smm::grib_pack_scratch(D, 1).bytes;
+  for (int64_t b = 0; b < n_rows; ++b)
+    out_row.push_back((size_t)(pk->offs[b + 1] - pk->offs[b]) + smm::kGribOutRecordBytes + smm::kGribPackTableBytes + scratch);
+  return out_row;
+}
 static_assert(sizeof(GribPackRow) + sizeof(GribRowBitmap) == smm::kGribPackTableBytes, "the pack tables of a row");
 static_assert(sizeof(smm_grib_row_t) + sizeof(smm_grib_bitmap_t) == smm::kGribOutRecordBytes, "the records of a row");
 
@@ -361,11 +372,12 @@ int launch_pack(int64_t D, int64_t nr, const double* y, int64_t ldy, const char*
 // buffers, Y into dy -- then Y to the host: y_to_host(ch, src, async, stream) copies the chunk's results from src to
 // their place in the caller's Y, from the slot's device buffer on the stream when Y is page-locked (y_direct), else from
 // the slot's pinned buffer once the chunk has drained.  div: grib_needs_division of the whole call.
-// pk (smm_apply_host_grib_pk), or null: the chunk's Y stays in the slot's device buffer and is packed there, on the
-// chunk's stream, into the slot's packed buffer -- the chunk's row and bitmap records, then its slots.  The pack tables
-// of the chunk ride behind its staged X (8-byte aligned).  y_direct then says that pk->out_host is page-locked: the slots
-// go there straight from the device and only the records pass through the pinned buffer; else both come back in one copy
-// and the slots are copied out once the chunk has drained.  y_to_host is not called.
+// pk (smm_apply_host_grib_pk, smm_group_apply_host_grib_pk), or null: the chunk's Y -- launch_chunk writes it as
+// (ch.nr, D), its rows in record order -- stays in the slot's device buffer and is packed there, on the chunk's stream,
+// into the slot's packed buffer -- the chunk's row and bitmap records, then its slots.  The pack tables of the chunk
+// ride behind its staged X (8-byte aligned).  y_direct then says that pk->out_host is page-locked: the slots go there
+// straight from the device and only the records pass through the pinned buffer; else both come back in one copy and
+// the slots are copied out once the chunk has drained.  y_to_host is not called.
 template <typename Launch, typename YToHost>
 int run_grib_pipeline(HostPipe& pipe, GribState& gs, const smm::GribChunkPlan& plan, const void* x_host,
                       const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t S, int64_t D, bool div, bool y_direct,
@@ -468,12 +480,7 @@ int smm_apply_host_grib_impl(smm_operator_t op, const void* x_host, const smm_gr
   if (n_batch == 0 || D == 0) return SMM_OK;
   DeviceGuard guard(op->device);
   if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the operator's device");
-  std::vector<size_t> out_row;   // pk: what a row's packed result takes on the device beside its Y
-  if (pk) {
-    const size_t scratch = smm::grib_pack_scratch(D, 1).bytes;
-    for (int64_t b = 0; b < n_batch; ++b)
-      out_row.push_back((size_t)(pk->offs[b + 1] - pk->offs[b]) + smm::kGribOutRecordBytes + smm::kGribPackTableBytes + scratch);
-  }
+  const std::vector<size_t> out_row = grib_out_row_bytes(pk, n_batch, D);
   const smm::GribChunkPlan plan = smm::plan_grib_chunks(rows, bitmaps, n_batch, 1, S, D, chunk_rows, free_device_bytes(),
                                                         pk ? out_row.data() : nullptr);
   const size_t yrow = (size_t)ldy * 8;
@@ -526,11 +533,12 @@ int smm_grib_pack_impl(int device, const void* y, int64_t ldy, int64_t D, int64_
 
 // Host buffers, a group: chunks of whole outer indices (units of n_lev * n_inner consecutive records); Y is delivered as
 // the whole-row mode of smm_group_apply_host delivers it, (n_outer, n_inner, n_lev, D) when transpose, else
-// (n_lev, n_outer, n_inner, D).
+// (n_lev, n_outer, n_inner, D).  pk (smm_group_apply_host_grib_pk): no Y is delivered -- a chunk's Y is written in record
+// order, the (ch.nr, D) rows the pipeline's pack reads; transpose is not looked at.
 int smm_group_apply_host_grib_impl(smm_group_t g, const void* x_host, const smm_grib_row_t* rows,
                                    const smm_grib_bitmap_t* bitmaps, void* y_host, int64_t n_outer, int64_t n_lev, int64_t n_inner,
                                    int transpose, const int32_t* level_index, const uint8_t* masked_levels, double area_min,
-                                   unsigned flags, int64_t chunk_outer) {
+                                   unsigned flags, int64_t chunk_outer, const GribOut* pk = nullptr) {
   const int64_t S = g->ops[0]->csr.n_src, D = g->ops[0]->csr.n_dst;
   const int64_t unit = n_lev * n_inner, n_rows = n_outer * unit;
   if (n_rows == 0 || D == 0) return SMM_OK;
@@ -539,11 +547,15 @@ int smm_group_apply_host_grib_impl(smm_group_t g, const void* x_host, const smm_
   const int32_t* d_map;
   const uint8_t* d_masked;
   if (int rc = group_level_cfg(g, n_lev, level_index, masked_levels, area_min, flags, &d_map, &d_masked)) return rc;
-  const smm::GribChunkPlan plan = smm::plan_grib_chunks(rows, bitmaps, n_outer, unit, S, D, chunk_outer, free_device_bytes());
+  const std::vector<size_t> out_row = grib_out_row_bytes(pk, n_rows, D);
+  const smm::GribChunkPlan plan = smm::plan_grib_chunks(rows, bitmaps, n_outer, unit, S, D, chunk_outer, free_device_bytes(),
+                                                        pk ? out_row.data() : nullptr);
   auto launch_chunk = [&](const GribIn& in, const smm::GribChunk& ch, void* dy, hipStream_t s) -> int {
     const int64_t no = ch.nr / unit;
     int64_t ys_o, ys_l, ys_i;   // the chunk's Y on the device, as smm_group_apply_host lays out a whole-row chunk
-    if (transpose) {
+    if (pk) {                   // ... or in record order: row (o, l, i) of the chunk is row (o * n_lev + l) * n_inner + i
+      ys_o = unit * D, ys_l = n_inner * D, ys_i = D;
+    } else if (transpose) {
       ys_o = n_inner * n_lev * D, ys_l = D, ys_i = n_lev * D;
     } else {
       ys_o = n_inner * D, ys_l = no * n_inner * D, ys_i = D;
@@ -569,7 +581,7 @@ int smm_group_apply_host_grib_impl(smm_group_t g, const void* x_host, const smm_
   };
   std::lock_guard<std::mutex> pipe_lock(g->pipe_mu);
   return run_grib_pipeline(g->pipe, g->grib, plan, x_host, rows, bitmaps, S, D, grib_needs_division(rows, n_rows),
-                           is_pinned(y_host), launch_chunk, y_to_host);
+                           is_pinned(pk ? (const void*)pk->out_host : y_host), launch_chunk, y_to_host, pk);
 }
 
 // ---- the four entries behind the extern "C" names.  na: the _na twin -- check_grib_call puts SMM_APPLY_SKIPNA into
@@ -724,6 +736,29 @@ int smm_apply_host_grib_pk(smm_operator_t op, const void* x_host, int64_t x_byte
     const GribOut pk{enc, offs.data(), (char*)out_host, rows_out, bitmaps_out};
     return smm_apply_host_grib_impl(op, x_host, rows, bitmaps, nullptr, op->csr.n_dst, n_batch, remap_area_min, flags,
                                     chunk_rows, &pk);
+  });
+}
+
+int smm_group_apply_host_grib_pk(smm_group_t g, const void* x_host, int64_t x_bytes, const smm_grib_row_t* rows,
+                                 const smm_grib_bitmap_t* bitmaps, const smm_grib_encode_t* enc, void* out_host, int64_t out_bytes,
+                                 smm_grib_row_t* rows_out, smm_grib_bitmap_t* bitmaps_out, int64_t n_outer, int64_t n_lev,
+                                 int64_t n_inner, const int32_t* level_index, const uint8_t* masked_levels,
+                                 double remap_area_min, unsigned flags, int64_t chunk_outer) {
+  return guarded([&] {
+    static const double no_y = 0.0;   // as smm_apply_host_grib_pk: no Y of the caller's to check
+    const bool na = (flags & SMM_APPLY_SKIPNA) != 0;
+    const int64_t n_rows = grib_group_rows(n_outer, n_lev, n_inner);
+    // the result side first; the layout needs the group's n_dst -- without a group the records alone are looked at
+    // (no cell, no slot bytes) and check_grib_group below refuses the handle
+    std::vector<uint64_t> offs;
+    if (int rc = check_grib_out(enc, out_host, false, out_bytes, rows_out, bitmaps_out, g ? g->ops[0]->csr.n_dst : 0, n_rows, offs))
+      return rc;
+    if (int rc = check_grib_call(x_host, false, x_bytes, rows, &no_y, SMM_F64, n_rows, remap_area_min, &flags, na)) return rc;
+    if (int rc = check_grib_group(g, x_bytes, rows, bitmaps, n_rows, n_lev, level_index, masked_levels, remap_area_min, flags))
+      return rc;
+    const GribOut pk{enc, offs.data(), (char*)out_host, rows_out, bitmaps_out};
+    return smm_group_apply_host_grib_impl(g, x_host, rows, bitmaps, nullptr, n_outer, n_lev, n_inner, 1, level_index,
+                                          masked_levels, remap_area_min, flags, chunk_outer, &pk);
   });
 }
 

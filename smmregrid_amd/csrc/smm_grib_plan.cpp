@@ -1,6 +1,7 @@
 // Host side of the GRIB entries that needs no device: the refusals of a row table and of its bitmap records, the chunk
 // plan of the host entries and the layout of a staged chunk (declared in smm_internal.h).  Plain C++:
-// tests/cpp/grib_harness.cpp, grib_bitmap_harness.cpp and grib_levels_harness.cpp link this file.
+// tests/cpp/grib_harness.cpp, grib_bitmap_harness.cpp, grib_levels_harness.cpp, grib_pack_harness.cpp and
+// grib_levels_pack_harness.cpp link this file.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>

@@ -231,8 +231,9 @@ struct GribChunkPlan {
   int64_t max_rows = 0;            // most rows of one chunk
   size_t max_rank = 0;             // largest rank_bytes of one chunk
 };
-// out_row_bytes: null, or per row what its packed result adds on the device beside its Y (smm_apply_host_grib_pk: the
-// row's records, slot and scratch -- grib_pack_row_bytes): counted into the chunk's bytes with the rest.
+// out_row_bytes: null, or per row what its packed result adds on the device beside its Y (smm_apply_host_grib_pk and
+// smm_group_apply_host_grib_pk: the row's slot, records, pack tables and scratch): counted into the chunk's bytes with
+// the rest, per unit.
 GribChunkPlan plan_grib_chunks(const smm_grib_row_t* rows, const smm_grib_bitmap_t* bitmaps, int64_t n_outer, int64_t unit,
                                int64_t n_src, int64_t D, int64_t requested_units, size_t free_bytes,
                                const size_t* out_row_bytes = nullptr);

@@ -658,18 +658,52 @@ class OperatorGroup:
                   n_lev, n_in, _cptr(lev), _cptr(ml), float(remap_area_min), fl, _stream_handle(stream))
         return y
 
+    def _apply_host_grib_out(self, buf, rows_p, bm_p, dims, lev, ml, out, masked, remap_area_min, flags, chunk_outer,
+                             skipna, grib_out):
+        """`apply_host_grib(grib_out=)`: smm_group_apply_host_grib_pk."""
+        from .griblite import GRIB_BITMAP_DTYPE, GRIB_ROW_DTYPE, GribField
+        n_rows = dims[0] * dims[1] * dims[2]
+        _, total = grib_out.layout(self.n_dst, n_rows)
+        if out is None:
+            out = result_cache.empty((max(total, 1),), np.uint8)
+        if out.dtype != np.uint8 or out.ndim != 1 or out.size < total or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous 1-d uint8 array of at least {total} bytes")
+        rec = grib_out.records(n_rows)
+        rows_out = np.zeros(n_rows, dtype=GRIB_ROW_DTYPE)
+        bitmaps_out = np.zeros(n_rows, dtype=GRIB_BITMAP_DTYPE)
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        _lib.call("smm_group_apply_host_grib_pk", self.handle, _cptr(buf), buf.size, rows_p, bm_p,
+                  ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribEncodeStruct)), _cptr(out), out.size,
+                  ctypes.cast(rows_out.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)),
+                  ctypes.cast(bitmaps_out.ctypes.data, ctypes.POINTER(_lib.GribBitmapStruct)), *dims, _cptr(lev), _cptr(ml),
+                  float(remap_area_min), fl, int(chunk_outer))
+        return GribField(out, rows_out, (*dims, self.n_dst), self.n_dst, bitmaps=bitmaps_out)
+
     def apply_host_grib(self, buf, rows, level_index, masked_levels=None, bitmaps=None, out=None, masked=False,
-                        remap_area_min=0.0, transpose=True, flags=0, chunk_outer=0, n_inner=1, skipna=False):
+                        remap_area_min=0.0, transpose=True, flags=0, chunk_outer=0, n_inner=1, skipna=False,
+                        grib_out=None):
         """The host twin (smm_group_apply_host_grib): buf is a host uint8 array -- typically a whole GRIB file -- rows
         and bitmaps as for `apply_grib`.  Blocks of the outer axis stream through the group's pipeline; each row's
         packed bytes (a bitmapped row's: its present cells only, and its bitmap) cross PCIe as they are and no host
         decode runs.  Returns the float64 array `apply_host` returns on the decoded float32 field, bit for bit.
-        skipna as for `apply_grib` (smm_group_apply_host_grib_na)."""
+        skipna as for `apply_grib` (smm_group_apply_host_grib_na).
+        grib_out: a `GribEncode` -- the result comes back GRIB simple-packed (smm_group_apply_host_grib_pk): a
+        `GribField` of shape (n_outer, n_lev, n_inner, D) with `bitmaps` set -- one record per batch row in the order
+        of `rows` -- over `out` (a 1-d uint8 array of at least `grib_out.layout(D, n_rows)[1]` bytes, pageable or from
+        `pinned_empty`) or a fresh buffer; its bytes and records are those of `grib_out.encode` on the float64 result
+        of the same call without grib_out, taken in that order.  No float64 array is delivered, so transpose=False is
+        a ValueError."""
         (n_outer, n_lev, n_in), (rows, rows_p), (bm, bm_p), (lev, ml) = self._grib_args(rows, bitmaps, level_index,
                                                                                          masked_levels, n_inner)
         buf = np.ascontiguousarray(buf)
         if buf.dtype != np.uint8 or buf.ndim != 1:
             raise TypeError("apply_host_grib takes the packed bytes as a 1-d uint8 array")
+        if grib_out is not None:
+            if not transpose:
+                raise ValueError("grib_out returns the rows in record order (n_outer, n_lev, n_inner): "
+                                 "transpose=False does not go with it")
+            return self._apply_host_grib_out(buf, rows_p, bm_p, (n_outer, n_lev, n_in), lev, ml, out, masked,
+                                             remap_area_min, flags, chunk_outer, skipna, grib_out)
         shape = (n_outer, n_in, n_lev, self.n_dst) if transpose else (n_lev, n_outer, n_in, self.n_dst)
         if out is None:
             out = result_cache.empty(shape, np.float64)

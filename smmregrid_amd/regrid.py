@@ -58,7 +58,8 @@ class Regridder(object):
                  vertical_dim=None, horizontal_dims=None, cdo_extra=None, cdo_options=None,
                  check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=None,
                  lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False,
-                 packed_levels=False, packed_out=False, packed_out_levels=False, half=False, packed_skipna=False, grib_out=False):
+                 packed_levels=False, packed_out=False, packed_out_levels=False, half=False, packed_skipna=False, grib_out=False,
+                 grib_out_levels=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -106,11 +107,20 @@ class Regridder(object):
         # encoded on the device with each source field's own width and decimal scale (GribEncode.from_field;
         # smm_apply_host_grib_pk), 2 B per cell at 16 bits over PCIe -- which a second Regridder(packed=True) ships raw
         # again and np.asarray decodes to float32.  Every other variable comes back as without it, with one INFO line
+        # (one on masked-level weights too, unless grib_out_levels=True)
         self.grib_out = bool(grib_out)
         if self.grib_out and not self.packed:
             raise ValueError('grib_out=True needs packed=True')
         if self.grib_out and self.lazy:
             raise ValueError('grib_out=True packs an eager result: it does not go with lazy=True')
+        # grib_out_levels (with grib_out=True and packed_levels=True): a raw GRIB variable on masked-level (3-D) weights
+        # comes back GRIB simple-packed too (smm_group_apply_host_grib_pk) -- a `GribField` with one packed field per
+        # source field, in the source's own order: its dims are the variable's (outer..., level, inner...) followed by
+        # the target's horizontal ones, whatever `transpose` says of a float result.  Off by default: such a variable
+        # comes back float64 with the INFO line, as before
+        self.grib_out_levels = bool(grib_out_levels)
+        if self.grib_out_levels and not (self.grib_out and self.packed_levels):
+            raise ValueError('grib_out_levels=True needs grib_out=True and packed_levels=True')
         # packed_out (with packed=True): a variable regridded raw comes back in its own raw dtype, encoded by the rule
         # of its own attributes (CFEncode) inside the kernels' stores, and keeps its packing attributes: it can be
         # written straight to a file.  Values that round outside the raw range become the fill value (no wrap-around)
@@ -326,7 +336,9 @@ class Regridder(object):
         was_grib = isinstance(source_data.data, GribField)
         if was_grib:
             source_data = self._grib_or_decoded(source_data, datagridtype)
-        if self.grib_out and not (isinstance(source_data.data, GribField) and not datagridtype.mask_dim):
+        grib_out = self.grib_out and isinstance(source_data.data, GribField) and (not datagridtype.mask_dim
+                                                                                 or self.grib_out_levels)
+        if self.grib_out and not grib_out:
             why = ("masked levels" if isinstance(source_data.data, GribField)
                    else "decoded on the host" if was_grib else "not a raw GRIB variable")
             self.loggy.info("grib_out: %s comes back as without it (%s)", source_data.name, why)
@@ -346,11 +358,12 @@ class Regridder(object):
             source_data = self._decode_on_host(source_data, cf)
             cf = None
         if datagridtype.mask_dim and self.packed_out_levels:
-            out = self.regrid3d(source_data, datagridtype, cf=cf, cf_out=enc, out_dtype=out_dtype)   # encoded inside the group kernels
+            out = self.regrid3d(source_data, datagridtype, cf=cf, cf_out=enc, out_dtype=out_dtype,   # encoded inside the
+                                grib_out=grib_out)                                                   # group kernels
             if out.data is None:
                 enc = None
         elif datagridtype.mask_dim:
-            out = self.regrid3d(source_data, datagridtype, cf=cf, out_dtype=out_dtype)
+            out = self.regrid3d(source_data, datagridtype, cf=cf, out_dtype=out_dtype, grib_out=grib_out)
             if enc is not None and out.data is not None:
                 enc = self._encode_on_host(out, enc)      # None when the result stays float64 (device-resident)
         else:
@@ -624,11 +637,12 @@ class Regridder(object):
                             tgt_shape, tgt_dims)
 
     # ------------------------------------------------------------------ apply (masked levels)
-    def regrid3d(self, source_data, datagridtype, cf=None, cf_out=None, out_dtype=None):
+    def regrid3d(self, source_data, datagridtype, cf=None, cf_out=None, out_dtype=None, grib_out=False):
         """regrid.py:339-427 as one grouped launch: per data level the nearest
         weights level (tolerance 1e-3) selects operator, mask and frac.  cf: the CFDecode of a raw int16 / uint16
         field (packed=True, packed_levels=True); cf_out: the CFEncode its result is stored with (packed_out=True,
-        packed_out_levels=True)."""
+        packed_out_levels=True); grib_out: a raw GRIB variable comes back as a `GribField` in its own field order
+        (grib_out_levels=True)."""
         source_data = from_xarray(source_data)
         gridtype = self._get_gridtype(datagridtype)
         if gridtype is None:
@@ -681,6 +695,10 @@ class Regridder(object):
         skipna = self.skipna
         if isinstance(src, GribField) and self._grib_decode_reason(source_data.dims, gridtype, out_dtype, True):
             src = src.decode()      # a direct call: only the raw road of _grib_or_decoded ships the bit streams
+        grib_out = bool(grib_out) and isinstance(src, GribField) and not self.lazy
+        if grib_out:      # one packed field per source field, in the source's order: no transpose
+            out_dims = kept_dims + tgt_dims
+            out_shape = [source_data.sizes[d] for d in kept_dims] + tgt_shape
         ship_half = self._ships_half(getattr(src, "dtype", None))
         sb_in = isinstance(src, DeviceArray) and src.layout == "sb"
         if sb_in:
@@ -706,6 +724,12 @@ class Regridder(object):
                 if src.rows.size != n_outer * n_lev * n_inner:
                     raise ValueError(f"{src.rows.size} GRIB fields for batch rows of shape {(n_outer, n_lev, n_inner)}")
                 dims3 = (n_outer, n_lev, n_inner)
+                if grib_out:     # the result packed on the device, each field by its source's width and D
+                    y = group.apply_host_grib(src.buf, src.rows.reshape(dims3), level_index, masked_levels,
+                                              bitmaps=None if src.bitmaps is None else src.bitmaps.reshape(dims3),
+                                              masked=any_masked, remap_area_min=area_min, skipna=skipna,
+                                              grib_out=GribEncode.from_field(src))
+                    return GribField(y.buf, y.rows, out_shape, D, bitmaps=y.bitmaps)
                 out = group.apply_host_grib(src.buf, src.rows.reshape(dims3), level_index, masked_levels,
                                             bitmaps=None if src.bitmaps is None else src.bitmaps.reshape(dims3),
                                             masked=any_masked, remap_area_min=area_min, transpose=transpose, skipna=skipna)
