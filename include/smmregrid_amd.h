@@ -156,6 +156,36 @@ typedef struct smm_grib_encode_t {   /* 16 B */
   int32_t reserved;   /* 0 */
 } smm_grib_encode_t;
 
+/* A GRIB-2 field in CCSDS packing (data representation template 5.42; smm_grib_aec_unpack, smm_grib_aec_decode_host):
+ * where the adaptive-entropy-coded stream of one batch row lies in x and the parameters it was written with.  The
+ * stream decodes to n_values unsigned integers of nbits bits -- the q of smm_grib_row_t's rule.  flags are the
+ * message's ccsdsFlags octet as it is (libaec's AEC_* bits): SMM_GRIB_AEC_PREPROCESS switches the unit-delay predictor
+ * on; SMM_GRIB_AEC_MSB and SMM_GRIB_AEC_3BYTE describe the encoder's sample container, not the stream, and are
+ * ignored; SMM_GRIB_AEC_SIGNED, SMM_GRIB_AEC_RESTRICTED, SMM_GRIB_AEC_PAD_RSI and every other bit are refused. */
+enum {
+  SMM_GRIB_AEC_SIGNED = 1u << 0,
+  SMM_GRIB_AEC_3BYTE = 1u << 1,
+  SMM_GRIB_AEC_MSB = 1u << 2,
+  SMM_GRIB_AEC_PREPROCESS = 1u << 3,
+  SMM_GRIB_AEC_RESTRICTED = 1u << 4,
+  SMM_GRIB_AEC_PAD_RSI = 1u << 5
+};
+typedef struct smm_grib_aec_t {   /* one batch row = one GRIB field, 48 B */
+  uint64_t byte_off;    /* of the stream's first byte, from x */
+  uint64_t byte_len;    /* bytes of the stream */
+  uint64_t n_values;    /* samples the stream codes: the grid's points, or the set bits of the row's bitmap; < 2^31 */
+  int32_t nbits;        /* 0..32; 0 = constant field, no stream (block_size, rsi and flags are not looked at) */
+  int32_t block_size;   /* 8, 16, 32 or 64 */
+  int32_t rsi;          /* reference sample interval in blocks, 1..4096 */
+  uint32_t flags;       /* ccsdsFlags */
+  uint64_t reserved;    /* 0 */
+} smm_grib_aec_t;
+/* how a row's stream ended */
+enum { SMM_GRIB_AEC_OK = 0, SMM_GRIB_AEC_EXHAUSTED = 1, SMM_GRIB_AEC_INVALID = 2 };
+/* bins of smm_grib_aec_decode_host's histogram, in order: zero-block run, zero-block run "to the end of the segment",
+ * second extension, split-sample k = 0, split-sample k > 0, uncompressed, blocks that carry a reference sample */
+#define SMM_GRIB_AEC_OPTIONS 7
+
 /* smm_apply flags.  Bits outside this set are refused with SMM_ERR_INVALID by every entry that takes `flags`
  * (ABI <= 4 encoded kernel variants in bits 16..23: those are smm_debug_set_tuning knobs now). */
 enum {
@@ -589,6 +619,38 @@ int smm_group_apply_host_grib_pk(smm_group_t g, const void* x_host, int64_t x_by
                                  smm_grib_bitmap_t* bitmaps_out, int64_t n_outer, int64_t n_lev, int64_t n_inner,
                                  const int32_t* level_index, const uint8_t* masked_levels, double remap_area_min,
                                  unsigned flags, int64_t chunk_outer);
+
+/*
+ * CCSDS-packed GRIB-2 fields (smm_grib_aec_t above) on the raw road: one device step turns the rows' adaptive-
+ * entropy-coded streams into the simple-packed streams smm_apply_grib_bm / _na take -- the mirror of smm_grib_pack.
+ * Row b's integers are stored with the row's own width nbits, big-endian, at a 4-byte-aligned offset of `out`, rows back
+ * to back in row order, every byte of every slot written (a slot is ceil(n_values * nbits / 8) bytes rounded up to 4).
+ * Three kernels: one wave per row parses the stream block after block (all lanes take part in a block: the wave finds
+ * the ends of its fundamental sequences by popcounts and a scan) into 4 bytes per sample of scratch; one lane per
+ * reference sample interval inverts the preprocessor, tiles of the scratch passing through LDS; one thread per 32-bit
+ * word packs the stream.  The decoder and its two rules are the text of smmregrid_amd/csrc/smm_grib_aec.hpp.
+ *   smm_grib_aec_layout       host only: byte_off[b] (may be NULL) = where row b's stream starts in `out`,
+ *                             *total_bytes = all of them.
+ *   smm_grib_aec_unpack       x: device bytes, 4-byte aligned, the allocation covering x_bytes rounded up to 4; recs and
+ *                             rows_in: HOST arrays of n_batch records; out: device, 4-byte aligned, out_bytes >= the
+ *                             layout's total.  rows_out[b] (HOST) = rows_in[b] with byte_off the row's place in `out`.
+ *                             A row with nbits == 0 passes through untouched.  Scratch is allocated and freed inside
+ *                             the call; the stream is synchronised before it returns.  A row whose stream does not end
+ *                             ok makes the call return SMM_ERR_INVALID, smm_last_error naming the first such row.
+ *   smm_grib_aec_decode_host  one row decoded on the host, no device: values[n_values] receives the integers,
+ *                             histogram (SMM_GRIB_AEC_OPTIONS counters, or NULL) is ADDED to, *status is how the stream
+ *                             ended (SMM_GRIB_AEC_*).  x_host needs no alignment.  A malformed stream costs wrong
+ *                             numbers and a status, never a read outside [0, x_bytes).
+ * SMM_ERR_INVALID, before any device is touched: null pointers, a negative count, nbits outside 0..32, a block size
+ * outside {8, 16, 32, 64}, rsi outside 1..4096, a refused flag, reserved != 0, n_values >= 2^31, a stream that leaves
+ * [0, x_bytes), rows_in[b].nbits != recs[b].nbits, out_bytes below the layout, a misaligned x or out.
+ */
+int smm_grib_aec_layout(const smm_grib_aec_t* recs, int64_t n_batch, uint64_t* byte_off, uint64_t* total_bytes);
+int smm_grib_aec_unpack(int device, const void* x, int64_t x_bytes, const smm_grib_aec_t* recs /* host */,
+                        const smm_grib_row_t* rows_in /* host */, int64_t n_batch, void* out, int64_t out_bytes,
+                        smm_grib_row_t* rows_out /* host */, void* stream);
+int smm_grib_aec_decode_host(const void* x_host, int64_t x_bytes, const smm_grib_aec_t* rec, uint32_t* values,
+                             uint64_t* histogram, int* status);
 
 /*
  * Masked-level apply (regrid.py:387-418 in one launch).  The kept dims of the

@@ -105,6 +105,22 @@ class GribEncodeStruct(ctypes.Structure):
 
 
 _gep = ctypes.POINTER(GribEncodeStruct)
+
+
+class GribAecStruct(ctypes.Structure):
+    """smm_grib_aec_t: where the CCSDS stream of one GRIB field lies in the bytes and the parameters it was coded with"""
+    _fields_ = [("byte_off", ctypes.c_uint64), ("byte_len", ctypes.c_uint64), ("n_values", ctypes.c_uint64),
+                ("nbits", ctypes.c_int32), ("block_size", ctypes.c_int32), ("rsi", ctypes.c_int32),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint64)]
+
+
+_gap = ctypes.POINTER(GribAecStruct)
+GRIB_AEC_OK, GRIB_AEC_EXHAUSTED, GRIB_AEC_INVALID = 0, 1, 2
+GRIB_AEC_SIGNED, GRIB_AEC_3BYTE, GRIB_AEC_MSB, GRIB_AEC_PREPROCESS, GRIB_AEC_RESTRICTED, GRIB_AEC_PAD_RSI = (
+    1, 2, 4, 8, 16, 32)
+# the bins of smm_grib_aec_decode_host's histogram, in order
+GRIB_AEC_OPTIONS = ("zero_block", "zero_block_ros", "second_extension", "split_k0", "split_k", "uncompressed",
+                    "reference")
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 
 # name -> argtypes; every entry point returns int status except the two noted
@@ -175,6 +191,9 @@ SIGNATURES = {
     "smm_grib_out_layout": [_i64, _gep, _i64, _u64p, _u64p],
     "smm_grib_pack": [_int, _p, _i64, _i64, _i64, _gep, _p, _i64, _grp, _gbp, _p],
     "smm_apply_host_grib_pk": [_p, _p, _i64, _grp, _gbp, _gep, _p, _i64, _grp, _gbp, _i64, _dbl, _uint, _i64],
+    "smm_grib_aec_layout": [_gap, _i64, _u64p, _u64p],
+    "smm_grib_aec_unpack": [_int, _p, _i64, _gap, _grp, _i64, _p, _i64, _grp, _p],
+    "smm_grib_aec_decode_host": [_p, _i64, _gap, ctypes.POINTER(ctypes.c_uint32), _u64p, ctypes.POINTER(_int)],
     "smm_group_apply": [_p, _p, _int, _i64, _i64, _i64, _p, _int, _i64, _i64, _i64,
                         _i64, _i64, _i64, _p, _p, _dbl, _uint, _p],
     "smm_group_prepare_sb": [_p],

@@ -155,6 +155,39 @@ uint64_t grib_out_layout(int64_t n_dst, const smm_grib_encode_t* enc, int64_t n_
   return at;
 }
 
+bool check_grib_aec(const smm_grib_aec_t* recs, int64_t n_batch, int64_t x_bytes, std::string& err) {
+  constexpr uint32_t kKnown = SMM_GRIB_AEC_SIGNED | SMM_GRIB_AEC_3BYTE | SMM_GRIB_AEC_MSB | SMM_GRIB_AEC_PREPROCESS |
+                              SMM_GRIB_AEC_RESTRICTED | SMM_GRIB_AEC_PAD_RSI;
+  for (int64_t b = 0; b < n_batch; ++b) {
+    const smm_grib_aec_t& r = recs[b];
+    const std::string at = "recs[" + std::to_string(b) + "]";
+    if (r.nbits < 0 || r.nbits > 32) return err = at + ".nbits must be within 0..32", false;
+    if (r.reserved != 0) return err = at + ".reserved must be 0", false;
+    if (r.n_values >= ((uint64_t)1 << 31)) return err = at + ".n_values must be below 2^31", false;
+    if (r.nbits == 0) continue;   // a constant field has no stream
+    if (r.block_size != 8 && r.block_size != 16 && r.block_size != 32 && r.block_size != 64)
+      return err = at + ".block_size must be 8, 16, 32 or 64", false;
+    if (r.rsi < 1 || r.rsi > 4096) return err = at + ".rsi must be within 1..4096", false;
+    if (r.flags & SMM_GRIB_AEC_SIGNED) return err = at + ".flags: AEC_DATA_SIGNED (signed samples) is not decoded", false;
+    if (r.flags & SMM_GRIB_AEC_RESTRICTED) return err = at + ".flags: AEC_RESTRICTED (the restricted code set) is not decoded", false;
+    if (r.flags & SMM_GRIB_AEC_PAD_RSI) return err = at + ".flags: AEC_PAD_RSI (byte-padded intervals) is not decoded", false;
+    if (r.flags & ~kKnown) return err = at + ".flags has bits outside ccsdsFlags", false;
+    if (r.byte_off > (uint64_t)x_bytes || r.byte_len > (uint64_t)x_bytes - r.byte_off)
+      return err = at + ": bytes [" + std::to_string(r.byte_off) + ", " + std::to_string(r.byte_off) + " + " +
+                   std::to_string(r.byte_len) + ") leave the buffer of " + std::to_string(x_bytes) + " bytes", false;
+  }
+  return true;
+}
+
+uint64_t grib_aec_layout(const smm_grib_aec_t* recs, int64_t n_batch, uint64_t* byte_off) {
+  uint64_t at = 0;
+  for (int64_t b = 0; b < n_batch; ++b) {
+    if (byte_off) byte_off[b] = at;
+    at += smm_grib::align4(smm_grib::row_bytes(recs[b].n_values, recs[b].nbits));
+  }
+  return at;
+}
+
 GribPackScratch grib_pack_scratch(int64_t n_dst, int64_t n_rows) {
   const size_t n = (size_t)std::max<int64_t>(n_rows, 0);
   const size_t segs = n * (size_t)smm_grib::bitmap_segments((uint64_t)n_dst);

@@ -9,6 +9,7 @@
 struct smm_grib_row_t;   // include/smmregrid_amd.h
 struct smm_grib_bitmap_t;
 struct smm_grib_encode_t;
+struct smm_grib_aec_t;
 
 namespace smm {
 
@@ -253,6 +254,12 @@ GribPackScratch grib_pack_scratch(int64_t n_dst, int64_t n_rows);
 constexpr size_t kGribOutRecordBytes = 40 + 16;
 // the pack tables of a row staged behind a chunk's X: GribPackRow + GribRowBitmap (smm_grib.hpp, smm_grib_codec.hpp)
 constexpr size_t kGribPackTableBytes = 32 + 16;
+// ---- CCSDS-packed fields (smm_grib_aec_unpack, smm_grib_aec_decode_host; smm_grib_plan.cpp).  What the entries refuse
+// about the records -- nbits 0..32, reserved 0, n_values < 2^31 and, for a row with a stream (nbits > 0), a block size of
+// 8 / 16 / 32 / 64, rsi 1..4096, the refused flags and a stream inside [0, x_bytes): false + err
+bool check_grib_aec(const smm_grib_aec_t* recs, int64_t n_batch, int64_t x_bytes, std::string& err);
+// the layout of the transcoded streams: byte_off[b] (may be null) = start of row b's; returns the bytes of all
+uint64_t grib_aec_layout(const smm_grib_aec_t* recs, int64_t n_batch, uint64_t* byte_off);
 // Where a chunk's pieces lie in its staging buffer hx (ch.x_bytes bytes, 8-byte aligned), written into hx: the table first
 // -- the rows' records with byte_off the staged offset of the row's data -- then, with bitmaps, their records
 // (GribRowBitmap, smm_grib_codec.hpp: bitmap_off a staged offset too, table_off the place of the row's rank table among

@@ -560,6 +560,38 @@ def grib_pack(y, enc, n_points=None, out=None, stream=None):
     return out, rows, bitmaps
 
 
+def grib_unpack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None):
+    """Turn the CCSDS streams of GRIB-2 fields (template 5.42) resident in HBM into simple-packed streams on the device
+    (smm_grib_aec_unpack).  device_bytes: a uint8 `DeviceArray` holding the streams (the array must cover x_bytes
+    rounded up to 4); rows: one GRIB_ROW_DTYPE record per field (its R, 2^E, 10^D and width); ccsds: one GRIB_AEC_DTYPE
+    record per field (where its stream lies, how many integers it codes, block size, interval, flags).  Returns
+    (DeviceArray of uint8, GRIB_ROW_DTYPE records): each field's integers big-endian with the field's own width at a
+    4-byte-aligned offset -- what `SparseOperator.apply_grib(x, rows, bitmaps=...)` takes as it is.  A field of width 0
+    passes through untouched.  out: a uint8 DeviceArray to unpack into.  The stream is synchronised on return."""
+    from .griblite import GRIB_AEC_DTYPE, GRIB_ROW_DTYPE
+    if not isinstance(device_bytes, DeviceArray) or device_bytes.dtype != np.uint8:
+        raise TypeError("grib_unpack takes the coded bytes as a uint8 DeviceArray")
+    rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
+    ccsds = np.ascontiguousarray(ccsds, dtype=GRIB_AEC_DTYPE).ravel()
+    if ccsds.size != rows.size:
+        raise ValueError(f"{ccsds.size} CCSDS records for {rows.size} rows")
+    n_bytes = device_bytes.nbytes if x_bytes is None else int(x_bytes)
+    if (n_bytes + 3) // 4 * 4 > device_bytes.nbytes:
+        raise ValueError(f"the array must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {device_bytes.nbytes}")
+    aec_p = ctypes.cast(ccsds.ctypes.data, ctypes.POINTER(_lib.GribAecStruct))
+    total = ctypes.c_uint64(0)
+    _lib.call("smm_grib_aec_layout", aec_p, rows.size, None, ctypes.byref(total))
+    if out is None:
+        out = DeviceArray((max(total.value, 4),), np.uint8)
+    elif not isinstance(out, DeviceArray) or out.dtype != np.uint8 or out.nbytes < total.value:
+        raise ValueError(f"out must be a uint8 DeviceArray of at least {total.value} bytes")
+    rows_out = np.zeros(rows.size, dtype=GRIB_ROW_DTYPE)
+    _lib.call("smm_grib_aec_unpack", current_device(), ctypes.c_void_p(device_bytes.ptr), n_bytes, aec_p,
+              ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)), rows.size, ctypes.c_void_p(out.ptr),
+              out.nbytes, ctypes.cast(rows_out.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)), _stream_handle(stream))
+    return out, rows_out
+
+
 def empty(shape, dtype=np.float64):
     if not isinstance(shape, tuple):
         shape = tuple(np.atleast_1d(shape).tolist())

@@ -20,12 +20,16 @@ when a file holds more than one of them, missing points as NaN, float32 fields.
 
 Edition 2 (WMO FM 92 GRIB edition 2; what newer IFS / ICON output comes in) is decoded for the same family: sections
 0 - 8, grid definition templates 3.0 (lon/lat) and 3.40 (Gaussian, regular or with the list of points per row),
-product definition templates 4.0 / 4.1 / 4.8 / 4.11 (the leading octets they share), data representation template 5.0
-(simple packing, IEEE reference value), bitmap section, several fields per message (repeated sections 2 - 7).
+product definition templates 4.0 / 4.1 / 4.8 / 4.11 (the leading octets they share), data representation templates 5.0
+(simple packing, IEEE reference value) and 5.42 (CCSDS packing: the same rule on integers that an adaptive entropy
+coder compressed; decoded by the library's host decoder, smm_grib_aec_decode_host), bitmap section, several fields per
+message (repeated sections 2 - 7).
 
-Anything else in a GRIB file (spherical harmonics, second-order / JPEG / PNG / CCSDS packing, rotated or projected
-grids) raises GribUnsupported naming the feature.
+Anything else in a GRIB file (spherical harmonics, second-order / JPEG / PNG packing, rotated or projected grids)
+raises GribUnsupported naming the feature.
 """
+import ctypes
+
 import numpy as np
 
 from .xrlite import DataArray, Dataset
@@ -53,6 +57,38 @@ GRIB_ENCODE_DTYPE = np.dtype({"names": ["ddiv", "nbits", "reserved"], "formats":
                               "offsets": [0, 8, 12], "itemsize": 16})
 
 
+# smm_grib_aec_t, field for field: one record per GRIB field of a raw-kept variable some of whose messages are CCSDS-packed
+# (template 5.42) -- where the message's coded stream lies in the file, how many integers it codes and with which
+# parameters.  block_size == 0: the field is simple-packed, its row record says it all
+GRIB_AEC_DTYPE = np.dtype({"names": ["byte_off", "byte_len", "n_values", "nbits", "block_size", "rsi", "flags", "reserved"],
+                           "formats": ["<u8", "<u8", "<u8", "<i4", "<i4", "<i4", "<u4", "<u8"],
+                           "offsets": [0, 8, 16, 24, 28, 32, 36, 40], "itemsize": 48})
+# ccsdsFlags (libaec's AEC_* bits): the preprocessor switch is honoured, the two container bits say nothing about the
+# stream, the others are refused
+_AEC_PREPROCESS = 8
+_AEC_REFUSED = {1: "AEC_DATA_SIGNED (signed samples)", 16: "AEC_RESTRICTED (the restricted code set)",
+                32: "AEC_PAD_RSI (byte-padded reference sample intervals)"}
+
+
+def aec_decode(buf, rec, histogram=None):
+    """The unsigned integers (uint32) of one CCSDS stream: `rec` a GRIB_AEC_DTYPE record over the bytes `buf`, decoded
+    by the library on the host (smm_grib_aec_decode_host; no GPU involved).  histogram: a uint64 array of 7 counters the
+    coding options taken are added to (`_lib.GRIB_AEC_OPTIONS`).  A stream that does not end ok is a ValueError."""
+    from . import _lib
+    rec = np.ascontiguousarray(rec, dtype=GRIB_AEC_DTYPE).reshape(1)
+    raw = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf)
+    out = np.empty(int(rec["n_values"][0]), dtype=np.uint32)
+    status = ctypes.c_int(0)
+    hist = None if histogram is None else histogram.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    _lib.call("smm_grib_aec_decode_host", ctypes.c_void_p(raw.ctypes.data if raw.size else None), raw.size,
+              ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribAecStruct)),
+              out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), hist, ctypes.byref(status))
+    if status.value != _lib.GRIB_AEC_OK:
+        raise ValueError("CCSDS stream " + ("ends before its values do" if status.value == _lib.GRIB_AEC_EXHAUSTED
+                                            else "is invalid"))
+    return out
+
+
 class GribField:
     """The fields of one GRIB variable kept as the file has them: `buf`, the file's bytes (one uint8 array shared by
     every variable of the file), and `rows`, a GRIB_ROW_DTYPE record per field in (time, level) order that says where
@@ -61,17 +97,23 @@ class GribField:
     `Regridder(packed=True)` hands buf and rows to the GPU as they are (smm_apply_host_grib): the bits are unpacked in
     the kernel, with the results of regridding `decode()`.  `bitmaps` is None, or a GRIB_BITMAP_DTYPE record per field
     (open_grib(path, decode=False, bitmaps=True) on a variable with bitmapped messages): the stream of a bitmapped
-    field holds its present points only, the others are NaN (smm_apply_host_grib_bm)."""
+    field holds its present points only, the others are NaN (smm_apply_host_grib_bm).  `ccsds` is None, or a
+    GRIB_AEC_DTYPE record per field (a variable with CCSDS-packed messages, template 5.42): such a field's q are what
+    its coded stream decodes to -- on the GPU for `Regridder(packed=True)` (smm_grib_aec_unpack ahead of the gather),
+    on the host for `decode()`; a record with block_size 0 marks a simple-packed field among them."""
 
     dtype = np.dtype(np.float32)
 
-    def __init__(self, buf, rows, shape, n_points, bitmaps=None):
+    def __init__(self, buf, rows, shape, n_points, bitmaps=None, ccsds=None):
         """n_points: grid points of one field -- the product of the trailing (horizontal) axes of `shape`."""
         self.buf = buf
         self.rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
         self.bitmaps = None if bitmaps is None else np.ascontiguousarray(bitmaps, dtype=GRIB_BITMAP_DTYPE).ravel()
         if self.bitmaps is not None and self.bitmaps.size != self.rows.size:
             raise ValueError(f"{self.bitmaps.size} bitmap records for {self.rows.size} GRIB fields")
+        self.ccsds = None if ccsds is None else np.ascontiguousarray(ccsds, dtype=GRIB_AEC_DTYPE).ravel()
+        if self.ccsds is not None and self.ccsds.size != self.rows.size:
+            raise ValueError(f"{self.ccsds.size} CCSDS records for {self.rows.size} GRIB fields")
         self.shape = tuple(int(n) for n in shape)
         self.n_points = int(n_points)
         if self.rows.size * self.n_points != int(np.prod(self.shape)):
@@ -93,7 +135,8 @@ class GribField:
             bm = None
             if self.bitmaps is not None and int(self.bitmaps[i]["bitmap_off"]) != GRIB_NO_BITMAP:
                 bm = (int(self.bitmaps[i]["bitmap_off"]), int(self.bitmaps[i]["n_values"]))
-            out[i] = _decode_rule(self.buf, rule, self.n_points, bm)
+            aec = None if self.ccsds is None or int(self.ccsds[i]["block_size"]) == 0 else self.ccsds[i]
+            out[i] = _decode_rule(self.buf, rule, self.n_points, bm, aec)
         return out.reshape(self.shape)
 
     def __array__(self, dtype=None, copy=None):
@@ -102,8 +145,10 @@ class GribField:
 
     def __repr__(self):
         n_bm = 0 if self.bitmaps is None else int((self.bitmaps["bitmap_off"] != GRIB_NO_BITMAP).sum())
+        n_aec = 0 if self.ccsds is None else int((self.ccsds["block_size"] != 0).sum())
         return (f"<GribField {self.shape} float32, {self.rows.size} packed fields, widths "
-                f"{sorted(set(self.rows['nbits'].tolist()))}" + (f", {n_bm} with a bitmap>" if n_bm else ">"))
+                f"{sorted(set(self.rows['nbits'].tolist()))}" + (f", {n_aec} CCSDS-packed" if n_aec else "")
+                + (f", {n_bm} with a bitmap>" if n_bm else ">"))
 
 
 _FLT_MAX = float(np.finfo(np.float32).max)
@@ -298,14 +343,20 @@ def _unpack_bits(raw, nbits, count):
     return bits.astype(np.uint64) @ (np.uint64(1) << np.arange(nbits - 1, -1, -1, dtype=np.uint64))
 
 
-def _decode_rule(buf, rule, count, bitmap=None):
+def _decode_rule(buf, rule, count, bitmap=None, aec=None):
     """The float64 values of one message from its rule (file offset of the packed values, R, 2^E, 10^D, bit width):
     the statement the message classes evaluate, on the message's own bytes only.  bitmap: None, or (file offset of the
-    bitmap's bytes, values in the stream) -- the values go to the points whose bit is set, the others are NaN."""
+    bitmap's bytes, values in the stream) -- the values go to the points whose bit is set, the others are NaN.
+    aec: None, or the GRIB_AEC_DTYPE record of a CCSDS-packed message -- its integers come out of the coded stream."""
     off, ref, scale, ddiv, nbits = rule
     n = count if bitmap is None else bitmap[1]
-    raw = bytes(memoryview(buf)[off:off + (n * nbits + 7) // 8])
-    packed = (ref + _unpack_bits(raw, nbits, n) * scale) / ddiv
+    if aec is not None and nbits:
+        if int(aec["n_values"]) != n:
+            raise ValueError(f"CCSDS stream of {int(aec['n_values'])} values for {n} points")
+        q = aec_decode(buf, aec).astype(np.float64)
+    else:
+        q = _unpack_bits(bytes(memoryview(buf)[off:off + (n * nbits + 7) // 8]), nbits, n)
+    packed = (ref + q * scale) / ddiv
     if bitmap is None:
         return packed
     present = np.unpackbits(np.frombuffer(bytes(memoryview(buf)[bitmap[0]:bitmap[0] + (count + 7) // 8]),
@@ -334,9 +385,13 @@ class _Field:
     keep_raw (only its `raw_rule` was recorded, and with keep_bitmaps the `raw_bitmap` of a message that has one: file
     offset of the bitmap's bytes and values in the stream); `field_values` decodes it on demand."""
     raw_bitmap = None
+    raw_aec = None        # the GRIB_AEC_DTYPE fields of a CCSDS-packed message (edition 2, template 5.42)
 
     def field_values(self, buf):
-        return self.values if self.values is not None else _decode_rule(buf, self.raw_rule, self.npoints, self.raw_bitmap)
+        if self.values is not None:
+            return self.values
+        aec = None if self.raw_aec is None else np.array(self.raw_aec, dtype=GRIB_AEC_DTYPE)
+        return _decode_rule(buf, self.raw_rule, self.npoints, self.raw_bitmap, aec)
 
     def _set_grid(self, rep, ni, nj, la1, lo1, la2, lo2, n_gauss, scan, pl, tol):
         if scan & 0x20:
@@ -488,6 +543,30 @@ class _Message(_Field):
         self._set_grid(rep, ni, nj, la1, lo1, la2, lo2, _uint(gds[25:27]), gds[27], pl, tol=2e-3)
 
 
+def _ccsds_template(sec5):
+    """Data representation template 5.42 (CCSDS packing) from section 5: (R, 2^E, D, bits per value, ccsdsFlags,
+    ccsdsBlockSize, ccsdsRsi).  Octets 12 - 20 are those of template 5.0 (R, E, D, bits per value; 21 = type of the
+    original values), 22 = ccsdsFlags, 23 = ccsdsBlockSize, 24 - 25 = ccsdsRsi -- taken from the WMO table; no file
+    written by ecCodes was at hand to pin them.  A flag the decoder does not take raises GribUnsupported naming it."""
+    if len(sec5) < 25:
+        raise GribUnsupported(f"GRIB-2 data representation template 5.42 (CCSDS packing) in a section 5 of {len(sec5)} "
+                              "octets: the template takes 25")
+    ref = float(np.frombuffer(bytes(sec5[11:15]), dtype=">f4")[0])
+    scale, decimal, nbits = 2.0 ** _sint(sec5[15:17]), _sint(sec5[17:19]), sec5[19]
+    flags, block, rsi = sec5[21], sec5[22], _uint(sec5[23:25])
+    for bit, what in _AEC_REFUSED.items():
+        if flags & bit:
+            raise GribUnsupported(f"CCSDS packing with ccsdsFlags {what}")
+    if flags & ~0x3F:
+        raise GribUnsupported(f"CCSDS packing with ccsdsFlags {flags:#x}: bits outside the flag table")
+    if nbits > 32:
+        raise GribUnsupported(f"CCSDS packing of {nbits} bits per value")
+    if nbits and (block not in (8, 16, 32, 64) or not 1 <= rsi <= 4096):
+        raise GribUnsupported(f"CCSDS packing with block size {block} and reference sample interval {rsi} "
+                              "(8 / 16 / 32 / 64 and 1..4096 are decoded)")
+    return ref, scale, decimal, nbits, flags, block, rsi
+
+
 class _Field2(_Field):
     """One field of a GRIB-2 message (a message may repeat sections 2 - 7 / 3 - 7 / 4 - 7 for further fields)."""
     edition = 2
@@ -534,12 +613,19 @@ class _Field2(_Field):
         self.level = level / 100.0 if self.level_type == 100 else level          # Pa -> hPa, as cfgrib's isobaricInhPa
         # --- section 5 / 6 / 7: packed values
         n_coded, drt = _uint(sec5[5:9]), _uint(sec5[9:11])
-        if drt != 0:
+        if drt not in (0, 42):
             names = {2: "complex packing", 3: "complex packing with spatial differencing", 40: "JPEG 2000 packing",
-                     41: "PNG packing", 42: "CCSDS packing", 50: "spherical harmonics", 51: "spherical harmonics"}
+                     41: "PNG packing", 50: "spherical harmonics", 51: "spherical harmonics"}
             raise GribUnsupported(f"GRIB-2 data representation template 5.{drt} ({names.get(drt, 'not simple packing')})")
-        ref = float(np.frombuffer(bytes(sec5[11:15]), dtype=">f4")[0])
-        scale, decimal, nbits = 2.0 ** _sint(sec5[15:17]), _sint(sec5[17:19]), sec5[19]
+        aec = None         # CCSDS: (ccsdsFlags, ccsdsBlockSize, ccsdsRsi); a constant field (0 bits) has no stream
+        if drt == 42:
+            ref, scale, decimal, nbits, *aec = _ccsds_template(sec5)
+            aec = tuple(aec) if nbits else None
+        else:
+            ref = float(np.frombuffer(bytes(sec5[11:15]), dtype=">f4")[0])
+            scale, decimal, nbits = 2.0 ** _sint(sec5[15:17]), _sint(sec5[17:19]), sec5[19]
+        if aec is not None and data_pos is not None:
+            self.raw_aec = (data_pos + 5, len(sec7) - 5, n_coded, nbits, aec[1], aec[2], aec[0], 0)
         indicator = sec6[5] if sec6 is not None else 255
         if keep_raw and bitmap_pos is not None and data_pos is not None and indicator in (0, 254):
             # kept raw with its bitmap: where the bitmap lies and how many bits it sets, nothing unpacked
@@ -549,7 +635,7 @@ class _Field2(_Field):
             self.bitmap = None
             if n_coded != self.raw_bitmap[1]:
                 raise ValueError(f"GRIB-2 data section codes {n_coded} values, grid and bitmap need {self.raw_bitmap[1]}")
-            if nbits and (len(sec7) - 5) * 8 < n_coded * nbits:
+            if nbits and aec is None and (len(sec7) - 5) * 8 < n_coded * nbits:
                 raise ValueError("GRIB-2 data section is shorter than its values")
             self.raw_rule = (data_pos + 5, ref, scale, 10.0 ** decimal, nbits)
             self.values = None
@@ -567,14 +653,19 @@ class _Field2(_Field):
         count = self.npoints if self.bitmap is None else int(self.bitmap.sum())
         if n_coded != count:
             raise ValueError(f"GRIB-2 data section codes {n_coded} values, grid and bitmap need {count}")
-        if nbits and (len(sec7) - 5) * 8 < count * nbits:
+        if nbits and aec is None and (len(sec7) - 5) * 8 < count * nbits:
             raise ValueError("GRIB-2 data section is shorter than its values")
         self.raw_rule = None if (self.bitmap is not None or data_pos is None) else \
             (data_pos + 5, ref, scale, 10.0 ** decimal, nbits)
         if keep_raw and self.raw_rule is not None:
             self.values = None
             return
-        packed = (ref + _unpack_bits(bytes(sec7[5:]), nbits, count) * scale) / 10.0 ** decimal
+        if aec is not None:       # the message's own stream, decoded on the host
+            q = aec_decode(bytes(sec7[5:]), np.array((0, len(sec7) - 5, count, nbits, aec[1], aec[2], aec[0], 0),
+                                                     dtype=GRIB_AEC_DTYPE)).astype(np.float64)
+        else:
+            q = _unpack_bits(bytes(sec7[5:]), nbits, count)
+        packed = (ref + q * scale) / 10.0 ** decimal
         if self.bitmap is None:
             self.values = packed
         else:
@@ -647,7 +738,9 @@ def open_grib(path, decode=True, bitmaps=False):
     they are; `np.asarray` of it is the decoded float32 array.  Any other variable is decoded as with decode=True.
     bitmaps=True (with decode=False) keeps messages with a bitmap section raw as well (edition 1 section 3; edition 2
     section 6 with its own bitmap or the previous field's): the reader records where the bitmap lies and how many bits
-    it sets, `GribField.bitmaps` holds one record per field, and a variable may mix messages with and without one."""
+    it sets, `GribField.bitmaps` holds one record per field, and a variable may mix messages with and without one.
+    CCSDS-packed messages (edition 2, template 5.42) are decoded on the host with decode=True and kept raw like the
+    others with decode=False: `GribField.ccsds` holds one record per field, simple-packed fields may stand among them."""
     with open(path, "rb") as f:
         file_bytes = f.read()
     msgs = _messages_of(file_bytes, path, keep_raw=not decode, keep_bitmaps=bool(bitmaps) and not decode)
@@ -698,12 +791,15 @@ def open_grib(path, decode=True, bitmaps=False):
         filled = np.zeros((len(times), len(levels)), dtype=bool)
         bms = np.zeros((len(times), len(levels)), dtype=GRIB_BITMAP_DTYPE)
         bms["bitmap_off"], bms["n_values"] = GRIB_NO_BITMAP, g.npoints
+        aecs = np.zeros((len(times), len(levels)), dtype=GRIB_AEC_DTYPE)
         for m, slot in zip(group, slots):
             if m.raw_rule is not None:
                 rows[slot] = m.raw_rule + (0,)
                 filled[slot] = True
                 if m.raw_bitmap is not None:
                     bms[slot] = m.raw_bitmap
+                if m.raw_aec is not None:
+                    aecs[slot] = m.raw_aec
         # raw: every (time, level) slot filled by a message without a bitmap (a missing slot is NaN, which only a
         # decoded array holds).  Such a variable is never unpacked here; any other is decoded as with decode=True
         raw_ok = not decode and all(m.raw_rule is not None for m in group) and bool(filled.all())
@@ -726,9 +822,10 @@ def open_grib(path, decode=True, bitmaps=False):
         shape = tuple(n for n, keep in ((len(times), len(times) > 1), (len(levels), len(levels) > 1)) if keep) + hshape
         if raw_ok:
             if len(times) == 1:
-                rows, bms = rows[0:1], bms[0:1]
+                rows, bms, aecs = rows[0:1], bms[0:1], aecs[0:1]
             arr = GribField(shared, rows, shape, int(np.prod(hshape)),
-                            bitmaps=bms if any(m.raw_bitmap is not None for m in group) else None)
+                            bitmaps=bms if any(m.raw_bitmap is not None for m in group) else None,
+                            ccsds=aecs if any(m.raw_aec is not None for m in group) else None)
         else:
             arr = arr.reshape(shape)
         ds[name] = DataArray(arr, dims=tuple(dims) + hdims, coords=vcoords, name=name,

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .device import (DeviceArray, bfloat16, check_half_pair, dtype_code, field_dtype_code, is_half_dtype,
-                     is_packed_dtype, result_cache, result_dtype, _stream_handle, current_device)
+                     is_packed_dtype, result_cache, result_dtype, _stream_handle, current_device, grib_unpack, mem_info)
 
 
 def _cptr(a):
@@ -332,8 +332,33 @@ class SparseOperator:
             raise ValueError(f"{bitmaps.size} bitmap records for {n_batch} rows")
         return bitmaps, ctypes.cast(bitmaps.ctypes.data, ctypes.POINTER(_lib.GribBitmapStruct))
 
+    @staticmethod
+    def _ccsds_records(ccsds, rows):
+        """(records, which rows have a coded stream, bytes of their transcoded streams): a record with block_size 0
+        marks a simple-packed row, a row of width 0 has no stream at all."""
+        from .griblite import GRIB_AEC_DTYPE
+        ccsds = np.ascontiguousarray(ccsds, dtype=GRIB_AEC_DTYPE).ravel()
+        if ccsds.size != rows.size:
+            raise ValueError(f"{ccsds.size} CCSDS records for {rows.size} rows")
+        idx = np.flatnonzero((ccsds["block_size"] != 0) & (rows["nbits"] != 0))
+        sub = np.ascontiguousarray(ccsds[idx])
+        total = ctypes.c_uint64(0)
+        _lib.call("smm_grib_aec_layout", ctypes.cast(sub.ctypes.data, ctypes.POINTER(_lib.GribAecStruct)), sub.size, None,
+                  ctypes.byref(total))
+        return ccsds, idx, int(total.value)
+
+    @staticmethod
+    def _ccsds_unpack(src, n_bytes, dst, shift, rows, ccsds, idx, stream):
+        """smm_grib_aec_unpack of rows `idx`: their streams in src[:n_bytes] become simple-packed streams in dst.  Returns
+        the row table with those rows pointing at `shift` + their place in dst, the others as they were."""
+        _, rows_c = grib_unpack(src, rows[idx], ccsds[idx], x_bytes=n_bytes, out=dst, stream=stream)
+        rows = rows.copy()
+        rows_c["byte_off"] += np.uint64(shift)
+        rows[idx] = rows_c
+        return rows
+
     def apply_grib(self, x, rows, x_bytes=None, y=None, masked=False, remap_area_min=0.0, flags=0, stream=None,
-                   bitmaps=None, skipna=False):
+                   bitmaps=None, skipna=False, ccsds=None):
         """Y = epilogue(fill(decode(X)) . W) for GRIB simple-packed fields resident in HBM as they are on disk
         (smm_apply_grib).  x: a `DeviceArray` of uint8 -- or a raw device pointer with x_bytes -- holding the packed
         bit streams (4-byte aligned; the array -- or the allocation behind a raw pointer -- must cover x_bytes rounded
@@ -345,8 +370,28 @@ class SparseOperator:
         `GRIB_NO_BITMAP`, and how many values its stream holds.  A cell whose bit is 0 is NaN, as the host decode has
         it; the cell's rank in the stream is looked up in a table built on the device ahead of the gather.
         skipna: renormalise over the valid source values of each row (smm_apply_grib_na) -- the bits of
-        `apply(..., skipna=True, flags=APPLY_KERNEL_SELL)` on the decoded float32 field, NaN where the bitmap is 0."""
+        `apply(..., skipna=True, flags=APPLY_KERNEL_SELL)` on the decoded float32 field, NaN where the bitmap is 0.
+        ccsds: one `GRIB_AEC_DTYPE` record per row -- x holds the CCSDS streams of GRIB-2 template 5.42 (a record with
+        block_size 0: that row is simple-packed).  One device step ahead of the gather turns them into simple-packed
+        streams (smm_grib_aec_unpack); the result has the bits of the same call on the simple-packed integers."""
         rows, rows_p = self._grib_rows(rows)
+        if ccsds is not None:
+            if not isinstance(x, DeviceArray) or x.dtype != np.uint8:
+                raise TypeError("apply_grib(ccsds=) takes the coded bytes as a uint8 DeviceArray")
+            n_bytes = x.nbytes if x_bytes is None else int(x_bytes)
+            if (n_bytes + 3) // 4 * 4 > x.nbytes:
+                raise ValueError(f"x must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {x.nbytes}")
+            ccsds, idx, total = self._ccsds_records(ccsds, rows)
+            # bitmaps and simple-packed rows stay where they are in x: then x travels along in front of the new streams
+            keep = bitmaps is not None or idx.size < int((rows["nbits"] != 0).sum())
+            base = (n_bytes + 3) // 4 * 4 if keep else 0
+            both = DeviceArray((max(base + total, 4),), np.uint8)
+            if keep and base:
+                _lib.call("smm_memcpy_d2d", ctypes.c_void_p(both.ptr), ctypes.c_void_p(x.ptr), base, _stream_handle(stream))
+            dst = DeviceArray((total,), np.uint8, ptr=both.ptr + base, base=both)
+            rows = self._ccsds_unpack(x, n_bytes, dst, base, rows, ccsds, idx, stream)
+            return self.apply_grib(both, rows, x_bytes=base + total, y=y, masked=masked, remap_area_min=remap_area_min,
+                                   flags=flags, stream=stream, bitmaps=bitmaps, skipna=skipna)
         if isinstance(x, DeviceArray):
             if x.dtype != np.uint8:
                 raise TypeError(f"apply_grib takes the packed bytes as uint8, got {x.dtype}")
@@ -401,8 +446,76 @@ class SparseOperator:
                   float(remap_area_min), fl, int(chunk_rows))
         return GribField(out, rows_out, (n_batch, self.n_dst), self.n_dst, bitmaps=bitmaps_out)
 
+    def _apply_host_grib_ccsds(self, buf, rows, out, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds):
+        """`apply_host_grib(ccsds=)`: a synchronous loop over chunks of consecutive rows -- the chunk's coded bytes (and
+        bitmaps) staged and copied to the device, smm_grib_aec_unpack behind them into the same buffer, the device
+        gather (smm_apply_grib_bm / _na), Y copied back.  A chunk's staged bytes, transcoded streams, 4 B per sample of
+        scratch and Y stay within 256 MiB and a quarter of the free device memory; chunk_rows > 0 fixes the rows."""
+        from .griblite import GRIB_NO_BITMAP
+        n_batch, S, D = rows.size, self.n_src, self.n_dst
+        if bitmaps is not None:
+            bitmaps, _ = self._grib_bitmaps(bitmaps, n_batch)
+        if out is None:
+            out = result_cache.empty((n_batch, D), np.float64)
+        if out.shape != (n_batch, D) or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous float64 ({n_batch}, {D}) array")
+        ccsds, idx, _ = self._ccsds_records(ccsds, rows)
+        coded = np.zeros(n_batch, dtype=bool)
+        coded[idx] = True
+        align4 = lambda v: (v + 3) // 4 * 4                                               # noqa: E731
+        has_bm = np.zeros(n_batch, dtype=bool) if bitmaps is None else bitmaps["bitmap_off"] != GRIB_NO_BITMAP
+        n_val = np.full(n_batch, S, dtype=np.int64) if bitmaps is None else \
+            np.where(has_bm, bitmaps["n_values"], S).astype(np.int64)
+        if (ccsds["n_values"][idx].astype(np.int64) != n_val[idx]).any():
+            raise ValueError("a CCSDS record's n_values differs from the points its row holds")
+        nbits = rows["nbits"].astype(np.int64)
+        in_off = np.where(coded, ccsds["byte_off"], rows["byte_off"]).astype(np.uint64)
+        in_len = np.where(coded, ccsds["byte_len"].astype(np.int64), (n_val * nbits + 7) // 8).astype(np.int64)
+        bm_len = (S + 7) // 8
+        if ((in_off.astype(object) + in_len.astype(object)) > buf.size).any() or \
+                (has_bm.any() and (bitmaps["bitmap_off"][has_bm].astype(object) + bm_len > buf.size).any()):
+            raise ValueError(f"a row's bytes leave the buffer of {buf.size} bytes")
+        cost = align4(in_len) + np.where(coded, align4((n_val * nbits + 7) // 8) + 4 * n_val, 0) + D * 8 + \
+            np.where(has_bm, align4(bm_len), 0)
+        free, _ = mem_info()
+        target = min(256 << 20, max(free // 4, 1))
+        fl = int(flags)
+        r0 = 0
+        while r0 < n_batch:
+            r1, used = r0, 0
+            while r1 < n_batch and (r1 - r0 < chunk_rows if chunk_rows > 0 else (r1 == r0 or used + int(cost[r1]) <= target)):
+                used += int(cost[r1])
+                r1 += 1
+            rows_c, aec_c = rows[r0:r1].copy(), ccsds[r0:r1].copy()
+            bm_c = None if bitmaps is None else bitmaps[r0:r1].copy()
+            pieces, at, seen = [], 0, {}
+            for i in range(r0, r1):
+                (aec_c if coded[i] else rows_c)["byte_off"][i - r0] = at
+                pieces.append((at, int(in_off[i]), int(in_len[i])))
+                at += align4(int(in_len[i]))
+                if has_bm[i]:                      # a bitmap several rows share is staged once
+                    off = int(bitmaps["bitmap_off"][i])
+                    if off not in seen:
+                        seen[off] = at
+                        pieces.append((at, off, bm_len))
+                        at += align4(bm_len)
+                    bm_c["bitmap_off"][i - r0] = seen[off]
+            staged = np.zeros(max(at, 4), dtype=np.uint8)
+            for a, off, n in pieces:
+                staged[a:a + n] = buf[off:off + n]
+            _, idx_c, total = self._ccsds_records(aec_c, rows_c)
+            both = DeviceArray((max(at + total, 4),), np.uint8)
+            src = DeviceArray((staged.size,), np.uint8, ptr=both.ptr, base=both).copy_from_host(staged)
+            dst = DeviceArray((total,), np.uint8, ptr=both.ptr + at, base=both)
+            rows_c = self._ccsds_unpack(src, at, dst, at, rows_c, aec_c, idx_c, None)
+            y = self.apply_grib(both, rows_c, x_bytes=at + total, masked=masked, remap_area_min=remap_area_min, flags=fl,
+                                bitmaps=bm_c, skipna=skipna)
+            y.to_host(out=out[r0:r1])
+            r0 = r1
+        return out
+
     def apply_host_grib(self, buf, rows, out=None, masked=False, remap_area_min=0.0, flags=0, chunk_rows=0, bitmaps=None,
-                        skipna=False, grib_out=None):
+                        skipna=False, grib_out=None, ccsds=None):
         """The host twin (smm_apply_host_grib): buf is a host uint8 array -- typically a whole GRIB file -- and rows as
         for `apply_grib`.  Each row's packed bytes are staged and cross PCIe as they are (2 B per cell at 16 bits), no
         host decode runs.  Returns a float64 (B, D) numpy array, the bits of `apply_host` on the decoded float32 field.
@@ -411,11 +524,18 @@ class SparseOperator:
         grib_out: a `GribEncode` -- the result comes back GRIB simple-packed (smm_apply_host_grib_pk): a `GribField` of
         shape (B, D) with `bitmaps` set, over `out` (a 1-d uint8 array of at least `grib_out.layout(D, B)` bytes) or a
         fresh buffer; its bytes and records are those of `grib_out.encode` on the float64 result of the same call
-        without grib_out.  The float64 result never leaves the device."""
+        without grib_out.  The float64 result never leaves the device.
+        ccsds as for `apply_grib`: the rows' CCSDS streams cross PCIe as they are and are decoded on the device, chunk
+        by chunk (a synchronous loop: no copy overlaps a kernel).  It does not go with grib_out."""
         rows, rows_p = self._grib_rows(rows)
         buf = np.ascontiguousarray(buf)
         if buf.dtype != np.uint8 or buf.ndim != 1:
             raise TypeError("apply_host_grib takes the packed bytes as a 1-d uint8 array")
+        if ccsds is not None:
+            if grib_out is not None:
+                raise ValueError("ccsds does not go with grib_out: decode the field on the host first")
+            return self._apply_host_grib_ccsds(buf, rows, out, masked, remap_area_min, flags, int(chunk_rows), bitmaps, skipna,
+                                               ccsds)
         if grib_out is not None:
             return self._apply_host_grib_out(buf, rows, rows_p, out, masked, remap_area_min, flags, chunk_rows, bitmaps,
                                              skipna, grib_out)

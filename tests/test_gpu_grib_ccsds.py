@@ -1,0 +1,234 @@
+"""CCSDS-packed GRIB-2 fields on the GPU (smm_grib_aec_unpack; `grib_unpack`, `apply_grib(ccsds=)`,
+`apply_host_grib(ccsds=)`, `Regridder(packed=True)` on a CCSDS variable).  Every comparison is bit for bit: against
+the fixtures' integers (tests/golden/ccsds, written by libaec's encoder) and against the same call on the simple-packed
+twin of those integers.  Malformed streams are the business of tests/test_grib_ccsds.py."""
+import numpy as np
+import pytest
+
+from smmregrid_amd import (GRIB_AEC_DTYPE, GRIB_BITMAP_DTYPE, GRIB_NO_BITMAP, GRIB_ROW_DTYPE, CdoGenerate, GribField, Regridder,
+                           SparseOperator, _lib, grib_unpack, to_device)
+from smmregrid_amd.io import open_dataset
+from smmregrid_amd.lazy import LazyArray
+from tests import ccsds_cases as cc
+
+pytestmark = pytest.mark.gpu
+S = cc.NI * cc.NJ            # 2048 source cells
+GRID_ROWS = ["grid_w12_smooth", "grid_w16_runs", "grid_w8_near_constant", "grid_w24_noise", "grid_w32_extremes",
+             "grid_w17_sparse", "grid_w1_bits", "grid_w16_rough"]                                   # B = 8, all different
+SHORT_ROWS = ["short_w16_smooth", "short_w12_rough", "short_w24_runs"]                              # 1500 values: bitmapped
+
+
+def same_bits(got, want, what=""):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype == np.float64, (what, got.shape, want.shape, got.dtype)
+    diff = got.view(np.uint64) != want.view(np.uint64)
+    assert not diff.any(), f"{what}: {int(diff.sum())} results differ in their bits, first at {np.argwhere(diff)[:3].tolist()}"
+
+
+def rules(n, seed=1):
+    """R, 2^E, 10^D of n rows: different in every row, with and without the division."""
+    rng = np.random.default_rng(seed)
+    rows = np.zeros(n, dtype=GRIB_ROW_DTYPE)
+    rows["ref"] = np.float32(rng.uniform(-300.0, 300.0, n))
+    rows["bscale"] = np.ldexp(1.0, rng.integers(-12, 3, n))
+    rows["ddiv"] = 10.0 ** rng.integers(0, 3, n)
+    return rows
+
+
+def build(names, bitmapped=(), simple=(), seed=1):
+    """The rows `names` as one CCSDS call and as its simple-packed twin: (buf, rows, ccsds, bitmaps) twice.  Streams lie
+    at odd offsets with garbage between them.  bitmapped: {row: row whose bitmap it shares, or itself}; simple: rows
+    that are simple-packed in the CCSDS call too (block_size 0)."""
+    fxs = [cc.fixture(n) for n in names]
+    rows = rules(len(fxs), seed)
+    rows["nbits"] = [f.nbits for f in fxs]
+    twin_rows, aec = rows.copy(), np.zeros(len(fxs), dtype=GRIB_AEC_DTYPE)
+    bms = np.zeros(len(fxs), dtype=GRIB_BITMAP_DTYPE)
+    bms["bitmap_off"], bms["n_values"] = GRIB_NO_BITMAP, S
+    twin_bms = bms.copy()
+    parts, twin_parts = [], []
+
+    def put(store, data):
+        at = sum(p.size for p in store) + 3                       # three bytes of garbage ahead of every piece
+        store.extend([np.full(3, 0xA5, np.uint8), np.asarray(data, np.uint8)])
+        return at
+    present = cc.message_present()
+    for i, f in enumerate(fxs):
+        packed = cc.pack_bits(f.values, f.nbits)
+        twin_rows["byte_off"][i] = put(twin_parts, packed)
+        if i in simple:
+            rows["byte_off"][i] = put(parts, packed)
+        else:
+            rows["byte_off"][i] = off = put(parts, f.stream)
+            aec[i] = (off, f.stream.size, f.n_values, f.nbits, f.block, f.rsi, f.flags, 0)
+    for i, owner in dict(bitmapped).items():
+        assert fxs[i].n_values == 1500
+        if owner == i:
+            bits = np.packbits(present)
+            bms["bitmap_off"][i], twin_bms["bitmap_off"][i] = put(parts, bits), put(twin_parts, bits)
+        else:
+            bms["bitmap_off"][i], twin_bms["bitmap_off"][i] = bms["bitmap_off"][owner], twin_bms["bitmap_off"][owner]
+        bms["n_values"][i] = twin_bms["n_values"][i] = 1500
+    use_bm = bool(bitmapped)
+    return ((np.concatenate(parts), rows, aec, bms if use_bm else None),
+            (np.concatenate(twin_parts), twin_rows, None, twin_bms if use_bm else None))
+
+
+def device_bytes(buf):
+    padded = np.full((buf.size + 3) // 4 * 4, 0x5A, dtype=np.uint8)
+    padded[:buf.size] = buf
+    return to_device(padded)
+
+
+_OP = []
+
+
+def operator():
+    """2048 source cells, 333 destination rows (no multiple of 64), three links a row, one row without links, an
+    epilogue."""
+    if not _OP:
+        rng = np.random.default_rng(3)
+        n_dst = 333
+        dst = np.repeat(np.arange(1, n_dst + 1), 3)
+        dst = dst[dst != 6]
+        src = rng.integers(1, S + 1, size=dst.size)
+        src[:3] = (1, S, S)
+        op = SparseOperator(S, n_dst, src, dst, rng.random(dst.size), device=0)
+        op.set_epilogue((rng.random(n_dst) > 0.2).astype(np.int32), rng.random(n_dst))
+        _OP.append(op)
+    return _OP[0]
+
+
+# ------------------------------------------------------------------------------------------------ grib_unpack
+def test_grib_unpack_gives_every_fixtures_integers_in_one_call(hip):
+    """All fixtures as the rows of one call -- every width, block size, interval and both preprocessor settings mixed,
+    5 to 2048 values -- and a constant row among them: each slot holds the bytes of the simple-packed twin, zero-padded to
+    4, and decodes to the floats of the fixture's integers."""
+    fxs = cc.fixtures()
+    rows = rules(len(fxs) + 1, seed=2)
+    aec = np.zeros(len(fxs) + 1, dtype=GRIB_AEC_DTYPE)
+    parts, at = [], 0
+    for i, f in enumerate(fxs):
+        parts += [np.full(1 + i % 3, 0xA5, np.uint8), f.stream]
+        at += 1 + i % 3
+        rows["nbits"][i] = f.nbits
+        aec[i] = (at, f.stream.size, f.n_values, f.nbits, f.block, f.rsi, f.flags, 0)
+        at += f.stream.size
+    rows["nbits"][-1], rows["byte_off"][-1] = 0, 12345                     # passes through untouched
+    aec[-1] = (0, 0, 77, 0, 0, 0, 0, 0)
+    buf = np.concatenate(parts)
+    filled = to_device(np.full(1 << 17, 0xFF, dtype=np.uint8))
+    out, rows_out = grib_unpack(device_bytes(buf), rows, aec, x_bytes=buf.size, out=filled)
+    host = out.to_host()
+    assert rows_out[-1].tobytes() == rows[-1].tobytes()
+    end = 0
+    for i, f in enumerate(fxs):
+        r = rows_out[i]
+        assert (r["ref"], r["bscale"], r["ddiv"], r["nbits"]) == (rows[i]["ref"], rows[i]["bscale"], rows[i]["ddiv"], f.nbits)
+        off = int(r["byte_off"])
+        assert off == end and off % 4 == 0, (f, off, end)                  # back to back, 4-byte aligned
+        twin = cc.pack_bits(f.values, f.nbits)
+        slot = (twin.size + 3) // 4 * 4
+        want = np.zeros(slot, np.uint8)
+        want[:twin.size] = twin
+        assert np.array_equal(host[off:off + slot], want), f
+        got = GribField(host, rows_out[i:i + 1], (1, f.n_values), f.n_values).decode()
+        twin_row = rows[i:i + 1].copy()
+        twin_row["byte_off"] = 0
+        ref = GribField(twin, twin_row, (1, f.n_values), f.n_values).decode()
+        assert got.tobytes() == ref.tobytes(), f
+        end = off + slot
+    assert (host[end:] == 0xFF).all()                                      # nothing behind the layout is written
+
+
+# ------------------------------------------------------------------------------------------------ the gather behind it
+CASES = {"plain": dict(names=GRID_ROWS),
+         "bitmaps": dict(names=GRID_ROWS[:4] + SHORT_ROWS + GRID_ROWS[4:5], bitmapped={4: 4, 5: 4, 6: 6}),
+         # short_w16_smooth owns the bitmap, the two others share it; grid_w16_runs and short_w12_rough stay simple-packed
+         "mixed": dict(names=GRID_ROWS[:5] + SHORT_ROWS, bitmapped={5: 5, 6: 5, 7: 5}, simple=(1, 6))}
+
+
+@pytest.mark.parametrize("skipna", [False, True])
+@pytest.mark.parametrize("case", list(CASES))
+def test_apply_grib_and_apply_host_grib_have_the_bits_of_the_simple_packed_twin(hip, case, skipna):
+    """B = 8 rows of different widths and coding parameters in one call; with bitmaps (one shared by two rows); with
+    simple-packed rows among the CCSDS ones; plain and under skipna; the host form with chunk_rows=3 (8 = 3 + 3 + 2)."""
+    op = operator()
+    (buf, rows, aec, bms), (tbuf, trows, _, tbms) = build(**CASES[case])
+    for masked, area_min in ((False, 0.0), (True, 0.5)):
+        common = dict(masked=masked, remap_area_min=area_min, skipna=skipna)
+        want = op.apply_grib(device_bytes(tbuf), trows, x_bytes=tbuf.size, bitmaps=tbms, **common).to_host()
+        assert np.isfinite(want).any() and (case == "plain" or skipna or np.isnan(want).any())
+        got = op.apply_grib(device_bytes(buf), rows, x_bytes=buf.size, bitmaps=bms, ccsds=aec, **common).to_host()
+        same_bits(got, want, f"apply_grib {case} {common}")
+        for chunk_rows in (0, 3):
+            got = op.apply_host_grib(buf, rows, bitmaps=bms, ccsds=aec, chunk_rows=chunk_rows, **common)
+            same_bits(got, want, f"apply_host_grib {case} chunk_rows={chunk_rows} {common}")
+        same_bits(op.apply_host_grib(tbuf, trows, bitmaps=tbms, **common), want, "the twin's own host form")
+
+
+# ------------------------------------------------------------------------------------------------ Regridder
+def same_arrays(got, want, what):
+    same_bits(np.asarray(got.values), np.asarray(want.values), what)
+    assert got.dims == want.dims and got.attrs == want.attrs and got.name == want.name, what
+    assert list(got.coords) == list(want.coords), what
+    for k in got.coords:
+        assert np.array_equal(got.coords[k].values, want.coords[k].values), (what, k)
+
+
+@pytest.fixture(scope="module")
+def ccsds_file(tmp_path_factory):
+    path = tmp_path_factory.mktemp("ccsds") / "t_ccsds.grib2"
+    path.write_bytes(cc.grib2_message(cc.message_fields(True), cc.NI, cc.NJ))
+    return str(path)
+
+
+def test_regridder_ships_a_ccsds_variable_raw(hip, ccsds_file, caplog, monkeypatch):
+    dec, raw = open_dataset(ccsds_file), open_dataset(ccsds_file, decode=False, bitmaps=True)
+    f = raw["t"].data
+    assert isinstance(f, GribField) and f.ccsds is not None and f.bitmaps is not None and np.isnan(dec["t"].values).any()
+    w = CdoGenerate(dec["t"], "r16x8").weights(method="con")
+    want = Regridder(weights=w).regrid(dec["t"])
+    assert want.dtype == np.float64 and np.isfinite(want.values).any()
+    names = []
+    real = _lib.call
+    monkeypatch.setattr(_lib, "call", lambda name, *a: names.append(name) or real(name, *a))
+    caplog.clear()
+    with caplog.at_level("INFO"):
+        got = Regridder(weights=w, packed=True, loglevel="INFO").regrid(raw["t"])
+    assert not any("decoded on the host" in r.getMessage() or r.levelname == "WARNING" for r in caplog.records)
+    assert names.count("smm_grib_aec_unpack") == 1 and names.count("smm_apply_grib_bm") == 1
+    assert "smm_grib_aec_decode_host" not in names and "smm_apply_host" not in names
+    same_arrays(got, want, "packed=True on the CCSDS variable")
+    # under skipna the raw road renormalises in the gather
+    want_na = Regridder(weights=w, skipna=True).regrid(dec["t"])
+    del names[:]
+    got_na = Regridder(weights=w, packed=True, skipna=True, packed_skipna=True).regrid(raw["t"])
+    assert names.count("smm_grib_aec_unpack") == 1 and names.count("smm_apply_grib_na") == 1
+    same_arrays(got_na, want_na, "skipna")
+    # lazy
+    lazy = Regridder(weights=w, packed=True, lazy=True).regrid(raw["t"])
+    assert isinstance(lazy.data, LazyArray)
+    same_bits(np.asarray(lazy.values), want.values, "lazy")
+    # what does not take the road decodes on the host with one INFO line and gives the bits of the decoded variable
+    for kw, word in ((dict(out_dtype=np.float32), "out_dtype float32"), (dict(grib_out=True), "grib_out")):
+        caplog.clear()
+        with caplog.at_level("INFO"):
+            fb = Regridder(weights=w, packed=True, loglevel="INFO", **kw).regrid(raw["t"])
+        lines = [r.getMessage() for r in caplog.records if "is decoded on the host" in r.getMessage()]
+        assert len(lines) == 1 and word in lines[0], lines
+        ref = Regridder(weights=w, **{k: v for k, v in kw.items() if k != "grib_out"}).regrid(dec["t"])
+        assert fb.dtype == ref.dtype and np.array_equal(np.asarray(fb.values).view(np.uint8), ref.values.view(np.uint8)), word
+
+
+def test_regridder_decodes_a_ccsds_variable_on_the_host_for_masked_levels(hip, ccsds_file, caplog):
+    dec, raw = open_dataset(ccsds_file), open_dataset(ccsds_file, decode=False, bitmaps=True)
+    w3 = CdoGenerate(dec["t"], "r16x8").weights(method="con", mask_dim="isobaricInhPa")
+    want = Regridder(weights=w3).regrid(dec["t"])
+    for kw in (dict(), dict(packed_levels=True)):
+        caplog.clear()
+        with caplog.at_level("INFO"):
+            got = Regridder(weights=w3, packed=True, loglevel="INFO", **kw).regrid(raw["t"])
+        lines = [r.getMessage() for r in caplog.records if "is decoded on the host" in r.getMessage()]
+        assert len(lines) == 1 and "CCSDS" in lines[0] and "masked levels" in lines[0], lines
+        same_arrays(got, want, f"masked levels {kw}")
