@@ -653,6 +653,46 @@ int smm_grib_aec_decode_host(const void* x_host, int64_t x_bytes, const smm_grib
                              uint64_t* histogram, int* status);
 
 /*
+ * The way back: simple-packed streams on the device coded as CCSDS streams (template 5.42), behind the four passes of
+ * smm_grib_pack or on any rows an smm_grib_row_t table describes.  THE RULE OF THIS ENCODER is the text of
+ * smmregrid_amd/csrc/smm_grib_aec.hpp: the option with the fewest bits per block, the split parameter searched
+ * exhaustively, zero blocks joined into runs within a 64-block segment.  It is fully deterministic -- the host entry and
+ * the kernels give the same bytes -- and it is not libaec's choice of bits: a valid CCSDS 121.0-B stream that
+ * smm_grib_aec_decode_host, smm_grib_aec_unpack and libaec decode.  recs are the parameters WANTED per row: n_values
+ * and nbits as the row has them, block_size, rsi and flags to code with (what smm_grib_aec_unpack takes, no more);
+ * byte_off and byte_len are not read.
+ *   smm_grib_aec_pack_bound   host only: the worst case per row, ceil(n_values / block_size) blocks of
+ *                             id length + block_size * nbits bits, rounded up to bytes and then to 4 (derived: no block
+ *                             is coded longer than uncompressed); byte_off[b] (may be NULL) = the sum before row b,
+ *                             *total_bytes = the sum.
+ *   smm_grib_aec_pack         x: device bytes, 4-byte aligned, the allocation covering x_bytes rounded up to 4;
+ *                             rows_in[b].byte_off: where row b's n_values integers of nbits bits begin in x; rows_in,
+ *                             recs and recs_out: HOST arrays of n_batch records; out: device, 4-byte aligned,
+ *                             out_bytes >= the bound.  recs_out[b] = recs[b] with byte_off and byte_len the row's
+ *                             stream in out: rows lie back to back in row order, each at a 4-byte-aligned offset, and
+ *                             every byte from a row's start to the aligned end of its stream is written;
+ *                             *used_bytes = the aligned end of the last row, bytes of out beyond it are unspecified.
+ *                             A row with nbits == 0 gets byte_len 0 and block_size 0 (the mark of a field without a
+ *                             coded stream).  Six kernels (cost per block, runs and offsets per segment, per row, over
+ *                             the rows, shared words zeroed, emit through LDS); nothing returns to the host between
+ *                             them.  Scratch (8 B per block, 12 B per segment) is allocated and freed inside the call;
+ *                             the stream is synchronised before it returns.
+ *   smm_grib_aec_encode_host  one row coded on the host, no device: values[n_values] (n_values == rec->n_values, each
+ *                             within nbits bits) into out[0, out_cap), *byte_len its bytes; histogram
+ *                             (SMM_GRIB_AEC_OPTIONS counters, or NULL) is ADDED to.  out needs no alignment; out_cap
+ *                             must reach the bound.
+ * SMM_ERR_INVALID, before any device is touched: everything smm_grib_aec_unpack refuses about a record (its place in x
+ * apart), rows_in[b].nbits != recs[b].nbits, a row's integers leaving [0, x_bytes), out_bytes / out_cap below the bound,
+ * a misaligned x or out, null pointers, negative counts, a value wider than nbits (host entry).
+ */
+int smm_grib_aec_pack_bound(const smm_grib_aec_t* recs, int64_t n_batch, uint64_t* byte_off, uint64_t* total_bytes);
+int smm_grib_aec_pack(int device, const void* x, int64_t x_bytes, const smm_grib_row_t* rows_in /* host */,
+                      const smm_grib_aec_t* recs /* host */, int64_t n_batch, void* out, int64_t out_bytes,
+                      smm_grib_aec_t* recs_out /* host */, uint64_t* used_bytes, void* stream);
+int smm_grib_aec_encode_host(const uint32_t* values, int64_t n_values, const smm_grib_aec_t* rec, void* out,
+                             int64_t out_cap, uint64_t* byte_len, uint64_t* histogram);
+
+/*
  * Masked-level apply (regrid.py:387-418 in one launch).  The kept dims of the
  * field are viewed as (n_outer, n_lev, n_inner) around the mask dimension;
  * data level l uses group member level_index[l] (host int32[n_lev], result of

@@ -194,6 +194,9 @@ SIGNATURES = {
     "smm_grib_aec_layout": [_gap, _i64, _u64p, _u64p],
     "smm_grib_aec_unpack": [_int, _p, _i64, _gap, _grp, _i64, _p, _i64, _grp, _p],
     "smm_grib_aec_decode_host": [_p, _i64, _gap, ctypes.POINTER(ctypes.c_uint32), _u64p, ctypes.POINTER(_int)],
+    "smm_grib_aec_pack_bound": [_gap, _i64, _u64p, _u64p],
+    "smm_grib_aec_pack": [_int, _p, _i64, _grp, _gap, _i64, _p, _i64, _gap, _u64p, _p],
+    "smm_grib_aec_encode_host": [ctypes.POINTER(ctypes.c_uint32), _i64, _gap, _p, _i64, _u64p, _u64p],
     "smm_group_apply": [_p, _p, _int, _i64, _i64, _i64, _p, _int, _i64, _i64, _i64,
                         _i64, _i64, _i64, _p, _p, _dbl, _uint, _p],
     "smm_group_prepare_sb": [_p],

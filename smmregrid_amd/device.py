@@ -592,6 +592,44 @@ def grib_unpack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None):
     return out, rows_out
 
 
+def grib_aec_pack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None):
+    """Code simple-packed streams resident in HBM as the CCSDS streams of GRIB-2 template 5.42 on the device
+    (smm_grib_aec_pack) -- the twin of `grib_unpack`, and what follows `grib_pack` when results leave CCSDS-packed.
+    device_bytes: a uint8 `DeviceArray` (it must cover x_bytes rounded up to 4); rows: one GRIB_ROW_DTYPE record per
+    field -- where its integers begin, their width; ccsds: one GRIB_AEC_DTYPE record per field with the parameters wanted
+    (n_values and nbits as the field has them, block_size, rsi, flags; `GribEncode.ccsds_records`).  Returns
+    (DeviceArray of uint8 cut to the bytes used, the rows with byte_off at their streams, GRIB_AEC_DTYPE records with
+    byte_off and byte_len set): the streams lie back to back in field order, each at a 4-byte-aligned offset, bytewise what
+    `griblite.aec_encode` gives.  A field of width 0 has no stream (byte_len 0, block_size 0).  out: a uint8 DeviceArray of
+    at least the bound (smm_grib_aec_pack_bound) to code into.  The stream is synchronised on return."""
+    from .griblite import GRIB_AEC_DTYPE, GRIB_ROW_DTYPE
+    if not isinstance(device_bytes, DeviceArray) or device_bytes.dtype != np.uint8:
+        raise TypeError("grib_aec_pack takes the packed bytes as a uint8 DeviceArray")
+    rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
+    ccsds = np.ascontiguousarray(ccsds, dtype=GRIB_AEC_DTYPE).ravel()
+    if ccsds.size != rows.size:
+        raise ValueError(f"{ccsds.size} CCSDS records for {rows.size} rows")
+    n_bytes = device_bytes.nbytes if x_bytes is None else int(x_bytes)
+    if (n_bytes + 3) // 4 * 4 > device_bytes.nbytes:
+        raise ValueError(f"the array must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {device_bytes.nbytes}")
+    aec_p = ctypes.cast(ccsds.ctypes.data, ctypes.POINTER(_lib.GribAecStruct))
+    bound = ctypes.c_uint64(0)
+    _lib.call("smm_grib_aec_pack_bound", aec_p, rows.size, None, ctypes.byref(bound))
+    if out is None:
+        out = DeviceArray((max(bound.value, 4),), np.uint8)
+    elif not isinstance(out, DeviceArray) or out.dtype != np.uint8 or out.nbytes < bound.value:
+        raise ValueError(f"out must be a uint8 DeviceArray of at least {bound.value} bytes")
+    ccsds_out = np.zeros(rows.size, dtype=GRIB_AEC_DTYPE)
+    used = ctypes.c_uint64(0)
+    _lib.call("smm_grib_aec_pack", current_device(), ctypes.c_void_p(device_bytes.ptr), n_bytes,
+              ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)), aec_p, rows.size, ctypes.c_void_p(out.ptr),
+              out.nbytes, ctypes.cast(ccsds_out.ctypes.data, ctypes.POINTER(_lib.GribAecStruct)), ctypes.byref(used),
+              _stream_handle(stream))
+    rows_out = rows.copy()
+    rows_out["byte_off"] = ccsds_out["byte_off"]
+    return DeviceArray((int(used.value),), np.uint8, ptr=out.ptr, base=out), rows_out, ccsds_out
+
+
 def empty(shape, dtype=np.float64):
     if not isinstance(shape, tuple):
         shape = tuple(np.atleast_1d(shape).tolist())

@@ -89,6 +89,27 @@ def aec_decode(buf, rec, histogram=None):
     return out
 
 
+def aec_encode(values, record, histogram=None):
+    """The CCSDS stream (a uint8 array) of the unsigned integers `values`, coded by the library on the host
+    (smm_grib_aec_encode_host; no GPU involved) by THE RULE OF THIS ENCODER of smm_grib_aec.hpp -- the oracle of
+    smm_grib_aec_pack.  record: a GRIB_AEC_DTYPE record whose nbits, block_size, rsi and flags say how to code (n_values
+    is set from `values`, byte_off and byte_len are not read).  histogram: a uint64 array of 7 counters the coding options
+    taken are added to (`_lib.GRIB_AEC_OPTIONS`)."""
+    from . import _lib
+    v = np.ascontiguousarray(values, dtype=np.uint32).ravel()
+    rec = np.array(record, dtype=GRIB_AEC_DTYPE).reshape(1)
+    rec["n_values"], rec["byte_off"], rec["byte_len"] = v.size, 0, 0
+    rec_p = ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribAecStruct))
+    bound = ctypes.c_uint64(0)
+    _lib.call("smm_grib_aec_pack_bound", rec_p, 1, None, ctypes.byref(bound))
+    out = np.zeros(max(int(bound.value), 1), dtype=np.uint8)
+    used = ctypes.c_uint64(0)
+    hist = None if histogram is None else histogram.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    _lib.call("smm_grib_aec_encode_host", v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size, rec_p,
+              ctypes.c_void_p(out.ctypes.data), int(bound.value), ctypes.byref(used), hist)
+    return out[:int(used.value)].copy()
+
+
 class GribField:
     """The fields of one GRIB variable kept as the file has them: `buf`, the file's bytes (one uint8 array shared by
     every variable of the file), and `rows`, a GRIB_ROW_DTYPE record per field in (time, level) order that says where
@@ -165,9 +186,16 @@ class GribEncode:
         t = v * 10^D; present iff v finite and |t| <= FLT_MAX; R = the largest float32 <= min t; ref = R + 0.0;
         range = max t - ref; E = the smallest integer with range * 2^-E <= 2^nbits - 1 (at least -1022);
         q = rint(ldexp(t - ref, -E)); a constant or empty field has width 0 and no data bits.
-    The result decodes with `GribField.decode` (value = (ref + q * 2^E) / 10^D)."""
+    The result decodes with `GribField.decode` (value = (ref + q * 2^E) / 10^D).
+    ccsds: None, True or (block_size, rsi, preprocess) -- or one such tuple per field: the q of every field are coded as
+    a CCSDS stream (template 5.42) by THE RULE OF THIS ENCODER of smm_grib_aec.hpp instead of stored at their width;
+    `encode` is then the host oracle of smm_grib_pack followed by smm_grib_aec_pack.  True means block size 32, a
+    reference sample interval of 128 blocks and the preprocessor on, with ccsdsFlags 0x0e -- ecCodes' defaults as
+    recalled, not pinned against an ecCodes file (like the section-5 octets)."""
 
-    def __init__(self, nbits, decimal_scale=0):
+    CCSDS_DEFAULT = (32, 128, True)
+
+    def __init__(self, nbits, decimal_scale=0, ccsds=None):
         nb, ds = np.asarray(nbits), np.asarray(decimal_scale)
         if nb.ndim > 1 or ds.ndim > 1:
             raise ValueError("nbits and decimal_scale are scalars or one entry per field")
@@ -184,11 +212,40 @@ class GribEncode:
         self.ddiv = np.array([10.0 ** int(d) if abs(int(d)) < 309 else np.inf for d in self.decimal_scale], dtype=np.float64)
         if not (np.isfinite(self.ddiv) & (self.ddiv > 0)).all():
             raise ValueError("10^D must be finite and positive")
+        self.ccsds = None if ccsds is None else self._ccsds_params(ccsds)
+        if self.ccsds is not None and self.ccsds.size > 1:
+            if self.n_fields is None:      # scalars beside one parameter set per field
+                self.n_fields = self.ccsds.size
+                self.nbits, self.decimal_scale, self.ddiv = (np.repeat(a, self.n_fields) for a in
+                                                              (self.nbits, self.decimal_scale, self.ddiv))
+            elif self.ccsds.size != self.n_fields:
+                raise ValueError(f"{self.ccsds.size} CCSDS parameter sets for {self.n_fields} fields")
 
     @classmethod
-    def from_field(cls, field):
+    def _ccsds_params(cls, ccsds):
+        """GRIB_AEC_DTYPE records with block_size, rsi and flags set, from True, one (block_size, rsi, preprocess) or a
+        list of them."""
+        if ccsds is True:
+            ccsds = cls.CCSDS_DEFAULT
+        if isinstance(ccsds, np.ndarray) and ccsds.dtype == GRIB_AEC_DTYPE:
+            par = [(int(r["block_size"]), int(r["rsi"]), bool(int(r["flags"]) & _AEC_PREPROCESS)) for r in ccsds.ravel()]
+        else:
+            par = [tuple(ccsds)] if np.ndim(ccsds[0]) == 0 else [tuple(c) for c in ccsds]
+        rec = np.zeros(len(par), dtype=GRIB_AEC_DTYPE)
+        for i, (block, rsi, pre) in enumerate(par):
+            if int(block) not in (8, 16, 32, 64) or not 1 <= int(rsi) <= 4096:
+                raise ValueError(f"CCSDS block size {block} / reference sample interval {rsi}: 8, 16, 32 or 64 and 1..4096")
+            rec[i] = (0, 0, 0, 0, int(block), int(rsi), 0x06 | (_AEC_PREPROCESS if pre else 0), 0)
+        return rec
+
+    @classmethod
+    def from_field(cls, field, ccsds=None):
         """Each source row's own width and D.  A width of 0 (a constant field) becomes the variable's largest width,
-        or 16 if all are 0."""
+        or 16 if all are 0.  ccsds=True: the result is CCSDS-coded, each field with its source field's own block size,
+        interval and preprocessor switch where the source is CCSDS-packed, with the defaults where it is not."""
+        if ccsds is True and getattr(field, "ccsds", None) is not None:
+            ccsds = [(int(r["block_size"]), int(r["rsi"]), bool(int(r["flags"]) & _AEC_PREPROCESS))
+                     if int(r["block_size"]) else cls.CCSDS_DEFAULT for r in field.ccsds]
         nbits = field.rows["nbits"].astype(np.int32)
         top = int(nbits.max()) if nbits.size and nbits.max() > 0 else 16
         nbits = np.where(nbits == 0, top, nbits).astype(np.int32)
@@ -199,7 +256,37 @@ class GribEncode:
         for d, want in zip(dec, ddiv):
             if 10.0 ** int(d) != want:
                 raise ValueError(f"ddiv {want!r} is not 10.0 ** D for an integer D")
-        return cls(nbits, dec)
+        return cls(nbits, dec, ccsds=ccsds)
+
+    def rows_of(self, r0, r1, n_fields):
+        """The GribEncode of fields [r0, r1) of n_fields."""
+        nbits, _ = self._per_field(n_fields)
+        par = None if self.ccsds is None else self.ccsds_records(n_fields)[r0:r1]
+        return GribEncode(nbits[r0:r1].copy(), np.broadcast_to(self.decimal_scale, (int(n_fields),))[r0:r1].copy(), ccsds=par)
+
+    def ccsds_records(self, n_fields, n_values=0, nbits=0):
+        """The wanted smm_grib_aec_t records of n_fields fields (smm_grib_aec_pack): block size, interval and flags of this
+        rule, n_values and nbits (the stored widths) as given."""
+        self._per_field(n_fields)
+        rec = np.zeros(int(n_fields), dtype=GRIB_AEC_DTYPE)
+        rec[:] = self.ccsds if self.ccsds.size > 1 else self.ccsds[0]
+        rec["n_values"], rec["nbits"] = n_values, nbits
+        return rec
+
+    def ccsds_bound(self, n_points, n_fields):
+        """Bytes the coded streams of n_fields fields of n_points points take at most (smm_grib_aec_pack_bound)."""
+        return int(self.ccsds_bounds(n_points, n_fields).sum())
+
+    def ccsds_bounds(self, n_points, n_fields):
+        """The same field by field (int64)."""
+        from . import _lib
+        nbits, _ = self._per_field(n_fields)
+        rec = self.ccsds_records(n_fields, int(n_points), nbits)
+        offs, total = np.zeros(rec.size + 1, dtype=np.uint64), ctypes.c_uint64(0)
+        _lib.call("smm_grib_aec_pack_bound", ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribAecStruct)), rec.size,
+                  offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(total))
+        offs[rec.size] = total.value
+        return np.diff(offs).astype(np.int64)
 
     def _per_field(self, n_fields):
         n_fields = int(n_fields)
@@ -269,7 +356,35 @@ class GribEncode:
                     buf[off + bm_bytes:off + bm_bytes + packed.size] = packed
             rows[b] = (off + bm_bytes, ref, float(np.ldexp(1.0, E)), dd, width, 0)
             bitmaps[b] = (GRIB_NO_BITMAP if nv == n else off, nv)
+        if self.ccsds is not None:
+            return self._encode_ccsds(buf, rows, bitmaps, shape, n)
         return GribField(buf, rows, shape, n, bitmaps=bitmaps)
+
+    def _encode_ccsds(self, buf, rows, bitmaps, shape, n):
+        """The simple-packed fields of `encode` with their integers coded as CCSDS streams.  The buffer: every field's
+        bitmap slot (align4(ceil(n_points / 8)) bytes, written whether the field has missing points or not) in field
+        order, then the streams back to back in field order, each at a 4-byte-aligned offset.  A field of width 0 has no
+        stream (block_size 0)."""
+        nf, bm_bytes = rows.size, _align4((n + 7) // 8)
+        rec = self.ccsds_records(nf, bitmaps["n_values"], rows["nbits"])
+        streams, at = [], nf * bm_bytes
+        head = np.zeros(at, dtype=np.uint8)
+        rows, bitmaps = rows.copy(), bitmaps.copy()
+        for b in range(nf):
+            w, nv, off = int(rows["nbits"][b]), int(bitmaps["n_values"][b]), int(rows["byte_off"][b])
+            head[b * bm_bytes:(b + 1) * bm_bytes] = buf[off - bm_bytes:off]
+            if int(bitmaps["bitmap_off"][b]) != GRIB_NO_BITMAP:
+                bitmaps["bitmap_off"][b] = b * bm_bytes
+            rec["byte_off"][b] = rows["byte_off"][b] = at
+            if w == 0:
+                rec["block_size"][b] = 0
+                continue
+            q = _unpack_bits(bytes(memoryview(buf)[off:off + (nv * w + 7) // 8]), w, nv).astype(np.uint32)
+            st = aec_encode(q, rec[b])
+            rec["byte_len"][b] = st.size
+            streams.append(np.concatenate([st, np.zeros(_align4(st.size) - st.size, dtype=np.uint8)]))
+            at += _align4(st.size)
+        return GribField(np.concatenate([head] + streams), rows, shape, n, bitmaps=bitmaps, ccsds=rec)
 
     def __repr__(self):
         return f"<GribEncode widths {sorted(set(self.nbits.tolist()))}, D {sorted(set(self.decimal_scale.tolist()))}>"

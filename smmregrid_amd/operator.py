@@ -12,7 +12,8 @@ import numpy as np
 
 from . import _lib
 from .device import (DeviceArray, bfloat16, check_half_pair, dtype_code, field_dtype_code, is_half_dtype,
-                     is_packed_dtype, result_cache, result_dtype, _stream_handle, current_device, grib_unpack, mem_info)
+                     is_packed_dtype, result_cache, result_dtype, _stream_handle, current_device, grib_aec_pack, grib_pack, grib_unpack,
+                     mem_info)
 
 
 def _cptr(a):
@@ -447,19 +448,29 @@ class SparseOperator:
         return GribField(out, rows_out, (n_batch, self.n_dst), self.n_dst, bitmaps=bitmaps_out)
 
     def _apply_host_grib_ccsds(self, buf, rows, out, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds):
-        """`apply_host_grib(ccsds=)`: a synchronous loop over chunks of consecutive rows -- the chunk's coded bytes (and
-        bitmaps) staged and copied to the device, smm_grib_aec_unpack behind them into the same buffer, the device
-        gather (smm_apply_grib_bm / _na), Y copied back.  A chunk's staged bytes, transcoded streams, 4 B per sample of
-        scratch and Y stay within 256 MiB and a quarter of the free device memory; chunk_rows > 0 fixes the rows."""
-        from .griblite import GRIB_NO_BITMAP
-        n_batch, S, D = rows.size, self.n_src, self.n_dst
-        if bitmaps is not None:
-            bitmaps, _ = self._grib_bitmaps(bitmaps, n_batch)
+        """`apply_host_grib(ccsds=)`: a synchronous loop over chunks of consecutive rows (`_grib_host_chunks`), each
+        chunk's Y copied back."""
+        n_batch, D = rows.size, self.n_dst
         if out is None:
             out = result_cache.empty((n_batch, D), np.float64)
         if out.shape != (n_batch, D) or out.dtype != np.float64 or not out.flags.c_contiguous:
             raise ValueError(f"out must be a C-contiguous float64 ({n_batch}, {D}) array")
-        ccsds, idx, _ = self._ccsds_records(ccsds, rows)
+        for r0, r1, y in self._grib_host_chunks(buf, rows, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds):
+            y.to_host(out=out[r0:r1])
+        return out
+
+    def _grib_host_chunks(self, buf, rows, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds, extra_cost=0):
+        """Chunks of consecutive rows, one after the other: the chunk's bytes (coded or simple-packed streams, bitmaps)
+        staged and copied to the device, smm_grib_aec_unpack behind them into the same buffer for the coded rows, the
+        device gather (smm_apply_grib_bm / _na).  Yields (first row, end row, the chunk's float64 Y on the device).  A
+        chunk's staged bytes, transcoded streams, 4 B per sample of scratch, Y and extra_cost (bytes per row, what the
+        caller puts beside them) stay within 256 MiB and a quarter of the free device memory; chunk_rows > 0 fixes the
+        rows.  ccsds: None -- every row is simple-packed."""
+        from .griblite import GRIB_AEC_DTYPE, GRIB_NO_BITMAP
+        n_batch, S, D = rows.size, self.n_src, self.n_dst
+        if bitmaps is not None:
+            bitmaps, _ = self._grib_bitmaps(bitmaps, n_batch)
+        ccsds, idx, _ = self._ccsds_records(np.zeros(n_batch, dtype=GRIB_AEC_DTYPE) if ccsds is None else ccsds, rows)
         coded = np.zeros(n_batch, dtype=bool)
         coded[idx] = True
         align4 = lambda v: (v + 3) // 4 * 4                                               # noqa: E731
@@ -476,7 +487,7 @@ class SparseOperator:
                 (has_bm.any() and (bitmaps["bitmap_off"][has_bm].astype(object) + bm_len > buf.size).any()):
             raise ValueError(f"a row's bytes leave the buffer of {buf.size} bytes")
         cost = align4(in_len) + np.where(coded, align4((n_val * nbits + 7) // 8) + 4 * n_val, 0) + D * 8 + \
-            np.where(has_bm, align4(bm_len), 0)
+            np.where(has_bm, align4(bm_len), 0) + extra_cost
         free, _ = mem_info()
         target = min(256 << 20, max(free // 4, 1))
         fl = int(flags)
@@ -507,12 +518,61 @@ class SparseOperator:
             both = DeviceArray((max(at + total, 4),), np.uint8)
             src = DeviceArray((staged.size,), np.uint8, ptr=both.ptr, base=both).copy_from_host(staged)
             dst = DeviceArray((total,), np.uint8, ptr=both.ptr + at, base=both)
-            rows_c = self._ccsds_unpack(src, at, dst, at, rows_c, aec_c, idx_c, None)
+            if idx_c.size:
+                rows_c = self._ccsds_unpack(src, at, dst, at, rows_c, aec_c, idx_c, None)
             y = self.apply_grib(both, rows_c, x_bytes=at + total, masked=masked, remap_area_min=remap_area_min, flags=fl,
                                 bitmaps=bm_c, skipna=skipna)
-            y.to_host(out=out[r0:r1])
+            yield r0, r1, y
             r0 = r1
-        return out
+
+    def _apply_host_grib_out_ccsds(self, buf, rows, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, grib_out,
+                                   ccsds):
+        """`apply_host_grib(grib_out=GribEncode(..., ccsds=...))`: the chunks of `_grib_host_chunks`, each chunk's float64
+        Y packed on the device (smm_grib_pack) and its integers coded as CCSDS streams (smm_grib_aec_pack); one D2H copy
+        of the chunk's bitmaps (none when no cell is missing: they are all ones) and one of the bytes its streams use.  Y
+        and the simple-packed streams never leave the device.  The chunk budget counts the simple-packed slots and the
+        streams' bound, not the bytes used.  The result's buffer is laid out as `GribEncode.encode` lays it out: every
+        field's bitmap slot, then the streams back to back."""
+        from .griblite import GRIB_AEC_DTYPE, GRIB_BITMAP_DTYPE, GRIB_NO_BITMAP, GRIB_ROW_DTYPE, GribField
+        n_batch, D = rows.size, self.n_dst
+        offs, total = grib_out.layout(D, n_batch)
+        slot = np.diff(np.append(offs, np.uint64(total))).astype(np.int64)
+        bound = grib_out.ccsds_bounds(D, n_batch)
+        bm_bytes = (D + 7) // 8 + (-((D + 7) // 8)) % 4
+        result = np.empty(n_batch * bm_bytes + int(bound.sum()), dtype=np.uint8)      # cut to the bytes used at the end
+        head = result[:n_batch * bm_bytes]
+        head[:] = 0
+        full = np.packbits(np.ones(D, dtype=np.uint8))
+        rows_out = np.zeros(n_batch, dtype=GRIB_ROW_DTYPE)
+        bitmaps_out = np.zeros(n_batch, dtype=GRIB_BITMAP_DTYPE)
+        ccsds_out = np.zeros(n_batch, dtype=GRIB_AEC_DTYPE)
+        at = n_batch * bm_bytes
+        # per row beside Y: its simple-packed slot, the bound of its stream, 8 B per block and 12 B per segment of scratch
+        extra = slot + bound + (D // 8 + 1) * 20
+        for r0, r1, y in self._grib_host_chunks(buf, rows, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds,
+                                                extra_cost=extra):
+            enc = grib_out.rows_of(r0, r1, n_batch)
+            packed, rows_c, bm_c = grib_pack(y, enc)
+            want = enc.ccsds_records(r1 - r0, bm_c["n_values"], rows_c["nbits"])
+            coded, rows_c, aec_c = grib_aec_pack(packed, rows_c, want)
+            missing = np.flatnonzero(bm_c["bitmap_off"] != GRIB_NO_BITMAP)
+            h = head[r0 * bm_bytes:r1 * bm_bytes].reshape(r1 - r0, bm_bytes)
+            h[:, :full.size] = full
+            if missing.size and (slot[r0:r1] == slot[r0]).all():      # one strided copy of the chunk's bitmap slots
+                _lib.call("smm_memcpy2d_d2h", _cptr(h), bm_bytes, ctypes.c_void_p(packed.ptr), int(slot[r0]), bm_bytes,
+                          r1 - r0, None)
+                _lib.call("smm_stream_sync", None)
+            else:
+                for i in missing:                                     # slots of different sizes: row by row
+                    DeviceArray((bm_bytes,), np.uint8, ptr=packed.ptr + int(bm_c["bitmap_off"][i]), base=packed).to_host(out=h[i])
+            bm_c["bitmap_off"][missing] = (r0 + missing) * bm_bytes
+            if coded.nbytes:
+                coded.to_host(out=result[at:at + coded.nbytes])
+            rows_c["byte_off"] += np.uint64(at)
+            aec_c["byte_off"] += np.uint64(at)
+            rows_out[r0:r1], bitmaps_out[r0:r1], ccsds_out[r0:r1] = rows_c, bm_c, aec_c
+            at += coded.nbytes
+        return GribField(result[:at], rows_out, (n_batch, D), D, bitmaps=bitmaps_out, ccsds=ccsds_out)
 
     def apply_host_grib(self, buf, rows, out=None, masked=False, remap_area_min=0.0, flags=0, chunk_rows=0, bitmaps=None,
                         skipna=False, grib_out=None, ccsds=None):
@@ -526,11 +586,20 @@ class SparseOperator:
         fresh buffer; its bytes and records are those of `grib_out.encode` on the float64 result of the same call
         without grib_out.  The float64 result never leaves the device.
         ccsds as for `apply_grib`: the rows' CCSDS streams cross PCIe as they are and are decoded on the device, chunk
-        by chunk (a synchronous loop: no copy overlaps a kernel).  It does not go with grib_out."""
+        by chunk (a synchronous loop: no copy overlaps a kernel).  It does not go with a simple-packed grib_out.
+        grib_out a `GribEncode` with `ccsds` set: the result comes back CCSDS-packed -- a `GribField` with `bitmaps` and
+        `ccsds` set, in a buffer of its own, bytewise `grib_out.encode` of the float64 result.  The same synchronous chunk
+        loop, with smm_grib_pack and smm_grib_aec_pack behind the gather; the input may be simple-packed or, through
+        ccsds=, CCSDS-packed itself."""
         rows, rows_p = self._grib_rows(rows)
         buf = np.ascontiguousarray(buf)
         if buf.dtype != np.uint8 or buf.ndim != 1:
             raise TypeError("apply_host_grib takes the packed bytes as a 1-d uint8 array")
+        if grib_out is not None and getattr(grib_out, "ccsds", None) is not None:
+            if out is not None:
+                raise ValueError("a CCSDS-coded result comes in a buffer of its own: its size is known only afterwards")
+            return self._apply_host_grib_out_ccsds(buf, rows, masked, remap_area_min, flags, int(chunk_rows), bitmaps, skipna,
+                                                   grib_out, ccsds)
         if ccsds is not None:
             if grib_out is not None:
                 raise ValueError("ccsds does not go with grib_out: decode the field on the host first")

@@ -59,7 +59,7 @@ class Regridder(object):
                  check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=None,
                  lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False,
                  packed_levels=False, packed_out=False, packed_out_levels=False, half=False, packed_skipna=False, grib_out=False,
-                 grib_out_levels=False):
+                 grib_out_levels=False, grib_out_ccsds=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -121,6 +121,13 @@ class Regridder(object):
         self.grib_out_levels = bool(grib_out_levels)
         if self.grib_out_levels and not (self.grib_out and self.packed_levels):
             raise ValueError('grib_out_levels=True needs grib_out=True and packed_levels=True')
+        # grib_out_ccsds (with grib_out=True): on 2-D weights the packed result is CCSDS-coded on the device behind the
+        # pack (smm_grib_aec_pack; GribEncode.from_field(src, ccsds=True)): a simple-packed source gets block size 32, an
+        # interval of 128 blocks and the preprocessor, a CCSDS-packed source keeps its own parameters and stays raw end
+        # to end -- no host decode, no INFO line.  Masked-level weights keep the simple-packed result of grib_out_levels
+        self.grib_out_ccsds = bool(grib_out_ccsds)
+        if self.grib_out_ccsds and not self.grib_out:
+            raise ValueError('grib_out_ccsds=True needs grib_out=True')
         # packed_out (with packed=True): a variable regridded raw comes back in its own raw dtype, encoded by the rule
         # of its own attributes (CFEncode) inside the kernels' stores, and keeps its packing attributes: it can be
         # written straight to a file.  Values that round outside the raw range become the fill value (no wrap-around)
@@ -411,7 +418,7 @@ class Regridder(object):
             return "packed=False"
         if ccsds and levels:
             return "CCSDS packing on masked levels"
-        if ccsds and self.grib_out:
+        if ccsds and self.grib_out and not getattr(self, "grib_out_ccsds", False):
             return "CCSDS packing with grib_out"
         if levels and not self.packed_levels:
             return "masked levels"
@@ -607,9 +614,11 @@ class Regridder(object):
                     raise ValueError(f"{src.rows.size} GRIB fields for {n_batch} batch rows of shape {tuple(kept_shape)}")
                 # (with their bitmaps, if any: smm_apply_host_grib_bm ranks them on the device)
                 if self.grib_out:     # the result packed on the device, each field by its source's width and D
+                    # (grib_out_ccsds: and its integers coded as CCSDS streams behind the pack; a CCSDS source goes in raw)
+                    enc = GribEncode.from_field(src, ccsds=True if self.grib_out_ccsds else None)
                     y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps,
-                                           skipna=skipna, grib_out=GribEncode.from_field(src))
-                    return GribField(y.buf, y.rows, kept_shape + tgt_shape, op.n_dst, bitmaps=y.bitmaps)
+                                           skipna=skipna, grib_out=enc, ccsds=src.ccsds if self.grib_out_ccsds else None)
+                    return GribField(y.buf, y.rows, kept_shape + tgt_shape, op.n_dst, bitmaps=y.bitmaps, ccsds=y.ccsds)
                 # (CCSDS-packed fields: their streams are decoded on the device ahead of the gather, smm_grib_aec_unpack)
                 y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps,
                                        skipna=skipna, ccsds=src.ccsds)
