@@ -186,6 +186,33 @@ enum { SMM_GRIB_AEC_OK = 0, SMM_GRIB_AEC_EXHAUSTED = 1, SMM_GRIB_AEC_INVALID = 2
  * second extension, split-sample k = 0, split-sample k > 0, uncompressed, blocks that carry a reference sample */
 #define SMM_GRIB_AEC_OPTIONS 7
 
+/* A GRIB-2 field in complex packing (data representation templates 5.2 and 5.3; smm_grib_cpx_unpack,
+ * smm_grib_cpx_decode_host): where section 7's bytes (from its octet 6 on) of one batch row lie in x, and section 5's
+ * parameters.  The stream decodes to n_values integers X in [0, 2^32) -- the q of smm_grib_row_t's rule; the rule is the
+ * text of smmregrid_amd/csrc/smm_grib_cpx.hpp.  order == SMM_GRIB_CPX_SIMPLE marks a row that is simple-packed already:
+ * nothing else of its record is looked at, its smm_grib_row_t says it all.  Missing value management (octet 23) is not
+ * in the record: the reader refuses everything but 0. */
+#define SMM_GRIB_CPX_SIMPLE (-1)
+typedef struct smm_grib_cpx_t {   /* one batch row = one GRIB field, 72 B */
+  uint64_t byte_off;      /* of the stream's first byte (octet 6 of section 7), from x */
+  uint64_t byte_len;      /* bytes of the stream */
+  uint64_t n_values;      /* values the stream codes: the grid's points, or the set bits of the row's bitmap; < 2^31 */
+  uint32_t n_groups;      /* NG (octets 32-35); <= n_values, or the row ends as invalid */
+  int32_t nbits;          /* octet 20: width of the group reference values, 0..32 */
+  uint32_t width_ref;     /* octet 36: reference for group widths */
+  int32_t width_bits;     /* octet 37: bits per stored group width, 0..32 */
+  uint32_t length_ref;    /* octets 38-41: reference for group lengths */
+  uint32_t length_inc;    /* octet 42: length increment */
+  uint32_t length_last;   /* octets 43-46: true length of the last group */
+  int32_t length_bits;    /* octet 47: bits per stored scaled group length, 0..32 */
+  int32_t order;          /* octet 48: order of spatial differencing, 0 (template 5.2), 1 or 2; SMM_GRIB_CPX_SIMPLE */
+  int32_t n_oct;          /* octet 49: octets per extra descriptor, 1..4 (order > 0) */
+  uint64_t reserved;      /* 0 */
+} smm_grib_cpx_t;
+/* how a row's stream ended: EXHAUSTED -- a section or a group's bits leave the stream; INVALID -- a group wider than 32
+ * bits, more groups than values, group lengths that do not sum to n_values, an X outside [0, 2^32) */
+enum { SMM_GRIB_CPX_OK = 0, SMM_GRIB_CPX_EXHAUSTED = 1, SMM_GRIB_CPX_INVALID = 2 };
+
 /* smm_apply flags.  Bits outside this set are refused with SMM_ERR_INVALID by every entry that takes `flags`
  * (ABI <= 4 encoded kernel variants in bits 16..23: those are smm_debug_set_tuning knobs now). */
 enum {
@@ -691,6 +718,41 @@ int smm_grib_aec_pack(int device, const void* x, int64_t x_bytes, const smm_grib
                       smm_grib_aec_t* recs_out /* host */, uint64_t* used_bytes, void* stream);
 int smm_grib_aec_encode_host(const uint32_t* values, int64_t n_values, const smm_grib_aec_t* rec, void* out,
                              int64_t out_cap, uint64_t* byte_len, uint64_t* histogram);
+
+/*
+ * Complex-packed GRIB-2 fields (templates 5.2 / 5.3, smm_grib_cpx_t above) on the raw road: one device step turns the
+ * rows' group-coded streams into the simple-packed streams smm_apply_grib_bm / _na take, as smm_grib_aec_unpack does for
+ * CCSDS.  Nothing in the format is serial beyond a prefix sum: the groups' widths and lengths are fixed-width tables, a
+ * scan gives every group its value and bit offset, every value is an independent bit extraction, and spatial
+ * differencing is undone by one or two prefix sums over the row.  The rule is the text of
+ * smmregrid_amd/csrc/smm_grib_cpx.hpp; the kernels are described in smm_grib_cpx.hip.
+ *   smm_grib_cpx_layout       host only: a coded row's slot is n_values * 4 bytes (the width of its integers is only known
+ *                             after the decode: the slot is a bound), a row marked SMM_GRIB_CPX_SIMPLE has none; slots lie
+ *                             back to back in row order, each 4-byte aligned.  byte_off[b] (may be NULL) = where row b's
+ *                             slot starts in `out`, *total_bytes = all of them.
+ *   smm_grib_cpx_unpack       x: device bytes, 4-byte aligned, the allocation covering x_bytes rounded up to 4; recs and
+ *                             rows_in: HOST arrays of n_batch records; out: device, 4-byte aligned, out_bytes >= the
+ *                             layout's total.  Row b's integers are stored big-endian from its slot's start with the
+ *                             row's own minimal width w_b = the bit length of its largest X (0 when every X is 0: a
+ *                             constant field); every byte of ceil(n_values * w_b / 8) rounded up to 4 is written, the
+ *                             rest of the slot is unspecified.  rows_out[b] (HOST) = rows_in[b] with byte_off the slot
+ *                             and nbits = w_b (rows_in[b].nbits is not read).  A marked row passes through untouched.
+ *                             Scratch (8 B per value, 16 B per group) is allocated and freed inside the call; the stream
+ *                             is synchronised before it returns.  A row whose status is not ok makes the call return
+ *                             SMM_ERR_INVALID, smm_last_error naming the first such row.
+ *   smm_grib_cpx_decode_host  one row decoded on the host, no device: values[n_values] receives the integers, *status is
+ *                             how the row ended (SMM_GRIB_CPX_*).  x_host needs no alignment.  A malformed stream costs
+ *                             wrong numbers and a status, never a read outside [0, x_bytes).
+ * SMM_ERR_INVALID, before any device is touched: null pointers, a negative count, order outside 0..2 (the mark apart),
+ * n_oct outside 1..4 when order > 0, nbits, width_bits or length_bits outside 0..32, width_ref or length_inc above 255,
+ * n_groups == 0 with n_values > 0, 0 < n_values <= order, n_values >= 2^31, reserved != 0, a stream that leaves
+ * [0, x_bytes), out_bytes below the layout, a misaligned x or out.
+ */
+int smm_grib_cpx_layout(const smm_grib_cpx_t* recs, int64_t n_batch, uint64_t* byte_off, uint64_t* total_bytes);
+int smm_grib_cpx_unpack(int device, const void* x, int64_t x_bytes, const smm_grib_cpx_t* recs /* host */,
+                        const smm_grib_row_t* rows_in /* host */, int64_t n_batch, void* out, int64_t out_bytes,
+                        smm_grib_row_t* rows_out /* host */, void* stream);
+int smm_grib_cpx_decode_host(const void* x_host, int64_t x_bytes, const smm_grib_cpx_t* rec, uint32_t* values, int* status);
 
 /*
  * Masked-level apply (regrid.py:387-418 in one launch).  The kept dims of the

@@ -121,6 +121,21 @@ GRIB_AEC_SIGNED, GRIB_AEC_3BYTE, GRIB_AEC_MSB, GRIB_AEC_PREPROCESS, GRIB_AEC_RES
 # the bins of smm_grib_aec_decode_host's histogram, in order
 GRIB_AEC_OPTIONS = ("zero_block", "zero_block_ros", "second_extension", "split_k0", "split_k", "uncompressed",
                     "reference")
+
+
+class GribCpxStruct(ctypes.Structure):
+    """smm_grib_cpx_t: where the complex-packed stream (templates 5.2 / 5.3) of one GRIB field lies in the bytes and
+    section 5's parameters"""
+    _fields_ = [("byte_off", ctypes.c_uint64), ("byte_len", ctypes.c_uint64), ("n_values", ctypes.c_uint64),
+                ("n_groups", ctypes.c_uint32), ("nbits", ctypes.c_int32), ("width_ref", ctypes.c_uint32),
+                ("width_bits", ctypes.c_int32), ("length_ref", ctypes.c_uint32), ("length_inc", ctypes.c_uint32),
+                ("length_last", ctypes.c_uint32), ("length_bits", ctypes.c_int32), ("order", ctypes.c_int32),
+                ("n_oct", ctypes.c_int32), ("reserved", ctypes.c_uint64)]
+
+
+_gcp = ctypes.POINTER(GribCpxStruct)
+GRIB_CPX_OK, GRIB_CPX_EXHAUSTED, GRIB_CPX_INVALID = 0, 1, 2
+GRIB_CPX_SIMPLE = -1      # smm_grib_cpx_t.order of a row that is simple-packed already
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 
 # name -> argtypes; every entry point returns int status except the two noted
@@ -194,6 +209,9 @@ SIGNATURES = {
     "smm_grib_aec_layout": [_gap, _i64, _u64p, _u64p],
     "smm_grib_aec_unpack": [_int, _p, _i64, _gap, _grp, _i64, _p, _i64, _grp, _p],
     "smm_grib_aec_decode_host": [_p, _i64, _gap, ctypes.POINTER(ctypes.c_uint32), _u64p, ctypes.POINTER(_int)],
+    "smm_grib_cpx_layout": [_gcp, _i64, _u64p, _u64p],
+    "smm_grib_cpx_unpack": [_int, _p, _i64, _gcp, _grp, _i64, _p, _i64, _grp, _p],
+    "smm_grib_cpx_decode_host": [_p, _i64, _gcp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_int)],
     "smm_grib_aec_pack_bound": [_gap, _i64, _u64p, _u64p],
     "smm_grib_aec_pack": [_int, _p, _i64, _grp, _gap, _i64, _p, _i64, _gap, _u64p, _p],
     "smm_grib_aec_encode_host": [ctypes.POINTER(ctypes.c_uint32), _i64, _gap, _p, _i64, _u64p, _u64p],

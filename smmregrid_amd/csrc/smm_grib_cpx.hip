@@ -1,0 +1,493 @@
+// smm_grib_cpx_unpack (gfx950): the complex-packed streams of GRIB-2 templates 5.2 / 5.3 turned into simple-packed
+// streams on the device, and the two host-only entries beside it (smm_grib_cpx_layout, smm_grib_cpx_decode_host).  The
+// format and the two rules that bound every loop and read are the text of smm_grib_cpx.hpp; the kernels read the stream
+// through its Stream::peek and take the tables apart with its sections / group_of / group_ref / descriptors.  Kernels
+// in stream order -- a kernel boundary is the only ordering between passes, no workgroup ever waits for another one:
+//   groups   a lane per group: stored width and length -> w_g, L_g, w_g L_g; a workgroup scan leaves every group its
+//            value and bit offset within its tile of 256 groups, and the tile's sums
+//   offsets  a wave per row scans the tile sums, 64 at a step; checks the sum of the lengths and the bits' end
+//   values   a lane per value: its group by binary search (the tiles' value offsets, then the groups of the tile),
+//            one extraction for the reference and one for the value; z + g (or the seed h) into 8 bytes of scratch
+//   order 1 and 2, once or twice: reduce (a workgroup per tile of 1024 values), carries (a wave per row over the tile
+//            sums), apply (the tile's inclusive prefix sum in place).  The last pass over a row -- the values kernel at
+//            order 0 -- checks X < 2^32 and raises the row's maximum with atomicMax
+//   store    a thread per 32-bit output word at the row's own width, the bit length of that maximum
+// A row that fails gets its status and is skipped by every later pass.  A kernel never reads a status word that the
+// same kernel writes: `structure` is written by groups / offsets and gates what follows, `range` is written by the
+// last pass and read by the store.  Plain vector stores and vector atomics (atomicMax on a 32-bit word per row).
+#include "smm_device.hpp"
+
+#include <algorithm>
+
+#include "smm_grib_cpx.hpp"
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kCpxThreads = 256;
+constexpr int kGroupTile = kCpxThreads;       // groups of a tile: one per lane
+constexpr int kPerLane = 4;
+constexpr int kValueTile = kCpxThreads * kPerLane;   // values of a tile of the prefix sums
+
+struct CpxRow {   // what a row of the call brings to the device
+  smm_cpx::Row r;
+  uint64_t group_off;   // the row's first entry in CpxArgs::groups
+  uint64_t gtile_off;   // ... in gtiles
+  uint64_t value_off;   // ... in values
+  uint64_t vtile_off;   // ... in vtiles
+  uint64_t out_off;     // the row's slot in out, in bytes: a multiple of 4
+  uint32_t coded;       // 0: the row is simple-packed already, or holds no value: nothing is done
+  uint32_t pad;
+};
+struct CpxGroup {       // a group after the groups kernel; 16 B
+  uint64_t bit_excl;    // bits of the tile's groups before it
+  uint32_t value_excl;  // values of the tile's groups before it
+  uint32_t width;
+};
+struct CpxTile {        // a tile of groups: its sums, after the offsets kernel the sums of the row's tiles before it
+  uint64_t values, bits;
+};
+struct CpxArgs {
+  const void* x;
+  const CpxRow* rows;
+  CpxGroup* groups;
+  CpxTile* gtiles;
+  uint64_t* values;     // 8 B per value: a_i, then its prefix sums
+  uint64_t* vtiles;     // a tile of values: its sum, then the sum of the row's tiles before it
+  uint32_t* out;
+  int32_t* structure;   // [n_j] status from the tables (the host puts what sections() says)
+  int32_t* range;       // [n_j] status from the integers
+  uint32_t* xmax;       // [n_j] the row's largest X
+};
+
+// inclusive prefix sum over the N lanes of a workgroup through N words of LDS; every lane of the workgroup calls it
+template <int N>
+__device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t* lds, uint32_t tid) {
+  lds[tid] = v;
+  __syncthreads();
+#pragma unroll
+  for (int o = 1; o < N; o <<= 1) {
+    const uint64_t t = (int)tid >= o ? lds[tid - o] : 0;
+    __syncthreads();
+    lds[tid] += t;
+    __syncthreads();
+  }
+  const uint64_t incl = lds[tid];
+  __syncthreads();   // lds is free again
+  return incl;
+}
+
+// ---- groups.  Workgroup (row, tile) takes groups [256 tile, 256 tile + 256).
+__global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_groups_kernel(CpxArgs a, int64_t b0, uint32_t per_row) {
+  __shared__ uint64_t lds[kCpxThreads];
+  const int64_t id = b0 + blockIdx.x;
+  const int64_t j = id / per_row;
+  const uint32_t tile = (uint32_t)(id % per_row), tid = threadIdx.x;
+  const CpxRow* __restrict__ rows = a.rows;
+  const CpxRow row = rows[j];
+  const smm_cpx::Row& r = row.r;
+  if (!row.coded || (uint64_t)tile * kGroupTile >= r.n_groups) return;
+  const smm_cpx::Sections sec = smm_cpx::sections(r);
+  if (sec.status != smm_cpx::kOk) return;   // the tables do not fit: nothing is read
+  const smm_cpx::Stream s = smm_cpx::stream_of(a.x, r);
+  const uint32_t g = tile * kGroupTile + tid;
+  uint64_t w = 0, len = 0;
+  bool bad = false;
+  if (g < r.n_groups) {
+    smm_cpx::group_of(s, r, sec, g, &w, &len);
+    bad = w > 32 || len > r.n_values;
+    if (bad) w = len = 0;
+  }
+  const uint64_t bits = w * len;
+  const uint64_t len_incl = block_scan<kCpxThreads>(len, lds, tid);
+  const uint64_t bits_incl = block_scan<kCpxThreads>(bits, lds, tid);
+  if (g < r.n_groups) a.groups[row.group_off + g] = CpxGroup{bits_incl - bits, (uint32_t)(len_incl - len), (uint32_t)w};
+  if (tid == kCpxThreads - 1) {
+    a.gtiles[row.gtile_off + tile] = CpxTile{len_incl, bits_incl};
+    bad = bad || len_incl > r.n_values;
+  }
+  if (bad) atomicMax(&a.structure[j], (int32_t)smm_cpx::kInvalid);
+}
+
+// ---- offsets.  One wave per row: the tile sums become the sums before each tile; the row's totals are checked.
+__global__ __launch_bounds__(kWave) void smm_grib_cpx_offsets_kernel(CpxArgs a, int64_t b0) {
+  __shared__ uint64_t lds[kWave];
+  const int64_t j = b0 + blockIdx.x;
+  const uint32_t lane = threadIdx.x;
+  const CpxRow* __restrict__ rows = a.rows;
+  const CpxRow row = rows[j];
+  const smm_cpx::Row& r = row.r;
+  if (!row.coded || a.structure[j] != smm_cpx::kOk) return;   // every tile sum is <= n_values from here on
+  const smm_cpx::Sections sec = smm_cpx::sections(r);
+  const uint32_t n_tiles = (r.n_groups + kGroupTile - 1) / kGroupTile;
+  CpxTile* __restrict__ tiles = a.gtiles + row.gtile_off;
+  uint64_t values = 0, bits = 0;
+  for (uint32_t t0 = 0; t0 < n_tiles; t0 += kWave) {
+    const uint32_t t = t0 + lane;
+    const CpxTile mine = t < n_tiles ? tiles[t] : CpxTile{0, 0};
+    const uint64_t v_incl = block_scan<kWave>(mine.values, lds, lane);
+    const uint64_t b_incl = block_scan<kWave>(mine.bits, lds, lane);
+    if (t < n_tiles) tiles[t] = CpxTile{values + v_incl - mine.values, bits + b_incl - mine.bits};
+    if (lane == kWave - 1) lds[0] = v_incl, lds[1] = b_incl;
+    __syncthreads();
+    values += lds[0];
+    bits += lds[1];
+    __syncthreads();
+  }
+  if (lane == 0) {
+    if (values != r.n_values)
+      a.structure[j] = smm_cpx::kInvalid;
+    else if (bits > sec.bit_end - sec.data_bit)
+      a.structure[j] = smm_cpx::kExhausted;
+  }
+}
+
+// the largest X of a wave's lanes and whether one of them left [0, 2^32): one atomic per wave at most
+__device__ __forceinline__ void raise_row(const CpxArgs& a, int64_t j, uint32_t m, bool high) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    const uint32_t t = __shfl_xor(m, o, kWave);
+    m = t > m ? t : m;
+  }
+  const bool any_high = __any(high);
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    // the word only grows: a look at it first spares the atomic of every wave that cannot raise it (a stale look costs
+    // an atomic that changes nothing, never a missed one)
+    if (m > __atomic_load_n(&a.xmax[j], __ATOMIC_RELAXED)) atomicMax(&a.xmax[j], m);
+    if (any_high && __atomic_load_n(&a.range[j], __ATOMIC_RELAXED) != smm_cpx::kInvalid)
+      atomicMax(&a.range[j], (int32_t)smm_cpx::kInvalid);
+  }
+}
+
+// ---- values.  Lane (row, i) finds the group of value i: the last tile whose value offset is <= i, then the last group
+// of that tile whose offset is <= i -- groups of no values share their offset with the group behind them, and the last
+// of equals is the one that holds i (the lengths sum to n_values > i).
+__global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_values_kernel(CpxArgs a, int64_t b0, uint32_t per_row) {
+  const int64_t id = b0 + blockIdx.x;
+  const int64_t j = id / per_row;
+  const uint32_t i = (uint32_t)(id % per_row) * kCpxThreads + threadIdx.x;
+  const CpxRow* __restrict__ rows = a.rows;
+  const CpxRow row = rows[j];
+  const smm_cpx::Row& r = row.r;
+  if (!row.coded || a.structure[j] != smm_cpx::kOk) return;
+  if ((uint64_t)(id % per_row) * kCpxThreads >= r.n_values) return;
+  const bool live = i < r.n_values;
+  uint64_t v = 0;
+  if (live) {
+    const smm_cpx::Sections sec = smm_cpx::sections(r);
+    const smm_cpx::Stream s = smm_cpx::stream_of(a.x, r);
+    uint64_t h1, h2, gmin;
+    smm_cpx::descriptors(s, r, &h1, &h2, &gmin);
+    if (i < (uint32_t)r.order) {
+      v = smm_cpx::seed(i, h1, h2);
+    } else {
+      const CpxTile* __restrict__ tiles = a.gtiles + row.gtile_off;
+      const CpxGroup* __restrict__ groups = a.groups + row.group_off;
+      uint32_t lo = 0, hi = (r.n_groups + kGroupTile - 1) / kGroupTile - 1;
+      while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (tiles[mid].values <= i)
+          lo = mid;
+        else
+          hi = mid - 1;
+      }
+      const CpxTile tile = tiles[lo];
+      const uint32_t rest = i - (uint32_t)tile.values;   // tile.values <= i: tile 0 starts at 0
+      uint32_t g0 = lo * kGroupTile, g1 = g0 + kGroupTile - 1;
+      if (g1 > r.n_groups - 1) g1 = r.n_groups - 1;
+      while (g0 < g1) {
+        const uint32_t mid = g0 + (g1 - g0 + 1) / 2;
+        if (groups[mid].value_excl <= rest)
+          g0 = mid;
+        else
+          g1 = mid - 1;
+      }
+      const CpxGroup grp = groups[g0];
+      const uint64_t k = rest - grp.value_excl;
+      const uint64_t p = sec.data_bit + tile.bits + grp.bit_excl + k * grp.width;
+      // the offsets kernel has checked that the row's bits end inside the stream; a width is at most 32
+      v = smm_cpx::group_ref(s, r, sec, g0) + s.peek(p, (int)grp.width) + gmin;
+    }
+    a.values[row.value_off + i] = v;
+  }
+  if (r.order <= 0) raise_row(a, j, live ? (uint32_t)v : 0u, live && (v >> 32) != 0);
+}
+
+// ---- the prefix sums of order 1 and 2; pass p (1 or 2) runs on the rows whose order is >= p
+__global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_reduce_kernel(CpxArgs a, int64_t b0, uint32_t per_row, int pass) {
+  __shared__ uint64_t lds[kCpxThreads];
+  const int64_t id = b0 + blockIdx.x;
+  const int64_t j = id / per_row;
+  const uint32_t tile = (uint32_t)(id % per_row), tid = threadIdx.x;
+  const CpxRow* __restrict__ rows = a.rows;
+  const CpxRow row = rows[j];
+  const uint32_t n = row.r.n_values;
+  if (!row.coded || row.r.order < pass || a.structure[j] != smm_cpx::kOk || (uint64_t)tile * kValueTile >= n) return;
+  const uint64_t* __restrict__ v = a.values + row.value_off;
+  uint64_t sum = 0;
+#pragma unroll
+  for (int q = 0; q < kPerLane; ++q) {
+    const uint64_t i = (uint64_t)tile * kValueTile + (uint64_t)q * kCpxThreads + tid;
+    if (i < n) sum += v[i];
+  }
+  const uint64_t incl = block_scan<kCpxThreads>(sum, lds, tid);
+  if (tid == kCpxThreads - 1) a.vtiles[row.vtile_off + tile] = incl;
+}
+
+__global__ __launch_bounds__(kWave) void smm_grib_cpx_carries_kernel(CpxArgs a, int64_t b0, int pass) {
+  __shared__ uint64_t lds[kWave];
+  const int64_t j = b0 + blockIdx.x;
+  const uint32_t lane = threadIdx.x;
+  const CpxRow* __restrict__ rows = a.rows;
+  const CpxRow row = rows[j];
+  if (!row.coded || row.r.order < pass || a.structure[j] != smm_cpx::kOk) return;
+  const uint32_t n_tiles = (row.r.n_values + kValueTile - 1) / kValueTile;
+  uint64_t* __restrict__ tiles = a.vtiles + row.vtile_off;
+  uint64_t carry = 0;
+  for (uint32_t t0 = 0; t0 < n_tiles; t0 += kWave) {
+    const uint32_t t = t0 + lane;
+    const uint64_t mine = t < n_tiles ? tiles[t] : 0;
+    const uint64_t incl = block_scan<kWave>(mine, lds, lane);
+    if (t < n_tiles) tiles[t] = carry + incl - mine;
+    if (lane == kWave - 1) lds[0] = incl;
+    __syncthreads();
+    carry += lds[0];
+    __syncthreads();
+  }
+}
+
+// lane tid owns the 4 consecutive values from 1024 tile + 4 tid on
+__global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_apply_kernel(CpxArgs a, int64_t b0, uint32_t per_row, int pass) {
+  __shared__ uint64_t lds[kCpxThreads];
+  const int64_t id = b0 + blockIdx.x;
+  const int64_t j = id / per_row;
+  const uint32_t tile = (uint32_t)(id % per_row), tid = threadIdx.x;
+  const CpxRow* __restrict__ rows = a.rows;
+  const CpxRow row = rows[j];
+  const uint32_t n = row.r.n_values;
+  if (!row.coded || row.r.order < pass || a.structure[j] != smm_cpx::kOk || (uint64_t)tile * kValueTile >= n) return;
+  uint64_t* __restrict__ v = a.values + row.value_off;
+  const uint64_t first = (uint64_t)tile * kValueTile + (uint64_t)tid * kPerLane;
+  uint64_t mine[kPerLane];
+  uint64_t sum = 0;
+#pragma unroll
+  for (int q = 0; q < kPerLane; ++q) {
+    mine[q] = first + q < n ? v[first + q] : 0;
+    sum += mine[q];
+    mine[q] = sum;
+  }
+  const uint64_t before = a.vtiles[row.vtile_off + tile] + block_scan<kCpxThreads>(sum, lds, tid) - sum;
+  const bool last = pass == row.r.order;
+  uint32_t m = 0;
+  bool high = false;
+#pragma unroll
+  for (int q = 0; q < kPerLane; ++q) {
+    const uint64_t X = before + mine[q];
+    if (first + q < n) {
+      v[first + q] = X;
+      m = (uint32_t)X > m ? (uint32_t)X : m;
+      high = high || (X >> 32) != 0;
+    }
+  }
+  if (last) raise_row(a, j, m, high);
+}
+
+// ---- store.  One thread per 32-bit word of the row's stream at its own width (the grid covers 32 bits a value; the
+// surplus threads leave), the values that overlap the word put in place as smm_grib_codec.hpp's grib_word_part has it.
+__global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_store_kernel(CpxArgs a, int64_t b0, uint32_t per_row) {
+  const int64_t id = b0 + blockIdx.x;
+  const int64_t j = id / per_row;
+  const uint32_t w = (uint32_t)(id % per_row) * kCpxThreads + threadIdx.x;
+  const CpxRow* __restrict__ rows = a.rows;
+  const CpxRow row = rows[j];
+  if (!row.coded || a.structure[j] != smm_cpx::kOk || a.range[j] != smm_cpx::kOk) return;
+  const uint32_t n = row.r.n_values;
+  const int width = smm_cpx::width_of(a.xmax[j]);
+  const uint64_t n_words = smm_grib::align4(smm_grib::row_bytes(n, width)) >> 2;   // <= n: inside the slot
+  if (width == 0 || w >= n_words) return;
+  const uint64_t* __restrict__ v = a.values + row.value_off;
+  uint64_t i = 0, end = 0;
+  smm_grib::grib_word_values(w, width, n, &i, &end);
+  uint32_t word = 0;
+  for (; i < end; ++i) word |= smm_grib::grib_word_part((uint32_t)v[i], i, width, w);
+  a.out[(row.out_off >> 2) + w] = __builtin_bswap32(word);
+}
+
+// launches `total` workgroups as grids of at most grid_limit(), the first workgroup's number handed to the kernel
+template <class F>
+int for_grid(int64_t total, F&& launch) {
+  const int64_t limit = std::min<int64_t>(std::max<int64_t>(grid_limit(), 1), 0x7fffffffLL);
+  for (int64_t b0 = 0; b0 < total; b0 += limit) {
+    launch(b0, (unsigned)std::min(limit, total - b0));
+    SMM_HIP(hipGetLastError());
+  }
+  return SMM_OK;
+}
+
+struct CpxShape {   // the widest row of the call
+  uint32_t gtiles = 0, vtiles = 0, blocks = 0;
+  int order = 0;
+};
+
+int launch_cpx(const CpxArgs& a, int64_t n_j, const CpxShape& sh, hipStream_t s) {
+  if (sh.gtiles)
+    if (int rc = for_grid(n_j * sh.gtiles, [&](int64_t b0, unsigned nb) {
+          hipLaunchKernelGGL(smm_grib_cpx_groups_kernel, dim3(nb), dim3(kCpxThreads), 0, s, a, b0, sh.gtiles);
+        }))
+      return rc;
+  if (int rc = for_grid(n_j, [&](int64_t b0, unsigned nb) {
+        hipLaunchKernelGGL(smm_grib_cpx_offsets_kernel, dim3(nb), dim3(kWave), 0, s, a, b0);
+      }))
+    return rc;
+  if (!sh.blocks) return SMM_OK;
+  if (int rc = for_grid(n_j * sh.blocks, [&](int64_t b0, unsigned nb) {
+        hipLaunchKernelGGL(smm_grib_cpx_values_kernel, dim3(nb), dim3(kCpxThreads), 0, s, a, b0, sh.blocks);
+      }))
+    return rc;
+  for (int pass = 1; pass <= sh.order; ++pass) {
+    if (int rc = for_grid(n_j * sh.vtiles, [&](int64_t b0, unsigned nb) {
+          hipLaunchKernelGGL(smm_grib_cpx_reduce_kernel, dim3(nb), dim3(kCpxThreads), 0, s, a, b0, sh.vtiles, pass);
+        }))
+      return rc;
+    if (int rc = for_grid(n_j, [&](int64_t b0, unsigned nb) {
+          hipLaunchKernelGGL(smm_grib_cpx_carries_kernel, dim3(nb), dim3(kWave), 0, s, a, b0, pass);
+        }))
+      return rc;
+    if (int rc = for_grid(n_j * sh.vtiles, [&](int64_t b0, unsigned nb) {
+          hipLaunchKernelGGL(smm_grib_cpx_apply_kernel, dim3(nb), dim3(kCpxThreads), 0, s, a, b0, sh.vtiles, pass);
+        }))
+      return rc;
+  }
+  return for_grid(n_j * sh.blocks, [&](int64_t b0, unsigned nb) {
+    hipLaunchKernelGGL(smm_grib_cpx_store_kernel, dim3(nb), dim3(kCpxThreads), 0, s, a, b0, sh.blocks);
+  });
+}
+
+// everything the entries with records refuse about them
+int check_cpx_records(const smm_grib_cpx_t* recs, int64_t n_batch, int64_t x_bytes) {
+  if (n_batch < 0) return fail(SMM_ERR_INVALID, "negative batch size");
+  if (x_bytes < 0) return fail(SMM_ERR_INVALID, "negative x_bytes");
+  if (!recs && n_batch > 0) return fail(SMM_ERR_INVALID, "null record pointer");
+  std::string err;
+  if (!smm::check_grib_cpx(recs, n_batch, x_bytes, err)) return fail(SMM_ERR_INVALID, err);
+  return SMM_OK;
+}
+
+const char* status_text(int status) {
+  return status == smm_cpx::kExhausted ? "ends before its tables or its groups' bits do"
+                                       : "is invalid (a group wider than 32 bits, group lengths that do not sum to "
+                                         "n_values, or an integer outside [0, 2^32))";
+}
+
+int smm_grib_cpx_unpack_impl(int device, const void* x, const smm_grib_cpx_t* recs, const smm_grib_row_t* rows_in,
+                             int64_t n_batch, void* out, const uint64_t* offs, smm_grib_row_t* rows_out, void* stream) {
+  const size_t n = (size_t)n_batch;
+  std::vector<CpxRow> table(n);
+  std::vector<int32_t> words(3 * n, 0);   // structure, range, xmax
+  uint64_t n_groups = 0, n_gtiles = 0, n_values = 0, n_vtiles = 0;
+  CpxShape sh;
+  for (size_t b = 0; b < n; ++b) {
+    const smm_grib_cpx_t& c = recs[b];
+    CpxRow& r = table[b];
+    r = CpxRow{smm_cpx::row_of(c), n_groups, n_gtiles, n_values, n_vtiles, offs[b], 0u, 0u};
+    rows_out[b] = rows_in[b];
+    if (c.order == SMM_GRIB_CPX_SIMPLE) continue;
+    rows_out[b].byte_off = offs[b];
+    rows_out[b].nbits = 0;
+    if (c.n_values == 0) continue;
+    r.coded = 1u;
+    const smm_cpx::Sections sec = smm_cpx::sections(r.r);
+    words[b] = sec.status;
+    if (sec.status != smm_cpx::kOk) continue;   // n_groups <= n_values from here on: the record bounds the scratch
+    const uint32_t gt = (uint32_t)((c.n_groups + (uint64_t)kGroupTile - 1) / kGroupTile);
+    const uint32_t vt = (uint32_t)((c.n_values + (uint64_t)kValueTile - 1) / kValueTile);
+    n_groups += c.n_groups;
+    n_gtiles += gt;
+    n_values += c.n_values;
+    n_vtiles += vt;
+    sh.gtiles = std::max(sh.gtiles, gt);
+    sh.vtiles = std::max(sh.vtiles, vt);
+    sh.blocks = std::max(sh.blocks, (uint32_t)((c.n_values + (uint64_t)kCpxThreads - 1) / kCpxThreads));
+    sh.order = std::max(sh.order, (int)c.order);
+  }
+  std::vector<int32_t> got(words);
+  if (n_values > 0) {
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the device");
+    hipStream_t s = (hipStream_t)stream;
+    auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t table_at = 0, words_at = align16(n * sizeof(CpxRow)), groups_at = align16(words_at + 3 * n * sizeof(int32_t)),
+                 gtiles_at = groups_at + (size_t)n_groups * sizeof(CpxGroup), values_at = gtiles_at + (size_t)n_gtiles * sizeof(CpxTile),
+                 vtiles_at = values_at + (size_t)n_values * sizeof(uint64_t), bytes = vtiles_at + (size_t)n_vtiles * sizeof(uint64_t);
+    DeviceBuf<char> d;
+    SMM_HIP(d.alloc(bytes));
+    SMM_HIP(hipMemcpyAsync(d.get() + table_at, table.data(), n * sizeof(CpxRow), hipMemcpyHostToDevice, s));
+    SMM_HIP(hipMemcpyAsync(d.get() + words_at, words.data(), 3 * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    int32_t* w = (int32_t*)(d.get() + words_at);
+    CpxArgs a{x, (const CpxRow*)(d.get() + table_at), (CpxGroup*)(d.get() + groups_at), (CpxTile*)(d.get() + gtiles_at),
+              (uint64_t*)(d.get() + values_at), (uint64_t*)(d.get() + vtiles_at), (uint32_t*)out, w, w + n, (uint32_t*)(w + 2 * n)};
+    int rc = launch_cpx(a, n_batch, sh, s);
+    if (rc == SMM_OK) {
+      const hipError_t e = hipMemcpyAsync(got.data(), w, 3 * n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+      if (e != hipSuccess) rc = fail(SMM_ERR_HIP, std::string("copying the rows' statuses: ") + hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(s);   // the tables and the scratch are in use until here
+    if (rc != SMM_OK) {
+      (void)hipGetLastError();
+      return rc;
+    }
+    SMM_HIP(e);
+  }
+  for (size_t b = 0; b < n; ++b) {
+    const int status = got[b] != smm_cpx::kOk ? got[b] : got[n + b];
+    if (status != smm_cpx::kOk)
+      return fail(SMM_ERR_INVALID, "recs[" + std::to_string(b) + "]: the complex-packed stream " + status_text(status));
+    if (table[b].coded) rows_out[b].nbits = smm_cpx::width_of((uint32_t)got[2 * n + b]);
+  }
+  return SMM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smm_grib_cpx_layout(const smm_grib_cpx_t* recs, int64_t n_batch, uint64_t* byte_off, uint64_t* total_bytes) {
+  return guarded([&] {
+    if (!total_bytes) return fail(SMM_ERR_INVALID, "null total pointer");
+    if (int rc = check_cpx_records(recs, n_batch, INT64_MAX)) return rc;
+    *total_bytes = smm::grib_cpx_layout(recs, n_batch, byte_off);
+    return (int)SMM_OK;
+  });
+}
+
+int smm_grib_cpx_unpack(int device, const void* x, int64_t x_bytes, const smm_grib_cpx_t* recs, const smm_grib_row_t* rows_in,
+                        int64_t n_batch, void* out, int64_t out_bytes, smm_grib_row_t* rows_out, void* stream) {
+  return guarded([&] {
+    if (int rc = check_cpx_records(recs, n_batch, x_bytes)) return rc;
+    if (n_batch > 0 && (!rows_in || !rows_out)) return fail(SMM_ERR_INVALID, "null row-table pointer");
+    if (out_bytes < 0) return fail(SMM_ERR_INVALID, "negative out_bytes");
+    std::vector<uint64_t> offs((size_t)n_batch + 1);
+    offs[(size_t)n_batch] = smm::grib_cpx_layout(recs, n_batch, offs.data());
+    if ((uint64_t)out_bytes < offs[(size_t)n_batch])
+      return fail(SMM_ERR_INVALID, "out_bytes " + std::to_string(out_bytes) + " is below the layout's " +
+                                       std::to_string(offs[(size_t)n_batch]) + " bytes");
+    if (offs[(size_t)n_batch] > 0 && (!x || !out)) return fail(SMM_ERR_INVALID, "null field or output pointer");
+    if ((uintptr_t)x % 4) return fail(SMM_ERR_INVALID, "field pointer is not 4-byte aligned");
+    if ((uintptr_t)out % 4) return fail(SMM_ERR_INVALID, "output pointer is not 4-byte aligned");
+    return smm_grib_cpx_unpack_impl(device, x, recs, rows_in, n_batch, out, offs.data(), rows_out, stream);
+  });
+}
+
+int smm_grib_cpx_decode_host(const void* x_host, int64_t x_bytes, const smm_grib_cpx_t* rec, uint32_t* values, int* status) {
+  return guarded([&] {
+    if (!rec || !status) return fail(SMM_ERR_INVALID, "null record or status pointer");
+    if (int rc = check_cpx_records(rec, 1, x_bytes)) return rc;
+    if (rec->order == SMM_GRIB_CPX_SIMPLE) return fail(SMM_ERR_INVALID, "rec is marked simple-packed: it has no complex-packed stream");
+    if (rec->n_values > 0 && !values) return fail(SMM_ERR_INVALID, "null values pointer");
+    if (!x_host && rec->byte_len > 0) return fail(SMM_ERR_INVALID, "null field pointer");
+    *status = smm_cpx::decode_row(x_host, smm_cpx::row_of(*rec), values);
+    return (int)SMM_OK;
+  });
+}
+
+}  // extern "C"

@@ -188,6 +188,40 @@ uint64_t grib_aec_layout(const smm_grib_aec_t* recs, int64_t n_batch, uint64_t* 
   return at;
 }
 
+bool check_grib_cpx(const smm_grib_cpx_t* recs, int64_t n_batch, int64_t x_bytes, std::string& err) {
+  for (int64_t b = 0; b < n_batch; ++b) {
+    const smm_grib_cpx_t& r = recs[b];
+    const std::string at = "recs[" + std::to_string(b) + "]";
+    if (r.order == SMM_GRIB_CPX_SIMPLE) continue;   // simple-packed already: the row's own record says it all
+    if (r.order < 0 || r.order > 2) return err = at + ".order (of spatial differencing) must be 0, 1 or 2", false;
+    if (r.order > 0 && (r.n_oct < 1 || r.n_oct > 4))
+      return err = at + ".n_oct (octets per extra descriptor) must be within 1..4", false;
+    if (r.nbits < 0 || r.nbits > 32) return err = at + ".nbits must be within 0..32", false;
+    if (r.width_bits < 0 || r.width_bits > 32) return err = at + ".width_bits must be within 0..32", false;
+    if (r.length_bits < 0 || r.length_bits > 32) return err = at + ".length_bits must be within 0..32", false;
+    if (r.width_ref > 255) return err = at + ".width_ref is one octet: 0..255", false;
+    if (r.length_inc > 255) return err = at + ".length_inc is one octet: 0..255", false;
+    if (r.reserved != 0) return err = at + ".reserved must be 0", false;
+    if (r.n_values >= ((uint64_t)1 << 31)) return err = at + ".n_values must be below 2^31", false;
+    if (r.n_values > 0 && r.n_groups == 0) return err = at + ".n_groups is 0 for " + std::to_string(r.n_values) + " values", false;
+    if (r.n_values > 0 && r.n_values <= (uint64_t)r.order)
+      return err = at + ".n_values must exceed the order of spatial differencing", false;
+    if (r.byte_off > (uint64_t)x_bytes || r.byte_len > (uint64_t)x_bytes - r.byte_off)
+      return err = at + ": bytes [" + std::to_string(r.byte_off) + ", " + std::to_string(r.byte_off) + " + " +
+                   std::to_string(r.byte_len) + ") leave the buffer of " + std::to_string(x_bytes) + " bytes", false;
+  }
+  return true;
+}
+
+uint64_t grib_cpx_layout(const smm_grib_cpx_t* recs, int64_t n_batch, uint64_t* byte_off) {
+  uint64_t at = 0;
+  for (int64_t b = 0; b < n_batch; ++b) {
+    if (byte_off) byte_off[b] = at;
+    if (recs[b].order != SMM_GRIB_CPX_SIMPLE) at += recs[b].n_values * 4;
+  }
+  return at;
+}
+
 GribPackScratch grib_pack_scratch(int64_t n_dst, int64_t n_rows) {
   const size_t n = (size_t)std::max<int64_t>(n_rows, 0);
   const size_t segs = n * (size_t)smm_grib::bitmap_segments((uint64_t)n_dst);

@@ -10,6 +10,7 @@ struct smm_grib_row_t;   // include/smmregrid_amd.h
 struct smm_grib_bitmap_t;
 struct smm_grib_encode_t;
 struct smm_grib_aec_t;
+struct smm_grib_cpx_t;
 
 namespace smm {
 
@@ -260,6 +261,13 @@ constexpr size_t kGribPackTableBytes = 32 + 16;
 bool check_grib_aec(const smm_grib_aec_t* recs, int64_t n_batch, int64_t x_bytes, std::string& err);
 // the layout of the transcoded streams: byte_off[b] (may be null) = start of row b's; returns the bytes of all
 uint64_t grib_aec_layout(const smm_grib_aec_t* recs, int64_t n_batch, uint64_t* byte_off);
+// ---- complex-packed fields (smm_grib_cpx_unpack, smm_grib_cpx_decode_host; smm_grib_plan.cpp).  What the entries refuse
+// about the records of rows that are not marked simple-packed -- order 0..2, n_oct 1..4 with an order, the three bit counts
+// 0..32, the two one-octet parameters 0..255, reserved 0, n_values < 2^31 and > order (or 0), a group for any value, a
+// stream inside [0, x_bytes): false + err
+bool check_grib_cpx(const smm_grib_cpx_t* recs, int64_t n_batch, int64_t x_bytes, std::string& err);
+// the layout of the transcoded rows, n_values * 4 bytes per coded row: byte_off[b] (may be null); returns the bytes of all
+uint64_t grib_cpx_layout(const smm_grib_cpx_t* recs, int64_t n_batch, uint64_t* byte_off);
 // Where a chunk's pieces lie in its staging buffer hx (ch.x_bytes bytes, 8-byte aligned), written into hx: the table first
 // -- the rows' records with byte_off the staged offset of the row's data -- then, with bitmaps, their records
 // (GribRowBitmap, smm_grib_codec.hpp: bitmap_off a staged offset too, table_off the place of the row's rank table among

@@ -592,6 +592,40 @@ def grib_unpack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None):
     return out, rows_out
 
 
+def grib_unpack_cpx(device_bytes, rows, cpx, x_bytes=None, out=None, stream=None):
+    """Turn the complex-packed streams of GRIB-2 fields (templates 5.2 / 5.3) resident in HBM into simple-packed streams
+    on the device (smm_grib_cpx_unpack).  device_bytes: a uint8 `DeviceArray` holding the streams (the array must cover
+    x_bytes rounded up to 4); rows: one GRIB_ROW_DTYPE record per field (its R, 2^E, 10^D; nbits is not read); cpx: one
+    GRIB_CPX_DTYPE record per field (where section 7's bytes lie, how many integers they code, section 5's group
+    parameters).  Returns (DeviceArray of uint8, GRIB_ROW_DTYPE records): each field's integers big-endian at the start
+    of a slot of 4 bytes per value, with the field's own minimal width -- the bit length of its largest integer, which
+    the returned record's nbits holds -- what `SparseOperator.apply_grib(x, rows, bitmaps=...)` takes as it is.  A field
+    whose record is marked GRIB_CPX_SIMPLE passes through untouched.  out: a uint8 DeviceArray to unpack into.  The
+    stream is synchronised on return."""
+    from .griblite import GRIB_CPX_DTYPE, GRIB_ROW_DTYPE
+    if not isinstance(device_bytes, DeviceArray) or device_bytes.dtype != np.uint8:
+        raise TypeError("grib_unpack_cpx takes the coded bytes as a uint8 DeviceArray")
+    rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
+    cpx = np.ascontiguousarray(cpx, dtype=GRIB_CPX_DTYPE).ravel()
+    if cpx.size != rows.size:
+        raise ValueError(f"{cpx.size} complex-packing records for {rows.size} rows")
+    n_bytes = device_bytes.nbytes if x_bytes is None else int(x_bytes)
+    if (n_bytes + 3) // 4 * 4 > device_bytes.nbytes:
+        raise ValueError(f"the array must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {device_bytes.nbytes}")
+    cpx_p = ctypes.cast(cpx.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct))
+    total = ctypes.c_uint64(0)
+    _lib.call("smm_grib_cpx_layout", cpx_p, rows.size, None, ctypes.byref(total))
+    if out is None:
+        out = DeviceArray((max(total.value, 4),), np.uint8)
+    elif not isinstance(out, DeviceArray) or out.dtype != np.uint8 or out.nbytes < total.value:
+        raise ValueError(f"out must be a uint8 DeviceArray of at least {total.value} bytes")
+    rows_out = np.zeros(rows.size, dtype=GRIB_ROW_DTYPE)
+    _lib.call("smm_grib_cpx_unpack", current_device(), ctypes.c_void_p(device_bytes.ptr), n_bytes, cpx_p,
+              ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)), rows.size, ctypes.c_void_p(out.ptr),
+              out.nbytes, ctypes.cast(rows_out.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)), _stream_handle(stream))
+    return out, rows_out
+
+
 def grib_aec_pack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None):
     """Code simple-packed streams resident in HBM as the CCSDS streams of GRIB-2 template 5.42 on the device
     (smm_grib_aec_pack) -- the twin of `grib_unpack`, and what follows `grib_pack` when results leave CCSDS-packed.

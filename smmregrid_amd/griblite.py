@@ -22,11 +22,13 @@ Edition 2 (WMO FM 92 GRIB edition 2; what newer IFS / ICON output comes in) is d
 0 - 8, grid definition templates 3.0 (lon/lat) and 3.40 (Gaussian, regular or with the list of points per row),
 product definition templates 4.0 / 4.1 / 4.8 / 4.11 (the leading octets they share), data representation templates 5.0
 (simple packing, IEEE reference value) and 5.42 (CCSDS packing: the same rule on integers that an adaptive entropy
-coder compressed; decoded by the library's host decoder, smm_grib_aec_decode_host), bitmap section, several fields per
-message (repeated sections 2 - 7).
+coder compressed; decoded by the library's host decoder, smm_grib_aec_decode_host), 5.2 and 5.3 (complex packing, plain
+and with spatial differencing -- what NCEP writes; the same rule on integers coded in groups of their own widths,
+smm_grib_cpx_decode_host; missing value management 0 only), bitmap section, several fields per message (repeated
+sections 2 - 7).
 
-Anything else in a GRIB file (spherical harmonics, second-order / JPEG / PNG packing, rotated or projected grids)
-raises GribUnsupported naming the feature.
+Anything else in a GRIB file (spherical harmonics, GRIB-1 second-order / JPEG / PNG packing, rotated or projected
+grids) raises GribUnsupported naming the feature.
 """
 import ctypes
 
@@ -89,6 +91,35 @@ def aec_decode(buf, rec, histogram=None):
     return out
 
 
+# smm_grib_cpx_t, field for field: one record per GRIB field of a raw-kept variable some of whose messages are complex-packed
+# (templates 5.2 / 5.3) -- where section 7's bytes lie in the file, how many integers they code, and section 5's group
+# parameters.  order == GRIB_CPX_SIMPLE (-1): the field is simple-packed, its row record says it all
+GRIB_CPX_DTYPE = np.dtype({"names": ["byte_off", "byte_len", "n_values", "n_groups", "nbits", "width_ref", "width_bits",
+                                     "length_ref", "length_inc", "length_last", "length_bits", "order", "n_oct", "reserved"],
+                           "formats": ["<u8", "<u8", "<u8", "<u4", "<i4", "<u4", "<i4", "<u4", "<u4", "<u4", "<i4", "<i4", "<i4",
+                                       "<u8"],
+                           "offsets": [0, 8, 16, 24, 28, 32, 36, 40, 44, 48, 52, 56, 60, 64], "itemsize": 72})
+GRIB_CPX_SIMPLE = -1
+
+
+def cpx_decode(buf, rec):
+    """The integers X (uint32) of one complex-packed stream: `rec` a GRIB_CPX_DTYPE record over the bytes `buf`, decoded
+    by the library on the host (smm_grib_cpx_decode_host; no GPU involved).  A row that does not end ok is a
+    ValueError."""
+    from . import _lib
+    rec = np.ascontiguousarray(rec, dtype=GRIB_CPX_DTYPE).reshape(1)
+    raw = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf)
+    out = np.empty(int(rec["n_values"][0]), dtype=np.uint32)
+    status = ctypes.c_int(0)
+    _lib.call("smm_grib_cpx_decode_host", ctypes.c_void_p(raw.ctypes.data if raw.size else None), raw.size,
+              ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)),
+              out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(status))
+    if status.value != _lib.GRIB_CPX_OK:
+        raise ValueError("complex-packed stream " + ("ends before its tables or its groups' bits do"
+                                                     if status.value == _lib.GRIB_CPX_EXHAUSTED else "is invalid"))
+    return out
+
+
 def aec_encode(values, record, histogram=None):
     """The CCSDS stream (a uint8 array) of the unsigned integers `values`, coded by the library on the host
     (smm_grib_aec_encode_host; no GPU involved) by THE RULE OF THIS ENCODER of smm_grib_aec.hpp -- the oracle of
@@ -121,11 +152,15 @@ class GribField:
     field holds its present points only, the others are NaN (smm_apply_host_grib_bm).  `ccsds` is None, or a
     GRIB_AEC_DTYPE record per field (a variable with CCSDS-packed messages, template 5.42): such a field's q are what
     its coded stream decodes to -- on the GPU for `Regridder(packed=True)` (smm_grib_aec_unpack ahead of the gather),
-    on the host for `decode()`; a record with block_size 0 marks a simple-packed field among them."""
+    on the host for `decode()`; a record with block_size 0 marks a simple-packed field among them.  `cpx` is None, or a
+    GRIB_CPX_DTYPE record per field (a variable with complex-packed messages, templates 5.2 / 5.3): such a field's q are
+    the integers its groups decode to (smm_grib_cpx_unpack ahead of the gather on the GPU, smm_grib_cpx_decode_host for
+    `decode()`), and its row's nbits is the width of the group references, not of q; a record whose order is
+    GRIB_CPX_SIMPLE marks a simple-packed field among them."""
 
     dtype = np.dtype(np.float32)
 
-    def __init__(self, buf, rows, shape, n_points, bitmaps=None, ccsds=None):
+    def __init__(self, buf, rows, shape, n_points, bitmaps=None, ccsds=None, cpx=None):
         """n_points: grid points of one field -- the product of the trailing (horizontal) axes of `shape`."""
         self.buf = buf
         self.rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
@@ -135,6 +170,11 @@ class GribField:
         self.ccsds = None if ccsds is None else np.ascontiguousarray(ccsds, dtype=GRIB_AEC_DTYPE).ravel()
         if self.ccsds is not None and self.ccsds.size != self.rows.size:
             raise ValueError(f"{self.ccsds.size} CCSDS records for {self.rows.size} GRIB fields")
+        self.cpx = None if cpx is None else np.ascontiguousarray(cpx, dtype=GRIB_CPX_DTYPE).ravel()
+        if self.cpx is not None and self.cpx.size != self.rows.size:
+            raise ValueError(f"{self.cpx.size} complex-packing records for {self.rows.size} GRIB fields")
+        if self.cpx is not None and self.ccsds is not None:
+            raise ValueError("a GribField holds CCSDS records or complex-packing records, not both")
         self.shape = tuple(int(n) for n in shape)
         self.n_points = int(n_points)
         if self.rows.size * self.n_points != int(np.prod(self.shape)):
@@ -157,7 +197,8 @@ class GribField:
             if self.bitmaps is not None and int(self.bitmaps[i]["bitmap_off"]) != GRIB_NO_BITMAP:
                 bm = (int(self.bitmaps[i]["bitmap_off"]), int(self.bitmaps[i]["n_values"]))
             aec = None if self.ccsds is None or int(self.ccsds[i]["block_size"]) == 0 else self.ccsds[i]
-            out[i] = _decode_rule(self.buf, rule, self.n_points, bm, aec)
+            cpx = None if self.cpx is None or int(self.cpx[i]["order"]) == GRIB_CPX_SIMPLE else self.cpx[i]
+            out[i] = _decode_rule(self.buf, rule, self.n_points, bm, aec, cpx)
         return out.reshape(self.shape)
 
     def __array__(self, dtype=None, copy=None):
@@ -167,8 +208,10 @@ class GribField:
     def __repr__(self):
         n_bm = 0 if self.bitmaps is None else int((self.bitmaps["bitmap_off"] != GRIB_NO_BITMAP).sum())
         n_aec = 0 if self.ccsds is None else int((self.ccsds["block_size"] != 0).sum())
+        n_cpx = 0 if self.cpx is None else int((self.cpx["order"] != GRIB_CPX_SIMPLE).sum())
         return (f"<GribField {self.shape} float32, {self.rows.size} packed fields, widths "
                 f"{sorted(set(self.rows['nbits'].tolist()))}" + (f", {n_aec} CCSDS-packed" if n_aec else "")
+                + (f", {n_cpx} complex-packed" if n_cpx else "")
                 + (f", {n_bm} with a bitmap>" if n_bm else ">"))
 
 
@@ -458,14 +501,19 @@ def _unpack_bits(raw, nbits, count):
     return bits.astype(np.uint64) @ (np.uint64(1) << np.arange(nbits - 1, -1, -1, dtype=np.uint64))
 
 
-def _decode_rule(buf, rule, count, bitmap=None, aec=None):
+def _decode_rule(buf, rule, count, bitmap=None, aec=None, cpx=None):
     """The float64 values of one message from its rule (file offset of the packed values, R, 2^E, 10^D, bit width):
     the statement the message classes evaluate, on the message's own bytes only.  bitmap: None, or (file offset of the
     bitmap's bytes, values in the stream) -- the values go to the points whose bit is set, the others are NaN.
-    aec: None, or the GRIB_AEC_DTYPE record of a CCSDS-packed message -- its integers come out of the coded stream."""
+    aec: None, or the GRIB_AEC_DTYPE record of a CCSDS-packed message -- its integers come out of the coded stream.
+    cpx: None, or the GRIB_CPX_DTYPE record of a complex-packed message -- its integers come out of its groups."""
     off, ref, scale, ddiv, nbits = rule
     n = count if bitmap is None else bitmap[1]
-    if aec is not None and nbits:
+    if cpx is not None:
+        if int(cpx["n_values"]) != n:
+            raise ValueError(f"complex-packed stream of {int(cpx['n_values'])} values for {n} points")
+        q = cpx_decode(buf, cpx).astype(np.float64)
+    elif aec is not None and nbits:
         if int(aec["n_values"]) != n:
             raise ValueError(f"CCSDS stream of {int(aec['n_values'])} values for {n} points")
         q = aec_decode(buf, aec).astype(np.float64)
@@ -501,12 +549,14 @@ class _Field:
     offset of the bitmap's bytes and values in the stream); `field_values` decodes it on demand."""
     raw_bitmap = None
     raw_aec = None        # the GRIB_AEC_DTYPE fields of a CCSDS-packed message (edition 2, template 5.42)
+    raw_cpx = None        # the GRIB_CPX_DTYPE fields of a complex-packed message (edition 2, templates 5.2 / 5.3)
 
     def field_values(self, buf):
         if self.values is not None:
             return self.values
         aec = None if self.raw_aec is None else np.array(self.raw_aec, dtype=GRIB_AEC_DTYPE)
-        return _decode_rule(buf, self.raw_rule, self.npoints, self.raw_bitmap, aec)
+        cpx = None if self.raw_cpx is None else np.array(self.raw_cpx, dtype=GRIB_CPX_DTYPE)
+        return _decode_rule(buf, self.raw_rule, self.npoints, self.raw_bitmap, aec, cpx)
 
     def _set_grid(self, rep, ni, nj, la1, lo1, la2, lo2, n_gauss, scan, pl, tol):
         if scan & 0x20:
@@ -682,6 +732,45 @@ def _ccsds_template(sec5):
     return ref, scale, decimal, nbits, flags, block, rsi
 
 
+def _complex_template(sec5, drt, n_values):
+    """Data representation templates 5.2 (complex packing) and 5.3 (with spatial differencing) from section 5: (R, 2^E, D,
+    width of the group references, then the fields of GRIB_CPX_DTYPE from n_groups to n_oct).  Octets 12 - 20 are those
+    of template 5.0, 21 = type of the original values, 22 = group splitting method, 23 = missing value management,
+    24 - 31 the two substitutes, 32 - 35 NG, 36 / 37 reference and bits of the group widths, 38 - 41 / 42 reference and
+    increment of the group lengths, 43 - 46 true length of the last group, 47 bits of the scaled group lengths; 5.3:
+    48 order of spatial differencing, 49 octets per extra descriptor -- taken from the WMO table; no file written by
+    NCEP's tools or ecCodes was at hand to pin them.  What the decoder does not take raises GribUnsupported naming it."""
+    what = f"GRIB-2 data representation template 5.{drt} (complex packing" + (" with spatial differencing)" if drt == 3 else ")")
+    need = 49 if drt == 3 else 47
+    if len(sec5) < need:
+        raise GribUnsupported(f"{what} in a section 5 of {len(sec5)} octets: the template takes {need}")
+    ref = float(np.frombuffer(bytes(sec5[11:15]), dtype=">f4")[0])
+    scale, decimal, nbits = 2.0 ** _sint(sec5[15:17]), _sint(sec5[17:19]), sec5[19]
+    mvm = sec5[22]
+    if mvm != 0:
+        raise GribUnsupported(f"{what} with missing value management {mvm} (substitute values inside the groups)")
+    n_groups, width_ref, width_bits = _uint(sec5[31:35]), sec5[35], sec5[36]
+    length_ref, length_inc, length_last, length_bits = _uint(sec5[37:41]), sec5[41], _uint(sec5[42:46]), sec5[46]
+    order, n_oct = (sec5[47], sec5[48]) if drt == 3 else (0, 0)
+    if order > 2:
+        raise GribUnsupported(f"{what} of order {order}: orders 0, 1 and 2 are decoded")
+    if order > 0 and not 1 <= n_oct <= 4:
+        raise GribUnsupported(f"{what} with {n_oct} octets per extra descriptor: 1..4 are decoded")
+    if nbits > 32:
+        raise GribUnsupported(f"{what} with group references of {nbits} bits")
+    if width_bits > 32 or length_bits > 32:
+        raise GribUnsupported(f"{what} with group widths stored in {width_bits} bits and group lengths in {length_bits}: "
+                              "at most 32 are decoded")
+    if n_values > 0 and n_groups == 0:
+        raise GribUnsupported(f"{what} of {n_values} values in no group")
+    if 0 < n_values <= order:
+        raise GribUnsupported(f"{what} of order {order} on {n_values} values")
+    if n_values >= 2 ** 31:
+        raise GribUnsupported(f"{what} of {n_values} values: fewer than 2^31 are decoded")
+    return ref, scale, decimal, nbits, (n_groups, nbits, width_ref, width_bits, length_ref, length_inc, length_last, length_bits,
+                                        order, n_oct if order else 0)
+
+
 class _Field2(_Field):
     """One field of a GRIB-2 message (a message may repeat sections 2 - 7 / 3 - 7 / 4 - 7 for further fields)."""
     edition = 2
@@ -728,19 +817,23 @@ class _Field2(_Field):
         self.level = level / 100.0 if self.level_type == 100 else level          # Pa -> hPa, as cfgrib's isobaricInhPa
         # --- section 5 / 6 / 7: packed values
         n_coded, drt = _uint(sec5[5:9]), _uint(sec5[9:11])
-        if drt not in (0, 42):
-            names = {2: "complex packing", 3: "complex packing with spatial differencing", 40: "JPEG 2000 packing",
-                     41: "PNG packing", 50: "spherical harmonics", 51: "spherical harmonics"}
+        if drt not in (0, 2, 3, 42):
+            names = {40: "JPEG 2000 packing", 41: "PNG packing", 50: "spherical harmonics", 51: "spherical harmonics"}
             raise GribUnsupported(f"GRIB-2 data representation template 5.{drt} ({names.get(drt, 'not simple packing')})")
         aec = None         # CCSDS: (ccsdsFlags, ccsdsBlockSize, ccsdsRsi); a constant field (0 bits) has no stream
+        cpx = None         # complex packing: GRIB_CPX_DTYPE's fields from n_groups to n_oct
         if drt == 42:
             ref, scale, decimal, nbits, *aec = _ccsds_template(sec5)
             aec = tuple(aec) if nbits else None
+        elif drt in (2, 3):
+            ref, scale, decimal, nbits, cpx = _complex_template(sec5, drt, n_coded)
         else:
             ref = float(np.frombuffer(bytes(sec5[11:15]), dtype=">f4")[0])
             scale, decimal, nbits = 2.0 ** _sint(sec5[15:17]), _sint(sec5[17:19]), sec5[19]
         if aec is not None and data_pos is not None:
             self.raw_aec = (data_pos + 5, len(sec7) - 5, n_coded, nbits, aec[1], aec[2], aec[0], 0)
+        if cpx is not None and data_pos is not None:
+            self.raw_cpx = (data_pos + 5, len(sec7) - 5, n_coded) + cpx + (0,)
         indicator = sec6[5] if sec6 is not None else 255
         if keep_raw and bitmap_pos is not None and data_pos is not None and indicator in (0, 254):
             # kept raw with its bitmap: where the bitmap lies and how many bits it sets, nothing unpacked
@@ -750,7 +843,7 @@ class _Field2(_Field):
             self.bitmap = None
             if n_coded != self.raw_bitmap[1]:
                 raise ValueError(f"GRIB-2 data section codes {n_coded} values, grid and bitmap need {self.raw_bitmap[1]}")
-            if nbits and aec is None and (len(sec7) - 5) * 8 < n_coded * nbits:
+            if nbits and aec is None and cpx is None and (len(sec7) - 5) * 8 < n_coded * nbits:
                 raise ValueError("GRIB-2 data section is shorter than its values")
             self.raw_rule = (data_pos + 5, ref, scale, 10.0 ** decimal, nbits)
             self.values = None
@@ -768,14 +861,16 @@ class _Field2(_Field):
         count = self.npoints if self.bitmap is None else int(self.bitmap.sum())
         if n_coded != count:
             raise ValueError(f"GRIB-2 data section codes {n_coded} values, grid and bitmap need {count}")
-        if nbits and aec is None and (len(sec7) - 5) * 8 < count * nbits:
+        if nbits and aec is None and cpx is None and (len(sec7) - 5) * 8 < count * nbits:
             raise ValueError("GRIB-2 data section is shorter than its values")
         self.raw_rule = None if (self.bitmap is not None or data_pos is None) else \
             (data_pos + 5, ref, scale, 10.0 ** decimal, nbits)
         if keep_raw and self.raw_rule is not None:
             self.values = None
             return
-        if aec is not None:       # the message's own stream, decoded on the host
+        if cpx is not None:       # the message's own groups, decoded on the host
+            q = cpx_decode(bytes(sec7[5:]), np.array((0, len(sec7) - 5, count) + cpx + (0,), dtype=GRIB_CPX_DTYPE)).astype(np.float64)
+        elif aec is not None:     # the message's own stream, decoded on the host
             q = aec_decode(bytes(sec7[5:]), np.array((0, len(sec7) - 5, count, nbits, aec[1], aec[2], aec[0], 0),
                                                      dtype=GRIB_AEC_DTYPE)).astype(np.float64)
         else:
@@ -855,7 +950,9 @@ def open_grib(path, decode=True, bitmaps=False):
     section 6 with its own bitmap or the previous field's): the reader records where the bitmap lies and how many bits
     it sets, `GribField.bitmaps` holds one record per field, and a variable may mix messages with and without one.
     CCSDS-packed messages (edition 2, template 5.42) are decoded on the host with decode=True and kept raw like the
-    others with decode=False: `GribField.ccsds` holds one record per field, simple-packed fields may stand among them."""
+    others with decode=False: `GribField.ccsds` holds one record per field, simple-packed fields may stand among them.
+    Complex-packed messages (templates 5.2 / 5.3) likewise: `GribField.cpx` holds one record per field, simple-packed
+    fields may stand among them; a variable that mixes CCSDS-packed and complex-packed messages is decoded."""
     with open(path, "rb") as f:
         file_bytes = f.read()
     msgs = _messages_of(file_bytes, path, keep_raw=not decode, keep_bitmaps=bool(bitmaps) and not decode)
@@ -907,6 +1004,8 @@ def open_grib(path, decode=True, bitmaps=False):
         bms = np.zeros((len(times), len(levels)), dtype=GRIB_BITMAP_DTYPE)
         bms["bitmap_off"], bms["n_values"] = GRIB_NO_BITMAP, g.npoints
         aecs = np.zeros((len(times), len(levels)), dtype=GRIB_AEC_DTYPE)
+        cpxs = np.zeros((len(times), len(levels)), dtype=GRIB_CPX_DTYPE)
+        cpxs["order"] = GRIB_CPX_SIMPLE
         for m, slot in zip(group, slots):
             if m.raw_rule is not None:
                 rows[slot] = m.raw_rule + (0,)
@@ -915,9 +1014,13 @@ def open_grib(path, decode=True, bitmaps=False):
                     bms[slot] = m.raw_bitmap
                 if m.raw_aec is not None:
                     aecs[slot] = m.raw_aec
+                if m.raw_cpx is not None:
+                    cpxs[slot] = m.raw_cpx
         # raw: every (time, level) slot filled by a message without a bitmap (a missing slot is NaN, which only a
         # decoded array holds).  Such a variable is never unpacked here; any other is decoded as with decode=True
         raw_ok = not decode and all(m.raw_rule is not None for m in group) and bool(filled.all())
+        has_aec, has_cpx = any(m.raw_aec is not None for m in group), any(m.raw_cpx is not None for m in group)
+        raw_ok = raw_ok and not (has_aec and has_cpx)      # one kind of coded record per variable
         arr = None
         if not raw_ok:
             arr = np.full((len(times), len(levels)) + hshape, np.nan, dtype=np.float32)
@@ -937,10 +1040,10 @@ def open_grib(path, decode=True, bitmaps=False):
         shape = tuple(n for n, keep in ((len(times), len(times) > 1), (len(levels), len(levels) > 1)) if keep) + hshape
         if raw_ok:
             if len(times) == 1:
-                rows, bms, aecs = rows[0:1], bms[0:1], aecs[0:1]
+                rows, bms, aecs, cpxs = rows[0:1], bms[0:1], aecs[0:1], cpxs[0:1]
             arr = GribField(shared, rows, shape, int(np.prod(hshape)),
                             bitmaps=bms if any(m.raw_bitmap is not None for m in group) else None,
-                            ccsds=aecs if any(m.raw_aec is not None for m in group) else None)
+                            ccsds=aecs if has_aec else None, cpx=cpxs if has_cpx else None)
         else:
             arr = arr.reshape(shape)
         ds[name] = DataArray(arr, dims=tuple(dims) + hdims, coords=vcoords, name=name,

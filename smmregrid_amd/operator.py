@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib
 from .device import (DeviceArray, bfloat16, check_half_pair, dtype_code, field_dtype_code, is_half_dtype,
                      is_packed_dtype, result_cache, result_dtype, _stream_handle, current_device, grib_aec_pack, grib_pack, grib_unpack,
-                     mem_info)
+                     grib_unpack_cpx, mem_info)
 
 
 def _cptr(a):
@@ -358,8 +358,38 @@ class SparseOperator:
         rows[idx] = rows_c
         return rows
 
+    @staticmethod
+    def _cpx_records(cpx, rows):
+        """`_ccsds_records` for complex packing: a record whose order is GRIB_CPX_SIMPLE marks a simple-packed row; the
+        bytes are those of the rows' slots, 4 per value."""
+        from .griblite import GRIB_CPX_DTYPE, GRIB_CPX_SIMPLE
+        cpx = np.ascontiguousarray(cpx, dtype=GRIB_CPX_DTYPE).ravel()
+        if cpx.size != rows.size:
+            raise ValueError(f"{cpx.size} complex-packing records for {rows.size} rows")
+        idx = np.flatnonzero(cpx["order"] != GRIB_CPX_SIMPLE)
+        sub = np.ascontiguousarray(cpx[idx])
+        total = ctypes.c_uint64(0)
+        _lib.call("smm_grib_cpx_layout", ctypes.cast(sub.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)), sub.size, None,
+                  ctypes.byref(total))
+        return cpx, idx, int(total.value)
+
+    @staticmethod
+    def _cpx_unpack(src, n_bytes, dst, shift, rows, cpx, idx, stream):
+        """`_ccsds_unpack` through smm_grib_cpx_unpack: the rows come back with the width their integers were stored at."""
+        _, rows_c = grib_unpack_cpx(src, rows[idx], cpx[idx], x_bytes=n_bytes, out=dst, stream=stream)
+        rows = rows.copy()
+        rows_c["byte_off"] += np.uint64(shift)
+        rows[idx] = rows_c
+        return rows
+
+    def _coded_road(self, ccsds, cpx):
+        """(records, `_*_records`, `_*_unpack`) of the coded rows of a call: CCSDS or complex packing, not both."""
+        if ccsds is not None and cpx is not None:
+            raise ValueError("cpx does not go with ccsds: a call's coded rows are of one kind")
+        return (cpx, self._cpx_records, self._cpx_unpack) if cpx is not None else (ccsds, self._ccsds_records, self._ccsds_unpack)
+
     def apply_grib(self, x, rows, x_bytes=None, y=None, masked=False, remap_area_min=0.0, flags=0, stream=None,
-                   bitmaps=None, skipna=False, ccsds=None):
+                   bitmaps=None, skipna=False, ccsds=None, cpx=None):
         """Y = epilogue(fill(decode(X)) . W) for GRIB simple-packed fields resident in HBM as they are on disk
         (smm_apply_grib).  x: a `DeviceArray` of uint8 -- or a raw device pointer with x_bytes -- holding the packed
         bit streams (4-byte aligned; the array -- or the allocation behind a raw pointer -- must cover x_bytes rounded
@@ -374,23 +404,29 @@ class SparseOperator:
         `apply(..., skipna=True, flags=APPLY_KERNEL_SELL)` on the decoded float32 field, NaN where the bitmap is 0.
         ccsds: one `GRIB_AEC_DTYPE` record per row -- x holds the CCSDS streams of GRIB-2 template 5.42 (a record with
         block_size 0: that row is simple-packed).  One device step ahead of the gather turns them into simple-packed
-        streams (smm_grib_aec_unpack); the result has the bits of the same call on the simple-packed integers."""
+        streams (smm_grib_aec_unpack); the result has the bits of the same call on the simple-packed integers.
+        cpx: one `GRIB_CPX_DTYPE` record per row -- x holds the complex-packed streams of templates 5.2 / 5.3 (a record
+        whose order is GRIB_CPX_SIMPLE: that row is simple-packed).  The same, through smm_grib_cpx_unpack; rows' nbits of
+        such a row is not read.  It does not go with ccsds."""
         rows, rows_p = self._grib_rows(rows)
-        if ccsds is not None:
+        if ccsds is not None or cpx is not None:
+            ccsds, records, unpack = self._coded_road(ccsds, cpx)
             if not isinstance(x, DeviceArray) or x.dtype != np.uint8:
-                raise TypeError("apply_grib(ccsds=) takes the coded bytes as a uint8 DeviceArray")
+                raise TypeError("apply_grib(ccsds= / cpx=) takes the coded bytes as a uint8 DeviceArray")
             n_bytes = x.nbytes if x_bytes is None else int(x_bytes)
             if (n_bytes + 3) // 4 * 4 > x.nbytes:
                 raise ValueError(f"x must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {x.nbytes}")
-            ccsds, idx, total = self._ccsds_records(ccsds, rows)
+            ccsds, idx, total = records(ccsds, rows)
             # bitmaps and simple-packed rows stay where they are in x: then x travels along in front of the new streams
-            keep = bitmaps is not None or idx.size < int((rows["nbits"] != 0).sum())
+            plain = rows["nbits"] != 0
+            plain[idx] = False
+            keep = bitmaps is not None or bool(plain.any())
             base = (n_bytes + 3) // 4 * 4 if keep else 0
             both = DeviceArray((max(base + total, 4),), np.uint8)
             if keep and base:
                 _lib.call("smm_memcpy_d2d", ctypes.c_void_p(both.ptr), ctypes.c_void_p(x.ptr), base, _stream_handle(stream))
             dst = DeviceArray((total,), np.uint8, ptr=both.ptr + base, base=both)
-            rows = self._ccsds_unpack(x, n_bytes, dst, base, rows, ccsds, idx, stream)
+            rows = unpack(x, n_bytes, dst, base, rows, ccsds, idx, stream)
             return self.apply_grib(both, rows, x_bytes=base + total, y=y, masked=masked, remap_area_min=remap_area_min,
                                    flags=flags, stream=stream, bitmaps=bitmaps, skipna=skipna)
         if isinstance(x, DeviceArray):
@@ -447,30 +483,35 @@ class SparseOperator:
                   float(remap_area_min), fl, int(chunk_rows))
         return GribField(out, rows_out, (n_batch, self.n_dst), self.n_dst, bitmaps=bitmaps_out)
 
-    def _apply_host_grib_ccsds(self, buf, rows, out, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds):
-        """`apply_host_grib(ccsds=)`: a synchronous loop over chunks of consecutive rows (`_grib_host_chunks`), each
+    def _apply_host_grib_ccsds(self, buf, rows, out, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds,
+                               cpx=None):
+        """`apply_host_grib(ccsds=)` and `apply_host_grib(cpx=)`: a synchronous loop over chunks of consecutive rows (`_grib_host_chunks`), each
         chunk's Y copied back."""
         n_batch, D = rows.size, self.n_dst
         if out is None:
             out = result_cache.empty((n_batch, D), np.float64)
         if out.shape != (n_batch, D) or out.dtype != np.float64 or not out.flags.c_contiguous:
             raise ValueError(f"out must be a C-contiguous float64 ({n_batch}, {D}) array")
-        for r0, r1, y in self._grib_host_chunks(buf, rows, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds):
+        for r0, r1, y in self._grib_host_chunks(buf, rows, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds,
+                                                cpx=cpx):
             y.to_host(out=out[r0:r1])
         return out
 
-    def _grib_host_chunks(self, buf, rows, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds, extra_cost=0):
+    def _grib_host_chunks(self, buf, rows, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds, extra_cost=0,
+                          cpx=None):
         """Chunks of consecutive rows, one after the other: the chunk's bytes (coded or simple-packed streams, bitmaps)
         staged and copied to the device, smm_grib_aec_unpack behind them into the same buffer for the coded rows, the
         device gather (smm_apply_grib_bm / _na).  Yields (first row, end row, the chunk's float64 Y on the device).  A
         chunk's staged bytes, transcoded streams, 4 B per sample of scratch, Y and extra_cost (bytes per row, what the
         caller puts beside them) stay within 256 MiB and a quarter of the free device memory; chunk_rows > 0 fixes the
-        rows.  ccsds: None -- every row is simple-packed."""
+        rows.  ccsds: None -- every row is simple-packed.  cpx: the coded rows are complex-packed instead
+        (smm_grib_cpx_unpack): such a row costs its slot of 4 B per value and 8 B per value plus 16 B per group of scratch."""
         from .griblite import GRIB_AEC_DTYPE, GRIB_NO_BITMAP
         n_batch, S, D = rows.size, self.n_src, self.n_dst
         if bitmaps is not None:
             bitmaps, _ = self._grib_bitmaps(bitmaps, n_batch)
-        ccsds, idx, _ = self._ccsds_records(np.zeros(n_batch, dtype=GRIB_AEC_DTYPE) if ccsds is None else ccsds, rows)
+        ccsds, records, unpack = self._coded_road(ccsds, cpx)
+        ccsds, idx, _ = records(np.zeros(n_batch, dtype=GRIB_AEC_DTYPE) if ccsds is None else ccsds, rows)
         coded = np.zeros(n_batch, dtype=bool)
         coded[idx] = True
         align4 = lambda v: (v + 3) // 4 * 4                                               # noqa: E731
@@ -478,7 +519,7 @@ class SparseOperator:
         n_val = np.full(n_batch, S, dtype=np.int64) if bitmaps is None else \
             np.where(has_bm, bitmaps["n_values"], S).astype(np.int64)
         if (ccsds["n_values"][idx].astype(np.int64) != n_val[idx]).any():
-            raise ValueError("a CCSDS record's n_values differs from the points its row holds")
+            raise ValueError("a coded row's record has n_values different from the points its row holds")
         nbits = rows["nbits"].astype(np.int64)
         in_off = np.where(coded, ccsds["byte_off"], rows["byte_off"]).astype(np.uint64)
         in_len = np.where(coded, ccsds["byte_len"].astype(np.int64), (n_val * nbits + 7) // 8).astype(np.int64)
@@ -486,7 +527,9 @@ class SparseOperator:
         if ((in_off.astype(object) + in_len.astype(object)) > buf.size).any() or \
                 (has_bm.any() and (bitmaps["bitmap_off"][has_bm].astype(object) + bm_len > buf.size).any()):
             raise ValueError(f"a row's bytes leave the buffer of {buf.size} bytes")
-        cost = align4(in_len) + np.where(coded, align4((n_val * nbits + 7) // 8) + 4 * n_val, 0) + D * 8 + \
+        device = 12 * n_val + 16 * ccsds["n_groups"].astype(np.int64) + 256 if cpx is not None else \
+            align4((n_val * nbits + 7) // 8) + 4 * n_val
+        cost = align4(in_len) + np.where(coded, device, 0) + D * 8 + \
             np.where(has_bm, align4(bm_len), 0) + extra_cost
         free, _ = mem_info()
         target = min(256 << 20, max(free // 4, 1))
@@ -514,12 +557,12 @@ class SparseOperator:
             staged = np.zeros(max(at, 4), dtype=np.uint8)
             for a, off, n in pieces:
                 staged[a:a + n] = buf[off:off + n]
-            _, idx_c, total = self._ccsds_records(aec_c, rows_c)
+            _, idx_c, total = records(aec_c, rows_c)
             both = DeviceArray((max(at + total, 4),), np.uint8)
             src = DeviceArray((staged.size,), np.uint8, ptr=both.ptr, base=both).copy_from_host(staged)
             dst = DeviceArray((total,), np.uint8, ptr=both.ptr + at, base=both)
             if idx_c.size:
-                rows_c = self._ccsds_unpack(src, at, dst, at, rows_c, aec_c, idx_c, None)
+                rows_c = unpack(src, at, dst, at, rows_c, aec_c, idx_c, None)
             y = self.apply_grib(both, rows_c, x_bytes=at + total, masked=masked, remap_area_min=remap_area_min, flags=fl,
                                 bitmaps=bm_c, skipna=skipna)
             yield r0, r1, y
@@ -575,7 +618,7 @@ class SparseOperator:
         return GribField(result[:at], rows_out, (n_batch, D), D, bitmaps=bitmaps_out, ccsds=ccsds_out)
 
     def apply_host_grib(self, buf, rows, out=None, masked=False, remap_area_min=0.0, flags=0, chunk_rows=0, bitmaps=None,
-                        skipna=False, grib_out=None, ccsds=None):
+                        skipna=False, grib_out=None, ccsds=None, cpx=None):
         """The host twin (smm_apply_host_grib): buf is a host uint8 array -- typically a whole GRIB file -- and rows as
         for `apply_grib`.  Each row's packed bytes are staged and cross PCIe as they are (2 B per cell at 16 bits), no
         host decode runs.  Returns a float64 (B, D) numpy array, the bits of `apply_host` on the decoded float32 field.
@@ -590,11 +633,20 @@ class SparseOperator:
         grib_out a `GribEncode` with `ccsds` set: the result comes back CCSDS-packed -- a `GribField` with `bitmaps` and
         `ccsds` set, in a buffer of its own, bytewise `grib_out.encode` of the float64 result.  The same synchronous chunk
         loop, with smm_grib_pack and smm_grib_aec_pack behind the gather; the input may be simple-packed or, through
-        ccsds=, CCSDS-packed itself."""
+        ccsds=, CCSDS-packed itself.
+        cpx as for `apply_grib`: the rows' complex-packed streams cross PCIe as they are and are decoded on the device, in
+        the same synchronous chunk loop.  It goes neither with ccsds nor with grib_out."""
         rows, rows_p = self._grib_rows(rows)
         buf = np.ascontiguousarray(buf)
         if buf.dtype != np.uint8 or buf.ndim != 1:
             raise TypeError("apply_host_grib takes the packed bytes as a 1-d uint8 array")
+        if cpx is not None:
+            if ccsds is not None:
+                raise ValueError("cpx does not go with ccsds: a call's coded rows are of one kind")
+            if grib_out is not None:
+                raise ValueError("cpx does not go with grib_out: decode the field on the host first")
+            return self._apply_host_grib_ccsds(buf, rows, out, masked, remap_area_min, flags, int(chunk_rows), bitmaps, skipna,
+                                               None, cpx=cpx)
         if grib_out is not None and getattr(grib_out, "ccsds", None) is not None:
             if out is not None:
                 raise ValueError("a CCSDS-coded result comes in a buffer of its own: its size is known only afterwards")

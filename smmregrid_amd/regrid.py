@@ -401,7 +401,8 @@ class Regridder(object):
         (outer..., level, inner..., horizontal...).  Everything else decodes it on the host -- what np.asarray would do
         anyway -- and goes on as before.  Under skipna it stays raw with packed_skipna=True (the _na entries)."""
         why = self._grib_decode_reason(source_data.dims, datagridtype, self._result_dtype(source_data),
-                                       bool(datagridtype.mask_dim), ccsds=source_data.data.ccsds is not None)
+                                       bool(datagridtype.mask_dim), ccsds=source_data.data.ccsds is not None,
+                                       cpx=source_data.data.cpx is not None)
         if why is None:
             return source_data
         if self.packed:
@@ -409,15 +410,22 @@ class Regridder(object):
         return DataArray(source_data.data.decode(), dims=source_data.dims, coords=source_data.coords,
                          attrs=source_data.attrs, name=source_data.name)
 
-    def _grib_decode_reason(self, dims, gridtype, out_dtype, levels, ccsds=False):
+    def _grib_decode_reason(self, dims, gridtype, out_dtype, levels, ccsds=False, cpx=False):
         """Why a `GribField` with these dims is decoded on the host, or None: it takes the raw road.  levels: it meets
         masked-level (3-D) weights.  ccsds: some of its fields are CCSDS-packed (`GribField.ccsds`) -- their road is the
-        one of 2-D weights and float64 results (smm_grib_aec_unpack ahead of the gather).  The one condition behind
-        `_grib_or_decoded` and the guards of `apply_weights` and `regrid3d`, which direct calls reach without it."""
+        one of 2-D weights and float64 results (smm_grib_aec_unpack ahead of the gather).  cpx: some are complex-packed
+        (`GribField.cpx`, templates 5.2 / 5.3) -- the same road through smm_grib_cpx_unpack, and no packed result: there is
+        no encoder for it, and the row record of such a field does not hold the width of its integers.  The one
+        condition behind `_grib_or_decoded` and the guards of `apply_weights` and `regrid3d`, which direct calls reach
+        without it."""
         if not self.packed:
             return "packed=False"
         if ccsds and levels:
             return "CCSDS packing on masked levels"
+        if cpx and levels:
+            return "complex packing on masked levels"
+        if cpx and self.grib_out:
+            return "complex packing with grib_out"
         if ccsds and self.grib_out and not getattr(self, "grib_out_ccsds", False):
             return "CCSDS packing with grib_out"
         if levels and not self.packed_levels:
@@ -572,7 +580,7 @@ class Regridder(object):
         src = source_data.data
         area_min, skipna = self.remap_area_min, self.skipna
         if isinstance(src, GribField) and self._grib_decode_reason(source_data.dims, None, out_dtype, False,
-                                                                   ccsds=src.ccsds is not None):
+                                                                   ccsds=src.ccsds is not None, cpx=src.cpx is not None):
             src = src.decode()      # a direct call: only the raw road of _grib_or_decoded ships the bit streams
         res_dtype = out_dtype if cf_out is None else cf_out.raw_dtype
         src_dtype = getattr(src, "dtype", None)
@@ -620,8 +628,9 @@ class Regridder(object):
                                            skipna=skipna, grib_out=enc, ccsds=src.ccsds if self.grib_out_ccsds else None)
                     return GribField(y.buf, y.rows, kept_shape + tgt_shape, op.n_dst, bitmaps=y.bitmaps, ccsds=y.ccsds)
                 # (CCSDS-packed fields: their streams are decoded on the device ahead of the gather, smm_grib_aec_unpack)
+                # (complex-packed fields likewise: smm_grib_cpx_unpack)
                 y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps,
-                                       skipna=skipna, ccsds=src.ccsds)
+                                       skipna=skipna, ccsds=src.ccsds, cpx=src.cpx)
                 return y.reshape(kept_shape + tgt_shape)
             if sb_in:
                 x = src.reshape(-1, n_batch)                  # (S, B): the batch values of a cell contiguous
@@ -710,7 +719,7 @@ class Regridder(object):
             out_dtype = self._result_dtype(source_data)
         skipna = self.skipna
         if isinstance(src, GribField) and self._grib_decode_reason(source_data.dims, gridtype, out_dtype, True,
-                                                                   ccsds=src.ccsds is not None):
+                                                                   ccsds=src.ccsds is not None, cpx=src.cpx is not None):
             src = src.decode()      # a direct call: only the raw road of _grib_or_decoded ships the bit streams
         grib_out = bool(grib_out) and isinstance(src, GribField) and not self.lazy
         if grib_out:      # one packed field per source field, in the source's order: no transpose

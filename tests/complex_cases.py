@@ -1,0 +1,369 @@
+"""Complex-packed GRIB-2 cases (data representation templates 5.2 / 5.3) shared by tests/test_grib_complex.py and
+tests/test_gpu_grib_complex.py.  Plain numpy, no GPU, and nothing of the product's parser: the encoder and the decoder
+below are written from the template text.
+
+    section 5 (octets)  12-15 R   16-17 E   18-19 D   20 bits of a group reference   21 type of original values
+                        22 group splitting method   23 missing value management   24-27, 28-31 substitutes   32-35 NG
+                        36 reference for group widths   37 bits per group width   38-41 reference for group lengths
+                        42 length increment   43-46 true length of the last group   47 bits per scaled group length
+                        5.3 only: 48 order of spatial differencing   49 octets per extra descriptor
+    section 7 (from octet 6)   [5.3: h_1 .. h_order, g -- sign-magnitude]   NG references | NG widths | NG lengths,
+                        each padded to an octet   the groups' values back to back
+
+THE HAND-ASSEMBLED MESSAGE (tests/golden/complex/hand_order2.grib2; `HAND_X`, `HAND_STREAM`): 12 values on a 4 x 3 grid,
+order 2, two octets per descriptor, three groups of 4, 5 and 3 values, R = 0, E = 0, D = 0.
+    X                  10 12 15 19 22 24 27 35 36 36 40 41
+    first differences     2  3  4  3  2  3  8  1  0  4  1
+    second differences       1  1 -1 -1  1  5 -7 -1  4 -3        g = -7
+    z = second - g     (0  0) 8  8  6  6  8 12  0  6 11  4        the two leading values are placeholders
+    groups             [0 0 8 8]  [6 6 8 12 0]  [6 11 4]          references 0, 0, 4; widths 4, 4, 3; lengths 4, 5, 3
+    section 5, octets 20 - 49:  03 (reference bits) 00 01 00 (type, splitting, missing value management)
+                       00000000 00000000 (substitutes)  00000003 (NG)  03 01 (width reference 3, 1 bit per width)
+                       00000004 01 00000003 01 (length reference 4, increment 1, last length 3, 1 bit per length)  02 02
+    section 7, octets 6 - 21:
+      00 0A  00 0C  80 07          h_1 = 10, h_2 = 12, g = -7 (sign bit + 7)
+      02 00                        references 000 000 100, seven pad bits
+      C0                           widths - 3: 1 1 0, five pad bits -- the section does not end on an octet
+      40                           (lengths - 4) / 1: 0 1 0 (the last group's entry is not used), five pad bits
+      00 88                        group 0, 4 bits each: 0000 0000 1000 1000
+      66 8C 0.                     group 1, 4 bits each: 0110 0110 1000 1100 0000
+      .5 C0                        group 2, 3 bits each after the nibble: (0000) 010 1|11 000 + 000 pad -> 05 C0
+"""
+import os
+
+import numpy as np
+
+from tests.ccsds_cases import _section, _sm, pack_bits
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "complex")
+HAND_X = np.array([10, 12, 15, 19, 22, 24, 27, 35, 36, 36, 40, 41], dtype=np.int64)
+HAND_STREAM = bytes.fromhex("000A000C8007" "0200" "C0" "40" "0088" "668C05C0")
+HAND_PARAMS = dict(n_groups=3, nbits=3, width_ref=3, width_bits=1, length_ref=4, length_inc=1, length_last=3, length_bits=1,
+                   order=2, n_oct=2)
+HAND_LENGTHS = [4, 5, 3]
+NI, NJ = 64, 32      # the 2048-cell source grid, as in tests/ccsds_cases.py
+S = NI * NJ
+PARAM_NAMES = ("n_groups", "nbits", "width_ref", "width_bits", "length_ref", "length_inc", "length_last", "length_bits",
+               "order", "n_oct")
+
+
+def bit_length(v):
+    return int(v).bit_length()
+
+
+def _bits(values, widths, total):
+    """The bit string (uint8 0/1, `total` long) of values[i] in widths[i] bits, big-endian, back to back."""
+    values, widths = np.asarray(values, dtype=np.uint64), np.asarray(widths, dtype=np.int64)
+    start = np.cumsum(widths) - widths
+    out = np.zeros(total, dtype=np.uint8)
+    for b in range(int(widths.max()) if widths.size else 0):
+        sel = widths > b
+        shift = (widths[sel] - 1 - b).astype(np.uint64)
+        out[start[sel] + b] = ((values[sel] >> shift) & np.uint64(1)).astype(np.uint8)
+    return out
+
+
+def _table(values, width):
+    """NG numbers of `width` bits, padded to an octet."""
+    values = np.asarray(values, dtype=np.uint64)
+    return np.packbits(_bits(values, np.full(values.size, width), values.size * width)).tobytes() if width else b""
+
+
+def differences(X, order):
+    """(z + g for every value -- zero for the placeholders --, g, [h_1 .. h_order]) of the integers X."""
+    X = np.asarray(X, dtype=np.int64)
+    d = np.zeros(X.size, dtype=np.int64)
+    if order == 1:
+        d[1:] = X[1:] - X[:-1]
+    elif order == 2:
+        d[2:] = X[2:] - 2 * X[1:-1] + X[:-2]
+    else:
+        return X.copy(), 0, []
+    g = int(d[order:].min())
+    d[:order] = g                 # so that the placeholders' z is 0
+    return d, g, [int(v) for v in X[:order]]
+
+
+def encode(X, order, lengths, n_oct=2, nbits=None, width_bits=None, length_bits=None, length_inc=1, widths=None,
+           zero_refs=False, width_ref=None):
+    """(stream: uint8 array, params: dict of PARAM_NAMES) for the integers X (0 <= X < 2^32) in groups of `lengths`.  Every
+    bit count is the smallest that holds its numbers unless given (a given one must hold them); widths: a width per
+    group instead of the minimal one; zero_refs: every group reference is 0 (then nbits may be 0)."""
+    X = np.asarray(X, dtype=np.int64)
+    lengths = [int(v) for v in lengths]
+    assert sum(lengths) == X.size and X.size > order and len(lengths) >= 1
+    d, g, heads = differences(X, order)
+    z = d - g
+    assert (z >= 0).all()
+    ends = np.cumsum(lengths)
+    starts = ends - lengths
+    refs, ws = [], []
+    for k, (a, b) in enumerate(zip(starts, ends)):
+        part = z[a:b]
+        ref = 0 if (zero_refs or part.size == 0) else int(part.min())
+        w = bit_length(int(part.max()) - ref) if part.size else 0
+        if widths is not None:
+            assert widths[k] >= w
+            w = int(widths[k])
+        refs.append(ref)
+        ws.append(w)
+    p = dict(n_groups=len(lengths), order=order, n_oct=n_oct if order else 0, length_inc=length_inc, length_last=lengths[-1])
+    p["nbits"] = bit_length(max(refs)) if nbits is None else nbits
+    p["width_ref"] = min(ws) if width_ref is None else width_ref
+    p["width_bits"] = bit_length(max(ws) - p["width_ref"]) if width_bits is None else width_bits
+    inner = lengths[:-1]
+    p["length_ref"] = min(inner) if inner else lengths[-1]
+    scaled = [(v - p["length_ref"]) // length_inc for v in inner] + [0]
+    assert all(p["length_ref"] + length_inc * s == v for s, v in zip(scaled, inner))
+    p["length_bits"] = bit_length(max(scaled)) if length_bits is None else length_bits
+    assert bit_length(max(refs)) <= p["nbits"] and bit_length(max(scaled)) <= p["length_bits"]
+    assert all(0 <= w - p["width_ref"] < (1 << p["width_bits"]) or w == p["width_ref"] for w in ws)
+    assert all(abs(v) < 1 << (8 * n_oct - 1) for v in heads + [g]), "a descriptor does not fit n_oct octets"
+    head = b"".join(_sm(v, n_oct) for v in heads + [g]) if order else b""
+    per_value_w = np.repeat(np.asarray(ws, dtype=np.int64), lengths)
+    per_value_ref = np.repeat(np.asarray(refs, dtype=np.int64), lengths)
+    total = int(per_value_w.sum())
+    data = np.packbits(_bits(z - per_value_ref, per_value_w, total)).tobytes()
+    stream = head + _table(refs, p["nbits"]) + _table([w - p["width_ref"] for w in ws], p["width_bits"]) + \
+        _table(scaled, p["length_bits"]) + data
+    return np.frombuffer(stream, dtype=np.uint8).copy(), p
+
+
+def numpy_decode(stream, n_values, p):
+    """The integers X (int64) of a stream, by the template text; plain numpy, with none of encode's helpers: the bits are
+    taken apart with np.unpackbits."""
+    bits = np.unpackbits(np.asarray(stream, dtype=np.uint8))
+    ng, order, n_oct = p["n_groups"], p["order"], p["n_oct"]
+    pos = 0
+
+    def number(at, width):
+        v = 0
+        for b in bits[at:at + width]:
+            v = (v << 1) | int(b)
+        return v
+
+    def signed(at):
+        v = number(at, 8 * n_oct)
+        sign = 1 << (8 * n_oct - 1)
+        return -(v & (sign - 1)) if v & sign else v
+    heads = []
+    g = 0
+    if order:
+        heads = [signed(8 * n_oct * k) for k in range(order)]
+        g = signed(8 * n_oct * order)
+        pos = 8 * n_oct * (order + 1)
+
+    def table(width):
+        nonlocal pos
+        if width == 0:
+            return np.zeros(ng, dtype=np.int64)
+        m = bits[pos:pos + ng * width].reshape(ng, width).astype(np.int64)
+        pos += (ng * width + 7) // 8 * 8
+        return m @ (np.int64(1) << np.arange(width - 1, -1, -1, dtype=np.int64))
+    refs = table(p["nbits"])
+    ws = p["width_ref"] + table(p["width_bits"])
+    ls = p["length_ref"] + p["length_inc"] * table(p["length_bits"])
+    ls[-1] = p["length_last"]
+    assert int(ls.sum()) == n_values and int(ws.max()) <= 32
+    w = np.repeat(ws, ls)
+    start = pos + np.cumsum(w) - w
+    stored = np.zeros(n_values, dtype=np.int64)
+    for b in range(int(ws.max())):
+        sel = w > b
+        stored[sel] = (stored[sel] << 1) | bits[start[sel] + b]
+    z = np.repeat(refs, ls) + stored
+    if order == 0:
+        return z
+    X = np.zeros(n_values, dtype=np.int64)
+    X[:order] = heads
+    if order == 1:
+        X[1:] = heads[0] + np.cumsum(z[1:] + g)
+    else:
+        first = np.cumsum(np.concatenate([[heads[1] - heads[0]], z[2:] + g]))       # X_i - X_(i-1) for i >= 1
+        X[1:] = heads[0] + np.cumsum(first)
+    return X
+
+
+def record(byte_off, byte_len, n_values, p):
+    """A GRIB_CPX_DTYPE record (the dtype comes from the product; the numbers do not)."""
+    from smmregrid_amd import GRIB_CPX_DTYPE
+    return np.array((byte_off, byte_len, n_values) + tuple(p[k] for k in PARAM_NAMES) + (0,), dtype=GRIB_CPX_DTYPE)
+
+
+def width_of(X):
+    return bit_length(int(np.max(X))) if len(X) else 0
+
+
+# ------------------------------------------------------------------------------------------------ the cases
+class Case:
+    def __init__(self, name, X, order, lengths, **kw):
+        self.name, self.X, self.order, self.lengths, self.kw = name, np.asarray(X, dtype=np.int64), order, list(lengths), kw
+        self.stream, self.params = encode(self.X, order, self.lengths, **kw)
+        self.n_values = int(self.X.size)
+        self.width = width_of(self.X)
+
+    def record(self, byte_off):
+        return record(byte_off, self.stream.size, self.n_values, self.params)
+
+    def __repr__(self):
+        return self.name
+
+
+def even(n, k):
+    """k lengths summing to n, as even as they get."""
+    return [n // k + (i < n % k) for i in range(k)]
+
+
+def _smooth(n, seed, amp, bits):
+    rng = np.random.default_rng(seed)
+    t = np.arange(n) / n
+    v = 0.5 + 0.35 * np.sin(2 * np.pi * (3 * t + rng.random())) + 0.1 * np.sin(2 * np.pi * 17 * t) + amp * rng.standard_normal(n)
+    return np.clip(np.rint(v * ((1 << bits) - 1)), 0, (1 << bits) - 1).astype(np.int64)
+
+
+_CASES = []
+
+
+def cases():
+    """Every case, built once.  2048 values unless the name says otherwise."""
+    if _CASES:
+        return list(_CASES)
+    rng = np.random.default_rng(11)
+    c = _CASES.append
+    n = S
+    c(Case("order0_noise12", rng.integers(0, 4096, n), 0, even(n, 64)))
+    c(Case("order1_noct1", 60 + np.cumsum(rng.integers(0, 4, n)) - np.arange(n) % 3, 1, even(n, 40), n_oct=1))
+    c(Case("order1_noct2", _smooth(n, 1, 0.002, 12), 1, even(n, 64), n_oct=2))
+    c(Case("order2_noct3", _smooth(n, 2, 0.0005, 16), 2, even(n, 64), n_oct=3))
+    c(Case("order2_noct4", _smooth(n, 3, 0.0, 30), 2, even(n, 33), n_oct=4))
+    c(Case("order1_descending", np.linspace(60000, 100, n).astype(np.int64) + rng.integers(0, 3, n), 1, even(n, 50), n_oct=3))
+    curved = (2000 + 1500 * np.sin(np.arange(n) / 9.0) + rng.integers(0, 40, n)).astype(np.int64)
+    c(Case("order2_curvature", curved, 2, even(n, 64)))
+    wide = np.concatenate([np.full(512, 5), 5 + rng.integers(0, 2, 512), rng.integers(0, 2 ** 31, 512), rng.integers(0, 2 ** 32, 512)])
+    wide[1030], wide[1600] = 2 ** 31 - 1, 2 ** 32 - 1
+    c(Case("order0_widths_0_1_31_32", wide, 0, [512, 512, 512, 512]))
+    c(Case("order0_width_bits0", rng.integers(0, 1000, n), 0, even(n, 30), widths=[10] * 30, width_bits=0))
+    c(Case("order1_length_bits0_last48", _smooth(n, 4, 0.001, 14), 1, [100] * 20 + [48], length_bits=0))
+    sevens = [3 + 7 * int(k) for k in rng.integers(0, 6, 60)]
+    c(Case("order2_inc7_last1", _smooth(sum(sevens) + 1, 5, 0.001, 16), 2, sevens + [1], length_inc=7, n_oct=3))
+    c(Case("order0_inc1", rng.integers(0, 300, n), 0, [20, 21, 25, 20, 30] + even(n - 116, 13)))
+    c(Case("order1_one_group", _smooth(n, 6, 0.01, 10), 1, [n]))
+    c(Case("order0_groups_of_one", rng.integers(0, 70000, n), 0, [1] * n))
+    # five groups: 15 bits in each of the three tables, none ends on an octet
+    c(Case("order0_five_groups_3bits", rng.integers(0, 8, n) + np.repeat([0, 1, 2, 3, 7], [400, 401, 405, 407, 435]),
+           0, [400, 401, 405, 407, 435], nbits=3, width_bits=3, length_bits=3, width_ref=0))
+    c(Case("order1_nbits0", _smooth(n, 8, 0.003, 12), 1, even(n, 64), zero_refs=True, nbits=0))
+    c(Case("order0_all_zero", np.zeros(n), 0, [n]))
+    c(Case("order1_constant_777", np.full(n, 777), 1, even(n, 8)))
+    c(Case("short1500_order2", _smooth(1500, 9, 0.001, 16), 2, even(1500, 47), n_oct=3))
+    c(Case("short1500_order1", _smooth(1500, 10, 0.01, 12), 1, even(1500, 20)))
+    c(Case("short1500_order0", rng.integers(0, 2 ** 24, 1500), 0, even(1500, 31)))
+    c(Case("n3_order2", [7, 3, 9], 2, [2, 1]))
+    c(Case("n2_order1", [5, 4], 1, [2]))
+    big_l = rng.integers(1, 15, 40000)             # uneven lengths; the last group takes what is left
+    big_l[-1] = 1
+    big_l[-1] = 300000 - int(big_l[:-1].sum()) if int(big_l[:-1].sum()) < 300000 else 0
+    while big_l[-1] < 1:                           # (the draw sums to about 300000: shorten groups until it fits)
+        k = int(np.argmax(big_l[:-1]))
+        big_l[k] -= 1
+        big_l[-1] = 300000 - int(big_l[:-1].sum())
+    c(Case("big300000_order2", _smooth(300000, 12, 0.0002, 16), 2, big_l, n_oct=3))
+    return list(_CASES)
+
+
+def case(name):
+    return next(k for k in cases() if k.name == name)
+
+
+GRID_ROWS = ["order2_noct3", "order1_noct2", "order0_noise12", "order2_curvature", "order0_widths_0_1_31_32", "order1_nbits0",
+             "order0_all_zero", "order1_constant_777"]                                   # B = 8, 2048 values each
+SHORT_ROWS = ["short1500_order2", "short1500_order1", "short1500_order0"]                # 1500 values: bitmapped
+
+
+def present_1500():
+    present = np.zeros(S, dtype=bool)
+    present[np.random.default_rng(5).permutation(S)[:1500]] = True
+    return present
+
+
+# ------------------------------------------------------------------------------------------------ GRIB-2 messages
+def section5(n_values, p, R=0.0, E=0, D=0, drt=None, mvm=0):
+    """The body of section 5 (from octet 6) for template 5.2 (order 0) or 5.3."""
+    drt = (3 if p["order"] else 2) if drt is None else drt
+    body = int(n_values).to_bytes(4, "big") + drt.to_bytes(2, "big") + np.array(R, dtype=">f4").tobytes() + _sm(E, 2) + _sm(D, 2) + \
+        bytes([p["nbits"], 0, 1, mvm]) + bytes(8) + p["n_groups"].to_bytes(4, "big") + bytes([p["width_ref"], p["width_bits"]]) + \
+        p["length_ref"].to_bytes(4, "big") + bytes([p["length_inc"]]) + p["length_last"].to_bytes(4, "big") + bytes([p["length_bits"]])
+    if drt == 3:
+        body += bytes([p["order"], p["n_oct"]])
+    return body
+
+
+def grib2_message(fields, ni=NI, nj=NJ):
+    """A GRIB-2 message on an ni x nj lon/lat grid, sections 4 - 7 once per field (sections 1, 3, 4 and 6 as
+    tests/ccsds_cases.grib2_message writes them).  A field is a dict: R, E, D, level (Pa), step, bitmap (None, a bool
+    array, or "previous"), and either cpx=(stream, params, n_values) with optional s5=a ready body of section 5, or
+    q + nbits for a simple-packed field."""
+    s1 = (7).to_bytes(2, "big") + (0).to_bytes(2, "big") + bytes([27, 0, 1]) + (2023).to_bytes(2, "big") + \
+        bytes([6, 27, 0, 0, 0, 0, 1])
+    g = bytearray(58)
+    g[0] = 6
+    g[16:20], g[20:24] = ni.to_bytes(4, "big"), nj.to_bytes(4, "big")
+    g[24:28], g[28:32] = (0).to_bytes(4, "big"), (0xFFFFFFFF).to_bytes(4, "big")
+    micro = lambda v: _sm(int(round(v * 1e6)), 4)         # noqa: E731
+    dlon, dlat = 360.0 / ni, 180.0 / nj
+    g[32:36], g[36:40] = micro(90.0 - dlat / 2), micro(0.0)
+    g[40] = 48
+    g[41:45], g[45:49] = micro(-90.0 + dlat / 2), micro(360.0 - dlon)
+    g[49:53] = int(round(dlon * 1e6)).to_bytes(4, "big")
+    g[53:57] = int(round(dlat * 1e6)).to_bytes(4, "big")
+    s3 = bytes([0]) + (ni * nj).to_bytes(4, "big") + bytes([0, 0]) + (0).to_bytes(2, "big") + bytes(g)
+    body = _section(1, s1) + _section(3, s3)
+    for f in fields:
+        s4 = (0).to_bytes(2, "big") + (0).to_bytes(2, "big") + bytes([0, 0, 2, 0, 0]) + (0).to_bytes(2, "big") + \
+            bytes([0, 1]) + int(f.get("step", 0)).to_bytes(4, "big") + bytes([100, 0]) + _sm(int(f.get("level", 85000)), 4) + \
+            bytes([255, 255]) + (0xFFFFFFFF).to_bytes(4, "big")
+        if f.get("cpx") is None:
+            q, nbits = np.asarray(f["q"], dtype=np.uint64), int(f["nbits"])
+            s5 = q.size.to_bytes(4, "big") + (0).to_bytes(2, "big") + np.array(f.get("R", 0.0), dtype=">f4").tobytes() + \
+                _sm(f.get("E", 0), 2) + _sm(f.get("D", 0), 2) + bytes([nbits, 0])
+            data = pack_bits(q, nbits).tobytes()
+        else:
+            stream, p, n_values = f["cpx"]
+            s5 = f.get("s5") or section5(n_values, p, f.get("R", 0.0), f.get("E", 0), f.get("D", 0))
+            data = np.asarray(stream, dtype=np.uint8).tobytes()
+        bitmap = f.get("bitmap")
+        if bitmap is None:
+            s6 = bytes([255])
+        elif isinstance(bitmap, str):
+            s6 = bytes([254])
+        else:
+            s6 = bytes([0]) + np.packbits(np.asarray(bitmap, np.uint8).ravel()).tobytes()
+        body += _section(4, s4) + _section(5, s5) + _section(6, s6) + _section(7, data)
+    body += b"7777"
+    return b"GRIB" + bytes([0, 0, 0, 2]) + (16 + len(body)).to_bytes(8, "big") + body
+
+
+# (case, level in Pa, step, bitmap, R, E, D) in message order: two times of three levels; the 850 hPa fields are
+# bitmapped, the second one through "the bitmap of the field before"; the last field is simple-packed in both files
+MESSAGE_SPECS = [("short1500_order2", 85000, 0, "own", 270.0, -4, 0), ("short1500_order1", 85000, 6, "previous", 0.0, 2, 2),
+                 ("order2_noct3", 50000, 0, None, -12.5, -6, 1), ("order1_noct2", 50000, 6, None, 1.0e3, -10, 0),
+                 ("order0_widths_0_1_31_32", 25000, 0, None, 250.0, -3, 0), ("order0_noise12", 25000, 6, None, 3.0, 0, 0)]
+
+
+def message_fields(coded, all_coded=False):
+    """The fields of MESSAGE_SPECS for `grib2_message`: complex-packed (but the last, simple-packed, unless all_coded),
+    or the simple-packed twins of the same integers at the integers' own minimal width."""
+    fields = []
+    for k, (name, level, step, bitmap, R, E, D) in enumerate(MESSAGE_SPECS):
+        cs = case(name)
+        f = dict(R=R, E=E, D=D, level=level, step=step, bitmap=present_1500() if bitmap == "own" else bitmap)
+        if coded and (all_coded or k != len(MESSAGE_SPECS) - 1):
+            f["cpx"] = (cs.stream, cs.params, cs.n_values)
+        else:
+            f["q"], f["nbits"] = cs.X, cs.width
+        fields.append(f)
+    return fields
+
+
+def hand_message():
+    return grib2_message([dict(cpx=(np.frombuffer(HAND_STREAM, np.uint8), HAND_PARAMS, 12))], 4, 3)
