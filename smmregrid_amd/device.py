@@ -568,28 +568,8 @@ def grib_unpack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None):
     (DeviceArray of uint8, GRIB_ROW_DTYPE records): each field's integers big-endian with the field's own width at a
     4-byte-aligned offset -- what `SparseOperator.apply_grib(x, rows, bitmaps=...)` takes as it is.  A field of width 0
     passes through untouched.  out: a uint8 DeviceArray to unpack into.  The stream is synchronised on return."""
-    from .griblite import GRIB_AEC_DTYPE, GRIB_ROW_DTYPE
-    if not isinstance(device_bytes, DeviceArray) or device_bytes.dtype != np.uint8:
-        raise TypeError("grib_unpack takes the coded bytes as a uint8 DeviceArray")
-    rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
-    ccsds = np.ascontiguousarray(ccsds, dtype=GRIB_AEC_DTYPE).ravel()
-    if ccsds.size != rows.size:
-        raise ValueError(f"{ccsds.size} CCSDS records for {rows.size} rows")
-    n_bytes = device_bytes.nbytes if x_bytes is None else int(x_bytes)
-    if (n_bytes + 3) // 4 * 4 > device_bytes.nbytes:
-        raise ValueError(f"the array must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {device_bytes.nbytes}")
-    aec_p = ctypes.cast(ccsds.ctypes.data, ctypes.POINTER(_lib.GribAecStruct))
-    total = ctypes.c_uint64(0)
-    _lib.call("smm_grib_aec_layout", aec_p, rows.size, None, ctypes.byref(total))
-    if out is None:
-        out = DeviceArray((max(total.value, 4),), np.uint8)
-    elif not isinstance(out, DeviceArray) or out.dtype != np.uint8 or out.nbytes < total.value:
-        raise ValueError(f"out must be a uint8 DeviceArray of at least {total.value} bytes")
-    rows_out = np.zeros(rows.size, dtype=GRIB_ROW_DTYPE)
-    _lib.call("smm_grib_aec_unpack", current_device(), ctypes.c_void_p(device_bytes.ptr), n_bytes, aec_p,
-              ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)), rows.size, ctypes.c_void_p(out.ptr),
-              out.nbytes, ctypes.cast(rows_out.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)), _stream_handle(stream))
-    return out, rows_out
+    from . import _grib
+    return _grib.unpack_device("grib_unpack", _grib.CCSDS, device_bytes, rows, ccsds, x_bytes, out, stream)
 
 
 def grib_unpack_cpx(device_bytes, rows, cpx, x_bytes=None, out=None, stream=None):
@@ -602,28 +582,8 @@ def grib_unpack_cpx(device_bytes, rows, cpx, x_bytes=None, out=None, stream=None
     the returned record's nbits holds -- what `SparseOperator.apply_grib(x, rows, bitmaps=...)` takes as it is.  A field
     whose record is marked GRIB_CPX_SIMPLE passes through untouched.  out: a uint8 DeviceArray to unpack into.  The
     stream is synchronised on return."""
-    from .griblite import GRIB_CPX_DTYPE, GRIB_ROW_DTYPE
-    if not isinstance(device_bytes, DeviceArray) or device_bytes.dtype != np.uint8:
-        raise TypeError("grib_unpack_cpx takes the coded bytes as a uint8 DeviceArray")
-    rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
-    cpx = np.ascontiguousarray(cpx, dtype=GRIB_CPX_DTYPE).ravel()
-    if cpx.size != rows.size:
-        raise ValueError(f"{cpx.size} complex-packing records for {rows.size} rows")
-    n_bytes = device_bytes.nbytes if x_bytes is None else int(x_bytes)
-    if (n_bytes + 3) // 4 * 4 > device_bytes.nbytes:
-        raise ValueError(f"the array must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {device_bytes.nbytes}")
-    cpx_p = ctypes.cast(cpx.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct))
-    total = ctypes.c_uint64(0)
-    _lib.call("smm_grib_cpx_layout", cpx_p, rows.size, None, ctypes.byref(total))
-    if out is None:
-        out = DeviceArray((max(total.value, 4),), np.uint8)
-    elif not isinstance(out, DeviceArray) or out.dtype != np.uint8 or out.nbytes < total.value:
-        raise ValueError(f"out must be a uint8 DeviceArray of at least {total.value} bytes")
-    rows_out = np.zeros(rows.size, dtype=GRIB_ROW_DTYPE)
-    _lib.call("smm_grib_cpx_unpack", current_device(), ctypes.c_void_p(device_bytes.ptr), n_bytes, cpx_p,
-              ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)), rows.size, ctypes.c_void_p(out.ptr),
-              out.nbytes, ctypes.cast(rows_out.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)), _stream_handle(stream))
-    return out, rows_out
+    from . import _grib
+    return _grib.unpack_device("grib_unpack_cpx", _grib.CPX, device_bytes, rows, cpx, x_bytes, out, stream)
 
 
 def grib_aec_pack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None):
@@ -636,27 +596,15 @@ def grib_aec_pack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None
     byte_off and byte_len set): the streams lie back to back in field order, each at a 4-byte-aligned offset, bytewise what
     `griblite.aec_encode` gives.  A field of width 0 has no stream (byte_len 0, block_size 0).  out: a uint8 DeviceArray of
     at least the bound (smm_grib_aec_pack_bound) to code into.  The stream is synchronised on return."""
-    from .griblite import GRIB_AEC_DTYPE, GRIB_ROW_DTYPE
-    if not isinstance(device_bytes, DeviceArray) or device_bytes.dtype != np.uint8:
-        raise TypeError("grib_aec_pack takes the packed bytes as a uint8 DeviceArray")
-    rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
-    ccsds = np.ascontiguousarray(ccsds, dtype=GRIB_AEC_DTYPE).ravel()
-    if ccsds.size != rows.size:
-        raise ValueError(f"{ccsds.size} CCSDS records for {rows.size} rows")
-    n_bytes = device_bytes.nbytes if x_bytes is None else int(x_bytes)
-    if (n_bytes + 3) // 4 * 4 > device_bytes.nbytes:
-        raise ValueError(f"the array must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {device_bytes.nbytes}")
-    aec_p = ctypes.cast(ccsds.ctypes.data, ctypes.POINTER(_lib.GribAecStruct))
-    bound = ctypes.c_uint64(0)
-    _lib.call("smm_grib_aec_pack_bound", aec_p, rows.size, None, ctypes.byref(bound))
-    if out is None:
-        out = DeviceArray((max(bound.value, 4),), np.uint8)
-    elif not isinstance(out, DeviceArray) or out.dtype != np.uint8 or out.nbytes < bound.value:
-        raise ValueError(f"out must be a uint8 DeviceArray of at least {bound.value} bytes")
+    from . import _grib
+    from .griblite import GRIB_AEC_DTYPE
+    x_ptr, n_bytes, rows, ccsds, out = _grib.transcode_args("grib_aec_pack", _grib.CCSDS, "smm_grib_aec_pack_bound",
+                                                            device_bytes, rows, ccsds, x_bytes, out)
     ccsds_out = np.zeros(rows.size, dtype=GRIB_AEC_DTYPE)
     used = ctypes.c_uint64(0)
-    _lib.call("smm_grib_aec_pack", current_device(), ctypes.c_void_p(device_bytes.ptr), n_bytes,
-              ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)), aec_p, rows.size, ctypes.c_void_p(out.ptr),
+    _lib.call("smm_grib_aec_pack", current_device(), x_ptr, n_bytes,
+              ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)),
+              ctypes.cast(ccsds.ctypes.data, ctypes.POINTER(_lib.GribAecStruct)), rows.size, ctypes.c_void_p(out.ptr),
               out.nbytes, ctypes.cast(ccsds_out.ctypes.data, ctypes.POINTER(_lib.GribAecStruct)), ctypes.byref(used),
               _stream_handle(stream))
     rows_out = rows.copy()

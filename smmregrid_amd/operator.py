@@ -10,10 +10,9 @@ import time
 
 import numpy as np
 
-from . import _lib
+from . import _grib, _lib
 from .device import (DeviceArray, bfloat16, check_half_pair, dtype_code, field_dtype_code, is_half_dtype,
-                     is_packed_dtype, result_cache, result_dtype, _stream_handle, current_device, grib_aec_pack, grib_pack, grib_unpack,
-                     grib_unpack_cpx, mem_info)
+                     is_packed_dtype, result_cache, result_dtype, _stream_handle, current_device, grib_aec_pack, grib_pack)
 
 
 def _cptr(a):
@@ -321,73 +320,6 @@ class SparseOperator:
         return _apply_call("smm_apply_host", self.handle, x, (ldx,), out,
                            (self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows)), y_res, cf, cf_out, "out")
 
-    def _grib_rows(self, rows):
-        from .griblite import GRIB_ROW_DTYPE
-        rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
-        return rows, ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct))
-
-    def _grib_bitmaps(self, bitmaps, n_batch):
-        from .griblite import GRIB_BITMAP_DTYPE
-        bitmaps = np.ascontiguousarray(bitmaps, dtype=GRIB_BITMAP_DTYPE).ravel()
-        if bitmaps.size != n_batch:
-            raise ValueError(f"{bitmaps.size} bitmap records for {n_batch} rows")
-        return bitmaps, ctypes.cast(bitmaps.ctypes.data, ctypes.POINTER(_lib.GribBitmapStruct))
-
-    @staticmethod
-    def _ccsds_records(ccsds, rows):
-        """(records, which rows have a coded stream, bytes of their transcoded streams): a record with block_size 0
-        marks a simple-packed row, a row of width 0 has no stream at all."""
-        from .griblite import GRIB_AEC_DTYPE
-        ccsds = np.ascontiguousarray(ccsds, dtype=GRIB_AEC_DTYPE).ravel()
-        if ccsds.size != rows.size:
-            raise ValueError(f"{ccsds.size} CCSDS records for {rows.size} rows")
-        idx = np.flatnonzero((ccsds["block_size"] != 0) & (rows["nbits"] != 0))
-        sub = np.ascontiguousarray(ccsds[idx])
-        total = ctypes.c_uint64(0)
-        _lib.call("smm_grib_aec_layout", ctypes.cast(sub.ctypes.data, ctypes.POINTER(_lib.GribAecStruct)), sub.size, None,
-                  ctypes.byref(total))
-        return ccsds, idx, int(total.value)
-
-    @staticmethod
-    def _ccsds_unpack(src, n_bytes, dst, shift, rows, ccsds, idx, stream):
-        """smm_grib_aec_unpack of rows `idx`: their streams in src[:n_bytes] become simple-packed streams in dst.  Returns
-        the row table with those rows pointing at `shift` + their place in dst, the others as they were."""
-        _, rows_c = grib_unpack(src, rows[idx], ccsds[idx], x_bytes=n_bytes, out=dst, stream=stream)
-        rows = rows.copy()
-        rows_c["byte_off"] += np.uint64(shift)
-        rows[idx] = rows_c
-        return rows
-
-    @staticmethod
-    def _cpx_records(cpx, rows):
-        """`_ccsds_records` for complex packing: a record whose order is GRIB_CPX_SIMPLE marks a simple-packed row; the
-        bytes are those of the rows' slots, 4 per value."""
-        from .griblite import GRIB_CPX_DTYPE, GRIB_CPX_SIMPLE
-        cpx = np.ascontiguousarray(cpx, dtype=GRIB_CPX_DTYPE).ravel()
-        if cpx.size != rows.size:
-            raise ValueError(f"{cpx.size} complex-packing records for {rows.size} rows")
-        idx = np.flatnonzero(cpx["order"] != GRIB_CPX_SIMPLE)
-        sub = np.ascontiguousarray(cpx[idx])
-        total = ctypes.c_uint64(0)
-        _lib.call("smm_grib_cpx_layout", ctypes.cast(sub.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)), sub.size, None,
-                  ctypes.byref(total))
-        return cpx, idx, int(total.value)
-
-    @staticmethod
-    def _cpx_unpack(src, n_bytes, dst, shift, rows, cpx, idx, stream):
-        """`_ccsds_unpack` through smm_grib_cpx_unpack: the rows come back with the width their integers were stored at."""
-        _, rows_c = grib_unpack_cpx(src, rows[idx], cpx[idx], x_bytes=n_bytes, out=dst, stream=stream)
-        rows = rows.copy()
-        rows_c["byte_off"] += np.uint64(shift)
-        rows[idx] = rows_c
-        return rows
-
-    def _coded_road(self, ccsds, cpx):
-        """(records, `_*_records`, `_*_unpack`) of the coded rows of a call: CCSDS or complex packing, not both."""
-        if ccsds is not None and cpx is not None:
-            raise ValueError("cpx does not go with ccsds: a call's coded rows are of one kind")
-        return (cpx, self._cpx_records, self._cpx_unpack) if cpx is not None else (ccsds, self._ccsds_records, self._ccsds_unpack)
-
     def apply_grib(self, x, rows, x_bytes=None, y=None, masked=False, remap_area_min=0.0, flags=0, stream=None,
                    bitmaps=None, skipna=False, ccsds=None, cpx=None):
         """Y = epilogue(fill(decode(X)) . W) for GRIB simple-packed fields resident in HBM as they are on disk
@@ -408,169 +340,41 @@ class SparseOperator:
         cpx: one `GRIB_CPX_DTYPE` record per row -- x holds the complex-packed streams of templates 5.2 / 5.3 (a record
         whose order is GRIB_CPX_SIMPLE: that row is simple-packed).  The same, through smm_grib_cpx_unpack; rows' nbits of
         such a row is not read.  It does not go with ccsds."""
-        rows, rows_p = self._grib_rows(rows)
-        if ccsds is not None or cpx is not None:
-            ccsds, records, unpack = self._coded_road(ccsds, cpx)
-            if not isinstance(x, DeviceArray) or x.dtype != np.uint8:
-                raise TypeError("apply_grib(ccsds= / cpx=) takes the coded bytes as a uint8 DeviceArray")
-            n_bytes = x.nbytes if x_bytes is None else int(x_bytes)
-            if (n_bytes + 3) // 4 * 4 > x.nbytes:
-                raise ValueError(f"x must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {x.nbytes}")
-            ccsds, idx, total = records(ccsds, rows)
+        rows, rows_p = _grib.grib_rows(rows)
+        kind, recs = _grib.one_kind(ccsds, cpx)
+        x_ptr, n_bytes = _grib.packed_bytes(x, x_bytes, "apply_grib", raw=kind is None)
+        if kind is not None:
+            recs = _grib.records(kind, recs, rows)
+            idx, total = _grib.coded_rows(kind, recs, rows)
             # bitmaps and simple-packed rows stay where they are in x: then x travels along in front of the new streams
             plain = rows["nbits"] != 0
             plain[idx] = False
             keep = bitmaps is not None or bool(plain.any())
-            base = (n_bytes + 3) // 4 * 4 if keep else 0
+            base = _grib.align4(n_bytes) if keep else 0
             both = DeviceArray((max(base + total, 4),), np.uint8)
             if keep and base:
-                _lib.call("smm_memcpy_d2d", ctypes.c_void_p(both.ptr), ctypes.c_void_p(x.ptr), base, _stream_handle(stream))
+                _lib.call("smm_memcpy_d2d", ctypes.c_void_p(both.ptr), x_ptr, base, _stream_handle(stream))
             dst = DeviceArray((total,), np.uint8, ptr=both.ptr + base, base=both)
-            rows = unpack(x, n_bytes, dst, base, rows, ccsds, idx, stream)
+            rows = _grib.unpack(kind, x, n_bytes, dst, base, rows, recs, idx, stream)
             return self.apply_grib(both, rows, x_bytes=base + total, y=y, masked=masked, remap_area_min=remap_area_min,
                                    flags=flags, stream=stream, bitmaps=bitmaps, skipna=skipna)
-        if isinstance(x, DeviceArray):
-            if x.dtype != np.uint8:
-                raise TypeError(f"apply_grib takes the packed bytes as uint8, got {x.dtype}")
-            x_ptr, n_bytes = ctypes.c_void_p(x.ptr), x.nbytes if x_bytes is None else int(x_bytes)
-            if (n_bytes + 3) // 4 * 4 > x.nbytes:      # the kernel reads whole 32-bit words
-                raise ValueError(f"x must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {x.nbytes}")
-        else:
-            if x_bytes is None:
-                raise TypeError("a raw device pointer needs x_bytes")
-            x_ptr, n_bytes = ctypes.c_void_p(int(x)), int(x_bytes)
         n_batch = rows.size
-        if y is None:
-            y = DeviceArray((n_batch, self.n_dst), np.float64)
-        elif y.shape != (n_batch, self.n_dst) or y.dtype != np.float64:
-            raise ValueError(f"Y must be a float64 ({n_batch}, {self.n_dst}) DeviceArray")
+        y = _grib.float64_result(y, (n_batch, self.n_dst), DeviceArray, "Y")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
-        if skipna:
-            bitmaps, bm_p = (None, None) if bitmaps is None else self._grib_bitmaps(bitmaps, n_batch)
-            _lib.call("smm_apply_grib_na", self.handle, x_ptr, n_bytes, rows_p, bm_p, _ptr(y), _lib.SMM_F64, self.n_dst,
-                      n_batch, float(remap_area_min), fl, _stream_handle(stream))
-            return y
-        if bitmaps is not None:
-            bitmaps, bm_p = self._grib_bitmaps(bitmaps, n_batch)
-            _lib.call("smm_apply_grib_bm", self.handle, x_ptr, n_bytes, rows_p, bm_p, _ptr(y), _lib.SMM_F64, self.n_dst,
-                      n_batch, float(remap_area_min), fl, _stream_handle(stream))
-            return y
-        _lib.call("smm_apply_grib", self.handle, x_ptr, n_bytes, rows_p, _ptr(y), _lib.SMM_F64, self.n_dst, n_batch,
-                  float(remap_area_min), fl, _stream_handle(stream))
+        _grib.call_grib("smm_apply_grib", self.handle, x_ptr, n_bytes, rows_p, bitmaps, n_batch, skipna, _ptr(y), _lib.SMM_F64,
+                        self.n_dst, n_batch, float(remap_area_min), fl, _stream_handle(stream))
         return y
 
-    def _apply_host_grib_out(self, buf, rows, rows_p, out, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna,
-                             grib_out):
-        """`apply_host_grib(grib_out=)`: smm_apply_host_grib_pk."""
-        from .griblite import GRIB_BITMAP_DTYPE, GRIB_ROW_DTYPE, GribField
-        n_batch = rows.size
-        _, total = grib_out.layout(self.n_dst, n_batch)
-        if out is None:
-            out = result_cache.empty((max(total, 1),), np.uint8)
-        if out.dtype != np.uint8 or out.ndim != 1 or out.size < total or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous 1-d uint8 array of at least {total} bytes")
-        bm_p = None
-        if bitmaps is not None:
-            bitmaps, bm_p = self._grib_bitmaps(bitmaps, n_batch)
-        rec = grib_out.records(n_batch)
-        rows_out = np.zeros(n_batch, dtype=GRIB_ROW_DTYPE)
-        bitmaps_out = np.zeros(n_batch, dtype=GRIB_BITMAP_DTYPE)
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
-        _lib.call("smm_apply_host_grib_pk", self.handle, _cptr(buf), buf.size, rows_p, bm_p,
-                  ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribEncodeStruct)), _cptr(out), out.size,
-                  ctypes.cast(rows_out.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)),
-                  ctypes.cast(bitmaps_out.ctypes.data, ctypes.POINTER(_lib.GribBitmapStruct)), n_batch,
-                  float(remap_area_min), fl, int(chunk_rows))
-        return GribField(out, rows_out, (n_batch, self.n_dst), self.n_dst, bitmaps=bitmaps_out)
-
-    def _apply_host_grib_ccsds(self, buf, rows, out, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds,
-                               cpx=None):
-        """`apply_host_grib(ccsds=)` and `apply_host_grib(cpx=)`: a synchronous loop over chunks of consecutive rows (`_grib_host_chunks`), each
-        chunk's Y copied back."""
-        n_batch, D = rows.size, self.n_dst
-        if out is None:
-            out = result_cache.empty((n_batch, D), np.float64)
-        if out.shape != (n_batch, D) or out.dtype != np.float64 or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous float64 ({n_batch}, {D}) array")
-        for r0, r1, y in self._grib_host_chunks(buf, rows, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds,
-                                                cpx=cpx):
+    def _apply_host_grib_coded(self, buf, rows, out, bitmaps, kind, recs, chunk_rows, **apply_kw):
+        """`apply_host_grib(ccsds=)` and `apply_host_grib(cpx=)`: a synchronous loop over chunks of consecutive rows
+        (`_grib.host_chunks`), each chunk's Y copied back."""
+        out = _grib.float64_result(out, (rows.size, self.n_dst), result_cache.empty, "out")
+        for r0, r1, y in _grib.host_chunks(self, buf, rows, bitmaps, kind, recs, chunk_rows, **apply_kw):
             y.to_host(out=out[r0:r1])
         return out
 
-    def _grib_host_chunks(self, buf, rows, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds, extra_cost=0,
-                          cpx=None):
-        """Chunks of consecutive rows, one after the other: the chunk's bytes (coded or simple-packed streams, bitmaps)
-        staged and copied to the device, smm_grib_aec_unpack behind them into the same buffer for the coded rows, the
-        device gather (smm_apply_grib_bm / _na).  Yields (first row, end row, the chunk's float64 Y on the device).  A
-        chunk's staged bytes, transcoded streams, 4 B per sample of scratch, Y and extra_cost (bytes per row, what the
-        caller puts beside them) stay within 256 MiB and a quarter of the free device memory; chunk_rows > 0 fixes the
-        rows.  ccsds: None -- every row is simple-packed.  cpx: the coded rows are complex-packed instead
-        (smm_grib_cpx_unpack): such a row costs its slot of 4 B per value and 8 B per value plus 16 B per group of scratch."""
-        from .griblite import GRIB_AEC_DTYPE, GRIB_NO_BITMAP
-        n_batch, S, D = rows.size, self.n_src, self.n_dst
-        if bitmaps is not None:
-            bitmaps, _ = self._grib_bitmaps(bitmaps, n_batch)
-        ccsds, records, unpack = self._coded_road(ccsds, cpx)
-        ccsds, idx, _ = records(np.zeros(n_batch, dtype=GRIB_AEC_DTYPE) if ccsds is None else ccsds, rows)
-        coded = np.zeros(n_batch, dtype=bool)
-        coded[idx] = True
-        align4 = lambda v: (v + 3) // 4 * 4                                               # noqa: E731
-        has_bm = np.zeros(n_batch, dtype=bool) if bitmaps is None else bitmaps["bitmap_off"] != GRIB_NO_BITMAP
-        n_val = np.full(n_batch, S, dtype=np.int64) if bitmaps is None else \
-            np.where(has_bm, bitmaps["n_values"], S).astype(np.int64)
-        if (ccsds["n_values"][idx].astype(np.int64) != n_val[idx]).any():
-            raise ValueError("a coded row's record has n_values different from the points its row holds")
-        nbits = rows["nbits"].astype(np.int64)
-        in_off = np.where(coded, ccsds["byte_off"], rows["byte_off"]).astype(np.uint64)
-        in_len = np.where(coded, ccsds["byte_len"].astype(np.int64), (n_val * nbits + 7) // 8).astype(np.int64)
-        bm_len = (S + 7) // 8
-        if ((in_off.astype(object) + in_len.astype(object)) > buf.size).any() or \
-                (has_bm.any() and (bitmaps["bitmap_off"][has_bm].astype(object) + bm_len > buf.size).any()):
-            raise ValueError(f"a row's bytes leave the buffer of {buf.size} bytes")
-        device = 12 * n_val + 16 * ccsds["n_groups"].astype(np.int64) + 256 if cpx is not None else \
-            align4((n_val * nbits + 7) // 8) + 4 * n_val
-        cost = align4(in_len) + np.where(coded, device, 0) + D * 8 + \
-            np.where(has_bm, align4(bm_len), 0) + extra_cost
-        free, _ = mem_info()
-        target = min(256 << 20, max(free // 4, 1))
-        fl = int(flags)
-        r0 = 0
-        while r0 < n_batch:
-            r1, used = r0, 0
-            while r1 < n_batch and (r1 - r0 < chunk_rows if chunk_rows > 0 else (r1 == r0 or used + int(cost[r1]) <= target)):
-                used += int(cost[r1])
-                r1 += 1
-            rows_c, aec_c = rows[r0:r1].copy(), ccsds[r0:r1].copy()
-            bm_c = None if bitmaps is None else bitmaps[r0:r1].copy()
-            pieces, at, seen = [], 0, {}
-            for i in range(r0, r1):
-                (aec_c if coded[i] else rows_c)["byte_off"][i - r0] = at
-                pieces.append((at, int(in_off[i]), int(in_len[i])))
-                at += align4(int(in_len[i]))
-                if has_bm[i]:                      # a bitmap several rows share is staged once
-                    off = int(bitmaps["bitmap_off"][i])
-                    if off not in seen:
-                        seen[off] = at
-                        pieces.append((at, off, bm_len))
-                        at += align4(bm_len)
-                    bm_c["bitmap_off"][i - r0] = seen[off]
-            staged = np.zeros(max(at, 4), dtype=np.uint8)
-            for a, off, n in pieces:
-                staged[a:a + n] = buf[off:off + n]
-            _, idx_c, total = records(aec_c, rows_c)
-            both = DeviceArray((max(at + total, 4),), np.uint8)
-            src = DeviceArray((staged.size,), np.uint8, ptr=both.ptr, base=both).copy_from_host(staged)
-            dst = DeviceArray((total,), np.uint8, ptr=both.ptr + at, base=both)
-            if idx_c.size:
-                rows_c = unpack(src, at, dst, at, rows_c, aec_c, idx_c, None)
-            y = self.apply_grib(both, rows_c, x_bytes=at + total, masked=masked, remap_area_min=remap_area_min, flags=fl,
-                                bitmaps=bm_c, skipna=skipna)
-            yield r0, r1, y
-            r0 = r1
-
-    def _apply_host_grib_out_ccsds(self, buf, rows, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, grib_out,
-                                   ccsds):
-        """`apply_host_grib(grib_out=GribEncode(..., ccsds=...))`: the chunks of `_grib_host_chunks`, each chunk's float64
+    def _apply_host_grib_out_ccsds(self, buf, rows, grib_out, bitmaps, kind, recs, chunk_rows, **apply_kw):
+        """`apply_host_grib(grib_out=GribEncode(..., ccsds=...))`: the chunks of `_grib.host_chunks`, each chunk's float64
         Y packed on the device (smm_grib_pack) and its integers coded as CCSDS streams (smm_grib_aec_pack); one D2H copy
         of the chunk's bitmaps (none when no cell is missing: they are all ones) and one of the bytes its streams use.  Y
         and the simple-packed streams never leave the device.  The chunk budget counts the simple-packed slots and the
@@ -592,8 +396,7 @@ class SparseOperator:
         at = n_batch * bm_bytes
         # per row beside Y: its simple-packed slot, the bound of its stream, 8 B per block and 12 B per segment of scratch
         extra = slot + bound + (D // 8 + 1) * 20
-        for r0, r1, y in self._grib_host_chunks(buf, rows, masked, remap_area_min, flags, chunk_rows, bitmaps, skipna, ccsds,
-                                                extra_cost=extra):
+        for r0, r1, y in _grib.host_chunks(self, buf, rows, bitmaps, kind, recs, chunk_rows, extra_cost=extra, **apply_kw):
             enc = grib_out.rows_of(r0, r1, n_batch)
             packed, rows_c, bm_c = grib_pack(y, enc)
             want = enc.ccsds_records(r1 - r0, bm_c["n_values"], rows_c["nbits"])
@@ -636,48 +439,31 @@ class SparseOperator:
         ccsds=, CCSDS-packed itself.
         cpx as for `apply_grib`: the rows' complex-packed streams cross PCIe as they are and are decoded on the device, in
         the same synchronous chunk loop.  It goes neither with ccsds nor with grib_out."""
-        rows, rows_p = self._grib_rows(rows)
+        rows, rows_p = _grib.grib_rows(rows)
         buf = np.ascontiguousarray(buf)
         if buf.dtype != np.uint8 or buf.ndim != 1:
             raise TypeError("apply_host_grib takes the packed bytes as a 1-d uint8 array")
-        if cpx is not None:
-            if ccsds is not None:
-                raise ValueError("cpx does not go with ccsds: a call's coded rows are of one kind")
-            if grib_out is not None:
-                raise ValueError("cpx does not go with grib_out: decode the field on the host first")
-            return self._apply_host_grib_ccsds(buf, rows, out, masked, remap_area_min, flags, int(chunk_rows), bitmaps, skipna,
-                                               None, cpx=cpx)
-        if grib_out is not None and getattr(grib_out, "ccsds", None) is not None:
-            if out is not None:
-                raise ValueError("a CCSDS-coded result comes in a buffer of its own: its size is known only afterwards")
-            return self._apply_host_grib_out_ccsds(buf, rows, masked, remap_area_min, flags, int(chunk_rows), bitmaps, skipna,
-                                                   grib_out, ccsds)
-        if ccsds is not None:
-            if grib_out is not None:
-                raise ValueError("ccsds does not go with grib_out: decode the field on the host first")
-            return self._apply_host_grib_ccsds(buf, rows, out, masked, remap_area_min, flags, int(chunk_rows), bitmaps, skipna,
-                                               ccsds)
-        if grib_out is not None:
-            return self._apply_host_grib_out(buf, rows, rows_p, out, masked, remap_area_min, flags, chunk_rows, bitmaps,
-                                             skipna, grib_out)
+        kind, recs = _grib.one_kind(ccsds, cpx)
+        ccsds_out = grib_out is not None and getattr(grib_out, "ccsds", None) is not None
+        if grib_out is not None and (kind is _grib.CPX or (kind is _grib.CCSDS and not ccsds_out)):
+            raise ValueError(f"{kind.arg} does not go with grib_out: decode the field on the host first")
+        if ccsds_out and out is not None:
+            raise ValueError("a CCSDS-coded result comes in a buffer of its own: its size is known only afterwards")
         n_batch = rows.size
-        if out is None:
-            out = result_cache.empty((n_batch, self.n_dst), np.float64)
-        if out.shape != (n_batch, self.n_dst) or out.dtype != np.float64 or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous float64 ({n_batch}, {self.n_dst}) array")
+        if kind is not None or ccsds_out:      # rows decoded or coded on the device: the chunk loop
+            apply_kw = dict(masked=masked, remap_area_min=remap_area_min, flags=int(flags), skipna=skipna)
+            if ccsds_out:
+                return self._apply_host_grib_out_ccsds(buf, rows, grib_out, bitmaps, kind, recs, int(chunk_rows), **apply_kw)
+            return self._apply_host_grib_coded(buf, rows, out, bitmaps, kind, recs, int(chunk_rows), **apply_kw)
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
-        if skipna:
-            bitmaps, bm_p = (None, None) if bitmaps is None else self._grib_bitmaps(bitmaps, n_batch)
-            _lib.call("smm_apply_host_grib_na", self.handle, _cptr(buf), buf.size, rows_p, bm_p, _cptr(out), _lib.SMM_F64,
-                      self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows))
-            return out
-        if bitmaps is not None:
-            bitmaps, bm_p = self._grib_bitmaps(bitmaps, n_batch)
-            _lib.call("smm_apply_host_grib_bm", self.handle, _cptr(buf), buf.size, rows_p, bm_p, _cptr(out), _lib.SMM_F64,
-                      self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows))
-            return out
-        _lib.call("smm_apply_host_grib", self.handle, _cptr(buf), buf.size, rows_p, _cptr(out), _lib.SMM_F64,
-                  self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows))
+        if grib_out is not None:
+            bitmaps, bm_p = (None, None) if bitmaps is None else _grib.grib_bitmaps(bitmaps, n_batch)
+            return _grib.host_grib_out("smm_apply_host_grib_pk", self.handle, buf, rows_p, bm_p, grib_out, out,
+                                       (n_batch, self.n_dst), n_batch, float(remap_area_min),
+                                       fl | (_lib.APPLY_SKIPNA if skipna else 0), int(chunk_rows))
+        out = _grib.float64_result(out, (n_batch, self.n_dst), result_cache.empty, "out")
+        _grib.call_grib("smm_apply_host_grib", self.handle, _cptr(buf), buf.size, rows_p, bitmaps, n_batch, skipna, _cptr(out),
+                        _lib.SMM_F64, self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows))
         return out
 
     def close(self):
@@ -855,12 +641,12 @@ class OperatorGroup:
         else:
             raise ValueError(f"rows must be flat or (n_outer, n_lev, n_inner), got {shaped.shape}")
         lev, ml = self._level_args(level_index, masked_levels, dims[1])
-        rows, rows_p = self.operators[0]._grib_rows(shaped)
+        rows, rows_p = _grib.grib_rows(shaped)
         bm, bm_p = None, None
         if bitmaps is not None:
             if np.ndim(bitmaps) not in (1, 3) or (np.ndim(bitmaps) == 3 and np.shape(bitmaps) != dims):
                 raise ValueError(f"bitmaps must be flat or {dims}, got {np.shape(bitmaps)}")
-            bm, bm_p = self.operators[0]._grib_bitmaps(bitmaps, rows.size)
+            bm, bm_p = _grib.grib_bitmaps(bitmaps, rows.size)
         return dims, (rows, rows_p), (bm, bm_p), (lev, ml)
 
     def apply_grib(self, x, rows, level_index, masked_levels=None, bitmaps=None, y=None, x_bytes=None, masked=False,
@@ -875,50 +661,17 @@ class OperatorGroup:
         `apply(..., skipna=True, flags=APPLY_KERNEL_SELL)` on that field."""
         (n_outer, n_lev, n_in), (rows, rows_p), (bm, bm_p), (lev, ml) = self._grib_args(rows, bitmaps, level_index,
                                                                                          masked_levels, n_inner)
-        if isinstance(x, DeviceArray):
-            if x.dtype != np.uint8:
-                raise TypeError(f"apply_grib takes the packed bytes as uint8, got {x.dtype}")
-            x_ptr, n_bytes = ctypes.c_void_p(x.ptr), x.nbytes if x_bytes is None else int(x_bytes)
-            if (n_bytes + 3) // 4 * 4 > x.nbytes:      # the kernel reads whole 32-bit words
-                raise ValueError(f"x must cover x_bytes rounded up to 4: {n_bytes} bytes in an array of {x.nbytes}")
-        else:
-            if x_bytes is None:
-                raise TypeError("a raw device pointer needs x_bytes")
-            x_ptr, n_bytes = ctypes.c_void_p(int(x)), int(x_bytes)
+        x_ptr, n_bytes = _grib.packed_bytes(x, x_bytes, "apply_grib", raw=True)
         D = self.n_dst
         if transpose:
             shape, ys = (n_outer, n_in, n_lev, D), (n_in * n_lev * D, D, n_lev * D)     # (outer, lev, inner) strides
         else:
             shape, ys = (n_lev, n_outer, n_in, D), (n_in * D, n_outer * n_in * D, D)
-        if y is None:
-            y = DeviceArray(shape, np.float64)
-        elif y.shape != shape or y.dtype != np.float64:
-            raise ValueError(f"Y must be a float64 {shape} DeviceArray")
+        y = _grib.float64_result(y, shape, DeviceArray, "Y")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
         _lib.call("smm_group_apply_grib_na" if skipna else "smm_group_apply_grib", self.handle, x_ptr, n_bytes, rows_p, bm_p, _ptr(y), _lib.SMM_F64, *ys, n_outer,
                   n_lev, n_in, _cptr(lev), _cptr(ml), float(remap_area_min), fl, _stream_handle(stream))
         return y
-
-    def _apply_host_grib_out(self, buf, rows_p, bm_p, dims, lev, ml, out, masked, remap_area_min, flags, chunk_outer,
-                             skipna, grib_out):
-        """`apply_host_grib(grib_out=)`: smm_group_apply_host_grib_pk."""
-        from .griblite import GRIB_BITMAP_DTYPE, GRIB_ROW_DTYPE, GribField
-        n_rows = dims[0] * dims[1] * dims[2]
-        _, total = grib_out.layout(self.n_dst, n_rows)
-        if out is None:
-            out = result_cache.empty((max(total, 1),), np.uint8)
-        if out.dtype != np.uint8 or out.ndim != 1 or out.size < total or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous 1-d uint8 array of at least {total} bytes")
-        rec = grib_out.records(n_rows)
-        rows_out = np.zeros(n_rows, dtype=GRIB_ROW_DTYPE)
-        bitmaps_out = np.zeros(n_rows, dtype=GRIB_BITMAP_DTYPE)
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
-        _lib.call("smm_group_apply_host_grib_pk", self.handle, _cptr(buf), buf.size, rows_p, bm_p,
-                  ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribEncodeStruct)), _cptr(out), out.size,
-                  ctypes.cast(rows_out.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)),
-                  ctypes.cast(bitmaps_out.ctypes.data, ctypes.POINTER(_lib.GribBitmapStruct)), *dims, _cptr(lev), _cptr(ml),
-                  float(remap_area_min), fl, int(chunk_outer))
-        return GribField(out, rows_out, (*dims, self.n_dst), self.n_dst, bitmaps=bitmaps_out)
 
     def apply_host_grib(self, buf, rows, level_index, masked_levels=None, bitmaps=None, out=None, masked=False,
                         remap_area_min=0.0, transpose=True, flags=0, chunk_outer=0, n_inner=1, skipna=False,
@@ -943,13 +696,12 @@ class OperatorGroup:
             if not transpose:
                 raise ValueError("grib_out returns the rows in record order (n_outer, n_lev, n_inner): "
                                  "transpose=False does not go with it")
-            return self._apply_host_grib_out(buf, rows_p, bm_p, (n_outer, n_lev, n_in), lev, ml, out, masked,
-                                             remap_area_min, flags, chunk_outer, skipna, grib_out)
+            fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+            return _grib.host_grib_out("smm_group_apply_host_grib_pk", self.handle, buf, rows_p, bm_p, grib_out, out,
+                                       (n_outer, n_lev, n_in, self.n_dst), n_outer, n_lev, n_in, _cptr(lev), _cptr(ml),
+                                       float(remap_area_min), fl, int(chunk_outer))
         shape = (n_outer, n_in, n_lev, self.n_dst) if transpose else (n_lev, n_outer, n_in, self.n_dst)
-        if out is None:
-            out = result_cache.empty(shape, np.float64)
-        if out.shape != shape or out.dtype != np.float64 or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous float64 {shape} array")
+        out = _grib.float64_result(out, shape, result_cache.empty, "out")
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
         _lib.call("smm_group_apply_host_grib_na" if skipna else "smm_group_apply_host_grib", self.handle, _cptr(buf), buf.size, rows_p, bm_p, _cptr(out), _lib.SMM_F64,
                   n_outer, n_lev, n_in, int(bool(transpose)), _cptr(lev), _cptr(ml), float(remap_area_min), fl,

@@ -13,7 +13,7 @@ import sys
 import numpy as np
 
 from smmregrid_amd import _lib
-from smmregrid_amd.griblite import GRIB_AEC_DTYPE, aec_decode
+from smmregrid_amd.griblite import GRIB_AEC_DTYPE, GRIB_BITMAP_DTYPE, GRIB_NO_BITMAP, GRIB_ROW_DTYPE, aec_decode
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ccsds")
 PREPROCESS, MSB, THREE_BYTE = _lib.GRIB_AEC_PREPROCESS, _lib.GRIB_AEC_MSB, _lib.GRIB_AEC_3BYTE
@@ -228,3 +228,63 @@ def message_fields(ccsds):
                            bitmap=message_present() if bitmap == "own" else bitmap,
                            ccsds=(fx.stream, fx.flags, fx.block, fx.rsi) if ccsds else None))
     return fields
+
+
+# ------------------------------------------------------------------------------------------------ the rows of one call
+GRID_ROWS = ["grid_w12_smooth", "grid_w16_runs", "grid_w8_near_constant", "grid_w24_noise", "grid_w32_extremes",
+             "grid_w17_sparse", "grid_w1_bits", "grid_w16_rough"]                                   # B = 8, all different
+SHORT_ROWS = ["short_w16_smooth", "short_w12_rough", "short_w24_runs"]                              # 1500 values: bitmapped
+CALLS = {"plain": dict(names=GRID_ROWS),
+         "bitmaps": dict(names=GRID_ROWS[:4] + SHORT_ROWS + GRID_ROWS[4:5], bitmapped={4: 4, 5: 4, 6: 6}),
+         # short_w16_smooth owns the bitmap, the two others share it; grid_w16_runs and short_w12_rough stay simple-packed
+         "mixed": dict(names=GRID_ROWS[:5] + SHORT_ROWS, bitmapped={5: 5, 6: 5, 7: 5}, simple=(1, 6))}
+
+
+def rules(n, seed=1):
+    """R, 2^E, 10^D of n rows: different in every row, with and without the division."""
+    rng = np.random.default_rng(seed)
+    rows = np.zeros(n, dtype=GRIB_ROW_DTYPE)
+    rows["ref"] = np.float32(rng.uniform(-300.0, 300.0, n))
+    rows["bscale"] = np.ldexp(1.0, rng.integers(-12, 3, n))
+    rows["ddiv"] = 10.0 ** rng.integers(0, 3, n)
+    return rows
+
+
+def build(names, bitmapped=(), simple=(), seed=1):
+    """The rows `names` as one CCSDS call and as its simple-packed twin: (buf, rows, ccsds, bitmaps) twice.  Streams lie
+    at odd offsets with garbage between them.  bitmapped: {row: row whose bitmap it shares, or itself}; simple: rows
+    that are simple-packed in the CCSDS call too (block_size 0)."""
+    S = NI * NJ
+    fxs = [fixture(n) for n in names]
+    rows = rules(len(fxs), seed)
+    rows["nbits"] = [f.nbits for f in fxs]
+    twin_rows, aec = rows.copy(), np.zeros(len(fxs), dtype=GRIB_AEC_DTYPE)
+    bms = np.zeros(len(fxs), dtype=GRIB_BITMAP_DTYPE)
+    bms["bitmap_off"], bms["n_values"] = GRIB_NO_BITMAP, S
+    twin_bms = bms.copy()
+    parts, twin_parts = [], []
+
+    def put(store, data):
+        at = sum(p.size for p in store) + 3                       # three bytes of garbage ahead of every piece
+        store.extend([np.full(3, 0xA5, np.uint8), np.asarray(data, np.uint8)])
+        return at
+    present = message_present()
+    for i, f in enumerate(fxs):
+        packed = pack_bits(f.values, f.nbits)
+        twin_rows["byte_off"][i] = put(twin_parts, packed)
+        if i in simple:
+            rows["byte_off"][i] = put(parts, packed)
+        else:
+            rows["byte_off"][i] = off = put(parts, f.stream)
+            aec[i] = (off, f.stream.size, f.n_values, f.nbits, f.block, f.rsi, f.flags, 0)
+    for i, owner in dict(bitmapped).items():
+        assert fxs[i].n_values == 1500
+        if owner == i:
+            bits = np.packbits(present)
+            bms["bitmap_off"][i], twin_bms["bitmap_off"][i] = put(parts, bits), put(twin_parts, bits)
+        else:
+            bms["bitmap_off"][i], twin_bms["bitmap_off"][i] = bms["bitmap_off"][owner], twin_bms["bitmap_off"][owner]
+        bms["n_values"][i] = twin_bms["n_values"][i] = 1500
+    use_bm = bool(bitmapped)
+    return ((np.concatenate(parts), rows, aec, bms if use_bm else None),
+            (np.concatenate(twin_parts), twin_rows, None, twin_bms if use_bm else None))

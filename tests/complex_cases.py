@@ -367,3 +367,61 @@ def message_fields(coded, all_coded=False):
 
 def hand_message():
     return grib2_message([dict(cpx=(np.frombuffer(HAND_STREAM, np.uint8), HAND_PARAMS, 12))], 4, 3)
+
+
+# ------------------------------------------------------------------------------------------------ the rows of one call
+CALLS = {"plain": dict(names=GRID_ROWS),
+         # short1500_order2 owns a bitmap that short1500_order1 shares, short1500_order0 has its own
+         "bitmaps": dict(names=GRID_ROWS[:4] + SHORT_ROWS + GRID_ROWS[4:5], bitmapped={4: 4, 5: 4, 6: 6}),
+         # order1_noct2 and short1500_order1 stay simple-packed among the complex-packed rows
+         "mixed": dict(names=GRID_ROWS[:5] + SHORT_ROWS, bitmapped={5: 5, 6: 5, 7: 5}, simple=(1, 6))}
+
+
+def simple_record():
+    from smmregrid_amd import GRIB_CPX_DTYPE, _lib
+    r = np.zeros(1, dtype=GRIB_CPX_DTYPE)
+    r["order"] = _lib.GRIB_CPX_SIMPLE
+    return r[0]
+
+
+def build(names, bitmapped=(), simple=(), seed=1):
+    """The rows `names` as one complex-packed call and as its simple-packed twin: (buf, rows, cpx, bitmaps) twice.
+    Streams lie at odd offsets with garbage between them.  bitmapped: {row: row whose bitmap it shares, or itself};
+    simple: rows that are simple-packed in the complex-packed call too."""
+    from smmregrid_amd import GRIB_BITMAP_DTYPE, GRIB_CPX_DTYPE, GRIB_NO_BITMAP
+    from tests.ccsds_cases import rules
+    cs = [case(n) for n in names]
+    rows = rules(len(cs), seed)
+    twin_rows = rows.copy()
+    twin_rows["nbits"] = [c.width for c in cs]
+    rows["nbits"] = [c.width if i in simple else c.params["nbits"] for i, c in enumerate(cs)]
+    cpx = np.zeros(len(cs), dtype=GRIB_CPX_DTYPE)
+    bms = np.zeros(len(cs), dtype=GRIB_BITMAP_DTYPE)
+    bms["bitmap_off"], bms["n_values"] = GRIB_NO_BITMAP, S
+    twin_bms = bms.copy()
+    parts, twin_parts = [], []
+
+    def put(store, data):
+        at = sum(p.size for p in store) + 3                       # three bytes of garbage ahead of every piece
+        store.extend([np.full(3, 0xA5, np.uint8), np.asarray(data, np.uint8)])
+        return at
+    for i, c in enumerate(cs):
+        packed = pack_bits(c.X, c.width)
+        twin_rows["byte_off"][i] = put(twin_parts, packed)
+        if i in simple:
+            rows["byte_off"][i] = put(parts, packed)
+            cpx[i] = simple_record()
+        else:
+            rows["byte_off"][i] = off = put(parts, c.stream)
+            cpx[i] = c.record(off)
+    for i, owner in dict(bitmapped).items():
+        assert cs[i].n_values == 1500
+        if owner == i:
+            bits = np.packbits(present_1500())
+            bms["bitmap_off"][i], twin_bms["bitmap_off"][i] = put(parts, bits), put(twin_parts, bits)
+        else:
+            bms["bitmap_off"][i], twin_bms["bitmap_off"][i] = bms["bitmap_off"][owner], twin_bms["bitmap_off"][owner]
+        bms["n_values"][i] = twin_bms["n_values"][i] = 1500
+    use_bm = bool(bitmapped)
+    return ((np.concatenate(parts), rows, cpx, bms if use_bm else None),
+            (np.concatenate(twin_parts), twin_rows, None, twin_bms if use_bm else None))

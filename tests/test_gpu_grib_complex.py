@@ -6,10 +6,10 @@ tests/test_grib_complex.py and its host harness; the one error status provoked h
 import numpy as np
 import pytest
 
-from smmregrid_amd import (GRIB_BITMAP_DTYPE, GRIB_CPX_DTYPE, GRIB_NO_BITMAP, GRIB_ROW_DTYPE, CdoGenerate, GribField, Regridder,
-                           SparseOperator, _lib, grib_unpack_cpx, to_device)
+from smmregrid_amd import GRIB_CPX_DTYPE, CdoGenerate, GribField, Regridder, SparseOperator, _lib, grib_unpack_cpx, to_device
 from smmregrid_amd.io import open_dataset
 from smmregrid_amd.lazy import LazyArray
+from tests import ccsds_cases as cc
 from tests import complex_cases as xc
 from tests.ccsds_cases import pack_bits
 
@@ -24,20 +24,7 @@ def same_bits(got, want, what=""):
     assert not diff.any(), f"{what}: {int(diff.sum())} results differ in their bits, first at {np.argwhere(diff)[:3].tolist()}"
 
 
-def rules(n, seed=1):
-    """R, 2^E, 10^D of n rows: different in every row, with and without the division."""
-    rng = np.random.default_rng(seed)
-    rows = np.zeros(n, dtype=GRIB_ROW_DTYPE)
-    rows["ref"] = np.float32(rng.uniform(-300.0, 300.0, n))
-    rows["bscale"] = np.ldexp(1.0, rng.integers(-12, 3, n))
-    rows["ddiv"] = 10.0 ** rng.integers(0, 3, n)
-    return rows
-
-
-def simple_record():
-    r = np.zeros(1, dtype=GRIB_CPX_DTYPE)
-    r["order"] = _lib.GRIB_CPX_SIMPLE
-    return r[0]
+rules, simple_record, build = cc.rules, xc.simple_record, xc.build      # shared with tests/test_grib_chunk_plan.py
 
 
 def device_bytes(buf):
@@ -143,47 +130,6 @@ def test_an_integer_outside_32_bits_is_the_rows_error(hip):
 
 
 # ------------------------------------------------------------------------------------------------ the gather behind it
-def build(names, bitmapped=(), simple=(), seed=1):
-    """The rows `names` as one complex-packed call and as its simple-packed twin: (buf, rows, cpx, bitmaps) twice.
-    Streams lie at odd offsets with garbage between them.  bitmapped: {row: row whose bitmap it shares, or itself};
-    simple: rows that are simple-packed in the complex-packed call too."""
-    cs = [xc.case(n) for n in names]
-    rows = rules(len(cs), seed)
-    twin_rows = rows.copy()
-    twin_rows["nbits"] = [c.width for c in cs]
-    rows["nbits"] = [c.width if i in simple else c.params["nbits"] for i, c in enumerate(cs)]
-    cpx = np.zeros(len(cs), dtype=GRIB_CPX_DTYPE)
-    bms = np.zeros(len(cs), dtype=GRIB_BITMAP_DTYPE)
-    bms["bitmap_off"], bms["n_values"] = GRIB_NO_BITMAP, S
-    twin_bms = bms.copy()
-    parts, twin_parts = [], []
-
-    def put(store, data):
-        at = sum(p.size for p in store) + 3                       # three bytes of garbage ahead of every piece
-        store.extend([np.full(3, 0xA5, np.uint8), np.asarray(data, np.uint8)])
-        return at
-    for i, c in enumerate(cs):
-        packed = pack_bits(c.X, c.width)
-        twin_rows["byte_off"][i] = put(twin_parts, packed)
-        if i in simple:
-            rows["byte_off"][i] = put(parts, packed)
-            cpx[i] = simple_record()
-        else:
-            rows["byte_off"][i] = off = put(parts, c.stream)
-            cpx[i] = c.record(off)
-    for i, owner in dict(bitmapped).items():
-        assert cs[i].n_values == 1500
-        if owner == i:
-            bits = np.packbits(xc.present_1500())
-            bms["bitmap_off"][i], twin_bms["bitmap_off"][i] = put(parts, bits), put(twin_parts, bits)
-        else:
-            bms["bitmap_off"][i], twin_bms["bitmap_off"][i] = bms["bitmap_off"][owner], twin_bms["bitmap_off"][owner]
-        bms["n_values"][i] = twin_bms["n_values"][i] = 1500
-    use_bm = bool(bitmapped)
-    return ((np.concatenate(parts), rows, cpx, bms if use_bm else None),
-            (np.concatenate(twin_parts), twin_rows, None, twin_bms if use_bm else None))
-
-
 _OP = []
 
 
@@ -203,11 +149,7 @@ def operator():
     return _OP[0]
 
 
-CASES = {"plain": dict(names=xc.GRID_ROWS),
-         # short1500_order2 owns a bitmap that short1500_order1 shares, short1500_order0 has its own
-         "bitmaps": dict(names=xc.GRID_ROWS[:4] + xc.SHORT_ROWS + xc.GRID_ROWS[4:5], bitmapped={4: 4, 5: 4, 6: 6}),
-         # order1_noct2 and short1500_order1 stay simple-packed among the complex-packed rows
-         "mixed": dict(names=xc.GRID_ROWS[:5] + xc.SHORT_ROWS, bitmapped={5: 5, 6: 5, 7: 5}, simple=(1, 6))}
+CASES = xc.CALLS
 
 
 @pytest.mark.parametrize("skipna", [False, True])
