@@ -755,6 +755,50 @@ int smm_grib_cpx_unpack(int device, const void* x, int64_t x_bytes, const smm_gr
 int smm_grib_cpx_decode_host(const void* x_host, int64_t x_bytes, const smm_grib_cpx_t* rec, uint32_t* values, int* status);
 
 /*
+ * The way back: simple-packed streams on the device coded as complex-packed streams (templates 5.2 / 5.3), behind the
+ * four passes of smm_grib_pack or on any rows an smm_grib_row_t table describes.  THE RULE OF THIS ENCODER is the text of
+ * smmregrid_amd/csrc/smm_grib_cpx.hpp: spatial differencing of the wanted order unless a descriptor or a difference would
+ * not fit (then order 0), groups of one fixed length, every table at its minimal width.  It is fully deterministic -- the
+ * host entry and the kernels give the same bytes -- and it is the project's own choice of groups, not g2c's: a valid
+ * stream that smm_grib_cpx_decode_host and smm_grib_cpx_unpack decode.  recs are the parameters WANTED per row: n_values
+ * and nbits (the width of the row's integers, 0..32) as the row has them, order (0, 1 or 2) and length_ref = the group
+ * length L (8, 16, 32 or 64) to code with; reserved must be 0, nothing else is read.
+ *   smm_grib_cpx_pack_bound   host only: the worst case per row, rounded up to 4 -- with m = min(32, nbits + order) and
+ *                             NG = ceil(n_values / L): (order + 1) * 4 octets of descriptors (none at order 0), NG
+ *                             references of m bits, NG widths of 6 bits, n_values values of m bits, each part rounded up
+ *                             to an octet (derived next to pack_bound_bytes in smm_grib_cpx.hpp); a row of no values or
+ *                             of width 0 needs none.  byte_off[b] (may be NULL) = the sum before row b, *total_bytes = the
+ *                             sum.
+ *   smm_grib_cpx_pack         x: device bytes, 4-byte aligned, the allocation covering x_bytes rounded up to 4;
+ *                             rows_in[b].byte_off: where row b's n_values integers of nbits bits begin in x; rows_in,
+ *                             recs and recs_out: HOST arrays of n_batch records; out: device, 4-byte aligned,
+ *                             out_bytes >= the bound.  recs_out[b] is the full record of the stream written (the
+ *                             effective order, n_oct, NG, the three table widths, the group lengths, byte_off and
+ *                             byte_len in out): rows lie back to back in row order, each at a 4-byte-aligned offset, and
+ *                             every byte from a row's start to the aligned end of its stream is written;
+ *                             *used_bytes = the aligned end of the last row, bytes of out beyond it are unspecified.
+ *                             A row with nbits == 0 is not coded: its record is marked SMM_GRIB_CPX_SIMPLE with byte_len
+ *                             0.  Seven kernels (differences and their extremes per row, the order per row, references
+ *                             and widths per group, offsets per row, over the rows, shared words zeroed, emit through
+ *                             LDS); nothing returns to the host between them.  Scratch (8 B per group, 12 B per 1024
+ *                             values) is allocated and freed inside the call; the stream is synchronised before it
+ *                             returns.
+ *   smm_grib_cpx_encode_host  one row coded on the host, no device: values[n_values] (n_values == rec->n_values, each
+ *                             within nbits bits) into out[0, out_cap), *byte_len its bytes, *rec_out its record with
+ *                             byte_off 0.  out needs no alignment; out_cap must reach the bound.
+ * SMM_ERR_INVALID, before any device is touched: null pointers, negative counts, order outside 0..2, length_ref outside
+ * {8, 16, 32, 64}, nbits outside 0..32 or different from rows_in[b].nbits, n_values >= 2^31, reserved != 0, a row's
+ * integers leaving [0, x_bytes), out_bytes / out_cap below the bound, a misaligned x or out, a value wider than nbits
+ * (host entry).
+ */
+int smm_grib_cpx_pack_bound(const smm_grib_cpx_t* recs, int64_t n_batch, uint64_t* byte_off, uint64_t* total_bytes);
+int smm_grib_cpx_pack(int device, const void* x, int64_t x_bytes, const smm_grib_row_t* rows_in /* host */,
+                      const smm_grib_cpx_t* recs /* host */, int64_t n_batch, void* out, int64_t out_bytes,
+                      smm_grib_cpx_t* recs_out /* host */, uint64_t* used_bytes, void* stream);
+int smm_grib_cpx_encode_host(const uint32_t* values, int64_t n_values, const smm_grib_cpx_t* rec, void* out,
+                             int64_t out_cap, uint64_t* byte_len, smm_grib_cpx_t* rec_out);
+
+/*
  * Masked-level apply (regrid.py:387-418 in one launch).  The kept dims of the
  * field are viewed as (n_outer, n_lev, n_inner) around the mask dimension;
  * data level l uses group member level_index[l] (host int32[n_lev], result of

@@ -1,5 +1,5 @@
 """What the GRIB calls of `SparseOperator` / `OperatorGroup` and the device wrappers `grib_unpack` / `grib_unpack_cpx` /
-`grib_aec_pack` share: the description of a kind of coded row (`CCSDS`, `CPX`), the check of the packed bytes, the
+`grib_aec_pack` / `grib_cpx_pack` share: the description of a kind of coded row (`CCSDS`, `CPX`), the check of the packed bytes, the
 entry dispatch, the result checks, and the chunk loop of the host calls whose rows are decoded or coded on the device --
 its plan (`plan_chunks`, host only) apart from its execution (`host_chunks`)."""
 import ctypes
@@ -37,6 +37,27 @@ CCSDS = Coded("ccsds", "CCSDS records", GRIB_AEC_DTYPE, _lib.GribAecStruct, "smm
 CPX = Coded("cpx", "complex-packing records", GRIB_CPX_DTYPE, _lib.GribCpxStruct, "smm_grib_cpx_layout",
             "smm_grib_cpx_unpack", lambda recs, rows: recs["order"] != GRIB_CPX_SIMPLE,
             lambda recs, n_val, nbits: 12 * n_val + 16 * recs["n_groups"].astype(np.int64) + 256)
+
+
+# What differs between the kinds of coded results (`apply_host_grib(grib_out=GribEncode(..., ccsds= / cpx=))`).  attr: the
+# attribute of `GribEncode` and `GribField` that carries the parameters / the records; records, bounds: the `GribEncode`
+# methods that give the wanted records of a chunk and the streams' bounds; pack: the device step behind `grib_pack`;
+# scratch(n_dst): the device bytes a row costs beside its streams' bound; takes: the kinds of coded INPUT it goes with.
+CodedOut = namedtuple("CodedOut", "attr words dtype records bounds pack scratch takes")
+# 8 B per block and 12 B per segment of scratch
+CCSDS_OUT = CodedOut("ccsds", "CCSDS-coded", GRIB_AEC_DTYPE, "ccsds_records", "ccsds_bounds", "grib_aec_pack",
+                     lambda n_dst: (n_dst // 8 + 1) * 20, (None, CCSDS))
+# 8 B per group of at least 8 values and 12 B per 1024 values of scratch
+CPX_OUT = CodedOut("cpx", "complex-packed", GRIB_CPX_DTYPE, "cpx_records", "cpx_bounds", "grib_cpx_pack",
+                   lambda n_dst: n_dst + 8 + (n_dst // 1024 + 1) * 12, (None, CPX))
+
+
+def out_kind(grib_out):
+    """The kind of coded result a `GribEncode` asks for, or None: simple-packed (or no grib_out at all)."""
+    if grib_out is None:
+        return None
+    return CPX_OUT if getattr(grib_out, "cpx", None) is not None else \
+        CCSDS_OUT if getattr(grib_out, "ccsds", None) is not None else None
 
 
 def one_kind(ccsds, cpx):
@@ -235,7 +256,8 @@ def plan_chunks(buf_size, rows, bitmaps, kind, recs, n_src, n_dst, chunk_rows, t
 def host_chunks(op, buf, rows, bitmaps, kind, recs, chunk_rows, extra_cost=0, **apply_kw):
     """The chunks of `plan_chunks`, one after the other: the chunk's bytes staged and copied to the device, its coded rows
     unpacked behind them into the same buffer (kind.unpack_entry), the device gather (`op.apply_grib` with apply_kw).
-    Yields (first row, end row, the chunk's float64 Y on the device).  A chunk stays within 256 MiB and a quarter of the
+    Yields (first row, end row, the chunk's float64 Y on the device, the chunk's row records as the gather took them:
+    a complex-packed row with the width its integers were stored at).  A chunk stays within 256 MiB and a quarter of the
     free device memory."""
     if bitmaps is not None:
         bitmaps, _ = grib_bitmaps(bitmaps, rows.size)
@@ -254,4 +276,4 @@ def host_chunks(op, buf, rows, bitmaps, kind, recs, chunk_rows, extra_cost=0, **
         if c.coded_idx.size:
             dst = DeviceArray((c.coded_bytes,), np.uint8, ptr=both.ptr + at, base=both)
             rows_c = unpack(kind, src, at, dst, at, rows_c, c.recs, c.coded_idx, None)
-        yield c.r0, c.r1, op.apply_grib(both, rows_c, x_bytes=at + c.coded_bytes, bitmaps=c.bitmaps, **apply_kw)
+        yield c.r0, c.r1, op.apply_grib(both, rows_c, x_bytes=at + c.coded_bytes, bitmaps=c.bitmaps, **apply_kw), rows_c

@@ -212,6 +212,9 @@ SIGNATURES = {
     "smm_grib_cpx_layout": [_gcp, _i64, _u64p, _u64p],
     "smm_grib_cpx_unpack": [_int, _p, _i64, _gcp, _grp, _i64, _p, _i64, _grp, _p],
     "smm_grib_cpx_decode_host": [_p, _i64, _gcp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_int)],
+    "smm_grib_cpx_pack_bound": [_gcp, _i64, _u64p, _u64p],
+    "smm_grib_cpx_pack": [_int, _p, _i64, _grp, _gcp, _i64, _p, _i64, _gcp, _u64p, _p],
+    "smm_grib_cpx_encode_host": [ctypes.POINTER(ctypes.c_uint32), _i64, _gcp, _p, _i64, _u64p, _gcp],
     "smm_grib_aec_pack_bound": [_gap, _i64, _u64p, _u64p],
     "smm_grib_aec_pack": [_int, _p, _i64, _grp, _gap, _i64, _p, _i64, _gap, _u64p, _p],
     "smm_grib_aec_encode_host": [ctypes.POINTER(ctypes.c_uint32), _i64, _gap, _p, _i64, _u64p, _u64p],

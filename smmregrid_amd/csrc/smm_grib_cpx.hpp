@@ -1,8 +1,10 @@
 // GRIB-2 complex packing (data representation template 5.2) and complex packing with spatial differencing (5.3), what
-// NCEP's g2c / wgrib2 write for GFS, GEFS, HRRR: the decoder, stated once.  Plain C++ that compiles for host and device
-// -- the host decode (smm_grib_cpx_decode_host), the kernels of smm_grib_cpx_unpack (smm_grib_cpx.hip) and
-// tests/cpp/grib_cpx_harness.cpp all read the stream through Stream::peek (smm_grib_aec.hpp's load_word / bits_of) and
-// take the tables apart with the small functions below.
+// NCEP's g2c / wgrib2 write for GFS, GEFS, HRRR: the decoder and the encoder, each stated once.  Plain C++ that compiles
+// for host and device -- the host decode (smm_grib_cpx_decode_host), the kernels of smm_grib_cpx_unpack
+// (smm_grib_cpx.hip) and tests/cpp/grib_cpx_harness.cpp all read the stream through Stream::peek (smm_grib_aec.hpp's
+// load_word / bits_of) and take the tables apart with the small functions below; the host encode
+// (smm_grib_cpx_encode_host), the kernels of smm_grib_cpx_pack (smm_grib_cpx_pack.hip) and
+// tests/cpp/grib_cpx_encode_harness.cpp share decide / z_of / coded_row / pack_bound_bytes behind decode_row.
 //
 // THE FORMAT.  Octets are WMO's (FM 92 GRIB edition 2), as recalled: no file written by g2c, wgrib2 or ecCodes was at
 // hand to pin them.
@@ -38,6 +40,28 @@
 // and its integers are then zero.  TWO RULES bound every loop and every read: (1) every loop runs over NG or n_values of
 // the record; (2) no load goes past the 32-bit word that holds the stream's last byte (load_word clamps; a stream of no
 // bytes is never loaded from).  A malformed stream costs wrong numbers and a status, never a read outside the buffer.
+//
+// THE RULE OF THIS ENCODER (smm_grib_cpx_encode_host: encode_row below; smm_grib_cpx_pack: the kernels of
+// smm_grib_cpx_pack.hip; tests/cpp/grib_cpx_encode_harness.cpp).  A row brings n integers X of nbits_in bits -- a
+// simple-packed stream --, a wanted order o of 0, 1 or 2 and a group length L of 8, 16, 32 or 64.
+//   1. effective order   o falls to 0 when n <= o; when |h_1|, |h_2| or |g| exceeds 2^31 - 1 (a descriptor is
+//      sign-magnitude in at most 4 octets); when some z >= 2^32.  There is no cascade from 2 to 1.  A row with
+//      nbits_in <= 29 never falls back: with X < 2^29, h < 2^29, |d| <= 2 (2^29 - 1) < 2^30 at order 2 (less at order
+//      1), so |g| < 2^30, and z = d - g <= max d - min d <= 4 (2^29 - 1) < 2^31
+//   2. differences       order 1: d_i = X_i - X_(i-1); order 2: d_i = X_i - 2 X_(i-1) + X_(i-2); g = min d_i over i >= o;
+//      z_i = d_i - g for i >= o and 0 for the o placeholders; h_1 = X_0, h_2 = X_1.  Order 0: z = X, no descriptors
+//      (n_oct = 0).  n_oct is the smallest of 1..4 that holds h_1 .. h_o and g
+//   3. groups            all of length L but the last: NG = ceil(n / L), length_inc = 1, length_bits = 0,
+//      length_last = n - (NG - 1) L, length_ref = L when NG > 1, else n.  ref_g = min z of the group,
+//      w_g = the bit length of (max z - ref_g)
+//   4. table widths      each the smallest that holds its table: nbits = bit length of max ref_g, width_ref = min w_g,
+//      width_bits = bit length of (max w_g - width_ref)
+//   5. the stream        descriptors | NG references | NG widths | an empty lengths table | the groups' bits, each part
+//      padded to an octet with zero bits
+//   6. special rows      n = 0: NG = 0 and no bytes.  nbits_in = 0: the row is not coded, it passes through marked
+//      SMM_GRIB_CPX_SIMPLE with byte length 0
+// The rule is deterministic -- host and kernels give the same bytes -- and it is the project's own choice of groups, not
+// g2c's: a valid 5.2 / 5.3 stream that decode_row above inverts.  Its bound is derived at pack_bound_bytes.
 #pragma once
 
 #include <cstdint>
@@ -190,6 +214,154 @@ SMM_GRIB_HD int decode_row(const void* x, const Row& r, uint32_t* out) {
   if (status != kOk)
     for (uint32_t i = 0; i < n; ++i) out[i] = 0;
   return status;
+}
+
+// ---- the encoder's small functions: what encode_row below and the kernels of smm_grib_cpx_pack.hip share
+// what is wanted of a row: n integers of nbits_in bits, coded at `order` in groups of L values
+struct Want {
+  uint32_t n_values;
+  int32_t nbits_in, order;
+  uint32_t L;
+};
+// rule 1 and the descriptors' size: the effective order (0: g and n_oct are 0)
+struct Decision {
+  int64_t g;
+  int32_t order, n_oct;
+};
+SMM_GRIB_HD int bit_length(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
+// the smallest n_oct of 1..4 whose sign-magnitude form holds a magnitude <= 2^31 - 1
+SMM_GRIB_HD int octets_of(uint64_t mag) { return mag < (1u << 7) ? 1 : mag < (1u << 15) ? 2 : mag < (1u << 23) ? 3 : 4; }
+// x0, x1: the row's first two integers (x1 is read at order 2 only); dmin, dmax: the extremes of d_i over i >= order
+SMM_GRIB_HD Decision decide(uint32_t n, int order, uint64_t x0, uint64_t x1, int64_t dmin, int64_t dmax) {
+  const Decision none{0, 0, 0};
+  if (order <= 0 || n <= (uint32_t)order) return none;
+  uint64_t top = dmin < 0 ? (uint64_t)0 - (uint64_t)dmin : (uint64_t)dmin;
+  if (x0 > top) top = x0;
+  if (order > 1 && x1 > top) top = x1;
+  if (top > 0x7fffffffull || (uint64_t)(dmax - dmin) > 0xffffffffull) return none;
+  return Decision{dmin, order, octets_of(top)};
+}
+// d_i (i >= order >= 1) of the integers q(0..n)
+template <class Q>
+SMM_GRIB_HD int64_t difference(Q&& q, uint32_t i, int order) {
+  const int64_t a = (int64_t)q(i) - (int64_t)q(i - 1);
+  return order == 1 ? a : a - ((int64_t)q(i - 1) - (int64_t)q(i - 2));
+}
+// z_i under a decision: in [0, 2^32)
+template <class Q>
+SMM_GRIB_HD uint32_t z_of(Q&& q, uint32_t i, const Decision& dec) {
+  if (dec.order <= 0) return q(i);
+  return i < (uint32_t)dec.order ? 0u : (uint32_t)(difference(q, i, dec.order) - dec.g);
+}
+SMM_GRIB_HD uint32_t sign_magnitude_of(int64_t v, int n_oct) {
+  return v < 0 ? (1u << (8 * n_oct - 1)) | (uint32_t)(-v) : (uint32_t)v;
+}
+SMM_GRIB_HD uint32_t groups_of(uint32_t n, uint32_t L) { return (uint32_t)(((uint64_t)n + L - 1) / L); }
+// rules 3 and 4 as a record: the stream of n values in groups of L with the three table widths from the extremes of the
+// groups' references and widths; byte_off is 0, byte_len the stream's bytes for data_bits bits of group values
+SMM_GRIB_HD Row coded_row(uint32_t n, uint32_t L, const Decision& dec, uint32_t ref_max, uint32_t w_min, uint32_t w_max,
+                          uint64_t data_bits) {
+  Row r{};
+  r.n_values = n;
+  r.n_groups = groups_of(n, L);
+  if (n == 0) return r;
+  r.nbits = bit_length(ref_max);
+  r.width_ref = w_min;
+  r.width_bits = bit_length(w_max - w_min);
+  r.length_ref = r.n_groups > 1 ? L : n;
+  r.length_inc = 1;
+  r.length_last = n - (r.n_groups - 1) * L;
+  r.order = dec.order;
+  r.n_oct = dec.n_oct;
+  const Sections sec = sections(r);
+  r.byte_len = (sec.data_bit + data_bits + 7) / 8;
+  return r;
+}
+SMM_GRIB_HD smm_grib_cpx_t record_of(const Row& r) {
+  smm_grib_cpx_t c{};
+  c.byte_off = r.byte_off, c.byte_len = r.byte_len, c.n_values = r.n_values, c.n_groups = r.n_groups, c.nbits = r.nbits;
+  c.width_ref = r.width_ref, c.width_bits = r.width_bits, c.length_ref = r.length_ref, c.length_inc = r.length_inc;
+  c.length_last = r.length_last, c.length_bits = r.length_bits, c.order = r.order, c.n_oct = r.n_oct;
+  return c;
+}
+// the record of a row that is not coded (nbits_in == 0): marked simple-packed, no bytes
+SMM_GRIB_HD smm_grib_cpx_t simple_record(uint64_t n_values, uint64_t byte_off) {
+  smm_grib_cpx_t c{};
+  c.byte_off = byte_off, c.n_values = n_values, c.order = SMM_GRIB_CPX_SIMPLE;
+  return c;
+}
+// THE BOUND of a row's stream, rounded up to 4 bytes.  With o the wanted order and w = nbits_in: z = X < 2^w at order 0,
+// z = d - g <= max d - min d <= 2 (2^w - 1) at order 1 and <= 4 (2^w - 1) at order 2, and z < 2^32 by rule 1, so every z --
+// hence every group reference and every group's max z - ref -- fits in m = min(32, w + o) bits; a fall to order 0 only
+// lowers that to w.  A group width is at most 32, so a stored width (w_g - width_ref <= 32) needs at most 6 bits.
+//   descriptors (o + 1) * 4 octets at most (none at order 0) | NG references of <= m bits | NG widths of <= 6 bits |
+//   no lengths | n values of <= m bits; each part rounded up to an octet.  A row of no values or of width 0 has no bytes.
+SMM_GRIB_HD uint64_t pack_bound_bytes(uint64_t n, int nbits_in, int order, uint32_t L) {
+  if (n == 0 || nbits_in == 0) return 0;
+  const uint64_t m = nbits_in + order < 32 ? (uint64_t)(nbits_in + order) : 32, ng = (n + L - 1) / L;
+  const uint64_t head = order > 0 ? (uint64_t)(order + 1) * 4 : 0;
+  return smm_grib::align4(head + (ng * m + 7) / 8 + (ng * 6 + 7) / 8 + (n * m + 7) / 8);
+}
+
+// n (0..32) bits of v at bit position p of the zeroed bytes out[0, cap); false: they would pass cap
+inline bool put_bits(uint8_t* out, uint64_t cap, uint64_t p, uint32_t v, int n) {
+  if (n <= 0) return true;
+  if ((p + (uint64_t)n + 7) / 8 > cap) return false;
+  for (int b = n - 1; b >= 0; --b, ++p)
+    if ((v >> b) & 1u) out[p >> 3] |= (uint8_t)(0x80u >> (p & 7));
+  return true;
+}
+// ---- the scalar encode: the integers q(0..n) into the zeroed out[0, cap) by THE RULE OF THIS ENCODER; *rec is the
+// record of the stream written (byte_off 0).  Returns its bytes, or UINT64_MAX when they would pass cap.  The row has
+// nbits_in >= 1.  Host only: the groups' references and widths are kept in two heap arrays between the passes.
+template <class Q>
+uint64_t encode_row(Q&& q, const Want& want, uint8_t* out, uint64_t cap, Row* rec) {
+  const uint32_t n = want.n_values, L = want.L, ng = groups_of(n, L);
+  int64_t dmin = INT64_MAX, dmax = INT64_MIN;
+  const int o = n > (uint32_t)want.order ? want.order : 0;
+  for (uint32_t i = (uint32_t)o; o > 0 && i < n; ++i) {
+    const int64_t d = difference(q, i, o);
+    dmin = d < dmin ? d : dmin;
+    dmax = d > dmax ? d : dmax;
+  }
+  const Decision dec = o > 0 ? decide(n, o, q(0), o > 1 ? q(1) : 0, dmin, dmax) : Decision{0, 0, 0};
+  uint32_t* refs = new uint32_t[2 * (size_t)ng + 1];
+  uint32_t* ws = refs + ng;
+  uint32_t ref_max = 0, w_min = 64, w_max = 0;
+  uint64_t data_bits = 0;
+  for (uint32_t g = 0; g < ng; ++g) {
+    const uint32_t i0 = g * L, i1 = n - i0 < L ? n : i0 + L;
+    uint32_t lo = 0xffffffffu, hi = 0;
+    for (uint32_t i = i0; i < i1; ++i) {
+      const uint32_t z = z_of(q, i, dec);
+      lo = z < lo ? z : lo;
+      hi = z > hi ? z : hi;
+    }
+    refs[g] = lo;
+    ws[g] = (uint32_t)bit_length(hi - lo);
+    ref_max = lo > ref_max ? lo : ref_max;
+    w_min = ws[g] < w_min ? ws[g] : w_min;
+    w_max = ws[g] > w_max ? ws[g] : w_max;
+    data_bits += (uint64_t)ws[g] * (i1 - i0);
+  }
+  *rec = coded_row(n, L, dec, ref_max, w_min, w_max, data_bits);
+  const Sections sec = sections(*rec);
+  bool ok = rec->byte_len <= cap;
+  if (ok && dec.order > 0) {
+    const int nb = 8 * dec.n_oct;
+    ok = put_bits(out, cap, 0, sign_magnitude_of((int64_t)q(0), dec.n_oct), nb);
+    if (dec.order > 1) ok = ok && put_bits(out, cap, (uint64_t)nb, sign_magnitude_of((int64_t)q(1), dec.n_oct), nb);
+    ok = ok && put_bits(out, cap, (uint64_t)dec.order * nb, sign_magnitude_of(dec.g, dec.n_oct), nb);
+  }
+  uint64_t pos = sec.data_bit;
+  for (uint32_t g = 0; ok && g < ng; ++g) {
+    ok = put_bits(out, cap, sec.refs_bit + (uint64_t)g * (uint64_t)rec->nbits, refs[g], rec->nbits) &&
+         put_bits(out, cap, sec.widths_bit + (uint64_t)g * (uint64_t)rec->width_bits, ws[g] - rec->width_ref, rec->width_bits);
+    const uint32_t i0 = g * L, i1 = n - i0 < L ? n : i0 + L;
+    for (uint32_t i = i0; ok && i < i1; ++i, pos += ws[g]) ok = put_bits(out, cap, pos, z_of(q, i, dec) - refs[g], (int)ws[g]);
+  }
+  delete[] refs;
+  return ok ? rec->byte_len : UINT64_MAX;
 }
 
 }  // namespace smm_cpx

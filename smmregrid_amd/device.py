@@ -612,6 +612,33 @@ def grib_aec_pack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None
     return DeviceArray((int(used.value),), np.uint8, ptr=out.ptr, base=out), rows_out, ccsds_out
 
 
+def grib_cpx_pack(device_bytes, rows, cpx, x_bytes=None, out=None, stream=None):
+    """Code simple-packed streams resident in HBM as the complex-packed streams of GRIB-2 templates 5.2 / 5.3 on the
+    device (smm_grib_cpx_pack) -- the twin of `grib_unpack_cpx`, and what follows `grib_pack` when results leave
+    complex-packed.  device_bytes: a uint8 `DeviceArray` (it must cover x_bytes rounded up to 4); rows: one GRIB_ROW_DTYPE
+    record per field -- where its integers begin, their width; cpx: one GRIB_CPX_DTYPE record per field with the
+    parameters wanted (n_values and nbits as the field has them, order, length_ref = the group length;
+    `GribEncode.cpx_records`, `griblite.cpx_want`).  Returns (DeviceArray of uint8 cut to the bytes used, the rows with
+    byte_off at their streams -- nbits stays the width of the integers --, the full GRIB_CPX_DTYPE records of the streams
+    written): the streams lie back to back in field order, each at a 4-byte-aligned offset, bytewise what
+    `griblite.cpx_encode` gives.  A field of width 0 is not coded (byte_len 0, order GRIB_CPX_SIMPLE).  out: a uint8 DeviceArray of at least the bound (smm_grib_cpx_pack_bound) to code into.  The stream is synchronised
+    on return."""
+    from . import _grib
+    from .griblite import GRIB_CPX_DTYPE
+    x_ptr, n_bytes, rows, cpx, out = _grib.transcode_args("grib_cpx_pack", _grib.CPX, "smm_grib_cpx_pack_bound",
+                                                          device_bytes, rows, cpx, x_bytes, out)
+    cpx_out = np.zeros(rows.size, dtype=GRIB_CPX_DTYPE)
+    used = ctypes.c_uint64(0)
+    _lib.call("smm_grib_cpx_pack", current_device(), x_ptr, n_bytes,
+              ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)),
+              ctypes.cast(cpx.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)), rows.size, ctypes.c_void_p(out.ptr),
+              out.nbytes, ctypes.cast(cpx_out.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)), ctypes.byref(used),
+              _stream_handle(stream))
+    rows_out = rows.copy()
+    rows_out["byte_off"] = cpx_out["byte_off"]
+    return DeviceArray((int(used.value),), np.uint8, ptr=out.ptr, base=out), rows_out, cpx_out
+
+
 def empty(shape, dtype=np.float64):
     if not isinstance(shape, tuple):
         shape = tuple(np.atleast_1d(shape).tolist())

@@ -141,6 +141,38 @@ def aec_encode(values, record, histogram=None):
     return out[:int(used.value)].copy()
 
 
+def cpx_encode(values, rec):
+    """(stream: a uint8 array, its GRIB_CPX_DTYPE record with byte_off 0) of the unsigned integers `values`, coded as a
+    complex-packed stream by the library on the host (smm_grib_cpx_encode_host; no GPU involved) by THE RULE OF THIS
+    ENCODER of smm_grib_cpx.hpp -- the oracle of smm_grib_cpx_pack.  rec: a GRIB_CPX_DTYPE record whose nbits (the width
+    of the integers), order (wanted, 0..2) and length_ref (the group length: 8, 16, 32 or 64) say how to code; n_values
+    is set from `values`, nothing else is read.  Integers of width 0 are not coded: no bytes, and a record whose order is
+    GRIB_CPX_SIMPLE."""
+    from . import _lib
+    v = np.ascontiguousarray(values, dtype=np.uint32).ravel()
+    rec = np.array(rec, dtype=GRIB_CPX_DTYPE).reshape(1)
+    rec["n_values"] = v.size
+    rec_p = ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct))
+    bound = ctypes.c_uint64(0)
+    _lib.call("smm_grib_cpx_pack_bound", rec_p, 1, None, ctypes.byref(bound))
+    out = np.zeros(max(int(bound.value), 1), dtype=np.uint8)
+    used = ctypes.c_uint64(0)
+    rec_out = np.zeros(1, dtype=GRIB_CPX_DTYPE)
+    _lib.call("smm_grib_cpx_encode_host", v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size, rec_p,
+              ctypes.c_void_p(out.ctypes.data), int(bound.value), ctypes.byref(used),
+              ctypes.cast(rec_out.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)))
+    return out[:int(used.value)].copy(), rec_out[0]
+
+
+def cpx_want(nbits, order, group_len, n_values=0):
+    """The wanted GRIB_CPX_DTYPE record(s) of `cpx_encode` / `device.grib_cpx_pack`: integers of nbits bits coded at
+    `order` in groups of group_len values.  Scalars give one record, arrays one per entry."""
+    shape = np.broadcast(nbits, order, group_len, n_values).shape
+    rec = np.zeros(shape, dtype=GRIB_CPX_DTYPE)
+    rec["nbits"], rec["order"], rec["length_ref"], rec["n_values"] = nbits, order, group_len, n_values
+    return rec
+
+
 class GribField:
     """The fields of one GRIB variable kept as the file has them: `buf`, the file's bytes (one uint8 array shared by
     every variable of the file), and `rows`, a GRIB_ROW_DTYPE record per field in (time, level) order that says where
@@ -234,11 +266,19 @@ class GribEncode:
     a CCSDS stream (template 5.42) by THE RULE OF THIS ENCODER of smm_grib_aec.hpp instead of stored at their width;
     `encode` is then the host oracle of smm_grib_pack followed by smm_grib_aec_pack.  True means block size 32, a
     reference sample interval of 128 blocks and the preprocessor on, with ccsdsFlags 0x0e -- ecCodes' defaults as
-    recalled, not pinned against an ecCodes file (like the section-5 octets)."""
+    recalled, not pinned against an ecCodes file (like the section-5 octets).
+    cpx: None, True or (order, group_len) -- or one such tuple per field: the q of every field are coded as a
+    complex-packed stream (templates 5.2 / 5.3) by THE RULE OF THIS ENCODER of smm_grib_cpx.hpp; `encode` is then the host
+    oracle of smm_grib_pack followed by smm_grib_cpx_pack.  True means second-order differencing in groups of 32.  It does
+    not go with ccsds.
+    A width of `SOURCE_WIDTH` marks a field whose width is the one its complex-packed source row's integers decode to:
+    only `apply_host_grib(cpx=..., grib_out=)` can resolve it (`resolved`); everything else refuses the mark."""
 
     CCSDS_DEFAULT = (32, 128, True)
+    CPX_DEFAULT = (2, 32)
+    SOURCE_WIDTH = -(1 << 15)      # no width: every other value outside 1..32 is refused
 
-    def __init__(self, nbits, decimal_scale=0, ccsds=None):
+    def __init__(self, nbits, decimal_scale=0, ccsds=None, cpx=None):
         nb, ds = np.asarray(nbits), np.asarray(decimal_scale)
         if nb.ndim > 1 or ds.ndim > 1:
             raise ValueError("nbits and decimal_scale are scalars or one entry per field")
@@ -250,8 +290,10 @@ class GribEncode:
         n = 1 if self.n_fields is None else self.n_fields
         self.nbits = np.broadcast_to(nb.astype(np.int32), (n,)).copy()
         self.decimal_scale = np.broadcast_to(ds.astype(np.int64), (n,)).copy()
-        if ((self.nbits < 1) | (self.nbits > 32)).any():
+        if (((self.nbits < 1) | (self.nbits > 32)) & (self.nbits != self.SOURCE_WIDTH)).any():
             raise ValueError("GRIB output widths are 1..32 bits")
+        if ccsds is not None and cpx is not None:
+            raise ValueError("cpx does not go with ccsds: a result is coded one way")
         self.ddiv = np.array([10.0 ** int(d) if abs(int(d)) < 309 else np.inf for d in self.decimal_scale], dtype=np.float64)
         if not (np.isfinite(self.ddiv) & (self.ddiv > 0)).all():
             raise ValueError("10^D must be finite and positive")
@@ -263,6 +305,14 @@ class GribEncode:
                                                               (self.nbits, self.decimal_scale, self.ddiv))
             elif self.ccsds.size != self.n_fields:
                 raise ValueError(f"{self.ccsds.size} CCSDS parameter sets for {self.n_fields} fields")
+        self.cpx = None if cpx is None else self._cpx_params(cpx)
+        if self.cpx is not None and self.cpx.size > 1:
+            if self.n_fields is None:      # scalars beside one parameter set per field
+                self.n_fields = self.cpx.size
+                self.nbits, self.decimal_scale, self.ddiv = (np.repeat(a, self.n_fields) for a in
+                                                              (self.nbits, self.decimal_scale, self.ddiv))
+            elif self.cpx.size != self.n_fields:
+                raise ValueError(f"{self.cpx.size} complex-packing parameter sets for {self.n_fields} fields")
 
     @classmethod
     def _ccsds_params(cls, ccsds):
@@ -282,7 +332,39 @@ class GribEncode:
         return rec
 
     @classmethod
-    def from_field(cls, field, ccsds=None):
+    def _cpx_params(cls, cpx):
+        """GRIB_CPX_DTYPE records with order and length_ref (the group length) set, from True, one (order, group_len) or
+        a list of them."""
+        if cpx is True:
+            cpx = cls.CPX_DEFAULT
+        if isinstance(cpx, np.ndarray) and cpx.dtype == GRIB_CPX_DTYPE:
+            par = [(int(r["order"]), int(r["length_ref"])) for r in cpx.ravel()]
+        else:
+            par = [tuple(cpx)] if np.ndim(cpx[0]) == 0 else [tuple(c) for c in cpx]
+        rec = np.zeros(len(par), dtype=GRIB_CPX_DTYPE)
+        for i, (order, group_len) in enumerate(par):
+            if int(order) not in (0, 1, 2) or int(group_len) not in (8, 16, 32, 64):
+                raise ValueError(f"complex packing of order {order} in groups of {group_len}: 0, 1 or 2 and 8, 16, 32 or 64")
+            rec[i]["order"], rec[i]["length_ref"] = int(order), int(group_len)
+        return rec
+
+    @property
+    def has_source_width(self):
+        return bool((self.nbits == self.SOURCE_WIDTH).any())
+
+    def resolved(self, widths):
+        """This rule with every `SOURCE_WIDTH` mark replaced by the entry of `widths` (one per field: what
+        smm_grib_cpx_unpack reports for the source rows).  A width of 0 there -- a constant source row -- becomes the
+        largest width of the resolved fields, or 16 if all are 0, as `from_field` has it for a constant row."""
+        widths = np.asarray(widths, dtype=np.int32).ravel()
+        nbits, _ = self._per_field(widths.size, marks=True)
+        nbits = np.where(nbits == self.SOURCE_WIDTH, widths, nbits).astype(np.int32)
+        top = int(nbits.max()) if nbits.size and nbits.max() > 0 else 16
+        return GribEncode(np.where(nbits == 0, top, nbits).astype(np.int32),
+                          np.broadcast_to(self.decimal_scale, nbits.shape).copy(), ccsds=self.ccsds, cpx=self.cpx)
+
+    @classmethod
+    def from_field(cls, field, ccsds=None, cpx=None):
         """Each source row's own width and D.  A width of 0 (a constant field) becomes the variable's largest width,
         or 16 if all are 0.  ccsds=True: the result is CCSDS-coded, each field with its source field's own block size,
         interval and preprocessor switch where the source is CCSDS-packed, with the defaults where it is not."""
@@ -290,8 +372,17 @@ class GribEncode:
             ccsds = [(int(r["block_size"]), int(r["rsi"]), bool(int(r["flags"]) & _AEC_PREPROCESS))
                      if int(r["block_size"]) else cls.CCSDS_DEFAULT for r in field.ccsds]
         nbits = field.rows["nbits"].astype(np.int32)
-        top = int(nbits.max()) if nbits.size and nbits.max() > 0 else 16
-        nbits = np.where(nbits == 0, top, nbits).astype(np.int32)
+        marked = np.zeros(nbits.size, dtype=bool)
+        if cpx is True:
+            # a complex-packed source row keeps its order and gets groups of 32; its row's nbits is octet 20, the width of
+            # its group references, not of its integers: the width is the one the device decode will report
+            src = getattr(field, "cpx", None)
+            if src is not None:
+                marked = src["order"] != GRIB_CPX_SIMPLE
+                cpx = [(int(r["order"]), cls.CPX_DEFAULT[1]) if m else cls.CPX_DEFAULT for r, m in zip(src, marked)]
+        live = nbits[~marked]
+        top = int(live.max()) if live.size and live.max() > 0 else 16
+        nbits = np.where(marked, cls.SOURCE_WIDTH, np.where(nbits == 0, top, nbits)).astype(np.int32)
         ddiv = field.rows["ddiv"].astype(np.float64)
         if not (np.isfinite(ddiv) & (ddiv > 0)).all():
             raise ValueError("a source row's ddiv is not finite and positive")
@@ -299,13 +390,39 @@ class GribEncode:
         for d, want in zip(dec, ddiv):
             if 10.0 ** int(d) != want:
                 raise ValueError(f"ddiv {want!r} is not 10.0 ** D for an integer D")
-        return cls(nbits, dec, ccsds=ccsds)
+        return cls(nbits, dec, ccsds=ccsds, cpx=cpx)
 
     def rows_of(self, r0, r1, n_fields):
-        """The GribEncode of fields [r0, r1) of n_fields."""
-        nbits, _ = self._per_field(n_fields)
+        """The GribEncode of fields [r0, r1) of n_fields (`SOURCE_WIDTH` marks stay)."""
+        nbits, _ = self._per_field(n_fields, marks=True)
         par = None if self.ccsds is None else self.ccsds_records(n_fields)[r0:r1]
-        return GribEncode(nbits[r0:r1].copy(), np.broadcast_to(self.decimal_scale, (int(n_fields),))[r0:r1].copy(), ccsds=par)
+        cpx = None if self.cpx is None else self.cpx_records(n_fields, marks=True)[r0:r1]
+        return GribEncode(nbits[r0:r1].copy(), np.broadcast_to(self.decimal_scale, (int(n_fields),))[r0:r1].copy(), ccsds=par,
+                          cpx=cpx)
+
+    def cpx_records(self, n_fields, n_values=0, nbits=0, marks=False):
+        """The wanted smm_grib_cpx_t records of n_fields fields (smm_grib_cpx_pack): order and group length of this rule,
+        n_values and nbits (the stored widths) as given."""
+        self._per_field(n_fields, marks=marks)
+        rec = np.zeros(int(n_fields), dtype=GRIB_CPX_DTYPE)
+        rec[:] = self.cpx if self.cpx.size > 1 else self.cpx[0]
+        rec["n_values"], rec["nbits"] = n_values, nbits
+        return rec
+
+    def cpx_bound(self, n_points, n_fields):
+        """Bytes the coded streams of n_fields fields of n_points points take at most (smm_grib_cpx_pack_bound)."""
+        return int(self.cpx_bounds(n_points, n_fields).sum())
+
+    def cpx_bounds(self, n_points, n_fields):
+        """The same field by field (int64)."""
+        from . import _lib
+        nbits, _ = self._per_field(n_fields)
+        rec = self.cpx_records(n_fields, int(n_points), nbits)
+        offs, total = np.zeros(rec.size + 1, dtype=np.uint64), ctypes.c_uint64(0)
+        _lib.call("smm_grib_cpx_pack_bound", ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)), rec.size,
+                  offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(total))
+        offs[rec.size] = total.value
+        return np.diff(offs).astype(np.int64)
 
     def ccsds_records(self, n_fields, n_values=0, nbits=0):
         """The wanted smm_grib_aec_t records of n_fields fields (smm_grib_aec_pack): block size, interval and flags of this
@@ -331,10 +448,13 @@ class GribEncode:
         offs[rec.size] = total.value
         return np.diff(offs).astype(np.int64)
 
-    def _per_field(self, n_fields):
+    def _per_field(self, n_fields, marks=False):
         n_fields = int(n_fields)
         if self.n_fields is not None and self.n_fields != n_fields:
             raise ValueError(f"a GribEncode of {self.n_fields} fields for {n_fields} fields")
+        if not marks and self.has_source_width:
+            raise ValueError("a width of GribEncode.SOURCE_WIDTH is the width of a complex-packed source row: only "
+                             "apply_host_grib(cpx=..., grib_out=) resolves it")
         return np.broadcast_to(self.nbits, (n_fields,)), np.broadcast_to(self.ddiv, (n_fields,))
 
     def records(self, n_fields):
@@ -399,17 +519,19 @@ class GribEncode:
                     buf[off + bm_bytes:off + bm_bytes + packed.size] = packed
             rows[b] = (off + bm_bytes, ref, float(np.ldexp(1.0, E)), dd, width, 0)
             bitmaps[b] = (GRIB_NO_BITMAP if nv == n else off, nv)
-        if self.ccsds is not None:
-            return self._encode_ccsds(buf, rows, bitmaps, shape, n)
+        if self.ccsds is not None or self.cpx is not None:
+            return self._encode_coded(buf, rows, bitmaps, shape, n)
         return GribField(buf, rows, shape, n, bitmaps=bitmaps)
 
-    def _encode_ccsds(self, buf, rows, bitmaps, shape, n):
-        """The simple-packed fields of `encode` with their integers coded as CCSDS streams.  The buffer: every field's
-        bitmap slot (align4(ceil(n_points / 8)) bytes, written whether the field has missing points or not) in field
-        order, then the streams back to back in field order, each at a 4-byte-aligned offset.  A field of width 0 has no
-        stream (block_size 0)."""
+    def _encode_coded(self, buf, rows, bitmaps, shape, n):
+        """The simple-packed fields of `encode` with their integers coded as CCSDS or complex-packed streams.  The buffer:
+        every field's bitmap slot (align4(ceil(n_points / 8)) bytes, written whether the field has missing points or not)
+        in field order, then the streams back to back in field order, each at a 4-byte-aligned offset.  A field of width 0
+        has no stream (block_size 0; order GRIB_CPX_SIMPLE).  The rows keep the widths of the integers."""
         nf, bm_bytes = rows.size, _align4((n + 7) // 8)
-        rec = self.ccsds_records(nf, bitmaps["n_values"], rows["nbits"])
+        aec = self.ccsds is not None
+        rec = self.ccsds_records(nf, bitmaps["n_values"], rows["nbits"]) if aec else \
+            self.cpx_records(nf, bitmaps["n_values"], rows["nbits"])
         streams, at = [], nf * bm_bytes
         head = np.zeros(at, dtype=np.uint8)
         rows, bitmaps = rows.copy(), bitmaps.copy()
@@ -419,15 +541,21 @@ class GribEncode:
             if int(bitmaps["bitmap_off"][b]) != GRIB_NO_BITMAP:
                 bitmaps["bitmap_off"][b] = b * bm_bytes
             rec["byte_off"][b] = rows["byte_off"][b] = at
-            if w == 0:
+            if w == 0 and aec:
                 rec["block_size"][b] = 0
                 continue
-            q = _unpack_bits(bytes(memoryview(buf)[off:off + (nv * w + 7) // 8]), w, nv).astype(np.uint32)
-            st = aec_encode(q, rec[b])
+            q = _unpack_bits(bytes(memoryview(buf)[off:off + (nv * w + 7) // 8]), w, nv).astype(np.uint32) if w else \
+                np.zeros(nv, dtype=np.uint32)
+            if aec:
+                st = aec_encode(q, rec[b])
+            else:      # the full record of the stream written (marked simple-packed, without bytes, at width 0)
+                st, rec[b] = cpx_encode(q, rec[b])
+                rec["byte_off"][b] = at
             rec["byte_len"][b] = st.size
             streams.append(np.concatenate([st, np.zeros(_align4(st.size) - st.size, dtype=np.uint8)]))
             at += _align4(st.size)
-        return GribField(np.concatenate([head] + streams), rows, shape, n, bitmaps=bitmaps, ccsds=rec)
+        return GribField(np.concatenate([head] + streams), rows, shape, n, bitmaps=bitmaps, ccsds=rec if aec else None,
+                         cpx=None if aec else rec)
 
     def __repr__(self):
         return f"<GribEncode widths {sorted(set(self.nbits.tolist()))}, D {sorted(set(self.decimal_scale.tolist()))}>"

@@ -11,8 +11,9 @@ import time
 import numpy as np
 
 from . import _grib, _lib
+from . import device as _device
 from .device import (DeviceArray, bfloat16, check_half_pair, dtype_code, field_dtype_code, is_half_dtype,
-                     is_packed_dtype, result_cache, result_dtype, _stream_handle, current_device, grib_aec_pack, grib_pack)
+                     is_packed_dtype, result_cache, result_dtype, _stream_handle, current_device, grib_pack)
 
 
 def _cptr(a):
@@ -369,22 +370,29 @@ class SparseOperator:
         """`apply_host_grib(ccsds=)` and `apply_host_grib(cpx=)`: a synchronous loop over chunks of consecutive rows
         (`_grib.host_chunks`), each chunk's Y copied back."""
         out = _grib.float64_result(out, (rows.size, self.n_dst), result_cache.empty, "out")
-        for r0, r1, y in _grib.host_chunks(self, buf, rows, bitmaps, kind, recs, chunk_rows, **apply_kw):
+        for r0, r1, y, _ in _grib.host_chunks(self, buf, rows, bitmaps, kind, recs, chunk_rows, **apply_kw):
             y.to_host(out=out[r0:r1])
         return out
 
-    def _apply_host_grib_out_ccsds(self, buf, rows, grib_out, bitmaps, kind, recs, chunk_rows, **apply_kw):
-        """`apply_host_grib(grib_out=GribEncode(..., ccsds=...))`: the chunks of `_grib.host_chunks`, each chunk's float64
-        Y packed on the device (smm_grib_pack) and its integers coded as CCSDS streams (smm_grib_aec_pack); one D2H copy
-        of the chunk's bitmaps (none when no cell is missing: they are all ones) and one of the bytes its streams use.  Y
-        and the simple-packed streams never leave the device.  The chunk budget counts the simple-packed slots and the
-        streams' bound, not the bytes used.  The result's buffer is laid out as `GribEncode.encode` lays it out: every
-        field's bitmap slot, then the streams back to back."""
-        from .griblite import GRIB_AEC_DTYPE, GRIB_BITMAP_DTYPE, GRIB_NO_BITMAP, GRIB_ROW_DTYPE, GribField
+    def _apply_host_grib_out_coded(self, buf, rows, grib_out, okind, bitmaps, kind, recs, chunk_rows, **apply_kw):
+        """`apply_host_grib(grib_out=GribEncode(..., ccsds=...))` and `(..., cpx=...)`, okind the `_grib.CodedOut` of the
+        two: the chunks of `_grib.host_chunks`, each chunk's float64 Y packed on the device (smm_grib_pack) and its
+        integers coded as CCSDS or complex-packed streams (smm_grib_aec_pack, smm_grib_cpx_pack); one D2H copy of the
+        chunk's bitmaps (none when no cell is missing: they are all ones) and one of the bytes its streams use.  Y and
+        the simple-packed streams never leave the device.  The chunk budget counts the simple-packed slots and the
+        streams' bound, not the bytes used; a width marked `GribEncode.SOURCE_WIDTH` counts as 32 bits there and becomes,
+        chunk by chunk, the width smm_grib_cpx_unpack reports for the source row.  The result's buffer is laid out as
+        `GribEncode.encode` lays it out: every field's bitmap slot, then the streams back to back."""
+        from .griblite import GRIB_BITMAP_DTYPE, GRIB_NO_BITMAP, GRIB_ROW_DTYPE, GribField
         n_batch, D = rows.size, self.n_dst
-        offs, total = grib_out.layout(D, n_batch)
+        worst = grib_out.rows_of(0, n_batch, n_batch)
+        if worst.has_source_width:
+            if kind is not _grib.CPX:
+                worst._per_field(n_batch)      # the ValueError of an unresolved mark
+            worst = worst.resolved(np.full(n_batch, 32, dtype=np.int32))
+        offs, total = worst.layout(D, n_batch)
         slot = np.diff(np.append(offs, np.uint64(total))).astype(np.int64)
-        bound = grib_out.ccsds_bounds(D, n_batch)
+        bound = getattr(worst, okind.bounds)(D, n_batch)
         bm_bytes = (D + 7) // 8 + (-((D + 7) // 8)) % 4
         result = np.empty(n_batch * bm_bytes + int(bound.sum()), dtype=np.uint8)      # cut to the bytes used at the end
         head = result[:n_batch * bm_bytes]
@@ -392,20 +400,24 @@ class SparseOperator:
         full = np.packbits(np.ones(D, dtype=np.uint8))
         rows_out = np.zeros(n_batch, dtype=GRIB_ROW_DTYPE)
         bitmaps_out = np.zeros(n_batch, dtype=GRIB_BITMAP_DTYPE)
-        ccsds_out = np.zeros(n_batch, dtype=GRIB_AEC_DTYPE)
+        recs_out = np.zeros(n_batch, dtype=okind.dtype)
         at = n_batch * bm_bytes
-        # per row beside Y: its simple-packed slot, the bound of its stream, 8 B per block and 12 B per segment of scratch
-        extra = slot + bound + (D // 8 + 1) * 20
-        for r0, r1, y in _grib.host_chunks(self, buf, rows, bitmaps, kind, recs, chunk_rows, extra_cost=extra, **apply_kw):
+        # per row beside Y: its simple-packed slot, the bound of its stream, the coder's scratch
+        extra = slot + bound + okind.scratch(D)
+        pack = getattr(_device, okind.pack)
+        for r0, r1, y, rows_in in _grib.host_chunks(self, buf, rows, bitmaps, kind, recs, chunk_rows, extra_cost=extra, **apply_kw):
             enc = grib_out.rows_of(r0, r1, n_batch)
+            if enc.has_source_width:
+                enc = enc.resolved(rows_in["nbits"])
             packed, rows_c, bm_c = grib_pack(y, enc)
-            want = enc.ccsds_records(r1 - r0, bm_c["n_values"], rows_c["nbits"])
-            coded, rows_c, aec_c = grib_aec_pack(packed, rows_c, want)
+            slot_c = np.diff(np.append(*enc.layout(D, r1 - r0))).astype(np.int64)
+            want = getattr(enc, okind.records)(r1 - r0, bm_c["n_values"], rows_c["nbits"])
+            coded, rows_c, recs_c = pack(packed, rows_c, want)
             missing = np.flatnonzero(bm_c["bitmap_off"] != GRIB_NO_BITMAP)
             h = head[r0 * bm_bytes:r1 * bm_bytes].reshape(r1 - r0, bm_bytes)
             h[:, :full.size] = full
-            if missing.size and (slot[r0:r1] == slot[r0]).all():      # one strided copy of the chunk's bitmap slots
-                _lib.call("smm_memcpy2d_d2h", _cptr(h), bm_bytes, ctypes.c_void_p(packed.ptr), int(slot[r0]), bm_bytes,
+            if missing.size and (slot_c == slot_c[0]).all():      # one strided copy of the chunk's bitmap slots
+                _lib.call("smm_memcpy2d_d2h", _cptr(h), bm_bytes, ctypes.c_void_p(packed.ptr), int(slot_c[0]), bm_bytes,
                           r1 - r0, None)
                 _lib.call("smm_stream_sync", None)
             else:
@@ -415,10 +427,10 @@ class SparseOperator:
             if coded.nbytes:
                 coded.to_host(out=result[at:at + coded.nbytes])
             rows_c["byte_off"] += np.uint64(at)
-            aec_c["byte_off"] += np.uint64(at)
-            rows_out[r0:r1], bitmaps_out[r0:r1], ccsds_out[r0:r1] = rows_c, bm_c, aec_c
+            recs_c["byte_off"] += np.uint64(at)
+            rows_out[r0:r1], bitmaps_out[r0:r1], recs_out[r0:r1] = rows_c, bm_c, recs_c
             at += coded.nbytes
-        return GribField(result[:at], rows_out, (n_batch, D), D, bitmaps=bitmaps_out, ccsds=ccsds_out)
+        return GribField(result[:at], rows_out, (n_batch, D), D, bitmaps=bitmaps_out, **{okind.attr: recs_out})
 
     def apply_host_grib(self, buf, rows, out=None, masked=False, remap_area_min=0.0, flags=0, chunk_rows=0, bitmaps=None,
                         skipna=False, grib_out=None, ccsds=None, cpx=None):
@@ -438,22 +450,29 @@ class SparseOperator:
         loop, with smm_grib_pack and smm_grib_aec_pack behind the gather; the input may be simple-packed or, through
         ccsds=, CCSDS-packed itself.
         cpx as for `apply_grib`: the rows' complex-packed streams cross PCIe as they are and are decoded on the device, in
-        the same synchronous chunk loop.  It goes neither with ccsds nor with grib_out."""
+        the same synchronous chunk loop.  It goes neither with ccsds nor with a simple-packed or CCSDS grib_out.
+        grib_out a `GribEncode` with `cpx` set: the result comes back complex-packed (templates 5.2 / 5.3) -- a `GribField`
+        with `bitmaps` and `cpx` set, in a buffer of its own, bytewise `grib_out.encode` of the float64 result; its rows
+        carry the widths the integers were packed at.  The same synchronous chunk loop, with smm_grib_pack and
+        smm_grib_cpx_pack behind the gather; the input may be simple-packed or, through cpx=, complex-packed itself (not
+        CCSDS-packed).  Only there a width of `GribEncode.SOURCE_WIDTH` is legal: it becomes, chunk by chunk, the width
+        the source row's integers decode to."""
         rows, rows_p = _grib.grib_rows(rows)
         buf = np.ascontiguousarray(buf)
         if buf.dtype != np.uint8 or buf.ndim != 1:
             raise TypeError("apply_host_grib takes the packed bytes as a 1-d uint8 array")
         kind, recs = _grib.one_kind(ccsds, cpx)
-        ccsds_out = grib_out is not None and getattr(grib_out, "ccsds", None) is not None
-        if grib_out is not None and (kind is _grib.CPX or (kind is _grib.CCSDS and not ccsds_out)):
+        okind = _grib.out_kind(grib_out)
+        if grib_out is not None and kind is not None and (okind is None or kind not in okind.takes):
             raise ValueError(f"{kind.arg} does not go with grib_out: decode the field on the host first")
-        if ccsds_out and out is not None:
-            raise ValueError("a CCSDS-coded result comes in a buffer of its own: its size is known only afterwards")
+        if okind is not None and out is not None:
+            raise ValueError(f"a {okind.words} result comes in a buffer of its own: its size is known only afterwards")
         n_batch = rows.size
-        if kind is not None or ccsds_out:      # rows decoded or coded on the device: the chunk loop
+        if kind is not None or okind is not None:      # rows decoded or coded on the device: the chunk loop
             apply_kw = dict(masked=masked, remap_area_min=remap_area_min, flags=int(flags), skipna=skipna)
-            if ccsds_out:
-                return self._apply_host_grib_out_ccsds(buf, rows, grib_out, bitmaps, kind, recs, int(chunk_rows), **apply_kw)
+            if okind is not None:
+                return self._apply_host_grib_out_coded(buf, rows, grib_out, okind, bitmaps, kind, recs, int(chunk_rows),
+                                                       **apply_kw)
             return self._apply_host_grib_coded(buf, rows, out, bitmaps, kind, recs, int(chunk_rows), **apply_kw)
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
         if grib_out is not None:

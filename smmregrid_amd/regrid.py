@@ -59,7 +59,7 @@ class Regridder(object):
                  check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=None,
                  lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False,
                  packed_levels=False, packed_out=False, packed_out_levels=False, half=False, packed_skipna=False, grib_out=False,
-                 grib_out_levels=False, grib_out_ccsds=False):
+                 grib_out_levels=False, grib_out_ccsds=False, grib_out_cpx=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -128,6 +128,16 @@ class Regridder(object):
         self.grib_out_ccsds = bool(grib_out_ccsds)
         if self.grib_out_ccsds and not self.grib_out:
             raise ValueError('grib_out_ccsds=True needs grib_out=True')
+        # grib_out_cpx (with grib_out=True): on 2-D weights the packed result is complex-packed on the device behind the
+        # pack (templates 5.2 / 5.3; smm_grib_cpx_pack; GribEncode.from_field(src, cpx=True)): a simple-packed source gets
+        # second-order differencing in groups of 32, a complex-packed source keeps its own order, is packed at the width
+        # its integers decode to and stays raw end to end -- no host decode, no INFO line.  Masked-level weights keep the
+        # simple-packed result of grib_out_levels
+        self.grib_out_cpx = bool(grib_out_cpx)
+        if self.grib_out_cpx and not self.grib_out:
+            raise ValueError('grib_out_cpx=True needs grib_out=True')
+        if self.grib_out_cpx and self.grib_out_ccsds:
+            raise ValueError('grib_out_cpx=True does not go with grib_out_ccsds=True: a result is coded one way')
         # packed_out (with packed=True): a variable regridded raw comes back in its own raw dtype, encoded by the rule
         # of its own attributes (CFEncode) inside the kernels' stores, and keeps its packing attributes: it can be
         # written straight to a file.  Values that round outside the raw range become the fill value (no wrap-around)
@@ -414,8 +424,9 @@ class Regridder(object):
         """Why a `GribField` with these dims is decoded on the host, or None: it takes the raw road.  levels: it meets
         masked-level (3-D) weights.  ccsds: some of its fields are CCSDS-packed (`GribField.ccsds`) -- their road is the
         one of 2-D weights and float64 results (smm_grib_aec_unpack ahead of the gather).  cpx: some are complex-packed
-        (`GribField.cpx`, templates 5.2 / 5.3) -- the same road through smm_grib_cpx_unpack, and no packed result: there is
-        no encoder for it, and the row record of such a field does not hold the width of its integers.  The one
+        (`GribField.cpx`, templates 5.2 / 5.3) -- the same road through smm_grib_cpx_unpack, and a packed result only
+        complex-packed again (grib_out_cpx): the row record of such a field does not hold the width of its integers, which
+        the device decode reports chunk by chunk.  The one
         condition behind `_grib_or_decoded` and the guards of `apply_weights` and `regrid3d`, which direct calls reach
         without it."""
         if not self.packed:
@@ -424,7 +435,7 @@ class Regridder(object):
             return "CCSDS packing on masked levels"
         if cpx and levels:
             return "complex packing on masked levels"
-        if cpx and self.grib_out:
+        if cpx and self.grib_out and not getattr(self, "grib_out_cpx", False):
             return "complex packing with grib_out"
         if ccsds and self.grib_out and not getattr(self, "grib_out_ccsds", False):
             return "CCSDS packing with grib_out"
@@ -622,11 +633,15 @@ class Regridder(object):
                     raise ValueError(f"{src.rows.size} GRIB fields for {n_batch} batch rows of shape {tuple(kept_shape)}")
                 # (with their bitmaps, if any: smm_apply_host_grib_bm ranks them on the device)
                 if self.grib_out:     # the result packed on the device, each field by its source's width and D
-                    # (grib_out_ccsds: and its integers coded as CCSDS streams behind the pack; a CCSDS source goes in raw)
-                    enc = GribEncode.from_field(src, ccsds=True if self.grib_out_ccsds else None)
+                    # (grib_out_ccsds: and its integers coded as CCSDS streams behind the pack; a CCSDS source goes in raw.
+                    # grib_out_cpx: the same with complex packing)
+                    enc = GribEncode.from_field(src, ccsds=True if self.grib_out_ccsds else None,
+                                                cpx=True if self.grib_out_cpx else None)
                     y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps,
-                                           skipna=skipna, grib_out=enc, ccsds=src.ccsds if self.grib_out_ccsds else None)
-                    return GribField(y.buf, y.rows, kept_shape + tgt_shape, op.n_dst, bitmaps=y.bitmaps, ccsds=y.ccsds)
+                                           skipna=skipna, grib_out=enc, ccsds=src.ccsds if self.grib_out_ccsds else None,
+                                           cpx=src.cpx if self.grib_out_cpx else None)
+                    return GribField(y.buf, y.rows, kept_shape + tgt_shape, op.n_dst, bitmaps=y.bitmaps, ccsds=y.ccsds,
+                                     cpx=y.cpx)
                 # (CCSDS-packed fields: their streams are decoded on the device ahead of the gather, smm_grib_aec_unpack)
                 # (complex-packed fields likewise: smm_grib_cpx_unpack)
                 y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps,
