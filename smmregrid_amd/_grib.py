@@ -24,19 +24,22 @@ def _cast(records, struct):
 # ---------------------------------------------------------------------------------------------- kinds of coded rows
 # What differs between the kinds of coded rows a call may hold.  arg: the keyword that carries the records; words: what
 # messages call them; is_coded(recs, rows): which rows of a call have a coded stream -- the others are simple-packed;
-# device_cost(recs, n_val, nbits): the device bytes a coded row costs in a chunk beside its staged stream.
-Coded = namedtuple("Coded", "arg words dtype struct layout_entry unpack_entry is_coded device_cost")
+# device_cost(recs, n_val, nbits): the device bytes a coded row costs in a chunk beside its staged stream; bound_entry,
+# pack_entry: the way back, simple-packed streams coded as rows of this kind.
+Coded = namedtuple("Coded", "arg words dtype struct layout_entry unpack_entry is_coded device_cost bound_entry pack_entry")
 
 # a record with block_size 0 marks a simple-packed row, a row of width 0 has no stream at all; a coded row costs its
 # transcoded stream and 4 B per sample of scratch
 CCSDS = Coded("ccsds", "CCSDS records", GRIB_AEC_DTYPE, _lib.GribAecStruct, "smm_grib_aec_layout", "smm_grib_aec_unpack",
               lambda recs, rows: (recs["block_size"] != 0) & (rows["nbits"] != 0),
-              lambda recs, n_val, nbits: align4((n_val * nbits + 7) // 8) + 4 * n_val)
+              lambda recs, n_val, nbits: align4((n_val * nbits + 7) // 8) + 4 * n_val,
+              "smm_grib_aec_pack_bound", "smm_grib_aec_pack")
 # a record whose order is GRIB_CPX_SIMPLE marks a simple-packed row; a coded row costs its slot of 4 B per value and
 # 8 B per value plus 16 B per group of scratch
 CPX = Coded("cpx", "complex-packing records", GRIB_CPX_DTYPE, _lib.GribCpxStruct, "smm_grib_cpx_layout",
             "smm_grib_cpx_unpack", lambda recs, rows: recs["order"] != GRIB_CPX_SIMPLE,
-            lambda recs, n_val, nbits: 12 * n_val + 16 * recs["n_groups"].astype(np.int64) + 256)
+            lambda recs, n_val, nbits: 12 * n_val + 16 * recs["n_groups"].astype(np.int64) + 256,
+            "smm_grib_cpx_pack_bound", "smm_grib_cpx_pack")
 
 
 # What differs between the kinds of coded results (`apply_host_grib(grib_out=GribEncode(..., ccsds= / cpx=))`).  attr: the
@@ -117,7 +120,7 @@ def packed_bytes(x, x_bytes, who, raw=False):
 
 
 def transcode_args(who, kind, bound_entry, device_bytes, rows, recs, x_bytes, out):
-    """What `grib_unpack`, `grib_unpack_cpx` and `grib_aec_pack` check alike: (pointer, n_bytes) of the bytes, the row
+    """What `unpack_device` and `pack_device` check alike: (pointer, n_bytes) of the bytes, the row
     and `kind` records, and `out` -- given or fresh -- holding at least what bound_entry says the records need."""
     x_ptr, n_bytes = packed_bytes(device_bytes, x_bytes, who)
     rows, _ = grib_rows(rows)
@@ -138,6 +141,20 @@ def unpack_device(who, kind, device_bytes, rows, recs, x_bytes=None, out=None, s
               _cast(rows, _lib.GribRowStruct), rows.size, ctypes.c_void_p(out.ptr), out.nbytes,
               _cast(rows_out, _lib.GribRowStruct), _stream_handle(stream))
     return out, rows_out
+
+
+def pack_device(who, kind, device_bytes, rows, recs, x_bytes=None, out=None, stream=None):
+    """`grib_aec_pack` (CCSDS) and `grib_cpx_pack` (CPX): (out cut to the bytes used, the rows with byte_off at their
+    streams, the records of the streams written)."""
+    x_ptr, n_bytes, rows, recs, out = transcode_args(who, kind, kind.bound_entry, device_bytes, rows, recs, x_bytes, out)
+    recs_out = np.zeros(rows.size, dtype=kind.dtype)
+    used = ctypes.c_uint64(0)
+    _lib.call(kind.pack_entry, device.current_device(), x_ptr, n_bytes, _cast(rows, _lib.GribRowStruct),
+              _cast(recs, kind.struct), rows.size, ctypes.c_void_p(out.ptr), out.nbytes, _cast(recs_out, kind.struct),
+              ctypes.byref(used), _stream_handle(stream))
+    rows_out = rows.copy()
+    rows_out["byte_off"] = recs_out["byte_off"]
+    return DeviceArray((int(used.value),), np.uint8, ptr=out.ptr, base=out), rows_out, recs_out
 
 
 def unpack(kind, src, n_bytes, dst, shift, rows, recs, idx, stream):

@@ -1,22 +1,21 @@
 // smm_grib_aec_unpack (gfx950): the CCSDS streams of GRIB-2 template 5.42 turned into simple-packed streams on the
 // device, and the two host-only entries beside it (smm_grib_aec_layout, smm_grib_aec_decode_host).  The format and the
-// decoder's two rules are the text of smm_grib_aec.hpp; the kernels read the stream through its load_word / bits_of and
-// take the options apart with its zero_run_blocks / second_ext_pair / unmap.  Three kernels in stream order:
+// decoder's two rules are the text of smm_grib_aec.hpp; the kernels read the stream through smm_grib_codec.hpp's
+// load_word / bits_of and take the options apart with its zero_run_blocks / second_ext_pair / unmap.  What the kernels
+// and the entries share with the other transcoders -- the cut launches, the scans, the store, the host shell and the
+// entry checks -- is smm_grib_xcode.hpp.  Three kernels in stream order:
 //   parse    one wave per row.  Block boundaries are only known by parsing, so a row is serial in blocks; a block is
 //            done by all 64 lanes over a window of 128 stream words held in LDS
 //   inverse  the preprocessor's inverse, one lane per reference sample interval, 64 intervals x 16 samples of the
 //            scratch at a time through LDS (the global accesses are runs of 64 B, not one word per 16 KiB)
 //   store    one thread per 32-bit word of a row's output stream, as smm_grib_pack's pack pass
 // Plain vector stores, no atomics.
-#include "smm_device.hpp"
-
-#include <algorithm>
+#include "smm_grib_xcode.hpp"
 
 #include "smm_grib_aec.hpp"
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kWinWords = 128;        // the parse kernel's window: 4096 bits
 constexpr uint32_t kRefillAt = 60;    // words the cursor may be into the window at a block's start: the largest block
                                       // (5 + 1 + 32 + 64 * 32 bits) then ends 4037 bits in at most
@@ -42,10 +41,10 @@ struct AecArgs {
 // ---- 1: parse.  Every value that steers the loop is the same in all lanes (the row's record, the cursor, words of the
 // window every lane reads alike): the branches and barriers are wave-uniform.  A step consumes at least the ID's bits
 // and J samples, so a row takes at most ceil(n_values / J) steps whatever its bytes hold.
-__global__ __launch_bounds__(kWave) void smm_grib_aec_parse_kernel(AecArgs a, int64_t j0) {
+__global__ __launch_bounds__(kWave) void smm_grib_aec_parse_kernel(AecArgs a, int64_t b0) {
   __shared__ uint32_t win[kWinWords];
   __shared__ uint32_t ones[kWave];
-  const int64_t j = j0 + blockIdx.x;
+  const int64_t j = b0 + blockIdx.x;
   const uint32_t lane = threadIdx.x;
   const AecRow* __restrict__ rows = a.rows;
   const AecRow r = rows[j];
@@ -71,15 +70,15 @@ __global__ __launch_bounds__(kWave) void smm_grib_aec_parse_kernel(AecArgs a, in
   auto wpeek = [&](uint64_t p, int nb) -> uint32_t {
     uint32_t i = (uint32_t)((p >> 5) - wbase);
     i = i < (uint32_t)(kWinWords - 1) ? i : (uint32_t)(kWinWords - 2);
-    return smm_aec::bits_of(win[i], win[i + 1], (unsigned)(p & 31), nb);
+    return smm_grib::bits_of(win[i], win[i + 1], (unsigned)(p & 31), nb);
   };
 
   while (at < n) {
     if (!have_win || (pos >> 5) - wbase >= kRefillAt) {
       __syncthreads();
       wbase = pos >> 5;
-      win[lane] = smm_aec::load_word(a.x, wbase + lane, last_word, end_byte);
-      win[lane + kWave] = smm_aec::load_word(a.x, wbase + kWave + lane, last_word, end_byte);
+      win[lane] = smm_grib::load_word(a.x, wbase + lane, last_word, end_byte);
+      win[lane + kWave] = smm_grib::load_word(a.x, wbase + kWave + lane, last_word, end_byte);
       have_win = true;
       __syncthreads();
     }
@@ -134,12 +133,7 @@ __global__ __launch_bounds__(kWave) void smm_grib_aec_parse_kernel(AecArgs a, in
           chunk = wpeek(p + cb, (int)take) << (32u - take);
         }
         const uint32_t cnt = (uint32_t)__builtin_popcount(chunk);
-        uint32_t incl = cnt;
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-          const uint32_t t = __shfl_up(incl, o, kWave);
-          if ((int)lane >= o) incl += t;
-        }
+        const uint32_t incl = wave_scan(cnt);
         const uint32_t total = __shfl(incl, kWave - 1, kWave);
         if (total < nc) {   // the nc-th terminating one is not there
           status = p + limit > bit_end ? smm_aec::kExhausted : smm_aec::kInvalid;
@@ -196,10 +190,11 @@ __global__ __launch_bounds__(kWave) void smm_grib_aec_parse_kernel(AecArgs a, in
 // samples are a serial recurrence from its reference sample on.  A tile of 64 intervals x kTile samples is loaded with
 // lanes running along the samples (16 consecutive words per interval), walked by the lanes along the intervals, and
 // stored back the way it came.  A row without the preprocessor has nothing to invert.
-__global__ __launch_bounds__(kWave) void smm_grib_aec_inverse_kernel(AecArgs a, int64_t j0, uint32_t groups_per_row) {
+__global__ __launch_bounds__(kWave) void smm_grib_aec_inverse_kernel(AecArgs a, int64_t b0, uint32_t per_row) {
   __shared__ uint32_t tile[kWave][kTile + 1];
-  const int64_t j = j0 + blockIdx.x / groups_per_row;
-  const uint32_t g = blockIdx.x % groups_per_row, lane = threadIdx.x;
+  const RowPart at = row_part(b0, per_row);
+  const int64_t j = at.j;
+  const uint32_t g = at.part, lane = threadIdx.x;
   const AecRow* __restrict__ rows = a.rows;
   const AecRow r = rows[j];
   if (r.nbits == 0 || r.preprocess == 0u) return;
@@ -207,7 +202,7 @@ __global__ __launch_bounds__(kWave) void smm_grib_aec_inverse_kernel(AecArgs a, 
   const uint64_t first = (uint64_t)g * kWave * span;                           // the group's first sample
   if (first >= n) return;
   uint32_t* __restrict__ sc = a.scratch + r.scratch_off;
-  const uint32_t xmax = smm_aec::sample_max(r.nbits);
+  const uint32_t xmax = smm_grib::sample_max(r.nbits);
   const uint64_t mine = first + (uint64_t)lane * span;   // the lane's interval starts here
   uint32_t xp = 0;
   for (uint32_t t0 = 0; t0 < span; t0 += kTile) {
@@ -239,47 +234,22 @@ __global__ __launch_bounds__(kWave) void smm_grib_aec_inverse_kernel(AecArgs a, 
 // ---- 3: store.  One thread per 32-bit word of the row's stream (the grid covers the widest row; a narrower row's
 // surplus threads leave): the samples that overlap the word, each cut to the row's width, put in place as
 // smm_grib_codec.hpp's grib_word_part has it.  Words the samples do not reach are stored as zero.
-__global__ __launch_bounds__(kStoreThreads) void smm_grib_aec_store_kernel(AecArgs a, int64_t j0, uint32_t blocks_per_row) {
-  const int64_t j = j0 + blockIdx.x / blocks_per_row;
-  const uint32_t w = (blockIdx.x % blocks_per_row) * kStoreThreads + threadIdx.x;
+__global__ __launch_bounds__(kStoreThreads) void smm_grib_aec_store_kernel(AecArgs a, int64_t b0, uint32_t per_row) {
+  const RowPart at = row_part(b0, per_row);
   const AecRow* __restrict__ rows = a.rows;
-  const AecRow r = rows[j];
-  if (r.nbits == 0) return;
-  const uint32_t n_words = (uint32_t)(smm_grib::align4(smm_grib::row_bytes(r.n_values, r.nbits)) >> 2);
-  if (w >= n_words) return;
+  const AecRow r = rows[at.j];
   const uint32_t* __restrict__ sc = a.scratch + r.scratch_off;
-  const uint32_t xmax = smm_aec::sample_max(r.nbits);
-  uint64_t i = 0, end = 0;
-  smm_grib::grib_word_values(w, r.nbits, r.n_values, &i, &end);
-  uint32_t word = 0;
-  for (; i < end; ++i) word |= smm_grib::grib_word_part(sc[i] & xmax, i, r.nbits, w);
-  a.out[(r.out_off >> 2) + w] = __builtin_bswap32(word);
+  const uint32_t xmax = smm_grib::sample_max(r.nbits);
+  store_row_word(a.out, r.out_off, at.part * kStoreThreads + threadIdx.x, r.nbits, r.n_values,
+                 [&](uint64_t i) { return sc[i] & xmax; });
 }
 
+// the widest row of the call takes max_groups workgroups of the inverse kernel and max_words words of the store
 int launch_aec(const AecArgs& a, int64_t n_j, uint32_t max_groups, uint32_t max_words, hipStream_t s) {
-  const int64_t limit = std::min<int64_t>(std::max<int64_t>(grid_limit(), 1), 0x7fffffffLL);
   const uint32_t blocks_per_row = (max_words + kStoreThreads - 1) / kStoreThreads;
-  const int64_t per_row = std::max<int64_t>(std::max<int64_t>(blocks_per_row, max_groups), 1);
-  if (per_row > limit)
-    return fail(SMM_ERR_INVALID, "one row alone needs a launch grid beyond " + std::to_string(limit) + " workgroups");
-  const int64_t rows_per = limit / per_row;
-  for (int64_t j0 = 0; j0 < n_j; j0 += limit) {
-    const int64_t nr = std::min(limit, n_j - j0);
-    hipLaunchKernelGGL(smm_grib_aec_parse_kernel, dim3((unsigned)nr), dim3(kWave), 0, s, a, j0);
-    SMM_HIP(hipGetLastError());
-  }
-  for (int64_t j0 = 0; j0 < n_j && max_groups > 0; j0 += rows_per) {
-    const int64_t nr = std::min(rows_per, n_j - j0);
-    hipLaunchKernelGGL(smm_grib_aec_inverse_kernel, dim3((unsigned)(nr * max_groups)), dim3(kWave), 0, s, a, j0, max_groups);
-    SMM_HIP(hipGetLastError());
-  }
-  for (int64_t j0 = 0; j0 < n_j && blocks_per_row > 0; j0 += rows_per) {
-    const int64_t nr = std::min(rows_per, n_j - j0);
-    hipLaunchKernelGGL(smm_grib_aec_store_kernel, dim3((unsigned)(nr * blocks_per_row)), dim3(kStoreThreads), 0, s, a, j0,
-                       blocks_per_row);
-    SMM_HIP(hipGetLastError());
-  }
-  return SMM_OK;
+  if (int rc = launch_flat(smm_grib_aec_parse_kernel, kWave, n_j, s, a)) return rc;
+  if (int rc = launch_flat(smm_grib_aec_inverse_kernel, kWave, n_j * max_groups, s, a, max_groups)) return rc;
+  return launch_flat(smm_grib_aec_store_kernel, kStoreThreads, n_j * blocks_per_row, s, a, blocks_per_row);
 }
 
 // everything the two entries with records refuse about them
@@ -314,28 +284,18 @@ int smm_grib_aec_unpack_impl(int device, const void* x, const smm_grib_aec_t* re
     }
   }
   if (samples == 0) return SMM_OK;
-  DeviceGuard guard(device);
-  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the device");
-  hipStream_t s = (hipStream_t)stream;
-  auto align8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
-  const size_t table_bytes = n * sizeof(AecRow), status_bytes = align8(n * sizeof(int32_t));
-  DeviceBuf<char> d;   // table, statuses, scratch
-  SMM_HIP(d.alloc(table_bytes + status_bytes + (size_t)samples * sizeof(uint32_t)));
-  SMM_HIP(hipMemcpyAsync(d.get(), table.data(), table_bytes, hipMemcpyHostToDevice, s));
-  AecArgs a{x, (const AecRow*)d.get(), (uint32_t*)(d.get() + table_bytes + status_bytes), (uint32_t*)out,
-            (int32_t*)(d.get() + table_bytes)};
+  Arena arena;
+  const size_t table_at = arena.add<AecRow>(n), status_at = arena.add<int32_t>(n), scratch_at = arena.add<uint32_t>(samples);
   std::vector<int32_t> status(n, smm_aec::kOk);
-  int rc = launch_aec(a, n_batch, max_groups, max_words, s);
-  if (rc == SMM_OK) {
-    const hipError_t e = hipMemcpyAsync(status.data(), a.status, n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) rc = fail(SMM_ERR_HIP, std::string("copying the rows' statuses: ") + hipGetErrorString(e));
-  }
-  const hipError_t e = hipStreamSynchronize(s);   // the table and the scratch are in use until here
-  if (rc != SMM_OK) {
-    (void)hipGetLastError();
+  if (int rc = run_transcode(
+          device, stream, arena.bytes(), {Span{table_at, table.data(), n * sizeof(AecRow)}},
+          [&](char* d, hipStream_t s) {
+            const AecArgs a{x, Arena::at<AecRow>(d, table_at), Arena::at<uint32_t>(d, scratch_at), (uint32_t*)out,
+                            Arena::at<int32_t>(d, status_at)};
+            return launch_aec(a, n_batch, max_groups, max_words, s);
+          },
+          Span{status_at, status.data(), n * sizeof(int32_t)}, "statuses"))
     return rc;
-  }
-  SMM_HIP(e);
   for (size_t b = 0; b < n; ++b)
     if (status[b] != smm_aec::kOk)
       return fail(SMM_ERR_INVALID, "recs[" + std::to_string(b) + "]: the CCSDS stream " +
@@ -348,34 +308,19 @@ int smm_grib_aec_unpack_impl(int device, const void* x, const smm_grib_aec_t* re
 extern "C" {
 
 int smm_grib_aec_layout(const smm_grib_aec_t* recs, int64_t n_batch, uint64_t* byte_off, uint64_t* total_bytes) {
-  return guarded([&] {
-    if (!total_bytes) return fail(SMM_ERR_INVALID, "null total pointer");
-    if (int rc = check_aec_records(recs, n_batch, INT64_MAX)) return rc;
-    *total_bytes = smm::grib_aec_layout(recs, n_batch, byte_off);
-    return (int)SMM_OK;
-  });
+  return offsets_entry(
+      recs, n_batch, byte_off, total_bytes, [](const smm_grib_aec_t* r, int64_t n) { return check_aec_records(r, n, INT64_MAX); },
+      smm::grib_aec_layout);
 }
 
 int smm_grib_aec_unpack(int device, const void* x, int64_t x_bytes, const smm_grib_aec_t* recs, const smm_grib_row_t* rows_in,
                         int64_t n_batch, void* out, int64_t out_bytes, smm_grib_row_t* rows_out, void* stream) {
   return guarded([&] {
     if (int rc = check_aec_records(recs, n_batch, x_bytes)) return rc;
-    if (n_batch > 0 && (!rows_in || !rows_out)) return fail(SMM_ERR_INVALID, "null row-table pointer");
-    if (out_bytes < 0) return fail(SMM_ERR_INVALID, "negative out_bytes");
-    std::vector<uint64_t> offs((size_t)n_batch + 1);
-    offs[(size_t)n_batch] = smm::grib_aec_layout(recs, n_batch, offs.data());
-    bool streams = false;
-    for (int64_t b = 0; b < n_batch; ++b) {
-      if (rows_in[b].nbits != recs[b].nbits)
-        return fail(SMM_ERR_INVALID, "rows_in[" + std::to_string(b) + "].nbits differs from recs[" + std::to_string(b) + "].nbits");
-      streams = streams || (recs[b].nbits != 0 && recs[b].n_values != 0);
-    }
-    if ((uint64_t)out_bytes < offs[(size_t)n_batch])
-      return fail(SMM_ERR_INVALID, "out_bytes " + std::to_string(out_bytes) + " is below the layout's " +
-                                       std::to_string(offs[(size_t)n_batch]) + " bytes");
-    if (streams && (!x || !out)) return fail(SMM_ERR_INVALID, "null field or output pointer");
-    if ((uintptr_t)x % 4) return fail(SMM_ERR_INVALID, "field pointer is not 4-byte aligned");
-    if ((uintptr_t)out % 4) return fail(SMM_ERR_INVALID, "output pointer is not 4-byte aligned");
+    std::vector<uint64_t> offs;
+    if (int rc = check_unpack_call(x, recs, rows_in, n_batch, out, out_bytes, rows_out, offs, smm::grib_aec_layout,
+                                   [&](int64_t b) { return check_row_width(rows_in, recs, b); }))
+      return rc;
     return smm_grib_aec_unpack_impl(device, x, recs, rows_in, n_batch, out, offs.data(), rows_out, stream);
   });
 }

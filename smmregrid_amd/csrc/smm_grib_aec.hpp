@@ -1,8 +1,8 @@
 // CCSDS 121.0-B adaptive entropy coding as GRIB-2 data representation template 5.42 carries it (what libaec writes
 // for ecCodes): the decoder and the encoder, each stated once.  Plain C++ that compiles for host and device -- the host
 // decode (smm_grib_aec_decode_host), the kernels of smm_grib_aec_unpack (smm_grib_aec.hip) and
-// tests/cpp/grib_aec_harness.cpp all read the stream through load_word / bits_of and take the options apart with the
-// small functions below; the host encode (smm_grib_aec_encode_host), the kernels of smm_grib_aec_pack
+// tests/cpp/grib_aec_harness.cpp all read the stream through smm_grib_codec.hpp's load_word / bits_of and take the
+// options apart with the small functions below; the host encode (smm_grib_aec_encode_host), the kernels of smm_grib_aec_pack
 // (smm_grib_aec_pack.hip) and tests/cpp/grib_aec_encode_harness.cpp put them together with the ones behind decode_row.
 //
 // THE FORMAT, for unsigned samples of nbits (1..32) bits, blocks of J (8 / 16 / 32 / 64) samples, a reference sample
@@ -68,30 +68,6 @@ static_assert(kNumOptions == SMM_GRIB_AEC_OPTIONS, "one bin per coding option");
 constexpr uint32_t kRos = 5, kSegmentBlocks = 64, kMaxSecondExt = 90, kMaxZeroFsBits = 65;
 
 SMM_GRIB_HD int id_len(int nbits) { return nbits > 16 ? 5 : nbits > 8 ? 4 : 3; }
-SMM_GRIB_HD uint32_t sample_max(int nbits) { return nbits >= 32 ? 0xffffffffu : (1u << nbits) - 1u; }
-
-// Word i of x as the big-endian number it holds, i clamped to last_word.  The device loads the aligned word (the
-// allocation covers x_bytes rounded up to 4); the host takes it byte by byte from any address and reads no byte at or
-// beyond end_byte (they count as zero).
-SMM_GRIB_HD uint32_t load_word(const void* x, uint64_t i, uint64_t last_word, uint64_t end_byte) {
-  const uint64_t w = i < last_word ? i : last_word;
-#if defined(__HIP_DEVICE_COMPILE__)
-  (void)end_byte;
-  return __builtin_bswap32(((const uint32_t*)x)[w]);
-#else
-  const uint8_t* p = (const uint8_t*)x;
-  uint32_t v = 0;
-  for (uint64_t k = 4 * w; k < 4 * w + 4; ++k) v = (v << 8) | (k < end_byte ? (uint32_t)p[k] : 0u);
-  return v;
-#endif
-}
-// the n (0..32) bits at bit `off` (0..31) of the 64 bits hi:lo
-SMM_GRIB_HD uint32_t bits_of(uint32_t hi, uint32_t lo, unsigned off, int n) {
-  const uint64_t both = ((uint64_t)hi << 32) | lo;
-  const unsigned shift = (unsigned)(64 - (int)off - n) & 63u;
-  return (uint32_t)(both >> shift) & (uint32_t)((1ull << n) - 1ull);
-}
-
 // blocks of a zero run from its FS value, at block b of the RSI (b < rsi)
 SMM_GRIB_HD uint32_t zero_run_blocks(uint32_t fs, uint32_t b, uint32_t rsi, bool* ros) {
   const uint32_t n = fs + 1;
@@ -139,7 +115,8 @@ struct Reader {
 
   SMM_GRIB_HD uint32_t peek(uint64_t p, int n) const {
     const uint64_t w = p >> 5;
-    return bits_of(load_word(x, w, last_word, end_byte), load_word(x, w + 1, last_word, end_byte), (unsigned)(p & 31), n);
+    return smm_grib::bits_of(smm_grib::load_word(x, w, last_word, end_byte), smm_grib::load_word(x, w + 1, last_word, end_byte),
+                             (unsigned)(p & 31), n);
   }
   // n (0..32) bits; 0 once the row has ended
   SMM_GRIB_HD uint32_t get(int n) {
@@ -190,7 +167,7 @@ SMM_GRIB_HD Reader make_reader(const void* x, const Row& r) {
 SMM_GRIB_HD int decode_row(const void* x, const Row& r, uint32_t* out, uint64_t* hist) {
   const uint32_t n = r.n_values, J = (uint32_t)r.block, rsi = (uint32_t)r.rsi;
   const int idl = id_len(r.nbits);
-  const uint32_t id_raw = (1u << idl) - 1u, xmax = sample_max(r.nbits), block_bits = J * (uint32_t)r.nbits;
+  const uint32_t id_raw = (1u << idl) - 1u, xmax = smm_grib::sample_max(r.nbits), block_bits = J * (uint32_t)r.nbits;
   Reader rd = make_reader(x, r);
   if (n == 0) return kOk;
   uint32_t at = 0, b = 0;
@@ -374,7 +351,7 @@ template <class Q>
 SMM_GRIB_HD uint64_t encode_row(Q&& q, const Row& r, uint8_t* out, uint64_t cap_bytes, uint64_t* hist) {
   const uint32_t n = r.n_values, J = (uint32_t)r.block, rsi = (uint32_t)r.rsi, span = J * rsi;
   const int idl = id_len(r.nbits);
-  const uint32_t xmax = sample_max(r.nbits), nb = row_blocks(n, J);
+  const uint32_t xmax = smm_grib::sample_max(r.nbits), nb = row_blocks(n, J);
   Writer w{out, 8 * cap_bytes, 0, true};
   uint32_t s[kSegmentBlocks];   // J <= 64 symbols
   auto load = [&](uint32_t blk, bool ref) {   // the block's symbols; are its coded ones all zero

@@ -14,16 +14,15 @@
 //   emit    a workgroup per segment assembles its bits in LDS (a lane per sample again; the symbols are recomputed, two
 //           extracts from lines the cost kernel just read, rather than kept in 4 B per sample of scratch that would be
 //           written and read once each), stores the whole words big-endian and ORs the two shared ones onto the zeros
-// Vector stores and vector atomics (LDS and global OR) only.  OR commutes: the bytes do not depend on the order.
-#include "smm_device.hpp"
-
-#include <algorithm>
+// Vector stores and vector atomics (LDS and global OR) only.  OR commutes: the bytes do not depend on the order.  The
+// row's input (RowBits), the scans, the LDS window (win_put / win_flush / zero_ends), the cut launches, the host shell
+// and the entry checks are smm_grib_xcode.hpp's, shared with the other transcoders.
+#include "smm_grib_xcode.hpp"
 
 #include "smm_grib_aec.hpp"
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kPackThreads = 256;
 constexpr uint32_t kSeg = smm_aec::kSegmentBlocks;
 // the emit kernel's window: a segment of 64 blocks of 5 + 1 + 32 + 64 * 32 bits, begun anywhere in a word
@@ -52,17 +51,8 @@ struct PackArgs {
 };
 
 // the row's samples, read from its simple-packed stream
-struct RowBits {
-  const uint32_t* words;
-  uint32_t bit0, last;
-  int nbits;
-  __device__ __forceinline__ uint32_t operator()(uint32_t i) const {
-    return smm_grib::grib_extract(words, (uint64_t)bit0 + (uint64_t)i * (uint32_t)nbits, nbits, last);
-  }
-};
 __device__ __forceinline__ RowBits row_bits(const PackArgs& a, const PackRow& r) {
-  const uint64_t w = std::min<uint64_t>(r.in_off >> 2, a.last_word);
-  return RowBits{a.x + w, 8u * (uint32_t)(r.in_off & 3), (uint32_t)std::min<uint64_t>(a.last_word - w, 0xfffffffeull), r.nbits};
+  return row_bits(a.x, a.last_word, r.in_off, r.nbits);
 }
 // where segment s of the row begins and how many blocks it has: block `first` of the row = block b0 of its RSI;
 // `full` blocks to the segment's or the RSI's end, `cnt` of them inside the data
@@ -82,11 +72,11 @@ __device__ __forceinline__ uint32_t group_sum(uint32_t v, uint32_t J) {
 // ---- 1: cost.  Workgroup (row, c) takes samples [256 c, 256 c + 256) of the row's blocks; 256 and 64 are multiples of
 // J, so a block lies in one wave and a group of J lanes is valid or surplus as a whole (surplus lanes redo block 0 and
 // store nothing: the shuffles stay whole).
-__global__ __launch_bounds__(kPackThreads) void smm_grib_aec_cost_kernel(PackArgs a, int64_t j0, uint32_t chunks_per_row) {
-  const int64_t j = j0 + blockIdx.x / chunks_per_row;
-  const uint32_t chunk = blockIdx.x % chunks_per_row;
+__global__ __launch_bounds__(kPackThreads) void smm_grib_aec_cost_kernel(PackArgs a, int64_t b0, uint32_t per_row) {
+  const RowPart at = row_part(b0, per_row);
+  const uint32_t chunk = at.part;
   const PackRow* __restrict__ rows = a.rows;
-  const PackRow r = rows[j];
+  const PackRow r = rows[at.j];
   if (r.nbits == 0) return;
   const uint32_t J = (uint32_t)r.block, total = r.n_blocks * J;   // < 2^31 + 64
   if ((uint64_t)chunk * kPackThreads >= total) return;
@@ -94,7 +84,7 @@ __global__ __launch_bounds__(kPackThreads) void smm_grib_aec_cost_kernel(PackArg
   const bool valid = t < total;
   const uint32_t i = valid ? t : threadIdx.x % J, p = i % J, blk = i / J;
   const bool pp = r.preprocess != 0u, ref = pp && blk % (uint32_t)r.rsi == 0u, coded = !(ref && p == 0u);
-  const uint32_t xmax = smm_aec::sample_max(r.nbits);
+  const uint32_t xmax = smm_grib::sample_max(r.nbits);
   const uint32_t d = smm_aec::symbol(row_bits(a, r), i, r.n_values, J * (uint32_t)r.rsi, pp, xmax);
   const uint32_t dz = coded ? d : 0u;
   // the pairs of the second extension sit on the even lanes: (dz, the next lane's symbol)
@@ -113,12 +103,12 @@ __global__ __launch_bounds__(kPackThreads) void smm_grib_aec_cost_kernel(PackArg
 
 // ---- 2: scan.  A wave per segment, four to a workgroup.  Lane l holds block l of the segment; Z has a bit per zero
 // block.  A run starts where a zero block has no zero block before it in the segment, and runs as far as Z has ones.
-__global__ __launch_bounds__(kPackThreads) void smm_grib_aec_scan_kernel(PackArgs a, int64_t j0, uint32_t groups_per_row) {
-  const int64_t j = j0 + blockIdx.x / groups_per_row;
+__global__ __launch_bounds__(kPackThreads) void smm_grib_aec_scan_kernel(PackArgs a, int64_t b0, uint32_t per_row) {
+  const RowPart at = row_part(b0, per_row);
   const uint32_t lane = threadIdx.x % kWave;
-  const uint32_t s = (blockIdx.x % groups_per_row) * (kPackThreads / kWave) + threadIdx.x / kWave;
+  const uint32_t s = at.part * (kPackThreads / kWave) + threadIdx.x / kWave;
   const PackRow* __restrict__ rows = a.rows;
-  const PackRow r = rows[j];
+  const PackRow r = rows[at.j];
   if (r.nbits == 0 || s >= r.n_segs) return;   // the same in all lanes of a wave
   const SegGeom g = seg_geom(r, s);
   uint32_t* rec = a.blocks + 2 * (r.blk_off + g.first + lane);
@@ -134,55 +124,28 @@ __global__ __launch_bounds__(kPackThreads) void smm_grib_aec_scan_kernel(PackArg
     const bool ref = r.preprocess != 0u && g.b0 + lane == 0u;
     bits = (uint32_t)smm_aec::id_len(r.nbits) + 1u + (ref ? (uint32_t)r.nbits : 0u) + fs + 1u;
   }
-  uint32_t incl = bits;
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const uint32_t up = __shfl_up(incl, o, kWave);
-    if ((int)lane >= o) incl += up;
-  }
+  const uint32_t incl = wave_scan(bits);
   if (lane < g.cnt) rec[1] = (incl - bits) | (fs << 20);   // < 64 * 2086 < 2^20
   if (lane == kWave - 1) a.seg_bits[r.seg_off + s] = incl;
 }
 
 // ---- 3: rows.  A wave per row: the exclusive scan of its segments' bits, 64 at a step, and the row's bytes.
-__global__ __launch_bounds__(kWave) void smm_grib_aec_rows_kernel(PackArgs a, int64_t j0) {
-  const int64_t j = j0 + blockIdx.x;
-  const uint32_t lane = threadIdx.x;
+__global__ __launch_bounds__(kWave) void smm_grib_aec_rows_kernel(PackArgs a, int64_t b0) {
+  const int64_t j = b0 + blockIdx.x;
   const PackRow* __restrict__ rows = a.rows;
   const PackRow r = rows[j];
-  unsigned long long carry = 0;
-  for (uint32_t s0 = 0; s0 < r.n_segs; s0 += kWave) {
-    const uint32_t s = s0 + lane;
-    const unsigned long long v = s < r.n_segs ? a.seg_bits[r.seg_off + s] : 0ull;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const unsigned long long up = __shfl_up(incl, o, kWave);
-      if ((int)lane >= o) incl += up;
-    }
-    if (s < r.n_segs) a.seg_at[r.seg_off + s] = carry + incl - v;
-    carry += __shfl(incl, kWave - 1, kWave);
-  }
-  if (lane == 0) a.row_out[2 * j + 1] = (carry + 7) / 8;
+  const uint64_t bits = scan_parts<uint64_t>(
+      r.n_segs, [&](uint32_t s) { return (uint64_t)a.seg_bits[r.seg_off + s]; },
+      [&](uint32_t s, uint64_t before) { a.seg_at[r.seg_off + s] = before; });
+  if (threadIdx.x == 0) a.row_out[2 * j + 1] = (bits + 7) / 8;
 }
 
 // ---- 4: layout.  One wave: rows back to back in row order, each at a 4-byte-aligned offset.
 __global__ __launch_bounds__(kWave) void smm_grib_aec_layout_kernel(PackArgs a, int64_t n_j) {
-  const uint32_t lane = threadIdx.x;
-  unsigned long long carry = 0;
-  for (int64_t b0 = 0; b0 < n_j; b0 += kWave) {
-    const int64_t b = b0 + lane;
-    const unsigned long long v = b < n_j ? smm_grib::align4(a.row_out[2 * b + 1]) : 0ull;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const unsigned long long up = __shfl_up(incl, o, kWave);
-      if ((int)lane >= o) incl += up;
-    }
-    if (b < n_j) a.row_out[2 * b] = carry + incl - v;
-    carry += __shfl(incl, kWave - 1, kWave);
-  }
-  if (lane == 0) a.row_out[2 * n_j] = carry;
+  const uint64_t used = scan_parts<uint64_t>(
+      n_j, [&](int64_t b) { return smm_grib::align4(a.row_out[2 * b + 1]); },
+      [&](int64_t b, uint64_t before) { a.row_out[2 * b] = before; });
+  if (threadIdx.x == 0) a.row_out[2 * n_j] = used;
 }
 
 // the segment's first bit in out, counted from out's first bit
@@ -193,30 +156,22 @@ __device__ __forceinline__ uint64_t seg_first_bit(const PackArgs& a, const PackR
 // ---- 5: edges.  The first and the last word of a segment's stream may hold bits of its neighbours in the row (a row
 // begins and ends on a word of its own): they are zeroed here and ORed into by the emit kernel.  A segment has at least
 // the bits of one ID.
-__global__ __launch_bounds__(kPackThreads) void smm_grib_aec_edges_kernel(PackArgs a, int64_t j0, uint32_t groups_per_row) {
-  const int64_t j = j0 + blockIdx.x / groups_per_row;
-  const uint32_t s = (blockIdx.x % groups_per_row) * kPackThreads + threadIdx.x;
+__global__ __launch_bounds__(kPackThreads) void smm_grib_aec_edges_kernel(PackArgs a, int64_t b0, uint32_t per_row) {
+  const RowPart at = row_part(b0, per_row);
+  const uint32_t s = at.part * kPackThreads + threadIdx.x;
   const PackRow* __restrict__ rows = a.rows;
-  const PackRow r = rows[j];
+  const PackRow r = rows[at.j];
   if (r.nbits == 0 || s >= r.n_segs) return;
-  const uint64_t first = seg_first_bit(a, r, j, s), last = first + a.seg_bits[r.seg_off + s] - 1;
-  if ((first >> 5) < a.out_words) a.out[first >> 5] = 0u;
-  if ((last >> 5) < a.out_words) a.out[last >> 5] = 0u;
+  const uint64_t first = seg_first_bit(a, r, at.j, s);
+  zero_ends(a.out, a.out_words, first, first + a.seg_bits[r.seg_off + s]);
 }
 
-// ---- 6: emit.  A workgroup per segment.  The window's word 0 is the word of out that holds the segment's first bit.
-// n (1..32) bits at bit `at` of the window; nothing goes past its n_words words.
-__device__ __forceinline__ void win_put(uint32_t* win, uint32_t n_words, uint32_t at, uint32_t v, uint32_t n) {
-  const uint32_t w = at >> 5;
-  const uint64_t both = (uint64_t)v << (64u - (at & 31u) - n);   // the shift is 1..63
-  const uint32_t hi = (uint32_t)(both >> 32), lo = (uint32_t)both;
-  if (hi != 0u && w < n_words) atomicOr(&win[w], hi);
-  if (lo != 0u && w + 1u < n_words) atomicOr(&win[w + 1u], lo);
-}
-__global__ __launch_bounds__(kPackThreads) void smm_grib_aec_emit_kernel(PackArgs a, int64_t j0, uint32_t segs_per_row) {
+// ---- 6: emit.  A workgroup per segment, its bits in one window.
+__global__ __launch_bounds__(kPackThreads) void smm_grib_aec_emit_kernel(PackArgs a, int64_t b0, uint32_t per_row) {
   __shared__ uint32_t win[kWinWords];
-  const int64_t j = j0 + blockIdx.x / segs_per_row;
-  const uint32_t s = blockIdx.x % segs_per_row, tid = threadIdx.x;
+  const RowPart where = row_part(b0, per_row);
+  const int64_t j = where.j;
+  const uint32_t s = where.part, tid = threadIdx.x;
   const PackRow* __restrict__ rows = a.rows;
   const PackRow r = rows[j];
   if (r.nbits == 0 || s >= r.n_segs) return;
@@ -227,7 +182,7 @@ __global__ __launch_bounds__(kPackThreads) void smm_grib_aec_emit_kernel(PackArg
   for (uint32_t w = tid; w < n_words; w += kPackThreads) win[w] = 0u;
   __syncthreads();
   const uint32_t J = (uint32_t)r.block, nbits = (uint32_t)r.nbits, idl = (uint32_t)smm_aec::id_len(r.nbits);
-  const uint32_t xmax = smm_aec::sample_max(r.nbits), total = g.cnt * J;   // <= 4096
+  const uint32_t xmax = smm_grib::sample_max(r.nbits), total = g.cnt * J;   // <= 4096
   const bool pp = r.preprocess != 0u;
   const RowBits q = row_bits(a, r);
   for (uint32_t base = 0; base < total; base += kPackThreads) {
@@ -247,11 +202,7 @@ __global__ __launch_bounds__(kPackThreads) void smm_grib_aec_emit_kernel(PackArg
     uint32_t len = 0;
     if (split && coded) len = (d >> k) + 1u;
     if (second && (p & 1u) == 0u) len = smm_aec::second_ext_value(coded ? d : 0u, next) + 1u;
-    uint32_t incl = len;
-    for (uint32_t o = 1; o < J; o <<= 1) {
-      const uint32_t up = __shfl_up(incl, o, kWave);
-      if (p >= o) incl += up;
-    }
+    const uint32_t incl = group_scan(len, J);   // p == the lane's place among its J
     const uint32_t fs_total = __shfl(incl, (int)(J - 1u), (int)J);
     if (!valid) continue;
     const bool low = option == smm_aec::kEncZero || second;   // ID 0 and a selector bit
@@ -271,57 +222,21 @@ __global__ __launch_bounds__(kPackThreads) void smm_grib_aec_emit_kernel(PackArg
     if (split && coded && k != 0u) win_put(win, n_words, hdr + fs_total + (p - nref) * k, d & ((1u << k) - 1u), k);
   }
   __syncthreads();
-  for (uint32_t w = tid; w < n_words; w += kPackThreads) {
-    const uint64_t at = w0 + w;
-    if (at >= a.out_words) continue;
-    const uint32_t word = __builtin_bswap32(win[w]);
-    if (w == 0u || w == n_words - 1u)
-      atomicOr(&a.out[at], word);
-    else
-      a.out[at] = word;
-  }
+  win_flush<kPackThreads>(a.out, a.out_words, win, n_words, w0, tid);
 }
 
-// Launch grids are cut at the workgroup limit: rows_per rows of per_row workgroups at a time.
-template <class L>
-int launch_rows(int64_t n_j, int64_t per_row, int64_t limit, L&& launch) {
-  if (per_row <= 0) return SMM_OK;
-  if (per_row > limit)
-    return fail(SMM_ERR_INVALID, "one row alone needs a launch grid beyond " + std::to_string(limit) + " workgroups");
-  const int64_t rows_per = limit / per_row;
-  for (int64_t j0 = 0; j0 < n_j; j0 += rows_per) {
-    launch(j0, (unsigned)(std::min(rows_per, n_j - j0) * per_row));
-    SMM_HIP(hipGetLastError());
-  }
-  return SMM_OK;
-}
-
+// the widest row of the call has max_samples samples in whole blocks and max_segs segments
 int launch_aec_pack(const PackArgs& a, int64_t n_j, uint32_t max_samples, uint32_t max_segs, hipStream_t s) {
-  const int64_t limit = std::min<int64_t>(std::max<int64_t>(grid_limit(), 1), 0x7fffffffLL);
   const uint32_t chunks = (uint32_t)(((uint64_t)max_samples + kPackThreads - 1) / kPackThreads);
   const uint32_t scan_groups = (max_segs + kPackThreads / kWave - 1) / (kPackThreads / kWave);
   const uint32_t edge_groups = (max_segs + kPackThreads - 1) / kPackThreads;
-  if (int rc = launch_rows(n_j, chunks, limit, [&](int64_t j0, unsigned grid) {
-        hipLaunchKernelGGL(smm_grib_aec_cost_kernel, dim3(grid), dim3(kPackThreads), 0, s, a, j0, chunks);
-      }))
-    return rc;
-  if (int rc = launch_rows(n_j, scan_groups, limit, [&](int64_t j0, unsigned grid) {
-        hipLaunchKernelGGL(smm_grib_aec_scan_kernel, dim3(grid), dim3(kPackThreads), 0, s, a, j0, scan_groups);
-      }))
-    return rc;
-  if (int rc = launch_rows(n_j, 1, limit, [&](int64_t j0, unsigned grid) {
-        hipLaunchKernelGGL(smm_grib_aec_rows_kernel, dim3(grid), dim3(kWave), 0, s, a, j0);
-      }))
-    return rc;
+  if (int rc = launch_flat(smm_grib_aec_cost_kernel, kPackThreads, n_j * chunks, s, a, chunks)) return rc;
+  if (int rc = launch_flat(smm_grib_aec_scan_kernel, kPackThreads, n_j * scan_groups, s, a, scan_groups)) return rc;
+  if (int rc = launch_flat(smm_grib_aec_rows_kernel, kWave, n_j, s, a)) return rc;
   hipLaunchKernelGGL(smm_grib_aec_layout_kernel, dim3(1), dim3(kWave), 0, s, a, n_j);
   SMM_HIP(hipGetLastError());
-  if (int rc = launch_rows(n_j, edge_groups, limit, [&](int64_t j0, unsigned grid) {
-        hipLaunchKernelGGL(smm_grib_aec_edges_kernel, dim3(grid), dim3(kPackThreads), 0, s, a, j0, edge_groups);
-      }))
-    return rc;
-  return launch_rows(n_j, max_segs, limit, [&](int64_t j0, unsigned grid) {
-    hipLaunchKernelGGL(smm_grib_aec_emit_kernel, dim3(grid), dim3(kPackThreads), 0, s, a, j0, max_segs);
-  });
+  if (int rc = launch_flat(smm_grib_aec_edges_kernel, kPackThreads, n_j * edge_groups, s, a, edge_groups)) return rc;
+  return launch_flat(smm_grib_aec_emit_kernel, kPackThreads, n_j * max_segs, s, a, max_segs);
 }
 
 // What the entries with "wanted" records refuse about them: everything smm_grib_aec_unpack refuses, the place of the
@@ -342,12 +257,8 @@ int check_pack_records(const smm_grib_aec_t* recs, int64_t n_batch) {
 }
 
 uint64_t pack_bound(const smm_grib_aec_t* recs, int64_t n_batch, uint64_t* byte_off) {
-  uint64_t at = 0;
-  for (int64_t b = 0; b < n_batch; ++b) {
-    if (byte_off) byte_off[b] = at;
-    at += smm_aec::pack_bound_bytes(recs[b].n_values, recs[b].nbits, recs[b].block_size);
-  }
-  return at;
+  return sum_rows(recs, n_batch, byte_off,
+                  [](const smm_grib_aec_t& c) { return smm_aec::pack_bound_bytes(c.n_values, c.nbits, c.block_size); });
 }
 
 int smm_grib_aec_pack_impl(int device, const void* x, int64_t x_bytes, const smm_grib_row_t* rows_in, const smm_grib_aec_t* recs,
@@ -381,39 +292,27 @@ int smm_grib_aec_pack_impl(int device, const void* x, int64_t x_bytes, const smm
   }
   *used_bytes = 0;
   if (n == 0) return SMM_OK;
-  DeviceGuard guard(device);
-  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the device");
-  hipStream_t s = (hipStream_t)stream;
-  auto align8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
-  const size_t table_bytes = n * sizeof(PackRow), rowout_bytes = (2 * n + 1) * sizeof(uint64_t);
-  const size_t segat_bytes = (size_t)segs * sizeof(uint64_t), blocks_bytes = (size_t)blocks * 2 * sizeof(uint32_t);
-  const size_t segbits_bytes = align8((size_t)segs * sizeof(uint32_t));
-  DeviceBuf<char> d;   // table, row results, segment offsets, block records, segment bits
-  SMM_HIP(d.alloc(table_bytes + rowout_bytes + segat_bytes + blocks_bytes + segbits_bytes));
-  SMM_HIP(hipMemcpyAsync(d.get(), table.data(), table_bytes, hipMemcpyHostToDevice, s));
-  char* at = d.get() + table_bytes;
-  PackArgs a{};
-  a.x = (const uint32_t*)x;
-  a.last_word = x_bytes > 0 ? smm_grib::align4((uint64_t)x_bytes) / 4 - 1 : 0;
-  a.rows = (const PackRow*)d.get();
-  a.row_out = (uint64_t*)at;
-  a.seg_at = (uint64_t*)(at += rowout_bytes);
-  a.blocks = (uint32_t*)(at += segat_bytes);
-  a.seg_bits = (uint32_t*)(at += blocks_bytes);
-  a.out = (uint32_t*)out;
-  a.out_words = (uint64_t)out_bytes / 4;
+  Arena arena;   // table, row results, segment offsets, block records, segment bits
+  const size_t table_at = arena.add<PackRow>(n), rowout_at = arena.add<uint64_t>(2 * n + 1), segat_at = arena.add<uint64_t>(segs),
+               blocks_at = arena.add<uint32_t>(2 * blocks), segbits_at = arena.add<uint32_t>(segs);
   std::vector<uint64_t> row_out(2 * n + 1, 0);
-  int rc = launch_aec_pack(a, n_batch, max_samples, max_segs, s);
-  if (rc == SMM_OK) {
-    const hipError_t e = hipMemcpyAsync(row_out.data(), a.row_out, rowout_bytes, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) rc = fail(SMM_ERR_HIP, std::string("copying the rows' places: ") + hipGetErrorString(e));
-  }
-  const hipError_t e = hipStreamSynchronize(s);   // the table and the scratch are in use until here
-  if (rc != SMM_OK) {
-    (void)hipGetLastError();
+  if (int rc = run_transcode(
+          device, stream, arena.bytes(), {Span{table_at, table.data(), n * sizeof(PackRow)}},
+          [&](char* d, hipStream_t s) {
+            PackArgs a{};
+            a.x = (const uint32_t*)x;
+            a.last_word = x_bytes > 0 ? smm_grib::align4((uint64_t)x_bytes) / 4 - 1 : 0;
+            a.rows = Arena::at<PackRow>(d, table_at);
+            a.row_out = Arena::at<uint64_t>(d, rowout_at);
+            a.seg_at = Arena::at<uint64_t>(d, segat_at);
+            a.blocks = Arena::at<uint32_t>(d, blocks_at);
+            a.seg_bits = Arena::at<uint32_t>(d, segbits_at);
+            a.out = (uint32_t*)out;
+            a.out_words = (uint64_t)out_bytes / 4;
+            return launch_aec_pack(a, n_batch, max_samples, max_segs, s);
+          },
+          Span{rowout_at, row_out.data(), (2 * n + 1) * sizeof(uint64_t)}, "places"))
     return rc;
-  }
-  SMM_HIP(e);
   for (size_t b = 0; b < n; ++b) {
     recs_out[b].byte_off = row_out[2 * b];
     recs_out[b].byte_len = row_out[2 * b + 1];
@@ -427,12 +326,7 @@ int smm_grib_aec_pack_impl(int device, const void* x, int64_t x_bytes, const smm
 extern "C" {
 
 int smm_grib_aec_pack_bound(const smm_grib_aec_t* recs, int64_t n_batch, uint64_t* byte_off, uint64_t* total_bytes) {
-  return guarded([&] {
-    if (!total_bytes) return fail(SMM_ERR_INVALID, "null total pointer");
-    if (int rc = check_pack_records(recs, n_batch)) return rc;
-    *total_bytes = pack_bound(recs, n_batch, byte_off);
-    return (int)SMM_OK;
-  });
+  return offsets_entry(recs, n_batch, byte_off, total_bytes, check_pack_records, pack_bound);
 }
 
 int smm_grib_aec_pack(int device, const void* x, int64_t x_bytes, const smm_grib_row_t* rows_in, const smm_grib_aec_t* recs,
@@ -440,29 +334,7 @@ int smm_grib_aec_pack(int device, const void* x, int64_t x_bytes, const smm_grib
                       void* stream) {
   return guarded([&] {
     if (int rc = check_pack_records(recs, n_batch)) return rc;
-    if (n_batch > 0 && (!rows_in || !recs_out)) return fail(SMM_ERR_INVALID, "null row-table or result pointer");
-    if (!used_bytes) return fail(SMM_ERR_INVALID, "null used_bytes pointer");
-    if (x_bytes < 0) return fail(SMM_ERR_INVALID, "negative x_bytes");
-    if (out_bytes < 0) return fail(SMM_ERR_INVALID, "negative out_bytes");
-    bool streams = false;
-    for (int64_t b = 0; b < n_batch; ++b) {
-      const std::string at = "rows_in[" + std::to_string(b) + "]";
-      if (rows_in[b].nbits != recs[b].nbits)
-        return fail(SMM_ERR_INVALID, at + ".nbits differs from recs[" + std::to_string(b) + "].nbits");
-      const uint64_t len = smm_grib::row_bytes(recs[b].n_values, recs[b].nbits);
-      if (len > 0 && (rows_in[b].byte_off > (uint64_t)x_bytes || len > (uint64_t)x_bytes - rows_in[b].byte_off))
-        return fail(SMM_ERR_INVALID, at + ": bytes [" + std::to_string(rows_in[b].byte_off) + ", " +
-                                         std::to_string(rows_in[b].byte_off) + " + " + std::to_string(len) +
-                                         ") leave the buffer of " + std::to_string(x_bytes) + " bytes");
-      streams = streams || len > 0;
-    }
-    const uint64_t bound = pack_bound(recs, n_batch, nullptr);
-    if ((uint64_t)out_bytes < bound)
-      return fail(SMM_ERR_INVALID, "out_bytes " + std::to_string(out_bytes) + " is below the bound of " + std::to_string(bound) +
-                                       " bytes");
-    if (streams && (!x || !out)) return fail(SMM_ERR_INVALID, "null field or output pointer");
-    if ((uintptr_t)x % 4) return fail(SMM_ERR_INVALID, "field pointer is not 4-byte aligned");
-    if ((uintptr_t)out % 4) return fail(SMM_ERR_INVALID, "output pointer is not 4-byte aligned");
+    if (int rc = check_pack_call(x, x_bytes, rows_in, recs, n_batch, out, out_bytes, recs_out, used_bytes, pack_bound)) return rc;
     return smm_grib_aec_pack_impl(device, x, x_bytes, rows_in, recs, n_batch, out, out_bytes, recs_out, used_bytes, stream);
   });
 }
@@ -481,7 +353,7 @@ int smm_grib_aec_encode_host(const uint32_t* values, int64_t n_values, const smm
     if ((uint64_t)out_cap < bound)
       return fail(SMM_ERR_INVALID, "out_cap " + std::to_string(out_cap) + " is below the bound of " + std::to_string(bound) + " bytes");
     if (!out) return fail(SMM_ERR_INVALID, "null output pointer");
-    const uint32_t xmax = smm_aec::sample_max(rec->nbits);
+    const uint32_t xmax = smm_grib::sample_max(rec->nbits);
     for (int64_t i = 0; i < n_values; ++i)
       if (values[i] > xmax) return fail(SMM_ERR_INVALID, "values[" + std::to_string(i) + "] does not fit into " + std::to_string(rec->nbits) + " bits");
     std::fill((uint8_t*)out, (uint8_t*)out + bound, (uint8_t)0);

@@ -37,6 +37,32 @@ SMM_GRIB_HD uint32_t grib_extract(const uint32_t* __restrict__ words, uint64_t p
   return (uint32_t)(both >> shift) & mask;
 }
 
+// ---- a byte range of x read as a bit stream that may begin and end at any byte: what the CCSDS and the complex-packed
+// decoders (smm_grib_aec.hpp, smm_grib_cpx.hpp) read their streams through.
+// the largest unsigned integer of nbits (0..32) bits
+SMM_GRIB_HD uint32_t sample_max(int nbits) { return nbits >= 32 ? 0xffffffffu : (1u << nbits) - 1u; }
+// Word i of x as the big-endian number it holds, i clamped to last_word.  The device loads the aligned word (the
+// allocation covers x_bytes rounded up to 4); the host takes it byte by byte from any address and reads no byte at or
+// beyond end_byte (they count as zero).
+SMM_GRIB_HD uint32_t load_word(const void* x, uint64_t i, uint64_t last_word, uint64_t end_byte) {
+  const uint64_t w = i < last_word ? i : last_word;
+#if defined(__HIP_DEVICE_COMPILE__)
+  (void)end_byte;
+  return __builtin_bswap32(((const uint32_t*)x)[w]);
+#else
+  const uint8_t* p = (const uint8_t*)x;
+  uint32_t v = 0;
+  for (uint64_t k = 4 * w; k < 4 * w + 4; ++k) v = (v << 8) | (k < end_byte ? (uint32_t)p[k] : 0u);
+  return v;
+#endif
+}
+// the n (0..32) bits at bit `off` (0..31) of the 64 bits hi:lo
+SMM_GRIB_HD uint32_t bits_of(uint32_t hi, uint32_t lo, unsigned off, int n) {
+  const uint64_t both = ((uint64_t)hi << 32) | lo;
+  const unsigned shift = (unsigned)(64 - (int)off - n) & 63u;
+  return (uint32_t)(both >> shift) & (uint32_t)((1ull << n) - 1ull);
+}
+
 // q -> the float32 field value: float64 arithmetic, multiply and add kept apart, IEEE division (DIV = false leaves it
 // out: the caller guarantees ddiv == 1.0, and t / 1.0 has the bits of t), one round-to-nearest-even conversion.
 // The multiply and the add must not be contracted into an FMA: clang is told so inside the function (the pragma ends

@@ -14,16 +14,15 @@
 //   store    a thread per 32-bit output word at the row's own width, the bit length of that maximum
 // A row that fails gets its status and is skipped by every later pass.  A kernel never reads a status word that the
 // same kernel writes: `structure` is written by groups / offsets and gates what follows, `range` is written by the
-// last pass and read by the store.  Plain vector stores and vector atomics (atomicMax on a 32-bit word per row).
-#include "smm_device.hpp"
-
-#include <algorithm>
+// last pass and read by the store.  Plain vector stores and vector atomics (atomicMax on a 32-bit word per row).  The
+// scans (block_scan, scan_parts), raise, the store, the cut launches, the host shell and the entry checks are
+// smm_grib_xcode.hpp's, shared with the other transcoders.
+#include "smm_grib_xcode.hpp"
 
 #include "smm_grib_cpx.hpp"
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kCpxThreads = 256;
 constexpr int kGroupTile = kCpxThreads;       // groups of a tile: one per lane
 constexpr int kPerLane = 4;
@@ -60,29 +59,18 @@ struct CpxArgs {
   uint32_t* xmax;       // [n_j] the row's largest X
 };
 
-// inclusive prefix sum over the N lanes of a workgroup through N words of LDS; every lane of the workgroup calls it
-template <int N>
-__device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t* lds, uint32_t tid) {
-  lds[tid] = v;
-  __syncthreads();
-#pragma unroll
-  for (int o = 1; o < N; o <<= 1) {
-    const uint64_t t = (int)tid >= o ? lds[tid - o] : 0;
-    __syncthreads();
-    lds[tid] += t;
-    __syncthreads();
-  }
-  const uint64_t incl = lds[tid];
-  __syncthreads();   // lds is free again
-  return incl;
-}
+// what scan_parts needs to scan both sums of the tiles at once
+__device__ __forceinline__ CpxTile operator+(CpxTile a, CpxTile b) { return CpxTile{a.values + b.values, a.bits + b.bits}; }
+__device__ __forceinline__ CpxTile operator-(CpxTile a, CpxTile b) { return CpxTile{a.values - b.values, a.bits - b.bits}; }
+__device__ __forceinline__ CpxTile wave_scan(CpxTile v) { return CpxTile{wave_scan(v.values), wave_scan(v.bits)}; }
+__device__ __forceinline__ CpxTile wave_last(CpxTile v) { return CpxTile{wave_last(v.values), wave_last(v.bits)}; }
 
 // ---- groups.  Workgroup (row, tile) takes groups [256 tile, 256 tile + 256).
 __global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_groups_kernel(CpxArgs a, int64_t b0, uint32_t per_row) {
   __shared__ uint64_t lds[kCpxThreads];
-  const int64_t id = b0 + blockIdx.x;
-  const int64_t j = id / per_row;
-  const uint32_t tile = (uint32_t)(id % per_row), tid = threadIdx.x;
+  const RowPart at = row_part(b0, per_row);
+  const int64_t j = at.j;
+  const uint32_t tile = at.part, tid = threadIdx.x;
   const CpxRow* __restrict__ rows = a.rows;
   const CpxRow row = rows[j];
   const smm_cpx::Row& r = row.r;
@@ -111,9 +99,7 @@ __global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_groups_kernel(CpxArg
 
 // ---- offsets.  One wave per row: the tile sums become the sums before each tile; the row's totals are checked.
 __global__ __launch_bounds__(kWave) void smm_grib_cpx_offsets_kernel(CpxArgs a, int64_t b0) {
-  __shared__ uint64_t lds[kWave];
   const int64_t j = b0 + blockIdx.x;
-  const uint32_t lane = threadIdx.x;
   const CpxRow* __restrict__ rows = a.rows;
   const CpxRow row = rows[j];
   const smm_cpx::Row& r = row.r;
@@ -121,23 +107,12 @@ __global__ __launch_bounds__(kWave) void smm_grib_cpx_offsets_kernel(CpxArgs a, 
   const smm_cpx::Sections sec = smm_cpx::sections(r);
   const uint32_t n_tiles = (r.n_groups + kGroupTile - 1) / kGroupTile;
   CpxTile* __restrict__ tiles = a.gtiles + row.gtile_off;
-  uint64_t values = 0, bits = 0;
-  for (uint32_t t0 = 0; t0 < n_tiles; t0 += kWave) {
-    const uint32_t t = t0 + lane;
-    const CpxTile mine = t < n_tiles ? tiles[t] : CpxTile{0, 0};
-    const uint64_t v_incl = block_scan<kWave>(mine.values, lds, lane);
-    const uint64_t b_incl = block_scan<kWave>(mine.bits, lds, lane);
-    if (t < n_tiles) tiles[t] = CpxTile{values + v_incl - mine.values, bits + b_incl - mine.bits};
-    if (lane == kWave - 1) lds[0] = v_incl, lds[1] = b_incl;
-    __syncthreads();
-    values += lds[0];
-    bits += lds[1];
-    __syncthreads();
-  }
-  if (lane == 0) {
-    if (values != r.n_values)
+  const CpxTile sum = scan_parts<CpxTile>(
+      n_tiles, [&](uint32_t t) { return tiles[t]; }, [&](uint32_t t, CpxTile before) { tiles[t] = before; });
+  if (threadIdx.x == 0) {
+    if (sum.values != r.n_values)
       a.structure[j] = smm_cpx::kInvalid;
-    else if (bits > sec.bit_end - sec.data_bit)
+    else if (sum.bits > sec.bit_end - sec.data_bit)
       a.structure[j] = smm_cpx::kExhausted;
   }
 }
@@ -151,11 +126,8 @@ __device__ __forceinline__ void raise_row(const CpxArgs& a, int64_t j, uint32_t 
   }
   const bool any_high = __any(high);
   if ((threadIdx.x & (kWave - 1)) == 0) {
-    // the word only grows: a look at it first spares the atomic of every wave that cannot raise it (a stale look costs
-    // an atomic that changes nothing, never a missed one)
-    if (m > __atomic_load_n(&a.xmax[j], __ATOMIC_RELAXED)) atomicMax(&a.xmax[j], m);
-    if (any_high && __atomic_load_n(&a.range[j], __ATOMIC_RELAXED) != smm_cpx::kInvalid)
-      atomicMax(&a.range[j], (int32_t)smm_cpx::kInvalid);
+    raise(&a.xmax[j], m);
+    if (any_high) raise(&a.range[j], (int32_t)smm_cpx::kInvalid);   // kOk < kInvalid
   }
 }
 
@@ -163,14 +135,14 @@ __device__ __forceinline__ void raise_row(const CpxArgs& a, int64_t j, uint32_t 
 // of that tile whose offset is <= i -- groups of no values share their offset with the group behind them, and the last
 // of equals is the one that holds i (the lengths sum to n_values > i).
 __global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_values_kernel(CpxArgs a, int64_t b0, uint32_t per_row) {
-  const int64_t id = b0 + blockIdx.x;
-  const int64_t j = id / per_row;
-  const uint32_t i = (uint32_t)(id % per_row) * kCpxThreads + threadIdx.x;
+  const RowPart at = row_part(b0, per_row);
+  const int64_t j = at.j;
+  const uint32_t i = at.part * kCpxThreads + threadIdx.x;
   const CpxRow* __restrict__ rows = a.rows;
   const CpxRow row = rows[j];
   const smm_cpx::Row& r = row.r;
   if (!row.coded || a.structure[j] != smm_cpx::kOk) return;
-  if ((uint64_t)(id % per_row) * kCpxThreads >= r.n_values) return;
+  if ((uint64_t)at.part * kCpxThreads >= r.n_values) return;
   const bool live = i < r.n_values;
   uint64_t v = 0;
   if (live) {
@@ -216,9 +188,9 @@ __global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_values_kernel(CpxArg
 // ---- the prefix sums of order 1 and 2; pass p (1 or 2) runs on the rows whose order is >= p
 __global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_reduce_kernel(CpxArgs a, int64_t b0, uint32_t per_row, int pass) {
   __shared__ uint64_t lds[kCpxThreads];
-  const int64_t id = b0 + blockIdx.x;
-  const int64_t j = id / per_row;
-  const uint32_t tile = (uint32_t)(id % per_row), tid = threadIdx.x;
+  const RowPart at = row_part(b0, per_row);
+  const int64_t j = at.j;
+  const uint32_t tile = at.part, tid = threadIdx.x;
   const CpxRow* __restrict__ rows = a.rows;
   const CpxRow row = rows[j];
   const uint32_t n = row.r.n_values;
@@ -235,33 +207,22 @@ __global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_reduce_kernel(CpxArg
 }
 
 __global__ __launch_bounds__(kWave) void smm_grib_cpx_carries_kernel(CpxArgs a, int64_t b0, int pass) {
-  __shared__ uint64_t lds[kWave];
   const int64_t j = b0 + blockIdx.x;
-  const uint32_t lane = threadIdx.x;
   const CpxRow* __restrict__ rows = a.rows;
   const CpxRow row = rows[j];
   if (!row.coded || row.r.order < pass || a.structure[j] != smm_cpx::kOk) return;
   const uint32_t n_tiles = (row.r.n_values + kValueTile - 1) / kValueTile;
   uint64_t* __restrict__ tiles = a.vtiles + row.vtile_off;
-  uint64_t carry = 0;
-  for (uint32_t t0 = 0; t0 < n_tiles; t0 += kWave) {
-    const uint32_t t = t0 + lane;
-    const uint64_t mine = t < n_tiles ? tiles[t] : 0;
-    const uint64_t incl = block_scan<kWave>(mine, lds, lane);
-    if (t < n_tiles) tiles[t] = carry + incl - mine;
-    if (lane == kWave - 1) lds[0] = incl;
-    __syncthreads();
-    carry += lds[0];
-    __syncthreads();
-  }
+  (void)scan_parts<uint64_t>(
+      n_tiles, [&](uint32_t t) { return tiles[t]; }, [&](uint32_t t, uint64_t before) { tiles[t] = before; });
 }
 
 // lane tid owns the 4 consecutive values from 1024 tile + 4 tid on
 __global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_apply_kernel(CpxArgs a, int64_t b0, uint32_t per_row, int pass) {
   __shared__ uint64_t lds[kCpxThreads];
-  const int64_t id = b0 + blockIdx.x;
-  const int64_t j = id / per_row;
-  const uint32_t tile = (uint32_t)(id % per_row), tid = threadIdx.x;
+  const RowPart at = row_part(b0, per_row);
+  const int64_t j = at.j;
+  const uint32_t tile = at.part, tid = threadIdx.x;
   const CpxRow* __restrict__ rows = a.rows;
   const CpxRow row = rows[j];
   const uint32_t n = row.r.n_values;
@@ -295,33 +256,15 @@ __global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_apply_kernel(CpxArgs
 // ---- store.  One thread per 32-bit word of the row's stream at its own width (the grid covers 32 bits a value; the
 // surplus threads leave), the values that overlap the word put in place as smm_grib_codec.hpp's grib_word_part has it.
 __global__ __launch_bounds__(kCpxThreads) void smm_grib_cpx_store_kernel(CpxArgs a, int64_t b0, uint32_t per_row) {
-  const int64_t id = b0 + blockIdx.x;
-  const int64_t j = id / per_row;
-  const uint32_t w = (uint32_t)(id % per_row) * kCpxThreads + threadIdx.x;
+  const RowPart at = row_part(b0, per_row);
+  const int64_t j = at.j;
   const CpxRow* __restrict__ rows = a.rows;
   const CpxRow row = rows[j];
   if (!row.coded || a.structure[j] != smm_cpx::kOk || a.range[j] != smm_cpx::kOk) return;
-  const uint32_t n = row.r.n_values;
-  const int width = smm_cpx::width_of(a.xmax[j]);
-  const uint64_t n_words = smm_grib::align4(smm_grib::row_bytes(n, width)) >> 2;   // <= n: inside the slot
-  if (width == 0 || w >= n_words) return;
   const uint64_t* __restrict__ v = a.values + row.value_off;
-  uint64_t i = 0, end = 0;
-  smm_grib::grib_word_values(w, width, n, &i, &end);
-  uint32_t word = 0;
-  for (; i < end; ++i) word |= smm_grib::grib_word_part((uint32_t)v[i], i, width, w);
-  a.out[(row.out_off >> 2) + w] = __builtin_bswap32(word);
-}
-
-// launches `total` workgroups as grids of at most grid_limit(), the first workgroup's number handed to the kernel
-template <class F>
-int for_grid(int64_t total, F&& launch) {
-  const int64_t limit = std::min<int64_t>(std::max<int64_t>(grid_limit(), 1), 0x7fffffffLL);
-  for (int64_t b0 = 0; b0 < total; b0 += limit) {
-    launch(b0, (unsigned)std::min(limit, total - b0));
-    SMM_HIP(hipGetLastError());
-  }
-  return SMM_OK;
+  // the row's words are at most n_values: inside the slot
+  store_row_word(a.out, row.out_off, at.part * kCpxThreads + threadIdx.x, smm_cpx::width_of(a.xmax[j]), row.r.n_values,
+                 [&](uint64_t i) { return (uint32_t)v[i]; });
 }
 
 struct CpxShape {   // the widest row of the call
@@ -330,37 +273,15 @@ struct CpxShape {   // the widest row of the call
 };
 
 int launch_cpx(const CpxArgs& a, int64_t n_j, const CpxShape& sh, hipStream_t s) {
-  if (sh.gtiles)
-    if (int rc = for_grid(n_j * sh.gtiles, [&](int64_t b0, unsigned nb) {
-          hipLaunchKernelGGL(smm_grib_cpx_groups_kernel, dim3(nb), dim3(kCpxThreads), 0, s, a, b0, sh.gtiles);
-        }))
-      return rc;
-  if (int rc = for_grid(n_j, [&](int64_t b0, unsigned nb) {
-        hipLaunchKernelGGL(smm_grib_cpx_offsets_kernel, dim3(nb), dim3(kWave), 0, s, a, b0);
-      }))
-    return rc;
-  if (!sh.blocks) return SMM_OK;
-  if (int rc = for_grid(n_j * sh.blocks, [&](int64_t b0, unsigned nb) {
-        hipLaunchKernelGGL(smm_grib_cpx_values_kernel, dim3(nb), dim3(kCpxThreads), 0, s, a, b0, sh.blocks);
-      }))
-    return rc;
+  if (int rc = launch_flat(smm_grib_cpx_groups_kernel, kCpxThreads, n_j * sh.gtiles, s, a, sh.gtiles)) return rc;
+  if (int rc = launch_flat(smm_grib_cpx_offsets_kernel, kWave, n_j, s, a)) return rc;
+  if (int rc = launch_flat(smm_grib_cpx_values_kernel, kCpxThreads, n_j * sh.blocks, s, a, sh.blocks)) return rc;
   for (int pass = 1; pass <= sh.order; ++pass) {
-    if (int rc = for_grid(n_j * sh.vtiles, [&](int64_t b0, unsigned nb) {
-          hipLaunchKernelGGL(smm_grib_cpx_reduce_kernel, dim3(nb), dim3(kCpxThreads), 0, s, a, b0, sh.vtiles, pass);
-        }))
-      return rc;
-    if (int rc = for_grid(n_j, [&](int64_t b0, unsigned nb) {
-          hipLaunchKernelGGL(smm_grib_cpx_carries_kernel, dim3(nb), dim3(kWave), 0, s, a, b0, pass);
-        }))
-      return rc;
-    if (int rc = for_grid(n_j * sh.vtiles, [&](int64_t b0, unsigned nb) {
-          hipLaunchKernelGGL(smm_grib_cpx_apply_kernel, dim3(nb), dim3(kCpxThreads), 0, s, a, b0, sh.vtiles, pass);
-        }))
-      return rc;
+    if (int rc = launch_flat(smm_grib_cpx_reduce_kernel, kCpxThreads, n_j * sh.vtiles, s, a, sh.vtiles, pass)) return rc;
+    if (int rc = launch_flat(smm_grib_cpx_carries_kernel, kWave, n_j, s, a, pass)) return rc;
+    if (int rc = launch_flat(smm_grib_cpx_apply_kernel, kCpxThreads, n_j * sh.vtiles, s, a, sh.vtiles, pass)) return rc;
   }
-  return for_grid(n_j * sh.blocks, [&](int64_t b0, unsigned nb) {
-    hipLaunchKernelGGL(smm_grib_cpx_store_kernel, dim3(nb), dim3(kCpxThreads), 0, s, a, b0, sh.blocks);
-  });
+  return launch_flat(smm_grib_cpx_store_kernel, kCpxThreads, n_j * sh.blocks, s, a, sh.blocks);
 }
 
 // everything the entries with records refuse about them
@@ -412,31 +333,21 @@ int smm_grib_cpx_unpack_impl(int device, const void* x, const smm_grib_cpx_t* re
   }
   std::vector<int32_t> got(words);
   if (n_values > 0) {
-    DeviceGuard guard(device);
-    if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the device");
-    hipStream_t s = (hipStream_t)stream;
-    auto align16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t table_at = 0, words_at = align16(n * sizeof(CpxRow)), groups_at = align16(words_at + 3 * n * sizeof(int32_t)),
-                 gtiles_at = groups_at + (size_t)n_groups * sizeof(CpxGroup), values_at = gtiles_at + (size_t)n_gtiles * sizeof(CpxTile),
-                 vtiles_at = values_at + (size_t)n_values * sizeof(uint64_t), bytes = vtiles_at + (size_t)n_vtiles * sizeof(uint64_t);
-    DeviceBuf<char> d;
-    SMM_HIP(d.alloc(bytes));
-    SMM_HIP(hipMemcpyAsync(d.get() + table_at, table.data(), n * sizeof(CpxRow), hipMemcpyHostToDevice, s));
-    SMM_HIP(hipMemcpyAsync(d.get() + words_at, words.data(), 3 * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    int32_t* w = (int32_t*)(d.get() + words_at);
-    CpxArgs a{x, (const CpxRow*)(d.get() + table_at), (CpxGroup*)(d.get() + groups_at), (CpxTile*)(d.get() + gtiles_at),
-              (uint64_t*)(d.get() + values_at), (uint64_t*)(d.get() + vtiles_at), (uint32_t*)out, w, w + n, (uint32_t*)(w + 2 * n)};
-    int rc = launch_cpx(a, n_batch, sh, s);
-    if (rc == SMM_OK) {
-      const hipError_t e = hipMemcpyAsync(got.data(), w, 3 * n * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-      if (e != hipSuccess) rc = fail(SMM_ERR_HIP, std::string("copying the rows' statuses: ") + hipGetErrorString(e));
-    }
-    const hipError_t e = hipStreamSynchronize(s);   // the tables and the scratch are in use until here
-    if (rc != SMM_OK) {
-      (void)hipGetLastError();
+    Arena arena;
+    const size_t table_at = arena.add<CpxRow>(n), words_at = arena.add<int32_t>(3 * n), groups_at = arena.add<CpxGroup>(n_groups),
+                 gtiles_at = arena.add<CpxTile>(n_gtiles), values_at = arena.add<uint64_t>(n_values), vtiles_at = arena.add<uint64_t>(n_vtiles);
+    if (int rc = run_transcode(
+            device, stream, arena.bytes(),
+            {Span{table_at, table.data(), n * sizeof(CpxRow)}, Span{words_at, words.data(), 3 * n * sizeof(int32_t)}},
+            [&](char* d, hipStream_t s) {
+              int32_t* w = Arena::at<int32_t>(d, words_at);
+              const CpxArgs a{x, Arena::at<CpxRow>(d, table_at), Arena::at<CpxGroup>(d, groups_at), Arena::at<CpxTile>(d, gtiles_at),
+                              Arena::at<uint64_t>(d, values_at), Arena::at<uint64_t>(d, vtiles_at), (uint32_t*)out, w, w + n,
+                              (uint32_t*)(w + 2 * n)};
+              return launch_cpx(a, n_batch, sh, s);
+            },
+            Span{words_at, got.data(), 3 * n * sizeof(int32_t)}, "statuses"))
       return rc;
-    }
-    SMM_HIP(e);
   }
   for (size_t b = 0; b < n; ++b) {
     const int status = got[b] != smm_cpx::kOk ? got[b] : got[n + b];
@@ -452,28 +363,19 @@ int smm_grib_cpx_unpack_impl(int device, const void* x, const smm_grib_cpx_t* re
 extern "C" {
 
 int smm_grib_cpx_layout(const smm_grib_cpx_t* recs, int64_t n_batch, uint64_t* byte_off, uint64_t* total_bytes) {
-  return guarded([&] {
-    if (!total_bytes) return fail(SMM_ERR_INVALID, "null total pointer");
-    if (int rc = check_cpx_records(recs, n_batch, INT64_MAX)) return rc;
-    *total_bytes = smm::grib_cpx_layout(recs, n_batch, byte_off);
-    return (int)SMM_OK;
-  });
+  return offsets_entry(
+      recs, n_batch, byte_off, total_bytes, [](const smm_grib_cpx_t* r, int64_t n) { return check_cpx_records(r, n, INT64_MAX); },
+      smm::grib_cpx_layout);
 }
 
 int smm_grib_cpx_unpack(int device, const void* x, int64_t x_bytes, const smm_grib_cpx_t* recs, const smm_grib_row_t* rows_in,
                         int64_t n_batch, void* out, int64_t out_bytes, smm_grib_row_t* rows_out, void* stream) {
   return guarded([&] {
     if (int rc = check_cpx_records(recs, n_batch, x_bytes)) return rc;
-    if (n_batch > 0 && (!rows_in || !rows_out)) return fail(SMM_ERR_INVALID, "null row-table pointer");
-    if (out_bytes < 0) return fail(SMM_ERR_INVALID, "negative out_bytes");
-    std::vector<uint64_t> offs((size_t)n_batch + 1);
-    offs[(size_t)n_batch] = smm::grib_cpx_layout(recs, n_batch, offs.data());
-    if ((uint64_t)out_bytes < offs[(size_t)n_batch])
-      return fail(SMM_ERR_INVALID, "out_bytes " + std::to_string(out_bytes) + " is below the layout's " +
-                                       std::to_string(offs[(size_t)n_batch]) + " bytes");
-    if (offs[(size_t)n_batch] > 0 && (!x || !out)) return fail(SMM_ERR_INVALID, "null field or output pointer");
-    if ((uintptr_t)x % 4) return fail(SMM_ERR_INVALID, "field pointer is not 4-byte aligned");
-    if ((uintptr_t)out % 4) return fail(SMM_ERR_INVALID, "output pointer is not 4-byte aligned");
+    std::vector<uint64_t> offs;
+    if (int rc = check_unpack_call(x, recs, rows_in, n_batch, out, out_bytes, rows_out, offs, smm::grib_cpx_layout,
+                                   [](int64_t) { return (int)SMM_OK; }))
+      return rc;
     return smm_grib_cpx_unpack_impl(device, x, recs, rows_in, n_batch, out, offs.data(), rows_out, stream);
   });
 }

@@ -1,7 +1,7 @@
 // GRIB-2 complex packing (data representation template 5.2) and complex packing with spatial differencing (5.3), what
 // NCEP's g2c / wgrib2 write for GFS, GEFS, HRRR: the decoder and the encoder, each stated once.  Plain C++ that compiles
 // for host and device -- the host decode (smm_grib_cpx_decode_host), the kernels of smm_grib_cpx_unpack
-// (smm_grib_cpx.hip) and tests/cpp/grib_cpx_harness.cpp all read the stream through Stream::peek (smm_grib_aec.hpp's
+// (smm_grib_cpx.hip) and tests/cpp/grib_cpx_harness.cpp all read the stream through Stream::peek (smm_grib_codec.hpp's
 // load_word / bits_of) and take the tables apart with the small functions below; the host encode
 // (smm_grib_cpx_encode_host), the kernels of smm_grib_cpx_pack (smm_grib_cpx_pack.hip) and
 // tests/cpp/grib_cpx_encode_harness.cpp share decide / z_of / coded_row / pack_bound_bytes behind decode_row.
@@ -66,7 +66,7 @@
 
 #include <cstdint>
 
-#include "smm_grib_aec.hpp"
+#include "smm_grib_codec.hpp"
 
 namespace smm_cpx {
 
@@ -116,8 +116,8 @@ struct Stream {
   SMM_GRIB_HD uint32_t peek(uint64_t p, int n) const {
     if (n <= 0 || empty) return 0u;
     const uint64_t w = p >> 5;
-    return smm_aec::bits_of(smm_aec::load_word(x, w, last_word, end_byte), smm_aec::load_word(x, w + 1, last_word, end_byte),
-                            (unsigned)(p & 31), n);
+    return smm_grib::bits_of(smm_grib::load_word(x, w, last_word, end_byte), smm_grib::load_word(x, w + 1, last_word, end_byte),
+                             (unsigned)(p & 31), n);
   }
 };
 SMM_GRIB_HD Stream stream_of(const void* x, const Row& r) {

@@ -20,16 +20,15 @@
 //            recomputed: three extracts from lines the groups kernel just read, rather than 4 B per value of scratch),
 //            stores the whole words big-endian and ORs the shared ones onto the zeros
 // Vector stores and vector atomics (LDS OR, global OR / min / max) only.  They commute: the bytes do not depend on the
-// order.  Every bit position is 64-bit; no store goes to or past out_words, no load past the last word of x.
-#include "smm_device.hpp"
-
-#include <algorithm>
+// order.  Every bit position is 64-bit; no store goes to or past out_words, no load past the last word of x.  The row's
+// input (RowBits), lower / raise, the scans, the LDS windows (win_put / win_flush / zero_ends), the cut launches, the
+// host shell and the entry checks are smm_grib_xcode.hpp's, shared with the other transcoders.
+#include "smm_grib_xcode.hpp"
 
 #include "smm_grib_cpx.hpp"
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kPackThreads = 256;
 constexpr int kPerLane = 4;
 constexpr uint32_t kTile = kPackThreads * kPerLane;       // values of a tile
@@ -58,62 +57,27 @@ struct PackArgs {
   const PackRow* rows;
   RowStats* stats;
   smm_cpx::Decision* plans;   // per row, from the decide kernel
-  smm_cpx::Row* recs;         // per row: the record of the stream (rows kernel; byte_off: layout kernel)
+  smm_cpx::Row* recs;         // per row: the record of the stream (rows kernel; byte_off: layout kernel); one more
+                              // behind them, whose byte_off takes the bytes used
   uint2* groups;          // per group: ref_g, w_g | bit offset in the tile << 8
   uint32_t* tile_bits;    // per tile: its data bits
   uint64_t* tile_at;      // per tile: its first data bit in the row's data part
-  uint64_t* used;         // the bytes used
   uint32_t* out;
   uint64_t out_words;     // no store goes to or past this word of out
 };
 
 // the row's integers, read from its simple-packed stream
-struct RowBits {
-  const uint32_t* words;
-  uint32_t bit0, last;
-  int nbits;
-  __device__ __forceinline__ uint32_t operator()(uint32_t i) const {
-    return smm_grib::grib_extract(words, (uint64_t)bit0 + (uint64_t)i * (uint32_t)nbits, nbits, last);
-  }
-};
 __device__ __forceinline__ RowBits row_bits(const PackArgs& a, const PackRow& r) {
-  const uint64_t w = std::min<uint64_t>(r.in_off >> 2, a.last_word);
-  return RowBits{a.x + w, 8u * (uint32_t)(r.in_off & 3), (uint32_t)std::min<uint64_t>(a.last_word - w, 0xfffffffeull), r.nbits};
-}
-// an atomic min / max onto a word that only falls / grows: a look at it first spares the atomic that cannot change it (a
-// stale look costs an atomic that changes nothing, never a missed one)
-template <class T>
-__device__ __forceinline__ void lower(T* at, T v) {
-  if (v < __atomic_load_n(at, __ATOMIC_RELAXED)) atomicMin(at, v);
-}
-template <class T>
-__device__ __forceinline__ void raise(T* at, T v) {
-  if (v > __atomic_load_n(at, __ATOMIC_RELAXED)) atomicMax(at, v);
+  return row_bits(a.x, a.last_word, r.in_off, r.nbits);
 }
 __device__ __forceinline__ uint32_t umin32(uint32_t a, uint32_t b) { return a < b ? a : b; }
 __device__ __forceinline__ uint32_t umax32(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
-// inclusive prefix sum over the 256 lanes of a workgroup through LDS; every lane of the workgroup calls it
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* lds, uint32_t tid) {
-  lds[tid] = v;
-  __syncthreads();
-#pragma unroll
-  for (int o = 1; o < kPackThreads; o <<= 1) {
-    const uint32_t t = (int)tid >= o ? lds[tid - o] : 0u;
-    __syncthreads();
-    lds[tid] += t;
-    __syncthreads();
-  }
-  const uint32_t incl = lds[tid];
-  __syncthreads();
-  return incl;
-}
-
 // ---- 1: diff.  Workgroup (row, tile); only rows whose wanted order can hold (order > 0, n > order) take part.
 __global__ __launch_bounds__(kPackThreads) void smm_grib_cpx_diff_kernel(PackArgs a, int64_t b0, uint32_t per_row) {
-  const int64_t id = b0 + blockIdx.x;
-  const int64_t j = id / per_row;
-  const uint32_t tile = (uint32_t)(id % per_row), tid = threadIdx.x;
+  const RowPart at = row_part(b0, per_row);
+  const int64_t j = at.j;
+  const uint32_t tile = at.part, tid = threadIdx.x;
   const PackRow* __restrict__ rows = a.rows;
   const PackRow r = rows[j];
   if (r.nbits == 0 || r.order <= 0 || r.n_values <= (uint32_t)r.order || tile >= r.n_tiles) return;
@@ -158,9 +122,9 @@ __global__ __launch_bounds__(kPackThreads) void smm_grib_cpx_decide_kernel(PackA
 // ---- 3: groups.  Workgroup (row, tile).  Lanes past the row's end hold the identities: the shuffles stay whole.
 __global__ __launch_bounds__(kPackThreads) void smm_grib_cpx_groups_kernel(PackArgs a, int64_t b0, uint32_t per_row) {
   __shared__ uint32_t s_ref[kTileGroups], s_w[kTileGroups], lds[kPackThreads];
-  const int64_t id = b0 + blockIdx.x;
-  const int64_t j = id / per_row;
-  const uint32_t tile = (uint32_t)(id % per_row), tid = threadIdx.x;
+  const RowPart at = row_part(b0, per_row);
+  const int64_t j = at.j;
+  const uint32_t tile = at.part, tid = threadIdx.x;
   const PackRow* __restrict__ rows = a.rows;
   const PackRow r = rows[j];
   if (r.nbits == 0 || tile >= r.n_tiles) return;
@@ -187,7 +151,7 @@ __global__ __launch_bounds__(kPackThreads) void smm_grib_cpx_groups_kernel(PackA
   const bool exists = tid < per_tile && g < r.n_groups;
   const uint32_t ref = exists ? s_ref[tid] : 0u, w = exists ? s_w[tid] : 0u;
   const uint32_t len = exists ? umin32(L, r.n_values - g * L) : 0u, bits = w * len;
-  const uint32_t incl = block_scan(bits, lds, tid);
+  const uint32_t incl = block_scan<kPackThreads>(bits, lds, tid);
   if (exists) a.groups[r.group_off + g] = make_uint2(ref, w | ((incl - bits) << 8));   // the offset is below 2^15
   if (tid == kPackThreads - 1) a.tile_bits[r.tile_off + tile] = incl;
   uint32_t ref_max = ref, w_min = exists ? w : 64u, w_max = w;
@@ -210,25 +174,15 @@ __global__ __launch_bounds__(kWave) void smm_grib_cpx_rows_kernel(PackArgs a, in
   const uint32_t lane = threadIdx.x;
   const PackRow* __restrict__ rows = a.rows;
   const PackRow r = rows[j];
-  unsigned long long carry = 0;
-  for (uint32_t t0 = 0; t0 < r.n_tiles; t0 += kWave) {
-    const uint32_t t = t0 + lane;
-    const unsigned long long v = t < r.n_tiles ? a.tile_bits[r.tile_off + t] : 0ull;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const unsigned long long up = __shfl_up(incl, o, kWave);
-      if ((int)lane >= o) incl += up;
-    }
-    if (t < r.n_tiles) a.tile_at[r.tile_off + t] = carry + incl - v;
-    carry += __shfl(incl, kWave - 1, kWave);
-  }
+  const uint64_t bits = scan_parts<uint64_t>(
+      r.n_tiles, [&](uint32_t t) { return (uint64_t)a.tile_bits[r.tile_off + t]; },
+      [&](uint32_t t, uint64_t before) { a.tile_at[r.tile_off + t] = before; });
   if (lane == 0) {
     smm_cpx::Row rec{};
     rec.n_values = r.n_values;
     if (r.nbits != 0 && r.n_values != 0) {
       const RowStats st = a.stats[j];
-      rec = smm_cpx::coded_row(r.n_values, r.L, a.plans[j], st.ref_max, st.w_min, st.w_max, carry);
+      rec = smm_cpx::coded_row(r.n_values, r.L, a.plans[j], st.ref_max, st.w_min, st.w_max, bits);
     }
     a.recs[j] = rec;
   }
@@ -236,21 +190,10 @@ __global__ __launch_bounds__(kWave) void smm_grib_cpx_rows_kernel(PackArgs a, in
 
 // ---- 5: layout.  One wave: rows back to back in row order, each at a 4-byte-aligned offset.
 __global__ __launch_bounds__(kWave) void smm_grib_cpx_layout_kernel(PackArgs a, int64_t n_j) {
-  const uint32_t lane = threadIdx.x;
-  unsigned long long carry = 0;
-  for (int64_t b0 = 0; b0 < n_j; b0 += kWave) {
-    const int64_t b = b0 + lane;
-    const unsigned long long v = b < n_j ? smm_grib::align4(a.recs[b].byte_len) : 0ull;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const unsigned long long up = __shfl_up(incl, o, kWave);
-      if ((int)lane >= o) incl += up;
-    }
-    if (b < n_j) a.recs[b].byte_off = carry + incl - v;
-    carry += __shfl(incl, kWave - 1, kWave);
-  }
-  if (lane == 0) *a.used = carry;
+  const uint64_t used = scan_parts<uint64_t>(
+      n_j, [&](int64_t b) { return smm_grib::align4(a.recs[b].byte_len); },
+      [&](int64_t b, uint64_t before) { a.recs[b].byte_off = before; });
+  if (threadIdx.x == 0) a.recs[n_j].byte_off = used;
 }
 
 // where a tile's share of the three parts lies in out, as bit positions counted from out's first bit: [first, end) each
@@ -278,60 +221,35 @@ __device__ __forceinline__ uint32_t head_words(const smm_cpx::Row& rec) {
 // ---- 6: edges.  A thread per tile.  A row begins and ends on a word of its own; inside it every part begins on an
 // octet, so the first and the last word of a tile's share of a part may hold bits of its neighbours: they are zeroed
 // here and ORed into by the emit kernel, as are the words of the descriptors.
-__device__ __forceinline__ void zero_ends(const PackArgs& a, uint64_t first, uint64_t end) {
-  if (end <= first) return;
-  if ((first >> 5) < a.out_words) a.out[first >> 5] = 0u;
-  if (((end - 1) >> 5) < a.out_words) a.out[(end - 1) >> 5] = 0u;
-}
 __global__ __launch_bounds__(kPackThreads) void smm_grib_cpx_edges_kernel(PackArgs a, int64_t b0, uint32_t per_row) {
-  const int64_t id = b0 + blockIdx.x;
-  const int64_t j = id / per_row;
-  const uint32_t tile = (uint32_t)(id % per_row) * kPackThreads + threadIdx.x;
+  const RowPart at = row_part(b0, per_row);
+  const int64_t j = at.j;
+  const uint32_t tile = at.part * kPackThreads + threadIdx.x;
   const PackRow* __restrict__ rows = a.rows;
   const PackRow r = rows[j];
   if (r.nbits == 0 || tile >= r.n_tiles) return;
   const smm_cpx::Row rec = a.recs[j];
   const TileBits t = tile_bits_of(a, r, rec, tile);
-  zero_ends(a, t.refs0, t.refs1);
-  zero_ends(a, t.widths0, t.widths1);
-  zero_ends(a, t.data0, t.data1);
+  zero_ends(a.out, a.out_words, t.refs0, t.refs1);
+  zero_ends(a.out, a.out_words, t.widths0, t.widths1);
+  zero_ends(a.out, a.out_words, t.data0, t.data1);
   if (tile == 0u)
     for (uint32_t w = 0; w < head_words(rec); ++w)
       if ((rec.byte_off >> 2) + w < a.out_words) a.out[(rec.byte_off >> 2) + w] = 0u;
 }
 
-// ---- 7: emit.  A workgroup per tile.  A window's word 0 is the word of out that holds the first bit of the tile's
-// share.  n (1..32) bits at bit `at` of a window; nothing goes past its n_words words.
-__device__ __forceinline__ void win_put(uint32_t* win, uint32_t n_words, uint32_t at, uint32_t v, uint32_t n) {
-  const uint32_t w = at >> 5;
-  const uint64_t both = (uint64_t)v << (64u - (at & 31u) - n);   // the shift is 1..63
-  const uint32_t hi = (uint32_t)(both >> 32), lo = (uint32_t)both;
-  if (hi != 0u && w < n_words) atomicOr(&win[w], hi);
-  if (lo != 0u && w + 1u < n_words) atomicOr(&win[w + 1u], lo);
-}
+// ---- 7: emit.  A workgroup per tile, a window for each of its three shares and one for the descriptors.
 // words of a window whose share is [first, end), cut to the window
 __device__ __forceinline__ uint32_t win_words(uint64_t first, uint64_t end, uint32_t cap) {
   if (end <= first) return 0u;
   const uint64_t n = ((first & 31u) + (end - first) + 31u) / 32u;
   return n < cap ? (uint32_t)n : cap;
 }
-// the window's words to out: whole words stored, the first and the last ORed onto the zeros
-__device__ __forceinline__ void win_flush(const PackArgs& a, const uint32_t* win, uint32_t n_words, uint64_t w0, uint32_t tid) {
-  for (uint32_t w = tid; w < n_words; w += kPackThreads) {
-    const uint64_t at = w0 + w;
-    if (at >= a.out_words) continue;
-    const uint32_t word = __builtin_bswap32(win[w]);
-    if (w == 0u || w == n_words - 1u)
-      atomicOr(&a.out[at], word);
-    else
-      a.out[at] = word;
-  }
-}
 __global__ __launch_bounds__(kPackThreads) void smm_grib_cpx_emit_kernel(PackArgs a, int64_t b0, uint32_t per_row) {
   __shared__ uint32_t win_d[kDataWords], win_r[kRefWords], win_w[kWidthWords], win_h[kHeadWords];
-  const int64_t id = b0 + blockIdx.x;
-  const int64_t j = id / per_row;
-  const uint32_t tile = (uint32_t)(id % per_row), tid = threadIdx.x;
+  const RowPart where = row_part(b0, per_row);
+  const int64_t j = where.j;
+  const uint32_t tile = where.part, tid = threadIdx.x;
   const PackRow* __restrict__ rows = a.rows;
   const PackRow r = rows[j];
   if (r.nbits == 0 || tile >= r.n_tiles) return;
@@ -368,51 +286,25 @@ __global__ __launch_bounds__(kPackThreads) void smm_grib_cpx_emit_kernel(PackArg
     win_put(win_h, n_h, (uint32_t)dec.order * nb, smm_cpx::sign_magnitude_of(dec.g, dec.n_oct), nb);
   }
   __syncthreads();
-  win_flush(a, win_d, n_d, t.data0 >> 5, tid);
-  win_flush(a, win_r, n_r, t.refs0 >> 5, tid);
-  win_flush(a, win_w, n_w, t.widths0 >> 5, tid);
+  win_flush<kPackThreads>(a.out, a.out_words, win_d, n_d, t.data0 >> 5, tid);
+  win_flush<kPackThreads>(a.out, a.out_words, win_r, n_r, t.refs0 >> 5, tid);
+  win_flush<kPackThreads>(a.out, a.out_words, win_w, n_w, t.widths0 >> 5, tid);
   if (tid < n_h && (rec.byte_off >> 2) + tid < a.out_words) atomicOr(&a.out[(rec.byte_off >> 2) + tid], __builtin_bswap32(win_h[tid]));
-}
-
-// launches `total` workgroups as grids of at most grid_limit(), the first workgroup's number handed to the kernel
-template <class F>
-int for_grid(int64_t total, F&& launch) {
-  const int64_t limit = std::min<int64_t>(std::max<int64_t>(grid_limit(), 1), 0x7fffffffLL);
-  for (int64_t b0 = 0; b0 < total; b0 += limit) {
-    launch(b0, (unsigned)std::min(limit, total - b0));
-    SMM_HIP(hipGetLastError());
-  }
-  return SMM_OK;
 }
 
 int launch_cpx_pack(const PackArgs& a, int64_t n_j, uint32_t max_tiles, bool any_order, hipStream_t s) {
   const int64_t tiles = n_j * (int64_t)max_tiles;
   const uint32_t edge_groups = (max_tiles + kPackThreads - 1) / kPackThreads;
-  if (any_order)
-    if (int rc = for_grid(tiles, [&](int64_t b0, unsigned nb) {
-          hipLaunchKernelGGL(smm_grib_cpx_diff_kernel, dim3(nb), dim3(kPackThreads), 0, s, a, b0, max_tiles);
-        }))
-      return rc;
+  if (int rc = launch_flat(smm_grib_cpx_diff_kernel, kPackThreads, any_order ? tiles : 0, s, a, max_tiles)) return rc;
   // one launch: a grid of n_j / 256 workgroups stays below every limit a test sets and the device has
   hipLaunchKernelGGL(smm_grib_cpx_decide_kernel, dim3((unsigned)((n_j + kPackThreads - 1) / kPackThreads)), dim3(kPackThreads), 0, s, a, n_j);
   SMM_HIP(hipGetLastError());
-  if (int rc = for_grid(tiles, [&](int64_t b0, unsigned nb) {
-        hipLaunchKernelGGL(smm_grib_cpx_groups_kernel, dim3(nb), dim3(kPackThreads), 0, s, a, b0, max_tiles);
-      }))
-    return rc;
-  if (int rc = for_grid(n_j, [&](int64_t b0, unsigned nb) {
-        hipLaunchKernelGGL(smm_grib_cpx_rows_kernel, dim3(nb), dim3(kWave), 0, s, a, b0);
-      }))
-    return rc;
+  if (int rc = launch_flat(smm_grib_cpx_groups_kernel, kPackThreads, tiles, s, a, max_tiles)) return rc;
+  if (int rc = launch_flat(smm_grib_cpx_rows_kernel, kWave, n_j, s, a)) return rc;
   hipLaunchKernelGGL(smm_grib_cpx_layout_kernel, dim3(1), dim3(kWave), 0, s, a, n_j);
   SMM_HIP(hipGetLastError());
-  if (int rc = for_grid(n_j * (int64_t)edge_groups, [&](int64_t b0, unsigned nb) {
-        hipLaunchKernelGGL(smm_grib_cpx_edges_kernel, dim3(nb), dim3(kPackThreads), 0, s, a, b0, edge_groups);
-      }))
-    return rc;
-  return for_grid(tiles, [&](int64_t b0, unsigned nb) {
-    hipLaunchKernelGGL(smm_grib_cpx_emit_kernel, dim3(nb), dim3(kPackThreads), 0, s, a, b0, max_tiles);
-  });
+  if (int rc = launch_flat(smm_grib_cpx_edges_kernel, kPackThreads, n_j * (int64_t)edge_groups, s, a, edge_groups)) return rc;
+  return launch_flat(smm_grib_cpx_emit_kernel, kPackThreads, tiles, s, a, max_tiles);
 }
 
 // What the entries with "wanted" records refuse about them; nothing but n_values, nbits, order, length_ref and reserved
@@ -434,12 +326,9 @@ int check_pack_records(const smm_grib_cpx_t* recs, int64_t n_batch) {
 }
 
 uint64_t pack_bound(const smm_grib_cpx_t* recs, int64_t n_batch, uint64_t* byte_off) {
-  uint64_t at = 0;
-  for (int64_t b = 0; b < n_batch; ++b) {
-    if (byte_off) byte_off[b] = at;
-    at += smm_cpx::pack_bound_bytes(recs[b].n_values, recs[b].nbits, recs[b].order, recs[b].length_ref);
-  }
-  return at;
+  return sum_rows(recs, n_batch, byte_off, [](const smm_grib_cpx_t& c) {
+    return smm_cpx::pack_bound_bytes(c.n_values, c.nbits, c.order, c.length_ref);
+  });
 }
 
 int smm_grib_cpx_pack_impl(int device, const void* x, int64_t x_bytes, const smm_grib_row_t* rows_in, const smm_grib_cpx_t* recs,
@@ -465,45 +354,31 @@ int smm_grib_cpx_pack_impl(int device, const void* x, int64_t x_bytes, const smm
   }
   *used_bytes = 0;
   if (n == 0) return SMM_OK;
-  DeviceGuard guard(device);
-  if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select the device");
-  hipStream_t s = (hipStream_t)stream;
-  auto align8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
-  const size_t table_at = 0, stats_at = table_at + n * sizeof(PackRow), plans_at = stats_at + n * sizeof(RowStats),
-               recs_at = plans_at + n * sizeof(smm_cpx::Decision), used_at = recs_at + n * sizeof(smm_cpx::Row),
-               groups_at = used_at + 8, tile_at_at = groups_at + (size_t)groups * sizeof(uint2),
-               tile_bits_at = tile_at_at + (size_t)tiles * sizeof(uint64_t), bytes = align8(tile_bits_at + (size_t)tiles * sizeof(uint32_t));
-  static_assert(sizeof(smm_cpx::Row) % 8 == 0 && sizeof(smm_cpx::Decision) % 8 == 0 && sizeof(RowStats) % 8 == 0, "8-byte aligned tables");
-  DeviceBuf<char> d;   // table, stats, plans, records, bytes used, group records, tile offsets, tile bits
-  SMM_HIP(d.alloc(bytes));
-  SMM_HIP(hipMemcpyAsync(d.get() + table_at, table.data(), n * sizeof(PackRow), hipMemcpyHostToDevice, s));
-  SMM_HIP(hipMemcpyAsync(d.get() + stats_at, stats.data(), n * sizeof(RowStats), hipMemcpyHostToDevice, s));
-  PackArgs a{};
-  a.x = (const uint32_t*)x;
-  a.last_word = x_bytes > 0 ? smm_grib::align4((uint64_t)x_bytes) / 4 - 1 : 0;
-  a.rows = (const PackRow*)(d.get() + table_at);
-  a.stats = (RowStats*)(d.get() + stats_at);
-  a.plans = (smm_cpx::Decision*)(d.get() + plans_at);
-  a.recs = (smm_cpx::Row*)(d.get() + recs_at);
-  a.used = (uint64_t*)(d.get() + used_at);
-  a.groups = (uint2*)(d.get() + groups_at);
-  a.tile_at = (uint64_t*)(d.get() + tile_at_at);
-  a.tile_bits = (uint32_t*)(d.get() + tile_bits_at);
-  a.out = (uint32_t*)out;
-  a.out_words = (uint64_t)out_bytes / 4;
-  std::vector<smm_cpx::Row> got(n + 1);   // the records, then the bytes used in the place of one more
-  static_assert(sizeof(smm_cpx::Row) >= 8, "the bytes used lie behind the records");
-  int rc = launch_cpx_pack(a, n_batch, max_tiles, any_order, s);
-  if (rc == SMM_OK) {
-    const hipError_t e = hipMemcpyAsync(got.data(), a.recs, n * sizeof(smm_cpx::Row) + 8, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) rc = fail(SMM_ERR_HIP, std::string("copying the rows' records: ") + hipGetErrorString(e));
-  }
-  const hipError_t e = hipStreamSynchronize(s);   // the tables and the scratch are in use until here
-  if (rc != SMM_OK) {
-    (void)hipGetLastError();
+  Arena arena;   // table, stats, plans, records and the bytes used, group records, tile offsets, tile bits
+  const size_t table_at = arena.add<PackRow>(n), stats_at = arena.add<RowStats>(n), plans_at = arena.add<smm_cpx::Decision>(n),
+               recs_at = arena.add<smm_cpx::Row>(n + 1), groups_at = arena.add<uint2>(groups), tile_at_at = arena.add<uint64_t>(tiles),
+               tile_bits_at = arena.add<uint32_t>(tiles);
+  std::vector<smm_cpx::Row> got(n + 1);   // the records, then the bytes used in the byte_off of one more
+  if (int rc = run_transcode(
+          device, stream, arena.bytes(),
+          {Span{table_at, table.data(), n * sizeof(PackRow)}, Span{stats_at, stats.data(), n * sizeof(RowStats)}},
+          [&](char* d, hipStream_t s) {
+            PackArgs a{};
+            a.x = (const uint32_t*)x;
+            a.last_word = x_bytes > 0 ? smm_grib::align4((uint64_t)x_bytes) / 4 - 1 : 0;
+            a.rows = Arena::at<PackRow>(d, table_at);
+            a.stats = Arena::at<RowStats>(d, stats_at);
+            a.plans = Arena::at<smm_cpx::Decision>(d, plans_at);
+            a.recs = Arena::at<smm_cpx::Row>(d, recs_at);
+            a.groups = Arena::at<uint2>(d, groups_at);
+            a.tile_at = Arena::at<uint64_t>(d, tile_at_at);
+            a.tile_bits = Arena::at<uint32_t>(d, tile_bits_at);
+            a.out = (uint32_t*)out;
+            a.out_words = (uint64_t)out_bytes / 4;
+            return launch_cpx_pack(a, n_batch, max_tiles, any_order, s);
+          },
+          Span{recs_at, got.data(), (n + 1) * sizeof(smm_cpx::Row)}, "records"))
     return rc;
-  }
-  SMM_HIP(e);
   for (size_t b = 0; b < n; ++b)
     recs_out[b] = recs[b].nbits == 0 ? smm_cpx::simple_record(recs[b].n_values, got[b].byte_off) : smm_cpx::record_of(got[b]);
   *used_bytes = got[n].byte_off;
@@ -515,12 +390,7 @@ int smm_grib_cpx_pack_impl(int device, const void* x, int64_t x_bytes, const smm
 extern "C" {
 
 int smm_grib_cpx_pack_bound(const smm_grib_cpx_t* recs, int64_t n_batch, uint64_t* byte_off, uint64_t* total_bytes) {
-  return guarded([&] {
-    if (!total_bytes) return fail(SMM_ERR_INVALID, "null total pointer");
-    if (int rc = check_pack_records(recs, n_batch)) return rc;
-    *total_bytes = pack_bound(recs, n_batch, byte_off);
-    return (int)SMM_OK;
-  });
+  return offsets_entry(recs, n_batch, byte_off, total_bytes, check_pack_records, pack_bound);
 }
 
 int smm_grib_cpx_pack(int device, const void* x, int64_t x_bytes, const smm_grib_row_t* rows_in, const smm_grib_cpx_t* recs,
@@ -528,29 +398,7 @@ int smm_grib_cpx_pack(int device, const void* x, int64_t x_bytes, const smm_grib
                       void* stream) {
   return guarded([&] {
     if (int rc = check_pack_records(recs, n_batch)) return rc;
-    if (n_batch > 0 && (!rows_in || !recs_out)) return fail(SMM_ERR_INVALID, "null row-table or result pointer");
-    if (!used_bytes) return fail(SMM_ERR_INVALID, "null used_bytes pointer");
-    if (x_bytes < 0) return fail(SMM_ERR_INVALID, "negative x_bytes");
-    if (out_bytes < 0) return fail(SMM_ERR_INVALID, "negative out_bytes");
-    bool streams = false;
-    for (int64_t b = 0; b < n_batch; ++b) {
-      const std::string at = "rows_in[" + std::to_string(b) + "]";
-      if (rows_in[b].nbits != recs[b].nbits)
-        return fail(SMM_ERR_INVALID, at + ".nbits differs from recs[" + std::to_string(b) + "].nbits");
-      const uint64_t len = smm_grib::row_bytes(recs[b].n_values, recs[b].nbits);
-      if (len > 0 && (rows_in[b].byte_off > (uint64_t)x_bytes || len > (uint64_t)x_bytes - rows_in[b].byte_off))
-        return fail(SMM_ERR_INVALID, at + ": bytes [" + std::to_string(rows_in[b].byte_off) + ", " +
-                                         std::to_string(rows_in[b].byte_off) + " + " + std::to_string(len) +
-                                         ") leave the buffer of " + std::to_string(x_bytes) + " bytes");
-      streams = streams || len > 0;
-    }
-    const uint64_t bound = pack_bound(recs, n_batch, nullptr);
-    if ((uint64_t)out_bytes < bound)
-      return fail(SMM_ERR_INVALID, "out_bytes " + std::to_string(out_bytes) + " is below the bound of " + std::to_string(bound) +
-                                       " bytes");
-    if (streams && (!x || !out)) return fail(SMM_ERR_INVALID, "null field or output pointer");
-    if ((uintptr_t)x % 4) return fail(SMM_ERR_INVALID, "field pointer is not 4-byte aligned");
-    if ((uintptr_t)out % 4) return fail(SMM_ERR_INVALID, "output pointer is not 4-byte aligned");
+    if (int rc = check_pack_call(x, x_bytes, rows_in, recs, n_batch, out, out_bytes, recs_out, used_bytes, pack_bound)) return rc;
     return smm_grib_cpx_pack_impl(device, x, x_bytes, rows_in, recs, n_batch, out, out_bytes, recs_out, used_bytes, stream);
   });
 }
@@ -564,7 +412,7 @@ int smm_grib_cpx_encode_host(const uint32_t* values, int64_t n_values, const smm
     if (out_cap < 0) return fail(SMM_ERR_INVALID, "negative out_cap");
     *byte_len = 0;
     if (n_values > 0 && !values) return fail(SMM_ERR_INVALID, "null values pointer");
-    const uint32_t xmax = smm_aec::sample_max(rec->nbits);
+    const uint32_t xmax = smm_grib::sample_max(rec->nbits);
     for (int64_t i = 0; i < n_values; ++i)
       if (values[i] > xmax)
         return fail(SMM_ERR_INVALID, "values[" + std::to_string(i) + "] does not fit into " + std::to_string(rec->nbits) + " bits");

@@ -597,19 +597,7 @@ def grib_aec_pack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None
     `griblite.aec_encode` gives.  A field of width 0 has no stream (byte_len 0, block_size 0).  out: a uint8 DeviceArray of
     at least the bound (smm_grib_aec_pack_bound) to code into.  The stream is synchronised on return."""
     from . import _grib
-    from .griblite import GRIB_AEC_DTYPE
-    x_ptr, n_bytes, rows, ccsds, out = _grib.transcode_args("grib_aec_pack", _grib.CCSDS, "smm_grib_aec_pack_bound",
-                                                            device_bytes, rows, ccsds, x_bytes, out)
-    ccsds_out = np.zeros(rows.size, dtype=GRIB_AEC_DTYPE)
-    used = ctypes.c_uint64(0)
-    _lib.call("smm_grib_aec_pack", current_device(), x_ptr, n_bytes,
-              ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)),
-              ctypes.cast(ccsds.ctypes.data, ctypes.POINTER(_lib.GribAecStruct)), rows.size, ctypes.c_void_p(out.ptr),
-              out.nbytes, ctypes.cast(ccsds_out.ctypes.data, ctypes.POINTER(_lib.GribAecStruct)), ctypes.byref(used),
-              _stream_handle(stream))
-    rows_out = rows.copy()
-    rows_out["byte_off"] = ccsds_out["byte_off"]
-    return DeviceArray((int(used.value),), np.uint8, ptr=out.ptr, base=out), rows_out, ccsds_out
+    return _grib.pack_device("grib_aec_pack", _grib.CCSDS, device_bytes, rows, ccsds, x_bytes, out, stream)
 
 
 def grib_cpx_pack(device_bytes, rows, cpx, x_bytes=None, out=None, stream=None):
@@ -624,19 +612,7 @@ def grib_cpx_pack(device_bytes, rows, cpx, x_bytes=None, out=None, stream=None):
     `griblite.cpx_encode` gives.  A field of width 0 is not coded (byte_len 0, order GRIB_CPX_SIMPLE).  out: a uint8 DeviceArray of at least the bound (smm_grib_cpx_pack_bound) to code into.  The stream is synchronised
     on return."""
     from . import _grib
-    from .griblite import GRIB_CPX_DTYPE
-    x_ptr, n_bytes, rows, cpx, out = _grib.transcode_args("grib_cpx_pack", _grib.CPX, "smm_grib_cpx_pack_bound",
-                                                          device_bytes, rows, cpx, x_bytes, out)
-    cpx_out = np.zeros(rows.size, dtype=GRIB_CPX_DTYPE)
-    used = ctypes.c_uint64(0)
-    _lib.call("smm_grib_cpx_pack", current_device(), x_ptr, n_bytes,
-              ctypes.cast(rows.ctypes.data, ctypes.POINTER(_lib.GribRowStruct)),
-              ctypes.cast(cpx.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)), rows.size, ctypes.c_void_p(out.ptr),
-              out.nbytes, ctypes.cast(cpx_out.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)), ctypes.byref(used),
-              _stream_handle(stream))
-    rows_out = rows.copy()
-    rows_out["byte_off"] = cpx_out["byte_off"]
-    return DeviceArray((int(used.value),), np.uint8, ptr=out.ptr, base=out), rows_out, cpx_out
+    return _grib.pack_device("grib_cpx_pack", _grib.CPX, device_bytes, rows, cpx, x_bytes, out, stream)
 
 
 def empty(shape, dtype=np.float64):

@@ -54,7 +54,7 @@ int main() {
             const uint32_t sizes[] = {0u, 1u, (uint32_t)J - 1u, (uint32_t)J, (uint32_t)J + 1u, (uint32_t)(rnd() % 700),
                                       span > 3000u ? 777u : span - 1u, span > 3000u ? 1030u : span + 1u};
             const uint32_t n = sizes[(cases + kind) % 8];
-            const uint32_t xmax = smm_aec::sample_max(nbits);
+            const uint32_t xmax = smm_grib::sample_max(nbits);
             std::vector<uint32_t> v(n), back(n + 1);
             fill(v, kind, xmax, (uint32_t)J);
             const uint64_t bound = smm_aec::pack_bound_bytes(n, nbits, J);

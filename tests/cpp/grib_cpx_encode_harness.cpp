@@ -51,7 +51,7 @@ int main() {
         for (int kind = 0; kind < 10; ++kind) {
           const uint32_t sizes[] = {1u, 2u, 3u, L - 1u, L, L + 1u, (uint32_t)(rnd() % 700) + 1u, 1030u};
           const uint32_t n = sizes[(cases + kind) % 8];
-          const uint32_t xmax = smm_aec::sample_max(nbits);
+          const uint32_t xmax = smm_grib::sample_max(nbits);
           std::vector<uint32_t> v(n), back(n + 1);
           fill(v, kind, xmax, L);
           const uint64_t bound = smm_cpx::pack_bound_bytes(n, nbits, order, L);

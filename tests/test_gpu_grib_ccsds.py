@@ -48,10 +48,9 @@ def operator():
 
 
 # ------------------------------------------------------------------------------------------------ grib_unpack
-def test_grib_unpack_gives_every_fixtures_integers_in_one_call(hip):
-    """All fixtures as the rows of one call -- every width, block size, interval and both preprocessor settings mixed,
-    5 to 2048 values -- and a constant row among them: each slot holds the bytes of the simple-packed twin, zero-padded to
-    4, and decodes to the floats of the fixture's integers."""
+def all_fixtures_call():
+    """(fixtures, packed bytes, row records, CCSDS records) of one call with every fixture as a row, their streams at
+    odd distances, and a constant row behind them."""
     fxs = cc.fixtures()
     rows = rules(len(fxs) + 1, seed=2)
     aec = np.zeros(len(fxs) + 1, dtype=GRIB_AEC_DTYPE)
@@ -64,7 +63,14 @@ def test_grib_unpack_gives_every_fixtures_integers_in_one_call(hip):
         at += f.stream.size
     rows["nbits"][-1], rows["byte_off"][-1] = 0, 12345                     # passes through untouched
     aec[-1] = (0, 0, 77, 0, 0, 0, 0, 0)
-    buf = np.concatenate(parts)
+    return fxs, np.concatenate(parts), rows, aec
+
+
+def test_grib_unpack_gives_every_fixtures_integers_in_one_call(hip):
+    """All fixtures as the rows of one call -- every width, block size, interval and both preprocessor settings mixed,
+    5 to 2048 values -- and a constant row among them: each slot holds the bytes of the simple-packed twin, zero-padded to
+    4, and decodes to the floats of the fixture's integers."""
+    fxs, buf, rows, aec = all_fixtures_call()
     filled = to_device(np.full(1 << 17, 0xFF, dtype=np.uint8))
     out, rows_out = grib_unpack(device_bytes(buf), rows, aec, x_bytes=buf.size, out=filled)
     host = out.to_host()
@@ -87,6 +93,32 @@ def test_grib_unpack_gives_every_fixtures_integers_in_one_call(hip):
         assert got.tobytes() == ref.tobytes(), f
         end = off + slot
     assert (host[end:] == 0xFF).all()                                      # nothing behind the layout is written
+
+
+def test_grib_unpack_with_cut_launch_grids_gives_the_same_bytes(hip):
+    """smm_debug_set_grid_limit: the all-fixtures call once whole and once with every kernel's grid cut into launches of
+    at most L workgroups gives the same bytes and the same records.  The widest row takes `per_row` workgroups of the
+    widest kernel (256 words of its stream a workgroup of the store, 64 reference sample intervals a workgroup of the
+    inverse).  L = 2 per_row + 1 is above that and no multiple of it, so the cuts fall inside rows; L = per_row - 1 is
+    below it: no launch holds a whole row of the widest kind."""
+    fxs, buf, rows, aec = all_fixtures_call()
+    words = max((f.n_values * f.nbits + 31) // 32 for f in fxs)
+    groups = max(-(-f.n_values // (f.block * f.rsi * 64)) for f in fxs if f.flags & cc.PREPROCESS)
+    per_row = max(-(-words // 256), groups)
+    assert per_row > 2, per_row
+
+    def run():
+        out, rows_out = grib_unpack(device_bytes(buf), rows, aec, x_bytes=buf.size,
+                                    out=to_device(np.full(1 << 17, 0xFF, dtype=np.uint8)))
+        return out.to_host().tobytes(), rows_out.tobytes()
+    whole = run()
+    for limit in (2 * per_row + 1, per_row - 1):
+        _lib.call("smm_debug_set_grid_limit", limit)
+        try:
+            cut = run()
+        finally:
+            _lib.call("smm_debug_set_grid_limit", 0)
+        assert cut == whole, limit
 
 
 # ------------------------------------------------------------------------------------------------ the gather behind it

@@ -107,6 +107,19 @@ def test_rows_of_many_segments_and_a_mixed_call(hip):
     check_against_host(cases, out, rows_out, recs, out.nbytes)
 
 
+def test_many_short_rows_in_one_call(hip):
+    """150 rows of 3 to 14 values, every seventh of width 0: the scan over the rows of the call (layout kernel, 64 rows at
+    a step) takes three steps, and rows' offsets carry over both step boundaries."""
+    rng = np.random.default_rng(11)
+    cases = [Constant if i % 7 == 3 else
+             ec.Case(f"short{i}", rng.integers(0, 1 << (1 + i % 16), 3 + i % 12), 1 + i % 16, (8, 16, 32, 64)[i % 4], 1 + i % 5, i % 2)
+             for i in range(150)]
+    x, x_bytes, rows, want = pack_call(cases)
+    out, rows_out, recs = grib_aec_pack(x, rows, want, x_bytes=x_bytes)
+    check_against_host(cases, out, rows_out, recs, out.nbytes)
+    assert int(recs["byte_off"][64]) > 0 and int(recs["byte_off"][128]) > int(recs["byte_off"][64])
+
+
 def test_round_trip_on_the_device(hip):
     """grib_unpack(grib_aec_pack(x)) is x: the integers come back at their width, byte for byte."""
     cases = [c for c in cc.fixtures() + ec.edge_cases()]

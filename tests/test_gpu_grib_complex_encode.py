@@ -136,6 +136,18 @@ def test_long_rows(hip):
     assert int(recs["n_groups"][0]) == 5000
 
 
+def test_many_short_rows_in_one_call(hip):
+    """150 rows of 3 to 14 values, every seventh of width 0: the scan over the rows of the call (layout kernel, 64 rows at
+    a step) takes three steps, and rows' offsets carry over both step boundaries."""
+    rng = np.random.default_rng(11)
+    cases = [PackCase(f"short{i}", np.zeros(3 + i % 12) if i % 7 == 3 else rng.integers(0, 1 << (1 + i % 16), 3 + i % 12),
+                      i % 3, (8, 16, 32, 64)[i % 4], nbits=0 if i % 7 == 3 else 1 + i % 16) for i in range(150)]
+    x, x_bytes, rows, want = pack_call(cases)
+    out, rows_out, recs = grib_cpx_pack(x, rows, want, x_bytes=x_bytes)
+    check_against_host(cases, out, rows_out, recs, out.nbytes)
+    assert int(recs["byte_off"][64]) > 0 and int(recs["byte_off"][128]) > int(recs["byte_off"][64])
+
+
 def test_round_trip_on_the_device(hip):
     """grib_unpack_cpx(grib_cpx_pack(x)) is x: the integers come back at their minimal width, byte for byte."""
     cases = [c for c in every_case() if c.n_values <= 5000]
