@@ -1,6 +1,8 @@
 """tests/far_cases.py catches what it is for: at modulus 2^12 a numpy stand-in for an apply has its read offsets, or
 its write offsets, narrowed in each of the four ways, in every layout the GPU test uses; the decoy / sentinel checks
-must fail for each of them and pass for the stand-in that narrows nothing."""
+must fail for each of them and pass for the stand-in that narrows nothing.  The byte-stream section does the same for
+the GRIB transcoders' buffers: the library's host decoders read every row at each narrowed byte offset, and a stand-in
+writes slots at narrowed output offsets."""
 import numpy as np
 import pytest
 
@@ -147,6 +149,107 @@ def test_the_host_layout_crosses_2_32_bytes_and_2_31_elements(itemsize):
     wins = fc.windows(lay, itemsize)
     assert all(e <= o or s >= o + lay.row_len for s, e in wins for o in lay.offsets)
     assert fc.aliases(lay.offsets[4], itemsize, lay.size) and (itemsize == 2 or fc.aliases(lay.offsets[2], 4, lay.size))
+
+
+# ------------------------------------------------------------------ byte streams at far byte offsets
+
+def _cpx_rows():
+    """Short complex-packed rows (the streams must fit below modulus / 4 = 1024 bytes): orders 2, 1 and 0 far, the alias
+    of the second, one near row."""
+    from tests import complex_cases as xc
+    rng = np.random.default_rng(21)
+    smooth = (2000 + 900 * np.sin(np.arange(60) / 7.0)).astype(np.int64) + rng.integers(0, 9, 60)
+    far = [xc.Case("far_order2", smooth, 2, xc.even(60, 5)), xc.Case("far_order1", smooth[::-1] + 3, 1, xc.even(60, 4)),
+           xc.Case("far_order0", rng.integers(0, 4096, 48), 0, xc.even(48, 6))]
+    return far + [fc.cpx_alias(far[1]), xc.case("n3_order2")]
+
+
+def _aec_rows():
+    from tests import ccsds_cases as cc
+    far = [cc.fixture("edge_n43_w12_pp1"), cc.fixture("edge_n43_w32_pp0"), cc.fixture("edge_n9_w16_pp0")]
+    return far + [fc.aec_alias(far[1]), cc.fixture("edge_n16_w17_pp0")]
+
+
+def _cpx_decode(buf, row, off):
+    from smmregrid_amd.griblite import cpx_decode
+    return cpx_decode(buf, row.record(off)), np.asarray(row.X, dtype=np.uint32)
+
+
+def _aec_decode(buf, row, off):
+    from smmregrid_amd.griblite import aec_decode
+    from tests.ccsds_cases import record
+    rec = record(off, row.stream.size, row.n_values, row.nbits, row.block, row.rsi, row.flags)
+    return aec_decode(buf, rec), np.asarray(row.values, dtype=np.uint32)
+
+
+@pytest.mark.parametrize("codec", ["cpx", "aec"])
+def test_a_stream_read_at_a_narrowed_byte_offset_is_caught(codec):
+    """The buffer of the GPU test's input-far cases at modulus 2^12, through the library's host decoders: every true row
+    decodes to its integers with its record; with its byte_off narrowed in each way that keeps it inside the buffer it
+    is refused or decodes to other integers -- and the row whose narrowed offset is the alias row's decodes CLEANLY to
+    the alias row's integers, the case that noise in the decoys cannot stand for."""
+    rows, decode = (_cpx_rows(), _cpx_decode) if codec == "cpx" else (_aec_rows(), _aec_decode)
+    lay = fc.stream_layout([r.stream.size for r in rows[:3]], [r.stream.size for r in rows[4:]], M, G)
+    assert lay.far[0] > M and lay.far[1] > 2 * M and lay.far[1] % 2 == 1 and lay.far[2] > 8 * M
+    assert lay.alias == lay.far[1] % (2 * M) and lay.x_bytes == lay.far[2] + rows[2].stream.size
+    buf = fc.stream_buffer(lay, [r.stream for r in rows], seed=3)
+    seen, clean = set(), set()
+    for off, row in zip(lay.offsets(), rows):
+        got, want = decode(buf, row, off)
+        assert np.array_equal(got, want), row
+        for kind, at in fc.stream_images(off, lay.x_bytes, M).items():
+            seen.add(kind)
+            try:
+                got, _ = decode(buf, row, at)
+            except ValueError:
+                continue
+            assert not np.array_equal(got, want), (row, kind, at)
+            if at == lay.alias:
+                assert np.array_equal(got, np.asarray(rows[3].X, dtype=np.uint32)), (row, kind)
+                clean.add(kind)
+    assert seen == set(fc.STREAM_TRUNCATIONS), seen
+    assert clean == {"elems31", "elems32", "bytes32", "sext32", "bits32"}, clean      # far[1] under all that move it
+
+
+def test_stream_images_by_hand():
+    big = 1 << 40
+    assert fc.stream_images((1 << 31) + 77, big) == {"elems31": 77, "bits32": 77}
+    assert fc.stream_images((1 << 32) + 77, big) == {k: 77 for k in ("elems31", "elems32", "bytes32", "sext32", "bits32")}
+    assert fc.stream_images((1 << 34) + 77, big) == {k: 77 for k in fc.STREAM_TRUNCATIONS}
+    assert fc.stream_images((1 << 29) + 77, big) == {"bits32": 77} and fc.stream_images(77, big) == {}
+    lay = fc.stream_layout([4100, 8200, 3001], [4100, 9])
+    assert [o >> 31 for o in lay.far] == [1, 2, 8] and lay.far[1] % 2 == 1 and lay.alias == lay.far[1] - (1 << 32)
+    assert (1 << 34) < lay.x_bytes < (1 << 34) + (1 << 20) and all(o < 1 << 20 for o in lay.near)
+
+
+def _slots(kind=None):
+    """[A, spacer, B, spacer, C] laid back to back, 4-byte aligned, as the packers lay their streams: B begins past
+    modulus bytes, C past twice that.  A stand-in writes every row at its offset narrowed by `kind`; a write that
+    leaves the buffer -- a fault on the device -- writes nothing."""
+    rng = np.random.default_rng(8)
+    rows = [rng.integers(0, 0x40, n, dtype=np.uint8) for n in (41, M + 50, 43, M + 10, 37)]
+    offs = np.concatenate([[0], np.cumsum([fc._round4(r.size) for r in rows])])
+    used, size = int(offs[-1]), int(offs[-1]) + 64
+    assert offs[2] >= M and offs[4] >= 2 * M
+    buf = np.full(size, fc.SENTINEL, np.uint8)
+    for off, r in zip(offs, rows):
+        at = int(off) if kind is None else fc.truncate(int(off), 1, kind, M)
+        if 0 <= at and at + r.size <= size:
+            buf[at:at + r.size] = r
+    checked = [(int(offs[i]), rows[i]) for i in (0, 2, 4)] + [(int(offs[i]), rows[i][:16]) for i in (1, 3)] + \
+        [(int(offs[i]) + rows[i].size - 16, rows[i][-16:]) for i in (1, 3)]
+    return lambda: fc.check_slots(lambda s, e: buf[s:e], checked, used, size, "slots")
+
+
+def test_a_slot_written_at_a_narrowed_offset_is_caught():
+    _slots()()
+    for kind in fc.TRUNCATIONS:
+        with pytest.raises(AssertionError, match="bytes differ"):
+            _slots(kind)()
+    buf = np.full(64, fc.SENTINEL, np.uint8)
+    buf[40] = 0
+    with pytest.raises(AssertionError, match="byte 40 behind the 32 bytes used"):
+        fc.check_slots(lambda s, e: buf[s:e], [], 32, 64)
 
 
 def test_aliases_by_hand():

@@ -1,6 +1,12 @@
-"""Every device entry at offsets past 2^31 and 2^32 elements (and past 2^32 bytes): a handful of batch rows on a huge
-pitch, so the arithmetic stays tiny and only the addresses are large (tests/far_cases.py; tests/test_far_cases.py
-shows that the checks catch an offset narrowed in any of four ways).
+"""The device entries at offsets past 2^31 and 2^32 elements (and past 2^32 bytes), in two files.  This one: smm_apply
+(tile and SELL kernels, every field and result type), smm_apply_sb, smm_group_apply, smm_group_apply_sb, smm_apply_grib,
+smm_apply_grib_bm, smm_fill_random, and the host pipelines smm_apply_host, smm_apply_host_cf, smm_group_apply_host and
+smm_apply_host_grib.  tests/test_gpu_grib_far_offsets.py: the GRIB entries that came later -- smm_apply_grib_na,
+smm_group_apply_grib, smm_group_apply_grib_na, smm_grib_pack and the four transcoders smm_grib_cpx_unpack,
+smm_grib_aec_unpack, smm_grib_cpx_pack, smm_grib_aec_pack -- with the buffers, the fixture and the memory rule below.
+
+Here: a handful of batch rows on a huge pitch, so the arithmetic stays tiny and only the addresses are large
+(tests/far_cases.py; tests/test_far_cases.py shows that the checks catch an offset narrowed in any of four ways).
 
 The pattern of every case: X is one flat buffer filled with decoys -- `fill_random` values of another mean for
 float32 / float64, which is all `smm_fill_random` builds; the byte 0x44 for 2-byte elements (785.0 as bfloat16, 4.27 as
@@ -422,22 +428,25 @@ def test_group_apply_sb(far, side, level_launches):
 
 # ------------------------------------------------------------------ smm_apply_grib, smm_apply_grib_bm
 
-def grib_case():
+def grib_case(S=None, n_rows=5):
     """One buffer of just over 2^34 bytes.  Row 0: 16 bits at a byte offset just over 2^32.  Row 1: 12 bits at an odd
     byte offset just over 2^34 (a word index past 2^32).  Row 2: a bitmap that lies far and a stream that lies near.
-    Row 3: a stream that lies far and a bitmap that lies near.  Row 4: plain and near.
-    Returns (x_bytes, pieces [(byte offset, bytes)], rows, bitmaps, decoded float32 field)."""
-    op = sell_operator()[0]
-    S = op.n_src
+    Row 3: a stream that lies far and a bitmap that lies near.  Row 4: plain and near.  With n_rows = 6 (the grouped
+    entries of tests/test_gpu_grib_far_offsets.py: records (outer, level) of 3 x 2) row 4 lies past 2^34 instead and
+    row 5 past 2^32, so each of the two levels has a record past either.  S: the source cells (default: the SELL
+    operator's).  Returns (x_bytes, pieces [(byte offset, bytes)], rows, bitmaps, decoded float32 field)."""
+    S = sell_operator()[0].n_src if S is None else int(S)
     rng = np.random.default_rng([SEED, 7])
-    nbits = (16, 12, 16, 12, 16)
+    nbits = (16, 12, 16, 12, 16, 12)[:n_rows]
     specs = [dict(q=grib_cases.random_q(rng, S, nb), nbits=nb, E=int(rng.integers(-6, 3)), D=int(b == 1),
                   ref=float(np.float32(rng.normal(0.0, 300.0)))) for b, nb in enumerate(nbits)]
     masks = {2: rng.random(S) < 0.6, 3: rng.random(S) < 0.3}
     data_off = {0: (1 << 32) + 8, 1: (1 << 34) + 4097, 2: 4099, 3: (1 << 32) + (1 << 31) + 6, 4: 40002}
+    if n_rows == 6:
+        data_off.update({4: (1 << 34) + 40002, 5: (1 << 32) + 90003})
     bm_off = {2: (1 << 33) + 5, 3: 80001}
-    rows = np.zeros(5, GRIB_ROW_DTYPE)
-    bitmaps = np.zeros(5, GRIB_BITMAP_DTYPE)
+    rows = np.zeros(n_rows, GRIB_ROW_DTYPE)
+    bitmaps = np.zeros(n_rows, GRIB_BITMAP_DTYPE)
     bitmaps["bitmap_off"] = GRIB_NO_BITMAP
     pieces = []
     fld = np.stack([grib_cases.decode_ref(s["q"], s["ref"], s["E"], s["D"]) for s in specs])

@@ -75,6 +75,12 @@ def test_grib_unpack_gives_every_fixtures_integers_in_one_call(hip):
     out, rows_out = grib_unpack(device_bytes(buf), rows, aec, x_bytes=buf.size, out=filled)
     host = out.to_host()
     assert rows_out[-1].tobytes() == rows[-1].tobytes()
+    end = check_unpacked(host, rows, rows_out, fxs)
+    assert (host[end:] == 0xFF).all()                                      # nothing behind the layout is written
+
+
+def check_unpacked(host, rows, rows_out, fxs):
+    """Every fixture's slot and record, back to back from byte 0; returns where the last slot ends."""
     end = 0
     for i, f in enumerate(fxs):
         r = rows_out[i]
@@ -92,7 +98,7 @@ def test_grib_unpack_gives_every_fixtures_integers_in_one_call(hip):
         ref = GribField(twin, twin_row, (1, f.n_values), f.n_values).decode()
         assert got.tobytes() == ref.tobytes(), f
         end = off + slot
-    assert (host[end:] == 0xFF).all()                                      # nothing behind the layout is written
+    return end
 
 
 def test_grib_unpack_with_cut_launch_grids_gives_the_same_bytes(hip):

@@ -27,19 +27,27 @@ class Constant:
     name, values, nbits, block, rsi, flags, n_values = "constant", np.zeros(0, np.uint32), 0, 0, 0, 0, 77
 
 
+def pack_records(cases, offsets):
+    """(rows, wanted records) of the cases with their simple-packed twins at byte `offsets`."""
+    rows = np.zeros(len(cases), dtype=GRIB_ROW_DTYPE)
+    want = np.zeros(len(cases), dtype=GRIB_AEC_DTYPE)
+    for i, (c, at) in enumerate(zip(cases, offsets)):
+        rows[i] = (at, 1.5, 0.25, 10.0, c.nbits, 0)
+        want[i] = (0xDEAD, 0xBEEF, c.n_values, c.nbits, c.block, c.rsi, c.flags, 0)      # byte_off / byte_len are not read
+    return rows, want
+
+
 def pack_call(cases, gap=3):
     """The cases as the rows of one smm_grib_aec_pack call: their simple-packed twins at odd offsets with garbage
     between them.  Returns (device bytes, x_bytes, rows, wanted records)."""
-    rows = np.zeros(len(cases), dtype=GRIB_ROW_DTYPE)
-    want = np.zeros(len(cases), dtype=GRIB_AEC_DTYPE)
-    parts, at = [], 0
+    parts, at, offsets = [], 0, []
     for i, c in enumerate(cases):
         twin = cc.pack_bits(c.values, c.nbits)
         parts += [np.full(gap + i % 2, 0xA5, np.uint8), twin]
         at += gap + i % 2
-        rows[i] = (at, 1.5, 0.25, 10.0, c.nbits, 0)
-        want[i] = (0xDEAD, 0xBEEF, c.n_values, c.nbits, c.block, c.rsi, c.flags, 0)      # byte_off / byte_len are not read
+        offsets.append(at)
         at += twin.size
+    rows, want = pack_records(cases, offsets)
     buf = np.concatenate(parts)
     padded = np.full((buf.size + 3) // 4 * 4, 0x5A, dtype=np.uint8)
     padded[:buf.size] = buf

@@ -52,20 +52,28 @@ def every_case():
     return out
 
 
+def pack_records(cases, offsets):
+    """(rows, wanted records) of the cases with their simple-packed streams at byte `offsets`."""
+    rows = np.zeros(len(cases), dtype=GRIB_ROW_DTYPE)
+    want = np.zeros(len(cases), dtype=GRIB_CPX_DTYPE)
+    for i, (c, at) in enumerate(zip(cases, offsets)):
+        rows[i] = (at, 1.5, 0.25, 10.0, c.nbits, 0)
+        # only n_values, nbits, order and length_ref are read
+        want[i] = (0xDEAD, 0xBEEF, c.n_values, 77, c.nbits, 9, 9, c.L, 9, 9, 9, c.order, 9, 0)
+    return rows, want
+
+
 def pack_call(cases, gap=3):
     """The cases as the rows of one smm_grib_cpx_pack call: their simple-packed streams at odd offsets with garbage
     between them.  Returns (device bytes, x_bytes, rows, wanted records)."""
-    rows = np.zeros(len(cases), dtype=GRIB_ROW_DTYPE)
-    want = np.zeros(len(cases), dtype=GRIB_CPX_DTYPE)
-    parts, at = [], 0
+    parts, at, offsets = [], 0, []
     for i, c in enumerate(cases):
         twin = pack_bits(c.X, c.nbits)
         parts += [np.full(gap + i % 2, 0xA5, np.uint8), twin]
         at += gap + i % 2
-        rows[i] = (at, 1.5, 0.25, 10.0, c.nbits, 0)
-        # only n_values, nbits, order and length_ref are read
-        want[i] = (0xDEAD, 0xBEEF, c.n_values, 77, c.nbits, 9, 9, c.L, 9, 9, 9, c.order, 9, 0)
+        offsets.append(at)
         at += twin.size
+    rows, want = pack_records(cases, offsets)
     buf = np.concatenate(parts)
     padded = np.full((buf.size + 3) // 4 * 4, 0x5A, dtype=np.uint8)
     padded[:buf.size] = buf
