@@ -191,7 +191,7 @@ enum { SMM_GRIB_AEC_OK = 0, SMM_GRIB_AEC_EXHAUSTED = 1, SMM_GRIB_AEC_INVALID = 2
  * parameters.  The stream decodes to n_values integers X in [0, 2^32) -- the q of smm_grib_row_t's rule; the rule is the
  * text of smmregrid_amd/csrc/smm_grib_cpx.hpp.  order == SMM_GRIB_CPX_SIMPLE marks a row that is simple-packed already:
  * nothing else of its record is looked at, its smm_grib_row_t says it all.  Missing value management (octet 23) is not
- * in the record: the reader refuses everything but 0. */
+ * in the record: the _mv entries take it in a parallel array, the others decode 0 only. */
 #define SMM_GRIB_CPX_SIMPLE (-1)
 typedef struct smm_grib_cpx_t {   /* one batch row = one GRIB field, 72 B */
   uint64_t byte_off;      /* of the stream's first byte (octet 6 of section 7), from x */
@@ -753,6 +753,41 @@ int smm_grib_cpx_unpack(int device, const void* x, int64_t x_bytes, const smm_gr
                         const smm_grib_row_t* rows_in /* host */, int64_t n_batch, void* out, int64_t out_bytes,
                         smm_grib_row_t* rows_out /* host */, void* stream);
 int smm_grib_cpx_decode_host(const void* x_host, int64_t x_bytes, const smm_grib_cpx_t* rec, uint32_t* values, int* status);
+
+/*
+ * The three entries above for rows with MISSING VALUES INSIDE THE GROUPS (section 5's octet 23, missing value management
+ * 1 or 2: what wgrib2 writes for undefined points instead of a section-6 bitmap; the rule is the text of
+ * smmregrid_amd/csrc/smm_grib_cpx.hpp).  smm_grib_cpx_t stays as it is: the octet travels in `mvm`, a HOST array of
+ * n_batch values 0, 1 or 2 parallel to recs, or NULL for all zero -- then each entry is the one above in every respect.
+ * The device step turns "codes inside the groups" into "a bitmap plus the compacted integers", the form
+ * smm_apply_grib_bm / _na take: both kinds of missing become a 0 bit, hence a float32 NaN; the substitute values of
+ * octets 24 - 31 are not read.
+ *   smm_grib_cpx_layout_mv       a coded row with mvm != 0 gets its slot of n_values * 4 bytes and, behind it, a bitmap
+ *                                slot of ceil(n_values / 8) bytes rounded up to 4.  bitmap_off[b] (may be NULL) = where
+ *                                that slot starts in `out`, SMM_GRIB_NO_BITMAP for a row without one.
+ *   smm_grib_cpx_unpack_mv       bitmaps_out: a HOST array of n_batch records.  A row with mvm != 0: its slot receives
+ *                                its P present integers big-endian at the row's own minimal width w_b, every byte of
+ *                                ceil(P * w_b / 8) rounded up to 4 written; its bitmap slot receives n_values bits, MSB
+ *                                first, zero-padded, every byte of the slot written; bitmaps_out[b] = {the bitmap slot's
+ *                                offset in out, P}; rows_out[b].nbits = w_b.  A row with mvm == 0 and a row marked
+ *                                SMM_GRIB_CPX_SIMPLE get {SMM_GRIB_NO_BITMAP, n_values} and the bytes of
+ *                                smm_grib_cpx_unpack.  Scratch: 8 B per value and 16 B per group as above, and for a row
+ *                                with mvm != 0 another 8 B per value and 4 B per 256 values (its integers pass through a
+ *                                second array on their way to their ranks).
+ *   smm_grib_cpx_decode_host_mv  mvm: one value, or NULL.  present[n_values] receives a flag per coded position,
+ *                                *n_present = P, values[n_values] the P compacted integers (zero behind them).  A row
+ *                                that does not end ok leaves zeros everywhere.
+ * SMM_ERR_INVALID before any device is touched, beside what the entries above refuse: an mvm value above 2 (the row is
+ * named), a null bitmaps_out, out_bytes below this layout.
+ */
+int smm_grib_cpx_layout_mv(const smm_grib_cpx_t* recs, const uint8_t* mvm, int64_t n_batch, uint64_t* byte_off,
+                           uint64_t* bitmap_off, uint64_t* total_bytes);
+int smm_grib_cpx_unpack_mv(int device, const void* x, int64_t x_bytes, const smm_grib_cpx_t* recs /* host */,
+                           const uint8_t* mvm /* host, or NULL */, const smm_grib_row_t* rows_in /* host */, int64_t n_batch,
+                           void* out, int64_t out_bytes, smm_grib_row_t* rows_out /* host */,
+                           smm_grib_bitmap_t* bitmaps_out /* host */, void* stream);
+int smm_grib_cpx_decode_host_mv(const void* x_host, int64_t x_bytes, const smm_grib_cpx_t* rec, const uint8_t* mvm,
+                                uint32_t* values, uint8_t* present, uint64_t* n_present, int* status);
 
 /*
  * The way back: simple-packed streams on the device coded as complex-packed streams (templates 5.2 / 5.3), behind the

@@ -35,11 +35,18 @@ CCSDS = Coded("ccsds", "CCSDS records", GRIB_AEC_DTYPE, _lib.GribAecStruct, "smm
               lambda recs, n_val, nbits: align4((n_val * nbits + 7) // 8) + 4 * n_val,
               "smm_grib_aec_pack_bound", "smm_grib_aec_pack")
 # a record whose order is GRIB_CPX_SIMPLE marks a simple-packed row; a coded row costs its slot of 4 B per value and
-# 8 B per value plus 16 B per group of scratch
+# 8 B per value plus 16 B per group of scratch; one with missing values inside its groups (`cpx_missing_cost`) also its
+# bitmap slot, 8 B more per value -- the integers pass through a second array on their way to their ranks -- and 4 B per
+# 256 values
 CPX = Coded("cpx", "complex-packing records", GRIB_CPX_DTYPE, _lib.GribCpxStruct, "smm_grib_cpx_layout",
             "smm_grib_cpx_unpack", lambda recs, rows: recs["order"] != GRIB_CPX_SIMPLE,
             lambda recs, n_val, nbits: 12 * n_val + 16 * recs["n_groups"].astype(np.int64) + 256,
             "smm_grib_cpx_pack_bound", "smm_grib_cpx_pack")
+
+
+def cpx_missing_cost(n_val):
+    """Device bytes a complex-packed row with missing values inside its groups costs beside `CPX.device_cost`."""
+    return align4((n_val + 7) // 8) + 8 * n_val + 4 * ((n_val + 255) // 256)
 
 
 # What differs between the kinds of coded results (`apply_host_grib(grib_out=GribEncode(..., ccsds= / cpx=))`).  attr: the
@@ -90,17 +97,40 @@ def records(kind, recs, rows):
     return recs
 
 
-def _layout_total(entry, kind, recs):
-    """Bytes the host-only layout entry (or the encoder's bound) gives for the records."""
+def _layout_total(entry, kind, recs, missing=None):
+    """Bytes the host-only layout entry (or the encoder's bound) gives for the records; missing: the complex-packed rows'
+    missing value management (smm_grib_cpx_layout_mv), or None."""
     total = ctypes.c_uint64(0)
-    _lib.call(entry, _cast(recs, kind.struct), recs.size, None, ctypes.byref(total))
+    if missing is not None:
+        _lib.call("smm_grib_cpx_layout_mv", _cast(recs, kind.struct), missing.ctypes.data_as(_lib._u8p), recs.size, None, None,
+                  ctypes.byref(total))
+    else:
+        _lib.call(entry, _cast(recs, kind.struct), recs.size, None, ctypes.byref(total))
     return int(total.value)
 
 
-def coded_rows(kind, recs, rows):
+def missing_of(missing, rows):
+    """One uint8 per row: the complex-packed rows' missing value management, or None."""
+    if missing is None:
+        return None
+    missing = np.ascontiguousarray(missing, dtype=np.uint8).ravel()
+    if missing.size != rows.size:
+        raise ValueError(f"{missing.size} missing-value-management values for {rows.size} rows")
+    return missing
+
+
+def refuse_bitmap_with_missing(bitmaps, missing, coded):
+    """A coded row with a bitmap of its own and missing values inside its groups is not composed on the device."""
+    if bitmaps is not None and missing is not None and \
+            ((bitmaps["bitmap_off"] != GRIB_NO_BITMAP) & (missing != 0) & coded).any():
+        raise ValueError("a row has a bitmap and missing values inside its groups: decode it on the host")
+
+
+def coded_rows(kind, recs, rows, missing=None):
     """(which rows have a coded stream, bytes of their transcoded streams)."""
     idx = np.flatnonzero(kind.is_coded(recs, rows))
-    return idx, _layout_total(kind.layout_entry, kind, np.ascontiguousarray(recs[idx]))
+    return idx, _layout_total(kind.layout_entry, kind, np.ascontiguousarray(recs[idx]),
+                              None if missing is None else np.ascontiguousarray(missing[idx]))
 
 
 # ---------------------------------------------------------------------------------------------- packed bytes on the device
@@ -119,24 +149,35 @@ def packed_bytes(x, x_bytes, who, raw=False):
     return ctypes.c_void_p(int(x)), int(x_bytes)
 
 
-def transcode_args(who, kind, bound_entry, device_bytes, rows, recs, x_bytes, out):
+def transcode_args(who, kind, bound_entry, device_bytes, rows, recs, x_bytes, out, missing=None):
     """What `unpack_device` and `pack_device` check alike: (pointer, n_bytes) of the bytes, the row
-    and `kind` records, and `out` -- given or fresh -- holding at least what bound_entry says the records need."""
+    and `kind` records, `out` -- given or fresh -- holding at least what bound_entry says the records need, and
+    `missing` as one uint8 per row (or None)."""
     x_ptr, n_bytes = packed_bytes(device_bytes, x_bytes, who)
     rows, _ = grib_rows(rows)
     recs = records(kind, recs, rows)
-    total = _layout_total(bound_entry, kind, recs)
+    missing = missing_of(missing, rows)
+    total = _layout_total(bound_entry, kind, recs, missing)
     if out is None:
         out = DeviceArray((max(total, 4),), np.uint8)
     elif not isinstance(out, DeviceArray) or out.dtype != np.uint8 or out.nbytes < total:
         raise ValueError(f"out must be a uint8 DeviceArray of at least {total} bytes")
-    return x_ptr, n_bytes, rows, recs, out
+    return x_ptr, n_bytes, rows, recs, out, missing
 
 
-def unpack_device(who, kind, device_bytes, rows, recs, x_bytes=None, out=None, stream=None):
-    """`grib_unpack` (CCSDS) and `grib_unpack_cpx` (CPX)."""
-    x_ptr, n_bytes, rows, recs, out = transcode_args(who, kind, kind.layout_entry, device_bytes, rows, recs, x_bytes, out)
+def unpack_device(who, kind, device_bytes, rows, recs, x_bytes=None, out=None, stream=None, missing=None, with_bitmaps=False):
+    """`grib_unpack` (CCSDS) and `grib_unpack_cpx` (CPX); with_bitmaps: `grib_unpack_cpx_mv` -- missing: the rows' missing
+    value management or None --, which returns the rows' bitmap records as well."""
+    x_ptr, n_bytes, rows, recs, out, missing = transcode_args(who, kind, kind.layout_entry, device_bytes, rows, recs, x_bytes, out,
+                                                              missing)
     rows_out = np.zeros(rows.size, dtype=GRIB_ROW_DTYPE)
+    if with_bitmaps:
+        bitmaps_out = np.zeros(rows.size, dtype=GRIB_BITMAP_DTYPE)
+        _lib.call("smm_grib_cpx_unpack_mv", device.current_device(), x_ptr, n_bytes, _cast(recs, kind.struct),
+                  None if missing is None else missing.ctypes.data_as(_lib._u8p), _cast(rows, _lib.GribRowStruct), rows.size,
+                  ctypes.c_void_p(out.ptr), out.nbytes, _cast(rows_out, _lib.GribRowStruct),
+                  _cast(bitmaps_out, _lib.GribBitmapStruct), _stream_handle(stream))
+        return out, rows_out, bitmaps_out
     _lib.call(kind.unpack_entry, device.current_device(), x_ptr, n_bytes, _cast(recs, kind.struct),
               _cast(rows, _lib.GribRowStruct), rows.size, ctypes.c_void_p(out.ptr), out.nbytes,
               _cast(rows_out, _lib.GribRowStruct), _stream_handle(stream))
@@ -146,7 +187,7 @@ def unpack_device(who, kind, device_bytes, rows, recs, x_bytes=None, out=None, s
 def pack_device(who, kind, device_bytes, rows, recs, x_bytes=None, out=None, stream=None):
     """`grib_aec_pack` (CCSDS) and `grib_cpx_pack` (CPX): (out cut to the bytes used, the rows with byte_off at their
     streams, the records of the streams written)."""
-    x_ptr, n_bytes, rows, recs, out = transcode_args(who, kind, kind.bound_entry, device_bytes, rows, recs, x_bytes, out)
+    x_ptr, n_bytes, rows, recs, out, _ = transcode_args(who, kind, kind.bound_entry, device_bytes, rows, recs, x_bytes, out)
     recs_out = np.zeros(rows.size, dtype=kind.dtype)
     used = ctypes.c_uint64(0)
     _lib.call(kind.pack_entry, device.current_device(), x_ptr, n_bytes, _cast(rows, _lib.GribRowStruct),
@@ -157,15 +198,30 @@ def pack_device(who, kind, device_bytes, rows, recs, x_bytes=None, out=None, str
     return DeviceArray((int(used.value),), np.uint8, ptr=out.ptr, base=out), rows_out, recs_out
 
 
-def unpack(kind, src, n_bytes, dst, shift, rows, recs, idx, stream):
-    """The coded streams of rows `idx` in src[:n_bytes] become simple-packed streams in dst.  Returns the row table with
+def unpack(kind, src, n_bytes, dst, shift, rows, recs, idx, stream, missing=None, bitmaps=None, n_src=0):
+    """The coded streams of rows `idx` in src[:n_bytes] become simple-packed streams in dst.  Returns (the row table with
     those rows pointing at `shift` + their place in dst (complex-packed ones with the width their integers were stored
-    at), the others as they were."""
-    _, rows_c = unpack_device("apply_grib", kind, src, rows[idx], recs[idx], x_bytes=n_bytes, out=dst, stream=stream)
+    at), the others as they were; the bitmap table).  missing: None, or the rows' missing value management (complex
+    packing): a row with missing != 0 gets the bitmap the device step wrote behind its slot -- offsets shifted like
+    byte_off, a table of GRIB_NO_BITMAP over n_src points made first when the call has none -- and the count of its
+    present values."""
+    if missing is None or not missing[idx].any():
+        _, rows_c = unpack_device("apply_grib", kind, src, rows[idx], recs[idx], x_bytes=n_bytes, out=dst, stream=stream)
+    else:
+        _, rows_c, bm_c = unpack_device("apply_grib", kind, src, rows[idx], recs[idx], x_bytes=n_bytes, out=dst, stream=stream,
+                                        missing=missing[idx], with_bitmaps=True)
+        if bitmaps is None:
+            bitmaps = np.zeros(rows.size, dtype=GRIB_BITMAP_DTYPE)
+            bitmaps["bitmap_off"], bitmaps["n_values"] = GRIB_NO_BITMAP, n_src
+        else:
+            bitmaps = bitmaps.copy()
+        written = np.flatnonzero(bm_c["bitmap_off"] != GRIB_NO_BITMAP)
+        bm_c["bitmap_off"][written] += np.uint64(shift)
+        bitmaps[idx[written]] = bm_c[written]
     rows = rows.copy()
     rows_c["byte_off"] += np.uint64(shift)
     rows[idx] = rows_c
-    return rows
+    return rows, bitmaps
 
 
 # ---------------------------------------------------------------------------------------------- entries and results
@@ -216,16 +272,18 @@ def host_grib_out(entry, handle, buf, rows_p, bm_p, grib_out, out, shape, *tail)
 # staged, every piece at a 4-byte-aligned offset --, the staged bytes, the row / coded / bitmap records with byte_off and
 # bitmap_off rewritten to the staged offsets (recs: None without a kind, bitmaps: None without bitmaps), the chunk's
 # coded rows and the bytes of their transcoded streams.
-Chunk = namedtuple("Chunk", "r0 r1 pieces staged_bytes rows recs bitmaps coded_idx coded_bytes")
+Chunk = namedtuple("Chunk", "r0 r1 pieces staged_bytes rows recs bitmaps coded_idx coded_bytes missing",
+                   defaults=(None,))
 
 
-def plan_chunks(buf_size, rows, bitmaps, kind, recs, n_src, n_dst, chunk_rows, target, extra_cost=0):
+def plan_chunks(buf_size, rows, bitmaps, kind, recs, n_src, n_dst, chunk_rows, target, extra_cost=0, missing=None):
     """The chunks of consecutive rows an `apply_host_grib` call with coded rows (kind, recs) or a CCSDS-packed result
     (kind None: every row is simple-packed) goes through, one after the other (an iterator of `Chunk`); host only.  A row
     costs its staged bytes (coded or simple-packed stream, bitmap), for a coded row kind.device_cost, its float64 Y and
     extra_cost (bytes per row, what the caller puts beside them); a chunk takes rows while their cost stays within
     `target` bytes, and at least one; chunk_rows > 0 fixes the rows.  A bitmap several rows of a chunk share is staged
-    once in it (and again in the next chunk)."""
+    once in it (and again in the next chunk).  missing: None, or the complex-packed rows' missing value management: a row
+    with missing != 0 costs `cpx_missing_cost` more, and the chunk carries its part of the array."""
     n_batch, S = rows.size, n_src
     coded = np.zeros(n_batch, dtype=bool) if kind is None else kind.is_coded(recs, rows)
     has_bm = np.zeros(n_batch, dtype=bool) if bitmaps is None else bitmaps["bitmap_off"] != GRIB_NO_BITMAP
@@ -239,6 +297,9 @@ def plan_chunks(buf_size, rows, bitmaps, kind, recs, n_src, n_dst, chunk_rows, t
         in_off = np.where(coded, recs["byte_off"], in_off).astype(np.uint64)
         in_len = np.where(coded, recs["byte_len"].astype(np.int64), in_len).astype(np.int64)
         device_cost = np.where(coded, kind.device_cost(recs, n_val, nbits), 0)
+        if missing is not None:
+            refuse_bitmap_with_missing(bitmaps, missing, coded)
+            device_cost = device_cost + np.where(coded & (missing != 0), cpx_missing_cost(n_val), 0)
     bm_len = (S + 7) // 8
     if ((in_off.astype(object) + in_len.astype(object)) > buf_size).any() or \
             (has_bm.any() and (bitmaps["bitmap_off"][has_bm].astype(object) + bm_len > buf_size).any()):
@@ -265,12 +326,13 @@ def plan_chunks(buf_size, rows, bitmaps, kind, recs, n_src, n_dst, chunk_rows, t
                     pieces.append((at, off, bm_len))
                     at += align4(bm_len)
                 bm_c["bitmap_off"][i - r0] = seen[off]
-        idx_c, total = (np.zeros(0, dtype=np.intp), 0) if kind is None else coded_rows(kind, recs_c, rows_c)
-        yield Chunk(r0, r1, pieces, at, rows_c, recs_c, bm_c, idx_c, total)
+        miss_c = None if missing is None else missing[r0:r1].copy()
+        idx_c, total = (np.zeros(0, dtype=np.intp), 0) if kind is None else coded_rows(kind, recs_c, rows_c, miss_c)
+        yield Chunk(r0, r1, pieces, at, rows_c, recs_c, bm_c, idx_c, total, miss_c)
         r0 = r1
 
 
-def host_chunks(op, buf, rows, bitmaps, kind, recs, chunk_rows, extra_cost=0, **apply_kw):
+def host_chunks(op, buf, rows, bitmaps, kind, recs, chunk_rows, extra_cost=0, missing=None, **apply_kw):
     """The chunks of `plan_chunks`, one after the other: the chunk's bytes staged and copied to the device, its coded rows
     unpacked behind them into the same buffer (kind.unpack_entry), the device gather (`op.apply_grib` with apply_kw).
     Yields (first row, end row, the chunk's float64 Y on the device, the chunk's row records as the gather took them:
@@ -280,17 +342,19 @@ def host_chunks(op, buf, rows, bitmaps, kind, recs, chunk_rows, extra_cost=0, **
         bitmaps, _ = grib_bitmaps(bitmaps, rows.size)
     if kind is not None:
         recs = records(kind, recs, rows)
-        coded_rows(kind, recs, rows)      # the layout entry refuses a malformed record ahead of all device work
+        missing = missing_of(missing, rows)
+        coded_rows(kind, recs, rows, missing)      # the layout entry refuses a malformed record ahead of all device work
+        refuse_bitmap_with_missing(bitmaps, missing, kind.is_coded(recs, rows))
     free, _ = device.mem_info()
     target = min(256 << 20, max(free // 4, 1))
-    for c in plan_chunks(buf.size, rows, bitmaps, kind, recs, op.n_src, op.n_dst, chunk_rows, target, extra_cost):
+    for c in plan_chunks(buf.size, rows, bitmaps, kind, recs, op.n_src, op.n_dst, chunk_rows, target, extra_cost, missing):
         staged = np.zeros(max(c.staged_bytes, 4), dtype=np.uint8)
         for a, off, n in c.pieces:
             staged[a:a + n] = buf[off:off + n]
-        at, rows_c = c.staged_bytes, c.rows
+        at, rows_c, bm_c = c.staged_bytes, c.rows, c.bitmaps
         both = DeviceArray((max(at + c.coded_bytes, 4),), np.uint8)
         src = DeviceArray((staged.size,), np.uint8, ptr=both.ptr, base=both).copy_from_host(staged)
         if c.coded_idx.size:
             dst = DeviceArray((c.coded_bytes,), np.uint8, ptr=both.ptr + at, base=both)
-            rows_c = unpack(kind, src, at, dst, at, rows_c, c.recs, c.coded_idx, None)
-        yield c.r0, c.r1, op.apply_grib(both, rows_c, x_bytes=at + c.coded_bytes, bitmaps=c.bitmaps, **apply_kw), rows_c
+            rows_c, bm_c = unpack(kind, src, at, dst, at, rows_c, c.recs, c.coded_idx, None, c.missing, bm_c, op.n_src)
+        yield c.r0, c.r1, op.apply_grib(both, rows_c, x_bytes=at + c.coded_bytes, bitmaps=bm_c, **apply_kw), rows_c

@@ -137,6 +137,7 @@ _gcp = ctypes.POINTER(GribCpxStruct)
 GRIB_CPX_OK, GRIB_CPX_EXHAUSTED, GRIB_CPX_INVALID = 0, 1, 2
 GRIB_CPX_SIMPLE = -1      # smm_grib_cpx_t.order of a row that is simple-packed already
 _u64p = ctypes.POINTER(ctypes.c_uint64)
+_u8p = ctypes.POINTER(ctypes.c_uint8)     # a row's missing value management (the _mv entries), present flags
 
 # name -> argtypes; every entry point returns int status except the two noted
 SIGNATURES = {
@@ -212,6 +213,10 @@ SIGNATURES = {
     "smm_grib_cpx_layout": [_gcp, _i64, _u64p, _u64p],
     "smm_grib_cpx_unpack": [_int, _p, _i64, _gcp, _grp, _i64, _p, _i64, _grp, _p],
     "smm_grib_cpx_decode_host": [_p, _i64, _gcp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_int)],
+    "smm_grib_cpx_layout_mv": [_gcp, _u8p, _i64, _u64p, _u64p, _u64p],
+    "smm_grib_cpx_unpack_mv": [_int, _p, _i64, _gcp, _u8p, _grp, _i64, _p, _i64, _grp, _gbp, _p],
+    "smm_grib_cpx_decode_host_mv": [_p, _i64, _gcp, _u8p, ctypes.POINTER(ctypes.c_uint32), _u8p, _u64p,
+                                    ctypes.POINTER(_int)],
     "smm_grib_cpx_pack_bound": [_gcp, _i64, _u64p, _u64p],
     "smm_grib_cpx_pack": [_int, _p, _i64, _grp, _gcp, _i64, _p, _i64, _gcp, _u64p, _p],
     "smm_grib_cpx_encode_host": [ctypes.POINTER(ctypes.c_uint32), _i64, _gcp, _p, _i64, _u64p, _gcp],

@@ -10,8 +10,9 @@
 // hand to pin them.
 //   section 5, template 5.2 (47 octets)
 //     12-15 R (IEEE f32)   16-17 E   18-19 D (sign-magnitude)   20 nbits, the width of the group references
-//     21 type of original values   22 group splitting method   23 missing value management (only 0 is decoded)
-//     24-27, 28-31 missing value substitutes   32-35 NG, the number of groups   36 reference for group widths
+//     21 type of original values   22 group splitting method   23 missing value management m (0, 1 or 2: MISSING
+//     VALUES INSIDE THE GROUPS below)
+//     24-27, 28-31 missing value substitutes (not read)   32-35 NG, the number of groups   36 reference for group widths
 //     37 bits per stored group width   38-41 reference for group lengths   42 length increment
 //     43-46 true length of the last group   47 bits per stored scaled group length
 //   template 5.3 (49 octets) adds   48 order of spatial differencing (1 or 2)   49 n_oct, octets per extra descriptor
@@ -30,6 +31,24 @@
 //   the field  value = (R + X * 2^E) / 10^D: smm_grib_row_t's rule with q = X
 // THE SAME AS PREFIX SUMS (what the kernels compute): with a_0 = h_1, a_1 = h_2 - 2 h_1 (order 2 only) and
 // a_i = z_i + g from i = order on, X is the inclusive prefix sum of a taken `order` times, modulo 2^64.
+//
+// MISSING VALUES INSIDE THE GROUPS (octet 23, m = 1 or 2; decode_row_mv, the _mv entries).  The wording is g2c's
+// comunpack as recalled: no file written by NCEP's tools was at hand to pin it.  The row codes N = n_values positions;
+// s_i is the stored value of position i, w_g and r_g the width and reference of its group.  Every comparison is made in
+// 64 bits, so a code that would be negative (2^0 - 2) matches nothing.
+//   w_g > 0    position i is missing iff s_i == 2^w_g - 1, or m == 2 and s_i == 2^w_g - 2; else present with
+//              z = r_g + s_i.  (w_g == 1 under m == 2: both stored values are codes.  w_g == 32: the code is 0xFFFFFFFF)
+//   w_g == 0   the whole group is missing iff r_g == 2^nbits - 1, or m == 2 and r_g == 2^nbits - 2; else every position
+//              is present with z = r_g.  (nbits == 0: r_g = 0 = 2^0 - 1, the group is missing)
+//   compaction the present values in order form c_0 .. c_(P-1); spatial differencing is undone over THAT sequence, not
+//              over the positions: a_0 = h_1, a_1 = h_2 - 2 h_1 (order 2 only), a_k = c_k + g for k >= order, and X is
+//              the inclusive prefix sum of a taken `order` times modulo 2^64 over k < P.  The placeholders are the first
+//              `order` PRESENT values wherever they lie in the row.  P may be 0 or at most `order`: the prefix-sum form
+//              gives X_0 = h_1 and X_1 = h_2 as it stands
+//   the field  the cell at position i is (R + X_rank(i) * 2^E) / 10^D when present and a float32 NaN when missing, both
+//              kinds of missing alike; the substitutes of octets 24-31 are not read
+//   statuses   as below, over the P integers; a row with P == 0 is ok
+// What the device step makes of such a row is a simple-packed row with a bitmap: N bits, MSB first, and the P integers.
 //
 // A ROW ENDS AS (first that applies)
 //   kInvalid    NG > n_values -- a group of no values is no group; it bounds the scratch by the record
@@ -213,6 +232,86 @@ SMM_GRIB_HD int decode_row(const void* x, const Row& r, uint32_t* out) {
   }
   if (status != kOk)
     for (uint32_t i = 0; i < n; ++i) out[i] = 0;
+  return status;
+}
+
+// ---- MISSING VALUES INSIDE THE GROUPS.  Whether a position of a group of width w (0..32) and reference ref is missing
+// under m (1 or 2): s is its stored value (0 when w == 0), nbits the width of the references
+SMM_GRIB_HD bool is_missing(int m, uint64_t w, int nbits, uint64_t ref, uint64_t s) {
+  const uint64_t v = w > 0 ? s : ref;
+  const uint64_t top = ((uint64_t)1 << (w > 0 ? w : (uint64_t)nbits)) - 1;   // 2^0 - 1 = 0; top - 1 wraps to 2^64 - 1 then
+  return v == top || (m == 2 && v == top - 1);
+}
+
+// the scalar decode of a row with m = 0, 1 or 2: the P present integers into out[0, P), present[i] = 1 for a position
+// that has one (n_values flags), *n_present = P.  out holds n_values integers; those behind P are zero.  Returns the
+// row's status; not ok: out and present are all zero and P is 0.  m == 0 is decode_row with every position present.
+SMM_GRIB_HD int decode_row_mv(const void* x, const Row& r, int m, uint32_t* out, uint8_t* present, uint64_t* n_present) {
+  const uint32_t n = r.n_values, ng = r.n_groups;
+  *n_present = 0;
+  if (m == 0) {
+    const int status = decode_row(x, r, out);
+    for (uint32_t i = 0; i < n; ++i) present[i] = status == kOk;
+    if (status == kOk) *n_present = n;
+    return status;
+  }
+  if (n == 0) return kOk;
+  const Sections sec = sections(r);
+  const Stream s = stream_of(x, r);
+  int status = sec.status;
+  if (status == kOk) {
+    uint64_t sum_len = 0, sum_bits = 0;
+    for (uint32_t g = 0; g < ng && status == kOk; ++g) {
+      uint64_t w, len;
+      group_of(s, r, sec, g, &w, &len);
+      if (w > 32 || len > n) status = kInvalid;
+      sum_len += len;
+      sum_bits += w * len;
+      if (sum_len > n) status = kInvalid;
+    }
+    if (status == kOk && sum_len != n) status = kInvalid;
+    if (status == kOk && sum_bits > sec.bit_end - sec.data_bit) status = kExhausted;
+  }
+  uint32_t k = 0;   // present values so far
+  if (status == kOk) {
+    uint64_t h1, h2, gmin;
+    descriptors(s, r, &h1, &h2, &gmin);
+    uint64_t pos = sec.data_bit, x1 = 0, x2 = 0, high = 0;
+    uint32_t i = 0;
+    for (uint32_t g = 0; g < ng; ++g) {
+      uint64_t w, len;
+      group_of(s, r, sec, g, &w, &len);
+      const uint64_t ref = group_ref(s, r, sec, g);
+      for (uint64_t q = 0; q < len; ++q, ++i, pos += w) {
+        const uint64_t stored = s.peek(pos, (int)w);
+        present[i] = !is_missing(m, w, r.nbits, ref, stored);
+        if (!present[i]) continue;
+        const uint64_t z = ref + stored;
+        uint64_t X;
+        if (r.order <= 0)
+          X = z;
+        else if (k == 0)
+          X = h1;
+        else if (r.order == 1)
+          X = x1 + z + gmin;
+        else if (k == 1)
+          X = h2;
+        else
+          X = 2 * x1 - x2 + z + gmin;
+        x2 = x1;
+        x1 = X;
+        high |= X >> 32;
+        out[k++] = (uint32_t)X;
+      }
+    }
+    if (high) status = kInvalid;
+  }
+  if (status != kOk) {
+    for (uint32_t i = 0; i < n; ++i) present[i] = 0;
+    k = 0;
+  }
+  for (uint32_t i = k; i < n; ++i) out[i] = 0;
+  *n_present = k;
   return status;
 }
 

@@ -222,6 +222,27 @@ uint64_t grib_cpx_layout(const smm_grib_cpx_t* recs, int64_t n_batch, uint64_t* 
   return at;
 }
 
+bool check_grib_cpx_mvm(const uint8_t* mvm, int64_t n_batch, std::string& err) {
+  for (int64_t b = 0; mvm && b < n_batch; ++b)
+    if (mvm[b] > 2)
+      return err = "mvm[" + std::to_string(b) + "] (missing value management) must be 0, 1 or 2, not " + std::to_string((int)mvm[b]), false;
+  return true;
+}
+
+uint64_t grib_cpx_layout_mv(const smm_grib_cpx_t* recs, const uint8_t* mvm, int64_t n_batch, uint64_t* byte_off,
+                            uint64_t* bitmap_off) {
+  uint64_t at = 0;
+  for (int64_t b = 0; b < n_batch; ++b) {
+    const bool coded = recs[b].order != SMM_GRIB_CPX_SIMPLE;
+    if (byte_off) byte_off[b] = at;
+    if (coded) at += recs[b].n_values * 4;
+    const bool bitmapped = coded && mvm && mvm[b] != 0;
+    if (bitmap_off) bitmap_off[b] = bitmapped ? at : SMM_GRIB_NO_BITMAP;
+    if (bitmapped) at += ((recs[b].n_values + 7) / 8 + 3) / 4 * 4;
+  }
+  return at;
+}
+
 GribPackScratch grib_pack_scratch(int64_t n_dst, int64_t n_rows) {
   const size_t n = (size_t)std::max<int64_t>(n_rows, 0);
   const size_t segs = n * (size_t)smm_grib::bitmap_segments((uint64_t)n_dst);

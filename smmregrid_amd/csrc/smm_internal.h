@@ -268,6 +268,12 @@ uint64_t grib_aec_layout(const smm_grib_aec_t* recs, int64_t n_batch, uint64_t* 
 bool check_grib_cpx(const smm_grib_cpx_t* recs, int64_t n_batch, int64_t x_bytes, std::string& err);
 // the layout of the transcoded rows, n_values * 4 bytes per coded row: byte_off[b] (may be null); returns the bytes of all
 uint64_t grib_cpx_layout(const smm_grib_cpx_t* recs, int64_t n_batch, uint64_t* byte_off);
+// missing value management per row (the _mv entries; mvm may be null: all zero): a value above 2 is refused: false + err
+bool check_grib_cpx_mvm(const uint8_t* mvm, int64_t n_batch, std::string& err);
+// the layout with mvm: a coded row with mvm != 0 gets, behind its slot, a bitmap slot of ceil(n_values / 8) bytes rounded
+// up to 4; bitmap_off[b] (may be null) = where it starts, SMM_GRIB_NO_BITMAP for a row without one
+uint64_t grib_cpx_layout_mv(const smm_grib_cpx_t* recs, const uint8_t* mvm, int64_t n_batch, uint64_t* byte_off,
+                            uint64_t* bitmap_off);
 // Where a chunk's pieces lie in its staging buffer hx (ch.x_bytes bytes, 8-byte aligned), written into hx: the table first
 // -- the rows' records with byte_off the staged offset of the row's data -- then, with bitmaps, their records
 // (GribRowBitmap, smm_grib_codec.hpp: bitmap_off a staged offset too, table_off the place of the row's rank table among

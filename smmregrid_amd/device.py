@@ -586,6 +586,19 @@ def grib_unpack_cpx(device_bytes, rows, cpx, x_bytes=None, out=None, stream=None
     return _grib.unpack_device("grib_unpack_cpx", _grib.CPX, device_bytes, rows, cpx, x_bytes, out, stream)
 
 
+def grib_unpack_cpx_mv(device_bytes, rows, cpx, missing, x_bytes=None, out=None, stream=None):
+    """`grib_unpack_cpx` for fields whose missing values are coded inside the groups (smm_grib_cpx_unpack_mv).  missing:
+    one uint8 per field, section 5's missing value management -- 0, or 1 / 2 (the rule: smm_grib_cpx.hpp) -- or None
+    for all zero.  Returns (out, rows_out, bitmaps_out): a field with missing != 0 gets its P present integers at its
+    slot's start at their own minimal width and, behind the slot, a bitmap of n_values bits (MSB first);
+    bitmaps_out -- GRIB_BITMAP_DTYPE records -- says where that bitmap lies in `out` and P, and GRIB_NO_BITMAP for the
+    other fields: rows_out and bitmaps_out are what `SparseOperator.apply_grib(out, rows_out, bitmaps=bitmaps_out)`
+    takes."""
+    from . import _grib
+    return _grib.unpack_device("grib_unpack_cpx_mv", _grib.CPX, device_bytes, rows, cpx, x_bytes, out, stream,
+                               missing=missing, with_bitmaps=True)
+
+
 def grib_aec_pack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None):
     """Code simple-packed streams resident in HBM as the CCSDS streams of GRIB-2 template 5.42 on the device
     (smm_grib_aec_pack) -- the twin of `grib_unpack`, and what follows `grib_pack` when results leave CCSDS-packed.

@@ -24,7 +24,8 @@ product definition templates 4.0 / 4.1 / 4.8 / 4.11 (the leading octets they sha
 (simple packing, IEEE reference value) and 5.42 (CCSDS packing: the same rule on integers that an adaptive entropy
 coder compressed; decoded by the library's host decoder, smm_grib_aec_decode_host), 5.2 and 5.3 (complex packing, plain
 and with spatial differencing -- what NCEP writes; the same rule on integers coded in groups of their own widths,
-smm_grib_cpx_decode_host; missing value management 0 only), bitmap section, several fields per message (repeated
+smm_grib_cpx_decode_host; missing value management 1 and 2 -- missing values coded inside the groups, wgrib2's way
+for undefined points -- with `cpx_missing=True`, smm_grib_cpx_decode_host_mv, else refused), bitmap section, several fields per message (repeated
 sections 2 - 7).
 
 Anything else in a GRIB file (spherical harmonics, GRIB-1 second-order / JPEG / PNG packing, rotated or projected
@@ -120,6 +121,27 @@ def cpx_decode(buf, rec):
     return out
 
 
+def cpx_decode_mv(buf, rec, mvm):
+    """(the P present integers X (uint32), present: a bool per coded position) of one complex-packed stream whose
+    missing value management (section 5's octet 23) is `mvm` -- 1 or 2: missing values are codes inside the groups, by
+    the rule of smm_grib_cpx.hpp; 0: every position is present.  Decoded by the library on the host
+    (smm_grib_cpx_decode_host_mv; no GPU involved).  A row that does not end ok is a ValueError."""
+    from . import _lib
+    rec = np.ascontiguousarray(rec, dtype=GRIB_CPX_DTYPE).reshape(1)
+    raw = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf)
+    n = int(rec["n_values"][0])
+    out, present = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint8)
+    status, count, m = ctypes.c_int(0), ctypes.c_uint64(0), ctypes.c_uint8(int(mvm))
+    _lib.call("smm_grib_cpx_decode_host_mv", ctypes.c_void_p(raw.ctypes.data if raw.size else None), raw.size,
+              ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)), ctypes.byref(m),
+              out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), present.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+              ctypes.byref(count), ctypes.byref(status))
+    if status.value != _lib.GRIB_CPX_OK:
+        raise ValueError("complex-packed stream " + ("ends before its tables or its groups' bits do"
+                                                     if status.value == _lib.GRIB_CPX_EXHAUSTED else "is invalid"))
+    return out[:int(count.value)].copy(), present.astype(bool)
+
+
 def aec_encode(values, record, histogram=None):
     """The CCSDS stream (a uint8 array) of the unsigned integers `values`, coded by the library on the host
     (smm_grib_aec_encode_host; no GPU involved) by THE RULE OF THIS ENCODER of smm_grib_aec.hpp -- the oracle of
@@ -188,11 +210,13 @@ class GribField:
     GRIB_CPX_DTYPE record per field (a variable with complex-packed messages, templates 5.2 / 5.3): such a field's q are
     the integers its groups decode to (smm_grib_cpx_unpack ahead of the gather on the GPU, smm_grib_cpx_decode_host for
     `decode()`), and its row's nbits is the width of the group references, not of q; a record whose order is
-    GRIB_CPX_SIMPLE marks a simple-packed field among them."""
+    GRIB_CPX_SIMPLE marks a simple-packed field among them.  `cpx_missing` is None, or one uint8 per field beside `cpx`:
+    the field's missing value management (1 or 2: missing values are codes inside its groups -- they become NaN;
+    smm_grib_cpx_unpack_mv on the GPU, smm_grib_cpx_decode_host_mv for `decode()`)."""
 
     dtype = np.dtype(np.float32)
 
-    def __init__(self, buf, rows, shape, n_points, bitmaps=None, ccsds=None, cpx=None):
+    def __init__(self, buf, rows, shape, n_points, bitmaps=None, ccsds=None, cpx=None, cpx_missing=None):
         """n_points: grid points of one field -- the product of the trailing (horizontal) axes of `shape`."""
         self.buf = buf
         self.rows = np.ascontiguousarray(rows, dtype=GRIB_ROW_DTYPE).ravel()
@@ -207,6 +231,9 @@ class GribField:
             raise ValueError(f"{self.cpx.size} complex-packing records for {self.rows.size} GRIB fields")
         if self.cpx is not None and self.ccsds is not None:
             raise ValueError("a GribField holds CCSDS records or complex-packing records, not both")
+        self.cpx_missing = None if cpx_missing is None else np.ascontiguousarray(cpx_missing, dtype=np.uint8).ravel()
+        if self.cpx_missing is not None and (self.cpx is None or self.cpx_missing.size != self.rows.size):
+            raise ValueError("cpx_missing goes with cpx: one value per GRIB field")
         self.shape = tuple(int(n) for n in shape)
         self.n_points = int(n_points)
         if self.rows.size * self.n_points != int(np.prod(self.shape)):
@@ -230,7 +257,8 @@ class GribField:
                 bm = (int(self.bitmaps[i]["bitmap_off"]), int(self.bitmaps[i]["n_values"]))
             aec = None if self.ccsds is None or int(self.ccsds[i]["block_size"]) == 0 else self.ccsds[i]
             cpx = None if self.cpx is None or int(self.cpx[i]["order"]) == GRIB_CPX_SIMPLE else self.cpx[i]
-            out[i] = _decode_rule(self.buf, rule, self.n_points, bm, aec, cpx)
+            mvm = 0 if self.cpx_missing is None or cpx is None else int(self.cpx_missing[i])
+            out[i] = _decode_rule(self.buf, rule, self.n_points, bm, aec, cpx, mvm)
         return out.reshape(self.shape)
 
     def __array__(self, dtype=None, copy=None):
@@ -244,6 +272,8 @@ class GribField:
         return (f"<GribField {self.shape} float32, {self.rows.size} packed fields, widths "
                 f"{sorted(set(self.rows['nbits'].tolist()))}" + (f", {n_aec} CCSDS-packed" if n_aec else "")
                 + (f", {n_cpx} complex-packed" if n_cpx else "")
+                + (f" ({int((self.cpx_missing != 0).sum())} with missing values inside the groups)"
+                   if self.cpx_missing is not None else "")
                 + (f", {n_bm} with a bitmap>" if n_bm else ">"))
 
 
@@ -629,7 +659,7 @@ def _unpack_bits(raw, nbits, count):
     return bits.astype(np.uint64) @ (np.uint64(1) << np.arange(nbits - 1, -1, -1, dtype=np.uint64))
 
 
-def _decode_rule(buf, rule, count, bitmap=None, aec=None, cpx=None):
+def _decode_rule(buf, rule, count, bitmap=None, aec=None, cpx=None, mvm=0):
     """The float64 values of one message from its rule (file offset of the packed values, R, 2^E, 10^D, bit width):
     the statement the message classes evaluate, on the message's own bytes only.  bitmap: None, or (file offset of the
     bitmap's bytes, values in the stream) -- the values go to the points whose bit is set, the others are NaN.
@@ -640,6 +670,11 @@ def _decode_rule(buf, rule, count, bitmap=None, aec=None, cpx=None):
     if cpx is not None:
         if int(cpx["n_values"]) != n:
             raise ValueError(f"complex-packed stream of {int(cpx['n_values'])} values for {n} points")
+        if mvm:               # missing values coded inside the groups (such a message has no bitmap here)
+            q, there = cpx_decode_mv(buf, cpx, mvm)
+            values = np.full(n, np.nan)
+            values[there] = (ref + q.astype(np.float64) * scale) / ddiv
+            return values
         q = cpx_decode(buf, cpx).astype(np.float64)
     elif aec is not None and nbits:
         if int(aec["n_values"]) != n:
@@ -678,13 +713,14 @@ class _Field:
     raw_bitmap = None
     raw_aec = None        # the GRIB_AEC_DTYPE fields of a CCSDS-packed message (edition 2, template 5.42)
     raw_cpx = None        # the GRIB_CPX_DTYPE fields of a complex-packed message (edition 2, templates 5.2 / 5.3)
+    raw_mvm = 0           # ... its missing value management (1 or 2: missing values are codes inside the groups)
 
     def field_values(self, buf):
         if self.values is not None:
             return self.values
         aec = None if self.raw_aec is None else np.array(self.raw_aec, dtype=GRIB_AEC_DTYPE)
         cpx = None if self.raw_cpx is None else np.array(self.raw_cpx, dtype=GRIB_CPX_DTYPE)
-        return _decode_rule(buf, self.raw_rule, self.npoints, self.raw_bitmap, aec, cpx)
+        return _decode_rule(buf, self.raw_rule, self.npoints, self.raw_bitmap, aec, cpx, self.raw_mvm)
 
     def _set_grid(self, rep, ni, nj, la1, lo1, la2, lo2, n_gauss, scan, pl, tol):
         if scan & 0x20:
@@ -860,7 +896,7 @@ def _ccsds_template(sec5):
     return ref, scale, decimal, nbits, flags, block, rsi
 
 
-def _complex_template(sec5, drt, n_values):
+def _complex_template(sec5, drt, n_values, cpx_missing=False):
     """Data representation templates 5.2 (complex packing) and 5.3 (with spatial differencing) from section 5: (R, 2^E, D,
     width of the group references, then the fields of GRIB_CPX_DTYPE from n_groups to n_oct).  Octets 12 - 20 are those
     of template 5.0, 21 = type of the original values, 22 = group splitting method, 23 = missing value management,
@@ -875,8 +911,9 @@ def _complex_template(sec5, drt, n_values):
     ref = float(np.frombuffer(bytes(sec5[11:15]), dtype=">f4")[0])
     scale, decimal, nbits = 2.0 ** _sint(sec5[15:17]), _sint(sec5[17:19]), sec5[19]
     mvm = sec5[22]
-    if mvm != 0:
-        raise GribUnsupported(f"{what} with missing value management {mvm} (substitute values inside the groups)")
+    if mvm > 2 or (mvm != 0 and not cpx_missing):
+        raise GribUnsupported(f"{what} with missing value management {mvm} (missing values coded inside the groups; "
+                              "1 and 2 are decoded by open_dataset(..., cpx_missing=True))")
     n_groups, width_ref, width_bits = _uint(sec5[31:35]), sec5[35], sec5[36]
     length_ref, length_inc, length_last, length_bits = _uint(sec5[37:41]), sec5[41], _uint(sec5[42:46]), sec5[46]
     order, n_oct = (sec5[47], sec5[48]) if drt == 3 else (0, 0)
@@ -896,7 +933,7 @@ def _complex_template(sec5, drt, n_values):
     if n_values >= 2 ** 31:
         raise GribUnsupported(f"{what} of {n_values} values: fewer than 2^31 are decoded")
     return ref, scale, decimal, nbits, (n_groups, nbits, width_ref, width_bits, length_ref, length_inc, length_last, length_bits,
-                                        order, n_oct if order else 0)
+                                        order, n_oct if order else 0), mvm
 
 
 class _Field2(_Field):
@@ -904,7 +941,7 @@ class _Field2(_Field):
     edition = 2
 
     def __init__(self, discipline, sec1, sec3, sec4, sec5, sec6, sec7, prev_bitmap, data_pos=None, keep_raw=False,
-                 bitmap_pos=None, prev_raw_bitmap=None):
+                 bitmap_pos=None, prev_raw_bitmap=None, cpx_missing=False):
         """data_pos: file offset of section 7 (its packed values follow 5 octets later).  bitmap_pos: file offset of
         section 6 when bitmapped fields are kept raw too (its bits follow 6 octets later); prev_raw_bitmap: the
         `raw_bitmap` of the field before, for a field that reuses its bitmap."""
@@ -950,11 +987,12 @@ class _Field2(_Field):
             raise GribUnsupported(f"GRIB-2 data representation template 5.{drt} ({names.get(drt, 'not simple packing')})")
         aec = None         # CCSDS: (ccsdsFlags, ccsdsBlockSize, ccsdsRsi); a constant field (0 bits) has no stream
         cpx = None         # complex packing: GRIB_CPX_DTYPE's fields from n_groups to n_oct
+        mvm = 0            # ... its missing value management (octet 23): 1 or 2 with cpx_missing
         if drt == 42:
             ref, scale, decimal, nbits, *aec = _ccsds_template(sec5)
             aec = tuple(aec) if nbits else None
         elif drt in (2, 3):
-            ref, scale, decimal, nbits, cpx = _complex_template(sec5, drt, n_coded)
+            ref, scale, decimal, nbits, cpx, mvm = _complex_template(sec5, drt, n_coded, cpx_missing)
         else:
             ref = float(np.frombuffer(bytes(sec5[11:15]), dtype=">f4")[0])
             scale, decimal, nbits = 2.0 ** _sint(sec5[15:17]), _sint(sec5[17:19]), sec5[19]
@@ -962,8 +1000,11 @@ class _Field2(_Field):
             self.raw_aec = (data_pos + 5, len(sec7) - 5, n_coded, nbits, aec[1], aec[2], aec[0], 0)
         if cpx is not None and data_pos is not None:
             self.raw_cpx = (data_pos + 5, len(sec7) - 5, n_coded) + cpx + (0,)
+            self.raw_mvm = mvm
         indicator = sec6[5] if sec6 is not None else 255
-        if keep_raw and bitmap_pos is not None and data_pos is not None and indicator in (0, 254):
+        # a bitmap and codes inside the groups on one message: decoded on the host, the bitmap first, the codes inside it
+        both = mvm != 0 and indicator in (0, 254)
+        if keep_raw and bitmap_pos is not None and data_pos is not None and indicator in (0, 254) and not both:
             # kept raw with its bitmap: where the bitmap lies and how many bits it sets, nothing unpacked
             if indicator == 254 and prev_raw_bitmap is None:
                 raise ValueError("GRIB-2 field refers to a previous bitmap that does not exist")
@@ -996,6 +1037,17 @@ class _Field2(_Field):
         if keep_raw and self.raw_rule is not None:
             self.values = None
             return
+        if cpx is not None and mvm != 0:      # codes inside the groups: the present positions, then the bitmap around them
+            rec = np.array((0, len(sec7) - 5, count) + cpx + (0,), dtype=GRIB_CPX_DTYPE)
+            q, there = cpx_decode_mv(bytes(sec7[5:]), rec, mvm)
+            coded = np.full(count, np.nan)
+            coded[there] = (ref + q.astype(np.float64) * scale) / 10.0 ** decimal
+            if self.bitmap is None:
+                self.values = coded
+            else:
+                self.values = np.full(self.npoints, np.nan)
+                self.values[self.bitmap] = coded
+            return
         if cpx is not None:       # the message's own groups, decoded on the host
             q = cpx_decode(bytes(sec7[5:]), np.array((0, len(sec7) - 5, count) + cpx + (0,), dtype=GRIB_CPX_DTYPE)).astype(np.float64)
         elif aec is not None:     # the message's own stream, decoded on the host
@@ -1011,7 +1063,7 @@ class _Field2(_Field):
             self.values[self.bitmap] = packed
 
 
-def _fields_of_message2(buf, start, keep_raw=False, keep_bitmaps=False):
+def _fields_of_message2(buf, start, keep_raw=False, keep_bitmaps=False, cpx_missing=False):
     """The fields of the GRIB-2 message at `start`, and the message's length."""
     discipline, total = buf[start + 6], _uint(buf[start + 8:start + 16])
     if buf[start + total - 4:start + total] != b"7777":
@@ -1033,7 +1085,7 @@ def _fields_of_message2(buf, start, keep_raw=False, keep_bitmaps=False):
                 if need not in sec:
                     raise ValueError(f"GRIB-2 message without section {need}")
             f = _Field2(discipline, sec[1], sec[3], sec[4], sec[5], sec.get(6), sec[7], bitmap, data_pos=pos, keep_raw=keep_raw,
-                        bitmap_pos=sec6_pos if keep_bitmaps else None, prev_raw_bitmap=raw_bitmap)
+                        bitmap_pos=sec6_pos if keep_bitmaps else None, prev_raw_bitmap=raw_bitmap, cpx_missing=cpx_missing)
             bitmap, raw_bitmap = f.bitmap, f.raw_bitmap
             fields.append(f)
         pos += length
@@ -1045,7 +1097,7 @@ def read_messages(path):
         return _messages_of(f.read(), path)
 
 
-def _messages_of(buf, path, keep_raw=False, keep_bitmaps=False):
+def _messages_of(buf, path, keep_raw=False, keep_bitmaps=False, cpx_missing=False):
     """The messages of a file's bytes.  keep_raw: those without a bitmap are not unpacked (`values` is None, `raw_rule`
     says how to); with keep_bitmaps neither are those with one (`raw_bitmap` says where it lies)."""
     out, pos = [], 0
@@ -1055,7 +1107,7 @@ def _messages_of(buf, path, keep_raw=False, keep_bitmaps=False):
             break
         edition = buf[pos + 7] if pos + 8 <= len(buf) else 0
         if edition == 2:
-            fields, length = _fields_of_message2(buf, pos, keep_raw, keep_bitmaps)
+            fields, length = _fields_of_message2(buf, pos, keep_raw, keep_bitmaps, cpx_missing)
             out.extend(fields)
             pos += length
             continue
@@ -1069,7 +1121,7 @@ def _messages_of(buf, path, keep_raw=False, keep_bitmaps=False):
     return out
 
 
-def open_grib(path, decode=True, bitmaps=False):
+def open_grib(path, decode=True, bitmaps=False, cpx_missing=False):
     """Dataset of the fields of a GRIB file, one variable per parameter.  All messages must share one grid.
     decode=False keeps every variable whose (time, level) slots are all filled by messages without a bitmap as a
     `GribField` -- the file's bytes and one decode rule per field, which `Regridder(packed=True)` ships to the GPU as
@@ -1080,10 +1132,16 @@ def open_grib(path, decode=True, bitmaps=False):
     CCSDS-packed messages (edition 2, template 5.42) are decoded on the host with decode=True and kept raw like the
     others with decode=False: `GribField.ccsds` holds one record per field, simple-packed fields may stand among them.
     Complex-packed messages (templates 5.2 / 5.3) likewise: `GribField.cpx` holds one record per field, simple-packed
-    fields may stand among them; a variable that mixes CCSDS-packed and complex-packed messages is decoded."""
+    fields may stand among them; a variable that mixes CCSDS-packed and complex-packed messages is decoded.
+    cpx_missing=True reads complex-packed messages whose missing value management (section 5's octet 23) is 1 or 2 --
+    missing values coded inside the groups, what wgrib2 writes for undefined points -- instead of refusing them: decoded
+    on the host with decode=True (smm_grib_cpx_decode_host_mv; a section-6 bitmap on the same message is honoured: the
+    bitmap first, the codes inside it), kept raw with decode=False -- `GribField.cpx_missing` holds the octet per field.
+    A variable with a message that has both a bitmap and such codes is decoded."""
     with open(path, "rb") as f:
         file_bytes = f.read()
-    msgs = _messages_of(file_bytes, path, keep_raw=not decode, keep_bitmaps=bool(bitmaps) and not decode)
+    msgs = _messages_of(file_bytes, path, keep_raw=not decode, keep_bitmaps=bool(bitmaps) and not decode,
+                        cpx_missing=bool(cpx_missing))
     shared = np.frombuffer(file_bytes, dtype=np.uint8) if not decode else None
     if len({m.grid_key for m in msgs}) != 1:
         raise GribUnsupported("GRIB file with fields on several grids")
@@ -1134,6 +1192,7 @@ def open_grib(path, decode=True, bitmaps=False):
         aecs = np.zeros((len(times), len(levels)), dtype=GRIB_AEC_DTYPE)
         cpxs = np.zeros((len(times), len(levels)), dtype=GRIB_CPX_DTYPE)
         cpxs["order"] = GRIB_CPX_SIMPLE
+        mvms = np.zeros((len(times), len(levels)), dtype=np.uint8)
         for m, slot in zip(group, slots):
             if m.raw_rule is not None:
                 rows[slot] = m.raw_rule + (0,)
@@ -1144,6 +1203,7 @@ def open_grib(path, decode=True, bitmaps=False):
                     aecs[slot] = m.raw_aec
                 if m.raw_cpx is not None:
                     cpxs[slot] = m.raw_cpx
+                    mvms[slot] = m.raw_mvm
         # raw: every (time, level) slot filled by a message without a bitmap (a missing slot is NaN, which only a
         # decoded array holds).  Such a variable is never unpacked here; any other is decoded as with decode=True
         raw_ok = not decode and all(m.raw_rule is not None for m in group) and bool(filled.all())
@@ -1168,10 +1228,11 @@ def open_grib(path, decode=True, bitmaps=False):
         shape = tuple(n for n, keep in ((len(times), len(times) > 1), (len(levels), len(levels) > 1)) if keep) + hshape
         if raw_ok:
             if len(times) == 1:
-                rows, bms, aecs, cpxs = rows[0:1], bms[0:1], aecs[0:1], cpxs[0:1]
+                rows, bms, aecs, cpxs, mvms = rows[0:1], bms[0:1], aecs[0:1], cpxs[0:1], mvms[0:1]
             arr = GribField(shared, rows, shape, int(np.prod(hshape)),
                             bitmaps=bms if any(m.raw_bitmap is not None for m in group) else None,
-                            ccsds=aecs if has_aec else None, cpx=cpxs if has_cpx else None)
+                            ccsds=aecs if has_aec else None, cpx=cpxs if has_cpx else None,
+                            cpx_missing=mvms if mvms.any() else None)
         else:
             arr = arr.reshape(shape)
         ds[name] = DataArray(arr, dims=tuple(dims) + hdims, coords=vcoords, name=name,

@@ -73,11 +73,13 @@ def write_netcdf3(ds, path):
     return path
 
 
-def open_weights(path, decode=True, bitmaps=False):
+def open_weights(path, decode=True, bitmaps=False, cpx_missing=False):
     """decode=False keeps CF-packed variables as stored -- the raw integers with their scale_factor / add_offset /
     _FillValue / missing_value attributes -- which is what `Regridder(..., packed=True)` regrids without a host decode.
     For a GRIB file it keeps the simple-packed bit streams (`griblite.GribField`), regridded raw the same way;
-    bitmaps=True keeps the variables whose messages carry a bitmap raw as well (`griblite.open_grib`)."""
+    bitmaps=True keeps the variables whose messages carry a bitmap raw as well (`griblite.open_grib`);
+    cpx_missing=True reads complex-packed GRIB-2 messages whose missing values are coded inside the groups (missing
+    value management 1 or 2) instead of refusing them."""
     if str(path).endswith(".npz"):
         z = np.load(path, allow_pickle=False)
         meta = json.loads(str(z["__meta__"]))
@@ -93,7 +95,7 @@ def open_weights(path, decode=True, bitmaps=False):
         magic = f.read(4)
     if magic == b"GRIB":
         from .griblite import open_grib      # GRIB edition 1 (the reference reads these through cfgrib)
-        return open_grib(path, decode=decode, bitmaps=bitmaps)    # decode=False: variables stay GribFields (raw bits + rules)
+        return open_grib(path, decode=decode, bitmaps=bitmaps, cpx_missing=cpx_missing)    # decode=False: variables stay GribFields (raw bits + rules)
     if magic[:3] == b"CDF":
         from scipy.io import netcdf_file
         with netcdf_file(path, "r", mmap=False) as nc:

@@ -322,7 +322,7 @@ class SparseOperator:
                            (self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows)), y_res, cf, cf_out, "out")
 
     def apply_grib(self, x, rows, x_bytes=None, y=None, masked=False, remap_area_min=0.0, flags=0, stream=None,
-                   bitmaps=None, skipna=False, ccsds=None, cpx=None):
+                   bitmaps=None, skipna=False, ccsds=None, cpx=None, cpx_missing=None):
         """Y = epilogue(fill(decode(X)) . W) for GRIB simple-packed fields resident in HBM as they are on disk
         (smm_apply_grib).  x: a `DeviceArray` of uint8 -- or a raw device pointer with x_bytes -- holding the packed
         bit streams (4-byte aligned; the array -- or the allocation behind a raw pointer -- must cover x_bytes rounded
@@ -340,13 +340,25 @@ class SparseOperator:
         streams (smm_grib_aec_unpack); the result has the bits of the same call on the simple-packed integers.
         cpx: one `GRIB_CPX_DTYPE` record per row -- x holds the complex-packed streams of templates 5.2 / 5.3 (a record
         whose order is GRIB_CPX_SIMPLE: that row is simple-packed).  The same, through smm_grib_cpx_unpack; rows' nbits of
-        such a row is not read.  It does not go with ccsds."""
+        such a row is not read.  It does not go with ccsds.
+        cpx_missing: beside cpx, one uint8 per row -- the row's missing value management (section 5's octet 23): 1 or 2
+        means missing values are codes inside the groups.  The device step (smm_grib_cpx_unpack_mv) turns them into a
+        bitmap and the present integers, and the gather runs as with bitmaps=: the bits of the same call on the
+        simple-packed integers with that bitmap.  Such a row cannot have a bitmap of its own as well."""
         rows, rows_p = _grib.grib_rows(rows)
         kind, recs = _grib.one_kind(ccsds, cpx)
+        if cpx_missing is not None and kind is not _grib.CPX:
+            raise ValueError("cpx_missing goes with cpx")
+        missing = None
+        if kind is not None:      # what is refused about the records comes before the device is looked at
+            recs = _grib.records(kind, recs, rows)
+            missing = _grib.missing_of(cpx_missing, rows)
+            if missing is not None and bitmaps is not None:
+                bitmaps, _ = _grib.grib_bitmaps(bitmaps, rows.size)
+                _grib.refuse_bitmap_with_missing(bitmaps, missing, kind.is_coded(recs, rows))
         x_ptr, n_bytes = _grib.packed_bytes(x, x_bytes, "apply_grib", raw=kind is None)
         if kind is not None:
-            recs = _grib.records(kind, recs, rows)
-            idx, total = _grib.coded_rows(kind, recs, rows)
+            idx, total = _grib.coded_rows(kind, recs, rows, missing)
             # bitmaps and simple-packed rows stay where they are in x: then x travels along in front of the new streams
             plain = rows["nbits"] != 0
             plain[idx] = False
@@ -356,7 +368,7 @@ class SparseOperator:
             if keep and base:
                 _lib.call("smm_memcpy_d2d", ctypes.c_void_p(both.ptr), x_ptr, base, _stream_handle(stream))
             dst = DeviceArray((total,), np.uint8, ptr=both.ptr + base, base=both)
-            rows = _grib.unpack(kind, x, n_bytes, dst, base, rows, recs, idx, stream)
+            rows, bitmaps = _grib.unpack(kind, x, n_bytes, dst, base, rows, recs, idx, stream, missing, bitmaps, self.n_src)
             return self.apply_grib(both, rows, x_bytes=base + total, y=y, masked=masked, remap_area_min=remap_area_min,
                                    flags=flags, stream=stream, bitmaps=bitmaps, skipna=skipna)
         n_batch = rows.size
@@ -366,15 +378,15 @@ class SparseOperator:
                         self.n_dst, n_batch, float(remap_area_min), fl, _stream_handle(stream))
         return y
 
-    def _apply_host_grib_coded(self, buf, rows, out, bitmaps, kind, recs, chunk_rows, **apply_kw):
+    def _apply_host_grib_coded(self, buf, rows, out, bitmaps, kind, recs, chunk_rows, missing=None, **apply_kw):
         """`apply_host_grib(ccsds=)` and `apply_host_grib(cpx=)`: a synchronous loop over chunks of consecutive rows
         (`_grib.host_chunks`), each chunk's Y copied back."""
         out = _grib.float64_result(out, (rows.size, self.n_dst), result_cache.empty, "out")
-        for r0, r1, y, _ in _grib.host_chunks(self, buf, rows, bitmaps, kind, recs, chunk_rows, **apply_kw):
+        for r0, r1, y, _ in _grib.host_chunks(self, buf, rows, bitmaps, kind, recs, chunk_rows, missing=missing, **apply_kw):
             y.to_host(out=out[r0:r1])
         return out
 
-    def _apply_host_grib_out_coded(self, buf, rows, grib_out, okind, bitmaps, kind, recs, chunk_rows, **apply_kw):
+    def _apply_host_grib_out_coded(self, buf, rows, grib_out, okind, bitmaps, kind, recs, chunk_rows, missing=None, **apply_kw):
         """`apply_host_grib(grib_out=GribEncode(..., ccsds=...))` and `(..., cpx=...)`, okind the `_grib.CodedOut` of the
         two: the chunks of `_grib.host_chunks`, each chunk's float64 Y packed on the device (smm_grib_pack) and its
         integers coded as CCSDS or complex-packed streams (smm_grib_aec_pack, smm_grib_cpx_pack); one D2H copy of the
@@ -405,7 +417,8 @@ class SparseOperator:
         # per row beside Y: its simple-packed slot, the bound of its stream, the coder's scratch
         extra = slot + bound + okind.scratch(D)
         pack = getattr(_device, okind.pack)
-        for r0, r1, y, rows_in in _grib.host_chunks(self, buf, rows, bitmaps, kind, recs, chunk_rows, extra_cost=extra, **apply_kw):
+        for r0, r1, y, rows_in in _grib.host_chunks(self, buf, rows, bitmaps, kind, recs, chunk_rows, extra_cost=extra,
+                                                    missing=missing, **apply_kw):
             enc = grib_out.rows_of(r0, r1, n_batch)
             if enc.has_source_width:
                 enc = enc.resolved(rows_in["nbits"])
@@ -433,7 +446,7 @@ class SparseOperator:
         return GribField(result[:at], rows_out, (n_batch, D), D, bitmaps=bitmaps_out, **{okind.attr: recs_out})
 
     def apply_host_grib(self, buf, rows, out=None, masked=False, remap_area_min=0.0, flags=0, chunk_rows=0, bitmaps=None,
-                        skipna=False, grib_out=None, ccsds=None, cpx=None):
+                        skipna=False, grib_out=None, ccsds=None, cpx=None, cpx_missing=None):
         """The host twin (smm_apply_host_grib): buf is a host uint8 array -- typically a whole GRIB file -- and rows as
         for `apply_grib`.  Each row's packed bytes are staged and cross PCIe as they are (2 B per cell at 16 bits), no
         host decode runs.  Returns a float64 (B, D) numpy array, the bits of `apply_host` on the decoded float32 field.
@@ -456,12 +469,16 @@ class SparseOperator:
         carry the widths the integers were packed at.  The same synchronous chunk loop, with smm_grib_pack and
         smm_grib_cpx_pack behind the gather; the input may be simple-packed or, through cpx=, complex-packed itself (not
         CCSDS-packed).  Only there a width of `GribEncode.SOURCE_WIDTH` is legal: it becomes, chunk by chunk, the width
-        the source row's integers decode to."""
+        the source row's integers decode to.
+        cpx_missing as for `apply_grib`, carried chunk by chunk; a result record never carries it: missing cells of the
+        result are bitmapped as ever."""
         rows, rows_p = _grib.grib_rows(rows)
         buf = np.ascontiguousarray(buf)
         if buf.dtype != np.uint8 or buf.ndim != 1:
             raise TypeError("apply_host_grib takes the packed bytes as a 1-d uint8 array")
         kind, recs = _grib.one_kind(ccsds, cpx)
+        if cpx_missing is not None and kind is not _grib.CPX:
+            raise ValueError("cpx_missing goes with cpx")
         okind = _grib.out_kind(grib_out)
         if grib_out is not None and kind is not None and (okind is None or kind not in okind.takes):
             raise ValueError(f"{kind.arg} does not go with grib_out: decode the field on the host first")
@@ -472,8 +489,9 @@ class SparseOperator:
             apply_kw = dict(masked=masked, remap_area_min=remap_area_min, flags=int(flags), skipna=skipna)
             if okind is not None:
                 return self._apply_host_grib_out_coded(buf, rows, grib_out, okind, bitmaps, kind, recs, int(chunk_rows),
-                                                       **apply_kw)
-            return self._apply_host_grib_coded(buf, rows, out, bitmaps, kind, recs, int(chunk_rows), **apply_kw)
+                                                       missing=cpx_missing, **apply_kw)
+            return self._apply_host_grib_coded(buf, rows, out, bitmaps, kind, recs, int(chunk_rows), missing=cpx_missing,
+                                               **apply_kw)
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
         if grib_out is not None:
             bitmaps, bm_p = (None, None) if bitmaps is None else _grib.grib_bitmaps(bitmaps, n_batch)

@@ -639,13 +639,15 @@ class Regridder(object):
                                                 cpx=True if self.grib_out_cpx else None)
                     y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps,
                                            skipna=skipna, grib_out=enc, ccsds=src.ccsds if self.grib_out_ccsds else None,
-                                           cpx=src.cpx if self.grib_out_cpx else None)
+                                           cpx=src.cpx if self.grib_out_cpx else None,
+                                           cpx_missing=src.cpx_missing if self.grib_out_cpx else None)
                     return GribField(y.buf, y.rows, kept_shape + tgt_shape, op.n_dst, bitmaps=y.bitmaps, ccsds=y.ccsds,
                                      cpx=y.cpx)
                 # (CCSDS-packed fields: their streams are decoded on the device ahead of the gather, smm_grib_aec_unpack)
-                # (complex-packed fields likewise: smm_grib_cpx_unpack)
+                # (complex-packed fields likewise: smm_grib_cpx_unpack; those with missing values inside their groups --
+                # open_dataset(..., cpx_missing=True) -- through smm_grib_cpx_unpack_mv, which hands the gather a bitmap)
                 y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps,
-                                       skipna=skipna, ccsds=src.ccsds, cpx=src.cpx)
+                                       skipna=skipna, ccsds=src.ccsds, cpx=src.cpx, cpx_missing=src.cpx_missing)
                 return y.reshape(kept_shape + tgt_shape)
             if sb_in:
                 x = src.reshape(-1, n_batch)                  # (S, B): the batch values of a cell contiguous
