@@ -532,6 +532,15 @@ def to_device_pitched(host, dtype=None, stream=None):
     return out
 
 
+def packed_out(out, total):
+    """out -- given or fresh -- as the uint8 `DeviceArray` a device step writes at most `total` packed bytes into."""
+    if out is None:
+        return DeviceArray((max(total, 4),), np.uint8)
+    if not isinstance(out, DeviceArray) or out.dtype != np.uint8 or out.nbytes < total:
+        raise ValueError(f"out must be a uint8 DeviceArray of at least {total} bytes")
+    return out
+
+
 def grib_pack(y, enc, n_points=None, out=None, stream=None):
     """Pack a float64 `DeviceArray` (..., ld) into GRIB simple packing on the device (smm_grib_pack): every leading
     index is one field of n_points cells (default: the whole last axis; a smaller n_points leaves the row's tail
@@ -546,10 +555,7 @@ def grib_pack(y, enc, n_points=None, out=None, stream=None):
     n_points = ld if n_points is None else int(n_points)
     n_fields = y.size // ld if ld else 0
     _, total = enc.layout(n_points, n_fields)
-    if out is None:
-        out = DeviceArray((max(total, 4),), np.uint8)
-    elif not isinstance(out, DeviceArray) or out.dtype != np.uint8 or out.nbytes < total:
-        raise ValueError(f"out must be a uint8 DeviceArray of at least {total} bytes")
+    out = packed_out(out, total)
     rec = enc.records(n_fields)
     rows = np.zeros(n_fields, dtype=GRIB_ROW_DTYPE)
     bitmaps = np.zeros(n_fields, dtype=GRIB_BITMAP_DTYPE)
@@ -569,7 +575,7 @@ def grib_unpack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None):
     4-byte-aligned offset -- what `SparseOperator.apply_grib(x, rows, bitmaps=...)` takes as it is.  A field of width 0
     passes through untouched.  out: a uint8 DeviceArray to unpack into.  The stream is synchronised on return."""
     from . import _grib
-    return _grib.unpack_device("grib_unpack", _grib.CCSDS, device_bytes, rows, ccsds, x_bytes, out, stream)
+    return _grib.unpack_device("grib_unpack", device_bytes, rows, x_bytes, out, stream, ccsds=ccsds)[:2]
 
 
 def grib_unpack_cpx(device_bytes, rows, cpx, x_bytes=None, out=None, stream=None):
@@ -583,7 +589,7 @@ def grib_unpack_cpx(device_bytes, rows, cpx, x_bytes=None, out=None, stream=None
     whose record is marked GRIB_CPX_SIMPLE passes through untouched.  out: a uint8 DeviceArray to unpack into.  The
     stream is synchronised on return."""
     from . import _grib
-    return _grib.unpack_device("grib_unpack_cpx", _grib.CPX, device_bytes, rows, cpx, x_bytes, out, stream)
+    return _grib.unpack_device("grib_unpack_cpx", device_bytes, rows, x_bytes, out, stream, cpx=cpx)[:2]
 
 
 def grib_unpack_cpx_mv(device_bytes, rows, cpx, missing, x_bytes=None, out=None, stream=None):
@@ -595,8 +601,8 @@ def grib_unpack_cpx_mv(device_bytes, rows, cpx, missing, x_bytes=None, out=None,
     other fields: rows_out and bitmaps_out are what `SparseOperator.apply_grib(out, rows_out, bitmaps=bitmaps_out)`
     takes."""
     from . import _grib
-    return _grib.unpack_device("grib_unpack_cpx_mv", _grib.CPX, device_bytes, rows, cpx, x_bytes, out, stream,
-                               missing=missing, with_bitmaps=True)
+    missing = np.zeros(np.size(cpx), dtype=np.uint8) if missing is None else missing
+    return _grib.unpack_device("grib_unpack_cpx_mv", device_bytes, rows, x_bytes, out, stream, cpx=cpx, cpx_missing=missing)
 
 
 def grib_aec_pack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None):
@@ -610,7 +616,7 @@ def grib_aec_pack(device_bytes, rows, ccsds, x_bytes=None, out=None, stream=None
     `griblite.aec_encode` gives.  A field of width 0 has no stream (byte_len 0, block_size 0).  out: a uint8 DeviceArray of
     at least the bound (smm_grib_aec_pack_bound) to code into.  The stream is synchronised on return."""
     from . import _grib
-    return _grib.pack_device("grib_aec_pack", _grib.CCSDS, device_bytes, rows, ccsds, x_bytes, out, stream)
+    return _grib.pack_device("grib_aec_pack", device_bytes, rows, x_bytes, out, stream, ccsds=ccsds)
 
 
 def grib_cpx_pack(device_bytes, rows, cpx, x_bytes=None, out=None, stream=None):
@@ -625,7 +631,7 @@ def grib_cpx_pack(device_bytes, rows, cpx, x_bytes=None, out=None, stream=None):
     `griblite.cpx_encode` gives.  A field of width 0 is not coded (byte_len 0, order GRIB_CPX_SIMPLE).  out: a uint8 DeviceArray of at least the bound (smm_grib_cpx_pack_bound) to code into.  The stream is synchronised
     on return."""
     from . import _grib
-    return _grib.pack_device("grib_cpx_pack", _grib.CPX, device_bytes, rows, cpx, x_bytes, out, stream)
+    return _grib.pack_device("grib_cpx_pack", device_bytes, rows, x_bytes, out, stream, cpx=cpx)
 
 
 def empty(shape, dtype=np.float64):

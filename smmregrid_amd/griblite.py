@@ -32,9 +32,11 @@ Anything else in a GRIB file (spherical harmonics, GRIB-1 second-order / JPEG / 
 grids) raises GribUnsupported naming the feature.
 """
 import ctypes
+from collections import namedtuple
 
 import numpy as np
 
+from . import _lib
 from .xrlite import DataArray, Dataset
 
 
@@ -77,15 +79,13 @@ def aec_decode(buf, rec, histogram=None):
     """The unsigned integers (uint32) of one CCSDS stream: `rec` a GRIB_AEC_DTYPE record over the bytes `buf`, decoded
     by the library on the host (smm_grib_aec_decode_host; no GPU involved).  histogram: a uint64 array of 7 counters the
     coding options taken are added to (`_lib.GRIB_AEC_OPTIONS`).  A stream that does not end ok is a ValueError."""
-    from . import _lib
     rec = np.ascontiguousarray(rec, dtype=GRIB_AEC_DTYPE).reshape(1)
     raw = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf)
     out = np.empty(int(rec["n_values"][0]), dtype=np.uint32)
     status = ctypes.c_int(0)
     hist = None if histogram is None else histogram.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
     _lib.call("smm_grib_aec_decode_host", ctypes.c_void_p(raw.ctypes.data if raw.size else None), raw.size,
-              ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribAecStruct)),
-              out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), hist, ctypes.byref(status))
+              CCSDS.cast(rec), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), hist, ctypes.byref(status))
     if status.value != _lib.GRIB_AEC_OK:
         raise ValueError("CCSDS stream " + ("ends before its values do" if status.value == _lib.GRIB_AEC_EXHAUSTED
                                             else "is invalid"))
@@ -107,14 +107,12 @@ def cpx_decode(buf, rec):
     """The integers X (uint32) of one complex-packed stream: `rec` a GRIB_CPX_DTYPE record over the bytes `buf`, decoded
     by the library on the host (smm_grib_cpx_decode_host; no GPU involved).  A row that does not end ok is a
     ValueError."""
-    from . import _lib
     rec = np.ascontiguousarray(rec, dtype=GRIB_CPX_DTYPE).reshape(1)
     raw = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf)
     out = np.empty(int(rec["n_values"][0]), dtype=np.uint32)
     status = ctypes.c_int(0)
     _lib.call("smm_grib_cpx_decode_host", ctypes.c_void_p(raw.ctypes.data if raw.size else None), raw.size,
-              ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)),
-              out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(status))
+              CPX.cast(rec), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(status))
     if status.value != _lib.GRIB_CPX_OK:
         raise ValueError("complex-packed stream " + ("ends before its tables or its groups' bits do"
                                                      if status.value == _lib.GRIB_CPX_EXHAUSTED else "is invalid"))
@@ -126,15 +124,14 @@ def cpx_decode_mv(buf, rec, mvm):
     missing value management (section 5's octet 23) is `mvm` -- 1 or 2: missing values are codes inside the groups, by
     the rule of smm_grib_cpx.hpp; 0: every position is present.  Decoded by the library on the host
     (smm_grib_cpx_decode_host_mv; no GPU involved).  A row that does not end ok is a ValueError."""
-    from . import _lib
     rec = np.ascontiguousarray(rec, dtype=GRIB_CPX_DTYPE).reshape(1)
     raw = np.frombuffer(buf, dtype=np.uint8) if not isinstance(buf, np.ndarray) else np.ascontiguousarray(buf)
     n = int(rec["n_values"][0])
     out, present = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint8)
     status, count, m = ctypes.c_int(0), ctypes.c_uint64(0), ctypes.c_uint8(int(mvm))
     _lib.call("smm_grib_cpx_decode_host_mv", ctypes.c_void_p(raw.ctypes.data if raw.size else None), raw.size,
-              ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)), ctypes.byref(m),
-              out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), present.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+              CPX.cast(rec), ctypes.byref(m), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+              present.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
               ctypes.byref(count), ctypes.byref(status))
     if status.value != _lib.GRIB_CPX_OK:
         raise ValueError("complex-packed stream " + ("ends before its tables or its groups' bits do"
@@ -148,18 +145,15 @@ def aec_encode(values, record, histogram=None):
     smm_grib_aec_pack.  record: a GRIB_AEC_DTYPE record whose nbits, block_size, rsi and flags say how to code (n_values
     is set from `values`, byte_off and byte_len are not read).  histogram: a uint64 array of 7 counters the coding options
     taken are added to (`_lib.GRIB_AEC_OPTIONS`)."""
-    from . import _lib
     v = np.ascontiguousarray(values, dtype=np.uint32).ravel()
     rec = np.array(record, dtype=GRIB_AEC_DTYPE).reshape(1)
     rec["n_values"], rec["byte_off"], rec["byte_len"] = v.size, 0, 0
-    rec_p = ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribAecStruct))
-    bound = ctypes.c_uint64(0)
-    _lib.call("smm_grib_aec_pack_bound", rec_p, 1, None, ctypes.byref(bound))
-    out = np.zeros(max(int(bound.value), 1), dtype=np.uint8)
+    bound = int(CCSDS.bounds(rec)[0])
+    out = np.zeros(max(bound, 1), dtype=np.uint8)
     used = ctypes.c_uint64(0)
     hist = None if histogram is None else histogram.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
-    _lib.call("smm_grib_aec_encode_host", v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size, rec_p,
-              ctypes.c_void_p(out.ctypes.data), int(bound.value), ctypes.byref(used), hist)
+    _lib.call("smm_grib_aec_encode_host", v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size, CCSDS.cast(rec),
+              ctypes.c_void_p(out.ctypes.data), bound, ctypes.byref(used), hist)
     return out[:int(used.value)].copy()
 
 
@@ -170,19 +164,15 @@ def cpx_encode(values, rec):
     of the integers), order (wanted, 0..2) and length_ref (the group length: 8, 16, 32 or 64) say how to code; n_values
     is set from `values`, nothing else is read.  Integers of width 0 are not coded: no bytes, and a record whose order is
     GRIB_CPX_SIMPLE."""
-    from . import _lib
     v = np.ascontiguousarray(values, dtype=np.uint32).ravel()
     rec = np.array(rec, dtype=GRIB_CPX_DTYPE).reshape(1)
     rec["n_values"] = v.size
-    rec_p = ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct))
-    bound = ctypes.c_uint64(0)
-    _lib.call("smm_grib_cpx_pack_bound", rec_p, 1, None, ctypes.byref(bound))
-    out = np.zeros(max(int(bound.value), 1), dtype=np.uint8)
+    bound = int(CPX.bounds(rec)[0])
+    out = np.zeros(max(bound, 1), dtype=np.uint8)
     used = ctypes.c_uint64(0)
     rec_out = np.zeros(1, dtype=GRIB_CPX_DTYPE)
-    _lib.call("smm_grib_cpx_encode_host", v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size, rec_p,
-              ctypes.c_void_p(out.ctypes.data), int(bound.value), ctypes.byref(used),
-              ctypes.cast(rec_out.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)))
+    _lib.call("smm_grib_cpx_encode_host", v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size, CPX.cast(rec),
+              ctypes.c_void_p(out.ctypes.data), bound, ctypes.byref(used), CPX.cast(rec_out))
     return out[:int(used.value)].copy(), rec_out[0]
 
 
@@ -193,6 +183,218 @@ def cpx_want(nbits, order, group_len, n_values=0):
     rec = np.zeros(shape, dtype=GRIB_CPX_DTYPE)
     rec["nbits"], rec["order"], rec["length_ref"], rec["n_values"] = nbits, order, group_len, n_values
     return rec
+
+
+# ---------------------------------------------------------------------------------------------- the codec table
+def align4(v):
+    return (v + 3) // 4 * 4
+
+
+def _cast(records, struct):
+    return ctypes.cast(records.ctypes.data, ctypes.POINTER(struct))
+
+
+class Codec(namedtuple("Codec", "name noun packing packed stream result dtype struct layout_entry unpack_entry bound_entry pack_entry "
+                                "mv_entries is_coded device_cost missing_cost out_scratch takes default params_of wanted "
+                                "encode decode")):
+    """One way GRIB codes a field's integers beside simple packing, for both directions: coded rows regridded raw
+    (`ccsds=`, `cpx=`) and results coded on their way out (`GribEncode(..., ccsds= / cpx=)`).  Everything that follows
+    from the kind of coded row stands here; a further codec is a further entry of `CODECS`.
+    name: the keyword and attribute that carries its records; noun, packing, packed, stream, result: what messages call it.
+    dtype, struct: its record, one per row; layout_entry, unpack_entry, bound_entry, pack_entry: the C entries behind
+    `layout`, `unpack`, `bounds` and `pack`; mv_entries: the layout and unpack entries that take the rows' missing value
+    management and give bitmaps, for a call that carries one (None: the codec has no missing values inside its streams).
+    is_coded(recs, rows): which rows have a coded stream -- the others are simple-packed.
+    device_cost(recs, n_val, nbits): the device bytes a coded row costs in a chunk beside its staged stream;
+    missing_cost(n_val): what a row with missing values inside its stream costs more.
+    out_scratch(n_dst): the device bytes a result row costs beside its stream's bound; takes: the names of the codecs
+    the input of a call may be coded with when its result is coded this way (simple-packed input always goes).
+    default, params_of(rec), wanted(*params): the parameters `True` stands for, those of a record, and the record that
+    asks for them (a ValueError when they are not valid).
+    encode(q, rec) -> (stream, the stream's record) and decode(buf, rec, mvm) -> (q, present or None): the host coder
+    and decoder; a field of width 0 has no stream, and the coder marks its record simple-packed."""
+    __slots__ = ()
+
+    def cast(self, recs):
+        return _cast(recs, self.struct)
+
+    def params(self, want):
+        """Records with the wanted parameters set, from True, one tuple of parameters, a list of them or records."""
+        if want is True:
+            want = self.default
+        if isinstance(want, np.ndarray) and want.dtype == self.dtype:
+            par = [self.params_of(r) for r in want.ravel()]
+        else:
+            par = [tuple(want)] if np.ndim(want[0]) == 0 else [tuple(c) for c in want]
+        rec = np.zeros(len(par), dtype=self.dtype)
+        for i, p in enumerate(par):
+            rec[i] = self.wanted(*p)
+        return rec
+
+    def layout(self, recs, missing=None):
+        """Bytes the simple-packed streams (and bitmaps) the records' streams unpack to take; host only, and a malformed
+        record is refused.  missing: the rows' missing value management, or None."""
+        total = ctypes.c_uint64(0)
+        if missing is None:
+            _lib.call(self.layout_entry, self.cast(recs), recs.size, None, ctypes.byref(total))
+        else:
+            _lib.call(self.mv_entries[0], self.cast(recs), missing.ctypes.data_as(_lib._u8p), recs.size, None, None,
+                      ctypes.byref(total))
+        return int(total.value)
+
+    def bounds(self, recs):
+        """Bytes the coded stream of each wanted record takes at most (int64); host only."""
+        offs, total = np.zeros(recs.size + 1, dtype=np.uint64), ctypes.c_uint64(0)
+        _lib.call(self.bound_entry, self.cast(recs), recs.size, offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                  ctypes.byref(total))
+        offs[recs.size] = total.value
+        return np.diff(offs).astype(np.int64)
+
+    def unpack(self, dev, x_ptr, n_bytes, recs, missing, rows, out_ptr, out_bytes, stream):
+        """The device step from coded to simple-packed streams.  Returns (the rows of the streams written, their bitmap
+        records -- None for a call without missing value management)."""
+        rows_out = np.zeros(rows.size, dtype=GRIB_ROW_DTYPE)
+        tail = (_cast(rows, _lib.GribRowStruct), rows.size, out_ptr, out_bytes, _cast(rows_out, _lib.GribRowStruct))
+        if missing is None:
+            _lib.call(self.unpack_entry, dev, x_ptr, n_bytes, self.cast(recs), *tail, stream)
+            return rows_out, None
+        bitmaps_out = np.zeros(rows.size, dtype=GRIB_BITMAP_DTYPE)
+        _lib.call(self.mv_entries[1], dev, x_ptr, n_bytes, self.cast(recs), missing.ctypes.data_as(_lib._u8p), *tail,
+                  _cast(bitmaps_out, _lib.GribBitmapStruct), stream)
+        return rows_out, bitmaps_out
+
+    def pack(self, dev, x_ptr, n_bytes, rows, recs, out_ptr, out_bytes, stream):
+        """The device step from simple-packed to coded streams.  Returns (bytes used, the records of the streams)."""
+        recs_out, used = np.zeros(rows.size, dtype=self.dtype), ctypes.c_uint64(0)
+        _lib.call(self.pack_entry, dev, x_ptr, n_bytes, _cast(rows, _lib.GribRowStruct), self.cast(recs), rows.size,
+                  out_ptr, out_bytes, self.cast(recs_out), ctypes.byref(used), stream)
+        return int(used.value), recs_out
+
+
+def _aec_wanted(block, rsi, pre):
+    if int(block) not in (8, 16, 32, 64) or not 1 <= int(rsi) <= 4096:
+        raise ValueError(f"CCSDS block size {block} / reference sample interval {rsi}: 8, 16, 32 or 64 and 1..4096")
+    return (0, 0, 0, 0, int(block), int(rsi), 0x06 | (_AEC_PREPROCESS if pre else 0), 0)
+
+
+def _aec_code(q, rec):
+    if int(rec["nbits"]) == 0:
+        rec = rec.copy()
+        rec["block_size"] = 0
+        return np.zeros(0, dtype=np.uint8), rec
+    return aec_encode(q, rec), rec
+
+
+def _cpx_wanted(order, group_len):
+    if int(order) not in (0, 1, 2) or int(group_len) not in (8, 16, 32, 64):
+        raise ValueError(f"complex packing of order {order} in groups of {group_len}: 0, 1 or 2 and 8, 16, 32 or 64")
+    return cpx_want(0, int(order), int(group_len))
+
+
+def cpx_missing_cost(n_val):
+    """Device bytes a complex-packed row with missing values inside its groups costs beside `CPX.device_cost`: its
+    bitmap slot, 8 B more per value -- the integers pass through a second array on their way to their ranks -- and 4 B
+    per 256 values."""
+    return align4((n_val + 7) // 8) + 8 * n_val + 4 * ((n_val + 255) // 256)
+
+
+# a record with block_size 0 marks a simple-packed row, a row of width 0 has no stream at all; a coded row costs its
+# transcoded stream and 4 B per sample of scratch; a result row 8 B per block and 12 B per segment of scratch
+CCSDS = Codec(
+    "ccsds", "CCSDS", "CCSDS packing", "CCSDS-packed", "CCSDS stream", "CCSDS-coded", GRIB_AEC_DTYPE, _lib.GribAecStruct,
+    "smm_grib_aec_layout", "smm_grib_aec_unpack", "smm_grib_aec_pack_bound", "smm_grib_aec_pack", mv_entries=None,
+    is_coded=lambda recs, rows: (recs["block_size"] != 0) & (rows["nbits"] != 0),
+    device_cost=lambda recs, n_val, nbits: align4((n_val * nbits + 7) // 8) + 4 * n_val, missing_cost=None,
+    out_scratch=lambda n_dst: (n_dst // 8 + 1) * 20, takes=("ccsds",), default=(32, 128, True),
+    params_of=lambda r: (int(r["block_size"]), int(r["rsi"]), bool(int(r["flags"]) & _AEC_PREPROCESS)),
+    wanted=_aec_wanted, encode=_aec_code, decode=lambda buf, rec, mvm: (aec_decode(buf, rec), None))
+# a record whose order is GRIB_CPX_SIMPLE marks a simple-packed row; a coded row costs its slot of 4 B per value and
+# 8 B per value plus 16 B per group of scratch; a result row 8 B per group of at least 8 values and 12 B per 1024 values
+# of scratch
+CPX = Codec(
+    "cpx", "complex-packing", "complex packing", "complex-packed", "complex-packed stream", "complex-packed",
+    GRIB_CPX_DTYPE, _lib.GribCpxStruct,
+    "smm_grib_cpx_layout", "smm_grib_cpx_unpack", "smm_grib_cpx_pack_bound", "smm_grib_cpx_pack",
+    mv_entries=("smm_grib_cpx_layout_mv", "smm_grib_cpx_unpack_mv"),
+    is_coded=lambda recs, rows: recs["order"] != GRIB_CPX_SIMPLE,
+    device_cost=lambda recs, n_val, nbits: 12 * n_val + 16 * recs["n_groups"].astype(np.int64) + 256,
+    missing_cost=cpx_missing_cost, out_scratch=lambda n_dst: n_dst + 8 + (n_dst // 1024 + 1) * 12, takes=("cpx",),
+    default=(2, 32), params_of=lambda r: (int(r["order"]), int(r["length_ref"])), wanted=_cpx_wanted, encode=cpx_encode,
+    decode=lambda buf, rec, mvm: cpx_decode_mv(buf, rec, mvm) if mvm else (cpx_decode(buf, rec), None))
+CODECS = (CCSDS, CPX)
+
+
+def one_codec(why, **given):
+    """(codec, what its keyword holds) for the one keyword of a codec (ccsds=, cpx=) that is not None, or (None, None)."""
+    given = [(c, given[c.name]) for c in CODECS if given.get(c.name) is not None]
+    if len(given) > 1:
+        raise ValueError(f"{given[1][0].name} does not go with {given[0][0].name}: {why}")
+    return given[0] if given else (None, None)
+
+
+class CodedRows:
+    """The coded rows of a call or of a `GribField`: the codec, its records -- one per row -- and the rows' missing value
+    management (one uint8 per row; None when no row has missing values inside its stream)."""
+
+    def __init__(self, codec, recs, missing=None):
+        self.codec, self.recs, self.missing = codec, recs, missing
+
+    @classmethod
+    def of(cls, n_rows, ccsds=None, cpx=None, cpx_missing=None, what="rows", coded=None):
+        """From the public keywords -- or `coded`, a `CodedRows` that stands in their place --, checked against the
+        call's `n_rows`; None when nothing is given."""
+        if coded is not None:
+            if ccsds is not None or cpx is not None or cpx_missing is not None or coded.recs.size != n_rows:
+                raise ValueError(f"coded stands in place of ccsds, cpx and cpx_missing, with a record for each of {n_rows} {what}")
+            return coded
+        codec, recs = one_codec("a call's coded rows are of one kind", ccsds=ccsds, cpx=cpx)
+        if cpx_missing is not None and codec is not CPX:
+            raise ValueError("cpx_missing goes with cpx")
+        if codec is None:
+            return None
+        recs = np.ascontiguousarray(recs, dtype=codec.dtype).ravel()
+        if recs.size != n_rows:
+            raise ValueError(f"{recs.size} {codec.noun} records for {n_rows} {what}")
+        if cpx_missing is not None:
+            cpx_missing = np.ascontiguousarray(cpx_missing, dtype=np.uint8).ravel()
+            if cpx_missing.size != n_rows:
+                raise ValueError(f"{cpx_missing.size} missing-value-management values for {n_rows} {what}")
+        return cls(codec, recs, cpx_missing)
+
+    def __getitem__(self, rows):
+        """The coded rows of a slice or an index array of the rows, as a copy: records and missing values stay together."""
+        return CodedRows(self.codec, np.array(self.recs[rows]), None if self.missing is None else np.array(self.missing[rows]))
+
+    def is_coded(self, rows):
+        return self.codec.is_coded(self.recs, rows)
+
+    def has_missing(self, is_coded):
+        return False if self.missing is None else is_coded & (self.missing != 0)
+
+    def streams(self, rows, bitmaps=None):
+        """(which rows have a coded stream, bytes of their transcoded streams).  A coded row with a bitmap of its own and
+        missing values inside its stream is refused: the two are not composed on the device."""
+        is_coded = self.is_coded(rows)
+        self.refuse_bitmaps(bitmaps, is_coded)
+        idx = np.flatnonzero(is_coded)
+        return idx, self[idx].nbytes()
+
+    def refuse_bitmaps(self, bitmaps, is_coded):
+        if bitmaps is not None and np.any((bitmaps["bitmap_off"] != GRIB_NO_BITMAP) & self.has_missing(is_coded)):
+            raise ValueError("a row has a bitmap and missing values inside its groups: decode it on the host")
+
+    def nbytes(self):
+        return self.codec.layout(self.recs, self.missing)
+
+    def bound(self):
+        return int(self.codec.bounds(self.recs).sum())
+
+    def device_cost(self, is_coded, n_val, nbits):
+        """The device bytes each row costs in a chunk beside its staged stream (0 for a simple-packed row)."""
+        cost = np.where(is_coded, self.codec.device_cost(self.recs, n_val, nbits), 0)
+        if self.missing is not None:
+            cost = cost + np.where(self.has_missing(is_coded), self.codec.missing_cost(n_val), 0)
+        return cost
 
 
 class GribField:
@@ -212,7 +414,8 @@ class GribField:
     `decode()`), and its row's nbits is the width of the group references, not of q; a record whose order is
     GRIB_CPX_SIMPLE marks a simple-packed field among them.  `cpx_missing` is None, or one uint8 per field beside `cpx`:
     the field's missing value management (1 or 2: missing values are codes inside its groups -- they become NaN;
-    smm_grib_cpx_unpack_mv on the GPU, smm_grib_cpx_decode_host_mv for `decode()`)."""
+    smm_grib_cpx_unpack_mv on the GPU, smm_grib_cpx_decode_host_mv for `decode()`).  The three are views of `coded`,
+    the `CodedRows` built from them (None for a variable of simple-packed fields only), which the calls take whole."""
 
     dtype = np.dtype(np.float32)
 
@@ -223,21 +426,20 @@ class GribField:
         self.bitmaps = None if bitmaps is None else np.ascontiguousarray(bitmaps, dtype=GRIB_BITMAP_DTYPE).ravel()
         if self.bitmaps is not None and self.bitmaps.size != self.rows.size:
             raise ValueError(f"{self.bitmaps.size} bitmap records for {self.rows.size} GRIB fields")
-        self.ccsds = None if ccsds is None else np.ascontiguousarray(ccsds, dtype=GRIB_AEC_DTYPE).ravel()
-        if self.ccsds is not None and self.ccsds.size != self.rows.size:
-            raise ValueError(f"{self.ccsds.size} CCSDS records for {self.rows.size} GRIB fields")
-        self.cpx = None if cpx is None else np.ascontiguousarray(cpx, dtype=GRIB_CPX_DTYPE).ravel()
-        if self.cpx is not None and self.cpx.size != self.rows.size:
-            raise ValueError(f"{self.cpx.size} complex-packing records for {self.rows.size} GRIB fields")
-        if self.cpx is not None and self.ccsds is not None:
+        if ccsds is not None and cpx is not None:
             raise ValueError("a GribField holds CCSDS records or complex-packing records, not both")
-        self.cpx_missing = None if cpx_missing is None else np.ascontiguousarray(cpx_missing, dtype=np.uint8).ravel()
-        if self.cpx_missing is not None and (self.cpx is None or self.cpx_missing.size != self.rows.size):
-            raise ValueError("cpx_missing goes with cpx: one value per GRIB field")
+        self.coded = CodedRows.of(self.rows.size, ccsds, cpx, cpx_missing, what="GRIB fields")
         self.shape = tuple(int(n) for n in shape)
         self.n_points = int(n_points)
         if self.rows.size * self.n_points != int(np.prod(self.shape)):
             raise ValueError(f"{self.rows.size} GRIB fields of {self.n_points} points for a variable of shape {self.shape}")
+
+    def _coded_as(self, codec):
+        return self.coded is not None and self.coded.codec is codec
+
+    ccsds = property(lambda self: self.coded.recs if self._coded_as(CCSDS) else None)
+    cpx = property(lambda self: self.coded.recs if self._coded_as(CPX) else None)
+    cpx_missing = property(lambda self: self.coded.missing if self._coded_as(CPX) else None)
 
     @property
     def ndim(self):
@@ -250,15 +452,14 @@ class GribField:
     def decode(self):
         """The float32 array `open_grib(path)` gives for this variable, bit for bit."""
         out = np.empty((self.rows.size, self.n_points), dtype=np.float32)
+        is_coded = None if self.coded is None else self.coded.is_coded(self.rows)
         for i, r in enumerate(self.rows):
             rule = (int(r["byte_off"]), float(r["ref"]), float(r["bscale"]), float(r["ddiv"]), int(r["nbits"]))
             bm = None
             if self.bitmaps is not None and int(self.bitmaps[i]["bitmap_off"]) != GRIB_NO_BITMAP:
                 bm = (int(self.bitmaps[i]["bitmap_off"]), int(self.bitmaps[i]["n_values"]))
-            aec = None if self.ccsds is None or int(self.ccsds[i]["block_size"]) == 0 else self.ccsds[i]
-            cpx = None if self.cpx is None or int(self.cpx[i]["order"]) == GRIB_CPX_SIMPLE else self.cpx[i]
-            mvm = 0 if self.cpx_missing is None or cpx is None else int(self.cpx_missing[i])
-            out[i] = _decode_rule(self.buf, rule, self.n_points, bm, aec, cpx, mvm)
+            coded = self.coded[i:i + 1] if is_coded is not None and is_coded[i] else None
+            out[i] = _decode_rule(self.buf, rule, self.n_points, bm, coded)
         return out.reshape(self.shape)
 
     def __array__(self, dtype=None, copy=None):
@@ -267,21 +468,15 @@ class GribField:
 
     def __repr__(self):
         n_bm = 0 if self.bitmaps is None else int((self.bitmaps["bitmap_off"] != GRIB_NO_BITMAP).sum())
-        n_aec = 0 if self.ccsds is None else int((self.ccsds["block_size"] != 0).sum())
-        n_cpx = 0 if self.cpx is None else int((self.cpx["order"] != GRIB_CPX_SIMPLE).sum())
+        n_coded = 0 if self.coded is None else int(self.coded.is_coded(self.rows).sum())
         return (f"<GribField {self.shape} float32, {self.rows.size} packed fields, widths "
-                f"{sorted(set(self.rows['nbits'].tolist()))}" + (f", {n_aec} CCSDS-packed" if n_aec else "")
-                + (f", {n_cpx} complex-packed" if n_cpx else "")
+                f"{sorted(set(self.rows['nbits'].tolist()))}" + (f", {n_coded} {self.coded.codec.packed}" if n_coded else "")
                 + (f" ({int((self.cpx_missing != 0).sum())} with missing values inside the groups)"
                    if self.cpx_missing is not None else "")
                 + (f", {n_bm} with a bitmap>" if n_bm else ">"))
 
 
 _FLT_MAX = float(np.finfo(np.float32).max)
-
-
-def _align4(n):
-    return (int(n) + 3) // 4 * 4
 
 
 class GribEncode:
@@ -304,8 +499,7 @@ class GribEncode:
     A width of `SOURCE_WIDTH` marks a field whose width is the one its complex-packed source row's integers decode to:
     only `apply_host_grib(cpx=..., grib_out=)` can resolve it (`resolved`); everything else refuses the mark."""
 
-    CCSDS_DEFAULT = (32, 128, True)
-    CPX_DEFAULT = (2, 32)
+    CCSDS_DEFAULT, CPX_DEFAULT = CCSDS.default, CPX.default
     SOURCE_WIDTH = -(1 << 15)      # no width: every other value outside 1..32 is refused
 
     def __init__(self, nbits, decimal_scale=0, ccsds=None, cpx=None):
@@ -322,61 +516,24 @@ class GribEncode:
         self.decimal_scale = np.broadcast_to(ds.astype(np.int64), (n,)).copy()
         if (((self.nbits < 1) | (self.nbits > 32)) & (self.nbits != self.SOURCE_WIDTH)).any():
             raise ValueError("GRIB output widths are 1..32 bits")
-        if ccsds is not None and cpx is not None:
-            raise ValueError("cpx does not go with ccsds: a result is coded one way")
+        self.codec, want = one_codec("a result is coded one way", ccsds=ccsds, cpx=cpx)
         self.ddiv = np.array([10.0 ** int(d) if abs(int(d)) < 309 else np.inf for d in self.decimal_scale], dtype=np.float64)
         if not (np.isfinite(self.ddiv) & (self.ddiv > 0)).all():
             raise ValueError("10^D must be finite and positive")
-        self.ccsds = None if ccsds is None else self._ccsds_params(ccsds)
-        if self.ccsds is not None and self.ccsds.size > 1:
+        self.params = None if self.codec is None else self.codec.params(want)
+        if self.params is not None and self.params.size > 1:
             if self.n_fields is None:      # scalars beside one parameter set per field
-                self.n_fields = self.ccsds.size
+                self.n_fields = self.params.size
                 self.nbits, self.decimal_scale, self.ddiv = (np.repeat(a, self.n_fields) for a in
                                                               (self.nbits, self.decimal_scale, self.ddiv))
-            elif self.ccsds.size != self.n_fields:
-                raise ValueError(f"{self.ccsds.size} CCSDS parameter sets for {self.n_fields} fields")
-        self.cpx = None if cpx is None else self._cpx_params(cpx)
-        if self.cpx is not None and self.cpx.size > 1:
-            if self.n_fields is None:      # scalars beside one parameter set per field
-                self.n_fields = self.cpx.size
-                self.nbits, self.decimal_scale, self.ddiv = (np.repeat(a, self.n_fields) for a in
-                                                              (self.nbits, self.decimal_scale, self.ddiv))
-            elif self.cpx.size != self.n_fields:
-                raise ValueError(f"{self.cpx.size} complex-packing parameter sets for {self.n_fields} fields")
+            elif self.params.size != self.n_fields:
+                raise ValueError(f"{self.params.size} {self.codec.noun} parameter sets for {self.n_fields} fields")
 
-    @classmethod
-    def _ccsds_params(cls, ccsds):
-        """GRIB_AEC_DTYPE records with block_size, rsi and flags set, from True, one (block_size, rsi, preprocess) or a
-        list of them."""
-        if ccsds is True:
-            ccsds = cls.CCSDS_DEFAULT
-        if isinstance(ccsds, np.ndarray) and ccsds.dtype == GRIB_AEC_DTYPE:
-            par = [(int(r["block_size"]), int(r["rsi"]), bool(int(r["flags"]) & _AEC_PREPROCESS)) for r in ccsds.ravel()]
-        else:
-            par = [tuple(ccsds)] if np.ndim(ccsds[0]) == 0 else [tuple(c) for c in ccsds]
-        rec = np.zeros(len(par), dtype=GRIB_AEC_DTYPE)
-        for i, (block, rsi, pre) in enumerate(par):
-            if int(block) not in (8, 16, 32, 64) or not 1 <= int(rsi) <= 4096:
-                raise ValueError(f"CCSDS block size {block} / reference sample interval {rsi}: 8, 16, 32 or 64 and 1..4096")
-            rec[i] = (0, 0, 0, 0, int(block), int(rsi), 0x06 | (_AEC_PREPROCESS if pre else 0), 0)
-        return rec
+    def _params(self, codec):
+        return self.params if self.codec is codec else None
 
-    @classmethod
-    def _cpx_params(cls, cpx):
-        """GRIB_CPX_DTYPE records with order and length_ref (the group length) set, from True, one (order, group_len) or
-        a list of them."""
-        if cpx is True:
-            cpx = cls.CPX_DEFAULT
-        if isinstance(cpx, np.ndarray) and cpx.dtype == GRIB_CPX_DTYPE:
-            par = [(int(r["order"]), int(r["length_ref"])) for r in cpx.ravel()]
-        else:
-            par = [tuple(cpx)] if np.ndim(cpx[0]) == 0 else [tuple(c) for c in cpx]
-        rec = np.zeros(len(par), dtype=GRIB_CPX_DTYPE)
-        for i, (order, group_len) in enumerate(par):
-            if int(order) not in (0, 1, 2) or int(group_len) not in (8, 16, 32, 64):
-                raise ValueError(f"complex packing of order {order} in groups of {group_len}: 0, 1 or 2 and 8, 16, 32 or 64")
-            rec[i]["order"], rec[i]["length_ref"] = int(order), int(group_len)
-        return rec
+    ccsds = property(lambda self: self._params(CCSDS))
+    cpx = property(lambda self: self._params(CPX))
 
     @property
     def has_source_width(self):
@@ -390,8 +547,8 @@ class GribEncode:
         nbits, _ = self._per_field(widths.size, marks=True)
         nbits = np.where(nbits == self.SOURCE_WIDTH, widths, nbits).astype(np.int32)
         top = int(nbits.max()) if nbits.size and nbits.max() > 0 else 16
-        return GribEncode(np.where(nbits == 0, top, nbits).astype(np.int32),
-                          np.broadcast_to(self.decimal_scale, nbits.shape).copy(), ccsds=self.ccsds, cpx=self.cpx)
+        return self._like(np.where(nbits == 0, top, nbits).astype(np.int32),
+                          np.broadcast_to(self.decimal_scale, nbits.shape).copy(), self.params)
 
     @classmethod
     def from_field(cls, field, ccsds=None, cpx=None):
@@ -399,8 +556,7 @@ class GribEncode:
         or 16 if all are 0.  ccsds=True: the result is CCSDS-coded, each field with its source field's own block size,
         interval and preprocessor switch where the source is CCSDS-packed, with the defaults where it is not."""
         if ccsds is True and getattr(field, "ccsds", None) is not None:
-            ccsds = [(int(r["block_size"]), int(r["rsi"]), bool(int(r["flags"]) & _AEC_PREPROCESS))
-                     if int(r["block_size"]) else cls.CCSDS_DEFAULT for r in field.ccsds]
+            ccsds = [CCSDS.params_of(r) if int(r["block_size"]) else cls.CCSDS_DEFAULT for r in field.ccsds]
         nbits = field.rows["nbits"].astype(np.int32)
         marked = np.zeros(nbits.size, dtype=bool)
         if cpx is True:
@@ -422,61 +578,55 @@ class GribEncode:
                 raise ValueError(f"ddiv {want!r} is not 10.0 ** D for an integer D")
         return cls(nbits, dec, ccsds=ccsds, cpx=cpx)
 
+    def _like(self, nbits, decimal_scale, params):
+        return GribEncode(nbits, decimal_scale, **({} if self.codec is None else {self.codec.name: params}))
+
     def rows_of(self, r0, r1, n_fields):
         """The GribEncode of fields [r0, r1) of n_fields (`SOURCE_WIDTH` marks stay)."""
         nbits, _ = self._per_field(n_fields, marks=True)
-        par = None if self.ccsds is None else self.ccsds_records(n_fields)[r0:r1]
-        cpx = None if self.cpx is None else self.cpx_records(n_fields, marks=True)[r0:r1]
-        return GribEncode(nbits[r0:r1].copy(), np.broadcast_to(self.decimal_scale, (int(n_fields),))[r0:r1].copy(), ccsds=par,
-                          cpx=cpx)
+        par = None if self.codec is None else self.coded_records(n_fields, marks=True)[r0:r1]
+        return self._like(nbits[r0:r1].copy(), np.broadcast_to(self.decimal_scale, (int(n_fields),))[r0:r1].copy(), par)
 
-    def cpx_records(self, n_fields, n_values=0, nbits=0, marks=False):
-        """The wanted smm_grib_cpx_t records of n_fields fields (smm_grib_cpx_pack): order and group length of this rule,
-        n_values and nbits (the stored widths) as given."""
+    def coded_records(self, n_fields, n_values=0, nbits=0, marks=False, codec=None):
+        """The wanted records of n_fields fields for the pack step of this rule's codec (smm_grib_aec_pack,
+        smm_grib_cpx_pack): the parameters of this rule, n_values and nbits (the stored widths) as given."""
+        codec = codec or self.codec
         self._per_field(n_fields, marks=marks)
-        rec = np.zeros(int(n_fields), dtype=GRIB_CPX_DTYPE)
-        rec[:] = self.cpx if self.cpx.size > 1 else self.cpx[0]
+        par = self._params(codec)
+        rec = np.zeros(int(n_fields), dtype=codec.dtype)
+        rec[:] = par if par.size > 1 else par[0]
         rec["n_values"], rec["nbits"] = n_values, nbits
         return rec
+
+    def coded_bounds(self, n_points, n_fields, codec=None):
+        """Bytes the coded stream of each of n_fields fields of n_points points takes at most (int64; the codec's
+        pack_bound entry)."""
+        nbits, _ = self._per_field(n_fields)
+        return (codec or self.codec).bounds(self.coded_records(n_fields, int(n_points), nbits, codec=codec))
+
+    def cpx_records(self, n_fields, n_values=0, nbits=0, marks=False):
+        """`coded_records` of a rule with `cpx` (smm_grib_cpx_t: order and group length of this rule)."""
+        return self.coded_records(n_fields, n_values, nbits, marks, CPX)
 
     def cpx_bound(self, n_points, n_fields):
         """Bytes the coded streams of n_fields fields of n_points points take at most (smm_grib_cpx_pack_bound)."""
-        return int(self.cpx_bounds(n_points, n_fields).sum())
+        return int(self.coded_bounds(n_points, n_fields, CPX).sum())
 
     def cpx_bounds(self, n_points, n_fields):
         """The same field by field (int64)."""
-        from . import _lib
-        nbits, _ = self._per_field(n_fields)
-        rec = self.cpx_records(n_fields, int(n_points), nbits)
-        offs, total = np.zeros(rec.size + 1, dtype=np.uint64), ctypes.c_uint64(0)
-        _lib.call("smm_grib_cpx_pack_bound", ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribCpxStruct)), rec.size,
-                  offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(total))
-        offs[rec.size] = total.value
-        return np.diff(offs).astype(np.int64)
+        return self.coded_bounds(n_points, n_fields, CPX)
 
     def ccsds_records(self, n_fields, n_values=0, nbits=0):
-        """The wanted smm_grib_aec_t records of n_fields fields (smm_grib_aec_pack): block size, interval and flags of this
-        rule, n_values and nbits (the stored widths) as given."""
-        self._per_field(n_fields)
-        rec = np.zeros(int(n_fields), dtype=GRIB_AEC_DTYPE)
-        rec[:] = self.ccsds if self.ccsds.size > 1 else self.ccsds[0]
-        rec["n_values"], rec["nbits"] = n_values, nbits
-        return rec
+        """`coded_records` of a rule with `ccsds` (smm_grib_aec_t: block size, interval and flags of this rule)."""
+        return self.coded_records(n_fields, n_values, nbits, codec=CCSDS)
 
     def ccsds_bound(self, n_points, n_fields):
         """Bytes the coded streams of n_fields fields of n_points points take at most (smm_grib_aec_pack_bound)."""
-        return int(self.ccsds_bounds(n_points, n_fields).sum())
+        return int(self.coded_bounds(n_points, n_fields, CCSDS).sum())
 
     def ccsds_bounds(self, n_points, n_fields):
         """The same field by field (int64)."""
-        from . import _lib
-        nbits, _ = self._per_field(n_fields)
-        rec = self.ccsds_records(n_fields, int(n_points), nbits)
-        offs, total = np.zeros(rec.size + 1, dtype=np.uint64), ctypes.c_uint64(0)
-        _lib.call("smm_grib_aec_pack_bound", ctypes.cast(rec.ctypes.data, ctypes.POINTER(_lib.GribAecStruct)), rec.size,
-                  offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ctypes.byref(total))
-        offs[rec.size] = total.value
-        return np.diff(offs).astype(np.int64)
+        return self.coded_bounds(n_points, n_fields, CCSDS)
 
     def _per_field(self, n_fields, marks=False):
         n_fields = int(n_fields)
@@ -501,7 +651,7 @@ class GribEncode:
         if n_points < 0 or n_points >= 2 ** 31:
             raise ValueError("n_points must be within [0, 2^31)")
         nbits, _ = self._per_field(n_fields)
-        sizes = np.array([_align4((n_points + 7) // 8) + _align4((n_points * int(w) + 7) // 8) for w in nbits], dtype=np.uint64)
+        sizes = np.array([align4((n_points + 7) // 8) + align4((n_points * int(w) + 7) // 8) for w in nbits], dtype=np.uint64)
         offs = np.zeros(int(n_fields), dtype=np.uint64)
         if offs.size:
             offs[1:] = np.cumsum(sizes)[:-1]
@@ -521,7 +671,7 @@ class GribEncode:
         buf = np.zeros(total, dtype=np.uint8)
         rows = np.zeros(nf, dtype=GRIB_ROW_DTYPE)
         bitmaps = np.zeros(nf, dtype=GRIB_BITMAP_DTYPE)
-        bm_bytes = _align4((n + 7) // 8)
+        bm_bytes = align4((n + 7) // 8)
         for b in range(nf):
             w, dd, off = int(nbits[b]), float(ddiv[b]), int(offs[b])
             with np.errstate(over="ignore", invalid="ignore"):
@@ -549,7 +699,7 @@ class GribEncode:
                     buf[off + bm_bytes:off + bm_bytes + packed.size] = packed
             rows[b] = (off + bm_bytes, ref, float(np.ldexp(1.0, E)), dd, width, 0)
             bitmaps[b] = (GRIB_NO_BITMAP if nv == n else off, nv)
-        if self.ccsds is not None or self.cpx is not None:
+        if self.codec is not None:
             return self._encode_coded(buf, rows, bitmaps, shape, n)
         return GribField(buf, rows, shape, n, bitmaps=bitmaps)
 
@@ -558,10 +708,8 @@ class GribEncode:
         every field's bitmap slot (align4(ceil(n_points / 8)) bytes, written whether the field has missing points or not)
         in field order, then the streams back to back in field order, each at a 4-byte-aligned offset.  A field of width 0
         has no stream (block_size 0; order GRIB_CPX_SIMPLE).  The rows keep the widths of the integers."""
-        nf, bm_bytes = rows.size, _align4((n + 7) // 8)
-        aec = self.ccsds is not None
-        rec = self.ccsds_records(nf, bitmaps["n_values"], rows["nbits"]) if aec else \
-            self.cpx_records(nf, bitmaps["n_values"], rows["nbits"])
+        nf, bm_bytes = rows.size, align4((n + 7) // 8)
+        rec = self.coded_records(nf, bitmaps["n_values"], rows["nbits"])
         streams, at = [], nf * bm_bytes
         head = np.zeros(at, dtype=np.uint8)
         rows, bitmaps = rows.copy(), bitmaps.copy()
@@ -570,22 +718,14 @@ class GribEncode:
             head[b * bm_bytes:(b + 1) * bm_bytes] = buf[off - bm_bytes:off]
             if int(bitmaps["bitmap_off"][b]) != GRIB_NO_BITMAP:
                 bitmaps["bitmap_off"][b] = b * bm_bytes
+            q = _unpack_bits(bytes(memoryview(buf)[off:off + (nv * w + 7) // 8]), w, nv).astype(np.uint32)
+            # the record of the stream written (marked simple-packed, without bytes, at width 0)
+            st, rec[b] = self.codec.encode(q, rec[b])
             rec["byte_off"][b] = rows["byte_off"][b] = at
-            if w == 0 and aec:
-                rec["block_size"][b] = 0
-                continue
-            q = _unpack_bits(bytes(memoryview(buf)[off:off + (nv * w + 7) // 8]), w, nv).astype(np.uint32) if w else \
-                np.zeros(nv, dtype=np.uint32)
-            if aec:
-                st = aec_encode(q, rec[b])
-            else:      # the full record of the stream written (marked simple-packed, without bytes, at width 0)
-                st, rec[b] = cpx_encode(q, rec[b])
-                rec["byte_off"][b] = at
             rec["byte_len"][b] = st.size
-            streams.append(np.concatenate([st, np.zeros(_align4(st.size) - st.size, dtype=np.uint8)]))
-            at += _align4(st.size)
-        return GribField(np.concatenate([head] + streams), rows, shape, n, bitmaps=bitmaps, ccsds=rec if aec else None,
-                         cpx=None if aec else rec)
+            streams.append(np.concatenate([st, np.zeros(align4(st.size) - st.size, dtype=np.uint8)]))
+            at += align4(st.size)
+        return GribField(np.concatenate([head] + streams), rows, shape, n, bitmaps=bitmaps, **{self.codec.name: rec})
 
     def __repr__(self):
         return f"<GribEncode widths {sorted(set(self.nbits.tolist()))}, D {sorted(set(self.decimal_scale.tolist()))}>"
@@ -659,27 +799,24 @@ def _unpack_bits(raw, nbits, count):
     return bits.astype(np.uint64) @ (np.uint64(1) << np.arange(nbits - 1, -1, -1, dtype=np.uint64))
 
 
-def _decode_rule(buf, rule, count, bitmap=None, aec=None, cpx=None, mvm=0):
+def _decode_rule(buf, rule, count, bitmap=None, coded=None):
     """The float64 values of one message from its rule (file offset of the packed values, R, 2^E, 10^D, bit width):
     the statement the message classes evaluate, on the message's own bytes only.  bitmap: None, or (file offset of the
     bitmap's bytes, values in the stream) -- the values go to the points whose bit is set, the others are NaN.
-    aec: None, or the GRIB_AEC_DTYPE record of a CCSDS-packed message -- its integers come out of the coded stream.
-    cpx: None, or the GRIB_CPX_DTYPE record of a complex-packed message -- its integers come out of its groups."""
+    coded: None, or the one-row `CodedRows` of a CCSDS- or complex-packed message -- its integers come out of the coded
+    stream (missing values coded inside it become NaN; such a message has no bitmap here)."""
     off, ref, scale, ddiv, nbits = rule
     n = count if bitmap is None else bitmap[1]
-    if cpx is not None:
-        if int(cpx["n_values"]) != n:
-            raise ValueError(f"complex-packed stream of {int(cpx['n_values'])} values for {n} points")
-        if mvm:               # missing values coded inside the groups (such a message has no bitmap here)
-            q, there = cpx_decode_mv(buf, cpx, mvm)
+    if coded is not None:
+        rec, mvm = coded.recs[0], 0 if coded.missing is None else int(coded.missing[0])
+        if int(rec["n_values"]) != n:
+            raise ValueError(f"{coded.codec.stream} of {int(rec['n_values'])} values for {n} points")
+        q, there = coded.codec.decode(buf, rec, mvm)
+        if there is not None:
             values = np.full(n, np.nan)
             values[there] = (ref + q.astype(np.float64) * scale) / ddiv
             return values
-        q = cpx_decode(buf, cpx).astype(np.float64)
-    elif aec is not None and nbits:
-        if int(aec["n_values"]) != n:
-            raise ValueError(f"CCSDS stream of {int(aec['n_values'])} values for {n} points")
-        q = aec_decode(buf, aec).astype(np.float64)
+        q = q.astype(np.float64)
     else:
         q = _unpack_bits(bytes(memoryview(buf)[off:off + (n * nbits + 7) // 8]), nbits, n)
     packed = (ref + q * scale) / ddiv
@@ -718,9 +855,10 @@ class _Field:
     def field_values(self, buf):
         if self.values is not None:
             return self.values
-        aec = None if self.raw_aec is None else np.array(self.raw_aec, dtype=GRIB_AEC_DTYPE)
-        cpx = None if self.raw_cpx is None else np.array(self.raw_cpx, dtype=GRIB_CPX_DTYPE)
-        return _decode_rule(buf, self.raw_rule, self.npoints, self.raw_bitmap, aec, cpx, self.raw_mvm)
+        coded = CodedRows.of(1, None if self.raw_aec is None else np.array(self.raw_aec, dtype=GRIB_AEC_DTYPE),
+                             None if self.raw_cpx is None else np.array(self.raw_cpx, dtype=GRIB_CPX_DTYPE),
+                             None if self.raw_cpx is None else [self.raw_mvm])
+        return _decode_rule(buf, self.raw_rule, self.npoints, self.raw_bitmap, coded)
 
     def _set_grid(self, rep, ni, nj, la1, lo1, la2, lo2, n_gauss, scan, pl, tol):
         if scan & 0x20:

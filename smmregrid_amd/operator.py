@@ -11,7 +11,6 @@ import time
 import numpy as np
 
 from . import _grib, _lib
-from . import device as _device
 from .device import (DeviceArray, bfloat16, check_half_pair, dtype_code, field_dtype_code, is_half_dtype,
                      is_packed_dtype, result_cache, result_dtype, _stream_handle, current_device, grib_pack)
 
@@ -322,7 +321,7 @@ class SparseOperator:
                            (self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows)), y_res, cf, cf_out, "out")
 
     def apply_grib(self, x, rows, x_bytes=None, y=None, masked=False, remap_area_min=0.0, flags=0, stream=None,
-                   bitmaps=None, skipna=False, ccsds=None, cpx=None, cpx_missing=None):
+                   bitmaps=None, skipna=False, ccsds=None, cpx=None, cpx_missing=None, coded=None):
         """Y = epilogue(fill(decode(X)) . W) for GRIB simple-packed fields resident in HBM as they are on disk
         (smm_apply_grib).  x: a `DeviceArray` of uint8 -- or a raw device pointer with x_bytes -- holding the packed
         bit streams (4-byte aligned; the array -- or the allocation behind a raw pointer -- must cover x_bytes rounded
@@ -344,21 +343,16 @@ class SparseOperator:
         cpx_missing: beside cpx, one uint8 per row -- the row's missing value management (section 5's octet 23): 1 or 2
         means missing values are codes inside the groups.  The device step (smm_grib_cpx_unpack_mv) turns them into a
         bitmap and the present integers, and the gather runs as with bitmaps=: the bits of the same call on the
-        simple-packed integers with that bitmap.  Such a row cannot have a bitmap of its own as well."""
+        simple-packed integers with that bitmap.  Such a row cannot have a bitmap of its own as well.
+        coded: what the three keywords say as one `CodedRows` (`GribField.coded`), in their place."""
         rows, rows_p = _grib.grib_rows(rows)
-        kind, recs = _grib.one_kind(ccsds, cpx)
-        if cpx_missing is not None and kind is not _grib.CPX:
-            raise ValueError("cpx_missing goes with cpx")
-        missing = None
-        if kind is not None:      # what is refused about the records comes before the device is looked at
-            recs = _grib.records(kind, recs, rows)
-            missing = _grib.missing_of(cpx_missing, rows)
-            if missing is not None and bitmaps is not None:
+        coded = _grib.CodedRows.of(rows.size, ccsds, cpx, cpx_missing, coded=coded)
+        if coded is not None:      # what is refused about the records comes before the device is looked at
+            if bitmaps is not None:
                 bitmaps, _ = _grib.grib_bitmaps(bitmaps, rows.size)
-                _grib.refuse_bitmap_with_missing(bitmaps, missing, kind.is_coded(recs, rows))
-        x_ptr, n_bytes = _grib.packed_bytes(x, x_bytes, "apply_grib", raw=kind is None)
-        if kind is not None:
-            idx, total = _grib.coded_rows(kind, recs, rows, missing)
+            idx, total = coded.streams(rows, bitmaps)
+        x_ptr, n_bytes = _grib.packed_bytes(x, x_bytes, "apply_grib", raw=coded is None)
+        if coded is not None:
             # bitmaps and simple-packed rows stay where they are in x: then x travels along in front of the new streams
             plain = rows["nbits"] != 0
             plain[idx] = False
@@ -368,7 +362,7 @@ class SparseOperator:
             if keep and base:
                 _lib.call("smm_memcpy_d2d", ctypes.c_void_p(both.ptr), x_ptr, base, _stream_handle(stream))
             dst = DeviceArray((total,), np.uint8, ptr=both.ptr + base, base=both)
-            rows, bitmaps = _grib.unpack(kind, x, n_bytes, dst, base, rows, recs, idx, stream, missing, bitmaps, self.n_src)
+            rows, bitmaps = _grib.unpack(coded, x, n_bytes, dst, base, rows, idx, stream, bitmaps, self.n_src)
             return self.apply_grib(both, rows, x_bytes=base + total, y=y, masked=masked, remap_area_min=remap_area_min,
                                    flags=flags, stream=stream, bitmaps=bitmaps, skipna=skipna)
         n_batch = rows.size
@@ -378,17 +372,17 @@ class SparseOperator:
                         self.n_dst, n_batch, float(remap_area_min), fl, _stream_handle(stream))
         return y
 
-    def _apply_host_grib_coded(self, buf, rows, out, bitmaps, kind, recs, chunk_rows, missing=None, **apply_kw):
+    def _apply_host_grib_coded(self, buf, rows, out, bitmaps, coded, chunk_rows, **apply_kw):
         """`apply_host_grib(ccsds=)` and `apply_host_grib(cpx=)`: a synchronous loop over chunks of consecutive rows
         (`_grib.host_chunks`), each chunk's Y copied back."""
         out = _grib.float64_result(out, (rows.size, self.n_dst), result_cache.empty, "out")
-        for r0, r1, y, _ in _grib.host_chunks(self, buf, rows, bitmaps, kind, recs, chunk_rows, missing=missing, **apply_kw):
+        for r0, r1, y, _ in _grib.host_chunks(self, buf, rows, bitmaps, coded, chunk_rows, **apply_kw):
             y.to_host(out=out[r0:r1])
         return out
 
-    def _apply_host_grib_out_coded(self, buf, rows, grib_out, okind, bitmaps, kind, recs, chunk_rows, missing=None, **apply_kw):
-        """`apply_host_grib(grib_out=GribEncode(..., ccsds=...))` and `(..., cpx=...)`, okind the `_grib.CodedOut` of the
-        two: the chunks of `_grib.host_chunks`, each chunk's float64 Y packed on the device (smm_grib_pack) and its
+    def _apply_host_grib_out_coded(self, buf, rows, grib_out, bitmaps, coded, chunk_rows, **apply_kw):
+        """`apply_host_grib(grib_out=GribEncode(..., ccsds=...))` and `(..., cpx=...)`, by the codec of grib_out: the
+        chunks of `_grib.host_chunks`, each chunk's float64 Y packed on the device (smm_grib_pack) and its
         integers coded as CCSDS or complex-packed streams (smm_grib_aec_pack, smm_grib_cpx_pack); one D2H copy of the
         chunk's bitmaps (none when no cell is missing: they are all ones) and one of the bytes its streams use.  Y and
         the simple-packed streams never leave the device.  The chunk budget counts the simple-packed slots and the
@@ -396,15 +390,15 @@ class SparseOperator:
         chunk by chunk, the width smm_grib_cpx_unpack reports for the source row.  The result's buffer is laid out as
         `GribEncode.encode` lays it out: every field's bitmap slot, then the streams back to back."""
         from .griblite import GRIB_BITMAP_DTYPE, GRIB_NO_BITMAP, GRIB_ROW_DTYPE, GribField
-        n_batch, D = rows.size, self.n_dst
+        n_batch, D, codec = rows.size, self.n_dst, grib_out.codec
         worst = grib_out.rows_of(0, n_batch, n_batch)
         if worst.has_source_width:
-            if kind is not _grib.CPX:
+            if coded is None or coded.codec is not _grib.CPX:
                 worst._per_field(n_batch)      # the ValueError of an unresolved mark
             worst = worst.resolved(np.full(n_batch, 32, dtype=np.int32))
         offs, total = worst.layout(D, n_batch)
         slot = np.diff(np.append(offs, np.uint64(total))).astype(np.int64)
-        bound = getattr(worst, okind.bounds)(D, n_batch)
+        bound = worst.coded_bounds(D, n_batch)
         bm_bytes = (D + 7) // 8 + (-((D + 7) // 8)) % 4
         result = np.empty(n_batch * bm_bytes + int(bound.sum()), dtype=np.uint8)      # cut to the bytes used at the end
         head = result[:n_batch * bm_bytes]
@@ -412,20 +406,18 @@ class SparseOperator:
         full = np.packbits(np.ones(D, dtype=np.uint8))
         rows_out = np.zeros(n_batch, dtype=GRIB_ROW_DTYPE)
         bitmaps_out = np.zeros(n_batch, dtype=GRIB_BITMAP_DTYPE)
-        recs_out = np.zeros(n_batch, dtype=okind.dtype)
+        recs_out = np.zeros(n_batch, dtype=codec.dtype)
         at = n_batch * bm_bytes
         # per row beside Y: its simple-packed slot, the bound of its stream, the coder's scratch
-        extra = slot + bound + okind.scratch(D)
-        pack = getattr(_device, okind.pack)
-        for r0, r1, y, rows_in in _grib.host_chunks(self, buf, rows, bitmaps, kind, recs, chunk_rows, extra_cost=extra,
-                                                    missing=missing, **apply_kw):
+        extra = slot + bound + codec.out_scratch(D)
+        for r0, r1, y, rows_in in _grib.host_chunks(self, buf, rows, bitmaps, coded, chunk_rows, extra_cost=extra, **apply_kw):
             enc = grib_out.rows_of(r0, r1, n_batch)
             if enc.has_source_width:
                 enc = enc.resolved(rows_in["nbits"])
             packed, rows_c, bm_c = grib_pack(y, enc)
             slot_c = np.diff(np.append(*enc.layout(D, r1 - r0))).astype(np.int64)
-            want = getattr(enc, okind.records)(r1 - r0, bm_c["n_values"], rows_c["nbits"])
-            coded, rows_c, recs_c = pack(packed, rows_c, want)
+            want = _grib.CodedRows(codec, enc.coded_records(r1 - r0, bm_c["n_values"], rows_c["nbits"]))
+            streams, rows_c, recs_c = _grib.pack_device("apply_host_grib", packed, rows_c, coded=want)
             missing = np.flatnonzero(bm_c["bitmap_off"] != GRIB_NO_BITMAP)
             h = head[r0 * bm_bytes:r1 * bm_bytes].reshape(r1 - r0, bm_bytes)
             h[:, :full.size] = full
@@ -437,16 +429,16 @@ class SparseOperator:
                 for i in missing:                                     # slots of different sizes: row by row
                     DeviceArray((bm_bytes,), np.uint8, ptr=packed.ptr + int(bm_c["bitmap_off"][i]), base=packed).to_host(out=h[i])
             bm_c["bitmap_off"][missing] = (r0 + missing) * bm_bytes
-            if coded.nbytes:
-                coded.to_host(out=result[at:at + coded.nbytes])
+            if streams.nbytes:
+                streams.to_host(out=result[at:at + streams.nbytes])
             rows_c["byte_off"] += np.uint64(at)
             recs_c["byte_off"] += np.uint64(at)
             rows_out[r0:r1], bitmaps_out[r0:r1], recs_out[r0:r1] = rows_c, bm_c, recs_c
-            at += coded.nbytes
-        return GribField(result[:at], rows_out, (n_batch, D), D, bitmaps=bitmaps_out, **{okind.attr: recs_out})
+            at += streams.nbytes
+        return GribField(result[:at], rows_out, (n_batch, D), D, bitmaps=bitmaps_out, **{codec.name: recs_out})
 
     def apply_host_grib(self, buf, rows, out=None, masked=False, remap_area_min=0.0, flags=0, chunk_rows=0, bitmaps=None,
-                        skipna=False, grib_out=None, ccsds=None, cpx=None, cpx_missing=None):
+                        skipna=False, grib_out=None, ccsds=None, cpx=None, cpx_missing=None, coded=None):
         """The host twin (smm_apply_host_grib): buf is a host uint8 array -- typically a whole GRIB file -- and rows as
         for `apply_grib`.  Each row's packed bytes are staged and cross PCIe as they are (2 B per cell at 16 bits), no
         host decode runs.  Returns a float64 (B, D) numpy array, the bits of `apply_host` on the decoded float32 field.
@@ -471,27 +463,23 @@ class SparseOperator:
         CCSDS-packed).  Only there a width of `GribEncode.SOURCE_WIDTH` is legal: it becomes, chunk by chunk, the width
         the source row's integers decode to.
         cpx_missing as for `apply_grib`, carried chunk by chunk; a result record never carries it: missing cells of the
-        result are bitmapped as ever."""
+        result are bitmapped as ever.  coded as for `apply_grib`."""
         rows, rows_p = _grib.grib_rows(rows)
         buf = np.ascontiguousarray(buf)
         if buf.dtype != np.uint8 or buf.ndim != 1:
             raise TypeError("apply_host_grib takes the packed bytes as a 1-d uint8 array")
-        kind, recs = _grib.one_kind(ccsds, cpx)
-        if cpx_missing is not None and kind is not _grib.CPX:
-            raise ValueError("cpx_missing goes with cpx")
-        okind = _grib.out_kind(grib_out)
-        if grib_out is not None and kind is not None and (okind is None or kind not in okind.takes):
-            raise ValueError(f"{kind.arg} does not go with grib_out: decode the field on the host first")
-        if okind is not None and out is not None:
-            raise ValueError(f"a {okind.words} result comes in a buffer of its own: its size is known only afterwards")
+        coded = _grib.CodedRows.of(rows.size, ccsds, cpx, cpx_missing, coded=coded)
+        codec_out = None if grib_out is None else grib_out.codec
+        if grib_out is not None and coded is not None and (codec_out is None or coded.codec.name not in codec_out.takes):
+            raise ValueError(f"{coded.codec.name} does not go with grib_out: decode the field on the host first")
+        if codec_out is not None and out is not None:
+            raise ValueError(f"a {codec_out.result} result comes in a buffer of its own: its size is known only afterwards")
         n_batch = rows.size
-        if kind is not None or okind is not None:      # rows decoded or coded on the device: the chunk loop
+        if coded is not None or codec_out is not None:      # rows decoded or coded on the device: the chunk loop
             apply_kw = dict(masked=masked, remap_area_min=remap_area_min, flags=int(flags), skipna=skipna)
-            if okind is not None:
-                return self._apply_host_grib_out_coded(buf, rows, grib_out, okind, bitmaps, kind, recs, int(chunk_rows),
-                                                       missing=cpx_missing, **apply_kw)
-            return self._apply_host_grib_coded(buf, rows, out, bitmaps, kind, recs, int(chunk_rows), missing=cpx_missing,
-                                               **apply_kw)
+            if codec_out is not None:
+                return self._apply_host_grib_out_coded(buf, rows, grib_out, bitmaps, coded, int(chunk_rows), **apply_kw)
+            return self._apply_host_grib_coded(buf, rows, out, bitmaps, coded, int(chunk_rows), **apply_kw)
         fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
         if grib_out is not None:
             bitmaps, bm_p = (None, None) if bitmaps is None else _grib.grib_bitmaps(bitmaps, n_batch)

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from .device import CFDecode, CFEncode, DeviceArray, bfloat16, is_half_dtype, is_packed_dtype, to_device
-from .griblite import GribEncode, GribField
+from .griblite import CCSDS, CPX, GribEncode, GribField
 from .gridtype import GridType, tolist
 from .lazy import LazyArray, is_dask, map_batch_blocks
 from .operator import OperatorGroup
@@ -422,23 +422,20 @@ class Regridder(object):
 
     def _grib_decode_reason(self, dims, gridtype, out_dtype, levels, ccsds=False, cpx=False):
         """Why a `GribField` with these dims is decoded on the host, or None: it takes the raw road.  levels: it meets
-        masked-level (3-D) weights.  ccsds: some of its fields are CCSDS-packed (`GribField.ccsds`) -- their road is the
-        one of 2-D weights and float64 results (smm_grib_aec_unpack ahead of the gather).  cpx: some are complex-packed
-        (`GribField.cpx`, templates 5.2 / 5.3) -- the same road through smm_grib_cpx_unpack, and a packed result only
-        complex-packed again (grib_out_cpx): the row record of such a field does not hold the width of its integers, which
-        the device decode reports chunk by chunk.  The one
+        masked-level (3-D) weights.  ccsds, cpx: some of its fields are CCSDS-packed or complex-packed (`GribField.coded`)
+        -- their road is the one of 2-D weights (the codec's unpack step ahead of the gather), and a packed result only
+        coded the same way again (grib_out_ccsds, grib_out_cpx): the row record of a complex-packed field does not hold
+        the width of its integers, which the device decode reports chunk by chunk.  The one
         condition behind `_grib_or_decoded` and the guards of `apply_weights` and `regrid3d`, which direct calls reach
         without it."""
+        codec, coded_out = (CPX, getattr(self, "grib_out_cpx", False)) if cpx else \
+            (CCSDS, getattr(self, "grib_out_ccsds", False)) if ccsds else (None, False)
         if not self.packed:
             return "packed=False"
-        if ccsds and levels:
-            return "CCSDS packing on masked levels"
-        if cpx and levels:
-            return "complex packing on masked levels"
-        if cpx and self.grib_out and not getattr(self, "grib_out_cpx", False):
-            return "complex packing with grib_out"
-        if ccsds and self.grib_out and not getattr(self, "grib_out_ccsds", False):
-            return "CCSDS packing with grib_out"
+        if codec is not None and levels:
+            return f"{codec.packing} on masked levels"
+        if codec is not None and self.grib_out and not coded_out:
+            return f"{codec.packing} with grib_out"
         if levels and not self.packed_levels:
             return "masked levels"
         if self.skipna and not self.packed_skipna:
@@ -638,16 +635,14 @@ class Regridder(object):
                     enc = GribEncode.from_field(src, ccsds=True if self.grib_out_ccsds else None,
                                                 cpx=True if self.grib_out_cpx else None)
                     y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps,
-                                           skipna=skipna, grib_out=enc, ccsds=src.ccsds if self.grib_out_ccsds else None,
-                                           cpx=src.cpx if self.grib_out_cpx else None,
-                                           cpx_missing=src.cpx_missing if self.grib_out_cpx else None)
+                                           skipna=skipna, grib_out=enc, coded=src.coded)
                     return GribField(y.buf, y.rows, kept_shape + tgt_shape, op.n_dst, bitmaps=y.bitmaps, ccsds=y.ccsds,
                                      cpx=y.cpx)
                 # (CCSDS-packed fields: their streams are decoded on the device ahead of the gather, smm_grib_aec_unpack)
                 # (complex-packed fields likewise: smm_grib_cpx_unpack; those with missing values inside their groups --
                 # open_dataset(..., cpx_missing=True) -- through smm_grib_cpx_unpack_mv, which hands the gather a bitmap)
                 y = op.apply_host_grib(src.buf, src.rows, masked=masked, remap_area_min=area_min, bitmaps=src.bitmaps,
-                                       skipna=skipna, ccsds=src.ccsds, cpx=src.cpx, cpx_missing=src.cpx_missing)
+                                       skipna=skipna, coded=src.coded)
                 return y.reshape(kept_shape + tgt_shape)
             if sb_in:
                 x = src.reshape(-1, n_batch)                  # (S, B): the batch values of a cell contiguous

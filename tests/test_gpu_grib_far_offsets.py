@@ -348,7 +348,7 @@ def test_cpx_pack_input_far(far):
     cases = _cpx_pack_rows()
     lay, x = far_streams(far, [_Stream(c, cc.pack_bits(c.X, c.nbits)) for c in cases], seed=13)
     rows, want = t_cpx_pack.pack_records(cases, lay.offsets())
-    bound = _grib._layout_total("smm_grib_cpx_pack_bound", _grib.CPX, want)
+    bound = _grib.CodedRows(_grib.CPX, want).bound()
     out = sentinel_bytes(far, bound + fc.GUARD)
     coded, rows_out, recs = grib_cpx_pack(x, rows, want, x_bytes=lay.x_bytes, out=out)
     assert coded.nbytes <= bound
@@ -367,7 +367,7 @@ def test_aec_pack_input_far(far):
     cases += [alias] + [cc.fixture(n) for n in ("edge_n43_w32_pp0", "short_w16_smooth")]
     lay, x = far_streams(far, [_Stream(c, cc.pack_bits(c.values, c.nbits)) for c in cases], seed=14)
     rows, want = t_aec_pack.pack_records(cases, lay.offsets())
-    bound = _grib._layout_total("smm_grib_aec_pack_bound", _grib.CCSDS, want)
+    bound = _grib.CodedRows(_grib.CCSDS, want).bound()
     out = sentinel_bytes(far, bound + fc.GUARD)
     coded, rows_out, recs = grib_aec_pack(x, rows, want, x_bytes=lay.x_bytes, out=out)
     assert coded.nbytes <= bound
@@ -465,7 +465,7 @@ def test_cpx_output_far(far):
     assert np.array_equal(Spacer(HEAD + 1, SAMPLE).edges(reader(xa))[0], sample[:EDGE])
     cases = [true[0], sp[0], true[1], sp[1], true[2]]
     rows, want = t_cpx_pack.pack_records(cases, [offs_in[0], sp[0].off, offs_in[1], sp[1].off, offs_in[2]])
-    bound = _grib._layout_total("smm_grib_cpx_pack_bound", _grib.CPX, want)
+    bound = _grib.CodedRows(_grib.CPX, want).bound()
     out = sentinel_bytes(far, bound + fc.GUARD)
     scratch(far, (2 * (n_sp // 64 + 1) + 3 * 256) * 8 + (2 * (n_sp // 1024 + 1) + 6) * 12 + 4096)   # groups and tiles
     coded, rows_c, recs = grib_cpx_pack(byte_view(xa), rows, want, x_bytes=x_bytes, out=out)
@@ -530,7 +530,7 @@ def test_aec_output_far(far):
     ib, ic = R + 1, 2 * R + 2
     rows, want = t_aec_pack.pack_records(cases, [offs_in[0]] + [s.off for s in sp[:R]] + [offs_in[1]] + [s.off for s in sp[R:]]
                                          + [offs_in[2]])
-    bound = _grib._layout_total("smm_grib_aec_pack_bound", _grib.CCSDS, want)
+    bound = _grib.CodedRows(_grib.CCSDS, want).bound()
     out = sentinel_bytes(far, bound + fc.GUARD)
     scratch(far, (2 * R * n_sp // 8 + 64) * 20 + (1 << 20))
     coded, rows_c, recs = grib_aec_pack(byte_view(xa), rows, want, x_bytes=x_bytes, out=out)

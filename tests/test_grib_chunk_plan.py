@@ -5,7 +5,7 @@ tests/test_gpu_grib_ccsds.py and tests/test_gpu_grib_complex.py, which run the p
 import numpy as np
 import pytest
 
-from smmregrid_amd import GRIB_AEC_DTYPE, GRIB_BITMAP_DTYPE, GRIB_NO_BITMAP, GRIB_ROW_DTYPE, _grib, _lib
+from smmregrid_amd import GRIB_AEC_DTYPE, GRIB_BITMAP_DTYPE, GRIB_CPX_DTYPE, GRIB_NO_BITMAP, GRIB_ROW_DTYPE, _grib, _lib
 from tests import ccsds_cases as cc
 from tests import complex_cases as xc
 
@@ -40,7 +40,11 @@ CALLS = ["ccsds-bitmaps", "ccsds-mixed", "cpx-bitmaps", "cpx-mixed", "simple"]
 
 def plan(name, chunk_rows, target=HUGE):
     kind, buf, rows, recs, bms, extra = call(name)
-    return list(_grib.plan_chunks(buf.size, rows, bms, kind, recs, S, D, chunk_rows, target, extra))
+    return list(_grib.plan_chunks(buf.size, rows, bms, coded_of(kind, rows, recs), S, D, chunk_rows, target, extra))
+
+
+def coded_of(kind, rows, recs):
+    return None if kind is None else _grib.CodedRows.of(rows.size, **{kind.name: recs})
 
 
 def is_coded(kind, rows, recs, i):
@@ -197,7 +201,7 @@ def hand_call():
 
 def hand_plan(chunk_rows, target, buf_size=400, rows=None, recs=None):
     r, q, bms = hand_call()
-    return list(_grib.plan_chunks(buf_size, r if rows is None else rows, bms, _grib.CCSDS, q if recs is None else recs,
+    return list(_grib.plan_chunks(buf_size, r if rows is None else rows, bms, coded_of(_grib.CCSDS, r, q if recs is None else recs),
                                   40, 5, chunk_rows, target))
 
 
@@ -239,3 +243,53 @@ def test_the_plan_refuses_bytes_outside_the_buffer_and_a_wrong_count():
     recs["n_values"][2] = 40                                           # the row holds the 25 points of its bitmap
     with pytest.raises(ValueError, match="a coded row's record has n_values different from the points its row holds"):
         hand_plan(0, HUGE, recs=recs)
+
+
+# ------------------------------------------------------------------------------------------------ the coded rows of a call
+def test_coded_rows_keep_records_and_missing_values_together():
+    """`CodedRows`: built once from the keywords with their checks; a slice or an index array is a copy that keeps each
+    row's record beside its missing value management; cost and refusal read the two together."""
+    recs = np.zeros(5, dtype=GRIB_CPX_DTYPE)
+    recs["byte_len"], recs["n_values"], recs["n_groups"], recs["nbits"], recs["width_ref"], recs["width_bits"] = 64, 100, 4, 8, 3, 3
+    recs["length_ref"], recs["length_inc"], recs["length_last"], recs["length_bits"], recs["n_oct"] = 20, 1, 40, 4, 2
+    recs["order"], recs["byte_off"] = (2, _lib.GRIB_CPX_SIMPLE, 1, _lib.GRIB_CPX_SIMPLE, 0), 100 * np.arange(5)
+    missing = np.array([0, 1, 2, 0, 1], dtype=np.uint8)
+    rows = np.zeros(5, dtype=GRIB_ROW_DTYPE)
+    coded = _grib.CodedRows.of(5, cpx=recs, cpx_missing=missing)
+    assert coded.codec is _grib.CPX and coded.is_coded(rows).tolist() == [True, False, True, False, True]
+    part, pick = coded[1:4], coded[np.array([4, 0])]
+    assert part.recs["byte_off"].tolist() == [100, 200, 300] and part.missing.tolist() == [1, 2, 0]
+    assert pick.recs["byte_off"].tolist() == [400, 0] and pick.missing.tolist() == [1, 0] and pick.codec is _grib.CPX
+    part.recs["byte_off"], part.missing[:] = 7, 9
+    assert coded.recs["byte_off"].tolist() == [0, 100, 200, 300, 400] and coded.missing.tolist() == [0, 1, 2, 0, 1]
+    assert _grib.CodedRows.of(5, cpx=recs)[2:].missing is None and _grib.CodedRows.of(5) is None
+    # the coded rows and the bytes of their transcoded streams: 4 B per value, and a bitmap slot of align4(ceil(100 / 8))
+    # bytes for a coded row with missing values inside its groups -- row 1 has the octet but no coded stream
+    idx, total = coded.streams(rows)
+    assert idx.tolist() == [0, 2, 4] and total == 3 * 400 + 2 * 16
+    assert _grib.CodedRows.of(5, cpx=recs).streams(rows)[1] == 3 * 400 and coded[1:2].streams(rows[1:2])[1] == 0
+    n_val, nbits = np.full(5, 100, dtype=np.int64), np.zeros(5, dtype=np.int64)
+    plain = 12 * 100 + 16 * 4 + 256
+    assert coded.device_cost(coded.is_coded(rows), n_val, nbits).tolist() == \
+        [plain, 0, plain + _grib.cpx_missing_cost(100), 0, plain + _grib.cpx_missing_cost(100)]
+    bms = np.zeros(5, dtype=GRIB_BITMAP_DTYPE)
+    bms["bitmap_off"], bms["n_values"] = GRIB_NO_BITMAP, 100
+    bms["bitmap_off"][[0, 1]] = 0                     # a coded row without missing values, a row that is not coded
+    assert coded.streams(rows, bms)[0].tolist() == [0, 2, 4]
+    bms["bitmap_off"][2] = 0
+    with pytest.raises(ValueError, match="bitmap and missing values"):
+        coded.streams(rows, bms)
+    assert coded[3:].streams(rows[3:], bms[3:])[0].tolist() == [1]
+    # the checks of the keywords
+    aec = np.zeros(5, dtype=GRIB_AEC_DTYPE)
+    for kw, text in ((dict(cpx=recs[:4]), "4 complex-packing records for 5 rows"),
+                     (dict(ccsds=aec[:3]), "3 CCSDS records for 5 rows"),
+                     (dict(ccsds=aec, cpx=recs), "cpx does not go with ccsds"),
+                     (dict(cpx_missing=missing), "cpx_missing goes with cpx"),
+                     (dict(ccsds=aec, cpx_missing=missing), "cpx_missing goes with cpx"),
+                     (dict(cpx=recs, cpx_missing=missing[:4]), "4 missing-value-management values for 5 rows"),
+                     (dict(coded=coded, cpx=recs), "coded stands in place of"),
+                     (dict(coded=coded[:4]), "coded stands in place of")):
+        with pytest.raises(ValueError, match=text):
+            _grib.CodedRows.of(5, **kw)
+    assert _grib.CodedRows.of(5, coded=coded) is coded

@@ -263,19 +263,18 @@ def test_plan_chunks_budgets_a_row_with_missing_values_by_the_stated_cost():
     missing = np.array([0, 1, 2, 0], dtype=np.uint8)
     n_dst = 100
     plain = 1000 + 12 * n + 16 * ng + 256 + 8 * n_dst
-    chunks = list(_grib.plan_chunks(4000, rows, None, _grib.CPX, recs, n, n_dst, 0, plain + 2 * (plain + _grib.cpx_missing_cost(n)), 0,
-                                    missing))
+    coded = _grib.CodedRows.of(4, cpx=recs, cpx_missing=missing)
+    chunks = list(_grib.plan_chunks(4000, rows, None, coded, n, n_dst, 0, plain + 2 * (plain + _grib.cpx_missing_cost(n)), 0))
     assert [(c.r0, c.r1) for c in chunks] == [(0, 3), (3, 4)] and chunks[0].missing.tolist() == [0, 1, 2]
     assert chunks[0].coded_bytes == 3 * 4 * n + 2 * 256 and chunks[1].coded_bytes == 4 * n
-    one_less = list(_grib.plan_chunks(4000, rows, None, _grib.CPX, recs, n, n_dst, 0, plain + 2 * (plain + _grib.cpx_missing_cost(n)) - 1,
-                                      0, missing))
+    one_less = list(_grib.plan_chunks(4000, rows, None, coded, n, n_dst, 0, plain + 2 * (plain + _grib.cpx_missing_cost(n)) - 1, 0))
     assert [(c.r0, c.r1) for c in one_less] == [(0, 2), (2, 4)]
-    without = list(_grib.plan_chunks(4000, rows, None, _grib.CPX, recs, n, n_dst, 0, 3 * plain, 0))
+    without = list(_grib.plan_chunks(4000, rows, None, _grib.CodedRows.of(4, cpx=recs), n, n_dst, 0, 3 * plain, 0))
     assert [(c.r0, c.r1) for c in without] == [(0, 3), (3, 4)] and without[0].missing is None
     bms = np.zeros(4, dtype=GRIB_BITMAP_DTYPE)
     bms["bitmap_off"], bms["n_values"] = 0, n
     with pytest.raises(ValueError, match="bitmap and missing values"):
-        list(_grib.plan_chunks(4000, rows, bms, _grib.CPX, recs, n, n_dst, 0, 1 << 30, 0, missing))
+        list(_grib.plan_chunks(4000, rows, bms, coded, n, n_dst, 0, 1 << 30, 0))
 
 
 # ------------------------------------------------------------------------------------------------ malformed input
