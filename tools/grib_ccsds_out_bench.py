@@ -15,153 +15,29 @@ simple-packed result.  One JSON line per block, printed and appended to profiles
   python tools/grib_ccsds_out_bench.py [--cfg4-rows 128] [--cfg2-rows 512] [--steps 5] [--warmup 1] [--only cfg2,cfg4]
                                        [--blocks kernel,host] [--widths 16,12]
 """
-import argparse
-import importlib.util
-import json
-import os
-import sys
-import time
+import functools
 
-import numpy as np
+import benchlib
+import coded_benches
+from smmregrid_amd.griblite import CCSDS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-_spec = importlib.util.spec_from_file_location("grib_ccsds_bench", os.path.join(ROOT, "tools", "grib_ccsds_bench.py"))
-_in = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(_in)
+bench_kernel = functools.partial(coded_benches.out_kernel, CCSDS)
+bench_host = functools.partial(coded_benches.out_host, CCSDS)
 
 
-def _median(v):
-    return float(np.median(np.asarray(v)))
-
-
-def source(S, rows):
-    """DISTINCT smooth 16-bit fields simple-packed in one buffer, `rows` records pointing at them in turn."""
-    from smmregrid_amd import GRIB_ROW_DTYPE
-    rng = np.random.default_rng(20261019)
-    blocks = [np.frombuffer(_in.smooth_field(S, i, rng).astype(">u2").tobytes(), dtype=np.uint8) for i in range(_in.DISTINCT)]
-    offs, pos = [], 116
-    for b in blocks:
-        offs.append(pos)
-        pos += b.size + 116
-    buf = np.zeros((pos + 3) // 4 * 4, dtype=np.uint8)
-    for o, b in zip(offs, blocks):
-        buf[o:o + b.size] = b
-    table = np.zeros(rows, dtype=GRIB_ROW_DTYPE)
-    for r in range(rows):
-        table[r] = (offs[r % _in.DISTINCT], float(np.float32(220.0 + r % _in.DISTINCT)), 2.0 ** -6, 1.0, 16, 0)
-    return buf, table
-
-
-def sample_rows(field, idx):
-    from smmregrid_amd import GribField
-    return GribField(field.buf, field.rows[idx], (len(idx), field.n_points), field.n_points, bitmaps=field.bitmaps[idx],
-                     ccsds=None if field.ccsds is None else field.ccsds[idx]).decode()
-
-
-def bench_kernel(op, name, rows, width, steps, warmup):
-    from smmregrid_amd import DeviceArray, GribEncode, GribField, grib_aec_pack, grib_pack, to_device
-    from smmregrid_amd.device import Event
-    buf, table = source(op.n_src, rows)
-    x = to_device(buf)
-    enc = GribEncode(width, 0, ccsds=True)
-    y = DeviceArray((rows, op.n_dst), np.float64)
-    op.apply_grib(x, table, y=y)
-    packed, rows_p, bms = grib_pack(y, enc)
-    want = enc.ccsds_records(rows, bms["n_values"], rows_p["nbits"])
-    bound = DeviceArray((max(enc.ccsds_bound(op.n_dst, rows), 4),), np.uint8)
-    coded, rows_c, recs = grib_aec_pack(packed, rows_p, want, out=bound)
-    idx = sorted({0, 1, rows - 1})
-    got = sample_rows(GribField(coded.to_host(), rows_c, (rows, op.n_dst), op.n_dst, bitmaps=bms, ccsds=recs), idx)
-    ref = sample_rows(GribField(packed.to_host(), rows_p, (rows, op.n_dst), op.n_dst, bitmaps=bms), idx)
-    if not np.array_equal(got.view(np.uint32), ref.view(np.uint32)):
-        raise SystemExit(f"{name}: the coded result decodes to other bits than the simple-packed one")
-    legs = {"gather": lambda: op.apply_grib(x, table, y=y), "grib_pack": lambda: grib_pack(y, enc, out=packed),
-            "grib_aec_pack": lambda: grib_aec_pack(packed, rows_p, want, out=bound)}
-    e0, e1 = Event(), Event()
-    times = {k: [] for k in legs}
-    for step in range(warmup + steps):
-        for leg, fn in legs.items():
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            if step >= warmup:
-                times[leg].append(e0.elapsed_ms(e1))
-    ms = {k: round(_median(v), 4) for k, v in times.items()}
-    simple = int(sum((op.n_dst * int(w) + 7) // 8 for w in rows_p["nbits"]))
-    return {"block": "kernel", "op": name, "rows": rows, "nbits": width, "n_src": op.n_src, "n_dst": op.n_dst, "steps": steps,
-            "ms": ms, "ms_min": {k: round(min(v), 4) for k, v in times.items()},
-            "aec_pack_over_grib_pack": round(ms["grib_aec_pack"] / ms["grib_pack"], 3),
-            "aec_pack_over_gather": round(ms["grib_aec_pack"] / ms["gather"], 3),
-            "coded_bytes": int(recs["byte_len"].sum()), "simple_bytes": simple, "bound_bytes": bound.nbytes,
-            "coded_over_simple_bytes": round(int(recs["byte_len"].sum()) / max(simple, 1), 4),
-            "samples_per_us": round(rows * op.n_dst / (ms["grib_aec_pack"] * 1e3), 1), "bits_equal_simple_packed": True}
-
-
-def bench_host(op, name, rows, width, steps, warmup):
-    from smmregrid_amd import GribEncode, _lib
-    buf, table = source(op.n_src, rows)
-    simple_enc, coded_enc = GribEncode(width, 0), GribEncode(width, 0, ccsds=True)
-    res = {}
-    legs = {"ccsds": lambda: op.apply_host_grib(buf, table, grib_out=coded_enc),
-            "simple": lambda: op.apply_host_grib(buf, table, grib_out=simple_enc)}
-    times, d2h, h2d = {k: [] for k in legs}, {}, {}
-    staged = int(sum((op.n_src * int(w) + 7) // 8 + (-((op.n_src * int(w) + 7) // 8)) % 4 for w in table["nbits"]))
-    for step in range(warmup + steps):
-        print(f"# {name} {width} bits: host step {step}", file=sys.stderr, flush=True)
-        for leg, fn in legs.items():
-            _lib.host_stats(reset=True)
-            t0 = time.perf_counter()
-            res[leg] = fn()
-            dt = (time.perf_counter() - t0) * 1e3
-            stats = _lib.host_stats(reset=True)
-            d2h[leg] = int(stats["d2h_bytes"]) if leg == "simple" else int(res[leg].buf.size)
-            h2d[leg] = int(stats["h2d_bytes"]) if leg == "simple" else staged      # every row's bytes are staged and shipped
-            if step >= warmup:
-                times[leg].append(dt)
-        if step == 0:
-            idx = sorted({0, 1, rows - 1})
-            if not np.array_equal(sample_rows(res["ccsds"], idx).view(np.uint32), sample_rows(res["simple"], idx).view(np.uint32)):
-                raise SystemExit(f"{name}: the coded result decodes to other bits than the simple-packed one")
-    ms = {k: round(_median(v), 3) for k, v in times.items()}
-    return {"block": "host_to_host", "op": name, "rows": rows, "nbits": width, "n_src": op.n_src, "n_dst": op.n_dst,
-            "steps": steps, "ms": ms, "ms_min": {k: round(min(v), 3) for k, v in times.items()},
-            "h2d_bytes": h2d, "d2h_bytes": d2h, "float64_bytes": rows * op.n_dst * 8,
-            "ccsds_over_simple_ms": round(ms["ccsds"] / ms["simple"], 3),
-            "ccsds_over_simple_d2h_bytes": round(d2h["ccsds"] / max(d2h["simple"], 1), 4), "bits_equal_simple_packed": True}
+def parser():
+    ap = benchlib.parser(__doc__, steps=5, warmup=1, only="cfg2,cfg4", blocks="kernel,host", out="grib_ccsds_out_bench.jsonl")
+    ap.add_argument("--widths", default="16,12")
+    return ap
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--cfg4-rows", type=int, default=128)
-    ap.add_argument("--cfg2-rows", type=int, default=512)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--only", default="cfg2,cfg4")
-    ap.add_argument("--blocks", default="kernel,host")
-    ap.add_argument("--widths", default="16,12")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grib_ccsds_out_bench.jsonl"))
-    args = ap.parse_args()
-    if args.steps < 5:
-        ap.error("medians need at least 5 timings")
-    from smmregrid_amd import SparseOperator, gridgen
-    cases = {"cfg4": ("n1280", "hp1024", args.cfg4_rows), "cfg2": ("r1440x721", "r360x180", args.cfg2_rows)}
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    for name in [c.strip() for c in args.only.split(",")]:
-        sgrid, tgrid, rows = cases[name]
-        w = gridgen.generate_weights(sgrid, tgrid, method="bil")
-        op = SparseOperator(w.sizes["src_grid_size"], w.sizes["dst_grid_size"], w["src_address"].values,
-                            w["dst_address"].values, w["remap_matrix"].values, device=0)
-        print(f"# {name}: operator built (S = {op.n_src}, D = {op.n_dst}), {rows} rows", file=sys.stderr, flush=True)
-        for block in [b.strip() for b in args.blocks.split(",")]:
+    args = benchlib.parse(parser(), why="medians need at least 5 timings")
+    for name, op, rows in benchlib.operators(args):
+        for block in benchlib.split(args.blocks):
             for width in [int(v) for v in args.widths.split(",")]:
-                res = (bench_kernel if block == "kernel" else bench_host)(op, name, rows, width, args.steps, args.warmup)
-                print(json.dumps(res), flush=True)
-                with open(args.out, "a") as f:
-                    f.write(json.dumps(res) + "\n")
-        op.close()
+                benchlib.emit((bench_kernel if block == "kernel" else bench_host)(op, name, rows, width, args.steps, args.warmup),
+                              args.out)
 
 
 if __name__ == "__main__":

@@ -14,19 +14,12 @@ is timed.  One JSON line per block, printed and appended to profiles/grib_out_be
 
   python tools/grib_out_bench.py [--cfg4-rows 128] [--cfg2-rows 512] [--steps 7] [--warmup 2] [--only cfg2,cfg4] [--blocks host,kernel]
 """
-import argparse
-import json
-import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from tools.grib_bench import _median, make_streams      # noqa: E402
+import benchlib
+from bench_inputs import make_streams, padded_upload
 
 
 def check_row0(name, what, field, y_row, enc):
@@ -50,96 +43,59 @@ def bench_host(op, name, rows, steps, warmup):
         outs[w] = (enc, np.empty(enc.layout(D_, rows)[1], np.uint8))
         legs[f"f64_of_{w}"] = lambda w=w: op.apply_host_grib(streams[w][0], streams[w][1], out=y)
         legs[f"grib_out{w}"] = lambda w=w: op.apply_host_grib(streams[w][0], streams[w][1], grib_out=outs[w][0], out=outs[w][1])
-    times, stats = {k: [] for k in legs}, {}
-    for step in range(warmup + steps):
-        print(f"# {name}: host step {step}", file=sys.stderr, flush=True)
-        for leg, fn in legs.items():
-            _lib.host_stats(reset=True)
-            t0 = time.perf_counter()
-            res = fn()
-            dt = (time.perf_counter() - t0) * 1e3
-            stats[leg] = _lib.host_stats(reset=True)
-            if step >= warmup:
-                times[leg].append(dt)
-            if step == 0 and leg.startswith("grib_out"):      # the float64 leg of the same width ran just before
-                check_row0(name, leg, res, y[0], outs[int(leg[8:])][0])
+
+    def check(leg, res):
+        if leg.startswith("grib_out"):      # the float64 leg of the same width ran just before
+            check_row0(name, leg, res, y[0], outs[int(leg[8:])][0])
+    times, stats = benchlib.time_wall(legs, steps, warmup, host_stats=_lib.host_stats, check=check,
+                                      announce=f"# {name}: host step {{}}")
     out = {"block": "host_to_host", "op": name, "rows": rows, "n_src": S, "n_dst": D_, "steps": steps,
-           "ms": {k: round(_median(v), 3) for k, v in times.items()},
-           "ms_min": {k: round(min(v), 3) for k, v in times.items()},
-           "h2d_bytes": {k: int(s["h2d_bytes"]) for k, s in stats.items()},
-           "d2h_bytes": {k: int(s["d2h_bytes"]) for k, s in stats.items()},
-           "chunks": {k: int(s["chunks"]) for k, s in stats.items()}, "row0_equals_numpy_rule": True}
+           **benchlib.summary(times, 3),
+           "h2d_bytes": {k: int(s[-1]["h2d_bytes"]) for k, s in stats.items()},
+           "d2h_bytes": {k: int(s[-1]["d2h_bytes"]) for k, s in stats.items()},
+           "chunks": {k: int(s[-1]["chunks"]) for k, s in stats.items()}, "row0_equals_numpy_rule": True}
     for w in (16, 12):
         out[f"f64_over_grib_out{w}"] = round(out["ms"][f"f64_of_{w}"] / out["ms"][f"grib_out{w}"], 3)
     return out
 
 
 def bench_kernel(op, name, rows, steps, warmup):
-    from smmregrid_amd import DeviceArray, GribEncode, GribField, grib_pack, to_device
-    from smmregrid_amd.device import Event
+    from smmregrid_amd import DeviceArray, GribEncode, GribField, grib_pack
     S, D_ = op.n_src, op.n_dst
-    legs, check = {}, {}
+    legs, checks = {}, {}
     for w in (16, 12):
         buf, table, _, *_ = make_streams(S, rows, 0, widths=(w,))[w]
-        padded = np.zeros((buf.size + 3) // 4 * 4, np.uint8)
-        padded[:buf.size] = buf
-        dx, y = to_device(padded), DeviceArray((rows, D_), np.float64)
+        dx, y = padded_upload(buf), DeviceArray((rows, D_), np.float64)
         enc = GribEncode(w)
         out = DeviceArray((enc.layout(D_, rows)[1],), np.uint8)
         legs[f"gather{w}"] = lambda dx=dx, y=y, table=table, n=buf.size: op.apply_grib(dx, table, x_bytes=n, y=y)
         legs[f"pack{w}"] = lambda y=y, enc=enc, out=out: grib_pack(y, enc, out=out)
-        check[w] = (y, enc)
-        del buf, padded
-    e0, e1 = Event(), Event()
-    times = {k: [] for k in legs}
-    for step in range(warmup + steps):
-        for leg, fn in legs.items():
-            e0.record()
-            res = fn()
-            e1.record()
-            e1.synchronize()
-            if step >= warmup:
-                times[leg].append(e0.elapsed_ms(e1))
-            if step == 0 and leg.startswith("pack"):
-                y, enc = check[int(leg[4:])]
-                packed, prow, pbm = res
-                n0 = enc.layout(D_, 1)[1]
-                head = DeviceArray((n0,), np.uint8, ptr=packed.ptr, base=packed).to_host()
-                check_row0(name, leg, GribField(head, prow[:1], (1, D_), D_, bitmaps=pbm[:1]), y.rows(0, 1).to_host()[0], enc)
-    ms = {k: round(_median(v), 4) for k, v in times.items()}
-    out = {"block": "kernel", "op": name, "rows": rows, "n_src": S, "n_dst": D_, "steps": steps, "ms": ms,
-           "ms_min": {k: round(min(v), 4) for k, v in times.items()}, "row0_equals_numpy_rule": True}
+        checks[w] = (y, enc)
+        del buf
+
+    def check(leg, res):
+        if leg.startswith("pack"):
+            y, enc = checks[int(leg[4:])]
+            packed, prow, pbm = res
+            n0 = enc.layout(D_, 1)[1]
+            head = DeviceArray((n0,), np.uint8, ptr=packed.ptr, base=packed).to_host()
+            check_row0(name, leg, GribField(head, prow[:1], (1, D_), D_, bitmaps=pbm[:1]), y.rows(0, 1).to_host()[0], enc)
+    out = {"block": "kernel", "op": name, "rows": rows, "n_src": S, "n_dst": D_, "steps": steps,
+           **benchlib.summary(benchlib.time_events(legs, steps, warmup, check=check), 4), "row0_equals_numpy_rule": True}
+    ms = out["ms"]
     out["pack_over_gather"] = {str(w): round(ms[f"pack{w}"] / ms[f"gather{w}"], 3) for w in (16, 12)}
     return out
 
 
+def parser():
+    return benchlib.parser(__doc__, steps=7, warmup=2, only="cfg2,cfg4", blocks="host,kernel", out="grib_out_bench.jsonl")
+
+
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--cfg4-rows", type=int, default=128)
-    ap.add_argument("--cfg2-rows", type=int, default=512)
-    ap.add_argument("--steps", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", default="cfg2,cfg4")
-    ap.add_argument("--blocks", default="host,kernel")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grib_out_bench.jsonl"))
-    args = ap.parse_args()
-    if args.steps < 5:
-        ap.error("median and best need at least 5 timings")
-    from smmregrid_amd import SparseOperator, gridgen
-    cases = {"cfg4": ("n1280", "hp1024", args.cfg4_rows), "cfg2": ("r1440x721", "r360x180", args.cfg2_rows)}
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    for name in [c.strip() for c in args.only.split(",")]:
-        sgrid, tgrid, rows = cases[name]
-        w = gridgen.generate_weights(sgrid, tgrid, method="bil")
-        op = SparseOperator(w.sizes["src_grid_size"], w.sizes["dst_grid_size"], w["src_address"].values,
-                            w["dst_address"].values, w["remap_matrix"].values, device=0)
-        print(f"# {name}: operator built (S = {op.n_src}, D = {op.n_dst}), {rows} rows", file=sys.stderr, flush=True)
-        for block in [b.strip() for b in args.blocks.split(",")]:
-            res = (bench_host if block == "host" else bench_kernel)(op, name, rows, args.steps, args.warmup)
-            print(json.dumps(res), flush=True)
-            with open(args.out, "a") as f:
-                f.write(json.dumps(res) + "\n")
-        op.close()
+    args = benchlib.parse(parser())
+    for name, op, rows in benchlib.operators(args):
+        for block in benchlib.split(args.blocks):
+            benchlib.emit((bench_host if block == "host" else bench_kernel)(op, name, rows, args.steps, args.warmup), args.out)
 
 
 if __name__ == "__main__":

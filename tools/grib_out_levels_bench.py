@@ -17,21 +17,12 @@ to profiles/grib_out_levels_bench.jsonl.
 
   python tools/grib_out_levels_bench.py [--levels 16] [--nsteps 32] [--steps 8] [--warmup 2]
 """
-import argparse
-import json
-import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from tools.grib_bench import _median                                 # noqa: E402
-from tools.grib_levels_bench import STAGES, make_level_streams       # noqa: E402
-from tools.packed_levels_bench import build_group                    # noqa: E402
+import benchlib
+from bench_inputs import make_level_streams
 
 
 def check_outer(what, field, y, enc_w, o, n_lev):
@@ -79,31 +70,14 @@ def bench(grp, masks, ml, n_steps, steps, warmup):
         field = legs[f"grib_out{w}"]()
         for o in (0, n_steps - 1):
             check_outer(f"grib_out{w}", field, y, w, o, n_lev)
-    names = list(legs)
-    times = {k: {"fwd": [], "rev": []} for k in legs}
-    stats = {k: [] for k in legs}
-    for step in range(warmup + steps):
-        print(f"# step {step}", file=sys.stderr, flush=True)
-        order = "fwd" if step % 2 == 0 else "rev"
-        for leg in (names if order == "fwd" else names[::-1]):
-            _lib.host_stats(reset=True)
-            t0 = time.perf_counter()
-            legs[leg]()
-            dt = (time.perf_counter() - t0) * 1e3
-            st = _lib.host_stats(reset=True)
-            if step >= warmup:
-                times[leg][order].append(dt)
-                stats[leg].append(st)
-    both = {k: v["fwd"] + v["rev"] for k, v in times.items()}
+    times, stats = benchlib.time_wall(legs, steps, warmup, host_stats=_lib.host_stats, both_orders=True, announce="# step {}")
+    fwd, rev = benchlib.by_order(times, warmup)
     res = {"block": "host_to_host", "levels": int(n_lev), "nsteps": int(n_steps), "n_src": int(S), "n_dst": int(D),
-           "steps": steps, "present_share": round(float((masks != 0).mean()), 4),
-           "ms": {k: round(_median(v), 3) for k, v in both.items()},
-           "ms_min": {k: round(min(v), 3) for k, v in both.items()},
-           "ms_fwd": {k: round(_median(v["fwd"]), 3) for k, v in times.items()},
-           "ms_rev": {k: round(_median(v["rev"]), 3) for k, v in times.items()},
+           "steps": steps, "present_share": round(float((masks != 0).mean()), 4), **benchlib.summary(times, 3),
+           "ms_fwd": benchlib.summary(fwd, 3)["ms"], "ms_rev": benchlib.summary(rev, 3)["ms"],
            "h2d_bytes": {k: int(s[0]["h2d_bytes"]) for k, s in stats.items()},
            "d2h_bytes": {k: int(s[0]["d2h_bytes"]) for k, s in stats.items()},
-           "stages": {k: {n: round(_median([st[n] for st in s]), 3) for n in STAGES} for k, s in stats.items()},
+           "stages": {k: benchlib.stage_split(s) for k, s in stats.items()},
            "first_and_last_outer_equal_numpy_rule": True}
     for w in (16, 12):
         res[f"f64_over_grib_out{w}"] = round(res["ms"][f"f64_of_{w}"] / res["ms"][f"grib_out{w}"], 3)   # < 1: nothing is won
@@ -111,23 +85,20 @@ def bench(grp, masks, ml, n_steps, steps, warmup):
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+def parser():
+    ap = benchlib.parser(__doc__, steps=8, warmup=2, out="grib_out_levels_bench.jsonl", cfg_rows=False,
+                         steps_help="timed repetitions (half in either order)")
     ap.add_argument("--levels", type=int, default=16)
     ap.add_argument("--nsteps", type=int, default=32, help="time steps of the variable")
-    ap.add_argument("--steps", type=int, default=8, help="timed repetitions (half in either order)")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grib_out_levels_bench.jsonl"))
-    args = ap.parse_args()
-    if args.steps < 8 or args.steps % 2 or args.warmup % 2:
-        ap.error("an even number of at least 8 timed steps after an even warm-up: both orders get the same share")
-    grp, masks, ml = build_group(args.levels)
+    return ap
+
+
+def main():
+    args = benchlib.parse(parser(), least=8, both_orders=True,
+                          why="an even number of at least 8 timed steps after an even warm-up: both orders get the same share")
+    grp, masks, ml = benchlib.build_group(args.levels)
     print(f"# group built: {args.levels} levels, S = {grp.n_src}, D = {grp.n_dst}", file=sys.stderr, flush=True)
-    res = bench(grp, masks, ml, args.nsteps, args.steps, args.warmup)
-    print(json.dumps(res), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "a") as f:
-        f.write(json.dumps(res) + "\n")
+    benchlib.emit(bench(grp, masks, ml, args.nsteps, args.steps, args.warmup), args.out)
 
 
 if __name__ == "__main__":

@@ -25,83 +25,29 @@ printed and appended to profiles/grib_skipna_bench.jsonl.
   python tools/grib_skipna_bench.py [--cfg4-rows 128] [--cfg2-rows 512] [--levels 16] [--nsteps 32] [--steps 8] [--warmup 2]
                                     [--only cfg2,cfg4,levels] [--blocks kernel,host] [--widths 16] [--plain-only] [--tag branch]
 """
-import argparse
-import json
-import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from tools.grib_bench import _median                                                  # noqa: E402
-from tools.grib_bitmap_bench import MISSING, make_bitmap_streams, same, time_decode   # noqa: E402
-from tools.grib_levels_bench import make_level_streams                                # noqa: E402
-from tools.grib_levels_bench import time_decode as time_level_decode                  # noqa: E402
-from tools.packed_levels_bench import build_group                                      # noqa: E402
-
-
-def padded(buf):
-    out = np.zeros((buf.size + 3) // 4 * 4, np.uint8)
-    out[:buf.size] = buf
-    return out
-
-
-def run_legs(legs, steps, warmup, timer, after_first=None):
-    """legs in order on even steps, reversed on odd ones; timer(fn) -> ms"""
-    names = list(legs)
-    times = {k: [] for k in legs}
-    for step in range(warmup + steps):
-        for leg in (names if step % 2 == 0 else names[::-1]):
-            dt = timer(legs[leg])
-            if step >= warmup:
-                times[leg].append(dt)
-        if step == 0 and after_first:
-            after_first()
-    return times
-
-
-def event_timer():
-    from smmregrid_amd.device import Event
-    e0, e1 = Event(), Event()
-
-    def timer(fn):
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_ms(e1)
-    return timer
-
-
-def wall_timer(fn):
-    t0 = time.perf_counter()
-    fn()
-    return (time.perf_counter() - t0) * 1e3
+import benchlib
+from bench_inputs import MISSING, make_bitmap_streams, make_level_streams, padded_upload, thinned
+from benchlib import same_bits as same
 
 
 def summary(times, digits):
-    return ({k: round(_median(v), digits) for k, v in times.items()}, {k: round(min(v), digits) for k, v in times.items()})
-
-
-def thinned(masks, seed=20261019):
-    """the levels' bitmaps: each level's source mask with a further MISSING of the cells cleared"""
-    rng = np.random.default_rng(seed)
-    return np.stack([(m != 0) & (rng.random(m.size) >= MISSING) for m in masks]).astype(masks.dtype)
+    s = benchlib.summary(times, digits)
+    return s["ms"], s["ms_min"]
 
 
 def bench_kernel(op, name, rows, args):
-    from smmregrid_amd import DeviceArray, SparseOperator, _lib, to_device
+    from smmregrid_amd import DeviceArray, _lib, to_device
     S, D_ = op.n_src, op.n_dst
-    one = SparseOperator(S, 1, np.array([1]), np.array([1]), np.array([1.0]), device=0)     # the build, next to no gather
+    one = benchlib.one_link_operator(S)                                                   # the build, next to no gather
     y_one = DeviceArray((rows, 1), np.float64)
     legs, check = {}, []
     for nbits in args.widths:
         buf, table, bitmaps, field, _, _ = make_bitmap_streams(S, rows, widths=(nbits,))[nbits]
-        dx, n = to_device(padded(buf)), buf.size
+        dx, n = padded_upload(buf), buf.size
         y_bm = DeviceArray((rows, D_), np.float64)
         if not args.plain_only:
             y_na, y32 = DeviceArray((rows, D_), np.float64), DeviceArray((rows, D_), np.float64)
@@ -119,7 +65,7 @@ def bench_kernel(op, name, rows, args):
             if not same(y_na.to_host(), y32.to_host()):
                 raise SystemExit(f"{name}: smm_apply_grib_na at {nbits} bits differs from smm_apply SKIPNA on the decoded field")
 
-    ms, ms_min = summary(run_legs(legs, args.steps, args.warmup, event_timer(), bits), 4)
+    ms, ms_min = summary(benchlib.time_events(legs, args.steps, args.warmup, after_first=bits, both_orders=True), 4)
     one.close()
     res = {"block": "kernel", "op": name, "build": args.tag, "rows": rows, "n_src": S, "n_dst": D_, "steps": args.steps,
            "missing": MISSING, "ms": ms, "ms_min": ms_min, "bits_equal_parent": not args.plain_only or None}
@@ -147,14 +93,14 @@ def bench_host(op, name, rows, args):
         legs[f"f32_na_of_{nbits}"]()
         if not same(y_raw, y_f32):
             raise SystemExit(f"{name}: apply_host_grib(skipna=True) at {nbits} bits differs from the decoded road")
-    ms, ms_min = summary(run_legs(legs, args.steps, args.warmup, wall_timer), 3)
+    ms, ms_min = summary(benchlib.time_wall(legs, args.steps, args.warmup, both_orders=True), 3)
     res = {"block": "host_to_host", "op": name, "build": args.tag, "rows": rows, "n_src": S, "n_dst": D_, "steps": args.steps,
            "missing": MISSING, "ms": ms, "ms_min": ms_min, "bits_equal_parent": True}
     for nbits in args.widths:
         buf, _, _, _, rule, bm = streams[nbits]
-        dec = time_decode(buf, rule, bm, S, max(5, args.steps))
-        res[f"decode{nbits}_ms_per_row"] = {"median": round(_median(dec), 3), "min": round(min(dec), 3)}
-        parent = _median(dec) * rows + ms[f"f32_na_of_{nbits}"]
+        dec = benchlib.time_decode_rule(buf, rule, bm, S, max(5, args.steps))
+        res[f"decode{nbits}_ms_per_row"] = benchlib.median_and_min(dec)
+        parent = benchlib.median(dec) * rows + ms[f"f32_na_of_{nbits}"]
         res[f"parent_road{nbits}_ms"] = round(parent, 1)          # decode of every row (one thread) + apply_host(skipna=True)
         res[f"parent_over_grib_na{nbits}"] = round(parent / ms[f"grib_na{nbits}"], 2)
         res[f"apply_host_f32_na_over_grib_na{nbits}"] = round(ms[f"f32_na_of_{nbits}"] / ms[f"grib_na{nbits}"], 3)   # < 1: raw loses
@@ -166,7 +112,7 @@ def bench_levels(grp, masks, ml, block, args):
     n_lev, S = masks.shape
     lev = np.arange(n_lev, dtype=np.int32)
     kw = dict(masked=True, remap_area_min=0.5)
-    legs, streams, checks = {}, {}, []
+    legs, streams = {}, {}
     for nbits in args.widths:
         buf, table, bitmaps, field, first = streams[nbits] = make_level_streams(thinned(masks), args.nsteps, nbits)
         if block == "host":
@@ -177,7 +123,7 @@ def bench_levels(grp, masks, ml, block, args):
             if not same(got, legs[f"f32_na_of_{nbits}"]()):
                 raise SystemExit(f"levels: apply_host_grib(skipna=True) at {nbits} bits differs from the decoded road")
         else:
-            dx, n = to_device(padded(buf)), buf.size
+            dx, n = padded_upload(buf), buf.size
             shape = (args.nsteps, 1, n_lev, grp.n_dst)
             y_bm = DeviceArray(shape, np.float64)
             if not args.plain_only:
@@ -191,14 +137,15 @@ def bench_levels(grp, masks, ml, block, args):
             legs[f"bm{nbits}"] = lambda dx=dx, t=table, b=bitmaps, n=n, y=y_bm: grp.apply_grib(dx, t, lev, ml, bitmaps=b, y=y,
                                                                                             x_bytes=n, **kw)
     host = block == "host"
-    ms, ms_min = summary(run_legs(legs, args.steps, args.warmup, wall_timer if host else event_timer()), 3 if host else 4)
+    timer = benchlib.time_wall if host else benchlib.time_events
+    ms, ms_min = summary(timer(legs, args.steps, args.warmup, both_orders=True), 3 if host else 4)
     res = {"block": "host_to_host" if host else "kernel", "op": "levels", "build": args.tag, "levels": int(n_lev),
            "nsteps": int(args.nsteps), "n_src": int(S), "n_dst": int(grp.n_dst), "steps": args.steps, "missing": MISSING,
            "present_share": round(float((thinned(masks) != 0).mean()), 4), "ms": ms, "ms_min": ms_min,
            "bits_equal_parent": not args.plain_only or None}
     for nbits in args.widths:
         if host:
-            dec = time_level_decode(streams[nbits][0], streams[nbits][4], S, max(5, args.steps)) * args.nsteps
+            dec = benchlib.time_level_decode(streams[nbits][0], streams[nbits][4], S, max(5, args.steps)) * args.nsteps
             res[f"decode{nbits}_ms"] = round(dec, 1)
             res[f"parent_road{nbits}_ms"] = round(dec + ms[f"f32_na_of_{nbits}"], 1)
             res[f"parent_over_grib_na{nbits}"] = round((dec + ms[f"f32_na_of_{nbits}"]) / ms[f"grib_na{nbits}"], 2)
@@ -209,50 +156,33 @@ def bench_levels(grp, masks, ml, block, args):
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--cfg4-rows", type=int, default=128)
-    ap.add_argument("--cfg2-rows", type=int, default=512)
+def parser():
+    ap = benchlib.parser(__doc__, steps=8, warmup=2, only="cfg2,cfg4,levels", blocks="kernel,host", out="grib_skipna_bench.jsonl",
+                         steps_help="timed repetitions (half in either order)")
     ap.add_argument("--levels", type=int, default=16)
     ap.add_argument("--nsteps", type=int, default=32, help="time steps of the levels variable")
-    ap.add_argument("--steps", type=int, default=8, help="timed repetitions (half in either order)")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", default="cfg2,cfg4,levels")
-    ap.add_argument("--blocks", default="kernel,host")
     ap.add_argument("--widths", default="16")
     ap.add_argument("--plain-only", action="store_true")
     ap.add_argument("--tag", default="branch")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grib_skipna_bench.jsonl"))
-    args = ap.parse_args()
-    if args.steps < 6 or args.steps % 2 or args.warmup % 2:
-        ap.error("an even number of at least 6 timed steps after an even warm-up: both orders get the same share")
+    return ap
+
+
+def main():
+    args = benchlib.parse(parser(), least=6, both_orders=True,
+                          why="an even number of at least 6 timed steps after an even warm-up: both orders get the same share")
     args.widths = [int(w) for w in args.widths.split(",")]
-    blocks = ["kernel"] if args.plain_only else [b.strip() for b in args.blocks.split(",")]
-    from smmregrid_amd import SparseOperator, gridgen
-    cases = {"cfg4": ("n1280", "hp1024", args.cfg4_rows), "cfg2": ("r1440x721", "r360x180", args.cfg2_rows)}
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-
-    def record(res):
-        print(json.dumps(res), flush=True)
-        with open(args.out, "a") as f:
-            f.write(json.dumps(res) + "\n")
-
-    for name in [c.strip() for c in args.only.split(",")]:
-        if name == "levels":
-            grp, masks, ml = build_group(args.levels)
-            print(f"# levels: group built, S = {grp.n_src}, D = {grp.n_dst}", file=sys.stderr, flush=True)
-            for block in blocks:
-                record(bench_levels(grp, masks, ml, block, args))
-            grp.close()
-            continue
-        sgrid, tgrid, rows = cases[name]
-        w = gridgen.generate_weights(sgrid, tgrid, method="bil")
-        op = SparseOperator(w.sizes["src_grid_size"], w.sizes["dst_grid_size"], w["src_address"].values,
-                            w["dst_address"].values, w["remap_matrix"].values, device=0)
-        print(f"# {name}: operator built (S = {op.n_src}, D = {op.n_dst}), {rows} rows", file=sys.stderr, flush=True)
+    blocks = ["kernel"] if args.plain_only else benchlib.split(args.blocks)
+    cases = benchlib.split(args.only)
+    args.only = ",".join(c for c in cases if c != "levels")
+    for name, op, rows in benchlib.operators(args) if args.only else ():
         for block in blocks:
-            record((bench_host if block == "host" else bench_kernel)(op, name, rows, args))
-        op.close()
+            benchlib.emit((bench_host if block == "host" else bench_kernel)(op, name, rows, args), args.out)
+    if "levels" in cases:                                   # the operators first, the group behind them
+        grp, masks, ml = benchlib.build_group(args.levels)
+        print(f"# levels: group built, S = {grp.n_src}, D = {grp.n_dst}", file=sys.stderr, flush=True)
+        for block in blocks:
+            benchlib.emit(bench_levels(grp, masks, ml, block, args), args.out)
+        grp.close()
 
 
 if __name__ == "__main__":

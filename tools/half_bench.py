@@ -11,59 +11,24 @@ One JSON line per block, printed and appended to profiles/half_bench.jsonl.
 
   python tools/half_bench.py [--rows 512] [--levels 16] [--nsteps 32] [--steps 9] [--warmup 2] [--only kernel,group,host]
 """
-import argparse
-import json
-import os
-import sys
-import time
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import benchlib
+from bench_inputs import half_fields
 
 PAIRS = ("f32->f32", "f16->f16", "bf16->bf16")
 
 
-def _median(v):
-    return float(np.median(np.asarray(v)))
-
-
-def _fields(shape, seed=20261018):
-    """The same values as float32, float16 and bfloat16 (16 distinct rows, tiled along the first axis)."""
-    from smmregrid_amd import to_bfloat16
-    rng = np.random.default_rng(seed)
-    blk = (250.0 + 30.0 * rng.standard_normal((16,) + tuple(shape[1:]))).astype(np.float32)
-    x32 = np.ascontiguousarray(np.tile(blk, ((shape[0] + 15) // 16,) + (1,) * (len(shape) - 1))[:shape[0]])
-    return {"f32": x32, "f16": x32.astype(np.float16), "bf16": to_bfloat16(x32)}
-
-
-def _time_device(legs, steps, warmup):
-    from smmregrid_amd.device import Event
-    e0, e1 = Event(), Event()
-    times = {k: [] for k in legs}
-    for step in range(warmup + steps):
-        for leg, fn in legs.items():
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            if step >= warmup:
-                times[leg].append(e0.elapsed_ms(e1))
-    return times
-
-
 def _result(block, name, rows, steps, times, digits=4):
-    ms = {k: round(_median(v), digits) for k, v in times.items()}
-    return {"block": block, "op": name, "rows": int(rows), "steps": steps, "ms": ms,
-            "ms_min": {k: round(min(v), digits) for k, v in times.items()},
-            "over_f32": {k: round(ms[k] / ms["f32->f32"], 3) for k in ms if k != "f32->f32"}}
+    res = {"block": block, "op": name, "rows": int(rows), "steps": steps, **benchlib.summary(times, digits)}
+    ms = res["ms"]
+    res["over_f32"] = {k: round(ms[k] / ms["f32->f32"], 3) for k in ms if k != "f32->f32"}
+    return res
 
 
 def bench_kernel(op, rows, steps, warmup):
     from smmregrid_amd import DeviceArray, _lib, to_device
-    xs = _fields((rows, op.n_src))
+    xs = half_fields((rows, op.n_src))
     legs = {}
     for pair in PAIRS:
         k = pair.split("->")[0]
@@ -75,15 +40,14 @@ def bench_kernel(op, rows, steps, warmup):
                 with _lib.tuning(sb_packed_y_rows=16):
                     op.apply_sb(dxt, y=y, out_dtype=y.dtype)
             legs[pair + "_td16"] = td16
-    return _result("kernel_c", "cfg2", rows, steps, _time_device(legs, steps, warmup))
+    return _result("kernel_c", "cfg2", rows, steps, benchlib.time_events(legs, steps, warmup))
 
 
 def bench_group(n_lev, n_steps, steps, warmup):
     from smmregrid_amd import DeviceArray, to_device
-    from tools.packed_levels_bench import build_group
-    grp, _, ml = build_group(n_lev)
+    grp, _, ml = benchlib.build_group(n_lev)
     lev = np.arange(n_lev, dtype=np.int32)
-    xs = _fields((n_steps, n_lev, grp.n_src))
+    xs = half_fields((n_steps, n_lev, grp.n_src))
     legs = {}
     for pair in PAIRS:
         k = pair.split("->")[0]
@@ -91,52 +55,38 @@ def bench_group(n_lev, n_steps, steps, warmup):
         y = DeviceArray((n_steps, n_lev, grp.n_dst), xs[k].dtype)
         legs[pair] = lambda dxt=dxt, y=y: grp.apply_sb(dxt, lev, ml, y=y, masked=True, remap_area_min=0.5,
                                                        out_dtype=y.dtype)
-    res = _result("group_kernel_c", "cfg3", n_steps, steps, _time_device(legs, steps, warmup))
+    res = _result("group_kernel_c", "cfg3", n_steps, steps, benchlib.time_events(legs, steps, warmup))
     res["levels"] = n_lev
     return res
 
 
 def bench_host(op, rows, steps, warmup):
     from smmregrid_amd import _lib
-    xs = _fields((rows, op.n_src))
+    xs = half_fields((rows, op.n_src))
     outs = {k: np.empty((rows, op.n_dst), v.dtype) for k, v in xs.items()}
-    times = {p: [] for p in PAIRS}
-    stats = {}
-    for step in range(warmup + steps):
-        for pair in PAIRS:
-            k = pair.split("->")[0]
-            _lib.host_stats(reset=True)
-            t0 = time.perf_counter()
-            op.apply_host(xs[k], out=outs[k], out_dtype=outs[k].dtype, half=True)
-            dt = (time.perf_counter() - t0) * 1e3
-            stats[pair] = _lib.host_stats(reset=True)
-            if step >= warmup:
-                times[pair].append(dt)
+    legs = {pair: (lambda k=pair.split("->")[0]: op.apply_host(xs[k], out=outs[k], out_dtype=outs[k].dtype, half=True))
+            for pair in PAIRS}
+    times, stats = benchlib.time_wall(legs, steps, warmup, host_stats=_lib.host_stats)
     res = _result("host", "cfg2", rows, steps, times, digits=3)
-    res["h2d_bytes"] = {p: int(s["h2d_bytes"]) for p, s in stats.items()}
-    res["d2h_bytes"] = {p: int(s["d2h_bytes"]) for p, s in stats.items()}
+    res["h2d_bytes"] = {p: int(s[-1]["h2d_bytes"]) for p, s in stats.items()}
+    res["d2h_bytes"] = {p: int(s[-1]["d2h_bytes"]) for p, s in stats.items()}
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+def parser():
+    ap = benchlib.parser(__doc__, steps=9, warmup=2, only="kernel,group,host", out="half_bench.jsonl", cfg_rows=False)
     ap.add_argument("--rows", type=int, default=512)
     ap.add_argument("--levels", type=int, default=16)
     ap.add_argument("--nsteps", type=int, default=32)
-    ap.add_argument("--steps", type=int, default=9)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", default="kernel,group,host")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "half_bench.jsonl"))
-    args = ap.parse_args()
-    if args.steps < 7:
-        ap.error("medians need at least 7 steps")
-    from smmregrid_amd import SparseOperator, gridgen
-    only = [b.strip() for b in args.only.split(",")]
+    return ap
+
+
+def main():
+    args = benchlib.parse(parser(), least=7, why="medians need at least 7 steps")
+    only = benchlib.split(args.only)
     lines = []
     if "kernel" in only or "host" in only:
-        w = gridgen.bilinear_weights("r1440x721", "r360x180")
-        op = SparseOperator(w.sizes["src_grid_size"], w.sizes["dst_grid_size"], w["src_address"].values,
-                            w["dst_address"].values, w["remap_matrix"].values, device=0)
+        op = benchlib.build_operator("cfg2")
         if "kernel" in only:
             lines.append(bench_kernel(op, args.rows, args.steps, args.warmup))
         if "host" in only:
@@ -144,10 +94,8 @@ def main():
         op.close()
     if "group" in only:
         lines.append(bench_group(args.levels, args.nsteps, args.steps, args.warmup))
-    with open(args.out, "a") as f:
-        for line in lines:
-            print(json.dumps(line), flush=True)
-            f.write(json.dumps(line) + "\n")
+    for line in lines:
+        benchlib.emit(line, args.out)
 
 
 if __name__ == "__main__":

@@ -18,46 +18,10 @@ Prints one JSON line per block.  --legs picks the host legs (f32,f64 run on a li
   python tools/packed_levels_bench.py [--levels 16] [--nsteps 32] [--full] [--steps 7] [--warmup 2]
                                       [--only host,kernel] [--legs i16,f32,f32b,f64,dec32,dec64]
 """
-import argparse
-import json
-import os
-import sys
-import time
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-NX, NY = 1440, 721
-STAGES = ("stage_in_ms", "h2d_ms", "kernel_ms", "d2h_ms", "copy_out_ms", "wait_ms", "chunks")
-
-
-def _median(v):
-    return float(np.median(np.asarray(v)))
-
-
-def build_group(n_lev):
-    from smmregrid_amd import OperatorGroup, gridgen
-    from smmregrid_amd.weights import compute_weights_matrix3d
-    masks = gridgen.synthetic_ocean_masks(NX, NY, n_lev)
-    w3 = gridgen.ConservativeLevels(gridgen.regular_grid(NX, NY), "r360x180").stack(masks, np.arange(n_lev, dtype=np.float64))
-    ops = compute_weights_matrix3d(w3, "lev", device=0)
-    imask = np.stack([op.mask_apply(masks[i]) for i, op in enumerate(ops)])
-    for i, op in enumerate(ops):
-        op.set_epilogue(imask[i], w3["dst_grid_frac"].values[i])
-    return OperatorGroup(ops), masks, (~(imask == 1).all(axis=1)).astype(np.uint8)
-
-
-def field(masks, n_steps, seed=20261016):
-    """(n_steps, n_lev, 1, S) int16: full range over the ocean, -32768 (_FillValue) where the level's mask is 0;
-    4 distinct time steps, tiled."""
-    rng = np.random.default_rng(seed)
-    n_lev, S = masks.shape
-    blk = rng.integers(-32767, 32768, size=(4, n_lev, 1, S)).astype(np.int16)
-    blk[:, masks[:, None, :] == 0] = -32768
-    return np.ascontiguousarray(np.tile(blk, ((n_steps + 3) // 4, 1, 1, 1))[:n_steps])
+import benchlib
+from bench_inputs import int16_levels
 
 
 def bench_host(grp, ml, q, cf, steps, warmup, want):
@@ -77,26 +41,12 @@ def bench_host(grp, ml, q, cf, steps, warmup, want):
         "dec64": lambda: cf64.decode(q),
     }
     legs = {k: v for k, v in legs.items() if k in want}
-    times = {k: [] for k in legs}
-    stats = {k: [] for k in legs if not k.startswith("dec")}
-    for step in range(warmup + steps):
-        for name, fn in legs.items():
-            _lib.host_stats(reset=True)
-            t0 = time.perf_counter()
-            fn()
-            dt = (time.perf_counter() - t0) * 1e3
-            st = _lib.host_stats(reset=True)
-            if step >= warmup:
-                times[name].append(dt)
-                if name in stats:
-                    stats[name].append(st)
+    times, stats = benchlib.time_wall(legs, steps, warmup, host_stats=_lib.host_stats)
     res = {"block": "host", "levels": int(n_lev), "nsteps": int(q.shape[0]), "cells": int(q.size), "steps": steps,
-           "ms": {k: round(_median(v), 3) for k, v in times.items()},
-           "ms_min": {k: round(min(v), 3) for k, v in times.items()},
-           "ms_max": {k: round(max(v), 3) for k, v in times.items()}}
-    for name, sts in stats.items():
-        res["stages_" + name] = {k: round(_median([s[k] for s in sts]), 3) for k in STAGES}
-        res["h2d_bytes_" + name] = int(sts[0]["h2d_bytes"])
+           **benchlib.summary(times, 3, maximum=True)}
+    for name in (k for k in legs if not k.startswith("dec")):
+        res["stages_" + name] = benchlib.stage_split(stats[name])
+        res["h2d_bytes_" + name] = int(stats[name][0]["h2d_bytes"])
     ms = res["ms"]
     if "i16" in ms and "f32" in ms:
         res["i16_over_f32"] = round(ms["i16"] / ms["f32"], 3)
@@ -106,18 +56,18 @@ def bench_host(grp, ml, q, cf, steps, warmup, want):
         # run-to-run spread of the float32 leg: its two medians against each other, and the range of all its samples
         both = times["f32"] + times["f32b"]
         res["f32_spread"] = {"median_ratio": round(ms["f32b"] / ms["f32"], 3),
-                             "range_over_median": round((max(both) - min(both)) / _median(both), 3)}
+                             "range_over_median": round((max(both) - min(both)) / benchlib.median(both), 3)}
     return res
 
 
 def bench_kernels(grp, ml, q, cf, steps, warmup):
     from smmregrid_amd import _lib, to_device
-    from smmregrid_amd.device import DeviceArray, Event
+    from smmregrid_amd.device import DeviceArray
     B, n_lev, _, S = q.shape
     lev = np.arange(n_lev, dtype=np.int32)
     x32 = cf.decode(q)
     dq, dx = to_device(q), to_device(x32)
-    sb = lambda a: to_device(np.ascontiguousarray(a.reshape(B, n_lev, S).transpose(1, 2, 0)), layout="sb")
+    sb = lambda a: to_device(np.ascontiguousarray(a.reshape(B, n_lev, S).transpose(1, 2, 0)), layout="sb")  # noqa: E731
     dqs, dxs = sb(q), sb(x32)
     del x32
     y = DeviceArray((B, 1, n_lev, grp.n_dst), np.float64)
@@ -130,49 +80,37 @@ def bench_kernels(grp, ml, q, cf, steps, warmup):
         "A_f32": lambda: grp.apply(dx, lev, ml, y=y, flags=_lib.APPLY_KERNEL_SELL, **kw),
         "tile_f32": lambda: grp.apply(dx, lev, ml, y=y, **kw),
     }
-    e0, e1 = Event(), Event()
-    times = {k: [] for k in legs}
-    for step in range(warmup + steps):
-        for name, fn in legs.items():
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            if step >= warmup:
-                times[name].append(e0.elapsed_ms(e1))
     res = {"block": "kernel", "levels": int(n_lev), "nsteps": int(B), "steps": steps,
-           "ms": {k: round(_median(v), 4) for k, v in times.items()},
-           "ms_min": {k: round(min(v), 4) for k, v in times.items()}}
+           **benchlib.summary(benchlib.time_events(legs, steps, warmup), 4)}
     res["C_i16_over_f32"] = round(res["ms"]["C_i16"] / res["ms"]["C_f32"], 3)
     res["A_i16_over_f32"] = round(res["ms"]["A_i16"] / res["ms"]["A_f32"], 3)
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+def parser():
+    ap = benchlib.parser(__doc__, steps=7, warmup=2, only="host,kernel", cfg_rows=False, steps_help="timed repetitions")
     ap.add_argument("--levels", type=int, default=16)
     ap.add_argument("--nsteps", type=int, default=32, help="time steps of the field")
     ap.add_argument("--full", action="store_true", help="75 levels x 120 time steps (BASELINE config 3; ~100 GB of host memory)")
-    ap.add_argument("--steps", type=int, default=7, help="timed repetitions")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", default="host,kernel")
     ap.add_argument("--legs", default="i16,f32,f32b,f64,dec32,dec64")
-    args = ap.parse_args()
-    if args.steps < 7:
-        ap.error("medians need at least 7 steps")
+    return ap
+
+
+def main():
+    args = benchlib.parse(parser(), least=7, why="medians need at least 7 steps")
     if args.full:
         args.levels, args.nsteps = 75, 120
     from smmregrid_amd import CFDecode
-    grp, masks, ml = build_group(args.levels)
+    grp, masks, ml = benchlib.build_group(args.levels)
     cf = CFDecode(1.0e-3, 20.0, (-32768,), np.float32)
-    q = field(masks, args.nsteps)
-    for block in args.only.split(","):
-        if block.strip() == "host":
-            res = bench_host(grp, ml, q, cf, args.steps, args.warmup, [s.strip() for s in args.legs.split(",")])
+    q = int16_levels(masks, args.nsteps)
+    for block in benchlib.split(args.only):
+        if block == "host":
+            res = bench_host(grp, ml, q, cf, args.steps, args.warmup, benchlib.split(args.legs))
         else:
             # the kernel block keeps the field on the device four times over: at most 32 time steps of it
             res = bench_kernels(grp, ml, q[:32], cf, args.steps, args.warmup)
-        print(json.dumps(res), flush=True)
+        benchlib.emit(res)
 
 
 if __name__ == "__main__":

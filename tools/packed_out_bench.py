@@ -15,29 +15,10 @@ Prints one JSON line per block and operator.
 
   python tools/packed_out_bench.py [--rows 512] [--steps 9] [--warmup 2] [--only host,kernel] [--ops cfg2,cfg5]
 """
-import argparse
-import json
-import os
-import sys
-import time
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-
-def _field(rows, n_src, seed=20261016):
-    """ERA5-like int16 rows: full range, -32768 as _FillValue on ~3 % of the cells."""
-    rng = np.random.default_rng(seed)
-    blk = rng.integers(-32767, 32768, size=(16, n_src)).astype(np.int16)
-    blk[rng.random(blk.shape) < 0.03] = -32768
-    return np.ascontiguousarray(np.tile(blk, ((rows + 15) // 16, 1))[:rows])
-
-
-def _median(v):
-    return float(np.median(np.asarray(v)))
+import benchlib
+from bench_inputs import int16_rows
 
 
 def bench_host(name, op, q, cf, enc, steps, warmup):
@@ -49,27 +30,12 @@ def bench_host(name, op, q, cf, enc, steps, warmup):
         "i16->f64": lambda: op.apply_host(q, out=out64, cf=cf),
         "i16->f64+enc": lambda: enc.encode(op.apply_host(q, out=out64, cf=cf)),
     }
-    times = {k: [] for k in legs}
-    stats = {k: [] for k in ("i16->i16", "i16->f64")}
-    for step in range(warmup + steps):
-        for leg, fn in legs.items():
-            _lib.host_stats(reset=True)
-            t0 = time.perf_counter()
-            fn()
-            dt = (time.perf_counter() - t0) * 1e3
-            st = _lib.host_stats(reset=True)
-            if step >= warmup:
-                times[leg].append(dt)
-                if leg in stats:
-                    stats[leg].append(st)
-    res = {"block": "host", "op": name, "rows": int(q.shape[0]), "steps": steps,
-           "ms": {k: round(_median(v), 3) for k, v in times.items()},
-           "ms_min": {k: round(min(v), 3) for k, v in times.items()}}
-    for leg, sts in stats.items():
-        res["stages_" + leg] = {k: round(_median([s[k] for s in sts]), 3)
-                                for k in ("stage_in_ms", "h2d_ms", "kernel_ms", "d2h_ms", "copy_out_ms", "wait_ms", "chunks")}
-        res["d2h_bytes_" + leg] = int(sts[0]["d2h_bytes"])
-        res["h2d_bytes_" + leg] = int(sts[0]["h2d_bytes"])
+    times, stats = benchlib.time_wall(legs, steps, warmup, host_stats=_lib.host_stats)
+    res = {"block": "host", "op": name, "rows": int(q.shape[0]), "steps": steps, **benchlib.summary(times, 3)}
+    for leg in ("i16->i16", "i16->f64"):
+        res["stages_" + leg] = benchlib.stage_split(stats[leg])
+        res["d2h_bytes_" + leg] = int(stats[leg][0]["d2h_bytes"])
+        res["h2d_bytes_" + leg] = int(stats[leg][0]["h2d_bytes"])
     res["i16_over_f64"] = round(res["ms"]["i16->i16"] / res["ms"]["i16->f64"], 3)
     res["i16_over_f64_enc"] = round(res["ms"]["i16->i16"] / res["ms"]["i16->f64+enc"], 3)
     return res
@@ -77,7 +43,7 @@ def bench_host(name, op, q, cf, enc, steps, warmup):
 
 def bench_kernels(name, op, q, cf, enc, steps, warmup):
     from smmregrid_amd import CFDecode, _lib, to_device
-    from smmregrid_amd.device import DeviceArray, Event
+    from smmregrid_amd.device import DeviceArray
     x64 = CFDecode(cf.scale_factor, cf.add_offset, cf.fill_values, np.float64).decode(q)
     B, D = q.shape[0], op.n_dst
     dq, dx = to_device(q), to_device(x64)
@@ -108,52 +74,34 @@ def bench_kernels(name, op, q, cf, enc, steps, warmup):
         "Csb_i16->i16": lambda: op.apply_sb(dqt, y=t16, cf=cf, cf_out=enc, keep_batch_fastest=True),
         "Csb_i16->i16_td16": rows16(lambda: op.apply_sb(dqt, y=t16, cf=cf, cf_out=enc, keep_batch_fastest=True)),
     }
-    e0, e1 = Event(), Event()
-    times = {k: [] for k in legs}
-    for step in range(warmup + steps):
-        for leg, fn in legs.items():
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            if step >= warmup:
-                times[leg].append(e0.elapsed_ms(e1))
     res = {"block": "kernel", "op": name, "rows": int(B), "steps": steps,
-           "ms": {k: round(_median(v), 4) for k, v in times.items()},
-           "ms_min": {k: round(min(v), 4) for k, v in times.items()}}
+           **benchlib.summary(benchlib.time_events(legs, steps, warmup), 4)}
     ms = res["ms"]
     res["packed_over_f64"] = {k: round(ms[k] / ms[k.replace("->i16", "->f64").replace("_td16", "")], 3)
                               for k in ms if "->i16" in k}
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+def parser():
+    ap = benchlib.parser(__doc__, steps=9, warmup=2, only="host,kernel", cfg_rows=False)
     ap.add_argument("--rows", type=int, default=512)
-    ap.add_argument("--steps", type=int, default=9)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", default="host,kernel")
     ap.add_argument("--ops", default="cfg2,cfg5")
-    args = ap.parse_args()
-    if args.steps < 7:
-        ap.error("medians need at least 7 steps")
-    from smmregrid_amd import CFDecode, CFEncode, SparseOperator, gridgen
+    return ap
+
+
+def main():
+    ap = parser()
+    args = benchlib.parse(ap, least=7, why="medians need at least 7 steps")
+    from smmregrid_amd import CFDecode, CFEncode
     cf = CFDecode(1.9e-3, 2.7e2, (-32768,), np.float32)
     enc = CFEncode(1.9e-3, 2.7e2, -32768, np.int16)
-    for name in args.ops.split(","):
-        name = name.strip()
-        if name == "cfg2":
-            w = gridgen.bilinear_weights("r1440x721", "r360x180")
-        elif name == "cfg5":
-            w = gridgen.conservative_weights("r1440x721", "r720x360")
-        else:
+    for name in benchlib.split(args.ops):
+        if name not in ("cfg2", "cfg5"):
             ap.error(f"unknown operator {name}")
-        op = SparseOperator(w.sizes["src_grid_size"], w.sizes["dst_grid_size"], w["src_address"].values,
-                            w["dst_address"].values, w["remap_matrix"].values, device=0)
-        q = _field(args.rows, op.n_src)
-        for block in args.only.split(","):
-            fn = {"host": bench_host, "kernel": bench_kernels}[block.strip()]
-            print(json.dumps(fn(name, op, q, cf, enc, args.steps, args.warmup)), flush=True)
+        op = benchlib.build_operator(name)
+        q = int16_rows(args.rows, op.n_src)
+        for block in benchlib.split(args.only):
+            benchlib.emit({"host": bench_host, "kernel": bench_kernels}[block](name, op, q, cf, enc, args.steps, args.warmup))
         op.close()
 
 

@@ -19,25 +19,12 @@ Prints one JSON line per block, with min and max of the samples beside the media
 
   python tools/packed_out_levels_bench.py [--levels 16] [--nsteps 32] [--steps 7] [--warmup 2] [--only host,kernel]
 """
-import argparse
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-from tools.packed_levels_bench import STAGES, _median, build_group, field      # noqa: E402  (the same group and field)
-
-
-def _summary(times, digits):
-    return {"ms": {k: round(_median(v), digits) for k, v in times.items()},
-            "ms_min": {k: round(min(v), digits) for k, v in times.items()},
-            "ms_max": {k: round(max(v), digits) for k, v in times.items()}}
+import benchlib
+from bench_inputs import int16_levels
 
 
 def bench_host(grp, ml, q, cf, enc, steps, warmup):
@@ -45,12 +32,12 @@ def bench_host(grp, ml, q, cf, enc, steps, warmup):
     n_lev = q.shape[1]
     lev = np.arange(n_lev, dtype=np.int32)
     kw = dict(masked=True, remap_area_min=0.5, cf=cf)
-    last = {}
+    regrid_ms = []
 
     def f64_then_encode():
         t0 = time.perf_counter()
         y = grp.apply_host(q, lev, ml, **kw)
-        last["regrid_ms"] = (time.perf_counter() - t0) * 1e3
+        regrid_ms.append((time.perf_counter() - t0) * 1e3)
         return enc.encode(y)
 
     legs = {
@@ -58,26 +45,13 @@ def bench_host(grp, ml, q, cf, enc, steps, warmup):
         "i16_f64": lambda: grp.apply_host(q, lev, ml, **kw),
         "i16_f64_enc": f64_then_encode,
     }
-    times = {k: [] for k in legs}
-    stats = {k: [] for k in legs}
-    encode_ms = []
-    for step in range(warmup + steps):
-        for name, fn in legs.items():
-            _lib.host_stats(reset=True)
-            t0 = time.perf_counter()
-            fn()
-            dt = (time.perf_counter() - t0) * 1e3
-            st = _lib.host_stats(reset=True)
-            if step >= warmup:
-                times[name].append(dt)
-                stats[name].append(st)
-                if name == "i16_f64_enc":
-                    encode_ms.append(dt - last["regrid_ms"])
+    times, stats = benchlib.time_wall(legs, steps, warmup, host_stats=_lib.host_stats)
+    encode_ms = [dt - regrid for dt, regrid in zip(times["i16_f64_enc"], regrid_ms[warmup:])]
     res = {"block": "host", "levels": int(n_lev), "nsteps": int(q.shape[0]), "cells": int(q.size), "steps": steps}
-    res.update(_summary(times, 3))
-    res["host_encode_ms"] = round(_median(encode_ms), 3)
+    res.update(benchlib.summary(times, 3, maximum=True))
+    res["host_encode_ms"] = round(benchlib.median(encode_ms), 3)
     for name, sts in stats.items():
-        res["stages_" + name] = {k: round(_median([s[k] for s in sts]), 3) for k in STAGES}
+        res["stages_" + name] = benchlib.stage_split(sts)
         res["h2d_bytes_" + name] = int(sts[0]["h2d_bytes"])
         res["d2h_bytes_" + name] = int(sts[0]["d2h_bytes"])
     ms = res["ms"]
@@ -88,7 +62,7 @@ def bench_host(grp, ml, q, cf, enc, steps, warmup):
 
 def bench_kernels(grp, ml, q, cf, enc, steps, warmup):
     from smmregrid_amd import _lib, to_device
-    from smmregrid_amd.device import DeviceArray, Event
+    from smmregrid_amd.device import DeviceArray
     B, n_lev, _, S = q.shape
     lev = np.arange(n_lev, dtype=np.int32)
     dq = to_device(q)
@@ -112,18 +86,8 @@ def bench_kernels(grp, ml, q, cf, enc, steps, warmup):
         "A_i16": lambda: grp.apply(dq, lev, ml, y=yq, cf_out=enc, **kw),
         "A_f64": lambda: grp.apply(dq, lev, ml, y=y, **kw),
     }
-    e0, e1 = Event(), Event()
-    times = {k: [] for k in legs}
-    for step in range(warmup + steps):
-        for name, fn in legs.items():
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            if step >= warmup:
-                times[name].append(e0.elapsed_ms(e1))
     res = {"block": "kernel", "levels": int(n_lev), "nsteps": int(B), "steps": steps}
-    res.update(_summary(times, 4))
+    res.update(benchlib.summary(benchlib.time_events(legs, steps, warmup), 4, maximum=True))
     ms = res["ms"]
     res["C_td64_over_f64"] = round(ms["C_i16_td64"] / ms["C_f64"], 3)
     res["C_td16_over_f64"] = round(ms["C_i16_td16"] / ms["C_f64"], 3)
@@ -131,28 +95,27 @@ def bench_kernels(grp, ml, q, cf, enc, steps, warmup):
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+def parser():
+    ap = benchlib.parser(__doc__, steps=7, warmup=2, only="host,kernel", cfg_rows=False, steps_help="timed repetitions")
     ap.add_argument("--levels", type=int, default=16)
     ap.add_argument("--nsteps", type=int, default=32, help="time steps of the field")
-    ap.add_argument("--steps", type=int, default=7, help="timed repetitions")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--only", default="host,kernel")
-    args = ap.parse_args()
-    if args.steps < 7:
-        ap.error("medians need at least 7 steps")
+    return ap
+
+
+def main():
+    args = benchlib.parse(parser(), least=7, why="medians need at least 7 steps")
     from smmregrid_amd import CFDecode, CFEncode
-    grp, masks, ml = build_group(args.levels)
+    grp, masks, ml = benchlib.build_group(args.levels)
     cf = CFDecode(1.0e-3, 20.0, (-32768,), np.float32)
     enc = CFEncode(1.0e-3, 20.0, -32768, np.int16)
-    q = field(masks, args.nsteps)
-    for block in args.only.split(","):
-        if block.strip() == "host":
+    q = int16_levels(masks, args.nsteps)
+    for block in benchlib.split(args.only):
+        if block == "host":
             res = bench_host(grp, ml, q, cf, enc, args.steps, args.warmup)
         else:
             # the kernel block keeps the field on the device twice and four results: at most 32 time steps of it
             res = bench_kernels(grp, ml, q[:32], cf, enc, args.steps, args.warmup)
-        print(json.dumps(res), flush=True)
+        benchlib.emit(res)
 
 
 if __name__ == "__main__":

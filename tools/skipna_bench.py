@@ -15,26 +15,13 @@ Kernel times for a profile: run under `rocprofv3 --kernel-trace --stats -- pytho
 """
 import argparse
 import ctypes
-import json
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import benchlib
+from bench_inputs import seeded_block
 
 BLOCK = 16   # seeded host rows, replicated over the batch on the device
-
-
-def _seeded_block(n_src, dtype, nan, seed=20261016):
-    rng = np.random.default_rng(seed)
-    blk = (250.0 + 30.0 * rng.standard_normal((BLOCK, n_src))).astype(dtype)
-    if nan:
-        blk[rng.random(blk.shape) < 0.03] = np.nan
-    return blk
 
 
 def _replicate(dev, blk):
@@ -53,21 +40,12 @@ def _replicate(dev, blk):
 
 def _time(run, steps, warmup):
     """run: {label: callable}; the labels alternate step by step.  Median device ms per label."""
-    from smmregrid_amd.device import Event, synchronize
-    e0, e1 = Event(), Event()
-    for _ in range(warmup):
-        for fn in run.values():
-            fn()
-    synchronize()
-    ms = {k: [] for k in run}
-    for _ in range(steps):
-        for k, fn in run.items():
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_ms(e1))
-    return {k: float(np.median(v)) for k, v in ms.items()}
+    return {k: benchlib.median(v) for k, v in benchlib.time_events(run, steps, warmup).items()}
+
+
+def _emit(workload, nan_frac, ms, nan, digits=4, **more):
+    benchlib.emit({"workload": workload, "nan_frac": nan_frac, **more, "plain_ms": round(ms[(nan, False)], digits),
+                   "skipna_ms": round(ms[(nan, True)], digits), "ratio": round(ms[(nan, True)] / ms[(nan, False)], 3)})
 
 
 def bench_2d(name, steps, warmup):
@@ -79,7 +57,7 @@ def bench_2d(name, steps, warmup):
     fields = {}
     for nan in (False, True):
         x = DeviceArray((p.n_batch, p.n_src), p.np_dt)
-        _replicate(x, _seeded_block(p.n_src, p.np_dt, nan))
+        _replicate(x, seeded_block(p.n_src, p.np_dt, nan, rows=BLOCK))
         fields[nan] = x
     run = {}
     for nan, x in fields.items():
@@ -89,9 +67,7 @@ def bench_2d(name, steps, warmup):
     li = p.op.launch_info(p.n_batch, p.np_dt)
     lk = p.op.launch_info(p.n_batch, p.np_dt, flags=_lib.APPLY_SKIPNA)
     for nan in (False, True):
-        print(json.dumps({"workload": name, "nan_frac": 0.03 if nan else 0.0, "kernel": [li["kernel"], lk["kernel"]],
-                          "plain_ms": round(ms[(nan, False)], 4), "skipna_ms": round(ms[(nan, True)], 4),
-                          "ratio": round(ms[(nan, True)] / ms[(nan, False)], 3)}), flush=True)
+        _emit(name, 0.03 if nan else 0.0, ms, nan, kernel=[li["kernel"], lk["kernel"]])
 
 
 def bench_levels(steps, warmup):
@@ -114,9 +90,7 @@ def bench_levels(steps, warmup):
                 x, p.level_index, p.masked_levels, y=y, masked=True, remap_area_min=0.5, n_batch=p.n_t, skipna=sk))
     ms = _time(run, steps, warmup)
     for nan in (False, True):
-        print(json.dumps({"workload": "cfg3sb", "nan_frac": "land + 0.03" if nan else "land", "kernel": "sb-group",
-                          "plain_ms": round(ms[(nan, False)], 4), "skipna_ms": round(ms[(nan, True)], 4),
-                          "ratio": round(ms[(nan, True)] / ms[(nan, False)], 3)}), flush=True)
+        _emit("cfg3sb", "land + 0.03" if nan else "land", ms, nan, kernel="sb-group")
 
 
 def bench_host(steps, warmup, rows=512):
@@ -124,29 +98,23 @@ def bench_host(steps, warmup, rows=512):
     from smmregrid_amd import pinned_empty
     p = bench.Problem2D("cfg2", 0, 0, batch=16)
     out = pinned_empty((rows, p.n_dst), np.float64)
-    res = {}
     for nan in (False, True):
-        blk = _seeded_block(p.n_src, np.float64, nan)
-        x = np.tile(blk, (rows // BLOCK, 1))
-        t = {False: [], True: []}
-        for i in range(warmup + steps):
-            for sk in (False, True):
-                t0 = time.perf_counter()
-                p.op.apply_host(x, out=out, remap_area_min=0.5, skipna=sk)
-                if i >= warmup:
-                    t[sk].append((time.perf_counter() - t0) * 1e3)
-        res[nan] = {k: float(np.median(v)) for k, v in t.items()}
-        print(json.dumps({"workload": f"host cfg2 x {rows} rows", "nan_frac": 0.03 if nan else 0.0,
-                          "plain_ms": round(res[nan][False], 3), "skipna_ms": round(res[nan][True], 3),
-                          "ratio": round(res[nan][True] / res[nan][False], 3)}), flush=True)
+        x = np.tile(seeded_block(p.n_src, np.float64, nan, rows=BLOCK), (rows // BLOCK, 1))
+        legs = {(nan, sk): (lambda sk=sk: p.op.apply_host(x, out=out, remap_area_min=0.5, skipna=sk)) for sk in (False, True)}
+        ms = {k: benchlib.median(v) for k, v in benchlib.time_wall(legs, steps, warmup).items()}
+        _emit(f"host cfg2 x {rows} rows", 0.03 if nan else 0.0, ms, nan, digits=3)
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only", default="cfg2,cfg5tile,cfg3sb,host")
-    a = ap.parse_args()
+    return ap
+
+
+def main():
+    a = parser().parse_args()
     names = a.only.split(",")
     for n in ("cfg2", "cfg5tile"):
         if n in names:
