@@ -1043,6 +1043,82 @@ int smm_group_apply_host_pk(smm_group_t g,
                             double remap_area_min, unsigned flags, int64_t chunk_outer,
                             const smm_cf_decode_t* cf, const smm_cf_encode_t* enc);
 
+/* ------------------------------------------- weight columns and source gradients (opt-in, beyond the reference)
+ *
+ * Bicubic weights (`cdo genbic`, num_wgts = 4) and second-order conservative weights (SCRIP-style, num_wgts = 3)
+ * carry more than the value weight in a row of remap_matrix: weights of the source field's gradients.  The reference
+ * applies column 0 alone (weights.py:33) and so does every entry above.  The entries below apply every column:
+ *
+ *     y[d] = epilogue( sum over the links of d:  w0 * fill(f[s]) + w1 * g1[s] + ... + w(K-1) * g(K-1)[s] )
+ *
+ * with g1 .. g(K-1) gradients of each batch row, computed on the device from the row itself.
+ *
+ * The gradient rule (stated in numpy by smmregrid_amd.gradients.GradientRule, which also makes the tables).  The source
+ * is a regular lon/lat grid of nx * ny cells, nx fastest; f is widened to float64 first.  A neighbour is ABSENT when it
+ * lies outside the grid (j beyond the first or last row; i beyond the ends unless `periodic`, which wraps) or its value
+ * is not finite; src_grid_imask is not consulted.  With i+ / i- the east / west and j+ / j- the next / previous row:
+ *     g_i [j,i] = ((f[j,i+] - f[j,i-]) * si[c * nx + i]) * ci[j]
+ *     g_j [j,i] =  (f[j+,i] - f[j-,i]) * sj[c * ny + j]
+ *     g_ij[j,i] = ((g_j[j,i+] - g_j[j,i-]) * si[c * nx + i]) * ci[j]      presence still judged on f
+ * an absent side is replaced by the cell itself; c = 0 with both sides present, 1 with the + side only, 2 with the -
+ * side only.  With both sides absent, or f[j,i] itself not finite, the gradient is exactly +0.0.  The tables are made
+ * on the host in float64 (1 / spacing, 1 / cos lat, signs): the device multiplies, it never divides, and keeps every
+ * multiply and subtract apart (no FMA).  A non-finite cell still enters the sum through column 0 as ever (the 1e20
+ * fill, then > 1e19 -> NaN), so the NaN footprint of a result is that of the column-0 result.  This is SCRIP's
+ * masked-neighbour convention as recalled, not pinned against a CDO run.
+ */
+enum { SMM_GRAD_I = 0, SMM_GRAD_J = 1, SMM_GRAD_IJ = 2 };   /* plane kinds */
+typedef struct smm_grad_plan* smm_grad_plan_t;              /* the tables of one source grid, resident in HBM */
+
+/* smm_operator_create_opt for links with n_cols weights each, 1..4: w is double[nnz * n_cols], rows as in remap_matrix.
+ * The sort by (dst, src), the tie-break and the sequential duplicate summing are applied to every column with the same
+ * permutation; SMM_CREATE_PRUNE_ZEROS drops a link only when all its columns are zero.  Column 0 of such an operator is
+ * exactly the operator smm_operator_create_opt builds from column 0, and every other entry works on it unchanged; the
+ * extra columns are kept as SELL slot planes beside it (padded slots +0.0) for smm_apply_cols. */
+int smm_operator_create_cols(int64_t n_src, int64_t n_dst, int64_t nnz, const int32_t* src_addr_1based,
+                             const int32_t* dst_addr_1based, const double* w, int n_cols, unsigned options,
+                             int device, smm_operator_t* out);
+int smm_operator_cols(smm_operator_t op, int* n_cols);
+/* every column of the canonical CSR for parity tests: val double[nnz * n_cols], link p's weights at val + p * n_cols, the
+ * links in the order of smm_operator_export_csr */
+int smm_operator_export_cols(smm_operator_t op, double* val);
+
+/* The gradient tables of one source grid: plane_kind int[n_planes] (SMM_GRAD_*) in the order of the weight columns
+ * 1.., si double[3 * nx], sj double[3 * ny], ci double[ny] (host arrays, copied).  SMM_ERR_INVALID, before any device is
+ * touched: nx or ny < 1, nx * ny beyond int32, n_planes outside 1..3, a null table, an unknown plane kind, an IJ plane
+ * without a J plane. */
+int smm_grad_plan_create(int64_t nx, int64_t ny, int periodic, int n_planes, const int* plane_kind, const double* si,
+                         const double* sj, const double* ci, int device, smm_grad_plan_t* out);
+int smm_grad_plan_destroy(smm_grad_plan_t plan);
+/* The planes of n_batch rows: x device (n_batch, ldx >= nx * ny) of x_dtype SMM_F32 / SMM_F64 (anything else:
+ * SMM_ERR_UNSUPPORTED); g device double, plane p of row b at g + b * ld_row + p * ld_plane (ld_plane >= nx * ny,
+ * ld_row >= (n_planes - 1) * ld_plane + nx * ny).  One stencil kernel: lanes run along i, a workgroup walks a band of
+ * rows and keeps the three source rows it needs in LDS, so f is read once (plus two halo rows per band) and every plane
+ * is written once.  Stream-ordered; allocates nothing. */
+int smm_gradients(smm_grad_plan_t plan, const void* x, int x_dtype, int64_t ldx, double* g, int64_t ld_plane,
+                  int64_t ld_row, int64_t n_batch, void* stream);
+
+/* The K-column apply: op from smm_operator_create_cols with K = n_cols >= 2, plan with K - 1 planes on a grid of
+ * nx * ny == n_src cells.  x, ldx, y, ldy, n_batch, remap_area_min and stream as for smm_apply.  `scratch` is device
+ * memory for the planes, 8-byte aligned: the call computes the planes of as many batch rows as fit in scratch_bytes,
+ * gathers them, and goes on until all rows are done; it allocates nothing and refuses (SMM_ERR_INVALID) only when not
+ * even one row's planes -- (K - 1) * n_src * 8 bytes -- fit.  smm_apply_cols_scratch reports the bytes that hold all
+ * n_batch rows at once.
+ * The gather is the row-per-lane SELL-64 kernel reading one column index and K weights per slot; links in ascending
+ * source index, per link the columns 0 .. K-1 in order, separate multiply and add into one accumulator per batch row.
+ * The result is bit for bit what smm_apply gives with SMM_APPLY_KERNEL_SELL on the "stacked" operator -- K * n_src
+ * source cells, link (d, s, k) at source index s * K + k -- and the stacked float64 field X[b, s * K + k], k = 0 holding
+ * f filled with its own dtype's 1e20 and widened, k >= 1 plane k.  SMM_APPLY_MASKED and SMM_APPLY_NO_FILL work as for
+ * smm_apply; SMM_APPLY_KERNEL_SELL is accepted (it is the kernel that runs).
+ * Built: SMM_F32 and SMM_F64 fields to SMM_F64 results in the native (B, S) layout.  SMM_ERR_UNSUPPORTED, checked
+ * before the handles are looked at: SMM_APPLY_SKIPNA, SMM_APPLY_KERNEL_TILE, the batch-fastest and host-pack flags,
+ * packed / half x_dtype (GRIB fields have no entry of this kind), any y_dtype but SMM_F64.  Level groups have no
+ * such entry. */
+int smm_apply_cols(smm_operator_t op, smm_grad_plan_t plan, const void* x, int x_dtype, int64_t ldx, void* y,
+                   int y_dtype, int64_t ldy, int64_t n_batch, double remap_area_min, unsigned flags, void* scratch,
+                   size_t scratch_bytes, void* stream);
+int smm_apply_cols_scratch(smm_operator_t op, int64_t n_batch, size_t* bytes);
+
 /* Test hook of the two host pipelines' error path: chunk number `chunk` (0-based) of every following
  * smm_apply_host / smm_group_apply_host call fails with SMM_ERR_HIP before its copies are queued;
  * chunk < 0 (the initial state) switches it off.  Process-wide; for tests only. */

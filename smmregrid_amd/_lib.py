@@ -249,6 +249,14 @@ SIGNATURES = {
                               _cfp, _cep],
     "smm_group_apply_host_pk": [_p, _p, _int, _p, _int, _i64, _i64, _i64, _int, _p, _p, _dbl, _uint, _i64, _cfp,
                                 _cep],
+    "smm_operator_create_cols": [_i64, _i64, _i64, _p, _p, _p, _int, _uint, _int, _pp],
+    "smm_operator_cols": [_p, ctypes.POINTER(_int)],
+    "smm_operator_export_cols": [_p, _p],
+    "smm_grad_plan_create": [_i64, _i64, _int, _int, ctypes.POINTER(_int), _p, _p, _p, _int, _pp],
+    "smm_grad_plan_destroy": [_p],
+    "smm_gradients": [_p, _p, _int, _i64, _p, _i64, _i64, _i64, _p],
+    "smm_apply_cols": [_p, _p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _p, _size, _p],
+    "smm_apply_cols_scratch": [_p, _i64, ctypes.POINTER(_size)],
     "smm_debug_fail_at_chunk": [_i64],
     "smm_debug_host_stats": [ctypes.POINTER(_dbl), _int, _int],
     "smm_debug_staging_faults": [_int, _i64],

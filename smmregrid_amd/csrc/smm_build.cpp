@@ -433,6 +433,81 @@ int64_t prune_zero_links(HostCsr& csr) {
   return dropped;
 }
 
+bool build_csr_cols(int64_t n_src, int64_t n_dst, int64_t nnz, const int32_t* src1, const int32_t* dst1, const double* w,
+                    int n_cols, HostCsr& out, std::vector<std::vector<double>>& extra, std::string& err) {
+  extra.clear();
+  if (n_cols < 1 || n_cols > kMaxWeightCols) {
+    err = "n_cols=" + std::to_string(n_cols) + " outside 1.." + std::to_string(kMaxWeightCols);
+    return false;
+  }
+  if (n_cols == 1) return build_csr(n_src, n_dst, nnz, src1, dst1, w, out, err);
+  if (nnz > 0 && !w) {
+    err = "null link array";
+    return false;
+  }
+  // One pass of build_csr per column on that column alone: the order of the links depends on (dst, src, link index)
+  // only, so every pass sorts, breaks ties and sums duplicates alike, and column 0 is build_csr's own output.
+  std::vector<double> one((size_t)std::max<int64_t>(nnz, 0));
+  extra.resize((size_t)n_cols - 1);
+  for (int k = 0; k < n_cols; ++k) {
+    for (int64_t i = 0; i < nnz; ++i) one[(size_t)i] = w[(size_t)i * (size_t)n_cols + (size_t)k];
+    if (k == 0) {
+      if (!build_csr(n_src, n_dst, nnz, src1, dst1, one.data(), out, err)) return false;
+    } else {
+      HostCsr col;
+      if (!build_csr(n_src, n_dst, nnz, src1, dst1, one.data(), col, err)) return false;
+      extra[(size_t)k - 1] = std::move(col.val);
+    }
+  }
+  return true;
+}
+
+int64_t prune_zero_links_cols(HostCsr& csr, std::vector<std::vector<double>>& extra) {
+  if (extra.empty()) return prune_zero_links(csr);
+  int64_t kept = 0, max_row = 0;
+  std::vector<int64_t> rowptr((size_t)csr.n_dst + 1, 0);
+  for (int64_t d = 0; d < csr.n_dst; ++d) {
+    const int64_t row_start = kept;
+    for (int64_t i = csr.rowptr[(size_t)d]; i < csr.rowptr[(size_t)d + 1]; ++i) {
+      bool zero = csr.val[(size_t)i] == 0.0;   // +0.0 and -0.0
+      for (const std::vector<double>& e : extra) zero = zero && e[(size_t)i] == 0.0;
+      if (zero) continue;
+      csr.col[(size_t)kept] = csr.col[(size_t)i];
+      csr.val[(size_t)kept] = csr.val[(size_t)i];
+      for (std::vector<double>& e : extra) e[(size_t)kept] = e[(size_t)i];
+      ++kept;
+    }
+    rowptr[(size_t)d + 1] = kept;
+    max_row = std::max(max_row, kept - row_start);
+  }
+  const int64_t dropped = csr.nnz - kept;
+  csr.rowptr.swap(rowptr);
+  csr.col.resize((size_t)kept);
+  csr.val.resize((size_t)kept);
+  for (std::vector<double>& e : extra) e.resize((size_t)kept);
+  csr.nnz = kept;
+  csr.max_row_nnz = max_row;
+  std::vector<uint8_t> used((size_t)csr.n_src, 0);
+  for (int32_t c : csr.col) used[(size_t)c] = 1;
+  int64_t u = 0;
+  for (uint8_t b : used) u += b;
+  csr.n_used_src = u;
+  return dropped;
+}
+
+void build_sell_cols(const HostCsr& csr, const HostSell& sell, const std::vector<std::vector<double>>& extra,
+                     std::vector<double>& out) {
+  out.assign((size_t)sell.n_slots * extra.size(), 0.0);   // padded slots: +0.0
+  for (size_t k = 0; k < extra.size(); ++k) {
+    double* plane = out.data() + k * (size_t)sell.n_slots;
+    for (int64_t d = 0; d < csr.n_dst; ++d) {
+      const int64_t base = sell.slice_off[(size_t)(d >> 6)] + (d & 63);
+      const int64_t p0 = csr.rowptr[(size_t)d], len = csr.rowptr[(size_t)d + 1] - p0;
+      for (int64_t i = 0; i < len; ++i) plane[(size_t)(base + i * 64)] = extra[k][(size_t)(p0 + i)];
+    }
+  }
+}
+
 HostChunk host_chunk_units(int64_t n_units, size_t x_unit, size_t y_unit, size_t xp_unit,
                            int64_t min_pack_units, int64_t pack_align, int64_t requested,
                            size_t free_bytes) {

@@ -629,7 +629,8 @@ int smm_fill_random(void* dst, int dtype, int64_t n, uint64_t seed, double mean,
 // Shared by the two constructors: `fill_csr` builds op->csr (false + err on invalid input).
 extern "C++" {
 template <typename F>
-static int create_operator(int device, smm_operator_t* out, F fill_csr, unsigned options = 0u) {
+static int create_operator(int device, smm_operator_t* out, F fill_csr, unsigned options = 0u,
+                           std::vector<std::vector<double>>* extra_cols = nullptr) {
   if (!out) return fail(SMM_ERR_INVALID, "null out handle");
   *out = nullptr;
   if (options & ~(unsigned)SMM_CREATE_PRUNE_ZEROS) return fail(SMM_ERR_INVALID, "unknown create option bits");
@@ -653,10 +654,16 @@ static int create_operator(int device, smm_operator_t* out, F fill_csr, unsigned
   try {
     std::string err;
     if (!fill_csr(op->csr, err)) return fail(SMM_ERR_INVALID, err);
-    if (options & SMM_CREATE_PRUNE_ZEROS) op->pruned_links = smm::prune_zero_links(op->csr);
+    if (extra_cols) {   // smm_operator_create_cols: fill_csr left the weight columns 1.. there
+      op->csr_xval = std::move(*extra_cols);
+      op->n_cols = 1 + (int)op->csr_xval.size();
+    }
+    if (options & SMM_CREATE_PRUNE_ZEROS) op->pruned_links = smm::prune_zero_links_cols(op->csr, op->csr_xval);
     const smm::HostCsr& kc = op->csr;
     smm::HostSell sell;
     smm::build_sell(kc, sell);
+    std::vector<double> xval;
+    if (!op->csr_xval.empty()) smm::build_sell_cols(kc, sell, op->csr_xval, xval);
 
     DeviceGuard guard(device);
     if (!guard.ok) return fail(SMM_ERR_HIP, "cannot select device " + std::to_string(device));
@@ -666,6 +673,7 @@ static int create_operator(int device, smm_operator_t* out, F fill_csr, unsigned
     if ((rc = upload(op->d_slice_off, sell.slice_off)) || (rc = upload(op->d_col, sell.col)) ||
         (rc = upload(op->d_val, sell.val)) || (rc = upload(op->d_rowlen, sell.rowlen)))
       return rc;
+    if (!xval.empty() && (rc = upload(op->d_xval, xval))) return rc;
     op->sell_shape.n_slices = sell.n_slices;
     op->sell_shape.n_slots = sell.n_slots;
     op->sell_shape.slice_off = std::move(sell.slice_off);
@@ -719,6 +727,34 @@ int smm_operator_create_opt(int64_t n_src, int64_t n_dst, int64_t nnz, const int
   return create_operator(device, out, [&](smm::HostCsr& csr, std::string& err) {
     return smm::build_csr(n_src, n_dst, nnz, src_addr_1based, dst_addr_1based, w, csr, err);
   }, options);
+}
+
+int smm_operator_create_cols(int64_t n_src, int64_t n_dst, int64_t nnz, const int32_t* src_addr_1based,
+                             const int32_t* dst_addr_1based, const double* w, int n_cols, unsigned options, int device,
+                             smm_operator_t* out) {
+  std::vector<std::vector<double>> extra;
+  return guarded([&]() -> int {
+    return create_operator(device, out, [&](smm::HostCsr& csr, std::string& err) {
+      return smm::build_csr_cols(n_src, n_dst, nnz, src_addr_1based, dst_addr_1based, w, n_cols, csr, extra, err);
+    }, options, &extra);
+  });
+}
+
+int smm_operator_cols(smm_operator_t op, int* n_cols) {
+  if (!op) return fail(SMM_ERR_INVALID, "null operator");
+  if (n_cols) *n_cols = op->n_cols;
+  return SMM_OK;
+}
+
+int smm_operator_export_cols(smm_operator_t op, double* val) {
+  if (!op) return fail(SMM_ERR_INVALID, "null operator");
+  if (!val && op->csr.nnz > 0) return fail(SMM_ERR_INVALID, "null output");
+  const size_t K = (size_t)op->n_cols;
+  for (int64_t p = 0; p < op->csr.nnz; ++p) {
+    val[(size_t)p * K] = op->csr.val[(size_t)p];
+    for (size_t k = 1; k < K; ++k) val[(size_t)p * K + k] = op->csr_xval[k - 1][(size_t)p];
+  }
+  return SMM_OK;
 }
 
 int smm_operator_create_csr(int64_t n_src, int64_t n_dst, const int64_t* rowptr, const int32_t* col,

@@ -136,6 +136,12 @@ struct smm_operator {
   DeviceBuf<int32_t> d_col;
   DeviceBuf<double> d_val;
   DeviceBuf<int32_t> d_rowlen;
+  // smm_operator_create_cols: weight columns 1 .. n_cols - 1 (gradient weights; column 0 is csr.val / d_val and every
+  // other entry sees that alone) -- per column the values of the canonical CSR's links, and on the device SELL slot
+  // planes of n_slots each beside d_val, padded slots +0.0 (smm_apply_cols)
+  int n_cols = 1;
+  std::vector<std::vector<double>> csr_xval;
+  DeviceBuf<double> d_xval;
   DeviceBuf<uint8_t> d_imask;
   DeviceBuf<double> d_frac;
   // LDS tile plans by block shape: [0] = 4 slices (256 rows) per block, [1] = 1 slice (heavy rows),

@@ -94,6 +94,21 @@ bool adopt_csr(int64_t n_src, int64_t n_dst, const int64_t* rowptr, const int32_
 int64_t prune_zero_links(HostCsr& csr);
 void build_sell(const HostCsr& csr, HostSell& out);
 
+// ---- operators with weight columns (smm_operator_create_cols): remap_matrix rows of n_cols weights, 1..4 -- the value
+// weight and the gradient weights of bicubic (4) and second-order conservative (3) files.  w is [nnz * n_cols], link k's
+// weights at w + k * n_cols.  out is the canonical CSR of column 0, exactly what build_csr makes of that column alone;
+// extra[k - 1][p] is column k of link p of that CSR: the sort by (dst, src), the tie-break and the sequential duplicate
+// summing are those of build_csr, applied to every column with the same permutation.  n_cols outside 1..4: false + err.
+constexpr int kMaxWeightCols = 4;
+bool build_csr_cols(int64_t n_src, int64_t n_dst, int64_t nnz, const int32_t* src1, const int32_t* dst1, const double* w,
+                    int n_cols, HostCsr& out, std::vector<std::vector<double>>& extra, std::string& err);
+// prune_zero_links for such an operator: a link goes only when ALL its columns are exactly +-0.0
+int64_t prune_zero_links_cols(HostCsr& csr, std::vector<std::vector<double>>& extra);
+// The SELL-64 slot planes of the extra columns beside HostSell.val: plane k - 1 at out[(k - 1) * n_slots ..], the slot
+// layout of build_sell, padded slots +0.0
+void build_sell_cols(const HostCsr& csr, const HostSell& sell, const std::vector<std::vector<double>>& extra,
+                     std::vector<double>& out);
+
 // Source-tile plan for the LDS-staged kernel.  Destination rows are grouped in
 // blocks of `rows_per_block` consecutive rows (4 SELL slices, 1 slice, or 1/2, 1/4, 1/8 of a slice
 // for rows whose footprint is wide); the distinct source cells a block

@@ -433,7 +433,8 @@ def bicubic_weights(src, dst, src_mask=None):
     """SCRIP bicubic from a regular lon/lat source: per corner of the enclosing source box four weights -- for the
     value and for its derivatives along i, along j and the cross derivative (cubic Hermite basis), `num_wgts` = 4 as
     CDO's genbic writes them.  The reference applies column 0 only (weights.py:33: `remap_matrix[:, 0]`), i.e. the
-    value basis h00(x) h00(y) with h00(t) = 1 - 3 t^2 + 2 t^3; columns 1 - 3 are there for the file's sake.
+    value basis h00(x) h00(y) with h00(t) = 1 - 3 t^2 + 2 t^3; columns 1 - 3 are applied by `Regridder(gradients=True)`
+    alone (`gradients.GradientRule` says which derivatives they multiply).
     Masked corners (src_mask == 0) drop out and column 0 is renormalised, as for bilinear weights."""
     src, dst = parse_grid(src), parse_grid(dst)
     if src.kind != "regular":
@@ -1306,7 +1307,8 @@ def conservative2_weights(src, dst, src_mask=None, norm="fracarea"):
 
     with (lat_n, lon_n) the area centroid of the source cell, all three normalised like the first-order weight.
     A destination value is then sum_n f_n w1 + (df/dlat)_n w2 + (1/cos(lat) df/dlon)_n w3.  The reference applies
-    column 0 only (weights.py:33), which is the first-order weight.  Exact for lon/lat boxes."""
+    column 0 only (weights.py:33), which is the first-order weight; `Regridder(gradients=True)` applies all three.  Exact
+    for lon/lat boxes."""
     src, dst = parse_grid(src), parse_grid(dst)
     if src.kind != "regular" or dst.kind != "regular":
         raise ValueError("second-order conservative generation needs regular source and destination grids")

@@ -74,26 +74,41 @@ class SparseOperator:
     """(S x D) weights matrix in HBM, built from SCRIP links (weights.py:25-44)."""
 
     def __init__(self, n_src, n_dst, src_address, dst_address, remap_matrix, device=None, dst_dims=None,
-                 prune_zeros=False):
+                 prune_zeros=False, columns=False):
         """dst_dims: shape of the destination grid as the weights file gives it (`dst_grid_dims`,
         fastest dimension first); kept as metadata (save / load).
         prune_zeros: drop links whose weight is exactly zero (bilinear weights between aligned grids are
-        mostly zeros); results stay bit-identical because every gathered value is finite after the fill."""
+        mostly zeros); results stay bit-identical because every gathered value is finite after the fill.
+        columns: keep every column of a 2-D remap_matrix (smm_operator_create_cols; 1..4 columns) -- the gradient
+        weights of bicubic and second-order conservative files, which `apply(..., gradients=rule)` applies.  Column 0
+        of such an operator is the operator built without `columns`, and everything else works on it as before;
+        prune_zeros then drops a link only when all its columns are zero."""
         src = np.ascontiguousarray(src_address, dtype=np.int32).ravel()
         dst = np.ascontiguousarray(dst_address, dtype=np.int32).ravel()
         w = np.asarray(remap_matrix, dtype=np.float64)
-        if w.ndim == 2:
-            w = w[:, 0]          # only the first weight column is used (weights.py:33)
-        w = np.ascontiguousarray(w).ravel()
-        if not (src.size == dst.size == w.size):
+        keep_cols = bool(columns) and w.ndim == 2
+        if keep_cols:
+            w = np.ascontiguousarray(w)
+            n_links = w.shape[0]
+        else:
+            if w.ndim == 2:
+                w = w[:, 0]          # only the first weight column is used (weights.py:33)
+            w = np.ascontiguousarray(w).ravel()
+            n_links = w.size
+        if not (src.size == dst.size == n_links):
             raise ValueError("src_address, dst_address and remap_matrix differ in length")
         if device is None:
             device = current_device()
         self.device = int(device)
         h = ctypes.c_void_p()
         t0 = time.perf_counter()
-        _lib.call("smm_operator_create_opt", int(n_src), int(n_dst), int(src.size), _cptr(src),
-                  _cptr(dst), _cptr(w), _lib.CREATE_PRUNE_ZEROS if prune_zeros else 0, self.device, ctypes.byref(h))
+        options = _lib.CREATE_PRUNE_ZEROS if prune_zeros else 0
+        if keep_cols:
+            _lib.call("smm_operator_create_cols", int(n_src), int(n_dst), int(src.size), _cptr(src), _cptr(dst),
+                      _cptr(w), int(w.shape[1]), options, self.device, ctypes.byref(h))
+        else:
+            _lib.call("smm_operator_create_opt", int(n_src), int(n_dst), int(src.size), _cptr(src),
+                      _cptr(dst), _cptr(w), options, self.device, ctypes.byref(h))
         self.create_ms = (time.perf_counter() - t0) * 1e3     # sort + duplicate sum + layouts + upload
         self.dst_dims = None if dst_dims is None else tuple(int(v) for v in np.asarray(dst_dims).ravel())
         self._adopt(h)
@@ -103,6 +118,9 @@ class SparseOperator:
         vals = [ctypes.c_int64(0) for _ in range(5)]
         _lib.call("smm_operator_info", self.handle, *[ctypes.byref(v) for v in vals])
         self.n_src, self.n_dst, self.nnz, self.n_used_src, self.max_row_nnz = [v.value for v in vals]
+        n_cols = ctypes.c_int(1)
+        _lib.call("smm_operator_cols", self.handle, ctypes.byref(n_cols))
+        self.n_cols = n_cols.value      # weight columns kept (SparseOperator(..., columns=True)); 1 otherwise
         self.has_imask = False
         self.has_frac = False
 
@@ -184,6 +202,57 @@ class SparseOperator:
         _lib.call("smm_operator_export_csr", self.handle, _cptr(rowptr), _cptr(col), _cptr(val))
         return rowptr, col, val
 
+    def export_cols(self):
+        """Every weight column of the canonical CSR, float64 (nnz, n_cols), the links in `export_csr`'s order."""
+        val = np.zeros((self.nnz, self.n_cols), dtype=np.float64)
+        _lib.call("smm_operator_export_cols", self.handle, _cptr(val))
+        return val
+
+    def _check_rule(self, rule):
+        if rule.size != self.n_src:
+            raise ValueError(f"the gradient rule's grid has {rule.size} cells, the operator {self.n_src} source cells")
+
+    def gradients(self, x, rule, out=None, stream=None):
+        """The gradient planes of a device-resident field x (B, S) -- or (B, ldx >= S) -- of float32 / float64 by
+        `rule` (a `GradientRule`), computed on the device (smm_gradients): a float64 DeviceArray (B, n_planes, S),
+        bit for bit `rule.gradients` of every row."""
+        if not isinstance(x, DeviceArray):
+            raise TypeError("SparseOperator.gradients takes a DeviceArray")
+        self._check_rule(rule)
+        if x.ndim != 2 or x.shape[1] < self.n_src:
+            raise ValueError(f"X must be (B, >= {self.n_src}), got {x.shape}")
+        shape = (x.shape[0], rule.n_planes, self.n_src)
+        if out is None:
+            out = DeviceArray(shape, np.float64)
+        elif out.shape != shape or out.dtype != np.float64:
+            raise ValueError(f"out must be a float64 DeviceArray {shape}")
+        _lib.call("smm_gradients", rule.plan(self.device), _ptr(x), dtype_code(x.dtype), x.shape[1], _ptr(out),
+                  self.n_src, rule.n_planes * self.n_src, x.shape[0], _stream_handle(stream))
+        return out
+
+    def _apply_cols(self, x, y, rule, masked, remap_area_min, out_dtype, flags, stream, scratch_rows, scratch=None):
+        """`apply(..., gradients=rule)`: smm_apply_cols.  The planes' scratch -- the caller's, or one made here for
+        scratch_rows rows -- lives as long as the result."""
+        self._check_rule(rule)
+        if x.ndim != 2 or x.shape[1] < self.n_src:
+            raise ValueError(f"X must be (B, >= {self.n_src}), got {x.shape}")
+        n_batch = x.shape[0]
+        if y is None:
+            y = DeviceArray((n_batch, self.n_dst), np.dtype(out_dtype))
+        elif y.shape != (n_batch, self.n_dst):
+            raise ValueError(f"Y must be ({n_batch}, {self.n_dst}), got {y.shape}")
+        per_row = rule.n_planes * self.n_src * 8
+        if scratch_rows is None:      # all rows when they fit 256 MiB, else as many as do
+            scratch_rows = max(1, min(n_batch, (256 << 20) // max(per_row, 1)))
+        if scratch is None:
+            scratch = DeviceArray((max(int(scratch_rows), 0) * per_row,), np.uint8)
+        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        _lib.call("smm_apply_cols", self.handle, rule.plan(self.device), _ptr(x), dtype_code(x.dtype), x.shape[1],
+                  _ptr(y), dtype_code(y.dtype), self.n_dst, n_batch, float(remap_area_min), fl,
+                  ctypes.c_void_p(scratch.ptr), scratch.nbytes, _stream_handle(stream))
+        y._scratch = scratch      # the gather may still be reading it when this returns
+        return y
+
     def plan_info(self):
         kind = ctypes.c_int(0)
         lds = ctypes.c_int64(0)
@@ -210,7 +279,8 @@ class SparseOperator:
         return out
 
     def apply(self, x, y=None, masked=False, remap_area_min=0.0, out_dtype=np.float64,
-              flags=0, stream=None, keep_batch_fastest=False, skipna=False, cf=None, cf_out=None):
+              flags=0, stream=None, keep_batch_fastest=False, skipna=False, cf=None, cf_out=None, gradients=None,
+              scratch_rows=None, scratch=None):
         """Y = epilogue(fill(X) . W) for a device-resident X of shape (B, S), or (B, ldx) with a
         padded row pitch ldx >= S (rows that start on 128-B lines are staged without straddling).
         A field tagged batch-fastest (`x.layout == "sb"`, shape (S, B)) goes through the batch-fastest
@@ -223,9 +293,22 @@ class SparseOperator:
         cf: a `CFDecode` -- x holds the raw int16 / uint16 of a CF-packed field, decoded inside the kernel
         (bit-identical to applying `cf.decode` on the host first; float64 results only).
         cf_out: a `CFEncode` -- the result is stored as raw int16 / uint16, encoded inside the kernel's stores
-        (bit-identical to `cf_out.encode` of the float64 result; out of range -> fill value, never wrapped)."""
+        (bit-identical to `cf_out.encode` of the float64 result; out of range -> fill value, never wrapped).
+        gradients: a `GradientRule` -- every weight column of an operator built with columns=True is applied
+        (smm_apply_cols): the gradient planes of each batch row are computed on the device and gathered beside the
+        field, sum over links of w0 * f + w1 * g1 + ...  float32 / float64 fields in the native (B, S) layout to
+        float64 results; skipna, a half or float32 out_dtype and the forced tile kernel are refused by the library
+        (SMM_ERR_UNSUPPORTED), cf / cf_out / a batch-fastest field here.  scratch_rows: batch rows whose planes the
+        scratch holds at a time (default: all of them up to 256 MiB); scratch: a DeviceArray to hold them instead of
+        one made by the call (its bytes decide how many rows a round takes)."""
         if not isinstance(x, DeviceArray):
             raise TypeError("SparseOperator.apply takes a DeviceArray (use Regridder for host data)")
+        if gradients is not None:
+            if x.layout == "sb" or keep_batch_fastest or cf is not None or cf_out is not None:
+                raise ValueError("gradients= goes with float32 / float64 fields in the native (B, S) layout and float64 "
+                                 "results: no batch-fastest field, no cf / cf_out")
+            return self._apply_cols(x, y, gradients, masked, remap_area_min, out_dtype,
+                                    int(flags) | (_lib.APPLY_SKIPNA if skipna else 0), stream, scratch_rows, scratch)
         if x.layout == "sb":
             return self.apply_sb(x, y=y, masked=masked, remap_area_min=remap_area_min, out_dtype=out_dtype,
                                  flags=flags, skipna=skipna, stream=stream, keep_batch_fastest=keep_batch_fastest,
@@ -293,7 +376,7 @@ class SparseOperator:
                            cf_out)
 
     def apply_host(self, x, out=None, masked=False, remap_area_min=0.0, out_dtype=np.float64,
-                   flags=0, chunk_rows=0, skipna=False, cf=None, cf_out=None, half=False):
+                   flags=0, chunk_rows=0, skipna=False, cf=None, cf_out=None, half=False, gradients=None):
         """Same product for a host (numpy) array of shape (B, S): the rows stream through the
         library's double-buffered H2D / kernel / D2H pipeline (smm_apply_host).  Arrays from
         `pinned_empty` are DMA'd without staging copies.  Returns a (B, D) numpy array.
@@ -303,7 +386,15 @@ class SparseOperator:
         raw int16 / uint16: a quarter of the float64 result's bytes over PCIe (smm_apply_host_pk).
         half: a float16 field is shipped as 2-byte cells and widened to float32 inside the kernels (by default it is
         promoted to float64 on the host, as before); a `bfloat16` field always is.  out_dtype float16 / `bfloat16`: the
-        result comes back as 2-byte cells."""
+        result comes back as 2-byte cells.
+        gradients: a `GradientRule` -- as for `apply`, for a host field.  This is the first form of that road: a
+        synchronous loop over chunks of rows -- H2D copy of the chunk, smm_apply_cols, D2H copy -- which overlaps
+        nothing.  A chunk's X, planes and Y stay within 256 MiB and a quarter of the free device memory; chunk_rows > 0
+        fixes the rows per chunk."""
+        if gradients is not None:
+            return self._apply_host_cols(x, out, gradients, masked, remap_area_min, out_dtype,
+                                         int(flags) | (_lib.APPLY_SKIPNA if skipna else 0), int(chunk_rows), cf, cf_out,
+                                         half)
         x = _host_field(x, cf, half)
         if x.ndim != 2 or x.shape[1] != self.n_src:
             raise ValueError(f"X must be (B, {self.n_src}), got {x.shape}")
@@ -319,6 +410,43 @@ class SparseOperator:
         ldx = x.strides[0] // x.itemsize if n_batch > 1 else max(self.n_src, 1)
         return _apply_call("smm_apply_host", self.handle, x, (ldx,), out,
                            (self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows)), y_res, cf, cf_out, "out")
+
+    def _apply_host_cols(self, x, out, rule, masked, remap_area_min, out_dtype, flags, chunk_rows, cf, cf_out, half):
+        """`apply_host(..., gradients=rule)`: the synchronous chunk loop."""
+        if cf is not None or cf_out is not None or half:
+            raise ValueError("gradients= goes with float32 / float64 fields and float64 results: no cf / cf_out / half")
+        if np.dtype(out_dtype) != np.dtype(np.float64):
+            raise ValueError("gradients= produces float64 results")
+        self._check_rule(rule)
+        x = np.asarray(x)
+        if x.dtype not in (np.float32, np.float64):
+            x = x.astype(np.float64)      # result_type(x, f64), regrid.py:550
+        if x.ndim != 2 or x.shape[1] != self.n_src:
+            raise ValueError(f"X must be (B, {self.n_src}), got {x.shape}")
+        x = np.ascontiguousarray(x)
+        n_batch = x.shape[0]
+        if out is None:
+            out = result_cache.empty((n_batch, self.n_dst), np.float64)
+        if out.shape != (n_batch, self.n_dst) or not out.flags.c_contiguous or out.dtype != np.float64:
+            raise ValueError(f"out must be a C-contiguous float64 ({n_batch}, {self.n_dst}) array")
+        if n_batch == 0:
+            return out
+        if chunk_rows <= 0:      # X, planes and Y of a chunk: 256 MiB and a quarter of the free memory, as _grib.host_chunks
+            from .device import mem_info
+            per_row = self.n_src * x.itemsize + rule.n_planes * self.n_src * 8 + self.n_dst * 8
+            budget = min(256 << 20, mem_info()[0] // 4)
+            chunk_rows = max(1, budget // max(per_row, 1))
+        chunk_rows = min(int(chunk_rows), n_batch)
+        dx = DeviceArray((chunk_rows, self.n_src), x.dtype)
+        dy = DeviceArray((chunk_rows, self.n_dst), np.float64)
+        scratch = DeviceArray((chunk_rows * rule.n_planes * self.n_src * 8,), np.uint8)
+        for r0 in range(0, n_batch, chunk_rows):
+            r1 = min(n_batch, r0 + chunk_rows)
+            xc, yc = dx.rows(0, r1 - r0), dy.rows(0, r1 - r0)
+            xc.copy_from_host(x[r0:r1])
+            self._apply_cols(xc, yc, rule, masked, remap_area_min, np.float64, flags, None, None, scratch=scratch)
+            yc.to_host(out=out[r0:r1])      # a blocking copy on the default stream: the chunk is done
+        return out
 
     def apply_grib(self, x, rows, x_bytes=None, y=None, masked=False, remap_area_min=0.0, flags=0, stream=None,
                    bitmaps=None, skipna=False, ccsds=None, cpx=None, cpx_missing=None, coded=None):

@@ -59,7 +59,7 @@ class Regridder(object):
                  check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=None,
                  lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False,
                  packed_levels=False, packed_out=False, packed_out_levels=False, half=False, packed_skipna=False, grib_out=False,
-                 grib_out_levels=False, grib_out_ccsds=False, grib_out_cpx=False):
+                 grib_out_levels=False, grib_out_ccsds=False, grib_out_cpx=False, gradients=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -166,6 +166,19 @@ class Regridder(object):
             raise ValueError('packed_out=True encodes the float64 result: out_dtype must stay float64')
         if self.grib_out and self.out_dtype != np.dtype(np.float64):
             raise ValueError('grib_out=True packs the float64 result: out_dtype must stay float64')
+        # gradients: every weight column of bicubic (`bic`, num_wgts = 4) and second-order conservative (`con2`,
+        # num_wgts = 3) weights is applied, not column 0 alone as the reference does: the gradients of each field are
+        # computed on the device by the rule of `gradients.GradientRule` and gathered beside the field
+        # (smm_apply_cols).  Beyond the reference, off by default; 2-D weights on a regular lon/lat source only
+        self.gradients = bool(gradients)
+        if self.gradients:
+            clash = [name for name, on in (("skipna", self.skipna), ("packed", self.packed), ("half", self.half),
+                                           ("keep_batch_fastest", self.keep_batch_fastest),
+                                           (f"out_dtype={self.out_dtype}", self.out_dtype != np.dtype(np.float64))) if on]
+            if clash:
+                raise ValueError(f"gradients=True does not go with {', '.join(clash)}: it goes with float32 / float64 "
+                                 "fields in the native layout (host, device-resident or lazy), float64 results, 2-D "
+                                 "weights, remap_area_min, the destination mask, lazy and prune_zero_weights")
         mask_dim = tolist(mask_dim)
         horizontal_dims = tolist(horizontal_dims)
         self.extra_dims = {'mask': mask_dim, 'horizontal': horizontal_dims}
@@ -215,6 +228,12 @@ class Regridder(object):
                                         loglevel=loglevel)
                 gridtype.weights = generator.weights(method=method, mask_dim=gridtype.mask_dim)
 
+        if self.gradients:      # refused before any device work: masked levels, a source that is no regular lon/lat grid
+            from .gradients import GradientRule
+            for gridtype in self.grids:
+                if gridtype.mask_dim:
+                    raise ValueError("gradients=True does not go with masked-level (3-D) weights: it goes with 2-D weights")
+                gridtype.grad_rule = GradientRule.from_weights(gridtype.weights)
         for gridtype in self.grids:
             self._setup_operators(gridtype)
 
@@ -228,7 +247,7 @@ class Regridder(object):
                                                                prune_zeros=self.prune_zero_weights)
         else:
             gridtype.weights_matrix = compute_weights_matrix(w, device=self.device,
-                                                             prune_zeros=self.prune_zero_weights)
+                                                             prune_zeros=self.prune_zero_weights, columns=self.gradients)
 
         if "dst_grid_masked" in w.variables:
             gridtype.masked = np.asarray(w["dst_grid_masked"].values)
@@ -515,7 +534,8 @@ class Regridder(object):
         return self.apply_weights(source_data, gridtype.weights,
                                   weights_matrix=gridtype.weights_matrix,
                                   masked=gridtype.masked,
-                                  horizontal_dims=gridtype.horizontal_dims, cf=cf, cf_out=cf_out, out_dtype=out_dtype)
+                                  horizontal_dims=gridtype.horizontal_dims, cf=cf, cf_out=cf_out, out_dtype=out_dtype,
+                                  gradients=getattr(gridtype, "grad_rule", None))
 
     # ------------------------------------------------------------------ apply (2-D)
     def _target_layout(self, weights):
@@ -554,10 +574,11 @@ class Regridder(object):
         return out
 
     def apply_weights(self, source_data, weights, weights_matrix=None, masked=True,
-                      horizontal_dims=None, cf=None, cf_out=None, out_dtype=None):
+                      horizontal_dims=None, cf=None, cf_out=None, out_dtype=None, gradients=None):
         """regrid.py:458-628 for one 2-D operator.  cf: the CFDecode of a raw int16 / uint16 field (packed=True);
         cf_out: the CFEncode its result is stored with (packed_out=True); out_dtype: this variable's result dtype
-        (None: the Regridder's, or the field's own half type under half=True)."""
+        (None: the Regridder's, or the field's own half type under half=True); gradients: the `GradientRule` of these
+        weights (Regridder(gradients=True); None there: made from `weights`)."""
         source_data = from_xarray(source_data)
         if out_dtype is None:
             out_dtype = self._result_dtype(source_data)
@@ -576,8 +597,12 @@ class Regridder(object):
         kept_shape = [source_data.sizes[d] for d in kept_dims]
         tgt_shape, tgt_dims = self._target_layout(weights)
 
+        rule = gradients
+        if rule is None and getattr(self, "gradients", False):
+            from .gradients import GradientRule
+            rule = GradientRule.from_weights(weights)
         if weights_matrix is None:
-            weights_matrix = compute_weights_matrix(weights, device=self.device)
+            weights_matrix = compute_weights_matrix(weights, device=self.device, columns=rule is not None)
             weights_matrix.set_epilogue(
                 weights["dst_grid_imask"].values,
                 weights["dst_grid_frac"].values if "dst_grid_frac" in weights else None)
@@ -602,6 +627,10 @@ class Regridder(object):
         elif self.keep_batch_fastest:
             raise ValueError("keep_batch_fastest needs a device-resident batch-fastest field "
                              "(source_data.data = DeviceArray(..., layout='sb'))")
+        if rule is not None and sb_in:
+            raise ValueError("gradients=True does not go with a batch-fastest field (layout='sb'): it goes with float32 / "
+                             "float64 fields in the native layout (host, device-resident or lazy)")
+        grad_kw = {} if rule is None else {"gradients": rule}
         sb_out = sb_in and self.keep_batch_fastest
         out_shape = (tgt_shape + kept_shape) if sb_out else (kept_shape + tgt_shape)
         out_dims = (tgt_dims + kept_dims) if sb_out else (kept_dims + tgt_dims)
@@ -619,7 +648,7 @@ class Regridder(object):
             if host.shape[1] != op.n_src:
                 raise ValueError(f"source grid has {host.shape[1]} cells, weights expect {op.n_src}")
             return op.apply_host(host, masked=masked, remap_area_min=area_min, out_dtype=out_dtype, skipna=skipna,
-                                 cf=cf, cf_out=cf_out, half=ship_half)
+                                 cf=cf, cf_out=cf_out, half=ship_half, **grad_kw)
 
         def compute():
             if isinstance(src, GribField):
@@ -656,7 +685,7 @@ class Regridder(object):
                 if x.shape[1] != op.n_src:
                     raise ValueError(f"source grid has {x.shape[1]} cells, weights expect {op.n_src}")
                 y = op.apply(x, masked=masked, remap_area_min=area_min, out_dtype=out_dtype, skipna=skipna, cf=cf,
-                             cf_out=cf_out)
+                             cf_out=cf_out, **grad_kw)
                 return y.reshape(*(kept_shape + tgt_shape))
             host = src.compute() if isinstance(src, LazyArray) else np.asarray(src)
             return apply_rows(host.reshape(n_batch, -1)).reshape(kept_shape + tgt_shape)

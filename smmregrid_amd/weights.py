@@ -27,18 +27,20 @@ def _dst_dims(weights):
     return np.asarray(weights["dst_grid_dims"].values).astype(np.int32).ravel()
 
 
-def compute_weights_matrix(weights, device=None, prune_zeros=False):
-    """CDO weights -> one operator of shape (S, D)   (weights.py:25-44)."""
+def compute_weights_matrix(weights, device=None, prune_zeros=False, columns=False):
+    """CDO weights -> one operator of shape (S, D)   (weights.py:25-44).
+    columns: keep every column of remap_matrix, not column 0 alone -- the gradient weights of bicubic and second-order
+    conservative files, which `SparseOperator.apply(..., gradients=rule)` applies (beyond the reference)."""
     weights = from_xarray(weights)
     src_address = weights["src_address"].values
     dst_address = weights["dst_address"].values
     remap_matrix = weights["remap_matrix"].values
-    if remap_matrix.ndim == 2:
+    if remap_matrix.ndim == 2 and not columns:
         remap_matrix = remap_matrix[:, 0]
     n_src = weights.sizes["src_grid_size"]
     n_dst = weights.sizes["dst_grid_size"]
     return SparseOperator(n_src, n_dst, src_address, dst_address, remap_matrix, device=device,
-                          dst_dims=_dst_dims(weights), prune_zeros=prune_zeros)
+                          dst_dims=_dst_dims(weights), prune_zeros=prune_zeros, columns=columns)
 
 
 def compute_weights_matrix3d(weights, mask_dim="lev", device=None, prune_zeros=False, workers=None):
