@@ -59,6 +59,44 @@ def _host_field(x, cf, half):
     return x
 
 
+def _device_result(y, shape, dtype, layout="bs"):
+    """y, or without one a fresh DeviceArray for the result; a y of another shape is refused."""
+    if y is None:
+        return DeviceArray(shape, dtype, layout=layout)
+    if y.shape != shape:
+        raise ValueError(f"Y must be {shape}, got {y.shape}")
+    return y
+
+
+class _Handle:
+    """Owns one handle of the library; `_destroy` names the entry that releases it."""
+
+    def close(self):
+        if getattr(self, "handle", None):
+            _lib.call(self._destroy, self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _flags(flags, masked=False, skipna=False, sb_packed=False, y_sb=False):
+    """The `flags` word of an apply entry: the caller's bits and those its keywords stand for."""
+    return int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0) | \
+        (_lib.APPLY_SB_PACKED if sb_packed else 0) | (_lib.APPLY_SB_Y_SB if y_sb else 0)
+
+
+def _level_result(n_outer, n_lev, n_inner, n_dst, transpose):
+    """(shape, (outer, lev, inner) strides in cells) of a level group's result: (n_outer, n_inner, n_lev, D) when
+    transpose (regrid.py:420-427) else (n_lev, n_outer, n_inner, D) (the concat order, regrid.py:410)."""
+    if transpose:
+        return (n_outer, n_inner, n_lev, n_dst), (n_inner * n_lev * n_dst, n_dst, n_lev * n_dst)
+    return (n_lev, n_outer, n_inner, n_dst), (n_inner * n_dst, n_outer * n_inner * n_dst, n_dst)
+
+
 def _launch_info(fn, handle, dt, sizes, flags):
     ints = [ctypes.c_int(0) for _ in range(5)]
     nb, lds = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -70,8 +108,9 @@ def _launch_info(fn, handle, dt, sizes, flags):
             "lds_bytes": lds.value, "big_operator": bool(ints[4].value)}
 
 
-class SparseOperator:
+class SparseOperator(_Handle):
     """(S x D) weights matrix in HBM, built from SCRIP links (weights.py:25-44)."""
+    _destroy = "smm_operator_destroy"
 
     def __init__(self, n_src, n_dst, src_address, dst_address, remap_matrix, device=None, dst_dims=None,
                  prune_zeros=False, columns=False):
@@ -237,16 +276,13 @@ class SparseOperator:
         if x.ndim != 2 or x.shape[1] < self.n_src:
             raise ValueError(f"X must be (B, >= {self.n_src}), got {x.shape}")
         n_batch = x.shape[0]
-        if y is None:
-            y = DeviceArray((n_batch, self.n_dst), np.dtype(out_dtype))
-        elif y.shape != (n_batch, self.n_dst):
-            raise ValueError(f"Y must be ({n_batch}, {self.n_dst}), got {y.shape}")
+        y = _device_result(y, (n_batch, self.n_dst), np.dtype(out_dtype))
         per_row = rule.n_planes * self.n_src * 8
         if scratch_rows is None:      # all rows when they fit 256 MiB, else as many as do
             scratch_rows = max(1, min(n_batch, (256 << 20) // max(per_row, 1)))
         if scratch is None:
             scratch = DeviceArray((max(int(scratch_rows), 0) * per_row,), np.uint8)
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        fl = _flags(flags, masked)
         _lib.call("smm_apply_cols", self.handle, rule.plan(self.device), _ptr(x), dtype_code(x.dtype), x.shape[1],
                   _ptr(y), dtype_code(y.dtype), self.n_dst, n_batch, float(remap_area_min), fl,
                   ctypes.c_void_p(scratch.ptr), scratch.nbytes, _stream_handle(stream))
@@ -307,8 +343,8 @@ class SparseOperator:
             if x.layout == "sb" or keep_batch_fastest or cf is not None or cf_out is not None:
                 raise ValueError("gradients= goes with float32 / float64 fields in the native (B, S) layout and float64 "
                                  "results: no batch-fastest field, no cf / cf_out")
-            return self._apply_cols(x, y, gradients, masked, remap_area_min, out_dtype,
-                                    int(flags) | (_lib.APPLY_SKIPNA if skipna else 0), stream, scratch_rows, scratch)
+            return self._apply_cols(x, y, gradients, masked, remap_area_min, out_dtype, _flags(flags, skipna=skipna), stream,
+                                    scratch_rows, scratch)
         if x.layout == "sb":
             return self.apply_sb(x, y=y, masked=masked, remap_area_min=remap_area_min, out_dtype=out_dtype,
                                  flags=flags, skipna=skipna, stream=stream, keep_batch_fastest=keep_batch_fastest,
@@ -319,11 +355,8 @@ class SparseOperator:
             raise ValueError(f"X must be (B, >= {self.n_src}), got {x.shape}")
         n_batch = x.shape[0]
         y_res = result_dtype(out_dtype, cf_out)
-        if y is None:
-            y = DeviceArray((n_batch, self.n_dst), y_res[0])
-        elif y.shape != (n_batch, self.n_dst):
-            raise ValueError(f"Y must be ({n_batch}, {self.n_dst}), got {y.shape}")
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        y = _device_result(y, (n_batch, self.n_dst), y_res[0])
+        fl = _flags(flags, masked, skipna)
         return _apply_call("smm_apply", self.handle, x, (x.shape[1],), y,
                            (self.n_dst, n_batch, float(remap_area_min), fl, _stream_handle(stream)), y_res, cf, cf_out)
 
@@ -363,14 +396,8 @@ class SparseOperator:
             raise ValueError(f"n_batch must be within the pitch {ldx}")
         y_shape = (self.n_dst, n_batch) if keep_batch_fastest else (n_batch, self.n_dst)
         y_res = result_dtype(out_dtype, cf_out)
-        if y is None:
-            y = DeviceArray(y_shape, y_res[0], layout="sb" if keep_batch_fastest else "bs")
-        elif y.shape != y_shape:
-            raise ValueError(f"Y must be {y_shape}, got {y.shape}")
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
-        fl |= _lib.APPLY_SB_PACKED if packed else 0
-        if keep_batch_fastest:
-            fl |= _lib.APPLY_SB_Y_SB
+        y = _device_result(y, y_shape, y_res[0], "sb" if keep_batch_fastest else "bs")
+        fl = _flags(flags, masked, skipna, sb_packed=packed, y_sb=keep_batch_fastest)
         return _apply_call("smm_apply_sb", self.handle, x, (max(ldx, 1),), y,
                            (max(y_shape[1], 1), n_batch, float(remap_area_min), fl, _stream_handle(stream)), y_res, cf,
                            cf_out)
@@ -392,9 +419,8 @@ class SparseOperator:
         nothing.  A chunk's X, planes and Y stay within 256 MiB and a quarter of the free device memory; chunk_rows > 0
         fixes the rows per chunk."""
         if gradients is not None:
-            return self._apply_host_cols(x, out, gradients, masked, remap_area_min, out_dtype,
-                                         int(flags) | (_lib.APPLY_SKIPNA if skipna else 0), int(chunk_rows), cf, cf_out,
-                                         half)
+            return self._apply_host_cols(x, out, gradients, masked, remap_area_min, out_dtype, _flags(flags, skipna=skipna),
+                                         int(chunk_rows), cf, cf_out, half)
         x = _host_field(x, cf, half)
         if x.ndim != 2 or x.shape[1] != self.n_src:
             raise ValueError(f"X must be (B, {self.n_src}), got {x.shape}")
@@ -406,7 +432,7 @@ class SparseOperator:
             out = result_cache.empty((n_batch, self.n_dst), y_res[0])      # page-locked and recycled when large
         if out.shape != (n_batch, self.n_dst) or not out.flags.c_contiguous:
             raise ValueError(f"out must be a C-contiguous ({n_batch}, {self.n_dst}) array")
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        fl = _flags(flags, masked, skipna)
         ldx = x.strides[0] // x.itemsize if n_batch > 1 else max(self.n_src, 1)
         return _apply_call("smm_apply_host", self.handle, x, (ldx,), out,
                            (self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows)), y_res, cf, cf_out, "out")
@@ -418,9 +444,9 @@ class SparseOperator:
         if np.dtype(out_dtype) != np.dtype(np.float64):
             raise ValueError("gradients= produces float64 results")
         self._check_rule(rule)
-        x = np.asarray(x)
-        if x.dtype not in (np.float32, np.float64):
-            x = x.astype(np.float64)      # result_type(x, f64), regrid.py:550
+        x = _host_field(x, None, False)
+        if x.dtype not in (np.float32, np.float64):      # `bfloat16`, which the other host entries ship as it is
+            x = x.astype(np.float64)
         if x.ndim != 2 or x.shape[1] != self.n_src:
             raise ValueError(f"X must be (B, {self.n_src}), got {x.shape}")
         x = np.ascontiguousarray(x)
@@ -495,9 +521,8 @@ class SparseOperator:
                                    flags=flags, stream=stream, bitmaps=bitmaps, skipna=skipna)
         n_batch = rows.size
         y = _grib.float64_result(y, (n_batch, self.n_dst), DeviceArray, "Y")
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
         _grib.call_grib("smm_apply_grib", self.handle, x_ptr, n_bytes, rows_p, bitmaps, n_batch, skipna, _ptr(y), _lib.SMM_F64,
-                        self.n_dst, n_batch, float(remap_area_min), fl, _stream_handle(stream))
+                        self.n_dst, n_batch, float(remap_area_min), _flags(flags, masked), _stream_handle(stream))
         return y
 
     def _apply_host_grib_coded(self, buf, rows, out, bitmaps, coded, chunk_rows, **apply_kw):
@@ -608,35 +633,24 @@ class SparseOperator:
             if codec_out is not None:
                 return self._apply_host_grib_out_coded(buf, rows, grib_out, bitmaps, coded, int(chunk_rows), **apply_kw)
             return self._apply_host_grib_coded(buf, rows, out, bitmaps, coded, int(chunk_rows), **apply_kw)
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
         if grib_out is not None:
             bitmaps, bm_p = (None, None) if bitmaps is None else _grib.grib_bitmaps(bitmaps, n_batch)
             return _grib.host_grib_out("smm_apply_host_grib_pk", self.handle, buf, rows_p, bm_p, grib_out, out,
                                        (n_batch, self.n_dst), n_batch, float(remap_area_min),
-                                       fl | (_lib.APPLY_SKIPNA if skipna else 0), int(chunk_rows))
+                                       _flags(flags, masked, skipna), int(chunk_rows))
         out = _grib.float64_result(out, (n_batch, self.n_dst), result_cache.empty, "out")
         _grib.call_grib("smm_apply_host_grib", self.handle, _cptr(buf), buf.size, rows_p, bitmaps, n_batch, skipna, _cptr(out),
-                        _lib.SMM_F64, self.n_dst, n_batch, float(remap_area_min), fl, int(chunk_rows))
+                        _lib.SMM_F64, self.n_dst, n_batch, float(remap_area_min), _flags(flags, masked), int(chunk_rows))
         return out
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.call("smm_operator_destroy", self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def __repr__(self):
         return (f"SparseOperator(S={self.n_src}, D={self.n_dst}, nnz={self.nnz}, "
                 f"device={self.device})")
 
 
-class OperatorGroup:
+class OperatorGroup(_Handle):
     """Ordered per-level operators applied in one launch (regrid.py:387-418)."""
+    _destroy = "smm_group_destroy"
 
     def __init__(self, operators):
         self.operators = list(operators)
@@ -700,21 +714,12 @@ class OperatorGroup:
         # the last axis may be a padded row pitch (>= S): rows that start on 128-B lines (a multiple
         # of 16 doubles / 32 floats) are staged without straddling lines
         n_outer, n_lev, n_inner, S = x.shape
-        D = self.n_dst
         lev, ml = self._level_args(level_index, masked_levels, n_lev)
-        if transpose:
-            shape = (n_outer, n_inner, n_lev, D)
-            ys = (n_inner * n_lev * D, D, n_lev * D)          # (outer, lev, inner) strides
-        else:
-            shape = (n_lev, n_outer, n_inner, D)
-            ys = (n_inner * D, n_outer * n_inner * D, D)
+        shape, ys = _level_result(n_outer, n_lev, n_inner, self.n_dst, transpose)
         y_res = result_dtype(out_dtype, cf_out)
-        if y is None:
-            y = DeviceArray(shape, y_res[0])
-        elif y.shape != shape:
-            raise ValueError(f"Y must be {shape}, got {y.shape}")
+        y = _device_result(y, shape, y_res[0])
         xs = (n_lev * n_inner * S, n_inner * S, S)
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        fl = _flags(flags, masked, skipna)
         return _apply_call("smm_group_apply", self.handle, x, xs, y,
                            (*ys, n_outer, n_lev, n_inner, _cptr(lev), _cptr(ml), float(remap_area_min), fl,
                             _stream_handle(stream)), y_res, cf, cf_out)
@@ -745,12 +750,8 @@ class OperatorGroup:
             shape = (B, n_lev, D) if transpose else (n_lev, B, D)
             ys_lev, ys_b = (D, n_lev * D) if transpose else (B * D, D)
         y_res = result_dtype(out_dtype, cf_out)
-        if y is None:
-            y = DeviceArray(shape, y_res[0], layout="sb" if keep_batch_fastest else "bs")
-        elif y.shape != shape:
-            raise ValueError(f"Y must be {shape}, got {y.shape}")
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
-        fl |= _lib.APPLY_SB_Y_SB if keep_batch_fastest else 0
+        y = _device_result(y, shape, y_res[0], "sb" if keep_batch_fastest else "bs")
+        fl = _flags(flags, masked, skipna, y_sb=keep_batch_fastest)
         return _apply_call("smm_group_apply_sb", self.handle, x, (S * max(ldx, 1), max(ldx, 1)), y,
                            (ys_lev, ys_b, B, n_lev, _cptr(lev), _cptr(ml), float(remap_area_min), fl,
                             _stream_handle(stream)), y_res, cf, cf_out)
@@ -770,10 +771,10 @@ class OperatorGroup:
             raise ValueError(f"X must be (n_outer, n_lev, n_inner, {self.n_src}), got {x.shape}")
         n_outer, n_lev, n_inner, _ = x.shape
         lev, ml = self._level_args(level_index, masked_levels, n_lev)
-        shape = (n_outer, n_inner, n_lev, self.n_dst) if transpose else (n_lev, n_outer, n_inner, self.n_dst)
+        shape, _ = _level_result(n_outer, n_lev, n_inner, self.n_dst, transpose)
         y_res = result_dtype(out_dtype, cf_out)
         out = result_cache.empty(shape, y_res[0])
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
+        fl = _flags(flags, masked, skipna)
         return _apply_call("smm_group_apply_host", self.handle, x, (), out,
                            (n_outer, n_lev, n_inner, int(bool(transpose)), _cptr(lev), _cptr(ml), float(remap_area_min),
                             fl, int(chunk_outer)), y_res, cf, cf_out, "out")
@@ -815,13 +816,9 @@ class OperatorGroup:
         (n_outer, n_lev, n_in), (rows, rows_p), (bm, bm_p), (lev, ml) = self._grib_args(rows, bitmaps, level_index,
                                                                                          masked_levels, n_inner)
         x_ptr, n_bytes = _grib.packed_bytes(x, x_bytes, "apply_grib", raw=True)
-        D = self.n_dst
-        if transpose:
-            shape, ys = (n_outer, n_in, n_lev, D), (n_in * n_lev * D, D, n_lev * D)     # (outer, lev, inner) strides
-        else:
-            shape, ys = (n_lev, n_outer, n_in, D), (n_in * D, n_outer * n_in * D, D)
+        shape, ys = _level_result(n_outer, n_lev, n_in, self.n_dst, transpose)
         y = _grib.float64_result(y, shape, DeviceArray, "Y")
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        fl = _flags(flags, masked)
         _lib.call("smm_group_apply_grib_na" if skipna else "smm_group_apply_grib", self.handle, x_ptr, n_bytes, rows_p, bm_p, _ptr(y), _lib.SMM_F64, *ys, n_outer,
                   n_lev, n_in, _cptr(lev), _cptr(ml), float(remap_area_min), fl, _stream_handle(stream))
         return y
@@ -849,25 +846,13 @@ class OperatorGroup:
             if not transpose:
                 raise ValueError("grib_out returns the rows in record order (n_outer, n_lev, n_inner): "
                                  "transpose=False does not go with it")
-            fl = int(flags) | (_lib.APPLY_MASKED if masked else 0) | (_lib.APPLY_SKIPNA if skipna else 0)
             return _grib.host_grib_out("smm_group_apply_host_grib_pk", self.handle, buf, rows_p, bm_p, grib_out, out,
                                        (n_outer, n_lev, n_in, self.n_dst), n_outer, n_lev, n_in, _cptr(lev), _cptr(ml),
-                                       float(remap_area_min), fl, int(chunk_outer))
-        shape = (n_outer, n_in, n_lev, self.n_dst) if transpose else (n_lev, n_outer, n_in, self.n_dst)
+                                       float(remap_area_min), _flags(flags, masked, skipna), int(chunk_outer))
+        shape, _ = _level_result(n_outer, n_lev, n_in, self.n_dst, transpose)
         out = _grib.float64_result(out, shape, result_cache.empty, "out")
-        fl = int(flags) | (_lib.APPLY_MASKED if masked else 0)
+        fl = _flags(flags, masked)
         _lib.call("smm_group_apply_host_grib_na" if skipna else "smm_group_apply_host_grib", self.handle, _cptr(buf), buf.size, rows_p, bm_p, _cptr(out), _lib.SMM_F64,
                   n_outer, n_lev, n_in, int(bool(transpose)), _cptr(lev), _cptr(ml), float(remap_area_min), fl,
                   int(chunk_outer))
         return out
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.call("smm_group_destroy", self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

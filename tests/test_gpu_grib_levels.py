@@ -11,6 +11,7 @@ import pytest
 from oracle import oracle
 from smmregrid_amd import (GRIB_BITMAP_DTYPE, GRIB_NO_BITMAP, CdoGenerate, DataArray, Dataset, GribField, OperatorGroup, Regridder,
                            SparseOperator, _lib, pinned_empty, to_device)
+from smmregrid_amd import road
 from smmregrid_amd.gridtype import GridType
 from smmregrid_amd.io import open_dataset
 from tests import grib_cases
@@ -479,17 +480,19 @@ def test_a_gribfield_whose_fields_are_not_ordered_by_level_is_decoded(hip, tmp_p
     path, var, _ = grib2_levels(tmp_path, np.random.default_rng(73), True)
     dec, raw = open_dataset(path), open_dataset(path, decode=False, bitmaps=True)
     mask_dim = "isobaricInhPa"
-    w3 = CdoGenerate(dec[var], "r12x6").weights(method="con", mask_dim=mask_dim)
-    rg = Regridder(weights=w3, packed=True, packed_levels=True, loglevel="INFO")
     dims = tuple(raw[var].dims)
     gt = GridType(dims=dims, extra_dims={"mask": [mask_dim]})
-    assert rg._grib_rows_by_level(dims, gt)
-    assert not rg._grib_rows_by_level(dims[2:] + dims[:2], gt) and not rg._grib_rows_by_level((dims[0],) + dims[2:], gt)
+    on = road.Switches.of(packed=True, packed_levels=True)
+
+    def way(d):
+        return road.decide(on, road.Facts(var, road.GRIB, np.float32, d, gt.horizontal_dims, mask_dim))
+    assert way(dims).source == road.RAW_GRIB and not way(dims).lines
+    assert way(dims[2:] + dims[:2]).source == road.DECODED and way((dims[0],) + dims[2:]).source == road.DECODED
     odd_dims = (dims[0], dims[2], dims[1], dims[3])
-    assert not rg._grib_rows_by_level(odd_dims, gt)
-    with caplog.at_level("INFO"):
-        out = rg._grib_or_decoded(DataArray(raw[var].data, dims=odd_dims, name=var), GridType(dims=odd_dims,
-                                                                                             extra_dims={"mask": [mask_dim]}))
-    lines = [r.getMessage() for r in caplog.records if "is decoded on the host" in r.getMessage()]
-    assert len(lines) == 1 and "not ordered (outer..., level, inner...)" in lines[0], lines
-    assert isinstance(out.data, np.ndarray) and np.array_equal(out.data.view(np.uint32), dec[var].values.view(np.uint32))
+    odd = way(odd_dims)
+    assert odd.source == road.DECODED
+    lines = [text for level, text in odd.lines if "is decoded on the host" in text]
+    assert len(lines) == 1 and odd.lines[0][0] == road.INFO and "not ordered (outer..., level, inner...)" in lines[0], lines
+    # the decode that road asks for: the bits of the decoded file
+    out = raw[var].data.decode()
+    assert isinstance(out, np.ndarray) and np.array_equal(out.view(np.uint32), dec[var].values.view(np.uint32))

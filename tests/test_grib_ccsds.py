@@ -256,20 +256,28 @@ def test_layout_and_host_decode_entries():
     assert status.value == _lib.GRIB_AEC_EXHAUSTED
 
 
+def grib_reason(dims, levels=False, out_dtype=np.float64, codec=None, mask_dim="isobaricInhPa", **switches):
+    """why `road.decide` sends a `GribField` with these dims to the host decoder, or None: it stays raw"""
+    from smmregrid_amd import road
+    horizontal = [d for d in dims if d in ("lat", "lon", "latitude", "longitude")]
+    way = road.decide(road.Switches.of(out_dtype=out_dtype, **switches),
+                      road.Facts("t", road.GRIB, np.float32, dims, horizontal, mask_dim if levels else None, codec=codec))
+    assert (way.source == road.RAW_GRIB) == (way.why is None) and way.source in (road.RAW_GRIB, road.DECODED)
+    return way.why
+
+
 def test_regridder_knows_why_a_ccsds_field_is_decoded():
-    """_grib_decode_reason: masked levels, grib_out and a non-float64 result send a CCSDS field to the host decoder."""
-    from smmregrid_amd import Regridder
-    rg = Regridder.__new__(Regridder)
-    rg.packed, rg.packed_levels, rg.skipna, rg.packed_skipna, rg.grib_out = True, True, False, False, False
+    """road.decide: masked levels, grib_out and a non-float64 result send a CCSDS field to the host decoder."""
+    on = dict(packed=True, packed_levels=True)
     dims = ("isobaricInhPa", "latitude", "longitude")
-    assert rg._grib_decode_reason(dims, None, np.float64, False, ccsds=True) is None
-    assert "CCSDS" in rg._grib_decode_reason(dims, None, np.float64, True, ccsds=True)
-    assert "float32" in rg._grib_decode_reason(dims, None, np.float32, False, ccsds=True)
-    rg.grib_out = True
-    assert "grib_out" in rg._grib_decode_reason(dims, None, np.float64, False, ccsds=True)
-    assert rg._grib_decode_reason(dims, None, np.float64, False, ccsds=False) is None
-    rg.skipna = True
-    assert rg._grib_decode_reason(dims, None, np.float64, False, ccsds=False) == "skipna"
+    assert grib_reason(dims, codec="ccsds", **on) is None
+    assert "CCSDS" in grib_reason(dims, levels=True, codec="ccsds", **on)
+    assert "float32" in grib_reason(dims, out_dtype=np.float32, codec="ccsds", **on)
+    on["grib_out"] = True
+    assert "grib_out" in grib_reason(dims, codec="ccsds", **on)
+    assert grib_reason(dims, **on) is None
+    on["skipna"] = True
+    assert grib_reason(dims, **on) == "skipna"
 
 
 # ------------------------------------------------------------------------------------------------ malformed streams

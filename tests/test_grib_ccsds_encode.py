@@ -257,14 +257,23 @@ def test_regridder_refuses_grib_out_ccsds_without_grib_out():
         Regridder(weights=object(), packed=True, grib_out_ccsds=True)
 
 
+def grib_reason(dims, levels=False, out_dtype=np.float64, codec=None, mask_dim="isobaricInhPa", **switches):
+    """why `road.decide` sends a `GribField` with these dims to the host decoder, or None: it stays raw"""
+    from smmregrid_amd import road
+    horizontal = [d for d in dims if d in ("lat", "lon", "latitude", "longitude")]
+    way = road.decide(road.Switches.of(out_dtype=out_dtype, **switches),
+                      road.Facts("t", road.GRIB, np.float32, dims, horizontal, mask_dim if levels else None, codec=codec))
+    assert (way.source == road.RAW_GRIB) == (way.why is None) and way.source in (road.RAW_GRIB, road.DECODED)
+    return way.why
+
+
 def test_regridder_keeps_a_ccsds_field_raw_only_with_grib_out_ccsds():
-    rg = Regridder.__new__(Regridder)
-    rg.packed, rg.packed_levels, rg.skipna, rg.packed_skipna, rg.grib_out, rg.grib_out_ccsds = True, True, False, False, True, False
+    on = dict(packed=True, packed_levels=True, grib_out=True)
     dims = ("isobaricInhPa", "latitude", "longitude")
-    assert "grib_out" in rg._grib_decode_reason(dims, None, np.float64, False, ccsds=True)
-    rg.grib_out_ccsds = True
-    assert rg._grib_decode_reason(dims, None, np.float64, False, ccsds=True) is None
-    assert "masked levels" in rg._grib_decode_reason(dims, None, np.float64, True, ccsds=True)
+    assert "grib_out" in grib_reason(dims, codec="ccsds", **on)
+    on["grib_out_ccsds"] = True
+    assert grib_reason(dims, codec="ccsds", **on) is None
+    assert "masked levels" in grib_reason(dims, levels=True, codec="ccsds", **on)
 
 
 # ------------------------------------------------------------------------------------------------ the stand-alone program

@@ -331,24 +331,32 @@ def test_host_decode_entry_refusals_and_statuses():
         griblite.cpx_decode(signed, c.record(0))
 
 
+def grib_reason(dims, levels=False, out_dtype=np.float64, codec=None, mask_dim="isobaricInhPa", **switches):
+    """why `road.decide` sends a `GribField` with these dims to the host decoder, or None: it stays raw"""
+    from smmregrid_amd import road
+    horizontal = [d for d in dims if d in ("lat", "lon", "latitude", "longitude")]
+    way = road.decide(road.Switches.of(out_dtype=out_dtype, **switches),
+                      road.Facts("t", road.GRIB, np.float32, dims, horizontal, mask_dim if levels else None, codec=codec))
+    assert (way.source == road.RAW_GRIB) == (way.why is None) and way.source in (road.RAW_GRIB, road.DECODED)
+    return way.why
+
+
 def test_regridder_knows_why_a_complex_packed_field_is_decoded():
-    """_grib_decode_reason: masked levels, grib_out and a non-float64 result send a complex-packed field to the host."""
-    from smmregrid_amd import Regridder
-    rg = Regridder.__new__(Regridder)
-    rg.packed, rg.packed_levels, rg.skipna, rg.packed_skipna, rg.grib_out, rg.grib_out_ccsds = True, True, False, False, False, False
+    """road.decide: masked levels, grib_out and a non-float64 result send a complex-packed field to the host."""
+    on = dict(packed=True, packed_levels=True)
     dims = ("isobaricInhPa", "latitude", "longitude")
-    assert rg._grib_decode_reason(dims, None, np.float64, False, cpx=True) is None
-    assert "complex packing" in rg._grib_decode_reason(dims, None, np.float64, True, cpx=True)
-    assert "float32" in rg._grib_decode_reason(dims, None, np.float32, False, cpx=True)
-    rg.grib_out = True
-    assert "grib_out" in rg._grib_decode_reason(dims, None, np.float64, False, cpx=True)
-    rg.grib_out_ccsds = True
-    assert "grib_out" in rg._grib_decode_reason(dims, None, np.float64, False, cpx=True)
-    assert rg._grib_decode_reason(dims, None, np.float64, False) is None
-    rg.grib_out, rg.skipna = False, True
-    assert rg._grib_decode_reason(dims, None, np.float64, False, cpx=True) == "skipna"
-    rg.packed_skipna = True
-    assert rg._grib_decode_reason(dims, None, np.float64, False, cpx=True) is None
+    assert grib_reason(dims, codec="cpx", **on) is None
+    assert "complex packing" in grib_reason(dims, levels=True, codec="cpx", **on)
+    assert "float32" in grib_reason(dims, out_dtype=np.float32, codec="cpx", **on)
+    on["grib_out"] = True
+    assert "grib_out" in grib_reason(dims, codec="cpx", **on)
+    on["grib_out_ccsds"] = True
+    assert "grib_out" in grib_reason(dims, codec="cpx", **on)
+    assert grib_reason(dims, **on) is None
+    on.update(grib_out=False, skipna=True)
+    assert grib_reason(dims, codec="cpx", **on) == "skipna"
+    on["packed_skipna"] = True
+    assert grib_reason(dims, codec="cpx", **on) is None
 
 
 def test_operator_refuses_cpx_with_ccsds_or_grib_out_before_any_device():

@@ -226,15 +226,22 @@ def test_regridder_packed_skipna_needs_packed_and_skipna():
         Regridder(weights=object(), packed_levels=True, packed_skipna=True, skipna=True)
 
 
+def grib_reason(dims, levels=False, out_dtype=np.float64, codec=None, mask_dim="isobaricInhPa", **switches):
+    """why `road.decide` sends a `GribField` with these dims to the host decoder, or None: it stays raw"""
+    from smmregrid_amd import road
+    horizontal = [d for d in dims if d in ("lat", "lon", "latitude", "longitude")]
+    way = road.decide(road.Switches.of(out_dtype=out_dtype, **switches),
+                      road.Facts("t", road.GRIB, np.float32, dims, horizontal, mask_dim if levels else None, codec=codec))
+    assert (way.source == road.RAW_GRIB) == (way.why is None) and way.source in (road.RAW_GRIB, road.DECODED)
+    return way.why
+
+
 def test_regridder_decides_the_raw_road_in_one_place():
-    """`_grib_decode_reason`, which `_grib_or_decoded` and the guards of `apply_weights` and `regrid3d` share: skipna
-    decodes on the host unless packed_skipna is on; the other fallbacks keep their reason either way."""
-    def reason(levels=False, out_dtype=np.float64, **kw):
-        r = Regridder.__new__(Regridder)
-        r.packed, r.packed_levels, r.skipna, r.packed_skipna = (kw.get(k, False) for k in
-                                                                ("packed", "packed_levels", "skipna", "packed_skipna"))
-        r._grib_rows_by_level = lambda dims, gridtype: kw.get("by_level", True)
-        return r._grib_decode_reason(("time", "lat", "lon"), None, out_dtype, levels)
+    """`road.decide`, which `regrid_array` and direct calls of `apply_weights` and `regrid3d` share: skipna decodes on
+    the host unless packed_skipna is on; the other fallbacks keep their reason either way."""
+    def reason(levels=False, out_dtype=np.float64, by_level=True, **kw):
+        dims = ("time", "lat", "lon") if not levels else ("time", "lev", "lat", "lon") if by_level else ("time", "lat", "lev", "lon")
+        return grib_reason(dims, levels, out_dtype, mask_dim="lev", **kw)
 
     assert reason(packed=True) is None
     assert reason() is not None
