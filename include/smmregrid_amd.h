@@ -1109,7 +1109,9 @@ int smm_gradients(smm_grad_plan_t plan, const void* x, int x_dtype, int64_t ldx,
  * The result is bit for bit what smm_apply gives with SMM_APPLY_KERNEL_SELL on the "stacked" operator -- K * n_src
  * source cells, link (d, s, k) at source index s * K + k -- and the stacked float64 field X[b, s * K + k], k = 0 holding
  * f filled with its own dtype's 1e20 and widened, k >= 1 plane k.  SMM_APPLY_MASKED and SMM_APPLY_NO_FILL work as for
- * smm_apply; SMM_APPLY_KERNEL_SELL is accepted (it is the kernel that runs).
+ * smm_apply (unfilled, a non-finite f enters through the links of its own rows alone, as on the stacked operator);
+ * SMM_APPLY_KERNEL_SELL is accepted (it is the kernel that runs).  A launch grid the rounds were not planned to fit is
+ * SMM_ERR_INVALID, never launched.
  * Built: SMM_F32 and SMM_F64 fields to SMM_F64 results in the native (B, S) layout.  SMM_ERR_UNSUPPORTED, checked
  * before the handles are looked at: SMM_APPLY_SKIPNA, SMM_APPLY_KERNEL_TILE, the batch-fastest and host-pack flags,
  * packed / half x_dtype (GRIB fields have no entry of this kind), any y_dtype but SMM_F64.  Level groups have no

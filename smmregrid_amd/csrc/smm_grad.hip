@@ -151,10 +151,14 @@ __global__ __launch_bounds__(kThreads) void smm_apply_cols_kernel(ColsArgs a, bo
     w[0] = vp[(int64_t)k * 64];
 #pragma unroll
     for (int q = 1; q < K; ++q) w[q] = xp[(int64_t)(q - 1) * a.n_slots + (int64_t)k * 64];
+    // unfilled (SMM_APPLY_NO_FILL) a padded slot must not see f: it repeats the row's last column, and +0.0 * inf is NaN
+    // where the row's own links give -inf.  The planes are finite, as the stacked operator's last column is.
+    const bool pad = !fill && k >= len;
     double v[BT][K];
 #pragma unroll
     for (int t = 0; t < BT; ++t) {
-      v[t][0] = load_fixed(xr[t] + c, fill);
+      const double f = load_fixed(xr[t] + c, fill);
+      v[t][0] = pad ? 0.0 : f;
 #pragma unroll
       for (int q = 1; q < K; ++q) v[t][q] = load_fixed(gr[t] + (int64_t)(q - 1) * a.g_ld_plane + c, fill);
     }
@@ -184,6 +188,14 @@ __global__ __launch_bounds__(kThreads) void smm_apply_cols_kernel(ColsArgs a, bo
 
 int cols_batch_rows(int64_t n_j) { return n_j >= 4 ? 4 : (n_j >= 2 ? 2 : 1); }
 
+// Workgroups of one gather launch of n_j batch rows.  Not monotonic in n_j: three rows take two j-tiles, four take one.
+int64_t cols_blocks(int64_t n_dblocks, int64_t n_j) {
+  const int bt = cols_batch_rows(n_j);
+  return n_dblocks * ((n_j + bt - 1) / bt);
+}
+
+int64_t cols_grid_limit() { return std::min<int64_t>(grid_limit(), 0x7fffffffLL); }
+
 template <typename XT, int K>
 int launch_cols(ColsArgs a, bool fill, hipStream_t s) {
   auto go = [&](auto bt_tag) -> int {
@@ -191,6 +203,9 @@ int launch_cols(ColsArgs a, bool fill, hipStream_t s) {
     a.n_jtiles = (a.n_j + BT - 1) / BT;
     const int64_t total = a.n_dblocks * a.n_jtiles;
     if (total <= 0) return SMM_OK;
+    if (total > cols_grid_limit())   // the rounds are planned to fit: a slip there is a status, not a launch
+      return fail(SMM_ERR_INVALID, "a gather launch of " + std::to_string(a.n_j) + " batch rows needs " + std::to_string(total) +
+                                       " workgroups, beyond the launch grid of " + std::to_string(cols_grid_limit()));
     hipLaunchKernelGGL((smm_apply_cols_kernel<XT, K, BT>), dim3((unsigned)total), dim3(kThreads), 0, s, a, fill);
     SMM_HIP(hipGetLastError());
     return SMM_OK;
@@ -407,12 +422,17 @@ int smm_apply_cols(smm_operator_t op, smm_grad_plan_t plan, const void* x, int x
     a.area_min = remap_area_min;
     a.masked = (flags & SMM_APPLY_MASKED) ? 1 : 0;
     const bool fill = !(flags & SMM_APPLY_NO_FILL);
-    const int64_t limit = std::min<int64_t>(grid_limit(), 0x7fffffffLL);
+    const int64_t limit = cols_grid_limit();
     if (a.n_dblocks > limit)
       return fail(SMM_ERR_INVALID, "one batch row alone needs a launch grid beyond " + std::to_string(limit) + " workgroups");
-    // rows per round: what the scratch holds, and what one gather launch may carry
+    // rows per round: what the scratch holds, and what one gather launch may carry -- the full rounds and the shorter
+    // last one, which may block fewer batch rows per thread and so need the larger grid
     int64_t rows = (int64_t)std::min<size_t>(scratch_bytes / per_row, (size_t)n_batch);
-    while (rows > 1 && a.n_dblocks * ((rows + cols_batch_rows(rows) - 1) / cols_batch_rows(rows)) > limit) rows = (rows + 1) / 2;
+    auto fits = [&](int64_t r) {
+      const int64_t tail = n_batch % r;
+      return cols_blocks(a.n_dblocks, r) <= limit && (tail == 0 || cols_blocks(a.n_dblocks, tail) <= limit);
+    };
+    while (rows > 1 && !fits(rows)) rows = (rows + 1) / 2;
     for (int64_t r0 = 0; r0 < n_batch; r0 += rows) {
       const int64_t nr = std::min(rows, n_batch - r0);
       const char* xr = (const char*)x + (size_t)(r0 * ldx) * xsz;

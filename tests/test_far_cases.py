@@ -31,10 +31,18 @@ def _layouts(name):
         lx, ly = fc.rows_layout(3, S, M, G, inner=2)[0], fc.rows_layout(3, D, M, G, inner=2)[0]
         bb = np.arange(6)[:, None]
         return lx, ly, np.asarray(lx.offsets)[bb] + s, np.asarray(ly.offsets)[bb] + d
+    if name == "grad-rows":                    # G of smm_gradients: 3 far batch rows of 3 near planes each
+        lx, ly = fc.rows_layout(3, S, M, G, inner=3)[0], fc.rows_layout(3, D, M, G, inner=3)[0]
+        bb = np.arange(9)[:, None]
+        return lx, ly, np.asarray(lx.offsets)[bb] + s, np.asarray(ly.offsets)[bb] + d
+    if name == "grad-planes":                  # ... and one batch row whose 3 planes lie far apart
+        lx, ly = fc.rows_layout(3, S, M, G)[0], fc.rows_layout(3, D, M, G)[0]
+        bb = np.arange(3)[:, None]
+        return lx, ly, np.asarray(lx.offsets)[bb] + s, np.asarray(ly.offsets)[bb] + d
     raise KeyError(name)
 
 
-LAYOUTS = ("row-major", "batch-fastest", "batch-fastest-x", "levels")
+LAYOUTS = ("row-major", "batch-fastest", "batch-fastest-x", "levels", "grad-rows", "grad-planes")
 
 
 def _row_starts(layout, off):
@@ -108,13 +116,58 @@ def test_a_wrapped_write_is_caught(name, dt, kind):
         wins()                                  # and the alias window names the truncation
 
 
+@pytest.mark.parametrize("kind", (None,) + fc.TRUNCATIONS)
+@pytest.mark.parametrize("which", ["ld_row", "ld_plane"])
+def test_a_narrowed_gradient_stride_is_caught(which, kind):
+    """smm_gradients writes plane p of batch row b at g + b * ld_row + p * ld_plane from the pointer to row 0.  Here one
+    of the two products alone is narrowed, in the layouts of tests/test_gpu_gradients_far_offsets.py: 3 rows of 3 near
+    planes on a far `ld_row`; one row of 3 planes on a far `ld_plane`."""
+    n_planes = 3
+    if which == "ld_row":
+        n_batch = 3
+        lay, ld_row = fc.rows_layout(n_batch, S, M, G, inner=n_planes)
+        ld_plane = lay.offsets[1] - lay.offsets[0]
+    else:
+        n_batch = 1
+        lay, ld_plane = fc.rows_layout(n_planes, S, M, G)
+        ld_row = n_planes * ld_plane
+    rng = np.random.default_rng(6)
+    want = rng.standard_normal((n_batch * n_planes, S))
+    ybuf = np.frombuffer(bytes([fc.SENTINEL]) * (lay.size * 8), dtype=np.float64).copy()
+    for b in range(n_batch):
+        for p in range(n_planes):
+            far_part, near_part = (b * ld_row, p * ld_plane) if which == "ld_row" else (p * ld_plane, b * ld_row)
+            assert lay.offsets[0] + far_part + near_part == lay.offsets[b * n_planes + p]
+            at = lay.offsets[0] + (far_part if kind is None else fc.truncate(far_part, 8, kind, M)) + near_part
+            if 0 <= at and at + S <= lay.size:             # elsewhere: a fault on the device
+                ybuf[at:at + S] = want[b * n_planes + p]
+
+    def rows():
+        fc.check_rows(np.stack([ybuf[o:o + S] for o in lay.offsets]), want, which)
+
+    def wins():
+        fc.check_windows(lambda s, e: ybuf[s:e], lay, 8, which)
+
+    if kind is None:
+        rows()
+        wins()
+    else:
+        with pytest.raises(AssertionError, match="differ in their bits"):
+            rows()
+        with pytest.raises(AssertionError, match=kind):
+            wins()
+
+
 SMALL = [(M, G, s) for s in ((5, 25, 1), (5, 24, 1), (9, 25, 1), (25, 3, 1), (24, 3, 1), (3, 24, 1), (3, 25, 2))]
 FULL = [(fc.MODULUS, fc.GUARD, s) for s in ((5, 1040, 1), (9, 4000, 1), (36, 131, 1), (3, 805, 1), (131, 36, 1),
-                                            (3, 1040, 2), (3, 36 * 136, 1))]
+                                            (3, 1040, 2), (3, 36 * 136, 1),
+                                            # the gradient cases: 257 x 33 cells, planes of 2 and 3, results of 300
+                                            (5, 8481, 1), (3, 8481, 1), (3, 8481, 2), (3, 8481, 3), (5, 300, 1))]
+GRAD_SMALL = [(M, G, (3, 25, 3))]              # appended last: the ids of the cases above keep their numbers
 
 
 @pytest.mark.parametrize("itemsize", (1, 2, 4, 8))
-@pytest.mark.parametrize("modulus,guard,shape", SMALL + FULL)
+@pytest.mark.parametrize("modulus,guard,shape", SMALL + FULL + GRAD_SMALL)
 def test_windows_never_overlap_a_true_row(shape, itemsize, modulus, guard):
     n_rows, row_len, inner = shape
     lay, ld = fc.rows_layout(n_rows, row_len, modulus, guard, inner=inner)
