@@ -119,7 +119,8 @@ __global__ __launch_bounds__(kWave) void smm_grib_aec_parse_kernel(AecArgs a, in
         // FS-coded samples: split-sample (k = ID - 1, J - nref codes) or second extension (J / 2 codes, no remainders)
         const uint32_t k = low ? 0u : id - 1u, nc = low ? J / 2 : J - nref;
         if (nc * k >= block_bits) {
-          status = smm_aec::kInvalid;
+          // no block has such a k -- but an ID or reference sample that the stream's end cuts is read from what lies behind
+          status = p > bit_end ? smm_aec::kExhausted : smm_aec::kInvalid;
           break;
         }
         const uint32_t limit = block_bits - nc * k;   // rule 1: the FS codes end within this many bits
@@ -135,10 +136,7 @@ __global__ __launch_bounds__(kWave) void smm_grib_aec_parse_kernel(AecArgs a, in
         const uint32_t cnt = (uint32_t)__builtin_popcount(chunk);
         const uint32_t incl = wave_scan(cnt);
         const uint32_t total = __shfl(incl, kWave - 1, kWave);
-        if (total < nc) {   // the nc-th terminating one is not there
-          status = p + limit > bit_end ? smm_aec::kExhausted : smm_aec::kInvalid;
-          break;
-        }
+        const uint32_t have = total < nc ? total : nc;   // codes whose terminating one is there
         // the positions of the first nc ones, in order: lane l's start at rank incl - cnt
         uint32_t idx = incl - cnt;
         while (chunk != 0u && idx < nc) {
@@ -147,14 +145,24 @@ __global__ __launch_bounds__(kWave) void smm_grib_aec_parse_kernel(AecArgs a, in
           chunk &= ~(0x80000000u >> z);
         }
         __syncthreads();
-        const uint32_t fs_end = ones[nc - 1] + 1u;
         uint32_t fs = 0;
-        if (lane < nc) fs = ones[lane] - (lane ? ones[lane - 1] + 1u : 0u);
+        if (lane < have) fs = ones[lane] - (lane ? ones[lane - 1] + 1u : 0u);
         if (low) {
-          if (__any(lane < nc && fs > smm_aec::kMaxSecondExt)) {
-            status = p + fs_end > bit_end ? smm_aec::kExhausted : smm_aec::kInvalid;
+          // the first value above the largest decides, as in decode_row, which takes the codes in order: it is invalid
+          // where its code ends inside the stream, whatever becomes of the codes behind it
+          const unsigned long long over = __ballot(lane < have && fs > smm_aec::kMaxSecondExt);
+          if (over != 0ull) {
+            const uint32_t first = (uint32_t)__builtin_ctzll(over);
+            status = p + ones[first] + 1u > bit_end ? smm_aec::kExhausted : smm_aec::kInvalid;
             break;
           }
+        }
+        if (total < nc) {   // the nc-th terminating one is not there
+          status = p + limit > bit_end ? smm_aec::kExhausted : smm_aec::kInvalid;
+          break;
+        }
+        const uint32_t fs_end = ones[nc - 1] + 1u;
+        if (low) {
           if (lane < nc) {
             uint32_t pa, pb;
             smm_aec::second_ext_pair(fs, &pa, &pb);

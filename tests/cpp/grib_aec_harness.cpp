@@ -2,10 +2,13 @@
 // encoder wrote: every fixture truncated at every byte, and with single bytes corrupted.  The stream always sits in a heap
 // block of exactly its bytes (at offset 0 and at the odd offset 3), so a read past its end is a sanitizer report; every
 // run must end with one of the three statuses, and a run that ends ok on a truncated stream must still give the
-// fixture's integers (only pad bits were cut).  tests/test_grib_ccsds.py writes the case file and runs this program.
+// fixture's integers (only pad bits were cut).  A case may be malformed as it stands (the forced streams of
+// tests/ccsds_forced_cases.py, group G): its whole stream must then end with the status the case names and leave the
+// values the case holds -- the samples up to the failing block, zeros from there on.  tests/test_grib_ccsds.py writes
+// the case file and runs this program.
 //
-// case file: int64 n_cases, then per case  int64 {n_values, nbits, block, rsi, preprocess, stream bytes},
-// the stream, the expected uint32 values.
+// case file: int64 n_cases, then per case  int64 {n_values, nbits, block, rsi, preprocess, stream bytes, the status of
+// the whole stream}, the stream, the expected uint32 values.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -38,8 +41,9 @@ int main(int argc, char** argv) {
   int64_t n_cases = 0;
   if (fread(&n_cases, 8, 1, f) != 1) return fail("short case file", -1, 0);
   for (int64_t c = 0; c < n_cases; ++c) {
-    int64_t h[6];
-    if (fread(h, 8, 6, f) != 6) return fail("short case header", c, 0);
+    int64_t h[7];
+    if (fread(h, 8, 7, f) != 7) return fail("short case header", c, 0);
+    const int expect = (int)h[6];
     std::vector<uint8_t> stream((size_t)h[5]);
     std::vector<uint32_t> want((size_t)h[0]), got((size_t)h[0] + 1);
     if (fread(stream.data(), 1, stream.size(), f) != stream.size()) return fail("short stream", c, 0);
@@ -58,14 +62,15 @@ int main(int argc, char** argv) {
         return fail("ended ok with other integers", c, at);
       return 0;
     };
-    // whole, at both offsets: ok and equal
+    // whole, at both offsets: the status expected (ok for a fixture) and the values expected
     for (size_t off : {(size_t)0, (size_t)3}) {
       if (run(stream.data(), stream.size(), off, true, -1)) return 1;
-      if (counts[smm_aec::kOk] != runs) return fail("the whole stream does not end ok", c, (long)off);
+      if (counts[expect] != runs) return fail("the whole stream does not end with the status expected", c, (long)off);
+      if (memcmp(got.data(), want.data(), want.size() * 4) != 0) return fail("the whole stream leaves other integers", c, (long)off);
     }
     // truncated at every byte
     for (size_t len = 0; len < stream.size(); ++len)
-      if (run(stream.data(), len, len & 1 ? 3 : 0, true, (long)len)) return 1;
+      if (run(stream.data(), len, len & 1 ? 3 : 0, expect == smm_aec::kOk, (long)len)) return 1;
     // single bytes corrupted: every byte of a short stream, some 500 spread over a long one
     const size_t step = stream.size() / 500 + 1;
     std::vector<uint8_t> bad(stream);

@@ -1,7 +1,8 @@
 """CCSDS-packed GRIB-2 fields on the GPU (smm_grib_aec_unpack; `grib_unpack`, `apply_grib(ccsds=)`,
 `apply_host_grib(ccsds=)`, `Regridder(packed=True)` on a CCSDS variable).  Every comparison is bit for bit: against
 the fixtures' integers (tests/golden/ccsds, written by libaec's encoder) and against the same call on the simple-packed
-twin of those integers.  Malformed streams are the business of tests/test_grib_ccsds.py."""
+twin of those integers.  Streams whose options the test chose, and malformed streams on the device, are the business of
+tests/test_gpu_grib_ccsds_forced.py; malformed streams on the host that of tests/test_grib_ccsds.py."""
 import numpy as np
 import pytest
 

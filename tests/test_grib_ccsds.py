@@ -290,19 +290,27 @@ def harness(tmp_path_factory):
 
 
 def test_truncated_and_corrupted_streams_end_with_a_status_and_no_sanitizer_report(harness, tmp_path):
-    """Malformed streams are tested here only: the GPU kernels take the options apart with the same functions."""
+    """Every fixture, and behind them the malformed forced streams of tests/ccsds_forced_cases.py (group G): those end
+    with the status the case names as they stand, and are cut and corrupted like the fixtures.  The device kernel meets
+    the G streams in tests/test_gpu_grib_ccsds_forced.py."""
+    from tests import ccsds_forced_cases as fc
+    forced = fc.group("G")
     path = str(tmp_path / "cases.bin")
     with open(path, "wb") as fh:
-        fh.write(np.int64(len(FIXTURES)).tobytes())
-        for fx in FIXTURES:
-            fh.write(np.array([fx.n_values, fx.nbits, fx.block, fx.rsi, int(fx.preprocess), fx.stream.size], np.int64).tobytes())
+        fh.write(np.int64(len(FIXTURES) + len(forced)).tobytes())
+        for i, fx in enumerate(FIXTURES + forced):
+            status = fx.meta["status"] if i >= len(FIXTURES) else _lib.GRIB_AEC_OK
+            fh.write(np.array([fx.n_values, fx.nbits, fx.block, fx.rsi, int(fx.preprocess), fx.stream.size, status], np.int64).tobytes())
             fh.write(fx.stream.tobytes())
             fh.write(fx.values.astype(np.uint32).tobytes())
     out = subprocess.run([harness, path], capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     lines = [ln.split() for ln in out.stdout.splitlines() if ln.startswith("case ")]
-    assert len(lines) == len(FIXTURES)
+    assert len(lines) == len(FIXTURES) + len(forced)
+    for g, ln in zip(forced, lines[len(FIXTURES):]):
+        runs, ok, exhausted, invalid = int(ln[3]), int(ln[5]), int(ln[7]), int(ln[9])
+        assert runs == ok + exhausted + invalid and runs >= 2 + g.stream.size, (g, ln)
     for fx, ln in zip(FIXTURES, lines):
         runs, ok, exhausted, invalid = int(ln[3]), int(ln[5]), int(ln[7]), int(ln[9])
         assert runs == ok + exhausted + invalid and runs >= 2 + fx.stream.size
