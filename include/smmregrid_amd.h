@@ -1121,6 +1121,67 @@ int smm_apply_cols(smm_operator_t op, smm_grad_plan_t plan, const void* x, int x
                    size_t scratch_bytes, void* stream);
 int smm_apply_cols_scratch(smm_operator_t op, int64_t n_batch, size_t* bytes);
 
+/* ------------------------------------------- categorical fields (opt-in, beyond the reference)
+ *
+ * Every entry above is a weighted sum of source values.  That is wrong for a field of class codes -- land cover, soil
+ * and vegetation type, masks, precipitation type: classes 3 and 7 do not average to 5.  smm_apply_mode stores, per
+ * destination cell, the class that covers the largest summed share of it ("largest area fraction").  This is CDO's
+ * remaplaf as recalled; it is not pinned against a cdo run.  The rule depends on the values, so no weights file
+ * expresses it: weights made with method "laf" hold one link per target cell, to the single source cell of largest
+ * overlap -- a static approximation.  Meant for conservative weights; on one-link rows it is the identity on the link.
+ *
+ * The rule (stated in numpy by smmregrid_amd.categorical.ModeRule), for destination row d, batch row b and the links k
+ * of the canonical CSR in ascending source order, w_k the weight of column 0:
+ *   missing  For SMM_F32 / SMM_F64, x[b, col_k] is missing when it is not finite; for SMM_I16 / SMM_U16 when it equals
+ *            one of the first n_fill entries of fill[2], compared on the raw integer.  A missing link takes part in no
+ *            class.
+ *   classes  Two links are of one class when their values compare equal with == (so -0.0 and +0.0 are one class); a
+ *            class is represented by the value of its first link.  share(c) is the sum of w_k over the links of class
+ *            c: float64, from +0.0, in ascending link order, one add per link -- the bits of smm_apply on the float64
+ *            indicator field x == c (w * 1.0 is w, w * 0.0 is +-0, and a sum that starts at +0.0 is never -0.0).
+ *   row sums tot = the sum of w_k over all links of the row, val = the same over the links that are not missing, both
+ *            in that order from +0.0: a row without a missing link has val bit-equal to tot.
+ *   winner   The class of the largest share, which must be > 0.0.  Bit-equal shares: the class whose first link comes
+ *            first wins (walk the first links in order, replace the best on a strictly greater share only).
+ *   dead     A row is dead when it is masked (SMM_APPLY_MASKED and dst_imask[d] == 0), when no class has a share > 0
+ *            (no links, all missing, all weights <= 0), or when remap_area_min > 0 and
+ *            frac_d * (val / tot) < remap_area_min, frac_d = dst_frac[d].  remap_area_min > 0 without dst_frac, and
+ *            MASKED without dst_imask, are refused as smm_apply with SMM_APPLY_SKIPNA refuses them.
+ *   result   y[b, d], of the field's own type, holds the winner's representative value bit for bit; a dead row NaN
+ *            (floats) or fill_out (integers).  share[b, d] (optional, float64) holds the winner's share as summed
+ *            above, not divided by anything; a dead row +0.0.
+ * There is no 1e20 fill, no > 1e19 test and no SMM_APPLY_NO_FILL; the rule works for any weights.
+ */
+typedef struct smm_mode_rule_t {
+  int32_t n_fill;     /* 0..2: how many entries of fill are missing values */
+  int32_t fill[2];    /* raw integers of the field's type */
+  int32_t fill_out;   /* what a dead row stores */
+  int32_t reserved;   /* 0 */
+} smm_mode_rule_t;
+
+/* x device (n_batch, ldx >= n_src) of x_dtype SMM_F32 / SMM_F64 / SMM_I16 / SMM_U16; y device (n_batch, ldy >= n_dst)
+ * of the same type; share device double (n_batch, ld_share >= n_dst) or NULL; rule NULL for float fields, required for
+ * integer ones.  Native (B, S) layout, stream-ordered, allocates nothing.  An operator from smm_operator_create_cols
+ * works through its column 0.
+ * The kernel walks the operator's SELL-64 tables, one destination row per lane: a slice's values are gathered once into
+ * LDS and the class scan -- O(links * distinct classes) per row -- runs from there; a slice with more slots than the
+ * LDS holds (smm_mode_launch_info) gathers from x again inside the scan, which is right for any length and slow.
+ * flags: SMM_APPLY_MASKED; SMM_APPLY_KERNEL_SELL is accepted (it is the kernel that runs); unknown bits are
+ * SMM_ERR_INVALID.  SMM_ERR_UNSUPPORTED, checked before the handles are looked at: SMM_APPLY_SKIPNA, SMM_APPLY_NO_FILL,
+ * SMM_APPLY_KERNEL_TILE, the batch-fastest and host-pack flags, SMM_F16 / SMM_BF16 and any other x_dtype.
+ * SMM_ERR_INVALID, before any device is touched: a rule with a float field or an integer field without one, n_fill
+ * outside 0..2, a fill or fill_out the raw type cannot hold, reserved != 0, ldx < n_src, ldy < n_dst, ld_share < n_dst,
+ * misaligned pointers, a negative n_batch.  Level groups, batch-fastest fields and host buffers have no such entry. */
+int smm_apply_mode(smm_operator_t op, const void* x, int x_dtype, int64_t ldx, void* y, int64_t ldy, double* share,
+                   int64_t ld_share, int64_t n_batch, double remap_area_min, unsigned flags, const smm_mode_rule_t* rule,
+                   void* stream);
+/* How smm_apply_mode would run op for fields of x_dtype (nothing is launched; every out pointer may be NULL): capacity =
+ * the most slots of a slice the LDS form takes (it depends on x_dtype alone: op may then be NULL); lds_slots = the slots
+ * per wave a launch asks for, min(capacity, the operator's longest row), and lds_bytes what that is per workgroup;
+ * n_lds_slices / n_global_slices = the slices that take each form. */
+int smm_mode_launch_info(smm_operator_t op, int x_dtype, int* capacity, int* lds_slots, int64_t* lds_bytes,
+                         int64_t* n_lds_slices, int64_t* n_global_slices);
+
 /* Test hook of the two host pipelines' error path: chunk number `chunk` (0-based) of every following
  * smm_apply_host / smm_group_apply_host call fails with SMM_ERR_HIP before its copies are queued;
  * chunk < 0 (the initial state) switches it off.  Process-wide; for tests only. */

@@ -10,6 +10,7 @@ from .device import (CFDecode, CFEncode, DeviceArray, bfloat16, from_bfloat16, g
                      to_bfloat16, to_device)
 from .xrlite import DataArray, Dataset
 from .gradients import GradientRule
+from .categorical import ModeRule
 from .griblite import GRIB_AEC_DTYPE, GRIB_BITMAP_DTYPE, GRIB_CPX_DTYPE, GRIB_ENCODE_DTYPE, GRIB_NO_BITMAP, GRIB_ROW_DTYPE, GribEncode, GribField, aec_encode, cpx_encode
 
 __version__ = '0.1.0'
@@ -20,4 +21,4 @@ __all__ = ["Regridder", "regrid", "CdoGenerate", "cdo_generate_weights", "GridTy
            "GRIB_BITMAP_DTYPE", "GRIB_NO_BITMAP", "GRIB_ENCODE_DTYPE", "GribEncode", "grib_pack",
            "GRIB_AEC_DTYPE", "grib_unpack", "grib_aec_pack", "aec_encode",
            "GRIB_CPX_DTYPE", "grib_unpack_cpx", "grib_unpack_cpx_mv", "grib_cpx_pack", "cpx_encode",
-           "GradientRule"]
+           "GradientRule", "ModeRule"]

@@ -134,6 +134,15 @@ class GribCpxStruct(ctypes.Structure):
 
 
 _gcp = ctypes.POINTER(GribCpxStruct)
+
+
+class ModeRuleStruct(ctypes.Structure):
+    """smm_mode_rule_t: the missing values of an integer class field and what a dead row stores"""
+    _fields_ = [("n_fill", ctypes.c_int32), ("fill", ctypes.c_int32 * 2), ("fill_out", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+_mrp = ctypes.POINTER(ModeRuleStruct)
 GRIB_CPX_OK, GRIB_CPX_EXHAUSTED, GRIB_CPX_INVALID = 0, 1, 2
 GRIB_CPX_SIMPLE = -1      # smm_grib_cpx_t.order of a row that is simple-packed already
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -257,6 +266,9 @@ SIGNATURES = {
     "smm_gradients": [_p, _p, _int, _i64, _p, _i64, _i64, _i64, _p],
     "smm_apply_cols": [_p, _p, _p, _int, _i64, _p, _int, _i64, _i64, _dbl, _uint, _p, _size, _p],
     "smm_apply_cols_scratch": [_p, _i64, ctypes.POINTER(_size)],
+    "smm_apply_mode": [_p, _p, _int, _i64, _p, _i64, _p, _i64, _i64, _dbl, _uint, _mrp, _p],
+    "smm_mode_launch_info": [_p, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_i64),
+                             ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     "smm_debug_fail_at_chunk": [_i64],
     "smm_debug_host_stats": [ctypes.POINTER(_dbl), _int, _int],
     "smm_debug_staging_faults": [_int, _i64],

@@ -289,6 +289,116 @@ class SparseOperator(_Handle):
         y._scratch = scratch      # the gather may still be reading it when this returns
         return y
 
+    # ------------------------------------------------------------------ categorical fields (largest area fraction)
+    _MODE_CODES = {np.dtype(np.float32): _lib.SMM_F32, np.dtype(np.float64): _lib.SMM_F64,
+                   np.dtype(np.int16): _lib.SMM_I16, np.dtype(np.uint16): _lib.SMM_U16}
+
+    def _mode_code(self, dtype):
+        try:
+            return self._MODE_CODES[np.dtype(dtype)]
+        except (KeyError, TypeError):
+            from .categorical import built_words
+            raise TypeError(f"apply_mode is built for {built_words()} class fields, not {dtype}") from None
+
+    def mode_launch_info(self, dtype):
+        """How `apply_mode` runs this operator for fields of `dtype` (smm_mode_launch_info; nothing is launched):
+        capacity -- the most slots of a slice the LDS form of the kernel takes; lds_slots / lds_bytes -- what a launch
+        asks for per wave / per workgroup; lds_slices / global_slices -- the slices that take each form."""
+        cap, slots = ctypes.c_int(0), ctypes.c_int(0)
+        lds, n_lds, n_glob = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.call("smm_mode_launch_info", self.handle, self._mode_code(dtype), ctypes.byref(cap), ctypes.byref(slots),
+                  ctypes.byref(lds), ctypes.byref(n_lds), ctypes.byref(n_glob))
+        return {"capacity": cap.value, "lds_slots": slots.value, "lds_bytes": lds.value, "lds_slices": n_lds.value,
+                "global_slices": n_glob.value}
+
+    def apply_mode(self, x, y=None, masked=False, remap_area_min=0.0, fill=(), fill_out=None, share=False, flags=0,
+                   stream=None):
+        """A field of class codes regridded by largest area fraction (smm_apply_mode): per destination cell and batch
+        row, the value whose links carry the largest summed weight -- `categorical.ModeRule.apply`, bit for bit.  Meant
+        for conservative weights; `method="laf"` weights are the one-cell approximation of it.
+        x: a `DeviceArray` (B, S) -- or (B, ldx >= S) -- of float32 / float64 (missing: whatever is not finite) or
+        int16 / uint16 (missing: the raw values in `fill`, at most two); fill_out: what a dead row of an integer field
+        stores (default: the first of `fill`), a float field's dead rows are NaN.  y: a DeviceArray of x's dtype,
+        (B, ldy >= D), or None.  share: True -- the winner's summed weight comes back too, float64 (B, D); a float64
+        DeviceArray (B, ld_share >= D) is filled instead of a fresh one.  Returns y, or (y, share)."""
+        if not isinstance(x, DeviceArray):
+            raise TypeError("SparseOperator.apply_mode takes a DeviceArray (apply_mode_host for host data)")
+        if x.layout == "sb":
+            raise ValueError("apply_mode takes the native (B, S) layout: no batch-fastest field")
+        from .categorical import ModeRule
+        code = self._mode_code(x.dtype)
+        fills, fill_out = ModeRule(fill, fill_out).checked(x.dtype)
+        if x.ndim != 2 or x.shape[1] < self.n_src:
+            raise ValueError(f"X must be (B, >= {self.n_src}), got {x.shape}")
+        n_batch = x.shape[0]
+        if y is None:
+            y = DeviceArray((n_batch, self.n_dst), x.dtype)
+        elif not isinstance(y, DeviceArray) or y.ndim != 2 or y.shape[0] != n_batch or y.shape[1] < self.n_dst \
+                or y.dtype != x.dtype:
+            raise ValueError(f"Y must be a {x.dtype} DeviceArray ({n_batch}, >= {self.n_dst})")
+        sh = None
+        if isinstance(share, DeviceArray):
+            sh = share
+            if sh.ndim != 2 or sh.shape[0] != n_batch or sh.shape[1] < self.n_dst or sh.dtype != np.float64:
+                raise ValueError(f"share must be a float64 DeviceArray ({n_batch}, >= {self.n_dst})")
+        elif share:
+            sh = DeviceArray((n_batch, self.n_dst), np.float64)
+        rule = None
+        if x.dtype.kind != "f":
+            rule = _lib.ModeRuleStruct(len(fills), (ctypes.c_int32 * 2)(*(list(fills) + [0, 0])[:2]), int(fill_out), 0)
+        _lib.call("smm_apply_mode", self.handle, _ptr(x), code, x.shape[1], _ptr(y), y.shape[1],
+                  None if sh is None else _ptr(sh), 0 if sh is None else sh.shape[1], n_batch, float(remap_area_min),
+                  _flags(flags, masked), None if rule is None else ctypes.byref(rule), _stream_handle(stream))
+        return y if sh is None else (y, sh)
+
+    def apply_mode_host(self, x, out=None, masked=False, remap_area_min=0.0, fill=(), fill_out=None, share=False,
+                        flags=0, chunk_rows=0):
+        """`apply_mode` for a host (numpy) array of shape (B, S).  This is the first form of that road: a synchronous
+        loop over chunks of rows -- H2D copy of the chunk, smm_apply_mode, D2H copy -- which overlaps nothing.  A
+        chunk's X, Y and share stay within 256 MiB and a quarter of the free device memory; chunk_rows > 0 fixes the
+        rows per chunk.  int8 / uint8 fields -- the usual type of land-cover classes -- are widened exactly to int16 on
+        the host and the result is narrowed back; fill and fill_out must then be values of the original type.  Any other
+        dtype (int32, int64, ...) is a TypeError.  Returns a (B, D) array of x's dtype, or (y, share)."""
+        from .categorical import BUILT_DTYPES, WIDENED_DTYPES, ModeRule, built_words
+        x = np.asarray(x)
+        own = x.dtype
+        if own not in BUILT_DTYPES and own not in WIDENED_DTYPES:
+            raise TypeError(f"apply_mode_host is built for {built_words()} class fields, not {own}")
+        fills, fill_out = ModeRule(fill, fill_out).checked(own)      # of the ORIGINAL type: the result is narrowed back
+        if x.ndim != 2 or x.shape[1] != self.n_src:
+            raise ValueError(f"X must be (B, {self.n_src}), got {x.shape}")
+        work = np.dtype(np.int16) if own in WIDENED_DTYPES else own
+        n_batch = x.shape[0]
+        if out is None:
+            out = np.empty((n_batch, self.n_dst), dtype=own)
+        if out.shape != (n_batch, self.n_dst) or not out.flags.c_contiguous or out.dtype != own:
+            raise ValueError(f"out must be a C-contiguous {own} ({n_batch}, {self.n_dst}) array")
+        share_out = np.empty((n_batch, self.n_dst), dtype=np.float64) if share else None
+        if n_batch == 0:
+            return (out, share_out) if share else out
+        if chunk_rows <= 0:
+            from .device import mem_info
+            per_row = self.n_src * work.itemsize + self.n_dst * (work.itemsize + (8 if share else 0))
+            budget = min(256 << 20, mem_info()[0] // 4)
+            chunk_rows = max(1, budget // max(per_row, 1))
+        chunk_rows = min(int(chunk_rows), n_batch)
+        dx = DeviceArray((chunk_rows, self.n_src), work)
+        dy = DeviceArray((chunk_rows, self.n_dst), work)
+        ds = DeviceArray((chunk_rows, self.n_dst), np.float64) if share else None
+        for r0 in range(0, n_batch, chunk_rows):
+            r1 = min(n_batch, r0 + chunk_rows)
+            xc, yc = dx.rows(0, r1 - r0), dy.rows(0, r1 - r0)
+            xc.copy_from_host(x[r0:r1].astype(work, copy=False))
+            self.apply_mode(xc, yc, masked=masked, remap_area_min=remap_area_min, fill=fills, fill_out=fill_out,
+                            share=ds.rows(0, r1 - r0) if share else False, flags=flags)
+            if work == own:
+                yc.to_host(out=out[r0:r1])      # a blocking copy on the default stream: the chunk is done
+            else:
+                out[r0:r1] = yc.to_host().astype(own)      # every value is a source value or fill_out: it fits
+            if share:
+                ds.rows(0, r1 - r0).to_host(out=share_out[r0:r1])
+        return (out, share_out) if share else out
+
     def plan_info(self):
         kind = ctypes.c_int(0)
         lds = ctypes.c_int64(0)

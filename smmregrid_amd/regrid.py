@@ -59,7 +59,7 @@ class Regridder(object):
                  check_nan=False, cdo='cdo', loglevel='WARNING', device=None, out_dtype=None,
                  lazy=False, prune_zero_weights=False, keep_batch_fastest=False, skipna=False, packed=False,
                  packed_levels=False, packed_out=False, packed_out_levels=False, half=False, packed_skipna=False, grib_out=False,
-                 grib_out_levels=False, grib_out_ccsds=False, grib_out_cpx=False, gradients=False):
+                 grib_out_levels=False, grib_out_ccsds=False, grib_out_cpx=False, gradients=False, categorical=False):
         if (source_grid is None or target_grid is None) and (weights is None):
             raise ValueError("Either weights or source_grid/target_grid must be supplied")
 
@@ -75,12 +75,18 @@ class Regridder(object):
         # opt-in: links of weight exactly 0 (3 of 4 bilinear links between aligned grids) are dropped when
         # the operators are built; results are bit-identical (SMM_CREATE_PRUNE_ZEROS)
         self.prune_zero_weights = bool(prune_zero_weights)
+        # categorical: True -- every variable is a class variable; a name or a collection of names -- those are
+        if isinstance(categorical, (bool, type(None))):
+            self.categorical_names = None
+        else:
+            self.categorical_names = frozenset([categorical] if isinstance(categorical, str) else categorical)
         # the switches (`road.Switches` says what each one does) live as attributes, read again at every call
         switches = road.Switches.of(
             out_dtype=out_dtype, transpose=transpose, lazy=lazy, skipna=skipna, keep_batch_fastest=keep_batch_fastest,
             packed=packed, packed_levels=packed_levels, packed_skipna=packed_skipna, packed_out=packed_out,
             packed_out_levels=packed_out_levels, half=half, grib_out=grib_out, grib_out_levels=grib_out_levels,
-            grib_out_ccsds=grib_out_ccsds, grib_out_cpx=grib_out_cpx, gradients=gradients)
+            grib_out_ccsds=grib_out_ccsds, grib_out_cpx=grib_out_cpx, gradients=gradients,
+            categorical=bool(categorical) if self.categorical_names is None else bool(self.categorical_names))
         for name, value in switches._asdict().items():
             setattr(self, name, value)
         refused = road.refusal(switches)
@@ -135,6 +141,10 @@ class Regridder(object):
                                         loglevel=loglevel)
                 gridtype.weights = generator.weights(method=method, mask_dim=gridtype.mask_dim)
 
+        if self.categorical:      # refused before any device work
+            for gridtype in self.grids:
+                if gridtype.mask_dim:
+                    raise ValueError("categorical does not go with masked-level (3-D) weights: it goes with 2-D weights")
         if self.gradients:      # refused before any device work: masked levels, a source that is no regular lon/lat grid
             from .gradients import GradientRule
             for gridtype in self.grids:
@@ -276,6 +286,8 @@ class Regridder(object):
             # without horizontal or mask dimension is cleaned away, :133-143 -- time_bnds(time, bnds) is one): nothing
             # to regrid, and the empty result is dropped from a Dataset (regrid.py:308-312, :262-264)
             return DataArray(data=None)
+        if self.categorical and (self.categorical_names is None or name in self.categorical_names):
+            return self._regrid_categorical(source_data, datagridtype)
         # the facts: the rules its attributes give (one WARNING each when they give none), its grid's gradient rule
         cf = self._packed_rule(source_data) if self.packed else None
         enc = self._packed_out_rule(source_data) if (self.packed_out and cf is not None) else None
@@ -308,6 +320,45 @@ class Regridder(object):
             for k in road.CF_PACKING_ATTRS:
                 out.attrs.pop(k, None)
         return out
+
+    def _regrid_categorical(self, source_data, datagridtype):
+        """A class variable (categorical): regridded by largest area fraction through `apply_mode` / `apply_mode_host`,
+        in its own dtype and with its own attributes.  An integer variable's missing values are its `_FillValue` /
+        `missing_value`, and dead target cells get the first of them; without either, one WARNING and the dtype's
+        minimum (signed) or maximum (unsigned).  A float variable's missing value is whatever is not finite."""
+        from .categorical import ModeRule
+        way = road.decide(self.switches, self._facts(source_data, datagridtype.horizontal_dims, datagridtype.mask_dim,
+                                                     categorical=True))
+        self._emit(way.lines)
+        if way.refusal is not None:
+            raise ValueError(way.refusal[1])
+        gridtype = self._get_gridtype(datagridtype)
+        if gridtype is None:
+            return DataArray(data=None)
+        horizontal_dims, weights, op = gridtype.horizontal_dims, gridtype.weights, gridtype.weights_matrix
+        if not any(x in source_data.dims for x in (horizontal_dims or [])):
+            self.loggy.error("None of dimensions on which we can interpolate is found in the DataArray.")
+            raise KeyError('Dimensions mismatch')
+        kept_dims = [d for d in source_data.dims if d not in horizontal_dims]
+        kept_shape = [source_data.sizes[d] for d in kept_dims]
+        tgt_shape, tgt_dims = self._target_layout(weights)
+        n_batch = int(np.prod(kept_shape)) if kept_shape else 1
+        masked = bool(np.asarray(gridtype.masked).any()) if np.ndim(gridtype.masked) else bool(gridtype.masked)
+        src = source_data.data
+        rule, found = ModeRule.from_attrs(source_data.attrs, src.dtype)
+        if not found:
+            self.loggy.warning("categorical variable %s names no _FillValue / missing_value: %d stands for a target cell "
+                               "without a class", source_data.name, rule.fill_out)
+        kw = dict(masked=masked, remap_area_min=self.remap_area_min, fill=rule.fill, fill_out=rule.fill_out)
+        if isinstance(src, DeviceArray):
+            x = src.reshape(n_batch, -1)
+            _check_cells(x.shape[1], op.n_src)
+            out_data = op.apply_mode(x, **kw).reshape(*(kept_shape + tgt_shape))
+        else:
+            host = np.ascontiguousarray(_computed(src)).reshape(n_batch, -1)
+            _check_cells(host.shape[1], op.n_src)
+            out_data = op.apply_mode_host(host, **kw).reshape(kept_shape + tgt_shape)
+        return self._finish(out_data, kept_dims + tgt_dims, source_data, kept_dims, weights, tgt_shape, tgt_dims)
 
     @property
     def switches(self):

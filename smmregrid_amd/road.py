@@ -20,7 +20,7 @@ def is_half(dtype):
 # ------------------------------------------------------------------------------------------------ the switches
 class Switches(namedtuple("Switches", "lazy skipna keep_batch_fastest transpose out_dtype out_dtype_given packed "
                                       "packed_levels packed_skipna packed_out packed_out_levels half grib_out "
-                                      "grib_out_levels grib_out_ccsds grib_out_cpx gradients")):
+                                      "grib_out_levels grib_out_ccsds grib_out_cpx gradients categorical")):
     """The Regridder's switches as one immutable value.
 
     lazy: nothing is launched before ``.values`` / ``.compute()`` (see `lazy`).
@@ -78,7 +78,12 @@ class Switches(namedtuple("Switches", "lazy skipna keep_batch_fastest transpose 
     gradients: every weight column of bicubic (`bic`, num_wgts = 4) and second-order conservative (`con2`,
       num_wgts = 3) weights is applied, not column 0 alone as the reference does: the gradients of each field are
       computed on the device by the rule of `gradients.GradientRule` and gathered beside the field (smm_apply_cols).
-      Beyond the reference, off by default; 2-D weights on a regular lon/lat source only."""
+      Beyond the reference, off by default; 2-D weights on a regular lon/lat source only.
+    categorical: variables of class codes (every variable, or those the Regridder was given by name) are regridded by
+      largest area fraction -- per target cell the class whose source cells cover the largest summed share of it
+      (`categorical.ModeRule`; smm_apply_mode) -- and come back in their own dtype with their attributes.  Meant for
+      conservative weights (`method="laf"` weights are the one-cell approximation of it).  Beyond the reference, off by
+      default; host fields and native-layout DeviceArrays on 2-D weights."""
     __slots__ = ()
 
     @classmethod
@@ -114,6 +119,12 @@ PREREQUISITES = (
      "gradients=True does not go with {clash}: it goes with float32 / float64 fields in the native layout (host, "
      "device-resident or lazy), float64 results, 2-D weights, remap_area_min, the destination mask, lazy and "
      "prune_zero_weights"),
+    ("categorical", EXCLUDES, ("skipna", "packed", "packed_levels", "packed_skipna", "packed_out", "packed_out_levels", "half",
+                               "keep_batch_fastest", "gradients", "grib_out", "grib_out_levels", "grib_out_ccsds",
+                               "grib_out_cpx", "lazy", "out_dtype_given"),
+     "categorical does not go with {clash}: a class variable comes back in its own dtype, eagerly, by largest area "
+     "fraction; it goes with host arrays and native-layout DeviceArrays, 2-D weights, remap_area_min, the destination "
+     "mask and prune_zero_weights"),
 )
 
 
@@ -122,7 +133,8 @@ def refusal(switches):
     for switch, kind, others, message in PREREQUISITES:
         if not getattr(switches, switch):
             continue
-        clash = [f"out_dtype={switches.out_dtype}" if o == "out_dtype_narrow" else o for o in others if getattr(switches, o)]
+        clash = [f"out_dtype={switches.out_dtype}" if o in ("out_dtype_narrow", "out_dtype_given") else o
+                 for o in others if getattr(switches, o)]
         if (kind == NEEDS and len(clash) < len(others)) or (kind == EXCLUDES and clash):
             return message.format(clash=", ".join(clash))
     return None
@@ -133,7 +145,7 @@ HOST, LAZY, DASK, BS, SB, GRIB = "host", "lazy", "dask", "bs", "sb", "grib"
 
 
 class Facts(namedtuple("Facts", "name held dtype dims horizontal_dims mask_dim cf cf_out codec grad_rule direct out_dtype "
-                                "grib_out", defaults=(False, False, None, False, False, None, False))):
+                                "grib_out categorical", defaults=(False, False, None, False, False, None, False, False))):
     """What is known of a variable without touching its values.
     held: HOST (a numpy array), LAZY (a `LazyArray`), DASK, BS / SB (a `DeviceArray` of that layout) or GRIB (a
     `GribField`); dtype, dims: the variable's; horizontal_dims: those of its dims the weights regrid; mask_dim: the
@@ -142,7 +154,8 @@ class Facts(namedtuple("Facts", "name held dtype dims horizontal_dims mask_dim c
     be built); codec: of a `GribField`, None (simple packing only), "ccsds" or "cpx"; grad_rule: its grid has a
     `GradientRule`.
     direct: `apply_weights` / `regrid3d` were called directly -- the caller chose cf, cf_out, out_dtype (None: by the
-    switches) and, on masked-level weights, grib_out itself; nothing is logged and no packed field is decoded."""
+    switches) and, on masked-level weights, grib_out itself; nothing is logged and no packed field is decoded.
+    categorical: the variable is one of those `Regridder(categorical=...)` regrids by largest area fraction."""
     __slots__ = ()
 
     @property
@@ -168,6 +181,8 @@ PLAIN, RAW_GRIB, RAW_CF, HALF, DECODED, PROMOTED = "plain", "raw GRIB", "raw CF"
 FLOAT, CF_KERNEL, CF_HOST, FLOAT64_DEVICE = "float", "CF in the kernel", "CF on the host", "float64 on the device"
 GRIB_SIMPLE, GRIB_CCSDS, GRIB_CPX = "GRIB simple", "GRIB CCSDS", "GRIB complex"
 GRIB_RESULTS = (GRIB_SIMPLE, GRIB_CCSDS, GRIB_CPX)
+# a class variable (categorical): its codes as they are, and the class of largest area fraction in the field's own dtype
+CLASS_CODES, MODE = "class codes", "mode"
 # a refusal is (stage, message), a ValueError: of the VARIABLE, raised before anything is done with it, or of its LAYOUT,
 # raised where the apply has found its dims and operator
 VARIABLE, LAYOUT = "variable", "layout"
@@ -226,8 +241,21 @@ def _layout_refusal(s, f, sb_in):
     return None
 
 
+def _decide_categorical(f):
+    """The road of a class variable: its codes as they are through the mode entries, or the refusal of what they are not
+    built for -- raw GRIB fields, batch-fastest fields, masked-level (3-D) weights."""
+    clash = "a GribField (raw GRIB input)" if f.held == GRIB else "a batch-fastest field (layout='sb')" if f.held == SB else \
+        "masked-level (3-D) weights" if f.levels else None
+    refused = None if clash is None else (VARIABLE, f"categorical does not go with {clash}: {f.name} is regridded by largest "
+                                                    "area fraction as a host array or a native-layout DeviceArray on 2-D weights")
+    return Road(CLASS_CODES, None, MODE, None if f.dtype is None else np.dtype(f.dtype), False, False, False, False, refused,
+                (), ())
+
+
 def decide(s, f):
     """The `Road` of a variable with the facts `f` under the switches `s`."""
+    if f.categorical:
+        return _decide_categorical(f)
     if f.out_dtype is not None:
         out_dtype = np.dtype(f.out_dtype)
     else:      # the Regridder's, or with half=True and no explicit out_dtype a half field's own type

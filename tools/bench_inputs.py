@@ -237,6 +237,21 @@ def half_fields(shape, seed=20261018):
     return {"f32": x32, "f16": x32.astype(np.float16), "bf16": to_bfloat16(x32)}
 
 
+def class_fields(shape, n_classes, seed=20261021):
+    """{"u16": uint16, "f32": float32} fields of `shape` holding class codes 1 .. n_classes in patches (a smooth field cut
+    into n_classes bands along its last axis, so neighbouring cells mostly share a class, as land cover does) with about
+    2 % of the cells missing: 65535 / NaN"""
+    rng = np.random.default_rng(seed)
+    n = shape[-1]
+    t = np.linspace(0.0, 40.0 * np.pi, n)
+    smooth = np.sin(t)[None, :] + 0.6 * np.sin(2.3 * t + rng.uniform(0, 6, size=(int(np.prod(shape[:-1])), 1)))
+    codes = 1 + np.minimum(((smooth + 1.6) / 3.2 * n_classes).astype(np.int64), n_classes - 1)
+    hole = rng.random(codes.shape) < 0.02
+    u16 = np.where(hole, 65535, codes).astype(np.uint16).reshape(shape)
+    f32 = np.where(hole, np.nan, codes).astype(np.float32).reshape(shape)
+    return {"u16": u16, "f32": f32}
+
+
 def seeded_block(n_src, dtype, nan, rows=16, seed=20261016):
     """`rows` rows around 250 +- 30, with ~3 % NaN when asked for"""
     rng = np.random.default_rng(seed)
