@@ -9,6 +9,11 @@
 //
 // case file: int64 n_cases, then per case  int64 {n_values, n_groups, nbits, width_ref, width_bits, length_ref, length_inc,
 // length_last, length_bits, order, n_oct, stream bytes}, the stream, the expected uint32 values.
+//
+// grib_cpx_harness <cases> pinned: rows with the status they must end with (tests/complex_seam_cases.py), malformed ones
+// among them.  The header has one more int64, that status; the values are n_values zeros when it is not ok.  Each row
+// is decoded once at each of the offsets 0..3, from a block of exactly its bytes: status and integers must be the
+// file's.  No truncation, no inversion -- the rows may be long.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -48,12 +53,44 @@ static uint64_t rnd() {   // xorshift64*
   return rng_state * 0x2545F4914F6CDD1Dull;
 }
 
+static int pinned(FILE* f, int64_t n_cases) {
+  long count[3] = {0, 0, 0};
+  for (int64_t c = 0; c < n_cases; ++c) {
+    int64_t h[13];
+    if (fread(h, 8, 13, f) != 13) return fail("short case header", c, 0);
+    const size_t n = (size_t)h[0], len = (size_t)h[11];
+    const int want_status = (int)h[12];
+    std::vector<uint8_t> stream(len + 1);
+    std::vector<uint32_t> want(n + 1), got(n + 1);
+    if (len && fread(stream.data(), 1, len, f) != len) return fail("short stream", c, 0);
+    if (n && fread(want.data(), 4, n, f) != n) return fail("short values", c, 0);
+    if (want_status < 0 || want_status > 2) return fail("no such status", c, want_status);
+    smm_cpx::Row proto{0,           0,           (uint32_t)h[0], (uint32_t)h[1], (int32_t)h[2],  (uint32_t)h[3], (int32_t)h[4],
+                       (uint32_t)h[5], (uint32_t)h[6], (uint32_t)h[7], (int32_t)h[8], (int32_t)h[9], (int32_t)h[10]};
+    for (size_t off = 0; off < 4; ++off) {
+      got.assign(n + 1, 0xDEADBEEFu);
+      const int st = decode_exact(proto, stream.data(), len, off, got);
+      if (st != want_status) return fail("the row ends with another status", c, st);
+      if (n && memcmp(got.data(), want.data(), 4 * n) != 0) return fail("the row's integers differ", c, (long)off);
+    }
+    ++count[want_status];
+  }
+  printf("pinned %ld ok %ld exhausted %ld invalid %ld\n", (long)n_cases, count[0], count[1], count[2]);
+  return 0;
+}
+
 int main(int argc, char** argv) {
-  if (argc != 2) return fail("usage: grib_cpx_harness <cases>", -1, 0);
+  const bool pin = argc == 3 && strcmp(argv[2], "pinned") == 0;
+  if (argc != 2 && !pin) return fail("usage: grib_cpx_harness <cases> [pinned]", -1, 0);
   FILE* f = fopen(argv[1], "rb");
   if (!f) return fail("cannot open the case file", -1, 0);
   int64_t n_cases = 0;
   if (fread(&n_cases, 8, 1, f) != 1) return fail("short case file", -1, 0);
+  if (pin) {
+    const int rc = pinned(f, n_cases);
+    fclose(f);
+    return rc;
+  }
   for (int64_t c = 0; c < n_cases; ++c) {
     int64_t h[12];
     if (fread(h, 8, 12, f) != 12) return fail("short case header", c, 0);

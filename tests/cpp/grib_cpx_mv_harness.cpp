@@ -7,6 +7,10 @@
 //
 // case file: int64 n_cases, then per case  int64 {n_values, n_groups, nbits, width_ref, width_bits, length_ref, length_inc,
 // length_last, length_bits, order, n_oct, stream bytes, m, P}, the stream, P uint32 integers, n_values flags.
+//
+// grib_cpx_mv_harness <cases> pinned: rows with the status they must end with (tests/complex_seam_cases.py), malformed
+// ones among them.  The header has one more int64, that status; a row that is not ok has P = 0 and flags of zero.  Each
+// row is decoded once at each of the offsets 0..3: status, count, integers (zero behind P) and flags must be the file's.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -46,12 +50,49 @@ static Run decode_exact(const smm_cpx::Row& proto, int m, const uint8_t* bytes, 
   return got;
 }
 
+static int pinned(FILE* f, int64_t n_cases) {
+  long count[3] = {0, 0, 0};
+  for (int64_t c = 0; c < n_cases; ++c) {
+    int64_t h[15];
+    if (fread(h, 8, 15, f) != 15) return fail("short case header", c, 0);
+    const size_t n = (size_t)h[0], len = (size_t)h[11], P = (size_t)h[13];
+    const int m = (int)h[12], want_status = (int)h[14];
+    std::vector<uint8_t> stream(len + 1), want_flags(n + 1), flags;
+    std::vector<uint32_t> want(P + 1), got;
+    if (len && fread(stream.data(), 1, len, f) != len) return fail("short stream", c, 0);
+    if (P && fread(want.data(), 4, P, f) != P) return fail("short values", c, 0);
+    if (n && fread(want_flags.data(), 1, n, f) != n) return fail("short flags", c, 0);
+    if (want_status < 0 || want_status > 2 || P > n) return fail("no such status or count", c, want_status);
+    smm_cpx::Row proto{0,           0,           (uint32_t)h[0], (uint32_t)h[1], (int32_t)h[2],  (uint32_t)h[3], (int32_t)h[4],
+                       (uint32_t)h[5], (uint32_t)h[6], (uint32_t)h[7], (int32_t)h[8], (int32_t)h[9], (int32_t)h[10]};
+    for (size_t off = 0; off < 4; ++off) {
+      const Run r = decode_exact(proto, m, stream.data(), len, off, got, flags);
+      if (r.status != want_status) return fail("the row ends with another status", c, r.status);
+      if (r.count != P) return fail("the row's count differs", c, (long)r.count);
+      if (P && memcmp(got.data(), want.data(), 4 * P) != 0) return fail("the row's integers differ", c, (long)off);
+      for (size_t i = P; i < n; ++i)
+        if (got[i]) return fail("an integer behind the count is not zero", c, (long)i);
+      for (size_t i = 0; i < n; ++i)
+        if ((flags[i] != 0) != (want_flags[i] != 0)) return fail("the row's flags differ", c, (long)i);
+    }
+    ++count[want_status];
+  }
+  printf("pinned %ld ok %ld exhausted %ld invalid %ld\n", (long)n_cases, count[0], count[1], count[2]);
+  return 0;
+}
+
 int main(int argc, char** argv) {
-  if (argc != 2) return fail("usage: grib_cpx_mv_harness <cases>", -1, 0);
+  const bool pin = argc == 3 && strcmp(argv[2], "pinned") == 0;
+  if (argc != 2 && !pin) return fail("usage: grib_cpx_mv_harness <cases> [pinned]", -1, 0);
   FILE* f = fopen(argv[1], "rb");
   if (!f) return fail("cannot open the case file", -1, 0);
   int64_t n_cases = 0;
   if (fread(&n_cases, 8, 1, f) != 1) return fail("short case file", -1, 0);
+  if (pin) {
+    const int rc = pinned(f, n_cases);
+    fclose(f);
+    return rc;
+  }
   for (int64_t c = 0; c < n_cases; ++c) {
     int64_t h[14];
     if (fread(h, 8, 14, f) != 14) return fail("short case header", c, 0);

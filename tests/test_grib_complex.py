@@ -382,8 +382,9 @@ def harness(tmp_path_factory):
 
 
 def test_malformed_input_ends_with_a_status_and_no_sanitizer_report(harness, tmp_path):
-    """Malformed tables, offsets and lengths are tested here only: the GPU kernels take the tables apart with the same
-    functions and check the same bounds before any load."""
+    """Truncated, corrupted and random input is tested here only, on the scalar decoder.  The GPU kernels take the tables
+    apart with the same functions, but raise their statuses in kernels of their own: malformed rows with the status each
+    must end with go through both in tests/test_grib_complex_seams.py and tests/test_gpu_grib_complex_seams.py."""
     cs = [c for c in CASES if c.n_values <= 4096]
     path = str(tmp_path / "cases.bin")
     with open(path, "wb") as fh:
